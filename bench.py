@@ -11,7 +11,13 @@ Workload at N=1: BASELINE.json configs[2] -- synthetic 10^8 events, -m GATC, NN 
 skip_thresh 0.  N>1: every rank scans its own 10^8-row shards of reads (weak scaling, no data-path collective).
 `python bench.py --gpus N` without WORLD_SIZE in the environment starts the N ranks itself.
 
-After the timed steps the ranks > 0 are done; rank 0 goes on alone (at every N) with the product-shaped legs, among them
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, warms up, times the K steps and prints the headline line
+(`metric`, `value`, `unit`, `ms_per_step`, `ms_per_step_steady`, `dtype`, the step's `config`) and nothing else.  Every other
+measurement below -- fp64 classifier, resident rescan, per-kernel times and roofline, the per-site reduction, device end to
+end, file to file, strong scaling, config5, the CPU legs, the details file -- runs with `--full` (`--kernels-only` implies it).
+`--dump-outputs DIR` writes what the last timed step handed its caller (rank 0's records) as float64 .npy files under DIR.
+
+With `--full`, after the timed steps the ranks > 0 are done; rank 0 goes on alone (at every N) with the product-shaped legs, among them
   strong_scaling             BASELINE.json configs[3] through the product path: ONE 10^8-row eventalign file ->
                              `python -m mcaller_amd.mCaller --gpus N --bed` (mcaller_amd/multi_gpu.py: N byte ranges cut at read
                              starts, one worker process per GPU streaming its range over its own PCIe link, the per-site
@@ -318,6 +324,30 @@ def write_details(full):
     sys.stderr.flush()
 
 
+DUMP_LIMIT = (64 << 20) - (1 << 16)     # bytes of array data --dump-outputs writes at most (the .npy headers fit in the rest of 64 MB)
+
+
+def dump_outputs(out_dir, rec):
+    """--dump-outputs: the records the last timed step handed its caller (Device.wait()) as float64 .npy files -- per flush record
+    its site position, segment, closing row and info bits; per call its probability and its k slot means (integers are exact in
+    float64).  Above DUMP_LIMIT a fixed, seeded sample of the records and of the calls, in their order, is written instead."""
+    n, m, k = int(rec.n), int(rec.n_calls), int(rec.k)
+    records = {'record_site_pos': rec.site_pos[:n], 'record_site_seg': rec.site_seg[:n], 'record_close_row': rec.close_row[:n],
+               'record_info': rec.info[:n]}
+    calls = {'call_prob': rec.prob[:m], 'call_feats': rec.feats[:m * k].reshape(m, k)}
+    total = 8 * (4 * n + (1 + k) * m)
+    if total > DUMP_LIMIT:
+        frac = DUMP_LIMIT / float(total)
+        rng = np.random.default_rng(0)
+        keep_r = np.sort(rng.choice(n, int(n * frac), replace=False))
+        keep_c = np.sort(rng.choice(m, int(m * frac), replace=False))
+        records = {name: a[keep_r] for name, a in records.items()}
+        calls = {name: a[keep_c] for name, a in calls.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in list(records.items()) + list(calls.items()):
+        np.save(os.path.join(out_dir, name + '.npy'), np.asarray(a, dtype=np.float64))
+
+
 REAL_STDOUT = None
 
 
@@ -509,7 +539,13 @@ def main():
                     help='file to file with -m A (dense mode), at the 10^7-row and at this size: rows of eventalign text (0: skip both)')
     ap.add_argument('--config5-events', type=float, default=1e7,
                     help='BASELINE.json configs[4] (--train on labelled positions + RF): rows of eventalign text (0: skip)')
-    ap.add_argument('--kernels-only', action='store_true', help='skip device end-to-end, file to file and the CPU legs (profiling runs)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, every other measurement too (fp64 classifier, rescan, per-kernel times and roofline, '
+                         'site reduction, device end to end, file to file, strong scaling, config5, CPU legs, details file)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write the records of the last timed step (rank 0) as float64 .npy files under DIR, at most 64 MB')
+    ap.add_argument('--kernels-only', action='store_true',
+                    help='--full without device end-to-end, file to file and the CPU legs (profiling runs)')
     ap.add_argument('--rescan-only', action='store_true',
                     help='profiling runs: the timed steps re-scan ONE validated table (config.resident_rescan) instead of full passes')
     ap.add_argument('--dry-ranks', action='store_true',
@@ -525,6 +561,7 @@ def main():
     if args.kernels_only:
         args.stream_shards, args.f2f_events, args.f2f_big_events, args.strong_events, args.no_cpu_baseline = 0, 0, 0, 0, True
         args.dense_events = args.config5_events = 0
+        args.full = True                                      # (the profiling scripts trace the per-kernel passes after the steps)
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
 
@@ -695,6 +732,31 @@ def main():
         c = torch.tensor([n_calls, calls_in_region], dtype=torch.float64)
         dist.all_reduce(c, op=dist.ReduceOp.SUM)
         elapsed_max, calls_total, calls_region_total = float(t[0]), int(c[0]), int(c[1])
+    calls_per_step = calls_region_total / float(args.steps * world)          # (per rank and step: the two tables differ by a few)
+    alg_bytes = 17.0 * n_rows + 64.0 * calls_per_step
+    workload = ('synthetic %.0e eventalign rows per GPU and step, -m %s, NN classifier (r95 two-base MLP), skip_thresh 0; %s'
+                % (n_rows, args.motif, 'two resident tables taken in turn, every step a FULL pass (the table declared new: positions + '
+                                       'event indices streamed, every row validated)' if full else
+                                       'ONE validated resident table re-scanned (--rescan-only)'))
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rec)
+    if not args.full:                       # a plain run: the headline line and nothing else
+        if rank == 0:
+            print_line(_r({'metric': METRIC, 'value': calls_region_total / elapsed_max, 'unit': 'calls/s', 'n_gpus': world,
+                           'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': elapsed_max / args.steps * 1e3,
+                           'ms_per_step_steady': steady_ms, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+                           'dtype': DTYPE, 'data': 'synthetic',
+                           'config': {'workload': workload, 'step': 'full pass' if full else 'resident rescan',
+                                      'passes_in_flight': depth_now, 'events_per_gpu': n_rows, 'calls_per_gpu': calls_per_step,
+                                      'flush_records_per_gpu': n_records, 'copy_out_bytes_per_pass': copy_out_bytes,
+                                      'events_per_s': n_rows * world * args.steps / elapsed_max,
+                                      'algorithmic_GBps_of_the_step': alg_bytes * world / (elapsed_max / args.steps) / 1e9}}))
+        if dist is not None:
+            barrier()
+            dist.destroy_process_group()
+        dev.close()
+        return
 
     # ---- the same steps with the classifier in fp64 throughout (MCALLER_MLP_FP64=1: how rounds 1-4 scored every record);
     #      the timed region above runs the default, the fast forward (hidden layer f32, output and near-boundary records f64) ----
@@ -1136,8 +1198,6 @@ def main():
         if kernel_ms.get('emit') == 0.0:      # pipelined passes time scan + ordering + emit as one span (no event in between)
             kernel_ms['window_scan_and_emit'] = kernel_ms.pop('window_scan')
             del kernel_ms['emit']
-        calls_per_step = calls_region_total / float(args.steps * world)          # (per rank and step: the two tables differ by a few)
-        alg_bytes = 17.0 * n_rows + 64.0 * calls_per_step
         # every kernel that touches a table once, one full pass at a time (hipEvents on the ctx stream)
         scan_ms = sync_ms['window_scan']
         per_table = {'strand_resolve': sync_ms['strand_resolve'], 'window_scan': scan_ms, 'order_and_emit': sync_ms['emit']}
@@ -1181,11 +1241,7 @@ def main():
             'dtype': DTYPE,
             'ms_per_step_fp64_mlp': fp64_ms,
             'data': 'synthetic',
-            'config': {'workload': 'synthetic %.0e eventalign rows per GPU and step, -m %s, NN classifier (r95 two-base MLP), '
-                                   'skip_thresh 0; %s' % (n_rows, args.motif,
-                                                          'two resident tables taken in turn, every step a FULL pass (the table '
-                                                          'declared new: positions + event indices streamed, every row validated)'
-                                                          if full else 'ONE validated resident table re-scanned (--rescan-only)'),
+            'config': {'workload': workload,
                        'step': 'full pass' if full else 'resident rescan',
                        'passes_in_flight': 1 if args.no_pipeline else max(1, min(args.depth, 5, args.steps)),
                        'events_per_gpu': n_rows, 'calls_per_gpu': calls_per_step, 'flush_records_per_gpu': n_records,

@@ -18,6 +18,7 @@ Outputs (all DATA: inputs + expected outputs + exported weight arrays, no refere
   tests/golden/ref_outputs/       outputs of the reference run here (diffs.6 for -p, -m GATC, -m A,
                                   --train; make_bed BEDs; stdout counter lines)
   mcaller_amd/models/*.npz        W1,b1,W2,b2 of every shipped estimator (meta: tests/golden/models/models_meta.json)
+  tests/golden/models/*_m6A.pkl   the four model files the reference ships, byte for byte (the unpickler's fixtures)
   tests/golden/micro_cases.json.gz  micro-cases with the reference's output for each
   tests/golden/PIN_REPORT.json    how many cases were compared, how many differed (must be 0)
 """
@@ -159,6 +160,8 @@ def export_models():
     for fn in ['r95_twobase_model_NN_6_m6A.pkl', 'r94_model_NN_6_m6A.pkl',
                'CAAYNNNNNRTAC_model_6_m6A.pkl', 'CRAANNNNNNNTGC_model_6_m6A.pkl']:
         raw = open(os.path.join(REF, fn), 'rb').read()
+        with open(os.path.join(outdir, fn), 'wb') as fh:        # the model file itself, byte for byte (tests/test_cli_host.py)
+            fh.write(raw)
         obj = pickle.loads(raw, encoding='latin')
         is_dict = isinstance(obj, dict)
         ests = obj if is_dict else {'general': obj}
@@ -434,9 +437,14 @@ def main():
     bed = os.path.join(td, 'masonread1.methylation.summary.bed')
 
     def bed_runs(tag):
-        for extra, name in [([], 'bed'), (['--vo'], 'vo.bed')]:
-            out, _ = run_cli('make_bed.py', ['-f', diffs, '-d', '1', '-t', '0.5'] + extra)
-            shutil.copy(bed, os.path.join(ref_out, '%s.%s' % (tag, name)))
+        cwd = os.getcwd()
+        os.chdir(td)                     # (make_bed names its output from the -f path up to its first dot: a relative name keeps it in td)
+        try:
+            for extra, name in [([], 'bed'), (['--vo'], 'vo.bed')]:
+                out, _ = run_cli('make_bed.py', ['-f', os.path.basename(diffs), '-d', '1', '-t', '0.5'] + extra)
+                shutil.copy(bed, os.path.join(ref_out, '%s.%s' % (tag, name)))
+        finally:
+            os.chdir(cwd)
 
     cli_cases = [
         ('config1_positions_m6A', ['-p', os.path.join(td, 'test_positions_m6A.txt'), '-d', model]),

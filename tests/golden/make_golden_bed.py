@@ -78,7 +78,7 @@ def main():
     manifest = {}
     try:
         for tag, extra in cases.items():
-            stdout, code = mg.run_cli('make_bed.py', ['-f', diffs] + extra)
+            stdout, code = mg.run_cli('make_bed.py', ['-f', os.path.basename(diffs)] + extra)     # (relative: the output is named from it)
             stem = 'multi.methylation' + ('.positions' if '-p' in extra else ('.control' if '--control' in extra else '')) + '.summary'
             produced = os.path.join(work, stem + ('.gff' if '--gff' in extra else '.bed'))
             name = tag + ('.gff' if '--gff' in extra else '.bed')

@@ -8,8 +8,6 @@ import pytest
 
 from tests import helpers as H
 
-REF = '/root/reference'
-
 
 def test_merge_orders_like_sort_n_k2(tmp_path):
     """Read names are UUIDs: many start with digits, and `sort -n -k2` orders those by their numeric prefix before it falls
@@ -36,15 +34,14 @@ def test_merge_orders_like_sort_n_k2(tmp_path):
     assert numeric_key_k2(b'c\t2289b392-x\t1\n') == 2289 and numeric_key_k2(b'c\tcc1d\t1\n') == 0
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='the reference checkout is only present in the build container')
 @pytest.mark.parametrize('tag', sorted(H.MODEL_STEMS))
 def test_the_shipped_pickles_load_without_scikit_learn(tag):
     """extract_contexts.py:123-130: the model file is a pickle of an estimator or of a dict of estimators.  The four files
-    the reference ships go through model_io's restricted unpickler (no scikit-learn import) and give the arrays of the
-    committed .npz exports."""
+    the reference ships (kept byte for byte under tests/golden/models/) go through model_io's restricted unpickler (no
+    scikit-learn import) and give the arrays of the committed .npz exports."""
     from mcaller_amd.model_io import load_model_file
     stem = H.MODEL_STEMS[tag]
-    got = load_model_file(os.path.join(REF, stem + '.pkl'))
+    got = load_model_file(os.path.join(H.GOLDEN, 'models', stem + '.pkl'))
     want = H.load_modelset(tag)
     assert got.keys() == want.keys() and got.twobase == want.twobase == H.model_meta()[stem]['is_dict']
     for key in want.keys():

@@ -82,7 +82,7 @@ def test_site_reduction_gloo_world2(tmp_path):
     assert a == b and a.count('\n') > 50
 
 
-def test_bed_from_reduced_counts_equals_make_bed_on_the_diffs_text(tmp_path):
+def test_bed_from_reduced_counts_equals_make_bed_on_the_diffs_text(tmp_path, monkeypatch):
     """The per-site reduction (site_counts -> write_bed_from_counts, what the all-reduce feeds) writes the same BED as the
     reference-compatible text path (records -> .diffs rows -> make_bed), for depth and fraction thresholds."""
     import contextlib
@@ -107,9 +107,10 @@ def test_bed_from_reduced_counts_equals_make_bed_on_the_diffs_text(tmp_path):
     diffs.write_bytes(fin.text())
     index = make_bed.SiteIndex(ref.meth, 1)
     counts = make_bed.site_counts(rec, table, index)
+    monkeypatch.chdir(tmp_path)         # (make_bed names its output from the -f path up to its first dot: a relative name keeps it here)
     for depth, thresh in ((1, 0.5), (5, 0.5), (3, 0.2), (8, 0.8)):
         with contextlib.redirect_stdout(io.StringIO()):
-            make_bed.main(['-f', str(diffs), '-d', str(depth), '-t', str(thresh)])
+            make_bed.main(['-f', diffs.name, '-d', str(depth), '-t', str(thresh)])
         want = (tmp_path / 'syn.methylation.summary.bed').read_text()
         out = tmp_path / 'reduced.bed'
         make_bed.write_bed_from_counts(str(out), counts[0], counts[1], counts[2], index, ref.names, ref.meth, 6, depth, thresh)

@@ -15,11 +15,11 @@ timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $ou
 timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $out/write -- python3 bench.py --steps 4 --warmup 0 --kernels-only > /dev/null 2>> $out/bench.err
 python3 tools/pmc_summary.py $out/fetch $out/write $out/pmc.json "python3 bench.py --steps 4 --warmup 0 --kernels-only" $head
 cp $out/pmc.json profiles/r06_pmc.json
-MCALLER_BENCH_DETAILS=$out/bench_details.json timeout 1200 python3 bench.py > $out/bench.json 2>> $out/bench.err
+MCALLER_BENCH_DETAILS=$out/bench_details.json timeout 1200 python3 bench.py --full > $out/bench.json 2>> $out/bench.err
 # the driver's own command line (20 steps: the pipeline's fill and drain inside the timed region; ms_per_step_steady beside it)
-MCALLER_BENCH_DETAILS=$out/bench_driver_cmdline_details.json timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_driver_cmdline.json 2>> $out/bench.err
+MCALLER_BENCH_DETAILS=$out/bench_driver_cmdline_details.json timeout 900 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench_driver_cmdline.json 2>> $out/bench.err
 # two ranks on the one GPU of this box (plumbing of the N > 1 line: both legs, the reduction's host-sum branch), at 2*10^7 rows
-MCALLER_BENCH_DETAILS=$out/bench_2ranks_details.json MCALLER_BENCH_ONE_DEVICE=1 timeout 900 python3 bench.py --gpus 2 --steps 20 --warmup 5 --events 2e7 --strong-events 2e7 --f2f-big-events 2e7 --f2f-events 1e6 > $out/bench_2ranks_on_one_gpu_plumbing.json 2>> $out/bench.err
+MCALLER_BENCH_DETAILS=$out/bench_2ranks_details.json MCALLER_BENCH_ONE_DEVICE=1 timeout 900 python3 bench.py --full --gpus 2 --steps 20 --warmup 5 --events 2e7 --strong-events 2e7 --f2f-big-events 2e7 --f2f-events 1e6 > $out/bench_2ranks_on_one_gpu_plumbing.json 2>> $out/bench.err
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --kernels-only > $out/stats_bench.json 2>> $out/bench.err
 cp $out/stats/*/*kernel_stats.csv $out/kernel_stats.csv
 rm -rf $out/fetch $out/write $out/stats
