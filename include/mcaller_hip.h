@@ -252,6 +252,18 @@ int mc_ctx_set_forest(mc_ctx *ctx, int32_t n_models, int32_t n_in, const int32_t
 int mc_ctx_set_simple_classifier(mc_ctx *ctx, int32_t kind, int32_t n_models, int32_t n_in, const double *params, int32_t stride,
                                  const uint8_t *submodel_of_char);
 
+/* RBF support-vector classifier of `-c SVM` (train_model.py:51-53: SVC(kernel='rbf', probability=True), two classes, dense; same call
+ * site :199), scored as scikit-learn's libsvm does.  Sub-models have different numbers of support vectors: model_sv_off[n_models+1]
+ * gives each sub-model's first one (model_sv_off[0] = 0); sv[n_sv_total*n_in]: the support vectors, row by row;
+ * dual_coef[n_sv_total]: their coefficients as scikit-learn hands them to libsvm (`_dual_coef_[0]`); params[n_models*4]: per
+ * sub-model gamma (resolved, `_gamma`), intercept (`_intercept_[0]`), A, B (`_probA[0]`, `_probB[0]`).
+ *   dec = sum_i dual_coef_i exp(-gamma sum_j (x_j - sv_ij)^2) + intercept   (support-vector order)
+ *   s   = Platt sigmoid of dec * A + B, clamped to [1e-7, 1 - 1e-7]
+ *   p   = libsvm's iterative pairwise coupling for two classes (r01 = s), the probability of classes_[1]
+ * fp64.  At most 8 sub-models.  Replaces the MLP / forest / closed-form classifier of the context. */
+int mc_ctx_set_svm(mc_ctx *ctx, int32_t n_models, int32_t n_in, const int32_t *model_sv_off, const double *sv,
+                   const double *dual_coef, const double *params, const uint8_t *submodel_of_char);
+
 typedef struct mc_params {
     int32_t k;             /* -n   (:110 `k`)            */
     int32_t skip_thresh;   /* -s   (:183,242)            */
@@ -322,6 +334,7 @@ int mc_ctx_sync(mc_ctx *ctx);
 int mc_mlp_forward(mc_ctx *ctx, const double *X, const uint8_t *submodel, int64_t n, double *p);
 int mc_forest_forward(mc_ctx *ctx, const double *X, const uint8_t *submodel, int64_t n, double *p);
 int mc_simple_forward(mc_ctx *ctx, const double *X, const uint8_t *submodel, int64_t n, double *p);     /* LR / NBC */
+int mc_svm_forward(mc_ctx *ctx, const double *X, const uint8_t *submodel, int64_t n, double *p);        /* SVM */
 
 /* ===== per-site reduction feeding make_bed (make_bed.py:86-96,:134,:143,:154), the one exchange step of a multi-GPU job =====
  * Sites = every 'M' of the marked strands, numbered per contig: '+' sites by position, then '-' sites by position

@@ -911,6 +911,151 @@ __global__ __launch_bounds__(64) void k3_simple(DevSimple S, const double *__res
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// K3'': RBF support-vector classifier, predict_proba of scikit-learn's SVC(kernel='rbf', probability=True) -- `-c SVM`,
+// train_model.py:51-53; call site :199 -- as its libsvm computes it (svm_predict_probability, two classes):
+//   dec = sum_i coef_i exp(-gamma sum_j (x_j - sv_ij)^2) + intercept     (support-vector order, the difference form)
+//   s   = sigmoid_predict(dec, A, B) clamped to [1e-7, 1 - 1e-7]          (P(classes_[0]))
+//   p   = multiclass_probability(k = 2, r01 = s, r10 = 1 - s)[1]          (the iterative coupling, even for two classes)
+// One lane per record, x in registers, fp64 throughout with the device library's exp.  The support vectors of a sub-model are
+// staged through LDS K3S_TILE at a time, every lane of a wave reading the same one (a broadcast).  A workgroup takes K3S_THREADS
+// records, buckets them by sub-model in LDS and walks each bucket's set with the bucket's records on the first lanes: a wave walks
+// one set at a time and waves with no record of the set skip the walk (they only join the tile barriers).  The order of the
+// records in a bucket does not matter -- each record's probability is its own.
+// Records on the KeyError path (sub-model >= n_models) and flush records with MC_I_TOO_MANY | MC_I_EDGE are left as they are.
+// ---------------------------------------------------------------------------------------------------
+constexpr int K3S_THREADS = 256, K3S_TILE = 256;
+
+__device__ __forceinline__ double svm_platt_couple(double dec, double A, double B) {
+    // sigmoid_predict: the branch that avoids cancellation in 1 - p
+    const double f = dec * A + B;
+    double s = f >= 0.0 ? exp(-f) / (1.0 + exp(-f)) : 1.0 / (1.0 + exp(f));
+    s = fmin(fmax(s, 1e-7), 1.0 - 1e-7);
+    // multiclass_probability, k = 2: Q = [[r10^2, -r10 r01], [-r10 r01, r01^2]], p = [1/2, 1/2], eps = 0.005 / 2, at most 100 rounds;
+    // each round tests the error first (s within (0.495, 0.505): no update at all, p = 1/2 exactly)
+    const double r01 = s, r10 = 1.0 - s;
+    const double q00 = r10 * r10, q01 = -r10 * r01, q11 = r01 * r01;
+    double p0 = 0.5, p1 = 0.5;
+    for (int it = 0; it < 100; ++it) {
+        double qp0 = q00 * p0 + q01 * p1, qp1 = q01 * p0 + q11 * p1;
+        double pqp = p0 * qp0 + p1 * qp1;
+        if (fmax(fabs(qp0 - pqp), fabs(qp1 - pqp)) < 0.005 / 2) break;
+        double diff = (-qp0 + pqp) / q00;                           // t = 0
+        p0 += diff;
+        pqp = (pqp + diff * (diff * q00 + 2 * qp0)) / (1 + diff) / (1 + diff);
+        qp0 = (qp0 + diff * q00) / (1 + diff);
+        p0 /= (1 + diff);
+        qp1 = (qp1 + diff * q01) / (1 + diff);
+        p1 /= (1 + diff);
+        diff = (-qp1 + pqp) / q11;                                  // t = 1
+        p1 += diff;
+        pqp = (pqp + diff * (diff * q11 + 2 * qp1)) / (1 + diff) / (1 + diff);
+        qp0 = (qp0 + diff * q01) / (1 + diff);
+        p0 /= (1 + diff);
+        qp1 = (qp1 + diff * q11) / (1 + diff);
+        p1 /= (1 + diff);
+    }
+    return p1;
+}
+
+// NI: inputs, known at compile time (7: the reference's k = 6 models); 0: any number up to MC_MAX_K + 1, the rows padded with zeros
+// in LDS (a zero coordinate against a zero input adds an exact 0 to the distance)
+template <int NI>
+__global__ __launch_bounds__(K3S_THREADS) void k3_svm(DevSvm V, const double *__restrict__ feats, int k,
+                                                      const int32_t *__restrict__ site_seg, const int32_t *__restrict__ seg_read,
+                                                      const double *__restrict__ qual, const uint32_t *__restrict__ info,
+                                                      const uint8_t *__restrict__ submodel_in, int64_t n,
+                                                      double *__restrict__ prob, const unsigned long long *__restrict__ n_dev,
+                                                      const unsigned int *__restrict__ overflow) {
+    constexpr int MAXI = NI > 0 ? NI : MC_MAX_K + 1;
+    constexpr int ROW = MAXI + 1;                   // doubles per staged support vector: coordinates, dual coefficient
+    __shared__ double s_sv[K3S_TILE * ROW];
+    __shared__ int32_t s_idx[K3S_THREADS];
+    __shared__ int32_t s_cnt[K3S_MAXM], s_start[K3S_MAXM];
+    if (overflow && *overflow) return;
+    if (n_dev) n = min(n, (int64_t)*n_dev);
+    const int ni = NI > 0 ? NI : V.n_in;
+    const int tid = threadIdx.x, wave = tid >> 6;
+    for (int64_t base = (int64_t)blockIdx.x * K3S_THREADS; base < n; base += (int64_t)gridDim.x * K3S_THREADS) {
+        // ---- bucket the workgroup's records by sub-model ----
+        if (tid < K3S_MAXM) s_cnt[tid] = 0;
+        __syncthreads();
+        const int64_t r = base + tid;
+        int mi = -1;
+        if (r < n) {
+            if (submodel_in) mi = submodel_in[r];
+            else {
+                const uint32_t inf = info[r];
+                if (!(inf & (MC_I_TOO_MANY | MC_I_EDGE))) mi = V.sub_of_char[(inf >> MC_I_NEXT_SHIFT) & 0xFFu];
+            }
+            if (mi >= V.n_models) mi = -1;
+        }
+        const int pos = mi >= 0 ? atomicAdd(&s_cnt[mi], 1) : 0;
+        __syncthreads();
+        if (tid == 0)
+            for (int m = 0, a = 0; m < V.n_models; ++m) { s_start[m] = a; a += s_cnt[m]; }
+        __syncthreads();
+        if (mi >= 0) s_idx[s_start[mi] + pos] = tid;
+        __syncthreads();
+        // ---- each bucket: its records on lanes 0 .. cnt-1, the sub-model's support vectors tile by tile ----
+        for (int m = 0; m < V.n_models; ++m) {
+            const int cnt = s_cnt[m];
+            if (cnt == 0) continue;
+            const bool mine = tid < cnt;
+            const bool walk = wave * 64 < cnt;              // (the same for the whole wave)
+            int64_t rr = 0;
+            double x[MAXI];
+#pragma unroll
+            for (int j = 0; j < MAXI; ++j) x[j] = 0.0;
+            if (mine) {
+                rr = base + s_idx[s_start[m] + tid];
+                if (submodel_in) {
+#pragma unroll
+                    for (int j = 0; j < MAXI; ++j) if (j < ni) x[j] = feats[rr * ni + j];
+                } else {
+#pragma unroll
+                    for (int j = 0; j < MAXI; ++j) if (j < k) x[j] = feats[rr * k + j];
+                    const double q = qual[seg_read[site_seg[rr]]];
+#pragma unroll
+                    for (int j = 0; j < MAXI; ++j) if (j == k) x[j] = q;
+                }
+            }
+            const double gamma = V.params[4 * m];
+            const int v0 = V.model_sv_off[m], v1 = V.model_sv_off[m + 1];
+            double dec = 0.0;
+            for (int t0 = v0; t0 < v1; t0 += K3S_TILE) {
+                const int nt = min(K3S_TILE, v1 - t0);
+                __syncthreads();                            // (the previous tile has been read)
+                if (NI > 0) {                               // rows as they are in memory
+                    const double *src = V.sv + (size_t)t0 * ROW;
+                    for (int e = tid; e < nt * ROW; e += K3S_THREADS) s_sv[e] = src[e];
+                } else {
+                    for (int e = tid; e < nt * ROW; e += K3S_THREADS) {
+                        const int v = e / ROW, j = e - v * ROW;
+                        const double *src = V.sv + (size_t)(t0 + v) * (ni + 1);
+                        s_sv[e] = j < ni ? src[j] : (j == MAXI ? src[ni] : 0.0);
+                    }
+                }
+                __syncthreads();
+                if (walk)
+#pragma unroll 2
+                    for (int v = 0; v < nt; ++v) {       // (two evaluations side by side: independent chains up to the sum)
+                        const double *q = &s_sv[v * ROW];
+                        double d2 = 0.0;
+#pragma unroll
+                        for (int j = 0; j < MAXI; ++j) {
+                            const double t = x[j] - q[j];
+                            d2 += t * t;
+                        }
+                        dec += q[MAXI] * exp(-gamma * d2);
+                    }
+            }
+            if (mine) prob[rr] = svm_platt_couple(dec + V.params[4 * m + 1], V.params[4 * m + 2], V.params[4 * m + 3]);
+        }
+        __syncthreads();                                    // (s_cnt, s_idx: the next round's)
+    }
+}
+
 
 // ---------------------------------------------------------------------------------------------------
 // Pipelined passes: every pass in flight has its own counters, strand-resolve output and record set; the host reads
@@ -1126,14 +1271,23 @@ __global__ __launch_bounds__(PACK_THREADS) void k_pack(DevRecords O, const Count
 #endif
 
 // the classifier of a context -- MLP (k2_mlp: the 7-input instance for k = 6, the reference's models, or the general one), forest
-// (k3_forest) or one of the closed forms (k3_simple) -- over n records (n_dev: the count is on the device, n is the capacity)
-void mc_launch_classifier(const DevMlp &M, const DevForest &F, const DevSimple &S, int n_cu, hipStream_t st, const double *feats, int k,
+// (k3_forest), one of the closed forms (k3_simple) or the RBF SVM (k3_svm) -- over n records (n_dev: the count is on the device, n
+// is the capacity)
+void mc_launch_classifier(const DevMlp &M, const DevForest &F, const DevSimple &S, const DevSvm &V, int n_cu, hipStream_t st, const double *feats, int k,
                           const int32_t *site_seg, const int32_t *seg_read, const double *qual, const uint32_t *info,
                           const uint8_t *submodel_in, int64_t n, double *prob, const unsigned long long *n_dev, const unsigned int *overflow,
                           const int32_t *piece_cnt, int piece_room, int64_t n_pieces) {
     if (n <= 0) return;
     const K2Pieces P{(piece_room > 0 && piece_room < K2B) ? piece_cnt : nullptr, piece_room, n_pieces};
-    if (F.left)                // (a wave per record or a lane per record: the kernel looks at the count, which may be on the device only)
+    if (V.sv) {                // (workgroups walk the records grid-stride: at most 8 per CU -- 32 waves -- resident at once)
+        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + K3S_THREADS - 1) / K3S_THREADS, (int64_t)n_cu * 8));
+        if (V.n_in == 7)
+            hipLaunchKernelGGL(k3_svm<7>, dim3(grid), dim3(K3S_THREADS), 0, st, V, feats, k, site_seg, seg_read, qual, info, submodel_in, n,
+                               prob, n_dev, overflow);
+        else
+            hipLaunchKernelGGL(k3_svm<0>, dim3(grid), dim3(K3S_THREADS), 0, st, V, feats, k, site_seg, seg_read, qual, info, submodel_in, n,
+                               prob, n_dev, overflow);
+    } else if (F.left)              // (a wave per record or a lane per record: the kernel looks at the count, which may be on the device only)
         hipLaunchKernelGGL(k3_forest, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 3) / 4, (int64_t)n_cu * 8))), dim3(K3_THREADS), 0, st,
                            F, feats, k, site_seg, seg_read, qual, info, submodel_in, n, prob, n_dev, overflow);
     else if (S.params)

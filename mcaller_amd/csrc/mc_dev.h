@@ -2,7 +2,7 @@
 // marked reference, name-block descriptors, records, payloads, counters), the constants of the tile / chunk geometry, and the small
 // device functions more than one unit uses.  The kernels themselves and their launch geometry: mc_k0.hip (strand resolve),
 // mc_scan.hip (the scan, ordering), mc_emit.hip (window emit, row-by-row kernels), mc_literal.hip (irregular reads),
-// mc_classify.hip (MLP / forest / LR / NBC, packing); the host side (contexts, table slots, passes, device parser, per-site
+// mc_classify.hip (MLP / forest / LR / NBC / SVM, packing); the host side (contexts, table slots, passes, device parser, per-site
 // reduction, RCCL): mc_stream.hip.  C ABI: include/mcaller_hip.h.
 #ifndef MC_DEV_H
 #define MC_DEV_H
@@ -151,6 +151,17 @@ struct DevForest {
 struct DevSimple {
     int32_t kind = 0, n_models = 0, n_in = 0, stride = 0;
     double *params = nullptr;
+    uint8_t *sub_of_char = nullptr;
+};
+
+// RBF support-vector classifier with Platt probabilities (-c SVM; train_model.py:51-53, scored at :199): sub-model m owns support
+// vectors model_sv_off[m] .. model_sv_off[m + 1] - 1.  Each is a row of n_in + 1 doubles, its coordinates and then its dual
+// coefficient (what k3_svm stages into LDS as it stands); per sub-model 4 doubles gamma, intercept, A, B.
+constexpr int K3S_MAXM = 8;        // sub-models k3_svm buckets (mc_ctx_set_svm refuses more)
+struct DevSvm {
+    int32_t n_models = 0, n_in = 0;
+    int32_t *model_sv_off = nullptr;
+    double *sv = nullptr, *params = nullptr;
     uint8_t *sub_of_char = nullptr;
 };
 
@@ -515,7 +526,7 @@ void mc_launch_rare_dev(const K1Args &A, const Payload *sorted, const int64_t *r
 void mc_launch_bigfix(const K1Args &A, int64_t n, hipStream_t st);
 void mc_launch_literal(const LitArgs &LA, unsigned grid, hipStream_t st);
 void mc_launch_merge(const DevRecords &O, int64_t n_o, const DevRecords &L, int64_t n_l, const DevRecords &M, int k, hipStream_t st);
-void mc_launch_classifier(const DevMlp &M, const DevForest &F, const DevSimple &S, int n_cu, hipStream_t st, const double *feats, int k,
+void mc_launch_classifier(const DevMlp &M, const DevForest &F, const DevSimple &S, const DevSvm &V, int n_cu, hipStream_t st, const double *feats, int k,
                           const int32_t *site_seg, const int32_t *seg_read, const double *qual, const uint32_t *info,
                           const uint8_t *submodel_in, int64_t n, double *prob, const unsigned long long *n_dev, const unsigned int *overflow,
                           const int32_t *piece_cnt = nullptr, int piece_room = 0, int64_t n_pieces = 0);

@@ -39,7 +39,7 @@
 //                k2_mlp<.., PACK>   the side stream of a pipelined pass as ONE kernel: the windows the emit left to the
 //                                row-by-row walk (its own records'), the MLP, the records packed for the copy-out
 //                k1_rare_dev, k_pack_count / k_pack   the same in kernels of their own (other classifiers than the MLP)
-//                k3_forest, k3_simple   random forest / LR / NBC predict_proba;  k_literal / k_merge  irregular reads, row by row
+//                k3_forest, k3_simple, k3_svm   random forest / LR / NBC / SVM predict_proba;  k_literal / k_merge  irregular reads, row by row
 //                k_rt_count / k_rt_scan / k_rt_wide / k_rt_digits / k_rt_rows<false> / k_rt_scan_len / k_rt_rows<true> / k_rt_copy   the
 //                                rows of a streamed shard as TEXT, written behind its packed records (mc_rowtext.hip; mc_ctx_row_text):
 //                                the digits of every 64-bit slot mean one lane per number, the rows one lane per record -- counted,
@@ -184,7 +184,8 @@ struct mc_ctx {
     DevMlp M;
     DevForest F;
     DevSimple Sc;                      // -c LR / -c NBC
-    std::vector<void *> forest_allocs, simple_allocs;
+    DevSvm Vs;                         // -c SVM
+    std::vector<void *> forest_allocs, simple_allocs, svm_allocs;
     double *qual = nullptr;
     int32_t n_qual = 0;
     NbDesc *desc = nullptr;
@@ -460,6 +461,7 @@ extern "C" void mc_ctx_destroy(mc_ctx *c) {
     free_pool(c->mlp_allocs);
     free_pool(c->forest_allocs);
     free_pool(c->simple_allocs);
+    free_pool(c->svm_allocs);
     free_pool(c->rec_allocs);
     free_pool(c->lit_allocs);
     if (c->qual_own) (void)hipFree(c->qual_own);
@@ -1272,8 +1274,10 @@ extern "C" int mc_ctx_set_mlp(mc_ctx *c, int32_t n_models, int32_t n_in, int32_t
     free_pool(c->mlp_allocs);
     free_pool(c->forest_allocs);
     free_pool(c->simple_allocs);
+    free_pool(c->svm_allocs);
     c->F = DevForest();
     c->Sc = DevSimple();
+    c->Vs = DevSvm();
     DevMlp &M = c->M;
     M.n_models = n_models;
     M.n_in = n_in;
@@ -1355,8 +1359,10 @@ extern "C" int mc_ctx_set_forest(mc_ctx *c, int32_t n_models, int32_t n_in, cons
     free_pool(c->forest_allocs);
     free_pool(c->mlp_allocs);
     free_pool(c->simple_allocs);
+    free_pool(c->svm_allocs);
     c->M = DevMlp();
     c->Sc = DevSimple();
+    c->Vs = DevSvm();
     DevForest &F = c->F;
     F.n_models = n_models;
     F.n_in = n_in;
@@ -1392,8 +1398,10 @@ extern "C" int mc_ctx_set_simple_classifier(mc_ctx *c, int32_t kind, int32_t n_m
     free_pool(c->forest_allocs);
     free_pool(c->mlp_allocs);
     free_pool(c->simple_allocs);
+    free_pool(c->svm_allocs);
     c->M = DevMlp();
     c->F = DevForest();
+    c->Vs = DevSvm();
     DevSimple &S = c->Sc;
     S = DevSimple();
     UP(S.params, params, (size_t)n_models * stride, c->simple_allocs);
@@ -1403,15 +1411,54 @@ extern "C" int mc_ctx_set_simple_classifier(mc_ctx *c, int32_t kind, int32_t n_m
     return 0;
 }
 
+extern "C" int mc_ctx_set_svm(mc_ctx *c, int32_t n_models, int32_t n_in, const int32_t *model_sv_off, const double *sv,
+                              const double *dual_coef, const double *params, const uint8_t *sub_of_char) {
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = sync_pass_streams(c)) return rc;            // (passes in flight score with the old one, on the side stream)
+    if (n_models < 1 || n_models > K3S_MAXM || n_in < 1 || n_in > MC_MAX_K + 1 || model_sv_off[0] != 0) {
+        mc_set_error("unsupported SVM shape: %d models (at most %d), %d inputs", n_models, K3S_MAXM, n_in);
+        return -12;
+    }
+    for (int m = 0; m < n_models; ++m)
+        if (model_sv_off[m + 1] <= model_sv_off[m] || !(params[4 * m] >= 0.0)) {
+            mc_set_error("SVM sub-model %d: %d support vectors, gamma %g", m, model_sv_off[m + 1] - model_sv_off[m], params[4 * m]);
+            return -12;
+        }
+    // the rows k3_svm stages: a support vector's coordinates, then its dual coefficient (alive until the copy has been waited for)
+    const size_t n_sv = (size_t)model_sv_off[n_models], row = (size_t)n_in + 1;
+    std::vector<double> rows(n_sv * row);
+    for (size_t i = 0; i < n_sv; ++i) {
+        memcpy(&rows[i * row], sv + i * n_in, (size_t)n_in * sizeof(double));
+        rows[i * row + n_in] = dual_coef[i];
+    }
+    free_pool(c->forest_allocs);
+    free_pool(c->mlp_allocs);
+    free_pool(c->simple_allocs);
+    free_pool(c->svm_allocs);
+    c->M = DevMlp();
+    c->F = DevForest();
+    c->Sc = DevSimple();
+    DevSvm &V = c->Vs;
+    V = DevSvm();
+    UP(V.model_sv_off, model_sv_off, (size_t)n_models + 1, c->svm_allocs);
+    UP(V.sv, rows.data(), rows.size(), c->svm_allocs);
+    UP(V.params, params, (size_t)n_models * 4, c->svm_allocs);
+    UP(V.sub_of_char, sub_of_char, 256, c->svm_allocs);
+    V.n_models = n_models;
+    V.n_in = n_in;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 static int classifier_inputs(const mc_ctx *c) {
-    return c->F.left ? c->F.n_in : (c->Sc.params ? c->Sc.n_in : (c->M.W1 ? c->M.n_in : 0));
+    return c->F.left ? c->F.n_in : (c->Sc.params ? c->Sc.n_in : (c->Vs.sv ? c->Vs.n_in : (c->M.W1 ? c->M.n_in : 0)));
 }
 // the classifier of the context over n records (mc_classify.hip)
 static void launch_classifier(mc_ctx *c, hipStream_t st, const double *feats, int k, const int32_t *site_seg, const int32_t *seg_read,
                               const double *qual, const uint32_t *info, const uint8_t *submodel_in, int64_t n, double *prob,
                               const unsigned long long *n_dev, const unsigned int *overflow, const int32_t *piece_cnt = nullptr,
                               int piece_room = 0, int64_t n_pieces = 0) {
-    mc_launch_classifier(c->M, c->F, c->Sc, c->n_cu, st, feats, k, site_seg, seg_read, qual, info, submodel_in, n, prob, n_dev, overflow,
+    mc_launch_classifier(c->M, c->F, c->Sc, c->Vs, c->n_cu, st, feats, k, site_seg, seg_read, qual, info, submodel_in, n, prob, n_dev, overflow,
                          piece_cnt, piece_room, n_pieces);
 }
 
@@ -1861,7 +1908,7 @@ static int enqueue_side(mc_ctx *c, mc_ctx::AsyncBuf &b, const K1Args &A, bool *d
     const DevTable &T = c->T;
     hipStream_t st = c->side_stream;
     *done = false;
-    const bool other = c->F.left != nullptr || c->Sc.params != nullptr;
+    const bool other = c->F.left != nullptr || c->Sc.params != nullptr || c->Vs.sv != nullptr;
     if (b.prm.score && (other || !c->M.W1)) return 0;
     HIP_TRY(hipStreamWaitEvent(st, b.ev_emit_end, 0));
     if (b.timed || !MC_EVENTS_ON_KERNELS) HIP_TRY(hipEventRecord(b.ev_k2_start, st));
@@ -2006,7 +2053,7 @@ static int enqueue_row_text(mc_ctx *c, mc_ctx::AsyncBuf &b, int64_t n, int64_t m
     if (b.slot < 0 || m <= 0 || n <= 0 || !c->side_stream) { R.n_other += 1; return 0; }
     TableSlot &S = c->slots[b.slot];
     if (!S.from_parser || !S.text || !S.kp_segs || !S.kp_segs_h || !c->kc.chars || S.T.n_seg <= 0) { R.n_other += 1; return 0; }
-    const uint8_t *soc = c->F.left ? c->F.sub_of_char : (c->Sc.params ? c->Sc.sub_of_char : c->M.sub_of_char);
+    const uint8_t *soc = c->F.left ? c->F.sub_of_char : (c->Sc.params ? c->Sc.sub_of_char : (c->Vs.sv ? c->Vs.sub_of_char : c->M.sub_of_char));
     if (!soc || !b.prm.score || !b.qual || !c->R.seq) { R.n_other += 1; return 0; }
     hipStream_t st = c->side_stream;
     if (R.bytes_per_row <= 0.0) {
@@ -2318,9 +2365,9 @@ extern "C" int mc_last_times_ms(mc_ctx *c, float *out5) {
 // predict_proba of the context's classifier on n input rows from the host (what the reference's call site :199 does, batched)
 static int classifier_forward(mc_ctx *c, int which, const double *X, const uint8_t *submodel, int64_t n, double *p) {
     HIP_TRY(hipSetDevice(c->device));
-    const bool have = which == 1 ? c->F.left != nullptr : (which == 2 ? c->Sc.params != nullptr : c->M.W1 != nullptr);
+    const bool have = which == 1 ? c->F.left != nullptr : (which == 2 ? c->Sc.params != nullptr : (which == 3 ? c->Vs.sv != nullptr : c->M.W1 != nullptr));
     if (!have) {
-        mc_set_error("classifier forward: no %s set", which == 1 ? "forest" : (which == 2 ? "logistic / naive Bayes model" : "MLP"));
+        mc_set_error("classifier forward: no %s set", which == 1 ? "forest" : (which == 2 ? "logistic / naive Bayes model" : (which == 3 ? "SVM" : "MLP")));
         return -12;
     }
     if (n <= 0) return 0;
@@ -2354,6 +2401,10 @@ extern "C" int mc_forest_forward(mc_ctx *c, const double *X, const uint8_t *subm
 
 extern "C" int mc_simple_forward(mc_ctx *c, const double *X, const uint8_t *submodel, int64_t n, double *p) {
     return classifier_forward(c, 2, X, submodel, n, p);
+}
+
+extern "C" int mc_svm_forward(mc_ctx *c, const double *X, const uint8_t *submodel, int64_t n, double *p) {
+    return classifier_forward(c, 3, X, submodel, n, p);
 }
 
 // ===================================================================================================

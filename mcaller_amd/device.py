@@ -222,13 +222,28 @@ class Device(object):
         check(lib().mc_ctx_set_simple_classifier(self._ctx, kind, len(models), models[0].n_in, _ptr(params), params.shape[1], _ptr(soc)))
         self._clf = 'simple'
 
+    @_serialized
+    def set_svm(self, models, submodel_of_char):
+        """models: list of SVMWeights (one per sub-model, support-vector counts of their own) -- `-c SVM`."""
+        if any(m.n_in != models[0].n_in for m in models):
+            raise NotImplementedError('sub-models of different shapes')
+        off = np.ascontiguousarray(np.concatenate([[0], np.cumsum([m.n_sv for m in models])]), dtype=np.int32)
+        sv = np.ascontiguousarray(np.concatenate([m.sv for m in models]), dtype=np.float64)
+        coef = np.ascontiguousarray(np.concatenate([m.dual_coef for m in models]), dtype=np.float64)
+        params = np.ascontiguousarray(np.stack([m.params() for m in models]), dtype=np.float64)
+        soc = np.ascontiguousarray(submodel_of_char, dtype=np.uint8)
+        check(lib().mc_ctx_set_svm(self._ctx, len(models), models[0].n_in, _ptr(off), _ptr(sv), _ptr(coef), _ptr(params), _ptr(soc)))
+        self._clf = 'svm'
+
     def set_classifier(self, weights, submodel_of_char):
-        """MLP, forest, logistic regression or naive Bayes, whatever the model file held (extract_contexts.py:199 calls any
-        of them the same way)."""
+        """MLP, forest, logistic regression, naive Bayes or RBF SVM, whatever the model file held (extract_contexts.py:199 calls
+        any of them the same way)."""
         if weights[0].kind == 'forest':
             self.set_forest(weights, submodel_of_char)
         elif weights[0].kind in ('logistic', 'gnb'):
             self.set_simple(weights, submodel_of_char)
+        elif weights[0].kind == 'svm':
+            self.set_svm(weights, submodel_of_char)
         else:
             self.set_mlp(weights, submodel_of_char)
             self._clf = 'mlp'
@@ -238,7 +253,8 @@ class Device(object):
         X = np.ascontiguousarray(X, dtype=np.float64)
         sm = np.ascontiguousarray(submodel, dtype=np.uint8)
         p = np.empty(len(X), dtype=np.float64)
-        fn = {'forest': lib().mc_forest_forward, 'simple': lib().mc_simple_forward}.get(getattr(self, '_clf', 'mlp'), lib().mc_mlp_forward)
+        fn = {'forest': lib().mc_forest_forward, 'simple': lib().mc_simple_forward,
+              'svm': lib().mc_svm_forward}.get(getattr(self, '_clf', 'mlp'), lib().mc_mlp_forward)
         check(fn(self._ctx, _ptr(X), _ptr(sm), len(X), _ptr(p)))
         return p
 

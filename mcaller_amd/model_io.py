@@ -135,6 +135,46 @@ class GaussianNBWeights(object):
         return np.concatenate([self.theta[0], self.var[0], self.theta[1], self.var[1], np.log(self.prior)])
 
 
+class SVMWeights(object):
+    """scikit-learn SVC(kernel='rbf', probability=True), two classes, dense (train_model.py:51-53, `-c SVM`): the support vectors
+    [n_sv, n_in] and what libsvm scores with -- the dual coefficients and intercept as scikit-learn hands them to libsvm
+    (`_dual_coef_`, `_intercept_`), the resolved gamma, the Platt parameters A, B."""
+    kind = 'svm'
+
+    def __init__(self, sv, dual_coef, gamma, intercept, A, B, classes=None):
+        self.sv = np.ascontiguousarray(sv, dtype=np.float64)
+        self.dual_coef = np.ascontiguousarray(dual_coef, dtype=np.float64).reshape(-1)
+        if self.sv.ndim != 2 or self.sv.shape[0] != len(self.dual_coef) or self.sv.shape[0] < 1:
+            raise NotImplementedError('SVC with %s support vectors and %d coefficients' % (self.sv.shape, len(self.dual_coef)))
+        self.gamma, self.intercept, self.A, self.B = float(gamma), float(intercept), float(A), float(B)
+        self.n_sv, self.n_in = self.sv.shape
+        self.classes = classes
+
+    def params(self):
+        return np.array([self.gamma, self.intercept, self.A, self.B])
+
+
+def _svc_weights(est, where):
+    """An SVC as SVMWeights, or NotImplementedError for what k3_svm does not score."""
+    kernel = _as_text(getattr(est, 'kernel', 'rbf'))
+    classes = [_as_text(c) for c in getattr(est, 'classes_', [])]
+    if kernel != 'rbf':
+        raise NotImplementedError('%s: SVC with kernel %r (the HIP path scores kernel=\'rbf\' only)' % (where, kernel))
+    if getattr(est, '_sparse', False):
+        raise NotImplementedError('%s: SVC fitted on sparse input (dense fits only)' % where)
+    if len(classes) != 2:
+        raise NotImplementedError('%s: SVC with %d classes (two are supported)' % (where, len(classes)))
+    A = getattr(est, '_probA', getattr(est, 'probA_', None))
+    B = getattr(est, '_probB', getattr(est, 'probB_', None))
+    if A is None or B is None or np.asarray(A).size < 1 or np.asarray(B).size < 1:
+        raise NotImplementedError('%s: SVC without probability estimates (fit with probability=True)' % where)
+    dual = np.asarray(est._dual_coef_, dtype=np.float64)
+    if dual.ndim != 2 or dual.shape[0] != 1:
+        raise NotImplementedError('%s: SVC with dual coefficients of shape %s' % (where, dual.shape))
+    return SVMWeights(est.support_vectors_, dual[0], est._gamma, np.asarray(est._intercept_, dtype=np.float64).reshape(-1)[0],
+                      np.asarray(A, dtype=np.float64).reshape(-1)[0], np.asarray(B, dtype=np.float64).reshape(-1)[0], classes)
+
+
 def _as_text(x):
     return x.decode('latin1') if isinstance(x, bytes) else str(x)
 
@@ -160,9 +200,11 @@ def _estimator_weights(est, where):
         if var is None:
             var = est.sigma_                                # (scikit-learn < 1.0)
         return GaussianNBWeights(est.theta_, var, est.class_prior_, [_as_text(c) for c in getattr(est, 'classes_', [])])
+    if cls == 'SVC':
+        return _svc_weights(est, where)
     if cls != 'MLPClassifier':
         raise NotImplementedError('%s: classifier %s is not supported by the HIP path (MLPClassifier, RandomForestClassifier, '
-                                  'LogisticRegression and GaussianNB are)' % (where, cls))
+                                  'LogisticRegression, GaussianNB and SVC are)' % (where, cls))
     coefs, inter = est.coefs_, est.intercepts_
     act = _as_text(getattr(est, 'activation', 'tanh'))
     out_act = _as_text(getattr(est, 'out_activation_', 'logistic'))
