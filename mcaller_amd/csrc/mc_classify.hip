@@ -855,9 +855,25 @@ __global__ __launch_bounds__(K3_THREADS) void k3_forest(DevForest F, const doubl
 
 // ---------------------------------------------------------------------------------------------------
 // K3': the closed-form classifiers -- logistic regression (-c LR) and Gaussian naive Bayes (-c NBC), train_model.py:55-60;
-// call site :199.  One lane per record, fp64, the sums in index order (scikit-learn: a BLAS dot / numpy sums over seven
-// terms: agreement to ~1e-16 relative, pinned at 1e-12 against captured predict_proba).
+// call site :199.  One lane per record, fp64; the logistic dot product in index order (scikit-learn: a BLAS dot, agreement to
+// ~1e-16 relative), naive Bayes' sums in numpy's order (np_row_sum); pinned at 1e-12 against captured predict_proba.
 // ---------------------------------------------------------------------------------------------------
+// np.sum of a row of n <= MC_MAX_K + 1 doubles, as numpy adds it (pairwise_sum): one after the other below 8 terms; from 8 on, eight
+// partial sums ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)) and then the rest in order.  GaussianNB's sums over the inputs
+// are these: at 8 and 9 inputs the order of the index differs from them in the last bits of jll, which a probability in the
+// middle of the range shows where |jll| is large.
+static_assert(MC_MAX_K + 1 < 16, "np_row_sum: one block of eight partial sums");
+__device__ __forceinline__ double np_row_sum(const double *v, int n) {
+    if (n < 8) {
+        double s = 0.0;
+        for (int i = 0; i < 8; ++i) if (i < n) s += v[i];
+        return s;
+    }
+    double s = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
+    for (int i = 8; i < MC_MAX_K + 1; ++i) if (i < n) s += v[i];
+    return s;
+}
+
 __global__ __launch_bounds__(64) void k3_simple(DevSimple S, const double *__restrict__ feats, int k,
                                                 const int32_t *__restrict__ site_seg, const int32_t *__restrict__ seg_read,
                                                 const double *__restrict__ qual, const uint32_t *__restrict__ info,
@@ -888,21 +904,22 @@ __global__ __launch_bounds__(64) void k3_simple(DevSimple S, const double *__res
         double d = 0.0;
         for (int i = 0; i < MC_MAX_K + 1; ++i) if (i < NI) d += x[i] * P[i];
         d += P[NI];
-        // scipy.special.expit: 1 / (1 + exp(-d)), the large-|d| ends as it writes them
-        prob[r] = d >= 0.0 ? 1.0 / (1.0 + exp(-d)) : exp(d) / (1.0 + exp(d));
+        // scipy.special.expit: 1 / (1 + exp(-d)) for every d -- below d = -709.78 exp(-d) overflows and p is exactly 0, as there
+        prob[r] = 1.0 / (1.0 + exp(-d));
     } else {
         // GaussianNB._joint_log_likelihood: log prior - 0.5 * sum(log(2 pi var)) - 0.5 * sum((x - theta)^2 / var)
+        // (each sum in numpy's order, np_row_sum: from 8 inputs on it is not the order of the index)
         double jll[2];
         for (int cls = 0; cls < 2; ++cls) {
             const double *theta = P + (size_t)cls * 2 * NI, *var = theta + NI;
-            double a = 0.0, b2 = 0.0;
+            double la[MC_MAX_K + 1], lb[MC_MAX_K + 1];
             for (int i = 0; i < MC_MAX_K + 1; ++i)
                 if (i < NI) {
-                    a += log(2.0 * 3.14159265358979323846 * var[i]);
+                    la[i] = log(2.0 * 3.14159265358979323846 * var[i]);
                     const double t = x[i] - theta[i];
-                    b2 += (t * t) / var[i];
+                    lb[i] = (t * t) / var[i];
                 }
-            jll[cls] = P[4 * (size_t)NI + cls] + (-0.5 * a) - 0.5 * b2;
+            jll[cls] = P[4 * (size_t)NI + cls] + (-0.5 * np_row_sum(la, NI)) - 0.5 * np_row_sum(lb, NI);
         }
         // exp(jll1 - logsumexp(jll0, jll1))
         const double mx = fmax(jll[0], jll[1]);

@@ -13,17 +13,23 @@ The arithmetic lives in a third-party dependency that is not under /root/referen
 
 Pinned: tests/golden/models/simple_meta.json holds predict_proba of estimators fitted and run in the build container
 (tests/golden/make_golden.py::export_simple_fixture); tests/test_simple_classifiers.py holds this file against them."""
+import math
+
 import numpy as np
 
 
 def logistic_proba(coef, intercept, X):
+    """expit(d) as scipy writes it, 1 / (1 + exp(-d)) for every d (exactly 0 once exp(-d) overflows, d < -709.78), with the
+    C library's exp (numpy's own vector exp differs from it in the last bit now and then)."""
     d = np.asarray(X, dtype=np.float64) @ np.asarray(coef, dtype=np.float64) + float(intercept)
-    out = np.empty_like(d)
-    pos = d >= 0
-    out[pos] = 1.0 / (1.0 + np.exp(-d[pos]))
-    e = np.exp(d[~pos])
-    out[~pos] = e / (1.0 + e)
-    return out
+    return np.array([1.0 / (1.0 + _exp(v)) for v in (-d).tolist()]).reshape(d.shape)
+
+
+def _exp(v):
+    try:
+        return math.exp(v)
+    except OverflowError:
+        return math.inf
 
 
 def gnb_proba(theta, var, prior, X):

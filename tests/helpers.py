@@ -104,6 +104,10 @@ def oracle_score(rec, table, qual, weights, soc, k):
         from oracle import clf_oracle
         rec.prob[:n] = clf_oracle.forward(weights, X, sub)
         return
+    if weights[0].kind == 'svm':
+        from tests import svm_oracle
+        rec.prob[:n] = svm_oracle.forward(weights, X, sub)
+        return
     W1 = np.ascontiguousarray(np.stack([w.W1 for w in weights]))
     b1 = np.ascontiguousarray(np.stack([w.b1 for w in weights]))
     W2 = np.ascontiguousarray(np.stack([w.W2 for w in weights]))
