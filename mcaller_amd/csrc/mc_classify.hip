@@ -231,7 +231,7 @@ struct SidePack {
     K1Args A;                     // the pass: table, reference, descriptors, records, counters, rare_list, chunk_cnt / piece_kw
     const Payload *sorted;        // its payloads in record order (the walk's input)
     unsigned char *out;           // the block the copy-out moves
-    size_t out_bytes;             // ... its size: a pass that needs more is marked (Counters.overflow, pack_need) and repeated
+    size_t out_bytes;             // ... its size: a pass that needs more is marked (overflow, pack_need of host_status) and repeated
     Counters *host_status;        // the pass's counters as the host reads them (pinned)
     int close32, score;
 };
@@ -374,17 +374,12 @@ __global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu((FAST && !RO
         for (int i = 0; i < 6; ++i) v[i] = s_red[PACK ? i : 0][0];
         __syncthreads();            // (s_red has been read)
         // (the block is sized for the records a table of this size is expected to leave, not for every slot of a fused pass: a pass that
-        // needs more says how much and is repeated -- every workgroup comes to the same conclusion from the same sums)
+        // needs more says how much and is repeated -- every workgroup comes to the same conclusion from the same sums, so nothing is
+        // marked on the device: Counters.overflow is what the workgroups look at when they START, and one that started behind the
+        // mark would return without counting itself in side_done -- the workgroup through last tells the host, below)
         const size_t need_bytes = pack_tail(pack_layout((int64_t)v[2], SP.close32).feats, (size_t)v[0], k, (size_t)v[1]).end;
         const bool too_big = need_bytes > SP.out_bytes;
-        if (too_big) {
-            if (blockIdx.x == 0 && tid == 0) {
-                atomicExch(&SP.A.cnt->pack_need, (unsigned long long)need_bytes);
-                const unsigned was = atomicOr(&SP.A.cnt->overflow, 1u);
-                asm volatile("" :: "v"(was));
-            }
-            lo = hi;                                   // (no stretch; the counters still go to the host, below)
-        }
+        if (too_big) lo = hi;                          // (no stretch; the counters still go to the host, below)
         if (tid == 0) {
             const PackLayout PL = pack_layout((int64_t)v[2], SP.close32);
             const PackTail PTl = pack_tail(PL.feats, (size_t)v[0], k, (size_t)v[1]);
@@ -392,6 +387,7 @@ __global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu((FAST && !RO
             s_lay[6] = PTl.prob;
             s_base[0][0] = v[3]; s_base[0][1] = v[4]; s_base[0][2] = v[5];
             s_red[0][1] = v[2]; s_red[1][1] = v[0]; s_red[2][1] = v[1];         // (records, calls, wide slot means in all: for the host, at the end)
+            s_red[3][1] = need_bytes;                                           // (... and the block they need)
         }
         __syncthreads();
         K2_WALL(3);
@@ -745,10 +741,18 @@ __global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu((FAST && !RO
         if (s_last) {
             constexpr unsigned head_words = offsetof(Counters, end_of_head) / 4;
             constexpr int kept_word = (int)(offsetof(Counters, n_kept) / 4);
+            constexpr int overflow_word = (int)(offsetof(Counters, overflow) / 4), need_word = (int)(offsetof(Counters, pack_need) / 4);
             static_assert(offsetof(Counters, n_wide) == offsetof(Counters, n_kept) + 8 && offsetof(Counters, n_records) == 0, "Counters layout");
-            if (tid < (int)head_words && (tid < kept_word || tid >= kept_word + 4) && tid >= 2)
-                reinterpret_cast<volatile unsigned int *>(SP.host_status)[tid] =
-                    __hip_atomic_load(reinterpret_cast<unsigned int *>(SP.A.cnt) + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            static_assert(sizeof(Counters::overflow) == 4 && sizeof(Counters::pack_need) == 8 && offsetof(Counters, pack_need) % 8 == 0, "Counters layout");
+            const unsigned long long need_bytes = s_red[PACK ? 3 : 0][PACK ? 1 : 0];
+            const bool too_big = need_bytes > SP.out_bytes;
+            if (tid < (int)head_words && (tid < kept_word || tid >= kept_word + 4) && tid >= 2) {
+                unsigned int w = __hip_atomic_load(reinterpret_cast<unsigned int *>(SP.A.cnt) + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                // (a packed block too small: marked here, as k_pack marks it -- the pass is repeated, the next block holds pack_need)
+                if (too_big && tid == overflow_word) w |= 1u;
+                if (too_big && (tid == need_word || tid == need_word + 1)) w = (unsigned int)(need_bytes >> (tid == need_word ? 0 : 32));
+                reinterpret_cast<volatile unsigned int *>(SP.host_status)[tid] = w;
+            }
             if (tid == 0) {
                 *reinterpret_cast<volatile unsigned long long *>(&SP.host_status->n_records) = s_red[0][PACK ? 1 : 0];
                 *reinterpret_cast<volatile unsigned long long *>(&SP.host_status->n_kept) = s_red[PACK ? 1 : 0][PACK ? 1 : 0];

@@ -181,8 +181,9 @@ struct Counters {          // device-side status block
     unsigned long long n_kept; // records without MC_I_TOO_MANY (k_pack: rows of the compacted slot means / probabilities)
     unsigned long long n_wide; // slot means of those records that travel as 64 bits (k_pack: the others as 32-bit integers)
     unsigned long long side_done;  // workgroups of the side stream's kernel (k2_mlp<.., PACK>) that are through: the last one sends the counters to the host
-    unsigned long long pack_need;  // bytes the packed block of the pass would take if it is more than the block has (set with `overflow`: the pass is
-                                   // repeated, the next one gets a bigger block); 0: it fitted
+    unsigned long long pack_need;  // bytes the packed block of the pass would take if it is more than the block has (set with `overflow` in the
+                                   // host's copy, by k_pack or the last k2_mlp<.., PACK> workgroup: the pass is repeated, the next one gets a
+                                   // bigger block); 0: it fitted
     // the pass in which a name block was last classified irregular (mc_params-independent pass number, never 0).  Written,
     // never zeroed: k0_first_site classifies while it zeroes the other counters, so a count could lose updates -- a pass is
     // special iff this equals its own number
@@ -191,6 +192,10 @@ struct Counters {          // device-side status block
     unsigned long long pad_to_line[SHARD_PAD];
     unsigned long long shard[NSHARD * SHARD_PAD];
 };
+// what the host writes into the pinned copy's side_done when it enqueues a pipelined pass: every kernel that publishes the counters
+// (k_pack, k2_mlp<.., PACK> on either of its paths) copies side_done, whose device value is a count of workgroups -- a copy that
+// still holds this after the pass's kernels are through was never written (mc_wait_records_begin refuses it)
+constexpr unsigned long long ST_UNPUBLISHED = ~0ull;
 
 // The small kernels on the ctx stream's critical path (strand resolve, tile descriptors, the ordering of the payloads) run
 // beside the previous pass's classifier, whose waves keep the vector pipes busy: with the default wave priority the

@@ -2004,6 +2004,8 @@ extern "C" int mc_extract_features_async(mc_ctx *c, const mc_params *prm) {
     b.timed = c->timing_every > 0 && (c->pass_seq++ % c->timing_every) == 0;
     const PassPlan plan = plan_pass(c, st);
     if (b.timed) HIP_TRY(hipEventRecord(b.ev_k0_start, st));
+    // (the buffer's last pass has been handed out, nothing on the device writes st_host: the mark mc_wait_records_begin looks for)
+    b.st_host->side_done = ST_UNPUBLISHED;
     b.pass_no = ++c->pass_counter;
     if (int rc = enqueue_k0(c, prm, b.K, b.cnt, st, b.pass_no, false, plan)) return rc;
     if (b.timed) HIP_TRY(hipEventRecord(b.ev_scan_start, st));
@@ -2152,6 +2154,12 @@ extern "C" int mc_wait_records_begin(mc_ctx *c) {
         HIP_TRY(hipStreamWaitEvent(cs, b.ev_done, 0));
     }
     const Counters &st = *b.st_host;
+    // (the pass's kernels are through: a block that still carries the mark of the enqueue was never written -- what it holds is an
+    // earlier pass's, and no copy may be sized from it)
+    if (b.used && st.side_done == ST_UNPUBLISHED) {
+        mc_set_error("mc_wait_records_begin: pass %llu did not publish its counters", (unsigned long long)b.pass_no);
+        return -12;
+    }
     const bool special = st.overflow || st.irregular_pass == b.pass_no;      // (long windows were finished on the device: k1_rare_dev)
     if (b.used && !special && st.n_records > 0) {
         const size_t n = (size_t)std::min<int64_t>((int64_t)st.n_records, b.cap);
@@ -2161,6 +2169,11 @@ extern "C" int mc_wait_records_begin(mc_ctx *c) {
         const size_t n_wide = (size_t)std::min<unsigned long long>(st.n_wide, (unsigned long long)m * (size_t)k);
         const PackTail PT_ = pack_tail(L.feats, m, k, n_wide);
         const size_t out_bytes = PT_.end;
+        if (out_bytes > b.pack_bytes) {
+            mc_set_error("mc_wait_records_begin: pass %llu counts %zu bytes of records, its packed block holds %zu",
+                         (unsigned long long)b.pass_no, out_bytes, b.pack_bytes);
+            return -12;
+        }
         // (a small record set -- a shard of a streamed file -- by kernel: the DMA engines may be busy with text, see k_copy_bytes;
         // and on the side stream, right behind the packing: the runtime folds the streams of a process onto four hardware
         // queues, and a copy stream that shares one with the parse stream would wait behind the kernels of the shards ahead,
