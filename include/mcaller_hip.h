@@ -294,6 +294,14 @@ int mc_last_pass_info(mc_ctx *ctx, int32_t *fused_room, int32_t *rerun);
 int mc_ctx_row_text(mc_ctx *ctx, int32_t on, const char *label_meth, const char *label_unmeth);
 int mc_last_row_text(mc_ctx *ctx, const char **text, int64_t *n_bytes, int64_t *n_rows, int32_t *block);
 int mc_row_text_release(mc_ctx *ctx, int32_t block);
+/* The row writer's number printing alone, on the device (tests).  The doubles v[0, n) go through the row writer's digit kernel, the first
+ * n / 2 as wide slot means, the rest as read qualities; then fixed[0, n_fixed) as integer slot means (repr(d / 1e4)) and prob[0, n_prob)
+ * as np.round(p, 2), through the same sinks the rows use.  Item i (numbers, then fixed, then prob) is written at text[i * 48 + (i + shift)
+ * % 8] (every start alignment; text: 48 bytes an item, filled with 0xA5 first); len[i] = the length the counting pass gives it, ok[i] =
+ * 1 if it is printed (0: the row would go to the host formatter -- nothing written, len -1).  shift >= 0. */
+#define MC_ROWTEXT_PROBE_STRIDE 48
+int mc_ctx_rowtext_probe(mc_ctx *ctx, const double *v, int64_t n, const int32_t *fixed, int64_t n_fixed, const double *prob, int64_t n_prob,
+                         int32_t shift, char *text, int32_t *len, uint8_t *ok);
 /* The hot path on the GPU: strand resolve + window scan + classifier.  Leaves the flush records on the
  * device, in file order; *n_records = how many. */
 int mc_extract_features(mc_ctx *ctx, const mc_params *prm, int64_t *n_records);

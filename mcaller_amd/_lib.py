@@ -193,6 +193,8 @@ def lib():
         L.mc_ctx_row_text.argtypes = [C.c_void_p, C.c_int32, C.c_char_p, C.c_char_p]
         L.mc_last_row_text.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
         L.mc_row_text_release.argtypes = [C.c_void_p, C.c_int32]
+        L.mc_ctx_rowtext_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 

@@ -587,5 +587,9 @@ struct RowTextScratch {
 void mc_row_text_scratch_sizes(int64_t n, int64_t m, int64_t *rec_blocks, int64_t *row_blocks);
 void mc_launch_row_text(const RowTextIn &I, const RowTextScratch &S, char *out, size_t out_cap, char *out_host, RowTextStatus *st_host,
                         hipStream_t st);
+// tests (mc_ctx_rowtext_probe): k_rt_digits over I.n_wide wide slot means (S.wval) and I.n_qual qualities, then every number, fixed[n_fixed]
+// and prob[n_prob] through the row sinks into out (MC_ROWTEXT_PROBE_STRIDE bytes an item)
+void mc_launch_row_text_probe(const RowTextIn &I, const RowTextScratch &S, const int32_t *fixed, int64_t n_fixed, const double *prob,
+                              int64_t n_prob, int shift, char *out, int32_t *len, uint8_t *ok, hipStream_t st);
 
 #endif  // MC_DEV_H

@@ -335,6 +335,33 @@ __global__ __launch_bounds__(RT_B) void k_rt_rows(RowTextIn I, RowTextScratch S,
     }
 }
 
+// Tests (mc_ctx_rowtext_probe): the numbers k_rt_digits left, then integer slot means, then probabilities, each through the sinks
+// k_rt_rows uses -- counted, and written at item i * MC_ROWTEXT_PROBE_STRIDE + (i + shift) % 8 (every start alignment)
+__global__ __launch_bounds__(RT_B) void k_rt_probe(RowTextScratch S, int64_t n_num, const int32_t *fixed, int64_t n_fixed, const double *prob,
+                                                  int64_t n_prob, int shift, char *out, int32_t *len, uint8_t *ok) {
+    const int64_t i = (int64_t)blockIdx.x * RT_B + threadIdx.x;
+    if (i >= n_num + n_fixed + n_prob) return;
+    RtStoreWords w(out + i * MC_ROWTEXT_PROBE_STRIDE + (i + shift) % 8);
+    RtCountRows c;
+    bool good = true;
+    if (i < n_num) {
+        const RtNum num = rt_num_unpack(S.num_lo[i], S.num_meta[i]);
+        good = num.ok;
+        if (good) { w.put_num(num); c.put_num(num); }
+    } else if (i < n_num + n_fixed) {
+        const int32_t d = fixed[i - n_num];
+        rt_put_fixed4(w, d);
+        rt_put_fixed4(c, d);
+    } else {
+        const double p1 = prob[i - n_num - n_fixed];
+        good = rt_put_prob2(w, p1, rint(p1 * 100.0));                                // (as rt_row)
+        (void)rt_put_prob2(c, p1, rint(p1 * 100.0));
+    }
+    w.flush();
+    len[i] = good ? c.n : -1;
+    ok[i] = good ? 1 : 0;
+}
+
 // offsets of the blocks' rows (one workgroup); the total and the number of rows -> the status
 __global__ __launch_bounds__(RT_B) void k_rt_scan_len(RowTextScratch S, int64_t n_rec_blocks, unsigned long long out_cap) {
     __shared__ uint32_t s_w[4];
@@ -390,4 +417,14 @@ void mc_launch_row_text(const RowTextIn &I, const RowTextScratch &S, char *out, 
     hipLaunchKernelGGL(k_rt_rows<true>, dim3((unsigned)nbr), dim3(RT_B), 0, st, I, S, out);
     const unsigned blocks = (unsigned)std::min<size_t>((out_cap / 16 + 255) / 256 + 1, 1024);
     hipLaunchKernelGGL(k_rt_copy, dim3(blocks), dim3(256), 0, st, (unsigned char *)out_host, (const unsigned char *)out, (const RowTextStatus *)S.st, st_host);
+}
+
+void mc_launch_row_text_probe(const RowTextIn &I, const RowTextScratch &S, const int32_t *fixed, int64_t n_fixed, const double *prob,
+                              int64_t n_prob, int shift, char *out, int32_t *len, uint8_t *ok, hipStream_t st) {
+    const int64_t n_num = I.n_wide + I.n_qual;
+    if (n_num > 0) hipLaunchKernelGGL(k_rt_digits, dim3((unsigned)((n_num + RT_B - 1) / RT_B)), dim3(RT_B), 0, st, I, S);
+    const int64_t n_all = n_num + n_fixed + n_prob;
+    if (n_all > 0)
+        hipLaunchKernelGGL(k_rt_probe, dim3((unsigned)((n_all + RT_B - 1) / RT_B)), dim3(RT_B), 0, st, S, n_num, fixed, n_fixed, prob, n_prob, shift,
+                           out, len, ok);
 }

@@ -2356,6 +2356,54 @@ extern "C" int mc_row_text_release(mc_ctx *c, int32_t block) {
     return 0;
 }
 
+// the row writer's numbers alone (tests): the digit kernel and the sinks of mc_rowtext.hip on the caller's values
+static int rowtext_probe(mc_ctx *c, std::vector<void *> &pool, const double *v, int64_t n, const int32_t *fixed, int64_t n_fixed,
+                         const double *prob, int64_t n_prob, int32_t shift, char *text, int32_t *len, uint8_t *ok) {
+    const int64_t n_all = n + n_fixed + n_prob;
+    const size_t text_bytes = (size_t)n_all * MC_ROWTEXT_PROBE_STRIDE;
+    hipStream_t st = c->stream;
+    RowTextScratch S = {};
+    double *d_q = nullptr, *d_prob = nullptr;
+    int32_t *d_fixed = nullptr, *d_len = nullptr;
+    uint8_t *d_ok = nullptr;
+    char *d_text = nullptr;
+    if (dev_alloc(pool, &S.wval, (size_t)n) || dev_alloc(pool, &d_q, (size_t)n) || dev_alloc(pool, &S.num_lo, (size_t)n) ||
+        dev_alloc(pool, &S.num_meta, (size_t)n) || dev_alloc(pool, &d_fixed, (size_t)n_fixed) || dev_alloc(pool, &d_prob, (size_t)n_prob) ||
+        dev_alloc(pool, &d_text, text_bytes) || dev_alloc(pool, &d_len, (size_t)n_all) || dev_alloc(pool, &d_ok, (size_t)n_all))
+        return -10;
+    RowTextIn I = {};
+    I.n_wide = n / 2;                                   // the first half as wide slot means, the rest as read qualities (k_rt_digits' two sources)
+    I.n_qual = (int32_t)(n - n / 2);
+    I.qual = d_q;
+    if (I.n_wide) HIP_TRY(hipMemcpyAsync(S.wval, v, (size_t)I.n_wide * 8, hipMemcpyHostToDevice, st));
+    if (I.n_qual) HIP_TRY(hipMemcpyAsync(d_q, v + I.n_wide, (size_t)I.n_qual * 8, hipMemcpyHostToDevice, st));
+    if (n_fixed) HIP_TRY(hipMemcpyAsync(d_fixed, fixed, (size_t)n_fixed * 4, hipMemcpyHostToDevice, st));
+    if (n_prob) HIP_TRY(hipMemcpyAsync(d_prob, prob, (size_t)n_prob * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(d_text, 0xA5, text_bytes, st));
+    mc_launch_row_text_probe(I, S, d_fixed, n_fixed, d_prob, n_prob, shift, d_text, d_len, d_ok, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(text, d_text, text_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(len, d_len, (size_t)n_all * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(ok, d_ok, (size_t)n_all, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int mc_ctx_rowtext_probe(mc_ctx *c, const double *v, int64_t n, const int32_t *fixed, int64_t n_fixed, const double *prob,
+                                    int64_t n_prob, int32_t shift, char *text, int32_t *len, uint8_t *ok) {
+    HIP_TRY(hipSetDevice(c->device));
+    if (n < 0 || n_fixed < 0 || n_prob < 0 || shift < 0 || n - n / 2 > INT32_MAX) {
+        mc_set_error("mc_ctx_rowtext_probe: counts and shift >= 0");
+        return -12;
+    }
+    if (n + n_fixed + n_prob == 0) return 0;
+    std::vector<void *> pool;
+    const int rc = rowtext_probe(c, pool, v, n, fixed, n_fixed, prob, n_prob, shift, text, len, ok);
+    if (rc) (void)hipStreamSynchronize(c->stream);      // (nothing may still be writing into what is freed)
+    free_pool(pool);
+    return rc;
+}
+
 extern "C" int mc_last_pass_info(mc_ctx *c, int32_t *fused_room, int32_t *rerun) {
     if (fused_room) *fused_room = c->last_fused_room;
     if (rerun) *rerun = c->last_rerun;

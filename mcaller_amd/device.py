@@ -316,6 +316,25 @@ class Device(object):
         check(lib().mc_ctx_row_text(self._ctx, (2 if first else 1) if on else 0, label_meth.encode() if label_meth else None,
                                     label_unmeth.encode() if label_unmeth else None))
 
+    ROWTEXT_PROBE_STRIDE = 48            # MC_ROWTEXT_PROBE_STRIDE
+    ROWTEXT_PROBE_FILL = 0xA5
+
+    @_serialized
+    def rowtext_probe(self, values=(), fixed=(), prob=(), shift=0):
+        """The row writer's numbers alone (mc_ctx_rowtext_probe, tests): doubles through the digit kernel (the first half as wide slot
+        means, the rest as read qualities), int32 slot means as repr(d / 1e4), probabilities as np.round(p, 2).  -> (text: uint8
+        [items, ROWTEXT_PROBE_STRIDE], item i written from byte (i + shift) % 8 of its line; counted lengths (-1: not printed); ok)."""
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        f = np.ascontiguousarray(fixed, dtype=np.int32)
+        p = np.ascontiguousarray(prob, dtype=np.float64)
+        n_all = len(v) + len(f) + len(p)
+        text = np.empty((n_all, self.ROWTEXT_PROBE_STRIDE), dtype=np.uint8)
+        length = np.empty(n_all, dtype=np.int32)
+        ok = np.empty(n_all, dtype=np.uint8)
+        check(lib().mc_ctx_rowtext_probe(self._ctx, _ptr(v), len(v), _ptr(f), len(f), _ptr(p), len(p), int(shift), _ptr(text), _ptr(length),
+                                         _ptr(ok)))
+        return text, length, ok.astype(bool)
+
     @_serialized
     def fetch(self, copy=True):
         """Records of the last run.  copy=False: views of the context's pinned buffers (overwritten by the next run)."""
