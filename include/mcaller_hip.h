@@ -397,6 +397,30 @@ int mc_mlp_fit(mc_ctx *ctx, const mc_fit_params *prm, const double *X, const uin
                double *W1, double *b1, double *W2, double *b2,      /* per job: [n_in*n_hidden], [n_hidden], [n_hidden], [1] */
                double *loss_curve /* [n_jobs*max_iter] */, int32_t *n_iter /* epochs run */, int64_t *val_correct);
 
+/* ===== the random-forest fit behind --train -c RF (train_model.py:39-45,:62-65,:92-100): scikit-learn's RandomForestClassifier =====
+ * (entropy, bootstrap) with keyed randomness (tests/forest_fit_oracle.py defines it; the kernel follows it bit for bit).  n_jobs x
+ * n_trees independent trees, a workgroup each (k5_forest_fit).  Job j fits on rows train_idx[train_off[j] .. train_off[j+1]) of X
+ * (n_samples x n_in, cast to float32), labels y in {0, 1}, seed seeds[j]; its trees score rows val_idx[val_off[j] .. val_off[j+1])
+ * (val_correct[j]: predictions p1 > p0 equal to y).  G[n_G]: G[m] = m ln m, G[0] = 0, n_G > the largest job's row count.
+ * Output: the trees one after the other (tree j*n_trees + t), nodes in depth-first pre-order with scikit-learn's fields and child
+ * links local to the tree (-1 at a leaf; feature -2, threshold -2.0 there); tree_node_off[n_jobs*n_trees+1]; value[2*node+c]: the
+ * weighted class fractions.  node_cap: room in the node arrays, at least the sum over jobs of n_trees * min(2^(max_depth+1) - 1,
+ * 2 * rows - 1).  Returns -12 on a parameter out of range (max_features > n_in included). */
+typedef struct mc_forest_params {
+    int32_t n_in;                  /* features, 1 .. MC_MAX_K+1                    */
+    int32_t n_trees;               /* 50   (1 .. 100000)                           */
+    int32_t max_depth;             /* 10   (1 .. 30: heap ids stay in 64 bits)     */
+    int32_t max_features;          /* 4    (1 .. n_in)                             */
+    int32_t min_samples_split;     /* 3    (>= 2)                                  */
+    int32_t min_samples_leaf;      /* 2    (>= 1)                                  */
+    int32_t bootstrap;             /* 1    (0: every training row once)            */
+} mc_forest_params;
+int mc_forest_fit(mc_ctx *ctx, const mc_forest_params *prm, const double *X, const uint8_t *y, int64_t n_samples, int32_t n_jobs,
+                  const int64_t *train_off, const int32_t *train_idx, const int64_t *val_off, const int32_t *val_idx,
+                  const uint64_t *seeds, const double *G, int64_t n_G, int64_t node_cap, int64_t *tree_node_off,
+                  int32_t *left, int32_t *right, int32_t *feature, double *threshold, double *value, double *impurity,
+                  int32_t *n_node_samples, double *weighted_n_node_samples, int64_t *val_correct);
+
 /* ===== the eventalign text parsed on the GPU (replaces the row ingest, extract_contexts.py:140-152, for streamed shards) =====
  * The host only moves bytes: mc_read_file_range preads a byte range into (pinned) memory with all cores;
  * mc_ctx_parse_begin sends it and enqueues the kernels that split it into lines, tokenise (str.split()'s ASCII whitespace,

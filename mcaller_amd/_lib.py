@@ -70,6 +70,11 @@ class FitParams(C.Structure):
                 ('epsilon', C.c_double), ('tol', C.c_double), ('seed', C.c_uint64)]
 
 
+class ForestParams(C.Structure):
+    _fields_ = [('n_in', C.c_int32), ('n_trees', C.c_int32), ('max_depth', C.c_int32), ('max_features', C.c_int32),
+                ('min_samples_split', C.c_int32), ('min_samples_leaf', C.c_int32), ('bootstrap', C.c_int32)]
+
+
 class Params(C.Structure):
     _fields_ = [('k', C.c_int32), ('skip_thresh', C.c_int32), ('qual_thresh', C.c_double),
                 ('tail_contig', C.c_int32), ('score', C.c_int32),
@@ -181,6 +186,8 @@ def lib():
         L.mc_comm_destroy.argtypes = [C.c_void_p]
         L.mc_site_allreduce.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
         L.mc_mlp_fit.argtypes = [C.c_void_p, C.POINTER(FitParams), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 13
+        L.mc_forest_fit.argtypes = [C.c_void_p, C.POINTER(ForestParams), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 6 + \
+            [C.c_int64, C.c_int64] + [C.c_void_p] * 10
         L.mc_calls_expand.argtypes = [C.POINTER(CallsView), C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mc_count_records.argtypes = [C.POINTER(CallsView), C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p,
                                        C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]

@@ -490,6 +490,50 @@ class Device(object):
                      n_iter=int(n_iter[j]), val_correct=int(correct[j]), n_val=len(va[j])) for j in range(nj)]
 
     @_serialized
+    def forest_fit(self, X, y, jobs, n_trees=50, max_depth=10, max_features=4, min_samples_split=3, min_samples_leaf=2,
+                   bootstrap=True, seed=1, seeds=None):
+        """Fit one random forest per job on the GPU (mc_forest_fit: every tree of every job side by side; scikit-learn's
+        RandomForestClassifier(criterion='entropy') with keyed randomness).  jobs: [(train_rows, validation_rows)] index arrays into
+        X / y (y in {0, 1}).  -> per job a dict: tree_off [n_trees+1], the node arrays of its trees concatenated (left, right local
+        to each tree; feature, threshold, value [n, 2], impurity, n_node_samples, weighted_n_node_samples), val_correct, n_val."""
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.uint8)
+        n, d = X.shape
+        if max_features > d:
+            raise ValueError('max_features must be in (0, n_features]: %d > %d' % (max_features, d))
+        nj = len(jobs)
+        tr = [np.ascontiguousarray(j[0], dtype=np.int32) for j in jobs]
+        va = [np.ascontiguousarray(j[1], dtype=np.int32) for j in jobs]
+        tr_off = np.concatenate([[0], np.cumsum([len(a) for a in tr])]).astype(np.int64)
+        va_off = np.concatenate([[0], np.cumsum([len(a) for a in va])]).astype(np.int64)
+        tr_idx = np.ascontiguousarray(np.concatenate(tr + [np.zeros(1, np.int32)]))
+        va_idx = np.ascontiguousarray(np.concatenate(va + [np.zeros(1, np.int32)]))
+        sd = np.ascontiguousarray([(seed + j) % (1 << 64) for j in range(nj)] if seeds is None else seeds, dtype=np.uint64)
+        max_tr = max(len(a) for a in tr)
+        m = np.arange(max_tr + 1, dtype=np.float64)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            G = m * np.log(m)                                     # G[m] = m ln m: both sides read these bits
+        G[0] = 0.0
+        cap = sum(int(n_trees) * min((2 << int(max_depth)) - 1, max(2 * len(a) - 1, 1)) for a in tr)
+        prm = _lib.ForestParams(d, int(n_trees), int(max_depth), int(max_features), int(min_samples_split), int(min_samples_leaf),
+                                1 if bootstrap else 0)
+        toff = np.zeros(nj * n_trees + 1, dtype=np.int64)
+        left = np.empty(cap, np.int32); right = np.empty(cap, np.int32); feature = np.empty(cap, np.int32)
+        threshold = np.empty(cap); value = np.empty((cap, 2)); impurity = np.empty(cap)
+        n_node = np.empty(cap, np.int32); weighted = np.empty(cap); correct = np.zeros(nj, dtype=np.int64)
+        check(lib().mc_forest_fit(self._ctx, C.byref(prm), _ptr(X), _ptr(y), n, nj, _ptr(tr_off), _ptr(tr_idx), _ptr(va_off),
+                                  _ptr(va_idx), _ptr(sd), _ptr(G), len(G), cap, _ptr(toff), _ptr(left), _ptr(right), _ptr(feature),
+                                  _ptr(threshold), _ptr(value), _ptr(impurity), _ptr(n_node), _ptr(weighted), _ptr(correct)))
+        out = []
+        for j in range(nj):
+            a, b = toff[j * n_trees], toff[(j + 1) * n_trees]
+            out.append(dict(tree_off=toff[j * n_trees:(j + 1) * n_trees + 1] - a, left=left[a:b].copy(), right=right[a:b].copy(),
+                            feature=feature[a:b].copy(), threshold=threshold[a:b].copy(), value=value[a:b].copy(),
+                            impurity=impurity[a:b].copy(), n_node_samples=n_node[a:b].copy(),
+                            weighted_n_node_samples=weighted[a:b].copy(), val_correct=int(correct[j]), n_val=len(va[j])))
+        return out
+
+    @_serialized
     def mlp_forward(self, X, submodel):
         if getattr(self, '_clf', 'mlp') != 'mlp':
             return self.classifier_forward(X, submodel)

@@ -247,10 +247,30 @@ def shipped_model(stem='r95_twobase_model_NN_6_m6A'):
     return os.path.join(os.path.dirname(os.path.abspath(__file__)), 'models', stem + '.npz')
 
 
+def forest_from_arrays(tree_off, left, right, feature, threshold, value, n_features, classes=None):
+    """ForestWeights from trees stored one after the other: node arrays with child links local to each tree, tree_off[n_trees+1]."""
+    trees = []
+    for a, b in zip(tree_off[:-1], tree_off[1:]):
+        nodes = np.zeros(int(b - a), dtype=[('left_child', np.int64), ('right_child', np.int64), ('feature', np.int64),
+                                            ('threshold', np.float64)])
+        nodes['left_child'], nodes['right_child'] = left[a:b], right[a:b]
+        nodes['feature'], nodes['threshold'] = feature[a:b], threshold[a:b]
+        trees.append((nodes, np.asarray(value[a:b], dtype=np.float64).reshape(int(b - a), 2)))
+    return ForestWeights(trees, n_features, classes)
+
+
 def load_npz_weights(path, is_dict):
-    """Neutral weight export (mcaller_amd/models/*.npz): arrays '<key>.W1' ... '<key>.b2'."""
+    """Neutral weight export (mcaller_amd/models/*.npz, or what `--train` writes without scikit-learn): arrays '<key>.W1' ...
+    '<key>.b2' of a perceptron, or '<key>.tree_off', '.left', '.right', '.feature', '.threshold', '.value' of a forest."""
     z = np.load(path)
     keys = sorted(set(n.split('.')[0] for n in z.files if not n.startswith('__')))
-    models = {k: MLPWeights(z[k + '.W1'], z[k + '.b1'], z[k + '.W2'], z[k + '.b2'],
-                            classes=[str(c) for c in z[k + '.classes']] if k + '.classes' in z.files else None) for k in keys}
+    models = {}
+    for k in keys:
+        classes = [str(c) for c in z[k + '.classes']] if k + '.classes' in z.files else None
+        if k + '.tree_off' in z.files:
+            n_feat = int(z[k + '.n_features'][0]) if k + '.n_features' in z.files else int(z[k + '.feature'].max()) + 1
+            models[k] = forest_from_arrays(z[k + '.tree_off'], z[k + '.left'], z[k + '.right'], z[k + '.feature'], z[k + '.threshold'],
+                                           z[k + '.value'], n_feat, classes)
+        else:
+            models[k] = MLPWeights(z[k + '.W1'], z[k + '.b1'], z[k + '.W2'], z[k + '.b2'], classes=classes)
     return ModelSet(models, is_dict)

@@ -8,8 +8,12 @@ reference's `random_state=None` fit, two runs differ unless MCALLER_SEED is set.
 
 The model file is what the reference writes -- a pickle of {sub-model: MLPClassifier} (:110-112) -- when scikit-learn is
 importable (the estimators are filled with the fitted arrays, so the reference can load them); otherwise a neutral
-`.npz` of the same arrays that mcaller_amd.model_io reads.  The other classifiers (RF, SVM, LR, NBC) are fitted by
-scikit-learn itself when it is installed (`RF` without `min_impurity_split`, which scikit-learn >= 1.0 rejects).
+`.npz` of the same arrays that mcaller_amd.model_io reads.
+
+`RF` (train_model.py:39-45, without `min_impurity_split`, which scikit-learn >= 1.0 rejects) is fitted on the GPU too: the same
+six jobs, 50 trees each, every tree a workgroup of one `mc_forest_fit` call (mcaller_amd/csrc/mc_forest_fit.hip); its model file
+is a pickle of {sub-model: RandomForestClassifier} or the neutral `.npz` of the trees.  SVM, LR and NBC are fitted by
+scikit-learn itself when it is installed.
 """
 import os
 import pickle
@@ -57,14 +61,12 @@ def _seed():
     return int(env) if env != '' else int.from_bytes(os.urandom(7), 'little')
 
 
-def fit_nn_on_gpu(labs, sigs, grps, use_groups, device=None, hidden=100):
-    """-> (classes, cross-validation scores, final weights dict)."""
-    from .device import get_device
-    dev = device if device is not None else get_device()
+def cv_jobs(labs, grps, use_groups):
+    """The six fits of a sub-model: 5-fold GroupKFold by context (StratifiedKFold without shuffling when there are no groups)
+    and the final fit on all rows, with their seeds.  -> (classes, y, jobs, seeds)."""
     classes = sorted(set(labs))                                   # LabelBinarizer order == estimator.classes_
     if len(classes) != 2:
         raise ValueError('training needs exactly two labels in the positions file, got %s' % classes)
-    X = np.asarray(sigs, dtype=np.float64)
     y = np.asarray([1 if lab == classes[1] else 0 for lab in labs], dtype=np.uint8)
     n = len(y)
     if use_groups:
@@ -77,9 +79,34 @@ def fit_nn_on_gpu(labs, sigs, grps, use_groups, device=None, hidden=100):
     rows = np.arange(n)
     jobs = [(rows[fold != f], rows[fold == f]) for f in range(5)] + [(rows, np.zeros(0, dtype=np.int64))]
     seed = _seed()
-    fits = dev.mlp_fit(X, y, jobs, hidden=hidden, seeds=[(seed + 0x9E3779B97F4A7C15 * j) % (1 << 64) for j in range(6)])
+    return classes, y, jobs, [(seed + 0x9E3779B97F4A7C15 * j) % (1 << 64) for j in range(6)]
+
+
+def fit_nn_on_gpu(labs, sigs, grps, use_groups, device=None, hidden=100):
+    """-> (classes, cross-validation scores, final weights dict)."""
+    from .device import get_device
+    dev = device if device is not None else get_device()
+    classes, y, jobs, seeds = cv_jobs(labs, grps, use_groups)
+    X = np.asarray(sigs, dtype=np.float64)
+    fits = dev.mlp_fit(X, y, jobs, hidden=hidden, seeds=seeds)
     scores = np.array([f['val_correct'] / float(f['n_val']) for f in fits[:5]])
     return classes, scores, fits[5]
+
+
+RF_PARAMS = dict(n_trees=50, max_depth=10, max_features=4, min_samples_split=3, min_samples_leaf=2, bootstrap=True)   # train_model.py:39-45
+
+
+def fit_rf_on_gpu(labs, sigs, grps, use_groups, device=None):
+    """`-c RF`: the six forests of a sub-model in one mc_forest_fit call (k5_forest_fit).  -> (classes, cross-validation scores,
+    final forest dict: Device.forest_fit's arrays plus n_features)."""
+    from .device import get_device
+    dev = device if device is not None else get_device()
+    classes, y, jobs, seeds = cv_jobs(labs, grps, use_groups)
+    X = np.asarray(sigs, dtype=np.float64)
+    fits = dev.forest_fit(X, y, jobs, seeds=seeds, **RF_PARAMS)
+    scores = np.array([f['val_correct'] / float(f['n_val']) for f in fits[:5]])
+    fit = dict(fits[5], n_features=X.shape[1])
+    return classes, scores, fit
 
 
 def as_sklearn_estimator(fit, classes, n_samples):
@@ -104,21 +131,75 @@ def as_sklearn_estimator(fit, classes, n_samples):
     return m
 
 
-def write_models(models, classes_of, n_of, modelfile):
+def as_sklearn_forest(fit, classes):
+    """A scikit-learn RandomForestClassifier holding the fitted trees (what the reference pickles for -c RF): every estimator's
+    tree_ filled through Tree.__setstate__ with scikit-learn's node records."""
+    from sklearn.ensemble import RandomForestClassifier
+    from sklearn.tree import DecisionTreeClassifier
+    from sklearn.tree._tree import NODE_DTYPE, Tree
+    p = RF_PARAMS
+    d = int(fit['n_features'])
+    kw = dict(criterion='entropy', max_depth=p['max_depth'], max_features=p['max_features'], min_samples_leaf=p['min_samples_leaf'],
+              min_samples_split=p['min_samples_split'])
+    off = fit['tree_off']
+    estimators = []
+    for t in range(len(off) - 1):
+        a, b = int(off[t]), int(off[t + 1])
+        nodes = np.zeros(b - a, dtype=NODE_DTYPE)
+        nodes['left_child'], nodes['right_child'] = fit['left'][a:b], fit['right'][a:b]
+        nodes['feature'], nodes['threshold'] = fit['feature'][a:b], fit['threshold'][a:b]
+        nodes['impurity'], nodes['n_node_samples'] = fit['impurity'][a:b], fit['n_node_samples'][a:b]
+        nodes['weighted_n_node_samples'] = fit['weighted_n_node_samples'][a:b]
+        if 'missing_go_to_left' in NODE_DTYPE.names:
+            nodes['missing_go_to_left'] = 0
+        tree = Tree(d, np.array([2], dtype=np.intp), 1)
+        tree.__setstate__(dict(max_depth=_tree_depth(fit['left'][a:b], fit['right'][a:b]), node_count=b - a, nodes=nodes,
+                               values=np.ascontiguousarray(fit['value'][a:b], dtype=np.float64).reshape(b - a, 1, 2)))
+        est = DecisionTreeClassifier(**kw)
+        est.tree_ = tree
+        est.n_features_in_, est.n_outputs_, est.n_classes_ = d, 1, np.intp(2)
+        est.classes_ = np.array([0.0, 1.0])
+        est.max_features_ = p['max_features']
+        estimators.append(est)
+    rf = RandomForestClassifier(bootstrap=p['bootstrap'], n_estimators=len(estimators), **kw)
+    rf.estimator_ = DecisionTreeClassifier(**kw)
+    rf.estimators_ = estimators
+    rf.n_features_in_, rf.n_outputs_, rf.n_classes_ = d, 1, 2
+    rf.classes_ = np.array(classes)
+    return rf
+
+
+def _tree_depth(left, right):
+    depth = np.zeros(len(left), dtype=np.int64)
+    for v in range(len(left)):                                    # pre-order: a parent comes before its children
+        if left[v] >= 0:
+            depth[left[v]] = depth[right[v]] = depth[v] + 1
+    return int(depth.max()) if len(depth) else 0
+
+
+def write_models(models, classes_of, n_of, modelfile, classifier='NN'):
     try:
         import sklearn  # noqa: F401
         have_sklearn = True
     except ImportError:
         have_sklearn = False
     if have_sklearn:
-        out = {key: as_sklearn_estimator(fit, classes_of[key], n_of[key]) for key, fit in models.items()}
+        if classifier == 'RF':
+            out = {key: as_sklearn_forest(fit, classes_of[key]) for key, fit in models.items()}
+        else:
+            out = {key: as_sklearn_estimator(fit, classes_of[key], n_of[key]) for key, fit in models.items()}
         with open(modelfile, 'wb') as modfi:
             pickle.dump(out, modfi)
         return out
     arrays = {'__is_dict__': np.array([1])}
     for key, fit in models.items():
-        arrays[key + '.W1'], arrays[key + '.b1'] = fit['W1'], fit['b1']
-        arrays[key + '.W2'], arrays[key + '.b2'] = fit['W2'], np.array([fit['b2']])
+        if classifier == 'RF':
+            for name in ('tree_off', 'left', 'right', 'feature', 'threshold', 'value'):
+                arrays[key + '.' + name] = fit[name]
+            arrays[key + '.n_features'] = np.array([fit['n_features']])
+        else:
+            arrays[key + '.W1'], arrays[key + '.b1'] = fit['W1'], fit['b1']
+            arrays[key + '.W2'], arrays[key + '.b2'] = fit['W2'], np.array([fit['b2']])
         arrays[key + '.classes'] = np.array(classes_of[key])
     with open(modelfile, 'wb') as modfi:
         np.savez(modfi, **arrays)
@@ -129,37 +210,34 @@ def train_classifier(signals, groups, modelfile, classifier='NN', plot=False, de
     if plot:
         raise NotImplementedError('--plot_training is not supported (it raises NameError in the reference: the import '
                                   'of plotlib is commented out, train_model.py:3,:108)')
-    if classifier != 'NN':
+    if classifier not in ('NN', 'RF'):
         return _train_with_sklearn(signals, groups, modelfile, classifier)
+    fit_on_gpu = fit_nn_on_gpu if classifier == 'NN' else fit_rf_on_gpu
     models, classes_of, n_of = {}, {}, {}
     for twobase_model in signals:
         labs, sigs, grps = balanced_rows(signals[twobase_model], groups[twobase_model])
         print(labs[:10])
         print(sigs[:10])
         print(grps[:10])
-        classes, scores, fit = fit_nn_on_gpu(labs, sigs, grps, bool(groups), device=device)
+        classes, scores, fit = fit_on_gpu(labs, sigs, grps, bool(groups), device=device)
         print('%s %s model scores: %s' % (classifier, twobase_model, ','.join([str(s) for s in scores])))
         print('Cross validation accuracy: %0.2f (+/- %0.2f)' % (scores.mean(), scores.std() * 2))
         models[twobase_model], classes_of[twobase_model], n_of[twobase_model] = fit, classes, len(labs)
-    return write_models(models, classes_of, n_of, modelfile)
+    return write_models(models, classes_of, n_of, modelfile, classifier)
 
 
 def _train_with_sklearn(signals, groups, modelfile, classifier):
     try:
-        from sklearn.ensemble import RandomForestClassifier
         from sklearn.linear_model import LogisticRegression
         from sklearn.model_selection import GroupKFold, cross_val_score
         from sklearn.naive_bayes import GaussianNB
         from sklearn import svm
     except ImportError:
-        raise ImportError('--train -c %s needs scikit-learn for the fit (only NN is fitted on the GPU; the feature matrix '
+        raise ImportError('--train -c %s needs scikit-learn for the fit (only NN and RF are fitted on the GPU; the feature matrix '
                           'has been written to the .train file)' % classifier)
     models = {}
     for twobase_model in signals:
-        if classifier == 'RF':
-            model = RandomForestClassifier(bootstrap=True, criterion='entropy', max_depth=10, max_features=4,
-                                           min_samples_leaf=2, min_samples_split=3, n_estimators=50)
-        elif classifier == 'SVM':
+        if classifier == 'SVM':
             model = svm.SVC(kernel='rbf', probability=True)
         elif classifier == 'LR':
             model = LogisticRegression(solver='liblinear', penalty='l1')
