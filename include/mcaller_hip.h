@@ -421,6 +421,28 @@ int mc_forest_fit(mc_ctx *ctx, const mc_forest_params *prm, const double *X, con
                   int32_t *left, int32_t *right, int32_t *feature, double *threshold, double *value, double *impurity,
                   int32_t *n_node_samples, double *weighted_n_node_samples, int64_t *val_correct);
 
+/* ===== the RBF support-vector fit behind --train -c SVM (train_model.py:51-53,:62-65,:92-101): scikit-learn's SVC(kernel='rbf') =====
+ * solved as libsvm's Solver does without shrinking (tests/svm_fit_oracle.py restates it): n_jobs independent solves, a workgroup each
+ * (k6_svm_fit).  Job j solves on rows train_idx[train_off[j] .. train_off[j+1]) of X (n_samples x n_in, fp64), labels y in {0, 1},
+ * RBF width gamma[j]; the rows arrive in the order libsvm solves them, grouped by the sub-problem's sorted labels: the class of the
+ * job's first row is the solve's +1.  Output per training entry alpha >= 0 (the dual coefficient is +alpha on +1 rows, -alpha on -1
+ * rows), per job rho (the intercept is -rho), n_iter and status (0: converged, 1: stopped at the iteration cap).  The job's held-out
+ * rows val_idx[val_off[j] .. val_off[j+1]) get val_dec, k3_svm's decision value turned so that > 0 means class 0 (libsvm's
+ * dec * label[0]), and val_correct[j] counts the rows whose prediction (class 0 iff val_dec > 0) equals y.  Returns -12 on a parameter
+ * out of range: n_in outside 1..64, C or tol <= 0, a job with fewer than two rows or one class, more than 2^26 rows, or more than
+ * 4 GiB of device work memory. */
+typedef struct mc_svm_params {
+    double C;                      /* 1.0   (> 0)                                          */
+    double tol;                    /* 1e-3  (> 0): stop when Gmax + Gmax2 < tol             */
+    int64_t max_iter;              /* 0: max(10^7, 100 * rows) per job                     */
+} mc_svm_params;
+int mc_svm_fit(mc_ctx *ctx, const mc_svm_params *prm, const double *X, const uint8_t *y, int64_t n_samples, int32_t n_in, int32_t n_jobs,
+               const int64_t *train_off, const int32_t *train_idx, const int64_t *val_off, const int32_t *val_idx, const double *gamma,
+               double *alpha, double *rho, int64_t *n_iter, int32_t *status, int64_t *val_correct, double *val_dec);
+/* libsvm's sigmoid_train (the Platt parameters A, B of svm_binary_svc_probability) on the device, one workgroup with fixed-order sums:
+ * dec[n] decision values, y[n] = 0 for label +1 (libsvm's prior1: classes_[0]), 1 for -1. */
+int mc_svm_sigmoid_train(mc_ctx *ctx, const double *dec, const uint8_t *y, int64_t n, double *A, double *B);
+
 /* ===== the eventalign text parsed on the GPU (replaces the row ingest, extract_contexts.py:140-152, for streamed shards) =====
  * The host only moves bytes: mc_read_file_range preads a byte range into (pinned) memory with all cores;
  * mc_ctx_parse_begin sends it and enqueues the kernels that split it into lines, tokenise (str.split()'s ASCII whitespace,

@@ -75,6 +75,10 @@ class ForestParams(C.Structure):
                 ('min_samples_split', C.c_int32), ('min_samples_leaf', C.c_int32), ('bootstrap', C.c_int32)]
 
 
+class SvmParams(C.Structure):
+    _fields_ = [('C', C.c_double), ('tol', C.c_double), ('max_iter', C.c_int64)]
+
+
 class Params(C.Structure):
     _fields_ = [('k', C.c_int32), ('skip_thresh', C.c_int32), ('qual_thresh', C.c_double),
                 ('tail_contig', C.c_int32), ('score', C.c_int32),
@@ -188,6 +192,9 @@ def lib():
         L.mc_mlp_fit.argtypes = [C.c_void_p, C.POINTER(FitParams), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 13
         L.mc_forest_fit.argtypes = [C.c_void_p, C.POINTER(ForestParams), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 6 + \
             [C.c_int64, C.c_int64] + [C.c_void_p] * 10
+        L.mc_svm_fit.argtypes = [C.c_void_p, C.POINTER(SvmParams), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32] + \
+            [C.c_void_p] * 11
+        L.mc_svm_sigmoid_train.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.mc_calls_expand.argtypes = [C.POINTER(CallsView), C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mc_count_records.argtypes = [C.POINTER(CallsView), C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p,
                                        C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]

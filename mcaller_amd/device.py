@@ -534,6 +534,55 @@ class Device(object):
         return out
 
     @_serialized
+    def svm_fit(self, X, y, jobs, gammas, C=1.0, tol=1e-3, max_iter=0):
+        """Solve one RBF SVC dual per job on the GPU (mc_svm_fit: every job a workgroup of k6_svm_fit, libsvm's Solver).  jobs:
+        [(train_rows, validation_rows)] index arrays into X / y (y in {0, 1}); a job's training rows come in libsvm's solve order,
+        the class of its first row being the solve's +1.  -> per job a dict: alpha (per training row), rho, n_iter, status (1: the
+        iteration cap was reached), val_dec (> 0: class 0), val_correct, n_val."""
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.uint8)
+        if X.ndim != 2 or not 1 <= X.shape[1] <= 64 or len(y) != len(X):
+            raise ValueError('svm_fit: X must be rows x 1..64 features with a label per row, got %s and %d labels' % (X.shape, len(y)))
+        if not np.isfinite(X).all() or (y > 1).any():
+            raise ValueError('svm_fit: X must be finite and y in {0, 1}')
+        n, d = X.shape
+        nj = len(jobs)
+        g = np.ascontiguousarray(gammas, dtype=np.float64)
+        if nj < 1 or len(g) != nj or not (np.isfinite(g) & (g > 0)).all():
+            raise ValueError('svm_fit: a finite gamma > 0 per job is needed')
+        if not (C > 0 and np.isfinite(C) and tol > 0 and np.isfinite(tol)) or max_iter < 0:
+            raise ValueError('svm_fit: C and tol must be finite and > 0, max_iter >= 0')
+        tr = [np.ascontiguousarray(j[0], dtype=np.int32) for j in jobs]
+        va = [np.ascontiguousarray(j[1], dtype=np.int32) for j in jobs]
+        for a, b in zip(tr, va):
+            if len(a) < 2 or (a < 0).any() or (a >= n).any() or (b < 0).any() or (b >= n).any():
+                raise ValueError('svm_fit: every job needs two training rows, every index within the %d rows' % n)
+            if len(np.unique(y[a])) != 2:
+                raise ValueError('svm_fit: a job whose training rows are of one class')
+        tr_off = np.concatenate([[0], np.cumsum([len(a) for a in tr])]).astype(np.int64)
+        va_off = np.concatenate([[0], np.cumsum([len(a) for a in va])]).astype(np.int64)
+        tr_idx = np.ascontiguousarray(np.concatenate(tr))
+        va_idx = np.ascontiguousarray(np.concatenate(va + [np.zeros(1, np.int32)]))
+        alpha = np.zeros(tr_off[-1]); rho = np.zeros(nj); n_iter = np.zeros(nj, np.int64); status = np.zeros(nj, np.int32)
+        correct = np.zeros(nj, np.int64); dec = np.zeros(max(int(va_off[-1]), 1))
+        prm = _lib.SvmParams(float(C), float(tol), int(max_iter))
+        check(lib().mc_svm_fit(self._ctx, _lib.C.byref(prm), _ptr(X), _ptr(y), n, d, nj, _ptr(tr_off), _ptr(tr_idx), _ptr(va_off),
+                               _ptr(va_idx), _ptr(g), _ptr(alpha), _ptr(rho), _ptr(n_iter), _ptr(status), _ptr(correct), _ptr(dec)))
+        return [dict(alpha=alpha[tr_off[j]:tr_off[j + 1]].copy(), rho=float(rho[j]), n_iter=int(n_iter[j]), status=int(status[j]),
+                     val_dec=dec[va_off[j]:va_off[j + 1]].copy(), val_correct=int(correct[j]), n_val=len(va[j])) for j in range(nj)]
+
+    @_serialized
+    def svm_sigmoid_train(self, dec, y):
+        """libsvm's sigmoid_train on the GPU: the Platt parameters (A, B) of decision values dec with labels y (0: libsvm's +1)."""
+        dec = np.ascontiguousarray(dec, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.uint8)
+        if dec.ndim != 1 or len(dec) < 1 or len(y) != len(dec) or not np.isfinite(dec).all() or (y > 1).any():
+            raise ValueError('svm_sigmoid_train: finite decision values with a label in {0, 1} each are needed')
+        A, B = C.c_double(), C.c_double()
+        check(lib().mc_svm_sigmoid_train(self._ctx, _ptr(dec), _ptr(y), len(dec), C.byref(A), C.byref(B)))
+        return A.value, B.value
+
+    @_serialized
     def mlp_forward(self, X, submodel):
         if getattr(self, '_clf', 'mlp') != 'mlp':
             return self.classifier_forward(X, submodel)

@@ -261,13 +261,17 @@ def forest_from_arrays(tree_off, left, right, feature, threshold, value, n_featu
 
 def load_npz_weights(path, is_dict):
     """Neutral weight export (mcaller_amd/models/*.npz, or what `--train` writes without scikit-learn): arrays '<key>.W1' ...
-    '<key>.b2' of a perceptron, or '<key>.tree_off', '.left', '.right', '.feature', '.threshold', '.value' of a forest."""
+    '<key>.b2' of a perceptron, '<key>.tree_off', '.left', '.right', '.feature', '.threshold', '.value' of a forest, or '<key>.sv',
+    '.dual_coef', '.svm_params' (gamma, intercept, A, B) of an RBF SVC."""
     z = np.load(path)
     keys = sorted(set(n.split('.')[0] for n in z.files if not n.startswith('__')))
     models = {}
     for k in keys:
         classes = [str(c) for c in z[k + '.classes']] if k + '.classes' in z.files else None
-        if k + '.tree_off' in z.files:
+        if k + '.sv' in z.files:
+            gamma, intercept, A, B = (float(x) for x in z[k + '.svm_params'])
+            models[k] = SVMWeights(z[k + '.sv'], z[k + '.dual_coef'], gamma, intercept, A, B, classes)
+        elif k + '.tree_off' in z.files:
             n_feat = int(z[k + '.n_features'][0]) if k + '.n_features' in z.files else int(z[k + '.feature'].max()) + 1
             models[k] = forest_from_arrays(z[k + '.tree_off'], z[k + '.left'], z[k + '.right'], z[k + '.feature'], z[k + '.threshold'],
                                            z[k + '.value'], n_feat, classes)

@@ -12,8 +12,12 @@ importable (the estimators are filled with the fitted arrays, so the reference c
 
 `RF` (train_model.py:39-45, without `min_impurity_split`, which scikit-learn >= 1.0 rejects) is fitted on the GPU too: the same
 six jobs, 50 trees each, every tree a workgroup of one `mc_forest_fit` call (mcaller_amd/csrc/mc_forest_fit.hip); its model file
-is a pickle of {sub-model: RandomForestClassifier} or the neutral `.npz` of the trees.  SVM, LR and NBC are fitted by
-scikit-learn itself when it is installed.
+is a pickle of {sub-model: RandomForestClassifier} or the neutral `.npz` of the trees.
+
+`SVM` (train_model.py:51-53: SVC(kernel='rbf', probability=True) with scikit-learn's defaults) is fitted on the GPU as well: the five
+fold solves, the final solve and the five solves of its Platt scaling -- eleven SMO solves, a workgroup each of one `mc_svm_fit` call
+(mcaller_amd/csrc/mc_svm_fit.hip) -- then libsvm's sigmoid_train on the device.  Its model file is a pickle of {sub-model: SVC} or
+the neutral `.npz` of the support vectors.  LR and NBC are fitted by scikit-learn itself when it is installed.
 """
 import os
 import pickle
@@ -177,6 +181,150 @@ def _tree_depth(left, right):
     return int(depth.max()) if len(depth) else 0
 
 
+SVM_PARAMS = dict(C=1.0, tol=1e-3)                               # SVC's defaults (train_model.py:51-53)
+
+
+def svc_gamma(X):
+    """gamma='scale' as scikit-learn's SVC.fit resolves it on the rows it is given: 1 / (n_features * X.var()), 1.0 if X.var() is 0."""
+    var = X.var()
+    return 1.0 / (X.shape[1] * var) if var != 0 else 1.0
+
+
+def platt_seed(seed):
+    """The 31-bit seed of the Platt shuffle: the final job's cv_jobs seed modulo 2^31 - 1 (the range of the seed scikit-learn draws
+    for libsvm, RandomState.randint(2**31 - 1))."""
+    return int(seed % (2 ** 31 - 1))
+
+
+def libsvm_permutation(l, seed):
+    """svm_binary_svc_probability's shuffle: perm[i] <-> perm[i + bounded_rand_int(l - i)] for i = 0 .. l-1, with libsvm's generator
+    in scikit-learn (std::mt19937 seeded with `seed`, Lemire's bounded draw, newrand.h).  NumPy's MT19937 with its legacy seeding
+    is the same generator."""
+    mt = np.random.MT19937()
+    mt._legacy_seeding(int(seed))
+    raw, p = mt.random_raw(l + 16), 0
+    pick = np.zeros(l, dtype=np.int64)
+    i = 0
+    while i < l:
+        rng = np.arange(l - i, 0, -1, dtype=np.uint64)
+        if len(raw) - p < len(rng):
+            raw = np.concatenate([raw[p:], mt.random_raw(len(rng) + 16)])
+            p = 0
+        m = raw[p:p + len(rng)] * rng
+        bad = np.nonzero((m & 0xFFFFFFFF) < (np.uint64(1 << 32) % rng))[0]      # rejected: low word below 2^32 mod range
+        ok = len(rng) if len(bad) == 0 else int(bad[0])
+        pick[i:i + ok] = (m[:ok] >> np.uint64(32)).astype(np.int64)
+        i, p = i + ok, p + ok + (0 if len(bad) == 0 else 1)
+        if len(bad):                                                              # redraw this position until accepted
+            r = np.uint64(l - i)
+            while True:
+                if p >= len(raw):
+                    raw, p = mt.random_raw(64), 0
+                m1 = raw[p] * r
+                p += 1
+                if (m1 & np.uint64(0xFFFFFFFF)) >= np.uint64(1 << 32) % r:
+                    pick[i] = int(m1 >> np.uint64(32))
+                    i += 1
+                    break
+    perm = list(range(l))
+    for i in range(l):
+        j = i + int(pick[i])
+        perm[i], perm[j] = perm[j], perm[i]
+    return np.asarray(perm, dtype=np.int64)
+
+
+def svm_plan(X, y, jobs, seed):
+    """The solves of a sub-model: the five fold jobs and the final job (their training rows grouped classes_[0]
+    first, each fold's own gamma), then the Platt folds of the final fit: its rows grouped classes_[0] first (libsvm's +1), shuffled
+    by libsvm_permutation, fold f = positions [f l / 5, (f+1) l / 5); a fold whose complement holds both classes is solved on it
+    (classes_[1] first, the sub-problem's sorted labels), one that does not gets dec = +1 / -1 on its held-out rows.
+    -> dict(device=[(train, val)], gammas, cv=[device job of fold f, or None when its training rows hold one class], final (its
+    device job), order (its rows), perm, platt=[(device job or None, held-out positions, constant dec)], gamma)."""
+    group = lambda rows, first: np.concatenate([rows[y[rows] == first], rows[y[rows] != first]])     # noqa: E731
+    device, gammas, cv = [], [], []
+    for tr, va in jobs[:5]:
+        if len(np.unique(y[tr])) < 2:
+            cv.append(None)
+            continue
+        cv.append(len(device))
+        device.append((group(tr, 0), va))
+        gammas.append(svc_gamma(X[tr]))
+    order = group(np.arange(len(y)), 0)
+    gamma = svc_gamma(X)
+    final = len(device)
+    device.append((order, np.zeros(0, dtype=np.int64)))
+    gammas.append(gamma)
+    l = len(order)
+    perm = libsvm_permutation(l, platt_seed(seed))
+    platt = []
+    for f in range(5):
+        begin, end = f * l // 5, (f + 1) * l // 5
+        comp = order[np.concatenate([perm[:begin], perm[end:]])]
+        held = perm[begin:end]
+        labs = set(y[comp].tolist())
+        if len(labs) == 2:
+            platt.append((len(device), held, 0.0))
+            device.append((group(comp, 1), order[held]))
+            gammas.append(gamma)
+        else:
+            platt.append((None, held, 0.0 if not labs else (1.0 if labs == {0} else -1.0)))
+    return dict(device=device, gammas=gammas, cv=cv, final=final, order=order, perm=perm, platt=platt, gamma=gamma)
+
+
+def fit_svm_on_gpu(labs, sigs, grps, use_groups, device=None):
+    """`-c SVM`: a sub-model's eleven SMO solves in one mc_svm_fit call (k6_svm_fit), the Platt parameters by mc_svm_sigmoid_train.
+    -> (classes, cross-validation scores, final fit dict: the support vectors and what SVC keeps of them)."""
+    from .device import get_device
+    dev = device if device is not None else get_device()
+    classes, y, jobs, seeds = cv_jobs(labs, grps, use_groups)
+    X = np.asarray(sigs, dtype=np.float64)
+    plan = svm_plan(X, y, jobs, seeds[5])
+    fits = dev.svm_fit(X, y, plan['device'], plan['gammas'], **SVM_PARAMS)
+    scores = np.array([np.nan if j is None else fits[j]['val_correct'] / float(fits[j]['n_val']) for j in plan['cv']])
+    order = plan['order']
+    dec = np.zeros(len(order))
+    for job, held, const in plan['platt']:
+        dec[held] = fits[job]['val_dec'] if job is not None else const
+    A, B = dev.svm_sigmoid_train(dec, y[order])
+    final = fits[plan['final']]
+    alpha = final['alpha']
+    sv = alpha > 0
+    support = order[sv]
+    ysolve = np.where(y[order] == 0, 1.0, -1.0)
+    fit = dict(support=support.astype(np.int32), sv=X[support], dual_coef=(ysolve * alpha)[sv], intercept=-final['rho'],
+               gamma=plan['gamma'], probA=A, probB=B, n_support=np.array([(y[support] == 0).sum(), (y[support] == 1).sum()], np.int32),
+               n_iter=final['n_iter'], status=final['status'], n_samples=len(y), n_features=X.shape[1])
+    return classes, scores, fit
+
+
+def as_sklearn_svc(fit, classes):
+    """A scikit-learn SVC(kernel='rbf', probability=True) holding the fitted model: every attribute SVC.fit sets, with its dtype and
+    shape (the libsvm arrays `_dual_coef_`, `_intercept_` and their public, sign-flipped copies for two classes)."""
+    from sklearn.svm import SVC
+    m = SVC(kernel='rbf', probability=True)
+    m._sparse = False
+    m.n_features_in_ = int(fit['n_features'])
+    m.classes_ = np.array(classes)
+    m.class_weight_ = np.ones(2, dtype=np.float64)
+    m.shape_fit_ = (int(fit['n_samples']), int(fit['n_features']))
+    m._gamma = np.float64(fit['gamma'])
+    m.support_ = np.asarray(fit['support'], dtype=np.int32)
+    m.support_vectors_ = np.ascontiguousarray(fit['sv'], dtype=np.float64)
+    m._n_support = np.asarray(fit['n_support'], dtype=np.int32)
+    m.dual_coef_ = np.asarray(fit['dual_coef'], dtype=np.float64).reshape(1, -1)
+    m.intercept_ = np.array([fit['intercept']], dtype=np.float64)
+    m._probA = np.array([fit['probA']], dtype=np.float64)
+    m._probB = np.array([fit['probB']], dtype=np.float64)
+    m.fit_status_ = int(fit['status'])
+    m._num_iter = np.array([fit['n_iter']], dtype=np.int32)
+    m.n_iter_ = m._num_iter
+    m._intercept_ = m.intercept_.copy()
+    m._dual_coef_ = m.dual_coef_
+    m.intercept_ *= -1                                            # (SVC.fit: two classes flip the public sign)
+    m.dual_coef_ = -m.dual_coef_
+    return m
+
+
 def write_models(models, classes_of, n_of, modelfile, classifier='NN'):
     try:
         import sklearn  # noqa: F401
@@ -186,6 +334,8 @@ def write_models(models, classes_of, n_of, modelfile, classifier='NN'):
     if have_sklearn:
         if classifier == 'RF':
             out = {key: as_sklearn_forest(fit, classes_of[key]) for key, fit in models.items()}
+        elif classifier == 'SVM':
+            out = {key: as_sklearn_svc(fit, classes_of[key]) for key, fit in models.items()}
         else:
             out = {key: as_sklearn_estimator(fit, classes_of[key], n_of[key]) for key, fit in models.items()}
         with open(modelfile, 'wb') as modfi:
@@ -197,6 +347,9 @@ def write_models(models, classes_of, n_of, modelfile, classifier='NN'):
             for name in ('tree_off', 'left', 'right', 'feature', 'threshold', 'value'):
                 arrays[key + '.' + name] = fit[name]
             arrays[key + '.n_features'] = np.array([fit['n_features']])
+        elif classifier == 'SVM':
+            arrays[key + '.sv'], arrays[key + '.dual_coef'] = fit['sv'], fit['dual_coef']
+            arrays[key + '.svm_params'] = np.array([fit['gamma'], fit['intercept'], fit['probA'], fit['probB']], dtype=np.float64)
         else:
             arrays[key + '.W1'], arrays[key + '.b1'] = fit['W1'], fit['b1']
             arrays[key + '.W2'], arrays[key + '.b2'] = fit['W2'], np.array([fit['b2']])
@@ -210,9 +363,9 @@ def train_classifier(signals, groups, modelfile, classifier='NN', plot=False, de
     if plot:
         raise NotImplementedError('--plot_training is not supported (it raises NameError in the reference: the import '
                                   'of plotlib is commented out, train_model.py:3,:108)')
-    if classifier not in ('NN', 'RF'):
+    if classifier not in ('NN', 'RF', 'SVM'):
         return _train_with_sklearn(signals, groups, modelfile, classifier)
-    fit_on_gpu = fit_nn_on_gpu if classifier == 'NN' else fit_rf_on_gpu
+    fit_on_gpu = {'NN': fit_nn_on_gpu, 'RF': fit_rf_on_gpu, 'SVM': fit_svm_on_gpu}[classifier]
     models, classes_of, n_of = {}, {}, {}
     for twobase_model in signals:
         labs, sigs, grps = balanced_rows(signals[twobase_model], groups[twobase_model])
@@ -233,7 +386,7 @@ def _train_with_sklearn(signals, groups, modelfile, classifier):
         from sklearn.naive_bayes import GaussianNB
         from sklearn import svm
     except ImportError:
-        raise ImportError('--train -c %s needs scikit-learn for the fit (only NN and RF are fitted on the GPU; the feature matrix '
+        raise ImportError('--train -c %s needs scikit-learn for the fit (only NN, RF and SVM are fitted on the GPU; the feature matrix '
                           'has been written to the .train file)' % classifier)
     models = {}
     for twobase_model in signals:
