@@ -443,6 +443,42 @@ int mc_svm_fit(mc_ctx *ctx, const mc_svm_params *prm, const double *X, const uin
  * dec[n] decision values, y[n] = 0 for label +1 (libsvm's prior1: classes_[0]), 1 for -1. */
 int mc_svm_sigmoid_train(mc_ctx *ctx, const double *dec, const uint8_t *y, int64_t n, double *A, double *B);
 
+/* ===== the logistic-regression fit behind --train -c LR (train_model.py:55-57,:62-65,:92-101): scikit-learn's ======================
+ * LogisticRegression(solver='liblinear', penalty='l1') -- liblinear's solve_l1r_lr (newGLMNET; tests/lr_fit_oracle.py restates it):
+ * n_jobs independent fits, a workgroup each (k7_lr_fit).  Job j fits on rows train_idx[train_off[j] .. train_off[j+1]) of X
+ * (n_samples x n_in, fp64, finite), labels y in {0, 1}; the rows may come in any order (the fit takes classes_[0]'s first, stable,
+ * as liblinear's group_classes does) and must hold both classes.  The bias is a column of 1.0 penalised like the other weights
+ * (intercept_scaling = 1).  seeds[j]: the 31-bit seed of the fit's std::mt19937 (the QP shuffle), scikit-learn's
+ * RandomState.randint(2^31 - 1).  Output per job: coef[j*n_in .. +n_in) (toward class 1), intercept[j], n_iter[j] (Newton
+ * iterations) and status[j] (1: max_iter was reached, scikit-learn's ConvergenceWarning).  The held-out rows
+ * val_idx[val_off[j] .. val_off[j+1]) get val_dec (k3_simple's decision value: the dot product in index order, plus the
+ * intercept), and val_correct[j] counts those whose prediction (class 1 iff val_dec > 0) equals y.  Returns -12 on a parameter out
+ * of range: n_in outside 1..64, C or tol not finite and > 0, max_iter outside 1..10^6, a job with fewer than two rows or one
+ * class, an index outside the rows, more than 2^26 rows, or more than 4 GiB of device work memory. */
+typedef struct mc_lr_params {
+    double C;                      /* 1.0   (> 0)                                          */
+    double tol;                    /* 1e-4  (> 0): liblinear's eps before its pos/neg scaling */
+    int32_t max_iter;              /* 100   Newton iterations                              */
+    int32_t pad;
+} mc_lr_params;
+int mc_lr_fit(mc_ctx *ctx, const mc_lr_params *prm, const double *X, const uint8_t *y, int64_t n_samples, int32_t n_in, int32_t n_jobs,
+              const int64_t *train_off, const int32_t *train_idx, const int64_t *val_off, const int32_t *val_idx, const uint32_t *seeds,
+              double *coef, double *intercept, int32_t *n_iter, int32_t *status, int64_t *val_correct, double *val_dec);
+
+/* ===== the Gaussian naive Bayes fit behind --train -c NBC (train_model.py:59-60,:62-65,:92-101): scikit-learn's GaussianNB() =====
+ * n_jobs independent fits, a workgroup each (k7_nb_fit), on the same job layout as mc_lr_fit (both classes in every job).  Output per
+ * job: theta[j*2*n_in ..] and var[j*2*n_in ..] ([class][feature]: the means and the centred variances plus epsilon_, as GaussianNB
+ * stores var_), epsilon[j] = var_smoothing * the largest per-feature variance of the job's rows, class_count[2*j + c]; the held-out
+ * rows are predicted as k3_simple scores them (argmax of the joint log-likelihood, ties to class 0) and val_correct[j] counts the
+ * right ones.  Returns -12 on what mc_lr_fit refuses, on var_smoothing not finite and > 0, and on a job whose training rows are all
+ * equal (epsilon_ = 0; the other outputs are written then). */
+typedef struct mc_nb_params {
+    double var_smoothing;          /* 1e-9  (> 0)                                          */
+} mc_nb_params;
+int mc_nb_fit(mc_ctx *ctx, const mc_nb_params *prm, const double *X, const uint8_t *y, int64_t n_samples, int32_t n_in, int32_t n_jobs,
+              const int64_t *train_off, const int32_t *train_idx, const int64_t *val_off, const int32_t *val_idx, double *theta,
+              double *var, double *epsilon, int64_t *class_count, int64_t *val_correct);
+
 /* ===== the eventalign text parsed on the GPU (replaces the row ingest, extract_contexts.py:140-152, for streamed shards) =====
  * The host only moves bytes: mc_read_file_range preads a byte range into (pinned) memory with all cores;
  * mc_ctx_parse_begin sends it and enqueues the kernels that split it into lines, tokenise (str.split()'s ASCII whitespace,

@@ -79,6 +79,14 @@ class SvmParams(C.Structure):
     _fields_ = [('C', C.c_double), ('tol', C.c_double), ('max_iter', C.c_int64)]
 
 
+class LrParams(C.Structure):
+    _fields_ = [('C', C.c_double), ('tol', C.c_double), ('max_iter', C.c_int32), ('pad', C.c_int32)]
+
+
+class NbParams(C.Structure):
+    _fields_ = [('var_smoothing', C.c_double)]
+
+
 class Params(C.Structure):
     _fields_ = [('k', C.c_int32), ('skip_thresh', C.c_int32), ('qual_thresh', C.c_double),
                 ('tail_contig', C.c_int32), ('score', C.c_int32),
@@ -195,6 +203,8 @@ def lib():
         L.mc_svm_fit.argtypes = [C.c_void_p, C.POINTER(SvmParams), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32] + \
             [C.c_void_p] * 11
         L.mc_svm_sigmoid_train.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.mc_lr_fit.argtypes = [C.c_void_p, C.POINTER(LrParams), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 11
+        L.mc_nb_fit.argtypes = [C.c_void_p, C.POINTER(NbParams), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 9
         L.mc_calls_expand.argtypes = [C.POINTER(CallsView), C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mc_count_records.argtypes = [C.POINTER(CallsView), C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p,
                                        C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]

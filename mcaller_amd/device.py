@@ -571,6 +571,72 @@ class Device(object):
         return [dict(alpha=alpha[tr_off[j]:tr_off[j + 1]].copy(), rho=float(rho[j]), n_iter=int(n_iter[j]), status=int(status[j]),
                      val_dec=dec[va_off[j]:va_off[j + 1]].copy(), val_correct=int(correct[j]), n_val=len(va[j])) for j in range(nj)]
 
+    @staticmethod
+    def _simple_jobs(who, X, y, jobs, need_spread):
+        """Validate and flatten a fit's jobs like svm_fit -> (X, y, tr, va, tr_off, va_off, tr_idx, va_idx)."""
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.uint8)
+        if X.ndim != 2 or not 1 <= X.shape[1] <= 64 or len(y) != len(X):
+            raise ValueError('%s: X must be rows x 1..64 features with a label per row, got %s and %d labels' % (who, X.shape, len(y)))
+        if not np.isfinite(X).all() or (y > 1).any():
+            raise ValueError('%s: X must be finite and y in {0, 1}' % who)
+        n = len(X)
+        if len(jobs) < 1:
+            raise ValueError('%s: at least one job is needed' % who)
+        tr = [np.ascontiguousarray(j[0], dtype=np.int32) for j in jobs]
+        va = [np.ascontiguousarray(j[1], dtype=np.int32) for j in jobs]
+        for a, b in zip(tr, va):
+            if len(a) < 2 or (a < 0).any() or (a >= n).any() or (b < 0).any() or (b >= n).any():
+                raise ValueError('%s: every job needs two training rows, every index within the %d rows' % (who, n))
+            if len(np.unique(y[a])) != 2:
+                raise ValueError('%s: a job whose training rows are of one class' % who)
+            if need_spread and np.ptp(X[a], axis=0).max() == 0:
+                raise ValueError('%s: a job whose training rows are all equal (epsilon_ = 0: every variance would be 0)' % who)
+        tr_off = np.concatenate([[0], np.cumsum([len(a) for a in tr])]).astype(np.int64)
+        va_off = np.concatenate([[0], np.cumsum([len(a) for a in va])]).astype(np.int64)
+        return X, y, tr, va, tr_off, va_off, np.ascontiguousarray(np.concatenate(tr)), np.ascontiguousarray(np.concatenate(va + [np.zeros(1, np.int32)]))
+
+    @_serialized
+    def lr_fit(self, X, y, jobs, seeds, C=1.0, tol=1e-4, max_iter=100):
+        """Fit one L1 logistic regression per job on the GPU (mc_lr_fit: every job a workgroup of k7_lr_fit, liblinear's
+        solve_l1r_lr).  jobs: [(train_rows, validation_rows)] index arrays into X / y (y in {0, 1}, both classes in every job's
+        training rows); seeds: a 31-bit liblinear seed per job.  -> per job a dict: coef [d] (toward class 1), intercept, n_iter
+        (Newton iterations), status (1: max_iter was reached), val_dec, val_correct, n_val."""
+        X, y, tr, va, tr_off, va_off, tr_idx, va_idx = self._simple_jobs('lr_fit', X, y, jobs, False)
+        n, d = X.shape
+        nj = len(jobs)
+        sd = np.asarray(seeds, dtype=np.int64)
+        if len(sd) != nj or (sd < 0).any() or (sd >= 2 ** 32).any():
+            raise ValueError('lr_fit: one seed in 0 .. 2^32 - 1 per job is needed')
+        if not (C > 0 and np.isfinite(C) and tol > 0 and np.isfinite(tol)) or not 1 <= max_iter <= 10 ** 6:
+            raise ValueError('lr_fit: C and tol must be finite and > 0, max_iter in 1 .. 10^6')
+        sd = np.ascontiguousarray(sd, dtype=np.uint32)
+        coef = np.zeros((nj, d)); intercept = np.zeros(nj); n_iter = np.zeros(nj, np.int32); status = np.zeros(nj, np.int32)
+        correct = np.zeros(nj, np.int64); dec = np.zeros(max(int(va_off[-1]), 1))
+        prm = _lib.LrParams(float(C), float(tol), int(max_iter), 0)
+        check(lib().mc_lr_fit(self._ctx, _lib.C.byref(prm), _ptr(X), _ptr(y), n, d, nj, _ptr(tr_off), _ptr(tr_idx), _ptr(va_off),
+                              _ptr(va_idx), _ptr(sd), _ptr(coef), _ptr(intercept), _ptr(n_iter), _ptr(status), _ptr(correct), _ptr(dec)))
+        return [dict(coef=coef[j].copy(), intercept=float(intercept[j]), n_iter=int(n_iter[j]), status=int(status[j]),
+                     val_dec=dec[va_off[j]:va_off[j + 1]].copy(), val_correct=int(correct[j]), n_val=len(va[j])) for j in range(nj)]
+
+    @_serialized
+    def nb_fit(self, X, y, jobs, var_smoothing=1e-9):
+        """Fit one Gaussian naive Bayes per job on the GPU (mc_nb_fit: every job a workgroup of k7_nb_fit, GaussianNB's fit).
+        jobs as lr_fit's (both classes in every job's training rows, not all of them equal).  -> per job a dict: theta [2, d],
+        var [2, d] (smoothing included), epsilon, class_count [2], val_correct, n_val."""
+        X, y, tr, va, tr_off, va_off, tr_idx, va_idx = self._simple_jobs('nb_fit', X, y, jobs, True)
+        n, d = X.shape
+        nj = len(jobs)
+        if not (var_smoothing > 0 and np.isfinite(var_smoothing)):
+            raise ValueError('nb_fit: var_smoothing must be finite and > 0')
+        theta = np.zeros((nj, 2, d)); var = np.zeros((nj, 2, d)); eps = np.zeros(nj); count = np.zeros((nj, 2), np.int64)
+        correct = np.zeros(nj, np.int64)
+        prm = _lib.NbParams(float(var_smoothing))
+        check(lib().mc_nb_fit(self._ctx, _lib.C.byref(prm), _ptr(X), _ptr(y), n, d, nj, _ptr(tr_off), _ptr(tr_idx), _ptr(va_off),
+                              _ptr(va_idx), _ptr(theta), _ptr(var), _ptr(eps), _ptr(count), _ptr(correct)))
+        return [dict(theta=theta[j].copy(), var=var[j].copy(), epsilon=float(eps[j]), class_count=count[j].copy(),
+                     val_correct=int(correct[j]), n_val=len(va[j])) for j in range(nj)]
+
     @_serialized
     def svm_sigmoid_train(self, dec, y):
         """libsvm's sigmoid_train on the GPU: the Platt parameters (A, B) of decision values dec with labels y (0: libsvm's +1)."""

@@ -262,7 +262,8 @@ def forest_from_arrays(tree_off, left, right, feature, threshold, value, n_featu
 def load_npz_weights(path, is_dict):
     """Neutral weight export (mcaller_amd/models/*.npz, or what `--train` writes without scikit-learn): arrays '<key>.W1' ...
     '<key>.b2' of a perceptron, '<key>.tree_off', '.left', '.right', '.feature', '.threshold', '.value' of a forest, or '<key>.sv',
-    '.dual_coef', '.svm_params' (gamma, intercept, A, B) of an RBF SVC."""
+    '.dual_coef', '.svm_params' (gamma, intercept, A, B) of an RBF SVC, '<key>.lr_coef', '.lr_intercept' of a logistic regression,
+    or '<key>.nb_theta', '.nb_var', '.nb_prior' of a Gaussian naive Bayes."""
     z = np.load(path)
     keys = sorted(set(n.split('.')[0] for n in z.files if not n.startswith('__')))
     models = {}
@@ -271,6 +272,10 @@ def load_npz_weights(path, is_dict):
         if k + '.sv' in z.files:
             gamma, intercept, A, B = (float(x) for x in z[k + '.svm_params'])
             models[k] = SVMWeights(z[k + '.sv'], z[k + '.dual_coef'], gamma, intercept, A, B, classes)
+        elif k + '.lr_coef' in z.files:
+            models[k] = LogisticWeights(z[k + '.lr_coef'], z[k + '.lr_intercept'], classes)
+        elif k + '.nb_theta' in z.files:
+            models[k] = GaussianNBWeights(z[k + '.nb_theta'], z[k + '.nb_var'], z[k + '.nb_prior'], classes)
         elif k + '.tree_off' in z.files:
             n_feat = int(z[k + '.n_features'][0]) if k + '.n_features' in z.files else int(z[k + '.feature'].max()) + 1
             models[k] = forest_from_arrays(z[k + '.tree_off'], z[k + '.left'], z[k + '.right'], z[k + '.feature'], z[k + '.threshold'],

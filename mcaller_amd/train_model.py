@@ -17,7 +17,12 @@ is a pickle of {sub-model: RandomForestClassifier} or the neutral `.npz` of the 
 `SVM` (train_model.py:51-53: SVC(kernel='rbf', probability=True) with scikit-learn's defaults) is fitted on the GPU as well: the five
 fold solves, the final solve and the five solves of its Platt scaling -- eleven SMO solves, a workgroup each of one `mc_svm_fit` call
 (mcaller_amd/csrc/mc_svm_fit.hip) -- then libsvm's sigmoid_train on the device.  Its model file is a pickle of {sub-model: SVC} or
-the neutral `.npz` of the support vectors.  LR and NBC are fitted by scikit-learn itself when it is installed.
+the neutral `.npz` of the support vectors.
+
+`LR` (train_model.py:55-57: LogisticRegression(solver='liblinear', penalty='l1')) and `NBC` (:59-60: GaussianNB()) are fitted on the
+GPU too: the six jobs of a sub-model, a workgroup each of one `mc_lr_fit` (liblinear's solve_l1r_lr, each fit seeded like scikit-learn's
+from its cv_jobs seed) or `mc_nb_fit` call (mcaller_amd/csrc/mc_simple_fit.hip).  Their model files are a pickle of
+{sub-model: LogisticRegression | GaussianNB} or the neutral `.npz` of the weights.  No classifier needs scikit-learn to be fitted.
 """
 import os
 import pickle
@@ -196,36 +201,53 @@ def platt_seed(seed):
     return int(seed % (2 ** 31 - 1))
 
 
+class MT19937Draws(object):
+    """The generator libsvm and liblinear use in scikit-learn (newrand.h): std::mt19937 seeded once (set_seed), and
+    bounded_rand_int(range) by Lemire's method -- a draw whose low word x * range mod 2^32 lies below 2^32 mod range is drawn
+    again.  NumPy's MT19937 with its legacy seeding is the same generator.  Draws are taken in order from one stream."""
+
+    def __init__(self, seed):
+        self._mt = np.random.MT19937()
+        self._mt._legacy_seeding(int(seed))
+        self._raw, self._p = np.zeros(0, dtype=np.uint64), 0
+
+    def _have(self, k):
+        if len(self._raw) - self._p < k:
+            self._raw, self._p = np.concatenate([self._raw[self._p:], self._mt.random_raw(k + 16)]), 0
+
+    def draws(self, ranges):
+        """bounded_rand_int(r) for every r of `ranges`, one after another."""
+        ranges = np.asarray(ranges, dtype=np.uint64)
+        out = np.zeros(len(ranges), dtype=np.int64)
+        i = 0
+        while i < len(ranges):
+            rng = ranges[i:]
+            self._have(len(rng))
+            m = self._raw[self._p:self._p + len(rng)] * rng
+            bad = np.nonzero((m & 0xFFFFFFFF) < (np.uint64(1 << 32) % rng))[0]      # rejected: low word below 2^32 mod range
+            ok = len(rng) if len(bad) == 0 else int(bad[0])
+            out[i:i + ok] = (m[:ok] >> np.uint64(32)).astype(np.int64)
+            i, self._p = i + ok, self._p + ok
+            if len(bad):                                                              # redraw this position until accepted
+                self._p += 1
+                r = ranges[i]
+                while True:
+                    self._have(1)
+                    m1 = self._raw[self._p] * r
+                    self._p += 1
+                    if (m1 & np.uint64(0xFFFFFFFF)) >= np.uint64(1 << 32) % r:
+                        out[i] = int(m1 >> np.uint64(32))
+                        i += 1
+                        break
+        return out
+
+    def draw(self, r):
+        return int(self.draws([r])[0])
+
+
 def libsvm_permutation(l, seed):
-    """svm_binary_svc_probability's shuffle: perm[i] <-> perm[i + bounded_rand_int(l - i)] for i = 0 .. l-1, with libsvm's generator
-    in scikit-learn (std::mt19937 seeded with `seed`, Lemire's bounded draw, newrand.h).  NumPy's MT19937 with its legacy seeding
-    is the same generator."""
-    mt = np.random.MT19937()
-    mt._legacy_seeding(int(seed))
-    raw, p = mt.random_raw(l + 16), 0
-    pick = np.zeros(l, dtype=np.int64)
-    i = 0
-    while i < l:
-        rng = np.arange(l - i, 0, -1, dtype=np.uint64)
-        if len(raw) - p < len(rng):
-            raw = np.concatenate([raw[p:], mt.random_raw(len(rng) + 16)])
-            p = 0
-        m = raw[p:p + len(rng)] * rng
-        bad = np.nonzero((m & 0xFFFFFFFF) < (np.uint64(1 << 32) % rng))[0]      # rejected: low word below 2^32 mod range
-        ok = len(rng) if len(bad) == 0 else int(bad[0])
-        pick[i:i + ok] = (m[:ok] >> np.uint64(32)).astype(np.int64)
-        i, p = i + ok, p + ok + (0 if len(bad) == 0 else 1)
-        if len(bad):                                                              # redraw this position until accepted
-            r = np.uint64(l - i)
-            while True:
-                if p >= len(raw):
-                    raw, p = mt.random_raw(64), 0
-                m1 = raw[p] * r
-                p += 1
-                if (m1 & np.uint64(0xFFFFFFFF)) >= np.uint64(1 << 32) % r:
-                    pick[i] = int(m1 >> np.uint64(32))
-                    i += 1
-                    break
+    """svm_binary_svc_probability's shuffle: perm[i] <-> perm[i + bounded_rand_int(l - i)] for i = 0 .. l-1 (MT19937Draws)."""
+    pick = MT19937Draws(seed).draws(np.arange(l, 0, -1, dtype=np.uint64))
     perm = list(range(l))
     for i in range(l):
         j = i + int(pick[i])
@@ -325,6 +347,79 @@ def as_sklearn_svc(fit, classes):
     return m
 
 
+LR_PARAMS = dict(C=1.0, tol=1e-4, max_iter=100)                  # LogisticRegression(solver='liblinear', penalty='l1') (train_model.py:55-57)
+
+
+def fit_lr_on_gpu(labs, sigs, grps, use_groups, device=None):
+    """`-c LR`: a sub-model's six liblinear fits in one mc_lr_fit call (k7_lr_fit), each seeded with its cv_jobs seed modulo
+    2^31 - 1 (platt_seed's rule, the range of scikit-learn's draw).  A fold whose training rows hold one class scores nan, as
+    cross_val_score gives for liblinear's refusal.  -> (classes, cross-validation scores, final fit dict: coef, intercept, n_iter,
+    status, n_features)."""
+    from .device import get_device
+    dev = device if device is not None else get_device()
+    classes, y, jobs, seeds = cv_jobs(labs, grps, use_groups)
+    X = np.asarray(sigs, dtype=np.float64)
+    run = [j for j, (tr, _) in enumerate(jobs) if len(np.unique(y[tr])) == 2]
+    fits = dict(zip(run, dev.lr_fit(X, y, [jobs[j] for j in run], [platt_seed(seeds[j]) for j in run], **LR_PARAMS)))
+    scores = np.array([fits[f]['val_correct'] / float(fits[f]['n_val']) if f in fits else np.nan for f in range(5)])
+    final = fits[5]
+    fit = dict(coef=final['coef'], intercept=final['intercept'], n_iter=final['n_iter'], status=final['status'], n_features=X.shape[1])
+    return classes, scores, fit
+
+
+NB_PARAMS = dict(var_smoothing=1e-9)                              # GaussianNB() (train_model.py:59-60)
+
+
+def fit_nb_on_gpu(labs, sigs, grps, use_groups, device=None):
+    """`-c NBC`: a sub-model's six GaussianNB fits in one mc_nb_fit call (k7_nb_fit).  A fold whose training rows hold one class
+    predicts that class everywhere, as the fitted GaussianNB would: its score is the share of held-out rows in it.  -> (classes,
+    cross-validation scores, final fit dict: theta, var, epsilon, class_count, class_prior, n_features)."""
+    from .device import get_device
+    dev = device if device is not None else get_device()
+    classes, y, jobs, seeds = cv_jobs(labs, grps, use_groups)
+    X = np.asarray(sigs, dtype=np.float64)
+    run = [j for j, (tr, _) in enumerate(jobs) if len(np.unique(y[tr])) == 2]
+    fits = dict(zip(run, dev.nb_fit(X, y, [jobs[j] for j in run], **NB_PARAMS)))
+    scores = []
+    for f, (tr, va) in enumerate(jobs[:5]):
+        if f in fits:
+            scores.append(fits[f]['val_correct'] / float(fits[f]['n_val']))
+        else:
+            scores.append(float(np.mean(y[va] == y[tr[0]])))
+    final = fits[5]
+    count = final['class_count'].astype(np.float64)
+    fit = dict(theta=final['theta'], var=final['var'], epsilon=final['epsilon'], class_count=count, class_prior=count / count.sum(),
+               n_features=X.shape[1])
+    return classes, np.array(scores), fit
+
+
+def as_sklearn_logistic(fit, classes):
+    """A scikit-learn LogisticRegression(solver='liblinear', penalty='l1') holding the fitted weights (what the reference pickles
+    for -c LR).  multi_class stays at its default, so predict_proba is expit(decision_function), the form model_io scores."""
+    from sklearn.linear_model import LogisticRegression
+    m = LogisticRegression(solver='liblinear', penalty='l1')
+    m.n_features_in_ = int(fit['n_features'])
+    m.classes_ = np.array(classes)
+    m.coef_ = np.asarray(fit['coef'], dtype=np.float64).reshape(1, -1)
+    m.intercept_ = np.array([fit['intercept']], dtype=np.float64).reshape(1)
+    m.n_iter_ = np.array([fit['n_iter']], dtype=np.int32)
+    return m
+
+
+def as_sklearn_gnb(fit, classes):
+    """A scikit-learn GaussianNB holding the fitted means, variances (smoothing included) and priors (-c NBC)."""
+    from sklearn.naive_bayes import GaussianNB
+    m = GaussianNB()
+    m.n_features_in_ = int(fit['n_features'])
+    m.classes_ = np.array(classes)
+    m.theta_ = np.asarray(fit['theta'], dtype=np.float64).reshape(2, -1)
+    m.var_ = np.asarray(fit['var'], dtype=np.float64).reshape(2, -1)
+    m.class_count_ = np.asarray(fit['class_count'], dtype=np.float64)
+    m.class_prior_ = np.asarray(fit['class_prior'], dtype=np.float64)
+    m.epsilon_ = float(fit['epsilon'])
+    return m
+
+
 def write_models(models, classes_of, n_of, modelfile, classifier='NN'):
     try:
         import sklearn  # noqa: F401
@@ -336,6 +431,10 @@ def write_models(models, classes_of, n_of, modelfile, classifier='NN'):
             out = {key: as_sklearn_forest(fit, classes_of[key]) for key, fit in models.items()}
         elif classifier == 'SVM':
             out = {key: as_sklearn_svc(fit, classes_of[key]) for key, fit in models.items()}
+        elif classifier == 'LR':
+            out = {key: as_sklearn_logistic(fit, classes_of[key]) for key, fit in models.items()}
+        elif classifier == 'NBC':
+            out = {key: as_sklearn_gnb(fit, classes_of[key]) for key, fit in models.items()}
         else:
             out = {key: as_sklearn_estimator(fit, classes_of[key], n_of[key]) for key, fit in models.items()}
         with open(modelfile, 'wb') as modfi:
@@ -350,6 +449,12 @@ def write_models(models, classes_of, n_of, modelfile, classifier='NN'):
         elif classifier == 'SVM':
             arrays[key + '.sv'], arrays[key + '.dual_coef'] = fit['sv'], fit['dual_coef']
             arrays[key + '.svm_params'] = np.array([fit['gamma'], fit['intercept'], fit['probA'], fit['probB']], dtype=np.float64)
+        elif classifier == 'LR':
+            arrays[key + '.lr_coef'] = np.asarray(fit['coef'], dtype=np.float64)
+            arrays[key + '.lr_intercept'] = np.array([fit['intercept']], dtype=np.float64)
+        elif classifier == 'NBC':
+            arrays[key + '.nb_theta'], arrays[key + '.nb_var'] = fit['theta'], fit['var']
+            arrays[key + '.nb_prior'] = fit['class_prior']
         else:
             arrays[key + '.W1'], arrays[key + '.b1'] = fit['W1'], fit['b1']
             arrays[key + '.W2'], arrays[key + '.b2'] = fit['W2'], np.array([fit['b2']])
@@ -363,9 +468,9 @@ def train_classifier(signals, groups, modelfile, classifier='NN', plot=False, de
     if plot:
         raise NotImplementedError('--plot_training is not supported (it raises NameError in the reference: the import '
                                   'of plotlib is commented out, train_model.py:3,:108)')
-    if classifier not in ('NN', 'RF', 'SVM'):
-        return _train_with_sklearn(signals, groups, modelfile, classifier)
-    fit_on_gpu = {'NN': fit_nn_on_gpu, 'RF': fit_rf_on_gpu, 'SVM': fit_svm_on_gpu}[classifier]
+    fit_on_gpu = {'NN': fit_nn_on_gpu, 'RF': fit_rf_on_gpu, 'SVM': fit_svm_on_gpu, 'LR': fit_lr_on_gpu, 'NBC': fit_nb_on_gpu}.get(classifier)
+    if fit_on_gpu is None:
+        raise ValueError('unknown classifier ' + str(classifier))
     models, classes_of, n_of = {}, {}, {}
     for twobase_model in signals:
         labs, sigs, grps = balanced_rows(signals[twobase_model], groups[twobase_model])
@@ -377,36 +482,3 @@ def train_classifier(signals, groups, modelfile, classifier='NN', plot=False, de
         print('Cross validation accuracy: %0.2f (+/- %0.2f)' % (scores.mean(), scores.std() * 2))
         models[twobase_model], classes_of[twobase_model], n_of[twobase_model] = fit, classes, len(labs)
     return write_models(models, classes_of, n_of, modelfile, classifier)
-
-
-def _train_with_sklearn(signals, groups, modelfile, classifier):
-    try:
-        from sklearn.linear_model import LogisticRegression
-        from sklearn.model_selection import GroupKFold, cross_val_score
-        from sklearn.naive_bayes import GaussianNB
-        from sklearn import svm
-    except ImportError:
-        raise ImportError('--train -c %s needs scikit-learn for the fit (only NN, RF and SVM are fitted on the GPU; the feature matrix '
-                          'has been written to the .train file)' % classifier)
-    models = {}
-    for twobase_model in signals:
-        if classifier == 'SVM':
-            model = svm.SVC(kernel='rbf', probability=True)
-        elif classifier == 'LR':
-            model = LogisticRegression(solver='liblinear', penalty='l1')
-        elif classifier == 'NBC':
-            model = GaussianNB()
-        else:
-            raise ValueError('unknown classifier ' + str(classifier))
-        labs, sigs, grps = balanced_rows(signals[twobase_model], groups[twobase_model])
-        print(labs[:10])
-        print(sigs[:10])
-        print(grps[:10])
-        scores = cross_val_score(model, sigs, labs, cv=GroupKFold(n_splits=5) if groups else 5, groups=grps)
-        print('%s %s model scores: %s' % (classifier, twobase_model, ','.join([str(s) for s in scores])))
-        print('Cross validation accuracy: %0.2f (+/- %0.2f)' % (scores.mean(), scores.std() * 2))
-        model.fit(sigs, labs)
-        models[twobase_model] = model
-    with open(modelfile, 'wb') as modfi:
-        pickle.dump(models, modfi)
-    return models
