@@ -16,20 +16,11 @@
 //   * nodes are written in level order with child links; the host renumbers them into scikit-learn's depth-first pre-order.
 // A second kernel (k5_forest_val) scores each job's validation rows with its trees in tree order, as k3_forest adds them.
 // Work arrays are in global memory, per workgroup; trees are grown in batches that fit MCALLER_FOREST_MEM_MB (default 4096).
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cmath>
+// The entry points' allocations, transfers and job checks, FitJob, splitmix64 and wave_sum: mc_fit.h.
 #include <cstdlib>
-#include <cstring>
 #include <numeric>
-#include <vector>
 
-#include "../../include/mcaller_hip.h"
-
-void mc_set_error(const char *fmt, ...);
-int mc_internal_device(const mc_ctx *c);
-hipStream_t mc_internal_stream(const mc_ctx *c);
+#include "mc_fit.h"
 
 namespace {
 
@@ -60,17 +51,13 @@ struct FNode {                          // output, level order
     int32_t left, right, feature, n_samples;
     double threshold, v0, v1, impurity, weighted;
 };
-struct FJob {
-    int64_t tr_off, n_tr, va_off, n_va;
-    uint64_t seed;
-};
 
 struct FitArgs {
     const float *Xt;                    // [d][n]
     const int32_t *order;               // [d][n] rows sorted by Xt[f]
     const uint8_t *y;
     const int32_t *tr_idx;
-    const FJob *jobs;
+    const FitJob *jobs;
     const double *G;
     int32_t d, n_trees, max_depth, max_features, mss, msl, bootstrap;
     int64_t n;
@@ -88,14 +75,6 @@ struct FitArgs {
     int32_t *n_nodes;                   // [batch]
     int *failed;
 };
-
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-    x += GOLD;
-    uint64_t z = x;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 // exclusive prefix sum of v over the workgroup; every thread calls it; *total: the sum
 __device__ __forceinline__ int block_scan(int v, int *tmp, int *total) {
@@ -127,7 +106,7 @@ __global__ __launch_bounds__(BT) void k5_forest_fit(FitArgs A) {
     const int64_t slot = blockIdx.x, g = A.g0 + slot;
     if (g >= A.n_total) return;
     const int job = (int)(g / A.n_trees), t = (int)(g % A.n_trees);
-    const FJob J = A.jobs[job];
+    const FitJob J = A.jobs[job];
     const int d = A.d;
     const int64_t n = A.n, cap_s = A.cap_s, cap_lvl = A.cap_lvl;
     int32_t *wy = A.wy + slot * n;
@@ -389,7 +368,7 @@ struct ValArgs {
     const double *X;
     const uint8_t *y;
     const int32_t *va_idx;
-    const FJob *jobs;
+    const FitJob *jobs;
     const int64_t *tree_node_off;       // [n_jobs * n_trees + 1], absolute
     const int32_t *left, *right, *feature;
     const double *threshold, *value;
@@ -400,7 +379,7 @@ struct ValArgs {
 // a lane per validation row of a job (grid.y: job): P_c = sum over trees, in tree order, of v_c / ((-0.0 + v0) + v1), over n_trees
 __global__ __launch_bounds__(256) void k5_forest_val(ValArgs A) {
     const int job = blockIdx.y;
-    const FJob J = A.jobs[job];
+    const FitJob J = A.jobs[job];
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     int ok = 0;
     if (i < J.n_va) {
@@ -427,21 +406,6 @@ __global__ __launch_bounds__(256) void k5_forest_val(ValArgs A) {
     const unsigned long long m = __ballot(ok);
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(&A.val_correct[job], (unsigned long long)__popcll(m));
 }
-
-struct Pool {
-    std::vector<void *> p;
-    ~Pool() { for (void *q : p) (void)hipFree(q); }
-    template <typename T>
-    T *get(size_t n) {
-        void *q = nullptr;
-        if (hipMalloc(&q, std::max<size_t>(n * sizeof(T), 256)) != hipSuccess) {
-            mc_set_error("mc_forest_fit: hipMalloc of %zu bytes failed", n * sizeof(T));
-            return nullptr;
-        }
-        p.push_back(q);
-        return (T *)q;
-    }
-};
 
 }  // namespace
 
@@ -470,30 +434,19 @@ extern "C" int mc_forest_fit(mc_ctx *c, const mc_forest_params *P, const double 
         mc_set_error("mc_forest_fit: %lld samples, %d jobs out of range", (long long)n_samples, n_jobs);
         return -12;
     }
-    int64_t max_tr = 0, need_nodes = 0;
+    if (int rc = check_jobs("mc_forest_fit", X, y, n_samples, d, n_jobs, train_off, train_idx, val_off, val_idx, (int64_t)1 << 28, 1, false, true, nullptr))
+        return rc;
+    int64_t max_tr = 0, max_va = 0, need_nodes = 0;
     const int64_t depth_nodes = ((int64_t)2 << P->max_depth) - 1;
     for (int j = 0; j < n_jobs; ++j) {
         const int64_t ntr = train_off[j + 1] - train_off[j];
-        if (train_off[j] < 0 || ntr < 1 || val_off[j] < 0 || val_off[j + 1] < val_off[j] || ntr > ((int64_t)1 << 28)) {
-            mc_set_error("mc_forest_fit: bad offsets for job %d (every job needs training rows)", j);
-            return -12;
-        }
-        for (int64_t i = train_off[j]; i < train_off[j + 1]; ++i)
-            if (train_idx[i] < 0 || train_idx[i] >= n_samples) { mc_set_error("mc_forest_fit: row index out of range"); return -12; }
-        for (int64_t i = val_off[j]; i < val_off[j + 1]; ++i)
-            if (val_idx[i] < 0 || val_idx[i] >= n_samples) { mc_set_error("mc_forest_fit: row index out of range"); return -12; }
         max_tr = std::max(max_tr, ntr);
+        max_va = std::max(max_va, val_off[j + 1] - val_off[j]);
         need_nodes += (int64_t)P->n_trees * std::min(depth_nodes, 2 * ntr - 1);
     }
     if (n_G < max_tr + 1) { mc_set_error("mc_forest_fit: G table of %lld entries, %lld needed", (long long)n_G, (long long)(max_tr + 1)); return -12; }
     if (node_cap < need_nodes) { mc_set_error("mc_forest_fit: node_cap %lld < %lld", (long long)node_cap, (long long)need_nodes); return -12; }
-    for (int64_t i = 0; i < n_samples; ++i) {
-        if (y[i] > 1) { mc_set_error("mc_forest_fit: labels must be 0 or 1"); return -12; }
-        for (int f = 0; f < d; ++f)
-            if (!std::isfinite((float)X[i * d + f])) { mc_set_error("mc_forest_fit: X holds a value that is not finite in float32"); return -12; }
-    }
-    if (hipSetDevice(mc_internal_device(c)) != hipSuccess) { mc_set_error("mc_forest_fit: hipSetDevice failed"); return -10; }
-    hipStream_t st = mc_internal_stream(c);
+    if (int rc = select_device("mc_forest_fit", c)) return rc;
     const int64_t n = n_samples, T = P->n_trees, total = (int64_t)n_jobs * T;
 
     // host: float32 columns and each column's row order (stable: rows in index order among equal values)
@@ -507,9 +460,9 @@ extern "C" int mc_forest_fit(mc_ctx *c, const mc_forest_params *P, const double 
         const float *col = Xt.data() + (size_t)f * n;
         std::stable_sort(o, o + n, [col](int32_t a, int32_t b) { return col[a] < col[b]; });
     }
-    std::vector<FJob> jobs((size_t)n_jobs);
+    std::vector<FitJob> jobs((size_t)n_jobs);
     for (int j = 0; j < n_jobs; ++j)
-        jobs[j] = FJob{train_off[j], train_off[j + 1] - train_off[j], val_off[j], val_off[j + 1] - val_off[j], seeds[j]};
+        jobs[j] = FitJob{train_off[j], train_off[j + 1] - train_off[j], val_off[j], val_off[j + 1] - val_off[j], seeds[j]};
 
     const int64_t cap_s = max_tr;
     const int64_t cap_lvl = std::max<int64_t>(2, std::min<int64_t>((int64_t)1 << P->max_depth, cap_s) + 1);
@@ -519,14 +472,14 @@ extern "C" int mc_forest_fit(mc_ctx *c, const mc_forest_params *P, const double 
     static const int64_t budget_mb = getenv("MCALLER_FOREST_MEM_MB") ? atoll(getenv("MCALLER_FOREST_MEM_MB")) : 4096;
     const int64_t batch = std::max<int64_t>(1, std::min<int64_t>(total, (std::max<int64_t>(budget_mb, 1) << 20) / (int64_t)per_tree));
 
-    Pool pool;
+    const int64_t n_tr = train_off[n_jobs], n_va = val_off[n_jobs];
+    Pool pool("mc_forest_fit");
     FitArgs A;
     float *dXt = pool.get<float>((size_t)d * n);
     int32_t *dorder = pool.get<int32_t>((size_t)d * n);
     uint8_t *dy = pool.get<uint8_t>((size_t)n);
-    int32_t *dtr = pool.get<int32_t>((size_t)train_off[n_jobs]);
-    int32_t *dva = pool.get<int32_t>((size_t)std::max<int64_t>(val_off[n_jobs], 1));
-    FJob *djobs = pool.get<FJob>((size_t)n_jobs);
+    int32_t *dtr = pool.get<int32_t>((size_t)n_tr), *dva = pool.get<int32_t>((size_t)n_va);
+    FitJob *djobs = pool.get<FitJob>((size_t)n_jobs);
     double *dG = pool.get<double>((size_t)n_G);
     double *dX = pool.get<double>((size_t)n * d);
     A.wy = pool.get<int32_t>((size_t)batch * n);
@@ -540,19 +493,18 @@ extern "C" int mc_forest_fit(mc_ctx *c, const mc_forest_params *P, const double 
     A.n_nodes = pool.get<int32_t>((size_t)batch);
     A.failed = pool.get<int>(1);
     unsigned long long *dcorrect = pool.get<unsigned long long>((size_t)n_jobs);
-    if (!dXt || !dorder || !dy || !dtr || !dva || !djobs || !dG || !dX || !A.wy || !A.node_of || !A.side || !A.S || !A.lvl || !A.work ||
-        !A.best || !A.nodes || !A.n_nodes || !A.failed || !dcorrect)
-        return -10;
-    hipError_t e = hipMemcpyAsync(dXt, Xt.data(), Xt.size() * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dorder, order.data(), order.size() * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dy, y, (size_t)n, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dtr, train_idx, (size_t)train_off[n_jobs] * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && val_off[n_jobs] > 0) e = hipMemcpyAsync(dva, val_idx, (size_t)val_off[n_jobs] * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(djobs, jobs.data(), jobs.size() * sizeof(FJob), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dG, G, (size_t)n_G * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dX, X, (size_t)n * d * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(A.failed, 0, sizeof(int), st);
-    if (e == hipSuccess) e = hipMemsetAsync(dcorrect, 0, (size_t)n_jobs * 8, st);
+    if (!pool.ok) return -10;
+    Xfer x("mc_forest_fit", mc_internal_stream(c));
+    x.up(dXt, Xt.data(), Xt.size());
+    x.up(dorder, order.data(), order.size());
+    x.up(dy, y, (size_t)n);
+    x.up(dtr, train_idx, (size_t)n_tr);
+    x.up(dva, val_idx, (size_t)n_va);
+    x.up(djobs, jobs.data(), jobs.size());
+    x.up(dG, G, (size_t)n_G);
+    x.up(dX, X, (size_t)n * d);
+    x.zero(A.failed, 1);
+    x.zero(dcorrect, (size_t)n_jobs);
     A.Xt = dXt; A.order = dorder; A.y = dy; A.tr_idx = dtr; A.jobs = djobs; A.G = dG;
     A.d = d; A.n_trees = P->n_trees; A.max_depth = P->max_depth; A.max_features = P->max_features;
     A.mss = P->min_samples_split; A.msl = P->min_samples_leaf; A.bootstrap = P->bootstrap;
@@ -564,23 +516,22 @@ extern "C" int mc_forest_fit(mc_ctx *c, const mc_forest_params *P, const double 
     std::vector<int32_t> stack, newid;
     int64_t out = 0;
     tree_node_off[0] = 0;
-    for (int64_t g0 = 0; g0 < total && e == hipSuccess; g0 += batch) {
+    for (int64_t g0 = 0; g0 < total && x.ok(); g0 += batch) {
         const int64_t nb = std::min(batch, total - g0);
         A.g0 = g0;
-        hipLaunchKernelGGL(k5_forest_fit, dim3((unsigned)nb), dim3(BT), 0, st, A);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(hcount.data(), A.n_nodes, (size_t)nb * 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        for (int64_t b = 0; b < nb && e == hipSuccess; ++b) {
+        x.launch(k5_forest_fit, dim3((unsigned)nb), dim3(BT), 0, A);
+        x.down(hcount.data(), A.n_nodes, (size_t)nb);
+        x.sync();
+        for (int64_t b = 0; b < nb && x.ok(); ++b) {
             const int cnt = hcount[b];
             if (cnt < 1 || cnt > cap_nodes || out + cnt > node_cap) {
                 mc_set_error("mc_forest_fit: tree %lld came back with %d nodes", (long long)(g0 + b), cnt);
                 return -10;
             }
-            e = hipMemcpyAsync(hn.data() + b * cap_nodes, A.nodes + b * cap_nodes, (size_t)cnt * sizeof(FNode), hipMemcpyDeviceToHost, st);
+            x.down(hn.data() + b * cap_nodes, A.nodes + b * cap_nodes, (size_t)cnt);
         }
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        for (int64_t b = 0; b < nb && e == hipSuccess; ++b) {
+        x.sync();
+        for (int64_t b = 0; b < nb && x.ok(); ++b) {
             const FNode *tn = hn.data() + b * cap_nodes;
             const int cnt = hcount[b];
             newid.assign((size_t)cnt, -1);
@@ -615,35 +566,28 @@ extern "C" int mc_forest_fit(mc_ctx *c, const mc_forest_params *P, const double 
         }
     }
     int failed = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&failed, A.failed, sizeof(int), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess && failed) { mc_set_error("mc_forest_fit: a tree outgrew its work arrays"); return -10; }
+    x.down(&failed, A.failed, 1);
+    x.sync();
+    if (x.ok() && failed) { mc_set_error("mc_forest_fit: a tree outgrew its work arrays"); return -10; }
 
     // validation: each job's rows scored by its own trees (the trees in pre-order, local child links)
-    if (e == hipSuccess) {
+    if (x.ok()) {
         int64_t *dtoff = pool.get<int64_t>((size_t)total + 1);
         int32_t *dl = pool.get<int32_t>((size_t)out), *dr = pool.get<int32_t>((size_t)out), *df = pool.get<int32_t>((size_t)out);
         double *dth = pool.get<double>((size_t)out), *dv = pool.get<double>((size_t)out * 2);
-        if (!dtoff || !dl || !dr || !df || !dth || !dv) return -10;
-        e = hipMemcpyAsync(dtoff, tree_node_off, (size_t)(total + 1) * 8, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(dl, left, (size_t)out * 4, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(dr, right, (size_t)out * 4, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(df, feature, (size_t)out * 4, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(dth, threshold, (size_t)out * 8, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(dv, value, (size_t)out * 16, hipMemcpyHostToDevice, st);
-        int64_t max_va = 0;
-        for (int j = 0; j < n_jobs; ++j) max_va = std::max(max_va, val_off[j + 1] - val_off[j]);
-        if (e == hipSuccess && max_va > 0) {
-            ValArgs V{dX, dy, dva, djobs, dtoff, dl, dr, df, dth, dv, d, P->n_trees, dcorrect};
-            hipLaunchKernelGGL(k5_forest_val, dim3((unsigned)((max_va + 255) / 256), (unsigned)n_jobs), dim3(256), 0, st, V);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(val_correct, dcorrect, (size_t)n_jobs * 8, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (!pool.ok) return -10;
+        x.up(dtoff, tree_node_off, (size_t)total + 1);
+        x.up(dl, left, (size_t)out);
+        x.up(dr, right, (size_t)out);
+        x.up(df, feature, (size_t)out);
+        x.up(dth, threshold, (size_t)out);
+        x.up(dv, value, (size_t)out * 2);
+        if (max_va > 0)
+            x.launch(k5_forest_val, dim3((unsigned)((max_va + 255) / 256), (unsigned)n_jobs), dim3(256), 0,
+                     ValArgs{dX, dy, dva, djobs, dtoff, dl, dr, df, dth, dv, d, P->n_trees, dcorrect});
+        x.down(val_correct, dcorrect, (size_t)n_jobs);
+        x.sync();
     }
-    if (e != hipSuccess) {
-        mc_set_error("mc_forest_fit failed: %s", hipGetErrorString(e));
-        return -10;
-    }
+    if (!x.ok()) return x.fail();
     return 0;
 }

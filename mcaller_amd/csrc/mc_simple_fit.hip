@@ -19,18 +19,8 @@
 //   * Then the same workgroup scores its held-out rows with k3_simple's arithmetic (dot product in index order, plus the intercept).
 // k7_nb_fit is GaussianNB's fit: per class the counts, means and centred (two-pass) variances, epsilon_ = var_smoothing times the
 // largest per-feature variance of the job's rows, added to every variance; then the held-out rows scored as k3_simple does.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cmath>
-#include <cstdint>
-#include <vector>
-
-#include "../../include/mcaller_hip.h"
-
-void mc_set_error(const char *fmt, ...);
-int mc_internal_device(const mc_ctx *c);
-hipStream_t mc_internal_stream(const mc_ctx *c);
+// The entry points' allocations, transfers and job checks, FitJob, splitmix64 and wave_sum: mc_fit.h.
+#include "mc_fit.h"
 
 namespace {
 
@@ -123,11 +113,6 @@ __device__ __forceinline__ void iswap(int &a, int &b) {
     const int t = a;
     a = b;
     b = t;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
 }
 
 // np.sum of n <= 128 doubles as numpy adds them (pairwise_sum): in order below 8 terms; from 8 on, eight partial sums, then
@@ -577,23 +562,6 @@ __global__ __launch_bounds__(BT) void k7_nb_fit(NbArgs A) {
     }
 }
 
-struct Pool {
-    std::vector<void *> p;
-    const char *who;
-    explicit Pool(const char *w) : who(w) {}
-    ~Pool() { for (void *q : p) (void)hipFree(q); }
-    template <typename T>
-    T *get(size_t n) {
-        void *q = nullptr;
-        if (hipMalloc(&q, std::max<size_t>(n * sizeof(T), 256)) != hipSuccess) {
-            mc_set_error("%s: hipMalloc of %zu bytes failed", who, n * sizeof(T));
-            return nullptr;
-        }
-        p.push_back(q);
-        return (T *)q;
-    }
-};
-
 // the checks both fits share, then the jobs with their rows grouped classes_[0] first (stable) -> 0, or -12 with the error set
 int plan_jobs(const char *who, const double *X, const uint8_t *y, int64_t n_samples, int32_t n_in, int32_t n_jobs,
               const int64_t *train_off, const int32_t *train_idx, const int64_t *val_off, const int32_t *val_idx,
@@ -604,35 +572,14 @@ int plan_jobs(const char *who, const double *X, const uint8_t *y, int64_t n_samp
         mc_set_error("%s: %lld samples, %d jobs out of range", who, (long long)n_samples, n_jobs);
         return -12;
     }
-    for (int64_t i = 0; i < n_samples; ++i) {
-        if (y[i] > 1) { mc_set_error("%s: labels must be 0 or 1", who); return -12; }
-        for (int f = 0; f < d; ++f)
-            if (!std::isfinite(X[i * d + f])) { mc_set_error("%s: X holds a value that is not finite", who); return -12; }
-    }
-    if (train_off[0] != 0 || val_off[0] != 0) { mc_set_error("%s: offsets must start at 0", who); return -12; }
-    jobs.assign((size_t)n_jobs, Job{});
+    std::vector<int64_t> n_neg((size_t)n_jobs);
+    if (int rc = check_jobs(who, X, y, n_samples, d, n_jobs, train_off, train_idx, val_off, val_idx, MAX_ROWS, 2, true, false, n_neg.data()))
+        return rc;
+    jobs.resize((size_t)n_jobs);
+    grouped.resize((size_t)train_off[n_jobs]);
     for (int j = 0; j < n_jobs; ++j) {
-        const int64_t ntr = train_off[j + 1] - train_off[j], nva = val_off[j + 1] - val_off[j];
-        if (ntr < 2 || ntr > MAX_ROWS || nva < 0 || nva > MAX_ROWS || train_off[j + 1] > ((int64_t)1 << 31) ||
-            val_off[j + 1] > ((int64_t)1 << 31)) {
-            mc_set_error("%s: bad offsets for job %d (every job needs two training rows)", who, j);
-            return -12;
-        }
-        int64_t cnt[2] = {0, 0};
-        for (int64_t i = train_off[j]; i < train_off[j + 1]; ++i) {
-            if (train_idx[i] < 0 || train_idx[i] >= n_samples) { mc_set_error("%s: row index out of range", who); return -12; }
-            ++cnt[y[train_idx[i]]];
-        }
-        if (cnt[0] == 0 || cnt[1] == 0) { mc_set_error("%s: job %d has training rows of one class only", who, j); return -12; }
-        if (nva > 0 && !val_idx) { mc_set_error("%s: a required pointer is NULL", who); return -12; }
-        for (int64_t i = val_off[j]; i < val_off[j + 1]; ++i)
-            if (val_idx[i] < 0 || val_idx[i] >= n_samples) { mc_set_error("%s: row index out of range", who); return -12; }
-        jobs[j] = Job{train_off[j], ntr, cnt[0], val_off[j], nva, 0u, 0};
-    }
-    const int64_t n_tr = train_off[n_jobs];
-    grouped.resize((size_t)n_tr);
-    for (int j = 0; j < n_jobs; ++j) {
-        int64_t a = train_off[j], b = train_off[j] + jobs[j].n_neg;
+        jobs[j] = Job{train_off[j], train_off[j + 1] - train_off[j], n_neg[j], val_off[j], val_off[j + 1] - val_off[j], 0u, 0};
+        int64_t a = train_off[j], b = train_off[j] + n_neg[j];
         for (int64_t i = train_off[j]; i < train_off[j + 1]; ++i) {
             const int32_t r = train_idx[i];
             grouped[(size_t)(y[r] == 0 ? a++ : b++)] = r;
@@ -668,45 +615,37 @@ extern "C" int mc_lr_fit(mc_ctx *c, const mc_lr_params *P, const double *X, cons
         mc_set_error("mc_lr_fit: %.0f bytes of work memory exceed the cap of %lld", bytes, (long long)MEM_CAP);
         return -12;
     }
-    if (hipSetDevice(mc_internal_device(c)) != hipSuccess) { mc_set_error("mc_lr_fit: hipSetDevice failed"); return -10; }
-    hipStream_t st = mc_internal_stream(c);
+    if ((rc = select_device("mc_lr_fit", c))) return rc;
     Pool pool("mc_lr_fit");
     double *dX = pool.get<double>((size_t)n_samples * d), *dXc = pool.get<double>((size_t)n_tr * n);
     uint8_t *dy = pool.get<uint8_t>((size_t)n_samples);
-    int32_t *dtr = pool.get<int32_t>((size_t)n_tr), *dva = pool.get<int32_t>((size_t)std::max<int64_t>(n_va, 1));
+    int32_t *dtr = pool.get<int32_t>((size_t)n_tr), *dva = pool.get<int32_t>((size_t)n_va);
     Job *djobs = pool.get<Job>((size_t)n_jobs);
     double *rows = pool.get<double>((size_t)n_tr * 5);
-    double *dw = pool.get<double>((size_t)n_jobs * n), *ddec = pool.get<double>((size_t)std::max<int64_t>(n_va, 1));
+    double *dw = pool.get<double>((size_t)n_jobs * n), *ddec = pool.get<double>((size_t)n_va);
     int *diter = pool.get<int>((size_t)n_jobs), *dstatus = pool.get<int>((size_t)n_jobs);
     long long *dcorrect = pool.get<long long>((size_t)n_jobs);
-    if (!dX || !dXc || !dy || !dtr || !dva || !djobs || !rows || !dw || !ddec || !diter || !dstatus || !dcorrect) return -10;
-    hipError_t e = hipMemcpyAsync(dX, X, (size_t)n_samples * d * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dy, y, (size_t)n_samples, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dtr, grouped.data(), grouped.size() * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && n_va > 0) e = hipMemcpyAsync(dva, val_idx, (size_t)n_va * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(djobs, jobs.data(), jobs.size() * sizeof(Job), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        LrArgs A{dX, dy, dtr, dva, djobs, dXc, rows, rows + n_tr, rows + 2 * n_tr, rows + 3 * n_tr, rows + 4 * n_tr,
-                 d, P->max_iter, P->C, P->tol, dw, diter, dstatus, ddec, dcorrect};
-        hipLaunchKernelGGL(k7_lr_fit, dim3((unsigned)n_jobs), dim3(BT), 0, st, A);
-        e = hipGetLastError();
-    }
+    if (!pool.ok) return -10;
+    Xfer x("mc_lr_fit", mc_internal_stream(c));
+    x.up(dX, X, (size_t)n_samples * d);
+    x.up(dy, y, (size_t)n_samples);
+    x.up(dtr, grouped.data(), grouped.size());
+    x.up(dva, val_idx, (size_t)n_va);
+    x.up(djobs, jobs.data(), jobs.size());
+    x.launch(k7_lr_fit, dim3((unsigned)n_jobs), dim3(BT), 0,
+             LrArgs{dX, dy, dtr, dva, djobs, dXc, rows, rows + n_tr, rows + 2 * n_tr, rows + 3 * n_tr, rows + 4 * n_tr,
+                    d, P->max_iter, P->C, P->tol, dw, diter, dstatus, ddec, dcorrect});
     std::vector<double> hw((size_t)n_jobs * n);
-    std::vector<long long> hcorrect((size_t)n_jobs);
-    if (e == hipSuccess) e = hipMemcpyAsync(hw.data(), dw, hw.size() * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(n_iter, diter, (size_t)n_jobs * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(status, dstatus, (size_t)n_jobs * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(hcorrect.data(), dcorrect, (size_t)n_jobs * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && n_va > 0) e = hipMemcpyAsync(val_dec, ddec, (size_t)n_va * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        mc_set_error("mc_lr_fit failed: %s", hipGetErrorString(e));
-        return -10;
-    }
+    x.down(hw.data(), dw, hw.size());
+    x.down(n_iter, diter, (size_t)n_jobs);
+    x.down(status, dstatus, (size_t)n_jobs);
+    x.down(val_correct, dcorrect, (size_t)n_jobs);
+    x.down(val_dec, ddec, (size_t)n_va);
+    x.sync();
+    if (!x.ok()) return x.fail();
     for (int j = 0; j < n_jobs; ++j) {
         for (int f = 0; f < d; ++f) coef[(size_t)j * d + f] = hw[(size_t)j * n + f];
         intercept[j] = hw[(size_t)j * n + d];
-        val_correct[j] = hcorrect[j];
     }
     return 0;
 }
@@ -734,41 +673,32 @@ extern "C" int mc_nb_fit(mc_ctx *c, const mc_nb_params *P, const double *X, cons
         mc_set_error("mc_nb_fit: %.0f bytes of work memory exceed the cap of %lld", bytes, (long long)MEM_CAP);
         return -12;
     }
-    if (hipSetDevice(mc_internal_device(c)) != hipSuccess) { mc_set_error("mc_nb_fit: hipSetDevice failed"); return -10; }
-    hipStream_t st = mc_internal_stream(c);
+    if ((rc = select_device("mc_nb_fit", c))) return rc;
     Pool pool("mc_nb_fit");
     double *dX = pool.get<double>((size_t)n_samples * d);
     uint8_t *dy = pool.get<uint8_t>((size_t)n_samples);
-    int32_t *dtr = pool.get<int32_t>((size_t)n_tr), *dva = pool.get<int32_t>((size_t)std::max<int64_t>(n_va, 1));
+    int32_t *dtr = pool.get<int32_t>((size_t)n_tr), *dva = pool.get<int32_t>((size_t)n_va);
     Job *djobs = pool.get<Job>((size_t)n_jobs);
     double *dtheta = pool.get<double>((size_t)n_jobs * 2 * d), *dvar = pool.get<double>((size_t)n_jobs * 2 * d);
     double *deps = pool.get<double>((size_t)n_jobs);
     long long *dcorrect = pool.get<long long>((size_t)n_jobs);
-    if (!dX || !dy || !dtr || !dva || !djobs || !dtheta || !dvar || !deps || !dcorrect) return -10;
-    hipError_t e = hipMemcpyAsync(dX, X, (size_t)n_samples * d * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dy, y, (size_t)n_samples, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dtr, grouped.data(), grouped.size() * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && n_va > 0) e = hipMemcpyAsync(dva, val_idx, (size_t)n_va * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(djobs, jobs.data(), jobs.size() * sizeof(Job), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        NbArgs A{dX, dy, dtr, dva, djobs, d, P->var_smoothing, dtheta, dvar, deps, dcorrect};
-        hipLaunchKernelGGL(k7_nb_fit, dim3((unsigned)n_jobs), dim3(BT), 0, st, A);
-        e = hipGetLastError();
-    }
-    std::vector<long long> hcorrect((size_t)n_jobs);
-    if (e == hipSuccess) e = hipMemcpyAsync(theta, dtheta, (size_t)n_jobs * 2 * d * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(var, dvar, (size_t)n_jobs * 2 * d * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(epsilon, deps, (size_t)n_jobs * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(hcorrect.data(), dcorrect, (size_t)n_jobs * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        mc_set_error("mc_nb_fit failed: %s", hipGetErrorString(e));
-        return -10;
-    }
+    if (!pool.ok) return -10;
+    Xfer x("mc_nb_fit", mc_internal_stream(c));
+    x.up(dX, X, (size_t)n_samples * d);
+    x.up(dy, y, (size_t)n_samples);
+    x.up(dtr, grouped.data(), grouped.size());
+    x.up(dva, val_idx, (size_t)n_va);
+    x.up(djobs, jobs.data(), jobs.size());
+    x.launch(k7_nb_fit, dim3((unsigned)n_jobs), dim3(BT), 0, NbArgs{dX, dy, dtr, dva, djobs, d, P->var_smoothing, dtheta, dvar, deps, dcorrect});
+    x.down(theta, dtheta, (size_t)n_jobs * 2 * d);
+    x.down(var, dvar, (size_t)n_jobs * 2 * d);
+    x.down(epsilon, deps, (size_t)n_jobs);
+    x.down(val_correct, dcorrect, (size_t)n_jobs);
+    x.sync();
+    if (!x.ok()) return x.fail();
     for (int j = 0; j < n_jobs; ++j) {
         class_count[2 * j] = jobs[j].n_neg;
         class_count[2 * j + 1] = jobs[j].n_tr - jobs[j].n_neg;
-        val_correct[j] = hcorrect[j];
     }
     for (int j = 0; j < n_jobs; ++j)
         if (!(epsilon[j] > 0.0)) {

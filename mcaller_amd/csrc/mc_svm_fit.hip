@@ -15,18 +15,10 @@
 //     the owner reads or writes its rows, so the block reductions are the only barriers (two per iteration, LDS double-buffered).
 // k6_svm_val then scores each job's held-out rows as k3_svm does (support vectors in order, dec += coef exp(-gamma d2), + intercept),
 // the sign turned so that dec > 0 means classes_[0]; k6_svm_sigmoid is libsvm's sigmoid_train in one workgroup, fixed-order sums.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cmath>
+// The entry points' allocations, transfers and job checks, FitJob, splitmix64 and wave_sum: mc_fit.h.
 #include <cstdlib>
-#include <vector>
 
-#include "../../include/mcaller_hip.h"
-
-void mc_set_error(const char *fmt, ...);
-int mc_internal_device(const mc_ctx *c);
-hipStream_t mc_internal_stream(const mc_ctx *c);
+#include "mc_fit.h"
 
 namespace {
 
@@ -351,21 +343,6 @@ __global__ __launch_bounds__(ST) void k6_svm_sigmoid(const double *__restrict__ 
     if (tid == 0) { out[0] = A; out[1] = B; }
 }
 
-struct Pool {
-    std::vector<void *> p;
-    ~Pool() { for (void *q : p) (void)hipFree(q); }
-    template <typename T>
-    T *get(size_t n) {
-        void *q = nullptr;
-        if (hipMalloc(&q, std::max<size_t>(n * sizeof(T), 256)) != hipSuccess) {
-            mc_set_error("mc_svm_fit: hipMalloc of %zu bytes failed", n * sizeof(T));
-            return nullptr;
-        }
-        p.push_back(q);
-        return (T *)q;
-    }
-};
-
 }  // namespace
 
 extern "C" int mc_svm_fit(mc_ctx *c, const mc_svm_params *P, const double *X, const uint8_t *y, int64_t n_samples, int32_t n_in,
@@ -385,39 +362,21 @@ extern "C" int mc_svm_fit(mc_ctx *c, const mc_svm_params *P, const double *X, co
         mc_set_error("mc_svm_fit: %lld samples, %d jobs out of range", (long long)n_samples, n_jobs);
         return -12;
     }
-    for (int64_t i = 0; i < n_samples; ++i) {
-        if (y[i] > 1) { mc_set_error("mc_svm_fit: labels must be 0 or 1"); return -12; }
-        for (int f = 0; f < d; ++f)
-            if (!std::isfinite(X[i * d + f])) { mc_set_error("mc_svm_fit: X holds a value that is not finite"); return -12; }
-    }
-    if (train_off[0] != 0 || val_off[0] != 0) { mc_set_error("mc_svm_fit: offsets must start at 0"); return -12; }
+    if (int rc = check_jobs("mc_svm_fit", X, y, n_samples, d, n_jobs, train_off, train_idx, val_off, val_idx, MAX_ROWS, 2, true, false, nullptr))
+        return rc;
     int64_t max_va = 0;
     for (int j = 0; j < n_jobs; ++j) {
-        const int64_t ntr = train_off[j + 1] - train_off[j], nva = val_off[j + 1] - val_off[j];
-        if (ntr < 2 || ntr > MAX_ROWS || nva < 0 || nva > MAX_ROWS || train_off[j + 1] > ((int64_t)1 << 31) || val_off[j + 1] > ((int64_t)1 << 31)) {
-            mc_set_error("mc_svm_fit: bad offsets for job %d (every job needs two training rows)", j);
-            return -12;
-        }
         if (!(gamma[j] > 0.0) || !std::isfinite(gamma[j])) { mc_set_error("mc_svm_fit: gamma of job %d must be finite and > 0", j); return -12; }
-        int cnt[2] = {0, 0};
-        for (int64_t i = train_off[j]; i < train_off[j + 1]; ++i) {
-            if (train_idx[i] < 0 || train_idx[i] >= n_samples) { mc_set_error("mc_svm_fit: row index out of range"); return -12; }
-            ++cnt[y[train_idx[i]]];
-        }
-        if (cnt[0] == 0 || cnt[1] == 0) { mc_set_error("mc_svm_fit: job %d has training rows of one class only", j); return -12; }
-        if (nva > 0 && (!val_idx || !val_dec)) { mc_set_error("mc_svm_fit: a required pointer is NULL"); return -12; }
-        for (int64_t i = val_off[j]; i < val_off[j + 1]; ++i)
-            if (val_idx[i] < 0 || val_idx[i] >= n_samples) { mc_set_error("mc_svm_fit: row index out of range"); return -12; }
-        max_va = std::max(max_va, nva);
+        max_va = std::max(max_va, val_off[j + 1] - val_off[j]);
     }
     const int64_t n_tr = train_off[n_jobs], n_va = val_off[n_jobs];
+    if (n_va > 0 && !val_dec) { mc_set_error("mc_svm_fit: a required pointer is NULL"); return -12; }
     const double bytes = ((double)n_tr * (d + 3) + (double)n_samples * d + (double)n_va) * 8.0 + (double)n_tr + (double)n_samples;
     if (bytes > (double)MEM_CAP) {
         mc_set_error("mc_svm_fit: %.0f bytes of work memory exceed the cap of %lld", bytes, (long long)MEM_CAP);
         return -12;
     }
-    if (hipSetDevice(mc_internal_device(c)) != hipSuccess) { mc_set_error("mc_svm_fit: hipSetDevice failed"); return -10; }
-    hipStream_t st = mc_internal_stream(c);
+    if (int rc = select_device("mc_svm_fit", c)) return rc;
 
     // host: each job's rows gathered feature-major, the solve labels (+1: the class of the job's first row, as libsvm's label[0])
     std::vector<double> Xt((size_t)n_tr * d);
@@ -434,7 +393,7 @@ extern "C" int mc_svm_fit(mc_ctx *c, const mc_svm_params *P, const double *X, co
         jobs[j] = SJob{o, l, val_off[j], val_off[j + 1] - val_off[j], gamma[j],
                        P->max_iter > 0 ? P->max_iter : std::max<int64_t>(10000000, 100 * l), first == 0 ? 1 : -1, 0};
     }
-    Pool pool;
+    Pool pool("mc_svm_fit");
     double *dXt = pool.get<double>((size_t)n_tr * d), *dX = pool.get<double>((size_t)n_samples * d);
     int8_t *dys = pool.get<int8_t>((size_t)n_tr);
     uint8_t *dy = pool.get<uint8_t>((size_t)n_samples);
@@ -443,40 +402,32 @@ extern "C" int mc_svm_fit(mc_ctx *c, const mc_svm_params *P, const double *X, co
     double *drho = pool.get<double>((size_t)n_jobs);
     long long *diter = pool.get<long long>((size_t)n_jobs);
     int *dstatus = pool.get<int>((size_t)n_jobs);
-    int32_t *dva = pool.get<int32_t>((size_t)std::max<int64_t>(n_va, 1));
-    double *ddec = pool.get<double>((size_t)std::max<int64_t>(n_va, 1));
+    int32_t *dva = pool.get<int32_t>((size_t)n_va);
+    double *ddec = pool.get<double>((size_t)n_va);
     unsigned long long *dcorrect = pool.get<unsigned long long>((size_t)n_jobs);
-    if (!dXt || !dX || !dys || !dy || !djobs || !dalpha || !dG || !dKi || !drho || !diter || !dstatus || !dva || !ddec || !dcorrect) return -10;
-    hipError_t e = hipMemcpyAsync(dXt, Xt.data(), Xt.size() * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dX, X, (size_t)n_samples * d * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dys, ys.data(), ys.size(), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dy, y, (size_t)n_samples, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(djobs, jobs.data(), jobs.size() * sizeof(SJob), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && n_va > 0) e = hipMemcpyAsync(dva, val_idx, (size_t)n_va * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(dcorrect, 0, (size_t)n_jobs * 8, st);
-    if (e == hipSuccess) {
-        FitArgs A{dXt, dys, djobs, dalpha, dG, dKi, drho, diter, dstatus, d, P->C, P->tol};
-        hipLaunchKernelGGL(k6_svm_fit, dim3((unsigned)n_jobs), dim3(BT), 0, st, A);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && max_va > 0) {
-        ValArgs V{dX, dy, dva, dXt, dys, dalpha, drho, djobs, d, ddec, dcorrect};
-        hipLaunchKernelGGL(k6_svm_val, dim3((unsigned)((max_va + 255) / 256), (unsigned)n_jobs), dim3(256), 0, st, V);
-        e = hipGetLastError();
-    }
+    if (!pool.ok) return -10;
+    Xfer x("mc_svm_fit", mc_internal_stream(c));
+    x.up(dXt, Xt.data(), Xt.size());
+    x.up(dX, X, (size_t)n_samples * d);
+    x.up(dys, ys.data(), ys.size());
+    x.up(dy, y, (size_t)n_samples);
+    x.up(djobs, jobs.data(), jobs.size());
+    x.up(dva, val_idx, (size_t)n_va);
+    x.zero(dcorrect, (size_t)n_jobs);
+    x.launch(k6_svm_fit, dim3((unsigned)n_jobs), dim3(BT), 0, FitArgs{dXt, dys, djobs, dalpha, dG, dKi, drho, diter, dstatus, d, P->C, P->tol});
+    if (max_va > 0)
+        x.launch(k6_svm_val, dim3((unsigned)((max_va + 255) / 256), (unsigned)n_jobs), dim3(256), 0,
+                 ValArgs{dX, dy, dva, dXt, dys, dalpha, drho, djobs, d, ddec, dcorrect});
     std::vector<long long> hiter((size_t)n_jobs);
     std::vector<int> hstatus((size_t)n_jobs);
-    if (e == hipSuccess) e = hipMemcpyAsync(alpha, dalpha, (size_t)n_tr * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(rho, drho, (size_t)n_jobs * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(hiter.data(), diter, (size_t)n_jobs * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(hstatus.data(), dstatus, (size_t)n_jobs * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(val_correct, dcorrect, (size_t)n_jobs * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && n_va > 0) e = hipMemcpyAsync(val_dec, ddec, (size_t)n_va * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        mc_set_error("mc_svm_fit failed: %s", hipGetErrorString(e));
-        return -10;
-    }
+    x.down(alpha, dalpha, (size_t)n_tr);
+    x.down(rho, drho, (size_t)n_jobs);
+    x.down(hiter.data(), diter, (size_t)n_jobs);
+    x.down(hstatus.data(), dstatus, (size_t)n_jobs);
+    x.down(val_correct, dcorrect, (size_t)n_jobs);
+    x.down(val_dec, ddec, (size_t)n_va);
+    x.sync();
+    if (!x.ok()) return x.fail();
     for (int j = 0; j < n_jobs; ++j) {
         n_iter[j] = hiter[j];
         status[j] = hstatus[j];
@@ -491,25 +442,19 @@ extern "C" int mc_svm_sigmoid_train(mc_ctx *c, const double *dec, const uint8_t 
         if (y[i] > 1) { mc_set_error("mc_svm_sigmoid_train: labels must be 0 or 1"); return -12; }
         if (!std::isfinite(dec[i])) { mc_set_error("mc_svm_sigmoid_train: a decision value is not finite"); return -12; }
     }
-    if (hipSetDevice(mc_internal_device(c)) != hipSuccess) { mc_set_error("mc_svm_sigmoid_train: hipSetDevice failed"); return -10; }
-    hipStream_t st = mc_internal_stream(c);
-    Pool pool;
+    if (int rc = select_device("mc_svm_sigmoid_train", c)) return rc;
+    Pool pool("mc_svm_sigmoid_train");
     double *ddec = pool.get<double>((size_t)n), *dout = pool.get<double>(2);
     uint8_t *dy = pool.get<uint8_t>((size_t)n);
-    if (!ddec || !dout || !dy) return -10;
+    if (!pool.ok) return -10;
     double out[2] = {0.0, 0.0};
-    hipError_t e = hipMemcpyAsync(ddec, dec, (size_t)n * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dy, y, (size_t)n, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k6_svm_sigmoid, dim3(1), dim3(ST), 0, st, ddec, dy, n, dout);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, 16, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        mc_set_error("mc_svm_sigmoid_train failed: %s", hipGetErrorString(e));
-        return -10;
-    }
+    Xfer x("mc_svm_sigmoid_train", mc_internal_stream(c));
+    x.up(ddec, dec, (size_t)n);
+    x.up(dy, y, (size_t)n);
+    x.launch(k6_svm_sigmoid, dim3(1), dim3(ST), 0, (const double *)ddec, (const uint8_t *)dy, n, dout);
+    x.down(out, dout, 2);
+    x.sync();
+    if (!x.ok()) return x.fail();
     *A = out[0];
     *B = out[1];
     return 0;

@@ -25,27 +25,10 @@
 // rows at a time per wave (their chains side by side), exp and log once for the two rows (lane r takes row r's output): 0.45; fused
 // multiply-adds: 0.41; FOUR workgroups per fit, on one XCD, meeting once per batch: **0.25 s**.  (Eight waves per workgroup halve a
 // lane's registers and spill: 0.75 s; three / four rows at a time: 0.49 / 0.53.)  fp64 throughout, like scikit-learn.
-#include <hip/hip_runtime.h>
+// The entry points' allocations, transfers and job checks, FitJob, splitmix64 and wave_sum: mc_fit.h.
+#include <cstdlib>
 
-#include <algorithm>
-#include <cmath>
-#include <cstring>
-#include <vector>
-
-#include "../../include/mcaller_hip.h"
-
-void mc_set_error(const char *fmt, ...);
-int mc_internal_device(const mc_ctx *c);
-hipStream_t mc_internal_stream(const mc_ctx *c);
-
-#define HIP_TRY(expr)                                                                       \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if (_e != hipSuccess) {                                                             \
-            mc_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-            return -10;                                                                     \
-        }                                                                                   \
-    } while (0)
+#include "mc_fit.h"
 
 // (x * w + z as one fma in this file: the dot products and the gradient sums are half the instructions of a row, and nothing here
 // is held to a CPU sum bit for bit -- the fit oracle and scikit-learn's own runs are matched to stated tolerances; 0.45 -> 0.41 s)
@@ -74,11 +57,6 @@ constexpr int NP = NC + 2;             // + the wave's loss sum and output-bias 
 constexpr int NPH = NP / 2;            // ... exchanged through LDS in two halves (FW x NPH x 64 doubles: 48 KB)
 static_assert(NP % 2 == 0, "two halves");
 
-struct FitJob {
-    long long tr_off, n_tr, va_off, n_va;
-    unsigned long long seed;
-};
-
 struct FitArgs {
     const double *X;         // [n_samples * d]
     const uint8_t *y;        // [n_samples] 0/1
@@ -97,14 +75,6 @@ struct FitArgs {
     unsigned *bar;           // [n_jobs]: workgroups that have written their partial sums, over all batches so far
     int *failed;             // a workgroup waited for the others for seconds: the call fails
 };
-
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ull;
-    unsigned long long z = x;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 __device__ __forceinline__ double uniform01(unsigned long long seed, unsigned long long index) {
     return (double)(splitmix64(seed + index * 0xD1342543DE82EF95ull) >> 11) * (1.0 / 9007199254740992.0);
@@ -164,12 +134,6 @@ __device__ __forceinline__ double fit_tanh(double x) {
     return copysign(fma(-2.0, q, 1.0), x);
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 __global__ __launch_bounds__(FT) void k4_mlp_fit(FitArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
     double(*s_part)[NPH][64] = reinterpret_cast<double(*)[NPH][64]>(s_raw);                 // [FW][NPH][64]
@@ -189,7 +153,7 @@ __global__ __launch_bounds__(FT) void k4_mlp_fit(FitArgs A) {
     const FitJob J = A.jobs[job];
     const int d = A.d, H = A.H;
     const uint32_t n = (uint32_t)J.n_tr;
-    const int B = (int)min((long long)A.batch, J.n_tr);
+    const int B = (int)min((long long)A.batch, (long long)J.n_tr);   // (one type: min(long long, int64_t) picks another overload)
     const int h[2] = {lane, lane + 64};
     const bool valid[2] = {h[0] < H, h[1] < H};
 
@@ -481,36 +445,18 @@ __global__ __launch_bounds__(FT) void k4_mlp_fit(FitArgs A) {
     if (lane == 0 && J.n_va > 0) atomicAdd(reinterpret_cast<unsigned long long *>(&A.val_correct[job]), (unsigned long long)correct);
 }
 
-template <typename T>
-int to_device(std::vector<void *> &pool, T **dst, const T *src, size_t n, hipStream_t st) {
-    void *q = nullptr;
-    if (hipMalloc(&q, std::max<size_t>(n * sizeof(T), 256)) != hipSuccess) {
-        mc_set_error("hipMalloc of %zu bytes failed", n * sizeof(T));
-        return -10;
-    }
-    pool.push_back(q);
-    *dst = (T *)q;
-    if (src && n) {
-        if (hipMemcpyAsync(q, src, n * sizeof(T), hipMemcpyHostToDevice, st) != hipSuccess) {
-            mc_set_error("H2D copy of %zu bytes failed", n * sizeof(T));
-            return -10;
-        }
-    } else if (n) {
-        (void)hipMemsetAsync(q, 0, n * sizeof(T), st);
-    }
-    return 0;
-}
-
 }  // namespace
 
 extern "C" int mc_mlp_fit(mc_ctx *c, const mc_fit_params *P, const double *X, const uint8_t *y, int64_t n_samples, int32_t n_jobs,
                           const int64_t *train_off, const int32_t *train_idx, const int64_t *val_off, const int32_t *val_idx,
                           const uint64_t *seeds, const double *init, double *W1, double *b1, double *W2, double *b2,
                           double *loss_curve, int32_t *n_iter, int64_t *val_correct) {
-    HIP_TRY(hipSetDevice(mc_internal_device(c)));
-    hipStream_t st = mc_internal_stream(c);
-    if (!P || P->n_in < 1 || P->n_in > DMAX || P->n_hidden < 1 || P->n_hidden > HMAX || P->batch_size < 1 || P->max_iter < 1 ||
-        n_jobs < 1 || n_samples < 1) {
+    if (!P || !X || !y || !train_off || !train_idx || !val_off || !W1 || !b1 || !W2 || !b2 || !loss_curve || !n_iter || !val_correct) {
+        mc_set_error("mc_mlp_fit: a required pointer is NULL");
+        return -12;
+    }
+    if (P->n_in < 1 || P->n_in > DMAX || P->n_hidden < 1 || P->n_hidden > HMAX || P->batch_size < 1 || P->max_iter < 1 || n_jobs < 1 ||
+        n_samples < 1) {
         mc_set_error("mc_mlp_fit: unsupported shape (inputs 1..%d, hidden 1..%d)", DMAX, HMAX);
         return -12;
     }
@@ -519,36 +465,23 @@ extern "C" int mc_mlp_fit(mc_ctx *c, const mc_fit_params *P, const double *X, co
         mc_set_error("mc_mlp_fit: batch size %d does not fit (max %d rows)", P->batch_size, FT);
         return -12;
     }
+    // (a job may come without training rows, and X and y are taken as they are: not check_jobs' rules)
+    if (train_off[0] < 0 || val_off[0] < 0) { mc_set_error("mc_mlp_fit: bad offsets for job 0"); return -12; }
+    std::vector<FitJob> jobs((size_t)n_jobs);
     for (int j = 0; j < n_jobs; ++j) {
         if (train_off[j + 1] < train_off[j] || val_off[j + 1] < val_off[j] || train_off[j + 1] - train_off[j] > (int64_t)1 << 31) {
             mc_set_error("mc_mlp_fit: bad offsets for job %d", j);
             return -12;
         }
-        for (int64_t i = train_off[j]; i < train_off[j + 1]; ++i)
-            if (train_idx[i] < 0 || train_idx[i] >= n_samples) { mc_set_error("mc_mlp_fit: row index out of range"); return -12; }
-        for (int64_t i = val_off[j]; i < val_off[j + 1]; ++i)
-            if (val_idx[i] < 0 || val_idx[i] >= n_samples) { mc_set_error("mc_mlp_fit: row index out of range"); return -12; }
+        if (val_off[j + 1] > val_off[j] && !val_idx) { mc_set_error("mc_mlp_fit: a required pointer is NULL"); return -12; }
+        if (check_rows("mc_mlp_fit", train_idx, train_off[j], train_off[j + 1], n_samples) ||
+            check_rows("mc_mlp_fit", val_idx, val_off[j], val_off[j + 1], n_samples))
+            return -12;
+        jobs[(size_t)j] = FitJob{train_off[j], train_off[j + 1] - train_off[j], val_off[j], val_off[j + 1] - val_off[j],
+                                 seeds ? seeds[j] : (uint64_t)(P->seed + (uint64_t)j)};
     }
+    if (int rc = select_device("mc_mlp_fit", c)) return rc;
     const int d = P->n_in, H = P->n_hidden;
-    std::vector<FitJob> jobs((size_t)n_jobs);
-    for (int j = 0; j < n_jobs; ++j) {
-        jobs[(size_t)j].tr_off = train_off[j];
-        jobs[(size_t)j].n_tr = train_off[j + 1] - train_off[j];
-        jobs[(size_t)j].va_off = val_off[j];
-        jobs[(size_t)j].n_va = val_off[j + 1] - val_off[j];
-        jobs[(size_t)j].seed = seeds ? seeds[j] : (uint64_t)(P->seed + (uint64_t)j);
-    }
-    std::vector<void *> pool;
-    auto cleanup = [&]() { for (void *p : pool) (void)hipFree(p); };
-    FitArgs A;
-    double *dX, *dinit = nullptr, *dW1, *db1, *dW2, *db2, *dcurve;
-    uint8_t *dy;
-    FitJob *djobs;
-    int32_t *dtr, *dva, *dnit;
-    long long *dcorrect;
-    double *dxpart;
-    unsigned *dbar;
-    int *dfailed;
     // workgroups per fit: four (the rows of a batch of 200 over 16 waves), one for small batches or on request
     static const int groups_env = getenv("MCALLER_FIT_WGS") ? atoi(getenv("MCALLER_FIT_WGS")) : 0;
     int G = std::max(1, std::min(16, groups_env > 0 ? groups_env : (P->batch_size >= 64 ? MC_FIT_GROUPS : 1)));
@@ -563,48 +496,59 @@ extern "C" int mc_mlp_fit(mc_ctx *c, const mc_fit_params *P, const double *X, co
         const int64_t wgs = (n_jobs <= 8 ? 8 : (int64_t)n_jobs) * G;            // (by_xcd launches 8 x G)
         if (per_cu <= 0 || n_cu <= 0 || wgs > (int64_t)per_cu * n_cu) G = 1;
     }
-    const size_t per_job = (size_t)d * H + 2 * (size_t)H + 1;
-    int rc = 0;
-    rc |= to_device(pool, &dX, X, (size_t)n_samples * d, st);
-    rc |= to_device(pool, &dy, y, (size_t)n_samples, st);
-    rc |= to_device(pool, &djobs, jobs.data(), (size_t)n_jobs, st);
-    rc |= to_device(pool, &dtr, train_idx, (size_t)std::max<int64_t>(train_off[n_jobs], 1), st);
-    rc |= to_device(pool, &dva, val_idx, (size_t)std::max<int64_t>(val_off[n_jobs], 1), st);
-    if (init) rc |= to_device(pool, &dinit, init, per_job * n_jobs, st);
-    rc |= to_device<double>(pool, &dW1, nullptr, (size_t)n_jobs * d * H, st);
-    rc |= to_device<double>(pool, &db1, nullptr, (size_t)n_jobs * H, st);
-    rc |= to_device<double>(pool, &dW2, nullptr, (size_t)n_jobs * H, st);
-    rc |= to_device<double>(pool, &db2, nullptr, (size_t)n_jobs, st);
-    rc |= to_device<double>(pool, &dcurve, nullptr, (size_t)n_jobs * P->max_iter, st);
-    rc |= to_device<int32_t>(pool, &dnit, nullptr, (size_t)n_jobs, st);
-    rc |= to_device<long long>(pool, &dcorrect, nullptr, (size_t)n_jobs, st);
-    rc |= to_device<double>(pool, &dxpart, nullptr, (size_t)n_jobs * 2 * G * FW * NP * 64, st);
-    rc |= to_device<unsigned>(pool, &dbar, nullptr, (size_t)n_jobs, st);
-    rc |= to_device<int>(pool, &dfailed, nullptr, 1, st);
-    if (rc) { cleanup(); return -10; }
-    A.X = dX; A.y = dy; A.jobs = djobs; A.tr_idx = dtr; A.va_idx = dva;
+    const size_t nj = (size_t)n_jobs, per_job = (size_t)d * H + 2 * (size_t)H + 1;
+    const size_t n_tr = (size_t)train_off[n_jobs], n_va = (size_t)val_off[n_jobs], n_xpart = nj * 2 * G * FW * NP * 64;
+    Pool pool("mc_mlp_fit");
+    FitArgs A;
+    double *dX = pool.get<double>((size_t)n_samples * d), *dinit = init ? pool.get<double>(per_job * nj) : nullptr;
+    uint8_t *dy = pool.get<uint8_t>((size_t)n_samples);
+    FitJob *djobs = pool.get<FitJob>(nj);
+    int32_t *dtr = pool.get<int32_t>(n_tr), *dva = pool.get<int32_t>(n_va);
+    A.W1 = pool.get<double>(nj * d * H);
+    A.b1 = pool.get<double>(nj * H);
+    A.W2 = pool.get<double>(nj * H);
+    A.b2 = pool.get<double>(nj);
+    A.loss_curve = pool.get<double>(nj * P->max_iter);
+    A.n_iter = pool.get<int32_t>(nj);
+    A.val_correct = pool.get<long long>(nj);
+    A.xpart = pool.get<double>(n_xpart);
+    A.bar = pool.get<unsigned>(nj);
+    A.failed = pool.get<int>(1);
+    if (!pool.ok) return -10;
+    Xfer x("mc_mlp_fit", mc_internal_stream(c));
+    x.up(dX, X, (size_t)n_samples * d);
+    x.up(dy, y, (size_t)n_samples);
+    x.up(djobs, jobs.data(), nj);
+    x.up(dtr, train_idx, n_tr);
+    x.up(dva, val_idx, n_va);
+    if (init) x.up(dinit, init, per_job * nj);
+    x.zero(A.W1, nj * d * H);
+    x.zero(A.b1, nj * H);
+    x.zero(A.W2, nj * H);
+    x.zero(A.b2, nj);
+    x.zero(A.loss_curve, nj * P->max_iter);
+    x.zero(A.n_iter, nj);
+    x.zero(A.val_correct, nj);
+    x.zero(A.xpart, n_xpart);
+    x.zero(A.bar, nj);
+    x.zero(A.failed, 1);
+    A.X = dX; A.y = dy; A.jobs = djobs; A.tr_idx = dtr; A.va_idx = dva; A.init = dinit;
     A.d = d; A.H = H; A.batch = P->batch_size; A.max_iter = P->max_iter; A.n_iter_no_change = P->n_iter_no_change;
     A.shuffle = P->shuffle;
     A.alpha = P->alpha; A.lr = P->lr_init; A.beta1 = P->beta1; A.beta2 = P->beta2; A.eps = P->epsilon; A.tol = P->tol;
-    A.G = G; A.n_jobs = n_jobs; A.by_xcd = (G > 1 && n_jobs <= 8) ? 1 : 0; A.xpart = dxpart; A.bar = dbar; A.failed = dfailed;
-    A.init = dinit; A.W1 = dW1; A.b1 = db1; A.W2 = dW2; A.b2 = db2; A.loss_curve = dcurve; A.n_iter = dnit; A.val_correct = dcorrect;
-    hipLaunchKernelGGL(k4_mlp_fit, dim3((unsigned)(A.by_xcd ? 8 * G : n_jobs * G)), dim3(FT), lds, st, A);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(W1, dW1, (size_t)n_jobs * d * H * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(b1, db1, (size_t)n_jobs * H * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(W2, dW2, (size_t)n_jobs * H * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(b2, db2, (size_t)n_jobs * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(loss_curve, dcurve, (size_t)n_jobs * P->max_iter * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(n_iter, dnit, (size_t)n_jobs * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(val_correct, dcorrect, (size_t)n_jobs * 8, hipMemcpyDeviceToHost, st);
+    A.G = G; A.n_jobs = n_jobs; A.by_xcd = (G > 1 && n_jobs <= 8) ? 1 : 0;
+    x.launch(k4_mlp_fit, dim3((unsigned)(A.by_xcd ? 8 * G : n_jobs * G)), dim3(FT), lds, A);
     int fit_failed = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&fit_failed, dfailed, sizeof(int), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    cleanup();
-    if (e != hipSuccess) {
-        mc_set_error("mc_mlp_fit failed: %s", hipGetErrorString(e));
-        return -10;
-    }
+    x.down(W1, A.W1, nj * d * H);
+    x.down(b1, A.b1, nj * H);
+    x.down(W2, A.W2, nj * H);
+    x.down(b2, A.b2, nj);
+    x.down(loss_curve, A.loss_curve, nj * P->max_iter);
+    x.down(n_iter, A.n_iter, nj);
+    x.down(val_correct, A.val_correct, nj);
+    x.down(&fit_failed, A.failed, 1);
+    x.sync();
+    if (!x.ok()) return x.fail();
     if (fit_failed) {
         mc_set_error("mc_mlp_fit: the %d workgroups of a fit did not meet (MCALLER_FIT_WGS=1 runs a fit in one workgroup)", G);
         return -10;

@@ -457,22 +457,48 @@ class Device(object):
         return n_meth, n_total, first, ms.value
 
     # ---- the classifier fit behind --train ----
+    @staticmethod
+    def _fit_jobs(X, y, jobs, who=None, need_spread=False):
+        """X, y and a fit's jobs [(train_rows, validation_rows)] as the C ABI takes them -> (X, y, tr, va, tr_off, va_off, tr_idx,
+        va_idx): the jobs' index arrays, their offsets and their concatenations (one spare entry at the end, so that neither is
+        empty).  With `who` (svm_fit, lr_fit, nb_fit) the call is validated first, a ValueError in that name: finite X of 1..64
+        features, y in {0, 1}, per job two training rows of both classes, every index a row of X and, for need_spread, training rows
+        that are not all equal."""
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.uint8)
+        if who:
+            if X.ndim != 2 or not 1 <= X.shape[1] <= 64 or len(y) != len(X):
+                raise ValueError('%s: X must be rows x 1..64 features with a label per row, got %s and %d labels' % (who, X.shape, len(y)))
+            if not np.isfinite(X).all() or (y > 1).any():
+                raise ValueError('%s: X must be finite and y in {0, 1}' % who)
+            if len(jobs) < 1:
+                raise ValueError('%s: at least one job is needed' % who)
+        n = len(X)
+        tr = [np.ascontiguousarray(j[0], dtype=np.int32) for j in jobs]
+        va = [np.ascontiguousarray(j[1], dtype=np.int32) for j in jobs]
+        if who:
+            for a, b in zip(tr, va):
+                if len(a) < 2 or (a < 0).any() or (a >= n).any() or (b < 0).any() or (b >= n).any():
+                    raise ValueError('%s: every job needs two training rows, every index within the %d rows' % (who, n))
+                if len(np.unique(y[a])) != 2:
+                    raise ValueError('%s: a job whose training rows are of one class' % who)
+                if need_spread and np.ptp(X[a], axis=0).max() == 0:
+                    raise ValueError('%s: a job whose training rows are all equal (epsilon_ = 0: every variance would be 0)' % who)
+        tr_off = np.concatenate([[0], np.cumsum([len(a) for a in tr])]).astype(np.int64)
+        va_off = np.concatenate([[0], np.cumsum([len(a) for a in va])]).astype(np.int64)
+        tr_idx = np.ascontiguousarray(np.concatenate(tr + [np.zeros(1, np.int32)]))
+        va_idx = np.ascontiguousarray(np.concatenate(va + [np.zeros(1, np.int32)]))
+        return X, y, tr, va, tr_off, va_off, tr_idx, va_idx
+
     @_serialized
     def mlp_fit(self, X, y, jobs, hidden=100, alpha=0.001, lr_init=0.001, beta1=0.9, beta2=0.999, epsilon=1e-8,
                 batch_size=200, max_iter=200, tol=1e-4, n_iter_no_change=10, shuffle=True, seed=1, seeds=None, init=None):
         """Fit one 7-H-1 tanh/logistic perceptron per job on the GPU (mc_mlp_fit; all jobs side by side).
         jobs: [(train_rows, validation_rows)] index arrays into X / y.  -> list of dicts W1, b1, W2, b2, loss_curve,
         n_iter, val_correct, n_val."""
-        X = np.ascontiguousarray(X, dtype=np.float64)
-        y = np.ascontiguousarray(y, dtype=np.uint8)
+        X, y, tr, va, tr_off, va_off, tr_idx, va_idx = self._fit_jobs(X, y, jobs)
         n, d = X.shape
         nj = len(jobs)
-        tr = [np.ascontiguousarray(j[0], dtype=np.int32) for j in jobs]
-        va = [np.ascontiguousarray(j[1], dtype=np.int32) for j in jobs]
-        tr_off = np.concatenate([[0], np.cumsum([len(a) for a in tr])]).astype(np.int64)
-        va_off = np.concatenate([[0], np.cumsum([len(a) for a in va])]).astype(np.int64)
-        tr_idx = np.ascontiguousarray(np.concatenate(tr + [np.zeros(1, np.int32)]))
-        va_idx = np.ascontiguousarray(np.concatenate(va + [np.zeros(1, np.int32)]))
         prm = _lib.FitParams(d, int(hidden), int(batch_size), int(max_iter), int(n_iter_no_change), 1 if shuffle else 0,
                              float(alpha), float(lr_init), float(beta1), float(beta2), float(epsilon), float(tol), int(seed))
         sd = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
@@ -496,18 +522,11 @@ class Device(object):
         RandomForestClassifier(criterion='entropy') with keyed randomness).  jobs: [(train_rows, validation_rows)] index arrays into
         X / y (y in {0, 1}).  -> per job a dict: tree_off [n_trees+1], the node arrays of its trees concatenated (left, right local
         to each tree; feature, threshold, value [n, 2], impurity, n_node_samples, weighted_n_node_samples), val_correct, n_val."""
-        X = np.ascontiguousarray(X, dtype=np.float64)
-        y = np.ascontiguousarray(y, dtype=np.uint8)
+        X, y, tr, va, tr_off, va_off, tr_idx, va_idx = self._fit_jobs(X, y, jobs)
         n, d = X.shape
         if max_features > d:
             raise ValueError('max_features must be in (0, n_features]: %d > %d' % (max_features, d))
         nj = len(jobs)
-        tr = [np.ascontiguousarray(j[0], dtype=np.int32) for j in jobs]
-        va = [np.ascontiguousarray(j[1], dtype=np.int32) for j in jobs]
-        tr_off = np.concatenate([[0], np.cumsum([len(a) for a in tr])]).astype(np.int64)
-        va_off = np.concatenate([[0], np.cumsum([len(a) for a in va])]).astype(np.int64)
-        tr_idx = np.ascontiguousarray(np.concatenate(tr + [np.zeros(1, np.int32)]))
-        va_idx = np.ascontiguousarray(np.concatenate(va + [np.zeros(1, np.int32)]))
         sd = np.ascontiguousarray([(seed + j) % (1 << 64) for j in range(nj)] if seeds is None else seeds, dtype=np.uint64)
         max_tr = max(len(a) for a in tr)
         m = np.arange(max_tr + 1, dtype=np.float64)
@@ -539,30 +558,14 @@ class Device(object):
         [(train_rows, validation_rows)] index arrays into X / y (y in {0, 1}); a job's training rows come in libsvm's solve order,
         the class of its first row being the solve's +1.  -> per job a dict: alpha (per training row), rho, n_iter, status (1: the
         iteration cap was reached), val_dec (> 0: class 0), val_correct, n_val."""
-        X = np.ascontiguousarray(X, dtype=np.float64)
-        y = np.ascontiguousarray(y, dtype=np.uint8)
-        if X.ndim != 2 or not 1 <= X.shape[1] <= 64 or len(y) != len(X):
-            raise ValueError('svm_fit: X must be rows x 1..64 features with a label per row, got %s and %d labels' % (X.shape, len(y)))
-        if not np.isfinite(X).all() or (y > 1).any():
-            raise ValueError('svm_fit: X must be finite and y in {0, 1}')
+        X, y, tr, va, tr_off, va_off, tr_idx, va_idx = self._fit_jobs(X, y, jobs, 'svm_fit')
         n, d = X.shape
         nj = len(jobs)
         g = np.ascontiguousarray(gammas, dtype=np.float64)
-        if nj < 1 or len(g) != nj or not (np.isfinite(g) & (g > 0)).all():
+        if len(g) != nj or not (np.isfinite(g) & (g > 0)).all():
             raise ValueError('svm_fit: a finite gamma > 0 per job is needed')
         if not (C > 0 and np.isfinite(C) and tol > 0 and np.isfinite(tol)) or max_iter < 0:
             raise ValueError('svm_fit: C and tol must be finite and > 0, max_iter >= 0')
-        tr = [np.ascontiguousarray(j[0], dtype=np.int32) for j in jobs]
-        va = [np.ascontiguousarray(j[1], dtype=np.int32) for j in jobs]
-        for a, b in zip(tr, va):
-            if len(a) < 2 or (a < 0).any() or (a >= n).any() or (b < 0).any() or (b >= n).any():
-                raise ValueError('svm_fit: every job needs two training rows, every index within the %d rows' % n)
-            if len(np.unique(y[a])) != 2:
-                raise ValueError('svm_fit: a job whose training rows are of one class')
-        tr_off = np.concatenate([[0], np.cumsum([len(a) for a in tr])]).astype(np.int64)
-        va_off = np.concatenate([[0], np.cumsum([len(a) for a in va])]).astype(np.int64)
-        tr_idx = np.ascontiguousarray(np.concatenate(tr))
-        va_idx = np.ascontiguousarray(np.concatenate(va + [np.zeros(1, np.int32)]))
         alpha = np.zeros(tr_off[-1]); rho = np.zeros(nj); n_iter = np.zeros(nj, np.int64); status = np.zeros(nj, np.int32)
         correct = np.zeros(nj, np.int64); dec = np.zeros(max(int(va_off[-1]), 1))
         prm = _lib.SvmParams(float(C), float(tol), int(max_iter))
@@ -571,38 +574,13 @@ class Device(object):
         return [dict(alpha=alpha[tr_off[j]:tr_off[j + 1]].copy(), rho=float(rho[j]), n_iter=int(n_iter[j]), status=int(status[j]),
                      val_dec=dec[va_off[j]:va_off[j + 1]].copy(), val_correct=int(correct[j]), n_val=len(va[j])) for j in range(nj)]
 
-    @staticmethod
-    def _simple_jobs(who, X, y, jobs, need_spread):
-        """Validate and flatten a fit's jobs like svm_fit -> (X, y, tr, va, tr_off, va_off, tr_idx, va_idx)."""
-        X = np.ascontiguousarray(X, dtype=np.float64)
-        y = np.ascontiguousarray(y, dtype=np.uint8)
-        if X.ndim != 2 or not 1 <= X.shape[1] <= 64 or len(y) != len(X):
-            raise ValueError('%s: X must be rows x 1..64 features with a label per row, got %s and %d labels' % (who, X.shape, len(y)))
-        if not np.isfinite(X).all() or (y > 1).any():
-            raise ValueError('%s: X must be finite and y in {0, 1}' % who)
-        n = len(X)
-        if len(jobs) < 1:
-            raise ValueError('%s: at least one job is needed' % who)
-        tr = [np.ascontiguousarray(j[0], dtype=np.int32) for j in jobs]
-        va = [np.ascontiguousarray(j[1], dtype=np.int32) for j in jobs]
-        for a, b in zip(tr, va):
-            if len(a) < 2 or (a < 0).any() or (a >= n).any() or (b < 0).any() or (b >= n).any():
-                raise ValueError('%s: every job needs two training rows, every index within the %d rows' % (who, n))
-            if len(np.unique(y[a])) != 2:
-                raise ValueError('%s: a job whose training rows are of one class' % who)
-            if need_spread and np.ptp(X[a], axis=0).max() == 0:
-                raise ValueError('%s: a job whose training rows are all equal (epsilon_ = 0: every variance would be 0)' % who)
-        tr_off = np.concatenate([[0], np.cumsum([len(a) for a in tr])]).astype(np.int64)
-        va_off = np.concatenate([[0], np.cumsum([len(a) for a in va])]).astype(np.int64)
-        return X, y, tr, va, tr_off, va_off, np.ascontiguousarray(np.concatenate(tr)), np.ascontiguousarray(np.concatenate(va + [np.zeros(1, np.int32)]))
-
     @_serialized
     def lr_fit(self, X, y, jobs, seeds, C=1.0, tol=1e-4, max_iter=100):
         """Fit one L1 logistic regression per job on the GPU (mc_lr_fit: every job a workgroup of k7_lr_fit, liblinear's
         solve_l1r_lr).  jobs: [(train_rows, validation_rows)] index arrays into X / y (y in {0, 1}, both classes in every job's
         training rows); seeds: a 31-bit liblinear seed per job.  -> per job a dict: coef [d] (toward class 1), intercept, n_iter
         (Newton iterations), status (1: max_iter was reached), val_dec, val_correct, n_val."""
-        X, y, tr, va, tr_off, va_off, tr_idx, va_idx = self._simple_jobs('lr_fit', X, y, jobs, False)
+        X, y, tr, va, tr_off, va_off, tr_idx, va_idx = self._fit_jobs(X, y, jobs, 'lr_fit')
         n, d = X.shape
         nj = len(jobs)
         sd = np.asarray(seeds, dtype=np.int64)
@@ -624,7 +602,7 @@ class Device(object):
         """Fit one Gaussian naive Bayes per job on the GPU (mc_nb_fit: every job a workgroup of k7_nb_fit, GaussianNB's fit).
         jobs as lr_fit's (both classes in every job's training rows, not all of them equal).  -> per job a dict: theta [2, d],
         var [2, d] (smoothing included), epsilon, class_count [2], val_correct, n_val."""
-        X, y, tr, va, tr_off, va_off, tr_idx, va_idx = self._simple_jobs('nb_fit', X, y, jobs, True)
+        X, y, tr, va, tr_off, va_off, tr_idx, va_idx = self._fit_jobs(X, y, jobs, 'nb_fit', need_spread=True)
         n, d = X.shape
         nj = len(jobs)
         if not (var_smoothing > 0 and np.isfinite(var_smoothing)):

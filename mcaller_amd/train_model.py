@@ -91,15 +91,29 @@ def cv_jobs(labs, grps, use_groups):
     return classes, y, jobs, [(seed + 0x9E3779B97F4A7C15 * j) % (1 << 64) for j in range(6)]
 
 
-def fit_nn_on_gpu(labs, sigs, grps, use_groups, device=None, hidden=100):
-    """-> (classes, cross-validation scores, final weights dict)."""
+def _open_fit(labs, sigs, grps, use_groups, device):
+    """What every fit_*_on_gpu starts from -> (device, classes, y, the six cv_jobs, their seeds, X)."""
     from .device import get_device
     dev = device if device is not None else get_device()
     classes, y, jobs, seeds = cv_jobs(labs, grps, use_groups)
-    X = np.asarray(sigs, dtype=np.float64)
+    return dev, classes, y, jobs, seeds, np.asarray(sigs, dtype=np.float64)
+
+
+def _fold_scores(fits):
+    """Cross-validation scores of the folds' fit dicts: held-out accuracy, nan for a fold that was not run (None)."""
+    return np.array([np.nan if f is None else f['val_correct'] / float(f['n_val']) for f in fits])
+
+
+def _two_class_jobs(y, jobs):
+    """The jobs, by number, whose training rows hold both classes."""
+    return [j for j, (tr, _) in enumerate(jobs) if len(np.unique(y[tr])) == 2]
+
+
+def fit_nn_on_gpu(labs, sigs, grps, use_groups, device=None, hidden=100):
+    """-> (classes, cross-validation scores, final weights dict)."""
+    dev, classes, y, jobs, seeds, X = _open_fit(labs, sigs, grps, use_groups, device)
     fits = dev.mlp_fit(X, y, jobs, hidden=hidden, seeds=seeds)
-    scores = np.array([f['val_correct'] / float(f['n_val']) for f in fits[:5]])
-    return classes, scores, fits[5]
+    return classes, _fold_scores(fits[:5]), fits[5]
 
 
 RF_PARAMS = dict(n_trees=50, max_depth=10, max_features=4, min_samples_split=3, min_samples_leaf=2, bootstrap=True)   # train_model.py:39-45
@@ -108,14 +122,9 @@ RF_PARAMS = dict(n_trees=50, max_depth=10, max_features=4, min_samples_split=3, 
 def fit_rf_on_gpu(labs, sigs, grps, use_groups, device=None):
     """`-c RF`: the six forests of a sub-model in one mc_forest_fit call (k5_forest_fit).  -> (classes, cross-validation scores,
     final forest dict: Device.forest_fit's arrays plus n_features)."""
-    from .device import get_device
-    dev = device if device is not None else get_device()
-    classes, y, jobs, seeds = cv_jobs(labs, grps, use_groups)
-    X = np.asarray(sigs, dtype=np.float64)
+    dev, classes, y, jobs, seeds, X = _open_fit(labs, sigs, grps, use_groups, device)
     fits = dev.forest_fit(X, y, jobs, seeds=seeds, **RF_PARAMS)
-    scores = np.array([f['val_correct'] / float(f['n_val']) for f in fits[:5]])
-    fit = dict(fits[5], n_features=X.shape[1])
-    return classes, scores, fit
+    return classes, _fold_scores(fits[:5]), dict(fits[5], n_features=X.shape[1])
 
 
 def as_sklearn_estimator(fit, classes, n_samples):
@@ -264,8 +273,9 @@ def svm_plan(X, y, jobs, seed):
     device job), order (its rows), perm, platt=[(device job or None, held-out positions, constant dec)], gamma)."""
     group = lambda rows, first: np.concatenate([rows[y[rows] == first], rows[y[rows] != first]])     # noqa: E731
     device, gammas, cv = [], [], []
-    for tr, va in jobs[:5]:
-        if len(np.unique(y[tr])) < 2:
+    run = _two_class_jobs(y, jobs[:5])
+    for f, (tr, va) in enumerate(jobs[:5]):
+        if f not in run:
             cv.append(None)
             continue
         cv.append(len(device))
@@ -296,13 +306,10 @@ def svm_plan(X, y, jobs, seed):
 def fit_svm_on_gpu(labs, sigs, grps, use_groups, device=None):
     """`-c SVM`: a sub-model's eleven SMO solves in one mc_svm_fit call (k6_svm_fit), the Platt parameters by mc_svm_sigmoid_train.
     -> (classes, cross-validation scores, final fit dict: the support vectors and what SVC keeps of them)."""
-    from .device import get_device
-    dev = device if device is not None else get_device()
-    classes, y, jobs, seeds = cv_jobs(labs, grps, use_groups)
-    X = np.asarray(sigs, dtype=np.float64)
+    dev, classes, y, jobs, seeds, X = _open_fit(labs, sigs, grps, use_groups, device)
     plan = svm_plan(X, y, jobs, seeds[5])
     fits = dev.svm_fit(X, y, plan['device'], plan['gammas'], **SVM_PARAMS)
-    scores = np.array([np.nan if j is None else fits[j]['val_correct'] / float(fits[j]['n_val']) for j in plan['cv']])
+    scores = _fold_scores([None if j is None else fits[j] for j in plan['cv']])
     order = plan['order']
     dec = np.zeros(len(order))
     for job, held, const in plan['platt']:
@@ -355,16 +362,12 @@ def fit_lr_on_gpu(labs, sigs, grps, use_groups, device=None):
     2^31 - 1 (platt_seed's rule, the range of scikit-learn's draw).  A fold whose training rows hold one class scores nan, as
     cross_val_score gives for liblinear's refusal.  -> (classes, cross-validation scores, final fit dict: coef, intercept, n_iter,
     status, n_features)."""
-    from .device import get_device
-    dev = device if device is not None else get_device()
-    classes, y, jobs, seeds = cv_jobs(labs, grps, use_groups)
-    X = np.asarray(sigs, dtype=np.float64)
-    run = [j for j, (tr, _) in enumerate(jobs) if len(np.unique(y[tr])) == 2]
+    dev, classes, y, jobs, seeds, X = _open_fit(labs, sigs, grps, use_groups, device)
+    run = _two_class_jobs(y, jobs)
     fits = dict(zip(run, dev.lr_fit(X, y, [jobs[j] for j in run], [platt_seed(seeds[j]) for j in run], **LR_PARAMS)))
-    scores = np.array([fits[f]['val_correct'] / float(fits[f]['n_val']) if f in fits else np.nan for f in range(5)])
     final = fits[5]
     fit = dict(coef=final['coef'], intercept=final['intercept'], n_iter=final['n_iter'], status=final['status'], n_features=X.shape[1])
-    return classes, scores, fit
+    return classes, _fold_scores([fits.get(f) for f in range(5)]), fit
 
 
 NB_PARAMS = dict(var_smoothing=1e-9)                              # GaussianNB() (train_model.py:59-60)
@@ -374,23 +377,18 @@ def fit_nb_on_gpu(labs, sigs, grps, use_groups, device=None):
     """`-c NBC`: a sub-model's six GaussianNB fits in one mc_nb_fit call (k7_nb_fit).  A fold whose training rows hold one class
     predicts that class everywhere, as the fitted GaussianNB would: its score is the share of held-out rows in it.  -> (classes,
     cross-validation scores, final fit dict: theta, var, epsilon, class_count, class_prior, n_features)."""
-    from .device import get_device
-    dev = device if device is not None else get_device()
-    classes, y, jobs, seeds = cv_jobs(labs, grps, use_groups)
-    X = np.asarray(sigs, dtype=np.float64)
-    run = [j for j, (tr, _) in enumerate(jobs) if len(np.unique(y[tr])) == 2]
+    dev, classes, y, jobs, seeds, X = _open_fit(labs, sigs, grps, use_groups, device)
+    run = _two_class_jobs(y, jobs)
     fits = dict(zip(run, dev.nb_fit(X, y, [jobs[j] for j in run], **NB_PARAMS)))
-    scores = []
+    scores = _fold_scores([fits.get(f) for f in range(5)])
     for f, (tr, va) in enumerate(jobs[:5]):
-        if f in fits:
-            scores.append(fits[f]['val_correct'] / float(fits[f]['n_val']))
-        else:
-            scores.append(float(np.mean(y[va] == y[tr[0]])))
+        if f not in fits:
+            scores[f] = float(np.mean(y[va] == y[tr[0]]))
     final = fits[5]
     count = final['class_count'].astype(np.float64)
     fit = dict(theta=final['theta'], var=final['var'], epsilon=final['epsilon'], class_count=count, class_prior=count / count.sum(),
                n_features=X.shape[1])
-    return classes, np.array(scores), fit
+    return classes, scores, fit
 
 
 def as_sklearn_logistic(fit, classes):
@@ -420,44 +418,43 @@ def as_sklearn_gnb(fit, classes):
     return m
 
 
+def _classifiers():
+    """What differs between the classifiers of `-c`, by name: the fit, the scikit-learn estimator of a fit (fit, classes, rows it was
+    fitted on) and the arrays of a fit in the neutral `.npz` (model_io reads them).  Built when asked for, so that a fit_*_on_gpu
+    replaced in this module is the one that runs."""
+    return {
+        'NN': dict(fit=fit_nn_on_gpu, as_sklearn=as_sklearn_estimator,
+                   npz=lambda fit: {'W1': fit['W1'], 'b1': fit['b1'], 'W2': fit['W2'], 'b2': np.array([fit['b2']])}),
+        'RF': dict(fit=fit_rf_on_gpu, as_sklearn=lambda fit, classes, n: as_sklearn_forest(fit, classes),
+                   npz=lambda fit: dict({name: fit[name] for name in ('tree_off', 'left', 'right', 'feature', 'threshold', 'value')},
+                                        n_features=np.array([fit['n_features']]))),
+        'SVM': dict(fit=fit_svm_on_gpu, as_sklearn=lambda fit, classes, n: as_sklearn_svc(fit, classes),
+                    npz=lambda fit: {'sv': fit['sv'], 'dual_coef': fit['dual_coef'],
+                                     'svm_params': np.array([fit['gamma'], fit['intercept'], fit['probA'], fit['probB']], dtype=np.float64)}),
+        'LR': dict(fit=fit_lr_on_gpu, as_sklearn=lambda fit, classes, n: as_sklearn_logistic(fit, classes),
+                   npz=lambda fit: {'lr_coef': np.asarray(fit['coef'], dtype=np.float64),
+                                    'lr_intercept': np.array([fit['intercept']], dtype=np.float64)}),
+        'NBC': dict(fit=fit_nb_on_gpu, as_sklearn=lambda fit, classes, n: as_sklearn_gnb(fit, classes),
+                    npz=lambda fit: {'nb_theta': fit['theta'], 'nb_var': fit['var'], 'nb_prior': fit['class_prior']}),
+    }
+
+
 def write_models(models, classes_of, n_of, modelfile, classifier='NN'):
+    clf = _classifiers()[classifier]
     try:
         import sklearn  # noqa: F401
         have_sklearn = True
     except ImportError:
         have_sklearn = False
     if have_sklearn:
-        if classifier == 'RF':
-            out = {key: as_sklearn_forest(fit, classes_of[key]) for key, fit in models.items()}
-        elif classifier == 'SVM':
-            out = {key: as_sklearn_svc(fit, classes_of[key]) for key, fit in models.items()}
-        elif classifier == 'LR':
-            out = {key: as_sklearn_logistic(fit, classes_of[key]) for key, fit in models.items()}
-        elif classifier == 'NBC':
-            out = {key: as_sklearn_gnb(fit, classes_of[key]) for key, fit in models.items()}
-        else:
-            out = {key: as_sklearn_estimator(fit, classes_of[key], n_of[key]) for key, fit in models.items()}
+        out = {key: clf['as_sklearn'](fit, classes_of[key], n_of.get(key)) for key, fit in models.items()}    # (n: the NN's t_ only)
         with open(modelfile, 'wb') as modfi:
             pickle.dump(out, modfi)
         return out
     arrays = {'__is_dict__': np.array([1])}
     for key, fit in models.items():
-        if classifier == 'RF':
-            for name in ('tree_off', 'left', 'right', 'feature', 'threshold', 'value'):
-                arrays[key + '.' + name] = fit[name]
-            arrays[key + '.n_features'] = np.array([fit['n_features']])
-        elif classifier == 'SVM':
-            arrays[key + '.sv'], arrays[key + '.dual_coef'] = fit['sv'], fit['dual_coef']
-            arrays[key + '.svm_params'] = np.array([fit['gamma'], fit['intercept'], fit['probA'], fit['probB']], dtype=np.float64)
-        elif classifier == 'LR':
-            arrays[key + '.lr_coef'] = np.asarray(fit['coef'], dtype=np.float64)
-            arrays[key + '.lr_intercept'] = np.array([fit['intercept']], dtype=np.float64)
-        elif classifier == 'NBC':
-            arrays[key + '.nb_theta'], arrays[key + '.nb_var'] = fit['theta'], fit['var']
-            arrays[key + '.nb_prior'] = fit['class_prior']
-        else:
-            arrays[key + '.W1'], arrays[key + '.b1'] = fit['W1'], fit['b1']
-            arrays[key + '.W2'], arrays[key + '.b2'] = fit['W2'], np.array([fit['b2']])
+        for name, array in clf['npz'](fit).items():
+            arrays[key + '.' + name] = array
         arrays[key + '.classes'] = np.array(classes_of[key])
     with open(modelfile, 'wb') as modfi:
         np.savez(modfi, **arrays)
@@ -468,8 +465,7 @@ def train_classifier(signals, groups, modelfile, classifier='NN', plot=False, de
     if plot:
         raise NotImplementedError('--plot_training is not supported (it raises NameError in the reference: the import '
                                   'of plotlib is commented out, train_model.py:3,:108)')
-    fit_on_gpu = {'NN': fit_nn_on_gpu, 'RF': fit_rf_on_gpu, 'SVM': fit_svm_on_gpu, 'LR': fit_lr_on_gpu, 'NBC': fit_nb_on_gpu}.get(classifier)
-    if fit_on_gpu is None:
+    if classifier not in _classifiers():
         raise ValueError('unknown classifier ' + str(classifier))
     models, classes_of, n_of = {}, {}, {}
     for twobase_model in signals:
@@ -477,7 +473,7 @@ def train_classifier(signals, groups, modelfile, classifier='NN', plot=False, de
         print(labs[:10])
         print(sigs[:10])
         print(grps[:10])
-        classes, scores, fit = fit_on_gpu(labs, sigs, grps, bool(groups), device=device)
+        classes, scores, fit = _classifiers()[classifier]['fit'](labs, sigs, grps, bool(groups), device=device)
         print('%s %s model scores: %s' % (classifier, twobase_model, ','.join([str(s) for s in scores])))
         print('Cross validation accuracy: %0.2f (+/- %0.2f)' % (scores.mean(), scores.std() * 2))
         models[twobase_model], classes_of[twobase_model], n_of[twobase_model] = fit, classes, len(labs)

@@ -4,6 +4,7 @@ import gzip
 import json
 import os
 import subprocess
+import sys
 
 import numpy as np
 
@@ -14,6 +15,27 @@ MODEL_STEMS = {'r95': 'r95_twobase_model_NN_6_m6A', 'r94': 'r94_model_NN_6_m6A',
                'CAAY': 'CAAYNNNNNRTAC_model_6_m6A', 'CRAA': 'CRAANNNNNNNTGC_model_6_m6A'}
 
 _oracle = None
+
+
+def block_sklearn(monkeypatch):
+    """Make `import sklearn` (and every submodule already loaded) fail with ImportError for the rest of the test."""
+    for name in list(sys.modules):
+        if name == 'sklearn' or name.startswith('sklearn.'):
+            monkeypatch.setitem(sys.modules, name, None)
+    monkeypatch.setitem(sys.modules, 'sklearn', None)
+
+
+def fit_data(n, d, seed, rounding=None):
+    """The seeded matrix and labels of the SVM, LR and NBC device tests (`data` there): every column rounded."""
+    rng = np.random.default_rng(seed)
+    X = rng.normal(size=(n, d)) * np.linspace(0.5, 3.0, d)
+    if d > 1:
+        X[:, -1] = 7.0 + 0.1 * rng.integers(0, 4, n)               # (a read-quality-like column: few distinct values)
+    if rounding is not None:
+        X = np.round(X, rounding)
+    z = X[:, 0] - 0.7 * X[:, min(1, d - 1)] + 0.3 * np.sin(3 * X[:, 0])
+    y = (rng.random(n) < 1.0 / (1.0 + np.exp(-2.0 * z))).astype(np.uint8)
+    return X, y
 
 
 def oracle_lib():

@@ -1,12 +1,12 @@
 """The random-forest fit's CPU restatement (tests/forest_fit_oracle.py) against scikit-learn -- exactly where scikit-learn's own
 randomness cannot matter, statistically where it can -- and the model files `--train -c RF` writes (no GPU needed)."""
 import pickle
-import sys
 
 import numpy as np
 import pytest
 
 from tests import forest_fit_oracle as fo
+from tests.helpers import block_sklearn
 
 LEAF_MIN = fo.REFERENCE['min_samples_leaf']
 
@@ -170,13 +170,6 @@ def as_fit(trees, d):
     return fit
 
 
-def _block_sklearn(monkeypatch):
-    for name in list(sys.modules):
-        if name == 'sklearn' or name.startswith('sklearn.'):
-            monkeypatch.setitem(sys.modules, name, None)
-    monkeypatch.setitem(sys.modules, 'sklearn', None)
-
-
 @pytest.fixture(scope='module')
 def small_forest():
     X, y = seven_features(800, 8)
@@ -197,7 +190,7 @@ def test_written_pickle_is_a_sklearn_forest_and_loads_without_sklearn(small_fore
     P = rf.predict_proba(X)
     assert (P[:, 1] == p1).all() and list(rf.classes_) == ['A', 'm6A']
     assert all(e.tree_.node_count == len(t['left']) for e, t in zip(rf.estimators_, trees))
-    _block_sklearn(monkeypatch)
+    block_sklearn(monkeypatch)
     ms = load_model_file(path)
     w = ms.models['general']
     assert ms.twobase and w.kind == 'forest' and w.n_trees == 12 and w.n_in == 7 and w.classes == ['A', 'm6A']
@@ -216,7 +209,7 @@ def test_npz_written_without_sklearn_loads_to_the_same_forest(small_forest, tmp_
         want = load_model_file(pk).models['general']
     except ImportError:
         pass
-    _block_sklearn(monkeypatch)
+    block_sklearn(monkeypatch)
     path = str(tmp_path / 'rf_model')
     train_model.write_models({'general': as_fit(trees, 7)}, {'general': ['A', 'm6A']}, {'general': len(X)}, path, 'RF')
     assert open(path, 'rb').read(2) == b'PK'
@@ -241,7 +234,7 @@ def test_rf_training_no_longer_needs_sklearn(monkeypatch):
     """`--train -c RF` goes to the GPU fitter, never to scikit-learn (which is blocked here): without a GPU the call fails in
     the device layer, not with the ImportError of the scikit-learn path."""
     from mcaller_amd import train_model
-    _block_sklearn(monkeypatch)
+    block_sklearn(monkeypatch)
     called = {}
 
     def fake_fit(labs, sigs, grps, use_groups, device=None):

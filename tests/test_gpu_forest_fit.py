@@ -5,13 +5,13 @@ import io
 import os
 import pickle
 import shutil
-import sys
 
 import numpy as np
 import pytest
 
 from tests import forest_fit_oracle as fo
 from tests import helpers as H
+from tests.helpers import block_sklearn
 
 pytestmark = pytest.mark.gpu
 FIELDS = ('left', 'right', 'feature', 'threshold', 'value', 'impurity', 'n_node_samples', 'weighted_n_node_samples')
@@ -128,13 +128,6 @@ def test_fitted_forest_scored_by_k3_forest_equals_the_oracle_and_sklearn(dev):
     assert (rf.predict_proba(Xq)[:, 1] == want).all()
 
 
-def _block_sklearn(monkeypatch):
-    for name in list(sys.modules):
-        if name == 'sklearn' or name.startswith('sklearn.'):
-            monkeypatch.setitem(sys.modules, name, None)
-    monkeypatch.setitem(sys.modules, 'sklearn', None)
-
-
 @pytest.mark.parametrize('with_sklearn', [True, False])
 def test_train_rf_cli_then_score_with_the_written_file(tmp_path, monkeypatch, with_sklearn):
     """`mCaller --train -c RF` on labelled rows: the reference's lines, the model file (a pickle, or the neutral .npz without
@@ -143,7 +136,7 @@ def test_train_rf_cli_then_score_with_the_written_file(tmp_path, monkeypatch, wi
     if with_sklearn:
         pytest.importorskip('sklearn')
     else:
-        _block_sklearn(monkeypatch)
+        block_sklearn(monkeypatch)
     from mcaller_amd import mCaller, train_model
     from mcaller_amd.load_mCaller_data import tsv2matrix
     from mcaller_amd.model_io import load_model_file

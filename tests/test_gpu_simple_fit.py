@@ -6,7 +6,6 @@ import io
 import os
 import pickle
 import shutil
-import sys
 
 import numpy as np
 import pytest
@@ -15,6 +14,7 @@ from oracle import clf_oracle
 from tests import helpers as H
 from tests import lr_fit_oracle as lo
 from tests import nb_fit_oracle as no
+from tests.helpers import block_sklearn, fit_data as data
 
 pytestmark = pytest.mark.gpu
 
@@ -25,18 +25,6 @@ def dev():
     d = Device(0)
     yield d
     d.close()
-
-
-def data(n, d, seed, rounding=None):
-    rng = np.random.default_rng(seed)
-    X = rng.normal(size=(n, d)) * np.linspace(0.5, 3.0, d)
-    if d > 1:
-        X[:, -1] = 7.0 + 0.1 * rng.integers(0, 4, n)               # (a read-quality-like column: few distinct values)
-    if rounding is not None:
-        X = np.round(X, rounding)
-    z = X[:, 0] - 0.7 * X[:, min(1, d - 1)] + 0.3 * np.sin(3 * X[:, 0])
-    y = (rng.random(n) < 1.0 / (1.0 + np.exp(-2.0 * z))).astype(np.uint8)
-    return X, y
 
 
 def some_jobs(n, y):
@@ -199,13 +187,6 @@ def test_bad_parameters_raise_and_never_fault(dev):
     assert ok['n_iter'] >= 1
 
 
-def _block_sklearn(monkeypatch):
-    for name in list(sys.modules):
-        if name == 'sklearn' or name.startswith('sklearn.'):
-            monkeypatch.setitem(sys.modules, name, None)
-    monkeypatch.setitem(sys.modules, 'sklearn', None)
-
-
 @pytest.mark.parametrize('with_sklearn', [True, False])
 @pytest.mark.parametrize('clf', ['LR', 'NBC'])
 def test_train_cli_then_score_with_the_written_file(tmp_path, monkeypatch, with_sklearn, clf):
@@ -215,7 +196,7 @@ def test_train_cli_then_score_with_the_written_file(tmp_path, monkeypatch, with_
     if with_sklearn:
         pytest.importorskip('sklearn')
     else:
-        _block_sklearn(monkeypatch)
+        block_sklearn(monkeypatch)
     from mcaller_amd import mCaller, train_model
     from mcaller_amd.load_mCaller_data import tsv2matrix
     from mcaller_amd.model_io import load_model_file

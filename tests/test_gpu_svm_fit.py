@@ -5,7 +5,6 @@ import io
 import os
 import pickle
 import shutil
-import sys
 
 import numpy as np
 import pytest
@@ -13,6 +12,7 @@ import pytest
 from tests import helpers as H
 from tests import svm_fit_oracle as so
 from tests import svm_oracle
+from tests.helpers import block_sklearn, fit_data as data
 
 pytestmark = pytest.mark.gpu
 BAND = 5e-3
@@ -24,18 +24,6 @@ def dev():
     d = Device(0)
     yield d
     d.close()
-
-
-def data(n, d, seed, rounding=None):
-    rng = np.random.default_rng(seed)
-    X = rng.normal(size=(n, d)) * np.linspace(0.5, 3.0, d)
-    if d > 1:
-        X[:, -1] = 7.0 + 0.1 * rng.integers(0, 4, n)               # (a read-quality-like column: few distinct values)
-    if rounding is not None:
-        X = np.round(X, rounding)
-    z = X[:, 0] - 0.7 * X[:, min(1, d - 1)] + 0.3 * np.sin(3 * X[:, 0])
-    y = (rng.random(n) < 1.0 / (1.0 + np.exp(-2.0 * z))).astype(np.uint8)
-    return X, y
 
 
 def assert_solve_matches(X, y, train, val, gamma, got, want):
@@ -174,13 +162,6 @@ def test_bad_parameters_raise_and_never_fault(dev):
     assert capped['status'] == 1 and capped['n_iter'] == 3
 
 
-def _block_sklearn(monkeypatch):
-    for name in list(sys.modules):
-        if name == 'sklearn' or name.startswith('sklearn.'):
-            monkeypatch.setitem(sys.modules, name, None)
-    monkeypatch.setitem(sys.modules, 'sklearn', None)
-
-
 @pytest.mark.parametrize('with_sklearn', [True, False])
 def test_train_svm_cli_then_score_with_the_written_file(tmp_path, monkeypatch, with_sklearn):
     """`mCaller --train -c SVM` on labelled rows: the reference's lines, the model file (a pickle, or the neutral .npz without
@@ -189,7 +170,7 @@ def test_train_svm_cli_then_score_with_the_written_file(tmp_path, monkeypatch, w
     if with_sklearn:
         pytest.importorskip('sklearn')
     else:
-        _block_sklearn(monkeypatch)
+        block_sklearn(monkeypatch)
     from mcaller_amd import mCaller, train_model
     from mcaller_amd.load_mCaller_data import tsv2matrix
     from mcaller_amd.model_io import load_model_file

@@ -91,3 +91,45 @@ def test_more_fits_than_xcds_and_repeatability(dev):
         assert np.array_equal(got[j]['W1'], again[j]['W1']) and np.array_equal(got[j]['loss_curve'], again[j]['loss_curve'])
     # (the library reads MCALLER_FIT_WGS once per process: other group sizes are exercised by tools/config5.py runs under that
     # variable -- profiles/README.md -- and by the build macro MC_FIT_GROUPS)
+
+
+def test_bad_parameters_raise_and_never_fault(dev):
+    """What mc_mlp_fit refuses, it refuses before it touches the device (-12 and a message, through the C ABI): a NULL pointer, an
+    index outside the matrix, a hidden width beyond two units per lane.  A fit afterwards still works."""
+    import ctypes as C
+    from mcaller_amd import _lib
+    z = np.load(os.path.join(TRAIN, 'n1000_h100.npz'))
+    X, y = np.ascontiguousarray(z['X'][:200], dtype=np.float64), np.ascontiguousarray(z['y'][:200], dtype=np.uint8)
+    n, d, H_ = len(y), X.shape[1], 16
+    L = _lib.lib()
+    off = np.array([0, n], np.int64)
+    rows = np.arange(n, dtype=np.int32)
+    out = dict(W1=np.zeros((d, H_)), b1=np.zeros(H_), W2=np.zeros(H_), b2=np.zeros(1), curve=np.zeros(4), n_iter=np.zeros(1, np.int32),
+               correct=np.zeros(1, np.int64))
+
+    def call(hidden=H_, train_off=off, train_idx=rows, val_idx=rows):
+        prm = _lib.FitParams(d, hidden, 200, 4, 10, 1, 0.001, 0.001, 0.9, 0.999, 1e-8, 1e-4, 1)
+        ptr = lambda a: None if a is None else _lib._ptr(a)                        # noqa: E731
+        rc = L.mc_mlp_fit(dev._ctx, C.byref(prm), _lib._ptr(X), _lib._ptr(y), n, 1, ptr(train_off), ptr(train_idx), _lib._ptr(off),
+                          ptr(val_idx), None, None, _lib._ptr(out['W1']), _lib._ptr(out['b1']), _lib._ptr(out['W2']), _lib._ptr(out['b2']),
+                          _lib._ptr(out['curve']), _lib._ptr(out['n_iter']), _lib._ptr(out['correct']))
+        return rc, L.mc_last_error()
+
+    rc, msg = call(train_off=None)
+    assert rc == -12 and b'mc_mlp_fit: a required pointer is NULL' in msg
+    rc, msg = call(val_idx=None)
+    assert rc == -12 and b'mc_mlp_fit: a required pointer is NULL' in msg
+    bad = rows.copy()
+    bad[7] = n
+    rc, msg = call(train_idx=bad)
+    assert rc == -12 and b'mc_mlp_fit: row index out of range' in msg
+    bad[7] = -1
+    rc, msg = call(val_idx=bad)
+    assert rc == -12 and b'mc_mlp_fit: row index out of range' in msg
+    rc, msg = call(hidden=129)
+    assert rc == -12 and b'mc_mlp_fit: unsupported shape' in msg
+    rc, msg = call()
+    assert rc == 0 and out['n_iter'][0] == 4 and np.isfinite(out['W1']).all() and np.abs(out['W1']).max() > 0
+    assert 0 <= out['correct'][0] <= n
+    again = dev.mlp_fit(X, y, [(rows, rows)], hidden=H_, max_iter=4, seed=1)[0]
+    assert (again['W1'] == out['W1']).all() and again['val_correct'] == out['correct'][0]

@@ -1,7 +1,6 @@
 """The `--train -c LR` / `-c NBC` fits' CPU restatements (tests/lr_fit_oracle.py, tests/nb_fit_oracle.py) against scikit-learn, the
 host side of the fits (train_model.fit_lr_on_gpu / fit_nb_on_gpu on a stand-in device that runs the oracles), and the writers and
 loader of the fitted models.  No GPU: the device is held to the oracles in tests/test_gpu_simple_fit.py."""
-import sys
 import warnings
 
 import numpy as np
@@ -10,6 +9,7 @@ import pytest
 from oracle import clf_oracle
 from tests import lr_fit_oracle as lo
 from tests import nb_fit_oracle as no
+from tests.helpers import block_sklearn
 
 
 def data(n, d, seed, rounding=None):
@@ -197,18 +197,11 @@ def test_estimators_predict_what_the_weights_score():
     assert np.abs(est.predict_proba(Xq)[:, 1] - clf_oracle.gnb_proba(g.theta, g.var, g.prior, Xq)).max() <= 1e-12
 
 
-def _block_sklearn(monkeypatch):
-    for name in list(sys.modules):
-        if name == 'sklearn' or name.startswith('sklearn.'):
-            monkeypatch.setitem(sys.modules, name, None)
-    monkeypatch.setitem(sys.modules, 'sklearn', None)
-
-
 def test_npz_round_trips_without_sklearn(tmp_path, monkeypatch):
     from mcaller_amd import train_model as tm
     from mcaller_amd.model_io import load_model_file, shipped_model
     X, classes, lr, nb = final_fits()
-    _block_sklearn(monkeypatch)
+    block_sklearn(monkeypatch)
     for clf, fit in (('LR', lr), ('NBC', nb)):
         path = str(tmp_path / ('m_%s.pkl' % clf))
         tm.write_models({'general': fit}, {'general': classes}, {'general': len(X)}, path, clf)
@@ -228,7 +221,7 @@ def test_npz_round_trips_without_sklearn(tmp_path, monkeypatch):
 def test_lr_and_nbc_training_no_longer_need_sklearn(clf, monkeypatch, tmp_path):
     """`--train -c LR|NBC` goes to the GPU fitters, never to scikit-learn (blocked here; the call raised ImportError before)."""
     from mcaller_amd import train_model
-    _block_sklearn(monkeypatch)
+    block_sklearn(monkeypatch)
     called = {}
     real = train_model.fit_lr_on_gpu if clf == 'LR' else train_model.fit_nb_on_gpu
 

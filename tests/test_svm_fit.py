@@ -1,13 +1,13 @@
 """The `--train -c SVM` fit's CPU restatement (tests/svm_fit_oracle.py) against scikit-learn's SVC, and the writers and loader of
 the fitted model.  No GPU: the device is held to the oracle in tests/test_gpu_svm_fit.py."""
 import pickle
-import sys
 
 import numpy as np
 import pytest
 
 from tests import svm_fit_oracle as so
 from tests import svm_oracle
+from tests.helpers import block_sklearn
 
 BAND = 5e-3
 
@@ -208,18 +208,11 @@ def test_as_sklearn_svc_round_trips_and_carries_every_attribute():
     assert est.predict(probe[:5]).dtype == ref.predict(probe[:5]).dtype
 
 
-def _block_sklearn(monkeypatch):
-    for name in list(sys.modules):
-        if name == 'sklearn' or name.startswith('sklearn.'):
-            monkeypatch.setitem(sys.modules, name, None)
-    monkeypatch.setitem(sys.modules, 'sklearn', None)
-
-
 def test_the_svm_npz_round_trips_through_model_io(tmp_path, monkeypatch):
     from mcaller_amd.model_io import load_model_file
     from mcaller_amd.train_model import write_models
     X, y, labs, sub = _oracle_fit(300, 4, 9)
-    _block_sklearn(monkeypatch)
+    block_sklearn(monkeypatch)
     path = str(tmp_path / 'm.npz')
     write_models({'general': sub['fit'], 'AC': sub['fit']}, {'general': ['A', 'm6A'], 'AC': ['A', 'm6A']}, {}, path, 'SVM')
     assert open(path, 'rb').read(2) == b'PK'
