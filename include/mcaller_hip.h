@@ -276,7 +276,7 @@ typedef struct mc_params {
 } mc_params;
 
 /* How the pass handed out last by mc_wait_records ran: *fused_room > 0 -- scan, ordering and emit as ONE kernel with that many
- * record slots per 1024-row piece (dense references: k1_fused; the slots a piece does not fill never reach the host);
+ * record slots per 960-row piece (dense references: k1_fused; the slots a piece does not fill never reach the host);
  * *rerun != 0 -- the pipelined pass could not be finished as enqueued (record room too small, an irregular read, a row that
  * contradicts what a block was classified on) and was repeated synchronously inside mc_wait_records. */
 int mc_last_pass_info(mc_ctx *ctx, int32_t *fused_room, int32_t *rerun);

@@ -1,5 +1,5 @@
 """The fused pass of a dense reference (k1_fused, mcaller_amd/csrc/mc_fused.hip): scan, ordering and emit of a pipelined pass over
-a one-base motif as ONE kernel with fixed room per 1024-row piece -- against the C oracle (the literal sequential machine,
+a one-base motif as ONE kernel with fixed room per 960-row piece (FT) -- against the C oracle (the literal sequential machine,
 extract_contexts.py:147-291), through the C ABI.  Every comparison also asks the library HOW the pass ran (mc_last_pass_info):
 a pass that fell back to the scan + emit pair would pass these tests without testing anything.  Runs on a real MI355X only."""
 import numpy as np

@@ -6,7 +6,10 @@ few hundred rows: they never cross a chunk.)  usage: fuzz_tables.py [n_tables] [
 ("sparse": the same tables under motifs of three to five bases -- k1_scan<64>'s candidate lists, k1_emit;
 "stalls": dense and sparse motifs over tables with stalls -- rows repeated 40-300 times: windows beyond what the emit looks back,
 slots of more than 128 events -- and gaps of the model -- 64-400 filtered rows in a row --, SCORED, pipelined first: what the side
-stream's one kernel finishes row by row for its own records, the rows the emit predicted for them, the special closer behind a gap)"""
+stream's one kernel finishes row by row for its own records, the rows the emit predicted for them, the special closer behind a gap)
+Random tables meet a cut only when the generator happens to put something on it (here only the table's END is aimed: around the
+multiples of a piece of k1_fused, 960 rows, of a chunk and of a tile).  The deterministic edges -- every kind of event on every cut --
+are in the suite: tests/edge_tables.py, tests/test_edge_tables.py, tests/test_gpu_edges.py."""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
@@ -35,7 +38,7 @@ for i in range(n_tables):
     base = 'A' if 'A' in motif else 'C'
     lo = int(rng.choice([8, 30, 120, 600, 3000]))
     read_len = (lo, lo * int(rng.integers(2, 12)))
-    around = int(rng.choice([1024, 2048, 3072, 4096, 10240, 50000, 200000]))
+    around = int(rng.choice([960, 1024, 1920, 2048, 3072, 4096, 4800, 10240, 15360, 50000, 200000]))
     n = max(50, around + int(rng.integers(-40, 41)) if rng.random() < 0.7 else int(rng.integers(100, 300000)))
     k = int(rng.choice([6, 6, 6, 4, 5, 7, 8]))
     skip = int(rng.integers(0, min(3, (k - 1) // 2 + 1)))
