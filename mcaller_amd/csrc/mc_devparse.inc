@@ -1,4 +1,4 @@
-// The eventalign text parsed ON THE GPU (included by mc_stream.hip; C ABI: mc_ctx_parse_begin / _end / _finish).
+// The eventalign text parsed ON THE GPU (included by mc_tables.hip, and by no other unit: the kernels sit in an unnamed namespace; C ABI: mc_ctx_parse_begin / _end / _finish).
 //
 // What it replaces: the row ingest of the reference's loop, extract_contexts.py:140-152 -- `line.split()[:12]`, int(), float(),
 // the two k-mer comparisons -- which mc_parse.cpp does on the host with every core the process may use.  On a GPU box the
@@ -27,37 +27,7 @@ constexpr int KP_ST_ROW = 0, KP_ST_SKIP = 1, KP_ST_UNKNOWN = 2, KP_ST_HOST = 3;
 constexpr int KP_MAX_UNKNOWN = 4096;
 constexpr int KP_EAGER_SEGS = 4096, KP_EAGER_UNKNOWN = 64;   // what travels to the host with the head, unasked
 
-struct KpHead {                 // device-side result block of one parse (copied to the host as it is)
-    long long n_newlines, n_lines, n_rows;
-    int n_seg, n_unknown;
-    long long first_host_line;  // first line that needs the host parser (LLONG_MAX: none)
-    int overflow;               // bit 0: more lines than the scratch holds, 1: segments, 2: unknown-contig lines
-    int pad;
-};
-// (struct KpSeg: mc_dev.h -- the row writer on the device reads the names where the parser found them)
-struct KpUnknown { long long line; long long off; int len; int pad; };
-
-struct KpScratch {              // line-indexed (kp_parse -> kp_place), shared by all slots: the parses are ordered on one stream
-    long long *line_start = nullptr;
-    int32_t *pos = nullptr, *idx = nullptr, *ev = nullptr, *mu = nullptr, *contig = nullptr;
-    uint32_t *name_off = nullptr;
-    uint16_t *name_len = nullptr;
-    uint8_t *fl = nullptr, *status = nullptr;
-    long long *tile_cnt = nullptr, *tile_off = nullptr;      // newline tiles, then row blocks
-    int64_t cap_lines = 0, cap_tiles = 0;
-    std::vector<void *> allocs;
-};
-
-struct KpContigs {              // the reference's contig names on the device: open addressing, FNV-1a
-    uint32_t *hash = nullptr;   // table_size entries: hash | 0 = empty (a zero hash is stored as 1)
-    int32_t *id = nullptr;
-    uint32_t *name_off = nullptr;   // per contig id
-    uint32_t *name_len = nullptr;
-    char *chars = nullptr;
-    int table_mask = 0, n = 0;
-    std::vector<void *> allocs;
-    std::vector<std::string> names; // what the table was built from
-};
+// (the host-side structures KpHead, KpUnknown, KpScratch, KpContigs: mc_ctx.h; struct KpSeg: mc_dev.h)
 
 __device__ __forceinline__ bool kp_is_ws(unsigned c) {      // ASCII subset of what str.split() treats as whitespace
     return c == ' ' || (c >= 9 && c <= 13) || (c >= 28 && c <= 31);

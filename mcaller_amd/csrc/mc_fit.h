@@ -2,7 +2,7 @@
 // point, and two small device helpers.  Included by those four units only, hence the unnamed namespace: nothing here is linked
 // across units.  An entry point refuses its arguments (-12) before it touches the device, then
 //
-//     Pool pool("mc_x_fit");                      // device allocations, freed when the entry point returns by any path
+//     Pool pool("mc_x_fit");                      // device allocations (mc_own.h), freed when the entry point returns by any path
 //     T *d = pool.get<T>(n); ...
 //     if (!pool.ok) return -10;                   // (the message is set)
 //     Xfer x("mc_x_fit", stream);                 // the first HIP error on this stream; every member is a no-op after one
@@ -18,8 +18,8 @@
 #include <vector>
 
 #include "../../include/mcaller_hip.h"
+#include "mc_own.h"
 
-void mc_set_error(const char *fmt, ...);
 int mc_internal_device(const mc_ctx *c);
 hipStream_t mc_internal_stream(const mc_ctx *c);
 
@@ -43,26 +43,6 @@ __device__ __forceinline__ double wave_sum(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
 }
-
-struct Pool {
-    const char *who;
-    bool ok = true;                             // false once an allocation has failed
-    std::vector<void *> p;
-    explicit Pool(const char *w) : who(w) {}
-    Pool(const Pool &) = delete;
-    ~Pool() { for (void *q : p) (void)hipFree(q); }
-    template <typename T>
-    T *get(size_t n) {
-        void *q = nullptr;
-        if (hipMalloc(&q, std::max<size_t>(n * sizeof(T), 256)) != hipSuccess) {
-            mc_set_error("%s: hipMalloc of %zu bytes failed", who, n * sizeof(T));
-            ok = false;
-            return nullptr;
-        }
-        p.push_back(q);
-        return (T *)q;
-    }
-};
 
 struct Xfer {
     const char *who;

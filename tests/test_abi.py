@@ -49,3 +49,17 @@ def test_every_library_call_from_python_has_argtypes():
     called = set(re.findall(r'\b(?:lib\(\)|L|_lib\.lib\(\))\.(mc_[a-z0-9_]+)\(', src))
     typed = set(re.findall(r'L\.(mc_[a-z0-9_]+)\.argtypes', open(os.path.join(here, '_lib.py')).read()))
     assert called - typed <= {'mc_host_cores', 'mc_last_error', 'mc_repr_fixed4'}, sorted(called - typed)
+
+
+def test_every_kernel_of_the_pass_path_is_in_the_hashed_sources():
+    """bench.KERNEL_SOURCES is what ties a PMC traffic figure to the kernels it was measured on: every file it names exists, and every
+    file under csrc/ that defines a kernel is on it, or is one of the --train fit units (which no pass runs)."""
+    import bench
+    fits = {'mc_train.hip', 'mc_forest_fit.hip', 'mc_svm_fit.hip', 'mc_simple_fit.hip', 'mc_fit.h'}
+    missing = [f for f in bench.KERNEL_SOURCES if not os.path.isfile(os.path.join(H.REPO, f))]
+    assert not missing, missing
+    hashed = {os.path.basename(f) for f in bench.KERNEL_SOURCES}
+    csrc = os.path.join(H.REPO, 'mcaller_amd', 'csrc')
+    with_kernels = {f for f in os.listdir(csrc) if os.path.isfile(os.path.join(csrc, f)) and '__global__' in open(os.path.join(csrc, f), errors='replace').read()}
+    assert len(with_kernels) >= 10
+    assert with_kernels <= hashed | fits, sorted(with_kernels - hashed - fits)

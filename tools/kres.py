@@ -9,7 +9,7 @@ import sys
 import tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-UNITS = ['mc_k0', 'mc_scan', 'mc_emit', 'mc_fused', 'mc_literal', 'mc_classify', 'mc_train', 'mc_forest_fit', 'mc_svm_fit', 'mc_simple_fit', 'mc_stream']
+UNITS = ['mc_k0', 'mc_scan', 'mc_emit', 'mc_fused', 'mc_literal', 'mc_classify', 'mc_train', 'mc_forest_fit', 'mc_svm_fit', 'mc_simple_fit', 'mc_stream', 'mc_tables']
 
 
 def report(src_dir, unit):
@@ -46,9 +46,14 @@ def main():
         subprocess.check_call('git -C %s archive %s mcaller_amd/csrc include | tar -x -C %s' % (REPO, rev, old_dir), shell=True)
     keys = ['VGPRs', 'TotalSGPRs', 'VGPRs Spill', 'SGPRs Spill', 'ScratchSize', 'LDS Size', 'Occupancy']
     print('%-44s %s' % ('kernel', ' '.join('%12s' % k for k in keys)))
+    # (the old figures are matched by kernel name across ALL the revision's units: a kernel may have moved to another unit)
+    old = {}
+    if old_dir:
+        for u in UNITS:
+            if os.path.exists(os.path.join(old_dir, 'mcaller_amd', 'csrc', u + '.hip')):
+                old.update(report(old_dir, u))
     for u in units:
         new = report(REPO, u)
-        old = report(old_dir, u) if old_dir and os.path.exists(os.path.join(old_dir, 'mcaller_amd', 'csrc', u + '.hip')) else {}
         for name, v in new.items():
             cells = []
             for k in keys:
