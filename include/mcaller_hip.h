@@ -559,6 +559,56 @@ int mc_repr_fixed4(int32_t d, char *out32);
  * 1e-29 <= |v| < 1e9 and for zero; -> length, -1: a double it does not print. */
 int mc_repr_double_rowtext(double v, char *out32);
 
+/* ===== the per-site summary of a `.diffs.<k>` file on the GPU (make_bed.py:67-164 for BED, BED --control, BED --vo, GFF) =====
+ * The text of the file -> the bytes make_bed writes: rows whose context has 'M' at its centre, grouped by the exact bytes of
+ * (chrom, pos, strand, context) in first-occurrence order, an entry written when depth >= min_depth and
+ * (n_meth / depth >= mod_threshold) != control.  Integer counts, byte comparisons and one fp64 division: the bytes are the
+ * reference's, or the call declines -- *status = 1, mc_last_error says why (and mc_bed_last_stats which line), nothing is
+ * handed out and the caller runs the host code on the file.  Declined: a byte >= 0x80, a control byte other than tab and
+ * newline (0x7f included), a line that is not 7 or 8 tab-separated fields (an empty line is one), a position that is not
+ * 1-9 decimal digits, an empty context or label, a 7-field row with with_probs, a line longer than 65535 bytes, 2^31 - 2
+ * lines or more, gff together with with_probs, a text that does not fit into free device memory beside its tables (the
+ * whole text stays resident).  *out points at n_out bytes of pinned memory owned by the context: valid until the next
+ * mc_bed_* call on it or mc_bed_release.  Test knobs (environment): MCALLER_BED_HASH_MASK=<hex> is anded onto the 64-bit
+ * hash of the key bytes; MCALLER_BED_TABLE_SLOTS=<n> fixes the number of table slots (fewer than 2 x the counted rows:
+ * declined). */
+typedef struct mc_bed_params {
+    int64_t min_depth;             /* make_bed -d                                         */
+    double mod_threshold;          /* make_bed -t                                         */
+    int32_t control;               /* --control                                           */
+    int32_t with_probs;            /* --vo                                                */
+    int32_t gff;                   /* --gff                                               */
+    int32_t pad;
+} mc_bed_params;
+typedef struct mc_bed_stats {
+    int64_t n_bytes, n_lines, n_counted, n_entries, n_sites, n_out_bytes;
+    int64_t decline_line;          /* 0-based line the decline names, -1: none            */
+    int32_t decline_reason;        /* 0: not declined; MC_BED_DECLINE_*                   */
+    int32_t longest_probe;         /* slots a row looked at beyond its first, at most     */
+    int64_t table_slots;
+    int64_t kernel_bytes;          /* bytes the kernels read and wrote, by construction   */
+    double ms_read, ms_h2d, ms_kernels, ms_d2h, ms_total;
+} mc_bed_stats;
+#define MC_BED_DECLINE_HIGH_BYTE   1
+#define MC_BED_DECLINE_CONTROL     2
+#define MC_BED_DECLINE_FIELDS      3
+#define MC_BED_DECLINE_POSITION    4
+#define MC_BED_DECLINE_CONTEXT     5
+#define MC_BED_DECLINE_LABEL       6
+#define MC_BED_DECLINE_NO_PROB     7
+#define MC_BED_DECLINE_LONG_LINE   8
+#define MC_BED_DECLINE_TABLE       9
+#define MC_BED_DECLINE_ROWS        10
+#define MC_BED_DECLINE_MEMORY      11
+#define MC_BED_DECLINE_OPTIONS     12
+int mc_bed_summarise_text(mc_ctx *ctx, const char *text, int64_t n_bytes, const mc_bed_params *prm, const char **out,
+                          int64_t *n_out, int64_t *n_sites, int32_t *status);
+/* ... of a file: read in pinned blocks (mc_read_file_range) while the block before is on its way to the device. */
+int mc_bed_summarise_file(mc_ctx *ctx, const char *path, const mc_bed_params *prm, const char **out, int64_t *n_out,
+                          int64_t *n_sites, int32_t *status);
+int mc_bed_last_stats(mc_ctx *ctx, mc_bed_stats *out);
+int mc_bed_release(mc_ctx *ctx);
+
 /* ===== measurement plumbing: a table as nanopolish-eventalign text (13 columns), written by all host cores =====
  * For file-to-file timing on synthetic workloads (bench.py); seq = the contig's bases (k-mers of columns 3 and 10). */
 int mc_synth_write_tsv(const char *path, const mc_table_view *table, const char *seq, int64_t seq_len, const char *contig,

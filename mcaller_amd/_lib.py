@@ -87,6 +87,20 @@ class NbParams(C.Structure):
     _fields_ = [('var_smoothing', C.c_double)]
 
 
+class BedParams(C.Structure):
+    """mc_bed_params (include/mcaller_hip.h)."""
+    _fields_ = [('min_depth', C.c_int64), ('mod_threshold', C.c_double), ('control', C.c_int32), ('with_probs', C.c_int32),
+                ('gff', C.c_int32), ('pad', C.c_int32)]
+
+
+class BedStats(C.Structure):
+    """mc_bed_stats (include/mcaller_hip.h)."""
+    _fields_ = [('n_bytes', C.c_int64), ('n_lines', C.c_int64), ('n_counted', C.c_int64), ('n_entries', C.c_int64),
+                ('n_sites', C.c_int64), ('n_out_bytes', C.c_int64), ('decline_line', C.c_int64), ('decline_reason', C.c_int32),
+                ('longest_probe', C.c_int32), ('table_slots', C.c_int64), ('kernel_bytes', C.c_int64), ('ms_read', C.c_double),
+                ('ms_h2d', C.c_double), ('ms_kernels', C.c_double), ('ms_d2h', C.c_double), ('ms_total', C.c_double)]
+
+
 class Params(C.Structure):
     _fields_ = [('k', C.c_int32), ('skip_thresh', C.c_int32), ('qual_thresh', C.c_double),
                 ('tail_contig', C.c_int32), ('score', C.c_int32),
@@ -219,6 +233,12 @@ def lib():
         L.mc_row_text_release.argtypes = [C.c_void_p, C.c_int32]
         L.mc_ctx_rowtext_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
                                            C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mc_bed_summarise_text.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.POINTER(BedParams), C.POINTER(C.c_void_p),
+                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        L.mc_bed_summarise_file.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(BedParams), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                            C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        L.mc_bed_last_stats.argtypes = [C.c_void_p, C.POINTER(BedStats)]
+        L.mc_bed_release.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 

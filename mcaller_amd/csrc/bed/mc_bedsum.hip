@@ -1,0 +1,748 @@
+// mc_bedsum.hip -- the per-site summary of a `.diffs.<k>` file on the GPU: what make_bed.py:67-164 writes for BED, BED --control,
+// BED --vo and GFF (C ABI: mc_bed_summarise_text / _file, mc_bed_last_stats, mc_bed_release; Python: Device.bed_summarise,
+// make_bed.summarise_diffs_device).  The unit stands in csrc/bed/, beside the units of the passes, not among them: no pass runs
+// its kernels, and the benchmark's kernel hash (bench.KERNEL_SOURCES) names the files of the pass path one by one.
+//
+// Everything here is exact by construction -- integer counts, byte comparisons, one fp64 division whose quotient is printed by the
+// digit generation of mc_rowtext.h -- or the call declines and the host code does the file (status 1, mc_last_error):
+//   * a byte >= 0x80; a control byte other than tab and newline (0x7f too; '\r': Python's universal newlines split there)
+//   * a line that is not 7 or 8 tab-separated fields (an empty line is one)
+//   * a position that is not 1-9 decimal digits (int() accepts more forms; the end column is the integer + 1)
+//   * an empty context or an empty label (the reference's IndexError)
+//   * a 7-field row together with --vo
+//   * a line longer than 65535 bytes (field offsets inside a line are 16 bits)
+//   * 2^31 - 2 lines or more (rows and entries are numbered in 32 bits; a slot of the table holds row + 1)
+//   * a table with fewer than 2 x the counted rows' slots (only MCALLER_BED_TABLE_SLOTS makes one)
+//   * a text that does not fit into free device memory beside its tables: the WHOLE text stays resident, entries are compared
+//     against the bytes of a representative row and the output copies its fields from there
+//   * --gff with --vo, -p, --ref: not attempted (the caller does not ask)
+//
+// The steps (one lane per line unless said otherwise; n = lines):
+//   kp_count / kp_scan / kp_starts   line starts (the device parser's kernels: mc_lines.h)
+//   kb_parse      256 lines of a workgroup staged in LDS with 16-byte loads; per line: the class of every byte, the tabs, centre 'M',
+//                 label 'm', the position as an integer, the stripped span of the probability, a 64-bit hash of the key bytes.
+//                 A flagged line: atomicMin of (line << 8 | reason) -- the decline names the FIRST such line, whatever the order
+//   kb_group      open addressing, slot = tag (high 32 bits of the hash) << 32 | row + 1, claimed by atomicCAS; a taken slot
+//                 matches when the tag, the whole hash and the key bytes of its row are equal.  The row that claimed the slot
+//                 numbers the entry; depth, n_meth, bytes of probabilities: atomicAdd, smallest row: atomicMin -- integers, so the
+//                 result does not depend on the order of arrival.  Nothing crosses workgroups but these atomics.
+//   kb_sums / kp_scan / kb_apply   a row is its entry's head when it is the entry's smallest row.  Over the lines, exclusive
+//                 scans of: depth at heads (an entry's bucket in rank order), selected heads, bytes of selected heads' text
+//   kb_place / kb_sort_small / kb_sort_large (--vo)   rows into their entry's bucket (atomicAdd), then every selected bucket into
+//                 ascending row order: up to 32 rows by insertion (one lane), more by a workgroup's LSD radix sort, 8 bits a
+//                 pass, stable scatter chunk by chunk -- linear in the depth
+//   kb_write / kb_write_vo   a lane per selected entry writes the columns (fields copied from the head row's spans, pos + 1 and
+//                 the depth from the integers, the fraction from its digits); a wave per selected entry writes the list
+// wave64; no library sort; every buffer, event and stream through the owners of mc_own.h.
+#include "../mc_lines.h"
+#include "../mc_rowtext.h"
+
+#include <sys/stat.h>
+
+extern "C" int mc_read_file_range(const char *path, int64_t lo, int64_t hi, char *dst, int32_t n_threads);
+
+namespace {
+
+constexpr int BS_STAGE = 48 * 1024;          // LDS a workgroup of kb_parse stages its 256 lines in (two workgroups share a CU's 160 KB)
+constexpr int BS_SMALL = 32;                 // buckets up to this depth are sorted by insertion
+constexpr uint8_t BS_F_COUNTED = 1, BS_F_METH = 2, BS_F_PROB = 4;
+
+struct BsHead {                              // device-side result block (copied to the host as it is)
+    KpHead kp;                               // n_newlines (kp_scan), n_lines (kp_starts)
+    unsigned long long decline;              // min over the flagged lines of line << 8 | reason (~0: none)
+    unsigned long long n_counted, n_entries;
+    long long tot_bucket, tot_sel, tot_bytes;     // totals of the three scans
+    unsigned int n_large;
+    int longest_probe;
+};
+
+struct BsRow { uint16_t t[7]; uint16_t len; };   // the tabs of a line (offsets from its start; t[6] = len in a 7-field row), its length
+
+struct BsArgs {
+    const char *text;
+    int64_t n_bytes, n_lines, n_nl;
+    const long long *line_start;
+    BsHead *head;
+    // per line
+    BsRow *row;
+    uint32_t *pos, *pspan, *row_ent, *ent_boff;
+    uint64_t *hash;
+    uint8_t *fl;
+    // per entry, indexed by the row that claimed its slot
+    uint32_t *ent_depth, *ent_meth, *ent_min, *ent_fill;
+    unsigned long long *ent_pbytes;
+    unsigned long long *table;
+    uint64_t table_mask, hash_mask;
+    long long min_depth;
+    double thresh;
+    int control, with_probs, gff;
+    long long *blk_sum, *blk_off;            // [3 * nblk] each
+    int64_t nblk;
+    // per selected entry
+    uint32_t *sel_line, *large;
+    long long *sel_off, *sel_vo_at;
+    uint32_t *bucket, *bucket_tmp;
+    char *out;
+};
+
+__device__ __forceinline__ void bs_flag(const BsArgs &A, int64_t li, int reason) {
+    atomicMin(&A.head->decline, ((unsigned long long)li << 8) | (unsigned long long)reason);
+}
+
+// One line: t[x - adj] is byte x of the text (the staged piece in LDS, or the text itself with adj = 0: one address space per call site)
+__device__ __forceinline__ bool bs_parse_line(const BsArgs &A, const char *t, const int64_t adj, const int64_t li) {
+    const int64_t b = A.line_start[li] - adj;
+    const int64_t e = (li < A.n_nl ? A.line_start[li + 1] - 1 : A.n_bytes) - adj;        // the newline, or the end of the text
+    A.fl[li] = 0;
+    if (e - b > 65535) { bs_flag(A, li, MC_BED_DECLINE_LONG_LINE); return false; }
+    const int len = (int)(e - b);
+    int t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0, t5 = 0, t6 = 0, nt = 0;
+    bool bad_hi = false, bad_ctrl = false;
+    uint64_t h = 0xcbf29ce484222325ull;                       // FNV-1a over the key fields, a 0xff between fields (no such byte in a line)
+    for (int i = 0; i < len; ++i) {
+        const unsigned c = (unsigned char)t[b + i];
+        bad_hi |= c >= 0x80u;
+        bad_ctrl |= (c < 0x20u && c != '\t') || c == 0x7fu;
+        if (c == '\t') {
+            t0 = nt == 0 ? i : t0; t1 = nt == 1 ? i : t1; t2 = nt == 2 ? i : t2; t3 = nt == 3 ? i : t3;
+            t4 = nt == 4 ? i : t4; t5 = nt == 5 ? i : t5; t6 = nt == 6 ? i : t6;
+            if (nt < 6) h = (h ^ 0xffu) * 0x100000001b3ull;      // (the tab before a probability is no part of the key)
+            ++nt;
+        } else if (nt == 0 || nt == 2 || nt == 3 || nt == 5) {     // chrom, pos, context, strand
+            h = (h ^ c) * 0x100000001b3ull;
+        }
+    }
+    int reason = 0;
+    uint32_t pos = 0;
+    if (bad_hi) reason = MC_BED_DECLINE_HIGH_BYTE;
+    else if (bad_ctrl) reason = MC_BED_DECLINE_CONTROL;
+    else if (nt != 6 && nt != 7) reason = MC_BED_DECLINE_FIELDS;
+    else {
+        if (nt == 6) t6 = len;
+        const int pn = t2 - t1 - 1;
+        if (pn < 1 || pn > 9) reason = MC_BED_DECLINE_POSITION;
+        else
+            for (int i = t1 + 1; i < t2; ++i) {
+                const unsigned d = (unsigned)((unsigned char)t[b + i]) - '0';
+                if (d > 9u) reason = MC_BED_DECLINE_POSITION;
+                pos = pos * 10u + d;
+            }
+        if (!reason && t3 - t2 - 1 < 1) reason = MC_BED_DECLINE_CONTEXT;
+        if (!reason && t6 - t5 - 1 < 1) reason = MC_BED_DECLINE_LABEL;
+        if (!reason && nt == 6 && A.with_probs) reason = MC_BED_DECLINE_NO_PROB;
+    }
+    if (reason) { bs_flag(A, li, reason); return false; }
+    const int cn = t3 - t2 - 1;
+    const bool counted = t[b + t2 + 1 + cn / 2] == 'M';
+    const bool meth = t[b + t5 + 1] == 'm';
+    int pb = len, pe = len;                                   // f[7].strip(): blanks are the only whitespace a line still holds
+    if (nt == 7) {
+        pb = t6 + 1;
+        while (pb < pe && t[b + pb] == ' ') ++pb;
+        while (pe > pb && t[b + pe - 1] == ' ') --pe;
+    }
+    h ^= h >> 33; h *= 0xff51afd7ed558ccdull; h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53ull; h ^= h >> 33;
+    uint4 r;
+    r.x = (uint32_t)t0 | ((uint32_t)t1 << 16); r.y = (uint32_t)t2 | ((uint32_t)t3 << 16);
+    r.z = (uint32_t)t4 | ((uint32_t)t5 << 16); r.w = (uint32_t)t6 | ((uint32_t)len << 16);
+    reinterpret_cast<uint4 *>(A.row)[li] = r;
+    A.pos[li] = pos;
+    A.pspan[li] = ((uint32_t)pb << 16) | (uint32_t)(pe - pb);
+    A.hash[li] = h & A.hash_mask;
+    A.fl[li] = (uint8_t)((counted ? BS_F_COUNTED : 0) | (meth ? BS_F_METH : 0) | (nt == 7 ? BS_F_PROB : 0));
+    return counted;
+}
+
+__global__ __launch_bounds__(256) void kb_parse(BsArgs A) {
+    extern __shared__ __attribute__((aligned(16))) char s_text[];      // BS_STAGE + 16 bytes
+    const int64_t l0 = (int64_t)blockIdx.x * 256;
+    const int64_t l1 = min(l0 + 256, A.n_lines);
+    const int64_t g0 = A.line_start[l0], g1 = l1 <= A.n_nl ? (int64_t)A.line_start[l1] : A.n_bytes;
+    const int64_t a0 = g0 & ~(int64_t)15;
+    const int64_t li = l0 + threadIdx.x;
+    bool counted = false;
+    if (g1 - a0 <= BS_STAGE) {                               // (the text buffer is padded: whole 16-byte groups are readable)
+        for (int64_t i = (int64_t)threadIdx.x * 16; i < g1 - a0; i += 256 * 16)
+            *reinterpret_cast<uint4 *>(s_text + i) = *reinterpret_cast<const uint4 *>(A.text + a0 + i);
+        __syncthreads();
+        if (li < l1) counted = bs_parse_line(A, s_text, a0, li);
+    } else if (li < l1) {                                    // very long lines: read in place
+        counted = bs_parse_line(A, A.text, 0, li);
+    }
+    const unsigned long long bal = __ballot(counted);
+    if ((threadIdx.x & 63) == 0 && bal) atomicAdd(&A.head->n_counted, (unsigned long long)__popcll(bal));
+}
+
+__device__ __forceinline__ BsRow bs_row(const BsArgs &A, int64_t li) {
+    const uint4 r = reinterpret_cast<const uint4 *>(A.row)[li];
+    BsRow R;
+    R.t[0] = (uint16_t)r.x; R.t[1] = (uint16_t)(r.x >> 16); R.t[2] = (uint16_t)r.y; R.t[3] = (uint16_t)(r.y >> 16);
+    R.t[4] = (uint16_t)r.z; R.t[5] = (uint16_t)(r.z >> 16); R.t[6] = (uint16_t)r.w; R.len = (uint16_t)(r.w >> 16);
+    return R;
+}
+
+__device__ __forceinline__ bool bs_same_bytes(const char *__restrict__ a, const char *__restrict__ b, int n) {
+    for (int i = 0; i < n; ++i)
+        if (a[i] != b[i]) return false;
+    return true;
+}
+
+// (chrom, pos, strand, context) of lines a and b, byte for byte: chrom = [0, t0), pos and context = (t1, t3) with the tab between
+// them at the same place, strand = (t4, t5)
+__device__ __forceinline__ bool bs_same_key(const BsArgs &A, int64_t a, int64_t b) {
+    const BsRow Ra = bs_row(A, a), Rb = bs_row(A, b);
+    if (Ra.t[0] != Rb.t[0] || Ra.t[2] - Ra.t[1] != Rb.t[2] - Rb.t[1] || Ra.t[3] - Ra.t[1] != Rb.t[3] - Rb.t[1] ||
+        Ra.t[5] - Ra.t[4] != Rb.t[5] - Rb.t[4])
+        return false;
+    const char *ta = A.text + A.line_start[a], *tb = A.text + A.line_start[b];
+    return bs_same_bytes(ta, tb, Ra.t[0]) && bs_same_bytes(ta + Ra.t[1] + 1, tb + Rb.t[1] + 1, Ra.t[3] - Ra.t[1] - 1) &&
+           bs_same_bytes(ta + Ra.t[4] + 1, tb + Rb.t[4] + 1, Ra.t[5] - Ra.t[4] - 1);
+}
+
+__global__ __launch_bounds__(256) void kb_group(BsArgs A) {
+    const int64_t li = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const uint8_t fl = li < A.n_lines ? A.fl[li] : (uint8_t)0;
+    int probes = 0;
+    if (fl & BS_F_COUNTED) {
+        const uint64_t h = A.hash[li];
+        const uint64_t tag = h >> 32;
+        const unsigned long long mine = (tag << 32) | (unsigned long long)(li + 1);
+        uint64_t slot = h & A.table_mask;
+        int64_t rep = -1;
+        for (;;) {
+            unsigned long long cur = A.table[slot];           // (a slot goes from empty to taken once: a stale "empty" is put right by the CAS)
+            if (cur == 0ull) {
+                cur = atomicCAS(&A.table[slot], 0ull, mine);
+                if (cur == 0ull) { rep = li; break; }
+            }
+            if ((cur >> 32) == tag) {
+                const int64_t r = (int64_t)(cur & 0xffffffffull) - 1;
+                if (A.hash[r] == h && bs_same_key(A, li, r)) { rep = r; break; }
+            }
+            slot = (slot + 1) & A.table_mask;
+            if ((uint64_t)++probes > A.table_mask) break;     // every slot seen: the table is full (the host sizes it so that it is not)
+        }
+        if (rep < 0) {
+            bs_flag(A, li, MC_BED_DECLINE_TABLE);
+            A.row_ent[li] = (uint32_t)li;                     // (an entry nobody counted: no head, whatever runs before the host looks)
+        } else {
+            A.row_ent[li] = (uint32_t)rep;
+            atomicAdd(&A.ent_depth[rep], 1u);
+            if (fl & BS_F_METH) atomicAdd(&A.ent_meth[rep], 1u);
+            atomicMin(&A.ent_min[rep], (uint32_t)li);
+            if (A.with_probs) atomicAdd(&A.ent_pbytes[rep], (unsigned long long)(A.pspan[li] & 0xffffu));
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) probes = max(probes, __shfl_xor(probes, o));
+    if ((threadIdx.x & 63) == 0 && probes > 0) atomicMax(&A.head->longest_probe, probes);
+}
+
+// The text of an entry, counted or stored: li its head row.  (--vo: the list itself is kb_write_vo's; *vo_at = where it begins)
+template <class Sink>
+__device__ __forceinline__ void bs_put_span(Sink &o, const char *__restrict__ p, int n) {
+    for (int i = 0; i < n; ++i) o.put(p[i]);
+}
+template <class Sink>
+__device__ __forceinline__ void bs_put_lit(Sink &o, const char *s) {
+    for (; *s; ++s) o.put(*s);
+}
+
+template <class Sink>
+__device__ __forceinline__ void bs_put_entry(const BsArgs &A, Sink &o, int64_t li, uint32_t depth, uint32_t meth) {
+    const BsRow R = bs_row(A, li);
+    const char *t = A.text + A.line_start[li];
+    const RtNum frac = rt_num_of((double)meth / (double)depth);       // np.float64(n_meth) / np.float64(depth)
+    const uint32_t end = A.pos[li] + 1u;                              // str(int(pos) + 1)
+    bs_put_span(o, t, R.t[0]);
+    o.put('\t');
+    if (A.gff) {
+        bs_put_lit(o, "kinModCall\tm6A\t");
+        rt_put_uint(o, end); o.put('\t'); rt_put_uint(o, end);
+        bs_put_lit(o, "\t10\t");
+        bs_put_span(o, t + R.t[4] + 1, R.t[5] - R.t[4] - 1);
+        bs_put_lit(o, "\t.\tcoverage=");
+        rt_put_uint(o, depth);
+        bs_put_lit(o, ";context=");
+        bs_put_span(o, t + R.t[2] + 1, R.t[3] - R.t[2] - 1);
+        bs_put_lit(o, ";IPDRatio=5;frac=");
+        rt_put_num(o, frac);
+        return;
+    }
+    bs_put_span(o, t + R.t[1] + 1, R.t[2] - R.t[1] - 1);
+    o.put('\t');
+    rt_put_uint(o, end);
+    o.put('\t');
+    bs_put_span(o, t + R.t[2] + 1, R.t[3] - R.t[2] - 1);
+    o.put('\t');
+    rt_put_num(o, frac);
+    o.put('\t');
+    bs_put_span(o, t + R.t[4] + 1, R.t[5] - R.t[4] - 1);
+    o.put('\t');
+    rt_put_uint(o, depth);
+}
+
+struct BsEnt { bool head, sel; uint32_t depth, meth, rep; long long bytes; };
+
+__device__ __forceinline__ BsEnt bs_entry(const BsArgs &A, int64_t li, bool want_bytes) {
+    BsEnt E;
+    E.head = E.sel = false; E.depth = E.meth = E.rep = 0; E.bytes = 0;
+    if (li >= A.n_lines || !(A.fl[li] & BS_F_COUNTED)) return E;
+    E.rep = A.row_ent[li];
+    if (A.ent_min[E.rep] != (uint32_t)li) return E;
+    E.head = true;
+    E.depth = A.ent_depth[E.rep];
+    E.meth = A.ent_meth[E.rep];
+    // depth >= d and (fraction >= t) != control, the fraction an fp64 quotient (make_bed.py:21-28,:135-138)
+    E.sel = (long long)E.depth >= A.min_depth && (((double)E.meth / (double)E.depth >= A.thresh) != (A.control != 0));
+    if (E.sel && want_bytes) {
+        RtCount c;
+        bs_put_entry(A, c, li, E.depth, E.meth);
+        E.bytes = (long long)c.n + 1;                                  // the newline
+        if (A.with_probs) E.bytes += 1 + (long long)A.ent_pbytes[E.rep] + ((long long)E.depth - 1);     // tab, texts, commas
+    }
+    return E;
+}
+
+// exclusive prefix of v over the workgroup's 256 threads; *total: the workgroup's sum
+__device__ __forceinline__ long long bs_block_excl(long long v, long long *s_w, long long *total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    long long incl = v;
+    for (int o = 1; o < 64; o <<= 1) {
+        const long long u = __shfl_up(incl, o);
+        if (lane >= o) incl += u;
+    }
+    __syncthreads();
+    if (lane == 63) s_w[wave] = incl;
+    __syncthreads();
+    long long before = 0;
+    for (int w = 0; w < wave; ++w) before += s_w[w];
+    *total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    return before + incl - v;
+}
+
+__global__ __launch_bounds__(256) void kb_sums(BsArgs A) {
+    __shared__ long long s_w[4];
+    const int64_t li = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const BsEnt E = bs_entry(A, li, true);
+    long long tot[3], heads;
+    (void)bs_block_excl(E.head ? (long long)E.depth : 0, s_w, &tot[0]);
+    (void)bs_block_excl(E.sel ? 1 : 0, s_w, &tot[1]);
+    (void)bs_block_excl(E.bytes, s_w, &tot[2]);
+    (void)bs_block_excl(E.head ? 1 : 0, s_w, &heads);
+    if (threadIdx.x == 0) {
+        for (int q = 0; q < 3; ++q) A.blk_sum[q * A.nblk + blockIdx.x] = tot[q];
+        if (heads) atomicAdd(&A.head->n_entries, (unsigned long long)heads);
+    }
+}
+
+__global__ __launch_bounds__(256) void kb_apply(BsArgs A) {
+    __shared__ long long s_w[4];
+    const int64_t li = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const BsEnt E = bs_entry(A, li, true);
+    long long tot;
+    const long long boff = A.blk_off[blockIdx.x] + bs_block_excl(E.head ? (long long)E.depth : 0, s_w, &tot);
+    const long long k = A.blk_off[A.nblk + blockIdx.x] + bs_block_excl(E.sel ? 1 : 0, s_w, &tot);
+    const long long at = A.blk_off[2 * A.nblk + blockIdx.x] + bs_block_excl(E.bytes, s_w, &tot);
+    if (E.head && A.with_probs) A.ent_boff[li] = (uint32_t)boff;
+    if (E.sel) { A.sel_line[k] = (uint32_t)li; A.sel_off[k] = at; }
+}
+
+__global__ __launch_bounds__(256) void kb_place(BsArgs A) {
+    const int64_t li = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (li >= A.n_lines || !(A.fl[li] & BS_F_COUNTED)) return;
+    const uint32_t rep = A.row_ent[li];
+    const uint32_t k = atomicAdd(&A.ent_fill[rep], 1u);
+    A.bucket[(size_t)A.ent_boff[A.ent_min[rep]] + k] = (uint32_t)li;
+}
+
+// a lane per selected entry: its bucket into ascending row order if it is small, else onto the list of kb_sort_large
+__global__ __launch_bounds__(256) void kb_sort_small(BsArgs A, int64_t n_sel) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n_sel) return;
+    const uint32_t li = A.sel_line[k];
+    const uint32_t depth = A.ent_depth[A.row_ent[li]];
+    if (depth > (uint32_t)BS_SMALL) { A.large[atomicAdd(&A.head->n_large, 1u)] = (uint32_t)k; return; }
+    uint32_t *b = A.bucket + A.ent_boff[li];
+    for (uint32_t i = 1; i < depth; ++i) {
+        const uint32_t v = b[i];
+        uint32_t j = i;
+        for (; j > 0 && b[j - 1] > v; --j) b[j] = b[j - 1];
+        b[j] = v;
+    }
+}
+
+// A workgroup per large bucket (taken in turn from the list): LSD radix sort, 8 bits a pass, between the bucket and its twin in
+// bucket_tmp; an even number of passes, so the rows end where they began.  The scatter goes chunk by chunk of 256 rows in order and
+// is stable: a row's place = the digit's base + rows of that digit in earlier waves of the chunk + those before it in its wave
+__global__ __launch_bounds__(256) void kb_sort_large(BsArgs A, int n_pass) {
+    __shared__ unsigned s_base[256];
+    __shared__ unsigned s_wc[4][256];
+    __shared__ unsigned s_w[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned n_large = A.head->n_large;
+    for (unsigned q = blockIdx.x; q < n_large; q += gridDim.x) {
+        const uint32_t li = A.sel_line[A.large[q]];
+        const uint32_t depth = A.ent_depth[A.row_ent[li]];
+        uint32_t *b0 = A.bucket + A.ent_boff[li], *b1 = A.bucket_tmp + A.ent_boff[li];
+        for (int p = 0; p < n_pass; ++p) {
+            const uint32_t *src = (p & 1) ? b1 : b0;
+            uint32_t *dst = (p & 1) ? b0 : b1;
+            const int sh = 8 * p;
+            s_base[tid] = 0;
+            __syncthreads();
+            for (uint32_t i = tid; i < depth; i += 256) atomicAdd(&s_base[(src[i] >> sh) & 255u], 1u);
+            __syncthreads();
+            {                                                       // exclusive scan of the 256 counts
+                const unsigned c = s_base[tid];
+                unsigned incl = c;
+                for (int o = 1; o < 64; o <<= 1) {
+                    const unsigned u = __shfl_up(incl, o);
+                    if (lane >= o) incl += u;
+                }
+                if (lane == 63) s_w[wave] = incl;
+                __syncthreads();
+                unsigned before = 0;
+                for (int w = 0; w < wave; ++w) before += s_w[w];
+                s_base[tid] = before + incl - c;
+            }
+            __syncthreads();
+            for (uint32_t c0 = 0; c0 < depth; c0 += 256) {
+                const uint32_t i = c0 + tid;
+                const bool valid = i < depth;
+                const uint32_t key = valid ? src[i] : 0u;
+                const unsigned d = (key >> sh) & 255u;
+                unsigned long long peers = __ballot(valid);         // lanes of the wave with a row of the same digit
+                for (int bit = 0; bit < 8; ++bit) {
+                    const bool one = (d >> bit) & 1u;
+                    const unsigned long long bal = __ballot(one);
+                    peers &= one ? bal : ~bal;
+                }
+                const unsigned before_me = (unsigned)__popcll(peers & ((1ull << lane) - 1ull));
+                const bool leader = valid && before_me == 0;
+                for (int w = 0; w < 4; ++w) s_wc[w][tid] = 0;
+                __syncthreads();
+                if (leader) s_wc[wave][d] = (unsigned)__popcll(peers);
+                __syncthreads();
+                if (valid) {
+                    unsigned at = s_base[d] + before_me;
+                    for (int w = 0; w < wave; ++w) at += s_wc[w][d];
+                    dst[at] = key;
+                }
+                __syncthreads();
+                if (leader) atomicAdd(&s_base[d], (unsigned)__popcll(peers));
+                __syncthreads();
+            }
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void kb_write(BsArgs A, int64_t n_sel) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n_sel) return;
+    const uint32_t li = A.sel_line[k];
+    const uint32_t rep = A.row_ent[li];
+    const uint32_t depth = A.ent_depth[rep];
+    RtStore o{A.out + A.sel_off[k]};
+    bs_put_entry(A, o, li, depth, A.ent_meth[rep]);
+    if (A.with_probs) {
+        o.put('\t');
+        A.sel_vo_at[k] = (long long)(o.p - A.out);
+        o.p += (long long)A.ent_pbytes[rep] + ((long long)depth - 1);
+    }
+    o.put('\n');
+}
+
+// a wave per selected entry: the stripped probability texts of its rows in row order, joined by ','
+__global__ __launch_bounds__(256) void kb_write_vo(BsArgs A, int64_t n_sel) {
+    const int lane = threadIdx.x & 63;
+    const int64_t k = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (k >= n_sel) return;
+    const uint32_t li = A.sel_line[k];
+    const uint32_t depth = A.ent_depth[A.row_ent[li]];
+    const uint32_t *b = A.bucket + A.ent_boff[li];
+    long long at = A.sel_vo_at[k];
+    for (uint32_t c0 = 0; c0 < depth; c0 += 64) {
+        const uint32_t i = c0 + lane;
+        const bool valid = i < depth;
+        const uint32_t r = valid ? b[i] : 0u;
+        const uint32_t ps = valid ? A.pspan[r] : 0u;
+        const int n = valid ? (int)(ps & 0xffffu) + (i > 0 ? 1 : 0) : 0;
+        int incl = n;
+        for (int o = 1; o < 64; o <<= 1) {
+            const int u = __shfl_up(incl, o);
+            if (lane >= o) incl += u;
+        }
+        if (valid) {
+            char *w = A.out + at + incl - n;
+            if (i > 0) *w++ = ',';
+            const char *s = A.text + A.line_start[r] + (ps >> 16);
+            for (int j = 0; j < (int)(ps & 0xffffu); ++j) w[j] = s[j];
+        }
+        at += __shfl(incl, 63);
+    }
+}
+
+const char *bs_reason_text(int reason) {
+    switch (reason) {
+    case MC_BED_DECLINE_HIGH_BYTE: return "a byte >= 0x80";
+    case MC_BED_DECLINE_CONTROL: return "a control byte other than tab and newline";
+    case MC_BED_DECLINE_FIELDS: return "a line that is not 7 or 8 tab-separated fields";
+    case MC_BED_DECLINE_POSITION: return "a position that is not 1-9 decimal digits";
+    case MC_BED_DECLINE_CONTEXT: return "an empty context";
+    case MC_BED_DECLINE_LABEL: return "an empty label";
+    case MC_BED_DECLINE_NO_PROB: return "a 7-field row together with --vo";
+    case MC_BED_DECLINE_LONG_LINE: return "a line longer than 65535 bytes";
+    case MC_BED_DECLINE_TABLE: return "the table has fewer than 2 x the counted rows' slots";
+    case MC_BED_DECLINE_ROWS: return "more lines than rows are numbered for (2^31 - 2)";
+    case MC_BED_DECLINE_MEMORY: return "the text and its tables do not fit into free device memory";
+    case MC_BED_DECLINE_OPTIONS: return "--gff with --vo is not summarised on the device";
+    }
+    return "unknown";
+}
+
+double bs_ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+int bs_decline(mc_ctx *c, int32_t *status, int reason, long long line) {
+    c->bed_stats.decline_reason = reason;
+    c->bed_stats.decline_line = line;
+    if (line >= 0) mc_set_error("the device summary declines: %s (line %lld)", bs_reason_text(reason), line + 1);
+    else mc_set_error("the device summary declines: %s", bs_reason_text(reason));
+    *status = 1;
+    return 0;
+}
+
+// does `bytes` more fit into device memory, with a margin for what the runtime and the other buffers of the context take
+bool bs_fits(size_t bytes) {
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return false; }
+    const size_t margin = (size_t)256 << 20;
+    return free_b > margin && bytes <= free_b - margin;
+}
+
+// The text is on the device (d_text[0, n), padded; copies enqueued on c->up_stream): everything behind that
+int bs_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const mc_bed_params *P, const char **out, int64_t *n_out,
+           int64_t *n_sites, int32_t *status) {
+    mc_bed_stats &S = c->bed_stats;
+    hipStream_t st = c->stream;
+    HIP_TRY(hipStreamSynchronize(c->up_stream));
+    const auto t_kernels = std::chrono::steady_clock::now();
+    if (n == 0) return 0;                                     // no line, no entry: an empty file
+    BsHead *d_head = nullptr, h = {};
+    if (pool.get(&d_head, 1)) return -10;
+    h.decline = ~0ull;
+    HIP_TRY(hipMemcpyAsync(d_head, &h, sizeof h, hipMemcpyHostToDevice, st));
+    const int64_t n_tiles = (n + KP_TILE - 1) / KP_TILE;
+    long long *tile_cnt = nullptr, *tile_off = nullptr;
+    if (pool.get(&tile_cnt, (size_t)n_tiles) || pool.get(&tile_off, (size_t)n_tiles)) return -10;
+    hipLaunchKernelGGL(kp_count, dim3((unsigned)n_tiles), dim3(KP_THREADS), 0, st, d_text, n, tile_cnt);
+    hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)tile_cnt, n_tiles, tile_off, &d_head->kp.n_newlines);
+    HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int64_t n_nl = h.kp.n_newlines;
+    if (n_nl + 1 >= ((int64_t)1 << 31) - 2) return bs_decline(c, status, MC_BED_DECLINE_ROWS, -1);
+    const int64_t cap_lines = n_nl + 2;
+    // per line: the start, the row, four 32-bit columns, the hash, the flags, the entry's five columns
+    if (!bs_fits((size_t)cap_lines * (8 + 16 + 4 * 4 + 8 + 1 + 4 * 4 + 8) + ((size_t)1 << 20))) return bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1);
+    BsArgs A = {};
+    long long *line_start = nullptr;
+    if (pool.get(&line_start, (size_t)cap_lines)) return -10;
+    hipLaunchKernelGGL(kp_starts, dim3((unsigned)n_tiles), dim3(KP_THREADS), 0, st, d_text, n, (const long long *)tile_off, line_start,
+                       cap_lines, &d_head->kp);
+    // (the last line may lack its newline: the same count kp_starts makes; the last byte is not on the host, so it is asked for)
+    HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int64_t n_lines = h.kp.n_lines;
+    S.n_lines = n_lines;
+    A.text = d_text; A.n_bytes = n; A.n_lines = n_lines; A.n_nl = n_nl; A.line_start = line_start; A.head = d_head;
+    A.min_depth = P->min_depth; A.thresh = P->mod_threshold; A.control = P->control; A.with_probs = P->with_probs; A.gff = P->gff;
+    A.hash_mask = ~0ull;
+    if (const char *e = getenv("MCALLER_BED_HASH_MASK")) A.hash_mask = strtoull(e, nullptr, 16);
+    const size_t nl = (size_t)n_lines;
+    if (pool.get(&A.row, nl) || pool.get(&A.pos, nl) || pool.get(&A.pspan, nl) || pool.get(&A.row_ent, nl) || pool.get(&A.ent_boff, nl) ||
+        pool.get(&A.hash, nl) || pool.get(&A.fl, nl) || pool.get(&A.ent_depth, nl) || pool.get(&A.ent_meth, nl) || pool.get(&A.ent_min, nl) ||
+        pool.get(&A.ent_fill, nl) || pool.get(&A.ent_pbytes, nl))
+        return -10;
+    const unsigned lb = (unsigned)((n_lines + 255) / 256);
+    A.nblk = lb;
+    hipLaunchKernelGGL(kb_parse, dim3(lb), dim3(256), BS_STAGE + 16, st, A);
+    HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    S.kernel_bytes += 3 * n + n_lines * (8 + 16 + 4 + 4 + 8 + 1);       // the text: counted, split, parsed; the line columns
+    if (h.decline != ~0ull) return bs_decline(c, status, (int)(h.decline & 0xff), (long long)(h.decline >> 8));
+    const int64_t n_counted = (int64_t)h.n_counted;
+    S.n_counted = n_counted;
+    uint64_t slots = 16;
+    while ((int64_t)slots < 2 * n_counted) slots <<= 1;
+    if (const char *e = getenv("MCALLER_BED_TABLE_SLOTS")) {
+        const long long want = atoll(e);
+        if (want > 0) { slots = 1; while ((long long)slots < want) slots <<= 1; }
+    }
+    S.table_slots = (int64_t)slots;
+    if ((int64_t)slots < 2 * n_counted) return bs_decline(c, status, MC_BED_DECLINE_TABLE, -1);
+    if (!bs_fits((size_t)slots * 8 + (size_t)3 * lb * 16 + (P->with_probs ? (size_t)n_counted * 8 : 0))) return bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1);
+    if (pool.get(&A.table, (size_t)slots) || pool.get(&A.blk_sum, (size_t)3 * lb) || pool.get(&A.blk_off, (size_t)3 * lb)) return -10;
+    A.table_mask = slots - 1;
+    HIP_TRY(hipMemsetAsync(A.table, 0, (size_t)slots * 8, st));
+    HIP_TRY(hipMemsetAsync(A.ent_depth, 0, nl * 4, st));
+    HIP_TRY(hipMemsetAsync(A.ent_meth, 0, nl * 4, st));
+    HIP_TRY(hipMemsetAsync(A.ent_fill, 0, nl * 4, st));
+    HIP_TRY(hipMemsetAsync(A.ent_min, 0xff, nl * 4, st));
+    HIP_TRY(hipMemsetAsync(A.ent_pbytes, 0, nl * 8, st));
+    hipLaunchKernelGGL(kb_group, dim3(lb), dim3(256), 0, st, A);
+    hipLaunchKernelGGL(kb_sums, dim3(lb), dim3(256), 0, st, A);
+    hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)A.blk_sum, (int64_t)lb, A.blk_off, &d_head->tot_bucket);
+    hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)(A.blk_sum + lb), (int64_t)lb, A.blk_off + lb, &d_head->tot_sel);
+    hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)(A.blk_sum + 2 * (size_t)lb), (int64_t)lb, A.blk_off + 2 * (size_t)lb,
+                       &d_head->tot_bytes);
+    HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    S.kernel_bytes += (int64_t)slots * 8 + n_lines * 5 * 8 + n_counted * (16 + 8 + 5 * 4 + 60) + 2 * n_lines * (1 + 4 + 3 * 4);
+    S.longest_probe = h.longest_probe;
+    if (h.decline != ~0ull) return bs_decline(c, status, (int)(h.decline & 0xff), (long long)(h.decline >> 8));
+    S.n_entries = (int64_t)h.n_entries;
+    const int64_t n_sel = h.tot_sel, n_outb = h.tot_bytes;
+    S.n_sites = n_sel;
+    S.n_out_bytes = n_outb;
+    *n_sites = n_sel;
+    if (n_sel > 0) {
+        if (!bs_fits((size_t)n_sel * 32 + (size_t)n_outb)) return bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1);
+        if (pool.get(&A.sel_line, (size_t)n_sel) || pool.get(&A.large, (size_t)n_sel) || pool.get(&A.sel_off, (size_t)n_sel) ||
+            pool.get(&A.sel_vo_at, (size_t)n_sel) || pool.get(&A.out, (size_t)n_outb))
+            return -10;
+        if (P->with_probs && (pool.get(&A.bucket, (size_t)n_counted) || pool.get(&A.bucket_tmp, (size_t)n_counted))) return -10;
+        const unsigned sb = (unsigned)((n_sel + 255) / 256);
+        hipLaunchKernelGGL(kb_apply, dim3(lb), dim3(256), 0, st, A);
+        if (P->with_probs) {
+            hipLaunchKernelGGL(kb_place, dim3(lb), dim3(256), 0, st, A);
+            hipLaunchKernelGGL(kb_sort_small, dim3(sb), dim3(256), 0, st, A, n_sel);
+            hipLaunchKernelGGL(kb_sort_large, dim3((unsigned)std::min<int64_t>(n_sel, 1024)), dim3(256), 0, st, A, n_lines <= 65536 ? 2 : 4);
+        }
+        hipLaunchKernelGGL(kb_write, dim3(sb), dim3(256), 0, st, A, n_sel);
+        if (P->with_probs) hipLaunchKernelGGL(kb_write_vo, dim3((unsigned)((n_sel + 3) / 4)), dim3(256), 0, st, A, n_sel);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));
+        S.kernel_bytes += n_lines * (1 + 4 + 3 * 4) + 2 * n_outb + (P->with_probs ? n_counted * 24 : 0);
+    }
+    S.ms_kernels = bs_ms_since(t_kernels);
+    const auto t_d2h = std::chrono::steady_clock::now();
+    if (n_outb > 0) {
+        if (c->bed_out_cap < (size_t)n_outb) {
+            c->bed_out_cap = 0;
+            if (int rc = c->bed_out.alloc((size_t)n_outb + (size_t)n_outb / 4)) return rc;
+            c->bed_out_cap = (size_t)n_outb + (size_t)n_outb / 4;
+        }
+        HIP_TRY(hipMemcpyAsync(c->bed_out.p, A.out, (size_t)n_outb, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    S.ms_d2h = bs_ms_since(t_d2h);
+    *out = (const char *)c->bed_out.p;
+    *n_out = n_outb;
+    return 0;
+}
+
+// what both entry points begin with -> 0: go on; 1: done (declined, *status set)
+int bs_begin(mc_ctx *c, const mc_bed_params *P, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status, int64_t n) {
+    c->bed_stats = mc_bed_stats();
+    c->bed_stats.decline_line = -1;
+    c->bed_stats.n_bytes = n;
+    *out = nullptr; *n_out = 0; *n_sites = 0; *status = 0;
+    if (P->gff && P->with_probs) { (void)bs_decline(c, status, MC_BED_DECLINE_OPTIONS, -1); return 1; }
+    if (!bs_fits((size_t)n + 4096)) { (void)bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1); return 1; }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int mc_bed_summarise_text(mc_ctx *c, const char *text, int64_t n_bytes, const mc_bed_params *P, const char **out, int64_t *n_out,
+                                     int64_t *n_sites, int32_t *status) {
+    if (!c || !P || !out || !n_out || !n_sites || !status || n_bytes < 0 || (n_bytes > 0 && !text)) {
+        mc_set_error("mc_bed_summarise_text: bad arguments");
+        return -12;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    if (bs_begin(c, P, out, n_out, n_sites, status, n_bytes)) return 0;
+    Pool pool("bed summary");
+    char *d_text = nullptr;
+    if (pool.get(&d_text, (size_t)n_bytes + 64)) return -10;
+    if (n_bytes > 0) HIP_TRY(hipMemcpyAsync(d_text, text, (size_t)n_bytes, hipMemcpyHostToDevice, c->up_stream));
+    HIP_TRY(hipMemsetAsync(d_text + n_bytes, 0, 64, c->up_stream));
+    HIP_TRY(hipStreamSynchronize(c->up_stream));
+    c->bed_stats.ms_h2d = bs_ms_since(t0);
+    const int rc = bs_run(c, pool, d_text, n_bytes, P, out, n_out, n_sites, status);
+    (void)hipStreamSynchronize(c->stream);                   // (an early return: nothing of the pool is in use when it goes)
+    c->bed_stats.ms_total = bs_ms_since(t0);
+    return rc;
+}
+
+extern "C" int mc_bed_summarise_file(mc_ctx *c, const char *path, const mc_bed_params *P, const char **out, int64_t *n_out, int64_t *n_sites,
+                                     int32_t *status) {
+    if (!c || !path || !P || !out || !n_out || !n_sites || !status) {
+        mc_set_error("mc_bed_summarise_file: bad arguments");
+        return -12;
+    }
+    struct stat sb;
+    if (stat(path, &sb) != 0 || !S_ISREG(sb.st_mode)) {
+        mc_set_error("mc_bed_summarise_file: %s is not a readable file", path);
+        return -1;
+    }
+    const int64_t n = (int64_t)sb.st_size;
+    HIP_TRY(hipSetDevice(c->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    if (bs_begin(c, P, out, n_out, n_sites, status, n)) return 0;
+    Pool pool("bed summary");
+    char *d_text = nullptr;
+    if (pool.get(&d_text, (size_t)n + 64)) return -10;
+    // the file in blocks, two pinned stages in turn: block i is read while block i - 1 is on its way
+    const size_t block = (size_t)std::min<int64_t>(std::max<int64_t>(n, 4096), (int64_t)64 << 20);
+    if (c->bed_stage_cap < block) {
+        c->bed_stage_cap = 0;
+        for (Pinned &p : c->bed_stage)
+            if (int rc = p.alloc(block)) return rc;
+        c->bed_stage_cap = block;
+    }
+    for (Event &e : c->bed_ev)
+        if (!e.e)
+            if (int rc = e.create()) return rc;
+    double ms_read = 0;
+    int rc = 0, turn = 0;
+    for (int64_t lo = 0; lo < n && rc == 0; lo += (int64_t)c->bed_stage_cap, turn ^= 1) {
+        const int64_t hi = std::min<int64_t>(n, lo + (int64_t)c->bed_stage_cap);
+        if (lo >= 2 * (int64_t)c->bed_stage_cap) HIP_TRY(hipEventSynchronize(c->bed_ev[turn]));     // the copy out of this stage is done
+        const auto tr = std::chrono::steady_clock::now();
+        rc = mc_read_file_range(path, lo, hi, c->bed_stage[turn].get<char>(), 0);
+        ms_read += bs_ms_since(tr);
+        if (rc) break;
+        HIP_TRY(hipMemcpyAsync(d_text + lo, c->bed_stage[turn].p, (size_t)(hi - lo), hipMemcpyHostToDevice, c->up_stream));
+        HIP_TRY(hipEventRecord(c->bed_ev[turn], c->up_stream));
+    }
+    HIP_TRY(hipMemsetAsync(d_text + n, 0, 64, c->up_stream));
+    HIP_TRY(hipStreamSynchronize(c->up_stream));
+    if (rc) return rc;
+    c->bed_stats.ms_read = ms_read;
+    c->bed_stats.ms_h2d = bs_ms_since(t0) - ms_read;         // what the copies added behind the reads they ran beside
+    rc = bs_run(c, pool, d_text, n, P, out, n_out, n_sites, status);
+    (void)hipStreamSynchronize(c->stream);
+    c->bed_stats.ms_total = bs_ms_since(t0);
+    return rc;
+}
+
+extern "C" int mc_bed_last_stats(mc_ctx *c, mc_bed_stats *out) {
+    if (!c || !out) { mc_set_error("mc_bed_last_stats: bad arguments"); return -12; }
+    *out = c->bed_stats;
+    return 0;
+}
+
+extern "C" int mc_bed_release(mc_ctx *c) {
+    if (!c) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipStreamSynchronize(c->up_stream));
+    c->bed_out.reset(); c->bed_out_cap = 0;
+    for (Pinned &p : c->bed_stage) p.reset();
+    c->bed_stage_cap = 0;
+    return 0;
+}

@@ -287,6 +287,14 @@ struct mc_ctx {
     Pinned site_status_host;                            // pinned copy the host reads (written by a kernel: no DMA)
     void *comm = nullptr;             // ncclComm_t
     int comm_world = 1;
+    // the summary of a .diffs file (bed/mc_bedsum.hip): the result handed out last, the file reader's two pinned blocks and the
+    // events that say a block's H2D copy is done, the figures of the last call
+    Pinned bed_out;
+    size_t bed_out_cap = 0;
+    Pinned bed_stage[2];
+    size_t bed_stage_cap = 0;
+    Event bed_ev[2];
+    mc_bed_stats bed_stats = {};
 };
 
 // ---- what crosses the units ----

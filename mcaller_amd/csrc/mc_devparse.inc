@@ -1,4 +1,4 @@
-// The eventalign text parsed ON THE GPU (included by mc_tables.hip, and by no other unit: the kernels sit in an unnamed namespace; C ABI: mc_ctx_parse_begin / _end / _finish).
+// The eventalign text parsed ON THE GPU (included by mc_tables.hip; its line-start kernels also by mc_lines.h, see below; the kernels sit in an unnamed namespace; C ABI: mc_ctx_parse_begin / _end / _finish).
 //
 // What it replaces: the row ingest of the reference's loop, extract_contexts.py:140-152 -- `line.split()[:12]`, int(), float(),
 // the two k-mer comparisons -- which mc_parse.cpp does on the host with every core the process may use.  On a GPU box the
@@ -20,9 +20,14 @@
 // that needs strtod (exponents, more digits, inf/nan), values out of range, more rows or segments than the slot holds --
 // the line is flagged and the caller parses the shard with the host parser instead (which also words the reference's error
 // messages).  tests/test_gpu_devparse.py compares every column with the host parser's on all fixtures and on random text.
+//
+// The line-start kernels serve a second unit, the summary of a .diffs file (bed/mc_bedsum.hip): it includes this file through
+// mc_lines.h, which defines MC_LINES_ONLY -- everything below kp_starts is left out then.  The kernels' text stays here, one
+// definition, in the file the benchmark's kernel hash covers.
 namespace {
 
 constexpr int KP_TILE = 16384, KP_THREADS = 256;           // bytes per tile of the newline passes: 64 per thread
+#ifndef MC_LINES_ONLY
 constexpr int KP_ST_ROW = 0, KP_ST_SKIP = 1, KP_ST_UNKNOWN = 2, KP_ST_HOST = 3;
 constexpr int KP_MAX_UNKNOWN = 4096;
 constexpr int KP_EAGER_SEGS = 4096, KP_EAGER_UNKNOWN = 64;   // what travels to the host with the head, unasked
@@ -32,6 +37,7 @@ constexpr int KP_EAGER_SEGS = 4096, KP_EAGER_UNKNOWN = 64;   // what travels to 
 __device__ __forceinline__ bool kp_is_ws(unsigned c) {      // ASCII subset of what str.split() treats as whitespace
     return c == ' ' || (c >= 9 && c <= 13) || (c >= 28 && c <= 31);
 }
+#endif
 
 // bit 7 of every byte of v that equals '\n'
 __device__ __forceinline__ uint32_t kp_nl_bits(uint32_t v) {
@@ -154,6 +160,7 @@ __global__ __launch_bounds__(KP_THREADS) void kp_starts(const char *__restrict__
     }
 }
 
+#ifndef MC_LINES_ONLY
 // A copy done by the compute units instead of a DMA engine (host memory: pinned, so the GPU addresses it).  The DMA
 // engines take transfers in the order they were submitted, whichever stream they came from: a 100 KB copy submitted while a
 // 150 MB shard of text is on its way completes when the text has arrived, 2.8 ms later (measured) -- and every small transfer of
@@ -508,5 +515,7 @@ __global__ __launch_bounds__(256) void kp_place(KpPlaceArgs A) {
     A.t_evmu[row] = make_int2(A.ev[li], A.mu[li]);
     A.t_flags[row] = fl;
 }
+
+#endif  // MC_LINES_ONLY
 
 }  // namespace

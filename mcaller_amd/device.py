@@ -626,6 +626,39 @@ class Device(object):
         check(lib().mc_svm_sigmoid_train(self._ctx, _ptr(dec), _ptr(y), len(dec), C.byref(A), C.byref(B)))
         return A.value, B.value
 
+    # ---- the per-site summary of a .diffs file (csrc/bed/mc_bedsum.hip) ----
+    @_serialized
+    def bed_summarise(self, path=None, text=None, min_depth=15, mod_threshold=0.5, control=False, with_probs=False, gff=False):
+        """The bytes make_bed writes for a `.diffs.<k>` file (`path`) or its text (`text`, bytes), made on the GPU.
+        -> (bytes, number of sites, None), or (None, 0, reason) when the device declines: the caller runs the host code."""
+        if (path is None) == (text is None):
+            raise ValueError('bed_summarise: a path or a text')
+        d = int(min_depth)
+        prm = _lib.BedParams(max(-2 ** 62, min(2 ** 62, d)), float(mod_threshold), int(bool(control)), int(bool(with_probs)), int(bool(gff)), 0)
+        out, n_out, n_sites, status = C.c_void_p(), C.c_int64(), C.c_int64(), C.c_int32()
+        if path is not None:
+            check(lib().mc_bed_summarise_file(self._ctx, os.fsencode(path), C.byref(prm), C.byref(out), C.byref(n_out), C.byref(n_sites),
+                                              C.byref(status)))
+        else:
+            text = bytes(text)
+            check(lib().mc_bed_summarise_text(self._ctx, text, len(text), C.byref(prm), C.byref(out), C.byref(n_out), C.byref(n_sites),
+                                              C.byref(status)))
+        if status.value != 0:
+            return None, 0, lib().mc_last_error().decode('utf-8', 'replace')
+        blob = C.string_at(out.value, n_out.value) if n_out.value else b''
+        return blob, int(n_sites.value), None
+
+    @_serialized
+    def bed_last_stats(self):
+        """Figures of the last bed_summarise: lines, counted rows, entries, sites, longest probe chain, the decline, milliseconds."""
+        st = _lib.BedStats()
+        check(lib().mc_bed_last_stats(self._ctx, C.byref(st)))
+        return {name: getattr(st, name) for name, _ in st._fields_}
+
+    @_serialized
+    def bed_release(self):
+        check(lib().mc_bed_release(self._ctx))
+
     @_serialized
     def mlp_forward(self, X, submodel):
         if getattr(self, '_clf', 'mlp') != 'mlp':

@@ -118,13 +118,15 @@ class Run(object):
             return
         from . import make_bed
         from . import multi_gpu
+        # the file summarised on the GPU (make_bed.summarise_diffs_device; what it declines, and everything with
+        # MCALLER_BED_DEVICE=0, goes through the Python pass)
+        summarise = make_bed.summarise_diffs if os.environ.get('MCALLER_BED_DEVICE', '1') == '0' else make_bed.summarise_diffs_device
         if not self.sharded or not multi_gpu.bed_written:       # (the sharded run declined, or its reduction did not finish)
-            make_bed.summarise_diffs(self.output, self.bed['path'], self.bed['min_depth'], self.bed['mod_threshold'])
+            summarise(self.output, self.bed['path'], self.bed['min_depth'], self.bed['mod_threshold'])
         if self.bed.get('vo'):
             # make_bed.py --vo's per-read probability lists (:114-115); the columns before them must be the reduced ones
             reduced = open(self.bed['path']).read().splitlines() if os.path.exists(self.bed['path']) else None
-            make_bed.summarise_diffs(self.output, self.bed['path'], self.bed['min_depth'], self.bed['mod_threshold'],
-                                     with_probs=True, quiet=True)
+            summarise(self.output, self.bed['path'], self.bed['min_depth'], self.bed['mod_threshold'], with_probs=True, quiet=True)
             if reduced is not None:
                 verbose = [line.rsplit('\t', 1)[0] for line in open(self.bed['path']).read().splitlines()]
                 if verbose != reduced:

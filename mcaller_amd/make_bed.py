@@ -3,7 +3,9 @@
 
   * a `.diffs.<n>` file (`summarise_diffs`, the command line below): rows -> SiteRows -> BED / GFF;
   * flush records on the GPUs (`site_counts`, `write_bed_from_counts`): per-site counts reduced on the device and summed
-    over ranks with one all-reduce (mc_site_allreduce), the one exchange step of the multi-GPU path.
+    over ranks with one all-reduce (mc_site_allreduce), the one exchange step of the multi-GPU path;
+  * the same file on the GPU (`summarise_diffs_device`, `--device`): BED, --control, --vo and GFF; what the device declines
+    goes through `summarise_diffs`.
 
 Options: -f, -d, -t, -p (per-position one-sample t-tests, make_bed.py:115-127; needs scipy, like the reference), --control,
 --vo, --gff (with --vo: fracLow/fracUp/identificationQv, make_bed.py:146-149), --ref.  Plotting is out of scope; the
@@ -154,6 +156,34 @@ def summarise_diffs(diffs_path, out_path, depth_thresh, mod_thresh, positions=No
             out.write('\t'.join(cols) + '\n')
     if wanted is None and not quiet:
         print(count, 'unmethylated' if control else 'methylated', 'loci found with min depth', depth_thresh, 'reads')
+    return count
+
+
+# ---- the same summary made on the GPU (csrc/bed/mc_bedsum.hip) -----------------------------------------------------------
+last_summary = None        # what summarise_diffs_device did last: dict(by='device' | 'host', reason=None | str, n_sites=int)
+
+
+def summarise_diffs_device(diffs_path, out_path, depth_thresh, mod_thresh, control=False, with_probs=False, gff=False,
+                           quiet=False):
+    """summarise_diffs with the file summarised on the GPU (Device.bed_summarise): BED, BED --control, BED --vo, GFF.  The device
+    writes the reference's bytes or declines; then, and for --gff --vo, the host function does the file (and words the
+    errors).  Returns the number of sites; `last_summary` says who made the file."""
+    global last_summary
+    reason = 'out of scope on the device: --gff with --vo' if (gff and with_probs) else None
+    if reason is None:
+        from .device import get_device
+        blob, count, reason = get_device().bed_summarise(path=diffs_path, min_depth=depth_thresh, mod_threshold=mod_thresh,
+                                                         control=control, with_probs=with_probs, gff=gff)
+    if reason is not None:
+        count = summarise_diffs(diffs_path, out_path, depth_thresh, mod_thresh, control=control, with_probs=with_probs, gff=gff,
+                                quiet=quiet)
+        last_summary = dict(by='host', reason=reason, n_sites=count)
+        return count
+    with open(out_path, 'wb') as out:
+        out.write(blob)
+    if not quiet:
+        print(count, 'unmethylated' if control else 'methylated', 'loci found with min depth', depth_thresh, 'reads')
+    last_summary = dict(by='device', reason=None, n_sites=count)
     return count
 
 
@@ -313,7 +343,7 @@ def write_bed_from_counts(aggfi, n_meth, n_total, first, index, contig_names, me
     return count
 
 
-def main(argv=None):
+def build_parser():
     from argparse import ArgumentParser
     parser = ArgumentParser(description='Produce bed file of methylated positions based on mCaller output')
     parser.add_argument('-d', '--min_read_depth', type=int, required=False, default=15)
@@ -328,7 +358,14 @@ def main(argv=None):
     parser.add_argument('--plotdir', type=str, required=False, default='mCaller_position_plots')
     parser.add_argument('--vo', action='store_true', required=False)
     parser.add_argument('-v', '--version', action='version', version='%(prog)s v1.0')
-    args = parser.parse_args(argv)
+    parser.add_argument('--device', action='store_true', required=False,
+                        help='(mcaller_amd) summarise the file on the GPU (BED, --control, --vo, --gff; -p, --ref and --gff --vo '
+                             'stay with the host code)')
+    return parser
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     assert os.path.isfile(args.mCaller_file), 'file not found at ' + args.mCaller_file
     if args.positions:
         output_file = args.mCaller_file.split('.')[0] + '.methylation.positions.summary'
@@ -340,8 +377,22 @@ def main(argv=None):
     print(args.mCaller_file)
     if args.plot or args.plotsummary:
         raise NotImplementedError('plotting is out of scope')
+    if args.device:
+        return _main_device(args, output_file)
     summarise_diffs(args.mCaller_file, output_file, args.min_read_depth, args.mod_threshold, positions=args.positions,
                     control=args.control, with_probs=args.vo, gff=args.gff, ref=args.ref)
+
+
+def _main_device(args, output_file):
+    """main --device: the options the device summarises go there, -p and --ref to the host function as without the flag."""
+    global last_summary
+    if args.positions or args.ref:
+        count = summarise_diffs(args.mCaller_file, output_file, args.min_read_depth, args.mod_threshold, positions=args.positions,
+                                control=args.control, with_probs=args.vo, gff=args.gff, ref=args.ref)
+        last_summary = dict(by='host', reason='out of scope on the device: ' + ('-p' if args.positions else '--ref'), n_sites=count)
+        return
+    summarise_diffs_device(args.mCaller_file, output_file, args.min_read_depth, args.mod_threshold, control=args.control,
+                           with_probs=args.vo, gff=args.gff)
 
 
 if __name__ == '__main__':
