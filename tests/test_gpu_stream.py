@@ -194,8 +194,9 @@ def test_parser_tables_come_from_the_pinned_pool(tmp_path):
 # ---------------------------------------------------------------------------------------------------------------------
 # extract_features over a file, streamed in shards (mcaller_amd.extract_contexts.stream_features)
 # ---------------------------------------------------------------------------------------------------------------------
-def _run_extract(paths, args, monkeypatch, shards):
-    """extract_features (the drop-in) on a case's files -> (outcome, text written, stdout lines)."""
+def _run_extract(paths, args, monkeypatch, shards, keep_output=False):
+    """extract_features (the drop-in) on a case's files -> (outcome, text written, stdout lines).  keep_output: the output file,
+    if there is one, is appended to (not removed first)."""
     import contextlib
     import io
     import os
@@ -207,7 +208,7 @@ def _run_extract(paths, args, monkeypatch, shards):
     else:
         monkeypatch.setenv('MCALLER_NO_STREAM', '1')
     out = '.'.join(paths['tsv'].split('.')[:-1]) + '.diffs.%d.tmp0' % args['k']
-    if os.path.exists(out):
+    if os.path.exists(out) and not keep_output:
         os.remove(out)
     buf = io.StringIO()
     outcome = 'ok'
@@ -332,7 +333,7 @@ def test_streamed_file_with_a_shard_the_device_parser_declines(tmp_path, monkeyp
 
     def spy(*a, **kw):
         out = real(*a, **kw)
-        clocks.append(dict(ec.stream_features.last_clock))
+        clocks.append(dict(real.last_clock))                 # (of the function itself: ec.stream_features is this spy meanwhile)
         return out
     monkeypatch.setattr(ec, 'stream_features', spy)
     got = _run_extract(paths, args, monkeypatch, shards=6)
@@ -408,3 +409,86 @@ def test_a_read_name_on_both_sides_of_a_cut_takes_the_one_table_path(tmp_path, m
     assert not streamed                                          # the stream gave up
     want = _run_extract(paths, args, monkeypatch, shards=0)
     assert got == want and got[0] == 'ok' and len(got[1]) > 500
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# a stream that something other than _Unstreamable stops (the disk is full, a device error, ^C): a host exception between passes
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope='module')
+def busy_case(tmp_path_factory):
+    """A file of twelve shards: when its third batch of rows is due, something is in every stage (ahead, parsing, in flight, pending)."""
+    from mcaller_amd import synth
+    codes = synth.genome(length=300000, seed=41)
+    table, qual = synth.make_table(120000, seed=9, codes=codes, read_len=(700, 4000))
+    paths = synth.write_inputs(table, qual, codes, str(tmp_path_factory.mktemp('busy')))
+    paths['positions'] = None
+    return paths, dict(k=6, skip_thresh=0, qual_thresh=0.0, base='A', motif='GATC', model='r95')
+
+
+@pytest.mark.parametrize('no_overlap', [False, True])
+def test_a_failing_sink_stops_the_stream_and_the_device_is_free_again(busy_case, monkeypatch, no_overlap):
+    """sink() raises on its third call: stream_features raises that very error (its cleanup neither replaces nor swallows it),
+    three times in a row on one device -- a failure that kept four of the twelve table slots would have taken them all -- and
+    the next stream over the same file is a stream (no fall-back for want of a slot) with the one-table path's bytes and lines."""
+    import os
+    from mcaller_amd import extract_contexts as ec
+    from mcaller_amd.device import get_device
+    from mcaller_amd.read_qual import extract_read_quality
+    paths, args = busy_case
+    if no_overlap:
+        monkeypatch.setenv('MCALLER_NO_OVERLAP', '1')
+    else:
+        monkeypatch.delenv('MCALLER_NO_OVERLAP', raising=False)
+    monkeypatch.setenv('MCALLER_STREAM_SHARDS', '12')
+    r2q = extract_read_quality(paths['fastq'])
+    modelset = H.load_modelset(args['model'])
+    dev = get_device()
+    for _ in range(3):
+        calls = []
+
+        def sink(b):
+            calls.append(len(b))
+            if len(calls) == 3:
+                raise OSError('disk full')
+        with pytest.raises(OSError, match='disk full'):
+            ec.stream_features(paths['tsv'], paths['fasta'], r2q, args['k'], args['skip_thresh'], args['qual_thresh'], modelset,
+                               os.path.getsize(paths['tsv']), args['base'], args['motif'], None, sink=sink, device=dev)
+        assert len(calls) >= 3
+    streamed = []
+    real = ec.stream_features
+
+    def spy(*a, **kw):
+        out = real(*a, **kw)
+        streamed.append(out.n_bytes)
+        return out
+    monkeypatch.setattr(ec, 'stream_features', spy)
+    got = _run_extract(paths, args, monkeypatch, shards=12)
+    assert streamed and streamed[0] > 0                         # streamed to the end: every slot was free again
+    want = _run_extract(paths, args, monkeypatch, shards=0)
+    assert got[0] == want[0] == 'ok' and got[2] == want[2]
+    assert got[1] == want[1] and len(got[1]) > 1000
+
+
+def test_a_failed_stream_leaves_no_half_file(busy_case, monkeypatch):
+    """Finisher.write_to raises on its third call (the disk is full): extract_features raises it, and the output file is as it was
+    before the call -- absent, or holding what it held."""
+    import os
+    from mcaller_amd import rows
+    paths, args = busy_case
+    out = '.'.join(paths['tsv'].split('.')[:-1]) + '.diffs.%d.tmp0' % args['k']
+    real, calls = rows.Finisher.write_to, []
+
+    def write_to(self, sink):
+        calls.append(1)
+        if len(calls) == 3:
+            raise OSError('disk full')
+        return real(self, sink)
+    monkeypatch.setattr(rows.Finisher, 'write_to', write_to)
+    outcome, _, _ = _run_extract(paths, args, monkeypatch, shards=8)
+    assert outcome == 'crash:OSError' and len(calls) >= 3 and not os.path.exists(out)
+    with open(out, 'wb') as fh:
+        fh.write(b'kept\n')
+    del calls[:]
+    outcome, _, _ = _run_extract(paths, args, monkeypatch, shards=8, keep_output=True)
+    assert outcome == 'crash:OSError' and len(calls) >= 3
+    assert open(out, 'rb').read() == b'kept\n'
