@@ -609,6 +609,68 @@ int mc_bed_summarise_file(mc_ctx *ctx, const char *path, const mc_bed_params *pr
 int mc_bed_last_stats(mc_ctx *ctx, mc_bed_stats *out);
 int mc_bed_release(mc_ctx *ctx);
 
+/* ===== decimal text -> double, correctly rounded (mcaller_amd/csrc/mc_decimal.h: one header for the host and the device) =====
+ * float(s) of a token [+-]? digits? ('.' digits?)? ([eE] [+-]? digits)? with at least one mantissa digit whose significand
+ * (leading zeros stripped, trailing zeros folded into the exponent) has at most 19 digits and whose decimal exponent q has
+ * |q| <= 27; a zero significand is +-0.0 for any exponent.  Every other form float() accepts or rejects -- whitespace, '_',
+ * inf, nan, more digits, other exponents, "", ".", "e5", "1e", hex -- is declined, never guessed.
+ * mc_parse_double: the host build on s[0, n) -> 1: *out = float(s) bit for bit; 0: declined.
+ * mc_parse_doubles_device: the device build, a lane per token: token i is text[off[i], off[i] + len[i]) (one outside
+ * text[0, n_bytes) is declined); out[i] (0.0 where declined) and ok[i] as above. */
+int mc_parse_double(const char *s, int32_t n, double *out);
+int mc_parse_doubles_device(mc_ctx *ctx, const char *text, int64_t n_bytes, const int64_t *off, const int32_t *len, int64_t n,
+                            double *out, uint8_t *ok);
+
+/* ===== the rows of a `--training_tsv` file as matrices, made on the GPU (load_mCaller_data.py:14-29; csrc/train/mc_trainrows.hip) =====
+ * The text of a `.diffs.<k>.train` file -> per label, in first-occurrence order, the fp64 feature rows and the contexts of the
+ * rows tsv2matrix keeps (>= 6 comma-separated features, none the literal "0"), in file order.  A label is registered by the
+ * first row that carries it, kept or not.  pairs[0, 2 * n_pairs): the two-character centre pairs a context may have (the keys
+ * of base_models; at most MC_TRAINROWS_MAX_PAIRS).  The matrices are tsv2matrix's bit for bit, or the call declines --
+ * *status = 1, mc_last_error says why (mc_train_rows_last_stats: which line and reason), the view is empty and the caller
+ * runs the host code on the file.  Declined: MC_TRAINROWS_DECLINE_* below.  The view's pointers are memory owned by the
+ * context: valid until the next mc_train_rows_* call on it or mc_train_rows_release.  Test knob (environment):
+ * MCALLER_TRAINROWS_HASH_MASK=<hex> is anded onto the 64-bit hash of a label's bytes. */
+#define MC_TRAINROWS_MAX_LABELS   16
+#define MC_TRAINROWS_MAX_FEATURES 64
+#define MC_TRAINROWS_MAX_CONTEXT  63
+#define MC_TRAINROWS_MAX_PAIRS    32
+typedef struct mc_train_rows_view {
+    int32_t n_labels, n_features;  /* n_features: 0 when no row is kept                   */
+    int32_t ctx_width, pad;        /* bytes per context: the longest kept one, NUL-padded */
+    int64_t n_rows_total;
+    const double *X;               /* [n_rows_total][n_features], the labels' blocks back to back, in label order */
+    const char *contexts;          /* [n_rows_total][ctx_width]                           */
+    const char *label_bytes;       /* label i = label_bytes[label_off[i], label_off[i + 1]) */
+    int32_t label_off[MC_TRAINROWS_MAX_LABELS + 1];
+    int32_t pad2;
+    int64_t n_rows[MC_TRAINROWS_MAX_LABELS];
+    int64_t first_line[MC_TRAINROWS_MAX_LABELS];      /* 0-based line that registered the label */
+} mc_train_rows_view;
+typedef struct mc_train_rows_stats {
+    int64_t n_bytes, n_lines, n_kept;
+    int64_t decline_line;          /* 0-based line the decline names, -1: none            */
+    int32_t decline_reason;        /* 0: not declined; MC_TRAINROWS_DECLINE_*             */
+    int32_t n_labels, n_features, in_place_blocks;    /* in_place_blocks: workgroups whose 256 lines did not fit the LDS stage */
+    double ms_read, ms_h2d, ms_kernels, ms_d2h, ms_total;
+} mc_train_rows_stats;
+#define MC_TRAINROWS_DECLINE_HIGH_BYTE     1   /* a byte >= 0x80                                                          */
+#define MC_TRAINROWS_DECLINE_CONTROL       2   /* a control byte other than tab and newline (0x7f and '\r' included)       */
+#define MC_TRAINROWS_DECLINE_FIELDS        3   /* a line with fewer than 7 tab-separated fields (the empty line is one)    */
+#define MC_TRAINROWS_DECLINE_PAIR          4   /* a context whose centre pair is not among `pairs` (the host's KeyError)   */
+#define MC_TRAINROWS_DECLINE_NUMBER        5   /* a kept row with a number mc_decimal.h declines                           */
+#define MC_TRAINROWS_DECLINE_FEATURES      6   /* kept rows with differing feature counts, or more than 64 features        */
+#define MC_TRAINROWS_DECLINE_CONTEXT       7   /* a context longer than 63 bytes                                           */
+#define MC_TRAINROWS_DECLINE_LABELS        8   /* more than 16 distinct labels                                             */
+#define MC_TRAINROWS_DECLINE_LONG_LINE     9   /* a line longer than 65535 bytes                                           */
+#define MC_TRAINROWS_DECLINE_ROWS          10  /* 2^31 - 2 lines or more                                                   */
+#define MC_TRAINROWS_DECLINE_MEMORY        11  /* the text does not fit into free device memory beside its outputs         */
+int mc_train_rows_text(mc_ctx *ctx, const char *text, int64_t n_bytes, const char *pairs, int32_t n_pairs, mc_train_rows_view *out,
+                       int32_t *status);
+/* ... of a file: read in pinned blocks (mc_read_file_range) while the block before is on its way to the device. */
+int mc_train_rows_file(mc_ctx *ctx, const char *path, const char *pairs, int32_t n_pairs, mc_train_rows_view *out, int32_t *status);
+int mc_train_rows_last_stats(mc_ctx *ctx, mc_train_rows_stats *out);
+int mc_train_rows_release(mc_ctx *ctx);
+
 /* ===== measurement plumbing: a table as nanopolish-eventalign text (13 columns), written by all host cores =====
  * For file-to-file timing on synthetic workloads (bench.py); seq = the contig's bases (k-mers of columns 3 and 10). */
 int mc_synth_write_tsv(const char *path, const mc_table_view *table, const char *seq, int64_t seq_len, const char *contig,

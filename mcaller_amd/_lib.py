@@ -101,6 +101,22 @@ class BedStats(C.Structure):
                 ('ms_h2d', C.c_double), ('ms_kernels', C.c_double), ('ms_d2h', C.c_double), ('ms_total', C.c_double)]
 
 
+class TrainRowsView(C.Structure):
+    """mc_train_rows_view (include/mcaller_hip.h)."""
+    MAX_LABELS = 16
+    _fields_ = [('n_labels', C.c_int32), ('n_features', C.c_int32), ('ctx_width', C.c_int32), ('pad', C.c_int32),
+                ('n_rows_total', C.c_int64), ('X', C.c_void_p), ('contexts', C.c_void_p), ('label_bytes', C.c_void_p),
+                ('label_off', C.c_int32 * 17), ('pad2', C.c_int32), ('n_rows', C.c_int64 * 16), ('first_line', C.c_int64 * 16)]
+
+
+class TrainRowsStats(C.Structure):
+    """mc_train_rows_stats (include/mcaller_hip.h)."""
+    _fields_ = [('n_bytes', C.c_int64), ('n_lines', C.c_int64), ('n_kept', C.c_int64), ('decline_line', C.c_int64),
+                ('decline_reason', C.c_int32), ('n_labels', C.c_int32), ('n_features', C.c_int32), ('in_place_blocks', C.c_int32),
+                ('ms_read', C.c_double), ('ms_h2d', C.c_double), ('ms_kernels', C.c_double), ('ms_d2h', C.c_double),
+                ('ms_total', C.c_double)]
+
+
 class Params(C.Structure):
     _fields_ = [('k', C.c_int32), ('skip_thresh', C.c_int32), ('qual_thresh', C.c_double),
                 ('tail_contig', C.c_int32), ('score', C.c_int32),
@@ -239,6 +255,13 @@ def lib():
                                             C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
         L.mc_bed_last_stats.argtypes = [C.c_void_p, C.POINTER(BedStats)]
         L.mc_bed_release.argtypes = [C.c_void_p]
+        L.mc_parse_double.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_double)]
+        L.mc_parse_doubles_device.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.mc_train_rows_text.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_char_p, C.c_int32, C.POINTER(TrainRowsView),
+                                         C.POINTER(C.c_int32)]
+        L.mc_train_rows_file.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int32, C.POINTER(TrainRowsView), C.POINTER(C.c_int32)]
+        L.mc_train_rows_last_stats.argtypes = [C.c_void_p, C.POINTER(TrainRowsStats)]
+        L.mc_train_rows_release.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
@@ -611,6 +634,15 @@ def repr_double(x):
     buf = C.create_string_buffer(40)
     lib().mc_repr_double(float(x), buf)
     return buf.value.decode()
+
+
+def parse_double(token):
+    """float(token) by mc_decimal.h's host build (mc_parse_double): the double, or None for a form that header declines.
+    `token`: bytes (a str is encoded as latin-1, so that every character is one byte)."""
+    if isinstance(token, str):
+        token = token.encode('latin-1', 'replace')
+    out = C.c_double()
+    return out.value if lib().mc_parse_double(token, len(token), C.byref(out)) else None
 
 
 def repr_double_rowtext(x):

@@ -295,6 +295,15 @@ struct mc_ctx {
     size_t bed_stage_cap = 0;
     Event bed_ev[2];
     mc_bed_stats bed_stats = {};
+    // the matrices of a --training_tsv file (train/mc_trainrows.hip): the result handed out last (X and the contexts in pinned
+    // memory, the labels' bytes), the file reader's two pinned blocks with their events, the figures of the last call
+    Pinned tr_X, tr_ctx;
+    size_t tr_X_cap = 0, tr_ctx_cap = 0;
+    std::string tr_labels;
+    Pinned tr_stage[2];
+    size_t tr_stage_cap = 0;
+    Event tr_ev[2];
+    mc_train_rows_stats tr_stats = {};
 };
 
 // ---- what crosses the units ----

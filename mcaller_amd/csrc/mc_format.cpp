@@ -7,6 +7,7 @@
 // in host memory.  Records the host must look at itself (a context that leaves the contig, an unscored record, a
 // sub-model key that does not exist, a base without a complement: the reference's exit/crash paths) stop the run:
 // *stop_at names the first such record and the rows before it are returned.
+#include "mc_decimal.h"
 #include "mc_rowtext.h"
 #include "../../include/mcaller_hip.h"
 
@@ -607,4 +608,10 @@ extern "C" int mc_repr_double(double v, char *out32) {
     char *e = put_repr(out32, v);
     *e = 0;
     return (int)(e - out32);
+}
+
+// float(s) of the token s[0, n) by mc_decimal.h's host build -> 1: *out holds its bits; 0: a form that header declines
+extern "C" int mc_parse_double(const char *s, int32_t n, double *out) {
+    if (!s || !out || n < 0) return 0;
+    return dc_parse(s, n, out);
 }

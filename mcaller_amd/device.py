@@ -659,6 +659,69 @@ class Device(object):
     def bed_release(self):
         check(lib().mc_bed_release(self._ctx))
 
+    # ---- decimal text -> double (csrc/mc_decimal.h) and the rows of a --training_tsv file (csrc/train/mc_trainrows.hip) ----
+    @_serialized
+    def parse_doubles(self, tokens):
+        """float() of every token (bytes) by mc_decimal.h's device build, a lane per token (mc_parse_doubles_device, tests).
+        -> (float64 [n], 0.0 where declined; ok: bool [n])."""
+        tokens = [bytes(t) for t in tokens]
+        length = np.asarray([len(t) for t in tokens], dtype=np.int32)
+        off = np.zeros(len(tokens), dtype=np.int64)
+        if len(tokens) > 1:
+            off[1:] = np.cumsum(length[:-1], dtype=np.int64)
+        text = b''.join(tokens)
+        out = np.zeros(len(tokens), dtype=np.float64)
+        ok = np.zeros(len(tokens), dtype=np.uint8)
+        check(lib().mc_parse_doubles_device(self._ctx, text, len(text), _ptr(off), _ptr(length), len(tokens), _ptr(out), _ptr(ok)))
+        return out, ok.astype(bool)
+
+    @_serialized
+    def training_rows(self, path=None, text=None, pairs=()):
+        """The matrices of a `.diffs.<k>.train` file (`path`) or its text (`text`, bytes), made on the GPU; `pairs`: the
+        two-character centre pairs a context may have.  -> (labels in first-occurrence order, {label: float64 [n, nf]},
+        {label: 'S' array [n]} of the contexts, None) -- copies, the caller's own --, or (None, None, None, reason) when the device
+        declines: the caller runs the host code."""
+        if (path is None) == (text is None):
+            raise ValueError('training_rows: a path or a text')
+        pairs = [p.encode('ascii') if isinstance(p, str) else bytes(p) for p in pairs]
+        if any(len(p) != 2 for p in pairs):
+            raise ValueError('training_rows: a centre pair is two characters')
+        blob = b''.join(pairs)
+        view, status = _lib.TrainRowsView(), C.c_int32()
+        if path is not None:
+            check(lib().mc_train_rows_file(self._ctx, os.fsencode(path), blob, len(pairs), C.byref(view), C.byref(status)))
+        else:
+            text = bytes(text)
+            check(lib().mc_train_rows_text(self._ctx, text, len(text), blob, len(pairs), C.byref(view), C.byref(status)))
+        if status.value != 0:
+            return None, None, None, lib().mc_last_error().decode('utf-8', 'replace')
+        nf, width, total = view.n_features, view.ctx_width, view.n_rows_total
+        X = np.empty((total, nf), dtype=np.float64)
+        ctx = np.empty(total, dtype='S%d' % max(width, 1))
+        if total:                                                 # (one copy each, out of the context's pinned memory)
+            C.memmove(X.ctypes.data, view.X, X.nbytes)
+            C.memmove(ctx.ctypes.data, view.contexts, ctx.nbytes)
+        names = C.string_at(view.label_bytes, view.label_off[view.n_labels]) if view.n_labels else b''
+        labels, sig, grp, at = [], {}, {}, 0
+        for i in range(view.n_labels):
+            label = names[view.label_off[i]:view.label_off[i + 1]].decode('ascii')
+            n = int(view.n_rows[i])
+            labels.append(label)
+            sig[label], grp[label] = X[at:at + n], ctx[at:at + n]
+            at += n
+        return labels, sig, grp, None
+
+    @_serialized
+    def training_rows_last_stats(self):
+        """Figures of the last training_rows: lines, kept rows, labels, features, the decline, milliseconds."""
+        st = _lib.TrainRowsStats()
+        check(lib().mc_train_rows_last_stats(self._ctx, C.byref(st)))
+        return {name: getattr(st, name) for name, _ in st._fields_}
+
+    @_serialized
+    def training_rows_release(self):
+        check(lib().mc_train_rows_release(self._ctx))
+
     @_serialized
     def mlp_forward(self, X, submodel):
         if getattr(self, '_clf', 'mlp') != 'mlp':

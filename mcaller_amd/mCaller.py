@@ -74,8 +74,8 @@ class Run(object):
     def extract(self):
         """-> (signals, contexts) in train mode, None else; leaves `<stem>.diffs.<k>[.train].tmp0` behind."""
         if self.training_tsv:                               # mCaller.py:35-36: the matrix comes from an earlier run
-            from .load_mCaller_data import tsv2matrix
-            return tsv2matrix(self.training_tsv, self.base)
+            from .load_mCaller_data import tsv2matrix_device      # (the file read on the GPU; what it declines: tsv2matrix)
+            return tsv2matrix_device(self.training_tsv, self.base)
         labels = pos2label(self.positions) if self.train else None
         if (self.n_gpus > 1 and self.train) or (not self.train and (self.n_gpus > 1 or self.bed)):     # reads shard over the GPUs of the node (multi_gpu.py)
             from .multi_gpu import extract_features_sharded

@@ -65,6 +65,27 @@ def balanced_rows(signals, groups):
     return labs, sigs, grps
 
 
+def balanced_arrays(signals, groups):
+    """balanced_rows for array leaves (load_mCaller_data.tsv2matrix_device): the same rows as slices of the labels' arrays, put
+    together once.  -> (labels: list, float64 [n, features], contexts [n])."""
+    num_examples = min([len(signals[label]) for label in signals])
+    labs = [label for label in signals for _ in range(num_examples)]
+    sigs = np.concatenate([np.asarray(signals[label], dtype=np.float64)[:num_examples] for label in signals])
+    grps = np.concatenate([np.asarray(groups[label])[:num_examples] for label in signals])
+    return labs, sigs, grps
+
+
+def _has_array_leaves(signals):
+    return len(signals) > 0 and all(isinstance(rows, np.ndarray) for rows in signals.values())
+
+
+def _shown(rows):
+    """The first ten of a balanced column as train_classifier prints them: array rows as lists, 'S' contexts as str."""
+    if not isinstance(rows, np.ndarray):
+        return rows[:10]
+    return [c.decode('ascii') for c in rows[:10].tolist()] if rows.dtype.kind == 'S' else rows[:10].tolist()
+
+
 def _seed():
     env = os.environ.get('MCALLER_SEED', '')
     return int(env) if env != '' else int.from_bytes(os.urandom(7), 'little')
@@ -96,7 +117,7 @@ def _open_fit(labs, sigs, grps, use_groups, device):
     from .device import get_device
     dev = device if device is not None else get_device()
     classes, y, jobs, seeds = cv_jobs(labs, grps, use_groups)
-    return dev, classes, y, jobs, seeds, np.asarray(sigs, dtype=np.float64)
+    return dev, classes, y, jobs, seeds, np.asarray(sigs, dtype=np.float64)     # (an fp64 array passes through as it is)
 
 
 def _fold_scores(fits):
@@ -469,10 +490,11 @@ def train_classifier(signals, groups, modelfile, classifier='NN', plot=False, de
         raise ValueError('unknown classifier ' + str(classifier))
     models, classes_of, n_of = {}, {}, {}
     for twobase_model in signals:
-        labs, sigs, grps = balanced_rows(signals[twobase_model], groups[twobase_model])
-        print(labs[:10])
-        print(sigs[:10])
-        print(grps[:10])
+        balance = balanced_arrays if _has_array_leaves(signals[twobase_model]) else balanced_rows
+        labs, sigs, grps = balance(signals[twobase_model], groups[twobase_model])
+        print(_shown(labs))
+        print(_shown(sigs))
+        print(_shown(grps))
         classes, scores, fit = _classifiers()[classifier]['fit'](labs, sigs, grps, bool(groups), device=device)
         print('%s %s model scores: %s' % (classifier, twobase_model, ','.join([str(s) for s in scores])))
         print('Cross validation accuracy: %0.2f (+/- %0.2f)' % (scores.mean(), scores.std() * 2))
