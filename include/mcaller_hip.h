@@ -671,6 +671,41 @@ int mc_train_rows_file(mc_ctx *ctx, const char *path, const char *pairs, int32_t
 int mc_train_rows_last_stats(mc_ctx *ctx, mc_train_rows_stats *out);
 int mc_train_rows_release(mc_ctx *ctx);
 
+/* ===== the merge behind `-t N` on the GPU: `sort -n -k2 | uniq` over the rows (mCaller.merge_like_sort_uniq; csrc/merge/mc_rowmerge.hip) =====
+ * The lines of the part files (each with its '\n') -> every distinct line once, ordered by (numeric prefix of field 2 as
+ * Decimal compares it, the bytes of the whole line, unsigned, the newline taking part): the bytes merge_like_sort_uniq
+ * writes, or the call declines -- *status = 1, mc_last_error says why (mc_rows_merge_last_stats: which line, reason and
+ * file), nothing is written and the caller runs the host code on the files.  Declined: MC_MERGE_DECLINE_* below.
+ * mc_rows_merge_files writes to `<out_path>.merging` and renames it when complete; it removes no input.
+ * mc_rows_merge_text takes one text; *out points at n_out bytes of pinned memory owned by the context: valid until the
+ * next mc_rows_merge_* call on it or mc_rows_merge_release.
+ * mc_sort_key: the numeric key of one line by the host build of mcaller_amd/csrc/mc_sortkey.h (needs no GPU) -> 0 and the key
+ * (hi, lo), compared as one 128-bit unsigned number; 1: beyond 18 integer or 18 fraction digits; -12: bad arguments. */
+typedef struct mc_rows_merge_stats {
+    int64_t n_bytes, n_lines, n_lines_out, n_out_bytes;
+    int64_t n_tied_after_key;      /* lines in a group of two or more once the numeric key is done */
+    int32_t n_rounds;              /* rounds of 8 bytes the sort ran (the key's two words included)  */
+    int32_t n_passes;              /* radix passes (8 bits each) that moved the rows               */
+    int32_t largest_compared;      /* largest group finished by direct comparison                  */
+    int32_t decline_reason;        /* 0: not declined; MC_MERGE_DECLINE_*                          */
+    int64_t decline_line;          /* 0-based line (over all files) the decline names, -1: none    */
+    int32_t decline_file, pad;     /* index of the part file it lies in, -1: none                  */
+    int64_t kernel_bytes;          /* bytes the kernels read and wrote, by construction            */
+    double ms_read, ms_h2d, ms_kernels, ms_d2h, ms_write, ms_total;
+} mc_rows_merge_stats;
+#define MC_MERGE_DECLINE_CR          1   /* a '\r' (bytes.splitlines cuts there)                                       */
+#define MC_MERGE_DECLINE_NO_NEWLINE  2   /* a part file whose last byte is not '\n'                                    */
+#define MC_MERGE_DECLINE_KEY         3   /* a numeric prefix with more than 18 integer or 18 fraction digits           */
+#define MC_MERGE_DECLINE_LONG_LINE   4   /* a line longer than 65535 bytes                                             */
+#define MC_MERGE_DECLINE_ROWS        5   /* 2^31 - 2 lines or more                                                     */
+#define MC_MERGE_DECLINE_MEMORY      6   /* the texts do not fit into free device memory beside the output and tables  */
+int mc_rows_merge_files(mc_ctx *ctx, const char *const *paths, int32_t n_paths, const char *out_path, int64_t *n_lines_out,
+                        int32_t *status);
+int mc_rows_merge_text(mc_ctx *ctx, const char *text, int64_t n_bytes, const char **out, int64_t *n_out, int32_t *status);
+int mc_rows_merge_last_stats(mc_ctx *ctx, mc_rows_merge_stats *out);
+int mc_rows_merge_release(mc_ctx *ctx);
+int mc_sort_key(const char *line, int64_t n, uint64_t *hi, uint64_t *lo);
+
 /* ===== measurement plumbing: a table as nanopolish-eventalign text (13 columns), written by all host cores =====
  * For file-to-file timing on synthetic workloads (bench.py); seq = the contig's bases (k-mers of columns 3 and 10). */
 int mc_synth_write_tsv(const char *path, const mc_table_view *table, const char *seq, int64_t seq_len, const char *contig,

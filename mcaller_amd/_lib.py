@@ -117,6 +117,18 @@ class TrainRowsStats(C.Structure):
                 ('ms_total', C.c_double)]
 
 
+class RowsMergeStats(C.Structure):
+    """mc_rows_merge_stats (include/mcaller_hip.h)."""
+    _fields_ = [('n_bytes', C.c_int64), ('n_lines', C.c_int64), ('n_lines_out', C.c_int64), ('n_out_bytes', C.c_int64),
+                ('n_tied_after_key', C.c_int64), ('n_rounds', C.c_int32), ('n_passes', C.c_int32), ('largest_compared', C.c_int32),
+                ('decline_reason', C.c_int32), ('decline_line', C.c_int64), ('decline_file', C.c_int32), ('pad', C.c_int32),
+                ('kernel_bytes', C.c_int64), ('ms_read', C.c_double), ('ms_h2d', C.c_double), ('ms_kernels', C.c_double),
+                ('ms_d2h', C.c_double), ('ms_write', C.c_double), ('ms_total', C.c_double)]
+
+
+MERGE_DECLINE = {'cr': 1, 'no_newline': 2, 'key': 3, 'long_line': 4, 'rows': 5, 'memory': 6}     # MC_MERGE_DECLINE_*
+
+
 class Params(C.Structure):
     _fields_ = [('k', C.c_int32), ('skip_thresh', C.c_int32), ('qual_thresh', C.c_double),
                 ('tail_contig', C.c_int32), ('score', C.c_int32),
@@ -256,6 +268,11 @@ def lib():
         L.mc_bed_last_stats.argtypes = [C.c_void_p, C.POINTER(BedStats)]
         L.mc_bed_release.argtypes = [C.c_void_p]
         L.mc_parse_double.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_double)]
+        L.mc_rows_merge_files.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_int32, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        L.mc_rows_merge_text.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        L.mc_rows_merge_last_stats.argtypes = [C.c_void_p, C.POINTER(RowsMergeStats)]
+        L.mc_rows_merge_release.argtypes = [C.c_void_p]
+        L.mc_sort_key.argtypes = [C.c_char_p, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.mc_parse_doubles_device.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.mc_train_rows_text.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_char_p, C.c_int32, C.POINTER(TrainRowsView),
                                          C.POINTER(C.c_int32)]

@@ -304,6 +304,14 @@ struct mc_ctx {
     size_t tr_stage_cap = 0;
     Event tr_ev[2];
     mc_train_rows_stats tr_stats = {};
+    // the merge behind `-t N` (merge/mc_rowmerge.hip): the text handed out last, the two pinned blocks the part files are read
+    // through and the output leaves through, with their events, the figures of the last call
+    Pinned mg_out;
+    size_t mg_out_cap = 0;
+    Pinned mg_stage[2];
+    size_t mg_stage_cap = 0;
+    Event mg_ev[2];
+    mc_rows_merge_stats mg_stats = {};
 };
 
 // ---- what crosses the units ----

@@ -8,6 +8,7 @@
 // sub-model key that does not exist, a base without a complement: the reference's exit/crash paths) stop the run:
 // *stop_at names the first such record and the rows before it are returned.
 #include "mc_decimal.h"
+#include "mc_sortkey.h"
 #include "mc_rowtext.h"
 #include "../../include/mcaller_hip.h"
 
@@ -614,4 +615,10 @@ extern "C" int mc_repr_double(double v, char *out32) {
 extern "C" int mc_parse_double(const char *s, int32_t n, double *out) {
     if (!s || !out || n < 0) return 0;
     return dc_parse(s, n, out);
+}
+
+// the numeric key of `sort -n -k2` for the line s[0, n) by mc_sortkey.h's host build -> 0: (*hi, *lo) hold it; 1: beyond the digit limits
+extern "C" int mc_sort_key(const char *s, int64_t n, uint64_t *hi, uint64_t *lo) {
+    if (!hi || !lo || n < 0 || (n > 0 && !s)) return -12;
+    return sk_key((const unsigned char *)s, n, hi, lo);
 }

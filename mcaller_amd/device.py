@@ -659,6 +659,41 @@ class Device(object):
     def bed_release(self):
         check(lib().mc_bed_release(self._ctx))
 
+    # ---- the merge behind `-t N` (csrc/merge/mc_rowmerge.hip) ----
+    @_serialized
+    def merge_rows(self, paths=None, text=None, out_path=None):
+        """`sort -n -k2 | uniq` as mCaller.merge_like_sort_uniq does it, on the GPU: over the part files `paths` into `out_path`
+        (written beside it and renamed when complete; the part files stay), or over one `text` (bytes).
+        -> (lines written, None) / (the merged bytes, None), or (None, reason) when the device declines: the caller runs the host code."""
+        if (paths is None) == (text is None) or (paths is not None and out_path is None):
+            raise ValueError('merge_rows: part files and an output path, or a text')
+        status = C.c_int32()
+        if paths is not None:
+            arr = (C.c_char_p * max(len(paths), 1))(*[os.fsencode(p) for p in paths])
+            n_lines = C.c_int64()
+            check(lib().mc_rows_merge_files(self._ctx, arr, len(paths), os.fsencode(out_path), C.byref(n_lines), C.byref(status)))
+            if status.value != 0:
+                return None, lib().mc_last_error().decode('utf-8', 'replace')
+            return int(n_lines.value), None
+        text = bytes(text)
+        out, n_out = C.c_void_p(), C.c_int64()
+        check(lib().mc_rows_merge_text(self._ctx, text, len(text), C.byref(out), C.byref(n_out), C.byref(status)))
+        if status.value != 0:
+            return None, lib().mc_last_error().decode('utf-8', 'replace')
+        return (C.string_at(out.value, n_out.value) if n_out.value else b''), None
+
+    @_serialized
+    def merge_rows_last_stats(self):
+        """Figures of the last merge_rows: bytes, lines in and out, rounds, radix passes, lines still tied after the numeric key,
+        the largest group finished by comparison, the decline (line, reason, file), kernel bytes, milliseconds."""
+        st = _lib.RowsMergeStats()
+        check(lib().mc_rows_merge_last_stats(self._ctx, C.byref(st)))
+        return {name: getattr(st, name) for name, _ in st._fields_ if name != 'pad'}
+
+    @_serialized
+    def merge_rows_release(self):
+        check(lib().mc_rows_merge_release(self._ctx))
+
     # ---- decimal text -> double (csrc/mc_decimal.h) and the rows of a --training_tsv file (csrc/train/mc_trainrows.hip) ----
     @_serialized
     def parse_doubles(self, tokens):

@@ -62,6 +62,31 @@ def merge_like_sort_uniq(paths, out_path):
         out.writelines(sorted(lines, key=lambda l: (numeric_key_k2(l), l)))
 
 
+MERGE_DEVICE_DEFAULT = '0'      # MCALLER_MERGE_DEVICE when it is not set: the device path is the default once it is measured faster (README)
+last_merge = None      # who did the last merge of a `-t N` run: dict(by='device' | 'host', reason, n_lines, n_written)
+
+
+def merge_like_sort_uniq_device(paths, out_path):
+    """merge_like_sort_uniq with the sort done on the GPU (Device.merge_rows), when MCALLER_MERGE_DEVICE=1.  The device writes
+    the host function's bytes or declines; then, and with MCALLER_MERGE_DEVICE=0, the host function does the files.  The part
+    files are removed either way; `last_merge` says who made the file."""
+    global last_merge
+    paths = list(paths)
+    reason = None if os.environ.get('MCALLER_MERGE_DEVICE', MERGE_DEVICE_DEFAULT) == '1' else 'MCALLER_MERGE_DEVICE is not 1'
+    n_written = None
+    if reason is None:
+        from .device import get_device
+        dev = get_device()
+        n_written, reason = dev.merge_rows(paths=paths, out_path=out_path)
+    if reason is not None:
+        merge_like_sort_uniq(paths, out_path)
+        last_merge = dict(by='host', reason=reason, n_lines=None, n_written=None)
+        return
+    for path in paths:
+        os.remove(path)
+    last_merge = dict(by='device', reason=None, n_lines=int(dev.merge_rows_last_stats()['n_lines']), n_written=n_written)
+
+
 class Run(object):
     """One invocation: what mCaller.py:25-115 does around extract_features, without its process fan-out (the GPU path is one
     process per GPU and writes the single-process row order; `-t` only selects the reference's merge step)."""
@@ -107,7 +132,7 @@ class Run(object):
         tmp = glob.glob(self.stem + '*.tmp[0-9]*')
         if self.threads > 1:
             print('Merging files...')
-            merge_like_sort_uniq(tmp, self.output)
+            merge_like_sort_uniq_device(tmp, self.output)
         else:
             os.rename(tmp[0], self.output)
 
