@@ -601,6 +601,20 @@ typedef struct mc_bed_stats {
 #define MC_BED_DECLINE_ROWS        10
 #define MC_BED_DECLINE_MEMORY      11
 #define MC_BED_DECLINE_OPTIONS     12
+/* ... with a positions file (mc_bed_positions_*); 13-15 name a line of the POSITIONS file, 16-19 a row, 20-25 an entry's first row */
+#define MC_BED_DECLINE_POS_HIGH_BYTE 13  /* positions: a byte >= 0x80                                                  */
+#define MC_BED_DECLINE_POS_CONTROL   14  /* positions: a control byte other than tab and newline                       */
+#define MC_BED_DECLINE_POS_LONG_LINE 15  /* positions: a line longer than 65535 bytes                                  */
+#define MC_BED_DECLINE_VALUE         16  /* a counted row with a value mc_decimal.h declines (nan, inf, blanks, ...)   */
+#define MC_BED_DECLINE_FEW_VALUES    17  /* a counted row with fewer than two values                                   */
+#define MC_BED_DECLINE_MANY_VALUES   18  /* a counted row with more than MC_BED_MAX_VALUES values                      */
+#define MC_BED_DECLINE_VALUE_COUNT   19  /* a counted row with another number of values than the first counted row     */
+#define MC_BED_DECLINE_ZERO_VARIANCE 20  /* depth >= 2 and a column without spread (the host prints inf / nan)         */
+#define MC_BED_DECLINE_FAR_TAIL      21  /* a log10 p below -290                                                       */
+#define MC_BED_DECLINE_PRINT_RANGE   22  /* a rounded value mc_rowtext.h does not print (|v| >= 1e9)                   */
+#define MC_BED_DECLINE_ROUNDING_TIE  23  /* a value within its error bound of a rounding tie of np.round(., 3)         */
+#define MC_BED_DECLINE_DEPTH         24  /* an entry of more than 100001 rows (the tail function's error is measured up to there) */
+#define MC_BED_MAX_VALUES 64
 int mc_bed_summarise_text(mc_ctx *ctx, const char *text, int64_t n_bytes, const mc_bed_params *prm, const char **out,
                           int64_t *n_out, int64_t *n_sites, int32_t *status);
 /* ... of a file: read in pinned blocks (mc_read_file_range) while the block before is on its way to the device. */
@@ -608,6 +622,38 @@ int mc_bed_summarise_file(mc_ctx *ctx, const char *path, const mc_bed_params *pr
                           int64_t *n_sites, int32_t *status);
 int mc_bed_last_stats(mc_ctx *ctx, mc_bed_stats *out);
 int mc_bed_release(mc_ctx *ctx);
+/* ... with make_bed -p: a positions file beside the .diffs file (make_bed.py:13-19,:84-96,:115-127).  Every positions line with
+ * len(line) > 3, the newline counted, is stripped (blanks and tabs) and split on tabs; its first four fields are one tuple; a
+ * row counts when its context has 'M' at its centre AND (chrom, pos text, decimal digits of pos + 1, strand) is such a tuple,
+ * byte for byte.  Every entry is written (min_depth, mod_threshold and control select nothing).  A BED row gets two more
+ * columns before the --vo list: str(np.round(., 3)) of the largest t statistic and of the sum of -log10 p of one-sample
+ * t-tests of every value column of field 5 but the last against 0 (mcaller_amd/csrc/mc_tstat.h); "nan" twice at depth 1.
+ * With gff the ordinary attributes are written for every entry.  Every printed value is the host's or the call declines
+ * (MC_BED_DECLINE_* 13-24 on top of the above): the sums are compensated, the bound on |device - host| of every value is
+ * derived (moments) and measured (tail function; profiles/tstat_error.json), and a value whose bound reaches a rounding
+ * tie declines the file.  MCALLER_BED_HASH_MASK applies to the hash of the position tuples too. */
+int mc_bed_positions_text(mc_ctx *ctx, const char *text, int64_t n_bytes, const char *positions, int64_t n_positions_bytes,
+                          const mc_bed_params *prm, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status);
+int mc_bed_positions_file(mc_ctx *ctx, const char *path, const char *positions_path, const mc_bed_params *prm, const char **out,
+                          int64_t *n_out, int64_t *n_sites, int32_t *status);
+
+/* ===== the Student t arithmetic of make_bed -p (mcaller_amd/csrc/mc_tstat.h: one header for the host and the device) =====
+ * mc_tstat: the host build on one triple (n rows, their mean, their sample variance with ddof = 1) -> status bits
+ * (0: fine; 1: n < 2; 2: no spread or not finite; 4: log10 p < -290; 8: the continued fraction did not settle), *t the
+ * statistic mean / sqrt(var / n), *log10_p the base-10 logarithm of the two-sided tail probability with n - 1 degrees of
+ * freedom, computed in the log domain.  mc_tstat_device: the device build, a lane per triple.
+ * mc_tstat_round3: rint(v * 1000) / 1000, the fp64 operations of np.round(v, 3).  mc_tstat_tie: 1 when np.round(h, 3) can
+ * differ from np.round(v, 3) for an h within err of v (another thousandth, or the other zero).
+ * mc_tstat_site: the host build of an entry's two printed values from its rows X[n_rows][n_cols] (row-major; the LAST
+ * column is dropped, as make_bed drops the last value) -> out2 = {round3(max t), round3(sum -log10 p)}, the return value
+ * the status bits above, 16: a rounding tie within the error bound, 32: more than 100001 rows, 64: a rounded value
+ * mc_rowtext.h does not print. */
+int mc_tstat(double n, double mean, double var, double *t, double *log10_p);
+int mc_tstat_device(mc_ctx *ctx, const double *n, const double *mean, const double *var, int64_t count, double *t,
+                    double *log10_p, int32_t *status);
+double mc_tstat_round3(double v);
+int mc_tstat_tie(double v, double err);
+int mc_tstat_site(const double *X, int64_t n_rows, int32_t n_cols, double *out2);
 
 /* ===== decimal text -> double, correctly rounded (mcaller_amd/csrc/mc_decimal.h: one header for the host and the device) =====
  * float(s) of a token [+-]? digits? ('.' digits?)? ([eE] [+-]? digits)? with at least one mantissa digit whose significand

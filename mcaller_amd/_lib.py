@@ -267,6 +267,16 @@ def lib():
                                             C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
         L.mc_bed_last_stats.argtypes = [C.c_void_p, C.POINTER(BedStats)]
         L.mc_bed_release.argtypes = [C.c_void_p]
+        L.mc_bed_positions_text.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, C.POINTER(BedParams),
+                                            C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        L.mc_bed_positions_file.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(BedParams), C.POINTER(C.c_void_p),
+                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        L.mc_tstat.argtypes = [C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.mc_tstat_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mc_tstat_round3.argtypes = [C.c_double]
+        L.mc_tstat_round3.restype = C.c_double
+        L.mc_tstat_tie.argtypes = [C.c_double, C.c_double]
+        L.mc_tstat_site.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
         L.mc_parse_double.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_double)]
         L.mc_rows_merge_files.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_int32, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
         L.mc_rows_merge_text.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
@@ -651,6 +661,33 @@ def repr_double(x):
     buf = C.create_string_buffer(40)
     lib().mc_repr_double(float(x), buf)
     return buf.value.decode()
+
+
+def tstat(n, mean, var):
+    """t and log10 p of a one-sample t-test from (rows, mean, sample variance) by mc_tstat.h's host build (mc_tstat).
+    -> (status bits, t, log10 p); the bits: include/mcaller_hip.h."""
+    t, l = C.c_double(), C.c_double()
+    st = lib().mc_tstat(float(n), float(mean), float(var), C.byref(t), C.byref(l))
+    return st, t.value, l.value
+
+
+def tstat_round3(v):
+    """np.round(v, 3) by mc_tstat.h's host build."""
+    return lib().mc_tstat_round3(float(v))
+
+
+def tstat_tie(v, err):
+    """Can np.round(h, 3) differ from np.round(v, 3) for an h within err of v?  (mc_tstat.h's tie test, host build)"""
+    return bool(lib().mc_tstat_tie(float(v), float(err)))
+
+
+def tstat_site(rows):
+    """The two values make_bed -p prints for an entry with the value rows `rows` ([n][values], the last value dropped), by the
+    host build of what the kernels do (mc_tstat_site) -> (status bits, round3(max t), round3(sum -log10 p))."""
+    X = np.ascontiguousarray(rows, dtype=np.float64)
+    out = np.zeros(2, dtype=np.float64)
+    st = lib().mc_tstat_site(X.ctypes.data, X.shape[0], X.shape[1], out.ctypes.data)
+    return st, float(out[0]), float(out[1])
 
 
 def parse_double(token):

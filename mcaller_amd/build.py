@@ -17,7 +17,8 @@ WARN = ['-Wall', '-Wno-unused-function', '-Wno-unused-const-variable']
 def shared_deps():
     """Headers and included files: every unit depends on them."""
     deps = [os.path.join(os.path.dirname(HERE), 'include', 'mcaller_hip.h')]
-    deps += [os.path.join(HERE, 'csrc', f) for f in os.listdir(os.path.join(HERE, 'csrc')) if f.endswith(('.inc', '.h'))]
+    for root, _, files in os.walk(os.path.join(HERE, 'csrc')):          # (csrc/bed/*.inc too)
+        deps += [os.path.join(root, f) for f in files if f.endswith(('.inc', '.h'))]
     return deps
 
 

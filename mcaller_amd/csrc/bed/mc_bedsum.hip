@@ -1,6 +1,7 @@
 // mc_bedsum.hip -- the per-site summary of a `.diffs.<k>` file on the GPU: what make_bed.py:67-164 writes for BED, BED --control,
-// BED --vo and GFF (C ABI: mc_bed_summarise_text / _file, mc_bed_last_stats, mc_bed_release; Python: Device.bed_summarise,
-// make_bed.summarise_diffs_device).  The unit stands in csrc/bed/, beside the units of the passes, not among them: no pass runs
+// BED --vo and GFF, and with a positions file for -p (C ABI: mc_bed_summarise_text / _file, mc_bed_positions_text / _file,
+// mc_bed_last_stats, mc_bed_release; Python: Device.bed_summarise, make_bed.summarise_diffs_device).  The unit stands in csrc/bed/,
+// beside the units of the passes, not among them: no pass runs
 // its kernels, and the benchmark's kernel hash (bench.KERNEL_SOURCES) names the files of the pass path one by one.
 //
 // Everything here is exact by construction -- integer counts, byte comparisons, one fp64 division whose quotient is printed by the
@@ -15,7 +16,34 @@
 //   * a table with fewer than 2 x the counted rows' slots (only MCALLER_BED_TABLE_SLOTS makes one)
 //   * a text that does not fit into free device memory beside its tables: the WHOLE text stays resident, entries are compared
 //     against the bytes of a representative row and the output copies its fields from there
-//   * --gff with --vo, -p, --ref: not attempted (the caller does not ask)
+//   * --gff with --vo, --ref: not attempted (the caller does not ask)
+//
+// make_bed -p (mc_bed_positions_text / _file; Device.bed_summarise(positions_path= / positions_text=), make_bed.summarise_diffs_device(
+// positions=); from the command line with MCALLER_BED_POSITIONS_DEVICE=1): a positions file beside the rows.  A row counts when its
+// context has 'M' at its centre AND (chrom, pos text, digits of pos + 1, strand) is a tuple of the file, byte for byte; every entry
+// is written, -d / -t / --control select nothing; a BED row carries two more columns before the --vo list, str(np.round(., 3)) of
+// the largest t statistic and of the sum of -log10 p of one-sample t-tests of every value column of field 5 but the last
+// ("nan" twice at depth 1); --gff writes the ordinary attributes.  The two numbers are not exact by construction, so every one comes
+// with a bound on |device - host| (mc_tstat.h: the moments' part derived, the tail function's part measured against SciPy), and
+// a value whose bound reaches a rounding tie declines the FILE -- exact bytes or a decline, never a guess.  More declines:
+//   * positions file: a byte >= 0x80; a control byte other than tab and newline; a line longer than 65535 bytes
+//   * a counted row with a value mc_decimal.h declines (nan, inf, blanks, more than 19 digits); with fewer than two values; with more
+//     than MC_BED_MAX_VALUES; with another number of values than the first counted row
+//   * an entry of depth >= 2 with a column without spread (the host prints inf / nan, and max() over NaNs depends on the order); a
+//     log10 p below -290; a rounded value of 1e9 or more (mc_rowtext.h does not print it; "-0.0" it does); more than 100001 rows
+//     (the tail function is measured up to 10^5 degrees of freedom); the tie test
+// Its steps (mc_posset.inc, mc_sitestats.inc):
+//   kq_parse / kq_insert   the positions file: line starts by kp_*, a lane per line (the `len(line) > 3` rule, strip, the first four
+//                 fields, a 64-bit hash), an open-addressing table (atomicCAS, byte comparison); MCALLER_BED_HASH_MASK applies
+//   kb_parse      probes that table for a row with a centre 'M' (the digits of pos + 1 are generated into the hash); an unwanted row is
+//                 not counted and its values are never looked at; a counted row's commas are counted
+//   kq_counts     every counted row has the first one's number of values
+//   kb_sums .. kb_sort_*   every entry selected, every entry's bucket in ascending row order (the --vo machinery)
+//   kq_features   a lane per NUMBER: mc_decimal.h into an fp64 matrix in bucket order
+//   kq_moments_small / _large   per (entry, column) the mean and the centred sum of squares, compensated (two-sum), in an order the
+//                 row order alone fixes: up to BS_SMALL rows a lane, more a wave (lane l the rows l, l + 64, ...; a fixed tree)
+//   kq_finish     a lane per entry: t, log10 p, their bounds, the maximum and the sum, np.round(., 3), the tie test, the digits
+//   kb_sums / kb_apply again (the rows' sizes with the two columns), kb_write
 //
 // The steps (one lane per line unless said otherwise; n = lines):
 //   kp_count / kp_scan / kp_starts   line starts (the device parser's kernels: mc_lines.h)
@@ -36,6 +64,8 @@
 // wave64; no library sort; every buffer, event and stream through the owners of mc_own.h.
 #include "../mc_lines.h"
 #include "../mc_rowtext.h"
+#include "../mc_decimal.h"
+#include "../mc_tstat.h"
 
 #include <sys/stat.h>
 
@@ -46,6 +76,7 @@ namespace {
 constexpr int BS_STAGE = 48 * 1024;          // LDS a workgroup of kb_parse stages its 256 lines in (two workgroups share a CU's 160 KB)
 constexpr int BS_SMALL = 32;                 // buckets up to this depth are sorted by insertion
 constexpr uint8_t BS_F_COUNTED = 1, BS_F_METH = 2, BS_F_PROB = 4;
+constexpr uint32_t BS_META_NAN = 1u << 20;   // a statistic the host prints as "nan" (beside the bits of rt_num_pack)
 
 struct BsHead {                              // device-side result block (copied to the host as it is)
     KpHead kp;                               // n_newlines (kp_scan), n_lines (kp_starts)
@@ -54,6 +85,8 @@ struct BsHead {                              // device-side result block (copied
     long long tot_bucket, tot_sel, tot_bytes;     // totals of the three scans
     unsigned int n_large;
     int longest_probe;
+    unsigned long long first_counted;        // -p: the smallest counted line (~0: none)
+    int nv, pad;                             // -p: values per row (kq_counts)
 };
 
 struct BsRow { uint16_t t[7]; uint16_t len; };   // the tabs of a line (offsets from its start; t[6] = len in a 7-field row), its length
@@ -83,11 +116,30 @@ struct BsArgs {
     long long *sel_off, *sel_vo_at;
     uint32_t *bucket, *bucket_tmp;
     char *out;
+    // -p (mc_posset.inc, mc_sitestats.inc)
+    int positions;                           // rows are wanted by the position set; every entry is written
+    int stats;                               // ... and a BED row carries the two statistics columns (not with --gff)
+    int stats_ready;                         // the statistics are made: the sizing and writing kernels count and print them
+    int buckets;                             // the rows of every entry are wanted in row order (--vo, or the statistics)
+    const char *ptext;
+    int64_t p_bytes, p_lines, p_nl;
+    const long long *p_start;
+    uint4 *p_line;
+    uint64_t *p_hash;
+    unsigned long long *p_table;
+    uint64_t p_mask;
+    uint32_t *nval;                          // per line: comma-separated values of field 5
+    int nv;
+    double *X, *mom;                         // [n_counted][nv] in bucket order; [n_sel][nv - 1][3]
+    uint64_t *st_lo;                         // per entry (by the row that claimed its slot) x 2: the digits of the two values
+    uint32_t *st_meta;
 };
 
 __device__ __forceinline__ void bs_flag(const BsArgs &A, int64_t li, int reason) {
     atomicMin(&A.head->decline, ((unsigned long long)li << 8) | (unsigned long long)reason);
 }
+
+#include "mc_posset.inc"
 
 // One line: t[x - adj] is byte x of the text (the staged piece in LDS, or the text itself with adj = 0: one address space per call site)
 __device__ __forceinline__ bool bs_parse_line(const BsArgs &A, const char *t, const int64_t adj, const int64_t li) {
@@ -96,7 +148,7 @@ __device__ __forceinline__ bool bs_parse_line(const BsArgs &A, const char *t, co
     A.fl[li] = 0;
     if (e - b > 65535) { bs_flag(A, li, MC_BED_DECLINE_LONG_LINE); return false; }
     const int len = (int)(e - b);
-    int t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0, t5 = 0, t6 = 0, nt = 0;
+    int t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0, t5 = 0, t6 = 0, nt = 0, commas = 0;
     bool bad_hi = false, bad_ctrl = false;
     uint64_t h = 0xcbf29ce484222325ull;                       // FNV-1a over the key fields, a 0xff between fields (no such byte in a line)
     for (int i = 0; i < len; ++i) {
@@ -110,6 +162,8 @@ __device__ __forceinline__ bool bs_parse_line(const BsArgs &A, const char *t, co
             ++nt;
         } else if (nt == 0 || nt == 2 || nt == 3 || nt == 5) {     // chrom, pos, context, strand
             h = (h ^ c) * 0x100000001b3ull;
+        } else if (nt == 4) {
+            commas += c == ',';
         }
     }
     int reason = 0;
@@ -133,7 +187,12 @@ __device__ __forceinline__ bool bs_parse_line(const BsArgs &A, const char *t, co
     }
     if (reason) { bs_flag(A, li, reason); return false; }
     const int cn = t3 - t2 - 1;
-    const bool counted = t[b + t2 + 1 + cn / 2] == 'M';
+    bool counted = t[b + t2 + 1 + cn / 2] == 'M';
+    if (counted && A.positions) counted = bq_wanted(A, t + b, t0, t1, t2, t4, t5, pos);      // an unwanted row: its values are never looked at
+    if (counted && A.stats) {
+        A.nval[li] = (uint32_t)commas + 1u;
+        atomicMin(&A.head->first_counted, (unsigned long long)li);
+    }
     const bool meth = t[b + t5 + 1] == 'm';
     int pb = len, pe = len;                                   // f[7].strip(): blanks are the only whitespace a line still holds
     if (nt == 7) {
@@ -279,6 +338,13 @@ __device__ __forceinline__ void bs_put_entry(const BsArgs &A, Sink &o, int64_t l
     bs_put_span(o, t + R.t[4] + 1, R.t[5] - R.t[4] - 1);
     o.put('\t');
     rt_put_uint(o, depth);
+    if (A.stats && A.stats_ready)
+        for (int q = 0; q < 2; ++q) {                                  // str(np.round(., 3)) of the largest t and of the sum of -log10 p
+            const uint32_t meta = A.st_meta[2 * (size_t)A.row_ent[li] + q];
+            o.put('\t');
+            if (meta & BS_META_NAN) bs_put_lit(o, "nan");
+            else rt_put_num(o, rt_num_unpack(A.st_lo[2 * (size_t)A.row_ent[li] + q], meta));
+        }
 }
 
 struct BsEnt { bool head, sel; uint32_t depth, meth, rep; long long bytes; };
@@ -293,7 +359,8 @@ __device__ __forceinline__ BsEnt bs_entry(const BsArgs &A, int64_t li, bool want
     E.depth = A.ent_depth[E.rep];
     E.meth = A.ent_meth[E.rep];
     // depth >= d and (fraction >= t) != control, the fraction an fp64 quotient (make_bed.py:21-28,:135-138)
-    E.sel = (long long)E.depth >= A.min_depth && (((double)E.meth / (double)E.depth >= A.thresh) != (A.control != 0));
+    // (-p: every entry -- its rows were wanted, make_bed.py:110-114)
+    E.sel = A.positions || ((long long)E.depth >= A.min_depth && (((double)E.meth / (double)E.depth >= A.thresh) != (A.control != 0)));
     if (E.sel && want_bytes) {
         RtCount c;
         bs_put_entry(A, c, li, E.depth, E.meth);
@@ -331,7 +398,7 @@ __global__ __launch_bounds__(256) void kb_sums(BsArgs A) {
     (void)bs_block_excl(E.head ? 1 : 0, s_w, &heads);
     if (threadIdx.x == 0) {
         for (int q = 0; q < 3; ++q) A.blk_sum[q * A.nblk + blockIdx.x] = tot[q];
-        if (heads) atomicAdd(&A.head->n_entries, (unsigned long long)heads);
+        if (heads && !A.stats_ready) atomicAdd(&A.head->n_entries, (unsigned long long)heads);      // (-p sizes twice)
     }
 }
 
@@ -343,7 +410,7 @@ __global__ __launch_bounds__(256) void kb_apply(BsArgs A) {
     const long long boff = A.blk_off[blockIdx.x] + bs_block_excl(E.head ? (long long)E.depth : 0, s_w, &tot);
     const long long k = A.blk_off[A.nblk + blockIdx.x] + bs_block_excl(E.sel ? 1 : 0, s_w, &tot);
     const long long at = A.blk_off[2 * A.nblk + blockIdx.x] + bs_block_excl(E.bytes, s_w, &tot);
-    if (E.head && A.with_probs) A.ent_boff[li] = (uint32_t)boff;
+    if (E.head && A.buckets) A.ent_boff[li] = (uint32_t)boff;
     if (E.sel) { A.sel_line[k] = (uint32_t)li; A.sel_off[k] = at; }
 }
 
@@ -437,6 +504,8 @@ __global__ __launch_bounds__(256) void kb_sort_large(BsArgs A, int n_pass) {
     }
 }
 
+#include "mc_sitestats.inc"
+
 __global__ __launch_bounds__(256) void kb_write(BsArgs A, int64_t n_sel) {
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (k >= n_sel) return;
@@ -497,6 +566,18 @@ const char *bs_reason_text(int reason) {
     case MC_BED_DECLINE_ROWS: return "more lines than rows are numbered for (2^31 - 2)";
     case MC_BED_DECLINE_MEMORY: return "the text and its tables do not fit into free device memory";
     case MC_BED_DECLINE_OPTIONS: return "--gff with --vo is not summarised on the device";
+    case MC_BED_DECLINE_POS_HIGH_BYTE: return "the positions file has a byte >= 0x80";
+    case MC_BED_DECLINE_POS_CONTROL: return "the positions file has a control byte other than tab and newline";
+    case MC_BED_DECLINE_POS_LONG_LINE: return "the positions file has a line longer than 65535 bytes";
+    case MC_BED_DECLINE_VALUE: return "a value that is not a plain decimal number of up to 19 digits";
+    case MC_BED_DECLINE_FEW_VALUES: return "a row with fewer than two values";
+    case MC_BED_DECLINE_MANY_VALUES: return "a row with more than 64 values";
+    case MC_BED_DECLINE_VALUE_COUNT: return "rows with differing numbers of values";
+    case MC_BED_DECLINE_ZERO_VARIANCE: return "a site with a value column without spread";
+    case MC_BED_DECLINE_FAR_TAIL: return "a log10 p below -290";
+    case MC_BED_DECLINE_PRINT_RANGE: return "a statistic of 1e9 or more";
+    case MC_BED_DECLINE_ROUNDING_TIE: return "a statistic too close to a rounding tie of np.round(., 3) to vouch for its last digit";
+    case MC_BED_DECLINE_DEPTH: return "a site of more than 100001 rows";
     }
     return "unknown";
 }
@@ -522,9 +603,65 @@ bool bs_fits(size_t bytes) {
     return free_b > margin && bytes <= free_b - margin;
 }
 
-// The text is on the device (d_text[0, n), padded; copies enqueued on c->up_stream): everything behind that
-int bs_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const mc_bed_params *P, const char **out, int64_t *n_out,
-           int64_t *n_sites, int32_t *status) {
+// the line starts of a text on the device (padded): *n_nl newlines, *n_lines lines, line_start[0 .. n_lines] (n > 0)
+int bs_lines(Pool &pool, hipStream_t st, const char *d_text, int64_t n, BsHead *d_head, BsHead &h, long long **line_start, int64_t *n_nl,
+             int64_t *n_lines, bool *too_many) {
+    const int64_t n_tiles = (n + KP_TILE - 1) / KP_TILE;
+    long long *tile_cnt = nullptr, *tile_off = nullptr;
+    *too_many = false;
+    if (pool.get(&tile_cnt, (size_t)n_tiles) || pool.get(&tile_off, (size_t)n_tiles)) return -10;
+    hipLaunchKernelGGL(kp_count, dim3((unsigned)n_tiles), dim3(KP_THREADS), 0, st, d_text, n, tile_cnt);
+    hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)tile_cnt, n_tiles, tile_off, &d_head->kp.n_newlines);
+    HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *n_nl = h.kp.n_newlines;
+    if (*n_nl + 1 >= ((int64_t)1 << 31) - 2) { *too_many = true; return 0; }
+    const int64_t cap_lines = *n_nl + 2;
+    if (!bs_fits((size_t)cap_lines * 8 + ((size_t)1 << 20))) { *too_many = true; return 0; }
+    if (pool.get(line_start, (size_t)cap_lines)) return -10;
+    hipLaunchKernelGGL(kp_starts, dim3((unsigned)n_tiles), dim3(KP_THREADS), 0, st, d_text, n, (const long long *)tile_off, *line_start,
+                       cap_lines, &d_head->kp);
+    // (the last line may lack its newline: the same count kp_starts makes; the last byte is not on the host, so it is asked for)
+    HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *n_lines = h.kp.n_lines;
+    return 0;
+}
+
+// -p: the positions text (on the device, padded) into the table the row parser probes -> 0: go on; 1: declined
+int bs_position_set(mc_ctx *c, Pool &pool, BsArgs &A, BsHead *d_head, BsHead &h, const char *d_ptext, int64_t pn, int32_t *status, int *rc) {
+    hipStream_t st = c->stream;
+    *rc = 0;
+    A.ptext = d_ptext; A.p_bytes = pn; A.p_mask = 15;
+    long long *p_start = nullptr;
+    if (pn > 0) {
+        bool too_many = false;
+        if ((*rc = bs_lines(pool, st, d_ptext, pn, d_head, h, &p_start, &A.p_nl, &A.p_lines, &too_many))) return 1;
+        if (too_many) { (void)bs_decline(c, status, MC_BED_DECLINE_ROWS, -1); return 1; }
+    }
+    A.p_start = p_start;
+    const size_t pl = (size_t)std::max<int64_t>(A.p_lines, 1);
+    uint64_t slots = 16;
+    while ((int64_t)slots < 2 * A.p_lines) slots <<= 1;
+    if (!bs_fits(pl * (16 + 8) + (size_t)slots * 8)) { (void)bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1); return 1; }
+    if (pool.get(&A.p_line, pl) || pool.get(&A.p_hash, pl) || pool.get(&A.p_table, (size_t)slots)) { *rc = -10; return 1; }
+    A.p_mask = slots - 1;
+    if (hipMemsetAsync(A.p_table, 0, (size_t)slots * 8, st) != hipSuccess) { *rc = -11; return 1; }
+    if (A.p_lines > 0) {
+        const unsigned pb = (unsigned)((A.p_lines + 255) / 256);
+        hipLaunchKernelGGL(kq_parse, dim3(pb), dim3(256), 0, st, A);
+        hipLaunchKernelGGL(kq_insert, dim3(pb), dim3(256), 0, st, A);
+        if (hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { *rc = -11; return 1; }
+        c->bed_stats.kernel_bytes += 3 * pn + A.p_lines * (8 + 16 + 8) * 2 + (int64_t)slots * 8;
+        if (h.decline != ~0ull) { (void)bs_decline(c, status, (int)(h.decline & 0xff), (long long)(h.decline >> 8)); return 1; }
+    }
+    return 0;
+}
+
+// The text is on the device (d_text[0, n), padded; copies enqueued on c->up_stream): everything behind that.  d_ptext: the
+// positions text of -p (pn bytes, padded), or null
+int bs_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *d_ptext, int64_t pn, const mc_bed_params *P, const char **out,
+           int64_t *n_out, int64_t *n_sites, int32_t *status) {
     mc_bed_stats &S = c->bed_stats;
     hipStream_t st = c->stream;
     HIP_TRY(hipStreamSynchronize(c->up_stream));
@@ -533,38 +670,38 @@ int bs_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const mc_bed_pa
     BsHead *d_head = nullptr, h = {};
     if (pool.get(&d_head, 1)) return -10;
     h.decline = ~0ull;
+    h.first_counted = ~0ull;
     HIP_TRY(hipMemcpyAsync(d_head, &h, sizeof h, hipMemcpyHostToDevice, st));
-    const int64_t n_tiles = (n + KP_TILE - 1) / KP_TILE;
-    long long *tile_cnt = nullptr, *tile_off = nullptr;
-    if (pool.get(&tile_cnt, (size_t)n_tiles) || pool.get(&tile_off, (size_t)n_tiles)) return -10;
-    hipLaunchKernelGGL(kp_count, dim3((unsigned)n_tiles), dim3(KP_THREADS), 0, st, d_text, n, tile_cnt);
-    hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)tile_cnt, n_tiles, tile_off, &d_head->kp.n_newlines);
-    HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const int64_t n_nl = h.kp.n_newlines;
-    if (n_nl + 1 >= ((int64_t)1 << 31) - 2) return bs_decline(c, status, MC_BED_DECLINE_ROWS, -1);
-    const int64_t cap_lines = n_nl + 2;
-    // per line: the start, the row, four 32-bit columns, the hash, the flags, the entry's five columns
-    if (!bs_fits((size_t)cap_lines * (8 + 16 + 4 * 4 + 8 + 1 + 4 * 4 + 8) + ((size_t)1 << 20))) return bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1);
     BsArgs A = {};
-    long long *line_start = nullptr;
-    if (pool.get(&line_start, (size_t)cap_lines)) return -10;
-    hipLaunchKernelGGL(kp_starts, dim3((unsigned)n_tiles), dim3(KP_THREADS), 0, st, d_text, n, (const long long *)tile_off, line_start,
-                       cap_lines, &d_head->kp);
-    // (the last line may lack its newline: the same count kp_starts makes; the last byte is not on the host, so it is asked for)
-    HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const int64_t n_lines = h.kp.n_lines;
-    S.n_lines = n_lines;
-    A.text = d_text; A.n_bytes = n; A.n_lines = n_lines; A.n_nl = n_nl; A.line_start = line_start; A.head = d_head;
-    A.min_depth = P->min_depth; A.thresh = P->mod_threshold; A.control = P->control; A.with_probs = P->with_probs; A.gff = P->gff;
+    A.head = d_head;
     A.hash_mask = ~0ull;
     if (const char *e = getenv("MCALLER_BED_HASH_MASK")) A.hash_mask = strtoull(e, nullptr, 16);
+    A.positions = d_ptext != nullptr;
+    A.stats = A.positions && !P->gff;
+    A.buckets = P->with_probs || A.stats;
+    if (A.positions) {
+        int rc = 0;
+        if (bs_position_set(c, pool, A, d_head, h, d_ptext, pn, status, &rc)) return rc;
+        h.kp = KpHead();                                      // (the line passes count from zero again)
+        HIP_TRY(hipMemcpyAsync(d_head, &h, sizeof h, hipMemcpyHostToDevice, st));
+    }
+    long long *line_start = nullptr;
+    int64_t n_nl = 0, n_lines = 0;
+    bool too_many = false;
+    if (int rc = bs_lines(pool, st, d_text, n, d_head, h, &line_start, &n_nl, &n_lines, &too_many)) return rc;
+    if (too_many) return bs_decline(c, status, n_nl + 1 >= ((int64_t)1 << 31) - 2 ? MC_BED_DECLINE_ROWS : MC_BED_DECLINE_MEMORY, -1);
+    // per line: the row, four 32-bit columns, the hash, the flags, the entry's five columns (-p: the value count, two numbers' digits)
+    if (!bs_fits((size_t)(n_nl + 2) * (16 + 4 * 4 + 8 + 1 + 4 * 4 + 8 + (A.stats ? 4 + 2 * 12 : 0)) + ((size_t)1 << 20)))
+        return bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1);
+    S.n_lines = n_lines;
+    A.text = d_text; A.n_bytes = n; A.n_lines = n_lines; A.n_nl = n_nl; A.line_start = line_start;
+    A.min_depth = P->min_depth; A.thresh = P->mod_threshold; A.control = P->control; A.with_probs = P->with_probs; A.gff = P->gff;
     const size_t nl = (size_t)n_lines;
     if (pool.get(&A.row, nl) || pool.get(&A.pos, nl) || pool.get(&A.pspan, nl) || pool.get(&A.row_ent, nl) || pool.get(&A.ent_boff, nl) ||
         pool.get(&A.hash, nl) || pool.get(&A.fl, nl) || pool.get(&A.ent_depth, nl) || pool.get(&A.ent_meth, nl) || pool.get(&A.ent_min, nl) ||
         pool.get(&A.ent_fill, nl) || pool.get(&A.ent_pbytes, nl))
         return -10;
+    if (A.stats && (pool.get(&A.nval, nl) || pool.get(&A.st_lo, 2 * nl) || pool.get(&A.st_meta, 2 * nl))) return -10;
     const unsigned lb = (unsigned)((n_lines + 255) / 256);
     A.nblk = lb;
     hipLaunchKernelGGL(kb_parse, dim3(lb), dim3(256), BS_STAGE + 16, st, A);
@@ -574,6 +711,13 @@ int bs_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const mc_bed_pa
     if (h.decline != ~0ull) return bs_decline(c, status, (int)(h.decline & 0xff), (long long)(h.decline >> 8));
     const int64_t n_counted = (int64_t)h.n_counted;
     S.n_counted = n_counted;
+    if (A.stats && n_counted > 0) {                           // every counted row has the first one's number of values, 2 .. 64
+        hipLaunchKernelGGL(kq_counts, dim3(lb), dim3(256), 0, st, A);
+        HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (h.decline != ~0ull) return bs_decline(c, status, (int)(h.decline & 0xff), (long long)(h.decline >> 8));
+        A.nv = h.nv;
+    }
     uint64_t slots = 16;
     while ((int64_t)slots < 2 * n_counted) slots <<= 1;
     if (const char *e = getenv("MCALLER_BED_TABLE_SLOTS")) {
@@ -582,7 +726,7 @@ int bs_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const mc_bed_pa
     }
     S.table_slots = (int64_t)slots;
     if ((int64_t)slots < 2 * n_counted) return bs_decline(c, status, MC_BED_DECLINE_TABLE, -1);
-    if (!bs_fits((size_t)slots * 8 + (size_t)3 * lb * 16 + (P->with_probs ? (size_t)n_counted * 8 : 0))) return bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1);
+    if (!bs_fits((size_t)slots * 8 + (size_t)3 * lb * 16 + (A.buckets ? (size_t)n_counted * 8 : 0))) return bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1);
     if (pool.get(&A.table, (size_t)slots) || pool.get(&A.blk_sum, (size_t)3 * lb) || pool.get(&A.blk_off, (size_t)3 * lb)) return -10;
     A.table_mask = slots - 1;
     HIP_TRY(hipMemsetAsync(A.table, 0, (size_t)slots * 8, st));
@@ -592,40 +736,67 @@ int bs_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const mc_bed_pa
     HIP_TRY(hipMemsetAsync(A.ent_min, 0xff, nl * 4, st));
     HIP_TRY(hipMemsetAsync(A.ent_pbytes, 0, nl * 8, st));
     hipLaunchKernelGGL(kb_group, dim3(lb), dim3(256), 0, st, A);
-    hipLaunchKernelGGL(kb_sums, dim3(lb), dim3(256), 0, st, A);
-    hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)A.blk_sum, (int64_t)lb, A.blk_off, &d_head->tot_bucket);
-    hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)(A.blk_sum + lb), (int64_t)lb, A.blk_off + lb, &d_head->tot_sel);
-    hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)(A.blk_sum + 2 * (size_t)lb), (int64_t)lb, A.blk_off + 2 * (size_t)lb,
-                       &d_head->tot_bytes);
-    HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    // the three scans over the lines: bucket places, selected entries, bytes of text (-p with statistics: once more when they are made)
+    auto size_entries = [&]() -> int {
+        hipLaunchKernelGGL(kb_sums, dim3(lb), dim3(256), 0, st, A);
+        hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)A.blk_sum, (int64_t)lb, A.blk_off, &d_head->tot_bucket);
+        hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)(A.blk_sum + lb), (int64_t)lb, A.blk_off + lb, &d_head->tot_sel);
+        hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)(A.blk_sum + 2 * (size_t)lb), (int64_t)lb, A.blk_off + 2 * (size_t)lb,
+                           &d_head->tot_bytes);
+        HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return 0;
+    };
+    if (int rc = size_entries()) return rc;
     S.kernel_bytes += (int64_t)slots * 8 + n_lines * 5 * 8 + n_counted * (16 + 8 + 5 * 4 + 60) + 2 * n_lines * (1 + 4 + 3 * 4);
     S.longest_probe = h.longest_probe;
     if (h.decline != ~0ull) return bs_decline(c, status, (int)(h.decline & 0xff), (long long)(h.decline >> 8));
     S.n_entries = (int64_t)h.n_entries;
-    const int64_t n_sel = h.tot_sel, n_outb = h.tot_bytes;
+    const int64_t n_sel = h.tot_sel;
+    int64_t n_outb = h.tot_bytes;
     S.n_sites = n_sel;
-    S.n_out_bytes = n_outb;
     *n_sites = n_sel;
     if (n_sel > 0) {
-        if (!bs_fits((size_t)n_sel * 32 + (size_t)n_outb)) return bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1);
+        if (!bs_fits((size_t)n_sel * 32 + (size_t)n_outb + (A.stats ? (size_t)n_counted * A.nv * 8 + (size_t)n_sel * A.nv * 24 : 0)))
+            return bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1);
         if (pool.get(&A.sel_line, (size_t)n_sel) || pool.get(&A.large, (size_t)n_sel) || pool.get(&A.sel_off, (size_t)n_sel) ||
-            pool.get(&A.sel_vo_at, (size_t)n_sel) || pool.get(&A.out, (size_t)n_outb))
+            pool.get(&A.sel_vo_at, (size_t)n_sel))
             return -10;
-        if (P->with_probs && (pool.get(&A.bucket, (size_t)n_counted) || pool.get(&A.bucket_tmp, (size_t)n_counted))) return -10;
+        if (A.buckets && (pool.get(&A.bucket, (size_t)n_counted) || pool.get(&A.bucket_tmp, (size_t)n_counted))) return -10;
         const unsigned sb = (unsigned)((n_sel + 255) / 256);
         hipLaunchKernelGGL(kb_apply, dim3(lb), dim3(256), 0, st, A);
-        if (P->with_probs) {
+        if (A.buckets) {
             hipLaunchKernelGGL(kb_place, dim3(lb), dim3(256), 0, st, A);
             hipLaunchKernelGGL(kb_sort_small, dim3(sb), dim3(256), 0, st, A, n_sel);
             hipLaunchKernelGGL(kb_sort_large, dim3((unsigned)std::min<int64_t>(n_sel, 1024)), dim3(256), 0, st, A, n_lines <= 65536 ? 2 : 4);
         }
+        if (A.stats) {
+            const int64_t n_num = n_counted * A.nv, n_mom = n_sel * (A.nv - 1);
+            if (pool.get(&A.X, (size_t)n_num) || pool.get(&A.mom, (size_t)n_mom * 3)) return -10;
+            hipLaunchKernelGGL(kq_features, dim3((unsigned)((n_num + 255) / 256)), dim3(256), 0, st, A, n_num);
+            HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));      // (a value that is no number: named before the moments run on it)
+            HIP_TRY(hipStreamSynchronize(st));
+            if (h.decline != ~0ull) return bs_decline(c, status, (int)(h.decline & 0xff), (long long)(h.decline >> 8));
+            hipLaunchKernelGGL(kq_moments_small, dim3((unsigned)((n_mom + 255) / 256)), dim3(256), 0, st, A, n_sel);
+            hipLaunchKernelGGL(kq_moments_large, dim3((unsigned)std::min<int64_t>((n_mom + 3) / 4, 4096)), dim3(256), 0, st, A);
+            hipLaunchKernelGGL(kq_finish, dim3(sb), dim3(256), 0, st, A, n_sel);
+            HIP_TRY(hipGetLastError());
+            A.stats_ready = 1;                                // the rows' sizes with the two columns, and their places
+            if (int rc = size_entries()) return rc;
+            S.kernel_bytes += n_counted * 60 + 3 * n_num * 8 + 2 * n_mom * 24 + n_lines * (1 + 4 + 3 * 4);
+            if (h.decline != ~0ull) return bs_decline(c, status, (int)(h.decline & 0xff), (long long)(h.decline >> 8));
+            n_outb = h.tot_bytes;
+            if (!bs_fits((size_t)n_outb)) return bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1);
+            hipLaunchKernelGGL(kb_apply, dim3(lb), dim3(256), 0, st, A);
+        }
+        if (pool.get(&A.out, (size_t)n_outb)) return -10;
         hipLaunchKernelGGL(kb_write, dim3(sb), dim3(256), 0, st, A, n_sel);
         if (P->with_probs) hipLaunchKernelGGL(kb_write_vo, dim3((unsigned)((n_sel + 3) / 4)), dim3(256), 0, st, A, n_sel);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(st));
-        S.kernel_bytes += n_lines * (1 + 4 + 3 * 4) + 2 * n_outb + (P->with_probs ? n_counted * 24 : 0);
+        S.kernel_bytes += n_lines * (1 + 4 + 3 * 4) + 2 * n_outb + (A.buckets ? n_counted * 24 : 0);
     }
+    S.n_out_bytes = n_outb;
     S.ms_kernels = bs_ms_since(t_kernels);
     const auto t_d2h = std::chrono::steady_clock::now();
     if (n_outb > 0) {
@@ -643,7 +814,7 @@ int bs_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const mc_bed_pa
     return 0;
 }
 
-// what both entry points begin with -> 0: go on; 1: done (declined, *status set)
+// what every entry point begins with -> 0: go on; 1: done (declined, *status set)
 int bs_begin(mc_ctx *c, const mc_bed_params *P, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status, int64_t n) {
     c->bed_stats = mc_bed_stats();
     c->bed_stats.decline_line = -1;
@@ -654,49 +825,18 @@ int bs_begin(mc_ctx *c, const mc_bed_params *P, const char **out, int64_t *n_out
     return 0;
 }
 
-}  // namespace
-
-extern "C" int mc_bed_summarise_text(mc_ctx *c, const char *text, int64_t n_bytes, const mc_bed_params *P, const char **out, int64_t *n_out,
-                                     int64_t *n_sites, int32_t *status) {
-    if (!c || !P || !out || !n_out || !n_sites || !status || n_bytes < 0 || (n_bytes > 0 && !text)) {
-        mc_set_error("mc_bed_summarise_text: bad arguments");
-        return -12;
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    if (bs_begin(c, P, out, n_out, n_sites, status, n_bytes)) return 0;
-    Pool pool("bed summary");
-    char *d_text = nullptr;
-    if (pool.get(&d_text, (size_t)n_bytes + 64)) return -10;
-    if (n_bytes > 0) HIP_TRY(hipMemcpyAsync(d_text, text, (size_t)n_bytes, hipMemcpyHostToDevice, c->up_stream));
-    HIP_TRY(hipMemsetAsync(d_text + n_bytes, 0, 64, c->up_stream));
+// a host text onto the device, padded with 64 zero bytes (enqueued on c->up_stream and waited for)
+int bs_upload_text(mc_ctx *c, Pool &pool, const char *text, int64_t n, char **d_text) {
+    if (pool.get(d_text, (size_t)n + 64)) return -10;
+    if (n > 0) HIP_TRY(hipMemcpyAsync(*d_text, text, (size_t)n, hipMemcpyHostToDevice, c->up_stream));
+    HIP_TRY(hipMemsetAsync(*d_text + n, 0, 64, c->up_stream));
     HIP_TRY(hipStreamSynchronize(c->up_stream));
-    c->bed_stats.ms_h2d = bs_ms_since(t0);
-    const int rc = bs_run(c, pool, d_text, n_bytes, P, out, n_out, n_sites, status);
-    (void)hipStreamSynchronize(c->stream);                   // (an early return: nothing of the pool is in use when it goes)
-    c->bed_stats.ms_total = bs_ms_since(t0);
-    return rc;
+    return 0;
 }
 
-extern "C" int mc_bed_summarise_file(mc_ctx *c, const char *path, const mc_bed_params *P, const char **out, int64_t *n_out, int64_t *n_sites,
-                                     int32_t *status) {
-    if (!c || !path || !P || !out || !n_out || !n_sites || !status) {
-        mc_set_error("mc_bed_summarise_file: bad arguments");
-        return -12;
-    }
-    struct stat sb;
-    if (stat(path, &sb) != 0 || !S_ISREG(sb.st_mode)) {
-        mc_set_error("mc_bed_summarise_file: %s is not a readable file", path);
-        return -1;
-    }
-    const int64_t n = (int64_t)sb.st_size;
-    HIP_TRY(hipSetDevice(c->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    if (bs_begin(c, P, out, n_out, n_sites, status, n)) return 0;
-    Pool pool("bed summary");
-    char *d_text = nullptr;
-    if (pool.get(&d_text, (size_t)n + 64)) return -10;
-    // the file in blocks, two pinned stages in turn: block i is read while block i - 1 is on its way
+// a file of n bytes onto the device, padded: in blocks, two pinned stages in turn -- block i is read while block i - 1 is on its way
+int bs_upload_file(mc_ctx *c, Pool &pool, const char *path, int64_t n, char **d_text, double *ms_read) {
+    if (pool.get(d_text, (size_t)n + 64)) return -10;
     const size_t block = (size_t)std::min<int64_t>(std::max<int64_t>(n, 4096), (int64_t)64 << 20);
     if (c->bed_stage_cap < block) {
         c->bed_stage_cap = 0;
@@ -707,27 +847,147 @@ extern "C" int mc_bed_summarise_file(mc_ctx *c, const char *path, const mc_bed_p
     for (Event &e : c->bed_ev)
         if (!e.e)
             if (int rc = e.create()) return rc;
-    double ms_read = 0;
     int rc = 0, turn = 0;
     for (int64_t lo = 0; lo < n && rc == 0; lo += (int64_t)c->bed_stage_cap, turn ^= 1) {
         const int64_t hi = std::min<int64_t>(n, lo + (int64_t)c->bed_stage_cap);
         if (lo >= 2 * (int64_t)c->bed_stage_cap) HIP_TRY(hipEventSynchronize(c->bed_ev[turn]));     // the copy out of this stage is done
         const auto tr = std::chrono::steady_clock::now();
         rc = mc_read_file_range(path, lo, hi, c->bed_stage[turn].get<char>(), 0);
-        ms_read += bs_ms_since(tr);
+        *ms_read += bs_ms_since(tr);
         if (rc) break;
-        HIP_TRY(hipMemcpyAsync(d_text + lo, c->bed_stage[turn].p, (size_t)(hi - lo), hipMemcpyHostToDevice, c->up_stream));
+        HIP_TRY(hipMemcpyAsync(*d_text + lo, c->bed_stage[turn].p, (size_t)(hi - lo), hipMemcpyHostToDevice, c->up_stream));
         HIP_TRY(hipEventRecord(c->bed_ev[turn], c->up_stream));
     }
-    HIP_TRY(hipMemsetAsync(d_text + n, 0, 64, c->up_stream));
+    HIP_TRY(hipMemsetAsync(*d_text + n, 0, 64, c->up_stream));
     HIP_TRY(hipStreamSynchronize(c->up_stream));
-    if (rc) return rc;
+    return rc;
+}
+
+int bs_file_size(const char *what, const char *path, int64_t *n) {
+    struct stat sb;
+    if (stat(path, &sb) != 0 || !S_ISREG(sb.st_mode)) {
+        mc_set_error("%s: %s is not a readable file", what, path);
+        return -1;
+    }
+    *n = (int64_t)sb.st_size;
+    return 0;
+}
+
+// texts: positions == null -> no -p
+int bs_text(mc_ctx *c, const char *text, int64_t n_bytes, const char *positions, int64_t pn, const mc_bed_params *P, const char **out,
+            int64_t *n_out, int64_t *n_sites, int32_t *status) {
+    HIP_TRY(hipSetDevice(c->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    if (bs_begin(c, P, out, n_out, n_sites, status, n_bytes + pn)) return 0;
+    c->bed_stats.n_bytes = n_bytes;
+    Pool pool("bed summary");
+    char *d_text = nullptr, *d_ptext = nullptr;
+    if (int rc = bs_upload_text(c, pool, text, n_bytes, &d_text)) return rc;
+    if (positions)
+        if (int rc = bs_upload_text(c, pool, positions, pn, &d_ptext)) return rc;
+    c->bed_stats.ms_h2d = bs_ms_since(t0);
+    const int rc = bs_run(c, pool, d_text, n_bytes, d_ptext, pn, P, out, n_out, n_sites, status);
+    (void)hipStreamSynchronize(c->stream);                   // (an early return: nothing of the pool is in use when it goes)
+    c->bed_stats.ms_total = bs_ms_since(t0);
+    return rc;
+}
+
+int bs_file(mc_ctx *c, const char *what, const char *path, const char *positions_path, const mc_bed_params *P, const char **out, int64_t *n_out,
+            int64_t *n_sites, int32_t *status) {
+    int64_t n = 0, pn = 0;
+    if (int rc = bs_file_size(what, path, &n)) return rc;
+    if (positions_path)
+        if (int rc = bs_file_size(what, positions_path, &pn)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    if (bs_begin(c, P, out, n_out, n_sites, status, n + pn)) return 0;
+    c->bed_stats.n_bytes = n;
+    Pool pool("bed summary");
+    char *d_text = nullptr, *d_ptext = nullptr;
+    double ms_read = 0;
+    if (int rc = bs_upload_file(c, pool, path, n, &d_text, &ms_read)) return rc;
+    if (positions_path)
+        if (int rc = bs_upload_file(c, pool, positions_path, pn, &d_ptext, &ms_read)) return rc;
     c->bed_stats.ms_read = ms_read;
     c->bed_stats.ms_h2d = bs_ms_since(t0) - ms_read;         // what the copies added behind the reads they ran beside
-    rc = bs_run(c, pool, d_text, n, P, out, n_out, n_sites, status);
+    const int rc = bs_run(c, pool, d_text, n, d_ptext, pn, P, out, n_out, n_sites, status);
     (void)hipStreamSynchronize(c->stream);
     c->bed_stats.ms_total = bs_ms_since(t0);
     return rc;
+}
+
+// the probe of mc_tstat.h's device build: a lane per triple
+__global__ __launch_bounds__(256) void k_ts_probe(const double *__restrict__ n, const double *__restrict__ mean, const double *__restrict__ var,
+                                                  int64_t count, double *__restrict__ t, double *__restrict__ l, int32_t *__restrict__ status) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    double tv, lv;
+    status[i] = ts_stat(n[i], mean[i], var[i], &tv, &lv);
+    t[i] = tv; l[i] = lv;
+}
+
+}  // namespace
+
+extern "C" int mc_bed_summarise_text(mc_ctx *c, const char *text, int64_t n_bytes, const mc_bed_params *P, const char **out, int64_t *n_out,
+                                     int64_t *n_sites, int32_t *status) {
+    if (!c || !P || !out || !n_out || !n_sites || !status || n_bytes < 0 || (n_bytes > 0 && !text)) {
+        mc_set_error("mc_bed_summarise_text: bad arguments");
+        return -12;
+    }
+    return bs_text(c, text, n_bytes, nullptr, 0, P, out, n_out, n_sites, status);
+}
+
+extern "C" int mc_bed_summarise_file(mc_ctx *c, const char *path, const mc_bed_params *P, const char **out, int64_t *n_out, int64_t *n_sites,
+                                     int32_t *status) {
+    if (!c || !path || !P || !out || !n_out || !n_sites || !status) {
+        mc_set_error("mc_bed_summarise_file: bad arguments");
+        return -12;
+    }
+    return bs_file(c, "mc_bed_summarise_file", path, nullptr, P, out, n_out, n_sites, status);
+}
+
+extern "C" int mc_bed_positions_text(mc_ctx *c, const char *text, int64_t n_bytes, const char *positions, int64_t pn, const mc_bed_params *P,
+                                     const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status) {
+    if (!c || !P || !out || !n_out || !n_sites || !status || n_bytes < 0 || (n_bytes > 0 && !text) || pn < 0 || !positions) {
+        mc_set_error("mc_bed_positions_text: bad arguments");
+        return -12;
+    }
+    return bs_text(c, text, n_bytes, positions, pn, P, out, n_out, n_sites, status);
+}
+
+extern "C" int mc_bed_positions_file(mc_ctx *c, const char *path, const char *positions_path, const mc_bed_params *P, const char **out,
+                                     int64_t *n_out, int64_t *n_sites, int32_t *status) {
+    if (!c || !path || !positions_path || !P || !out || !n_out || !n_sites || !status) {
+        mc_set_error("mc_bed_positions_file: bad arguments");
+        return -12;
+    }
+    return bs_file(c, "mc_bed_positions_file", path, positions_path, P, out, n_out, n_sites, status);
+}
+
+extern "C" int mc_tstat_device(mc_ctx *c, const double *n, const double *mean, const double *var, int64_t count, double *t, double *log10_p,
+                               int32_t *status) {
+    if (!c || count < 0 || (count > 0 && (!n || !mean || !var || !t || !log10_p || !status))) {
+        mc_set_error("mc_tstat_device: bad arguments");
+        return -12;
+    }
+    if (count == 0) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    Pool pool("t statistic probe");
+    double *d_in = nullptr, *d_out = nullptr;
+    int32_t *d_st = nullptr;
+    if (pool.get(&d_in, (size_t)count * 3) || pool.get(&d_out, (size_t)count * 2) || pool.get(&d_st, (size_t)count)) return -10;
+    hipStream_t st = c->stream;
+    HIP_TRY(hipMemcpyAsync(d_in, n, (size_t)count * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_in + count, mean, (size_t)count * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_in + 2 * count, var, (size_t)count * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_ts_probe, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, (const double *)d_in, (const double *)(d_in + count),
+                       (const double *)(d_in + 2 * count), count, d_out, d_out + count, d_st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(t, d_out, (size_t)count * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(log10_p, d_out + count, (size_t)count * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(status, d_st, (size_t)count * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
 }
 
 extern "C" int mc_bed_last_stats(mc_ctx *c, mc_bed_stats *out) {

@@ -10,6 +10,7 @@
 #include "mc_decimal.h"
 #include "mc_sortkey.h"
 #include "mc_rowtext.h"
+#include "mc_tstat.h"
 #include "../../include/mcaller_hip.h"
 
 #include <algorithm>
@@ -615,6 +616,32 @@ extern "C" int mc_repr_double(double v, char *out32) {
 extern "C" int mc_parse_double(const char *s, int32_t n, double *out) {
     if (!s || !out || n < 0) return 0;
     return dc_parse(s, n, out);
+}
+
+// the Student t arithmetic of make_bed -p by mc_tstat.h's host build (include/mcaller_hip.h)
+extern "C" int mc_tstat(double n, double mean, double var, double *t, double *log10_p) {
+    if (!t || !log10_p) return -12;
+    return ts_stat(n, mean, var, t, log10_p);
+}
+extern "C" double mc_tstat_round3(double v) { return ts_round3(v); }
+extern "C" int mc_tstat_tie(double v, double err) { return ts_tie(v, err) ? 1 : 0; }
+// an entry's two values from its rows, the way the kernels of bed/mc_bedpos.inc make them: per column the compensated sum, the mean,
+// the compensated centred sum of squares, then TsSite
+extern "C" int mc_tstat_site(const double *X, int64_t n_rows, int32_t n_cols, double *out2) {
+    if (!X || !out2 || n_rows < 1 || n_cols < 2) return -12;
+    TsSite site;
+    if (n_rows < 2) site.flags = TS_BAD_N;
+    for (int32_t j = 0; j + 1 < n_cols && n_rows >= 2; ++j) {
+        TsSum sum, sq;
+        double sum_abs = 0.0;
+        for (int64_t i = 0; i < n_rows; ++i) { sum.add(X[i * n_cols + j]); sum_abs += fabs(X[i * n_cols + j]); }
+        const double mean = sum.value() / (double)n_rows;
+        for (int64_t i = 0; i < n_rows; ++i) { const double d = X[i * n_cols + j] - mean; sq.add(d * d); }
+        site.column((double)n_rows, mean, sq.value(), sum_abs);
+    }
+    int flags = site.finish(&out2[0], &out2[1]);
+    if (n_rows >= 2 && (!rt_num_of(out2[0]).ok || !rt_num_of(out2[1]).ok)) flags |= 64;      // (a value mc_rowtext.h does not print)
+    return flags;
 }
 
 // the numeric key of `sort -n -k2` for the line s[0, n) by mc_sortkey.h's host build -> 0: (*hi, *lo) hold it; 1: beyond the digit limits

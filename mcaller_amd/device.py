@@ -628,15 +628,27 @@ class Device(object):
 
     # ---- the per-site summary of a .diffs file (csrc/bed/mc_bedsum.hip) ----
     @_serialized
-    def bed_summarise(self, path=None, text=None, min_depth=15, mod_threshold=0.5, control=False, with_probs=False, gff=False):
-        """The bytes make_bed writes for a `.diffs.<k>` file (`path`) or its text (`text`, bytes), made on the GPU.
+    def bed_summarise(self, path=None, text=None, min_depth=15, mod_threshold=0.5, control=False, with_probs=False, gff=False,
+                      positions_path=None, positions_text=None):
+        """The bytes make_bed writes for a `.diffs.<k>` file (`path`) or its text (`text`, bytes), made on the GPU; with
+        `positions_path` (beside `path`) or `positions_text` (beside `text`) what make_bed -p writes: the rows at the listed
+        positions, every entry, two t-test columns in a BED row.
         -> (bytes, number of sites, None), or (None, 0, reason) when the device declines: the caller runs the host code."""
         if (path is None) == (text is None):
             raise ValueError('bed_summarise: a path or a text')
+        if (positions_path is not None and path is None) or (positions_text is not None and text is None):
+            raise ValueError('bed_summarise: positions_path goes with path, positions_text with text')
         d = int(min_depth)
         prm = _lib.BedParams(max(-2 ** 62, min(2 ** 62, d)), float(mod_threshold), int(bool(control)), int(bool(with_probs)), int(bool(gff)), 0)
         out, n_out, n_sites, status = C.c_void_p(), C.c_int64(), C.c_int64(), C.c_int32()
-        if path is not None:
+        if positions_path is not None:
+            check(lib().mc_bed_positions_file(self._ctx, os.fsencode(path), os.fsencode(positions_path), C.byref(prm), C.byref(out),
+                                              C.byref(n_out), C.byref(n_sites), C.byref(status)))
+        elif positions_text is not None:
+            text, positions_text = bytes(text), bytes(positions_text)
+            check(lib().mc_bed_positions_text(self._ctx, text, len(text), positions_text, len(positions_text), C.byref(prm), C.byref(out),
+                                              C.byref(n_out), C.byref(n_sites), C.byref(status)))
+        elif path is not None:
             check(lib().mc_bed_summarise_file(self._ctx, os.fsencode(path), C.byref(prm), C.byref(out), C.byref(n_out), C.byref(n_sites),
                                               C.byref(status)))
         else:
@@ -709,6 +721,17 @@ class Device(object):
         ok = np.zeros(len(tokens), dtype=np.uint8)
         check(lib().mc_parse_doubles_device(self._ctx, text, len(text), _ptr(off), _ptr(length), len(tokens), _ptr(out), _ptr(ok)))
         return out, ok.astype(bool)
+
+    @_serialized
+    def tstat(self, n, mean, var):
+        """t and log10 p of one-sample t-tests from (rows, mean, sample variance) triples by mc_tstat.h's device build, a lane
+        per triple (mc_tstat_device, tests) -> (status bits int32 [k], t float64 [k], log10 p float64 [k])."""
+        n, mean, var = (np.ascontiguousarray(a, dtype=np.float64) for a in (n, mean, var))
+        if not (n.ndim == 1 and n.shape == mean.shape == var.shape):
+            raise ValueError('tstat: three arrays of one length')
+        t, l, st = np.zeros(len(n)), np.zeros(len(n)), np.zeros(len(n), dtype=np.int32)
+        check(lib().mc_tstat_device(self._ctx, _ptr(n), _ptr(mean), _ptr(var), len(n), _ptr(t), _ptr(l), _ptr(st)))
+        return st, t, l
 
     @_serialized
     def training_rows(self, path=None, text=None, pairs=()):
