@@ -614,6 +614,16 @@ typedef struct mc_bed_stats {
 #define MC_BED_DECLINE_PRINT_RANGE   22  /* a rounded value mc_rowtext.h does not print (|v| >= 1e9)                   */
 #define MC_BED_DECLINE_ROUNDING_TIE  23  /* a value within its error bound of a rounding tie of np.round(., 3)         */
 #define MC_BED_DECLINE_DEPTH         24  /* an entry of more than 100001 rows (the tail function's error is measured up to there) */
+/* ... through mc_bed_annotate_*: 25-27 with --gff --vo (25 names a row, 26-27 an entry's first row); 28-30 name a line of the FASTA,
+ * 31-32 an entry's first row */
+#define MC_BED_DECLINE_PROBABILITY   25  /* a row of a written entry with a probability mc_decimal.h declines           */
+#define MC_BED_DECLINE_STAT_RANGE    26  /* a fracLow / fracUp mc_rowtext.h does not print (0.0 and nan are printed)     */
+#define MC_BED_DECLINE_QV_RANGE      27  /* |100 * mean| >= 2^53                                                        */
+#define MC_BED_DECLINE_REF_HIGH_BYTE 28  /* FASTA: a byte >= 0x80                                                       */
+#define MC_BED_DECLINE_REF_CONTROL   29  /* FASTA: a control byte other than tab and newline ('\r' too)                 */
+#define MC_BED_DECLINE_REF_SEQ_BYTE  30  /* FASTA: a sequence line with a byte that is not a letter (the host strips blanks) */
+#define MC_BED_DECLINE_REF_LETTER    31  /* an entry on '-' with a letter outside ACGTNM in its window (the host's KeyError) */
+#define MC_BED_DECLINE_REF_CONTIG    32  /* a written entry whose contig the FASTA lacks (the host's KeyError)           */
 #define MC_BED_MAX_VALUES 64
 int mc_bed_summarise_text(mc_ctx *ctx, const char *text, int64_t n_bytes, const mc_bed_params *prm, const char **out,
                           int64_t *n_out, int64_t *n_sites, int32_t *status);
@@ -636,6 +646,34 @@ int mc_bed_positions_text(mc_ctx *ctx, const char *text, int64_t n_bytes, const 
                           const mc_bed_params *prm, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status);
 int mc_bed_positions_file(mc_ctx *ctx, const char *path, const char *positions_path, const mc_bed_params *prm, const char **out,
                           int64_t *n_out, int64_t *n_sites, int32_t *status);
+
+/* ... with make_bed --gff --vo and --ref (make_bed.py:36-48,:146-149).  positions / positions_path and fasta / fasta_path may be
+ * null: without them and without gff && with_probs the calls are mc_bed_summarise_*.  gff && with_probs: every written entry
+ * carries ";fracLow=..;fracUp=..;identificationQv=.." from the probabilities of its rows in row order, in NumPy's own order of
+ * additions (mcaller_amd/csrc/mc_npsum.h): the host's bits, no bound.  A FASTA: an entry's context in the GFF attributes is
+ * the 41 bases around its position (Python's slice rule; upper-cased; complemented and reversed on '-'), a BED row keeps its own.
+ * Declines on top of the above: MC_BED_DECLINE_* 25-32; a FASTA that does not fit beside the rest is MC_BED_DECLINE_MEMORY. */
+int mc_bed_annotate_text(mc_ctx *ctx, const char *text, int64_t n_bytes, const char *positions, int64_t n_positions_bytes,
+                         const char *fasta, int64_t n_fasta_bytes, const mc_bed_params *prm, const char **out, int64_t *n_out,
+                         int64_t *n_sites, int32_t *status);
+int mc_bed_annotate_file(mc_ctx *ctx, const char *path, const char *positions_path, const char *fasta_path,
+                         const mc_bed_params *prm, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status);
+
+/* ===== NumPy's summation order for make_bed --gff --vo (mcaller_amd/csrc/mc_npsum.h: one header for the host and the device) =====
+ * p[0, n): an entry's probabilities in row order.  mc_gff_site_moments: out3 = {np.mean(p), np.var(p, ddof=1),
+ * np.std(p, ddof=1) / np.sqrt(n)}, bit for bit.  mc_gff_site_stats: out3 = {frac - 2 se, frac + 2 se, 100 * mean}.  Both return
+ * status bits: 1 fracLow / fracUp are nan (n = 1; printed), 2 a value the device does not print, 4 |100 * mean| >= 2^53, 8 the
+ * workgroup's tree of additions differs from NumPy's recursion (never), 16 n < 1.  mc_gff_site_text: the attribute text the
+ * kernels write, into buf -> its length (-1 - status bits: the device declines).  mc_gff_site_stats_device: the device build
+ * on `count` arrays, one behind the other in p (off[count + 1]); out6 per array = {fracLow, fracUp, 100 * mean, mean, var, se}.
+ * mc_npsum_se / mc_npsum_se_device: sqrt(var) / sqrt(n), both square roots correctly rounded. */
+int mc_gff_site_moments(const double *p, int64_t n, double out3[3]);
+int mc_gff_site_stats(const double *p, int64_t n, double frac, double out3[3]);
+int mc_gff_site_text(const double *p, int64_t n, double frac, char *buf, int32_t cap);
+int mc_gff_site_stats_device(mc_ctx *ctx, const double *p, const int64_t *off, const double *frac, int64_t count, double *out6,
+                             int32_t *status);
+double mc_npsum_se(double var, double n);
+int mc_npsum_se_device(mc_ctx *ctx, const double *var, const double *n, int64_t count, double *se);
 
 /* ===== the Student t arithmetic of make_bed -p (mcaller_amd/csrc/mc_tstat.h: one header for the host and the device) =====
  * mc_tstat: the host build on one triple (n rows, their mean, their sample variance with ddof = 1) -> status bits

@@ -271,6 +271,17 @@ def lib():
                                             C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
         L.mc_bed_positions_file.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(BedParams), C.POINTER(C.c_void_p),
                                             C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        L.mc_bed_annotate_text.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, C.POINTER(BedParams),
+                                           C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        L.mc_bed_annotate_file.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(BedParams), C.POINTER(C.c_void_p),
+                                           C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        L.mc_gff_site_moments.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+        L.mc_gff_site_stats.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_void_p]
+        L.mc_gff_site_text.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_char_p, C.c_int32]
+        L.mc_gff_site_stats_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.mc_npsum_se.argtypes = [C.c_double, C.c_double]
+        L.mc_npsum_se.restype = C.c_double
+        L.mc_npsum_se_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         L.mc_tstat.argtypes = [C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.mc_tstat_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mc_tstat_round3.argtypes = [C.c_double]
@@ -669,6 +680,36 @@ def tstat(n, mean, var):
     t, l = C.c_double(), C.c_double()
     st = lib().mc_tstat(float(n), float(mean), float(var), C.byref(t), C.byref(l))
     return st, t.value, l.value
+
+
+def gff_site_moments(p):
+    """(status bits, np.mean(p), np.var(p, ddof=1), np.std(p, ddof=1) / np.sqrt(len(p))) by mc_npsum.h's host build: NumPy's own
+    order of additions (mc_gff_site_moments)."""
+    p = np.ascontiguousarray(p, dtype=np.float64)
+    out = np.zeros(3)
+    st = lib().mc_gff_site_moments(p.ctypes.data, len(p), out.ctypes.data)
+    return st, out[0], out[1], out[2]
+
+
+def gff_site_stats(p, frac):
+    """(status bits, fracLow, fracUp, 100 * mean) of make_bed --gff --vo by mc_npsum.h's host build (mc_gff_site_stats)."""
+    p = np.ascontiguousarray(p, dtype=np.float64)
+    out = np.zeros(3)
+    st = lib().mc_gff_site_stats(p.ctypes.data, len(p), float(frac), out.ctypes.data)
+    return st, out[0], out[1], out[2]
+
+
+def gff_site_text(p, frac):
+    """';fracLow=..;fracUp=..;identificationQv=..' as the kernels print it (mc_gff_site_text), or None where the device declines."""
+    p = np.ascontiguousarray(p, dtype=np.float64)
+    buf = C.create_string_buffer(160)
+    n = lib().mc_gff_site_text(p.ctypes.data, len(p), float(frac), buf, 160)
+    return buf.raw[:n].decode('ascii') if n >= 0 else None
+
+
+def npsum_se(var, n):
+    """sqrt(var) / sqrt(n) with mc_npsum.h's correctly rounded square root (host build)."""
+    return lib().mc_npsum_se(float(var), float(n))
 
 
 def tstat_round3(v):

@@ -1,6 +1,7 @@
 // mc_bedsum.hip -- the per-site summary of a `.diffs.<k>` file on the GPU: what make_bed.py:67-164 writes for BED, BED --control,
-// BED --vo and GFF, and with a positions file for -p (C ABI: mc_bed_summarise_text / _file, mc_bed_positions_text / _file,
-// mc_bed_last_stats, mc_bed_release; Python: Device.bed_summarise, make_bed.summarise_diffs_device).  The unit stands in csrc/bed/,
+// BED --vo and GFF, with a positions file for -p, and through mc_bed_annotate_* for --gff --vo and --ref (C ABI: mc_bed_summarise_text /
+// _file, mc_bed_positions_text / _file, mc_bed_annotate_text / _file, mc_bed_last_stats, mc_bed_release; Python: Device.bed_summarise,
+// make_bed.summarise_diffs_device).  The unit stands in csrc/bed/,
 // beside the units of the passes, not among them: no pass runs
 // its kernels, and the benchmark's kernel hash (bench.KERNEL_SOURCES) names the files of the pass path one by one.
 //
@@ -16,7 +17,7 @@
 //   * a table with fewer than 2 x the counted rows' slots (only MCALLER_BED_TABLE_SLOTS makes one)
 //   * a text that does not fit into free device memory beside its tables: the WHOLE text stays resident, entries are compared
 //     against the bytes of a representative row and the output copies its fields from there
-//   * --gff with --vo, --ref: not attempted (the caller does not ask)
+//   * --gff with --vo through mc_bed_summarise_* / mc_bed_positions_*: not attempted (mc_bed_annotate_* makes it, below)
 //
 // make_bed -p (mc_bed_positions_text / _file; Device.bed_summarise(positions_path= / positions_text=), make_bed.summarise_diffs_device(
 // positions=); from the command line with MCALLER_BED_POSITIONS_DEVICE=1): a positions file beside the rows.  A row counts when its
@@ -45,6 +46,30 @@
 //   kq_finish     a lane per entry: t, log10 p, their bounds, the maximum and the sum, np.round(., 3), the tie test, the digits
 //   kb_sums / kb_apply again (the rows' sizes with the two columns), kb_write
 //
+// make_bed --gff --vo and --ref (mc_bed_annotate_text / _file; Device.bed_summarise(site_stats=, ref_path= / ref_text=),
+// make_bed.summarise_diffs_device(ref=); from the command line with MCALLER_BED_GFF_DEVICE=1, with -p both knobs).  --gff --vo: every
+// written entry carries ";fracLow=..;fracUp=..;identificationQv=.." -- frac -+ 2 np.std(p, ddof=1) / np.sqrt(n) and int(100 np.mean(p))
+// of its probabilities in row order, every fp64 operation with NumPy's two operands (mc_npsum.h: the pairwise order of np.add.reduce,
+// a square root rounded in integers), so the values are the host's bits and nothing is bounded.  --ref: the FASTA text beside the
+// rows; an entry's context in the GFF attributes is seq[p - 20 : p + 21] of its contig, upper-cased, on '-' complemented and
+// reversed (a BED row keeps its own).  More declines:
+//   * a row of a written entry with a probability mc_decimal.h declines (nan, inf, more than 19 digits, an exponent out of range)
+//   * a fracLow / fracUp mc_rowtext.h does not print (0.0 and nan are printed); |100 * mean| >= 2^53
+//   * FASTA: a byte >= 0x80; a control byte other than tab and newline ('\r' too); a sequence line of a record with a byte that is
+//     no letter (the host strips blanks and keeps the rest: left to it); a text that does not fit beside the rest
+//   * an entry on '-' whose window holds a letter outside ACGTNM (written or not: the host's KeyError); a written entry whose contig
+//     the FASTA lacks (the host's KeyError, with and without --gff)
+// Its steps (mc_gffstats.inc, mc_fastactx.inc; each file's head says more):
+//   kf_lines / kp_scan x 2 / kf_pack / kf_ids   the FASTA: titles, ids and their hashes, the sequences packed upper-cased, a table of ids
+//                 in which the LAST record of an id wins (atomicMax)
+//   kf_context    behind kb_group, a lane per entry: the table probed with the chrom bytes, the slice rule, the letters on '-'
+//   kb_sums .. kb_sort_*   as for --vo: every entry's bucket in ascending row order
+//   kg_probs      a lane per row of a selected entry: the stripped probability text into fp64, in bucket order
+//   kg_moments_small / _large   the mean and the sum of the rounded squares: up to 128 rows a lane (one leaf of NumPy's recursion),
+//                 more a workgroup (thread k is node k of the tree of a chunk of 8192; the chunks joined in order)
+//   kg_finish     a lane per entry: the three values, the digits -- or the decline
+//   kb_sums / kb_apply again (the rows' sizes with the attributes), kb_write (no list: --gff writes none)
+//
 // The steps (one lane per line unless said otherwise; n = lines):
 //   kp_count / kp_scan / kp_starts   line starts (the device parser's kernels: mc_lines.h)
 //   kb_parse      256 lines of a workgroup staged in LDS with 16-byte loads; per line: the class of every byte, the tabs, centre 'M',
@@ -66,6 +91,7 @@
 #include "../mc_rowtext.h"
 #include "../mc_decimal.h"
 #include "../mc_tstat.h"
+#include "../mc_npsum.h"
 
 #include <sys/stat.h>
 
@@ -87,6 +113,8 @@ struct BsHead {                              // device-side result block (copied
     int longest_probe;
     unsigned long long first_counted;        // -p: the smallest counted line (~0: none)
     int nv, pad;                             // -p: values per row (kq_counts)
+    unsigned int g_n_large, pad2;            // --gff --vo: entries deeper than a leaf (kg_moments_small)
+    long long f_total, f_nrec;               // --ref: sequence bytes, records (the two scans over the FASTA's lines)
 };
 
 struct BsRow { uint16_t t[7]; uint16_t len; };   // the tabs of a line (offsets from its start; t[6] = len in a 7-field row), its length
@@ -133,6 +161,30 @@ struct BsArgs {
     double *X, *mom;                         // [n_counted][nv] in bucket order; [n_sel][nv - 1][3]
     uint64_t *st_lo;                         // per entry (by the row that claimed its slot) x 2: the digits of the two values
     uint32_t *st_meta;
+    // --gff --vo (mc_gffstats.inc): X holds the probabilities in bucket order, mom [n_sel][2] the mean and the sum of the squares,
+    // st_lo / st_meta the digits of fracLow and fracUp
+    int gstats;                              // the three attributes are wanted (then stats_ready says they are made)
+    int vo_list;                             // a BED row ends with the list of probabilities (--vo without --gff)
+    uint32_t *g_large;
+    double *g_qv;                            // per entry: 100 * mean
+    // --ref (mc_fastactx.inc)
+    int ref;
+    const char *ftext;
+    int64_t f_bytes, f_lines, f_nl;
+    const long long *f_start;
+    long long *f_cnt, *f_off;                // [2 * f_lines] each: sequence bytes / titles of a line; their exclusive scans
+    uint8_t *f_bad;
+    uint32_t *f_idb, *f_idn;                 // per line: a title's id (offset from the line start, length)
+    uint64_t *f_hash;
+    char *f_seq;                             // the packed sequences, upper-cased
+    long long n_rec;
+    long long *rec_begin;                    // [n_rec + 1]
+    uint32_t *rec_line;
+    unsigned long long *f_table;
+    uint32_t *f_win;                         // per slot: the last record of the id + 1
+    uint64_t f_mask;
+    long long *ctx_at;                       // per entry: where its window begins in f_seq
+    uint8_t *ctx_len;                        // ... its length, bit 7: reversed and complemented
 };
 
 __device__ __forceinline__ void bs_flag(const BsArgs &A, int64_t li, int reason) {
@@ -296,6 +348,13 @@ __global__ __launch_bounds__(256) void kb_group(BsArgs A) {
     if ((threadIdx.x & 63) == 0 && probes > 0) atomicMax(&A.head->longest_probe, probes);
 }
 
+// depth >= d and (fraction >= t) != control, the fraction an fp64 quotient (make_bed.py:21-28,:135-138)
+// (-p: every entry -- its rows were wanted, make_bed.py:110-114)
+__device__ __forceinline__ bool bs_selected(const BsArgs &A, uint32_t rep) {
+    const uint32_t depth = A.ent_depth[rep], meth = A.ent_meth[rep];
+    return A.positions || ((long long)depth >= A.min_depth && (((double)meth / (double)depth >= A.thresh) != (A.control != 0)));
+}
+
 // The text of an entry, counted or stored: li its head row.  (--vo: the list itself is kb_write_vo's; *vo_at = where it begins)
 template <class Sink>
 __device__ __forceinline__ void bs_put_span(Sink &o, const char *__restrict__ p, int n) {
@@ -305,6 +364,8 @@ template <class Sink>
 __device__ __forceinline__ void bs_put_lit(Sink &o, const char *s) {
     for (; *s; ++s) o.put(*s);
 }
+
+#include "mc_fastactx.inc"
 
 template <class Sink>
 __device__ __forceinline__ void bs_put_entry(const BsArgs &A, Sink &o, int64_t li, uint32_t depth, uint32_t meth) {
@@ -322,9 +383,15 @@ __device__ __forceinline__ void bs_put_entry(const BsArgs &A, Sink &o, int64_t l
         bs_put_lit(o, "\t.\tcoverage=");
         rt_put_uint(o, depth);
         bs_put_lit(o, ";context=");
-        bs_put_span(o, t + R.t[2] + 1, R.t[3] - R.t[2] - 1);
+        if (A.ref) bs_put_context(A, o, A.row_ent[li]);                 // (--ref reaches the GFF attributes only: make_bed.py:142,:155)
+        else bs_put_span(o, t + R.t[2] + 1, R.t[3] - R.t[2] - 1);
         bs_put_lit(o, ";IPDRatio=5;frac=");
         rt_put_num(o, frac);
+        if (A.gstats && A.stats_ready) {
+            const size_t at = 2 * (size_t)A.row_ent[li];
+            ns_put_attributes(o, rt_num_unpack(A.st_lo[at], A.st_meta[at]), (A.st_meta[at] & BS_META_NAN) != 0,
+                              rt_num_unpack(A.st_lo[at + 1], A.st_meta[at + 1]), (A.st_meta[at + 1] & BS_META_NAN) != 0, A.g_qv[A.row_ent[li]]);
+        }
         return;
     }
     bs_put_span(o, t + R.t[1] + 1, R.t[2] - R.t[1] - 1);
@@ -358,14 +425,12 @@ __device__ __forceinline__ BsEnt bs_entry(const BsArgs &A, int64_t li, bool want
     E.head = true;
     E.depth = A.ent_depth[E.rep];
     E.meth = A.ent_meth[E.rep];
-    // depth >= d and (fraction >= t) != control, the fraction an fp64 quotient (make_bed.py:21-28,:135-138)
-    // (-p: every entry -- its rows were wanted, make_bed.py:110-114)
-    E.sel = A.positions || ((long long)E.depth >= A.min_depth && (((double)E.meth / (double)E.depth >= A.thresh) != (A.control != 0)));
+    E.sel = bs_selected(A, E.rep);
     if (E.sel && want_bytes) {
         RtCount c;
         bs_put_entry(A, c, li, E.depth, E.meth);
         E.bytes = (long long)c.n + 1;                                  // the newline
-        if (A.with_probs) E.bytes += 1 + (long long)A.ent_pbytes[E.rep] + ((long long)E.depth - 1);     // tab, texts, commas
+        if (A.vo_list) E.bytes += 1 + (long long)A.ent_pbytes[E.rep] + ((long long)E.depth - 1);     // tab, texts, commas
     }
     return E;
 }
@@ -505,6 +570,7 @@ __global__ __launch_bounds__(256) void kb_sort_large(BsArgs A, int n_pass) {
 }
 
 #include "mc_sitestats.inc"
+#include "mc_gffstats.inc"
 
 __global__ __launch_bounds__(256) void kb_write(BsArgs A, int64_t n_sel) {
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -514,7 +580,7 @@ __global__ __launch_bounds__(256) void kb_write(BsArgs A, int64_t n_sel) {
     const uint32_t depth = A.ent_depth[rep];
     RtStore o{A.out + A.sel_off[k]};
     bs_put_entry(A, o, li, depth, A.ent_meth[rep]);
-    if (A.with_probs) {
+    if (A.vo_list) {
         o.put('\t');
         A.sel_vo_at[k] = (long long)(o.p - A.out);
         o.p += (long long)A.ent_pbytes[rep] + ((long long)depth - 1);
@@ -578,6 +644,14 @@ const char *bs_reason_text(int reason) {
     case MC_BED_DECLINE_PRINT_RANGE: return "a statistic of 1e9 or more";
     case MC_BED_DECLINE_ROUNDING_TIE: return "a statistic too close to a rounding tie of np.round(., 3) to vouch for its last digit";
     case MC_BED_DECLINE_DEPTH: return "a site of more than 100001 rows";
+    case MC_BED_DECLINE_PROBABILITY: return "a probability that is not a plain decimal number of up to 19 digits";
+    case MC_BED_DECLINE_STAT_RANGE: return "a fracLow or fracUp outside the range the device prints";
+    case MC_BED_DECLINE_QV_RANGE: return "100 x the mean probability is 2^53 or more";
+    case MC_BED_DECLINE_REF_HIGH_BYTE: return "the FASTA has a byte >= 0x80";
+    case MC_BED_DECLINE_REF_CONTROL: return "the FASTA has a control byte other than tab and newline";
+    case MC_BED_DECLINE_REF_SEQ_BYTE: return "the FASTA has a sequence line with a byte that is not a letter";
+    case MC_BED_DECLINE_REF_LETTER: return "a site on '-' with a letter outside ACGTNM in its window of the FASTA";
+    case MC_BED_DECLINE_REF_CONTIG: return "a written site on a contig the FASTA lacks";
     }
     return "unknown";
 }
@@ -658,10 +732,48 @@ int bs_position_set(mc_ctx *c, Pool &pool, BsArgs &A, BsHead *d_head, BsHead &h,
     return 0;
 }
 
+// --ref: the FASTA text (on the device, padded) into the packed sequences and the table of ids -> 0: go on; 1: declined or failed
+int bs_fasta(mc_ctx *c, Pool &pool, BsArgs &A, BsHead *d_head, BsHead &h, const char *d_ftext, int64_t fn, int32_t *status, int *rc) {
+    hipStream_t st = c->stream;
+    *rc = 0;
+    A.ref = 1; A.ftext = d_ftext; A.f_bytes = fn; A.f_mask = 15;
+    if (fn == 0) return 0;                                    // no record: every written entry lacks its contig
+    long long *f_start = nullptr;
+    bool too_many = false;
+    if ((*rc = bs_lines(pool, st, d_ftext, fn, d_head, h, &f_start, &A.f_nl, &A.f_lines, &too_many))) return 1;
+    if (too_many) { (void)bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1); return 1; }
+    A.f_start = f_start;
+    const size_t fl = (size_t)A.f_lines;
+    if (!bs_fits(fl * (4 * 8 + 1 + 4 + 4 + 8) + ((size_t)1 << 20))) { (void)bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1); return 1; }
+    if (pool.get(&A.f_cnt, 2 * fl) || pool.get(&A.f_off, 2 * fl) || pool.get(&A.f_bad, fl) || pool.get(&A.f_idb, fl) || pool.get(&A.f_idn, fl) ||
+        pool.get(&A.f_hash, fl)) { *rc = -10; return 1; }
+    const unsigned wb = (unsigned)((A.f_lines + 3) / 4);
+    hipLaunchKernelGGL(kf_lines, dim3(wb), dim3(256), 0, st, A);
+    hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)A.f_cnt, A.f_lines, A.f_off, &d_head->f_total);
+    hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)(A.f_cnt + fl), A.f_lines, A.f_off + fl, &d_head->f_nrec);
+    if (hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { *rc = -11; return 1; }
+    c->bed_stats.kernel_bytes += 3 * fn + A.f_lines * 6 * 8;
+    if (h.decline != ~0ull) { (void)bs_decline(c, status, (int)(h.decline & 0xff), (long long)(h.decline >> 8)); return 1; }
+    A.n_rec = h.f_nrec;
+    uint64_t slots = 16;
+    while ((long long)slots < 2 * A.n_rec) slots <<= 1;
+    if (!bs_fits((size_t)h.f_total + (size_t)A.n_rec * 12 + (size_t)slots * 12 + ((size_t)1 << 20))) { (void)bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1); return 1; }
+    if (pool.get(&A.f_seq, (size_t)h.f_total + 1) || pool.get(&A.rec_begin, (size_t)A.n_rec + 1) || pool.get(&A.rec_line, (size_t)A.n_rec + 1) ||
+        pool.get(&A.f_table, (size_t)slots) || pool.get(&A.f_win, (size_t)slots)) { *rc = -10; return 1; }
+    A.f_mask = slots - 1;
+    if (hipMemsetAsync(A.f_table, 0, (size_t)slots * 8, st) != hipSuccess || hipMemsetAsync(A.f_win, 0, (size_t)slots * 4, st) != hipSuccess) { *rc = -11; return 1; }
+    hipLaunchKernelGGL(kf_pack, dim3(wb), dim3(256), 0, st, A, A.n_rec, h.f_total);
+    if (A.n_rec > 0) hipLaunchKernelGGL(kf_ids, dim3((unsigned)((A.n_rec + 255) / 256)), dim3(256), 0, st, A, A.n_rec);
+    if (hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { *rc = -11; return 1; }
+    c->bed_stats.kernel_bytes += fn + h.f_total + A.f_lines * 3 * 8 + A.n_rec * 40;
+    if (h.decline != ~0ull) { (void)bs_decline(c, status, (int)(h.decline & 0xff), (long long)(h.decline >> 8)); return 1; }
+    return 0;
+}
+
 // The text is on the device (d_text[0, n), padded; copies enqueued on c->up_stream): everything behind that.  d_ptext: the
-// positions text of -p (pn bytes, padded), or null
-int bs_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *d_ptext, int64_t pn, const mc_bed_params *P, const char **out,
-           int64_t *n_out, int64_t *n_sites, int32_t *status) {
+// positions text of -p (pn bytes, padded), or null; d_ftext: the FASTA text of --ref (fn bytes, padded), or null
+int bs_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *d_ptext, int64_t pn, const char *d_ftext, int64_t fn,
+           const mc_bed_params *P, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status) {
     mc_bed_stats &S = c->bed_stats;
     hipStream_t st = c->stream;
     HIP_TRY(hipStreamSynchronize(c->up_stream));
@@ -679,6 +791,14 @@ int bs_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *d_p
     A.positions = d_ptext != nullptr;
     A.stats = A.positions && !P->gff;
     A.buckets = P->with_probs || A.stats;
+    A.gstats = P->gff && P->with_probs;
+    A.vo_list = P->with_probs && !P->gff;
+    if (d_ftext) {
+        int rc = 0;
+        if (bs_fasta(c, pool, A, d_head, h, d_ftext, fn, status, &rc)) return rc;
+        h.kp = KpHead();                                      // (the line passes count from zero again)
+        HIP_TRY(hipMemcpyAsync(d_head, &h, sizeof h, hipMemcpyHostToDevice, st));
+    }
     if (A.positions) {
         int rc = 0;
         if (bs_position_set(c, pool, A, d_head, h, d_ptext, pn, status, &rc)) return rc;
@@ -691,7 +811,8 @@ int bs_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *d_p
     if (int rc = bs_lines(pool, st, d_text, n, d_head, h, &line_start, &n_nl, &n_lines, &too_many)) return rc;
     if (too_many) return bs_decline(c, status, n_nl + 1 >= ((int64_t)1 << 31) - 2 ? MC_BED_DECLINE_ROWS : MC_BED_DECLINE_MEMORY, -1);
     // per line: the row, four 32-bit columns, the hash, the flags, the entry's five columns (-p: the value count, two numbers' digits)
-    if (!bs_fits((size_t)(n_nl + 2) * (16 + 4 * 4 + 8 + 1 + 4 * 4 + 8 + (A.stats ? 4 + 2 * 12 : 0)) + ((size_t)1 << 20)))
+    if (!bs_fits((size_t)(n_nl + 2) * (16 + 4 * 4 + 8 + 1 + 4 * 4 + 8 + (A.stats ? 4 + 2 * 12 : 0) + (A.gstats ? 2 * 12 + 8 : 0) + (A.ref ? 9 : 0)) +
+                 ((size_t)1 << 20)))
         return bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1);
     S.n_lines = n_lines;
     A.text = d_text; A.n_bytes = n; A.n_lines = n_lines; A.n_nl = n_nl; A.line_start = line_start;
@@ -702,6 +823,12 @@ int bs_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *d_p
         pool.get(&A.ent_fill, nl) || pool.get(&A.ent_pbytes, nl))
         return -10;
     if (A.stats && (pool.get(&A.nval, nl) || pool.get(&A.st_lo, 2 * nl) || pool.get(&A.st_meta, 2 * nl))) return -10;
+    if (A.gstats && (pool.get(&A.st_lo, 2 * nl) || pool.get(&A.st_meta, 2 * nl) || pool.get(&A.g_qv, nl))) return -10;
+    if (A.ref) {
+        if (pool.get(&A.ctx_at, nl) || pool.get(&A.ctx_len, nl)) return -10;
+        HIP_TRY(hipMemsetAsync(A.ctx_at, 0, nl * 8, st));
+        HIP_TRY(hipMemsetAsync(A.ctx_len, 0, nl, st));
+    }
     const unsigned lb = (unsigned)((n_lines + 255) / 256);
     A.nblk = lb;
     hipLaunchKernelGGL(kb_parse, dim3(lb), dim3(256), BS_STAGE + 16, st, A);
@@ -736,6 +863,7 @@ int bs_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *d_p
     HIP_TRY(hipMemsetAsync(A.ent_min, 0xff, nl * 4, st));
     HIP_TRY(hipMemsetAsync(A.ent_pbytes, 0, nl * 8, st));
     hipLaunchKernelGGL(kb_group, dim3(lb), dim3(256), 0, st, A);
+    if (A.ref) hipLaunchKernelGGL(kf_context, dim3(lb), dim3(256), 0, st, A);      // (before the sizes: an entry's text holds its window)
     // the three scans over the lines: bucket places, selected entries, bytes of text (-p with statistics: once more when they are made)
     auto size_entries = [&]() -> int {
         hipLaunchKernelGGL(kb_sums, dim3(lb), dim3(256), 0, st, A);
@@ -757,7 +885,8 @@ int bs_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *d_p
     S.n_sites = n_sel;
     *n_sites = n_sel;
     if (n_sel > 0) {
-        if (!bs_fits((size_t)n_sel * 32 + (size_t)n_outb + (A.stats ? (size_t)n_counted * A.nv * 8 + (size_t)n_sel * A.nv * 24 : 0)))
+        if (!bs_fits((size_t)n_sel * 32 + (size_t)n_outb + (A.stats ? (size_t)n_counted * A.nv * 8 + (size_t)n_sel * A.nv * 24 : 0) +
+                     (A.gstats ? (size_t)n_counted * 8 + (size_t)n_sel * 20 + (size_t)n_sel * 64 : 0)))
             return bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1);
         if (pool.get(&A.sel_line, (size_t)n_sel) || pool.get(&A.large, (size_t)n_sel) || pool.get(&A.sel_off, (size_t)n_sel) ||
             pool.get(&A.sel_vo_at, (size_t)n_sel))
@@ -789,9 +918,27 @@ int bs_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *d_p
             if (!bs_fits((size_t)n_outb)) return bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1);
             hipLaunchKernelGGL(kb_apply, dim3(lb), dim3(256), 0, st, A);
         }
+        if (A.gstats) {
+            if (pool.get(&A.X, (size_t)n_counted) || pool.get(&A.mom, (size_t)n_sel * 2) || pool.get(&A.g_large, (size_t)n_sel)) return -10;
+            hipLaunchKernelGGL(kg_probs, dim3((unsigned)((n_counted + 255) / 256)), dim3(256), 0, st, A, n_counted);
+            HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));      // (a text that is no number: named before the sums run on it)
+            HIP_TRY(hipStreamSynchronize(st));
+            if (h.decline != ~0ull) return bs_decline(c, status, (int)(h.decline & 0xff), (long long)(h.decline >> 8));
+            hipLaunchKernelGGL(kg_moments_small, dim3(sb), dim3(256), 0, st, A, n_sel);
+            hipLaunchKernelGGL(kg_moments_large, dim3((unsigned)std::min<int64_t>(n_sel, 4096)), dim3(NS_NODES), 0, st, A);
+            hipLaunchKernelGGL(kg_finish, dim3(sb), dim3(256), 0, st, A, n_sel);
+            HIP_TRY(hipGetLastError());
+            A.stats_ready = 1;                                // the rows' sizes with the three attributes, and their places
+            if (int rc = size_entries()) return rc;
+            S.kernel_bytes += n_counted * (60 + 3 * 8) + n_sel * 2 * (16 + 12) + n_lines * (1 + 4 + 3 * 4);
+            if (h.decline != ~0ull) return bs_decline(c, status, (int)(h.decline & 0xff), (long long)(h.decline >> 8));
+            n_outb = h.tot_bytes;
+            if (!bs_fits((size_t)n_outb)) return bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1);
+            hipLaunchKernelGGL(kb_apply, dim3(lb), dim3(256), 0, st, A);
+        }
         if (pool.get(&A.out, (size_t)n_outb)) return -10;
         hipLaunchKernelGGL(kb_write, dim3(sb), dim3(256), 0, st, A, n_sel);
-        if (P->with_probs) hipLaunchKernelGGL(kb_write_vo, dim3((unsigned)((n_sel + 3) / 4)), dim3(256), 0, st, A, n_sel);
+        if (A.vo_list) hipLaunchKernelGGL(kb_write_vo, dim3((unsigned)((n_sel + 3) / 4)), dim3(256), 0, st, A, n_sel);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(st));
         S.kernel_bytes += n_lines * (1 + 4 + 3 * 4) + 2 * n_outb + (A.buckets ? n_counted * 24 : 0);
@@ -815,12 +962,12 @@ int bs_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *d_p
 }
 
 // what every entry point begins with -> 0: go on; 1: done (declined, *status set)
-int bs_begin(mc_ctx *c, const mc_bed_params *P, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status, int64_t n) {
+int bs_begin(mc_ctx *c, const mc_bed_params *P, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status, int64_t n, bool annotate) {
     c->bed_stats = mc_bed_stats();
     c->bed_stats.decline_line = -1;
     c->bed_stats.n_bytes = n;
     *out = nullptr; *n_out = 0; *n_sites = 0; *status = 0;
-    if (P->gff && P->with_probs) { (void)bs_decline(c, status, MC_BED_DECLINE_OPTIONS, -1); return 1; }
+    if (P->gff && P->with_probs && !annotate) { (void)bs_decline(c, status, MC_BED_DECLINE_OPTIONS, -1); return 1; }
     if (!bs_fits((size_t)n + 4096)) { (void)bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1); return 1; }
     return 0;
 }
@@ -873,44 +1020,50 @@ int bs_file_size(const char *what, const char *path, int64_t *n) {
     return 0;
 }
 
-// texts: positions == null -> no -p
-int bs_text(mc_ctx *c, const char *text, int64_t n_bytes, const char *positions, int64_t pn, const mc_bed_params *P, const char **out,
-            int64_t *n_out, int64_t *n_sites, int32_t *status) {
+// texts: positions == null -> no -p; fasta == null -> no --ref; annotate: the mc_bed_annotate_* entry points (--gff --vo is made)
+int bs_text(mc_ctx *c, const char *text, int64_t n_bytes, const char *positions, int64_t pn, const char *fasta, int64_t fn, bool annotate,
+            const mc_bed_params *P, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status) {
     HIP_TRY(hipSetDevice(c->device));
     const auto t0 = std::chrono::steady_clock::now();
-    if (bs_begin(c, P, out, n_out, n_sites, status, n_bytes + pn)) return 0;
+    if (bs_begin(c, P, out, n_out, n_sites, status, n_bytes + pn + fn, annotate)) return 0;
     c->bed_stats.n_bytes = n_bytes;
     Pool pool("bed summary");
-    char *d_text = nullptr, *d_ptext = nullptr;
+    char *d_text = nullptr, *d_ptext = nullptr, *d_ftext = nullptr;
     if (int rc = bs_upload_text(c, pool, text, n_bytes, &d_text)) return rc;
     if (positions)
         if (int rc = bs_upload_text(c, pool, positions, pn, &d_ptext)) return rc;
+    if (fasta)
+        if (int rc = bs_upload_text(c, pool, fasta, fn, &d_ftext)) return rc;
     c->bed_stats.ms_h2d = bs_ms_since(t0);
-    const int rc = bs_run(c, pool, d_text, n_bytes, d_ptext, pn, P, out, n_out, n_sites, status);
+    const int rc = bs_run(c, pool, d_text, n_bytes, d_ptext, pn, d_ftext, fn, P, out, n_out, n_sites, status);
     (void)hipStreamSynchronize(c->stream);                   // (an early return: nothing of the pool is in use when it goes)
     c->bed_stats.ms_total = bs_ms_since(t0);
     return rc;
 }
 
-int bs_file(mc_ctx *c, const char *what, const char *path, const char *positions_path, const mc_bed_params *P, const char **out, int64_t *n_out,
-            int64_t *n_sites, int32_t *status) {
-    int64_t n = 0, pn = 0;
+int bs_file(mc_ctx *c, const char *what, const char *path, const char *positions_path, const char *fasta_path, bool annotate,
+            const mc_bed_params *P, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status) {
+    int64_t n = 0, pn = 0, fn = 0;
     if (int rc = bs_file_size(what, path, &n)) return rc;
     if (positions_path)
         if (int rc = bs_file_size(what, positions_path, &pn)) return rc;
+    if (fasta_path)
+        if (int rc = bs_file_size(what, fasta_path, &fn)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     const auto t0 = std::chrono::steady_clock::now();
-    if (bs_begin(c, P, out, n_out, n_sites, status, n + pn)) return 0;
+    if (bs_begin(c, P, out, n_out, n_sites, status, n + pn + fn, annotate)) return 0;
     c->bed_stats.n_bytes = n;
     Pool pool("bed summary");
-    char *d_text = nullptr, *d_ptext = nullptr;
+    char *d_text = nullptr, *d_ptext = nullptr, *d_ftext = nullptr;
     double ms_read = 0;
     if (int rc = bs_upload_file(c, pool, path, n, &d_text, &ms_read)) return rc;
     if (positions_path)
         if (int rc = bs_upload_file(c, pool, positions_path, pn, &d_ptext, &ms_read)) return rc;
+    if (fasta_path)
+        if (int rc = bs_upload_file(c, pool, fasta_path, fn, &d_ftext, &ms_read)) return rc;
     c->bed_stats.ms_read = ms_read;
     c->bed_stats.ms_h2d = bs_ms_since(t0) - ms_read;         // what the copies added behind the reads they ran beside
-    const int rc = bs_run(c, pool, d_text, n, d_ptext, pn, P, out, n_out, n_sites, status);
+    const int rc = bs_run(c, pool, d_text, n, d_ptext, pn, d_ftext, fn, P, out, n_out, n_sites, status);
     (void)hipStreamSynchronize(c->stream);
     c->bed_stats.ms_total = bs_ms_since(t0);
     return rc;
@@ -934,7 +1087,7 @@ extern "C" int mc_bed_summarise_text(mc_ctx *c, const char *text, int64_t n_byte
         mc_set_error("mc_bed_summarise_text: bad arguments");
         return -12;
     }
-    return bs_text(c, text, n_bytes, nullptr, 0, P, out, n_out, n_sites, status);
+    return bs_text(c, text, n_bytes, nullptr, 0, nullptr, 0, false, P, out, n_out, n_sites, status);
 }
 
 extern "C" int mc_bed_summarise_file(mc_ctx *c, const char *path, const mc_bed_params *P, const char **out, int64_t *n_out, int64_t *n_sites,
@@ -943,7 +1096,7 @@ extern "C" int mc_bed_summarise_file(mc_ctx *c, const char *path, const mc_bed_p
         mc_set_error("mc_bed_summarise_file: bad arguments");
         return -12;
     }
-    return bs_file(c, "mc_bed_summarise_file", path, nullptr, P, out, n_out, n_sites, status);
+    return bs_file(c, "mc_bed_summarise_file", path, nullptr, nullptr, false, P, out, n_out, n_sites, status);
 }
 
 extern "C" int mc_bed_positions_text(mc_ctx *c, const char *text, int64_t n_bytes, const char *positions, int64_t pn, const mc_bed_params *P,
@@ -952,7 +1105,7 @@ extern "C" int mc_bed_positions_text(mc_ctx *c, const char *text, int64_t n_byte
         mc_set_error("mc_bed_positions_text: bad arguments");
         return -12;
     }
-    return bs_text(c, text, n_bytes, positions, pn, P, out, n_out, n_sites, status);
+    return bs_text(c, text, n_bytes, positions, pn, nullptr, 0, false, P, out, n_out, n_sites, status);
 }
 
 extern "C" int mc_bed_positions_file(mc_ctx *c, const char *path, const char *positions_path, const mc_bed_params *P, const char **out,
@@ -961,7 +1114,77 @@ extern "C" int mc_bed_positions_file(mc_ctx *c, const char *path, const char *po
         mc_set_error("mc_bed_positions_file: bad arguments");
         return -12;
     }
-    return bs_file(c, "mc_bed_positions_file", path, positions_path, P, out, n_out, n_sites, status);
+    return bs_file(c, "mc_bed_positions_file", path, positions_path, nullptr, false, P, out, n_out, n_sites, status);
+}
+
+extern "C" int mc_bed_annotate_text(mc_ctx *c, const char *text, int64_t n_bytes, const char *positions, int64_t pn, const char *fasta, int64_t fn,
+                                    const mc_bed_params *P, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status) {
+    if (!c || !P || !out || !n_out || !n_sites || !status || n_bytes < 0 || (n_bytes > 0 && !text) || pn < 0 || fn < 0) {
+        mc_set_error("mc_bed_annotate_text: bad arguments");
+        return -12;
+    }
+    return bs_text(c, text, n_bytes, positions, positions ? pn : 0, fasta, fasta ? fn : 0, true, P, out, n_out, n_sites, status);
+}
+
+extern "C" int mc_bed_annotate_file(mc_ctx *c, const char *path, const char *positions_path, const char *fasta_path, const mc_bed_params *P,
+                                    const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status) {
+    if (!c || !path || !P || !out || !n_out || !n_sites || !status) {
+        mc_set_error("mc_bed_annotate_file: bad arguments");
+        return -12;
+    }
+    return bs_file(c, "mc_bed_annotate_file", path, positions_path, fasta_path, true, P, out, n_out, n_sites, status);
+}
+
+// p: the arrays one behind the other, off[count + 1] their places; out6 per array: fracLow, fracUp, 100 * mean, mean, var, se
+extern "C" int mc_gff_site_stats_device(mc_ctx *c, const double *p, const int64_t *off, const double *frac, int64_t count, double *out6,
+                                        int32_t *status) {
+    if (!c || count < 0 || (count > 0 && (!p || !off || !frac || !out6 || !status))) {
+        mc_set_error("mc_gff_site_stats_device: bad arguments");
+        return -12;
+    }
+    if (count == 0) return 0;
+    for (int64_t i = 0; i < count; ++i)
+        if (off[i + 1] <= off[i] || off[0] != 0) { mc_set_error("mc_gff_site_stats_device: an empty array"); return -12; }
+    HIP_TRY(hipSetDevice(c->device));
+    Pool pool("site statistics probe");
+    const int64_t total = off[count];
+    double *d_p = nullptr, *d_frac = nullptr, *d_out = nullptr;
+    long long *d_off = nullptr;
+    int32_t *d_st = nullptr;
+    if (pool.get(&d_p, (size_t)total) || pool.get(&d_off, (size_t)count + 1) || pool.get(&d_frac, (size_t)count) || pool.get(&d_out, (size_t)count * 6) ||
+        pool.get(&d_st, (size_t)count))
+        return -10;
+    hipStream_t st = c->stream;
+    HIP_TRY(hipMemcpyAsync(d_p, p, (size_t)total * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_off, off, ((size_t)count + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_frac, frac, (size_t)count * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_ns_probe, dim3((unsigned)std::min<int64_t>(count, 4096)), dim3(NS_NODES), 0, st, (const double *)d_p, (const long long *)d_off,
+                       (const double *)d_frac, count, d_out, d_st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out6, d_out, (size_t)count * 48, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(status, d_st, (size_t)count * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int mc_npsum_se_device(mc_ctx *c, const double *var, const double *n, int64_t count, double *se) {
+    if (!c || count < 0 || (count > 0 && (!var || !n || !se))) {
+        mc_set_error("mc_npsum_se_device: bad arguments");
+        return -12;
+    }
+    if (count == 0) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    Pool pool("standard error probe");
+    double *d_in = nullptr, *d_out = nullptr;
+    if (pool.get(&d_in, (size_t)count * 2) || pool.get(&d_out, (size_t)count)) return -10;
+    hipStream_t st = c->stream;
+    HIP_TRY(hipMemcpyAsync(d_in, var, (size_t)count * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_in + count, n, (size_t)count * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_ns_se_probe, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, (const double *)d_in, (const double *)(d_in + count), count, d_out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(se, d_out, (size_t)count * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
 }
 
 extern "C" int mc_tstat_device(mc_ctx *c, const double *n, const double *mean, const double *var, int64_t count, double *t, double *log10_p,

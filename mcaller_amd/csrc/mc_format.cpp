@@ -11,6 +11,7 @@
 #include "mc_sortkey.h"
 #include "mc_rowtext.h"
 #include "mc_tstat.h"
+#include "mc_npsum.h"
 #include "../../include/mcaller_hip.h"
 
 #include <algorithm>
@@ -643,6 +644,40 @@ extern "C" int mc_tstat_site(const double *X, int64_t n_rows, int32_t n_cols, do
     if (n_rows >= 2 && (!rt_num_of(out2[0]).ok || !rt_num_of(out2[1]).ok)) flags |= 64;      // (a value mc_rowtext.h does not print)
     return flags;
 }
+
+// the attributes of make_bed --gff --vo by mc_npsum.h's host build (include/mcaller_hip.h): p[0, n) the probabilities in row order
+extern "C" int mc_gff_site_moments(const double *p, int64_t n, double out3[3]) {
+    if (!p || !out3 || n < 1) return NS_BAD_N;
+    double mean, ss;
+    const int st = ns_moments(p, n, &mean, &ss);
+    out3[0] = mean;
+    out3[1] = ss / (double)(n - 1);
+    out3[2] = ns_se(out3[1], (double)n);
+    return st;
+}
+extern "C" int mc_gff_site_stats(const double *p, int64_t n, double frac, double out3[3]) {
+    if (!p || !out3 || n < 1) return NS_BAD_N;
+    double mean, ss;
+    const int st = ns_moments(p, n, &mean, &ss);
+    return st | ns_finish(mean, ss, n, frac, out3);
+}
+// ... as the kernels print them: ";fracLow=..;fracUp=..;identificationQv=.." into buf[0, cap) -> its length, or -1 - (status bits) when
+// the device would decline, or -12
+extern "C" int mc_gff_site_text(const double *p, int64_t n, double frac, char *buf, int32_t cap) {
+    double out3[3];
+    if (!buf) return -12;
+    const int st = mc_gff_site_stats(p, n, frac, out3);
+    if (st & ~NS_NAN) return -1 - st;
+    const bool lo_nan = !(out3[0] == out3[0]), hi_nan = !(out3[1] == out3[1]);
+    const RtNum lo = lo_nan ? RtNum() : rt_num_of(out3[0]), hi = hi_nan ? RtNum() : rt_num_of(out3[1]);
+    RtCount count;
+    ns_put_attributes(count, lo, lo_nan, hi, hi_nan, out3[2]);
+    if (count.n > cap) return -12;
+    RtStore store{buf};
+    ns_put_attributes(store, lo, lo_nan, hi, hi_nan, out3[2]);
+    return count.n;
+}
+extern "C" double mc_npsum_se(double var, double n) { return ns_se(var, n); }
 
 // the numeric key of `sort -n -k2` for the line s[0, n) by mc_sortkey.h's host build -> 0: (*hi, *lo) hold it; 1: beyond the digit limits
 extern "C" int mc_sort_key(const char *s, int64_t n, uint64_t *hi, uint64_t *lo) {

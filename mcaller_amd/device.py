@@ -629,19 +629,36 @@ class Device(object):
     # ---- the per-site summary of a .diffs file (csrc/bed/mc_bedsum.hip) ----
     @_serialized
     def bed_summarise(self, path=None, text=None, min_depth=15, mod_threshold=0.5, control=False, with_probs=False, gff=False,
-                      positions_path=None, positions_text=None):
+                      positions_path=None, positions_text=None, ref_path=None, ref_text=None, site_stats=False):
         """The bytes make_bed writes for a `.diffs.<k>` file (`path`) or its text (`text`, bytes), made on the GPU; with
         `positions_path` (beside `path`) or `positions_text` (beside `text`) what make_bed -p writes: the rows at the listed
         positions, every entry, two t-test columns in a BED row.
+        With `ref_path` / `ref_text` (a FASTA: make_bed --ref) the GFF attributes carry the 41 bases around the site; with
+        `site_stats` --gff --vo is made (fracLow, fracUp, identificationQv: mc_bed_annotate_*) -- without it that combination
+        declines, as it always did.
         -> (bytes, number of sites, None), or (None, 0, reason) when the device declines: the caller runs the host code."""
         if (path is None) == (text is None):
             raise ValueError('bed_summarise: a path or a text')
         if (positions_path is not None and path is None) or (positions_text is not None and text is None):
             raise ValueError('bed_summarise: positions_path goes with path, positions_text with text')
+        if (ref_path is not None and path is None) or (ref_text is not None and text is None):
+            raise ValueError('bed_summarise: ref_path goes with path, ref_text with text')
         d = int(min_depth)
         prm = _lib.BedParams(max(-2 ** 62, min(2 ** 62, d)), float(mod_threshold), int(bool(control)), int(bool(with_probs)), int(bool(gff)), 0)
         out, n_out, n_sites, status = C.c_void_p(), C.c_int64(), C.c_int64(), C.c_int32()
-        if positions_path is not None:
+        if site_stats or ref_path is not None or ref_text is not None:
+            if path is not None:
+                check(lib().mc_bed_annotate_file(self._ctx, os.fsencode(path), None if positions_path is None else os.fsencode(positions_path),
+                                                 None if ref_path is None else os.fsencode(ref_path), C.byref(prm), C.byref(out),
+                                                 C.byref(n_out), C.byref(n_sites), C.byref(status)))
+            else:
+                text = bytes(text)
+                positions_text = None if positions_text is None else bytes(positions_text)
+                ref_text = None if ref_text is None else bytes(ref_text)
+                check(lib().mc_bed_annotate_text(self._ctx, text, len(text), positions_text, len(positions_text or b''), ref_text,
+                                                 len(ref_text or b''), C.byref(prm), C.byref(out), C.byref(n_out), C.byref(n_sites),
+                                                 C.byref(status)))
+        elif positions_path is not None:
             check(lib().mc_bed_positions_file(self._ctx, os.fsencode(path), os.fsencode(positions_path), C.byref(prm), C.byref(out),
                                               C.byref(n_out), C.byref(n_sites), C.byref(status)))
         elif positions_text is not None:
@@ -732,6 +749,32 @@ class Device(object):
         t, l, st = np.zeros(len(n)), np.zeros(len(n)), np.zeros(len(n), dtype=np.int32)
         check(lib().mc_tstat_device(self._ctx, _ptr(n), _ptr(mean), _ptr(var), len(n), _ptr(t), _ptr(l), _ptr(st)))
         return st, t, l
+
+    @_serialized
+    def gff_site_stats(self, arrays, frac):
+        """fracLow, fracUp and 100 * mean of make_bed --gff --vo for every array of probabilities (frac: its entry's fraction) by
+        mc_npsum.h's device build, a workgroup per array (mc_gff_site_stats_device, tests)
+        -> (status bits int32 [k], float64 [k, 6]: fracLow, fracUp, 100 * mean, mean, var, se)."""
+        arrays = [np.ascontiguousarray(a, dtype=np.float64) for a in arrays]
+        frac = np.ascontiguousarray(frac, dtype=np.float64)
+        if len(frac) != len(arrays) or any(a.ndim != 1 or len(a) < 1 for a in arrays):
+            raise ValueError('gff_site_stats: a fraction for every array, no array empty')
+        off = np.zeros(len(arrays) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(a) for a in arrays], dtype=np.int64)
+        p = np.concatenate(arrays) if arrays else np.zeros(0)
+        out, st = np.zeros((len(arrays), 6)), np.zeros(len(arrays), dtype=np.int32)
+        check(lib().mc_gff_site_stats_device(self._ctx, _ptr(p), _ptr(off), _ptr(frac), len(arrays), _ptr(out), _ptr(st)))
+        return st, out
+
+    @_serialized
+    def npsum_se(self, var, n):
+        """sqrt(var) / sqrt(n) by mc_npsum.h's device build, a lane per pair (mc_npsum_se_device, tests)."""
+        var, n = (np.ascontiguousarray(a, dtype=np.float64) for a in (var, n))
+        if not (var.ndim == 1 and var.shape == n.shape):
+            raise ValueError('npsum_se: two arrays of one length')
+        se = np.zeros(len(var))
+        check(lib().mc_npsum_se_device(self._ctx, _ptr(var), _ptr(n), len(var), _ptr(se)))
+        return se
 
     @_serialized
     def training_rows(self, path=None, text=None, pairs=()):

@@ -5,7 +5,8 @@
   * flush records on the GPUs (`site_counts`, `write_bed_from_counts`): per-site counts reduced on the device and summed
     over ranks with one all-reduce (mc_site_allreduce), the one exchange step of the multi-GPU path;
   * the same file on the GPU (`summarise_diffs_device`, `--device`): BED, --control, --vo and GFF, and -p (per-site t-tests;
-    from the command line with MCALLER_BED_POSITIONS_DEVICE=1); what the device declines goes through `summarise_diffs`.
+    from the command line with MCALLER_BED_POSITIONS_DEVICE=1), and with MCALLER_BED_GFF_DEVICE=1 --gff --vo and --ref; what the
+    device declines goes through `summarise_diffs`.
 
 Options: -f, -d, -t, -p (per-position one-sample t-tests, make_bed.py:115-127; needs scipy, like the reference), --control,
 --vo, --gff (with --vo: fracLow/fracUp/identificationQv, make_bed.py:146-149), --ref.  Plotting is out of scope; the
@@ -163,22 +164,31 @@ def summarise_diffs(diffs_path, out_path, depth_thresh, mod_thresh, positions=No
 last_summary = None        # what summarise_diffs_device did last: dict(by='device' | 'host', reason=None | str, n_sites=int)
 
 
+def gff_device_wanted():
+    """MCALLER_BED_GFF_DEVICE=1: --gff --vo (fracLow, fracUp, identificationQv) and --ref go to the device too."""
+    return os.environ.get('MCALLER_BED_GFF_DEVICE') == '1'
+
+
 def summarise_diffs_device(diffs_path, out_path, depth_thresh, mod_thresh, control=False, with_probs=False, gff=False,
-                           quiet=False, positions=None):
+                           quiet=False, positions=None, ref=None):
     """summarise_diffs with the file summarised on the GPU (Device.bed_summarise): BED, BED --control, BED --vo, GFF, and with
     `positions` what -p writes (every entry at a listed position; two t-test columns in a BED row).  The device writes the
-    reference's bytes or declines; then, and for --gff --vo, the host function does the file (and words the errors).
+    reference's bytes or declines; then the host function does the file (and words the errors) -- as it does --gff --vo and
+    `ref` (--ref) unless MCALLER_BED_GFF_DEVICE=1 sends those to the device as well.
     Returns the number of sites; `last_summary` says who made the file."""
     global last_summary
-    reason = 'out of scope on the device: --gff with --vo' if (gff and with_probs) else None
+    reason = None
+    if not gff_device_wanted():
+        reason = 'out of scope on the device: ' + ('--gff with --vo' if (gff and with_probs) else '--ref') if ((gff and with_probs) or ref) else None
     if reason is None:
         from .device import get_device
         blob, count, reason = get_device().bed_summarise(path=diffs_path, min_depth=depth_thresh, mod_threshold=mod_thresh,
                                                          control=control, with_probs=with_probs, gff=gff,
-                                                         positions_path=positions or None)
+                                                         positions_path=positions or None, ref_path=ref or None,
+                                                         site_stats=bool(gff and with_probs))
     if reason is not None:
         count = summarise_diffs(diffs_path, out_path, depth_thresh, mod_thresh, positions=positions, control=control,
-                                with_probs=with_probs, gff=gff, quiet=quiet)
+                                with_probs=with_probs, gff=gff, ref=ref or None, quiet=quiet)
         last_summary = dict(by='host', reason=reason, n_sites=count)
         return count
     with open(out_path, 'wb') as out:
@@ -362,7 +372,8 @@ def build_parser():
     parser.add_argument('-v', '--version', action='version', version='%(prog)s v1.0')
     parser.add_argument('--device', action='store_true', required=False,
                         help='(mcaller_amd) summarise the file on the GPU (BED, --control, --vo, --gff; -p with '
-                             'MCALLER_BED_POSITIONS_DEVICE=1; --ref and --gff --vo stay with the host code)')
+                             'MCALLER_BED_POSITIONS_DEVICE=1; --ref and --gff --vo with MCALLER_BED_GFF_DEVICE=1, else '
+                             'they stay with the host code)')
     return parser
 
 
@@ -386,17 +397,18 @@ def main(argv=None):
 
 
 def _main_device(args, output_file):
-    """main --device: the options the device summarises go there; --ref, and -p unless MCALLER_BED_POSITIONS_DEVICE=1 asks for it
-    (and then not with --gff --vo), go to the host function as without the flag."""
+    """main --device: the options the device summarises go there; --ref and --gff --vo unless MCALLER_BED_GFF_DEVICE=1 asks for
+    them, and -p unless MCALLER_BED_POSITIONS_DEVICE=1 asks for it, go to the host function as without the flag."""
     global last_summary
-    positions_device = bool(args.positions) and os.environ.get('MCALLER_BED_POSITIONS_DEVICE') == '1' and not (args.gff and args.vo)
-    if args.ref or (args.positions and not positions_device):
+    gff_device = gff_device_wanted()
+    positions_device = bool(args.positions) and os.environ.get('MCALLER_BED_POSITIONS_DEVICE') == '1' and (gff_device or not (args.gff and args.vo))
+    if (args.ref and not gff_device) or (args.positions and not positions_device):
         count = summarise_diffs(args.mCaller_file, output_file, args.min_read_depth, args.mod_threshold, positions=args.positions,
                                 control=args.control, with_probs=args.vo, gff=args.gff, ref=args.ref)
         last_summary = dict(by='host', reason='out of scope on the device: ' + ('-p' if args.positions else '--ref'), n_sites=count)
         return
     summarise_diffs_device(args.mCaller_file, output_file, args.min_read_depth, args.mod_threshold, control=args.control,
-                           with_probs=args.vo, gff=args.gff, positions=args.positions)
+                           with_probs=args.vo, gff=args.gff, positions=args.positions, ref=args.ref)
 
 
 if __name__ == '__main__':
