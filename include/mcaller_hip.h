@@ -790,6 +790,49 @@ int mc_rows_merge_last_stats(mc_ctx *ctx, mc_rows_merge_stats *out);
 int mc_rows_merge_release(mc_ctx *ctx);
 int mc_sort_key(const char *line, int64_t n, uint64_t *hi, uint64_t *lo);
 
+/* ===== the read qualities of a FASTQ file, made on the GPU (read_qual.py:15-47; csrc/mc_fastqrec.h, csrc/fastq/mc_fastqual.hip) =====
+ * The text of a FASTQ file -> one (key, mean phred) pair per record in file order, in the layout of mc_fastq_view: the keys in
+ * one pool with '\n' behind each, n + 1 offsets, n means.  The pairs are read_qual.extract_read_quality_py's bit for bit, or
+ * the call declines -- *status = 1, mc_last_error says why (mc_fastq_quality_last_stats: which line and reason), the view is
+ * empty and the caller runs the host reader on the file, which raises the reference's errors.  Declined:
+ * MC_FASTQ_DECLINE_* below; of several offending lines the first is named, of several reasons on it the smallest.  The
+ * view's pointers are pinned memory owned by the context: valid until the next mc_fastq_quality_* call on it or
+ * mc_fastq_quality_release.
+ * mc_fastq_records_host: the same rules (csrc/mc_fastqrec.h) run line by line on the CPU, no GPU and no context -> a handle
+ * for mc_fastq_view / mc_fastq_free (null when declined); mc_fastq_records_host_decline: the line and reason of the calling
+ * thread's last decline. */
+typedef struct mc_fastq_quality_view {
+    const char *key_pool;          /* key i = key_pool[key_off[i], key_off[i + 1] - 1), a '\n' behind it */
+    const int64_t *key_off;        /* [n_records + 1] */
+    const double *mean;            /* [n_records]; NaN for a record without bases */
+    int64_t n_records;
+} mc_fastq_quality_view;
+typedef struct mc_fastq_quality_stats {
+    int64_t n_bytes, n_lines, n_records;
+    int64_t n_pieces;              /* pieces the quality lines were cut into: a wave sums one */
+    int64_t decline_line;          /* 0-based line the decline names, -1: none            */
+    int32_t decline_reason;        /* 0: not declined; MC_FASTQ_DECLINE_*                 */
+    int32_t piece_bytes;           /* bytes of a piece                                    */
+    double ms_read, ms_h2d, ms_kernels, ms_d2h, ms_total;
+} mc_fastq_quality_stats;
+#define MC_FASTQ_DECLINE_HIGH_BYTE  1   /* a byte >= 0x80                                                                 */
+#define MC_FASTQ_DECLINE_CONTROL    2   /* a control byte other than tab, '\n' and '\r', or 0x7f                          */
+#define MC_FASTQ_DECLINE_LONE_CR    3   /* a '\r' not directly followed by '\n' (Python's universal newlines split there) */
+#define MC_FASTQ_DECLINE_TITLE      4   /* a title line that does not start with '@' (a blank line between records too)   */
+#define MC_FASTQ_DECLINE_PLUS       5   /* a third line that does not start with '+' (a file that ends inside a record)   */
+#define MC_FASTQ_DECLINE_LENGTH     6   /* a quality line as long as its stripped sequence line it is not                 */
+#define MC_FASTQ_DECLINE_EMPTY_ID   7   /* a title line with nothing but blanks and tabs behind its '@'                   */
+#define MC_FASTQ_DECLINE_ROWS       8   /* 2^31 - 2 lines or more                                                         */
+#define MC_FASTQ_DECLINE_MEMORY     9   /* the text does not fit into free device memory beside its outputs               */
+#define MC_FASTQ_DECLINE_GZ         10  /* a path containing ".gz": decided by the caller (read_qual.py), nothing is read  */
+int mc_fastq_quality_text(mc_ctx *ctx, const char *text, int64_t n_bytes, mc_fastq_quality_view *out, int32_t *status);
+/* ... of a file: read in pinned blocks (mc_read_file_range) while the block before is on its way to the device. */
+int mc_fastq_quality_file(mc_ctx *ctx, const char *path, mc_fastq_quality_view *out, int32_t *status);
+int mc_fastq_quality_last_stats(mc_ctx *ctx, mc_fastq_quality_stats *out);
+int mc_fastq_quality_release(mc_ctx *ctx);
+int mc_fastq_records_host(const char *text, int64_t n_bytes, mc_fastq **out, int32_t *status);
+int mc_fastq_records_host_decline(int32_t *reason, int64_t *line);
+
 /* ===== measurement plumbing: a table as nanopolish-eventalign text (13 columns), written by all host cores =====
  * For file-to-file timing on synthetic workloads (bench.py); seq = the contig's bases (k-mers of columns 3 and 10). */
 int mc_synth_write_tsv(const char *path, const mc_table_view *table, const char *seq, int64_t seq_len, const char *contig,

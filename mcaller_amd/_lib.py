@@ -126,6 +126,20 @@ class RowsMergeStats(C.Structure):
                 ('ms_d2h', C.c_double), ('ms_write', C.c_double), ('ms_total', C.c_double)]
 
 
+class FastqQualityView(C.Structure):
+    """mc_fastq_quality_view (include/mcaller_hip.h)."""
+    _fields_ = [('key_pool', C.c_void_p), ('key_off', C.c_void_p), ('mean', C.c_void_p), ('n_records', C.c_int64)]
+
+
+class FastqQualityStats(C.Structure):
+    """mc_fastq_quality_stats (include/mcaller_hip.h)."""
+    _fields_ = [('n_bytes', C.c_int64), ('n_lines', C.c_int64), ('n_records', C.c_int64), ('n_pieces', C.c_int64),
+                ('decline_line', C.c_int64), ('decline_reason', C.c_int32), ('piece_bytes', C.c_int32), ('ms_read', C.c_double),
+                ('ms_h2d', C.c_double), ('ms_kernels', C.c_double), ('ms_d2h', C.c_double), ('ms_total', C.c_double)]
+
+
+FASTQ_DECLINE = {'high_byte': 1, 'control': 2, 'lone_cr': 3, 'title': 4, 'plus': 5, 'length': 6, 'empty_id': 7, 'rows': 8,
+                 'memory': 9, 'gz': 10}                                                          # MC_FASTQ_DECLINE_*
 MERGE_DECLINE = {'cr': 1, 'no_newline': 2, 'key': 3, 'long_line': 4, 'rows': 5, 'memory': 6}     # MC_MERGE_DECLINE_*
 
 
@@ -159,6 +173,12 @@ def lib():
         L.mc_fastq_view.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
         L.mc_fastq_view.restype = C.c_int64
         L.mc_fastq_free.argtypes = [C.c_void_p]
+        L.mc_fastq_records_host.argtypes = [C.c_char_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]
+        L.mc_fastq_records_host_decline.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+        L.mc_fastq_quality_text.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.POINTER(FastqQualityView), C.POINTER(C.c_int32)]
+        L.mc_fastq_quality_file.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(FastqQualityView), C.POINTER(C.c_int32)]
+        L.mc_fastq_quality_last_stats.argtypes = [C.c_void_p, C.POINTER(FastqQualityStats)]
+        L.mc_fastq_quality_release.argtypes = [C.c_void_p]
         L.mc_parsed_view.argtypes = [C.c_void_p, C.POINTER(TableView)]
         L.mc_parsed_read_name.argtypes = [C.c_void_p, C.c_int32]
         L.mc_parsed_read_name.restype = C.c_char_p
@@ -490,12 +510,38 @@ def fastq_read_quality(path, n_threads=0):
     try:
         pool, off, mean = C.c_void_p(), C.c_void_p(), C.c_void_p()
         n = L.mc_fastq_view(handle, C.byref(pool), C.byref(off), C.byref(mean))
-        if n <= 0:
-            return [], np.zeros(0, dtype=np.float64)
-        offs = np.ctypeslib.as_array(C.cast(off, C.POINTER(C.c_int64)), shape=(n + 1,))
-        text = C.string_at(pool, int(offs[n])).decode('utf-8')
-        means = np.ctypeslib.as_array(C.cast(mean, C.POINTER(C.c_double)), shape=(n,)).copy()
-        return text.split('\n')[:n], means
+        return fastq_unpack(pool, off, mean, n)
+    finally:
+        L.mc_fastq_free(handle)
+
+
+def fastq_unpack(pool, off, mean, n):
+    """The layout of mc_fastq_view (and of mc_fastq_quality_view): a pool of keys with a newline behind each, n + 1 offsets, n means
+    -> (keys: list of str, means: float64 array), copies."""
+    if n <= 0:
+        return [], np.zeros(0, dtype=np.float64)
+    offs = np.ctypeslib.as_array(C.cast(off, C.POINTER(C.c_int64)), shape=(n + 1,))
+    text = C.string_at(pool, int(offs[n])).decode('utf-8')
+    means = np.ctypeslib.as_array(C.cast(mean, C.POINTER(C.c_double)), shape=(n,)).copy()
+    return text.split('\n')[:n], means
+
+
+def fastq_records_host(text):
+    """The record rules of csrc/mc_fastqrec.h run on the CPU over `text` (bytes), no GPU (mc_fastq_records_host): what the device
+    reader is held against.  -> (keys, means, None), or (None, None, dict(reason=MC_FASTQ_DECLINE_*, line=0-based, text=str)) where
+    the rules decline."""
+    L = lib()
+    text = bytes(text)
+    handle, status = C.c_void_p(), C.c_int32()
+    check(L.mc_fastq_records_host(text, len(text), C.byref(handle), C.byref(status)))
+    if status.value != 0:
+        reason, line = C.c_int32(), C.c_int64()
+        L.mc_fastq_records_host_decline(C.byref(reason), C.byref(line))
+        return None, None, dict(reason=reason.value, line=line.value, text=L.mc_last_error().decode('utf-8', 'replace'))
+    try:
+        pool, off, mean = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        n = L.mc_fastq_view(handle, C.byref(pool), C.byref(off), C.byref(mean))
+        return fastq_unpack(pool, off, mean, n) + (None,)
     finally:
         L.mc_fastq_free(handle)
 

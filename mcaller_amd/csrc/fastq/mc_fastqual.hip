@@ -1,0 +1,441 @@
+// mc_fastqual.hip -- the read qualities of a FASTQ file, made on the GPU: one (key, mean phred) pair per record, what
+// read_qual.py:15-47 builds line by line in Python (C ABI: mc_fastq_quality_text / _file, mc_fastq_quality_last_stats,
+// mc_fastq_quality_release; Python: Device.fastq_qualities, read_qual.extract_read_quality_device).  The unit stands in csrc/fastq/,
+// beside the units of the passes like csrc/bed/, csrc/train/ and csrc/merge/: no pass runs its kernels.
+//
+// The rules of a record, and what makes the reader decline (status 1, mc_last_error; MC_FASTQ_DECLINE_*), are mc_fastqrec.h's --
+// the same functions mc_fastq_records_host runs on the CPU.  Beyond them the call declines for 2^31 - 2 lines or more and for a text
+// that does not fit into free device memory beside its outputs: the WHOLE text stays resident.
+//
+// The steps (R = records, P = FQ_PIECE bytes):
+//   kp_count / kp_scan / kp_starts   line starts (the device parser's kernels: mc_lines.h)
+//   kfq_class    a stream over the whole text, 64 bytes a lane in four 16-byte loads: the byte classes and the '\r' rule four bytes
+//                at a time (the byte behind a word and behind the tile is looked at too), the last byte that is no blank, tab or
+//                line break by atomicMax.  Only a lane that found something walks its bytes: atomicMin of line << 8 | reason
+//   kfq_last     one lane: the line of that last byte -> R
+//   kfq_records  a lane per record: fq_record on its four line spans (the title line, the two ends of the sequence line, one byte
+//                of the third) -> the key's span and length + 1 (kfq_keylen is merged into it: the title is read once), the
+//                quality line's span, its pieces ceil(n / P), a zeroed 64-bit sum
+//   kp_scan x 2  the pieces and the key lengths, exclusive
+//   kfq_piecemap a lane per record: the record of each of its pieces (a read of 10^6 bases has 245)
+//   kfq_sum      a WAVE per piece: 16-byte loads from the aligned address at or below the piece's first byte, the bytes outside the
+//                piece masked off, byte sums by v_sad_u8, one 64-bit integer atomicAdd a piece into its record's sum -- integer
+//                addition: the result does not depend on the order of arrival.  Only quality lines are read
+//   kfq_finish   a lane per record: fq_mean
+//   kfq_keys     a lane per record: its key and a '\n' into the pool; the offsets' last entry
+// wave64; no library sort or scan; every buffer, event and stream through the owners of mc_own.h.
+#include "../mc_lines.h"
+#include "../mc_fastqrec.h"
+
+#include <sys/stat.h>
+
+#include <chrono>
+#include <cstring>
+
+extern "C" int mc_read_file_range(const char *path, int64_t lo, int64_t hi, char *dst, int32_t n_threads);
+
+namespace {
+
+struct FqHead {                              // device-side result block (copied to the host as it is)
+    KpHead kp;                               // n_newlines (kp_scan), n_lines (kp_starts)
+    unsigned long long decline;              // min over the offending lines of line << 8 | reason (~0: none)
+    unsigned long long last_off1;            // 1 + the offset of the last byte that is no blank, tab or line break (0: none)
+    long long last_line;                     // its line (-1: none)
+    long long n_pieces, pool_bytes;          // totals of the two scans
+};
+
+struct FqArgs {
+    const char *text;
+    int64_t n_bytes, n_lines, n_nl, R;
+    const long long *line_start;
+    FqHead *head;
+    // per record
+    long long *key_b, *key_len1, *qual_b, *qual_n, *pieces, *piece_off, *key_off;
+    unsigned long long *sum;
+    double *mean;
+    // per piece; the keys
+    uint32_t *piece_rec;
+    int64_t n_pieces;
+    char *pool;
+};
+
+__device__ __forceinline__ void fq_flag(FqHead *head, unsigned long long code) {
+    if (code < head->decline) atomicMin(&head->decline, code);     // (the value only falls: a stale one costs an atomic, no more)
+}
+
+// the bytes [b, e) one by one: the declines with their lines, the last byte that fills a line -> 1 + its offset, 0: none
+__device__ __noinline__ unsigned long long fq_class_bytes(const char *__restrict__ text, int64_t n, const long long *__restrict__ line_start,
+                                                          int64_t n_nl, FqHead *head, int64_t b, int64_t e) {
+    unsigned long long last1 = 0;
+    int64_t line = -1;
+    for (int64_t i = b; i < e; ++i) {
+        const unsigned c = (unsigned char)text[i];
+        const int reason = fq_byte_reason(c, i + 1 < n ? (int)(unsigned char)text[i + 1] : -1);
+        if (reason) {
+            if (line < 0) line = fq_line_of(line_start, n_nl, i);
+            fq_flag(head, fq_code(line, reason));
+        }
+        if (!fq_blank(c) && c != '\r' && c != '\n') last1 = (unsigned long long)i + 1;
+        if (c == '\n' && line >= 0) ++line;
+    }
+    return last1;
+}
+
+__global__ __launch_bounds__(KP_THREADS) void kfq_class(const char *__restrict__ text, int64_t n, const long long *__restrict__ line_start,
+                                                        int64_t n_nl, FqHead *__restrict__ head) {
+    __shared__ unsigned long long s_last[KP_THREADS / 64];
+    const int64_t b = (int64_t)blockIdx.x * KP_TILE + threadIdx.x * 64;
+    unsigned long long last1 = 0;
+    if (b + 64 <= n) {
+        uint32_t w[16];
+        const uint4 *p = reinterpret_cast<const uint4 *>(text + b);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint4 v = p[i];
+            w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+        }
+        const unsigned behind = b + 64 < n ? (unsigned)(unsigned char)text[b + 64] : 0u;      // the byte behind the lane's: across the word, the lane, the tile
+        uint32_t any = 0, top_bits = 0;
+        int top = -1;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            uint32_t cr, nl, fill;
+            const uint32_t bad = fq_bad_bits(w[i], &cr, &nl, &fill);
+            const unsigned next = i < 15 ? (w[i < 15 ? i + 1 : 15] & 0xffu) : behind;
+            uint32_t lone = (cr << 8) & ~nl;                   // a '\r' in bytes 0..2: the byte above it is no '\n'
+            if ((cr >> 31) && next != '\n') lone |= 1u;
+            any |= bad | lone;
+            const uint32_t fills = ~fill & 0x80808080u;
+            if (fills) { top = i; top_bits = fills; }
+        }
+        if (top >= 0) last1 = (unsigned long long)(b + 4 * top + ((31 - __clz(top_bits)) >> 3)) + 1;
+        if (any) (void)fq_class_bytes(text, n, line_start, n_nl, head, b, b + 64);
+    } else if (b < n) {
+        last1 = fq_class_bytes(text, n, line_start, n_nl, head, b, n);
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long v = __shfl_xor(last1, o);
+        last1 = v > last1 ? v : last1;
+    }
+    if ((threadIdx.x & 63) == 0) s_last[threadIdx.x >> 6] = last1;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long m = s_last[0];
+        for (int i = 1; i < KP_THREADS / 64; ++i) m = s_last[i] > m ? s_last[i] : m;
+        if (m) atomicMax(&head->last_off1, m);
+    }
+}
+
+__global__ void kfq_last(const long long *__restrict__ line_start, int64_t n_nl, FqHead *__restrict__ head) {
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        head->last_line = head->last_off1 ? (long long)fq_line_of(line_start, n_nl, (int64_t)head->last_off1 - 1) : -1;
+}
+
+__global__ __launch_bounds__(256) void kfq_records(FqArgs A) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= A.R) return;
+    int64_t b[4], e[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) fq_line_span(A.text, A.n_bytes, A.line_start, A.n_nl, A.n_lines, 4 * r + i, &b[i], &e[i]);
+    FqRecord rec;
+    const unsigned long long code = fq_record(A.text, r, b, e, &rec);
+    if (code) {
+        fq_flag(A.head, code);
+        rec.key_n = 0; rec.qual_n = 0;                         // (nothing behind this kernel runs on a declined text; the arrays are whole all the same)
+    }
+    A.key_b[r] = rec.key_b;
+    A.key_len1[r] = rec.key_n + 1;
+    A.qual_b[r] = rec.qual_b;
+    A.qual_n[r] = rec.qual_n;
+    A.pieces[r] = (rec.qual_n + FQ_PIECE - 1) / FQ_PIECE;
+    A.sum[r] = 0ull;
+}
+
+__global__ __launch_bounds__(256) void kfq_piecemap(FqArgs A) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= A.R) return;
+    const long long at = A.piece_off[r], k = A.pieces[r];
+    for (long long j = 0; j < k; ++j)
+        if (at + j < A.n_pieces) A.piece_rec[at + j] = (uint32_t)r;
+}
+
+__device__ __forceinline__ uint32_t fq_sum4(uint32_t w, uint32_t acc) {       // acc + the four bytes of w
+    return __builtin_amdgcn_sad_u8(w, 0u, acc);
+}
+
+// the bytes of the word at address `at` that lie in [s, e): the others zeroed
+__device__ __forceinline__ uint32_t fq_inside(uint32_t w, int64_t at, int64_t s, int64_t e) {
+    const int lo = (int)max((int64_t)0, min((int64_t)4, s - at)), hi = (int)max((int64_t)0, min((int64_t)4, e - at));
+    if (hi <= lo) return 0u;
+    const uint32_t below_hi = hi == 4 ? 0xffffffffu : (1u << (8 * hi)) - 1u;
+    const uint32_t below_lo = (1u << (8 * lo)) - 1u;           // (lo < hi <= 4: lo <= 3)
+    return w & below_hi & ~below_lo;
+}
+
+__global__ __launch_bounds__(256) void kfq_sum(FqArgs A) {
+    const int lane = threadIdx.x & 63;
+    const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);     // (the same for the whole wave)
+    if (p >= A.n_pieces) return;
+    const uint32_t r = A.piece_rec[p];
+    if ((int64_t)r >= A.R) return;
+    const int64_t j = p - A.piece_off[r];
+    const int64_t qb = A.qual_b[r], qn = A.qual_n[r];
+    const int64_t s = qb + j * FQ_PIECE;
+    const int64_t e = min(s + (int64_t)FQ_PIECE, qb + qn);
+    if (j < 0 || s >= e || e > A.n_bytes) return;              // (cannot be: the scan counted these pieces)
+    uint32_t acc = 0;
+    // whole 16-byte groups from the aligned address at or below s: the text's buffer begins aligned and is padded behind its end
+    for (int64_t a = (s & ~(int64_t)15) + (int64_t)lane * 16; a < e; a += 64 * 16) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(A.text + a);
+        if (a >= s && a + 16 <= e) {
+            acc = fq_sum4(v.x, acc); acc = fq_sum4(v.y, acc); acc = fq_sum4(v.z, acc); acc = fq_sum4(v.w, acc);
+        } else {                                               // the piece's unaligned head or tail
+            acc = fq_sum4(fq_inside(v.x, a, s, e), acc); acc = fq_sum4(fq_inside(v.y, a + 4, s, e), acc);
+            acc = fq_sum4(fq_inside(v.z, a + 8, s, e), acc); acc = fq_sum4(fq_inside(v.w, a + 12, s, e), acc);
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);       // (a piece's bytes sum to less than 2^21)
+    if (lane == 0) atomicAdd(&A.sum[r], (unsigned long long)acc);
+}
+
+__global__ __launch_bounds__(256) void kfq_finish(FqArgs A) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= A.R) return;
+    A.mean[r] = fq_mean((uint64_t)A.sum[r], (int64_t)A.qual_n[r]);
+}
+
+__global__ __launch_bounds__(256) void kfq_keys(FqArgs A) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r == 0) A.key_off[A.R] = A.head->pool_bytes;
+    if (r >= A.R) return;
+    const long long at = A.key_off[r], k = A.key_len1[r] - 1;
+    if (at < 0 || at + k + 1 > A.head->pool_bytes) return;     // (cannot be: the scan counted these bytes)
+    const char *src = A.text + A.key_b[r];
+    for (long long i = 0; i < k; ++i) A.pool[at + i] = src[i];
+    A.pool[at + k] = '\n';
+}
+
+double fq_ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+int fq_decline(mc_ctx *c, int32_t *status, int reason, long long line) {
+    c->fq_stats.decline_reason = reason;
+    c->fq_stats.decline_line = line;
+    if (line >= 0) mc_set_error("the device reader declines: %s (line %lld)", fq_reason_text(reason), line + 1);
+    else mc_set_error("the device reader declines: %s", fq_reason_text(reason));
+    *status = 1;
+    return 0;
+}
+
+int fq_decline_head(mc_ctx *c, int32_t *status, const FqHead &h) {
+    return fq_decline(c, status, (int)(h.decline & 0xff), (long long)(h.decline >> 8));
+}
+
+// does `bytes` more fit into device memory, with a margin for what the runtime and the other buffers of the context take
+bool fq_fits(size_t bytes) {
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return false; }
+    const size_t margin = (size_t)256 << 20;
+    return free_b > margin && bytes <= free_b - margin;
+}
+
+int fq_grow(Pinned &p, size_t &cap, size_t bytes) {
+    if (cap >= bytes) return 0;
+    cap = 0;
+    if (int rc = p.alloc(bytes + bytes / 4)) return rc;
+    cap = bytes + bytes / 4;
+    return 0;
+}
+
+// The text is on the device (d_text[0, n), its buffer aligned and padded; copies enqueued on c->up_stream): everything behind that
+int fq_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, mc_fastq_quality_view *V, int32_t *status) {
+    mc_fastq_quality_stats &S = c->fq_stats;
+    hipStream_t st = c->stream;
+    HIP_TRY(hipStreamSynchronize(c->up_stream));
+    const auto t_kernels = std::chrono::steady_clock::now();
+    if (n == 0) return 0;                                     // no line, no record: an empty file
+    FqHead *d_head = nullptr, h = {};
+    if (pool.get(&d_head, 1)) return -10;
+    h.decline = FQ_NO_DECLINE;
+    h.last_line = -1;
+    HIP_TRY(hipMemcpyAsync(d_head, &h, sizeof h, hipMemcpyHostToDevice, st));
+    const int64_t n_tiles = (n + KP_TILE - 1) / KP_TILE;
+    long long *tile_cnt = nullptr, *tile_off = nullptr;
+    if (pool.get(&tile_cnt, (size_t)n_tiles) || pool.get(&tile_off, (size_t)n_tiles)) return -10;
+    hipLaunchKernelGGL(kp_count, dim3((unsigned)n_tiles), dim3(KP_THREADS), 0, st, d_text, n, tile_cnt);
+    hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)tile_cnt, n_tiles, tile_off, &d_head->kp.n_newlines);
+    HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int64_t n_nl = h.kp.n_newlines;
+    if (n_nl + 1 >= ((int64_t)1 << 31) - 2) return fq_decline(c, status, MC_FASTQ_DECLINE_ROWS, -1);
+    const int64_t cap_lines = n_nl + 2;
+    if (!fq_fits((size_t)cap_lines * 8 + ((size_t)1 << 20))) return fq_decline(c, status, MC_FASTQ_DECLINE_MEMORY, -1);
+    long long *line_start = nullptr;
+    if (pool.get(&line_start, (size_t)cap_lines)) return -10;
+    hipLaunchKernelGGL(kp_starts, dim3((unsigned)n_tiles), dim3(KP_THREADS), 0, st, d_text, n, (const long long *)tile_off, line_start,
+                       cap_lines, &d_head->kp);
+    hipLaunchKernelGGL(kfq_class, dim3((unsigned)n_tiles), dim3(KP_THREADS), 0, st, d_text, n, (const long long *)line_start, n_nl, d_head);
+    hipLaunchKernelGGL(kfq_last, dim3(1), dim3(64), 0, st, (const long long *)line_start, n_nl, d_head);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    S.n_lines = h.kp.n_lines;
+    const int64_t R = h.last_line < 0 ? 0 : h.last_line / 4 + 1;
+    if (R == 0) {                                             // nothing but blanks, tabs and line breaks -- or bytes that decline
+        if (h.decline != FQ_NO_DECLINE) return fq_decline_head(c, status, h);
+        S.ms_kernels = fq_ms_since(t_kernels);
+        return 0;
+    }
+    FqArgs A = {};
+    A.text = d_text; A.n_bytes = n; A.n_lines = h.kp.n_lines; A.n_nl = n_nl; A.R = R; A.line_start = line_start; A.head = d_head;
+    const size_t nr = (size_t)R;
+    if (!fq_fits(nr * 80 + ((size_t)1 << 20))) return fq_decline(c, status, MC_FASTQ_DECLINE_MEMORY, -1);
+    if (pool.get(&A.key_b, nr) || pool.get(&A.key_len1, nr) || pool.get(&A.qual_b, nr) || pool.get(&A.qual_n, nr) || pool.get(&A.pieces, nr) ||
+        pool.get(&A.piece_off, nr) || pool.get(&A.key_off, nr + 1) || pool.get(&A.sum, nr) || pool.get(&A.mean, nr))
+        return -10;
+    const unsigned rb = (unsigned)((R + 255) / 256);
+    hipLaunchKernelGGL(kfq_records, dim3(rb), dim3(256), 0, st, A);
+    hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)A.pieces, R, A.piece_off, &d_head->n_pieces);
+    hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)A.key_len1, R, A.key_off, &d_head->pool_bytes);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (h.decline != FQ_NO_DECLINE) return fq_decline_head(c, status, h);
+    A.n_pieces = h.n_pieces;
+    S.n_records = R;
+    S.n_pieces = h.n_pieces;
+    const size_t np = (size_t)h.n_pieces, pb = (size_t)h.pool_bytes;
+    if (!fq_fits(np * 4 + pb + ((size_t)1 << 20))) return fq_decline(c, status, MC_FASTQ_DECLINE_MEMORY, -1);
+    if (pool.get(&A.piece_rec, np) || pool.get(&A.pool, pb)) return -10;
+    if (np > 0) {
+        hipLaunchKernelGGL(kfq_piecemap, dim3(rb), dim3(256), 0, st, A);
+        hipLaunchKernelGGL(kfq_sum, dim3((unsigned)((np + 3) / 4)), dim3(256), 0, st, A);
+    }
+    hipLaunchKernelGGL(kfq_finish, dim3(rb), dim3(256), 0, st, A);
+    hipLaunchKernelGGL(kfq_keys, dim3(rb), dim3(256), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    S.ms_kernels = fq_ms_since(t_kernels);
+    const auto t_d2h = std::chrono::steady_clock::now();
+    if (int rc = fq_grow(c->fq_pool, c->fq_pool_cap, pb)) return rc;
+    if (int rc = fq_grow(c->fq_off, c->fq_off_cap, (nr + 1) * 8)) return rc;
+    if (int rc = fq_grow(c->fq_mean, c->fq_mean_cap, nr * 8)) return rc;
+    HIP_TRY(hipMemcpyAsync(c->fq_pool.p, A.pool, pb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(c->fq_off.p, A.key_off, (nr + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(c->fq_mean.p, A.mean, nr * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    S.ms_d2h = fq_ms_since(t_d2h);
+    V->key_pool = c->fq_pool.get<char>();
+    V->key_off = c->fq_off.get<int64_t>();
+    V->mean = c->fq_mean.get<double>();
+    V->n_records = R;
+    return 0;
+}
+
+// what both entry points begin with -> 0: go on; 1: done (declined, *status set)
+int fq_begin(mc_ctx *c, mc_fastq_quality_view *V, int32_t *status, int64_t n) {
+    c->fq_stats = mc_fastq_quality_stats();
+    c->fq_stats.decline_line = -1;
+    c->fq_stats.n_bytes = n;
+    c->fq_stats.piece_bytes = FQ_PIECE;
+    *V = mc_fastq_quality_view();
+    *status = 0;
+    if (!fq_fits((size_t)n + 4096)) { (void)fq_decline(c, status, MC_FASTQ_DECLINE_MEMORY, -1); return 1; }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int mc_fastq_quality_text(mc_ctx *c, const char *text, int64_t n_bytes, mc_fastq_quality_view *out, int32_t *status) {
+    if (!c || !out || !status || n_bytes < 0 || (n_bytes > 0 && !text)) {
+        mc_set_error("mc_fastq_quality_text: bad arguments");
+        return -12;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    if (fq_begin(c, out, status, n_bytes)) return 0;
+    Pool pool("fastq qualities");
+    char *d_text = nullptr;
+    if (pool.get(&d_text, (size_t)n_bytes + 64)) return -10;
+    if (n_bytes > 0) HIP_TRY(hipMemcpyAsync(d_text, text, (size_t)n_bytes, hipMemcpyHostToDevice, c->up_stream));
+    HIP_TRY(hipMemsetAsync(d_text + n_bytes, 0, 64, c->up_stream));
+    HIP_TRY(hipStreamSynchronize(c->up_stream));
+    c->fq_stats.ms_h2d = fq_ms_since(t0);
+    const int rc = fq_run(c, pool, d_text, n_bytes, out, status);
+    (void)hipStreamSynchronize(c->stream);                   // (an early return: nothing of the pool is in use when it goes)
+    if (rc != 0 || *status != 0) *out = mc_fastq_quality_view();
+    c->fq_stats.ms_total = fq_ms_since(t0);
+    return rc;
+}
+
+extern "C" int mc_fastq_quality_file(mc_ctx *c, const char *path, mc_fastq_quality_view *out, int32_t *status) {
+    if (!c || !path || !out || !status) {
+        mc_set_error("mc_fastq_quality_file: bad arguments");
+        return -12;
+    }
+    struct stat sb;
+    if (stat(path, &sb) != 0 || !S_ISREG(sb.st_mode)) {
+        mc_set_error("mc_fastq_quality_file: %s is not a readable file", path);
+        return -1;
+    }
+    const int64_t n = (int64_t)sb.st_size;
+    HIP_TRY(hipSetDevice(c->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    if (fq_begin(c, out, status, n)) return 0;
+    Pool pool("fastq qualities");
+    char *d_text = nullptr;
+    if (pool.get(&d_text, (size_t)n + 64)) return -10;
+    // the file in blocks, two pinned stages in turn: block i is read while block i - 1 is on its way
+    const size_t block = (size_t)std::min<int64_t>(std::max<int64_t>(n, 4096), (int64_t)32 << 20);
+    if (c->fq_stage_cap < block) {
+        c->fq_stage_cap = 0;
+        for (Pinned &p : c->fq_stage)
+            if (int rc = p.alloc(block)) return rc;
+        c->fq_stage_cap = block;
+    }
+    for (Event &e : c->fq_ev)
+        if (!e.e)
+            if (int rc = e.create()) return rc;
+    double ms_read = 0;
+    int rc = 0, turn = 0;
+    for (int64_t lo = 0; lo < n && rc == 0; lo += (int64_t)c->fq_stage_cap, turn ^= 1) {
+        const int64_t hi = std::min<int64_t>(n, lo + (int64_t)c->fq_stage_cap);
+        if (lo >= 2 * (int64_t)c->fq_stage_cap) HIP_TRY(hipEventSynchronize(c->fq_ev[turn]));     // the copy out of this stage is done
+        const auto tr = std::chrono::steady_clock::now();
+        rc = mc_read_file_range(path, lo, hi, c->fq_stage[turn].get<char>(), 0);
+        ms_read += fq_ms_since(tr);
+        if (rc) break;
+        HIP_TRY(hipMemcpyAsync(d_text + lo, c->fq_stage[turn].p, (size_t)(hi - lo), hipMemcpyHostToDevice, c->up_stream));
+        HIP_TRY(hipEventRecord(c->fq_ev[turn], c->up_stream));
+    }
+    HIP_TRY(hipMemsetAsync(d_text + n, 0, 64, c->up_stream));
+    HIP_TRY(hipStreamSynchronize(c->up_stream));
+    if (rc) return rc;
+    c->fq_stats.ms_read = ms_read;
+    c->fq_stats.ms_h2d = fq_ms_since(t0) - ms_read;          // what the copies added behind the reads they ran beside
+    rc = fq_run(c, pool, d_text, n, out, status);
+    (void)hipStreamSynchronize(c->stream);
+    if (rc != 0 || *status != 0) *out = mc_fastq_quality_view();
+    c->fq_stats.ms_total = fq_ms_since(t0);
+    return rc;
+}
+
+extern "C" int mc_fastq_quality_last_stats(mc_ctx *c, mc_fastq_quality_stats *out) {
+    if (!c || !out) { mc_set_error("mc_fastq_quality_last_stats: bad arguments"); return -12; }
+    *out = c->fq_stats;
+    return 0;
+}
+
+extern "C" int mc_fastq_quality_release(mc_ctx *c) {
+    if (!c) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipStreamSynchronize(c->up_stream));
+    c->fq_pool.reset(); c->fq_pool_cap = 0;
+    c->fq_off.reset(); c->fq_off_cap = 0;
+    c->fq_mean.reset(); c->fq_mean_cap = 0;
+    for (Pinned &p : c->fq_stage) p.reset();
+    c->fq_stage_cap = 0;
+    return 0;
+}

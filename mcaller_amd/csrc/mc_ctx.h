@@ -312,6 +312,14 @@ struct mc_ctx {
     size_t mg_stage_cap = 0;
     Event mg_ev[2];
     mc_rows_merge_stats mg_stats = {};
+    // the read qualities of a FASTQ file (fastq/mc_fastqual.hip): the result handed out last (keys, offsets and means in pinned
+    // memory), the file reader's two pinned blocks with their events, the figures of the last call
+    Pinned fq_pool, fq_off, fq_mean;
+    size_t fq_pool_cap = 0, fq_off_cap = 0, fq_mean_cap = 0;
+    Pinned fq_stage[2];
+    size_t fq_stage_cap = 0;
+    Event fq_ev[2];
+    mc_fastq_quality_stats fq_stats = {};
 };
 
 // ---- what crosses the units ----

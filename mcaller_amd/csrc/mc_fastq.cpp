@@ -12,6 +12,7 @@
 // Any irregularity (error, failed resynchronisation) reruns the whole buffer on one thread so that the first error in
 // file order is the one reported.
 #include "../../include/mcaller_hip.h"
+#include "mc_fastqrec.h"
 
 #include <dlfcn.h>
 #include <fcntl.h>
@@ -19,6 +20,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -246,3 +248,79 @@ extern "C" int64_t mc_fastq_view(const mc_fastq *f, const char **key_pool, const
 }
 
 extern "C" void mc_fastq_free(mc_fastq *f) { delete f; }
+
+// ---- the record rules of mc_fastqrec.h run line by line, without a GPU: what the device reader (fastq/mc_fastqual.hip) is held against ----
+namespace {
+thread_local int32_t fq_host_reason = 0;
+thread_local int64_t fq_host_line = -1;
+}  // namespace
+
+extern "C" int mc_fastq_records_host(const char *text, int64_t n_bytes, mc_fastq **out, int32_t *status) {
+    if (!out || !status || n_bytes < 0 || (n_bytes > 0 && !text)) { mc_set_error("mc_fastq_records_host: bad arguments"); return -12; }
+    *out = nullptr;
+    *status = 0;
+    fq_host_reason = 0;
+    fq_host_line = -1;
+    std::vector<int64_t> line_start(1, 0);
+    for (int64_t i = 0; i < n_bytes; ++i)
+        if (text[i] == '\n') line_start.push_back(i + 1);
+    const int64_t n_nl = int64_t(line_start.size()) - 1;
+    const int64_t n_lines = n_bytes > 0 ? n_nl + (text[n_bytes - 1] != '\n' ? 1 : 0) : 0;
+    unsigned long long decline = FQ_NO_DECLINE;
+    if (n_nl + 1 >= (int64_t(1) << 31) - 2) decline = fq_code(0, MC_FASTQ_DECLINE_ROWS);
+    int64_t last_off = -1, line = 0;
+    for (int64_t i = 0; i < n_bytes && decline == FQ_NO_DECLINE; ++i) {      // (the lines rise with i: the first code is the smallest of its line ...)
+        const unsigned c = (unsigned char)text[i];
+        if (const int reason = fq_byte_reason(c, i + 1 < n_bytes ? (unsigned char)text[i + 1] : -1)) {
+            decline = fq_code(line, reason);
+            for (int64_t j = i + 1; j < n_bytes && text[j] != '\n'; ++j)     // (... but for a smaller reason further along it)
+                if (const int other = fq_byte_reason((unsigned char)text[j], j + 1 < n_bytes ? (unsigned char)text[j + 1] : -1))
+                    decline = std::min(decline, fq_code(line, other));
+        }
+        if (!fq_blank(c) && c != '\r' && c != '\n') last_off = i;
+        if (c == '\n') ++line;
+    }
+    if (decline != FQ_NO_DECLINE && (decline & 0xff) != MC_FASTQ_DECLINE_ROWS)
+        for (int64_t i = 0; i < n_bytes; ++i) {                              // (the scan stopped early: the last line with a byte that fills)
+            const unsigned c = (unsigned char)text[i];
+            if (!fq_blank(c) && c != '\r' && c != '\n') last_off = i;
+        }
+    const int64_t R = last_off < 0 ? 0 : fq_line_of(line_start.data(), n_nl, last_off) / 4 + 1;
+    mc_fastq *f = new mc_fastq();
+    f->off.reserve(size_t(R) + 1);
+    f->mean.reserve(size_t(R));
+    for (int64_t r = 0; r < R && (decline & 0xff) != MC_FASTQ_DECLINE_ROWS; ++r) {
+        int64_t b[4], e[4];
+        for (int i = 0; i < 4; ++i) fq_line_span(text, n_bytes, line_start.data(), n_nl, n_lines, 4 * r + i, &b[i], &e[i]);
+        FqRecord rec;
+        if (const unsigned long long code = fq_record(text, r, b, e, &rec)) {
+            decline = std::min(decline, code);
+            break;                                                           // (the records rise too: a later one names a later line)
+        }
+        if ((decline >> 8) < (unsigned long long)(4 * r + 4)) break;         // a byte's decline in front of every record still to come
+        uint64_t sum = 0;
+        for (int64_t i = 0; i < rec.qual_n; ++i) sum += (unsigned char)text[rec.qual_b + i];
+        f->off.push_back(int64_t(f->pool.size()));
+        f->pool.append(text + rec.key_b, size_t(rec.key_n));
+        f->pool.push_back('\n');
+        f->mean.push_back(fq_mean(sum, rec.qual_n));
+    }
+    if (decline != FQ_NO_DECLINE) {
+        delete f;
+        fq_host_reason = int32_t(decline & 0xff);
+        fq_host_line = fq_host_reason == MC_FASTQ_DECLINE_ROWS ? -1 : int64_t(decline >> 8);
+        if (fq_host_line >= 0) mc_set_error("the device reader declines: %s (line %lld)", fq_reason_text(fq_host_reason), (long long)fq_host_line + 1);
+        else mc_set_error("the device reader declines: %s", fq_reason_text(fq_host_reason));
+        *status = 1;
+        return 0;
+    }
+    f->off.push_back(int64_t(f->pool.size()));
+    *out = f;
+    return 0;
+}
+
+extern "C" int mc_fastq_records_host_decline(int32_t *reason, int64_t *line) {
+    if (reason) *reason = fq_host_reason;
+    if (line) *line = fq_host_line;
+    return 0;
+}

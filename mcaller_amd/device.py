@@ -823,6 +823,35 @@ class Device(object):
     def training_rows_release(self):
         check(lib().mc_train_rows_release(self._ctx))
 
+    # ---- the read qualities of a FASTQ file (csrc/fastq/mc_fastqual.hip) ----
+    @_serialized
+    def fastq_qualities(self, path=None, text=None):
+        """One (key, mean phred) pair per record of a FASTQ file (`path`) or its text (`text`, bytes), made on the GPU
+        -> (keys: list of str, means: float64 [n], None) -- copies, the caller's own --, or (None, None, reason) when the device
+        declines: the caller runs the host reader."""
+        if (path is None) == (text is None):
+            raise ValueError('fastq_qualities: a path or a text')
+        view, status = _lib.FastqQualityView(), C.c_int32()
+        if path is not None:
+            check(lib().mc_fastq_quality_file(self._ctx, os.fsencode(path), C.byref(view), C.byref(status)))
+        else:
+            text = bytes(text)
+            check(lib().mc_fastq_quality_text(self._ctx, text, len(text), C.byref(view), C.byref(status)))
+        if status.value != 0:
+            return None, None, lib().mc_last_error().decode('utf-8', 'replace')
+        return _lib.fastq_unpack(view.key_pool, view.key_off, view.mean, int(view.n_records)) + (None,)
+
+    @_serialized
+    def fastq_qualities_last_stats(self):
+        """Figures of the last fastq_qualities: bytes, lines, records, pieces and their size, the decline, milliseconds."""
+        st = _lib.FastqQualityStats()
+        check(lib().mc_fastq_quality_last_stats(self._ctx, C.byref(st)))
+        return {name: getattr(st, name) for name, _ in st._fields_}
+
+    @_serialized
+    def fastq_qualities_release(self):
+        check(lib().mc_fastq_quality_release(self._ctx))
+
     @_serialized
     def mlp_forward(self, X, submodel):
         if getattr(self, '_clf', 'mlp') != 'mlp':

@@ -12,7 +12,7 @@ import sys
 assert sys.version_info >= (3, 0), 'please use python3'
 
 from .extract_contexts import extract_features
-from .read_qual import extract_read_quality
+from .read_qual import extract_read_quality, read_qualities      # noqa: F401 (extract_read_quality: the package's listed entry point)
 from .refmark import read_fasta
 
 
@@ -242,7 +242,7 @@ def main(argv=None):
 
     def qualities():
         try:
-            box['r2q'] = extract_read_quality(args.fastq)
+            box['r2q'] = read_qualities(args.fastq)
         except BaseException as e:                                   # noqa
             box['err'] = e
     th = threading.Thread(target=qualities)

@@ -123,8 +123,8 @@ def _job(conn, device, job, cache):
     if read2qual is None:                 # (every worker reads the FASTQ itself, natively: a pickled dict per worker costs more)
         key = ('fastq', job['fastq'], os.path.getmtime(job['fastq']), os.path.getsize(job['fastq']))
         if cache.get('fastq_key') != key:
-            from .read_qual import extract_read_quality
-            cache['fastq_key'], cache['read2qual'] = key, extract_read_quality(job['fastq'])
+            from .read_qual import read_qualities
+            cache['fastq_key'], cache['read2qual'] = key, read_qualities(job['fastq'])
         read2qual = cache['read2qual']
     train = bool(job.get('train'))
     modelset = None if train else load_model_file(job['modelfile'])      # (train mode: features only, :131-134)
