@@ -165,6 +165,7 @@ __global__ __launch_bounds__(FT) void k4_mlp_fit(FitArgs A) {
         const double bound_h = sqrt(6.0 / (double)(d + H)), bound_o = sqrt(6.0 / (double)(H + 1));
         const double *init = A.init ? A.init + (size_t)job * ((size_t)d * H + 2 * (size_t)H + 1) : nullptr;
         auto start = [&](unsigned long long idx, double bound) -> double {
+#pragma clang fp contract(off)     // the product rounded, then the sum, as init_weights rounds them: one fma gives another last bit on some weights
             return init ? init[idx] : -bound + 2.0 * bound * uniform01(J.seed, idx);
         };
 #pragma unroll

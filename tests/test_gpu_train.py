@@ -55,7 +55,8 @@ def test_seeded_fits_equal_the_oracle(dev):
         want = mo.fit(X[tr], y[tr], hidden=100, max_iter=25, seed=seeds[j])
         assert got[j]['n_iter'] == want['n_iter'] == 25
         np.testing.assert_allclose(got[j]['loss_curve'], want['loss_curve'], rtol=1e-7)
-        np.testing.assert_allclose(got[j]['W1'], want['W1'], rtol=1e-5, atol=1e-7)
+        for k in ('W1', 'b1', 'W2', 'b2'):
+            np.testing.assert_allclose(got[j][k], want[k], rtol=1e-5, atol=1e-7, err_msg=k)
         if len(va):
             assert abs(got[j]['val_correct'] - round(mo.accuracy(want, X[va], y[va]) * len(va))) <= 1
             assert got[j]["val_correct"] > 0.6 * len(va)          # better than chance after 25 epochs
@@ -86,11 +87,14 @@ def test_more_fits_than_xcds_and_repeatability(dev):
     for j in (0, 5, 10):
         want = mo.fit(X[jobs[j][0]], y[jobs[j][0]], hidden=100, max_iter=12, seed=seeds[j])
         np.testing.assert_allclose(got[j]['loss_curve'], want['loss_curve'], rtol=1e-7)
-        np.testing.assert_allclose(got[j]['W1'], want['W1'], rtol=1e-5, atol=1e-7)
+        for k in ('W1', 'b1', 'W2', 'b2'):
+            np.testing.assert_allclose(got[j][k], want[k], rtol=1e-5, atol=1e-7, err_msg=k)
     for j in range(11):
         assert np.array_equal(got[j]['W1'], again[j]['W1']) and np.array_equal(got[j]['loss_curve'], again[j]['loss_curve'])
-    # (the library reads MCALLER_FIT_WGS once per process: other group sizes are exercised by tools/config5.py runs under that
-    # variable -- profiles/README.md -- and by the build macro MC_FIT_GROUPS)
+        assert all(np.array_equal(got[j][k], again[j][k]) for k in ('b1', 'W2', 'b2'))
+    # (the library reads MCALLER_FIT_WGS once per process: one workgroup per fit, the switch at batch_size 64 and the group sizes 1, 2
+    # and 8 under that variable, in processes of their own, are in tests/test_gpu_mlp_fit_shapes.py; the build macro MC_FIT_GROUPS
+    # is exercised by tools/config5.py runs only -- profiles/README.md)
 
 
 def test_bad_parameters_raise_and_never_fault(dev):
