@@ -118,6 +118,28 @@ int mc_host_cores(void);
 int mc_mark_motifs(const char *seq, int64_t n, const char *motif_fwd, const char *repl_fwd, int32_t m_fwd,
                    const char *motif_rev, const char *repl_rev, int32_t m_rev, char *upper_out, char *fwd_out, char *rev_out);
 
+/* ===== degenerate (IUPAC) motifs, several at once (--motifs; the rule: csrc/mc_iupac.h) =====
+ * One motif of one strand: letter i as a set over A, C, G, T (bits 1, 2, 4, 8), bit j of `called`: letter j is marked. */
+#define MC_IUPAC_MAX_MOTIFS 8
+#define MC_IUPAC_MAX_LEN 32
+typedef struct mc_iupac_motif {
+    int32_t m;                            /* 1 .. MC_IUPAC_MAX_LEN letters */
+    uint32_t called;
+    uint8_t set[MC_IUPAC_MAX_LEN];
+} mc_iupac_motif;
+typedef struct mc_iupac_spec {
+    int32_t n_motifs, pad;                /* 1 .. MC_IUPAC_MAX_MOTIFS */
+    mc_iupac_motif fwd[MC_IUPAC_MAX_MOTIFS];    /* what is looked for on the forward sequence for the '+' strand ...      */
+    mc_iupac_motif rev[MC_IUPAC_MAX_MOTIFS];    /* ... and for the '-' strand: the reverse complements, offsets mirrored */
+} mc_iupac_spec;
+/* Appends a motif (upper-case IUPAC letters; bit j of called: letter j is marked) to the spec, both strands' tables; a spec
+ * starts zero-filled. */
+int mc_iupac_spec_add(mc_iupac_spec *spec, const char *motif, int32_t m, uint32_t called);
+/* The marking of a contig for a spec, sequentially and without the interpreter lock: upper_out = seq upper-cased (ASCII),
+ * fwd_out / rev_out = upper_out with 'M' at every called letter of every occurrence (overlapping ones included) of the
+ * spec's motifs / of their reverse complements; all buffers n bytes. */
+int mc_mark_iupac(const char *seq, int64_t n, const mc_iupac_spec *spec, char *upper_out, char *fwd_out, char *rev_out);
+
 /* ===== pinned host memory, recycled =====
  * The DMA engines read a table at PCIe speed, beside running kernels, only from pinned memory.  Blocks handed back with
  * mc_host_free are kept (up to keep_bytes of idle memory) and handed out again: pinning costs page-table work per page, a
@@ -187,6 +209,11 @@ int mc_ctx_set_reference(mc_ctx *ctx, const mc_ref_view *host_ref);          /* 
  * would with every contig marked (mc_ctx_fetch_reference copies it back: the parity tests). */
 int mc_ctx_set_reference_motif(mc_ctx *ctx, const mc_ref_view *host_ref, const char *motif_fwd, const char *repl_fwd, int32_t m_fwd,
                                const char *motif_rev, const char *repl_rev, int32_t m_rev);
+/* The same for a set of degenerate motifs (csrc/mc_iupac.h: every occurrence counts, a literal 'M' of the sequence stays a
+ * mark on both strands): host_ref as above, with ceil(contig_len / 32) + 2 mask words per contig and the contigs' bases inside
+ * seq[0, n_seq_bytes); spec: mc_iupac_spec_add.  Leaves the device reference exactly as mc_ctx_set_reference would with
+ * every contig marked by mc_mark_iupac. */
+int mc_ctx_set_reference_iupac(mc_ctx *ctx, const mc_ref_view *host_ref, const mc_iupac_spec *spec);
 int mc_ctx_fetch_reference(mc_ctx *ctx, uint8_t *seq, int64_t n_seq_bytes, uint32_t *mbits_fwd, uint32_t *mbits_rev,
                            int32_t *rank_fwd, int32_t *rank_rev, int64_t n_words, int64_t *site_base, int64_t *n_sites);
 int mc_ctx_upload_table(mc_ctx *ctx, const mc_table_view *host_table);        /* H2D of the columns; returns when done */

@@ -40,6 +40,16 @@ class RefView(C.Structure):
                 ('n_seq_bytes', C.c_int64), ('n_words', C.c_int64)]
 
 
+class IupacMotif(C.Structure):
+    """mc_iupac_motif (include/mcaller_hip.h)."""
+    _fields_ = [('m', C.c_int32), ('called', C.c_uint32), ('set', C.c_uint8 * 32)]
+
+
+class IupacSpec(C.Structure):
+    """mc_iupac_spec (include/mcaller_hip.h)."""
+    _fields_ = [('n_motifs', C.c_int32), ('pad', C.c_int32), ('fwd', IupacMotif * 8), ('rev', IupacMotif * 8)]
+
+
 class DevParseResult(C.Structure):
     """mc_devparse_result (include/mcaller_hip.h)."""
     _fields_ = [('status', C.c_int32), ('n_lines', C.c_int64), ('n_rows', C.c_int64), ('n_seg', C.c_int32), ('n_unknown', C.c_int32),
@@ -202,6 +212,9 @@ def lib():
                                      C.c_void_p, C.c_void_p, C.c_void_p]
         L.mc_ctx_set_reference_motif.argtypes = [C.c_void_p, C.POINTER(RefView), C.c_char_p, C.c_char_p, C.c_int32, C.c_char_p, C.c_char_p,
                                                  C.c_int32]
+        L.mc_iupac_spec_add.argtypes = [C.POINTER(IupacSpec), C.c_char_p, C.c_int32, C.c_uint32]
+        L.mc_mark_iupac.argtypes = [C.c_char_p, C.c_int64, C.POINTER(IupacSpec), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mc_ctx_set_reference_iupac.argtypes = [C.c_void_p, C.POINTER(RefView), C.POINTER(IupacSpec)]
         L.mc_ctx_fetch_reference.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                              C.c_void_p, C.POINTER(C.c_int64)]
         L.mc_read_file_range.argtypes = [C.c_char_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32]

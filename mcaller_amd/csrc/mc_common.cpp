@@ -1,5 +1,6 @@
 // Error text, version, host core count and the pinned host buffer pool of libmcaller_hip.so (C ABI: include/mcaller_hip.h).
 #include "../../include/mcaller_hip.h"
+#include "mc_iupac.h"
 
 #include <hip/hip_runtime_api.h>
 #include <sched.h>
@@ -292,7 +293,36 @@ extern "C" int mc_mark_motifs(const char *seq, int64_t n, const char *motif_fwd,
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Worker threads, kept and PINNED.  The parser, the FASTQ reader and the row formatter run one task per piece of their input;
+// The same for a set of degenerate motifs (--motifs): the rule of mc_iupac.h run sequentially, the two strands side by side.
+// What the device makes as masks (k_mark_iupac) this makes as strings: the one-table path, contigs the device path does not
+// cover, and the strings the host formatter slices contexts from.
+// ---------------------------------------------------------------------------------------------------
+extern "C" int mc_iupac_spec_add(mc_iupac_spec *spec, const char *motif, int32_t m, uint32_t called) {
+    if (!spec || !motif || spec->n_motifs < 0 || spec->n_motifs >= MC_IUPAC_MAX_MOTIFS || iu_set_entry(spec, spec->n_motifs, motif, m, called)) {
+        mc_set_error("mc_iupac_spec_add: at most %d motifs of 1..%d IUPAC letters, at least one of them called", MC_IUPAC_MAX_MOTIFS,
+                     MC_IUPAC_MAX_LEN);
+        return -12;
+    }
+    spec->n_motifs += 1;
+    return 0;
+}
+
+extern "C" int mc_mark_iupac(const char *seq, int64_t n, const mc_iupac_spec *spec, char *upper_out, char *fwd_out, char *rev_out) {
+    if (!seq || n < 0 || !upper_out || !fwd_out || !rev_out || !iu_spec_ok(spec)) {
+        mc_set_error("mc_mark_iupac: bad arguments");
+        return -12;
+    }
+    for (int64_t i = 0; i < n; ++i) upper_out[i] = (char)iu_upper((unsigned char)seq[i]);
+    mc_parallel_for(2, [&](int strand) {
+        char *out = strand ? rev_out : fwd_out;
+        memcpy(out, upper_out, (size_t)n);
+        iu_mark_strand(strand ? spec->rev : spec->fwd, spec->n_motifs, (const uint8_t *)upper_out, n, out);
+    });
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Worker threads, kept and PINNED. The parser, the FASTQ reader and the row formatter run one task per piece of their input;
 // a file streamed in shards calls them once per shard, and starting a few dozen std::threads per call (one at a time, by the
 // caller) was half a shard's parse time.  mc_parallel_for hands the tasks to threads that stay around: one per CPU the
 // process may run on, each bound to its CPU.  The binding is the point: threads that are merely woken (condition variable,

@@ -253,6 +253,75 @@ __global__ __launch_bounds__(256) void k_mark_ranks(const long long *__restrict_
     if (w == 0) { site_base[2 * ci] = f0; site_base[2 * ci + 1] = r0; }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// The site masks of a set of degenerate motifs (mc_ctx_set_reference_iupac; the rule: mc_iupac.h).  k_mark_words compares bytes,
+// up to 32 x m x m per lane, and knows one literal motif; here the bases become bit-planes once and a motif is matched 96
+// positions at a time: starts = AND over its letters of (the letter set's plane >> i), marks = OR over the called j of
+// (starts << j).  kp_scan and k_mark_ranks follow as they do behind k_mark_words.
+// ---------------------------------------------------------------------------------------------------
+constexpr int IU_PLANES = 5;        // A, C, G, T, and the literal 'M' of the sequence: plane k is planes[k * n_words, (k + 1) * n_words)
+
+// A wave takes 64 bases per step -- two mask words, each half of the wave one (they may lie in two contigs) --, writes the
+// upper-cased bytes and, by ballots, the planes on the masks' own word grid (word_off, pad words included).  Past a contig's
+// length the planes are zero: nothing matches across a contig end.
+__global__ __launch_bounds__(256) void k_ref_planes(const uint8_t *__restrict__ raw, uint8_t *__restrict__ seq,
+                                                    const int64_t *__restrict__ contig_len, const int64_t *__restrict__ seq_off,
+                                                    const int64_t *__restrict__ word_off, int n_contigs, int64_t n_words,
+                                                    uint32_t *__restrict__ planes) {
+    const int lane = threadIdx.x & 63, half = lane >> 5, bit = lane & 31;
+    const int64_t n_steps = (n_words + 1) / 2;
+    const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t step = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; step < n_steps; step += n_waves) {      // (uniform in the wave)
+        const int64_t gw = 2 * step + half;
+        unsigned ch = 0;
+        if (gw < n_words) {
+            const int ci = mark_contig_of_word(word_off, n_contigs, gw);
+            const int64_t p = 32 * (gw - word_off[ci]) + bit;
+            if (p < contig_len[ci]) {
+                const int64_t at = seq_off[ci] + p;
+                ch = iu_upper(raw[at]);
+                seq[at] = (uint8_t)ch;
+            }
+        }
+        const unsigned long long b[IU_PLANES] = {__ballot(ch == 'A'), __ballot(ch == 'C'), __ballot(ch == 'G'), __ballot(ch == 'T'),
+                                                 __ballot(ch == 'M')};
+        if (bit == 0 && gw < n_words) {
+#pragma unroll
+            for (int k = 0; k < IU_PLANES; ++k) planes[(int64_t)k * n_words + gw] = (uint32_t)(b[k] >> (32 * half));
+        }
+    }
+}
+
+// one thread per mask word and strand pair, like k_mark_words (and the same cnt layout); S: at most 8 x 2 motifs, by value
+__global__ __launch_bounds__(256) void k_mark_iupac(const uint32_t *__restrict__ planes, const int64_t *__restrict__ word_off,
+                                                    int n_contigs, int64_t n_words, const mc_iupac_spec S,
+                                                    uint32_t *__restrict__ mf, uint32_t *__restrict__ mr,
+                                                    long long *__restrict__ cnt) {
+    const int64_t gw = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gw >= n_words) return;
+    const int ci = mark_contig_of_word(word_off, n_contigs, gw);
+    const int64_t w = gw - word_off[ci];
+    const int64_t nw = (ci + 1 < n_contigs ? word_off[ci + 1] : n_words) - word_off[ci];
+    // positions [32 w - 32, 32 w + 64) of the contig: bit 32 of the window is the word's first position
+    iu_u128 P[IU_PLANES];
+#pragma unroll
+    for (int k = 0; k < IU_PLANES; ++k) {
+        const uint32_t *__restrict__ pl = planes + (int64_t)k * n_words + word_off[ci];
+        const uint32_t lo = w > 0 ? pl[w - 1] : 0u, mid = pl[w], hi = w + 1 < nw ? pl[w + 1] : 0u;
+        P[k] = (iu_u128)lo | ((iu_u128)mid << 32) | ((iu_u128)hi << 64);
+    }
+    iu_u128 f = P[4], r = P[4];                          // a literal 'M' is a mark on both strands
+    for (int k = 0; k < S.n_motifs; ++k) {
+        f |= iu_window_marks(&S.fwd[k], P[0], P[1], P[2], P[3]);
+        r |= iu_window_marks(&S.rev[k], P[0], P[1], P[2], P[3]);
+    }
+    const uint32_t bf = (uint32_t)(f >> 32), br = (uint32_t)(r >> 32);
+    mf[gw] = bf;
+    mr[gw] = br;
+    cnt[2 * word_off[ci] + w] = __popc(bf);
+    cnt[2 * word_off[ci] + nw + w] = __popc(br);
+}
+
 struct KpTok { int64_t b; int n; };
 
 __device__ __forceinline__ bool kp_int(const char *__restrict__ t, KpTok k, long long *out) {       // mc_parse.cpp parse_int

@@ -1,7 +1,8 @@
 // mc_tables.hip -- table slots (uploads, select, fetch), the host side of the device parser and the reference setters: the one
-// unit that includes mc_devparse.inc, whose kernels (kp_*, k_mark_*, k_copy_bytes) sit in an unnamed namespace.  The structures:
+// unit that includes mc_devparse.inc, whose kernels (kp_*, k_mark_*, k_ref_planes, k_copy_bytes) sit in an unnamed namespace.  The structures:
 // mc_ctx.h.
 #include "mc_ctx.h"
+#include "mc_iupac.h"
 
 static SmallLayout small_layout(int64_t n_seg, int64_t n_tiles, int64_t n_reads) {
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -161,6 +162,74 @@ extern "C" int mc_ctx_set_reference_motif(mc_ctx *c, const mc_ref_view *h, const
         long long n_sites = 0;
         if (hipMemcpyAsync(&n_sites, total, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
             mc_set_error("mc_ctx_set_reference_motif: the marking failed: %s", hipGetErrorString(hipGetLastError()));
+            rc = -11;
+        }
+        R.n_sites = n_sites;
+    }
+    if (rc) return rc;
+    end_reference(c);
+    return 0;
+}
+
+// The reference from its raw bases for a set of degenerate motifs (mc_iupac.h), the masks made on the device: k_ref_planes turns
+// the bases into bit-planes, k_mark_iupac matches every motif of both strands on them.  The same staging and the same results as
+// mc_ctx_set_reference_motif: R.seq upper-cased, R.mf / R.mr, the site numbering.
+extern "C" int mc_ctx_set_reference_iupac(mc_ctx *c, const mc_ref_view *h, const mc_iupac_spec *spec) {
+    HIP_TRY(hipSetDevice(c->device));
+    bool ok = h && h->n_contigs >= 1 && h->seq && h->n_words >= 1 && h->n_seq_bytes >= 0 && iu_spec_ok(spec);
+    // (the kernels index by this layout: every contig's bases inside seq, its mask words -- two of padding -- inside the grid)
+    for (int32_t ci = 0; ok && ci < h->n_contigs; ++ci) {
+        const int64_t L = h->contig_len[ci], w0 = h->word_off[ci], w1 = ci + 1 < h->n_contigs ? h->word_off[ci + 1] : h->n_words;
+        ok = L >= 0 && h->seq_off[ci] >= 0 && h->seq_off[ci] <= h->n_seq_bytes - L && w0 >= 0 && (ci > 0 || w0 == 0) &&
+             w1 - w0 >= (L + 31) / 32 + 2 && w1 <= h->n_words;
+    }
+    if (!ok) {
+        mc_set_error("mc_ctx_set_reference_iupac: bad arguments (1..%d motifs of 1..%d letters; ceil(len / 32) + 2 mask words per contig)",
+                     MC_IUPAC_MAX_MOTIFS, MC_IUPAC_MAX_LEN);
+        return -12;
+    }
+    if (int rc = begin_reference(c, h)) return rc;
+    DevRef &R = c->R;
+    // one pinned stage for the small arrays and the bases, moved by a kernel (see mc_ctx_set_reference)
+    const size_t nc = (size_t)h->n_contigs, nb = (size_t)h->n_seq_bytes, nw = (size_t)h->n_words;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t o_len = 0, o_soff = al(nc * 8), o_woff = o_soff + al(nc * 8), o_raw = o_woff + al(nc * 8), in_total = o_raw + al(nb + 16);
+    unsigned char *dev_in = nullptr;
+    uint8_t *seq = nullptr;
+    uint32_t *planes = nullptr;
+    long long *cnt = nullptr, *off = nullptr, *total = nullptr;
+    Pool tmp("mc_ctx_set_reference_iupac");                  // scratch of this call
+    Pinned stage_pin;
+    if (c->ref_allocs.get(&dev_in, in_total) || c->ref_allocs.get(&seq, nb + 16) || c->ref_allocs.get(&R.mf, nw) ||
+        c->ref_allocs.get(&R.mr, nw) || c->ref_allocs.get(&R.rank_f, nw) || c->ref_allocs.get(&R.rank_r, nw) ||
+        c->ref_allocs.get(&R.site_base, nc * 2) || tmp.get(&planes, (size_t)IU_PLANES * nw) || tmp.get(&cnt, 2 * nw + 1) ||
+        tmp.get(&off, 2 * nw + 1) || tmp.get(&total, 1) || stage_pin.alloc(in_total))
+        return -10;
+    unsigned char *stage = stage_pin.get<unsigned char>();
+    memcpy(stage + o_len, h->contig_len, nc * 8);
+    memcpy(stage + o_soff, h->seq_off, nc * 8);
+    memcpy(stage + o_woff, h->word_off, nc * 8);
+    memcpy(stage + o_raw, h->seq, nb);
+    memset(stage + o_raw + nb, 0, 16);
+    R.contig_len = (int64_t *)(dev_in + o_len); R.seq_off = (int64_t *)(dev_in + o_soff); R.word_off = (int64_t *)(dev_in + o_woff);
+    R.seq = seq;
+    hipStream_t st = c->stream;
+    int rc = mc_copy_by_kernel(dev_in, stage, in_total, st);
+    if (!rc) {
+        // (bytes of seq that belong to no contig, and the 16 behind the last one: upper-cased as they are)
+        hipLaunchKernelGGL(k_mark_upper, dim3(1024), dim3(256), 0, st, (const uint8_t *)(dev_in + o_raw), seq, (int64_t)nb + 16);
+        const unsigned pb = (unsigned)std::min<size_t>(((nw + 1) / 2 + 3) / 4, 4096);      // (four waves a block, 64 bases a wave and step)
+        hipLaunchKernelGGL(k_ref_planes, dim3(pb), dim3(256), 0, st, (const uint8_t *)(dev_in + o_raw), seq, (const int64_t *)R.contig_len,
+                           (const int64_t *)R.seq_off, (const int64_t *)R.word_off, h->n_contigs, (int64_t)nw, planes);
+        const unsigned wb = (unsigned)((nw + 255) / 256);
+        hipLaunchKernelGGL(k_mark_iupac, dim3(wb), dim3(256), 0, st, (const uint32_t *)planes, (const int64_t *)R.word_off, h->n_contigs,
+                           (int64_t)nw, *spec, R.mf, R.mr, cnt);
+        hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)cnt, (int64_t)(2 * nw), off, total);
+        hipLaunchKernelGGL(k_mark_ranks, dim3(wb), dim3(256), 0, st, (const long long *)off, (const int64_t *)R.word_off, h->n_contigs,
+                           (int64_t)nw, R.rank_f, R.rank_r, R.site_base);
+        long long n_sites = 0;
+        if (hipMemcpyAsync(&n_sites, total, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+            mc_set_error("mc_ctx_set_reference_iupac: the marking failed: %s", hipGetErrorString(hipGetLastError()));
             rc = -11;
         }
         R.n_sites = n_sites;

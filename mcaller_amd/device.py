@@ -74,6 +74,14 @@ class Device(object):
                                                len(motif_rev)))
 
     @_serialized
+    def set_reference_iupac(self, arrays, spec):
+        """The same for a set of degenerate motifs (arrays: MarkedReference.raw_arrays(); spec: MarkedReference.iupac_for_the_device(),
+        an _lib.IupacSpec)."""
+        v = _lib.make_ref_view(arrays)
+        v.n_words = int(arrays['n_words'])
+        check(lib().mc_ctx_set_reference_iupac(self._ctx, C.byref(v), C.byref(spec)))
+
+    @_serialized
     def fetch_reference(self, n_seq_bytes, n_words, n_contigs):
         """(seq, mbits_fwd, mbits_rev, rank_fwd, rank_rev, site_base, n_sites) as the device holds them (tests)."""
         seq = np.empty(n_seq_bytes, dtype=np.uint8)

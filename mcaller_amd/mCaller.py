@@ -13,7 +13,7 @@ assert sys.version_info >= (3, 0), 'please use python3'
 
 from .extract_contexts import extract_features
 from .read_qual import extract_read_quality, read_qualities      # noqa: F401 (extract_read_quality: the package's listed entry point)
-from .refmark import read_fasta
+from .refmark import parse_motifs, read_fasta
 
 
 def pos2label(positions):
@@ -180,6 +180,11 @@ _SITE_CHOICE = (
     (('-p', '--positions'), dict(type=str, help='file with a list of positions at which to classify bases (must be formatted as '
                                                 'space- or tab-separated file with chromosome, position, strand, and label if training)')),
     (('-m', '--motif'), dict(type=str, help='classify every base of type --base in the motif specified instead (can be single one-mer)')),
+    (('--motifs',), dict(type=str, metavar='SPEC',
+                         help='(mcaller_amd) classify the sites of up to 8 degenerate motifs in one pass: MOTIF[:I+J...][,MOTIF...], IUPAC '
+                              'letters (ACGT RYSWKM BDHV N; here M means A or C, it is not the mark letter), up to 32 each; the '
+                              'bases called are the 1-based indices I, J ... (each must hold --base) or, without indices, every '
+                              '--base of the motif; every occurrence counts, overlapping ones included, on both strands')),
 )
 _REFERENCE_FLAGS = (
     (('-r', '--reference'), dict(type=str, required=True, help='fasta file with reference aligned to')),
@@ -214,7 +219,20 @@ _OWN_FLAGS = (
 
 def build_parser():
     from argparse import ArgumentParser
-    parser = ArgumentParser(description='Classify bases as methylated or unmethylated', prog='mCaller')
+
+    class Parser(ArgumentParser):
+        """--motifs is read with --base, which may follow it: the spec is parsed once all arguments are known."""
+
+        def parse_args(self, args=None, namespace=None):
+            ns = ArgumentParser.parse_args(self, args, namespace)
+            if ns.motifs is not None:
+                try:
+                    ns.motifs = parse_motifs(ns.motifs, ns.base)
+                except ValueError as e:
+                    self.error(str(e))                      # (exit status 2, like every other bad argument)
+            return ns
+
+    parser = Parser(description='Classify bases as methylated or unmethylated', prog='mCaller')
     one_of = parser.add_mutually_exclusive_group(required=True)
     for flags, kw in _SITE_CHOICE:
         one_of.add_argument(*flags, **kw)
@@ -258,7 +276,7 @@ def main(argv=None):
         raise box['err']
     bed = dict(min_depth=args.bed_min_depth, mod_threshold=args.bed_mod_threshold, vo=args.bed_vo) if args.bed else None
     Run(tsv=args.tsv, reference=args.reference, read2qual=box['r2q'], num_refs=num_refs, positions=args.positions,
-        motif=args.motif, base=args.motif if (args.motif and len(args.motif) == 1) else args.base, k=args.num_variables,
+        motif=args.motifs or args.motif, base=args.motif if (args.motif and len(args.motif) == 1) else args.base, k=args.num_variables,
         threads=args.threads, train=args.train, training_tsv=args.training_tsv or None, modelfile=modelfile,
         skip_thresh=args.skip_thresh, qual_thresh=args.qual_thresh, classifier=args.classifier,
         plot_training=args.plot_training, n_gpus=max(1, n_gpus), bed=bed, fastq=args.fastq).go()

@@ -110,6 +110,105 @@ def methylate_references(ref_seq, base, motif=None, positions=None, train=False,
     return meth_fwd, meth_rev
 
 
+# ---- degenerate (IUPAC) motifs, several at once: --motifs (the rule in C: csrc/mc_iupac.h) ----
+IUPAC_SETS = {'A': 'A', 'C': 'C', 'G': 'G', 'T': 'T', 'R': 'AG', 'Y': 'CT', 'S': 'CG', 'W': 'AT', 'K': 'GT', 'M': 'AC',
+              'B': 'CGT', 'D': 'AGT', 'H': 'ACT', 'V': 'ACG', 'N': 'ACGT'}       # (M: {A, C} -- in a spec it is not the mark letter)
+_IUPAC_COMP = {frozenset(comp(v)): k for k, v in IUPAC_SETS.items()}
+IUPAC_MAX_MOTIFS, IUPAC_MAX_LEN = 8, 32
+
+
+class IupacMotifs(object):
+    """A parsed --motifs spec.  text: the canonical spelling (upper case, every entry with its called indices, ascending);
+    entries: ((motif, (1-based called indices)), ...); base: the base the called letters hold.  Plain data: it travels to the
+    workers of a sharded run in the job dicts."""
+
+    def __init__(self, text, entries, base):
+        self.text, self.entries, self.base = text, tuple(entries), base
+
+    def __str__(self):
+        return self.text
+
+    def __repr__(self):
+        return 'IupacMotifs(%r, base=%r)' % (self.text, self.base)
+
+    def __eq__(self, other):
+        return isinstance(other, IupacMotifs) and (self.text, self.base) == (other.text, other.base)
+
+    def __hash__(self):
+        return hash((self.text, self.base))
+
+    def strands(self):
+        """[(letters, 0-based called offsets)] for the '+' strand, and for the '-' strand: the IUPAC reverse complements,
+        offsets mirrored."""
+        fwd = [(m, tuple(i - 1 for i in idx)) for m, idx in self.entries]
+        rev = [(''.join(_IUPAC_COMP[frozenset(IUPAC_SETS[ch])] for ch in reversed(m)), tuple(sorted(len(m) - 1 - j for j in offs)))
+               for m, offs in fwd]
+        return fwd, rev
+
+    def native(self):
+        """The spec as the library takes it (_lib.IupacSpec), built by the library from the letters."""
+        from . import _lib
+        spec = _lib.IupacSpec()
+        for m, idx in self.entries:
+            _lib.check(_lib.lib().mc_iupac_spec_add(spec, m.encode('ascii'), len(m), sum(1 << (i - 1) for i in idx)))
+        return spec
+
+
+def parse_motifs(text, base):
+    """`MOTIF[:I+J+...][,MOTIF...]` -> IupacMotifs; ValueError (naming the entry) for anything else.  1 to 8 entries of 1 to 32
+    IUPAC letters; the called letters of an entry are the 1-based indices given, each of which must hold `base`, or, without
+    indices, every letter equal to `base` (what -m does); an entry calls at least one letter."""
+    base = base.upper()
+    if base not in ('A', 'C', 'G', 'T'):
+        raise ValueError('--base %r: the called base is one of A, C, G, T' % base)
+    parts = text.upper().split(',')
+    if not 1 <= len(parts) <= IUPAC_MAX_MOTIFS:
+        raise ValueError('--motifs %r: 1 to %d entries, %d given' % (text, IUPAC_MAX_MOTIFS, len(parts)))
+    entries = []
+    for part in parts:
+        entry = part.strip()
+        motif, colon, idx_text = entry.partition(':')
+        if not 1 <= len(motif) <= IUPAC_MAX_LEN:
+            raise ValueError('--motifs entry %r: a motif has 1 to %d letters' % (entry, IUPAC_MAX_LEN))
+        bad = sorted(set(ch for ch in motif if ch not in IUPAC_SETS))
+        if bad:
+            raise ValueError('--motifs entry %r: %r is no IUPAC letter (ACGT RYSWKM BDHV N)' % (entry, ''.join(bad)))
+        if colon:
+            tokens = idx_text.split('+')
+            if not all(t.isascii() and t.isdigit() for t in tokens):
+                raise ValueError('--motifs entry %r: the called letters are 1-based indices joined by "+"' % entry)
+            idx = sorted(set(int(t) for t in tokens))
+            for i in idx:
+                if not 1 <= i <= len(motif):
+                    raise ValueError('--motifs entry %r: index %d lies outside the motif' % (entry, i))
+                if motif[i - 1] != base:
+                    raise ValueError('--motifs entry %r: letter %d is %s, not the called base %s' % (entry, i, motif[i - 1], base))
+        else:
+            idx = [i + 1 for i, ch in enumerate(motif) if ch == base]
+            if not idx:
+                raise ValueError('--motifs entry %r: no letter is the called base %s' % (entry, base))
+        entries.append((motif, tuple(idx)))
+    canonical = ','.join('%s:%s' % (m, '+'.join(str(i) for i in idx)) for m, idx in entries)
+    return IupacMotifs(canonical, entries, base)
+
+
+def methylate_iupac(ref_seq, spec):
+    """The literal statement of the rule (csrc/mc_iupac.h) on an upper-cased contig -> (meth_fwd, meth_rev): 'M' at every called
+    letter of every occurrence, overlapping ones included (a zero-width lookahead finds a match at every start); a sequence
+    letter other than A, C, G, T matches nothing; what is 'M' in the sequence stays 'M' on both strands."""
+    import re
+    out = []
+    for table in spec.strands():
+        buf = bytearray(ref_seq, 'latin1')
+        for motif, offsets in table:
+            pattern = re.compile('(?=%s)' % ''.join('[%s]' % IUPAC_SETS[ch] for ch in motif))
+            for hit in pattern.finditer(ref_seq):
+                for j in offsets:
+                    buf[hit.start() + j] = 77               # ord('M')
+        out.append(buf.decode('latin1'))
+    return out[0], out[1]
+
+
 def m_bitmask(meth, pad_words=2):
     """bit p of the little-endian u32 array is set <=> meth[p] == 'M'; zero padding at the end."""
     raw = np.frombuffer(meth.encode('latin1'), dtype=np.uint8)
@@ -130,6 +229,7 @@ class MarkedReference(object):
         self.base, self.motif, self.positions_list = base, motif, positions_list
         self.meth = {}                                  # contig id -> (meth_fwd, meth_rev)
         self.quiet = False                              # the exit paths of the marking do not print
+        self.native = True                              # a --motifs spec is marked in the library (False: by methylate_iupac)
         self._arrays = (None, None)
         self._upper = {}
         self._upper_bytes = {}
@@ -174,8 +274,28 @@ class MarkedReference(object):
         self._upper_bytes[contig_id] = bufs[0]                        # (what device_arrays sends; the string is made on demand)
         self.meth[contig_id] = (str(memoryview(bufs[1]), 'ascii'), str(memoryview(bufs[2]), 'ascii'))
 
+    def _mark_iupac_native(self, contig_id):
+        """A --motifs spec on an ASCII contig in the library (mc_mark_iupac: the rule of csrc/mc_iupac.h, sequentially)."""
+        seq = self.records[contig_id][1]
+        if not self.native or not seq.isascii():
+            return
+        try:
+            from . import _lib
+            L = _lib.lib()
+        except (ImportError, OSError):
+            return
+        raw, n = seq.encode('ascii'), len(seq)
+        bufs = [np.empty(n, dtype=np.uint8) for _ in range(3)]        # (not zero-filled: every byte is written)
+        _lib.check(L.mc_mark_iupac(raw, n, self.motif.native(), bufs[0].ctypes.data, bufs[1].ctypes.data, bufs[2].ctypes.data))
+        self._upper_bytes[contig_id] = bufs[0]
+        self.meth[contig_id] = (str(memoryview(bufs[1]), 'ascii'), str(memoryview(bufs[2]), 'ascii'))
+
     def mark(self, contig_id):
         with self._lock:                                # (a streamed file marks its first contig ahead of time, in a thread)
+            if contig_id not in self.meth and isinstance(self.motif, IupacMotifs) and not self.positions_list:
+                self._mark_iupac_native(contig_id)
+                if contig_id not in self.meth:
+                    self.meth[contig_id] = methylate_iupac(self.upper(contig_id), self.motif)
             if contig_id not in self.meth and self.motif and not self.positions_list:
                 self._mark_motif_native(contig_id)
             if contig_id not in self.meth:
@@ -188,7 +308,7 @@ class MarkedReference(object):
         """(motif_fwd, repl_fwd, motif_rev, repl_rev) as bytes if the device can make the site masks itself
         (mc_ctx_set_reference_motif): motif mode, ASCII, at most 16 bases, and neither motif can overlap itself (no proper
         prefix is also a suffix -- str.replace's left-to-right, non-overlapping rule is then "every occurrence"); else None."""
-        if not self.motif or self.positions_list:
+        if not self.motif or self.positions_list or isinstance(self.motif, IupacMotifs):
             return None
         try:
             motif_f, motif_r = self.motif, revcomp(self.motif)
@@ -201,6 +321,15 @@ class MarkedReference(object):
         if not all(seq.isascii() for _, seq in self.records):
             return None
         return motif_f.encode('ascii'), repl_f.encode('ascii'), motif_r.encode('ascii'), repl_r.encode('ascii')
+
+    def iupac_for_the_device(self):
+        """The spec as the library takes it if the device can make the site masks itself (mc_ctx_set_reference_iupac): a --motifs
+        run on ASCII contigs; else None."""
+        if not isinstance(self.motif, IupacMotifs) or self.positions_list:
+            return None
+        if not all(seq.isascii() for _, seq in self.records):
+            return None
+        return self.motif.native()
 
     def raw_arrays(self):
         """The arrays of mc_ref_view for mc_ctx_set_reference_motif: the raw bases of EVERY contig, laid out as device_arrays

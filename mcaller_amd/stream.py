@@ -275,10 +275,15 @@ class PassQueue(object):
         are not waited for by the passes.  (Not for motifs that can overlap themselves, positions mode, very long references:
         then the masks come from the host's marking, contig by contig as they appear.)"""
         dev_motif = self.ref.motif_for_the_device() if self.on_device else None
-        if dev_motif is not None and sum(len(seq) for _, seq in self.ref.records) <= (256 << 20):
+        dev_iupac = self.ref.iupac_for_the_device() if self.on_device else None       # (a --motifs spec: mc_ctx_set_reference_iupac)
+        if (dev_motif is None and dev_iupac is None) or sum(len(seq) for _, seq in self.ref.records) > (256 << 20):
+            return
+        if dev_iupac is not None:
+            self.dev.set_reference_iupac(self.ref.raw_arrays(), dev_iupac)
+        else:
             self.dev.set_reference_motif(self.ref.raw_arrays(), *dev_motif)
-            self.masks_on_device = True
-            self.marked = 0
+        self.masks_on_device = True
+        self.marked = 0
 
     def enqueue(self, P, tail_id, rows_before):
         while len(self.in_flight) >= 2:
