@@ -71,7 +71,7 @@
 //   kb_sums / kb_apply again (the rows' sizes with the attributes), kb_write (no list: --gff writes none)
 //
 // The steps (one lane per line unless said otherwise; n = lines):
-//   kp_count / kp_scan / kp_starts   line starts (the device parser's kernels: mc_lines.h)
+//   kp_count / kp_scan / kp_starts   line starts (the device parser's kernels: mc_lines.h, launched by mc_textfeed.h)
 //   kb_parse      256 lines of a workgroup staged in LDS with 16-byte loads; per line: the class of every byte, the tabs, centre 'M',
 //                 label 'm', the position as an integer, the stripped span of the probability, a 64-bit hash of the key bytes.
 //                 A flagged line: atomicMin of (line << 8 | reason) -- the decline names the FIRST such line, whatever the order
@@ -87,15 +87,13 @@
 //   kb_write / kb_write_vo   a lane per selected entry writes the columns (fields copied from the head row's spans, pos + 1 and
 //                 the depth from the integers, the fraction from its digits); a wave per selected entry writes the list
 // wave64; no library sort; every buffer, event and stream through the owners of mc_own.h.
-#include "../mc_lines.h"
+// The host side around the kernels -- a file's way onto the device through the context's two pinned stages, the line starts, the
+// head's way back, the decline, the clock -- is mc_textfeed.h's, shared with the other three units that take a whole text file.
+#include "../mc_textfeed.h"
 #include "../mc_rowtext.h"
 #include "../mc_decimal.h"
 #include "../mc_tstat.h"
 #include "../mc_npsum.h"
-
-#include <sys/stat.h>
-
-extern "C" int mc_read_file_range(const char *path, int64_t lo, int64_t hi, char *dst, int32_t n_threads);
 
 namespace {
 
@@ -656,48 +654,26 @@ const char *bs_reason_text(int reason) {
     return "unknown";
 }
 
-double bs_ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 int bs_decline(mc_ctx *c, int32_t *status, int reason, long long line) {
-    c->bed_stats.decline_reason = reason;
-    c->bed_stats.decline_line = line;
-    if (line >= 0) mc_set_error("the device summary declines: %s (line %lld)", bs_reason_text(reason), line + 1);
-    else mc_set_error("the device summary declines: %s", bs_reason_text(reason));
-    *status = 1;
-    return 0;
+    return decline(c->bed_stats, status, "summary", bs_reason_text(reason), reason, line);
 }
 
-// does `bytes` more fit into device memory, with a margin for what the runtime and the other buffers of the context take
-bool bs_fits(size_t bytes) {
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return false; }
-    const size_t margin = (size_t)256 << 20;
-    return free_b > margin && bytes <= free_b - margin;
+int bs_decline_head(mc_ctx *c, int32_t *status, const BsHead &h) {
+    return bs_decline(c, status, decline_reason(h.decline), decline_line(h.decline));
 }
 
 // the line starts of a text on the device (padded): *n_nl newlines, *n_lines lines, line_start[0 .. n_lines] (n > 0)
 int bs_lines(Pool &pool, hipStream_t st, const char *d_text, int64_t n, BsHead *d_head, BsHead &h, long long **line_start, int64_t *n_nl,
              int64_t *n_lines, bool *too_many) {
-    const int64_t n_tiles = (n + KP_TILE - 1) / KP_TILE;
-    long long *tile_cnt = nullptr, *tile_off = nullptr;
+    long long *tile_off = nullptr;
     *too_many = false;
-    if (pool.get(&tile_cnt, (size_t)n_tiles) || pool.get(&tile_off, (size_t)n_tiles)) return -10;
-    hipLaunchKernelGGL(kp_count, dim3((unsigned)n_tiles), dim3(KP_THREADS), 0, st, d_text, n, tile_cnt);
-    hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)tile_cnt, n_tiles, tile_off, &d_head->kp.n_newlines);
-    HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = lines_count(pool, st, d_text, n, &d_head->kp, &tile_off)) return rc;
+    if (int rc = fetch_head(st, d_head, h)) return rc;
     *n_nl = h.kp.n_newlines;
-    if (*n_nl + 1 >= ((int64_t)1 << 31) - 2) { *too_many = true; return 0; }
-    const int64_t cap_lines = *n_nl + 2;
-    if (!bs_fits((size_t)cap_lines * 8 + ((size_t)1 << 20))) { *too_many = true; return 0; }
-    if (pool.get(line_start, (size_t)cap_lines)) return -10;
-    hipLaunchKernelGGL(kp_starts, dim3((unsigned)n_tiles), dim3(KP_THREADS), 0, st, d_text, n, (const long long *)tile_off, *line_start,
-                       cap_lines, &d_head->kp);
+    if (too_many_lines(*n_nl) || !device_fits((size_t)(*n_nl + 2) * 8 + ((size_t)1 << 20))) { *too_many = true; return 0; }
+    if (int rc = lines_starts(pool, st, d_text, n, *n_nl, tile_off, &d_head->kp, line_start)) return rc;
     // (the last line may lack its newline: the same count kp_starts makes; the last byte is not on the host, so it is asked for)
-    HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = fetch_head(st, d_head, h)) return rc;
     *n_lines = h.kp.n_lines;
     return 0;
 }
@@ -717,7 +693,7 @@ int bs_position_set(mc_ctx *c, Pool &pool, BsArgs &A, BsHead *d_head, BsHead &h,
     const size_t pl = (size_t)std::max<int64_t>(A.p_lines, 1);
     uint64_t slots = 16;
     while ((int64_t)slots < 2 * A.p_lines) slots <<= 1;
-    if (!bs_fits(pl * (16 + 8) + (size_t)slots * 8)) { (void)bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1); return 1; }
+    if (!device_fits(pl * (16 + 8) + (size_t)slots * 8)) { (void)bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1); return 1; }
     if (pool.get(&A.p_line, pl) || pool.get(&A.p_hash, pl) || pool.get(&A.p_table, (size_t)slots)) { *rc = -10; return 1; }
     A.p_mask = slots - 1;
     if (hipMemsetAsync(A.p_table, 0, (size_t)slots * 8, st) != hipSuccess) { *rc = -11; return 1; }
@@ -725,9 +701,9 @@ int bs_position_set(mc_ctx *c, Pool &pool, BsArgs &A, BsHead *d_head, BsHead &h,
         const unsigned pb = (unsigned)((A.p_lines + 255) / 256);
         hipLaunchKernelGGL(kq_parse, dim3(pb), dim3(256), 0, st, A);
         hipLaunchKernelGGL(kq_insert, dim3(pb), dim3(256), 0, st, A);
-        if (hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { *rc = -11; return 1; }
+        if (fetch_head(st, d_head, h)) { *rc = -11; return 1; }
         c->bed_stats.kernel_bytes += 3 * pn + A.p_lines * (8 + 16 + 8) * 2 + (int64_t)slots * 8;
-        if (h.decline != ~0ull) { (void)bs_decline(c, status, (int)(h.decline & 0xff), (long long)(h.decline >> 8)); return 1; }
+        if (h.decline != ~0ull) { (void)bs_decline_head(c, status, h); return 1; }
     }
     return 0;
 }
@@ -744,29 +720,29 @@ int bs_fasta(mc_ctx *c, Pool &pool, BsArgs &A, BsHead *d_head, BsHead &h, const 
     if (too_many) { (void)bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1); return 1; }
     A.f_start = f_start;
     const size_t fl = (size_t)A.f_lines;
-    if (!bs_fits(fl * (4 * 8 + 1 + 4 + 4 + 8) + ((size_t)1 << 20))) { (void)bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1); return 1; }
+    if (!device_fits(fl * (4 * 8 + 1 + 4 + 4 + 8) + ((size_t)1 << 20))) { (void)bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1); return 1; }
     if (pool.get(&A.f_cnt, 2 * fl) || pool.get(&A.f_off, 2 * fl) || pool.get(&A.f_bad, fl) || pool.get(&A.f_idb, fl) || pool.get(&A.f_idn, fl) ||
         pool.get(&A.f_hash, fl)) { *rc = -10; return 1; }
     const unsigned wb = (unsigned)((A.f_lines + 3) / 4);
     hipLaunchKernelGGL(kf_lines, dim3(wb), dim3(256), 0, st, A);
     hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)A.f_cnt, A.f_lines, A.f_off, &d_head->f_total);
     hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)(A.f_cnt + fl), A.f_lines, A.f_off + fl, &d_head->f_nrec);
-    if (hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { *rc = -11; return 1; }
+    if (fetch_head(st, d_head, h)) { *rc = -11; return 1; }
     c->bed_stats.kernel_bytes += 3 * fn + A.f_lines * 6 * 8;
-    if (h.decline != ~0ull) { (void)bs_decline(c, status, (int)(h.decline & 0xff), (long long)(h.decline >> 8)); return 1; }
+    if (h.decline != ~0ull) { (void)bs_decline_head(c, status, h); return 1; }
     A.n_rec = h.f_nrec;
     uint64_t slots = 16;
     while ((long long)slots < 2 * A.n_rec) slots <<= 1;
-    if (!bs_fits((size_t)h.f_total + (size_t)A.n_rec * 12 + (size_t)slots * 12 + ((size_t)1 << 20))) { (void)bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1); return 1; }
+    if (!device_fits((size_t)h.f_total + (size_t)A.n_rec * 12 + (size_t)slots * 12 + ((size_t)1 << 20))) { (void)bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1); return 1; }
     if (pool.get(&A.f_seq, (size_t)h.f_total + 1) || pool.get(&A.rec_begin, (size_t)A.n_rec + 1) || pool.get(&A.rec_line, (size_t)A.n_rec + 1) ||
         pool.get(&A.f_table, (size_t)slots) || pool.get(&A.f_win, (size_t)slots)) { *rc = -10; return 1; }
     A.f_mask = slots - 1;
     if (hipMemsetAsync(A.f_table, 0, (size_t)slots * 8, st) != hipSuccess || hipMemsetAsync(A.f_win, 0, (size_t)slots * 4, st) != hipSuccess) { *rc = -11; return 1; }
     hipLaunchKernelGGL(kf_pack, dim3(wb), dim3(256), 0, st, A, A.n_rec, h.f_total);
     if (A.n_rec > 0) hipLaunchKernelGGL(kf_ids, dim3((unsigned)((A.n_rec + 255) / 256)), dim3(256), 0, st, A, A.n_rec);
-    if (hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { *rc = -11; return 1; }
+    if (fetch_head(st, d_head, h)) { *rc = -11; return 1; }
     c->bed_stats.kernel_bytes += fn + h.f_total + A.f_lines * 3 * 8 + A.n_rec * 40;
-    if (h.decline != ~0ull) { (void)bs_decline(c, status, (int)(h.decline & 0xff), (long long)(h.decline >> 8)); return 1; }
+    if (h.decline != ~0ull) { (void)bs_decline_head(c, status, h); return 1; }
     return 0;
 }
 
@@ -811,7 +787,7 @@ int bs_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *d_p
     if (int rc = bs_lines(pool, st, d_text, n, d_head, h, &line_start, &n_nl, &n_lines, &too_many)) return rc;
     if (too_many) return bs_decline(c, status, n_nl + 1 >= ((int64_t)1 << 31) - 2 ? MC_BED_DECLINE_ROWS : MC_BED_DECLINE_MEMORY, -1);
     // per line: the row, four 32-bit columns, the hash, the flags, the entry's five columns (-p: the value count, two numbers' digits)
-    if (!bs_fits((size_t)(n_nl + 2) * (16 + 4 * 4 + 8 + 1 + 4 * 4 + 8 + (A.stats ? 4 + 2 * 12 : 0) + (A.gstats ? 2 * 12 + 8 : 0) + (A.ref ? 9 : 0)) +
+    if (!device_fits((size_t)(n_nl + 2) * (16 + 4 * 4 + 8 + 1 + 4 * 4 + 8 + (A.stats ? 4 + 2 * 12 : 0) + (A.gstats ? 2 * 12 + 8 : 0) + (A.ref ? 9 : 0)) +
                  ((size_t)1 << 20)))
         return bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1);
     S.n_lines = n_lines;
@@ -832,17 +808,15 @@ int bs_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *d_p
     const unsigned lb = (unsigned)((n_lines + 255) / 256);
     A.nblk = lb;
     hipLaunchKernelGGL(kb_parse, dim3(lb), dim3(256), BS_STAGE + 16, st, A);
-    HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = fetch_head(st, d_head, h)) return rc;
     S.kernel_bytes += 3 * n + n_lines * (8 + 16 + 4 + 4 + 8 + 1);       // the text: counted, split, parsed; the line columns
-    if (h.decline != ~0ull) return bs_decline(c, status, (int)(h.decline & 0xff), (long long)(h.decline >> 8));
+    if (h.decline != ~0ull) return bs_decline_head(c, status, h);
     const int64_t n_counted = (int64_t)h.n_counted;
     S.n_counted = n_counted;
     if (A.stats && n_counted > 0) {                           // every counted row has the first one's number of values, 2 .. 64
         hipLaunchKernelGGL(kq_counts, dim3(lb), dim3(256), 0, st, A);
-        HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (h.decline != ~0ull) return bs_decline(c, status, (int)(h.decline & 0xff), (long long)(h.decline >> 8));
+        if (int rc = fetch_head(st, d_head, h)) return rc;
+        if (h.decline != ~0ull) return bs_decline_head(c, status, h);
         A.nv = h.nv;
     }
     uint64_t slots = 16;
@@ -853,7 +827,7 @@ int bs_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *d_p
     }
     S.table_slots = (int64_t)slots;
     if ((int64_t)slots < 2 * n_counted) return bs_decline(c, status, MC_BED_DECLINE_TABLE, -1);
-    if (!bs_fits((size_t)slots * 8 + (size_t)3 * lb * 16 + (A.buckets ? (size_t)n_counted * 8 : 0))) return bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1);
+    if (!device_fits((size_t)slots * 8 + (size_t)3 * lb * 16 + (A.buckets ? (size_t)n_counted * 8 : 0))) return bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1);
     if (pool.get(&A.table, (size_t)slots) || pool.get(&A.blk_sum, (size_t)3 * lb) || pool.get(&A.blk_off, (size_t)3 * lb)) return -10;
     A.table_mask = slots - 1;
     HIP_TRY(hipMemsetAsync(A.table, 0, (size_t)slots * 8, st));
@@ -871,21 +845,20 @@ int bs_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *d_p
         hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)(A.blk_sum + lb), (int64_t)lb, A.blk_off + lb, &d_head->tot_sel);
         hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)(A.blk_sum + 2 * (size_t)lb), (int64_t)lb, A.blk_off + 2 * (size_t)lb,
                            &d_head->tot_bytes);
-        HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        if (int rc = fetch_head(st, d_head, h)) return rc;
         return 0;
     };
     if (int rc = size_entries()) return rc;
     S.kernel_bytes += (int64_t)slots * 8 + n_lines * 5 * 8 + n_counted * (16 + 8 + 5 * 4 + 60) + 2 * n_lines * (1 + 4 + 3 * 4);
     S.longest_probe = h.longest_probe;
-    if (h.decline != ~0ull) return bs_decline(c, status, (int)(h.decline & 0xff), (long long)(h.decline >> 8));
+    if (h.decline != ~0ull) return bs_decline_head(c, status, h);
     S.n_entries = (int64_t)h.n_entries;
     const int64_t n_sel = h.tot_sel;
     int64_t n_outb = h.tot_bytes;
     S.n_sites = n_sel;
     *n_sites = n_sel;
     if (n_sel > 0) {
-        if (!bs_fits((size_t)n_sel * 32 + (size_t)n_outb + (A.stats ? (size_t)n_counted * A.nv * 8 + (size_t)n_sel * A.nv * 24 : 0) +
+        if (!device_fits((size_t)n_sel * 32 + (size_t)n_outb + (A.stats ? (size_t)n_counted * A.nv * 8 + (size_t)n_sel * A.nv * 24 : 0) +
                      (A.gstats ? (size_t)n_counted * 8 + (size_t)n_sel * 20 + (size_t)n_sel * 64 : 0)))
             return bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1);
         if (pool.get(&A.sel_line, (size_t)n_sel) || pool.get(&A.large, (size_t)n_sel) || pool.get(&A.sel_off, (size_t)n_sel) ||
@@ -903,9 +876,8 @@ int bs_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *d_p
             const int64_t n_num = n_counted * A.nv, n_mom = n_sel * (A.nv - 1);
             if (pool.get(&A.X, (size_t)n_num) || pool.get(&A.mom, (size_t)n_mom * 3)) return -10;
             hipLaunchKernelGGL(kq_features, dim3((unsigned)((n_num + 255) / 256)), dim3(256), 0, st, A, n_num);
-            HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));      // (a value that is no number: named before the moments run on it)
-            HIP_TRY(hipStreamSynchronize(st));
-            if (h.decline != ~0ull) return bs_decline(c, status, (int)(h.decline & 0xff), (long long)(h.decline >> 8));
+            if (int rc = fetch_head(st, d_head, h)) return rc;                            // (a value that is no number: named before the moments run on it)
+            if (h.decline != ~0ull) return bs_decline_head(c, status, h);
             hipLaunchKernelGGL(kq_moments_small, dim3((unsigned)((n_mom + 255) / 256)), dim3(256), 0, st, A, n_sel);
             hipLaunchKernelGGL(kq_moments_large, dim3((unsigned)std::min<int64_t>((n_mom + 3) / 4, 4096)), dim3(256), 0, st, A);
             hipLaunchKernelGGL(kq_finish, dim3(sb), dim3(256), 0, st, A, n_sel);
@@ -913,17 +885,16 @@ int bs_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *d_p
             A.stats_ready = 1;                                // the rows' sizes with the two columns, and their places
             if (int rc = size_entries()) return rc;
             S.kernel_bytes += n_counted * 60 + 3 * n_num * 8 + 2 * n_mom * 24 + n_lines * (1 + 4 + 3 * 4);
-            if (h.decline != ~0ull) return bs_decline(c, status, (int)(h.decline & 0xff), (long long)(h.decline >> 8));
+            if (h.decline != ~0ull) return bs_decline_head(c, status, h);
             n_outb = h.tot_bytes;
-            if (!bs_fits((size_t)n_outb)) return bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1);
+            if (!device_fits((size_t)n_outb)) return bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1);
             hipLaunchKernelGGL(kb_apply, dim3(lb), dim3(256), 0, st, A);
         }
         if (A.gstats) {
             if (pool.get(&A.X, (size_t)n_counted) || pool.get(&A.mom, (size_t)n_sel * 2) || pool.get(&A.g_large, (size_t)n_sel)) return -10;
             hipLaunchKernelGGL(kg_probs, dim3((unsigned)((n_counted + 255) / 256)), dim3(256), 0, st, A, n_counted);
-            HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));      // (a text that is no number: named before the sums run on it)
-            HIP_TRY(hipStreamSynchronize(st));
-            if (h.decline != ~0ull) return bs_decline(c, status, (int)(h.decline & 0xff), (long long)(h.decline >> 8));
+            if (int rc = fetch_head(st, d_head, h)) return rc;                            // (a text that is no number: named before the sums run on it)
+            if (h.decline != ~0ull) return bs_decline_head(c, status, h);
             hipLaunchKernelGGL(kg_moments_small, dim3(sb), dim3(256), 0, st, A, n_sel);
             hipLaunchKernelGGL(kg_moments_large, dim3((unsigned)std::min<int64_t>(n_sel, 4096)), dim3(NS_NODES), 0, st, A);
             hipLaunchKernelGGL(kg_finish, dim3(sb), dim3(256), 0, st, A, n_sel);
@@ -931,9 +902,9 @@ int bs_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *d_p
             A.stats_ready = 1;                                // the rows' sizes with the three attributes, and their places
             if (int rc = size_entries()) return rc;
             S.kernel_bytes += n_counted * (60 + 3 * 8) + n_sel * 2 * (16 + 12) + n_lines * (1 + 4 + 3 * 4);
-            if (h.decline != ~0ull) return bs_decline(c, status, (int)(h.decline & 0xff), (long long)(h.decline >> 8));
+            if (h.decline != ~0ull) return bs_decline_head(c, status, h);
             n_outb = h.tot_bytes;
-            if (!bs_fits((size_t)n_outb)) return bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1);
+            if (!device_fits((size_t)n_outb)) return bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1);
             hipLaunchKernelGGL(kb_apply, dim3(lb), dim3(256), 0, st, A);
         }
         if (pool.get(&A.out, (size_t)n_outb)) return -10;
@@ -944,18 +915,14 @@ int bs_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *d_p
         S.kernel_bytes += n_lines * (1 + 4 + 3 * 4) + 2 * n_outb + (A.buckets ? n_counted * 24 : 0);
     }
     S.n_out_bytes = n_outb;
-    S.ms_kernels = bs_ms_since(t_kernels);
+    S.ms_kernels = ms_since(t_kernels);
     const auto t_d2h = std::chrono::steady_clock::now();
     if (n_outb > 0) {
-        if (c->bed_out_cap < (size_t)n_outb) {
-            c->bed_out_cap = 0;
-            if (int rc = c->bed_out.alloc((size_t)n_outb + (size_t)n_outb / 4)) return rc;
-            c->bed_out_cap = (size_t)n_outb + (size_t)n_outb / 4;
-        }
+        if (int rc = grow(c->bed_out, c->bed_out_cap, (size_t)n_outb)) return rc;
         HIP_TRY(hipMemcpyAsync(c->bed_out.p, A.out, (size_t)n_outb, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
-    S.ms_d2h = bs_ms_since(t_d2h);
+    S.ms_d2h = ms_since(t_d2h);
     *out = (const char *)c->bed_out.p;
     *n_out = n_outb;
     return 0;
@@ -968,105 +935,47 @@ int bs_begin(mc_ctx *c, const mc_bed_params *P, const char **out, int64_t *n_out
     c->bed_stats.n_bytes = n;
     *out = nullptr; *n_out = 0; *n_sites = 0; *status = 0;
     if (P->gff && P->with_probs && !annotate) { (void)bs_decline(c, status, MC_BED_DECLINE_OPTIONS, -1); return 1; }
-    if (!bs_fits((size_t)n + 4096)) { (void)bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1); return 1; }
+    if (!device_fits((size_t)n + 4096)) { (void)bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1); return 1; }
     return 0;
 }
 
-// a host text onto the device, padded with 64 zero bytes (enqueued on c->up_stream and waited for)
-int bs_upload_text(mc_ctx *c, Pool &pool, const char *text, int64_t n, char **d_text) {
-    if (pool.get(d_text, (size_t)n + 64)) return -10;
-    if (n > 0) HIP_TRY(hipMemcpyAsync(*d_text, text, (size_t)n, hipMemcpyHostToDevice, c->up_stream));
-    HIP_TRY(hipMemsetAsync(*d_text + n, 0, 64, c->up_stream));
-    HIP_TRY(hipStreamSynchronize(c->up_stream));
-    return 0;
-}
-
-// a file of n bytes onto the device, padded: in blocks, two pinned stages in turn -- block i is read while block i - 1 is on its way
-int bs_upload_file(mc_ctx *c, Pool &pool, const char *path, int64_t n, char **d_text, double *ms_read) {
-    if (pool.get(d_text, (size_t)n + 64)) return -10;
-    const size_t block = (size_t)std::min<int64_t>(std::max<int64_t>(n, 4096), (int64_t)64 << 20);
-    if (c->bed_stage_cap < block) {
-        c->bed_stage_cap = 0;
-        for (Pinned &p : c->bed_stage)
-            if (int rc = p.alloc(block)) return rc;
-        c->bed_stage_cap = block;
-    }
-    for (Event &e : c->bed_ev)
-        if (!e.e)
-            if (int rc = e.create()) return rc;
-    int rc = 0, turn = 0;
-    for (int64_t lo = 0; lo < n && rc == 0; lo += (int64_t)c->bed_stage_cap, turn ^= 1) {
-        const int64_t hi = std::min<int64_t>(n, lo + (int64_t)c->bed_stage_cap);
-        if (lo >= 2 * (int64_t)c->bed_stage_cap) HIP_TRY(hipEventSynchronize(c->bed_ev[turn]));     // the copy out of this stage is done
-        const auto tr = std::chrono::steady_clock::now();
-        rc = mc_read_file_range(path, lo, hi, c->bed_stage[turn].get<char>(), 0);
-        *ms_read += bs_ms_since(tr);
-        if (rc) break;
-        HIP_TRY(hipMemcpyAsync(*d_text + lo, c->bed_stage[turn].p, (size_t)(hi - lo), hipMemcpyHostToDevice, c->up_stream));
-        HIP_TRY(hipEventRecord(c->bed_ev[turn], c->up_stream));
-    }
-    HIP_TRY(hipMemsetAsync(*d_text + n, 0, 64, c->up_stream));
-    HIP_TRY(hipStreamSynchronize(c->up_stream));
-    return rc;
-}
-
-int bs_file_size(const char *what, const char *path, int64_t *n) {
-    struct stat sb;
-    if (stat(path, &sb) != 0 || !S_ISREG(sb.st_mode)) {
-        mc_set_error("%s: %s is not a readable file", what, path);
-        return -1;
-    }
-    *n = (int64_t)sb.st_size;
-    return 0;
-}
-
-// texts: positions == null -> no -p; fasta == null -> no --ref; annotate: the mc_bed_annotate_* entry points (--gff --vo is made)
-int bs_text(mc_ctx *c, const char *text, int64_t n_bytes, const char *positions, int64_t pn, const char *fasta, int64_t fn, bool annotate,
-            const mc_bed_params *P, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status) {
+// What every entry point runs: the texts of the sources, each padded in a buffer of its own, onto the device and through bs_run.
+// pos == null -> no -p; fa == null -> no --ref; annotate: the mc_bed_annotate_* entry points (--gff --vo is made)
+int bs_call(mc_ctx *c, const TextSource &src, const TextSource *pos, const TextSource *fa, bool annotate, const mc_bed_params *P,
+            const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status) {
     HIP_TRY(hipSetDevice(c->device));
     const auto t0 = std::chrono::steady_clock::now();
-    if (bs_begin(c, P, out, n_out, n_sites, status, n_bytes + pn + fn, annotate)) return 0;
-    c->bed_stats.n_bytes = n_bytes;
+    const int64_t pn = pos ? pos->n : 0, fn = fa ? fa->n : 0;
+    if (bs_begin(c, P, out, n_out, n_sites, status, src.n + pn + fn, annotate)) return 0;
+    c->bed_stats.n_bytes = src.n;
     Pool pool("bed summary");
+    TextFeed feed(c, (size_t)64 << 20);
     char *d_text = nullptr, *d_ptext = nullptr, *d_ftext = nullptr;
-    if (int rc = bs_upload_text(c, pool, text, n_bytes, &d_text)) return rc;
-    if (positions)
-        if (int rc = bs_upload_text(c, pool, positions, pn, &d_ptext)) return rc;
-    if (fasta)
-        if (int rc = bs_upload_text(c, pool, fasta, fn, &d_ftext)) return rc;
-    c->bed_stats.ms_h2d = bs_ms_since(t0);
-    const int rc = bs_run(c, pool, d_text, n_bytes, d_ptext, pn, d_ftext, fn, P, out, n_out, n_sites, status);
+    if (int rc = feed.put(pool, src, &d_text)) return rc;
+    if (pos)
+        if (int rc = feed.put(pool, *pos, &d_ptext)) return rc;
+    if (fa)
+        if (int rc = feed.put(pool, *fa, &d_ftext)) return rc;
+    feed.times(c->bed_stats, t0);
+    const int rc = bs_run(c, pool, d_text, src.n, d_ptext, pn, d_ftext, fn, P, out, n_out, n_sites, status);
     (void)hipStreamSynchronize(c->stream);                   // (an early return: nothing of the pool is in use when it goes)
-    c->bed_stats.ms_total = bs_ms_since(t0);
+    c->bed_stats.ms_total = ms_since(t0);
     return rc;
+}
+
+int bs_text(mc_ctx *c, const char *text, int64_t n_bytes, const char *positions, int64_t pn, const char *fasta, int64_t fn, bool annotate,
+            const mc_bed_params *P, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status) {
+    const TextSource src = {text, nullptr, n_bytes}, pos = {positions, nullptr, pn}, fa = {fasta, nullptr, fn};
+    return bs_call(c, src, positions ? &pos : nullptr, fasta ? &fa : nullptr, annotate, P, out, n_out, n_sites, status);
 }
 
 int bs_file(mc_ctx *c, const char *what, const char *path, const char *positions_path, const char *fasta_path, bool annotate,
             const mc_bed_params *P, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status) {
-    int64_t n = 0, pn = 0, fn = 0;
-    if (int rc = bs_file_size(what, path, &n)) return rc;
-    if (positions_path)
-        if (int rc = bs_file_size(what, positions_path, &pn)) return rc;
-    if (fasta_path)
-        if (int rc = bs_file_size(what, fasta_path, &fn)) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    if (bs_begin(c, P, out, n_out, n_sites, status, n + pn + fn, annotate)) return 0;
-    c->bed_stats.n_bytes = n;
-    Pool pool("bed summary");
-    char *d_text = nullptr, *d_ptext = nullptr, *d_ftext = nullptr;
-    double ms_read = 0;
-    if (int rc = bs_upload_file(c, pool, path, n, &d_text, &ms_read)) return rc;
-    if (positions_path)
-        if (int rc = bs_upload_file(c, pool, positions_path, pn, &d_ptext, &ms_read)) return rc;
-    if (fasta_path)
-        if (int rc = bs_upload_file(c, pool, fasta_path, fn, &d_ftext, &ms_read)) return rc;
-    c->bed_stats.ms_read = ms_read;
-    c->bed_stats.ms_h2d = bs_ms_since(t0) - ms_read;         // what the copies added behind the reads they ran beside
-    const int rc = bs_run(c, pool, d_text, n, d_ptext, pn, d_ftext, fn, P, out, n_out, n_sites, status);
-    (void)hipStreamSynchronize(c->stream);
-    c->bed_stats.ms_total = bs_ms_since(t0);
-    return rc;
+    TextSource src[3] = {{nullptr, path, 0}, {nullptr, positions_path, 0}, {nullptr, fasta_path, 0}};
+    for (TextSource &s : src)
+        if (s.path)
+            if (int rc = regular_file_size(what, s.path, &s.n)) return rc;
+    return bs_call(c, src[0], positions_path ? &src[1] : nullptr, fasta_path ? &src[2] : nullptr, annotate, P, out, n_out, n_sites, status);
 }
 
 // the probe of mc_tstat.h's device build: a lane per triple
@@ -1225,7 +1134,6 @@ extern "C" int mc_bed_release(mc_ctx *c) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipStreamSynchronize(c->up_stream));
     c->bed_out.reset(); c->bed_out_cap = 0;
-    for (Pinned &p : c->bed_stage) p.reset();
-    c->bed_stage_cap = 0;
+    c->text_stages.release();
     return 0;
 }

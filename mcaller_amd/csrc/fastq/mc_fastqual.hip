@@ -8,7 +8,7 @@
 // that does not fit into free device memory beside its outputs: the WHOLE text stays resident.
 //
 // The steps (R = records, P = FQ_PIECE bytes):
-//   kp_count / kp_scan / kp_starts   line starts (the device parser's kernels: mc_lines.h)
+//   kp_count / kp_scan / kp_starts   line starts (the device parser's kernels: mc_lines.h, launched by mc_textfeed.h)
 //   kfq_class    a stream over the whole text, 64 bytes a lane in four 16-byte loads: the byte classes and the '\r' rule four bytes
 //                at a time (the byte behind a word and behind the tile is looked at too), the last byte that is no blank, tab or
 //                line break by atomicMax.  Only a lane that found something walks its bytes: atomicMin of line << 8 | reason
@@ -24,15 +24,12 @@
 //   kfq_finish   a lane per record: fq_mean
 //   kfq_keys     a lane per record: its key and a '\n' into the pool; the offsets' last entry
 // wave64; no library sort or scan; every buffer, event and stream through the owners of mc_own.h.
-#include "../mc_lines.h"
+// The host side around the kernels -- a file's way onto the device through the context's two pinned stages, the line starts, the
+// head's way back, the decline, the clock -- is mc_textfeed.h's, shared with the other three units that take a whole text file.
+#include "../mc_textfeed.h"
 #include "../mc_fastqrec.h"
 
-#include <sys/stat.h>
-
-#include <chrono>
 #include <cstring>
-
-extern "C" int mc_read_file_range(const char *path, int64_t lo, int64_t hi, char *dst, int32_t n_threads);
 
 namespace {
 
@@ -215,37 +212,12 @@ __global__ __launch_bounds__(256) void kfq_keys(FqArgs A) {
     A.pool[at + k] = '\n';
 }
 
-double fq_ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 int fq_decline(mc_ctx *c, int32_t *status, int reason, long long line) {
-    c->fq_stats.decline_reason = reason;
-    c->fq_stats.decline_line = line;
-    if (line >= 0) mc_set_error("the device reader declines: %s (line %lld)", fq_reason_text(reason), line + 1);
-    else mc_set_error("the device reader declines: %s", fq_reason_text(reason));
-    *status = 1;
-    return 0;
+    return decline(c->fq_stats, status, "reader", fq_reason_text(reason), reason, line);
 }
 
 int fq_decline_head(mc_ctx *c, int32_t *status, const FqHead &h) {
-    return fq_decline(c, status, (int)(h.decline & 0xff), (long long)(h.decline >> 8));
-}
-
-// does `bytes` more fit into device memory, with a margin for what the runtime and the other buffers of the context take
-bool fq_fits(size_t bytes) {
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return false; }
-    const size_t margin = (size_t)256 << 20;
-    return free_b > margin && bytes <= free_b - margin;
-}
-
-int fq_grow(Pinned &p, size_t &cap, size_t bytes) {
-    if (cap >= bytes) return 0;
-    cap = 0;
-    if (int rc = p.alloc(bytes + bytes / 4)) return rc;
-    cap = bytes + bytes / 4;
-    return 0;
+    return fq_decline(c, status, decline_reason(h.decline), decline_line(h.decline));
 }
 
 // The text is on the device (d_text[0, n), its buffer aligned and padded; copies enqueued on c->up_stream): everything behind that
@@ -261,36 +233,28 @@ int fq_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, mc_fastq_qualit
     h.last_line = -1;
     HIP_TRY(hipMemcpyAsync(d_head, &h, sizeof h, hipMemcpyHostToDevice, st));
     const int64_t n_tiles = (n + KP_TILE - 1) / KP_TILE;
-    long long *tile_cnt = nullptr, *tile_off = nullptr;
-    if (pool.get(&tile_cnt, (size_t)n_tiles) || pool.get(&tile_off, (size_t)n_tiles)) return -10;
-    hipLaunchKernelGGL(kp_count, dim3((unsigned)n_tiles), dim3(KP_THREADS), 0, st, d_text, n, tile_cnt);
-    hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)tile_cnt, n_tiles, tile_off, &d_head->kp.n_newlines);
-    HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    long long *tile_off = nullptr, *line_start = nullptr;
+    if (int rc = lines_count(pool, st, d_text, n, &d_head->kp, &tile_off)) return rc;
+    if (int rc = fetch_head(st, d_head, h)) return rc;
     const int64_t n_nl = h.kp.n_newlines;
-    if (n_nl + 1 >= ((int64_t)1 << 31) - 2) return fq_decline(c, status, MC_FASTQ_DECLINE_ROWS, -1);
-    const int64_t cap_lines = n_nl + 2;
-    if (!fq_fits((size_t)cap_lines * 8 + ((size_t)1 << 20))) return fq_decline(c, status, MC_FASTQ_DECLINE_MEMORY, -1);
-    long long *line_start = nullptr;
-    if (pool.get(&line_start, (size_t)cap_lines)) return -10;
-    hipLaunchKernelGGL(kp_starts, dim3((unsigned)n_tiles), dim3(KP_THREADS), 0, st, d_text, n, (const long long *)tile_off, line_start,
-                       cap_lines, &d_head->kp);
+    if (too_many_lines(n_nl)) return fq_decline(c, status, MC_FASTQ_DECLINE_ROWS, -1);
+    if (!device_fits((size_t)(n_nl + 2) * 8 + ((size_t)1 << 20))) return fq_decline(c, status, MC_FASTQ_DECLINE_MEMORY, -1);
+    if (int rc = lines_starts(pool, st, d_text, n, n_nl, tile_off, &d_head->kp, &line_start)) return rc;
     hipLaunchKernelGGL(kfq_class, dim3((unsigned)n_tiles), dim3(KP_THREADS), 0, st, d_text, n, (const long long *)line_start, n_nl, d_head);
     hipLaunchKernelGGL(kfq_last, dim3(1), dim3(64), 0, st, (const long long *)line_start, n_nl, d_head);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = fetch_head(st, d_head, h)) return rc;
     S.n_lines = h.kp.n_lines;
     const int64_t R = h.last_line < 0 ? 0 : h.last_line / 4 + 1;
     if (R == 0) {                                             // nothing but blanks, tabs and line breaks -- or bytes that decline
         if (h.decline != FQ_NO_DECLINE) return fq_decline_head(c, status, h);
-        S.ms_kernels = fq_ms_since(t_kernels);
+        S.ms_kernels = ms_since(t_kernels);
         return 0;
     }
     FqArgs A = {};
     A.text = d_text; A.n_bytes = n; A.n_lines = h.kp.n_lines; A.n_nl = n_nl; A.R = R; A.line_start = line_start; A.head = d_head;
     const size_t nr = (size_t)R;
-    if (!fq_fits(nr * 80 + ((size_t)1 << 20))) return fq_decline(c, status, MC_FASTQ_DECLINE_MEMORY, -1);
+    if (!device_fits(nr * 80 + ((size_t)1 << 20))) return fq_decline(c, status, MC_FASTQ_DECLINE_MEMORY, -1);
     if (pool.get(&A.key_b, nr) || pool.get(&A.key_len1, nr) || pool.get(&A.qual_b, nr) || pool.get(&A.qual_n, nr) || pool.get(&A.pieces, nr) ||
         pool.get(&A.piece_off, nr) || pool.get(&A.key_off, nr + 1) || pool.get(&A.sum, nr) || pool.get(&A.mean, nr))
         return -10;
@@ -299,14 +263,13 @@ int fq_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, mc_fastq_qualit
     hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)A.pieces, R, A.piece_off, &d_head->n_pieces);
     hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)A.key_len1, R, A.key_off, &d_head->pool_bytes);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = fetch_head(st, d_head, h)) return rc;
     if (h.decline != FQ_NO_DECLINE) return fq_decline_head(c, status, h);
     A.n_pieces = h.n_pieces;
     S.n_records = R;
     S.n_pieces = h.n_pieces;
     const size_t np = (size_t)h.n_pieces, pb = (size_t)h.pool_bytes;
-    if (!fq_fits(np * 4 + pb + ((size_t)1 << 20))) return fq_decline(c, status, MC_FASTQ_DECLINE_MEMORY, -1);
+    if (!device_fits(np * 4 + pb + ((size_t)1 << 20))) return fq_decline(c, status, MC_FASTQ_DECLINE_MEMORY, -1);
     if (pool.get(&A.piece_rec, np) || pool.get(&A.pool, pb)) return -10;
     if (np > 0) {
         hipLaunchKernelGGL(kfq_piecemap, dim3(rb), dim3(256), 0, st, A);
@@ -316,16 +279,16 @@ int fq_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, mc_fastq_qualit
     hipLaunchKernelGGL(kfq_keys, dim3(rb), dim3(256), 0, st, A);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
-    S.ms_kernels = fq_ms_since(t_kernels);
+    S.ms_kernels = ms_since(t_kernels);
     const auto t_d2h = std::chrono::steady_clock::now();
-    if (int rc = fq_grow(c->fq_pool, c->fq_pool_cap, pb)) return rc;
-    if (int rc = fq_grow(c->fq_off, c->fq_off_cap, (nr + 1) * 8)) return rc;
-    if (int rc = fq_grow(c->fq_mean, c->fq_mean_cap, nr * 8)) return rc;
+    if (int rc = grow(c->fq_pool, c->fq_pool_cap, pb)) return rc;
+    if (int rc = grow(c->fq_off, c->fq_off_cap, (nr + 1) * 8)) return rc;
+    if (int rc = grow(c->fq_mean, c->fq_mean_cap, nr * 8)) return rc;
     HIP_TRY(hipMemcpyAsync(c->fq_pool.p, A.pool, pb, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(c->fq_off.p, A.key_off, (nr + 1) * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(c->fq_mean.p, A.mean, nr * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    S.ms_d2h = fq_ms_since(t_d2h);
+    S.ms_d2h = ms_since(t_d2h);
     V->key_pool = c->fq_pool.get<char>();
     V->key_off = c->fq_off.get<int64_t>();
     V->mean = c->fq_mean.get<double>();
@@ -341,8 +304,25 @@ int fq_begin(mc_ctx *c, mc_fastq_quality_view *V, int32_t *status, int64_t n) {
     c->fq_stats.piece_bytes = FQ_PIECE;
     *V = mc_fastq_quality_view();
     *status = 0;
-    if (!fq_fits((size_t)n + 4096)) { (void)fq_decline(c, status, MC_FASTQ_DECLINE_MEMORY, -1); return 1; }
+    if (!device_fits((size_t)n + 4096)) { (void)fq_decline(c, status, MC_FASTQ_DECLINE_MEMORY, -1); return 1; }
     return 0;
+}
+
+// what both entry points run: the text of `src` onto the device and through fq_run
+int fq_call(mc_ctx *c, const TextSource &src, mc_fastq_quality_view *out, int32_t *status) {
+    HIP_TRY(hipSetDevice(c->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    if (fq_begin(c, out, status, src.n)) return 0;
+    Pool pool("fastq qualities");
+    TextFeed feed(c, (size_t)32 << 20);
+    char *d_text = nullptr;
+    if (int rc = feed.put(pool, src, &d_text)) return rc;
+    feed.times(c->fq_stats, t0);
+    const int rc = fq_run(c, pool, d_text, src.n, out, status);
+    (void)hipStreamSynchronize(c->stream);                   // (an early return: nothing of the pool is in use when it goes)
+    if (rc != 0 || *status != 0) *out = mc_fastq_quality_view();
+    c->fq_stats.ms_total = ms_since(t0);
+    return rc;
 }
 
 }  // namespace
@@ -352,21 +332,7 @@ extern "C" int mc_fastq_quality_text(mc_ctx *c, const char *text, int64_t n_byte
         mc_set_error("mc_fastq_quality_text: bad arguments");
         return -12;
     }
-    HIP_TRY(hipSetDevice(c->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    if (fq_begin(c, out, status, n_bytes)) return 0;
-    Pool pool("fastq qualities");
-    char *d_text = nullptr;
-    if (pool.get(&d_text, (size_t)n_bytes + 64)) return -10;
-    if (n_bytes > 0) HIP_TRY(hipMemcpyAsync(d_text, text, (size_t)n_bytes, hipMemcpyHostToDevice, c->up_stream));
-    HIP_TRY(hipMemsetAsync(d_text + n_bytes, 0, 64, c->up_stream));
-    HIP_TRY(hipStreamSynchronize(c->up_stream));
-    c->fq_stats.ms_h2d = fq_ms_since(t0);
-    const int rc = fq_run(c, pool, d_text, n_bytes, out, status);
-    (void)hipStreamSynchronize(c->stream);                   // (an early return: nothing of the pool is in use when it goes)
-    if (rc != 0 || *status != 0) *out = mc_fastq_quality_view();
-    c->fq_stats.ms_total = fq_ms_since(t0);
-    return rc;
+    return fq_call(c, TextSource{text, nullptr, n_bytes}, out, status);
 }
 
 extern "C" int mc_fastq_quality_file(mc_ctx *c, const char *path, mc_fastq_quality_view *out, int32_t *status) {
@@ -374,51 +340,9 @@ extern "C" int mc_fastq_quality_file(mc_ctx *c, const char *path, mc_fastq_quali
         mc_set_error("mc_fastq_quality_file: bad arguments");
         return -12;
     }
-    struct stat sb;
-    if (stat(path, &sb) != 0 || !S_ISREG(sb.st_mode)) {
-        mc_set_error("mc_fastq_quality_file: %s is not a readable file", path);
-        return -1;
-    }
-    const int64_t n = (int64_t)sb.st_size;
-    HIP_TRY(hipSetDevice(c->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    if (fq_begin(c, out, status, n)) return 0;
-    Pool pool("fastq qualities");
-    char *d_text = nullptr;
-    if (pool.get(&d_text, (size_t)n + 64)) return -10;
-    // the file in blocks, two pinned stages in turn: block i is read while block i - 1 is on its way
-    const size_t block = (size_t)std::min<int64_t>(std::max<int64_t>(n, 4096), (int64_t)32 << 20);
-    if (c->fq_stage_cap < block) {
-        c->fq_stage_cap = 0;
-        for (Pinned &p : c->fq_stage)
-            if (int rc = p.alloc(block)) return rc;
-        c->fq_stage_cap = block;
-    }
-    for (Event &e : c->fq_ev)
-        if (!e.e)
-            if (int rc = e.create()) return rc;
-    double ms_read = 0;
-    int rc = 0, turn = 0;
-    for (int64_t lo = 0; lo < n && rc == 0; lo += (int64_t)c->fq_stage_cap, turn ^= 1) {
-        const int64_t hi = std::min<int64_t>(n, lo + (int64_t)c->fq_stage_cap);
-        if (lo >= 2 * (int64_t)c->fq_stage_cap) HIP_TRY(hipEventSynchronize(c->fq_ev[turn]));     // the copy out of this stage is done
-        const auto tr = std::chrono::steady_clock::now();
-        rc = mc_read_file_range(path, lo, hi, c->fq_stage[turn].get<char>(), 0);
-        ms_read += fq_ms_since(tr);
-        if (rc) break;
-        HIP_TRY(hipMemcpyAsync(d_text + lo, c->fq_stage[turn].p, (size_t)(hi - lo), hipMemcpyHostToDevice, c->up_stream));
-        HIP_TRY(hipEventRecord(c->fq_ev[turn], c->up_stream));
-    }
-    HIP_TRY(hipMemsetAsync(d_text + n, 0, 64, c->up_stream));
-    HIP_TRY(hipStreamSynchronize(c->up_stream));
-    if (rc) return rc;
-    c->fq_stats.ms_read = ms_read;
-    c->fq_stats.ms_h2d = fq_ms_since(t0) - ms_read;          // what the copies added behind the reads they ran beside
-    rc = fq_run(c, pool, d_text, n, out, status);
-    (void)hipStreamSynchronize(c->stream);
-    if (rc != 0 || *status != 0) *out = mc_fastq_quality_view();
-    c->fq_stats.ms_total = fq_ms_since(t0);
-    return rc;
+    int64_t n = 0;
+    if (int rc = regular_file_size("mc_fastq_quality_file", path, &n)) return rc;
+    return fq_call(c, TextSource{nullptr, path, n}, out, status);
 }
 
 extern "C" int mc_fastq_quality_last_stats(mc_ctx *c, mc_fastq_quality_stats *out) {
@@ -435,7 +359,6 @@ extern "C" int mc_fastq_quality_release(mc_ctx *c) {
     c->fq_pool.reset(); c->fq_pool_cap = 0;
     c->fq_off.reset(); c->fq_off_cap = 0;
     c->fq_mean.reset(); c->fq_mean_cap = 0;
-    for (Pinned &p : c->fq_stage) p.reset();
-    c->fq_stage_cap = 0;
+    c->text_stages.release();
     return 0;
 }

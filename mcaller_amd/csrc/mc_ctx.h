@@ -213,6 +213,17 @@ struct RowTextCtx {
     int64_t last_bytes = 0, last_rows = 0;
 };
 
+// the two pinned blocks a file is read through on its way to the device, and the events behind the copies out of them (mc_textfeed.h)
+struct TextStages {
+    Pinned stage[2];
+    size_t cap = 0;
+    Event ev[2];
+    void release() {
+        for (Pinned &p : stage) p.reset();
+        cap = 0;
+    }
+};
+
 // The members' order is the order of construction, and its reverse the order of destruction (mc_ctx_destroy: `delete c` behind a
 // sync of every stream): the streams stand first and go last, behind every event, allocation and pinned block used on them.
 struct mc_ctx {
@@ -287,38 +298,27 @@ struct mc_ctx {
     Pinned site_status_host;                            // pinned copy the host reads (written by a kernel: no DMA)
     void *comm = nullptr;             // ncclComm_t
     int comm_world = 1;
-    // the summary of a .diffs file (bed/mc_bedsum.hip): the result handed out last, the file reader's two pinned blocks and the
-    // events that say a block's H2D copy is done, the figures of the last call
+    // The four units that take a whole text file through the GPU (mc_textfeed.h).  Their calls are synchronous and never run side
+    // by side, so they share the file reader's two pinned blocks and the events that say a block's copy is done (the merge's
+    // output leaves through them too): grown on demand, freed by every mc_*_release.  What a call hands out is its pipeline's own
+    // and stays valid until the next call of that pipeline:
+    TextStages text_stages;
+    // ... the summary of a .diffs file (bed/mc_bedsum.hip) and the figures of the last call
     Pinned bed_out;
     size_t bed_out_cap = 0;
-    Pinned bed_stage[2];
-    size_t bed_stage_cap = 0;
-    Event bed_ev[2];
     mc_bed_stats bed_stats = {};
-    // the matrices of a --training_tsv file (train/mc_trainrows.hip): the result handed out last (X and the contexts in pinned
-    // memory, the labels' bytes), the file reader's two pinned blocks with their events, the figures of the last call
+    // ... the matrices of a --training_tsv file (train/mc_trainrows.hip): X and the contexts in pinned memory, the labels' bytes
     Pinned tr_X, tr_ctx;
     size_t tr_X_cap = 0, tr_ctx_cap = 0;
     std::string tr_labels;
-    Pinned tr_stage[2];
-    size_t tr_stage_cap = 0;
-    Event tr_ev[2];
     mc_train_rows_stats tr_stats = {};
-    // the merge behind `-t N` (merge/mc_rowmerge.hip): the text handed out last, the two pinned blocks the part files are read
-    // through and the output leaves through, with their events, the figures of the last call
+    // ... the text of the merge behind `-t N` (merge/mc_rowmerge.hip)
     Pinned mg_out;
     size_t mg_out_cap = 0;
-    Pinned mg_stage[2];
-    size_t mg_stage_cap = 0;
-    Event mg_ev[2];
     mc_rows_merge_stats mg_stats = {};
-    // the read qualities of a FASTQ file (fastq/mc_fastqual.hip): the result handed out last (keys, offsets and means in pinned
-    // memory), the file reader's two pinned blocks with their events, the figures of the last call
+    // ... the read qualities of a FASTQ file (fastq/mc_fastqual.hip): keys, offsets and means in pinned memory
     Pinned fq_pool, fq_off, fq_mean;
     size_t fq_pool_cap = 0, fq_off_cap = 0, fq_mean_cap = 0;
-    Pinned fq_stage[2];
-    size_t fq_stage_cap = 0;
-    Event fq_ev[2];
     mc_fastq_quality_stats fq_stats = {};
 };
 

@@ -1,0 +1,189 @@
+// mc_textfeed.h -- what the four units that take a whole text file through the GPU share on the host side (bed/mc_bedsum.hip,
+// train/mc_trainrows.hip, merge/mc_rowmerge.hip, fastq/mc_fastqual.hip).  Included by those four units only, hence the unnamed
+// namespace: nothing here is linked across units.  An entry point refuses its arguments (-12), sizes its files
+// (regular_file_size), selects the device, and then
+//
+//     const auto t0 = std::chrono::steady_clock::now();
+//     ... blank the stats and the result; device_fits(n + ...) or decline(stats, status, "reader", text, reason, -1) ...
+//     Pool pool("x");                                  // device allocations (mc_own.h), freed when the entry point returns
+//     TextFeed feed(c, (size_t)64 << 20);              // the step through a file: at most this (MCALLER_TEXT_STAGE_BYTES)
+//     char *d_text = nullptr;
+//     if (int rc = feed.put(pool, src, &d_text)) return rc;        // src: a host text or a file; padded and waited for
+//     feed.times(stats, t0);                           // ms_read, ms_h2d
+//     long long *tile_off = nullptr, *line_start = nullptr;
+//     lines_count(pool, st, d_text, n, &d_head->kp, &tile_off); ... the unit's own kernels ...; fetch_head(st, d_head, h);
+//     if (too_many_lines(h.kp.n_newlines)) return decline(...);
+//     lines_starts(pool, st, d_text, n, h.kp.n_newlines, tile_off, &d_head->kp, &line_start); ...; fetch_head(st, d_head, h);
+//     if (h.decline != ~0ull) return decline(stats, status, "reader", text, decline_reason(h.decline), decline_line(h.decline));
+//
+// Several texts behind one another in one buffer (the merge): feed.send(src, d_dst, &last_byte) for each, then
+// feed.pad_and_wait(d_end).  The feed's two pinned stages and their events are the context's (mc_ctx::text_stages): the calls of
+// the four units are synchronous and never run side by side, so one pair serves them all.
+#pragma once
+#include "mc_lines.h"
+
+#include <sys/stat.h>
+
+#include <chrono>
+
+extern "C" int mc_read_file_range(const char *path, int64_t lo, int64_t hi, char *dst, int32_t n_threads);
+
+namespace {
+
+inline double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// does `bytes` more fit into device memory, with a margin for what the runtime and the other buffers of the context take
+inline bool device_fits(size_t bytes) {
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return false; }
+    const size_t margin = (size_t)256 << 20;
+    return free_b > margin && bytes <= free_b - margin;
+}
+
+// a pinned block a result is handed out in: at least `bytes`, a quarter more when it has to grow
+inline int grow(Pinned &p, size_t &cap, size_t bytes) {
+    if (cap >= bytes) return 0;
+    cap = 0;
+    if (int rc = p.alloc(bytes + bytes / 4)) return rc;
+    cap = bytes + bytes / 4;
+    return 0;
+}
+
+inline int regular_file_size(const char *what, const char *path, int64_t *n) {
+    struct stat sb;
+    if (!path || stat(path, &sb) != 0 || !S_ISREG(sb.st_mode)) {
+        mc_set_error("%s: %s is not a readable file", what, path ? path : "(null)");
+        return -1;
+    }
+    *n = (int64_t)sb.st_size;
+    return 0;
+}
+
+// the device-side result block of a unit onto the host, waited for
+template <typename H>
+int fetch_head(hipStream_t st, const H *d_head, H &h) {
+    HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+// A call declines (status 1, mc_last_error; the host code does the file): the reason and the line (-1: none) into the unit's stats.
+// A head's `decline` word is the minimum over the offending lines of line << 8 | reason
+template <typename S>
+int decline(S &stats, int32_t *status, const char *noun, const char *text, int reason, long long line) {
+    stats.decline_reason = reason;
+    stats.decline_line = line;
+    if (line >= 0) mc_set_error("the device %s declines: %s (line %lld)", noun, text, line + 1);
+    else mc_set_error("the device %s declines: %s", noun, text);
+    *status = 1;
+    return 0;
+}
+inline int decline_reason(unsigned long long word) { return (int)(word & 0xff); }
+inline long long decline_line(unsigned long long word) { return (long long)(word >> 8); }
+
+// ---- the line starts of a text on the device (padded, n > 0), in two halves: a unit puts kernels of its own between them and
+// fetches its head once for both.  tile_off: the scan of the first half, which the second reads ----
+inline int lines_count(Pool &pool, hipStream_t st, const char *d_text, int64_t n, KpHead *d_kp, long long **tile_off) {
+    const int64_t n_tiles = (n + KP_TILE - 1) / KP_TILE;
+    long long *tile_cnt = nullptr;
+    if (pool.get(&tile_cnt, (size_t)n_tiles) || pool.get(tile_off, (size_t)n_tiles)) return -10;
+    hipLaunchKernelGGL(kp_count, dim3((unsigned)n_tiles), dim3(KP_THREADS), 0, st, d_text, n, tile_cnt);
+    hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)tile_cnt, n_tiles, *tile_off, &d_kp->n_newlines);
+    return 0;
+}
+
+inline bool too_many_lines(int64_t n_nl) { return n_nl + 1 >= ((int64_t)1 << 31) - 2; }      // lines are numbered in 32 bits
+
+// line_start[0 .. n_lines] (n_nl + 2 entries of room), KpHead.n_lines: the last line may lack its newline
+inline int lines_starts(Pool &pool, hipStream_t st, const char *d_text, int64_t n, int64_t n_nl, const long long *tile_off, KpHead *d_kp,
+                        long long **line_start) {
+    const int64_t n_tiles = (n + KP_TILE - 1) / KP_TILE, cap_lines = n_nl + 2;
+    if (pool.get(line_start, (size_t)cap_lines)) return -10;
+    hipLaunchKernelGGL(kp_starts, dim3((unsigned)n_tiles), dim3(KP_THREADS), 0, st, d_text, n, tile_off, *line_start, cap_lines, d_kp);
+    return 0;
+}
+
+// what an entry point takes its text from: a host text, or (path != nullptr) a file of n bytes
+struct TextSource {
+    const char *text, *path;
+    int64_t n;
+};
+
+// Host texts and files, one behind the other, into device buffers: copies on c->up_stream.  A file goes in blocks through the
+// context's two pinned stages in turn: block i is read while block i - 1 is on its way.  A stage is not written again until the
+// event recorded behind the copy out of it has completed; the block count runs across the files of a call.
+struct TextFeed {
+    mc_ctx *c;
+    size_t max_block;                            // a file's step: the caller's, or MCALLER_TEXT_STAGE_BYTES (tests; Pinned's 256 or more)
+    double ms_read = 0;                          // in mc_read_file_range
+    int64_t n_blocks = 0;                        // blocks sent: block i goes through stage i & 1
+    TextFeed(mc_ctx *ctx, size_t caller_max) : c(ctx), max_block(caller_max) {
+        const char *e = getenv("MCALLER_TEXT_STAGE_BYTES");
+        const long long want = e ? atoll(e) : 0;                    // (empty, no number or below 256: as if unset)
+        if (want >= 256) max_block = (size_t)want;
+    }
+    size_t block_for(int64_t n) const { return std::min<size_t>((size_t)std::max<int64_t>(n, 4096), max_block); }
+    int stages(size_t block) {                   // the two stages hold a block each; their events exist
+        TextStages &T = c->text_stages;
+        if (T.cap < block) {
+            T.cap = 0;
+            for (Pinned &p : T.stage)
+                if (int rc = p.alloc(block)) return rc;
+            T.cap = block;
+        }
+        for (Event &e : T.ev)
+            if (!e.e)
+                if (int rc = e.create()) return rc;
+        return 0;
+    }
+    int text(const char *src, int64_t n, char *d_dst) {
+        if (n > 0) HIP_TRY(hipMemcpyAsync(d_dst, src, (size_t)n, hipMemcpyHostToDevice, c->up_stream));
+        return 0;
+    }
+    // last_byte: the file's last byte as it was read (n > 0)
+    int file(const char *path, int64_t n, char *d_dst, char *last_byte = nullptr) {
+        const int64_t step = (int64_t)block_for(n);
+        if (int rc = stages((size_t)step)) return rc;
+        TextStages &T = c->text_stages;
+        for (int64_t lo = 0; lo < n; lo += step, ++n_blocks) {
+            const int turn = (int)(n_blocks & 1);
+            const int64_t hi = std::min<int64_t>(n, lo + step);
+            if (n_blocks >= 2) HIP_TRY(hipEventSynchronize(T.ev[turn]));      // the copy out of this stage is done
+            const auto tr = std::chrono::steady_clock::now();
+            const int rc = mc_read_file_range(path, lo, hi, T.stage[turn].get<char>(), 0);
+            ms_read += ms_since(tr);
+            if (rc) {
+                (void)hipStreamSynchronize(c->up_stream);                     // (nothing is on its way when the caller's pool goes)
+                return rc;
+            }
+            if (last_byte && hi == n) *last_byte = T.stage[turn].get<char>()[hi - lo - 1];
+            HIP_TRY(hipMemcpyAsync(d_dst + lo, T.stage[turn].p, (size_t)(hi - lo), hipMemcpyHostToDevice, c->up_stream));
+            HIP_TRY(hipEventRecord(T.ev[turn], c->up_stream));
+        }
+        return 0;
+    }
+    int send(const TextSource &s, char *d_dst, char *last_byte = nullptr) {
+        if (s.path) return file(s.path, s.n, d_dst, last_byte);
+        if (last_byte && s.n > 0) *last_byte = s.text[s.n - 1];
+        return text(s.text, s.n, d_dst);
+    }
+    int pad_and_wait(char *d_end) {              // 64 zero bytes behind a buffer's texts; everything sent is there
+        HIP_TRY(hipMemsetAsync(d_end, 0, 64, c->up_stream));
+        HIP_TRY(hipStreamSynchronize(c->up_stream));
+        return 0;
+    }
+    int put(Pool &pool, const TextSource &s, char **d_text) {      // one text in a buffer of its own, padded and waited for
+        if (pool.get(d_text, (size_t)s.n + 64)) return -10;
+        if (int rc = send(s, *d_text)) return rc;
+        return pad_and_wait(*d_text + s.n);
+    }
+    template <typename S>
+    void times(S &stats, std::chrono::steady_clock::time_point t0) const {             // ms_h2d: what the copies added behind the reads they ran beside
+        stats.ms_read = ms_read;
+        stats.ms_h2d = ms_since(t0) - ms_read;
+    }
+};
+
+}  // namespace

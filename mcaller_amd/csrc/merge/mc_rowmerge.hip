@@ -16,7 +16,7 @@
 // Bytes >= 0x80 and control bytes other than '\r' compare as unsigned bytes: in scope.
 //
 // The steps (one lane per line or item unless said otherwise; n = lines):
-//   kp_count / kp_scan / kp_starts   line starts (the device parser's kernels: mc_lines.h)
+//   kp_count / kp_scan / kp_starts   line starts (the device parser's kernels: mc_lines.h, launched by mc_textfeed.h)
 //   km_cr         the smallest offset of a '\r', 16 bytes a load (atomicMin: whatever the order)
 //   km_key        mc_sortkey.h on the line -> the 128-bit key (hi, lo), the length; a flagged line: atomicMin of line << 8 | reason
 // then rounds over the ITEMS, the lines whose place is not yet decided (at first all of them, one segment).  A round orders every
@@ -37,18 +37,17 @@
 // Rounds are bounded by the longest line; every kernel runs to its end alone; what crosses workgroups is a separate launch or an
 // integer atomic (min, or, and, add to a counter; the list of km_small is worked through segment by segment, so its order does not
 // matter).  wave64; no library sort; every buffer, event and stream through the owners of mc_own.h.
-#include "../mc_lines.h"
+// The host side around the kernels -- a file's way onto the device through the context's two pinned stages, the line starts, the
+// head's way back, the decline, the clock -- is mc_textfeed.h's, shared with the other three units that take a whole text file.
+#include "../mc_textfeed.h"
 #include "../mc_sortkey.h"
 
 #include <fcntl.h>
-#include <sys/stat.h>
 #include <unistd.h>
 
 #include <cerrno>
 #include <cstring>
 #include <string>
-
-extern "C" int mc_read_file_range(const char *path, int64_t lo, int64_t hi, char *dst, int32_t n_threads);
 
 namespace {
 
@@ -388,10 +387,6 @@ const char *mg_reason_text(int reason) {
     return "unknown";
 }
 
-double mg_ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 // the part files' texts, one behind the other: file i is bytes [end[i - 1], end[i])
 struct MgFiles { std::vector<int64_t> end; };
 
@@ -402,21 +397,8 @@ int mg_file_of(const MgFiles &F, int64_t offset) {
 }
 
 int mg_decline(mc_ctx *c, int32_t *status, int reason, long long line, int file) {
-    c->mg_stats.decline_reason = reason;
-    c->mg_stats.decline_line = line;
     c->mg_stats.decline_file = file;
-    if (line >= 0) mc_set_error("the device merge declines: %s (line %lld)", mg_reason_text(reason), line + 1);
-    else mc_set_error("the device merge declines: %s", mg_reason_text(reason));
-    *status = 1;
-    return 0;
-}
-
-// does `bytes` more fit into device memory, with a margin for what the runtime and the other buffers of the context take
-bool mg_fits(size_t bytes) {
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return false; }
-    const size_t margin = (size_t)256 << 20;
-    return free_b > margin && bytes <= free_b - margin;
+    return decline(c->mg_stats, status, "merge", mg_reason_text(reason), reason, line);
 }
 
 constexpr size_t MG_BYTES_PER_LINE = 8 + 8 + 8 + 2 + 4 + 1 + 8 + 2 * (8 + 4 + 4 + 4) + 1 + 4 + 4 + 4 + 4;   // the tables of MgArgs
@@ -434,6 +416,19 @@ int mg_pass(mc_ctx *c, MgArgs &A, int64_t m, int of_seg, int sh) {
     return 0;
 }
 
+// a call of either entry point: the texts one behind the other on the device (mg_upload), and what mg_run makes of them
+struct MgCall {
+    std::chrono::steady_clock::time_point t0;
+    Pool pool{"row merge"};
+    MgFiles F;
+    char *d_text = nullptr;
+    int64_t n = 0;                               // bytes of all texts
+    int64_t bad_end = -1;                        // the offset behind the first part file that does not end in a newline, -1: none
+    size_t block = 0;                            // the step the output leaves in (mc_rows_merge_files)
+    MgArgs A = {};                               // A.out: the output on the device ...
+    int64_t nb = 0;                              // ... and its bytes
+};
+
 // The texts are on the device (d_text[0, n), padded; copies enqueued on c->up_stream): everything up to the output in A.out.
 // bad_end: the offset behind a part file that does not end in a newline, -1: none
 int mg_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const MgFiles &F, int64_t bad_end, MgArgs &A, int64_t *n_out,
@@ -448,23 +443,15 @@ int mg_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const MgFiles &
     if (pool.get(&d_head, 1)) return -10;
     h.decline = ~0ull; h.cr_at = ~0ull;
     HIP_TRY(hipMemcpyAsync(d_head, &h, sizeof h, hipMemcpyHostToDevice, st));
-    const int64_t n_tiles = (n + KP_TILE - 1) / KP_TILE;
-    long long *tile_cnt = nullptr, *tile_off = nullptr;
-    if (pool.get(&tile_cnt, (size_t)n_tiles) || pool.get(&tile_off, (size_t)n_tiles)) return -10;
-    hipLaunchKernelGGL(kp_count, dim3((unsigned)n_tiles), dim3(KP_THREADS), 0, st, d_text, n, tile_cnt);
-    hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)tile_cnt, n_tiles, tile_off, &d_head->kp.n_newlines);
+    long long *tile_off = nullptr, *line_start = nullptr;
+    if (int rc = lines_count(pool, st, d_text, n, &d_head->kp, &tile_off)) return rc;
     hipLaunchKernelGGL(km_cr, dim3((unsigned)std::min<int64_t>((n + 4095) / 4096, 8192)), dim3(256), 0, st, d_text, n, d_head);
-    HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = fetch_head(st, d_head, h)) return rc;
     S.kernel_bytes += 2 * n;
     const int64_t n_nl = h.kp.n_newlines;
-    if (n_nl + 1 >= ((int64_t)1 << 31) - 2) return mg_decline(c, status, MC_MERGE_DECLINE_ROWS, -1, -1);
-    const int64_t cap_lines = n_nl + 2;
-    if (!mg_fits((size_t)cap_lines * MG_BYTES_PER_LINE + (size_t)n + ((size_t)4 << 20))) return mg_decline(c, status, MC_MERGE_DECLINE_MEMORY, -1, -1);
-    long long *line_start = nullptr;
-    if (pool.get(&line_start, (size_t)cap_lines)) return -10;
-    hipLaunchKernelGGL(kp_starts, dim3((unsigned)n_tiles), dim3(KP_THREADS), 0, st, d_text, n, (const long long *)tile_off, line_start,
-                       cap_lines, &d_head->kp);
+    if (too_many_lines(n_nl)) return mg_decline(c, status, MC_MERGE_DECLINE_ROWS, -1, -1);
+    if (!device_fits((size_t)(n_nl + 2) * MG_BYTES_PER_LINE + (size_t)n + ((size_t)4 << 20))) return mg_decline(c, status, MC_MERGE_DECLINE_MEMORY, -1, -1);
+    if (int rc = lines_starts(pool, st, d_text, n, n_nl, tile_off, &d_head->kp, &line_start)) return rc;
     S.kernel_bytes += n + n_nl * 8;
     // a '\r' or a file without its last newline: the first of them, and the line it lies in (the starts are fetched for that alone)
     int64_t bad_at = -1;
@@ -493,14 +480,13 @@ int mg_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const MgFiles &
         return -10;
     const unsigned lb = (unsigned)nblk;
     hipLaunchKernelGGL(km_key, dim3(lb), dim3(256), 0, st, A);
-    HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = fetch_head(st, d_head, h)) return rc;
     S.kernel_bytes += n_lines * (8 + 60 + 8 + 8 + 2 + 4 * 4 + 1);       // the starts, the bytes up to the key's end, the columns
     if (h.decline != ~0ull) {
-        const long long line = (long long)(h.decline >> 8);
+        const long long line = decline_line(h.decline);
         long long at = 0;
         HIP_TRY(hipMemcpy(&at, line_start + line, 8, hipMemcpyDeviceToHost));
-        return mg_decline(c, status, (int)(h.decline & 0xff), line, mg_file_of(F, at));
+        return mg_decline(c, status, decline_reason(h.decline), line, mg_file_of(F, at));
     }
     // the rounds
     int64_t m = n_lines;
@@ -512,8 +498,7 @@ int mg_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const MgFiles &
         hipLaunchKernelGGL(km_round_init, dim3(1), dim3(1), 0, st, d_head);
         hipLaunchKernelGGL(km_word, dim3(mb), dim3(256), 0, st, A, m, kind, off);
         hipLaunchKernelGGL(km_differs, dim3(mb), dim3(256), 0, st, A, m);
-        HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        if (int rc = fetch_head(st, d_head, h)) return rc;
         S.kernel_bytes += m * (4 + 8 + 4 + (kind == MG_TEXT ? 8 + 2 + 8 : 8)) + m * 12;
         const uint64_t diff_w = h.w_or ^ h.w_and;
         const uint32_t diff_s = h.s_or ^ h.s_and;
@@ -532,8 +517,7 @@ int mg_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const MgFiles &
         hipLaunchKernelGGL(km_select, dim3(mb), dim3(256), 0, st, A, m, mblk, kind == MG_HI ? 1u : (uint32_t)MG_SMALL);
         hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)(A.blk_sum + mblk), mblk, A.blk_off + mblk, &d_head->n_stay);
         hipLaunchKernelGGL(km_compact, dim3(mb), dim3(256), 0, st, A, m, mblk);
-        HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        if (int rc = fetch_head(st, d_head, h)) return rc;
         if (h.n_small > 0)
             hipLaunchKernelGGL(km_small, dim3((h.n_small + 255) / 256), dim3(256), 0, st, A, h.n_small, off_next);
         HIP_TRY(hipGetLastError());
@@ -552,40 +536,48 @@ int mg_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const MgFiles &
     hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)A.blk_sum, nblk, A.blk_off, &d_head->n_out_bytes);
     hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)(A.blk_sum + nblk), nblk, A.blk_off + nblk, &d_head->n_kept);
     hipLaunchKernelGGL(km_outoff, dim3(lb), dim3(256), 0, st, A);
-    HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = fetch_head(st, d_head, h)) return rc;
     S.n_lines_out = h.n_kept;
     S.n_out_bytes = h.n_out_bytes;
     if (h.n_out_bytes > 0) {
-        if (!mg_fits((size_t)h.n_out_bytes)) return mg_decline(c, status, MC_MERGE_DECLINE_MEMORY, -1, -1);
+        if (!device_fits((size_t)h.n_out_bytes)) return mg_decline(c, status, MC_MERGE_DECLINE_MEMORY, -1, -1);
         if (pool.get(&A.out, (size_t)h.n_out_bytes)) return -10;
         hipLaunchKernelGGL(km_gather, dim3((unsigned)((n_lines + 3) / 4)), dim3(256), 0, st, A);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(st));
     }
     S.kernel_bytes += 2 * n_lines * (1 + 4 + 2) + n_lines * (8 + 1 + 4 + 8 + 8 + 2) + 2 * h.n_out_bytes;
-    S.ms_kernels = mg_ms_since(t_kernels);
+    S.ms_kernels = ms_since(t_kernels);
     *n_out = h.n_out_bytes;
     return 0;
 }
 
-void mg_begin(mc_ctx *c, int64_t n) {
+// what both entry points begin with: the sources' texts onto the device, one behind the other -> 0: go on; 1: done (declined,
+// *status set); < 0: an error
+int mg_upload(mc_ctx *c, MgCall &M, const TextSource *src, int n_src, int32_t *status) {
+    HIP_TRY(hipSetDevice(c->device));
+    M.t0 = std::chrono::steady_clock::now();
+    for (int i = 0; i < n_src; ++i) M.F.end.push_back(M.n += src[i].n);
     c->mg_stats = mc_rows_merge_stats();
     c->mg_stats.decline_line = -1;
     c->mg_stats.decline_file = -1;
-    c->mg_stats.n_bytes = n;
-}
-
-int mg_stages(mc_ctx *c, size_t block) {
-    if (c->mg_stage_cap < block) {
-        c->mg_stage_cap = 0;
-        for (Pinned &p : c->mg_stage)
-            if (int rc = p.alloc(block)) return rc;
-        c->mg_stage_cap = block;
+    c->mg_stats.n_bytes = M.n;
+    *status = 0;
+    if (!device_fits(2 * (size_t)M.n + 4096)) { (void)mg_decline(c, status, MC_MERGE_DECLINE_MEMORY, -1, -1); return 1; }
+    if (M.pool.get(&M.d_text, (size_t)M.n + 64)) return -10;
+    TextFeed feed(c, (size_t)64 << 20);
+    M.block = feed.block_for(M.n);
+    // files (a call's sources are all files or all texts): the stages sized once, before the first block, for the step of all
+    // texts together -- the output's
+    if (n_src > 0 && src[0].path)
+        if (int rc = feed.stages(M.block)) return rc;
+    for (int i = 0; i < n_src; ++i) {
+        char last = '\n';
+        if (int rc = feed.send(src[i], M.d_text + (M.F.end[i] - src[i].n), &last)) return rc;
+        if (last != '\n' && M.bad_end < 0) M.bad_end = M.F.end[i];
     }
-    for (Event &e : c->mg_ev)
-        if (!e.e)
-            if (int rc = e.create()) return rc;
+    if (int rc = feed.pad_and_wait(M.d_text + M.n)) return rc;
+    feed.times(c->mg_stats, M.t0);
     return 0;
 }
 
@@ -608,38 +600,22 @@ extern "C" int mc_rows_merge_text(mc_ctx *c, const char *text, int64_t n_bytes, 
         mc_set_error("mc_rows_merge_text: bad arguments");
         return -12;
     }
-    HIP_TRY(hipSetDevice(c->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    mg_begin(c, n_bytes);
-    *out = nullptr; *n_out = 0; *status = 0;
-    if (!mg_fits(2 * (size_t)n_bytes + 4096)) return mg_decline(c, status, MC_MERGE_DECLINE_MEMORY, -1, -1);
-    Pool pool("row merge");
-    char *d_text = nullptr;
-    if (pool.get(&d_text, (size_t)n_bytes + 64)) return -10;
-    if (n_bytes > 0) HIP_TRY(hipMemcpyAsync(d_text, text, (size_t)n_bytes, hipMemcpyHostToDevice, c->up_stream));
-    HIP_TRY(hipMemsetAsync(d_text + n_bytes, 0, 64, c->up_stream));
-    HIP_TRY(hipStreamSynchronize(c->up_stream));
-    c->mg_stats.ms_h2d = mg_ms_since(t0);
-    MgFiles F;
-    F.end.push_back(n_bytes);
-    const int64_t bad_end = n_bytes > 0 && text[n_bytes - 1] != '\n' ? n_bytes : -1;
-    MgArgs A = {};
-    int64_t nb = 0;
-    int rc = mg_run(c, pool, d_text, n_bytes, F, bad_end, A, &nb, status);
-    if (rc == 0 && *status == 0 && nb > 0) {
+    *out = nullptr; *n_out = 0;
+    const TextSource src = {text, nullptr, n_bytes};
+    MgCall M;
+    if (int rc = mg_upload(c, M, &src, 1, status)) return rc < 0 ? rc : 0;
+    int rc = mg_run(c, M.pool, M.d_text, M.n, M.F, M.bad_end, M.A, &M.nb, status);
+    if (rc == 0 && *status == 0 && M.nb > 0) {
         const auto t_d2h = std::chrono::steady_clock::now();
-        if (c->mg_out_cap < (size_t)nb) {
-            c->mg_out_cap = 0;
-            if (int rc2 = c->mg_out.alloc((size_t)nb + (size_t)nb / 4)) return rc2;
-            c->mg_out_cap = (size_t)nb + (size_t)nb / 4;
-        }
-        rc = mc_hip_rc(hipMemcpyAsync(c->mg_out.p, A.out, (size_t)nb, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync");
+        const size_t nb = (size_t)M.nb;
+        rc = grow(c->mg_out, c->mg_out_cap, nb);
+        if (rc == 0) rc = mc_hip_rc(hipMemcpyAsync(c->mg_out.p, M.A.out, nb, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync");
         if (rc == 0) rc = mc_hip_rc(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
-        c->mg_stats.ms_d2h = mg_ms_since(t_d2h);
-        if (rc == 0) { *out = (const char *)c->mg_out.p; *n_out = nb; }
+        c->mg_stats.ms_d2h = ms_since(t_d2h);
+        if (rc == 0) { *out = (const char *)c->mg_out.p; *n_out = M.nb; }
     }
     (void)hipStreamSynchronize(c->stream);                   // (an early return: nothing of the pool is in use when it goes)
-    c->mg_stats.ms_total = mg_ms_since(t0);
+    c->mg_stats.ms_total = ms_since(M.t0);
     return rc;
 }
 
@@ -649,56 +625,20 @@ extern "C" int mc_rows_merge_files(mc_ctx *c, const char *const *paths, int32_t 
         mc_set_error("mc_rows_merge_files: bad arguments");
         return -12;
     }
-    MgFiles F;
-    int64_t n = 0;
+    std::vector<TextSource> src((size_t)n_paths);
     for (int i = 0; i < n_paths; ++i) {
-        struct stat sb;
-        if (!paths[i] || stat(paths[i], &sb) != 0 || !S_ISREG(sb.st_mode)) {
-            mc_set_error("mc_rows_merge_files: %s is not a readable file", paths[i] ? paths[i] : "(null)");
-            return -1;
-        }
-        n += (int64_t)sb.st_size;
-        F.end.push_back(n);
+        src[i] = TextSource{nullptr, paths[i], 0};
+        if (int rc = regular_file_size("mc_rows_merge_files", paths[i], &src[i].n)) return rc;
     }
-    HIP_TRY(hipSetDevice(c->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    mg_begin(c, n);
-    *n_lines_out = 0; *status = 0;
-    if (!mg_fits(2 * (size_t)n + 4096)) return mg_decline(c, status, MC_MERGE_DECLINE_MEMORY, -1, -1);
-    Pool pool("row merge");
-    char *d_text = nullptr;
-    if (pool.get(&d_text, (size_t)n + 64)) return -10;
-    // the files in blocks, two pinned stages in turn: a block is read while the block before is on its way
-    if (int rc = mg_stages(c, (size_t)std::min<int64_t>(std::max<int64_t>(n, 4096), (int64_t)64 << 20))) return rc;
-    const int64_t cap = (int64_t)c->mg_stage_cap;
-    double ms_read = 0;
-    int rc = 0, turn = 0;
-    int64_t bad_end = -1, n_blocks = 0;
-    for (int i = 0; i < n_paths && rc == 0; ++i) {
-        const int64_t f0 = i ? F.end[i - 1] : 0, fn = F.end[i] - f0;
-        for (int64_t lo = 0; lo < fn && rc == 0; lo += cap, turn ^= 1, ++n_blocks) {
-            const int64_t hi = std::min<int64_t>(fn, lo + cap);
-            if (n_blocks >= 2) HIP_TRY(hipEventSynchronize(c->mg_ev[turn]));      // the copy out of this stage is done
-            const auto tr = std::chrono::steady_clock::now();
-            rc = mc_read_file_range(paths[i], lo, hi, c->mg_stage[turn].get<char>(), 0);
-            ms_read += mg_ms_since(tr);
-            if (rc) break;
-            if (hi == fn && c->mg_stage[turn].get<char>()[hi - lo - 1] != '\n' && bad_end < 0) bad_end = F.end[i];
-            HIP_TRY(hipMemcpyAsync(d_text + f0 + lo, c->mg_stage[turn].p, (size_t)(hi - lo), hipMemcpyHostToDevice, c->up_stream));
-            HIP_TRY(hipEventRecord(c->mg_ev[turn], c->up_stream));
-        }
-    }
-    HIP_TRY(hipMemsetAsync(d_text + n, 0, 64, c->up_stream));
-    HIP_TRY(hipStreamSynchronize(c->up_stream));
-    if (rc) return rc;
-    c->mg_stats.ms_read = ms_read;
-    c->mg_stats.ms_h2d = mg_ms_since(t0) - ms_read;          // what the copies added behind the reads they ran beside
-    MgArgs A = {};
-    int64_t nb = 0;
-    rc = mg_run(c, pool, d_text, n, F, bad_end, A, &nb, status);
+    *n_lines_out = 0;
+    MgCall M;
+    if (int rc = mg_upload(c, M, src.data(), n_paths, status)) return rc < 0 ? rc : 0;
+    int rc = mg_run(c, M.pool, M.d_text, M.n, M.F, M.bad_end, M.A, &M.nb, status);
     if (rc == 0 && *status == 0) {
-        // the output in blocks through the same two stages: a block is written while the next is on its way.  The file appears
+        // the output in blocks through the feed's two stages: a block is written while the next is on its way.  The file appears
         // under its name only when it is complete
+        TextStages &T = c->text_stages;
+        const int64_t nb = M.nb, cap = (int64_t)M.block;
         const std::string tmp = std::string(out_path) + ".merging";
         const int fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
         if (fd < 0) { mc_set_error("mc_rows_merge_files: cannot write %s: %s", tmp.c_str(), strerror(errno)); rc = -1; }
@@ -708,21 +648,21 @@ extern "C" int mc_rows_merge_files(mc_ctx *c, const char *const *paths, int32_t 
         const int64_t n_blocks_out = (nb + cap - 1) / cap;
         auto enqueue = [&](int64_t i) {
             const int64_t lo = i * cap, k = std::min<int64_t>(cap, nb - lo);
-            int r = mc_hip_rc(hipMemcpyAsync(c->mg_stage[i & 1].p, A.out + lo, (size_t)k, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync");
-            if (r == 0) r = mc_hip_rc(hipEventRecord(c->mg_ev[i & 1], c->stream), "hipEventRecord");
+            int r = mc_hip_rc(hipMemcpyAsync(T.stage[i & 1].p, M.A.out + lo, (size_t)k, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync");
+            if (r == 0) r = mc_hip_rc(hipEventRecord(T.ev[i & 1], c->stream), "hipEventRecord");
             return r;
         };
         if (rc == 0 && n_blocks_out > 0) rc = enqueue(0);
         for (int64_t i = 0; i < n_blocks_out && rc == 0; ++i) {
             if (i + 1 < n_blocks_out) rc = enqueue(i + 1);
-            if (rc == 0) rc = mc_hip_rc(hipEventSynchronize(c->mg_ev[i & 1]), "hipEventSynchronize");
+            if (rc == 0) rc = mc_hip_rc(hipEventSynchronize(T.ev[i & 1]), "hipEventSynchronize");
             if (rc) break;
             const auto tw = std::chrono::steady_clock::now();
-            if (mg_write_all(fd, c->mg_stage[i & 1].get<char>(), (size_t)std::min<int64_t>(cap, nb - i * cap))) {
+            if (mg_write_all(fd, T.stage[i & 1].get<char>(), (size_t)std::min<int64_t>(cap, nb - i * cap))) {
                 mc_set_error("mc_rows_merge_files: writing %s failed: %s", tmp.c_str(), strerror(errno));
                 rc = -1;
             }
-            ms_write += mg_ms_since(tw);
+            ms_write += ms_since(tw);
         }
         if (fd >= 0 && close(fd) != 0 && rc == 0) { mc_set_error("mc_rows_merge_files: closing %s failed: %s", tmp.c_str(), strerror(errno)); rc = -1; }
         if (rc == 0 && rename(tmp.c_str(), out_path) != 0) {
@@ -731,11 +671,11 @@ extern "C" int mc_rows_merge_files(mc_ctx *c, const char *const *paths, int32_t 
         }
         if (rc != 0 && fd >= 0) (void)unlink(tmp.c_str());
         c->mg_stats.ms_write = ms_write;
-        c->mg_stats.ms_d2h = mg_ms_since(t_out) - ms_write;
+        c->mg_stats.ms_d2h = ms_since(t_out) - ms_write;
         if (rc == 0) *n_lines_out = c->mg_stats.n_lines_out;
     }
     (void)hipStreamSynchronize(c->stream);
-    c->mg_stats.ms_total = mg_ms_since(t0);
+    c->mg_stats.ms_total = ms_since(M.t0);
     return rc;
 }
 
@@ -751,7 +691,6 @@ extern "C" int mc_rows_merge_release(mc_ctx *c) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipStreamSynchronize(c->up_stream));
     c->mg_out.reset(); c->mg_out_cap = 0;
-    for (Pinned &p : c->mg_stage) p.reset();
-    c->mg_stage_cap = 0;
+    c->text_stages.release();
     return 0;
 }

@@ -21,7 +21,7 @@
 //   * a text that does not fit into free device memory beside its outputs: the WHOLE text stays resident
 //
 // The steps (one lane per line unless said otherwise; n = lines):
-//   kp_count / kp_scan / kp_starts   line starts (the device parser's kernels: mc_lines.h)
+//   kp_count / kp_scan / kp_starts   line starts (the device parser's kernels: mc_lines.h, launched by mc_textfeed.h)
 //   kt_parse     256 lines of a workgroup staged in LDS with 16-byte loads (a piece that does not fit: read in place); per line the
 //                class of every byte, the tabs, the context's span and centre pair, the stripped label's span and a 64-bit hash
 //                of its bytes, the commas of the feature field, the literal-"0" test, the kept flag.  A flagged line: atomicMin of
@@ -35,15 +35,12 @@
 //                lists the row's feature tokens (offset | length << 16) and checks its feature count
 //   kt_place     a lane per NUMBER: mc_decimal.h on the token -> X[row][j]; lane j = 0 copies the context, NUL-padded
 // wave64; no library sort; every buffer, event and stream through the owners of mc_own.h.
-#include "../mc_lines.h"
+// The host side around the kernels -- a file's way onto the device through the context's two pinned stages, the line starts, the
+// head's way back, the decline, the clock -- is mc_textfeed.h's, shared with the other three units that take a whole text file.
+#include "../mc_textfeed.h"
 #include "../mc_decimal.h"
 
-#include <sys/stat.h>
-
-#include <chrono>
 #include <cstring>
-
-extern "C" int mc_read_file_range(const char *path, int64_t lo, int64_t hi, char *dst, int32_t n_threads);
 
 namespace {
 
@@ -319,37 +316,12 @@ const char *tr_reason_text(int reason) {
     return "unknown";
 }
 
-double tr_ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 int tr_decline(mc_ctx *c, int32_t *status, int reason, long long line) {
-    c->tr_stats.decline_reason = reason;
-    c->tr_stats.decline_line = line;
-    if (line >= 0) mc_set_error("the device reader declines: %s (line %lld)", tr_reason_text(reason), line + 1);
-    else mc_set_error("the device reader declines: %s", tr_reason_text(reason));
-    *status = 1;
-    return 0;
+    return decline(c->tr_stats, status, "reader", tr_reason_text(reason), reason, line);
 }
 
 int tr_decline_head(mc_ctx *c, int32_t *status, const TrHead &h) {
-    return tr_decline(c, status, (int)(h.decline & 0xff), (long long)(h.decline >> 8));
-}
-
-// does `bytes` more fit into device memory, with a margin for what the runtime and the other buffers of the context take
-bool tr_fits(size_t bytes) {
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return false; }
-    const size_t margin = (size_t)256 << 20;
-    return free_b > margin && bytes <= free_b - margin;
-}
-
-int tr_grow(Pinned &p, size_t &cap, size_t bytes) {
-    if (cap >= bytes) return 0;
-    cap = 0;
-    if (int rc = p.alloc(bytes + bytes / 4)) return rc;
-    cap = bytes + bytes / 4;
-    return 0;
+    return tr_decline(c, status, decline_reason(h.decline), decline_line(h.decline));
 }
 
 // The text is on the device (d_text[0, n), padded; copies enqueued on c->up_stream): everything behind that
@@ -365,25 +337,16 @@ int tr_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *pai
     for (int s = 0; s < TR_SLOTS; ++s) h.first[s] = ~0ull;
     for (int k = 0; k < n_pairs; ++k) h.pairs[k] = (uint16_t)((unsigned char)pairs[2 * k] | ((unsigned)(unsigned char)pairs[2 * k + 1] << 8));
     HIP_TRY(hipMemcpyAsync(d_head, &h, sizeof h, hipMemcpyHostToDevice, st));
-    const int64_t n_tiles = (n + KP_TILE - 1) / KP_TILE;
-    long long *tile_cnt = nullptr, *tile_off = nullptr;
-    if (pool.get(&tile_cnt, (size_t)n_tiles) || pool.get(&tile_off, (size_t)n_tiles)) return -10;
-    hipLaunchKernelGGL(kp_count, dim3((unsigned)n_tiles), dim3(KP_THREADS), 0, st, d_text, n, tile_cnt);
-    hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)tile_cnt, n_tiles, tile_off, &d_head->kp.n_newlines);
-    HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    long long *tile_off = nullptr, *line_start = nullptr;
+    if (int rc = lines_count(pool, st, d_text, n, &d_head->kp, &tile_off)) return rc;
+    if (int rc = fetch_head(st, d_head, h)) return rc;
     const int64_t n_nl = h.kp.n_newlines;
-    if (n_nl + 1 >= ((int64_t)1 << 31) - 2) return tr_decline(c, status, MC_TRAINROWS_DECLINE_ROWS, -1);
-    const int64_t cap_lines = n_nl + 2;
+    if (too_many_lines(n_nl)) return tr_decline(c, status, MC_TRAINROWS_DECLINE_ROWS, -1);
     // per line: the start, the row, the hash, the slot; per workgroup the counts and their offsets
-    if (!tr_fits((size_t)cap_lines * (8 + 16 + 8 + 1 + 1) + ((size_t)1 << 20))) return tr_decline(c, status, MC_TRAINROWS_DECLINE_MEMORY, -1);
+    if (!device_fits((size_t)(n_nl + 2) * (8 + 16 + 8 + 1 + 1) + ((size_t)1 << 20))) return tr_decline(c, status, MC_TRAINROWS_DECLINE_MEMORY, -1);
     TrArgs A = {};
-    long long *line_start = nullptr;
-    if (pool.get(&line_start, (size_t)cap_lines)) return -10;
-    hipLaunchKernelGGL(kp_starts, dim3((unsigned)n_tiles), dim3(KP_THREADS), 0, st, d_text, n, (const long long *)tile_off, line_start,
-                       cap_lines, &d_head->kp);
-    HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = lines_starts(pool, st, d_text, n, n_nl, tile_off, &d_head->kp, &line_start)) return rc;
+    if (int rc = fetch_head(st, d_head, h)) return rc;
     const int64_t n_lines = h.kp.n_lines;
     S.n_lines = n_lines;
     A.text = d_text; A.n_bytes = n; A.n_lines = n_lines; A.n_nl = n_nl; A.line_start = line_start; A.head = d_head;
@@ -395,13 +358,11 @@ int tr_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *pai
     A.nblk = lb;
     if (pool.get(&A.row, nl) || pool.get(&A.hash, nl) || pool.get(&A.slot, nl)) return -10;
     hipLaunchKernelGGL(kt_parse, dim3(lb), dim3(256), TR_STAGE + 16, st, A);
-    HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = fetch_head(st, d_head, h)) return rc;
     S.in_place_blocks = (int32_t)h.in_place;
     if (h.decline != ~0ull) return tr_decline_head(c, status, h);
     hipLaunchKernelGGL(kt_intern, dim3(lb), dim3(256), 0, st, A);
-    HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = fetch_head(st, d_head, h)) return rc;
     if (h.n_claimed > MC_TRAINROWS_MAX_LABELS) return tr_decline(c, status, MC_TRAINROWS_DECLINE_LABELS, -1);
     // the labels in the order of the lines that registered them
     int slots[MC_TRAINROWS_MAX_LABELS], n_labels = 0;
@@ -431,16 +392,15 @@ int tr_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *pai
     A.n_kept = n_kept;
     if (n_kept > 0) {
         const size_t nk = (size_t)n_kept, nx = nk * (size_t)A.nf;
-        if (!tr_fits(nk * 4 + nx * 12 + nk * (size_t)A.ctx_w)) return tr_decline(c, status, MC_TRAINROWS_DECLINE_MEMORY, -1);
+        if (!device_fits(nk * 4 + nx * 12 + nk * (size_t)A.ctx_w)) return tr_decline(c, status, MC_TRAINROWS_DECLINE_MEMORY, -1);
         if (pool.get(&A.row_line, nk) || pool.get(&A.tok, nx) || pool.get(&A.X, nx) || pool.get(&A.ctx, nk * (size_t)A.ctx_w)) return -10;
         hipLaunchKernelGGL(kt_rank, dim3(lb), dim3(256), 0, st, A);
         hipLaunchKernelGGL(kt_place, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, st, A);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&h, d_head, sizeof h, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        if (int rc = fetch_head(st, d_head, h)) return rc;
         if (h.decline != ~0ull) return tr_decline_head(c, status, h);
     }
-    S.ms_kernels = tr_ms_since(t_kernels);
+    S.ms_kernels = ms_since(t_kernels);
     const auto t_d2h = std::chrono::steady_clock::now();
     // the labels' bytes: where the row that claimed the slot has them
     c->tr_labels.clear();
@@ -460,15 +420,15 @@ int tr_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *pai
     }
     if (n_kept > 0) {
         const size_t xb = (size_t)n_kept * (size_t)A.nf * 8, cb = (size_t)n_kept * (size_t)A.ctx_w;
-        if (int rc = tr_grow(c->tr_X, c->tr_X_cap, xb)) return rc;
-        if (int rc = tr_grow(c->tr_ctx, c->tr_ctx_cap, cb)) return rc;
+        if (int rc = grow(c->tr_X, c->tr_X_cap, xb)) return rc;
+        if (int rc = grow(c->tr_ctx, c->tr_ctx_cap, cb)) return rc;
         HIP_TRY(hipMemcpyAsync(c->tr_X.p, A.X, xb, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(c->tr_ctx.p, A.ctx, cb, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         V->X = c->tr_X.get<double>();
         V->contexts = c->tr_ctx.get<char>();
     }
-    S.ms_d2h = tr_ms_since(t_d2h);
+    S.ms_d2h = ms_since(t_d2h);
     V->n_labels = n_labels;
     V->n_features = n_kept > 0 ? A.nf : 0;
     V->ctx_width = n_kept > 0 ? A.ctx_w : 0;
@@ -488,8 +448,25 @@ int tr_begin(mc_ctx *c, const char *pairs, int32_t n_pairs, mc_train_rows_view *
         mc_set_error("mc_train_rows: 0 to %d centre pairs", MC_TRAINROWS_MAX_PAIRS);
         return -12;
     }
-    if (!tr_fits((size_t)n + 4096)) { (void)tr_decline(c, status, MC_TRAINROWS_DECLINE_MEMORY, -1); return 1; }
+    if (!device_fits((size_t)n + 4096)) { (void)tr_decline(c, status, MC_TRAINROWS_DECLINE_MEMORY, -1); return 1; }
     return 0;
+}
+
+// what both entry points run: the text of `src` onto the device and through tr_run
+int tr_call(mc_ctx *c, const TextSource &src, const char *pairs, int32_t n_pairs, mc_train_rows_view *out, int32_t *status) {
+    HIP_TRY(hipSetDevice(c->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    if (int rc = tr_begin(c, pairs, n_pairs, out, status, src.n)) return rc < 0 ? rc : 0;
+    Pool pool("training rows");
+    TextFeed feed(c, (size_t)64 << 20);
+    char *d_text = nullptr;
+    if (int rc = feed.put(pool, src, &d_text)) return rc;
+    feed.times(c->tr_stats, t0);
+    const int rc = tr_run(c, pool, d_text, src.n, pairs, n_pairs, out, status);
+    (void)hipStreamSynchronize(c->stream);                   // (an early return: nothing of the pool is in use when it goes)
+    if (rc != 0 || *status != 0) *out = mc_train_rows_view();
+    c->tr_stats.ms_total = ms_since(t0);
+    return rc;
 }
 
 }  // namespace
@@ -500,21 +477,7 @@ extern "C" int mc_train_rows_text(mc_ctx *c, const char *text, int64_t n_bytes, 
         mc_set_error("mc_train_rows_text: bad arguments");
         return -12;
     }
-    HIP_TRY(hipSetDevice(c->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    if (int rc = tr_begin(c, pairs, n_pairs, out, status, n_bytes)) return rc < 0 ? rc : 0;
-    Pool pool("training rows");
-    char *d_text = nullptr;
-    if (pool.get(&d_text, (size_t)n_bytes + 64)) return -10;
-    if (n_bytes > 0) HIP_TRY(hipMemcpyAsync(d_text, text, (size_t)n_bytes, hipMemcpyHostToDevice, c->up_stream));
-    HIP_TRY(hipMemsetAsync(d_text + n_bytes, 0, 64, c->up_stream));
-    HIP_TRY(hipStreamSynchronize(c->up_stream));
-    c->tr_stats.ms_h2d = tr_ms_since(t0);
-    const int rc = tr_run(c, pool, d_text, n_bytes, pairs, n_pairs, out, status);
-    (void)hipStreamSynchronize(c->stream);                   // (an early return: nothing of the pool is in use when it goes)
-    if (rc != 0 || *status != 0) *out = mc_train_rows_view();
-    c->tr_stats.ms_total = tr_ms_since(t0);
-    return rc;
+    return tr_call(c, TextSource{text, nullptr, n_bytes}, pairs, n_pairs, out, status);
 }
 
 extern "C" int mc_train_rows_file(mc_ctx *c, const char *path, const char *pairs, int32_t n_pairs, mc_train_rows_view *out, int32_t *status) {
@@ -522,51 +485,9 @@ extern "C" int mc_train_rows_file(mc_ctx *c, const char *path, const char *pairs
         mc_set_error("mc_train_rows_file: bad arguments");
         return -12;
     }
-    struct stat sb;
-    if (stat(path, &sb) != 0 || !S_ISREG(sb.st_mode)) {
-        mc_set_error("mc_train_rows_file: %s is not a readable file", path);
-        return -1;
-    }
-    const int64_t n = (int64_t)sb.st_size;
-    HIP_TRY(hipSetDevice(c->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    if (int rc = tr_begin(c, pairs, n_pairs, out, status, n)) return rc < 0 ? rc : 0;
-    Pool pool("training rows");
-    char *d_text = nullptr;
-    if (pool.get(&d_text, (size_t)n + 64)) return -10;
-    // the file in blocks, two pinned stages in turn: block i is read while block i - 1 is on its way
-    const size_t block = (size_t)std::min<int64_t>(std::max<int64_t>(n, 4096), (int64_t)64 << 20);
-    if (c->tr_stage_cap < block) {
-        c->tr_stage_cap = 0;
-        for (Pinned &p : c->tr_stage)
-            if (int rc = p.alloc(block)) return rc;
-        c->tr_stage_cap = block;
-    }
-    for (Event &e : c->tr_ev)
-        if (!e.e)
-            if (int rc = e.create()) return rc;
-    double ms_read = 0;
-    int rc = 0, turn = 0;
-    for (int64_t lo = 0; lo < n && rc == 0; lo += (int64_t)c->tr_stage_cap, turn ^= 1) {
-        const int64_t hi = std::min<int64_t>(n, lo + (int64_t)c->tr_stage_cap);
-        if (lo >= 2 * (int64_t)c->tr_stage_cap) HIP_TRY(hipEventSynchronize(c->tr_ev[turn]));     // the copy out of this stage is done
-        const auto tr = std::chrono::steady_clock::now();
-        rc = mc_read_file_range(path, lo, hi, c->tr_stage[turn].get<char>(), 0);
-        ms_read += tr_ms_since(tr);
-        if (rc) break;
-        HIP_TRY(hipMemcpyAsync(d_text + lo, c->tr_stage[turn].p, (size_t)(hi - lo), hipMemcpyHostToDevice, c->up_stream));
-        HIP_TRY(hipEventRecord(c->tr_ev[turn], c->up_stream));
-    }
-    HIP_TRY(hipMemsetAsync(d_text + n, 0, 64, c->up_stream));
-    HIP_TRY(hipStreamSynchronize(c->up_stream));
-    if (rc) return rc;
-    c->tr_stats.ms_read = ms_read;
-    c->tr_stats.ms_h2d = tr_ms_since(t0) - ms_read;          // what the copies added behind the reads they ran beside
-    rc = tr_run(c, pool, d_text, n, pairs, n_pairs, out, status);
-    (void)hipStreamSynchronize(c->stream);
-    if (rc != 0 || *status != 0) *out = mc_train_rows_view();
-    c->tr_stats.ms_total = tr_ms_since(t0);
-    return rc;
+    int64_t n = 0;
+    if (int rc = regular_file_size("mc_train_rows_file", path, &n)) return rc;
+    return tr_call(c, TextSource{nullptr, path, n}, pairs, n_pairs, out, status);
 }
 
 extern "C" int mc_train_rows_last_stats(mc_ctx *c, mc_train_rows_stats *out) {
@@ -583,8 +504,7 @@ extern "C" int mc_train_rows_release(mc_ctx *c) {
     c->tr_X.reset(); c->tr_X_cap = 0;
     c->tr_ctx.reset(); c->tr_ctx_cap = 0;
     std::string().swap(c->tr_labels);
-    for (Pinned &p : c->tr_stage) p.reset();
-    c->tr_stage_cap = 0;
+    c->text_stages.release();
     return 0;
 }
 

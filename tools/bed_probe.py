@@ -77,14 +77,18 @@ def main():
         for vo in (False, True):
             outs = [os.path.join(d, 'host.bed'), os.path.join(d, 'device.bed')]
             host = lambda: make_bed.summarise_diffs(path, outs[0], 1, 0.5, with_probs=vo, quiet=True)
-            dev = lambda: make_bed.summarise_diffs_device(path, outs[1], 1, 0.5, with_probs=vo, quiet=True)
+            ms_all = []                                        # the call's own split of every device run, the warm-up included
+
+            def dev():
+                make_bed.summarise_diffs_device(path, outs[1], 1, 0.5, with_probs=vo, quiet=True)
+                ms_all.append({k: v for k, v in get_device().bed_last_stats().items() if k.startswith('ms_')})
             t_dev, all_dev = timed(dev, runs)
             assert make_bed.last_summary['by'] == 'device', make_bed.last_summary
             st = get_device().bed_last_stats()
             t_host, all_host = timed(host, host_runs, warm=host_runs > 1)       # (a single host run: the interpreter has nothing to warm)
             assert open(outs[0], 'rb').read() == open(outs[1], 'rb').read(), 'the device summary differs from the host function\'s'
             r = dict(rows=rows, file_bytes=os.path.getsize(path), vo=vo, host_s=t_host, device_s=t_dev, ratio=t_host / t_dev,
-                     host_runs=host_runs, device_runs=runs, host_all_s=all_host, device_all_s=all_dev, stats=st,
+                     host_runs=host_runs, device_runs=runs, host_all_s=all_host, device_all_s=all_dev, device_all_ms=ms_all[-runs:], stats=st,
                      kernel_ms=st['ms_kernels'], kernel_bytes=st['kernel_bytes'],
                      kernel_fraction_of_peak=st['kernel_bytes'] / (st['ms_kernels'] * 1e-3) / PEAK_BYTES_PER_S if st['ms_kernels'] > 0 else None)
             results.append(r)

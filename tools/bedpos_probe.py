@@ -83,14 +83,15 @@ def main():
             make_bed.summarise_diffs_device(path, outs[1], 15, 0.5, positions=pos, with_probs=False, quiet=True)
             assert make_bed.last_summary['by'] == 'device', make_bed.last_summary
         device()                                           # warm-up: pinned blocks, the first launches
-        t_dev, t_host = [], []
+        t_dev, t_host, ms_all = [], [], []
         for _ in range(runs):
             t = time.perf_counter()
             device()
             t_dev.append(time.perf_counter() - t)
+            ms_all.append({k: v for k, v in get_device().bed_last_stats().items() if k.startswith('ms_')})       # the call's own split of the run
         st = get_device().bed_last_stats()
         r = dict(rows=n_rows, sites=n_sites, rows_at_listed_sites=wanted, file_bytes=os.path.getsize(path), positions_bytes=os.path.getsize(pos),
-                 device_s=statistics.median(t_dev), device_all_s=t_dev, device_runs=runs, stats=st, kernel_ms=st['ms_kernels'])
+                 device_s=statistics.median(t_dev), device_all_s=t_dev, device_all_ms=ms_all, device_runs=runs, stats=st, kernel_ms=st['ms_kernels'])
         if not device_only:
             for _ in range(host_runs):
                 t = time.perf_counter()

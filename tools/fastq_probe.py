@@ -93,14 +93,15 @@ def main():
             got['host'] = read_qual.extract_read_quality(path)
 
         device()                                                # warm-up: pinned blocks, the first launches, the file in the page cache
-        t_dev, t_host, st = [], [], None
+        t_dev, t_host, ms_all, st = [], [], [], None
         for _ in range(runs):
             t = time.perf_counter()
             device()
             t_dev.append(time.perf_counter() - t)
             st = get_device().fastq_qualities_last_stats()
+            ms_all.append({k: v for k, v in st.items() if k.startswith('ms_')})       # the call's own split of the run
         r = dict(reads=n, file_bytes=n_bytes, bases=n_bases, reads_above_1e5=n_long, longest_read=longest, device_s=statistics.median(t_dev),
-                 device_all_s=t_dev, device_runs=runs, stats=st, kernel_ms=st['ms_kernels'], piece_bytes=st['piece_bytes'],
+                 device_all_s=t_dev, device_all_ms=ms_all, device_runs=runs, stats=st, kernel_ms=st['ms_kernels'], piece_bytes=st['piece_bytes'],
                  kernel_bytes=3 * n_bytes + n_bases,           # the text three times (newlines twice, the classes), the quality lines once
                  kernel_fraction_of_peak=(3 * n_bytes + n_bases) / (st['ms_kernels'] * 1e-3) / PEAK_BYTES_PER_S if st['ms_kernels'] > 0 else None)
         if not device_only:

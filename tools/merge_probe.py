@@ -106,7 +106,7 @@ def main():
         outs = [os.path.join(d, 'host.merged'), os.path.join(d, 'device.merged')]
         mCaller.merge_like_sort_uniq_device(link_parts(masters, d), outs[1])          # warm-up: pinned blocks, the first launches
         assert mCaller.last_merge['by'] == 'device', mCaller.last_merge
-        t_dev, t_host, st = [], [], None
+        t_dev, t_host, ms_all, st = [], [], [], None
         for i in range(max(runs, 0 if device_only else host_runs)):
             if i < runs:
                 paths = link_parts(masters, d)
@@ -115,12 +115,13 @@ def main():
                 t_dev.append(time.perf_counter() - t)
                 assert mCaller.last_merge['by'] == 'device', mCaller.last_merge
                 st = get_device().merge_rows_last_stats()
+                ms_all.append({k: v for k, v in st.items() if k.startswith('ms_')})       # the call's own split of the run
             if i < host_runs and not device_only:
                 paths = link_parts(masters, d)
                 t = time.perf_counter()
                 mCaller.merge_like_sort_uniq(paths, outs[0])
                 t_host.append(time.perf_counter() - t)
-        r = dict(rows=rows, parts=n_parts, file_bytes=n_bytes, device_s=statistics.median(t_dev), device_all_s=t_dev, device_runs=runs, stats=st,
+        r = dict(rows=rows, parts=n_parts, file_bytes=n_bytes, device_s=statistics.median(t_dev), device_all_s=t_dev, device_all_ms=ms_all, device_runs=runs, stats=st,
                  rounds=st['n_rounds'], passes=st['n_passes'], kernel_ms=st['ms_kernels'], kernel_bytes=st['kernel_bytes'],
                  kernel_fraction_of_peak=st['kernel_bytes'] / (st['ms_kernels'] * 1e-3) / PEAK_BYTES_PER_S if st['ms_kernels'] > 0 else None)
         if t_host:

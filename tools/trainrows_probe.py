@@ -96,7 +96,9 @@ def main():
             t2 = time.perf_counter()
             parts['device'] = dict(tsv2matrix_device_s=t1 - t0, balance_s=t2 - t1)
             got['device'] = (labs, X, grps)
+            ms_all.append({k: v for k, v in get_device().training_rows_last_stats().items() if k.startswith('ms_')})       # the call's own split of the run
 
+        ms_all = []
         t_dev, all_dev = timed(device, runs)
         st = get_device().training_rows_last_stats()
         t_host, all_host = timed(host, host_runs, warm=host_runs > 1)
@@ -104,7 +106,7 @@ def main():
         assert h[0] == v[0] and h[1].tobytes() == v[1].tobytes() and h[2] == [c.decode('ascii') for c in v[2].tolist()], \
             'the device matrices differ from the host function\'s'
         r = dict(rows=n, file_bytes=n_bytes, host_s=t_host, device_s=t_dev, ratio=t_host / t_dev, host_runs=host_runs, device_runs=runs,
-                 host_all_s=all_host, device_all_s=all_dev, host_parts=parts['host'], device_parts=parts['device'], stats=st,
+                 host_all_s=all_host, device_all_s=all_dev, device_all_ms=ms_all[-runs:], host_parts=parts['host'], device_parts=parts['device'], stats=st,
                  kernel_ms=st['ms_kernels'])
         results.append(r)
         print('%9d rows  host %7.3f s (tsv2matrix %.3f)  device %7.4f s  x%-6.1f  read %.1f ms, H2D %.1f ms, kernels %.2f ms, D2H %.1f ms, '
