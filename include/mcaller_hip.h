@@ -860,6 +860,63 @@ int mc_fastq_quality_release(mc_ctx *ctx);
 int mc_fastq_records_host(const char *text, int64_t n_bytes, mc_fastq **out, int32_t *status);
 int mc_fastq_records_host_decline(int32_t *reason, int64_t *line);
 
+/* ===== two `make_bed --vo` BED files compared per site on the GPU (mcaller_amd/compare_genomes.py; csrc/mc_twosample.h,
+ * csrc/compare/mc_bedcompare.hip) =====
+ * One row per key (chrom, start, end, strand) of bed1 that bed2 also has, in bed1's file order: the two samples' Mann-Whitney,
+ * rank-sum, Student and Kolmogorov-Smirnov statistics and -log10 p values.  The bytes are those of
+ * compare_genomes.compare_by_position, or the call declines -- *status = 1, mc_last_error says why (mc_bed_compare_last_stats:
+ * which file, line and reason), nothing is handed out and the caller runs the host statement, which words the errors.
+ * Declined: MC_CMP_DECLINE_* below; of several offending lines the first is named (bed1's before bed2's), of several reasons
+ * on it the smallest.  *out points at n_out bytes of pinned memory owned by the context: valid until the next
+ * mc_bed_compare_* call on it or mc_bed_compare_release.
+ * mc_twosample: the arithmetic of one site by the host build of csrc/mc_twosample.h (needs no GPU) -> 0; out[9] = U, z_mwu, z_rs,
+ * t, D, nlp_mwu, nlp_rs, nlp_t, nlp_ks (U and D as they are, the others rounded to three places), bound[9] the bound on
+ * |device - host| of each before rounding, *status the TW_* bits of that header (0: every value is vouched for); -12: bad
+ * arguments.  mc_twosample_device: the device build on k sites, site i = x[x_off[i], x_off[i + 1]) against y[y_off[i], y_off[i + 1])
+ * -> out[k][9], bound[k][9], status[k].  mc_twosample_log10_2sf / _log10_kolmogorov: the two tail functions of the host build. */
+typedef struct mc_cmp_stats {
+    int64_t n_bytes1, n_bytes2, n_lines1, n_lines2;
+    int64_t n_keys2;               /* bed2's lines in the table                                  */
+    int64_t n_sites;               /* keys both files have                                       */
+    int64_t n_values;              /* probabilities of the shared sites, both samples            */
+    int64_t n_rank_small, n_rank_large;   /* sites a wave ranked (<= 64 pooled values), sites a workgroup ranked */
+    int64_t n_out_bytes, table_slots;
+    int64_t decline_line;          /* 0-based line in its file the decline names, -1: none       */
+    int32_t decline_reason;        /* 0: not declined; MC_CMP_DECLINE_*                          */
+    int32_t decline_file;          /* 1: bed1, 2: bed2, 0: none                                  */
+    int32_t longest_probe;         /* slots the longest probe of the table looked at             */
+    int32_t deepest_site;          /* pooled values of the deepest shared site                   */
+    double ms_read, ms_h2d, ms_kernels, ms_d2h, ms_total;
+} mc_cmp_stats;
+#define MC_CMP_DECLINE_HIGH_BYTE   1   /* a byte >= 0x80                                                                  */
+#define MC_CMP_DECLINE_CONTROL     2   /* a control byte other than tab and newline (0x7f and '\r' included)               */
+#define MC_CMP_DECLINE_FIELDS      3   /* a line that does not have exactly 8 tab-separated fields (the host's ValueError) */
+#define MC_CMP_DECLINE_EMPTY       4   /* an empty chrom, start, end or strand, or an empty probability list              */
+#define MC_CMP_DECLINE_LONG_LINE   5   /* a line longer than 65535 bytes                                                  */
+#define MC_CMP_DECLINE_ROWS        6   /* 2^31 - 2 lines or more in the two files together                                */
+#define MC_CMP_DECLINE_MEMORY      7   /* the texts do not fit into free device memory beside their tables                */
+#define MC_CMP_DECLINE_TABLE       8   /* the key table is full (MCALLER_CMP_TABLE_SLOTS)                                 */
+#define MC_CMP_DECLINE_DUPLICATE   9   /* a key that occurs twice in one file (the host's dict rule does the file)        */
+#define MC_CMP_DECLINE_NUMBER      10  /* a probability, on any line of either file, that mc_decimal.h declines            */
+#define MC_CMP_DECLINE_DEPTH       11  /* a shared site with more than 8192 pooled values                                 */
+#define MC_CMP_DECLINE_NAN         12  /* fewer than 3 pooled values or a zero pooled variance (SciPy's nan)              */
+#define MC_CMP_DECLINE_ALL_EQUAL   13  /* all pooled values of a shared site equal (SciPy's nan)                          */
+#define MC_CMP_DECLINE_FAR_TAIL    14  /* a log10 p below -290                                                            */
+#define MC_CMP_DECLINE_PRINT       15  /* a value mc_rowtext.h does not print                                             */
+#define MC_CMP_DECLINE_TIE         16  /* a value within its error bound of a rounding tie of np.round(., 3)              */
+int mc_bed_compare_text(mc_ctx *ctx, const char *text1, int64_t n_bytes1, const char *text2, int64_t n_bytes2, const char **out,
+                        int64_t *n_out, int64_t *n_sites, int32_t *status);
+/* ... of two files: read in pinned blocks (mc_read_file_range) while the block before is on its way to the device. */
+int mc_bed_compare_file(mc_ctx *ctx, const char *path1, const char *path2, const char **out, int64_t *n_out, int64_t *n_sites,
+                        int32_t *status);
+int mc_bed_compare_last_stats(mc_ctx *ctx, mc_cmp_stats *out);
+int mc_bed_compare_release(mc_ctx *ctx);
+int mc_twosample(const double *x, int64_t n1, const double *y, int64_t n2, double *out, double *bound, int32_t *status);
+int mc_twosample_device(mc_ctx *ctx, const double *x, const int64_t *x_off, const double *y, const int64_t *y_off, int64_t k,
+                        double *out, double *bound, int32_t *status);
+double mc_twosample_log10_2sf(double z);
+double mc_twosample_log10_kolmogorov(double lam);
+
 /* ===== measurement plumbing: a table as nanopolish-eventalign text (13 columns), written by all host cores =====
  * For file-to-file timing on synthetic workloads (bench.py); seq = the contig's bases (k-mers of columns 3 and 10). */
 int mc_synth_write_tsv(const char *path, const mc_table_view *table, const char *seq, int64_t seq_len, const char *contig,

@@ -148,6 +148,22 @@ class FastqQualityStats(C.Structure):
                 ('ms_h2d', C.c_double), ('ms_kernels', C.c_double), ('ms_d2h', C.c_double), ('ms_total', C.c_double)]
 
 
+class CmpStats(C.Structure):
+    """mc_cmp_stats (include/mcaller_hip.h)."""
+    _fields_ = [('n_bytes1', C.c_int64), ('n_bytes2', C.c_int64), ('n_lines1', C.c_int64), ('n_lines2', C.c_int64),
+                ('n_keys2', C.c_int64), ('n_sites', C.c_int64), ('n_values', C.c_int64), ('n_rank_small', C.c_int64),
+                ('n_rank_large', C.c_int64), ('n_out_bytes', C.c_int64), ('table_slots', C.c_int64), ('decline_line', C.c_int64),
+                ('decline_reason', C.c_int32), ('decline_file', C.c_int32), ('longest_probe', C.c_int32),
+                ('deepest_site', C.c_int32), ('ms_read', C.c_double), ('ms_h2d', C.c_double), ('ms_kernels', C.c_double),
+                ('ms_d2h', C.c_double), ('ms_total', C.c_double)]
+
+
+CMP_DECLINE = {'high_byte': 1, 'control': 2, 'fields': 3, 'empty': 4, 'long_line': 5, 'rows': 6, 'memory': 7, 'table': 8,
+               'duplicate': 9, 'number': 10, 'depth': 11, 'nan': 12, 'all_equal': 13, 'far_tail': 14, 'print': 15,
+               'tie': 16}                                                                        # MC_CMP_DECLINE_*
+TW_STATUS = {'bad_n': 1, 'zero_var': 2, 'far_tail': 4, 'no_convergence': 8, 'all_equal': 16, 'tie': 32, 'unprintable': 64,
+             'deep': 128}                                                                        # TW_* (csrc/mc_twosample.h)
+TW_NAMES = ('U', 'z_mwu', 'z_rs', 't', 'D', 'nlp_mwu', 'nlp_rs', 'nlp_t', 'nlp_ks')
 FASTQ_DECLINE = {'high_byte': 1, 'control': 2, 'lone_cr': 3, 'title': 4, 'plus': 5, 'length': 6, 'empty_id': 7, 'rows': 8,
                  'memory': 9, 'gz': 10}                                                          # MC_FASTQ_DECLINE_*
 MERGE_DECLINE = {'cr': 1, 'no_newline': 2, 'key': 3, 'long_line': 4, 'rows': 5, 'memory': 6}     # MC_MERGE_DECLINE_*
@@ -189,6 +205,19 @@ def lib():
         L.mc_fastq_quality_file.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(FastqQualityView), C.POINTER(C.c_int32)]
         L.mc_fastq_quality_last_stats.argtypes = [C.c_void_p, C.POINTER(FastqQualityStats)]
         L.mc_fastq_quality_release.argtypes = [C.c_void_p]
+        L.mc_bed_compare_text.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, C.POINTER(C.c_void_p),
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        L.mc_bed_compare_file.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        L.mc_bed_compare_last_stats.argtypes = [C.c_void_p, C.POINTER(CmpStats)]
+        L.mc_bed_compare_release.argtypes = [C.c_void_p]
+        L.mc_twosample.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+        L.mc_twosample_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]
+        L.mc_twosample_log10_2sf.argtypes = [C.c_double]
+        L.mc_twosample_log10_2sf.restype = C.c_double
+        L.mc_twosample_log10_kolmogorov.argtypes = [C.c_double]
+        L.mc_twosample_log10_kolmogorov.restype = C.c_double
         L.mc_parsed_view.argtypes = [C.c_void_p, C.POINTER(TableView)]
         L.mc_parsed_read_name.argtypes = [C.c_void_p, C.c_int32]
         L.mc_parsed_read_name.restype = C.c_char_p
@@ -953,3 +982,25 @@ class Records(object):
         r.feats.reshape(-1, k)[:n][kept] = self.feats.reshape(-1, k)[rows]
         r.prob[:n][kept] = self.prob[rows]
         return r
+
+
+def twosample(x, y):
+    """The nine values of a compare_genomes row for the samples x and y by mc_twosample.h's host build (mc_twosample)
+    -> (status bits, float64 [9] in TW_NAMES' order, float64 [9]: the bound on |device - host| of each before rounding)."""
+    import numpy as np
+    x, y = (np.ascontiguousarray(a, dtype=np.float64) for a in (x, y))
+    out, bound, st = np.zeros(9), np.zeros(9), C.c_int32()
+    rc = lib().mc_twosample(x.ctypes.data, len(x), y.ctypes.data, len(y), out.ctypes.data, bound.ctypes.data, C.byref(st))
+    if rc != 0:
+        raise ValueError('mc_twosample: bad arguments')
+    return st.value, out, bound
+
+
+def twosample_log10_2sf(z):
+    """log10(2 * norm.sf(z)), z >= 0, by mc_twosample.h's host build."""
+    return lib().mc_twosample_log10_2sf(float(z))
+
+
+def twosample_log10_kolmogorov(lam):
+    """log10(scipy.special.kolmogorov(lam)) by mc_twosample.h's host build."""
+    return lib().mc_twosample_log10_kolmogorov(float(lam))

@@ -298,7 +298,7 @@ struct mc_ctx {
     Pinned site_status_host;                            // pinned copy the host reads (written by a kernel: no DMA)
     void *comm = nullptr;             // ncclComm_t
     int comm_world = 1;
-    // The four units that take a whole text file through the GPU (mc_textfeed.h).  Their calls are synchronous and never run side
+    // The five units that take whole text files through the GPU (mc_textfeed.h).  Their calls are synchronous and never run side
     // by side, so they share the file reader's two pinned blocks and the events that say a block's copy is done (the merge's
     // output leaves through them too): grown on demand, freed by every mc_*_release.  What a call hands out is its pipeline's own
     // and stays valid until the next call of that pipeline:
@@ -320,6 +320,10 @@ struct mc_ctx {
     Pinned fq_pool, fq_off, fq_mean;
     size_t fq_pool_cap = 0, fq_off_cap = 0, fq_mean_cap = 0;
     mc_fastq_quality_stats fq_stats = {};
+    // ... the rows of two --vo BED files compared per site (compare/mc_bedcompare.hip)
+    Pinned cmp_out;
+    size_t cmp_out_cap = 0;
+    mc_cmp_stats cmp_stats = {};
 };
 
 // ---- what crosses the units ----

@@ -11,6 +11,7 @@
 #include "mc_sortkey.h"
 #include "mc_rowtext.h"
 #include "mc_tstat.h"
+#include "mc_twosample.h"
 #include "mc_npsum.h"
 #include "../../include/mcaller_hip.h"
 
@@ -644,6 +645,34 @@ extern "C" int mc_tstat_site(const double *X, int64_t n_rows, int32_t n_cols, do
     if (n_rows >= 2 && (!rt_num_of(out2[0]).ok || !rt_num_of(out2[1]).ok)) flags |= 64;      // (a value mc_rowtext.h does not print)
     return flags;
 }
+
+// the two-sample arithmetic of compare_genomes by mc_twosample.h's host build (include/mcaller_hip.h): the counts from sorted
+// copies of the two samples, the moments in row order, then tw_finish
+extern "C" int mc_twosample(const double *x, int64_t n1, const double *y, int64_t n2, double *out, double *bound, int32_t *status) {
+    if (!out || !bound || !status || n1 < 0 || n2 < 0 || (n1 > 0 && !x) || (n2 > 0 && !y) || n1 + n2 > ((int64_t)1 << 20)) return -12;
+    TwSite S;
+    S.n1 = n1; S.n2 = n2;
+    if (n1 >= 1 && n2 >= 1) {
+        std::vector<double> sx(x, x + n1), sy(y, y + n2);
+        std::sort(sx.begin(), sx.end());
+        std::sort(sy.begin(), sy.end());
+        TwCount C;
+        for (int side = 0; side < 2; ++side)
+            for (int64_t i = 0; i < (side ? n2 : n1); ++i) {
+                const double v = side ? y[i] : x[i];
+                if (!(v == v)) { *status = TW_ZERO_VAR; for (int k = 0; k < TW_N_OUT; ++k) { out[k] = __builtin_nan(""); bound[k] = 0.0; } return 0; }
+                C.value(side == 0, std::lower_bound(sx.begin(), sx.end(), v) - sx.begin(), std::upper_bound(sx.begin(), sx.end(), v) - sx.begin(),
+                        std::lower_bound(sy.begin(), sy.end(), v) - sy.begin(), std::upper_bound(sy.begin(), sy.end(), v) - sy.begin(), n1, n2);
+            }
+        S.r1x2 = C.r1x2; S.tie = C.tie; S.D = C.D;
+        tw_moments(x, n1, &S.mean1, &S.ss1);
+        tw_moments(y, n2, &S.mean2, &S.ss2);
+    }
+    *status = tw_finish(S, out, bound);
+    return 0;
+}
+extern "C" double mc_twosample_log10_2sf(double z) { return tw_log10_2sf(z); }
+extern "C" double mc_twosample_log10_kolmogorov(double lam) { return tw_log10_kolmogorov(lam); }
 
 // the attributes of make_bed --gff --vo by mc_npsum.h's host build (include/mcaller_hip.h): p[0, n) the probabilities in row order
 extern "C" int mc_gff_site_moments(const double *p, int64_t n, double out3[3]) {

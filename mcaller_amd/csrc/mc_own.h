@@ -3,7 +3,7 @@
 // context that is deleted free everything on every path.  hipFree, hipHostFree, hipEventDestroy and hipStreamDestroy are called
 // here and in two other places under csrc/: mc_host_alloc's block cache (mc_common.cpp: process-wide host buffers that fall back
 // to malloc, no context owns them) and mc_debug_tanh32_max_err (mc_classify.hip, a kernel unit: eight bytes around one launch).
-// Included by mc_ctx.h (the context's units; through it by mc_lines.h and mc_textfeed.h, the four file pipelines' units) and by
+// Included by mc_ctx.h (the context's units; through it by mc_lines.h and mc_textfeed.h, the five file pipelines' units) and by
 // mc_fit.h (the --train fits).
 #pragma once
 

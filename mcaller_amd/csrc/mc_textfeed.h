@@ -1,5 +1,5 @@
-// mc_textfeed.h -- what the four units that take a whole text file through the GPU share on the host side (bed/mc_bedsum.hip,
-// train/mc_trainrows.hip, merge/mc_rowmerge.hip, fastq/mc_fastqual.hip).  Included by those four units only, hence the unnamed
+// mc_textfeed.h -- what the five units that take whole text files through the GPU share on the host side (bed/mc_bedsum.hip,
+// train/mc_trainrows.hip, merge/mc_rowmerge.hip, fastq/mc_fastqual.hip, compare/mc_bedcompare.hip).  Included by those five units only, hence the unnamed
 // namespace: nothing here is linked across units.  An entry point refuses its arguments (-12), sizes its files
 // (regular_file_size), selects the device, and then
 //
@@ -16,9 +16,9 @@
 //     lines_starts(pool, st, d_text, n, h.kp.n_newlines, tile_off, &d_head->kp, &line_start); ...; fetch_head(st, d_head, h);
 //     if (h.decline != ~0ull) return decline(stats, status, "reader", text, decline_reason(h.decline), decline_line(h.decline));
 //
-// Several texts behind one another in one buffer (the merge): feed.send(src, d_dst, &last_byte) for each, then
+// Several texts behind one another in one buffer (the merge, the comparison): feed.send(src, d_dst, &last_byte) for each, then
 // feed.pad_and_wait(d_end).  The feed's two pinned stages and their events are the context's (mc_ctx::text_stages): the calls of
-// the four units are synchronous and never run side by side, so one pair serves them all.
+// the five units are synchronous and never run side by side, so one pair serves them all.
 #pragma once
 #include "mc_lines.h"
 

@@ -860,6 +860,55 @@ class Device(object):
     def fastq_qualities_release(self):
         check(lib().mc_fastq_quality_release(self._ctx))
 
+    # ---- two --vo BED files compared per site (csrc/compare/mc_bedcompare.hip) ----
+    @_serialized
+    def bed_compare(self, path1=None, path2=None, text1=None, text2=None):
+        """The rows of compare_genomes for two `make_bed --vo` files (`path1`, `path2`) or their texts (`text1`, `text2`, bytes),
+        made on the GPU -> (blob: bytes, n_sites, None), or (None, 0, reason) when the device declines: the caller runs the
+        host statement."""
+        if (path1 is None) != (path2 is None) or (text1 is None) != (text2 is None) or (path1 is None) == (text1 is None):
+            raise ValueError('bed_compare: two paths or two texts')
+        out, n_out, n_sites, status = C.c_void_p(), C.c_int64(), C.c_int64(), C.c_int32()
+        if path1 is not None:
+            check(lib().mc_bed_compare_file(self._ctx, os.fsencode(path1), os.fsencode(path2), C.byref(out), C.byref(n_out),
+                                            C.byref(n_sites), C.byref(status)))
+        else:
+            text1, text2 = bytes(text1), bytes(text2)
+            check(lib().mc_bed_compare_text(self._ctx, text1, len(text1), text2, len(text2), C.byref(out), C.byref(n_out),
+                                            C.byref(n_sites), C.byref(status)))
+        if status.value != 0:
+            return None, 0, lib().mc_last_error().decode('utf-8', 'replace')
+        return (C.string_at(out.value, n_out.value) if n_out.value else b''), int(n_sites.value), None
+
+    @_serialized
+    def bed_compare_last_stats(self):
+        """Figures of the last bed_compare: bytes, lines, keys, shared sites, the rank kernels' shares, the decline, milliseconds."""
+        st = _lib.CmpStats()
+        check(lib().mc_bed_compare_last_stats(self._ctx, C.byref(st)))
+        return {name: getattr(st, name) for name, _ in st._fields_}
+
+    @_serialized
+    def bed_compare_release(self):
+        check(lib().mc_bed_compare_release(self._ctx))
+
+    @_serialized
+    def twosample(self, xs, ys):
+        """The nine values of a compare_genomes row for every pair of samples by mc_twosample.h's device build, a wave or a
+        workgroup per pair (mc_twosample_device, tests) -> (status bits int32 [k], float64 [k, 9], float64 [k, 9] bounds)."""
+        xs = [np.ascontiguousarray(a, dtype=np.float64) for a in xs]
+        ys = [np.ascontiguousarray(a, dtype=np.float64) for a in ys]
+        if len(xs) != len(ys) or any(a.ndim != 1 for a in xs + ys):
+            raise ValueError('twosample: a y for every x')
+        k = len(xs)
+        x_off, y_off = np.zeros(k + 1, dtype=np.int64), np.zeros(k + 1, dtype=np.int64)
+        x_off[1:] = np.cumsum([len(a) for a in xs], dtype=np.int64)
+        y_off[1:] = np.cumsum([len(a) for a in ys], dtype=np.int64)
+        x = np.concatenate(xs + [np.zeros(1)])
+        y = np.concatenate(ys + [np.zeros(1)])
+        out, bound, st = np.zeros((k, 9)), np.zeros((k, 9)), np.zeros(k, dtype=np.int32)
+        check(lib().mc_twosample_device(self._ctx, _ptr(x), _ptr(x_off), _ptr(y), _ptr(y_off), k, _ptr(out), _ptr(bound), _ptr(st)))
+        return st, out, bound
+
     @_serialized
     def mlp_forward(self, X, submodel):
         if getattr(self, '_clf', 'mlp') != 'mlp':
