@@ -35,7 +35,7 @@
 //     (the tail function is measured up to 10^5 degrees of freedom); the tie test
 // Its steps (mc_posset.inc, mc_sitestats.inc):
 //   kq_parse / kq_insert   the positions file: line starts by kp_*, a lane per line (the `len(line) > 3` rule, strip, the first four
-//                 fields, a 64-bit hash), an open-addressing table (atomicCAS, byte comparison); MCALLER_BED_HASH_MASK applies
+//                 fields, their KeyHash), a key table (mc_textdev.h); MCALLER_BED_HASH_MASK applies
 //   kb_parse      probes that table for a row with a centre 'M' (the digits of pos + 1 are generated into the hash); an unwanted row is
 //                 not counted and its values are never looked at; a counted row's commas are counted
 //   kq_counts     every counted row has the first one's number of values
@@ -72,13 +72,12 @@
 //
 // The steps (one lane per line unless said otherwise; n = lines):
 //   kp_count / kp_scan / kp_starts   line starts (the device parser's kernels: mc_lines.h, launched by mc_textfeed.h)
-//   kb_parse      256 lines of a workgroup staged in LDS with 16-byte loads; per line: the class of every byte, the tabs, centre 'M',
-//                 label 'm', the position as an integer, the stripped span of the probability, a 64-bit hash of the key bytes.
-//                 A flagged line: atomicMin of (line << 8 | reason) -- the decline names the FIRST such line, whatever the order
-//   kb_group      open addressing, slot = tag (high 32 bits of the hash) << 32 | row + 1, claimed by atomicCAS; a taken slot
-//                 matches when the tag, the whole hash and the key bytes of its row are equal.  The row that claimed the slot
-//                 numbers the entry; depth, n_meth, bytes of probabilities: atomicAdd, smallest row: atomicMin -- integers, so the
-//                 result does not depend on the order of arrival.  Nothing crosses workgroups but these atomics.
+//   kb_parse      256 lines of a workgroup through LDS (staged_lines); per line: the class of every byte, the tabs, centre 'M',
+//                 label 'm', the position as an integer, the stripped span of the probability, the KeyHash of the key fields.
+//                 A flagged line: line_flag
+//   kb_group      the keys into a table (kt_claim; ids are rows).  The row that claimed the slot numbers the entry; depth, n_meth,
+//                 bytes of probabilities: atomicAdd, smallest row: atomicMin -- integers, so the result does not depend on the
+//                 order of arrival.  Nothing crosses workgroups but these atomics.  longest_probe: slots that held another key
 //   kb_sums / kp_scan / kb_apply   a row is its entry's head when it is the entry's smallest row.  Over the lines, exclusive
 //                 scans of: depth at heads (an entry's bucket in rank order), selected heads, bytes of selected heads' text
 //   kb_place / kb_sort_small / kb_sort_large (--vo)   rows into their entry's bucket (atomicAdd), then every selected bucket into
@@ -88,7 +87,8 @@
 //                 the depth from the integers, the fraction from its digits); a wave per selected entry writes the list
 // wave64; no library sort; every buffer, event and stream through the owners of mc_own.h.
 // The host side around the kernels -- a file's way onto the device through the context's two pinned stages, the line starts, the
-// head's way back, the decline, the clock -- is mc_textfeed.h's, shared with the other three units that take a whole text file.
+// head's way back, the decline, the clock, a key table's size -- is mc_textfeed.h's, and line_flag, ByteClass, KeyHash, kt_claim /
+// kt_find, tabs_pack / tabs_unpack and staged_lines are mc_textdev.h's: shared with the other units that take a whole text file.
 #include "../mc_textfeed.h"
 #include "../mc_rowtext.h"
 #include "../mc_decimal.h"
@@ -115,15 +115,13 @@ struct BsHead {                              // device-side result block (copied
     long long f_total, f_nrec;               // --ref: sequence bytes, records (the two scans over the FASTA's lines)
 };
 
-struct BsRow { uint16_t t[7]; uint16_t len; };   // the tabs of a line (offsets from its start; t[6] = len in a 7-field row), its length
-
 struct BsArgs {
     const char *text;
     int64_t n_bytes, n_lines, n_nl;
     const long long *line_start;
     BsHead *head;
     // per line
-    BsRow *row;
+    uint4 *row;                              // tabs_pack: the tabs of a line (t[6] = len in a 7-field row), its length
     uint32_t *pos, *pspan, *row_ent, *ent_boff;
     uint64_t *hash;
     uint8_t *fl;
@@ -185,10 +183,6 @@ struct BsArgs {
     uint8_t *ctx_len;                        // ... its length, bit 7: reversed and complemented
 };
 
-__device__ __forceinline__ void bs_flag(const BsArgs &A, int64_t li, int reason) {
-    atomicMin(&A.head->decline, ((unsigned long long)li << 8) | (unsigned long long)reason);
-}
-
 #include "mc_posset.inc"
 
 // One line: t[x - adj] is byte x of the text (the staged piece in LDS, or the text itself with adj = 0: one address space per call site)
@@ -196,30 +190,30 @@ __device__ __forceinline__ bool bs_parse_line(const BsArgs &A, const char *t, co
     const int64_t b = A.line_start[li] - adj;
     const int64_t e = (li < A.n_nl ? A.line_start[li + 1] - 1 : A.n_bytes) - adj;        // the newline, or the end of the text
     A.fl[li] = 0;
-    if (e - b > 65535) { bs_flag(A, li, MC_BED_DECLINE_LONG_LINE); return false; }
+    if (e - b > 65535) { line_flag(&A.head->decline, li, MC_BED_DECLINE_LONG_LINE); return false; }
     const int len = (int)(e - b);
-    int t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0, t5 = 0, t6 = 0, nt = 0, commas = 0;
-    bool bad_hi = false, bad_ctrl = false;
-    uint64_t h = 0xcbf29ce484222325ull;                       // FNV-1a over the key fields, a 0xff between fields (no such byte in a line)
+    int tab[7] = {0, 0, 0, 0, 0, 0, 0}, nt = 0, commas = 0;
+    ByteClass bad;
+    KeyHash H;                                                // the key fields in the one pass over the line
     for (int i = 0; i < len; ++i) {
         const unsigned c = (unsigned char)t[b + i];
-        bad_hi |= c >= 0x80u;
-        bad_ctrl |= (c < 0x20u && c != '\t') || c == 0x7fu;
+        bad.see(c);
         if (c == '\t') {
-            t0 = nt == 0 ? i : t0; t1 = nt == 1 ? i : t1; t2 = nt == 2 ? i : t2; t3 = nt == 3 ? i : t3;
-            t4 = nt == 4 ? i : t4; t5 = nt == 5 ? i : t5; t6 = nt == 6 ? i : t6;
-            if (nt < 6) h = (h ^ 0xffu) * 0x100000001b3ull;      // (the tab before a probability is no part of the key)
+#pragma unroll
+            for (int k = 0; k < 7; ++k) tab[k] = nt == k ? i : tab[k];
+            if (nt < 6) H.sep();                              // (the tab before a probability is no part of the key)
             ++nt;
         } else if (nt == 0 || nt == 2 || nt == 3 || nt == 5) {     // chrom, pos, context, strand
-            h = (h ^ c) * 0x100000001b3ull;
+            H.put((char)c);
         } else if (nt == 4) {
             commas += c == ',';
         }
     }
+    int &t1 = tab[1], &t2 = tab[2], &t3 = tab[3], &t5 = tab[5], &t6 = tab[6];       // (names for the rules below)
     int reason = 0;
     uint32_t pos = 0;
-    if (bad_hi) reason = MC_BED_DECLINE_HIGH_BYTE;
-    else if (bad_ctrl) reason = MC_BED_DECLINE_CONTROL;
+    if (bad.hi) reason = MC_BED_DECLINE_HIGH_BYTE;
+    else if (bad.ctrl) reason = MC_BED_DECLINE_CONTROL;
     else if (nt != 6 && nt != 7) reason = MC_BED_DECLINE_FIELDS;
     else {
         if (nt == 6) t6 = len;
@@ -235,10 +229,10 @@ __device__ __forceinline__ bool bs_parse_line(const BsArgs &A, const char *t, co
         if (!reason && t6 - t5 - 1 < 1) reason = MC_BED_DECLINE_LABEL;
         if (!reason && nt == 6 && A.with_probs) reason = MC_BED_DECLINE_NO_PROB;
     }
-    if (reason) { bs_flag(A, li, reason); return false; }
+    if (reason) { line_flag(&A.head->decline, li, reason); return false; }
     const int cn = t3 - t2 - 1;
     bool counted = t[b + t2 + 1 + cn / 2] == 'M';
-    if (counted && A.positions) counted = bq_wanted(A, t + b, t0, t1, t2, t4, t5, pos);      // an unwanted row: its values are never looked at
+    if (counted && A.positions) counted = bq_wanted(A, t + b, tab[0], t1, t2, tab[4], t5, pos);      // an unwanted row: its values are never looked at
     if (counted && A.stats) {
         A.nval[li] = (uint32_t)commas + 1u;
         atomicMin(&A.head->first_counted, (unsigned long long)li);
@@ -250,89 +244,47 @@ __device__ __forceinline__ bool bs_parse_line(const BsArgs &A, const char *t, co
         while (pb < pe && t[b + pb] == ' ') ++pb;
         while (pe > pb && t[b + pe - 1] == ' ') --pe;
     }
-    h ^= h >> 33; h *= 0xff51afd7ed558ccdull; h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53ull; h ^= h >> 33;
-    uint4 r;
-    r.x = (uint32_t)t0 | ((uint32_t)t1 << 16); r.y = (uint32_t)t2 | ((uint32_t)t3 << 16);
-    r.z = (uint32_t)t4 | ((uint32_t)t5 << 16); r.w = (uint32_t)t6 | ((uint32_t)len << 16);
-    reinterpret_cast<uint4 *>(A.row)[li] = r;
+    A.row[li] = tabs_pack(tab, len);
     A.pos[li] = pos;
     A.pspan[li] = ((uint32_t)pb << 16) | (uint32_t)(pe - pb);
-    A.hash[li] = h & A.hash_mask;
+    A.hash[li] = H.done(A.hash_mask);
     A.fl[li] = (uint8_t)((counted ? BS_F_COUNTED : 0) | (meth ? BS_F_METH : 0) | (nt == 7 ? BS_F_PROB : 0));
     return counted;
 }
 
 __global__ __launch_bounds__(256) void kb_parse(BsArgs A) {
-    extern __shared__ __attribute__((aligned(16))) char s_text[];      // BS_STAGE + 16 bytes
-    const int64_t l0 = (int64_t)blockIdx.x * 256;
-    const int64_t l1 = min(l0 + 256, A.n_lines);
-    const int64_t g0 = A.line_start[l0], g1 = l1 <= A.n_nl ? (int64_t)A.line_start[l1] : A.n_bytes;
-    const int64_t a0 = g0 & ~(int64_t)15;
-    const int64_t li = l0 + threadIdx.x;
     bool counted = false;
-    if (g1 - a0 <= BS_STAGE) {                               // (the text buffer is padded: whole 16-byte groups are readable)
-        for (int64_t i = (int64_t)threadIdx.x * 16; i < g1 - a0; i += 256 * 16)
-            *reinterpret_cast<uint4 *>(s_text + i) = *reinterpret_cast<const uint4 *>(A.text + a0 + i);
-        __syncthreads();
-        if (li < l1) counted = bs_parse_line(A, s_text, a0, li);
-    } else if (li < l1) {                                    // very long lines: read in place
-        counted = bs_parse_line(A, A.text, 0, li);
-    }
+    (void)staged_lines<BS_STAGE>(A.text, A.n_bytes, A.line_start, A.n_lines, A.n_nl,
+                                 [&](const char *t, int64_t adj, int64_t li) { counted = bs_parse_line(A, t, adj, li); });
     const unsigned long long bal = __ballot(counted);
     if ((threadIdx.x & 63) == 0 && bal) atomicAdd(&A.head->n_counted, (unsigned long long)__popcll(bal));
 }
 
-__device__ __forceinline__ BsRow bs_row(const BsArgs &A, int64_t li) {
-    const uint4 r = reinterpret_cast<const uint4 *>(A.row)[li];
-    BsRow R;
-    R.t[0] = (uint16_t)r.x; R.t[1] = (uint16_t)(r.x >> 16); R.t[2] = (uint16_t)r.y; R.t[3] = (uint16_t)(r.y >> 16);
-    R.t[4] = (uint16_t)r.z; R.t[5] = (uint16_t)(r.z >> 16); R.t[6] = (uint16_t)r.w; R.len = (uint16_t)(r.w >> 16);
-    return R;
-}
-
-__device__ __forceinline__ bool bs_same_bytes(const char *__restrict__ a, const char *__restrict__ b, int n) {
-    for (int i = 0; i < n; ++i)
-        if (a[i] != b[i]) return false;
-    return true;
-}
+__device__ __forceinline__ TabSpan bs_row(const BsArgs &A, int64_t li) { return tabs_unpack(A.row[li]); }
 
 // (chrom, pos, strand, context) of lines a and b, byte for byte: chrom = [0, t0), pos and context = (t1, t3) with the tab between
 // them at the same place, strand = (t4, t5)
 __device__ __forceinline__ bool bs_same_key(const BsArgs &A, int64_t a, int64_t b) {
-    const BsRow Ra = bs_row(A, a), Rb = bs_row(A, b);
+    const TabSpan Ra = bs_row(A, a), Rb = bs_row(A, b);
     if (Ra.t[0] != Rb.t[0] || Ra.t[2] - Ra.t[1] != Rb.t[2] - Rb.t[1] || Ra.t[3] - Ra.t[1] != Rb.t[3] - Rb.t[1] ||
         Ra.t[5] - Ra.t[4] != Rb.t[5] - Rb.t[4])
         return false;
     const char *ta = A.text + A.line_start[a], *tb = A.text + A.line_start[b];
-    return bs_same_bytes(ta, tb, Ra.t[0]) && bs_same_bytes(ta + Ra.t[1] + 1, tb + Rb.t[1] + 1, Ra.t[3] - Ra.t[1] - 1) &&
-           bs_same_bytes(ta + Ra.t[4] + 1, tb + Rb.t[4] + 1, Ra.t[5] - Ra.t[4] - 1);
+    return same_bytes(ta, tb, Ra.t[0]) && same_bytes(ta + Ra.t[1] + 1, tb + Rb.t[1] + 1, Ra.t[3] - Ra.t[1] - 1) &&
+           same_bytes(ta + Ra.t[4] + 1, tb + Rb.t[4] + 1, Ra.t[5] - Ra.t[4] - 1);
 }
 
 __global__ __launch_bounds__(256) void kb_group(BsArgs A) {
     const int64_t li = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const uint8_t fl = li < A.n_lines ? A.fl[li] : (uint8_t)0;
-    int probes = 0;
+    int probes = 0;                                           // slots that held another key
     if (fl & BS_F_COUNTED) {
         const uint64_t h = A.hash[li];
-        const uint64_t tag = h >> 32;
-        const unsigned long long mine = (tag << 32) | (unsigned long long)(li + 1);
-        uint64_t slot = h & A.table_mask;
-        int64_t rep = -1;
-        for (;;) {
-            unsigned long long cur = A.table[slot];           // (a slot goes from empty to taken once: a stale "empty" is put right by the CAS)
-            if (cur == 0ull) {
-                cur = atomicCAS(&A.table[slot], 0ull, mine);
-                if (cur == 0ull) { rep = li; break; }
-            }
-            if ((cur >> 32) == tag) {
-                const int64_t r = (int64_t)(cur & 0xffffffffull) - 1;
-                if (A.hash[r] == h && bs_same_key(A, li, r)) { rep = r; break; }
-            }
-            slot = (slot + 1) & A.table_mask;
-            if ((uint64_t)++probes > A.table_mask) break;     // every slot seen: the table is full (the host sizes it so that it is not)
-        }
-        if (rep < 0) {
-            bs_flag(A, li, MC_BED_DECLINE_TABLE);
+        const KtHit hit = kt_claim(A.table, A.table_mask, h, li, [&](int64_t r) { return A.hash[r] == h && bs_same_key(A, li, r); });
+        const int64_t rep = hit.id;                           // the row that claimed the slot numbers the entry
+        probes = (int)hit.looked - (hit.slot >= 0 ? 1 : 0);
+        if (hit.slot < 0) {
+            line_flag(&A.head->decline, li, MC_BED_DECLINE_TABLE);
             A.row_ent[li] = (uint32_t)li;                     // (an entry nobody counted: no head, whatever runs before the host looks)
         } else {
             A.row_ent[li] = (uint32_t)rep;
@@ -367,7 +319,7 @@ __device__ __forceinline__ void bs_put_lit(Sink &o, const char *s) {
 
 template <class Sink>
 __device__ __forceinline__ void bs_put_entry(const BsArgs &A, Sink &o, int64_t li, uint32_t depth, uint32_t meth) {
-    const BsRow R = bs_row(A, li);
+    const TabSpan R = bs_row(A, li);
     const char *t = A.text + A.line_start[li];
     const RtNum frac = rt_num_of((double)meth / (double)depth);       // np.float64(n_meth) / np.float64(depth)
     const uint32_t end = A.pos[li] + 1u;                              // str(int(pos) + 1)
@@ -691,12 +643,10 @@ int bs_position_set(mc_ctx *c, Pool &pool, BsArgs &A, BsHead *d_head, BsHead &h,
     }
     A.p_start = p_start;
     const size_t pl = (size_t)std::max<int64_t>(A.p_lines, 1);
-    uint64_t slots = 16;
-    while ((int64_t)slots < 2 * A.p_lines) slots <<= 1;
+    const uint64_t slots = table_slots(A.p_lines, 16);
     if (!device_fits(pl * (16 + 8) + (size_t)slots * 8)) { (void)bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1); return 1; }
-    if (pool.get(&A.p_line, pl) || pool.get(&A.p_hash, pl) || pool.get(&A.p_table, (size_t)slots)) { *rc = -10; return 1; }
+    if (pool.get(&A.p_line, pl) || pool.get(&A.p_hash, pl) || table_get(pool, st, &A.p_table, slots)) { *rc = -10; return 1; }
     A.p_mask = slots - 1;
-    if (hipMemsetAsync(A.p_table, 0, (size_t)slots * 8, st) != hipSuccess) { *rc = -11; return 1; }
     if (A.p_lines > 0) {
         const unsigned pb = (unsigned)((A.p_lines + 255) / 256);
         hipLaunchKernelGGL(kq_parse, dim3(pb), dim3(256), 0, st, A);
@@ -731,13 +681,12 @@ int bs_fasta(mc_ctx *c, Pool &pool, BsArgs &A, BsHead *d_head, BsHead &h, const 
     c->bed_stats.kernel_bytes += 3 * fn + A.f_lines * 6 * 8;
     if (h.decline != ~0ull) { (void)bs_decline_head(c, status, h); return 1; }
     A.n_rec = h.f_nrec;
-    uint64_t slots = 16;
-    while ((long long)slots < 2 * A.n_rec) slots <<= 1;
+    const uint64_t slots = table_slots(A.n_rec, 16);
     if (!device_fits((size_t)h.f_total + (size_t)A.n_rec * 12 + (size_t)slots * 12 + ((size_t)1 << 20))) { (void)bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1); return 1; }
     if (pool.get(&A.f_seq, (size_t)h.f_total + 1) || pool.get(&A.rec_begin, (size_t)A.n_rec + 1) || pool.get(&A.rec_line, (size_t)A.n_rec + 1) ||
-        pool.get(&A.f_table, (size_t)slots) || pool.get(&A.f_win, (size_t)slots)) { *rc = -10; return 1; }
+        pool.get(&A.f_win, (size_t)slots) || table_get(pool, st, &A.f_table, slots)) { *rc = -10; return 1; }
     A.f_mask = slots - 1;
-    if (hipMemsetAsync(A.f_table, 0, (size_t)slots * 8, st) != hipSuccess || hipMemsetAsync(A.f_win, 0, (size_t)slots * 4, st) != hipSuccess) { *rc = -11; return 1; }
+    if (hipMemsetAsync(A.f_win, 0, (size_t)slots * 4, st) != hipSuccess) { *rc = -11; return 1; }
     hipLaunchKernelGGL(kf_pack, dim3(wb), dim3(256), 0, st, A, A.n_rec, h.f_total);
     if (A.n_rec > 0) hipLaunchKernelGGL(kf_ids, dim3((unsigned)((A.n_rec + 255) / 256)), dim3(256), 0, st, A, A.n_rec);
     if (fetch_head(st, d_head, h)) { *rc = -11; return 1; }
@@ -819,18 +768,12 @@ int bs_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *d_p
         if (h.decline != ~0ull) return bs_decline_head(c, status, h);
         A.nv = h.nv;
     }
-    uint64_t slots = 16;
-    while ((int64_t)slots < 2 * n_counted) slots <<= 1;
-    if (const char *e = getenv("MCALLER_BED_TABLE_SLOTS")) {
-        const long long want = atoll(e);
-        if (want > 0) { slots = 1; while ((long long)slots < want) slots <<= 1; }
-    }
+    const uint64_t slots = table_slots(n_counted, 16, "MCALLER_BED_TABLE_SLOTS");
     S.table_slots = (int64_t)slots;
     if ((int64_t)slots < 2 * n_counted) return bs_decline(c, status, MC_BED_DECLINE_TABLE, -1);
     if (!device_fits((size_t)slots * 8 + (size_t)3 * lb * 16 + (A.buckets ? (size_t)n_counted * 8 : 0))) return bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1);
-    if (pool.get(&A.table, (size_t)slots) || pool.get(&A.blk_sum, (size_t)3 * lb) || pool.get(&A.blk_off, (size_t)3 * lb)) return -10;
+    if (pool.get(&A.blk_sum, (size_t)3 * lb) || pool.get(&A.blk_off, (size_t)3 * lb) || table_get(pool, st, &A.table, slots)) return -10;      // (cleared behind the last allocation)
     A.table_mask = slots - 1;
-    HIP_TRY(hipMemsetAsync(A.table, 0, (size_t)slots * 8, st));
     HIP_TRY(hipMemsetAsync(A.ent_depth, 0, nl * 4, st));
     HIP_TRY(hipMemsetAsync(A.ent_meth, 0, nl * 4, st));
     HIP_TRY(hipMemsetAsync(A.ent_fill, 0, nl * 4, st));

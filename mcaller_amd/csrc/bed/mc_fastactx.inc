@@ -10,8 +10,8 @@
 //   kf_pack      a wave per line: a title notes where its record begins; a sequence line of a record goes upper-cased into the
 //                packed array -- with a byte that is no letter (a blank, a digit, '*', '-') it declines the file: the host strips
 //                whitespace there and keeps the rest, the device leaves both to the host
-//   kf_ids       a lane per record: open addressing like kq_insert (atomicCAS, byte comparison); atomicMax of the record number on
-//                the slot, so the last record of an id wins whatever the order of arrival
+//   kf_ids       a lane per record: its id into a key table (kt_claim, mc_textdev.h; ids of the table are records); atomicMax of the
+//                record number on the slot, so the last record of an id wins whatever the order of arrival
 //   kf_context   a lane per entry (its first row): the table probed with the chrom bytes, the slice rule -> where the window begins
 //                in the packed array, its length (0 .. 41) and whether it is reversed; bs_put_context writes it from there
 //                (complemented and reversed on the fly) for the sizing pass and kb_write.  On '-' a letter outside ACGTNM declines
@@ -27,22 +27,22 @@ __global__ __launch_bounds__(256) void kf_lines(BsArgs A) {
     const int64_t e = li < A.f_nl ? (int64_t)A.f_start[li + 1] - 1 : A.f_bytes;
     const char *t = A.ftext;
     const bool title = e > b && t[b] == '>';
-    bool bad_hi = false, bad_ctrl = false, other = false;
+    ByteClass bad;
+    bool other = false;
     for (int64_t i = b + lane; i < e; i += 64) {
         const unsigned c = (unsigned char)t[i];
-        bad_hi |= c >= 0x80u;
-        bad_ctrl |= (c < 0x20u && c != '\t') || c == 0x7fu;
+        bad.see(c);
         other |= !((c | 0x20u) >= 'a' && (c | 0x20u) <= 'z');
     }
-    const bool any_hi = __ballot(bad_hi) != 0ull, any_ctrl = __ballot(bad_ctrl) != 0ull, any_other = __ballot(other) != 0ull;
+    const bool any_hi = __ballot(bad.hi) != 0ull, any_ctrl = __ballot(bad.ctrl) != 0ull, any_other = __ballot(other) != 0ull;
     if (lane != 0) return;
-    if (any_hi) bs_flag(A, li, MC_BED_DECLINE_REF_HIGH_BYTE);
-    else if (any_ctrl) bs_flag(A, li, MC_BED_DECLINE_REF_CONTROL);
+    if (any_hi) line_flag(&A.head->decline, li, MC_BED_DECLINE_REF_HIGH_BYTE);
+    else if (any_ctrl) line_flag(&A.head->decline, li, MC_BED_DECLINE_REF_CONTROL);
     A.f_cnt[li] = title ? 0 : e - b;
     A.f_cnt[A.f_lines + li] = title ? 1 : 0;
     A.f_bad[li] = (uint8_t)(!title && any_other);
     uint32_t ib = 0, in = 0;
-    BqHash H;
+    KeyHash H;
     if (title && !any_hi && !any_ctrl) {
         int64_t i = b + 1;
         while (i < e && bf_blank((unsigned char)t[i])) ++i;
@@ -67,55 +67,39 @@ __global__ __launch_bounds__(256) void kf_pack(BsArgs A, long long n_rec, long l
         return;
     }
     if (rec == 0) return;                                              // before the first record
-    if (A.f_bad[li]) { if (lane == 0) bs_flag(A, li, MC_BED_DECLINE_REF_SEQ_BYTE); return; }
+    if (A.f_bad[li]) { if (lane == 0) line_flag(&A.head->decline, li, MC_BED_DECLINE_REF_SEQ_BYTE); return; }
     const int64_t b = A.f_start[li], n = A.f_cnt[li];
     for (int64_t i = lane; i < n; i += 64) A.f_seq[at + i] = (char)((unsigned char)A.ftext[b + i] & 0xdfu);      // upper case
 }
 
 __device__ __forceinline__ bool bf_same_id(const BsArgs &A, uint32_t line, const char *s, uint32_t n) {
-    return A.f_idn[line] == n && bq_same(A.ftext + A.f_start[line] + A.f_idb[line], s, (int)n);
+    return A.f_idn[line] == n && same_bytes(A.ftext + A.f_start[line] + A.f_idb[line], s, (int)n);
 }
 
 __global__ __launch_bounds__(256) void kf_ids(BsArgs A, long long n_rec) {
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (r >= n_rec) return;
     const uint32_t line = A.rec_line[r];
-    const uint64_t h = A.f_hash[line], tag = h >> 32;
-    const unsigned long long mine = (tag << 32) | (unsigned long long)(r + 1);
+    const uint64_t h = A.f_hash[line];
     const char *id = A.ftext + A.f_start[line] + A.f_idb[line];
-    uint64_t slot = h & A.f_mask, probes = 0;
-    for (;;) {
-        unsigned long long cur = A.f_table[slot];
-        if (cur == 0ull) {
-            cur = atomicCAS(&A.f_table[slot], 0ull, mine);
-            if (cur == 0ull) break;
-        }
-        if ((cur >> 32) == tag) {
-            const uint32_t other = A.rec_line[(cur & 0xffffffffull) - 1];
-            if (A.f_hash[other] == h && bf_same_id(A, other, id, A.f_idn[line])) break;      // the same id again
-        }
-        slot = (slot + 1) & A.f_mask;
-        if (++probes > A.f_mask) { bs_flag(A, line, MC_BED_DECLINE_TABLE); return; }      // (the host sizes the table so that it is not full)
-    }
-    atomicMax(&A.f_win[slot], (uint32_t)(r + 1));
+    const KtHit hit = kt_claim(A.f_table, A.f_mask, h, r, [&](int64_t q) {      // (ids of the table are records)
+        const uint32_t other = A.rec_line[q];
+        return A.f_hash[other] == h && bf_same_id(A, other, id, A.f_idn[line]);
+    });
+    if (hit.slot < 0) { line_flag(&A.head->decline, line, MC_BED_DECLINE_TABLE); return; }
+    atomicMax(&A.f_win[hit.slot], (uint32_t)(r + 1));                  // claimed, or the same id again: the last record wins
 }
 
 // the record (the last of its id) whose id is s[0, n), or -1
 __device__ __forceinline__ long long bf_find(const BsArgs &A, const char *s, int n) {
-    BqHash H;
+    KeyHash H;
     H.span(s, n);
-    const uint64_t h = H.done(A.hash_mask), tag = h >> 32;
-    uint64_t slot = h & A.f_mask, probes = 0;
-    for (;;) {
-        const unsigned long long cur = A.f_table[slot];                // (the table is complete: kf_ids ran before)
-        if (cur == 0ull) return -1;
-        if ((cur >> 32) == tag) {
-            const uint32_t line = A.rec_line[(cur & 0xffffffffull) - 1];
-            if (A.f_hash[line] == h && bf_same_id(A, line, s, (uint32_t)n)) return (long long)A.f_win[slot] - 1;
-        }
-        slot = (slot + 1) & A.f_mask;
-        if (++probes > A.f_mask) return -1;
-    }
+    const uint64_t h = H.done(A.hash_mask);
+    const KtHit hit = kt_find(A.f_table, A.f_mask, h, [&](int64_t q) {   // (the table is complete: kf_ids ran before)
+        const uint32_t line = A.rec_line[q];
+        return A.f_hash[line] == h && bf_same_id(A, line, s, (uint32_t)n);
+    });
+    return hit.slot < 0 ? -1 : (long long)A.f_win[hit.slot] - 1;
 }
 
 __global__ __launch_bounds__(256) void kf_context(BsArgs A) {
@@ -123,11 +107,11 @@ __global__ __launch_bounds__(256) void kf_context(BsArgs A) {
     if (li >= A.n_lines || !(A.fl[li] & BS_F_COUNTED)) return;
     const uint32_t rep = A.row_ent[li];
     if (A.ent_min[rep] != (uint32_t)li) return;                        // the entry's first row speaks for it
-    const BsRow R = bs_row(A, li);
+    const TabSpan R = bs_row(A, li);
     const char *t = A.text + A.line_start[li];
     const long long r = A.n_rec > 0 ? bf_find(A, t, R.t[0]) : -1;
     if (r < 0) {
-        if (bs_selected(A, rep)) bs_flag(A, li, MC_BED_DECLINE_REF_CONTIG);
+        if (bs_selected(A, rep)) line_flag(&A.head->decline, li, MC_BED_DECLINE_REF_CONTIG);
         return;
     }
     const long long begin = A.rec_begin[r], L = A.rec_begin[r + 1] - begin;
@@ -140,7 +124,7 @@ __global__ __launch_bounds__(256) void kf_context(BsArgs A) {
     if (rev)
         for (int i = 0; i < n; ++i) {
             const char c = A.f_seq[begin + start + i];
-            if (!(c == 'A' || c == 'C' || c == 'G' || c == 'T' || c == 'N' || c == 'M')) { bs_flag(A, li, MC_BED_DECLINE_REF_LETTER); return; }
+            if (!(c == 'A' || c == 'C' || c == 'G' || c == 'T' || c == 'N' || c == 'M')) { line_flag(&A.head->decline, li, MC_BED_DECLINE_REF_LETTER); return; }
         }
     A.ctx_at[rep] = begin + start;
     A.ctx_len[rep] = (uint8_t)(n | (rev ? 0x80 : 0));

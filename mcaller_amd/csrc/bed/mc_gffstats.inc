@@ -20,7 +20,7 @@ __global__ __launch_bounds__(256) void kg_probs(BsArgs A, int64_t n_counted) {
     double v = 0.0;
     if (bs_selected(A, A.row_ent[li])) {
         const uint32_t ps = A.pspan[li];
-        if (!dc_parse(A.text + A.line_start[li] + (ps >> 16), (int)(ps & 0xffffu), &v)) bs_flag(A, li, MC_BED_DECLINE_PROBABILITY);
+        if (!dc_parse(A.text + A.line_start[li] + (ps >> 16), (int)(ps & 0xffffu), &v)) line_flag(&A.head->decline, li, MC_BED_DECLINE_PROBABILITY);
     }
     A.X[s] = v;
 }
@@ -89,8 +89,8 @@ __global__ __launch_bounds__(256) void kg_finish(BsArgs A, int64_t n_sel) {
     const uint32_t depth = A.ent_depth[rep];
     double out3[3];
     const int st = ns_finish(A.mom[2 * k], A.mom[2 * k + 1], (int64_t)depth, (double)A.ent_meth[rep] / (double)depth, out3);
-    if (st & NS_QV_RANGE) { bs_flag(A, li, MC_BED_DECLINE_QV_RANGE); return; }
-    if (st & NS_PRINT_RANGE) { bs_flag(A, li, MC_BED_DECLINE_STAT_RANGE); return; }
+    if (st & NS_QV_RANGE) { line_flag(&A.head->decline, li, MC_BED_DECLINE_QV_RANGE); return; }
+    if (st & NS_PRINT_RANGE) { line_flag(&A.head->decline, li, MC_BED_DECLINE_STAT_RANGE); return; }
     for (int q = 0; q < 2; ++q) {
         const bool is_nan = !(out3[q] == out3[q]);
         bq_store_num(A, 2 * (size_t)rep + q, is_nan ? RtNum() : rt_num_of(out3[q]), is_nan);

@@ -4,9 +4,9 @@
 //   kq_parse    a lane per positions line: the class of every byte; the `len(line) > 3` rule, the newline counted; strip() (blanks
 //               and tabs: the only whitespace a line may still hold); the first four tab-separated fields; a 64-bit hash of them.
 //               A line with fewer than four fields is no tuple a row can equal: it is left out
-//   kq_insert   open addressing like kb_group: slot = tag << 32 | line + 1, claimed by atomicCAS; a line whose four fields equal
-//               those of the slot's line byte for byte is a duplicate and stops there
-//   bq_wanted   the row's probe: the same hash (the digits of pos + 1 are generated into it, never stored), then tag, hash and bytes.
+//   kq_insert   the tuples into a key table (kt_claim, mc_textdev.h; ids are lines): a line whose four fields equal those of the
+//               slot's line byte for byte is a duplicate and stops there
+//   bq_wanted   the row's probe (kt_find): the same hash (the digits of pos + 1 are generated into it, never stored), then the bytes.
 //               Field 3 of a tuple equals str(int(pos) + 1) iff it is that number written without a leading zero
 
 struct BqLine { int sb, t0, t1, t2, e3; bool ok; };      // offsets from the line start: the stripped begin, three tabs, the end of field 4
@@ -19,24 +19,6 @@ __device__ __forceinline__ BqLine bq_line(const BsArgs &A, int64_t li) {
     return L;
 }
 
-struct BqHash {                                          // FNV-1a, a 0xff between fields (no such byte in a text that is not declined)
-    uint64_t h = 0xcbf29ce484222325ull;
-    __device__ __forceinline__ void put(char c) { h = (h ^ (uint64_t)(unsigned char)c) * 0x100000001b3ull; }
-    __device__ __forceinline__ void span(const char *p, int n) { for (int i = 0; i < n; ++i) put(p[i]); }
-    __device__ __forceinline__ void sep() { h = (h ^ 0xffull) * 0x100000001b3ull; }
-    __device__ __forceinline__ uint64_t done(uint64_t mask) {
-        uint64_t v = h;
-        v ^= v >> 33; v *= 0xff51afd7ed558ccdull; v ^= v >> 33; v *= 0xc4ceb9fe1a85ec53ull; v ^= v >> 33;
-        return v & mask;
-    }
-};
-
-__device__ __forceinline__ bool bq_same(const char *a, const char *b, int n) {
-    for (int i = 0; i < n; ++i)
-        if (a[i] != b[i]) return false;
-    return true;
-}
-
 __global__ __launch_bounds__(256) void kq_parse(BsArgs A) {
     const int64_t li = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (li >= A.p_lines) return;
@@ -45,17 +27,13 @@ __global__ __launch_bounds__(256) void kq_parse(BsArgs A) {
     const int64_t e = li < A.p_nl ? e_nl - 1 : A.p_bytes;
     A.p_line[li] = make_uint4(0u, 0u, 0u, 0u);
     A.p_hash[li] = 0;
-    if (e - b > 65535) { bs_flag(A, li, MC_BED_DECLINE_POS_LONG_LINE); return; }
+    if (e - b > 65535) { line_flag(&A.head->decline, li, MC_BED_DECLINE_POS_LONG_LINE); return; }
     const char *t = A.ptext + b;
     const int len = (int)(e - b);
-    bool bad_hi = false, bad_ctrl = false;
-    for (int i = 0; i < len; ++i) {
-        const unsigned c = (unsigned char)t[i];
-        bad_hi |= c >= 0x80u;
-        bad_ctrl |= (c < 0x20u && c != '\t') || c == 0x7fu;
-    }
-    if (bad_hi) { bs_flag(A, li, MC_BED_DECLINE_POS_HIGH_BYTE); return; }
-    if (bad_ctrl) { bs_flag(A, li, MC_BED_DECLINE_POS_CONTROL); return; }
+    ByteClass bad;
+    for (int i = 0; i < len; ++i) bad.see((unsigned char)t[i]);
+    if (bad.hi) { line_flag(&A.head->decline, li, MC_BED_DECLINE_POS_HIGH_BYTE); return; }
+    if (bad.ctrl) { line_flag(&A.head->decline, li, MC_BED_DECLINE_POS_CONTROL); return; }
     if (e_nl - b <= 3) return;                                         // len(line) > 3, the newline counted
     int sb = 0, se = len;
     while (sb < se && (t[sb] == ' ' || t[sb] == '\t')) ++sb;
@@ -67,7 +45,7 @@ __global__ __launch_bounds__(256) void kq_parse(BsArgs A) {
             ++nt;
         }
     if (nt < 3) return;                                                // fewer than four fields
-    BqHash H;
+    KeyHash H;
     H.span(t + sb, t0 - sb); H.sep();
     H.span(t + t0 + 1, t1 - t0 - 1); H.sep();
     H.span(t + t1 + 1, t2 - t1 - 1); H.sep();
@@ -81,61 +59,41 @@ __device__ __forceinline__ bool bq_same_tuple(const BsArgs &A, int64_t a, int64_
     if (La.t0 - La.sb != Lb.t0 - Lb.sb || La.t1 - La.t0 != Lb.t1 - Lb.t0 || La.t2 - La.t1 != Lb.t2 - Lb.t1 || La.e3 - La.t2 != Lb.e3 - Lb.t2)
         return false;
     // (equal field lengths: the four fields with the tabs between them are one span of equal length)
-    return bq_same(A.ptext + A.p_start[a] + La.sb, A.ptext + A.p_start[b] + Lb.sb, La.e3 - La.sb);
+    return same_bytes(A.ptext + A.p_start[a] + La.sb, A.ptext + A.p_start[b] + Lb.sb, La.e3 - La.sb);
 }
 
 __global__ __launch_bounds__(256) void kq_insert(BsArgs A) {
     const int64_t li = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (li >= A.p_lines || !bq_line(A, li).ok) return;
-    const uint64_t h = A.p_hash[li], tag = h >> 32;
-    const unsigned long long mine = (tag << 32) | (unsigned long long)(li + 1);
-    uint64_t slot = h & A.p_mask, probes = 0;
-    for (;;) {
-        unsigned long long cur = A.p_table[slot];
-        if (cur == 0ull) {
-            cur = atomicCAS(&A.p_table[slot], 0ull, mine);
-            if (cur == 0ull) return;
-        }
-        if ((cur >> 32) == tag) {
-            const int64_t r = (int64_t)(cur & 0xffffffffull) - 1;
-            if (A.p_hash[r] == h && bq_same_tuple(A, li, r)) return;      // listed twice
-        }
-        slot = (slot + 1) & A.p_mask;
-        if (++probes > A.p_mask) { bs_flag(A, li, MC_BED_DECLINE_TABLE); return; }     // (the host sizes the table so that it is not full)
-    }
+    const uint64_t h = A.p_hash[li];
+    // (a tuple listed twice finds its slot taken and stops there)
+    if (kt_claim(A.p_table, A.p_mask, h, li, [&](int64_t r) { return A.p_hash[r] == h && bq_same_tuple(A, li, r); }).slot < 0)
+        line_flag(&A.head->decline, li, MC_BED_DECLINE_TABLE);
 }
 
 // is (chrom, pos text, str(pos + 1), strand) of the row at t listed?  t0 .. t5: the row's tabs, pos: its position as an integer
 __device__ __forceinline__ bool bq_wanted(const BsArgs &A, const char *t, int t0, int t1, int t2, int t4, int t5, uint32_t pos) {
     const uint32_t end = pos + 1u;
-    BqHash H;
+    KeyHash H;
     H.span(t, t0); H.sep();
     H.span(t + t1 + 1, t2 - t1 - 1); H.sep();
     rt_put_uint(H, end); H.sep();
     H.span(t + t4 + 1, t5 - t4 - 1);
-    const uint64_t h = H.done(A.hash_mask), tag = h >> 32;
-    uint64_t slot = h & A.p_mask, probes = 0;
-    for (;;) {
-        const unsigned long long cur = A.p_table[slot];                // (the table is complete: kq_insert ran before)
-        if (cur == 0ull) return false;
-        if ((cur >> 32) == tag) {
-            const int64_t r = (int64_t)(cur & 0xffffffffull) - 1;
-            const BqLine L = bq_line(A, r);
-            const char *q = A.ptext + A.p_start[r];
-            if (A.p_hash[r] == h && L.t0 - L.sb == t0 && L.t1 - L.t0 == t2 - t1 && L.e3 - L.t2 == t5 - t4 &&
-                bq_same(q + L.sb, t, t0) && bq_same(q + L.t0 + 1, t + t1 + 1, t2 - t1 - 1) && bq_same(q + L.t2 + 1, t + t4 + 1, t5 - t4 - 1)) {
-                const int nd = L.t2 - L.t1 - 1;                        // field 3 == str(end): 1-10 digits, no leading zero, the same number
-                bool same = nd >= 1 && nd <= 10 && q[L.t1 + 1] != '0';
-                uint64_t v = 0;
-                for (int i = 0; i < nd && same; ++i) {
-                    const unsigned d = (unsigned)(unsigned char)q[L.t1 + 1 + i] - '0';
-                    same = d <= 9u;
-                    v = v * 10u + d;
-                }
-                if (same && v == (uint64_t)end) return true;
-            }
+    const uint64_t h = H.done(A.hash_mask);
+    return kt_find(A.p_table, A.p_mask, h, [&](int64_t r) {              // (the table is complete: kq_insert ran before)
+        const BqLine L = bq_line(A, r);
+        const char *q = A.ptext + A.p_start[r];
+        if (!(A.p_hash[r] == h && L.t0 - L.sb == t0 && L.t1 - L.t0 == t2 - t1 && L.e3 - L.t2 == t5 - t4 &&
+              same_bytes(q + L.sb, t, t0) && same_bytes(q + L.t0 + 1, t + t1 + 1, t2 - t1 - 1) && same_bytes(q + L.t2 + 1, t + t4 + 1, t5 - t4 - 1)))
+            return false;
+        const int nd = L.t2 - L.t1 - 1;                                // field 3 == str(end): 1-10 digits, no leading zero, the same number
+        bool same = nd >= 1 && nd <= 10 && q[L.t1 + 1] != '0';
+        uint64_t v = 0;
+        for (int i = 0; i < nd && same; ++i) {
+            const unsigned d = (unsigned)(unsigned char)q[L.t1 + 1 + i] - '0';
+            same = d <= 9u;
+            v = v * 10u + d;
         }
-        slot = (slot + 1) & A.p_mask;
-        if (++probes > A.p_mask) return false;
-    }
+        return same && v == (uint64_t)end;
+    }).slot >= 0;
 }

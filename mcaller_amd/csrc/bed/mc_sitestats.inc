@@ -15,9 +15,9 @@ __global__ __launch_bounds__(256) void kq_counts(BsArgs A) {
     if (li >= A.n_lines || !(A.fl[li] & BS_F_COUNTED)) return;
     const int64_t first = (int64_t)A.head->first_counted;
     const uint32_t nv = A.nval[li], ref = A.nval[first];
-    if (nv < 2u) bs_flag(A, li, MC_BED_DECLINE_FEW_VALUES);
-    else if (nv > (uint32_t)MC_BED_MAX_VALUES) bs_flag(A, li, MC_BED_DECLINE_MANY_VALUES);
-    else if (nv != ref) bs_flag(A, li, MC_BED_DECLINE_VALUE_COUNT);
+    if (nv < 2u) line_flag(&A.head->decline, li, MC_BED_DECLINE_FEW_VALUES);
+    else if (nv > (uint32_t)MC_BED_MAX_VALUES) line_flag(&A.head->decline, li, MC_BED_DECLINE_MANY_VALUES);
+    else if (nv != ref) line_flag(&A.head->decline, li, MC_BED_DECLINE_VALUE_COUNT);
     if (li == first) A.head->nv = (int)nv;
 }
 
@@ -27,7 +27,7 @@ __global__ __launch_bounds__(256) void kq_features(BsArgs A, int64_t n_num) {
     const int64_t s = idx / A.nv;
     const int j = (int)(idx - s * A.nv);
     const int64_t li = A.bucket[s];
-    const BsRow R = bs_row(A, li);
+    const TabSpan R = bs_row(A, li);
     const char *t = A.text + A.line_start[li];
     int b = R.t[3] + 1, k = 0;                                         // field 5 = (t3, t4): to the j-th comma
     const int fe = R.t[4];
@@ -35,7 +35,7 @@ __global__ __launch_bounds__(256) void kq_features(BsArgs A, int64_t n_num) {
     int e = b;
     while (e < fe && t[e] != ',') ++e;
     double v = 0.0;
-    if (k != j || !dc_parse(t + b, e - b, &v)) bs_flag(A, li, MC_BED_DECLINE_VALUE);
+    if (k != j || !dc_parse(t + b, e - b, &v)) line_flag(&A.head->decline, li, MC_BED_DECLINE_VALUE);
     A.X[idx] = v;
 }
 
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(256) void kq_finish(BsArgs A, int64_t n_sel) {
     else if (flags & TS_FAR_TAIL) reason = MC_BED_DECLINE_FAR_TAIL;
     else if (!n_t.ok || !n_sum.ok) reason = MC_BED_DECLINE_PRINT_RANGE;      // (before the tie: from 1e9 up a double has no thousandths left)
     else if (flags & (TS_TIE | TS_NO_CONVERGENCE | TS_BAD_N)) reason = MC_BED_DECLINE_ROUNDING_TIE;      // (no value to vouch for)
-    if (reason) { bs_flag(A, li, reason); return; }
+    if (reason) { line_flag(&A.head->decline, li, reason); return; }
     bq_store_num(A, 2 * (size_t)rep, n_t, false);
     bq_store_num(A, 2 * (size_t)rep + 1, n_sum, false);
 }

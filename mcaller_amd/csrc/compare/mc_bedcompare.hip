@@ -23,18 +23,19 @@
 //                MC_CMP_DECLINE_FAR_TAIL    a log10 p below -290
 //                MC_CMP_DECLINE_PRINT       a value mc_rowtext.h does not print
 //                MC_CMP_DECLINE_TIE         a value within its error bound of a rounding tie (mc_twosample.h)
-// Of several offending lines the first is named, bed1's before bed2's; of several reasons on it the smallest: atomicMin of
-// line << 8 | reason over the lines of both texts, as in the other file pipelines.
+// Of several offending lines the first is named, bed1's before bed2's; of several reasons on it the smallest: line_flag
+// (mc_textdev.h) over the lines of both texts.
 //
 // The two texts stand behind one another in one device buffer (a '\n' between them when bed1's last line has none), so one set of
 // line starts serves both; a line is bed1's when it starts before bed2's text.  The steps (L lines, S shared sites, V values):
 //   kp_count / kp_scan / kp_starts   line starts (mc_lines.h, launched by mc_textfeed.h)
-//   kc_parse     a lane per line: byte classes, the seven tabs, the key's 64-bit hash, the list's comma count, EVERY number's
+//   kc_parse     a lane per line: ByteClass, the seven tabs (tabs_pack), the key's KeyHash, the list's comma count, EVERY number's
 //                grammar (mc_decimal.h: the host calls float() on every line, shared or not); bed1's line count
-//   kc_insert    twice: bed2's keys, then bed1's, each into an open-addressing table of its own (slot = tag << 32 | line + 1 by
-//                atomicCAS, byte comparison on equal tags).  An equal key is a duplicate: the slot keeps the smaller line by
-//                atomicMin and the larger one is named, whatever order the lanes arrive in
-//   kc_probe     a lane per bed1 line against bed2's table -> the matching line or none, a 0 / 1 flag; the longest probe
+//   kc_insert    twice: bed2's keys, then bed1's, each into a key table of its own (kt_claim; ids are lines).  An equal key is a
+//                duplicate: the slot keeps the smaller line by atomicMin and the larger one is named, whatever order the lanes
+//                arrive in
+//   kc_probe     a lane per bed1 line against bed2's table (kt_find) -> the matching line or none, a 0 / 1 flag; the longest
+//                probe in slots read, the empty one included
 //   kp_scan      the flags: bed1's matched lines numbered in file order (no atomicAdd decides an order anywhere)
 //   kc_sites     a lane per bed1 line: its site's two lines and value counts; kp_scan x 2: the samples' offsets
 //   kc_tokens    a lane per site and sample: the spans of its numbers
@@ -113,32 +114,7 @@ struct CmpArgs {
     char *out;
 };
 
-__device__ __forceinline__ void cmp_flag(CmpHead *head, long long line, int reason) {
-    const unsigned long long code = ((unsigned long long)line << 8) | (unsigned)reason;
-    if (code < head->decline) atomicMin(&head->decline, code);     // (the value only falls: a stale one costs an atomic, no more)
-}
-
-struct CmpHash {                                         // FNV-1a, a 0xff between fields (no such byte in a text that is not declined)
-    uint64_t h = 0xcbf29ce484222325ull;
-    __device__ __forceinline__ void span(const char *p, int n) { for (int i = 0; i < n; ++i) h = (h ^ (uint64_t)(unsigned char)p[i]) * 0x100000001b3ull; }
-    __device__ __forceinline__ void sep() { h = (h ^ 0xffull) * 0x100000001b3ull; }
-    __device__ __forceinline__ uint64_t done(uint64_t mask) {
-        uint64_t v = h;
-        v ^= v >> 33; v *= 0xff51afd7ed558ccdull; v ^= v >> 33; v *= 0xc4ceb9fe1a85ec53ull; v ^= v >> 33;
-        return v & mask;
-    }
-};
-
-struct CmpLine { int t[7], len; bool ok; };
-
-__device__ __forceinline__ CmpLine cmp_line(const CmpArgs &A, int64_t li) {
-    const uint4 r = A.span[li];
-    CmpLine L;
-    L.t[0] = (int)(r.x & 0xffffu); L.t[1] = (int)(r.x >> 16); L.t[2] = (int)(r.y & 0xffffu); L.t[3] = (int)(r.y >> 16);
-    L.t[4] = (int)(r.z & 0xffffu); L.t[5] = (int)(r.z >> 16); L.t[6] = (int)(r.w & 0xffffu); L.len = (int)(r.w >> 16);
-    L.ok = r.w != 0u;
-    return L;
-}
+__device__ __forceinline__ TabSpan cmp_line(const CmpArgs &A, int64_t li) { return tabs_unpack(A.span[li]); }
 
 __global__ __launch_bounds__(256) void kc_parse(CmpArgs A) {
     const int64_t li = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -150,15 +126,14 @@ __global__ __launch_bounds__(256) void kc_parse(CmpArgs A) {
     A.hash[li] = 0;
     A.n_vals[li] = 0;
     if (b < A.off2 && (li + 1 >= n_lines || (int64_t)A.line_start[li + 1] >= A.off2)) A.head->n_lines1 = li + 1;      // bed1's last line alone
-    if (e - b > 65535) { cmp_flag(A.head, li, MC_CMP_DECLINE_LONG_LINE); return; }
+    if (e - b > 65535) { line_flag(&A.head->decline, li, MC_CMP_DECLINE_LONG_LINE); return; }
     const char *t = A.text + b;
     const int len = (int)(e - b);
-    bool bad_hi = false, bad_ctrl = false;
+    ByteClass bad;
     int tab[7] = {0, 0, 0, 0, 0, 0, 0}, nt = 0, commas = 0;
     for (int i = 0; i < len; ++i) {
         const unsigned c = (unsigned char)t[i];
-        bad_hi |= c >= 0x80u;
-        bad_ctrl |= (c < 0x20u && c != '\t') || c == 0x7fu;
+        bad.see(c);
         if (c == '\t') {
 #pragma unroll
             for (int k = 0; k < 7; ++k) tab[k] = nt == k ? i : tab[k];
@@ -166,12 +141,12 @@ __global__ __launch_bounds__(256) void kc_parse(CmpArgs A) {
         }
         commas += (c == ',' && nt == 7) ? 1 : 0;
     }
-    if (bad_hi) { cmp_flag(A.head, li, MC_CMP_DECLINE_HIGH_BYTE); return; }
-    if (bad_ctrl) { cmp_flag(A.head, li, MC_CMP_DECLINE_CONTROL); return; }
-    if (nt != 7) { cmp_flag(A.head, li, MC_CMP_DECLINE_FIELDS); return; }
+    if (bad.hi) { line_flag(&A.head->decline, li, MC_CMP_DECLINE_HIGH_BYTE); return; }
+    if (bad.ctrl) { line_flag(&A.head->decline, li, MC_CMP_DECLINE_CONTROL); return; }
+    if (nt != 7) { line_flag(&A.head->decline, li, MC_CMP_DECLINE_FIELDS); return; }
     // chrom [0, t0), start (t0, t1), end (t1, t2), strand (t4, t5), the list (t6, len)
     if (tab[0] == 0 || tab[1] - tab[0] == 1 || tab[2] - tab[1] == 1 || tab[5] - tab[4] == 1 || len - tab[6] == 1) {
-        cmp_flag(A.head, li, MC_CMP_DECLINE_EMPTY);
+        line_flag(&A.head->decline, li, MC_CMP_DECLINE_EMPTY);
         return;
     }
     // every number of every line, shared or not: the host calls float() on all of them before it looks at a key
@@ -182,58 +157,38 @@ __global__ __launch_bounds__(256) void kc_parse(CmpArgs A) {
             bad_number |= !dc_parse(t + tb, p - tb, &d);
             tb = p + 1;
         }
-    if (bad_number) { cmp_flag(A.head, li, MC_CMP_DECLINE_NUMBER); return; }
-    CmpHash H;
+    if (bad_number) { line_flag(&A.head->decline, li, MC_CMP_DECLINE_NUMBER); return; }
+    KeyHash H;
     H.span(t, tab[0]); H.sep();
     H.span(t + tab[0] + 1, tab[1] - tab[0] - 1); H.sep();
     H.span(t + tab[1] + 1, tab[2] - tab[1] - 1); H.sep();
     H.span(t + tab[4] + 1, tab[5] - tab[4] - 1);
     A.hash[li] = H.done(A.hash_mask);
     A.n_vals[li] = (uint32_t)commas + 1u;
-    A.span[li] = make_uint4((uint32_t)tab[0] | ((uint32_t)tab[1] << 16), (uint32_t)tab[2] | ((uint32_t)tab[3] << 16),
-                            (uint32_t)tab[4] | ((uint32_t)tab[5] << 16), (uint32_t)tab[6] | ((uint32_t)len << 16));
-}
-
-__device__ __forceinline__ bool cmp_same(const char *a, const char *b, int n) {
-    for (int i = 0; i < n; ++i)
-        if (a[i] != b[i]) return false;
-    return true;
+    A.span[li] = tabs_pack(tab, len);
 }
 
 // the keys of lines a and b, byte for byte: chrom, start and end are one span with its tabs, the strand another
 __device__ __forceinline__ bool cmp_same_key(const CmpArgs &A, int64_t a, int64_t b) {
-    const CmpLine La = cmp_line(A, a), Lb = cmp_line(A, b);
+    const TabSpan La = cmp_line(A, a), Lb = cmp_line(A, b);
     if (La.t[0] != Lb.t[0] || La.t[1] != Lb.t[1] || La.t[2] != Lb.t[2] || La.t[5] - La.t[4] != Lb.t[5] - Lb.t[4]) return false;
     const char *pa = A.text + A.line_start[a], *pb = A.text + A.line_start[b];
-    return cmp_same(pa, pb, La.t[2]) && cmp_same(pa + La.t[4] + 1, pb + Lb.t[4] + 1, La.t[5] - La.t[4] - 1);
+    return same_bytes(pa, pb, La.t[2]) && same_bytes(pa + La.t[4] + 1, pb + Lb.t[4] + 1, La.t[5] - La.t[4] - 1);
 }
 
 // which = 0: bed1's lines [0, n_lines1) into table[0]; 1: bed2's [n_lines1, n_lines) into table[1]
 __global__ __launch_bounds__(256) void kc_insert(CmpArgs A, int which) {
     const int64_t li = (int64_t)blockIdx.x * 256 + threadIdx.x + (which ? A.n_lines1 : 0);
-    if (li >= (which ? A.n_lines : A.n_lines1) || !cmp_line(A, li).ok) return;
+    if (li >= (which ? A.n_lines : A.n_lines1) || cmp_line(A, li).len == 0) return;      // (a line kc_parse left out)
     unsigned long long *table = A.table[which];
-    const uint64_t mask = A.mask[which], h = A.hash[li], tag = h >> 32;
-    const unsigned long long mine = (tag << 32) | (unsigned long long)(li + 1);
-    uint64_t slot = h & mask, probes = 0;
-    for (;;) {
-        unsigned long long cur = table[slot];
-        if (cur == 0ull) {
-            cur = atomicCAS(&table[slot], 0ull, mine);
-            if (cur == 0ull) return;
-        }
-        if ((cur >> 32) == tag) {
-            const int64_t r = (int64_t)(cur & 0xffffffffull) - 1;
-            if (A.hash[r] == h && cmp_same_key(A, li, r)) {
-                // the same key twice: the slot keeps the smaller line, the larger of the two that met here is named
-                const unsigned long long old = atomicMin(&table[slot], mine);
-                const int64_t other = (int64_t)(old & 0xffffffffull) - 1;
-                cmp_flag(A.head, other > li ? other : li, MC_CMP_DECLINE_DUPLICATE);
-                return;
-            }
-        }
-        slot = (slot + 1) & mask;
-        if (++probes > mask) { cmp_flag(A.head, li, MC_CMP_DECLINE_TABLE); return; }
+    const uint64_t h = A.hash[li];
+    const KtHit hit = kt_claim(table, A.mask[which], h, li, [&](int64_t r) { return A.hash[r] == h && cmp_same_key(A, li, r); });
+    if (hit.slot < 0) line_flag(&A.head->decline, li, MC_CMP_DECLINE_TABLE);
+    else if (!hit.claimed) {
+        // the same key twice: the slot keeps the smaller line, the larger of the two that met here is named
+        const unsigned long long old = atomicMin(&table[hit.slot], kt_word(h, li));
+        const int64_t other = (int64_t)(old & 0xffffffffull) - 1;
+        line_flag(&A.head->decline, other > li ? other : li, MC_CMP_DECLINE_DUPLICATE);
     }
 }
 
@@ -241,22 +196,12 @@ __global__ __launch_bounds__(256) void kc_probe(CmpArgs A) {
     const int64_t li = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (li >= A.n_lines1) return;
     long long found = -1;
-    int looked = 0;
-    if (cmp_line(A, li).ok) {
-        const unsigned long long *table = A.table[1];
-        const uint64_t mask = A.mask[1], h = A.hash[li], tag = h >> 32;
-        uint64_t slot = h & mask, probes = 0;
-        for (;;) {
-            const unsigned long long cur = table[slot];                // (the table is complete: kc_insert ran before)
-            ++looked;
-            if (cur == 0ull) break;
-            if ((cur >> 32) == tag) {
-                const int64_t r = (int64_t)(cur & 0xffffffffull) - 1;
-                if (A.hash[r] == h && cmp_same_key(A, li, r)) { found = r; break; }
-            }
-            slot = (slot + 1) & mask;
-            if (++probes > mask) break;
-        }
+    int looked = 0;                                                    // slots read, the empty one included
+    if (cmp_line(A, li).len != 0) {
+        const uint64_t h = A.hash[li];                                 // (the table is complete: kc_insert ran before)
+        const KtHit hit = kt_find(A.table[1], A.mask[1], h, [&](int64_t r) { return A.hash[r] == h && cmp_same_key(A, li, r); });
+        found = hit.id;
+        looked = (int)hit.looked;
     }
     A.match[li] = found;
     A.flag[li] = found >= 0 ? 1 : 0;
@@ -272,7 +217,7 @@ __global__ __launch_bounds__(256) void kc_sites(CmpArgs A) {
     A.line1[s] = li; A.line2[s] = r;
     A.cnt1[s] = c1; A.cnt2[s] = c2;
     const long long n = c1 + c2;
-    if (n > TW_MAX_N) { cmp_flag(A.head, li, MC_CMP_DECLINE_DEPTH); A.cnt1[s] = 0; A.cnt2[s] = 0; }
+    if (n > TW_MAX_N) { line_flag(&A.head->decline, li, MC_CMP_DECLINE_DEPTH); A.cnt1[s] = 0; A.cnt2[s] = 0; }
     const int deep = (int)(n > 0x7fffffffll ? 0x7fffffffll : n);
     if (deep > A.head->deepest) atomicMax(&A.head->deepest, deep);
 }
@@ -285,7 +230,7 @@ __global__ __launch_bounds__(256) void kc_tokens(CmpArgs A) {
     const int side = (int)(i & 1);
     const long long li = side ? A.line2[s] : A.line1[s];
     const long long at = side ? A.n_x + A.off2v[s] : A.off1[s], k = side ? A.cnt2[s] : A.cnt1[s];
-    const CmpLine L = cmp_line(A, li);
+    const TabSpan L = cmp_line(A, li);
     const int64_t b = A.line_start[li];
     long long j = 0;
     int tb = L.t[6] + 1;
@@ -300,7 +245,7 @@ __global__ __launch_bounds__(256) void kc_values(CmpArgs A) {
     const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (v >= A.n_x + A.n_y) return;
     double d = 0.0;
-    if (!dc_parse(A.text + A.tok_b[v], (int)A.tok_n[v], &d)) cmp_flag(A.head, A.tok_line[v], MC_CMP_DECLINE_NUMBER);
+    if (!dc_parse(A.text + A.tok_b[v], (int)A.tok_n[v], &d)) line_flag(&A.head->decline, A.tok_line[v], MC_CMP_DECLINE_NUMBER);
     A.vals[v] = d;
 }
 
@@ -464,7 +409,7 @@ __global__ __launch_bounds__(256) void kc_finish(const TwSite *__restrict__ site
 template <class Sink>
 __device__ __forceinline__ void cmp_put_row(const CmpArgs &A, int64_t s, Sink &o) {
     const long long l1 = A.line1[s], l2 = A.line2[s];
-    const CmpLine L1 = cmp_line(A, l1), L2 = cmp_line(A, l2);
+    const TabSpan L1 = cmp_line(A, l1), L2 = cmp_line(A, l2);
     const char *p1 = A.text + A.line_start[l1], *p2 = A.text + A.line_start[l2];
     for (int i = 0; i <= L1.t[2]; ++i) o.put(p1[i]);                   // chrom, start, end and the tab behind each
     for (int i = L1.t[4] + 1; i <= L1.t[5]; ++i) o.put(p1[i]);         // strand, its tab
@@ -487,7 +432,7 @@ __global__ __launch_bounds__(256) void kc_size(CmpArgs A) {
         const int reason = (st & TW_ALL_EQUAL) ? MC_CMP_DECLINE_ALL_EQUAL : (st & (TW_BAD_N | TW_ZERO_VAR)) ? MC_CMP_DECLINE_NAN
                          : (st & TW_DEEP) ? MC_CMP_DECLINE_DEPTH : (st & TW_FAR_TAIL) ? MC_CMP_DECLINE_FAR_TAIL
                          : (st & TW_UNPRINTABLE) ? MC_CMP_DECLINE_PRINT : MC_CMP_DECLINE_TIE;
-        cmp_flag(A.head, A.line1[s], reason);
+        line_flag(&A.head->decline, A.line1[s], reason);
         return;
     }
     RtCount count;
@@ -550,15 +495,6 @@ bool cmp_fits(size_t bytes) {
     return have > 0 ? bytes <= (size_t)have : device_fits(bytes);
 }
 
-int64_t table_slots(int64_t keys) {
-    const char *e = getenv("MCALLER_CMP_TABLE_SLOTS");
-    int64_t want = e ? atoll(e) : 0;                                   // (tests: a table that is too small)
-    if (want < 1) want = std::max<int64_t>(64, 2 * keys);
-    int64_t slots = 1;
-    while (slots < want) slots <<= 1;
-    return slots;
-}
-
 int launch_ranks(hipStream_t st, const RankArgs &R) {
     if (R.S <= 0) return 0;
     hipLaunchKernelGGL(kc_rank_small, dim3((unsigned)((R.S + 3) / 4)), dim3(CR_THREADS), 0, st, R);
@@ -602,13 +538,11 @@ int cmp_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, int64_t off2, 
     A.n_lines = L; A.n_lines1 = L1;
     S.n_keys2 = L2;
     if (L1 > 0 && L2 > 0) {
-        A.mask[0] = (uint64_t)table_slots(L1) - 1; A.mask[1] = (uint64_t)table_slots(L2) - 1;
+        A.mask[0] = table_slots(L1, 64, "MCALLER_CMP_TABLE_SLOTS") - 1; A.mask[1] = table_slots(L2, 64, "MCALLER_CMP_TABLE_SLOTS") - 1;
         S.table_slots = (int64_t)A.mask[1] + 1;
         if (!cmp_fits((A.mask[0] + A.mask[1] + 2) * 8 + ((size_t)1 << 20))) return cmp_decline(c, status, MC_CMP_DECLINE_MEMORY, 0, -1);
-        for (int w = 0; w < 2; ++w) {
-            if (pool.get(&A.table[w], (size_t)A.mask[w] + 1)) return -10;
-            HIP_TRY(hipMemsetAsync(A.table[w], 0, ((size_t)A.mask[w] + 1) * 8, st));
-        }
+        for (int w = 0; w < 2; ++w)
+            if (int rc = table_get(pool, st, &A.table[w], A.mask[w] + 1)) return rc;
         hipLaunchKernelGGL(kc_insert, dim3(blocks(L2)), dim3(256), 0, st, A, 1);
         hipLaunchKernelGGL(kc_insert, dim3(blocks(L1)), dim3(256), 0, st, A, 0);
         hipLaunchKernelGGL(kc_probe, dim3(blocks(L1)), dim3(256), 0, st, A);

@@ -11,7 +11,7 @@
 //   kp_count / kp_scan / kp_starts   line starts (the device parser's kernels: mc_lines.h, launched by mc_textfeed.h)
 //   kfq_class    a stream over the whole text, 64 bytes a lane in four 16-byte loads: the byte classes and the '\r' rule four bytes
 //                at a time (the byte behind a word and behind the tile is looked at too), the last byte that is no blank, tab or
-//                line break by atomicMax.  Only a lane that found something walks its bytes: atomicMin of line << 8 | reason
+//                line break by atomicMax.  Only a lane that found something walks its bytes: line_flag (mc_textdev.h)
 //   kfq_last     one lane: the line of that last byte -> R
 //   kfq_records  a lane per record: fq_record on its four line spans (the title line, the two ends of the sequence line, one byte
 //                of the third) -> the key's span and length + 1 (kfq_keylen is merged into it: the title is read once), the
@@ -25,7 +25,7 @@
 //   kfq_keys     a lane per record: its key and a '\n' into the pool; the offsets' last entry
 // wave64; no library sort or scan; every buffer, event and stream through the owners of mc_own.h.
 // The host side around the kernels -- a file's way onto the device through the context's two pinned stages, the line starts, the
-// head's way back, the decline, the clock -- is mc_textfeed.h's, shared with the other three units that take a whole text file.
+// head's way back, the decline, the clock -- is mc_textfeed.h's, shared with the other units that take a whole text file.
 #include "../mc_textfeed.h"
 #include "../mc_fastqrec.h"
 
@@ -56,10 +56,6 @@ struct FqArgs {
     char *pool;
 };
 
-__device__ __forceinline__ void fq_flag(FqHead *head, unsigned long long code) {
-    if (code < head->decline) atomicMin(&head->decline, code);     // (the value only falls: a stale one costs an atomic, no more)
-}
-
 // the bytes [b, e) one by one: the declines with their lines, the last byte that fills a line -> 1 + its offset, 0: none
 __device__ __noinline__ unsigned long long fq_class_bytes(const char *__restrict__ text, int64_t n, const long long *__restrict__ line_start,
                                                           int64_t n_nl, FqHead *head, int64_t b, int64_t e) {
@@ -70,7 +66,7 @@ __device__ __noinline__ unsigned long long fq_class_bytes(const char *__restrict
         const int reason = fq_byte_reason(c, i + 1 < n ? (int)(unsigned char)text[i + 1] : -1);
         if (reason) {
             if (line < 0) line = fq_line_of(line_start, n_nl, i);
-            fq_flag(head, fq_code(line, reason));
+            line_flag(&head->decline, line, reason);
         }
         if (!fq_blank(c) && c != '\r' && c != '\n') last1 = (unsigned long long)i + 1;
         if (c == '\n' && line >= 0) ++line;
@@ -137,7 +133,7 @@ __global__ __launch_bounds__(256) void kfq_records(FqArgs A) {
     FqRecord rec;
     const unsigned long long code = fq_record(A.text, r, b, e, &rec);
     if (code) {
-        fq_flag(A.head, code);
+        line_flag(&A.head->decline, (long long)(code >> 8), (int)(code & 0xff));       // (fq_record's code: fq_code of the line and the reason)
         rec.key_n = 0; rec.qual_n = 0;                         // (nothing behind this kernel runs on a declined text; the arrays are whole all the same)
     }
     A.key_b[r] = rec.key_b;

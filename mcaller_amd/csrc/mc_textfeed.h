@@ -19,8 +19,11 @@
 // Several texts behind one another in one buffer (the merge, the comparison): feed.send(src, d_dst, &last_byte) for each, then
 // feed.pad_and_wait(d_end).  The feed's two pinned stages and their events are the context's (mc_ctx::text_stages): the calls of
 // the five units are synchronous and never run side by side, so one pair serves them all.
+// The device side the five share -- the decline word, byte classes, key hash, key table, tab spans, LDS staging -- is mc_textdev.h,
+// which comes in through this header; table_slots / table_get below are its key table's host half.
 #pragma once
 #include "mc_lines.h"
+#include "mc_textdev.h"
 
 #include <sys/stat.h>
 
@@ -82,6 +85,23 @@ int decline(S &stats, int32_t *status, const char *noun, const char *text, int r
 }
 inline int decline_reason(unsigned long long word) { return (int)(word & 0xff); }
 inline long long decline_line(unsigned long long word) { return (long long)(word >> 8); }
+
+// ---- a key table (mc_textdev.h): its slots, a power of two of at least `floor` and 2 x keys -- or of at least the number in the
+// environment variable `knob`, where that is 1 or more (tests: a table that is too small) -- and the table itself from the pool,
+// every slot empty (on the stream) ----
+inline uint64_t table_slots(int64_t keys, int64_t floor, const char *knob = nullptr) {
+    const char *e = knob ? getenv(knob) : nullptr;
+    long long want = e ? atoll(e) : 0;
+    if (want < 1) want = std::max<long long>(floor, 2 * keys);
+    uint64_t slots = 1;
+    while ((long long)slots < want) slots <<= 1;
+    return slots;
+}
+inline int table_get(Pool &pool, hipStream_t st, unsigned long long **table, uint64_t slots) {
+    if (pool.get(table, (size_t)slots)) return -10;
+    HIP_TRY(hipMemsetAsync(*table, 0, (size_t)slots * 8, st));
+    return 0;
+}
 
 // ---- the line starts of a text on the device (padded, n > 0), in two halves: a unit puts kernels of its own between them and
 // fetches its head once for both.  tile_off: the scan of the first half, which the second reads ----

@@ -18,7 +18,7 @@
 // The steps (one lane per line or item unless said otherwise; n = lines):
 //   kp_count / kp_scan / kp_starts   line starts (the device parser's kernels: mc_lines.h, launched by mc_textfeed.h)
 //   km_cr         the smallest offset of a '\r', 16 bytes a load (atomicMin: whatever the order)
-//   km_key        mc_sortkey.h on the line -> the 128-bit key (hi, lo), the length; a flagged line: atomicMin of line << 8 | reason
+//   km_key        mc_sortkey.h on the line -> the 128-bit key (hi, lo), the length; a flagged line: line_flag (mc_textdev.h)
 // then rounds over the ITEMS, the lines whose place is not yet decided (at first all of them, one segment).  A round orders every
 // segment by one 64-bit word: the key's hi, the key's lo, then bytes [8r, 8r + 8) of the line, big-endian, zeros behind the newline:
 //   km_word       the word of every item; OR and AND of all words and of all segment numbers (atomicOr / atomicAnd): a byte in which
@@ -38,7 +38,7 @@
 // integer atomic (min, or, and, add to a counter; the list of km_small is worked through segment by segment, so its order does not
 // matter).  wave64; no library sort; every buffer, event and stream through the owners of mc_own.h.
 // The host side around the kernels -- a file's way onto the device through the context's two pinned stages, the line starts, the
-// head's way back, the decline, the clock -- is mc_textfeed.h's, shared with the other three units that take a whole text file.
+// head's way back, the decline, the clock -- is mc_textfeed.h's, shared with the other units that take a whole text file.
 #include "../mc_textfeed.h"
 #include "../mc_sortkey.h"
 
@@ -91,10 +91,6 @@ struct MgArgs {
     char *out;
 };
 
-__device__ __forceinline__ void mg_flag(const MgArgs &A, int64_t li, int reason) {
-    atomicMin(&A.head->decline, ((unsigned long long)li << 8) | (unsigned long long)reason);
-}
-
 // bit 7 of every byte of v that equals '\r'
 __device__ __forceinline__ uint32_t mg_cr_bits(uint32_t v) {
     v ^= 0x0D0D0D0Du;
@@ -120,10 +116,10 @@ __global__ __launch_bounds__(256) void km_key(MgArgs A) {
     const int64_t b = A.line_start[li], e = A.line_start[li + 1];       // (every line has its newline: the host saw to it)
     uint64_t hi = 0, lo = 0;
     int len = 0;
-    if (e - b > MG_MAX_LINE) mg_flag(A, li, MC_MERGE_DECLINE_LONG_LINE);
+    if (e - b > MG_MAX_LINE) line_flag(&A.head->decline, li, MC_MERGE_DECLINE_LONG_LINE);
     else {
         len = (int)(e - b);
-        if (sk_key(reinterpret_cast<const unsigned char *>(A.text + b), len, &hi, &lo)) mg_flag(A, li, MC_MERGE_DECLINE_KEY);
+        if (sk_key(reinterpret_cast<const unsigned char *>(A.text + b), len, &hi, &lo)) line_flag(&A.head->decline, li, MC_MERGE_DECLINE_KEY);
     }
     A.khi[li] = hi; A.klo[li] = lo; A.len[li] = (uint16_t)len;
     A.ln[li] = (uint32_t)li; A.sg[li] = 0u; A.apos[li] = (uint32_t)li;

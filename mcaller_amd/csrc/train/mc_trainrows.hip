@@ -22,21 +22,20 @@
 //
 // The steps (one lane per line unless said otherwise; n = lines):
 //   kp_count / kp_scan / kp_starts   line starts (the device parser's kernels: mc_lines.h, launched by mc_textfeed.h)
-//   kt_parse     256 lines of a workgroup staged in LDS with 16-byte loads (a piece that does not fit: read in place); per line the
-//                class of every byte, the tabs, the context's span and centre pair, the stripped label's span and a 64-bit hash
-//                of its bytes, the commas of the feature field, the literal-"0" test, the kept flag.  A flagged line: atomicMin of
-//                line << 8 | reason -- the decline names the FIRST such line, whatever the order; the first kept line's
-//                feature count the same way
-//   kt_intern    labels into a table of 64 slots: slot = tag << 32 | row + 1 claimed by atomicCAS, a taken slot matches when the
-//                tag, the whole hash and the label bytes of its row are equal; atomicMin of the line per slot.  The host orders
-//                the (at most 16) taken slots by that line: label ids do not depend on the order of arrival
+//   kt_parse     256 lines of a workgroup through LDS (staged_lines, mc_textdev.h; a piece that does not fit: read in place, and
+//                counted); per line the class of every byte, the tabs, the context's span and centre pair, the stripped label's
+//                span and the KeyHash of its bytes, the commas of the feature field, the literal-"0" test, the kept flag.  A
+//                flagged line: line_flag; the first kept line's feature count by an atomicMin of the same form
+//   kt_intern    labels into the key table of 64 slots inside the head (kt_claim; ids are rows); atomicMin of the line per slot.
+//                The host orders the (at most 16) taken slots by that line: label ids do not depend on the order of arrival
 //   kt_count / kp_scan / kt_rank   kept rows per label and workgroup, exclusive scan label-major: a kept row's place among all
 //                rows of the result (ballots and scans, never atomicAdd: file order is part of the contract); kt_rank also
 //                lists the row's feature tokens (offset | length << 16) and checks its feature count
 //   kt_place     a lane per NUMBER: mc_decimal.h on the token -> X[row][j]; lane j = 0 copies the context, NUL-padded
 // wave64; no library sort; every buffer, event and stream through the owners of mc_own.h.
 // The host side around the kernels -- a file's way onto the device through the context's two pinned stages, the line starts, the
-// head's way back, the decline, the clock -- is mc_textfeed.h's, shared with the other three units that take a whole text file.
+// head's way back, the decline, the clock -- is mc_textfeed.h's, the device side named above mc_textdev.h's: shared with the other
+// units that take a whole text file.
 #include "../mc_textfeed.h"
 #include "../mc_decimal.h"
 
@@ -52,7 +51,7 @@ struct TrHead {                              // device-side result block (copied
     KpHead kp;                               // n_newlines (kp_scan), n_lines (kp_starts)
     unsigned long long decline;              // min over the flagged lines of line << 8 | reason (~0: none)
     unsigned long long first_kept;           // min over the kept lines of line << 8 | features (~0: none)
-    unsigned long long table[TR_SLOTS];      // 0: empty, else tag << 32 | row + 1
+    unsigned long long table[TR_SLOTS];      // the labels' key table (mc_textdev.h; ids are rows)
     unsigned long long first[TR_SLOTS];      // the smallest line that carries the slot's label
     long long n_kept;                        // total of the scan
     unsigned int n_claimed;                  // slots taken (+ 1000 for every row that found the table full)
@@ -82,10 +81,6 @@ struct TrArgs {
     char *ctx;
 };
 
-__device__ __forceinline__ void tr_flag(const TrArgs &A, int64_t li, int reason) {
-    atomicMin(&A.head->decline, ((unsigned long long)li << 8) | (unsigned long long)reason);
-}
-
 // One line: t[x - adj] is byte x of the text (the staged piece in LDS, or the text itself with adj = 0: one address space per call
 // site) -> the context's length if the row is kept, -1 if it is not
 __device__ __forceinline__ int tr_parse_line(const TrArgs &A, const char *t, const int64_t adj, const int64_t li) {
@@ -93,16 +88,16 @@ __device__ __forceinline__ int tr_parse_line(const TrArgs &A, const char *t, con
     const int64_t e = (li < A.n_nl ? A.line_start[li + 1] - 1 : A.n_bytes) - adj;        // the newline, or the end of the text
     A.row[li] = make_uint4(0u, 0u, 0u, 0u);
     A.hash[li] = 0;
-    if (e - b > 65535) { tr_flag(A, li, MC_TRAINROWS_DECLINE_LONG_LINE); return -1; }
+    if (e - b > 65535) { line_flag(&A.head->decline, li, MC_TRAINROWS_DECLINE_LONG_LINE); return -1; }
     const int len = (int)(e - b);
     int t2 = 0, t3 = 0, t4 = 0, t5 = 0, t6 = 0, nt = 0;
-    bool bad_hi = false, bad_ctrl = false, has0 = false;
+    ByteClass bad;
+    bool has0 = false;
     int commas = 0, flen = 0;
     unsigned lastc = 0;
     for (int i = 0; i < len; ++i) {
         const unsigned c = (unsigned char)t[b + i];
-        bad_hi |= c >= 0x80u;
-        bad_ctrl |= (c < 0x20u && c != '\t') || c == 0x7fu;
+        bad.see(c);
         if (c == '\t') {
             t2 = nt == 2 ? i : t2; t3 = nt == 3 ? i : t3; t4 = nt == 4 ? i : t4; t5 = nt == 5 ? i : t5; t6 = nt == 6 ? i : t6;
             ++nt;
@@ -113,31 +108,30 @@ __device__ __forceinline__ int tr_parse_line(const TrArgs &A, const char *t, con
     }
     has0 |= flen == 1 && lastc == '0';
     int reason = 0;
-    if (bad_hi) reason = MC_TRAINROWS_DECLINE_HIGH_BYTE;
-    else if (bad_ctrl) reason = MC_TRAINROWS_DECLINE_CONTROL;
+    if (bad.hi) reason = MC_TRAINROWS_DECLINE_HIGH_BYTE;
+    else if (bad.ctrl) reason = MC_TRAINROWS_DECLINE_CONTROL;
     else if (nt < 6) reason = MC_TRAINROWS_DECLINE_FIELDS;
-    if (reason) { tr_flag(A, li, reason); return -1; }
+    if (reason) { line_flag(&A.head->decline, li, reason); return -1; }
     if (nt == 6) t6 = len;
     const int cb = t2 + 1, cn = t3 - t2 - 1;
-    if (cn > MC_TRAINROWS_MAX_CONTEXT) { tr_flag(A, li, MC_TRAINROWS_DECLINE_CONTEXT); return -1; }
+    if (cn > MC_TRAINROWS_MAX_CONTEXT) { line_flag(&A.head->decline, li, MC_TRAINROWS_DECLINE_CONTEXT); return -1; }
     bool known = false;
     if (cn / 2 + 2 <= cn) {                                       // (a shorter slice is no two-character key)
         const unsigned pair = (unsigned)(unsigned char)t[b + cb + cn / 2] | ((unsigned)(unsigned char)t[b + cb + cn / 2 + 1] << 8);
         for (int k = 0; k < A.n_pairs; ++k) known |= (unsigned)A.head->pairs[k] == pair;
     }
-    if (!known) { tr_flag(A, li, MC_TRAINROWS_DECLINE_PAIR); return -1; }
+    if (!known) { line_flag(&A.head->decline, li, MC_TRAINROWS_DECLINE_PAIR); return -1; }
     int lb = t5 + 1, le = t6;                                     // columns[6].strip(): blanks are the only whitespace a line still holds
     while (lb < le && t[b + lb] == ' ') ++lb;
     while (le > lb && t[b + le - 1] == ' ') --le;
-    uint64_t h = 0xcbf29ce484222325ull;                           // FNV-1a over the label's bytes, then a finaliser
-    for (int i = lb; i < le; ++i) h = (h ^ (unsigned)(unsigned char)t[b + i]) * 0x100000001b3ull;
-    h ^= h >> 33; h *= 0xff51afd7ed558ccdull; h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53ull; h ^= h >> 33;
+    KeyHash H;                                                    // the label's bytes
+    H.span(t + b + lb, le - lb);
     const int nf = commas + 1;
     const bool kept = nf >= 6 && !has0;
-    if (kept && nf > MC_TRAINROWS_MAX_FEATURES) { tr_flag(A, li, MC_TRAINROWS_DECLINE_FEATURES); return -1; }
+    if (kept && nf > MC_TRAINROWS_MAX_FEATURES) { line_flag(&A.head->decline, li, MC_TRAINROWS_DECLINE_FEATURES); return -1; }
     A.row[li] = make_uint4((uint32_t)(t3 + 1) | ((uint32_t)t4 << 16), (uint32_t)cb | ((uint32_t)cn << 16), (uint32_t)lb | ((uint32_t)(le - lb) << 16),
                            (uint32_t)(nf > 65535 ? 65535 : nf) | ((kept ? TR_F_KEPT : 0u) << 16));
-    A.hash[li] = h & A.hash_mask;
+    A.hash[li] = H.done(A.hash_mask);
     if (kept) {
         const unsigned long long mine = ((unsigned long long)li << 8) | (unsigned long long)nf;
         if (mine < A.head->first_kept) atomicMin(&A.head->first_kept, mine);      // (the value only falls: a stale one costs an atomic, no more)
@@ -146,22 +140,10 @@ __device__ __forceinline__ int tr_parse_line(const TrArgs &A, const char *t, con
 }
 
 __global__ __launch_bounds__(256) void kt_parse(TrArgs A) {
-    extern __shared__ __attribute__((aligned(16))) char s_text[];      // TR_STAGE + 16 bytes
-    const int64_t l0 = (int64_t)blockIdx.x * 256;
-    const int64_t l1 = min(l0 + 256, A.n_lines);
-    const int64_t g0 = A.line_start[l0], g1 = l1 <= A.n_nl ? (int64_t)A.line_start[l1] : A.n_bytes;
-    const int64_t a0 = g0 & ~(int64_t)15;
-    const int64_t li = l0 + threadIdx.x;
     int cn = -1;
-    if (g1 - a0 <= TR_STAGE) {                               // (the text buffer is padded: whole 16-byte groups are readable)
-        for (int64_t i = (int64_t)threadIdx.x * 16; i < g1 - a0; i += 256 * 16)
-            *reinterpret_cast<uint4 *>(s_text + i) = *reinterpret_cast<const uint4 *>(A.text + a0 + i);
-        __syncthreads();
-        if (li < l1) cn = tr_parse_line(A, s_text, a0, li);
-    } else {                                                 // very long lines: read in place
-        if (threadIdx.x == 0) atomicAdd(&A.head->in_place, 1u);
-        if (li < l1) cn = tr_parse_line(A, A.text, 0, li);
-    }
+    const bool in_place = staged_lines<TR_STAGE>(A.text, A.n_bytes, A.line_start, A.n_lines, A.n_nl,
+                                                 [&](const char *t, int64_t adj, int64_t li) { cn = tr_parse_line(A, t, adj, li); });
+    if (in_place && threadIdx.x == 0) atomicAdd(&A.head->in_place, 1u);
     for (int o = 32; o > 0; o >>= 1) cn = max(cn, __shfl_xor(cn, o));
     if ((threadIdx.x & 63) == 0 && cn > 0) atomicMax(&A.head->max_ctx, cn);
 }
@@ -169,10 +151,7 @@ __global__ __launch_bounds__(256) void kt_parse(TrArgs A) {
 __device__ __forceinline__ bool tr_same_label(const TrArgs &A, int64_t a, int64_t b) {
     const uint32_t za = A.row[a].z, zb = A.row[b].z;
     if ((za >> 16) != (zb >> 16)) return false;
-    const char *ta = A.text + A.line_start[a] + (za & 0xffffu), *tb = A.text + A.line_start[b] + (zb & 0xffffu);
-    for (int i = 0; i < (int)(za >> 16); ++i)
-        if (ta[i] != tb[i]) return false;
-    return true;
+    return same_bytes(A.text + A.line_start[a] + (za & 0xffffu), A.text + A.line_start[b] + (zb & 0xffffu), (int)(za >> 16));
 }
 
 __global__ __launch_bounds__(256) void kt_intern(TrArgs A) {
@@ -180,28 +159,15 @@ __global__ __launch_bounds__(256) void kt_intern(TrArgs A) {
     if (li >= A.n_lines) return;
     TrHead *H = A.head;
     const uint64_t h = A.hash[li];
-    const uint64_t tag = h >> 32;
-    const unsigned long long mine = (tag << 32) | (unsigned long long)(li + 1);
-    int slot = (int)(h & (uint64_t)(TR_SLOTS - 1)), found = -1;
-    for (int probes = 0; probes < TR_SLOTS; ++probes) {
-        unsigned long long cur = H->table[slot];              // (a slot goes from empty to taken once: a stale "empty" is put right by the CAS)
-        if (cur == 0ull) {
-            cur = atomicCAS(&H->table[slot], 0ull, mine);
-            if (cur == 0ull) { found = slot; atomicAdd(&H->n_claimed, 1u); break; }
-        }
-        if ((cur >> 32) == tag) {
-            const int64_t r = (int64_t)(cur & 0xffffffffull) - 1;
-            if (A.hash[r] == h && tr_same_label(A, li, r)) { found = slot; break; }
-        }
-        slot = (slot + 1) & (TR_SLOTS - 1);
-    }
-    if (found < 0) {                                          // every slot holds another label: far more labels than a file may have
+    const KtHit hit = kt_claim(H->table, TR_SLOTS - 1, h, li, [&](int64_t r) { return A.hash[r] == h && tr_same_label(A, li, r); });
+    if (hit.slot < 0) {                                       // every slot holds another label: far more labels than a file may have
         atomicAdd(&H->n_claimed, 1000u);
         A.slot[li] = 0;
         return;
     }
-    A.slot[li] = (uint8_t)found;
-    if ((unsigned long long)li < H->first[found]) atomicMin(&H->first[found], (unsigned long long)li);
+    if (hit.claimed) atomicAdd(&H->n_claimed, 1u);
+    A.slot[li] = (uint8_t)hit.slot;
+    if ((unsigned long long)li < H->first[hit.slot]) atomicMin(&H->first[hit.slot], (unsigned long long)li);
 }
 
 // is line li kept, and which label does it carry (bounds, flags, the host's order of the slots)
@@ -221,7 +187,7 @@ __global__ __launch_bounds__(256) void kt_count(TrArgs A) {
     int id;
     uint4 row;
     const bool kept = tr_kept(A, li, &id, &row);
-    if (kept && (int)(row.w & 0xffffu) != A.nf) tr_flag(A, li, MC_TRAINROWS_DECLINE_FEATURES);
+    if (kept && (int)(row.w & 0xffffu) != A.nf) line_flag(&A.head->decline, li, MC_TRAINROWS_DECLINE_FEATURES);
     for (int L = 0; L < A.n_labels; ++L) {
         const unsigned long long bal = __ballot(kept && id == L);
         if ((threadIdx.x & 63) == 0 && bal) atomicAdd(&s_cnt[L], (unsigned)__popcll(bal));
@@ -274,7 +240,7 @@ __global__ __launch_bounds__(256) void kt_place(TrArgs A) {
     const char *t = A.text + A.line_start[li];
     const uint32_t tk = A.tok[xrow * A.nf + j];
     double v = 0.0;
-    if (!dc_parse(t + (tk & 0xffffu), (int)(tk >> 16), &v)) tr_flag(A, li, MC_TRAINROWS_DECLINE_NUMBER);
+    if (!dc_parse(t + (tk & 0xffffu), (int)(tk >> 16), &v)) line_flag(&A.head->decline, li, MC_TRAINROWS_DECLINE_NUMBER);
     A.X[xrow * A.nf + j] = v;
     if (j == 0) {
         const uint32_t y = A.row[li].y;

@@ -231,6 +231,27 @@ def ref_cases():
 REF_OPTIONS = [dict(gff=True, with_probs=False), dict(gff=True, with_probs=True), dict(gff=False, with_probs=False)]
 
 
+def id_hash(name):
+    """The 64-bit hash the device gives a FASTA id (KeyHash of csrc/mc_textdev.h: FNV-1a, then a finaliser)."""
+    m, h = (1 << 64) - 1, 0xcbf29ce484222325
+    for c in name.encode('ascii'):
+        h = ((h ^ c) * 0x100000001b3) & m
+    for mul in (0xff51afd7ed558ccd, 0xc4ceb9fe1a85ec53):
+        h = ((h ^ (h >> 33)) * mul) & m
+    return h ^ (h >> 33)
+
+
+def chained_ids_case():
+    """-> (fasta text, diffs text): twelve records whose ids all have the hash of 'ctg' in the four bits MCALLER_BED_HASH_MASK=f
+    leaves, so the table holds ONE probe chain; 'ctg' is the first, the sixth and the last record, each with another sequence."""
+    same = [n for n in ('r%d' % i for i in range(1000)) if id_hash(n) & 15 == id_hash('ctg') & 15][:7]
+    assert len(same) == 7
+    recs = ([('ctg', _seq(REF_L, 9))] + [(n, _seq(50, 30 + i)) for i, n in enumerate(same[:4])] + [('ctg', _seq(77, 10)), ('c30', SEQS['c30'])] +
+            [(n, _seq(50, 40 + i)) for i, n in enumerate(same[4:])] + [('c41', SEQS['c41']), ('ctg', SEQS['ctg'])])
+    assert len(recs) == 12
+    return fasta(recs), ref_rows()
+
+
 def decline_cases():
     """name -> (diffs text, fasta text or None, options, reason code of include/mcaller_hip.h, 0-based line the decline names)."""
     good = [B.row('ctg', str(30 + i % 3), 'AMA', '+', 'm6A', '0.5') for i in range(6)]

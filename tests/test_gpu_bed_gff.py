@@ -216,6 +216,19 @@ def test_ref_edges(tmp_path, monkeypatch, name):
             assert all(l.split(b'\t')[3] == b'AMA' for l in got.splitlines())
 
 
+def test_repeated_id_in_one_probe_chain(tmp_path, monkeypatch):
+    """Twelve records in one probe chain (MCALLER_BED_HASH_MASK=f, ids chosen for it), `ctg` the first, the sixth and the last of them
+    with three sequences: the last record wins, wherever in the chain the id stands."""
+    monkeypatch.setenv('MCALLER_BED_GFF_DEVICE', '1')
+    monkeypatch.setenv('MCALLER_BED_HASH_MASK', 'f')
+    fasta, text = F.chained_ids_case()
+    for opts in F.REF_OPTIONS[:2]:
+        (want, said, n), (got, got_said, got_n), who = both(tmp_path, text, opts, fasta=fasta)
+        assert who == dict(by='device', reason=None, n_sites=n), (opts, who)
+        assert got == want and got_said == said and got_n == n and n > 0, opts
+    assert F.SEQS['ctg'][:41].encode() in got and F._seq(F.REF_L, 9)[:41].encode() not in got
+
+
 def test_the_text_entry_point_equals_the_file_entry_point(tmp_path):
     from mcaller_amd.device import get_device
     fasta, text = REF_CASES['repeated_id']

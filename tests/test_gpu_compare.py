@@ -99,6 +99,23 @@ def test_long_probe_chains(dev, tmp_path, monkeypatch):
     device_makes_it(dev, tmp_path, t1, t2, 'hash mask, keys')
 
 
+@pytest.mark.parametrize('file', [1, 2])
+def test_duplicate_at_the_end_of_a_probe_chain(dev, monkeypatch, file):
+    """Forty keys in sixteen hash values (one cluster of taken slots), one of them once more as the file's last line: the later line
+    of the pair is named, as in duplicate_1 / duplicate_2 without the mask."""
+    monkeypatch.setenv('MCALLER_CMP_HASH_MASK', 'f')
+    t1, t2 = GC.small_pair()
+    assert t1.count(b'\n') == t2.count(b'\n') == 40
+    if file == 1:
+        t1 += t1.splitlines(True)[3]
+    else:
+        t2 += t2.splitlines(True)[17]
+    blob, n_sites, why = dev.bed_compare(text1=t1, text2=t2)
+    st = dev.bed_compare_last_stats()
+    assert blob is None and n_sites == 0 and '(bed%d)' % file in why and '(line 41)' in why
+    assert (st['decline_reason'], st['decline_file'], st['decline_line']) == (_lib.CMP_DECLINE['duplicate'], file, 40)
+
+
 def test_table_forced_too_small_declines(dev, tmp_path, monkeypatch):
     monkeypatch.setenv('MCALLER_CMP_TABLE_SLOTS', '8')
     t1, t2 = GC.small_pair()
