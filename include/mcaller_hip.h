@@ -917,6 +917,66 @@ int mc_twosample_device(mc_ctx *ctx, const double *x, const int64_t *x_off, cons
 double mc_twosample_log10_2sf(double z);
 double mc_twosample_log10_kolmogorov(double lam);
 
+/* ===== methylated motifs found de novo from called sites on the GPU (mcaller_amd/find_motifs.py; csrc/motifs/mc_motifscan.hip) =====
+ * For every shape (a string of X and '.', first and last X, at most MC_MOTIF_MAX_WIDTH wide, 2 to 8 X), every X of it as the called
+ * letter and every assignment of A, C, G, T to the X: the candidates of the reference (ref: contig_len, seq_off and the upper-cased
+ * seq; the masks are not read) that stand in such a window, those the bed or the control lists (covered; without a control all
+ * are) and those the bed lists (methylated).  The rows with nMethylated >= min_sites and nMethylated / nCovered >= min_fraction,
+ * less (keep_all = 0) those a selected row on a strict subset of their letters explains, ordered and printed as
+ * find_motifs.find_motifs does -- or the call declines: *status = 1, mc_last_error says why (mc_motif_report_last_stats: which
+ * file, line and reason), nothing is handed out and the caller runs the host statement, which words the errors.  Of several
+ * offending lines the first is named (the bed's before the control's), of several reasons on it the smallest.  *out points at
+ * n_out bytes of pinned memory owned by the context: valid until the next mc_motif_report_* call on it.
+ * Test knobs, read per call: MCALLER_MOTIF_HASH_MASK=<hex>, MCALLER_MOTIF_TABLE_SLOTS=n (the contig table),
+ * MCALLER_MOTIF_STRETCH=n (bases a workgroup of the counting kernel takes: a multiple of 64, the effective value is in the
+ * stats), MCALLER_MOTIF_DEVICE_BYTES=n (stands for the free device memory), MCALLER_TEXT_STAGE_BYTES (the feed). */
+#define MC_MOTIF_MAX_SHAPES 64
+#define MC_MOTIF_MAX_WIDTH 24
+typedef struct mc_motif_params {
+    int32_t base;                  /* 'A', 'C', 'G' or 'T'                                        */
+    int32_t n_shapes;              /* 1 .. MC_MOTIF_MAX_SHAPES                                    */
+    char shapes[MC_MOTIF_MAX_SHAPES][MC_MOTIF_MAX_WIDTH + 8];      /* NUL-terminated              */
+    int64_t min_sites;
+    double min_fraction;
+    int32_t keep_all, pad;         /* --all: rows that a shorter selected row explains stay       */
+    const char *contig_ids;        /* the ids of ref's contigs, one behind the other ...          */
+    const int64_t *contig_id_off;  /* ... id i is contig_ids[contig_id_off[i], contig_id_off[i + 1]); n_contigs + 1 entries */
+} mc_motif_params;
+typedef struct mc_motif_stats {
+    int64_t n_bytes1, n_bytes2, n_lines1, n_lines2;
+    int64_t n_candidates;          /* (position, strand) pairs whose base is the called base     */
+    int64_t n_sites, n_control;    /* distinct sites the bed lists, the control lists            */
+    int64_t n_off_base;            /* distinct listed sites whose base is not the called base    */
+    int64_t n_selected, n_rows;    /* entries over both thresholds; rows after redundancy        */
+    int64_t stretch, n_stretches;  /* bases a workgroup of km_count takes (effective), workgroups per table */
+    int64_t n_entries, table_slots, n_out_bytes;
+    int64_t decline_line;          /* 0-based line in its file the decline names, -1: none       */
+    int32_t decline_reason;        /* 0: not declined; MC_MOTIF_DECLINE_*                        */
+    int32_t decline_file;          /* 1: the bed, 2: the control, 0: none                        */
+    int32_t n_tables_lds, n_tables_global;      /* (shape, j) tables counted in LDS, straight in global memory */
+    double ms_read, ms_h2d, ms_kernels, ms_d2h, ms_total;
+} mc_motif_stats;
+#define MC_MOTIF_DECLINE_HIGH_BYTE   1   /* a byte >= 0x80                                                          */
+#define MC_MOTIF_DECLINE_CONTROL     2   /* a control byte other than tab and newline (0x7f and '\r' included)       */
+#define MC_MOTIF_DECLINE_LONG_LINE   3   /* a line longer than 65535 bytes                                          */
+#define MC_MOTIF_DECLINE_FIELDS      4   /* a line with fewer than 6 tab-separated fields (the host's ValueError)   */
+#define MC_MOTIF_DECLINE_FIELD       5   /* an empty chrom, a start that is not plain digits, a strand other than + / - */
+#define MC_MOTIF_DECLINE_CHROM       6   /* a chrom that is no contig of the reference                              */
+#define MC_MOTIF_DECLINE_RANGE       7   /* a start outside its contig                                              */
+#define MC_MOTIF_DECLINE_TABLE       8   /* the contig table is full (MCALLER_MOTIF_TABLE_SLOTS)                    */
+#define MC_MOTIF_DECLINE_MEMORY      9   /* the reference, the texts and the tables do not fit into device memory   */
+#define MC_MOTIF_DECLINE_REFERENCE   10  /* a reference of 2^31 bases or more (the counters are 32-bit)             */
+#define MC_MOTIF_DECLINE_PRINT       11  /* a fraction mc_rowtext.h does not print                                  */
+#define MC_MOTIF_DECLINE_ROWS        12  /* 2^31 - 2 lines or more in the two files together                        */
+int mc_motif_report_text(mc_ctx *ctx, const mc_ref_view *ref, const char *bed, int64_t n_bed, const char *control_or_null,
+                         int64_t n_control, const mc_motif_params *params, const char **out, int64_t *n_out, int64_t *n_rows,
+                         int32_t *status);
+/* ... of files: read in pinned blocks (mc_read_file_range) while the block before is on its way to the device. */
+int mc_motif_report_file(mc_ctx *ctx, const mc_ref_view *ref, const char *bed_path, const char *control_path_or_null,
+                         const mc_motif_params *params, const char **out, int64_t *n_out, int64_t *n_rows, int32_t *status);
+int mc_motif_report_last_stats(mc_ctx *ctx, mc_motif_stats *out);
+int mc_motif_report_release(mc_ctx *ctx);
+
 /* ===== measurement plumbing: a table as nanopolish-eventalign text (13 columns), written by all host cores =====
  * For file-to-file timing on synthetic workloads (bench.py); seq = the contig's bases (k-mers of columns 3 and 10). */
 int mc_synth_write_tsv(const char *path, const mc_table_view *table, const char *seq, int64_t seq_len, const char *contig,

@@ -158,6 +158,26 @@ class CmpStats(C.Structure):
                 ('ms_d2h', C.c_double), ('ms_total', C.c_double)]
 
 
+class MotifParams(C.Structure):
+    """mc_motif_params (include/mcaller_hip.h)."""
+    _fields_ = [('base', C.c_int32), ('n_shapes', C.c_int32), ('shapes', (C.c_char * 32) * 64), ('min_sites', C.c_int64),
+                ('min_fraction', C.c_double), ('keep_all', C.c_int32), ('pad', C.c_int32), ('contig_ids', C.c_void_p),
+                ('contig_id_off', C.c_void_p)]
+
+
+class MotifStats(C.Structure):
+    """mc_motif_stats (include/mcaller_hip.h)."""
+    _fields_ = [('n_bytes1', C.c_int64), ('n_bytes2', C.c_int64), ('n_lines1', C.c_int64), ('n_lines2', C.c_int64),
+                ('n_candidates', C.c_int64), ('n_sites', C.c_int64), ('n_control', C.c_int64), ('n_off_base', C.c_int64),
+                ('n_selected', C.c_int64), ('n_rows', C.c_int64), ('stretch', C.c_int64), ('n_stretches', C.c_int64),
+                ('n_entries', C.c_int64), ('table_slots', C.c_int64), ('n_out_bytes', C.c_int64), ('decline_line', C.c_int64),
+                ('decline_reason', C.c_int32), ('decline_file', C.c_int32), ('n_tables_lds', C.c_int32),
+                ('n_tables_global', C.c_int32), ('ms_read', C.c_double), ('ms_h2d', C.c_double), ('ms_kernels', C.c_double),
+                ('ms_d2h', C.c_double), ('ms_total', C.c_double)]
+
+
+MOTIF_DECLINE = {'high_byte': 1, 'control': 2, 'long_line': 3, 'fields': 4, 'field': 5, 'chrom': 6, 'range': 7, 'table': 8,
+                 'memory': 9, 'reference': 10, 'print': 11, 'rows': 12}                          # MC_MOTIF_DECLINE_*
 CMP_DECLINE = {'high_byte': 1, 'control': 2, 'fields': 3, 'empty': 4, 'long_line': 5, 'rows': 6, 'memory': 7, 'table': 8,
                'duplicate': 9, 'number': 10, 'depth': 11, 'nan': 12, 'all_equal': 13, 'far_tail': 14, 'print': 15,
                'tie': 16}                                                                        # MC_CMP_DECLINE_*
@@ -211,6 +231,13 @@ def lib():
                                           C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
         L.mc_bed_compare_last_stats.argtypes = [C.c_void_p, C.POINTER(CmpStats)]
         L.mc_bed_compare_release.argtypes = [C.c_void_p]
+        L.mc_motif_report_text.argtypes = [C.c_void_p, C.POINTER(RefView), C.c_char_p, C.c_int64, C.c_char_p, C.c_int64,
+                                           C.POINTER(MotifParams), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                           C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        L.mc_motif_report_file.argtypes = [C.c_void_p, C.POINTER(RefView), C.c_char_p, C.c_char_p, C.POINTER(MotifParams),
+                                           C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        L.mc_motif_report_last_stats.argtypes = [C.c_void_p, C.POINTER(MotifStats)]
+        L.mc_motif_report_release.argtypes = [C.c_void_p]
         L.mc_twosample.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
         L.mc_twosample_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                           C.c_void_p, C.c_void_p]

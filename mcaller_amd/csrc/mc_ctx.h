@@ -324,6 +324,10 @@ struct mc_ctx {
     Pinned cmp_out;
     size_t cmp_out_cap = 0;
     mc_cmp_stats cmp_stats = {};
+    // ... the rows of the motif finder (motifs/mc_motifscan.hip)
+    Pinned motif_out;
+    size_t motif_out_cap = 0;
+    mc_motif_stats motif_stats = {};
 };
 
 // ---- what crosses the units ----

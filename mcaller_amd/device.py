@@ -891,6 +891,62 @@ class Device(object):
     def bed_compare_release(self):
         check(lib().mc_bed_compare_release(self._ctx))
 
+    # ---- methylated motifs from called sites (csrc/motifs/mc_motifscan.hip) ----
+    @_serialized
+    def motif_report(self, ref, path=None, control_path=None, text=None, control_text=None, base='A', shapes=('XXXX',), min_sites=20,
+                     min_fraction=0.5, keep_all=False):
+        """The rows of find_motifs for the reference `ref` ({id: upper-cased sequence}), the sites of a make_bed summary (`path`,
+        or its `text`, bytes) and optionally a make_bed --control summary (`control_path` / `control_text`), made on the GPU ->
+        (blob: bytes, n_rows, None), or (None, 0, reason) when the device declines: the caller runs the host statement."""
+        if (path is None) == (text is None) or (path is None and control_path is not None) or (text is None and control_text is not None):
+            raise ValueError('motif_report: paths or texts')
+        ids = [name.encode('latin-1', 'replace') for name in ref]
+        seqs = [seq.encode('latin-1', 'replace') for seq in ref.values()]
+        lens = np.asarray([len(s) for s in seqs], dtype=np.int64).reshape(-1)
+        seq_off = np.zeros(len(seqs) + 1, dtype=np.int64)
+        seq_off[1:] = np.cumsum(lens, dtype=np.int64)
+        seq = np.frombuffer(b''.join(seqs) + b'\0', dtype=np.uint8)
+        id_off = np.zeros(len(ids) + 1, dtype=np.int64)
+        id_off[1:] = np.cumsum([len(i) for i in ids], dtype=np.int64)
+        id_pool = np.frombuffer(b''.join(ids) + b'\0', dtype=np.uint8)
+        v = _lib.RefView()
+        v.n_contigs = len(seqs)
+        v.contig_len, v.seq_off, v.seq = _ptr(lens), _ptr(seq_off), _ptr(seq)
+        v.n_seq_bytes = int(seq_off[-1])
+        shapes = list(shapes)
+        if not 1 <= len(shapes) <= 64 or any(len(s) > 24 for s in shapes):
+            raise ValueError('motif_report: 1 to 64 shapes of at most 24 characters')
+        P = _lib.MotifParams()
+        P.base, P.n_shapes = ord(base), len(shapes)
+        for i, s in enumerate(shapes):
+            P.shapes[i].value = s.encode('ascii')
+        P.min_sites, P.min_fraction, P.keep_all = int(min_sites), float(min_fraction), int(bool(keep_all))
+        P.contig_ids, P.contig_id_off = _ptr(id_pool), _ptr(id_off)
+        out, n_out, n_rows, status = C.c_void_p(), C.c_int64(), C.c_int64(), C.c_int32()
+        if path is not None:
+            check(lib().mc_motif_report_file(self._ctx, C.byref(v), os.fsencode(path), None if control_path is None else os.fsencode(control_path),
+                                             C.byref(P), C.byref(out), C.byref(n_out), C.byref(n_rows), C.byref(status)))
+        else:
+            text = bytes(text)
+            control_text = None if control_text is None else bytes(control_text)
+            check(lib().mc_motif_report_text(self._ctx, C.byref(v), text, len(text), control_text, 0 if control_text is None else len(control_text),
+                                             C.byref(P), C.byref(out), C.byref(n_out), C.byref(n_rows), C.byref(status)))
+        if status.value != 0:
+            return None, 0, lib().mc_last_error().decode('utf-8', 'replace')
+        return (C.string_at(out.value, n_out.value) if n_out.value else b''), int(n_rows.value), None
+
+    @_serialized
+    def motif_report_last_stats(self):
+        """Figures of the last motif_report: bytes, lines, candidates and sites, selected entries and rows, the stretch and the tables'
+        placements, the decline, milliseconds."""
+        st = _lib.MotifStats()
+        check(lib().mc_motif_report_last_stats(self._ctx, C.byref(st)))
+        return {name: getattr(st, name) for name, _ in st._fields_}
+
+    @_serialized
+    def motif_report_release(self):
+        check(lib().mc_motif_report_release(self._ctx))
+
     @_serialized
     def twosample(self, xs, ys):
         """The nine values of a compare_genomes row for every pair of samples by mc_twosample.h's device build, a wave or a

@@ -1,0 +1,280 @@
+"""Find methylated motifs de novo from called sites: which short sequence patterns around the called base are mostly methylated?
+
+    python -m mcaller_amd.find_motifs -r ref.fasta --bed SUMMARY.bed [--control CONTROL.bed] [-b A] [--shapes LIST]
+                                      [--min_sites 20] [--min_fraction 0.5] [--all] [-o OUT] [--device]
+
+The reference has no such program: its GFF output and `make_bed --control` are shaped for an external motif finder.  This module
+closes the loop: every row it prints is a motif in the syntax `--motifs` parses (refmark.parse_motifs).
+
+Inputs.  -r is read with refmark.read_fasta and upper-cased; of several records with one id the last counts.  --bed is a make_bed
+summary (plain, --vo or -p form), --control a `make_bed --control` summary.  Of each line only fields 1, 2 and 6 are used: chrom,
+0-based start (the index into the contig), strand.  A line with fewer than 6 tab-separated fields, a start int() does not take, a
+strand other than + / -, an unknown chrom or a start outside its contig is a ValueError.  A site listed twice counts once.
+
+A CANDIDATE is a (position p, strand) whose base on that strand is --base (on '-': seq[p] is its complement).  It is METHYLATED
+if --bed lists it and COVERED if --bed or --control lists it; without --control every candidate is covered.  A listed site whose
+reference base is not --base is ignored and counted (n_off_base).
+
+A SHAPE is a string of X and '.', first and last X, at most 24 wide, 2 to 8 X.  For a shape of width W, its j-th X at offset o and
+a candidate at p the window is seq[p-o : p-o+W] on '+' and revcomp(seq[p-(W-1-o) : p+o+1]) on '-'.  It counts only if it lies
+inside the contig and every letter under an X is one of ACGT; letters under '.' are free.  A counting window adds 1 to
+nGenome[shape, j, letters], 1 to nCovered if the candidate is covered and 1 to nMethylated if it is methylated.
+
+A row is SELECTED when nMethylated >= min_sites and float64(nMethylated) / float64(nCovered) >= min_fraction.  Without --all a
+selected row is dropped when another selected row (of any shape) has X positions, taken relative to the called base, that are a
+strict subset of this row's, with the same letters there: once GATC:2 is selected, GATCA:2 and GATC.....ACG:2 are dropped.
+
+One line per row: SPEC, nGenome, nCovered, nMethylated, fraction, tab-separated.  SPEC is the window with N under every '.',
+':' and the 1-based index of the called letter; fraction is repr(float) of the quotient.  Rows are ordered by nMethylated
+descending (sites explained, not fraction: a 5-of-5 noise window does not beat GATC at 423 of 423), then fraction descending, then
+shape index, j and the letters.
+
+Out of scope: merging rows into IUPAC letters (GANTC shows as its four 5-mers), iterative removal of explained sites, circular
+contigs.
+
+`find_motifs` is that definition in NumPy (the host statement; no SciPy, no GPU).  `find_motifs_device` (--device) has the GPU make
+the same bytes (Device.motif_report: csrc/motifs/mc_motifscan.hip) and runs the host statement whenever the device declines;
+`last_report` says who made the output, `last_counts` what the host statement counted."""
+import os
+import sys
+
+import numpy as np
+
+from . import refmark
+
+last_report = None         # what the last call did: dict(by='device' | 'host', reason=None | str, n_rows=int)
+last_counts = None         # the host statement's figures: dict(n_candidates, n_sites, n_control, n_off_base, n_selected)
+
+MAX_WIDTH = 24
+MAX_SHAPES = 64            # what the device takes in one call (the host statement has no limit)
+DEFAULT_SHAPES = ['XXX', 'XXXX', 'XXXXX', 'XXXXXX'] + ['X' * a + '.' * g + 'X' * b for a in (3, 4) for g in (5, 6, 7, 8) for b in (3, 4)]
+_CODE = np.full(256, 4, dtype=np.uint8)
+for _i, _c in enumerate(b'ACGT'):
+    _CODE[_c] = _i
+
+
+def parse_shapes(text):
+    """`SHAPE[,SHAPE...]` -> the list; ValueError for anything that is no shape, and for a shape given twice."""
+    shapes = [s.strip() for s in text.split(',')] if isinstance(text, str) else list(text)
+    for s in shapes:
+        if not s or set(s) - set('X.') or s[0] != 'X' or s[-1] != 'X' or len(s) > MAX_WIDTH or not 2 <= s.count('X') <= 8:
+            raise ValueError("--shapes entry %r: a shape is a string of X and '.', first and last X, at most %d wide, 2 to 8 X" % (s, MAX_WIDTH))
+    if len(set(shapes)) != len(shapes):
+        raise ValueError('--shapes %r: a shape is given twice' % (text,))
+    return shapes
+
+
+def read_reference(path):
+    """{id: upper-cased sequence}, in file order; of several records with one id the last counts."""
+    ref = {}
+    for name, seq in refmark.read_fasta(path):
+        ref[name] = seq.upper()
+    return ref
+
+
+def read_sites(path, ref):
+    """{contig: (bool[len] listed on '+', bool[len] listed on '-')} of a BED file's fields 1, 2 and 6."""
+    with open(path, 'rb') as fh:
+        lines = fh.read().decode('latin-1').split('\n')
+    if lines and lines[-1] == '':
+        lines.pop()
+    listed = {name: (np.zeros(len(seq), dtype=bool), np.zeros(len(seq), dtype=bool)) for name, seq in ref.items()}
+    for n, line in enumerate(lines, 1):
+        fields = line.split('\t')
+        if len(fields) < 6:
+            raise ValueError('%s line %d: %d tab-separated fields, at least 6 are needed' % (path, n, len(fields)))
+        start = int(fields[1])
+        if fields[5] not in ('+', '-'):
+            raise ValueError('%s line %d: strand %r is neither + nor -' % (path, n, fields[5]))
+        if fields[0] not in listed:
+            raise ValueError('%s line %d: contig %r is not in the reference' % (path, n, fields[0]))
+        if not 0 <= start < len(ref[fields[0]]):
+            raise ValueError('%s line %d: start %d lies outside contig %r of %d bases' % (path, n, start, fields[0], len(ref[fields[0]])))
+        listed[fields[0]][fields[5] == '-'][start] = True
+    return listed
+
+
+def count_tables(ref, shapes, base, meth, control):
+    """-> ([shape][j] -> (nGenome, nCovered, nMethylated), int64 arrays over the 4^k letter codes, first letter highest), counts."""
+    b = 'ACGT'.index(base)
+    tables = [[tuple(np.zeros(4 ** s.count('X'), dtype=np.int64) for _ in range(3)) for _ in range(s.count('X'))] for s in shapes]
+    counts = dict(n_candidates=0, n_sites=0, n_control=0, n_off_base=0)
+    for name, seq in ref.items():
+        fwd = _CODE[np.frombuffer(seq.encode('latin-1', 'replace'), dtype=np.uint8)]
+        L = len(fwd)
+        for rev in (False, True):
+            # the '-' strand is the '+' strand of the reverse complement: position p stands at L - 1 - p there
+            code = np.where(fwd < 4, 3 - fwd, 4).astype(np.uint8)[::-1] if rev else fwd
+            m = meth[name][rev][::-1] if rev else meth[name][rev]
+            c = None if control is None else (control[name][rev][::-1] if rev else control[name][rev])
+            cand = code == b
+            listed = m if c is None else (m | c)
+            counts['n_candidates'] += int(cand.sum())
+            counts['n_sites'] += int(m.sum())
+            counts['n_control'] += 0 if c is None else int(c.sum())
+            counts['n_off_base'] += int((listed & ~cand).sum())
+            is_meth = m & cand
+            is_cov = cand if c is None else (listed & cand)
+            for si, shape in enumerate(shapes):
+                W = len(shape)
+                xs = [i for i, ch in enumerate(shape) if ch == 'X']
+                n_win = L - W + 1
+                if n_win <= 0:
+                    continue
+                key = np.zeros(n_win, dtype=np.int64)
+                ok = np.ones(n_win, dtype=bool)
+                for x in xs:
+                    piece = code[x:x + n_win]
+                    key = key * 4 + (piece & 3)
+                    ok &= piece < 4
+                for j, o in enumerate(xs):
+                    at = ok & cand[o:o + n_win]                # windows whose j-th X is a candidate
+                    nG, nC, nM = tables[si][j]
+                    size = len(nG)
+                    nG += np.bincount(key[at], minlength=size)
+                    nC += np.bincount(key[at & is_cov[o:o + n_win]], minlength=size)
+                    nM += np.bincount(key[at & is_meth[o:o + n_win]], minlength=size)
+    return tables, counts
+
+
+def _letters(code, k):
+    return ''.join('ACGT'[(code >> (2 * (k - 1 - i))) & 3] for i in range(k))
+
+
+def report_rows(ref, shapes, base, meth, control, min_sites=20, min_fraction=0.5, keep_all=False):
+    """The rows of the definition as bytes, their number, and the counts."""
+    tables, counts = count_tables(ref, shapes, base, meth, control)
+    selected = []            # (nM, fraction, shape index, j, letters, nG, nC)
+    for si, shape in enumerate(shapes):
+        k = shape.count('X')
+        for j in range(k):
+            nG, nC, nM = tables[si][j]
+            with np.errstate(all='ignore'):
+                frac = nM.astype(np.float64) / nC.astype(np.float64)
+                pick = np.nonzero((nM >= min_sites) & (frac >= np.float64(min_fraction)))[0]
+            for code in pick.tolist():
+                selected.append((int(nM[code]), float(frac[code]), si, j, _letters(code, k), int(nG[code]), int(nC[code])))
+    counts['n_selected'] = len(selected)
+    offsets = [[i for i, ch in enumerate(s) if ch == 'X'] for s in shapes]
+
+    def placed(row):         # the row's letters by their place relative to the called base
+        xs = offsets[row[2]]
+        return frozenset((x - xs[row[3]], ch) for x, ch in zip(xs, row[4]))
+    if not keep_all:
+        sets = [placed(r) for r in selected]
+        have = set(sets)
+        kept = []
+        for r, mine in zip(selected, sets):
+            items = sorted(mine)
+            called = [it for it in items if it[0] == 0]
+            rest = [it for it in items if it[0] != 0]
+            # every strict subset that holds the called base (a row's set always does)
+            redundant = any(frozenset(called + [rest[i] for i in range(len(rest)) if sub >> i & 1]) in have for sub in range(2 ** len(rest) - 1))
+            if not redundant:
+                kept.append(r)
+        selected = kept
+    selected.sort(key=lambda r: (-r[0], -r[1], r[2], r[3], r[4]))
+    out = []
+    for nM, frac, si, j, letters, nG, nC in selected:
+        window, it = [], iter(letters)
+        for ch in shapes[si]:
+            window.append(next(it) if ch == 'X' else 'N')
+        out.append('%s:%d\t%d\t%d\t%d\t%s\n' % (''.join(window), offsets[si][j] + 1, nG, nC, nM, repr(frac)))
+    return ''.join(out).encode('ascii'), len(out), counts
+
+
+def _write(out, data):
+    """data (bytes) to `out`: None is stdout, a str a path, anything else a file object."""
+    if isinstance(out, (str, os.PathLike)):
+        with open(out, 'wb') as fo:
+            fo.write(data)
+        return
+    fo = sys.stdout if out is None else out
+    if hasattr(fo, 'buffer'):
+        fo.flush()
+        fo.buffer.write(data)
+        fo.buffer.flush()
+    else:
+        try:
+            fo.write(data.decode('ascii'))
+        except TypeError:
+            fo.write(data)
+
+
+def _checked(base, shapes, min_sites, min_fraction):
+    base = str(base).upper()
+    if base not in ('A', 'C', 'G', 'T'):
+        raise ValueError('--base %r: the called base is one of A, C, G, T' % base)
+    shapes = parse_shapes(DEFAULT_SHAPES if shapes is None else shapes)
+    min_sites = int(min_sites)
+    min_fraction = float(min_fraction)
+    if min_sites < 0 or not min_fraction >= 0.0:
+        raise ValueError('--min_sites and --min_fraction are not negative')
+    return base, shapes, min_sites, min_fraction
+
+
+def _host(reference, bed, control, base, shapes, min_sites, min_fraction, keep_all, out, reason):
+    global last_report, last_counts
+    last_report = last_counts = None
+    ref = read_reference(reference)
+    meth = read_sites(bed, ref)
+    ctl = None if control is None else read_sites(control, ref)
+    data, n_rows, counts = report_rows(ref, shapes, base, meth, ctl, min_sites, min_fraction, keep_all)
+    _write(out, data)
+    last_counts = counts
+    last_report = dict(by='host', reason=reason, n_rows=n_rows)
+    return n_rows
+
+
+def find_motifs(reference, bed, control=None, base='A', shapes=None, min_sites=20, min_fraction=0.5, keep_all=False, out=None):
+    """The host statement: the definition above in NumPy -> the number of rows."""
+    base, shapes, min_sites, min_fraction = _checked(base, shapes, min_sites, min_fraction)
+    return _host(reference, bed, control, base, shapes, min_sites, min_fraction, keep_all, out, 'the host statement was asked for')
+
+
+def find_motifs_device(reference, bed, control=None, base='A', shapes=None, min_sites=20, min_fraction=0.5, keep_all=False, out=None):
+    """The same bytes made on the GPU, or -- when the device declines -- by the host statement, which also words the errors."""
+    global last_report, last_counts
+    base, shapes, min_sites, min_fraction = _checked(base, shapes, min_sites, min_fraction)
+    last_report = last_counts = None
+    if len(shapes) > MAX_SHAPES:
+        reason = 'the device takes at most %d shapes in one call' % MAX_SHAPES
+    else:
+        from .device import get_device
+        ref = read_reference(reference)
+        blob, n_rows, reason = get_device().motif_report(ref, path=bed, control_path=control, base=base, shapes=shapes, min_sites=min_sites,
+                                                         min_fraction=min_fraction, keep_all=keep_all)
+        if blob is not None:
+            _write(out, blob)
+            last_report = dict(by='device', reason=None, n_rows=n_rows)
+            return n_rows
+    return _host(reference, bed, control, base, shapes, min_sites, min_fraction, keep_all, out, reason)
+
+
+def main(argv=None):
+    from argparse import ArgumentParser
+    parser = ArgumentParser(description='Report the sequence patterns around the called base whose occurrences are mostly methylated')
+    parser.add_argument('-r', '--reference', type=str, required=True, help='fasta file with the reference the sites were called on')
+    parser.add_argument('--bed', type=str, required=True, help='summary bed file from make_bed (plain, --vo or -p): the methylated sites')
+    parser.add_argument('--control', type=str, required=False, help='summary from make_bed --control: covered sites that were not called')
+    parser.add_argument('-b', '--base', type=str, required=False, default='A', help='the called base (default: A)')
+    parser.add_argument('--shapes', type=str, required=False,
+                        help="comma list of shapes of X and '.' (default: XXX to XXXXXX and the bipartite X{3,4}.{5-8}X{3,4})")
+    parser.add_argument('--min_sites', type=int, required=False, default=20, help='methylated occurrences a row needs (default: 20)')
+    parser.add_argument('--min_fraction', type=float, required=False, default=0.5,
+                        help='methylated / covered occurrences a row needs (default: 0.5)')
+    parser.add_argument('--all', action='store_true', required=False, help='keep rows that a shorter selected row explains')
+    parser.add_argument('-o', '--output', type=str, required=False, help='write the rows to this file (default: standard output)')
+    parser.add_argument('--device', action='store_true', required=False, help='count on the GPU (the host statement runs when it declines)')
+    args = parser.parse_args(argv)
+
+    assert os.path.isfile(args.reference), 'file not found at ' + args.reference
+    assert os.path.isfile(args.bed), 'file not found at ' + args.bed
+    assert args.control is None or os.path.isfile(args.control), 'file not found at ' + args.control
+
+    run = find_motifs_device if args.device else find_motifs
+    return run(args.reference, args.bed, args.control, args.base, args.shapes, args.min_sites, args.min_fraction, args.all, args.output)
+
+
+if __name__ == '__main__':
+    main()
