@@ -447,6 +447,18 @@ int mc_forest_fit(mc_ctx *ctx, const mc_forest_params *prm, const double *X, con
                   const uint64_t *seeds, const double *G, int64_t n_G, int64_t node_cap, int64_t *tree_node_off,
                   int32_t *left, int32_t *right, int32_t *feature, double *threshold, double *value, double *impurity,
                   int32_t *n_node_samples, double *weighted_n_node_samples, int64_t *val_correct);
+/* How the last mc_forest_fit call on the context that reached the device ran.  The trees are grown `batch` at a time, as many as
+ * fit MCALLER_FOREST_MEM_MB (default 4096; read once per process) of per-tree work arrays: batch = max(1, min(n_trees_total,
+ * MB * 2^20 / per_tree_bytes)), n_batches launches of k5_forest_fit, the last one with the remainder.  All zero before the first
+ * call; a call refused with -12 leaves the figures of the call before. */
+typedef struct mc_forest_fit_stats {
+    int64_t n_batches;             /* launches of k5_forest_fit                              */
+    int64_t batch;                 /* trees (workgroups) of a full batch                     */
+    int64_t per_tree_bytes;        /* work memory of one tree                                */
+    int64_t n_trees_total;         /* n_jobs * n_trees                                       */
+    int64_t n_nodes;               /* nodes written over all trees (0 if the call failed)    */
+} mc_forest_fit_stats;
+int mc_forest_fit_last_stats(mc_ctx *ctx, mc_forest_fit_stats *out);
 
 /* ===== the RBF support-vector fit behind --train -c SVM (train_model.py:51-53,:62-65,:92-101): scikit-learn's SVC(kernel='rbf') =====
  * solved as libsvm's Solver does without shrinking (tests/svm_fit_oracle.py restates it): n_jobs independent solves, a workgroup each

@@ -85,6 +85,12 @@ class ForestParams(C.Structure):
                 ('min_samples_split', C.c_int32), ('min_samples_leaf', C.c_int32), ('bootstrap', C.c_int32)]
 
 
+class ForestFitStats(C.Structure):
+    """mc_forest_fit_stats (include/mcaller_hip.h)."""
+    _fields_ = [('n_batches', C.c_int64), ('batch', C.c_int64), ('per_tree_bytes', C.c_int64), ('n_trees_total', C.c_int64),
+                ('n_nodes', C.c_int64)]
+
+
 class SvmParams(C.Structure):
     _fields_ = [('C', C.c_double), ('tol', C.c_double), ('max_iter', C.c_int64)]
 
@@ -331,6 +337,7 @@ def lib():
         L.mc_mlp_fit.argtypes = [C.c_void_p, C.POINTER(FitParams), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 13
         L.mc_forest_fit.argtypes = [C.c_void_p, C.POINTER(ForestParams), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 6 + \
             [C.c_int64, C.c_int64] + [C.c_void_p] * 10
+        L.mc_forest_fit_last_stats.argtypes = [C.c_void_p, C.POINTER(ForestFitStats)]
         L.mc_svm_fit.argtypes = [C.c_void_p, C.POINTER(SvmParams), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32] + \
             [C.c_void_p] * 11
         L.mc_svm_sigmoid_train.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double)]

@@ -7,6 +7,7 @@
 // for the other translation units of the library (mc_train.hip)
 int mc_internal_device(const mc_ctx *c) { return c->device; }
 hipStream_t mc_internal_stream(const mc_ctx *c) { return c->stream; }
+mc_forest_fit_stats *mc_internal_forest_stats(mc_ctx *c) { return &c->forest_stats; }
 
 // Multi-GPU hosts: one process per GPU, and what a process copies out lands in ITS pinned memory.  Bound to the cores of the
 // NUMA node the GPU hangs off, the process allocates there (first touch) and the DMA writes do not cross the socket link.

@@ -328,6 +328,8 @@ struct mc_ctx {
     Pinned motif_out;
     size_t motif_out_cap = 0;
     mc_motif_stats motif_stats = {};
+    // the figures of the last random-forest fit (mc_forest_fit.hip, through mc_internal_forest_stats)
+    mc_forest_fit_stats forest_stats = {};
 };
 
 // ---- what crosses the units ----

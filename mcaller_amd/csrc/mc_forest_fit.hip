@@ -15,12 +15,15 @@
 //     so the children's segments are sorted again without a sort;
 //   * nodes are written in level order with child links; the host renumbers them into scikit-learn's depth-first pre-order.
 // A second kernel (k5_forest_val) scores each job's validation rows with its trees in tree order, as k3_forest adds them.
-// Work arrays are in global memory, per workgroup; trees are grown in batches that fit MCALLER_FOREST_MEM_MB (default 4096).
+// Work arrays are in global memory, per workgroup; trees are grown in batches that fit MCALLER_FOREST_MEM_MB (default 4096);
+// mc_forest_fit_last_stats tells how a call was cut.
 // The entry points' allocations, transfers and job checks, FitJob, splitmix64 and wave_sum: mc_fit.h.
 #include <cstdlib>
 #include <numeric>
 
 #include "mc_fit.h"
+
+mc_forest_fit_stats *mc_internal_forest_stats(mc_ctx *c);      // mc_context.hip: the context's figures of its last forest fit
 
 namespace {
 
@@ -471,6 +474,8 @@ extern "C" int mc_forest_fit(mc_ctx *c, const mc_forest_params *P, const double 
                             (size_t)cap_nodes * sizeof(FNode) + 64;
     static const int64_t budget_mb = getenv("MCALLER_FOREST_MEM_MB") ? atoll(getenv("MCALLER_FOREST_MEM_MB")) : 4096;
     const int64_t batch = std::max<int64_t>(1, std::min<int64_t>(total, (std::max<int64_t>(budget_mb, 1) << 20) / (int64_t)per_tree));
+    mc_forest_fit_stats &stats = *mc_internal_forest_stats(c);
+    stats = mc_forest_fit_stats{(total + batch - 1) / batch, batch, (int64_t)per_tree, total, 0};
 
     const int64_t n_tr = train_off[n_jobs], n_va = val_off[n_jobs];
     Pool pool("mc_forest_fit");
@@ -589,5 +594,12 @@ extern "C" int mc_forest_fit(mc_ctx *c, const mc_forest_params *P, const double 
         x.sync();
     }
     if (!x.ok()) return x.fail();
+    stats.n_nodes = out;
+    return 0;
+}
+
+extern "C" int mc_forest_fit_last_stats(mc_ctx *c, mc_forest_fit_stats *out) {
+    if (!c || !out) { mc_set_error("mc_forest_fit_last_stats: bad arguments"); return -12; }
+    *out = *mc_internal_forest_stats(c);
     return 0;
 }

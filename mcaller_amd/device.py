@@ -561,6 +561,14 @@ class Device(object):
         return out
 
     @_serialized
+    def forest_fit_last_stats(self):
+        """How the last forest_fit ran (mc_forest_fit_stats): n_batches launches of `batch` trees each (what fits
+        MCALLER_FOREST_MEM_MB at per_tree_bytes a tree), n_trees_total, n_nodes."""
+        st = _lib.ForestFitStats()
+        check(lib().mc_forest_fit_last_stats(self._ctx, C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in st._fields_}
+
+    @_serialized
     def svm_fit(self, X, y, jobs, gammas, C=1.0, tol=1e-3, max_iter=0):
         """Solve one RBF SVC dual per job on the GPU (mc_svm_fit: every job a workgroup of k6_svm_fit, libsvm's Solver).  jobs:
         [(train_rows, validation_rows)] index arrays into X / y (y in {0, 1}); a job's training rows come in libsvm's solve order,
