@@ -17,6 +17,13 @@
  * local; MC_E_NO_FREE_SLOT is the one code a caller acts on: hand out the oldest pass and try again).  Plain pointers and sizes only; no exceptions or callbacks cross the ABI.  Host buffers are
  * caller-allocated and never retained after the call returns.  One mc_ctx per GPU; calls on a ctx
  * are serialised by the caller (one process per GPU).
+ *
+ * This file is also read as text by the Python binding (mcaller_amd/_abi.py), which takes every struct, integer constant and
+ * prototype from it and stops on what it does not understand.  So it stays in a small subset of C: plain declarations, one
+ * statement each; char, int, float, double and the fixed-width <stdint.h> types; `typedef struct x { ... } x;` whose fields are
+ * such scalars, pointers, earlier structs of this file and arrays of them; array sizes and `#define MC_...` values that are
+ * integer expressions over literals and earlier defines; opaque handles as `typedef struct x x;`.  No unions, bit fields,
+ * enums, function pointers, function-like macros or other typedefs.
  */
 #ifndef MCALLER_HIP_H
 #define MCALLER_HIP_H

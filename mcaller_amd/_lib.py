@@ -8,15 +8,19 @@ import os
 
 import numpy as np
 
+from . import _abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('MCALLER_LIB') or os.path.join(_HERE, 'libmcaller_hip.so')      # (MCALLER_LIB: a variant build, tools/variants.sh)
 
-MC_MAX_K = 8
-F_KMER_EQ, F_MODEL_N, F_SEG_START, F_NAME_START = 1, 2, 4, 8
-I_EMPTY_MASK, I_REV, I_TOO_MANY, I_MULTI, I_EDGE, I_NEXT_SHIFT = 0xFF, 0x100, 0x200, 0x400, 0x800, 16
+ABI = _abi.load()      # include/mcaller_hip.h: the one statement of the structs, the constants and the prototypes
+_K, _S = ABI.constants, ABI.structs
 
-
-E_NO_FREE_SLOT = -16      # include/mcaller_hip.h: MC_E_NO_FREE_SLOT
+MC_MAX_K = _K['MC_MAX_K']
+F_KMER_EQ, F_MODEL_N, F_SEG_START, F_NAME_START = (_K['MC_F_' + n] for n in ('KMER_EQ', 'MODEL_N', 'SEG_START', 'NAME_START'))
+I_EMPTY_MASK, I_REV, I_TOO_MANY, I_MULTI, I_EDGE, I_NEXT_SHIFT = (
+    _K['MC_I_' + n] for n in ('EMPTY_MASK', 'REV', 'TOO_MANY', 'MULTI', 'EDGE', 'NEXT_SHIFT'))
+E_NO_FREE_SLOT = _K['MC_E_NO_FREE_SLOT']
 
 
 class McError(RuntimeError):
@@ -24,385 +28,64 @@ class McError(RuntimeError):
     code = None
 
 
-class TableView(C.Structure):
-    _fields_ = [('n_rows', C.c_int64),
-                ('pos', C.c_void_p), ('event_model_e4', C.c_void_p),
-                ('event_idx', C.c_void_p), ('flags', C.c_void_p),
-                ('n_seg', C.c_int32),
-                ('seg_row_begin', C.c_void_p), ('seg_read', C.c_void_p), ('seg_contig', C.c_void_p),
-                ('n_reads', C.c_int32)]
+TableView = _S['mc_table_view']
+RefView = _S['mc_ref_view']
+IupacMotif = _S['mc_iupac_motif']
+IupacSpec = _S['mc_iupac_spec']
+DevParseResult = _S['mc_devparse_result']
+CallsView = _S['mc_calls_view']
+FormatArgs = _S['mc_format_args']
+FitParams = _S['mc_fit_params']
+ForestParams = _S['mc_forest_params']
+ForestFitStats = _S['mc_forest_fit_stats']
+SvmParams = _S['mc_svm_params']
+LrParams = _S['mc_lr_params']
+NbParams = _S['mc_nb_params']
+BedParams = _S['mc_bed_params']
+BedStats = _S['mc_bed_stats']
+TrainRowsView = _S['mc_train_rows_view']
+TrainRowsView.MAX_LABELS = _K['MC_TRAINROWS_MAX_LABELS']
+TrainRowsStats = _S['mc_train_rows_stats']
+RowsMergeStats = _S['mc_rows_merge_stats']
+FastqQualityView = _S['mc_fastq_quality_view']
+FastqQualityStats = _S['mc_fastq_quality_stats']
+CmpStats = _S['mc_cmp_stats']
+MotifParams = _S['mc_motif_params']
+MotifStats = _S['mc_motif_stats']
+Params = _S['mc_params']
 
-
-class RefView(C.Structure):
-    _fields_ = [('n_contigs', C.c_int32),
-                ('contig_len', C.c_void_p), ('seq_off', C.c_void_p), ('seq', C.c_void_p),
-                ('word_off', C.c_void_p), ('mbits_fwd', C.c_void_p), ('mbits_rev', C.c_void_p),
-                ('n_seq_bytes', C.c_int64), ('n_words', C.c_int64)]
-
-
-class IupacMotif(C.Structure):
-    """mc_iupac_motif (include/mcaller_hip.h)."""
-    _fields_ = [('m', C.c_int32), ('called', C.c_uint32), ('set', C.c_uint8 * 32)]
-
-
-class IupacSpec(C.Structure):
-    """mc_iupac_spec (include/mcaller_hip.h)."""
-    _fields_ = [('n_motifs', C.c_int32), ('pad', C.c_int32), ('fwd', IupacMotif * 8), ('rev', IupacMotif * 8)]
-
-
-class DevParseResult(C.Structure):
-    """mc_devparse_result (include/mcaller_hip.h)."""
-    _fields_ = [('status', C.c_int32), ('n_lines', C.c_int64), ('n_rows', C.c_int64), ('n_seg', C.c_int32), ('n_unknown', C.c_int32),
-                ('seg_row_begin', C.c_void_p), ('seg_contig', C.c_void_p), ('seg_name_off', C.c_void_p), ('seg_name_len', C.c_void_p),
-                ('seg_name_start', C.c_void_p), ('unknown_off', C.c_void_p), ('unknown_len', C.c_void_p), ('flags', C.c_void_p)]
-
-
-class CallsView(C.Structure):
-    _fields_ = [('capacity', C.c_int64),
-                ('feats', C.c_void_p), ('site_pos', C.c_void_p), ('site_seg', C.c_void_p),
-                ('close_row', C.c_void_p), ('info', C.c_void_p), ('prob', C.c_void_p),
-                ('call_row', C.c_void_p), ('n_call_rows', C.c_int64), ('close_row32', C.c_void_p), ('compacted', C.c_int32),
-                ('feats_lo32', C.c_void_p), ('feats_hi32', C.c_void_p), ('feats_wide', C.c_void_p), ('n_wide', C.c_int64)]
-
-
-class FormatArgs(C.Structure):
-    _fields_ = [('rec', C.POINTER(CallsView)), ('n_records', C.c_int64), ('k', C.c_int32),
-                ('table', C.POINTER(TableView)), ('ref', C.POINTER(RefView)),
-                ('contig_names', C.POINTER(C.c_char_p)), ('read_names', C.POINTER(C.c_char_p)),
-                ('read_qual_txt', C.POINTER(C.c_char_p)), ('tail_chrom', C.c_char_p),
-                ('label_meth', C.c_char_p), ('label_unmeth', C.c_char_p), ('submodel_of_char', C.c_void_p)]
-
-
-class FitParams(C.Structure):
-    _fields_ = [('n_in', C.c_int32), ('n_hidden', C.c_int32), ('batch_size', C.c_int32), ('max_iter', C.c_int32),
-                ('n_iter_no_change', C.c_int32), ('shuffle', C.c_int32),
-                ('alpha', C.c_double), ('lr_init', C.c_double), ('beta1', C.c_double), ('beta2', C.c_double),
-                ('epsilon', C.c_double), ('tol', C.c_double), ('seed', C.c_uint64)]
-
-
-class ForestParams(C.Structure):
-    _fields_ = [('n_in', C.c_int32), ('n_trees', C.c_int32), ('max_depth', C.c_int32), ('max_features', C.c_int32),
-                ('min_samples_split', C.c_int32), ('min_samples_leaf', C.c_int32), ('bootstrap', C.c_int32)]
-
-
-class ForestFitStats(C.Structure):
-    """mc_forest_fit_stats (include/mcaller_hip.h)."""
-    _fields_ = [('n_batches', C.c_int64), ('batch', C.c_int64), ('per_tree_bytes', C.c_int64), ('n_trees_total', C.c_int64),
-                ('n_nodes', C.c_int64)]
-
-
-class SvmParams(C.Structure):
-    _fields_ = [('C', C.c_double), ('tol', C.c_double), ('max_iter', C.c_int64)]
-
-
-class LrParams(C.Structure):
-    _fields_ = [('C', C.c_double), ('tol', C.c_double), ('max_iter', C.c_int32), ('pad', C.c_int32)]
-
-
-class NbParams(C.Structure):
-    _fields_ = [('var_smoothing', C.c_double)]
-
-
-class BedParams(C.Structure):
-    """mc_bed_params (include/mcaller_hip.h)."""
-    _fields_ = [('min_depth', C.c_int64), ('mod_threshold', C.c_double), ('control', C.c_int32), ('with_probs', C.c_int32),
-                ('gff', C.c_int32), ('pad', C.c_int32)]
-
-
-class BedStats(C.Structure):
-    """mc_bed_stats (include/mcaller_hip.h)."""
-    _fields_ = [('n_bytes', C.c_int64), ('n_lines', C.c_int64), ('n_counted', C.c_int64), ('n_entries', C.c_int64),
-                ('n_sites', C.c_int64), ('n_out_bytes', C.c_int64), ('decline_line', C.c_int64), ('decline_reason', C.c_int32),
-                ('longest_probe', C.c_int32), ('table_slots', C.c_int64), ('kernel_bytes', C.c_int64), ('ms_read', C.c_double),
-                ('ms_h2d', C.c_double), ('ms_kernels', C.c_double), ('ms_d2h', C.c_double), ('ms_total', C.c_double)]
-
-
-class TrainRowsView(C.Structure):
-    """mc_train_rows_view (include/mcaller_hip.h)."""
-    MAX_LABELS = 16
-    _fields_ = [('n_labels', C.c_int32), ('n_features', C.c_int32), ('ctx_width', C.c_int32), ('pad', C.c_int32),
-                ('n_rows_total', C.c_int64), ('X', C.c_void_p), ('contexts', C.c_void_p), ('label_bytes', C.c_void_p),
-                ('label_off', C.c_int32 * 17), ('pad2', C.c_int32), ('n_rows', C.c_int64 * 16), ('first_line', C.c_int64 * 16)]
-
-
-class TrainRowsStats(C.Structure):
-    """mc_train_rows_stats (include/mcaller_hip.h)."""
-    _fields_ = [('n_bytes', C.c_int64), ('n_lines', C.c_int64), ('n_kept', C.c_int64), ('decline_line', C.c_int64),
-                ('decline_reason', C.c_int32), ('n_labels', C.c_int32), ('n_features', C.c_int32), ('in_place_blocks', C.c_int32),
-                ('ms_read', C.c_double), ('ms_h2d', C.c_double), ('ms_kernels', C.c_double), ('ms_d2h', C.c_double),
-                ('ms_total', C.c_double)]
-
-
-class RowsMergeStats(C.Structure):
-    """mc_rows_merge_stats (include/mcaller_hip.h)."""
-    _fields_ = [('n_bytes', C.c_int64), ('n_lines', C.c_int64), ('n_lines_out', C.c_int64), ('n_out_bytes', C.c_int64),
-                ('n_tied_after_key', C.c_int64), ('n_rounds', C.c_int32), ('n_passes', C.c_int32), ('largest_compared', C.c_int32),
-                ('decline_reason', C.c_int32), ('decline_line', C.c_int64), ('decline_file', C.c_int32), ('pad', C.c_int32),
-                ('kernel_bytes', C.c_int64), ('ms_read', C.c_double), ('ms_h2d', C.c_double), ('ms_kernels', C.c_double),
-                ('ms_d2h', C.c_double), ('ms_write', C.c_double), ('ms_total', C.c_double)]
-
-
-class FastqQualityView(C.Structure):
-    """mc_fastq_quality_view (include/mcaller_hip.h)."""
-    _fields_ = [('key_pool', C.c_void_p), ('key_off', C.c_void_p), ('mean', C.c_void_p), ('n_records', C.c_int64)]
-
-
-class FastqQualityStats(C.Structure):
-    """mc_fastq_quality_stats (include/mcaller_hip.h)."""
-    _fields_ = [('n_bytes', C.c_int64), ('n_lines', C.c_int64), ('n_records', C.c_int64), ('n_pieces', C.c_int64),
-                ('decline_line', C.c_int64), ('decline_reason', C.c_int32), ('piece_bytes', C.c_int32), ('ms_read', C.c_double),
-                ('ms_h2d', C.c_double), ('ms_kernels', C.c_double), ('ms_d2h', C.c_double), ('ms_total', C.c_double)]
-
-
-class CmpStats(C.Structure):
-    """mc_cmp_stats (include/mcaller_hip.h)."""
-    _fields_ = [('n_bytes1', C.c_int64), ('n_bytes2', C.c_int64), ('n_lines1', C.c_int64), ('n_lines2', C.c_int64),
-                ('n_keys2', C.c_int64), ('n_sites', C.c_int64), ('n_values', C.c_int64), ('n_rank_small', C.c_int64),
-                ('n_rank_large', C.c_int64), ('n_out_bytes', C.c_int64), ('table_slots', C.c_int64), ('decline_line', C.c_int64),
-                ('decline_reason', C.c_int32), ('decline_file', C.c_int32), ('longest_probe', C.c_int32),
-                ('deepest_site', C.c_int32), ('ms_read', C.c_double), ('ms_h2d', C.c_double), ('ms_kernels', C.c_double),
-                ('ms_d2h', C.c_double), ('ms_total', C.c_double)]
-
-
-class MotifParams(C.Structure):
-    """mc_motif_params (include/mcaller_hip.h)."""
-    _fields_ = [('base', C.c_int32), ('n_shapes', C.c_int32), ('shapes', (C.c_char * 32) * 64), ('min_sites', C.c_int64),
-                ('min_fraction', C.c_double), ('keep_all', C.c_int32), ('pad', C.c_int32), ('contig_ids', C.c_void_p),
-                ('contig_id_off', C.c_void_p)]
-
-
-class MotifStats(C.Structure):
-    """mc_motif_stats (include/mcaller_hip.h)."""
-    _fields_ = [('n_bytes1', C.c_int64), ('n_bytes2', C.c_int64), ('n_lines1', C.c_int64), ('n_lines2', C.c_int64),
-                ('n_candidates', C.c_int64), ('n_sites', C.c_int64), ('n_control', C.c_int64), ('n_off_base', C.c_int64),
-                ('n_selected', C.c_int64), ('n_rows', C.c_int64), ('stretch', C.c_int64), ('n_stretches', C.c_int64),
-                ('n_entries', C.c_int64), ('table_slots', C.c_int64), ('n_out_bytes', C.c_int64), ('decline_line', C.c_int64),
-                ('decline_reason', C.c_int32), ('decline_file', C.c_int32), ('n_tables_lds', C.c_int32),
-                ('n_tables_global', C.c_int32), ('ms_read', C.c_double), ('ms_h2d', C.c_double), ('ms_kernels', C.c_double),
-                ('ms_d2h', C.c_double), ('ms_total', C.c_double)]
-
-
-MOTIF_DECLINE = {'high_byte': 1, 'control': 2, 'long_line': 3, 'fields': 4, 'field': 5, 'chrom': 6, 'range': 7, 'table': 8,
-                 'memory': 9, 'reference': 10, 'print': 11, 'rows': 12}                          # MC_MOTIF_DECLINE_*
-CMP_DECLINE = {'high_byte': 1, 'control': 2, 'fields': 3, 'empty': 4, 'long_line': 5, 'rows': 6, 'memory': 7, 'table': 8,
-               'duplicate': 9, 'number': 10, 'depth': 11, 'nan': 12, 'all_equal': 13, 'far_tail': 14, 'print': 15,
-               'tie': 16}                                                                        # MC_CMP_DECLINE_*
+MOTIF_DECLINE = ABI.prefixed('MC_MOTIF_DECLINE_')
+CMP_DECLINE = ABI.prefixed('MC_CMP_DECLINE_')
+FASTQ_DECLINE = ABI.prefixed('MC_FASTQ_DECLINE_')
+MERGE_DECLINE = ABI.prefixed('MC_MERGE_DECLINE_')
 TW_STATUS = {'bad_n': 1, 'zero_var': 2, 'far_tail': 4, 'no_convergence': 8, 'all_equal': 16, 'tie': 32, 'unprintable': 64,
              'deep': 128}                                                                        # TW_* (csrc/mc_twosample.h)
 TW_NAMES = ('U', 'z_mwu', 'z_rs', 't', 'D', 'nlp_mwu', 'nlp_rs', 'nlp_t', 'nlp_ks')
-FASTQ_DECLINE = {'high_byte': 1, 'control': 2, 'lone_cr': 3, 'title': 4, 'plus': 5, 'length': 6, 'empty_id': 7, 'rows': 8,
-                 'memory': 9, 'gz': 10}                                                          # MC_FASTQ_DECLINE_*
-MERGE_DECLINE = {'cr': 1, 'no_newline': 2, 'key': 3, 'long_line': 4, 'rows': 5, 'memory': 6}     # MC_MERGE_DECLINE_*
-
-
-class Params(C.Structure):
-    _fields_ = [('k', C.c_int32), ('skip_thresh', C.c_int32), ('qual_thresh', C.c_double),
-                ('tail_contig', C.c_int32), ('score', C.c_int32),
-                ('entry_read', C.c_int32), ('entry_first_idx', C.c_int32)]
-
 
 _lib = None
 
 
 def lib():
-    """Load libmcaller_hip.so (once).  Raises ImportError if it has not been built."""
+    """Load libmcaller_hip.so (once), every function typed as the header declares it.  Raises ImportError if it has not been built."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise ImportError('%s is missing: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                               '(hipcc --offload-arch=gfx950); there is no CPU fallback' % LIB_PATH)
         L = C.CDLL(LIB_PATH)
-        L.mc_last_error.restype = C.c_char_p
-        L.mc_version.restype = C.c_char_p
-        L.mc_parse_eventalign.argtypes = [C.c_char_p, C.c_int64, C.c_int64, C.POINTER(C.c_char_p), C.c_int32,
-                                          C.c_int32, C.POINTER(C.c_void_p)]
-        L.mc_parse_eventalign_range.argtypes = L.mc_parse_eventalign.argtypes
-        L.mc_eventalign_read_cuts.argtypes = [C.c_char_p, C.c_int32, C.c_void_p]
-        L.mc_eventalign_read_cuts_range.argtypes = [C.c_char_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]
-        L.mc_eventalign_read_cuts_at.argtypes = [C.c_char_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]
-        L.mc_eventalign_consumed_range.argtypes = [C.c_char_p, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        L.mc_fastq_read_quality.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_void_p)]
-        L.mc_fastq_view.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
-        L.mc_fastq_view.restype = C.c_int64
-        L.mc_fastq_free.argtypes = [C.c_void_p]
-        L.mc_fastq_records_host.argtypes = [C.c_char_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]
-        L.mc_fastq_records_host_decline.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
-        L.mc_fastq_quality_text.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.POINTER(FastqQualityView), C.POINTER(C.c_int32)]
-        L.mc_fastq_quality_file.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(FastqQualityView), C.POINTER(C.c_int32)]
-        L.mc_fastq_quality_last_stats.argtypes = [C.c_void_p, C.POINTER(FastqQualityStats)]
-        L.mc_fastq_quality_release.argtypes = [C.c_void_p]
-        L.mc_bed_compare_text.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, C.POINTER(C.c_void_p),
-                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
-        L.mc_bed_compare_file.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
-                                          C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
-        L.mc_bed_compare_last_stats.argtypes = [C.c_void_p, C.POINTER(CmpStats)]
-        L.mc_bed_compare_release.argtypes = [C.c_void_p]
-        L.mc_motif_report_text.argtypes = [C.c_void_p, C.POINTER(RefView), C.c_char_p, C.c_int64, C.c_char_p, C.c_int64,
-                                           C.POINTER(MotifParams), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
-                                           C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
-        L.mc_motif_report_file.argtypes = [C.c_void_p, C.POINTER(RefView), C.c_char_p, C.c_char_p, C.POINTER(MotifParams),
-                                           C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
-        L.mc_motif_report_last_stats.argtypes = [C.c_void_p, C.POINTER(MotifStats)]
-        L.mc_motif_report_release.argtypes = [C.c_void_p]
-        L.mc_twosample.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
-        L.mc_twosample_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                                          C.c_void_p, C.c_void_p]
-        L.mc_twosample_log10_2sf.argtypes = [C.c_double]
-        L.mc_twosample_log10_2sf.restype = C.c_double
-        L.mc_twosample_log10_kolmogorov.argtypes = [C.c_double]
-        L.mc_twosample_log10_kolmogorov.restype = C.c_double
-        L.mc_parsed_view.argtypes = [C.c_void_p, C.POINTER(TableView)]
-        L.mc_parsed_read_name.argtypes = [C.c_void_p, C.c_int32]
-        L.mc_parsed_read_name.restype = C.c_char_p
-        L.mc_parsed_n_unknown.argtypes = [C.c_void_p]
-        L.mc_parsed_n_unknown.restype = C.c_int64
-        L.mc_parsed_unknown_name.argtypes = [C.c_void_p, C.c_int64]
-        L.mc_parsed_unknown_name.restype = C.c_char_p
-        L.mc_parsed_free.argtypes = [C.c_void_p]
-        L.mc_parsed_free.restype = None
-        L.mc_parsed_n_pieces.argtypes = [C.c_void_p]
-        L.mc_synth_write_tsv.argtypes = [C.c_char_p, C.POINTER(TableView), C.c_char_p, C.c_int64, C.c_char_p,
-                                         C.POINTER(C.c_char_p), C.c_int32, C.POINTER(C.c_int64)]
-        L.mc_host_alloc.argtypes = [C.c_int64]
-        L.mc_host_alloc.restype = C.c_void_p
-        L.mc_host_free.argtypes = [C.c_void_p]
-        L.mc_host_free.restype = None
-        L.mc_host_is_pinned.argtypes = [C.c_void_p]
-        L.mc_host_pool_config.argtypes = [C.c_int32, C.c_int64]
-        L.mc_ctx_reserve_tables.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32]
-        L.mc_mark_motifs.argtypes = [C.c_char_p, C.c_int64, C.c_char_p, C.c_char_p, C.c_int32, C.c_char_p, C.c_char_p, C.c_int32,
-                                     C.c_void_p, C.c_void_p, C.c_void_p]
-        L.mc_ctx_set_reference_motif.argtypes = [C.c_void_p, C.POINTER(RefView), C.c_char_p, C.c_char_p, C.c_int32, C.c_char_p, C.c_char_p,
-                                                 C.c_int32]
-        L.mc_iupac_spec_add.argtypes = [C.POINTER(IupacSpec), C.c_char_p, C.c_int32, C.c_uint32]
-        L.mc_mark_iupac.argtypes = [C.c_char_p, C.c_int64, C.POINTER(IupacSpec), C.c_void_p, C.c_void_p, C.c_void_p]
-        L.mc_ctx_set_reference_iupac.argtypes = [C.c_void_p, C.POINTER(RefView), C.POINTER(IupacSpec)]
-        L.mc_ctx_fetch_reference.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                             C.c_void_p, C.POINTER(C.c_int64)]
-        L.mc_read_file_range.argtypes = [C.c_char_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32]
-        L.mc_map_file_range.argtypes = [C.c_char_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
-        L.mc_unmap_file_range.argtypes = [C.c_void_p]
-        L.mc_unmap_file_range.restype = None
-        L.mc_ctx_parse_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_char_p), C.c_int32, C.c_int64,
-                                         C.POINTER(C.c_int32)]
-        L.mc_ctx_parse_end.argtypes = [C.c_void_p, C.c_int32, C.POINTER(DevParseResult)]
-        L.mc_ctx_parse_finish.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
-        L.mc_ctx_parse_abandon.argtypes = [C.c_void_p, C.c_int32]
-        L.mc_ctx_fetch_columns.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.mc_ctx_upload_table_async.argtypes = [C.c_void_p, C.POINTER(TableView), C.c_void_p, C.POINTER(C.c_int32)]
-        L.mc_ctx_wait_upload.argtypes = [C.c_void_p, C.c_int32]
-        L.mc_ctx_current_slot.argtypes = [C.c_void_p]
-        L.mc_ctx_select_table.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
-        L.mc_ctx_upload_times_ms.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
-        L.mc_last_pass_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        L.mc_ctx_parse_times_ms.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
-        L.mc_ctx_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-        L.mc_ctx_destroy.argtypes = [C.c_void_p]
-        L.mc_ctx_destroy.restype = None
-        L.mc_ctx_set_reference.argtypes = [C.c_void_p, C.POINTER(RefView)]
-        L.mc_ctx_upload_table.argtypes = [C.c_void_p, C.POINTER(TableView)]
-        L.mc_ctx_set_read_quality.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
-        L.mc_ctx_set_mlp.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                     C.c_void_p, C.c_void_p, C.c_void_p]
-        L.mc_extract_features.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(C.c_int64)]
-        L.mc_fetch_records.argtypes = [C.c_void_p, C.POINTER(CallsView)]
-        L.mc_fetch_records_view.argtypes = [C.c_void_p, C.POINTER(CallsView)]
-        L.mc_extract_features_async.argtypes = [C.c_void_p, C.POINTER(Params)]
-        L.mc_wait_records.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(CallsView)]
-        L.mc_wait_records_begin.argtypes = [C.c_void_p]
-        L.mc_last_times_ms.argtypes = [C.c_void_p, C.c_void_p]
-        L.mc_ctx_sync.argtypes = [C.c_void_p]
-        L.mc_ctx_set_pass_timing.argtypes = [C.c_void_p, C.c_int]
-        L.mc_last_pass_timed.argtypes = [C.c_void_p]
-        L.mc_bind_to_device_numa_node.argtypes = [C.c_int]
-        L.mc_mlp_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-        L.mc_forest_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-        L.mc_ctx_set_forest.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 8
-        L.mc_simple_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-        L.mc_ctx_set_simple_classifier.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
-        L.mc_svm_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-        L.mc_ctx_set_svm.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5
-        L.mc_site_count.argtypes = [C.c_void_p]
-        L.mc_site_count.restype = C.c_int64
-        L.mc_site_counts.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        L.mc_site_counts_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
-        L.mc_site_counts_reset.argtypes = [C.c_void_p]
-        L.mc_site_counts_accumulate.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        L.mc_comm_unique_id.argtypes = [C.c_void_p]
-        L.mc_comm_available.argtypes = []
-        L.mc_site_counts_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.mc_comm_init.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
-        L.mc_comm_destroy.argtypes = [C.c_void_p]
-        L.mc_site_allreduce.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
-        L.mc_mlp_fit.argtypes = [C.c_void_p, C.POINTER(FitParams), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 13
-        L.mc_forest_fit.argtypes = [C.c_void_p, C.POINTER(ForestParams), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 6 + \
-            [C.c_int64, C.c_int64] + [C.c_void_p] * 10
-        L.mc_forest_fit_last_stats.argtypes = [C.c_void_p, C.POINTER(ForestFitStats)]
-        L.mc_svm_fit.argtypes = [C.c_void_p, C.POINTER(SvmParams), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32] + \
-            [C.c_void_p] * 11
-        L.mc_svm_sigmoid_train.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-        L.mc_lr_fit.argtypes = [C.c_void_p, C.POINTER(LrParams), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 11
-        L.mc_nb_fit.argtypes = [C.c_void_p, C.POINTER(NbParams), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 9
-        L.mc_calls_expand.argtypes = [C.POINTER(CallsView), C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.mc_count_records.argtypes = [C.POINTER(CallsView), C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p,
-                                       C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        L.mc_format_diffs.argtypes = [C.POINTER(FormatArgs), C.c_int64, C.c_int32, C.POINTER(C.c_void_p),
-                                      C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        L.mc_free.argtypes = [C.c_void_p]
-        L.mc_free.restype = None
-        L.mc_repr_double.argtypes = [C.c_double, C.c_char_p]
-        L.mc_repr_double_rowtext.argtypes = [C.c_double, C.c_char_p]
-        L.mc_ctx_row_text.argtypes = [C.c_void_p, C.c_int32, C.c_char_p, C.c_char_p]
-        L.mc_last_row_text.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
-        L.mc_row_text_release.argtypes = [C.c_void_p, C.c_int32]
-        L.mc_ctx_rowtext_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
-                                           C.c_void_p, C.c_void_p, C.c_void_p]
-        L.mc_bed_summarise_text.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.POINTER(BedParams), C.POINTER(C.c_void_p),
-                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
-        L.mc_bed_summarise_file.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(BedParams), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
-                                            C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
-        L.mc_bed_last_stats.argtypes = [C.c_void_p, C.POINTER(BedStats)]
-        L.mc_bed_release.argtypes = [C.c_void_p]
-        L.mc_bed_positions_text.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, C.POINTER(BedParams),
-                                            C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
-        L.mc_bed_positions_file.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(BedParams), C.POINTER(C.c_void_p),
-                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
-        L.mc_bed_annotate_text.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, C.POINTER(BedParams),
-                                           C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
-        L.mc_bed_annotate_file.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(BedParams), C.POINTER(C.c_void_p),
-                                           C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
-        L.mc_gff_site_moments.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
-        L.mc_gff_site_stats.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_void_p]
-        L.mc_gff_site_text.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_char_p, C.c_int32]
-        L.mc_gff_site_stats_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-        L.mc_npsum_se.argtypes = [C.c_double, C.c_double]
-        L.mc_npsum_se.restype = C.c_double
-        L.mc_npsum_se_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-        L.mc_tstat.argtypes = [C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-        L.mc_tstat_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.mc_tstat_round3.argtypes = [C.c_double]
-        L.mc_tstat_round3.restype = C.c_double
-        L.mc_tstat_tie.argtypes = [C.c_double, C.c_double]
-        L.mc_tstat_site.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
-        L.mc_parse_double.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_double)]
-        L.mc_rows_merge_files.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_int32, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
-        L.mc_rows_merge_text.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
-        L.mc_rows_merge_last_stats.argtypes = [C.c_void_p, C.POINTER(RowsMergeStats)]
-        L.mc_rows_merge_release.argtypes = [C.c_void_p]
-        L.mc_sort_key.argtypes = [C.c_char_p, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-        L.mc_parse_doubles_device.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-        L.mc_train_rows_text.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_char_p, C.c_int32, C.POINTER(TrainRowsView),
-                                         C.POINTER(C.c_int32)]
-        L.mc_train_rows_file.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int32, C.POINTER(TrainRowsView), C.POINTER(C.c_int32)]
-        L.mc_train_rows_last_stats.argtypes = [C.c_void_p, C.POINTER(TrainRowsStats)]
-        L.mc_train_rows_release.argtypes = [C.c_void_p]
+        ABI.declare(L)
         _lib = L
     return _lib
 
 
+def last_error():
+    """The calling thread's last error text: why a call failed, or why it declined."""
+    return lib().mc_last_error().decode('utf-8', 'replace')
+
+
 def check(rc):
     if rc != 0:
-        e = McError(lib().mc_last_error().decode('utf-8', 'replace') or 'libmcaller_hip error %d' % rc)
+        e = McError(last_error() or 'libmcaller_hip error %d' % rc)
         e.code = rc
         raise e
 
@@ -582,7 +265,7 @@ def fastq_read_quality(path, n_threads=0):
     L = lib()
     handle = C.c_void_p()
     if L.mc_fastq_read_quality(path.encode('utf-8'), int(n_threads), C.byref(handle)) != 0:
-        raise ValueError(L.mc_last_error().decode('utf-8', 'replace'))
+        raise ValueError(last_error())
     try:
         pool, off, mean = C.c_void_p(), C.c_void_p(), C.c_void_p()
         n = L.mc_fastq_view(handle, C.byref(pool), C.byref(off), C.byref(mean))
@@ -613,7 +296,7 @@ def fastq_records_host(text):
     if status.value != 0:
         reason, line = C.c_int32(), C.c_int64()
         L.mc_fastq_records_host_decline(C.byref(reason), C.byref(line))
-        return None, None, dict(reason=reason.value, line=line.value, text=L.mc_last_error().decode('utf-8', 'replace'))
+        return None, None, dict(reason=reason.value, line=line.value, text=last_error())
     try:
         pool, off, mean = C.c_void_p(), C.c_void_p(), C.c_void_p()
         n = L.mc_fastq_view(handle, C.byref(pool), C.byref(off), C.byref(mean))
@@ -718,12 +401,13 @@ class DiffsFormatter(object):
         self._contigs, self._reads = _cstr_array(contig_names), _cstr_array(table.read_names)
         self._quals = _cstr_array(read_qual_txt)
         self._soc = np.ascontiguousarray(submodel_of_char, dtype=np.uint8)
-        a = FormatArgs()
-        a.rec, a.n_records, a.k = C.pointer(self._rv), rec.n, k
-        a.table, a.ref = C.pointer(self._tv), C.pointer(self._fv)
-        a.contig_names, a.read_names, a.read_qual_txt = self._contigs, self._reads, self._quals
-        a.tail_chrom = tail_chrom.encode('utf-8', 'surrogateescape') if tail_chrom is not None else None
-        a.label_meth, a.label_unmeth = label_meth.encode(), label_unmeth.encode()
+        self._tail = tail_chrom.encode('utf-8', 'surrogateescape') if tail_chrom is not None else None
+        self._labels = label_meth.encode(), label_unmeth.encode()
+        a = FormatArgs()                 # (its pointer fields are plain addresses: everything they point at is kept in self)
+        a.rec, a.n_records, a.k = C.addressof(self._rv), rec.n, k
+        a.table, a.ref = C.addressof(self._tv), C.addressof(self._fv)
+        a.contig_names, a.read_names, a.read_qual_txt = (C.addressof(s) for s in (self._contigs, self._reads, self._quals))
+        a.tail_chrom, a.label_meth, a.label_unmeth = (C.cast(s, C.c_void_p) for s in (self._tail,) + self._labels)
         a.submodel_of_char = _ptr(self._soc)
         self._args = a
 

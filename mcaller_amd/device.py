@@ -5,7 +5,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import Params, Records, check, lib, make_ref_view, _ptr
+from ._lib import Params, Records, check, last_error, lib, make_ref_view, _ptr
 
 
 def default_device_index():
@@ -57,6 +57,12 @@ class Device(object):
             self.close()
         except Exception:
             pass
+
+    def _last_stats(self, fn, struct):
+        """A *_last_stats call of the library as a dict of the struct's fields (padding left out)."""
+        st = struct()
+        check(fn(self._ctx, C.byref(st)))
+        return {name: getattr(st, name) for name, _ in st._fields_ if not name.startswith('pad')}
 
     # ---- resident inputs ----
     @_serialized
@@ -151,7 +157,7 @@ class Device(object):
         res = _lib.DevParseResult()
         check(lib().mc_ctx_parse_end(self._ctx, int(slot), C.byref(res)))
         if res.status != 0:
-            self.parse_fallback_reason = lib().mc_last_error().decode('utf-8', 'replace')
+            self.parse_fallback_reason = last_error()
             check(lib().mc_ctx_parse_abandon(self._ctx, int(slot)))
             return None
         t = _lib.device_table(res, text)
@@ -564,9 +570,7 @@ class Device(object):
     def forest_fit_last_stats(self):
         """How the last forest_fit ran (mc_forest_fit_stats): n_batches launches of `batch` trees each (what fits
         MCALLER_FOREST_MEM_MB at per_tree_bytes a tree), n_trees_total, n_nodes."""
-        st = _lib.ForestFitStats()
-        check(lib().mc_forest_fit_last_stats(self._ctx, C.byref(st)))
-        return {k: int(getattr(st, k)) for k, _ in st._fields_}
+        return self._last_stats(lib().mc_forest_fit_last_stats, _lib.ForestFitStats)
 
     @_serialized
     def svm_fit(self, X, y, jobs, gammas, C=1.0, tol=1e-3, max_iter=0):
@@ -689,16 +693,14 @@ class Device(object):
             check(lib().mc_bed_summarise_text(self._ctx, text, len(text), C.byref(prm), C.byref(out), C.byref(n_out), C.byref(n_sites),
                                               C.byref(status)))
         if status.value != 0:
-            return None, 0, lib().mc_last_error().decode('utf-8', 'replace')
+            return None, 0, last_error()
         blob = C.string_at(out.value, n_out.value) if n_out.value else b''
         return blob, int(n_sites.value), None
 
     @_serialized
     def bed_last_stats(self):
         """Figures of the last bed_summarise: lines, counted rows, entries, sites, longest probe chain, the decline, milliseconds."""
-        st = _lib.BedStats()
-        check(lib().mc_bed_last_stats(self._ctx, C.byref(st)))
-        return {name: getattr(st, name) for name, _ in st._fields_}
+        return self._last_stats(lib().mc_bed_last_stats, _lib.BedStats)
 
     @_serialized
     def bed_release(self):
@@ -718,22 +720,20 @@ class Device(object):
             n_lines = C.c_int64()
             check(lib().mc_rows_merge_files(self._ctx, arr, len(paths), os.fsencode(out_path), C.byref(n_lines), C.byref(status)))
             if status.value != 0:
-                return None, lib().mc_last_error().decode('utf-8', 'replace')
+                return None, last_error()
             return int(n_lines.value), None
         text = bytes(text)
         out, n_out = C.c_void_p(), C.c_int64()
         check(lib().mc_rows_merge_text(self._ctx, text, len(text), C.byref(out), C.byref(n_out), C.byref(status)))
         if status.value != 0:
-            return None, lib().mc_last_error().decode('utf-8', 'replace')
+            return None, last_error()
         return (C.string_at(out.value, n_out.value) if n_out.value else b''), None
 
     @_serialized
     def merge_rows_last_stats(self):
         """Figures of the last merge_rows: bytes, lines in and out, rounds, radix passes, lines still tied after the numeric key,
         the largest group finished by comparison, the decline (line, reason, file), kernel bytes, milliseconds."""
-        st = _lib.RowsMergeStats()
-        check(lib().mc_rows_merge_last_stats(self._ctx, C.byref(st)))
-        return {name: getattr(st, name) for name, _ in st._fields_ if name != 'pad'}
+        return self._last_stats(lib().mc_rows_merge_last_stats, _lib.RowsMergeStats)
 
     @_serialized
     def merge_rows_release(self):
@@ -811,7 +811,7 @@ class Device(object):
             text = bytes(text)
             check(lib().mc_train_rows_text(self._ctx, text, len(text), blob, len(pairs), C.byref(view), C.byref(status)))
         if status.value != 0:
-            return None, None, None, lib().mc_last_error().decode('utf-8', 'replace')
+            return None, None, None, last_error()
         nf, width, total = view.n_features, view.ctx_width, view.n_rows_total
         X = np.empty((total, nf), dtype=np.float64)
         ctx = np.empty(total, dtype='S%d' % max(width, 1))
@@ -831,9 +831,7 @@ class Device(object):
     @_serialized
     def training_rows_last_stats(self):
         """Figures of the last training_rows: lines, kept rows, labels, features, the decline, milliseconds."""
-        st = _lib.TrainRowsStats()
-        check(lib().mc_train_rows_last_stats(self._ctx, C.byref(st)))
-        return {name: getattr(st, name) for name, _ in st._fields_}
+        return self._last_stats(lib().mc_train_rows_last_stats, _lib.TrainRowsStats)
 
     @_serialized
     def training_rows_release(self):
@@ -854,15 +852,13 @@ class Device(object):
             text = bytes(text)
             check(lib().mc_fastq_quality_text(self._ctx, text, len(text), C.byref(view), C.byref(status)))
         if status.value != 0:
-            return None, None, lib().mc_last_error().decode('utf-8', 'replace')
+            return None, None, last_error()
         return _lib.fastq_unpack(view.key_pool, view.key_off, view.mean, int(view.n_records)) + (None,)
 
     @_serialized
     def fastq_qualities_last_stats(self):
         """Figures of the last fastq_qualities: bytes, lines, records, pieces and their size, the decline, milliseconds."""
-        st = _lib.FastqQualityStats()
-        check(lib().mc_fastq_quality_last_stats(self._ctx, C.byref(st)))
-        return {name: getattr(st, name) for name, _ in st._fields_}
+        return self._last_stats(lib().mc_fastq_quality_last_stats, _lib.FastqQualityStats)
 
     @_serialized
     def fastq_qualities_release(self):
@@ -885,15 +881,13 @@ class Device(object):
             check(lib().mc_bed_compare_text(self._ctx, text1, len(text1), text2, len(text2), C.byref(out), C.byref(n_out),
                                             C.byref(n_sites), C.byref(status)))
         if status.value != 0:
-            return None, 0, lib().mc_last_error().decode('utf-8', 'replace')
+            return None, 0, last_error()
         return (C.string_at(out.value, n_out.value) if n_out.value else b''), int(n_sites.value), None
 
     @_serialized
     def bed_compare_last_stats(self):
         """Figures of the last bed_compare: bytes, lines, keys, shared sites, the rank kernels' shares, the decline, milliseconds."""
-        st = _lib.CmpStats()
-        check(lib().mc_bed_compare_last_stats(self._ctx, C.byref(st)))
-        return {name: getattr(st, name) for name, _ in st._fields_}
+        return self._last_stats(lib().mc_bed_compare_last_stats, _lib.CmpStats)
 
     @_serialized
     def bed_compare_release(self):
@@ -940,16 +934,14 @@ class Device(object):
             check(lib().mc_motif_report_text(self._ctx, C.byref(v), text, len(text), control_text, 0 if control_text is None else len(control_text),
                                              C.byref(P), C.byref(out), C.byref(n_out), C.byref(n_rows), C.byref(status)))
         if status.value != 0:
-            return None, 0, lib().mc_last_error().decode('utf-8', 'replace')
+            return None, 0, last_error()
         return (C.string_at(out.value, n_out.value) if n_out.value else b''), int(n_rows.value), None
 
     @_serialized
     def motif_report_last_stats(self):
         """Figures of the last motif_report: bytes, lines, candidates and sites, selected entries and rows, the stretch and the tables'
         placements, the decline, milliseconds."""
-        st = _lib.MotifStats()
-        check(lib().mc_motif_report_last_stats(self._ctx, C.byref(st)))
-        return {name: getattr(st, name) for name, _ in st._fields_}
+        return self._last_stats(lib().mc_motif_report_last_stats, _lib.MotifStats)
 
     @_serialized
     def motif_report_release(self):
