@@ -930,6 +930,65 @@ int mc_bed_compare_file(mc_ctx *ctx, const char *path1, const char *path2, const
                         int32_t *status);
 int mc_bed_compare_last_stats(mc_ctx *ctx, mc_cmp_stats *out);
 int mc_bed_compare_release(mc_ctx *ctx);
+/* ----- two genomes with their own assemblies: the comparison through a Mauve alignment (csrc/compare/mc_xmfamap.inc; the
+ * definition stands in mcaller_amd/compare_genomes.py) -----
+ * mc_xmfa_map_text / _file: the coordinate map of an XMFA file for its sequence numbers seq1 (n1 bases in concatenated
+ * coordinates, bed1's genome) and seq2 (n2 bases), built on the GPU and kept in the context until the next mc_xmfa_map_* call or
+ * mc_xmfa_map_release: 8 bytes a base of genome 1.  view (may be NULL): host copies of g2[0 .. n1] and flip[0 .. n1], index g1,
+ * 0: unmapped -- pinned memory of the context, valid as long as the map.  Declined (*status = 1, mc_last_error,
+ * mc_xmfa_map_last_stats: reason and line; no map is kept): the MC_CMP_DECLINE_XMFA_* below, MC_CMP_DECLINE_ROWS,
+ * MC_CMP_DECLINE_MEMORY (the map and the text beside free device memory, for which MCALLER_CMP_DEVICE_BYTES stands in tests).  Line by
+ * line the first offending line is named and on it the smallest reason; in a file whose lines are sound, the header line of the
+ * first offending entry and on it the smallest reason.
+ * mc_bed_compare_lifted_text / _file: mc_bed_compare_text / _file through the resident map (-12 without one): a bed1 line is
+ * matched to bed2 by its image, and a row carries the image's four fields behind bed1's.  contigs1 / contigs2: the two genomes'
+ * .fai tables, whose totals must be the map's n1 and n2 (-12).  *n_unaligned: bed1's lines that have no image.  Declines as
+ * mc_bed_compare_*, and MC_CMP_DECLINE_LIFT_START. */
+typedef struct mc_contig_table {
+    int64_t n_contigs;
+    const char *ids;               /* the names, one behind the other ...                          */
+    const int64_t *id_off;         /* ... name i is ids[id_off[i], id_off[i + 1]); n_contigs + 1 entries */
+    const int64_t *off;            /* contig i starts behind off[i] bases; n_contigs + 1 entries, off[n_contigs]: the genome's length */
+} mc_contig_table;
+typedef struct mc_xmfa_map_view {
+    int64_t n1;
+    const int64_t *g2;             /* [n1 + 1]                                                     */
+    const uint8_t *flip;           /* [n1 + 1]                                                     */
+} mc_xmfa_map_view;
+typedef struct mc_xmfa_stats {
+    int64_t n_bytes, n_lines;
+    int64_t n_entries, n_blocks;   /* headers; '=' lines                                           */
+    int64_t n_paired_blocks;       /* blocks that hold both sequence numbers, neither as 0-0       */
+    int64_t n_columns;             /* columns of the paired blocks                                 */
+    int64_t n_words;               /* 64-column words of one gap plane                             */
+    int64_t n_mapped;              /* bases of genome 1 that have an image                         */
+    int64_t n1, n2;
+    int64_t decline_line;          /* 0-based line of the XMFA the decline names, -1: none         */
+    int32_t decline_reason;        /* 0: not declined; MC_CMP_DECLINE_*                            */
+    int32_t pad;
+    double ms_read, ms_h2d, ms_kernels, ms_d2h, ms_total;
+} mc_xmfa_stats;
+#define MC_CMP_DECLINE_XMFA_BYTE     17  /* a '\r' or a byte >= 0x80 in the XMFA                                           */
+#define MC_CMP_DECLINE_XMFA_HEADER   18  /* a malformed header, or a sequence line before its block's first header          */
+#define MC_CMP_DECLINE_XMFA_SEQ_BYTE 19  /* a sequence byte that is neither '-' nor a letter                                */
+#define MC_CMP_DECLINE_XMFA_COUNT    20  /* an entry whose non-gap count disagrees with its header                          */
+#define MC_CMP_DECLINE_XMFA_COLUMNS  21  /* an entry with another column count than the entry before it in the block        */
+#define MC_CMP_DECLINE_XMFA_UNCLOSED 22  /* an entry behind the last '='                                                    */
+#define MC_CMP_DECLINE_XMFA_RANGE    23  /* an END beyond the .fai total of its genome                                      */
+#define MC_CMP_DECLINE_XMFA_GENOME   24  /* a genome of more than 2^31 - 2 bases, or 2^31 columns or more in paired blocks  */
+#define MC_CMP_DECLINE_LIFT_START    25  /* a bed1 start that is not plain digits (int() may accept it: the host decides)   */
+int mc_xmfa_map_text(mc_ctx *ctx, const char *text, int64_t n_bytes, int32_t seq1, int32_t seq2, int64_t n1, int64_t n2,
+                     mc_xmfa_map_view *view, int32_t *status);
+int mc_xmfa_map_file(mc_ctx *ctx, const char *path, int32_t seq1, int32_t seq2, int64_t n1, int64_t n2, mc_xmfa_map_view *view,
+                     int32_t *status);
+int mc_xmfa_map_last_stats(mc_ctx *ctx, mc_xmfa_stats *out);
+int mc_xmfa_map_release(mc_ctx *ctx);
+int mc_bed_compare_lifted_text(mc_ctx *ctx, const char *text1, int64_t n_bytes1, const char *text2, int64_t n_bytes2,
+                               const mc_contig_table *contigs1, const mc_contig_table *contigs2, const char **out, int64_t *n_out,
+                               int64_t *n_sites, int64_t *n_unaligned, int32_t *status);
+int mc_bed_compare_lifted_file(mc_ctx *ctx, const char *path1, const char *path2, const mc_contig_table *contigs1,
+                               const mc_contig_table *contigs2, const char **out, int64_t *n_out, int64_t *n_sites,
+                               int64_t *n_unaligned, int32_t *status);
 int mc_twosample(const double *x, int64_t n1, const double *y, int64_t n2, double *out, double *bound, int32_t *status);
 int mc_twosample_device(mc_ctx *ctx, const double *x, const int64_t *x_off, const double *y, const int64_t *y_off, int64_t k,
                         double *out, double *bound, int32_t *status);

@@ -50,6 +50,9 @@ RowsMergeStats = _S['mc_rows_merge_stats']
 FastqQualityView = _S['mc_fastq_quality_view']
 FastqQualityStats = _S['mc_fastq_quality_stats']
 CmpStats = _S['mc_cmp_stats']
+ContigTable = _S['mc_contig_table']
+XmfaMapView = _S['mc_xmfa_map_view']
+XmfaStats = _S['mc_xmfa_stats']
 MotifParams = _S['mc_motif_params']
 MotifStats = _S['mc_motif_stats']
 Params = _S['mc_params']

@@ -20,14 +20,54 @@ z and t are str(np.round(v, 3)), every nlp is str(np.round(0.0 - np.log10(p), 3)
 
 `compare_by_position` is that definition written with the SciPy calls (the host statement).  `compare_by_position_device`
 (--device) has the GPU make the same bytes (Device.bed_compare: csrc/compare/mc_bedcompare.hip) and runs the host statement
-whenever the device declines; `last_compare` says who made the output.  -g is accepted and unused, as in the reference."""
+whenever the device declines; `last_compare` says who made the output.  -g is accepted and unused, as in the reference.
+
+TWO GENOMES WITH THEIR OWN ASSEMBLIES are compared through a Mauve alignment (the reference declares -g and never reads it):
+
+    python -m mcaller_amd.compare_genomes --bed1 A.bed --bed2 B.bed --xmfa AB.xmfa --fai1 A.fasta.fai --fai2 B.fasta.fai
+                                          [--xmfa_seqs 1,2] [-o OUT] [--device]
+
+.fai files: the first two tab-separated fields of each non-blank line, name and length, in file order.  Mauve numbers a
+multi-FASTA genome in concatenated coordinates in that order: contig k starts at offset sum(len[:k]).  Of two contigs with one
+name the first is meant.
+
+XMFA lines: lines beginning with '#' and empty lines are ignored.  A block is a run of entries ended by a line that is exactly
+'='.  An entry is a header line followed by sequence lines of any widths.  The header is '>', optional blanks (spaces, tabs), then
+SEQ:START-END, one or more blanks, '+' or '-', and optionally a blank followed by anything; SEQ, START and END are plain decimal,
+coordinates 1-based and inclusive in concatenated coordinates.  A sequence byte is '-' (a gap) or an ASCII letter.
+Entries: START-END of 0-0 means the sequence is absent from the block: the entry must be all gaps and contributes nothing; any
+other entry has 1 <= START <= END and END - START + 1 non-gaps.  All entries of a block have the same number of columns.  The
+non-gap of rank r (0-based) of a '+' entry is coordinate START + r, of a '-' entry END - r.
+Columns: for the two sequence numbers of --xmfa_seqs (bed1's genome, then bed2's; the block's first entry of each number), a
+column where both are non-gap maps g1 -> (g2, flip), flip: the two entries' strands differ.  A block that lacks either sequence
+maps nothing.  A g1 aligned more than once keeps the first column in file order.
+Lifting a bed1 line (chrom, start, end, strand, ...): chrom is a name of --fai1, start plain digits (no sign, no blanks, no
+leading zero unless it is 0; the host takes whatever else int() accepts, and a line whose start int() rejects has no image),
+g1 = off1[chrom] + start + 1 <= off1[chrom] + len1[chrom], strand '+' or '-'.  Its image is the bed2 key (chrom2, str(start2),
+str(start2 + 1), strand2): g2 falls in contig chrom2 of --fai2, start2 = g2 - off2[chrom2] - 1, strand2 the strand, flipped if
+flip.  The image is matched against bed2's (chrom, start, end, strand) as text.  A line with an unknown chrom, a start past its
+contig, a strand that is neither '+' nor '-' or an unmapped g1 has no image: it is counted in last_compare['n_unaligned'] (per
+key of bed1) and writes no row.
+One row per bed1 line whose image is a key of bed2, in bed1's order:
+
+    chrom1 start1 end1 strand1 chrom2 start2 end2 strand2 frac1 depth1 frac2 depth2 U z_mwu z_rs t D nlp_mwu nlp_rs nlp_t nlp_ks
+
+with the nine statistics of the row above for the same two lists.
+Errors (ValueError, 'xmfa line N: ...'): line by line, the first offending line and on it the first of: a '\r' or a byte >= 0x80;
+a malformed header, or a sequence line before its block's first header; a sequence byte that is neither '-' nor a letter.  In a
+file whose lines are sound, entry by entry (the header's line is named), the first of: a non-gap count that disagrees with the
+header; a column count other than that of the entry before it in the block; an entry behind the last '='; an END beyond the
+.fai total of its genome (--xmfa_seqs' two).  The device declines on each (MC_CMP_DECLINE_XMFA_*) and this statement words the error;
+it also declines a bed1 start that is not plain digits, and this statement does the file."""
 import os
+import re
 import sys
 import warnings
 
 import numpy as np
 
-last_compare = None        # what the last comparison did: dict(by='device' | 'host', reason=None | str, n_sites=int)
+# what the last comparison did: dict(by='device' | 'host', reason=None | str, n_sites=int), and n_unaligned=int with --xmfa
+last_compare = None
 
 
 def read_bed(bed):
@@ -86,43 +126,227 @@ def _write(out, data):
             fo.write(data)
 
 
-def compare_rows(bed1, bed2):
-    """The rows of the definition as bytes, and their number."""
+def read_fai(path):
+    """(names, lens int64 [k], offs int64 [k + 1]) of a .fai file: name and length of every non-blank line, in file order;
+    offs[k] is the genome's length in concatenated coordinates."""
+    names, lens = [], []
+    with open(path, 'r') as fi:
+        for no, line in enumerate(fi, 1):
+            if not line.strip():
+                continue
+            fields = line.rstrip('\n').split('\t')
+            if len(fields) < 2 or not fields[1].isascii() or not fields[1].isdigit():
+                raise ValueError('%s line %d: not a name and a length' % (path, no))
+            names.append(fields[0])
+            lens.append(int(fields[1]))
+    lens = np.asarray(lens, dtype=np.int64).reshape(-1)
+    offs = np.zeros(len(lens) + 1, dtype=np.int64)
+    offs[1:] = np.cumsum(lens, dtype=np.int64)
+    return names, lens, offs
+
+
+_XMFA_HEADER = re.compile(rb'>[ \t]*([0-9]+):([0-9]+)-([0-9]+)[ \t]+([+-])(?:[ \t].*)?', re.S)
+_XMFA_NOT_SEQ = re.compile(rb'[^A-Za-z-]')
+
+
+def _xmfa_error(no, what):
+    return ValueError('xmfa line %d: %s' % (no, what))
+
+
+def xmfa_blocks(path):
+    """The entries of an XMFA file, line-level errors raised: [(closed, [(header's 1-based line, seq, start, end, strand, joined
+    sequence bytes)])], one per block in file order; the entries behind the last '=' are a block that is not closed."""
+    with open(path, 'rb') as fi:
+        lines = fi.read().split(b'\n')
+    if lines and lines[-1] == b'':
+        lines.pop()
+    blocks, cur = [], []
+    for no, line in enumerate(lines, 1):
+        if b'\r' in line or not line.isascii():
+            raise _xmfa_error(no, "a '\\r' or a byte >= 0x80")
+        if not line or line[:1] == b'#':
+            continue
+        if line == b'=':
+            blocks.append((True, cur))
+            cur = []
+        elif line[:1] == b'>':
+            m = _XMFA_HEADER.fullmatch(line)
+            if m is None:
+                raise _xmfa_error(no, 'a malformed header')
+            seq, start, end = int(m.group(1)), int(m.group(2)), int(m.group(3))
+            if (start, end) != (0, 0) and not 1 <= start <= end:
+                raise _xmfa_error(no, 'a malformed header (START-END is neither 0-0 nor 1 <= START <= END)')
+            cur.append([no, seq, start, end, m.group(4).decode(), []])
+        else:
+            if not cur:
+                raise _xmfa_error(no, "a sequence line before its block's first header")
+            if _XMFA_NOT_SEQ.search(line):
+                raise _xmfa_error(no, "a sequence byte that is neither '-' nor a letter")
+            cur[-1][5].append(line)
+    if cur:
+        blocks.append((False, cur))
+    return [(closed, [tuple(e[:5]) + (b''.join(e[5]),) for e in entries]) for closed, entries in blocks]
+
+
+def xmfa_map(path, n1, seqs=(1, 2), n2=None):
+    """The coordinate map of the definition for genome seqs[0] (n1 bases) onto genome seqs[1] (n2 bases, None: not checked)
+    -> (g2: int64 [n1 + 1], flip: uint8 [n1 + 1]), index g1, 0: unmapped."""
+    seq1, seq2 = int(seqs[0]), int(seqs[1])
+    if seq1 == seq2:
+        raise ValueError('xmfa_map: two different sequence numbers')
+    G1, G2, F = [], [], []
+    for closed, entries in xmfa_blocks(path):
+        pick = {}
+        for k, (no, seq, start, end, strand, text) in enumerate(entries):
+            cols = len(text)
+            if cols - text.count(b'-') != (0 if end == 0 else end - start + 1):
+                raise _xmfa_error(no, "a non-gap count that disagrees with the header's %d-%d" % (start, end))
+            if k > 0 and cols != len(entries[k - 1][5]):
+                raise _xmfa_error(no, 'unequal column counts in a block')
+            if not closed:
+                raise _xmfa_error(no, "an entry behind the last '=' without a closing '='")
+            if (seq == seq1 and end > n1) or (seq == seq2 and n2 is not None and end > n2):
+                raise _xmfa_error(no, 'a coordinate beyond the .fai total of its genome')
+            pick.setdefault(seq, k)
+        if seq1 not in pick or seq2 not in pick:
+            continue
+        _, _, s1, e1, st1, t1 = entries[pick[seq1]]
+        _, _, s2, e2, st2, t2 = entries[pick[seq2]]
+        if e1 == 0 or e2 == 0:
+            continue
+        a1, a2 = np.frombuffer(t1, dtype=np.uint8) != 45, np.frombuffer(t2, dtype=np.uint8) != 45
+        both = np.flatnonzero(a1 & a2)
+        r1, r2 = np.cumsum(a1, dtype=np.int64)[both] - 1, np.cumsum(a2, dtype=np.int64)[both] - 1
+        G1.append(s1 + r1 if st1 == '+' else e1 - r1)
+        G2.append(s2 + r2 if st2 == '+' else e2 - r2)
+        F.append(np.full(len(both), st1 != st2, dtype=np.uint8))
+    g2, flip = np.zeros(n1 + 1, dtype=np.int64), np.zeros(n1 + 1, dtype=np.uint8)
+    if G1:
+        at, first = np.unique(np.concatenate(G1), return_index=True)          # the first column in file order wins
+        g2[at], flip[at] = np.concatenate(G2)[first], np.concatenate(F)[first]
+    return g2, flip
+
+
+def plain_digits(text):
+    return text.isascii() and text.isdigit() and (text == '0' or text[0] != '0')
+
+
+def lift_key(key, contigs1, contigs2, g2, flip):
+    """The image of bed1's key (chrom, start, end, strand) in bed2's coordinates, or None.  contigs: ({name: index}, lens, offs,
+    names)."""
+    chrom, start, _, strand = key
+    index1, lens1, offs1, _ = contigs1
+    _, _, offs2, names2 = contigs2
+    k = index1.get(chrom)
+    if k is None or strand not in ('+', '-'):
+        return None
+    if plain_digits(start):
+        start = int(start)
+    else:
+        try:
+            start = int(start)
+        except ValueError:
+            return None
+    if not 0 <= start < lens1[k]:
+        return None
+    to = int(g2[offs1[k] + start + 1])
+    if to == 0 or to > offs2[-1]:
+        return None
+    k2 = int(np.searchsorted(offs2, to, side='left')) - 1
+    start2 = to - int(offs2[k2]) - 1
+    return (names2[k2], str(start2), str(start2 + 1), strand if not flip[offs1[k] + start + 1] else '+-'[strand == '+'])
+
+
+def _contigs(fai):
+    """read_fai's result, or a path -> ({name: index of the first contig of that name}, lens, offs, names)."""
+    names, lens, offs = read_fai(fai) if isinstance(fai, (str, os.PathLike)) else fai
+    index = {}
+    for k, name in enumerate(names):
+        index.setdefault(name, k)
+    return index, lens, offs, list(names)
+
+
+def _rows(bed1, bed2, xmfa_path=None, fai1=None, fai2=None, seqs=(1, 2)):
+    """-> the rows as bytes, their number, and (with an alignment) the keys of bed1 that have no image, else None."""
     sites1, sites2 = read_bed(bed1), read_bed(bed2)
     rows = []
+    if xmfa_path is None:
+        for pos in sites1:
+            if pos in sites2:
+                (frac1, depth1), x = sites1[pos]
+                (frac2, depth2), y = sites2[pos]
+                rows.append('\t'.join(list(pos) + [frac1, depth1, frac2, depth2] + site_values(x, y)) + '\n')
+        return ''.join(rows).encode('utf-8', 'surrogateescape'), len(rows), None
+    if fai1 is None or fai2 is None:
+        raise ValueError('an alignment needs the .fai of both genomes')
+    contigs1, contigs2 = _contigs(fai1), _contigs(fai2)
+    g2, flip = xmfa_map(xmfa_path, int(contigs1[2][-1]), seqs, int(contigs2[2][-1]))
+    n_unaligned = 0
     for pos in sites1:
-        if pos in sites2:
+        image = lift_key(pos, contigs1, contigs2, g2, flip)
+        if image is None:
+            n_unaligned += 1
+        elif image in sites2:
             (frac1, depth1), x = sites1[pos]
-            (frac2, depth2), y = sites2[pos]
-            rows.append('\t'.join(list(pos) + [frac1, depth1, frac2, depth2] + site_values(x, y)) + '\n')
-    return ''.join(rows).encode('utf-8', 'surrogateescape'), len(rows)
+            (frac2, depth2), y = sites2[image]
+            rows.append('\t'.join(list(pos) + list(image) + [frac1, depth1, frac2, depth2] + site_values(x, y)) + '\n')
+    return ''.join(rows).encode('utf-8', 'surrogateescape'), len(rows), n_unaligned
 
 
-def _host(bed1, bed2, out, reason):
+def compare_rows(bed1, bed2, xmfa_path=None, fai1=None, fai2=None, seqs=(1, 2)):
+    """The rows of the definition as bytes, and their number."""
+    return _rows(bed1, bed2, xmfa_path, fai1, fai2, seqs)[:2]
+
+
+def _done(by, reason, n_sites, n_unaligned):
     global last_compare
-    last_compare = None
-    data, n_sites = compare_rows(bed1, bed2)
-    _write(out, data)
-    last_compare = dict(by='host', reason=reason, n_sites=n_sites)
+    last_compare = dict(by=by, reason=reason, n_sites=n_sites)
+    if n_unaligned is not None:
+        last_compare['n_unaligned'] = n_unaligned
     return n_sites
 
 
-def compare_by_position(bed1, bed2, xmfa=None, out=None):
-    """The host statement: the definition above, one SciPy call after the other.  xmfa is accepted and unused."""
-    return _host(bed1, bed2, out, 'the host statement was asked for')
+def _host(bed1, bed2, out, reason, lift=()):
+    global last_compare
+    last_compare = None
+    data, n_sites, n_unaligned = _rows(bed1, bed2, *lift)
+    _write(out, data)
+    return _done('host', reason, n_sites, n_unaligned)
 
 
-def compare_by_position_device(bed1, bed2, xmfa=None, out=None):
+def compare_by_position(bed1, bed2, xmfa=None, out=None, xmfa_path=None, fai1=None, fai2=None, seqs=(1, 2)):
+    """The host statement: the definition above, one SciPy call after the other.  xmfa (-g) is accepted and unused; the
+    alignment is xmfa_path."""
+    return _host(bed1, bed2, out, 'the host statement was asked for', (xmfa_path, fai1, fai2, seqs))
+
+
+def compare_by_position_device(bed1, bed2, xmfa=None, out=None, xmfa_path=None, fai1=None, fai2=None, seqs=(1, 2)):
     """The same bytes made on the GPU, or -- when the device declines -- by the host statement, which also words the errors."""
     global last_compare
     from .device import get_device
     last_compare = None
-    blob, n_sites, reason = get_device().bed_compare(path1=bed1, path2=bed2)
+    lift = (xmfa_path, fai1, fai2, seqs)
+    if xmfa_path is None:
+        blob, n_sites, reason = get_device().bed_compare(path1=bed1, path2=bed2)
+        n_unaligned = None
+    else:
+        if fai1 is None or fai2 is None:
+            raise ValueError('an alignment needs the .fai of both genomes')
+        dev, contigs1, contigs2 = get_device(), read_fai(fai1), read_fai(fai2)
+        if int(seqs[0]) == int(seqs[1]):
+            raise ValueError('xmfa_map: two different sequence numbers')
+        _, _, reason = dev.xmfa_map(path=xmfa_path, n1=int(contigs1[2][-1]), n2=int(contigs2[2][-1]), seqs=seqs, view=False)
+        if reason is not None:
+            return _host(bed1, bed2, out, reason, lift)
+        try:
+            blob, n_sites, reason = dev.bed_compare(path1=bed1, path2=bed2, contigs1=contigs1, contigs2=contigs2)
+        finally:
+            dev.xmfa_map_release()
+        n_unaligned = dev.bed_compare_last_unaligned()
     if blob is None:
-        return _host(bed1, bed2, out, reason)
+        return _host(bed1, bed2, out, reason, lift)
     _write(out, blob)
-    last_compare = dict(by='device', reason=None, n_sites=n_sites)
-    return n_sites
+    return _done('device', None, n_sites, n_unaligned)
 
 
 def main(argv=None):
@@ -132,6 +356,10 @@ def main(argv=None):
     parser.add_argument('--bed2', type=str, required=False, help='bed file 2 with verbose output from make_bed.py')
     parser.add_argument('-g', '--genome_alignment', type=str, required=False,
                         help='an xmfa file from mauve (if absent, alignments assumed to be to the same reference genome)')
+    parser.add_argument('--xmfa', type=str, required=False, help='compare through this Mauve alignment (needs --fai1 and --fai2)')
+    parser.add_argument('--fai1', type=str, required=False, help="the .fai of bed1's genome")
+    parser.add_argument('--fai2', type=str, required=False, help="the .fai of bed2's genome")
+    parser.add_argument('--xmfa_seqs', type=str, default='1,2', help="the alignment's sequence numbers of bed1's and bed2's genome (default 1,2)")
     parser.add_argument('-o', '--output', type=str, required=False, help='write the rows to this file (default: standard output)')
     parser.add_argument('--device', action='store_true', required=False, help='make the rows on the GPU (the host statement runs when it declines)')
     parser.add_argument('-v', '--version', action='store_true', required=False, help='print version')
@@ -147,7 +375,18 @@ def main(argv=None):
     assert os.path.isfile(args.bed2), 'file not found at ' + args.bed2
 
     run = compare_by_position_device if args.device else compare_by_position
-    run(args.bed1, args.bed2, args.genome_alignment, args.output)
+    if args.xmfa is None:
+        run(args.bed1, args.bed2, args.genome_alignment, args.output)
+        return
+    if args.fai1 is None or args.fai2 is None:
+        parser.error('--xmfa needs --fai1 and --fai2')
+    seqs = args.xmfa_seqs.split(',')
+    if len(seqs) != 2 or not all(plain_digits(s) for s in seqs) or seqs[0] == seqs[1]:
+        parser.error('--xmfa_seqs: two different sequence numbers, as in 1,2')
+    for path in (args.xmfa, args.fai1, args.fai2):
+        assert os.path.isfile(path), 'file not found at ' + path
+    run(args.bed1, args.bed2, args.genome_alignment, args.output, xmfa_path=args.xmfa, fai1=args.fai1, fai2=args.fai2,
+        seqs=(int(seqs[0]), int(seqs[1])))
 
 
 if __name__ == '__main__':

@@ -3,6 +3,9 @@
 // four SciPy calls per site in a Python loop (C ABI: mc_bed_compare_text / _file, mc_bed_compare_last_stats,
 // mc_bed_compare_release, mc_twosample_device; Python: Device.bed_compare, compare_genomes.compare_by_position_device).  The unit
 // stands in csrc/compare/, beside csrc/bed/, csrc/train/, csrc/merge/ and csrc/fastq/: no pass runs its kernels.
+// Two genomes with their own assemblies are compared through a Mauve alignment: mc_xmfamap.inc, included below, builds the coordinate
+// map from the XMFA text (kx_*) and lifts bed1's lines onto bed2's keys (kc_lift, in kc_probe's place; mc_bed_compare_lifted_*); its
+// header comment lists its declines (MC_CMP_DECLINE_XMFA_*, MC_CMP_DECLINE_LIFT_START) and its kernels' resources.
 //
 // The result is the host statement's bytes or a decline (status 1, mc_last_error; the stats say which file and line):
 //   file-level   MC_CMP_DECLINE_HIGH_BYTE   a byte >= 0x80 (the host decodes the file; the device compares bytes)
@@ -85,6 +88,17 @@ struct CmpHead {                             // device-side result block (copied
     long long n_sites, n_x, n_y, out_bytes;  // totals of the scans
     unsigned long long n_small, n_large;     // sites each rank kernel took
     int longest_probe, deepest;
+    unsigned long long n_unaligned;          // (a lifted comparison) bed1's lines that have no image
+};
+
+// a lifted comparison (mc_xmfamap.inc): the resident map, genome 1's contig names in a key table, both genomes' offsets
+struct LiftDev {
+    const unsigned long long *map;
+    int64_t n1, nc1, nc2;
+    const unsigned long long *ctable;
+    uint64_t cmask;
+    const char *ids1, *ids2;
+    const long long *id_off1, *id_off2, *off1, *off2;
 };
 
 struct CmpArgs {
@@ -112,6 +126,8 @@ struct CmpArgs {
     double *out9, *bound9;
     int32_t *status;
     char *out;
+    int lifted;                              // 1: kc_lift matched the lines; a row carries the image's key behind bed1's
+    LiftDev lift;
 };
 
 __device__ __forceinline__ TabSpan cmp_line(const CmpArgs &A, int64_t li) { return tabs_unpack(A.span[li]); }
@@ -413,6 +429,10 @@ __device__ __forceinline__ void cmp_put_row(const CmpArgs &A, int64_t s, Sink &o
     const char *p1 = A.text + A.line_start[l1], *p2 = A.text + A.line_start[l2];
     for (int i = 0; i <= L1.t[2]; ++i) o.put(p1[i]);                   // chrom, start, end and the tab behind each
     for (int i = L1.t[4] + 1; i <= L1.t[5]; ++i) o.put(p1[i]);         // strand, its tab
+    if (A.lifted) {                                                    // the image: bed2's key as it stands
+        for (int i = 0; i <= L2.t[2]; ++i) o.put(p2[i]);
+        for (int i = L2.t[4] + 1; i <= L2.t[5]; ++i) o.put(p2[i]);
+    }
     for (int i = L1.t[3] + 1; i <= L1.t[4]; ++i) o.put(p1[i]);         // frac1
     for (int i = L1.t[5] + 1; i <= L1.t[6]; ++i) o.put(p1[i]);         // depth1
     for (int i = L2.t[3] + 1; i <= L2.t[4]; ++i) o.put(p2[i]);
@@ -469,6 +489,7 @@ const char *cmp_reason_text(int reason) {
         case MC_CMP_DECLINE_FAR_TAIL: return "a log10 p below -290";
         case MC_CMP_DECLINE_PRINT: return "a value the device's row writer does not print";
         case MC_CMP_DECLINE_TIE: return "a value within its error bound of a rounding tie";
+        case MC_CMP_DECLINE_LIFT_START: return "a start that is not plain digits";
     }
     return "unknown";
 }
@@ -504,9 +525,12 @@ int launch_ranks(hipStream_t st, const RankArgs &R) {
     return 0;
 }
 
+#include "mc_xmfamap.inc"
+
 // The texts are on the device (d_text[0, n): bed1's, a newline if it lacked its last, bed2's from off2 on; padded): everything behind that
+// (lift: the device side of a lifted comparison, nullptr: keys are matched as they stand)
 int cmp_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, int64_t off2, const char **out, int64_t *n_out, int64_t *n_sites,
-            int32_t *status) {
+            int32_t *status, const LiftDev *lift) {
     mc_cmp_stats &S = c->cmp_stats;
     hipStream_t st = c->stream;
     if (n == 0) return 0;
@@ -524,6 +548,7 @@ int cmp_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, int64_t off2, 
     if (int rc = lines_starts(pool, st, d_text, n, n_nl, tile_off, &d_head->kp, &line_start)) return rc;
     CmpArgs A = {};
     A.text = d_text; A.n_bytes = n; A.off2 = off2; A.n_nl = n_nl; A.line_start = line_start; A.head = d_head;
+    if (lift) { A.lifted = 1; A.lift = *lift; }
     const char *hm = getenv("MCALLER_CMP_HASH_MASK");
     A.hash_mask = hm && *hm ? strtoull(hm, nullptr, 16) : ~0ull;      // (tests: long probe chains)
     if (pool.get(&A.span, cap) || pool.get(&A.hash, cap) || pool.get(&A.n_vals, cap) || pool.get(&A.match, cap) || pool.get(&A.flag, cap) ||
@@ -537,20 +562,22 @@ int cmp_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, int64_t off2, 
     if (h.decline != CMP_NO_DECLINE) return cmp_decline_head(c, status, h);
     A.n_lines = L; A.n_lines1 = L1;
     S.n_keys2 = L2;
-    if (L1 > 0 && L2 > 0) {
+    if (L1 > 0 && (L2 > 0 || lift)) {                                  // (a lifted comparison counts bed1's lines without an image in any case)
         A.mask[0] = table_slots(L1, 64, "MCALLER_CMP_TABLE_SLOTS") - 1; A.mask[1] = table_slots(L2, 64, "MCALLER_CMP_TABLE_SLOTS") - 1;
         S.table_slots = (int64_t)A.mask[1] + 1;
         if (!cmp_fits((A.mask[0] + A.mask[1] + 2) * 8 + ((size_t)1 << 20))) return cmp_decline(c, status, MC_CMP_DECLINE_MEMORY, 0, -1);
         for (int w = 0; w < 2; ++w)
             if (int rc = table_get(pool, st, &A.table[w], A.mask[w] + 1)) return rc;
-        hipLaunchKernelGGL(kc_insert, dim3(blocks(L2)), dim3(256), 0, st, A, 1);
+        if (L2 > 0) hipLaunchKernelGGL(kc_insert, dim3(blocks(L2)), dim3(256), 0, st, A, 1);
         hipLaunchKernelGGL(kc_insert, dim3(blocks(L1)), dim3(256), 0, st, A, 0);
-        hipLaunchKernelGGL(kc_probe, dim3(blocks(L1)), dim3(256), 0, st, A);
+        if (lift) hipLaunchKernelGGL(kc_lift, dim3(blocks(L1)), dim3(256), 0, st, A);
+        else hipLaunchKernelGGL(kc_probe, dim3(blocks(L1)), dim3(256), 0, st, A);
         hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)A.flag, L1, A.site_of, &d_head->n_sites);
         HIP_TRY(hipGetLastError());
         if (int rc = fetch_head(st, d_head, h)) return rc;
         if (h.decline != CMP_NO_DECLINE) return cmp_decline_head(c, status, h);
         S.longest_probe = h.longest_probe;
+        c->cmp_unaligned = (int64_t)h.n_unaligned;
     }
     const int64_t NS = h.n_sites;
     S.n_sites = NS;
@@ -610,10 +637,50 @@ int cmp_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, int64_t off2, 
     return 0;
 }
 
-int cmp_call(mc_ctx *c, const TextSource &s1, const TextSource &s2, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status) {
+// a contig table's arrays onto the device (the pool's) -> the device pointers
+int lift_upload(Pool &pool, hipStream_t st, const mc_contig_table *t, const char **ids, const long long **id_off, const long long **off) {
+    const size_t nc = (size_t)t->n_contigs, n_ids = (size_t)t->id_off[nc];
+    char *d_ids = nullptr;
+    long long *d_id_off = nullptr, *d_off = nullptr;
+    if (pool.get(&d_ids, n_ids + 1) || pool.get(&d_id_off, nc + 1) || pool.get(&d_off, nc + 1)) return -10;
+    if (n_ids) HIP_TRY(hipMemcpyAsync(d_ids, t->ids, n_ids, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_id_off, t->id_off, (nc + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_off, t->off, (nc + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));                                 // (the host arrays are the caller's)
+    *ids = d_ids; *id_off = d_id_off; *off = d_off;
+    return 0;
+}
+
+// the device side of a lifted comparison: the contig tables, genome 1's names in a key table, the context's resident map
+int lift_prepare(mc_ctx *c, Pool &pool, const mc_contig_table *t1, const mc_contig_table *t2, LiftDev *T) {
+    hipStream_t st = c->stream;
+    *T = LiftDev();
+    T->map = c->xmfa_map; T->n1 = c->xmfa_n1; T->nc1 = t1->n_contigs; T->nc2 = t2->n_contigs;
+    if (int rc = lift_upload(pool, st, t1, &T->ids1, &T->id_off1, &T->off1)) return rc;
+    if (int rc = lift_upload(pool, st, t2, &T->ids2, &T->id_off2, &T->off2)) return rc;
+    T->cmask = table_slots(T->nc1, 64) - 1;
+    unsigned long long *table = nullptr;
+    if (int rc = table_get(pool, st, &table, T->cmask + 1)) return rc;
+    T->ctable = table;
+    const char *hm = getenv("MCALLER_CMP_HASH_MASK");
+    if (T->nc1 > 0) hipLaunchKernelGGL(kc_contigs, dim3(blocks(T->nc1)), dim3(256), 0, st, *T, table, hm && *hm ? strtoull(hm, nullptr, 16) : ~0ull);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+bool lift_tables_ok(const mc_contig_table *t) {
+    if (!t || t->n_contigs < 0 || !t->id_off || !t->off || (t->id_off[t->n_contigs] > 0 && !t->ids) || t->id_off[0] != 0 || t->off[0] != 0) return false;
+    for (int64_t i = 0; i < t->n_contigs; ++i)
+        if (t->id_off[i + 1] < t->id_off[i] || t->id_off[i + 1] - t->id_off[i] > 65535 || t->off[i + 1] < t->off[i]) return false;
+    return true;
+}
+
+int cmp_call(mc_ctx *c, const TextSource &s1, const TextSource &s2, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status,
+             const mc_contig_table *t1 = nullptr, const mc_contig_table *t2 = nullptr) {
     HIP_TRY(hipSetDevice(c->device));
     const auto t0 = std::chrono::steady_clock::now();
     c->cmp_stats = mc_cmp_stats();
+    c->cmp_unaligned = 0;
     c->cmp_stats.decline_line = -1;
     c->cmp_stats.n_bytes1 = s1.n; c->cmp_stats.n_bytes2 = s2.n;
     *out = nullptr; *n_out = 0; *n_sites = 0; *status = 0;
@@ -632,7 +699,9 @@ int cmp_call(mc_ctx *c, const TextSource &s1, const TextSource &s2, const char *
     if (int rc = feed.pad_and_wait(d_text + off2 + s2.n)) return rc;
     feed.times(c->cmp_stats, t0);
     const auto t_kernels = std::chrono::steady_clock::now();
-    const int rc = cmp_run(c, pool, d_text, off2 + s2.n, off2, out, n_out, n_sites, status);
+    LiftDev lift;
+    int rc = t1 ? lift_prepare(c, pool, t1, t2, &lift) : 0;
+    if (rc == 0) rc = cmp_run(c, pool, d_text, off2 + s2.n, off2, out, n_out, n_sites, status, t1 ? &lift : nullptr);
     (void)hipStreamSynchronize(c->stream);                             // (an early return: nothing of the pool is in use when it goes)
     c->cmp_stats.ms_kernels = ms_since(t_kernels) - c->cmp_stats.ms_d2h;      // a declined call too: what ran until it declined
     if (rc != 0 || *status != 0) { *out = nullptr; *n_out = 0; *n_sites = 0; }
@@ -661,6 +730,77 @@ extern "C" int mc_bed_compare_file(mc_ctx *c, const char *path1, const char *pat
     if (int rc = regular_file_size("mc_bed_compare_file", path1, &n1)) return rc;
     if (int rc = regular_file_size("mc_bed_compare_file", path2, &n2)) return rc;
     return cmp_call(c, TextSource{nullptr, path1, n1}, TextSource{nullptr, path2, n2}, out, n_out, n_sites, status);
+}
+
+// the arguments of a lifted comparison beyond those of a plain one -> 0, or -12 with the error set
+static int lifted_arguments(const char *who, mc_ctx *c, const mc_contig_table *t1, const mc_contig_table *t2, int64_t *n_unaligned) {
+    if (!n_unaligned || !lift_tables_ok(t1) || !lift_tables_ok(t2)) { mc_set_error("%s: bad arguments", who); return -12; }
+    *n_unaligned = 0;
+    if (!c->xmfa_map) { mc_set_error("%s: no alignment map is resident (mc_xmfa_map_text / _file first)", who); return -12; }
+    if (t1->off[t1->n_contigs] != c->xmfa_n1 || t2->off[t2->n_contigs] != c->xmfa_n2) {
+        mc_set_error("%s: the contig tables' totals are not those the map was built for", who);
+        return -12;
+    }
+    return 0;
+}
+
+extern "C" int mc_bed_compare_lifted_text(mc_ctx *c, const char *text1, int64_t n1, const char *text2, int64_t n2, const mc_contig_table *t1,
+                                          const mc_contig_table *t2, const char **out, int64_t *n_out, int64_t *n_sites, int64_t *n_unaligned,
+                                          int32_t *status) {
+    if (!c || !out || !n_out || !n_sites || !status || n1 < 0 || n2 < 0 || (n1 > 0 && !text1) || (n2 > 0 && !text2)) {
+        mc_set_error("mc_bed_compare_lifted_text: bad arguments");
+        return -12;
+    }
+    if (int rc = lifted_arguments("mc_bed_compare_lifted_text", c, t1, t2, n_unaligned)) return rc;
+    const int rc = cmp_call(c, TextSource{text1, nullptr, n1}, TextSource{text2, nullptr, n2}, out, n_out, n_sites, status, t1, t2);
+    if (rc == 0 && *status == 0) *n_unaligned = c->cmp_unaligned;
+    return rc;
+}
+
+extern "C" int mc_bed_compare_lifted_file(mc_ctx *c, const char *path1, const char *path2, const mc_contig_table *t1, const mc_contig_table *t2,
+                                          const char **out, int64_t *n_out, int64_t *n_sites, int64_t *n_unaligned, int32_t *status) {
+    if (!c || !path1 || !path2 || !out || !n_out || !n_sites || !status) {
+        mc_set_error("mc_bed_compare_lifted_file: bad arguments");
+        return -12;
+    }
+    if (int rc = lifted_arguments("mc_bed_compare_lifted_file", c, t1, t2, n_unaligned)) return rc;
+    int64_t n1 = 0, n2 = 0;
+    if (int rc = regular_file_size("mc_bed_compare_lifted_file", path1, &n1)) return rc;
+    if (int rc = regular_file_size("mc_bed_compare_lifted_file", path2, &n2)) return rc;
+    const int rc = cmp_call(c, TextSource{nullptr, path1, n1}, TextSource{nullptr, path2, n2}, out, n_out, n_sites, status, t1, t2);
+    if (rc == 0 && *status == 0) *n_unaligned = c->cmp_unaligned;
+    return rc;
+}
+
+extern "C" int mc_xmfa_map_text(mc_ctx *c, const char *text, int64_t n, int32_t seq1, int32_t seq2, int64_t n1, int64_t n2,
+                                mc_xmfa_map_view *view, int32_t *status) {
+    if (!c || !status || n < 0 || (n > 0 && !text) || n1 < 0 || n2 < 0 || seq1 == seq2) { mc_set_error("mc_xmfa_map_text: bad arguments"); return -12; }
+    return xm_call(c, TextSource{text, nullptr, n}, seq1, seq2, n1, n2, view, status);
+}
+
+extern "C" int mc_xmfa_map_file(mc_ctx *c, const char *path, int32_t seq1, int32_t seq2, int64_t n1, int64_t n2, mc_xmfa_map_view *view,
+                                int32_t *status) {
+    if (!c || !path || !status || n1 < 0 || n2 < 0 || seq1 == seq2) { mc_set_error("mc_xmfa_map_file: bad arguments"); return -12; }
+    int64_t n = 0;
+    if (int rc = regular_file_size("mc_xmfa_map_file", path, &n)) return rc;
+    return xm_call(c, TextSource{nullptr, path, n}, seq1, seq2, n1, n2, view, status);
+}
+
+extern "C" int mc_xmfa_map_last_stats(mc_ctx *c, mc_xmfa_stats *out) {
+    if (!c || !out) { mc_set_error("mc_xmfa_map_last_stats: bad arguments"); return -12; }
+    *out = c->xmfa_stats;
+    return 0;
+}
+
+extern "C" int mc_xmfa_map_release(mc_ctx *c) {
+    if (!c) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipStreamSynchronize(c->up_stream));
+    xm_release(c);
+    c->xmfa_g2.reset(); c->xmfa_flip.reset();
+    c->text_stages.release();
+    return 0;
 }
 
 extern "C" int mc_bed_compare_last_stats(mc_ctx *c, mc_cmp_stats *out) {

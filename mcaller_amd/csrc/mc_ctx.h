@@ -324,6 +324,14 @@ struct mc_ctx {
     Pinned cmp_out;
     size_t cmp_out_cap = 0;
     mc_cmp_stats cmp_stats = {};
+    int64_t cmp_unaligned = 0;                    // (a lifted comparison) bed1's lines without an image
+    // ... the coordinate map of an XMFA alignment (compare/mc_xmfamap.inc): on the device from mc_xmfa_map_* until the next such
+    // call or mc_xmfa_map_release; map[g1] = ordinal << 33 | g2 << 1 | flip, ~0: unmapped.  The view's host copies are pinned
+    Pool xmfa_allocs{"alignment map"};
+    unsigned long long *xmfa_map = nullptr;
+    int64_t xmfa_n1 = 0, xmfa_n2 = 0;
+    Pinned xmfa_g2, xmfa_flip;
+    mc_xmfa_stats xmfa_stats = {};
     // ... the rows of the motif finder (motifs/mc_motifscan.hip)
     Pinned motif_out;
     size_t motif_out_cap = 0;

@@ -1,5 +1,6 @@
 // mc_textfeed.h -- what the six units that take whole text files through the GPU share on the host side (bed/mc_bedsum.hip,
-// train/mc_trainrows.hip, merge/mc_rowmerge.hip, fastq/mc_fastqual.hip, compare/mc_bedcompare.hip, motifs/mc_motifscan.hip).  Included by those six units only, hence the unnamed
+// train/mc_trainrows.hip, merge/mc_rowmerge.hip, fastq/mc_fastqual.hip, compare/mc_bedcompare.hip -- whose mc_xmfamap.inc sends an XMFA
+// alignment through the same feed, the seventh kind of file --, motifs/mc_motifscan.hip).  Included by those six units only, hence the unnamed
 // namespace: nothing here is linked across units.  An entry point refuses its arguments (-12), sizes its files
 // (regular_file_size), selects the device, and then
 //

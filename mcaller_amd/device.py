@@ -26,6 +26,20 @@ def _serialized(fn):
     return call
 
 
+def _contig_table(contigs):
+    """compare_genomes.read_fai's (names, lens, offs) as a mc_contig_table -> (the struct, what its pointers point at)."""
+    names, _, offs = contigs
+    ids = [name.encode('utf-8', 'surrogateescape') for name in names]
+    id_off = np.zeros(len(ids) + 1, dtype=np.int64)
+    id_off[1:] = np.cumsum([len(i) for i in ids], dtype=np.int64)
+    pool = np.frombuffer(b''.join(ids) + b'\0', dtype=np.uint8)
+    offs = np.ascontiguousarray(offs, dtype=np.int64)
+    t = _lib.ContigTable()
+    t.n_contigs = len(ids)
+    t.ids, t.id_off, t.off = _ptr(pool), _ptr(id_off), _ptr(offs)
+    return t, (pool, id_off, offs)
+
+
 class Device(object):
     def __init__(self, index=None):
         import threading
@@ -866,14 +880,32 @@ class Device(object):
 
     # ---- two --vo BED files compared per site (csrc/compare/mc_bedcompare.hip) ----
     @_serialized
-    def bed_compare(self, path1=None, path2=None, text1=None, text2=None):
+    def bed_compare(self, path1=None, path2=None, text1=None, text2=None, contigs1=None, contigs2=None):
         """The rows of compare_genomes for two `make_bed --vo` files (`path1`, `path2`) or their texts (`text1`, `text2`, bytes),
         made on the GPU -> (blob: bytes, n_sites, None), or (None, 0, reason) when the device declines: the caller runs the
-        host statement."""
+        host statement.  contigs1 / contigs2 (compare_genomes.read_fai's (names, lens, offs) of the two genomes): the comparison
+        through the alignment map that xmfa_map left in the context; bed_compare_last_unaligned() then says how many lines of
+        bed1 had no image."""
         if (path1 is None) != (path2 is None) or (text1 is None) != (text2 is None) or (path1 is None) == (text1 is None):
             raise ValueError('bed_compare: two paths or two texts')
+        if (contigs1 is None) != (contigs2 is None):
+            raise ValueError('bed_compare: the contigs of both genomes or of neither')
         out, n_out, n_sites, status = C.c_void_p(), C.c_int64(), C.c_int64(), C.c_int32()
-        if path1 is not None:
+        self._unaligned = None
+        if contigs1 is not None:
+            (t1, keep1), (t2, keep2) = _contig_table(contigs1), _contig_table(contigs2)
+            n_unaligned = C.c_int64()
+            if path1 is not None:
+                check(lib().mc_bed_compare_lifted_file(self._ctx, os.fsencode(path1), os.fsencode(path2), C.byref(t1), C.byref(t2),
+                                                       C.byref(out), C.byref(n_out), C.byref(n_sites), C.byref(n_unaligned), C.byref(status)))
+            else:
+                text1, text2 = bytes(text1), bytes(text2)
+                check(lib().mc_bed_compare_lifted_text(self._ctx, text1, len(text1), text2, len(text2), C.byref(t1), C.byref(t2),
+                                                       C.byref(out), C.byref(n_out), C.byref(n_sites), C.byref(n_unaligned), C.byref(status)))
+            del keep1, keep2
+            if status.value == 0:
+                self._unaligned = int(n_unaligned.value)
+        elif path1 is not None:
             check(lib().mc_bed_compare_file(self._ctx, os.fsencode(path1), os.fsencode(path2), C.byref(out), C.byref(n_out),
                                             C.byref(n_sites), C.byref(status)))
         else:
@@ -883,6 +915,45 @@ class Device(object):
         if status.value != 0:
             return None, 0, last_error()
         return (C.string_at(out.value, n_out.value) if n_out.value else b''), int(n_sites.value), None
+
+    def bed_compare_last_unaligned(self):
+        """bed1's lines without an image in the last bed_compare through an alignment (None: it declined, or had none)."""
+        return getattr(self, '_unaligned', None)
+
+    # ---- the coordinate map of a Mauve alignment (csrc/compare/mc_xmfamap.inc) ----
+    @_serialized
+    def xmfa_map(self, path=None, text=None, n1=0, seqs=(1, 2), n2=None, view=True):
+        """The map of an XMFA file (`path`, or its `text`, bytes) from genome seqs[0] (n1 bases) onto genome seqs[1] (n2 bases;
+        None: 2^31 - 2, no END is beyond it), built on the GPU and kept in the context for bed_compare(contigs1=, contigs2=)
+        -> (g2: int64 [n1 + 1], flip: uint8 [n1 + 1], None) -- copies; (None, None, None) with view=False --, or (None, None,
+        reason) when the device declines: no map is kept, compare_genomes' host statement words the error."""
+        if (path is None) == (text is None):
+            raise ValueError('xmfa_map: a path or a text')
+        v, status = _lib.XmfaMapView(), C.c_int32()
+        pv = C.byref(v) if view else None
+        n2 = (1 << 31) - 2 if n2 is None else int(n2)
+        if path is not None:
+            check(lib().mc_xmfa_map_file(self._ctx, os.fsencode(path), int(seqs[0]), int(seqs[1]), int(n1), n2, pv, C.byref(status)))
+        else:
+            text = bytes(text)
+            check(lib().mc_xmfa_map_text(self._ctx, text, len(text), int(seqs[0]), int(seqs[1]), int(n1), n2, pv, C.byref(status)))
+        if status.value != 0:
+            return None, None, last_error()
+        if not view:
+            return None, None, None
+        n = int(v.n1) + 1
+        return (np.ctypeslib.as_array(C.cast(v.g2, C.POINTER(C.c_int64)), shape=(n,)).copy(),
+                np.ctypeslib.as_array(C.cast(v.flip, C.POINTER(C.c_uint8)), shape=(n,)).copy(), None)
+
+    @_serialized
+    def xmfa_map_last_stats(self):
+        """Figures of the last xmfa_map: bytes, lines, entries, blocks, paired blocks, columns, mapped bases, the decline,
+        milliseconds."""
+        return self._last_stats(lib().mc_xmfa_map_last_stats, _lib.XmfaStats)
+
+    @_serialized
+    def xmfa_map_release(self):
+        check(lib().mc_xmfa_map_release(self._ctx))
 
     @_serialized
     def bed_compare_last_stats(self):
