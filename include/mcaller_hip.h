@@ -1053,6 +1053,24 @@ int mc_motif_report_text(mc_ctx *ctx, const mc_ref_view *ref, const char *bed, i
 int mc_motif_report_file(mc_ctx *ctx, const mc_ref_view *ref, const char *bed_path, const char *control_path_or_null,
                          const mc_motif_params *params, const char **out, int64_t *n_out, int64_t *n_rows, int32_t *status);
 int mc_motif_report_last_stats(mc_ctx *ctx, mc_motif_stats *out);
+/* --iupac: the rows merged into degenerate motifs (the definition: mcaller_amd/find_motifs.py; csrc/motifs/mc_motifiupac.inc).  The
+ * same arguments, declines and ownership of *out as above; a row is a maximal pure pattern, SPEC carries IUPAC letters.  Every
+ * table's purity lattice (15^(k-1) bytes) is resident during the call: lattice_bytes is what that adds to the plain call's need,
+ * counted against free device memory (MCALLER_MOTIF_DEVICE_BYTES) before anything is allocated -> MC_MOTIF_DECLINE_MEMORY.
+ * mc_motif_report_last_stats holds for these calls too (n_selected: maximal patterns over both thresholds). */
+typedef struct mc_motif_iupac_stats {
+    int64_t n_good;                /* concrete entries seen covered with nMethylated / nCovered >= min_fraction */
+    int64_t n_pure, n_maximal;     /* patterns whose members are all good; those no larger pure pattern holds   */
+    int64_t lattice_bytes;         /* good flags, lattices and the transform's two scratch blocks               */
+    int64_t decline_line;          /* as in mc_motif_stats                                                      */
+    int32_t decline_reason, decline_file;
+} mc_motif_iupac_stats;
+int mc_motif_report_iupac_text(mc_ctx *ctx, const mc_ref_view *ref, const char *bed, int64_t n_bed, const char *control_or_null,
+                               int64_t n_control, const mc_motif_params *params, const char **out, int64_t *n_out, int64_t *n_rows,
+                               int32_t *status);
+int mc_motif_report_iupac_file(mc_ctx *ctx, const mc_ref_view *ref, const char *bed_path, const char *control_path_or_null,
+                               const mc_motif_params *params, const char **out, int64_t *n_out, int64_t *n_rows, int32_t *status);
+int mc_motif_report_iupac_last_stats(mc_ctx *ctx, mc_motif_iupac_stats *out);
 int mc_motif_report_release(mc_ctx *ctx);
 
 /* ===== measurement plumbing: a table as nanopolish-eventalign text (13 columns), written by all host cores =====

@@ -55,6 +55,7 @@ XmfaMapView = _S['mc_xmfa_map_view']
 XmfaStats = _S['mc_xmfa_stats']
 MotifParams = _S['mc_motif_params']
 MotifStats = _S['mc_motif_stats']
+MotifIupacStats = _S['mc_motif_iupac_stats']
 Params = _S['mc_params']
 
 MOTIF_DECLINE = ABI.prefixed('MC_MOTIF_DECLINE_')

@@ -336,6 +336,7 @@ struct mc_ctx {
     Pinned motif_out;
     size_t motif_out_cap = 0;
     mc_motif_stats motif_stats = {};
+    mc_motif_iupac_stats motif_iupac_stats = {};
     // the figures of the last random-forest fit (mc_forest_fit.hip, through mc_internal_forest_stats)
     mc_forest_fit_stats forest_stats = {};
 };

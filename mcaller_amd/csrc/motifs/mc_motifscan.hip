@@ -46,6 +46,8 @@
 //                parent letter comes from), the parent's selected flag at the parent's key: set -> dropped.  Counts the survivors
 //   km_gather    the survivors' (entry, nGenome, nCovered, nMethylated) into a list, slots by atomicAdd: the host sorts them by
 //                the integer keys of the definition (they are few) and writes SPEC and the numbers with mc_rowtext.h
+//   --iupac      behind km_count, in place of km_select / km_keep / km_gather: mc_motifiupac.inc (C ABI: mc_motif_report_iupac_text /
+//                _file, mc_motif_report_iupac_last_stats)
 // No floating-point atomic anywhere; the counts are exact integers whatever the order of arrival.
 #include "../mc_textfeed.h"
 #include "../mc_rowtext.h"
@@ -75,6 +77,7 @@ struct MsTable {                             // a (shape, j)
     int32_t parent_lo, parent_hi;            // its parents in MsParent[]
     uint64_t idx[2];                         // byte i: where the letter under X i stands in the neighbourhood, '+' and '-'
     int8_t x[8];
+    uint64_t lat;                            // --iupac: its purity lattice begins here (mc_motifiupac.inc)
 };
 
 struct MsParent {
@@ -427,9 +430,24 @@ struct MsText {                              // the rows' bytes, built on the ho
     void put(char c) { s.push_back(c); }
 };
 
+// behind a row's SPEC: ':', the 1-based index of the called letter, the three counts and the fraction -> false: mc_rowtext.h does
+// not print the fraction
+bool ms_put_numbers(MsText &text, int o, uint32_t nG, uint32_t nC, uint32_t nM) {
+    text.put(':');
+    rt_put_uint(text, (uint32_t)(o + 1)); text.put('\t');
+    rt_put_uint(text, nG); text.put('\t');
+    rt_put_uint(text, nC); text.put('\t');
+    rt_put_uint(text, nM); text.put('\t');
+    if (!rt_put_repr(text, (double)nM / (double)nC)) return false;
+    text.put('\n');
+    return true;
+}
+
+#include "mc_motifiupac.inc"
+
 // Everything behind the uploads.  d_text[0, n): the bed's text, a newline if it lacked its last, the control's from off2 on; padded
-int ms_run(mc_ctx *c, Pool &pool, MsArgs &A, MsHead *d_head, const mc_motif_params &P, const std::vector<MsTable> &tables, const char **out,
-           int64_t *n_out, int64_t *n_rows, int32_t *status) {
+int ms_run(mc_ctx *c, Pool &pool, MsArgs &A, MsHead *d_head, const mc_motif_params &P, const std::vector<MsTable> &tables, bool iupac,
+           size_t scratch, const char **out, int64_t *n_out, int64_t *n_rows, int32_t *status) {
     mc_motif_stats &S = c->motif_stats;
     hipStream_t st = c->stream;
     MsHead h = {};
@@ -472,6 +490,10 @@ int ms_run(mc_ctx *c, Pool &pool, MsArgs &A, MsHead *d_head, const mc_motif_para
             ++S.n_tables_global;
         }
     }
+    if (iupac) {
+        HIP_TRY(hipGetLastError());
+        return mi_run(c, pool, A, P, tables, scratch, out, n_out, n_rows, status);
+    }
     hipLaunchKernelGGL(km_select, dim3(blocks(A.n_entries)), dim3(256), 0, st, A);
     hipLaunchKernelGGL(km_keep, dim3(blocks(A.n_entries)), dim3(256), 0, st, A);
     HIP_TRY(hipGetLastError());
@@ -512,13 +534,7 @@ int ms_run(mc_ctx *c, Pool &pool, MsArgs &A, MsHead *d_head, const mc_motif_para
             else { text.put("ACGT"[(key >> (2 * d)) & 3u]); --d; }
             ++x;
         }
-        text.put(':');
-        rt_put_uint(text, (uint32_t)(T.o + 1)); text.put('\t');
-        rt_put_uint(text, r.nG); text.put('\t');
-        rt_put_uint(text, r.nC); text.put('\t');
-        rt_put_uint(text, r.nM); text.put('\t');
-        if (!rt_put_repr(text, (double)r.nM / (double)r.nC)) return ms_decline(c, status, MC_MOTIF_DECLINE_PRINT, 0, -1);
-        text.put('\n');
+        if (!ms_put_numbers(text, T.o, r.nG, r.nC, r.nM)) return ms_decline(c, status, MC_MOTIF_DECLINE_PRINT, 0, -1);
     }
     if (int rc = grow(c->motif_out, c->motif_out_cap, text.s.size())) return rc;
     memcpy(c->motif_out.p, text.s.data(), text.s.size());
@@ -530,14 +546,15 @@ int ms_run(mc_ctx *c, Pool &pool, MsArgs &A, MsHead *d_head, const mc_motif_para
     return 0;
 }
 
-int ms_call(mc_ctx *c, const mc_ref_view *ref, const TextSource &s1, const TextSource *s2, const mc_motif_params *P, const char **out,
-            int64_t *n_out, int64_t *n_rows, int32_t *status) {
+int ms_call(mc_ctx *c, const mc_ref_view *ref, const TextSource &s1, const TextSource *s2, const mc_motif_params *P, bool iupac,
+            const char **out, int64_t *n_out, int64_t *n_rows, int32_t *status) {
     HIP_TRY(hipSetDevice(c->device));
     const auto t0 = std::chrono::steady_clock::now();
     mc_motif_stats &S = c->motif_stats;
     S = mc_motif_stats();
     S.decline_line = -1;
     S.n_bytes1 = s1.n; S.n_bytes2 = s2 ? s2->n : 0;
+    c->motif_iupac_stats = mc_motif_iupac_stats();
     *out = nullptr; *n_out = 0; *n_rows = 0; *status = 0;
     std::vector<MsTable> tables;
     std::vector<MsParent> parents;
@@ -569,7 +586,10 @@ int ms_call(mc_ctx *c, const mc_ref_view *ref, const TextSource &s1, const TextS
     S.table_slots = (int64_t)slots;
     const size_t need = (size_t)ref->n_seq_bytes + (size_t)n_words * 8 * 9 + (size_t)n_entries * 14 + (size_t)n_text + (size_t)id_bytes +
                         (size_t)NC * 32 + slots * 8 + parents.size() * sizeof(MsParent) + ((size_t)1 << 20);
-    if (!ms_fits(need)) return ms_decline(c, status, MC_MOTIF_DECLINE_MEMORY, 0, -1);
+    size_t scratch = 0;
+    const size_t need_iupac = iupac ? mi_need(tables, &scratch) : 0;    // (and the tables learn their places in the lattice block)
+    c->motif_iupac_stats.lattice_bytes = (int64_t)need_iupac;
+    if (!ms_fits(need + need_iupac)) return ms_decline(c, status, MC_MOTIF_DECLINE_MEMORY, 0, -1);
     Pool pool("motif finder");
     hipStream_t up = c->up_stream;
     MsArgs A = {};
@@ -633,7 +653,7 @@ int ms_call(mc_ctx *c, const mc_ref_view *ref, const TextSource &s1, const TextS
     A.keep = A.selected + n_entries;
     A.min_sites = P->min_sites; A.min_fraction = P->min_fraction;
     const auto t_kernels = std::chrono::steady_clock::now();
-    const int rc = ms_run(c, pool, A, d_head, *P, tables, out, n_out, n_rows, status);
+    const int rc = ms_run(c, pool, A, d_head, *P, tables, iupac, scratch, out, n_out, n_rows, status);
     (void)hipStreamSynchronize(c->stream);                             // (an early return: nothing of the pool is in use when it goes)
     S.ms_kernels = ms_since(t_kernels) - S.ms_d2h;                     // a declined call too: what ran until it declined
     if (rc != 0 || *status != 0) { *out = nullptr; *n_out = 0; *n_rows = 0; }
@@ -662,7 +682,7 @@ extern "C" int mc_motif_report_text(mc_ctx *c, const mc_ref_view *ref, const cha
         return -12;
     }
     const TextSource s1{bed, nullptr, n_bed}, s2{control, nullptr, n_control};
-    return ms_call(c, ref, s1, control ? &s2 : nullptr, params, out, n_out, n_rows, status);
+    return ms_call(c, ref, s1, control ? &s2 : nullptr, params, false, out, n_out, n_rows, status);
 }
 
 extern "C" int mc_motif_report_file(mc_ctx *c, const mc_ref_view *ref, const char *bed_path, const char *control_path,
@@ -676,12 +696,50 @@ extern "C" int mc_motif_report_file(mc_ctx *c, const mc_ref_view *ref, const cha
     if (control_path)
         if (int rc = regular_file_size("mc_motif_report_file", control_path, &n2)) return rc;
     const TextSource s1{nullptr, bed_path, n1}, s2{nullptr, control_path, n2};
-    return ms_call(c, ref, s1, control_path ? &s2 : nullptr, params, out, n_out, n_rows, status);
+    return ms_call(c, ref, s1, control_path ? &s2 : nullptr, params, false, out, n_out, n_rows, status);
 }
 
 extern "C" int mc_motif_report_last_stats(mc_ctx *c, mc_motif_stats *out) {
     if (!c || !out) { mc_set_error("mc_motif_report_last_stats: bad arguments"); return -12; }
     *out = c->motif_stats;
+    return 0;
+}
+
+// ---- --iupac: the same calls with the rows merged into degenerate motifs (mc_motifiupac.inc) ----
+static int mi_done(mc_ctx *c, int rc) {                               // the decline, if any, in the iupac stats too
+    mc_motif_iupac_stats &I = c->motif_iupac_stats;
+    I.decline_line = c->motif_stats.decline_line; I.decline_reason = c->motif_stats.decline_reason; I.decline_file = c->motif_stats.decline_file;
+    return rc;
+}
+
+extern "C" int mc_motif_report_iupac_text(mc_ctx *c, const mc_ref_view *ref, const char *bed, int64_t n_bed, const char *control,
+                                          int64_t n_control, const mc_motif_params *params, const char **out, int64_t *n_out, int64_t *n_rows,
+                                          int32_t *status) {
+    if (ms_bad_args(c, ref, params, out, n_out, n_rows, status) || n_bed < 0 || (n_bed > 0 && !bed) || n_control < 0) {
+        mc_set_error("mc_motif_report_iupac_text: bad arguments");
+        return -12;
+    }
+    const TextSource s1{bed, nullptr, n_bed}, s2{control, nullptr, n_control};
+    return mi_done(c, ms_call(c, ref, s1, control ? &s2 : nullptr, params, true, out, n_out, n_rows, status));
+}
+
+extern "C" int mc_motif_report_iupac_file(mc_ctx *c, const mc_ref_view *ref, const char *bed_path, const char *control_path,
+                                          const mc_motif_params *params, const char **out, int64_t *n_out, int64_t *n_rows, int32_t *status) {
+    if (ms_bad_args(c, ref, params, out, n_out, n_rows, status) || !bed_path) {
+        mc_set_error("mc_motif_report_iupac_file: bad arguments");
+        return -12;
+    }
+    int64_t n1 = 0, n2 = 0;
+    if (int rc = regular_file_size("mc_motif_report_iupac_file", bed_path, &n1)) return rc;
+    if (control_path)
+        if (int rc = regular_file_size("mc_motif_report_iupac_file", control_path, &n2)) return rc;
+    const TextSource s1{nullptr, bed_path, n1}, s2{nullptr, control_path, n2};
+    return mi_done(c, ms_call(c, ref, s1, control_path ? &s2 : nullptr, params, true, out, n_out, n_rows, status));
+}
+
+extern "C" int mc_motif_report_iupac_last_stats(mc_ctx *c, mc_motif_iupac_stats *out) {
+    if (!c || !out) { mc_set_error("mc_motif_report_iupac_last_stats: bad arguments"); return -12; }
+    *out = c->motif_iupac_stats;
     return 0;
 }
 

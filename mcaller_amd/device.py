@@ -967,10 +967,11 @@ class Device(object):
     # ---- methylated motifs from called sites (csrc/motifs/mc_motifscan.hip) ----
     @_serialized
     def motif_report(self, ref, path=None, control_path=None, text=None, control_text=None, base='A', shapes=('XXXX',), min_sites=20,
-                     min_fraction=0.5, keep_all=False):
+                     min_fraction=0.5, keep_all=False, iupac=False):
         """The rows of find_motifs for the reference `ref` ({id: upper-cased sequence}), the sites of a make_bed summary (`path`,
         or its `text`, bytes) and optionally a make_bed --control summary (`control_path` / `control_text`), made on the GPU ->
-        (blob: bytes, n_rows, None), or (None, 0, reason) when the device declines: the caller runs the host statement."""
+        (blob: bytes, n_rows, None), or (None, 0, reason) when the device declines: the caller runs the host statement.
+        iupac: the rows merged into degenerate motifs (find_motifs --iupac)."""
         if (path is None) == (text is None) or (path is None and control_path is not None) or (text is None and control_text is not None):
             raise ValueError('motif_report: paths or texts')
         ids = [name.encode('latin-1', 'replace') for name in ref]
@@ -996,14 +997,22 @@ class Device(object):
         P.min_sites, P.min_fraction, P.keep_all = int(min_sites), float(min_fraction), int(bool(keep_all))
         P.contig_ids, P.contig_id_off = _ptr(id_pool), _ptr(id_off)
         out, n_out, n_rows, status = C.c_void_p(), C.c_int64(), C.c_int64(), C.c_int32()
-        if path is not None:
+        if path is not None and iupac:
+            check(lib().mc_motif_report_iupac_file(self._ctx, C.byref(v), os.fsencode(path), None if control_path is None else os.fsencode(control_path),
+                                                   C.byref(P), C.byref(out), C.byref(n_out), C.byref(n_rows), C.byref(status)))
+        elif path is not None:
             check(lib().mc_motif_report_file(self._ctx, C.byref(v), os.fsencode(path), None if control_path is None else os.fsencode(control_path),
                                              C.byref(P), C.byref(out), C.byref(n_out), C.byref(n_rows), C.byref(status)))
         else:
             text = bytes(text)
             control_text = None if control_text is None else bytes(control_text)
-            check(lib().mc_motif_report_text(self._ctx, C.byref(v), text, len(text), control_text, 0 if control_text is None else len(control_text),
-                                             C.byref(P), C.byref(out), C.byref(n_out), C.byref(n_rows), C.byref(status)))
+            n_control = 0 if control_text is None else len(control_text)
+            if iupac:
+                check(lib().mc_motif_report_iupac_text(self._ctx, C.byref(v), text, len(text), control_text, n_control, C.byref(P), C.byref(out),
+                                                       C.byref(n_out), C.byref(n_rows), C.byref(status)))
+            else:
+                check(lib().mc_motif_report_text(self._ctx, C.byref(v), text, len(text), control_text, n_control, C.byref(P), C.byref(out),
+                                                 C.byref(n_out), C.byref(n_rows), C.byref(status)))
         if status.value != 0:
             return None, 0, last_error()
         return (C.string_at(out.value, n_out.value) if n_out.value else b''), int(n_rows.value), None
@@ -1013,6 +1022,11 @@ class Device(object):
         """Figures of the last motif_report: bytes, lines, candidates and sites, selected entries and rows, the stretch and the tables'
         placements, the decline, milliseconds."""
         return self._last_stats(lib().mc_motif_report_last_stats, _lib.MotifStats)
+
+    @_serialized
+    def motif_report_iupac_last_stats(self):
+        """Figures of the last motif_report(iupac=True): good entries, pure and maximal patterns, the lattices' bytes, the decline."""
+        return self._last_stats(lib().mc_motif_report_iupac_last_stats, _lib.MotifIupacStats)
 
     @_serialized
     def motif_report_release(self):

@@ -1,7 +1,7 @@
 """Find methylated motifs de novo from called sites: which short sequence patterns around the called base are mostly methylated?
 
     python -m mcaller_amd.find_motifs -r ref.fasta --bed SUMMARY.bed [--control CONTROL.bed] [-b A] [--shapes LIST]
-                                      [--min_sites 20] [--min_fraction 0.5] [--all] [-o OUT] [--device]
+                                      [--min_sites 20] [--min_fraction 0.5] [--all] [--iupac] [-o OUT] [--device]
 
 The reference has no such program: its GFF output and `make_bed --control` are shaped for an external motif finder.  This module
 closes the loop: every row it prints is a motif in the syntax `--motifs` parses (refmark.parse_motifs).
@@ -29,12 +29,32 @@ One line per row: SPEC, nGenome, nCovered, nMethylated, fraction, tab-separated.
 descending (sites explained, not fraction: a 5-of-5 noise window does not beat GATC at 423 of 423), then fraction descending, then
 shape index, j and the letters.
 
-Out of scope: merging rows into IUPAC letters (GANTC shows as its four 5-mers), iterative removal of explained sites, circular
-contigs.
+--iupac merges rows into degenerate motifs: GANTC is one row, not its four 5-mers, each of which may miss --min_sites alone.
+Per table (shape, j), from the same three counters:
+  GOOD      a concrete entry with nCovered >= 1 and float64(nMethylated) / float64(nCovered) >= min_fraction.  An entry that was
+            never seen covered vouches for nothing and is not good.
+  PATTERN   the called X holds --base, every other X a non-empty subset of ACGT: one of the 15 IUPAC letters
+            A C G T R Y S W K M B D H V N, coded as the bit mask A = 1, C = 2, G = 4, T = 8.  Its MEMBERS are the concrete entries
+            of the product of its sets, its counts the integer sums of its members' counts.
+  PURE      every member is good.  (A sub-pattern of a pure pattern is pure.)
+  MAXIMAL   pure, and no pattern made by adding one letter to one X's set is pure -- by the closure above: no strictly larger
+            pattern is pure.
+A row is a maximal pure pattern with summed nMethylated >= min_sites and float64(nMethylated) / float64(nCovered) >= min_fraction
+(the division stays: the mediant of the members' fractions is not trusted to survive rounding).  Without --all a row is dropped when,
+for some table whose X positions relative to the called base are a strict subset of this table's, the row's pattern restricted to
+those positions is pure in that table -- that table then has a row which covers every occurrence of this one: GATCN:2 of XXXXX is
+dropped for GATC:2, GANTC:2 is not, because GANT is not pure.  The line is as above, SPEC with the IUPAC letter of each X's set and
+N under every '.'; the order is nMethylated descending, fraction descending, shape index, j, then the masks of the X from left to
+right as integers.  Every concrete row of the plain mode is a pure singleton and so contained in some row of --iupac (before the
+redundancy rule): the option loses nothing.  `last_counts` gains n_good, n_pure and n_maximal, summed over the tables; n_selected
+counts the rows before the redundancy rule.  The host statement builds a table's lattice only inside the box of the letters that
+occur, per X, among its good entries (every pure pattern lies in it), not all 15^(k-1) patterns.
+
+Out of scope: iterative removal of explained sites, circular contigs.
 
 `find_motifs` is that definition in NumPy (the host statement; no SciPy, no GPU).  `find_motifs_device` (--device) has the GPU make
-the same bytes (Device.motif_report: csrc/motifs/mc_motifscan.hip) and runs the host statement whenever the device declines;
-`last_report` says who made the output, `last_counts` what the host statement counted."""
+the same bytes (Device.motif_report: csrc/motifs/mc_motifscan.hip, --iupac: csrc/motifs/mc_motifiupac.inc) and runs the host
+statement whenever the device declines; `last_report` says who made the output, `last_counts` what the host statement counted."""
 import os
 import sys
 
@@ -44,6 +64,7 @@ from . import refmark
 
 last_report = None         # what the last call did: dict(by='device' | 'host', reason=None | str, n_rows=int)
 last_counts = None         # the host statement's figures: dict(n_candidates, n_sites, n_control, n_off_base, n_selected)
+                           # and, with iupac, n_good, n_pure, n_maximal
 
 MAX_WIDTH = 24
 MAX_SHAPES = 64            # what the device takes in one call (the host statement has no limit)
@@ -141,9 +162,11 @@ def _letters(code, k):
     return ''.join('ACGT'[(code >> (2 * (k - 1 - i))) & 3] for i in range(k))
 
 
-def report_rows(ref, shapes, base, meth, control, min_sites=20, min_fraction=0.5, keep_all=False):
+def report_rows(ref, shapes, base, meth, control, min_sites=20, min_fraction=0.5, keep_all=False, iupac=False):
     """The rows of the definition as bytes, their number, and the counts."""
     tables, counts = count_tables(ref, shapes, base, meth, control)
+    if iupac:
+        return _iupac_rows(tables, counts, shapes, base, min_sites, min_fraction, keep_all)
     selected = []            # (nM, fraction, shape index, j, letters, nG, nC)
     for si, shape in enumerate(shapes):
         k = shape.count('X')
@@ -183,6 +206,98 @@ def report_rows(ref, shapes, base, meth, control, min_sites=20, min_fraction=0.5
     return ''.join(out).encode('ascii'), len(out), counts
 
 
+IUPAC_LETTER = ' ACMGRSVTWYHKDBN'            # the letter of a set over A = 1, C = 2, G = 4, T = 8
+
+
+def _lattice(good):
+    """good: bool [4] * n over the letters of the free X -> (box, pure, maximal) or None where nothing is good.  box[i]: the letter
+    codes that occur at free X i among the good entries, ascending; pure and maximal: bool [2 ** len(box[i]) - 1 for i], index
+    s - 1 at X i is the set of box[i][l] for the bits l of s.  Every pure pattern lies in the box, so nothing outside is built."""
+    n = good.ndim
+    box = [np.nonzero(good.any(axis=tuple(a for a in range(n) if a != i)))[0] for i in range(n)]
+    if not len(box[0]):
+        return None
+    pure = good[np.ix_(*box)]
+    for i in range(n):                           # the AND transform, one X at a time: 4 letters -> their non-empty sets
+        b = len(box[i])
+        pure = np.stack([np.logical_and.reduce(pure.take([l for l in range(b) if sub >> l & 1], axis=i), axis=i) for sub in range(1, 2 ** b)], axis=i)
+    maximal = pure.copy()
+    for i in range(n):                           # (a letter from outside the box never keeps a pattern pure)
+        subs = np.arange(1, 2 ** len(box[i]))
+        along = [1] * n
+        along[i] = -1
+        for l in range(len(box[i])):
+            grown = subs | (1 << l)
+            maximal &= ~(pure.take(grown - 1, axis=i) & (grown != subs).reshape(along))
+    return box, pure, maximal
+
+
+def _iupac_rows(tables, counts, shapes, base, min_sites, min_fraction, keep_all):
+    """report_rows for --iupac: the maximal pure patterns of every table over both thresholds, less those a smaller table explains."""
+    b = 'ACGT'.index(base)
+    offsets = [[i for i, ch in enumerate(s) if ch == 'X'] for s in shapes]
+    lattices = {}                                # (shape index, j) -> _lattice of the table
+    selected = []                                # (nM, fraction, shape index, j, masks of the X, nG, nC)
+    counts.update(n_good=0, n_pure=0, n_maximal=0)
+    for si, shape in enumerate(shapes):
+        k = shape.count('X')
+        for j in range(k):
+            nG, nC, nM = (a.reshape((4,) * k).take(b, axis=j) for a in tables[si][j])
+            with np.errstate(all='ignore'):
+                good = (nC >= 1) & (nM.astype(np.float64) / nC.astype(np.float64) >= np.float64(min_fraction))
+            counts['n_good'] += int(good.sum())
+            lat = lattices[si, j] = _lattice(good)
+            if lat is None:
+                continue
+            box, pure, maximal = lat
+            counts['n_pure'] += int(pure.sum())
+            counts['n_maximal'] += int(maximal.sum())
+            for at in np.argwhere(maximal).tolist():
+                members = [[int(box[i][l]) for l in range(len(box[i])) if (s + 1) >> l & 1] for i, s in enumerate(at)]
+                cells = np.ix_(*members)
+                sums = [int(a[cells].sum()) for a in (nG, nC, nM)]
+                frac = np.float64(sums[2]) / np.float64(sums[1])         # (a pure pattern's members are covered: no 0 / 0)
+                if sums[2] >= min_sites and frac >= np.float64(min_fraction):
+                    masks = [sum(1 << c for c in m) for m in members]
+                    masks.insert(j, 1 << b)
+                    selected.append((sums[2], float(frac), si, j, tuple(masks), sums[0], sums[1]))
+    counts['n_selected'] = len(selected)
+
+    def is_pure(si, j, masks):                   # masks of the free X of table (si, j)
+        lat = lattices[si, j]
+        if lat is None:
+            return False
+        at = []
+        for letters, mask in zip(lat[0], masks):
+            local = sum(1 << l for l, c in enumerate(letters.tolist()) if mask >> c & 1)
+            if local == 0 or (sum(1 << c for c in letters.tolist()) & mask) != mask:       # a letter from outside the box
+                return False
+            at.append(local - 1)
+        return bool(lat[1][tuple(at)])
+    if not keep_all:
+        kept = []
+        for row in selected:
+            si, j, masks = row[2], row[3], row[4]
+            mine = {x - offsets[si][j]: m for x, m in zip(offsets[si], masks)}
+            redundant = False
+            for ui in range(len(shapes)):
+                for uj in range(len(offsets[ui])):
+                    theirs = [x - offsets[ui][uj] for x in offsets[ui]]
+                    if len(theirs) < len(mine) and all(r in mine for r in theirs):
+                        redundant = redundant or is_pure(ui, uj, [mine[r] for r in theirs if r != 0])
+            if not redundant:
+                kept.append(row)
+        selected = kept
+    selected.sort(key=lambda r: (-r[0], -r[1], r[2], r[3], r[4]))
+    out = []
+    for nM, frac, si, j, masks, nG, nC in selected:
+        window, it = [], iter(masks)
+        for ch in shapes[si]:
+            window.append(IUPAC_LETTER[next(it)] if ch == 'X' else 'N')
+        out.append('%s:%d\t%d\t%d\t%d\t%s\n' % (''.join(window), offsets[si][j] + 1, nG, nC, nM, repr(frac)))
+    return ''.join(out).encode('ascii'), len(out), counts
+
+
 def _write(out, data):
     """data (bytes) to `out`: None is stdout, a str a path, anything else a file object."""
     if isinstance(out, (str, os.PathLike)):
@@ -213,26 +328,27 @@ def _checked(base, shapes, min_sites, min_fraction):
     return base, shapes, min_sites, min_fraction
 
 
-def _host(reference, bed, control, base, shapes, min_sites, min_fraction, keep_all, out, reason):
+def _host(reference, bed, control, base, shapes, min_sites, min_fraction, keep_all, out, reason, iupac=False):
     global last_report, last_counts
     last_report = last_counts = None
     ref = read_reference(reference)
     meth = read_sites(bed, ref)
     ctl = None if control is None else read_sites(control, ref)
-    data, n_rows, counts = report_rows(ref, shapes, base, meth, ctl, min_sites, min_fraction, keep_all)
+    data, n_rows, counts = report_rows(ref, shapes, base, meth, ctl, min_sites, min_fraction, keep_all, iupac)
     _write(out, data)
     last_counts = counts
     last_report = dict(by='host', reason=reason, n_rows=n_rows)
     return n_rows
 
 
-def find_motifs(reference, bed, control=None, base='A', shapes=None, min_sites=20, min_fraction=0.5, keep_all=False, out=None):
+def find_motifs(reference, bed, control=None, base='A', shapes=None, min_sites=20, min_fraction=0.5, keep_all=False, out=None, iupac=False):
     """The host statement: the definition above in NumPy -> the number of rows."""
     base, shapes, min_sites, min_fraction = _checked(base, shapes, min_sites, min_fraction)
-    return _host(reference, bed, control, base, shapes, min_sites, min_fraction, keep_all, out, 'the host statement was asked for')
+    return _host(reference, bed, control, base, shapes, min_sites, min_fraction, keep_all, out, 'the host statement was asked for', iupac)
 
 
-def find_motifs_device(reference, bed, control=None, base='A', shapes=None, min_sites=20, min_fraction=0.5, keep_all=False, out=None):
+def find_motifs_device(reference, bed, control=None, base='A', shapes=None, min_sites=20, min_fraction=0.5, keep_all=False, out=None,
+                        iupac=False):
     """The same bytes made on the GPU, or -- when the device declines -- by the host statement, which also words the errors."""
     global last_report, last_counts
     base, shapes, min_sites, min_fraction = _checked(base, shapes, min_sites, min_fraction)
@@ -243,12 +359,12 @@ def find_motifs_device(reference, bed, control=None, base='A', shapes=None, min_
         from .device import get_device
         ref = read_reference(reference)
         blob, n_rows, reason = get_device().motif_report(ref, path=bed, control_path=control, base=base, shapes=shapes, min_sites=min_sites,
-                                                         min_fraction=min_fraction, keep_all=keep_all)
+                                                         min_fraction=min_fraction, keep_all=keep_all, iupac=iupac)
         if blob is not None:
             _write(out, blob)
             last_report = dict(by='device', reason=None, n_rows=n_rows)
             return n_rows
-    return _host(reference, bed, control, base, shapes, min_sites, min_fraction, keep_all, out, reason)
+    return _host(reference, bed, control, base, shapes, min_sites, min_fraction, keep_all, out, reason, iupac)
 
 
 def main(argv=None):
@@ -264,6 +380,7 @@ def main(argv=None):
     parser.add_argument('--min_fraction', type=float, required=False, default=0.5,
                         help='methylated / covered occurrences a row needs (default: 0.5)')
     parser.add_argument('--all', action='store_true', required=False, help='keep rows that a shorter selected row explains')
+    parser.add_argument('--iupac', action='store_true', required=False, help='merge rows into degenerate (IUPAC) motifs')
     parser.add_argument('-o', '--output', type=str, required=False, help='write the rows to this file (default: standard output)')
     parser.add_argument('--device', action='store_true', required=False, help='count on the GPU (the host statement runs when it declines)')
     args = parser.parse_args(argv)
@@ -273,7 +390,8 @@ def main(argv=None):
     assert args.control is None or os.path.isfile(args.control), 'file not found at ' + args.control
 
     run = find_motifs_device if args.device else find_motifs
-    return run(args.reference, args.bed, args.control, args.base, args.shapes, args.min_sites, args.min_fraction, args.all, args.output)
+    return run(args.reference, args.bed, args.control, args.base, args.shapes, args.min_sites, args.min_fraction, args.all, args.output,
+               args.iupac)
 
 
 if __name__ == '__main__':

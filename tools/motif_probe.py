@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """tools/motif_probe.py [--bases 4.6e6] [--runs 3] [--host-runs 1] [--json profiles/motif_probe.json]
                        [--kernel-stats profiles/motif_kernel_stats.csv] [--keep DIR] [--device-only] [--host-only] [--seed 7]
+                       [--iupac]
 
 A reference and two make_bed summaries to the rows of find_motifs, host statement against device, file to file on the same box:
   host    find_motifs.find_motifs          (NumPy)
@@ -11,6 +12,12 @@ host's byte for byte.  A call the device declines is recorded with its reason an
 The genome: --bases random bases on one contig with AACNNNNNNGTGC planted every ~8000 bases.  Methylated: the A of every GATC
 and the second A of every AACNNNNNNGTGC, on both strands; 90 % of all candidates are covered, 1 % of the covered others are false
 calls.  The first rows must be GATC:2 and AACNNNNNNGTGC:2.
+--iupac: the same two legs with find_motifs --iupac (csrc/motifs/mc_motifiupac.inc).  GANTC and CAAYNNNNNRTAC are planted beside
+the others, each every ~8000 bases with random letters under its degenerate positions, and the A of every GANTC and the second A
+of every CAAYNNNNNRTAC are methylated too; the first rows (in the result) hold GANTC:2, GATC:2 and AACNNNNNNGTGC:2, and
+CAAYNNNNNRTAC as the rows of the seven-letter shapes that explain it (CAANNNNNNRTAC:3, CAAYNNNNNNTAC:3).  Meant to be
+run with --host-runs 3 --json profiles/motif_iupac_probe.json --kernel-stats profiles/motif_iupac_kernel_stats.csv; the stats of
+mc_motif_report_iupac_last_stats go into the result.
 --host-only needs no GPU.  --kernel-stats: the kernels' times from a `rocprofv3 --kernel-trace --stats` run of this tool's own
 (--device-only), the program behind `--`, under its own time limit."""
 import glob
@@ -26,6 +33,8 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 BIPARTITE = 'AACNNNNNNGTGC'
+DEGENERATE = ('GANTC', 'CAAYNNNNNRTAC')        # --iupac plants these too
+SETS = {'A': 'A', 'C': 'C', 'G': 'G', 'T': 'T', 'R': 'AG', 'Y': 'CT', 'N': 'ACGT'}
 
 
 def arg(name, default):
@@ -34,17 +43,17 @@ def arg(name, default):
 
 
 def occurrences(seq, motif):
-    """Starts of `motif` (N: any letter) in the uint8 array seq."""
+    """Starts of `motif` (letters of SETS; N: any letter) in the uint8 array seq."""
     import numpy as np
     n = len(seq) - len(motif) + 1
     hit = np.ones(n, dtype=bool)
     for i, ch in enumerate(motif):
         if ch != 'N':
-            hit &= seq[i:i + n] == ord(ch)
+            hit &= np.isin(seq[i:i + n], [ord(c) for c in SETS[ch]])
     return np.nonzero(hit)[0]
 
 
-def write_case(d, n_bases, seed):
+def write_case(d, n_bases, seed, iupac=False):
     """-> (reference, bed, control paths, dict of figures)."""
     import numpy as np
     rng = np.random.default_rng(seed)
@@ -53,12 +62,27 @@ def write_case(d, n_bases, seed):
     for at in range(4000, n_bases - 100, 8000):
         for i, c in fixed:
             seq[at + i] = c
+    if iupac:
+        letters = np.frombuffer(b'ACGT', dtype=np.uint8)
+        for motif, first in zip(DEGENERATE, (1000, 6000)):
+            for at in range(first, n_bases - 100, 8000):
+                for i, ch in enumerate(motif):
+                    if ch != 'N':
+                        seq[at + i] = ord(SETS[ch][rng.integers(0, len(SETS[ch]))]) if len(SETS[ch]) > 1 else ord(ch)
+                    else:
+                        seq[at + i] = letters[rng.integers(0, 4)]
     meth = np.zeros((2, n_bases), dtype=bool)                 # [strand][position]
     gatc = occurrences(seq, 'GATC')
     meth[0, gatc + 1] = True
     meth[1, gatc + 2] = True                                  # GATC is its own reverse complement: the T at +2 is the A of '-'
     meth[0, occurrences(seq, BIPARTITE) + 1] = True
     meth[1, occurrences(seq, 'GCACNNNNNNGTT') + 11] = True      # the motif on '-': its second A is the T at +11 of the reverse complement
+    if iupac:
+        gantc = occurrences(seq, 'GANTC')                     # its own reverse complement: the T at +3 is the A of '-'
+        meth[0, gantc + 1] = True
+        meth[1, gantc + 3] = True
+        meth[0, occurrences(seq, 'CAAYNNNNNRTAC') + 2] = True
+        meth[1, occurrences(seq, 'GTAYNNNNNRTTG') + 10] = True  # on '-': its second A is the T at +10 of the reverse complement
     cand = np.stack([seq == ord('A'), seq == ord('T')])
     covered = cand & (rng.random((2, n_bases)) < 0.9)
     called = covered & (meth | (rng.random((2, n_bases)) < 0.01))
@@ -75,12 +99,13 @@ def write_case(d, n_bases, seed):
                                bed_bytes=os.path.getsize(bed), control_bytes=os.path.getsize(ctl))
 
 
-def kernel_stats(out_csv, n_bases, seed):
+def kernel_stats(out_csv, n_bases, seed, iupac=False):
     """The kernels' times of the device path alone, from a rocprofv3 run of this tool in a process of its own."""
     d = tempfile.mkdtemp(prefix='mc_motif_stats_')
     try:
         cmd = ['timeout', '-k', '10', '600', 'rocprofv3', '--kernel-trace', '--stats', '--output-format', 'csv', '-d', d, '--', sys.executable,
                os.path.abspath(__file__), '--device-only', '--bases', str(n_bases), '--runs', '2', '--seed', str(seed)]
+        cmd += ['--iupac'] if iupac else []
         subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL)
         found = glob.glob(os.path.join(d, '**', '*kernel_stats.csv'), recursive=True)
         if not found:
@@ -94,17 +119,18 @@ def main():
     from mcaller_amd import _lib, find_motifs
     n_bases = int(float(arg('--bases', '4.6e6')))
     runs, host_runs, seed = int(arg('--runs', '3')), int(arg('--host-runs', '1')), int(arg('--seed', '7'))
-    device_only, host_only = '--device-only' in sys.argv, '--host-only' in sys.argv
+    device_only, host_only, iupac = '--device-only' in sys.argv, '--host-only' in sys.argv, '--iupac' in sys.argv
     d = arg('--keep', None) or tempfile.mkdtemp(prefix='mc_motif_probe_')
     os.makedirs(d, exist_ok=True)
-    ref, bed, ctl, r = write_case(d, n_bases, seed)
+    ref, bed, ctl, r = write_case(d, n_bases, seed, iupac)
+    r['iupac'] = iupac
     out_d, out_h = os.path.join(d, 'device.tsv'), os.path.join(d, 'host.tsv')
     r['host_cores'] = int(_lib.lib().mc_host_cores())
     if not host_only:
         from mcaller_amd.device import get_device
 
         def device():
-            find_motifs.find_motifs_device(ref, bed, ctl, out=out_d)
+            find_motifs.find_motifs_device(ref, bed, ctl, out=out_d, iupac=iupac)
             return find_motifs.last_report
 
         who = device()                                          # warm-up: pinned blocks, the first launches, the files in the page cache
@@ -118,12 +144,14 @@ def main():
                 t_dev.append(time.perf_counter() - t)
                 st = get_device().motif_report_last_stats()
             r.update(device_s=statistics.median(t_dev), device_all_s=t_dev, device_runs=runs, stats=st, kernel_ms=st['ms_kernels'],
-                     first_rows=open(out_d).read().splitlines()[:4])
+                     first_rows=open(out_d).read().splitlines()[:6 if iupac else 4])
+            if iupac:
+                r.update(iupac_stats=get_device().motif_report_iupac_last_stats())
     if not device_only:
         t_host = []
         for _ in range(host_runs):
             t = time.perf_counter()
-            find_motifs.find_motifs(ref, bed, ctl, out=out_h)
+            find_motifs.find_motifs(ref, bed, ctl, out=out_h, iupac=iupac)
             t_host.append(time.perf_counter() - t)
         r.update(host_s=statistics.median(t_host), host_all_s=t_host, host_runs=host_runs)
         if 'device_s' in r:
@@ -139,7 +167,7 @@ def main():
     if stats_csv and not device_only and not host_only:
         from mcaller_amd.device import get_device
         get_device().motif_report_release()
-        kernel_stats(stats_csv, n_bases, seed)
+        kernel_stats(stats_csv, n_bases, seed, iupac)
     if not arg('--keep', None):
         shutil.rmtree(d, ignore_errors=True)
 
