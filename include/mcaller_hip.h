@@ -1071,6 +1071,37 @@ int mc_motif_report_iupac_text(mc_ctx *ctx, const mc_ref_view *ref, const char *
 int mc_motif_report_iupac_file(mc_ctx *ctx, const mc_ref_view *ref, const char *bed_path, const char *control_path_or_null,
                                const mc_motif_params *params, const char **out, int64_t *n_out, int64_t *n_rows, int32_t *status);
 int mc_motif_report_iupac_last_stats(mc_ctx *ctx, mc_motif_iupac_stats *out);
+/* --iterative: the motifs peeled off one at a time (the definition: mcaller_amd/find_motifs.py; csrc/motifs/mc_motifiter.inc).  The
+ * same arguments, declines and ownership of *out as above, and iupac (0: concrete rows, 1: degenerate ones) and max_motifs (1 ..
+ * MC_MOTIF_MAX_ROUNDS).  Round 1 is the call above; every later round takes the candidates the printed row explains out of the
+ * candidate planes and out of every table's counters and selects again: planes, tables and lattices stay on the device for the
+ * whole call.  The list of a round's explained candidates (list_bytes: 8 bytes a base) is counted against free device memory
+ * (MCALLER_MOTIF_DEVICE_BYTES) before anything is allocated -> MC_MOTIF_DECLINE_MEMORY.  mc_motif_report_last_stats and
+ * mc_motif_report_iupac_last_stats hold the figures of round 1 (n_rows and n_out_bytes: of what is handed out). */
+#define MC_MOTIF_MAX_ROUNDS 64
+typedef struct mc_motif_iter_stats {
+    int64_t n_rounds;              /* rows printed                                                              */
+    int64_t n_explained[MC_MOTIF_MAX_ROUNDS];      /* candidates row r explains: its nGenome                    */
+    int64_t n_unexplained;         /* methylated candidates left after the last round                           */
+    int64_t list_bytes;            /* the list of a round's explained candidates                                */
+    int64_t need_bytes;            /* all the call counted against free device memory before it allocated       */
+    int64_t decline_line;          /* as in mc_motif_stats                                                      */
+    int32_t decline_reason, decline_file;
+    double ms_first_round;         /* from the first kernel to the first row: the plain call's ms_kernels       */
+    double ms_later_rounds;        /* all later rounds together, the explain step of the round before included  */
+} mc_motif_iter_stats;
+int mc_motif_report_iter_text(mc_ctx *ctx, const mc_ref_view *ref, const char *bed, int64_t n_bed, const char *control_or_null,
+                              int64_t n_control, const mc_motif_params *params, int32_t iupac, int32_t max_motifs, const char **out,
+                              int64_t *n_out, int64_t *n_rows, int32_t *status);
+int mc_motif_report_iter_file(mc_ctx *ctx, const mc_ref_view *ref, const char *bed_path, const char *control_path_or_null,
+                              const mc_motif_params *params, int32_t iupac, int32_t max_motifs, const char **out, int64_t *n_out,
+                              int64_t *n_rows, int32_t *status);
+int mc_motif_report_iter_last_stats(mc_ctx *ctx, mc_motif_iter_stats *out);
+/* The methylated candidates the last mc_motif_report_iter_* call left unexplained, as two bit planes of n_words 64-bit words in
+ * pinned memory owned by the context ('+' and '-'; bit i of word w: base index 64 w + i), and contig_start[c], the base index of
+ * contig c's first base (n_contigs entries).  Valid until the next mc_motif_report_* call; all null / 0 after a decline. */
+int mc_motif_report_iter_left(mc_ctx *ctx, const uint64_t **plus, const uint64_t **minus, int64_t *n_words, const int64_t **contig_start,
+                              int32_t *n_contigs);
 int mc_motif_report_release(mc_ctx *ctx);
 
 /* ===== measurement plumbing: a table as nanopolish-eventalign text (13 columns), written by all host cores =====

@@ -56,6 +56,7 @@ XmfaStats = _S['mc_xmfa_stats']
 MotifParams = _S['mc_motif_params']
 MotifStats = _S['mc_motif_stats']
 MotifIupacStats = _S['mc_motif_iupac_stats']
+MotifIterStats = _S['mc_motif_iter_stats']
 Params = _S['mc_params']
 
 MOTIF_DECLINE = ABI.prefixed('MC_MOTIF_DECLINE_')

@@ -337,6 +337,12 @@ struct mc_ctx {
     size_t motif_out_cap = 0;
     mc_motif_stats motif_stats = {};
     mc_motif_iupac_stats motif_iupac_stats = {};
+    // ... --iterative (motifs/mc_motifiter.inc): the left-over sites' two planes, '+' then '-', and where the contigs stand in them
+    Pinned motif_left;
+    size_t motif_left_cap = 0;
+    int64_t motif_left_words = 0;
+    std::vector<int64_t> motif_left_starts;
+    mc_motif_iter_stats motif_iter_stats = {};
     // the figures of the last random-forest fit (mc_forest_fit.hip, through mc_internal_forest_stats)
     mc_forest_fit_stats forest_stats = {};
 };

@@ -203,23 +203,37 @@ inline size_t mi_need(std::vector<MsTable> &tables, size_t *scratch) {
     return lat + 2 * *scratch + entries;
 }
 
-// Everything behind km_count.  A.nG / nC / nM hold the counts of every table; `tables` carry their places in the lattice block
-int mi_run(mc_ctx *c, Pool &pool, const MsArgs &A, const mc_motif_params &P, const std::vector<MsTable> &tables, size_t scratch,
-           const char **out, int64_t *n_out, int64_t *n_rows, int32_t *status) {
-    mc_motif_stats &S = c->motif_stats;
-    mc_motif_iupac_stats &I = c->motif_iupac_stats;
-    hipStream_t st = c->stream;
+struct MiState {                             // what a call keeps on the device behind km_count, allocated once
     MiArgs M = {};
+    uint8_t *tmp[2] = {nullptr, nullptr};
+    int64_t cap_pats = 0;
+};
+
+// A.nG / nC / nM hold the counts of every table; `tables` carry their places in the lattice block
+int mi_setup(Pool &pool, const MsArgs &A, const std::vector<MsTable> &tables, size_t scratch, MiState &mi) {
+    MiArgs &M = mi.M;
     M.tables = A.tables; M.parents = A.parents;
     M.nG = A.nG; M.nC = A.has_control ? A.nC : A.nG; M.nM = A.nM;
     M.n_entries = A.n_entries; M.min_sites = A.min_sites; M.min_fraction = A.min_fraction; M.keep_all = A.keep_all;
     const size_t n_lat = tables.back().lat + mi_pow15(tables.back().k - 1);
-    uint8_t *tmp[2] = {nullptr, nullptr};
-    if (pool.get(&M.good, (size_t)A.n_entries) || pool.get(&M.lattice, n_lat) || pool.get(&tmp[0], scratch + 1) ||
-        pool.get(&tmp[1], scratch + 1) || pool.get(&M.head, 1))
+    if (pool.get(&M.good, (size_t)A.n_entries) || pool.get(&M.lattice, n_lat) || pool.get(&mi.tmp[0], scratch + 1) ||
+        pool.get(&mi.tmp[1], scratch + 1) || pool.get(&M.head, 1))
         return -10;
+    return 0;
+}
+
+// The tables are counted -> the rows of the definition in its order, in structured form.  again (--iterative, rounds 2 on): the
+// stats keep round 1's figures; the flags, the lattices and the head are made anew every round
+int mi_rows(mc_ctx *c, Pool &pool, MiState &mi, const std::vector<MsTable> &tables, bool again, std::vector<MiPat> &rows,
+            std::chrono::steady_clock::time_point *t_d2h, int32_t *status) {
+    mc_motif_stats &S = c->motif_stats;
+    mc_motif_iupac_stats &I = c->motif_iupac_stats;
+    hipStream_t st = c->stream;
+    MiArgs &M = mi.M;
+    rows.clear();
+    *t_d2h = std::chrono::steady_clock::now();
     HIP_TRY(hipMemsetAsync(M.head, 0, sizeof(MiHead), st));
-    hipLaunchKernelGGL(ki_good, dim3(blocks(A.n_entries)), dim3(256), 0, st, M);
+    hipLaunchKernelGGL(ki_good, dim3(blocks(M.n_entries)), dim3(256), 0, st, M);
     for (size_t t = 0; t < tables.size(); ++t) {
         const MsTable &T = tables[t];
         const int n = T.k - 1;
@@ -227,7 +241,7 @@ int mi_run(mc_ctx *c, Pool &pool, const MsArgs &A, const mc_motif_params &P, con
         uint32_t lo = 1;
         for (int s = 0; s < n; ++s) {
             const uint32_t hi = 1u << (2 * (n - 1 - s)), n_pass = hi * 15u * lo;
-            uint8_t *to = s == n - 1 ? M.lattice + T.lat : tmp[s & 1];
+            uint8_t *to = s == n - 1 ? M.lattice + T.lat : mi.tmp[s & 1];
             hipLaunchKernelGGL(ki_widen, dim3(blocks(((int64_t)n_pass + 3) / 4)), dim3(256), 0, st, in, to, lo, n_pass);
             in = to;
             lo *= 15u;
@@ -237,11 +251,14 @@ int mi_run(mc_ctx *c, Pool &pool, const MsArgs &A, const mc_motif_params &P, con
     HIP_TRY(hipGetLastError());
     MiHead h = {};
     if (int rc = fetch_head(st, M.head, h)) return rc;
-    I.n_good = (int64_t)h.n_good; I.n_pure = (int64_t)h.n_pure; I.n_maximal = (int64_t)h.n_maximal;
+    if (!again) { I.n_good = (int64_t)h.n_good; I.n_pure = (int64_t)h.n_pure; I.n_maximal = (int64_t)h.n_maximal; }
     const int64_t NP = (int64_t)h.n_maximal;
     if (NP == 0) return 0;
-    if (!ms_fits((size_t)NP * (2 * sizeof(MiPat) + 16) + ((size_t)1 << 20))) return ms_decline(c, status, MC_MOTIF_DECLINE_MEMORY, 0, -1);
-    if (pool.get(&M.pats, (size_t)NP) || pool.get(&M.rows, (size_t)NP) || pool.get(&M.flag, (size_t)NP * 2)) return -10;
+    if (NP > mi.cap_pats) {
+        if (!ms_fits((size_t)NP * (2 * sizeof(MiPat) + 16) + ((size_t)1 << 20))) return ms_decline(c, status, MC_MOTIF_DECLINE_MEMORY, 0, -1);
+        if (pool.get(&M.pats, (size_t)NP) || pool.get(&M.rows, (size_t)NP) || pool.get(&M.flag, (size_t)NP * 2)) return -10;
+        mi.cap_pats = NP;
+    }
     M.place = M.flag + NP;
     M.n_pats = NP;
     for (size_t t = 0; t < tables.size(); ++t) {
@@ -254,12 +271,11 @@ int mi_run(mc_ctx *c, Pool &pool, const MsArgs &A, const mc_motif_params &P, con
     hipLaunchKernelGGL(ki_gather, dim3(blocks(NP)), dim3(256), 0, st, M);
     HIP_TRY(hipGetLastError());
     if (int rc = fetch_head(st, M.head, h)) return rc;
-    S.n_selected = (int64_t)h.n_selected;
     const int64_t NR = h.n_rows;
-    S.n_rows = NR;
+    if (!again) { S.n_selected = (int64_t)h.n_selected; S.n_rows = NR; }
     if (NR == 0) return 0;
-    const auto t_d2h = std::chrono::steady_clock::now();
-    std::vector<MiPat> rows((size_t)NR);
+    *t_d2h = std::chrono::steady_clock::now();
+    rows.resize((size_t)NR);
     HIP_TRY(hipMemcpyAsync(rows.data(), M.rows, (size_t)NR * sizeof(MiPat), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     // the order of the definition: tables stand in shape and j order, a table's indices in the order of the masks left to right
@@ -270,25 +286,19 @@ int mi_run(mc_ctx *c, Pool &pool, const MsArgs &A, const mc_motif_params &P, con
         if (a.table != b.table) return a.table < b.table;
         return a.index < b.index;
     });
-    MsText text;
-    for (const MiPat &r : rows) {
-        const MsTable &T = tables[(size_t)r.table];
-        const char *shape = P.shapes[T.shape];
-        uint32_t place = mi_pow15(T.k - 2);                            // of the first free X's digit
-        for (int i = 0, x = 0; i < T.W; ++i) {
-            if (shape[i] != 'X') { text.put('N'); continue; }
-            if (x == T.j) text.put((char)P.base);
-            else { text.put(" ACMGRSVTWYHKDBN"[r.index / place % 15u + 1]); place /= 15u; }
-            ++x;
-        }
-        if (!ms_put_numbers(text, T.o, r.nG, r.nC, r.nM)) return ms_decline(c, status, MC_MOTIF_DECLINE_PRINT, 0, -1);
-    }
-    if (int rc = grow(c->motif_out, c->motif_out_cap, text.s.size())) return rc;
-    memcpy(c->motif_out.p, text.s.data(), text.s.size());
-    S.ms_d2h = ms_since(t_d2h);
-    S.n_out_bytes = (int64_t)text.s.size();
-    *out = c->motif_out.get<char>();
-    *n_out = (int64_t)text.s.size();
-    *n_rows = NR;
     return 0;
+}
+
+// a row's line -> false: mc_rowtext.h does not print the fraction
+bool mi_line(MsText &text, const mc_motif_params &P, const std::vector<MsTable> &tables, const MiPat &r) {
+    const MsTable &T = tables[(size_t)r.table];
+    const char *shape = P.shapes[T.shape];
+    uint32_t place = mi_pow15(T.k - 2);                                // of the first free X's digit
+    for (int i = 0, x = 0; i < T.W; ++i) {
+        if (shape[i] != 'X') { text.put('N'); continue; }
+        if (x == T.j) text.put((char)P.base);
+        else { text.put(" ACMGRSVTWYHKDBN"[r.index / place % 15u + 1]); place /= 15u; }
+        ++x;
+    }
+    return ms_put_numbers(text, T.o, r.nG, r.nC, r.nM);
 }

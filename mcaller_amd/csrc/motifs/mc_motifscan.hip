@@ -48,6 +48,11 @@
 //                the integer keys of the definition (they are few) and writes SPEC and the numbers with mc_rowtext.h
 //   --iupac      behind km_count, in place of km_select / km_keep / km_gather: mc_motifiupac.inc (C ABI: mc_motif_report_iupac_text /
 //                _file, mc_motif_report_iupac_last_stats)
+//   --iterative  behind km_count, round after round: the selection above (ms_rows, or mi_rows of mc_motifiupac.inc) gives the ordered
+//                rows in structured form, the first is printed, km_explain takes the candidates it explains out of the candidate
+//                planes and km_uncount out of every table (ms_key: the one statement of a window's validity and key, shared with
+//                km_count), and the selection runs again: mc_motifiter.inc (C ABI: mc_motif_report_iter_text / _file, _iter_last_stats,
+//                _iter_left: the methylated candidates no row explains, as two planes in pinned memory)
 // No floating-point atomic anywhere; the counts are exact integers whatever the order of arrival.
 #include "../mc_textfeed.h"
 #include "../mc_rowtext.h"
@@ -68,6 +73,7 @@ struct MsHead {                              // device-side result block (copied
     long long n_lines1;                      // lines that start before the control's text
     unsigned long long n_candidates, n_sites, n_control, n_off_base, n_selected, n_rows, cursor;
     int table_full, pad;
+    unsigned long long n_list, n_left;       // --iterative: candidates the round's row explains; methylated candidates left
 };
 
 struct MsTable {                             // a (shape, j)
@@ -116,6 +122,10 @@ struct MsArgs {
     double min_fraction;
     MsRow *rows;
     int64_t cap_rows;
+    // --iterative (mc_motifiter.inc)
+    long long *list;                         // the candidates a round's row explains: base index << 1 | strand
+    int64_t cap_list;
+    uint64_t *left;                          // meth & cand of '+', then of '-'
 };
 
 __device__ __forceinline__ int ms_code(unsigned c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : 4; }
@@ -229,6 +239,27 @@ __device__ __forceinline__ uint64_t ms_funnel(const uint64_t *plane, int64_t g0)
     return s ? (lo >> s) | (hi << (64 - s)) : lo;
 }
 
+// the window of table T around the candidate at base index g of strand s -> false: it does not count; else its key.  Bit i of the
+// neighbourhood is base g - MS_REACH + i (g >= 64 > MS_REACH: the first contig begins at 64); on '-' the letters stand at the
+// mirrored offsets and are complemented (both code bits flipped).  km_count adds with it and km_uncount takes away
+__device__ __forceinline__ bool ms_key(const MsArgs &A, const MsTable &T, int64_t g, int s, uint32_t *key_out) {
+    const uint64_t nv = ms_funnel(A.valid, g - MS_REACH);
+    const uint64_t mask = T.mask[s], idx = T.idx[s];
+    if ((nv & mask) != mask) return false;
+    const uint64_t n0 = ms_funnel(A.code0, g - MS_REACH), n1 = ms_funnel(A.code1, g - MS_REACH);
+    const uint64_t flip = s ? ~0ull : 0ull;                          // '-': the complement, 3 - code
+    const uint64_t c0 = n0 ^ flip, c1 = n1 ^ flip;
+    const int k = T.k, j = T.j;
+    uint32_t key = 0;
+    for (int i = 0; i < k; ++i) {
+        if (i == j) continue;
+        const int at = (int)((idx >> (8 * i)) & 63ull);
+        key = (key << 2) | (uint32_t)((c0 >> at) & 1ull) | ((uint32_t)((c1 >> at) & 1ull) << 1);
+    }
+    *key_out = key;
+    return key < T.entries;                                          // (always: k - 1 letters of two bits)
+}
+
 template <bool IN_LDS>
 __global__ __launch_bounds__(256) void km_count(MsArgs A, int ti) {
     extern __shared__ unsigned int s_hist[];
@@ -238,27 +269,14 @@ __global__ __launch_bounds__(256) void km_count(MsArgs A, int ti) {
         for (uint32_t i = threadIdx.x; i < T.entries; i += 256) s_hist[i] = 0u;
         __syncthreads();
     }
-    const int k = T.k, j = T.j;
     for (int64_t g = g_lo + threadIdx.x; g < g_hi; g += 256) {
         const int64_t w = g >> 6;
         const int bit = (int)(g & 63);
         const bool plus = (A.cand[0][w] >> bit) & 1ull, minus = (A.cand[1][w] >> bit) & 1ull;
         if (!plus && !minus) continue;                               // (no base is a candidate of both strands)
         const int s = minus ? 1 : 0;
-        // bit i of the neighbourhood is base g - MS_REACH + i (g >= 64 > MS_REACH: the first contig begins at 64)
-        const uint64_t nv = ms_funnel(A.valid, g - MS_REACH);
-        const uint64_t mask = T.mask[s], idx = T.idx[s];
-        if ((nv & mask) != mask) continue;
-        const uint64_t n0 = ms_funnel(A.code0, g - MS_REACH), n1 = ms_funnel(A.code1, g - MS_REACH);
-        const uint64_t flip = s ? ~0ull : 0ull;                      // '-': the complement, 3 - code
-        const uint64_t c0 = n0 ^ flip, c1 = n1 ^ flip;
-        uint32_t key = 0;
-        for (int i = 0; i < k; ++i) {
-            if (i == j) continue;
-            const int at = (int)((idx >> (8 * i)) & 63ull);
-            key = (key << 2) | (uint32_t)((c0 >> at) & 1ull) | ((uint32_t)((c1 >> at) & 1ull) << 1);
-        }
-        if (key >= T.entries) continue;                              // (cannot be: k - 1 letters of two bits)
+        uint32_t key;
+        if (!ms_key(A, T, g, s, &key)) continue;
         if (IN_LDS) atomicAdd(&s_hist[key], 1u);
         else atomicAdd(&A.nG[T.off + key], 1u);
         const bool is_meth = (A.meth[s][w] >> bit) & 1ull;
@@ -282,6 +300,11 @@ __device__ __forceinline__ int ms_table_of(const MsArgs &A, uint32_t e) {
         if (A.tables[mid].off <= e) lo = mid; else hi = mid;
     }
     return lo;
+}
+
+// --iterative, rounds 2 on: the counters of the three kernels below begin at 0 again
+__global__ void km_again(MsArgs A) {
+    if (threadIdx.x == 0) { A.head->n_selected = 0; A.head->n_rows = 0; A.head->cursor = 0; }
 }
 
 __global__ __launch_bounds__(256) void km_select(MsArgs A) {
@@ -443,13 +466,88 @@ bool ms_put_numbers(MsText &text, int o, uint32_t nG, uint32_t nC, uint32_t nM) 
     return true;
 }
 
-#include "mc_motifiupac.inc"
+// the rows' bytes into the context's pinned block, handed out
+int ms_hand_out(mc_ctx *c, const MsText &text, std::chrono::steady_clock::time_point t_d2h, const char **out, int64_t *n_out) {
+    mc_motif_stats &S = c->motif_stats;
+    if (int rc = grow(c->motif_out, c->motif_out_cap, text.s.size())) return rc;
+    memcpy(c->motif_out.p, text.s.data(), text.s.size());
+    S.ms_d2h = ms_since(t_d2h);
+    S.n_out_bytes = (int64_t)text.s.size();
+    *out = c->motif_out.get<char>();
+    *n_out = (int64_t)text.s.size();
+    return 0;
+}
 
-// Everything behind the uploads.  d_text[0, n): the bed's text, a newline if it lacked its last, the control's from off2 on; padded
-int ms_run(mc_ctx *c, Pool &pool, MsArgs &A, MsHead *d_head, const mc_motif_params &P, const std::vector<MsTable> &tables, bool iupac,
-           size_t scratch, const char **out, int64_t *n_out, int64_t *n_rows, int32_t *status) {
+// The tables are counted -> the rows of the definition in its order, in structured form.  again (--iterative, rounds 2 on): the
+// head's counters are zeroed first and the stats keep round 1's figures
+int ms_rows(mc_ctx *c, Pool &pool, MsArgs &A, MsHead *d_head, bool again, std::vector<MsRow> &rows, std::chrono::steady_clock::time_point *t_d2h,
+            int32_t *status) {
     mc_motif_stats &S = c->motif_stats;
     hipStream_t st = c->stream;
+    MsHead h = {};
+    rows.clear();
+    *t_d2h = std::chrono::steady_clock::now();
+    if (again) hipLaunchKernelGGL(km_again, dim3(1), dim3(64), 0, st, A);
+    hipLaunchKernelGGL(km_select, dim3(blocks(A.n_entries)), dim3(256), 0, st, A);
+    hipLaunchKernelGGL(km_keep, dim3(blocks(A.n_entries)), dim3(256), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    if (int rc = fetch_head(st, d_head, h)) return rc;
+    const int64_t NR = (int64_t)h.n_rows;
+    if (!again) { S.n_selected = (int64_t)h.n_selected; S.n_rows = NR; }
+    if (NR == 0) return 0;
+    if (NR > A.cap_rows) {
+        if (!ms_fits((size_t)NR * sizeof(MsRow) + ((size_t)1 << 20))) return ms_decline(c, status, MC_MOTIF_DECLINE_MEMORY, 0, -1);
+        if (pool.get(&A.rows, (size_t)NR)) return -10;
+        A.cap_rows = NR;
+    }
+    hipLaunchKernelGGL(km_gather, dim3(blocks(A.n_entries)), dim3(256), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    *t_d2h = std::chrono::steady_clock::now();
+    rows.resize((size_t)NR);
+    HIP_TRY(hipMemcpyAsync(rows.data(), A.rows, (size_t)NR * sizeof(MsRow), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    // the order of the definition: nMethylated and the fraction descending, then the entry (tables stand in shape and j order,
+    // a table's keys in the letters' order)
+    std::sort(rows.begin(), rows.end(), [](const MsRow &a, const MsRow &b) {
+        if (a.nM != b.nM) return a.nM > b.nM;
+        const double fa = (double)a.nM / (double)a.nC, fb = (double)b.nM / (double)b.nC;
+        if (fa != fb) return fa > fb;
+        return a.entry < b.entry;
+    });
+    return 0;
+}
+
+inline size_t ms_table_of_entry(const std::vector<MsTable> &tables, uint32_t entry) {
+    size_t ti = 0;
+    while (ti + 1 < tables.size() && tables[ti + 1].off <= entry) ++ti;
+    return ti;
+}
+
+// a row's line -> false: mc_rowtext.h does not print the fraction
+bool ms_line(MsText &text, const mc_motif_params &P, const std::vector<MsTable> &tables, const MsRow &r) {
+    const MsTable &T = tables[ms_table_of_entry(tables, r.entry)];
+    const uint32_t key = r.entry - T.off;
+    const char *shape = P.shapes[T.shape];
+    for (int i = 0, x = 0, d = T.k - 2; i < T.W; ++i) {
+        if (shape[i] != 'X') { text.put('N'); continue; }
+        if (x == T.j) text.put((char)P.base);
+        else { text.put("ACGT"[(key >> (2 * d)) & 3u]); --d; }
+        ++x;
+    }
+    return ms_put_numbers(text, T.o, r.nG, r.nC, r.nM);
+}
+
+#include "mc_motifiupac.inc"
+#include "mc_motifiter.inc"
+
+// Everything behind the uploads.  d_text[0, n): the bed's text, a newline if it lacked its last, the control's from off2 on; padded.
+// max_motifs: 0, or --iterative's
+int ms_run(mc_ctx *c, Pool &pool, MsArgs &A, MsHead *d_head, const mc_motif_params &P, const std::vector<MsTable> &tables, bool iupac,
+           int max_motifs, size_t scratch, const char **out, int64_t *n_out, int64_t *n_rows, int32_t *status) {
+    mc_motif_stats &S = c->motif_stats;
+    hipStream_t st = c->stream;
+    const auto t_first = std::chrono::steady_clock::now();
     MsHead h = {};
     hipLaunchKernelGGL(km_pack, dim3((unsigned)(A.n_words * 64 / 256 + (A.n_words * 64 % 256 ? 1 : 0))), dim3(256), 0, st, A);
     if (A.n_contigs > 0) hipLaunchKernelGGL(km_contigs, dim3(blocks(A.n_contigs)), dim3(256), 0, st, A);
@@ -490,64 +588,36 @@ int ms_run(mc_ctx *c, Pool &pool, MsArgs &A, MsHead *d_head, const mc_motif_para
             ++S.n_tables_global;
         }
     }
-    if (iupac) {
-        HIP_TRY(hipGetLastError());
-        return mi_run(c, pool, A, P, tables, scratch, out, n_out, n_rows, status);
-    }
-    hipLaunchKernelGGL(km_select, dim3(blocks(A.n_entries)), dim3(256), 0, st, A);
-    hipLaunchKernelGGL(km_keep, dim3(blocks(A.n_entries)), dim3(256), 0, st, A);
     HIP_TRY(hipGetLastError());
-    if (int rc = fetch_head(st, d_head, h)) return rc;
-    S.n_selected = (int64_t)h.n_selected;
-    const int64_t NR = (int64_t)h.n_rows;
-    S.n_rows = NR;
-    if (NR == 0) return 0;
-    if (!ms_fits((size_t)NR * sizeof(MsRow) + ((size_t)1 << 20))) return ms_decline(c, status, MC_MOTIF_DECLINE_MEMORY, 0, -1);
-    if (pool.get(&A.rows, (size_t)NR)) return -10;
-    A.cap_rows = NR;
-    hipLaunchKernelGGL(km_gather, dim3(blocks(A.n_entries)), dim3(256), 0, st, A);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-    const auto t_d2h = std::chrono::steady_clock::now();
-    std::vector<MsRow> rows((size_t)NR);
-    HIP_TRY(hipMemcpyAsync(rows.data(), A.rows, (size_t)NR * sizeof(MsRow), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    // the order of the definition: nMethylated and the fraction descending, then the entry (tables stand in shape and j order,
-    // a table's keys in the letters' order)
-    std::sort(rows.begin(), rows.end(), [](const MsRow &a, const MsRow &b) {
-        if (a.nM != b.nM) return a.nM > b.nM;
-        const double fa = (double)a.nM / (double)a.nC, fb = (double)b.nM / (double)b.nC;
-        if (fa != fb) return fa > fb;
-        return a.entry < b.entry;
-    });
+    if (max_motifs > 0) return it_run(c, pool, A, d_head, P, tables, iupac, max_motifs, scratch, t_first, out, n_out, n_rows, status);
+    auto t_d2h = std::chrono::steady_clock::now();
     MsText text;
-    size_t ti = 0;
-    for (const MsRow &r : rows) {
-        ti = 0;
-        while (ti + 1 < tables.size() && tables[ti + 1].off <= r.entry) ++ti;
-        const MsTable &T = tables[ti];
-        const uint32_t key = r.entry - T.off;
-        const char *shape = P.shapes[T.shape];
-        for (int i = 0, x = 0, d = T.k - 2; i < T.W; ++i) {
-            if (shape[i] != 'X') { text.put('N'); continue; }
-            if (x == T.j) text.put((char)P.base);
-            else { text.put("ACGT"[(key >> (2 * d)) & 3u]); --d; }
-            ++x;
-        }
-        if (!ms_put_numbers(text, T.o, r.nG, r.nC, r.nM)) return ms_decline(c, status, MC_MOTIF_DECLINE_PRINT, 0, -1);
+    int64_t NR = 0;
+    if (iupac) {
+        MiState mi;
+        std::vector<MiPat> rows;
+        if (int rc = mi_setup(pool, A, tables, scratch, mi)) return rc;
+        if (int rc = mi_rows(c, pool, mi, tables, false, rows, &t_d2h, status)) return rc;
+        if (*status != 0 || rows.empty()) return 0;
+        for (const MiPat &r : rows)
+            if (!mi_line(text, P, tables, r)) return ms_decline(c, status, MC_MOTIF_DECLINE_PRINT, 0, -1);
+        NR = (int64_t)rows.size();
+    } else {
+        std::vector<MsRow> rows;
+        if (int rc = ms_rows(c, pool, A, d_head, false, rows, &t_d2h, status)) return rc;
+        if (*status != 0 || rows.empty()) return 0;
+        for (const MsRow &r : rows)
+            if (!ms_line(text, P, tables, r)) return ms_decline(c, status, MC_MOTIF_DECLINE_PRINT, 0, -1);
+        NR = (int64_t)rows.size();
     }
-    if (int rc = grow(c->motif_out, c->motif_out_cap, text.s.size())) return rc;
-    memcpy(c->motif_out.p, text.s.data(), text.s.size());
-    S.ms_d2h = ms_since(t_d2h);
-    S.n_out_bytes = (int64_t)text.s.size();
-    *out = c->motif_out.get<char>();
-    *n_out = (int64_t)text.s.size();
+    if (int rc = ms_hand_out(c, text, t_d2h, out, n_out)) return rc;
     *n_rows = NR;
     return 0;
 }
 
+// max_motifs: 0, or --iterative's 1 .. MC_MOTIF_MAX_ROUNDS
 int ms_call(mc_ctx *c, const mc_ref_view *ref, const TextSource &s1, const TextSource *s2, const mc_motif_params *P, bool iupac,
-            const char **out, int64_t *n_out, int64_t *n_rows, int32_t *status) {
+            int max_motifs, const char **out, int64_t *n_out, int64_t *n_rows, int32_t *status) {
     HIP_TRY(hipSetDevice(c->device));
     const auto t0 = std::chrono::steady_clock::now();
     mc_motif_stats &S = c->motif_stats;
@@ -555,6 +625,10 @@ int ms_call(mc_ctx *c, const mc_ref_view *ref, const TextSource &s1, const TextS
     S.decline_line = -1;
     S.n_bytes1 = s1.n; S.n_bytes2 = s2 ? s2->n : 0;
     c->motif_iupac_stats = mc_motif_iupac_stats();
+    c->motif_iter_stats = mc_motif_iter_stats();
+    c->motif_iter_stats.decline_line = -1;
+    c->motif_left_words = 0;
+    c->motif_left_starts.clear();
     *out = nullptr; *n_out = 0; *n_rows = 0; *status = 0;
     std::vector<MsTable> tables;
     std::vector<MsParent> parents;
@@ -589,7 +663,9 @@ int ms_call(mc_ctx *c, const mc_ref_view *ref, const TextSource &s1, const TextS
     size_t scratch = 0;
     const size_t need_iupac = iupac ? mi_need(tables, &scratch) : 0;    // (and the tables learn their places in the lattice block)
     c->motif_iupac_stats.lattice_bytes = (int64_t)need_iupac;
-    if (!ms_fits(need + need_iupac)) return ms_decline(c, status, MC_MOTIF_DECLINE_MEMORY, 0, -1);
+    const size_t need_iter = max_motifs > 0 ? it_need(n_bases, n_words, &c->motif_iter_stats.list_bytes) : 0;
+    c->motif_iter_stats.need_bytes = (int64_t)(need + need_iupac + need_iter);
+    if (!ms_fits(need + need_iupac + need_iter)) return ms_decline(c, status, MC_MOTIF_DECLINE_MEMORY, 0, -1);
     Pool pool("motif finder");
     hipStream_t up = c->up_stream;
     MsArgs A = {};
@@ -605,6 +681,10 @@ int ms_call(mc_ctx *c, const mc_ref_view *ref, const TextSource &s1, const TextS
         pool.get(&d_tables, tables.size()) || pool.get(&d_parents, parents.size() + 1) || pool.get(&d_head, 1) ||
         pool.get(&A.nG, (size_t)n_entries * 3) || pool.get(&A.selected, (size_t)n_entries * 2))
         return -10;
+    if (max_motifs > 0) {
+        if (pool.get(&A.list, (size_t)n_bases + 1) || pool.get(&A.left, (size_t)n_words * 2)) return -10;
+        A.cap_list = n_bases;
+    }
     if (int rc = table_get(pool, up, &A.table, slots)) return rc;
     // the reference and the tables (pageable host memory: the copies are done when the calls return), then the texts
     std::vector<int64_t> meta((size_t)NC * 3 + 1);
@@ -653,10 +733,11 @@ int ms_call(mc_ctx *c, const mc_ref_view *ref, const TextSource &s1, const TextS
     A.keep = A.selected + n_entries;
     A.min_sites = P->min_sites; A.min_fraction = P->min_fraction;
     const auto t_kernels = std::chrono::steady_clock::now();
-    const int rc = ms_run(c, pool, A, d_head, *P, tables, iupac, scratch, out, n_out, n_rows, status);
+    const int rc = ms_run(c, pool, A, d_head, *P, tables, iupac, max_motifs, scratch, out, n_out, n_rows, status);
     (void)hipStreamSynchronize(c->stream);                             // (an early return: nothing of the pool is in use when it goes)
     S.ms_kernels = ms_since(t_kernels) - S.ms_d2h;                     // a declined call too: what ran until it declined
-    if (rc != 0 || *status != 0) { *out = nullptr; *n_out = 0; *n_rows = 0; }
+    if (rc != 0 || *status != 0) { *out = nullptr; *n_out = 0; *n_rows = 0; c->motif_left_words = 0; }
+    else if (max_motifs > 0) c->motif_left_starts.assign(gstart.begin(), gstart.begin() + NC);
     S.ms_total = ms_since(t0);
     return rc;
 }
@@ -682,7 +763,7 @@ extern "C" int mc_motif_report_text(mc_ctx *c, const mc_ref_view *ref, const cha
         return -12;
     }
     const TextSource s1{bed, nullptr, n_bed}, s2{control, nullptr, n_control};
-    return ms_call(c, ref, s1, control ? &s2 : nullptr, params, false, out, n_out, n_rows, status);
+    return ms_call(c, ref, s1, control ? &s2 : nullptr, params, false, 0, out, n_out, n_rows, status);
 }
 
 extern "C" int mc_motif_report_file(mc_ctx *c, const mc_ref_view *ref, const char *bed_path, const char *control_path,
@@ -696,7 +777,7 @@ extern "C" int mc_motif_report_file(mc_ctx *c, const mc_ref_view *ref, const cha
     if (control_path)
         if (int rc = regular_file_size("mc_motif_report_file", control_path, &n2)) return rc;
     const TextSource s1{nullptr, bed_path, n1}, s2{nullptr, control_path, n2};
-    return ms_call(c, ref, s1, control_path ? &s2 : nullptr, params, false, out, n_out, n_rows, status);
+    return ms_call(c, ref, s1, control_path ? &s2 : nullptr, params, false, 0, out, n_out, n_rows, status);
 }
 
 extern "C" int mc_motif_report_last_stats(mc_ctx *c, mc_motif_stats *out) {
@@ -720,7 +801,7 @@ extern "C" int mc_motif_report_iupac_text(mc_ctx *c, const mc_ref_view *ref, con
         return -12;
     }
     const TextSource s1{bed, nullptr, n_bed}, s2{control, nullptr, n_control};
-    return mi_done(c, ms_call(c, ref, s1, control ? &s2 : nullptr, params, true, out, n_out, n_rows, status));
+    return mi_done(c, ms_call(c, ref, s1, control ? &s2 : nullptr, params, true, 0, out, n_out, n_rows, status));
 }
 
 extern "C" int mc_motif_report_iupac_file(mc_ctx *c, const mc_ref_view *ref, const char *bed_path, const char *control_path,
@@ -734,12 +815,64 @@ extern "C" int mc_motif_report_iupac_file(mc_ctx *c, const mc_ref_view *ref, con
     if (control_path)
         if (int rc = regular_file_size("mc_motif_report_iupac_file", control_path, &n2)) return rc;
     const TextSource s1{nullptr, bed_path, n1}, s2{nullptr, control_path, n2};
-    return mi_done(c, ms_call(c, ref, s1, control_path ? &s2 : nullptr, params, true, out, n_out, n_rows, status));
+    return mi_done(c, ms_call(c, ref, s1, control_path ? &s2 : nullptr, params, true, 0, out, n_out, n_rows, status));
 }
 
 extern "C" int mc_motif_report_iupac_last_stats(mc_ctx *c, mc_motif_iupac_stats *out) {
     if (!c || !out) { mc_set_error("mc_motif_report_iupac_last_stats: bad arguments"); return -12; }
     *out = c->motif_iupac_stats;
+    return 0;
+}
+
+// ---- --iterative: the motifs peeled off one at a time (mc_motifiter.inc) ----
+static int it_done(mc_ctx *c, int rc) {                               // the decline, if any, in the iterative stats too
+    mc_motif_iter_stats &I = c->motif_iter_stats;
+    I.decline_line = c->motif_stats.decline_line; I.decline_reason = c->motif_stats.decline_reason; I.decline_file = c->motif_stats.decline_file;
+    return mi_done(c, rc);
+}
+
+extern "C" int mc_motif_report_iter_text(mc_ctx *c, const mc_ref_view *ref, const char *bed, int64_t n_bed, const char *control, int64_t n_control,
+                                         const mc_motif_params *params, int32_t iupac, int32_t max_motifs, const char **out, int64_t *n_out,
+                                         int64_t *n_rows, int32_t *status) {
+    if (ms_bad_args(c, ref, params, out, n_out, n_rows, status) || n_bed < 0 || (n_bed > 0 && !bed) || n_control < 0 || max_motifs < 1 ||
+        max_motifs > MC_MOTIF_MAX_ROUNDS) {
+        mc_set_error("mc_motif_report_iter_text: bad arguments");
+        return -12;
+    }
+    const TextSource s1{bed, nullptr, n_bed}, s2{control, nullptr, n_control};
+    return it_done(c, ms_call(c, ref, s1, control ? &s2 : nullptr, params, iupac != 0, max_motifs, out, n_out, n_rows, status));
+}
+
+extern "C" int mc_motif_report_iter_file(mc_ctx *c, const mc_ref_view *ref, const char *bed_path, const char *control_path,
+                                         const mc_motif_params *params, int32_t iupac, int32_t max_motifs, const char **out, int64_t *n_out,
+                                         int64_t *n_rows, int32_t *status) {
+    if (ms_bad_args(c, ref, params, out, n_out, n_rows, status) || !bed_path || max_motifs < 1 || max_motifs > MC_MOTIF_MAX_ROUNDS) {
+        mc_set_error("mc_motif_report_iter_file: bad arguments");
+        return -12;
+    }
+    int64_t n1 = 0, n2 = 0;
+    if (int rc = regular_file_size("mc_motif_report_iter_file", bed_path, &n1)) return rc;
+    if (control_path)
+        if (int rc = regular_file_size("mc_motif_report_iter_file", control_path, &n2)) return rc;
+    const TextSource s1{nullptr, bed_path, n1}, s2{nullptr, control_path, n2};
+    return it_done(c, ms_call(c, ref, s1, control_path ? &s2 : nullptr, params, iupac != 0, max_motifs, out, n_out, n_rows, status));
+}
+
+extern "C" int mc_motif_report_iter_last_stats(mc_ctx *c, mc_motif_iter_stats *out) {
+    if (!c || !out) { mc_set_error("mc_motif_report_iter_last_stats: bad arguments"); return -12; }
+    *out = c->motif_iter_stats;
+    return 0;
+}
+
+extern "C" int mc_motif_report_iter_left(mc_ctx *c, const uint64_t **plus, const uint64_t **minus, int64_t *n_words, const int64_t **contig_start,
+                                         int32_t *n_contigs) {
+    if (!c || !plus || !minus || !n_words || !contig_start || !n_contigs) { mc_set_error("mc_motif_report_iter_left: bad arguments"); return -12; }
+    const bool have = c->motif_left_words > 0 && c->motif_left.p;
+    *plus = have ? c->motif_left.get<uint64_t>() : nullptr;
+    *minus = have ? c->motif_left.get<uint64_t>() + c->motif_left_words : nullptr;
+    *n_words = have ? c->motif_left_words : 0;
+    *contig_start = have && !c->motif_left_starts.empty() ? c->motif_left_starts.data() : nullptr;
+    *n_contigs = have ? (int32_t)c->motif_left_starts.size() : 0;
     return 0;
 }
 
@@ -749,6 +882,7 @@ extern "C" int mc_motif_report_release(mc_ctx *c) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipStreamSynchronize(c->up_stream));
     c->motif_out.reset(); c->motif_out_cap = 0;
+    c->motif_left.reset(); c->motif_left_cap = 0; c->motif_left_words = 0;
     c->text_stages.release();
     return 0;
 }

@@ -967,11 +967,15 @@ class Device(object):
     # ---- methylated motifs from called sites (csrc/motifs/mc_motifscan.hip) ----
     @_serialized
     def motif_report(self, ref, path=None, control_path=None, text=None, control_text=None, base='A', shapes=('XXXX',), min_sites=20,
-                     min_fraction=0.5, keep_all=False, iupac=False):
+                     min_fraction=0.5, keep_all=False, iupac=False, iterative=False, max_motifs=16, left=False):
         """The rows of find_motifs for the reference `ref` ({id: upper-cased sequence}), the sites of a make_bed summary (`path`,
         or its `text`, bytes) and optionally a make_bed --control summary (`control_path` / `control_text`), made on the GPU ->
         (blob: bytes, n_rows, None), or (None, 0, reason) when the device declines: the caller runs the host statement.
-        iupac: the rows merged into degenerate motifs (find_motifs --iupac)."""
+        iupac: the rows merged into degenerate motifs (find_motifs --iupac).
+        iterative: the first row of every round, at most max_motifs (find_motifs --iterative) -> a fourth value: with `left` the
+        bytes of the --unexplained file, else None."""
+        if iterative and not 1 <= int(max_motifs) <= 64:
+            raise ValueError('motif_report: max_motifs is 1 to 64')
         if (path is None) == (text is None) or (path is None and control_path is not None) or (text is None and control_text is not None):
             raise ValueError('motif_report: paths or texts')
         ids = [name.encode('latin-1', 'replace') for name in ref]
@@ -997,7 +1001,17 @@ class Device(object):
         P.min_sites, P.min_fraction, P.keep_all = int(min_sites), float(min_fraction), int(bool(keep_all))
         P.contig_ids, P.contig_id_off = _ptr(id_pool), _ptr(id_off)
         out, n_out, n_rows, status = C.c_void_p(), C.c_int64(), C.c_int64(), C.c_int32()
-        if path is not None and iupac:
+        if iterative and path is not None:
+            check(lib().mc_motif_report_iter_file(self._ctx, C.byref(v), os.fsencode(path), None if control_path is None else os.fsencode(control_path),
+                                                  C.byref(P), int(bool(iupac)), int(max_motifs), C.byref(out), C.byref(n_out), C.byref(n_rows),
+                                                  C.byref(status)))
+        elif iterative:
+            text = bytes(text)
+            control_text = None if control_text is None else bytes(control_text)
+            check(lib().mc_motif_report_iter_text(self._ctx, C.byref(v), text, len(text), control_text, 0 if control_text is None else len(control_text),
+                                                  C.byref(P), int(bool(iupac)), int(max_motifs), C.byref(out), C.byref(n_out), C.byref(n_rows),
+                                                  C.byref(status)))
+        elif path is not None and iupac:
             check(lib().mc_motif_report_iupac_file(self._ctx, C.byref(v), os.fsencode(path), None if control_path is None else os.fsencode(control_path),
                                                    C.byref(P), C.byref(out), C.byref(n_out), C.byref(n_rows), C.byref(status)))
         elif path is not None:
@@ -1013,9 +1027,39 @@ class Device(object):
             else:
                 check(lib().mc_motif_report_text(self._ctx, C.byref(v), text, len(text), control_text, n_control, C.byref(P), C.byref(out),
                                                  C.byref(n_out), C.byref(n_rows), C.byref(status)))
+        blob = C.string_at(out.value, n_out.value) if status.value == 0 and n_out.value else b''
+        if iterative:
+            if status.value != 0:
+                return None, 0, last_error(), None
+            return blob, int(n_rows.value), None, (self._motif_left(list(ref), lens) if left else None)
         if status.value != 0:
             return None, 0, last_error()
-        return (C.string_at(out.value, n_out.value) if n_out.value else b''), int(n_rows.value), None
+        return blob, int(n_rows.value), None
+
+    def _motif_left(self, names, lens):
+        """The --unexplained file of the last motif_report(iterative=True): the two planes of left-over sites as bed lines, contigs
+        in the reference's order, start ascending."""
+        plus, minus, starts = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        n_words, n_contigs = C.c_int64(), C.c_int32()
+        check(lib().mc_motif_report_iter_left(self._ctx, C.byref(plus), C.byref(minus), C.byref(n_words), C.byref(starts), C.byref(n_contigs)))
+        if n_words.value == 0 or n_contigs.value != len(names):
+            raise RuntimeError('motif_report: the left-over sites of the last call are not there')
+        bits = [np.unpackbits(np.frombuffer(C.string_at(p.value, n_words.value * 8), dtype=np.uint8), bitorder='little') for p in (plus, minus)]
+        at = np.frombuffer(C.string_at(starts.value, len(names) * 8), dtype=np.int64) if names else ()
+        out = []
+        for name, n, g in zip(names, lens.tolist(), at):
+            on = [b[g:g + n] for b in bits]
+            for p in np.nonzero(on[0] | on[1])[0].tolist():
+                out.append('%s\t%d\t%d\t.\t.\t%s\n' % (name, p, p + 1, '-' if on[1][p] else '+'))
+        return ''.join(out).encode('latin-1', 'replace')
+
+    @_serialized
+    def motif_report_iter_last_stats(self):
+        """Figures of the last motif_report(iterative=True): the rounds, the candidates every row explained, the methylated candidates
+        left, the bytes counted against device memory, the decline, the milliseconds of the first and of all later rounds."""
+        st = self._last_stats(lib().mc_motif_report_iter_last_stats, _lib.MotifIterStats)
+        st['n_explained'] = list(st['n_explained'])[:st['n_rounds']]
+        return st
 
     @_serialized
     def motif_report_last_stats(self):

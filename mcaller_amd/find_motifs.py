@@ -2,6 +2,7 @@
 
     python -m mcaller_amd.find_motifs -r ref.fasta --bed SUMMARY.bed [--control CONTROL.bed] [-b A] [--shapes LIST]
                                       [--min_sites 20] [--min_fraction 0.5] [--all] [--iupac] [-o OUT] [--device]
+                                      [--iterative [--max_motifs 16] [--unexplained OUT]]
 
 The reference has no such program: its GFF output and `make_bed --control` are shaped for an external motif finder.  This module
 closes the loop: every row it prints is a motif in the syntax `--motifs` parses (refmark.parse_motifs).
@@ -50,10 +51,32 @@ redundancy rule): the option loses nothing.  `last_counts` gains n_good, n_pure 
 counts the rows before the redundancy rule.  The host statement builds a table's lattice only inside the box of the letters that
 occur, per X, among its good entries (every pure pattern lies in it), not all 15^(k-1) patterns.
 
-Out of scope: iterative removal of explained sites, circular contigs.
+--iterative [--max_motifs N] peels the motifs off one at a time; N is 1 to 64, 16 by default, anything else a ValueError.  Round
+r = 1, 2, ...:
+  1. the report is made exactly as a call without --iterative makes it with the same --shapes, -b, --min_sites, --min_fraction,
+     --all and --iupac, but the candidates explained in earlier rounds are NOT CANDIDATES: they add nothing to nGenome, nCovered
+     or nMethylated of any table;
+  2. a report without a row ends the run;
+  3. otherwise its FIRST row, in the order above, is printed with that round's counts (the line format is unchanged: every line is
+     a --motifs spec and four numbers);
+  4. the row belongs to a table (shape, j) and gives every X of it a set of letters -- a singleton, with --iupac the IUPAC set.  It
+     EXPLAINS every remaining candidate (p, strand) whose window in that table counts (inside the contig, every letter under an
+     X one of ACGT) and whose letter under X i lies in set i, for every X.  Letters under '.' are free, an N of the reference
+     included.  The sets decide, not the SPEC text: in GANNCN:2 of XX..XX the last N is {A, C, G, T}, the middle two are free;
+  5. N rows end the run.
+The explained candidates of a round are exactly the ones that round's row counted, their number is the row's nGenome; every
+printed row explains at least one candidate (nGenome >= nMethylated >= 1 for a row to pass: 0 / 0 is no fraction), so the loop
+ends even without --max_motifs; `--iterative --max_motifs 1` prints the first line of the plain call.  `last_counts` holds the
+figures of round 1 and gains n_rounds (the rows printed), n_explained (a list: one nGenome per row) and n_unexplained (the
+methylated candidates left after the last round: round 1's methylated candidates less the sum of the rows' nMethylated).
+--unexplained OUT (only with --iterative) writes those as `chrom\tstart\tstart+1\t.\t.\tstrand\n`, contigs in the reference's
+order, start ascending (no base is a candidate of both strands: a total order); the file is a valid --bed for another run.
+
+Out of scope: circular contigs.
 
 `find_motifs` is that definition in NumPy (the host statement; no SciPy, no GPU).  `find_motifs_device` (--device) has the GPU make
-the same bytes (Device.motif_report: csrc/motifs/mc_motifscan.hip, --iupac: csrc/motifs/mc_motifiupac.inc) and runs the host
+the same bytes (Device.motif_report: csrc/motifs/mc_motifscan.hip, --iupac: csrc/motifs/mc_motifiupac.inc, --iterative:
+csrc/motifs/mc_motifiter.inc) and runs the host
 statement whenever the device declines; `last_report` says who made the output, `last_counts` what the host statement counted."""
 import os
 import sys
@@ -64,10 +87,11 @@ from . import refmark
 
 last_report = None         # what the last call did: dict(by='device' | 'host', reason=None | str, n_rows=int)
 last_counts = None         # the host statement's figures: dict(n_candidates, n_sites, n_control, n_off_base, n_selected)
-                           # and, with iupac, n_good, n_pure, n_maximal
+                           # and, with iupac, n_good, n_pure, n_maximal; with iterative, n_rounds, n_explained, n_unexplained
 
 MAX_WIDTH = 24
 MAX_SHAPES = 64            # what the device takes in one call (the host statement has no limit)
+MAX_MOTIFS = 64            # --max_motifs: 1 to this
 DEFAULT_SHAPES = ['XXX', 'XXXX', 'XXXXX', 'XXXXXX'] + ['X' * a + '.' * g + 'X' * b for a in (3, 4) for g in (5, 6, 7, 8) for b in (3, 4)]
 _CODE = np.full(256, 4, dtype=np.uint8)
 for _i, _c in enumerate(b'ACGT'):
@@ -115,8 +139,15 @@ def read_sites(path, ref):
     return listed
 
 
-def count_tables(ref, shapes, base, meth, control):
-    """-> ([shape][j] -> (nGenome, nCovered, nMethylated), int64 arrays over the 4^k letter codes, first letter highest), counts."""
+def _on_strand(fwd, rev):
+    """The letter codes of a contig as its strand reads them: the '-' strand is the '+' strand of the reverse complement, position
+    p stands at L - 1 - p there."""
+    return np.where(fwd < 4, 3 - fwd, 4).astype(np.uint8)[::-1] if rev else fwd
+
+
+def count_tables(ref, shapes, base, meth, control, explained=None):
+    """-> ([shape][j] -> (nGenome, nCovered, nMethylated), int64 arrays over the 4^k letter codes, first letter highest), counts.
+    explained: {contig: (bool[len] '+', bool[len] '-')}, candidates that are none any more (--iterative); the counts do not see it."""
     b = 'ACGT'.index(base)
     tables = [[tuple(np.zeros(4 ** s.count('X'), dtype=np.int64) for _ in range(3)) for _ in range(s.count('X'))] for s in shapes]
     counts = dict(n_candidates=0, n_sites=0, n_control=0, n_off_base=0)
@@ -124,8 +155,7 @@ def count_tables(ref, shapes, base, meth, control):
         fwd = _CODE[np.frombuffer(seq.encode('latin-1', 'replace'), dtype=np.uint8)]
         L = len(fwd)
         for rev in (False, True):
-            # the '-' strand is the '+' strand of the reverse complement: position p stands at L - 1 - p there
-            code = np.where(fwd < 4, 3 - fwd, 4).astype(np.uint8)[::-1] if rev else fwd
+            code = _on_strand(fwd, rev)
             m = meth[name][rev][::-1] if rev else meth[name][rev]
             c = None if control is None else (control[name][rev][::-1] if rev else control[name][rev])
             cand = code == b
@@ -134,6 +164,8 @@ def count_tables(ref, shapes, base, meth, control):
             counts['n_sites'] += int(m.sum())
             counts['n_control'] += 0 if c is None else int(c.sum())
             counts['n_off_base'] += int((listed & ~cand).sum())
+            if explained is not None:
+                cand = cand & ~(explained[name][rev][::-1] if rev else explained[name][rev])
             is_meth = m & cand
             is_cov = cand if c is None else (listed & cand)
             for si, shape in enumerate(shapes):
@@ -162,11 +194,17 @@ def _letters(code, k):
     return ''.join('ACGT'[(code >> (2 * (k - 1 - i))) & 3] for i in range(k))
 
 
-def report_rows(ref, shapes, base, meth, control, min_sites=20, min_fraction=0.5, keep_all=False, iupac=False):
-    """The rows of the definition as bytes, their number, and the counts."""
-    tables, counts = count_tables(ref, shapes, base, meth, control)
-    if iupac:
-        return _iupac_rows(tables, counts, shapes, base, min_sites, min_fraction, keep_all)
+def report_rows(ref, shapes, base, meth, control, min_sites=20, min_fraction=0.5, keep_all=False, iupac=False, explained=None,
+                with_first=False):
+    """The rows of the definition as bytes, their number, and the counts.  explained: as in count_tables.  with_first: a fourth
+    value, the first row's (shape index, j, the sets of its X from left to right as masks over A = 1, C = 2, G = 4, T = 8), None
+    where there is no row."""
+    tables, counts = count_tables(ref, shapes, base, meth, control, explained)
+    data, n_rows, counts, first = (_iupac_rows if iupac else _plain_rows)(tables, counts, shapes, base, min_sites, min_fraction, keep_all)
+    return (data, n_rows, counts, first) if with_first else (data, n_rows, counts)
+
+
+def _plain_rows(tables, counts, shapes, base, min_sites, min_fraction, keep_all):
     selected = []            # (nM, fraction, shape index, j, letters, nG, nC)
     for si, shape in enumerate(shapes):
         k = shape.count('X')
@@ -203,7 +241,8 @@ def report_rows(ref, shapes, base, meth, control, min_sites=20, min_fraction=0.5
         for ch in shapes[si]:
             window.append(next(it) if ch == 'X' else 'N')
         out.append('%s:%d\t%d\t%d\t%d\t%s\n' % (''.join(window), offsets[si][j] + 1, nG, nC, nM, repr(frac)))
-    return ''.join(out).encode('ascii'), len(out), counts
+    first = (selected[0][2], selected[0][3], tuple(1 << 'ACGT'.index(ch) for ch in selected[0][4])) if selected else None
+    return ''.join(out).encode('ascii'), len(out), counts, first
 
 
 IUPAC_LETTER = ' ACMGRSVTWYHKDBN'            # the letter of a set over A = 1, C = 2, G = 4, T = 8
@@ -295,7 +334,59 @@ def _iupac_rows(tables, counts, shapes, base, min_sites, min_fraction, keep_all)
         for ch in shapes[si]:
             window.append(IUPAC_LETTER[next(it)] if ch == 'X' else 'N')
         out.append('%s:%d\t%d\t%d\t%d\t%s\n' % (''.join(window), offsets[si][j] + 1, nG, nC, nM, repr(frac)))
-    return ''.join(out).encode('ascii'), len(out), counts
+    first = (selected[0][2], selected[0][3], tuple(selected[0][4])) if selected else None
+    return ''.join(out).encode('ascii'), len(out), counts, first
+
+
+def explain(ref, shapes, base, first, explained):
+    """Step 4 of --iterative: marks in `explained` every remaining candidate the row `first` (shape index, j, masks) explains ->
+    their number."""
+    b = 'ACGT'.index(base)
+    si, j, masks = first
+    xs = [i for i, ch in enumerate(shapes[si]) if ch == 'X']
+    W, o = len(shapes[si]), xs[j]
+    member = [np.array([m >> c & 1 for c in range(4)] + [0], dtype=bool) for m in masks]      # code 4 (no ACGT) is in no set
+    n = 0
+    for name, seq in ref.items():
+        fwd = _CODE[np.frombuffer(seq.encode('latin-1', 'replace'), dtype=np.uint8)]
+        n_win = len(fwd) - W + 1
+        if n_win <= 0:
+            continue
+        for rev in (False, True):
+            code = _on_strand(fwd, rev)
+            mine = explained[name][rev][::-1] if rev else explained[name][rev]                 # a view: position p at L - 1 - p
+            hit = (code[o:o + n_win] == b) & ~mine[o:o + n_win]
+            for x, inside in zip(xs, member):
+                hit &= inside[code[x:x + n_win]]
+            mine[o:o + n_win] |= hit
+            n += int(hit.sum())
+    return n
+
+
+def iterative_rows(ref, shapes, base, meth, control, min_sites=20, min_fraction=0.5, keep_all=False, iupac=False, max_motifs=16):
+    """--iterative: the first row of every round as bytes, their number, the counts of round 1 with n_rounds, n_explained and
+    n_unexplained, and the left-over sites as the --unexplained bytes."""
+    explained = {name: (np.zeros(len(seq), dtype=bool), np.zeros(len(seq), dtype=bool)) for name, seq in ref.items()}
+    out, n_explained, counts = [], [], None
+    while len(out) < max_motifs:
+        data, n_rows, now, first = report_rows(ref, shapes, base, meth, control, min_sites, min_fraction, keep_all, iupac, explained, True)
+        counts = counts or now
+        if n_rows == 0:
+            break
+        out.append(data[:data.index(b'\n') + 1])
+        n_explained.append(explain(ref, shapes, base, first, explained))
+        if n_explained[-1] != int(out[-1].split(b'\t')[1]):
+            raise AssertionError('the row %r explains %d candidates' % (out[-1], n_explained[-1]))
+    b = 'ACGT'.index(base)
+    left = []
+    for name, seq in ref.items():
+        fwd = _CODE[np.frombuffer(seq.encode('latin-1', 'replace'), dtype=np.uint8)]
+        plus = meth[name][0] & (fwd == b) & ~explained[name][0]
+        minus = meth[name][1] & (fwd == 3 - b) & ~explained[name][1]
+        at = np.nonzero(plus | minus)[0]
+        left += ['%s\t%d\t%d\t.\t.\t%s\n' % (name, p, p + 1, '-' if minus[p] else '+') for p in at.tolist()]
+    counts.update(n_rounds=len(out), n_explained=n_explained, n_unexplained=len(left))
+    return b''.join(out), len(out), counts, ''.join(left).encode('latin-1', 'replace')
 
 
 def _write(out, data):
@@ -328,43 +419,69 @@ def _checked(base, shapes, min_sites, min_fraction):
     return base, shapes, min_sites, min_fraction
 
 
-def _host(reference, bed, control, base, shapes, min_sites, min_fraction, keep_all, out, reason, iupac=False):
+def _checked_iterative(iterative, max_motifs, unexplained):
+    if unexplained is not None and not iterative:
+        raise ValueError('--unexplained goes with --iterative')
+    if isinstance(max_motifs, bool) or not isinstance(max_motifs, (int, np.integer)) or not 1 <= max_motifs <= MAX_MOTIFS:
+        raise ValueError('--max_motifs %r: 1 to %d' % (max_motifs, MAX_MOTIFS))
+    return int(max_motifs)
+
+
+def _host(reference, bed, control, base, shapes, min_sites, min_fraction, keep_all, out, reason, iupac=False, iterative=False, max_motifs=16,
+          unexplained=None):
     global last_report, last_counts
     last_report = last_counts = None
     ref = read_reference(reference)
     meth = read_sites(bed, ref)
     ctl = None if control is None else read_sites(control, ref)
-    data, n_rows, counts = report_rows(ref, shapes, base, meth, ctl, min_sites, min_fraction, keep_all, iupac)
+    if iterative:
+        data, n_rows, counts, left = iterative_rows(ref, shapes, base, meth, ctl, min_sites, min_fraction, keep_all, iupac, max_motifs)
+        if unexplained is not None:
+            _write(unexplained, left)
+    else:
+        data, n_rows, counts = report_rows(ref, shapes, base, meth, ctl, min_sites, min_fraction, keep_all, iupac)
     _write(out, data)
     last_counts = counts
     last_report = dict(by='host', reason=reason, n_rows=n_rows)
     return n_rows
 
 
-def find_motifs(reference, bed, control=None, base='A', shapes=None, min_sites=20, min_fraction=0.5, keep_all=False, out=None, iupac=False):
+def find_motifs(reference, bed, control=None, base='A', shapes=None, min_sites=20, min_fraction=0.5, keep_all=False, out=None, iupac=False,
+                iterative=False, max_motifs=16, unexplained=None):
     """The host statement: the definition above in NumPy -> the number of rows."""
     base, shapes, min_sites, min_fraction = _checked(base, shapes, min_sites, min_fraction)
-    return _host(reference, bed, control, base, shapes, min_sites, min_fraction, keep_all, out, 'the host statement was asked for', iupac)
+    max_motifs = _checked_iterative(iterative, max_motifs, unexplained)
+    return _host(reference, bed, control, base, shapes, min_sites, min_fraction, keep_all, out, 'the host statement was asked for', iupac,
+                 iterative, max_motifs, unexplained)
 
 
 def find_motifs_device(reference, bed, control=None, base='A', shapes=None, min_sites=20, min_fraction=0.5, keep_all=False, out=None,
-                        iupac=False):
+                        iupac=False, iterative=False, max_motifs=16, unexplained=None):
     """The same bytes made on the GPU, or -- when the device declines -- by the host statement, which also words the errors."""
     global last_report, last_counts
     base, shapes, min_sites, min_fraction = _checked(base, shapes, min_sites, min_fraction)
+    max_motifs = _checked_iterative(iterative, max_motifs, unexplained)
     last_report = last_counts = None
     if len(shapes) > MAX_SHAPES:
         reason = 'the device takes at most %d shapes in one call' % MAX_SHAPES
     else:
         from .device import get_device
         ref = read_reference(reference)
-        blob, n_rows, reason = get_device().motif_report(ref, path=bed, control_path=control, base=base, shapes=shapes, min_sites=min_sites,
-                                                         min_fraction=min_fraction, keep_all=keep_all, iupac=iupac)
+        if iterative:
+            blob, n_rows, reason, left = get_device().motif_report(ref, path=bed, control_path=control, base=base, shapes=shapes,
+                                                                   min_sites=min_sites, min_fraction=min_fraction, keep_all=keep_all,
+                                                                   iupac=iupac, iterative=True, max_motifs=max_motifs,
+                                                                   left=unexplained is not None)
+        else:
+            blob, n_rows, reason = get_device().motif_report(ref, path=bed, control_path=control, base=base, shapes=shapes, min_sites=min_sites,
+                                                             min_fraction=min_fraction, keep_all=keep_all, iupac=iupac)
         if blob is not None:
+            if unexplained is not None:
+                _write(unexplained, left)
             _write(out, blob)
             last_report = dict(by='device', reason=None, n_rows=n_rows)
             return n_rows
-    return _host(reference, bed, control, base, shapes, min_sites, min_fraction, keep_all, out, reason, iupac)
+    return _host(reference, bed, control, base, shapes, min_sites, min_fraction, keep_all, out, reason, iupac, iterative, max_motifs, unexplained)
 
 
 def main(argv=None):
@@ -383,7 +500,14 @@ def main(argv=None):
     parser.add_argument('--iupac', action='store_true', required=False, help='merge rows into degenerate (IUPAC) motifs')
     parser.add_argument('-o', '--output', type=str, required=False, help='write the rows to this file (default: standard output)')
     parser.add_argument('--device', action='store_true', required=False, help='count on the GPU (the host statement runs when it declines)')
+    parser.add_argument('--iterative', action='store_true', required=False,
+                        help='print the best row, set the candidates it explains aside, look again; until nothing passes')
+    parser.add_argument('--max_motifs', type=int, required=False, default=16, help='with --iterative: at most this many rows, 1 to 64 (default: 16)')
+    parser.add_argument('--unexplained', type=str, required=False,
+                        help='with --iterative: write the methylated sites no printed row explains to this file, as a bed')
     args = parser.parse_args(argv)
+    if args.unexplained is not None and not args.iterative:
+        parser.error('--unexplained goes with --iterative')
 
     assert os.path.isfile(args.reference), 'file not found at ' + args.reference
     assert os.path.isfile(args.bed), 'file not found at ' + args.bed
@@ -391,7 +515,7 @@ def main(argv=None):
 
     run = find_motifs_device if args.device else find_motifs
     return run(args.reference, args.bed, args.control, args.base, args.shapes, args.min_sites, args.min_fraction, args.all, args.output,
-               args.iupac)
+               args.iupac, args.iterative, args.max_motifs, args.unexplained)
 
 
 if __name__ == '__main__':

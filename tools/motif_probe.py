@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """tools/motif_probe.py [--bases 4.6e6] [--runs 3] [--host-runs 1] [--json profiles/motif_probe.json]
                        [--kernel-stats profiles/motif_kernel_stats.csv] [--keep DIR] [--device-only] [--host-only] [--seed 7]
-                       [--iupac]
+                       [--iupac] [--iterative [--max-motifs 16]]
 
 A reference and two make_bed summaries to the rows of find_motifs, host statement against device, file to file on the same box:
   host    find_motifs.find_motifs          (NumPy)
@@ -18,6 +18,11 @@ of every CAAYNNNNNRTAC are methylated too; the first rows (in the result) hold G
 CAAYNNNNNRTAC as the rows of the seven-letter shapes that explain it (CAANNNNNNRTAC:3, CAAYNNNNNNTAC:3).  Meant to be
 run with --host-runs 3 --json profiles/motif_iupac_probe.json --kernel-stats profiles/motif_iupac_kernel_stats.csv; the stats of
 mc_motif_report_iupac_last_stats go into the result.
+--iterative: the two legs with find_motifs --iterative (csrc/motifs/mc_motifiter.inc) on the genome of --iupac, in the plain mode or,
+with --iupac, in that mode; the rows AND the --unexplained files are compared.  mc_motif_report_iter_last_stats goes into the result
+with ms_first_round and the mean of the later rounds (ms_later_rounds / (n_rounds - 1): each holds the explain step of the row
+before it, km_uncount and the selection; in --iupac the lattices are made anew in every round).  Meant to be run with --host-runs 3
+--json profiles/motif_iter_probe.json --kernel-stats profiles/motif_iter_kernel_stats.csv.
 --host-only needs no GPU.  --kernel-stats: the kernels' times from a `rocprofv3 --kernel-trace --stats` run of this tool's own
 (--device-only), the program behind `--`, under its own time limit."""
 import glob
@@ -99,13 +104,13 @@ def write_case(d, n_bases, seed, iupac=False):
                                bed_bytes=os.path.getsize(bed), control_bytes=os.path.getsize(ctl))
 
 
-def kernel_stats(out_csv, n_bases, seed, iupac=False):
+def kernel_stats(out_csv, n_bases, seed, iupac=False, more=()):
     """The kernels' times of the device path alone, from a rocprofv3 run of this tool in a process of its own."""
     d = tempfile.mkdtemp(prefix='mc_motif_stats_')
     try:
         cmd = ['timeout', '-k', '10', '600', 'rocprofv3', '--kernel-trace', '--stats', '--output-format', 'csv', '-d', d, '--', sys.executable,
                os.path.abspath(__file__), '--device-only', '--bases', str(n_bases), '--runs', '2', '--seed', str(seed)]
-        cmd += ['--iupac'] if iupac else []
+        cmd += (['--iupac'] if iupac else []) + list(more)
         subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL)
         found = glob.glob(os.path.join(d, '**', '*kernel_stats.csv'), recursive=True)
         if not found:
@@ -120,17 +125,23 @@ def main():
     n_bases = int(float(arg('--bases', '4.6e6')))
     runs, host_runs, seed = int(arg('--runs', '3')), int(arg('--host-runs', '1')), int(arg('--seed', '7'))
     device_only, host_only, iupac = '--device-only' in sys.argv, '--host-only' in sys.argv, '--iupac' in sys.argv
+    iterative, max_motifs = '--iterative' in sys.argv, int(arg('--max-motifs', '16'))
     d = arg('--keep', None) or tempfile.mkdtemp(prefix='mc_motif_probe_')
     os.makedirs(d, exist_ok=True)
-    ref, bed, ctl, r = write_case(d, n_bases, seed, iupac)
+    ref, bed, ctl, r = write_case(d, n_bases, seed, iupac or iterative)
     r['iupac'] = iupac
     out_d, out_h = os.path.join(d, 'device.tsv'), os.path.join(d, 'host.tsv')
+    left_d, left_h = os.path.join(d, 'device.bed'), os.path.join(d, 'host.bed')
+    more = {}
+    if iterative:
+        r.update(iterative=True, max_motifs=max_motifs)
+        more = dict(iterative=True, max_motifs=max_motifs)
     r['host_cores'] = int(_lib.lib().mc_host_cores())
     if not host_only:
         from mcaller_amd.device import get_device
 
         def device():
-            find_motifs.find_motifs_device(ref, bed, ctl, out=out_d, iupac=iupac)
+            find_motifs.find_motifs_device(ref, bed, ctl, out=out_d, iupac=iupac, **(dict(more, unexplained=left_d) if iterative else {}))
             return find_motifs.last_report
 
         who = device()                                          # warm-up: pinned blocks, the first launches, the files in the page cache
@@ -147,15 +158,21 @@ def main():
                      first_rows=open(out_d).read().splitlines()[:6 if iupac else 4])
             if iupac:
                 r.update(iupac_stats=get_device().motif_report_iupac_last_stats())
+            if iterative:
+                it = get_device().motif_report_iter_last_stats()
+                r.update(iter_stats=it, rows=open(out_d).read().splitlines(), ms_first_round=it['ms_first_round'],
+                         ms_later_round_mean=it['ms_later_rounds'] / (it['n_rounds'] - 1) if it['n_rounds'] > 1 else None)
     if not device_only:
         t_host = []
         for _ in range(host_runs):
             t = time.perf_counter()
-            find_motifs.find_motifs(ref, bed, ctl, out=out_h, iupac=iupac)
+            find_motifs.find_motifs(ref, bed, ctl, out=out_h, iupac=iupac, **(dict(more, unexplained=left_h) if iterative else {}))
             t_host.append(time.perf_counter() - t)
         r.update(host_s=statistics.median(t_host), host_all_s=t_host, host_runs=host_runs)
         if 'device_s' in r:
             assert open(out_h, 'rb').read() == open(out_d, 'rb').read(), 'the device\'s rows differ from the host statement\'s'
+            if iterative:
+                assert open(left_h, 'rb').read() == open(left_d, 'rb').read(), 'the device\'s left-over sites differ from the host statement\'s'
             r.update(ratio=r['host_s'] / r['device_s'], files_equal=True)
     print(json.dumps(r), flush=True)
     out = arg('--json', None)
@@ -167,7 +184,7 @@ def main():
     if stats_csv and not device_only and not host_only:
         from mcaller_amd.device import get_device
         get_device().motif_report_release()
-        kernel_stats(stats_csv, n_bases, seed, iupac)
+        kernel_stats(stats_csv, n_bases, seed, iupac, ['--iterative', '--max-motifs', str(max_motifs)] if iterative else [])
     if not arg('--keep', None):
         shutil.rmtree(d, ignore_errors=True)
 
