@@ -61,7 +61,13 @@ typedef struct mc_table_view {
     const int32_t *seg_read;      /* [n_seg] read id: equal names <=> equal ids               :161 */
     const int32_t *seg_contig;    /* [n_seg] contig id (index into the reference set)         :154 */
     int32_t n_reads;
+    const uint8_t *model_n_bits;  /* [ceil(n_rows / 8)] bit r & 7 of byte r >> 3: (flags[r] & MC_F_MODEL_N) != 0 -- the one bit of the
+                                     flag column the scan looks at, 1/8 B/row where the flag bytes are 1 (mc_pack_model_n).  NULL: the
+                                     upload calls pack it from `flags` */
 } mc_table_view;
+/* The model-N bit column of a flag column: out[r >> 3] bit r & 7 = (flags[r] & MC_F_MODEL_N) != 0, every byte of
+ * [0, ceil(n_rows / 8)) written (bits at or beyond n_rows: 0). */
+void mc_pack_model_n(const uint8_t *flags, int64_t n_rows, uint8_t *out);
 
 /* ---- marked reference: what find_and_methylate builds (extract_contexts.py:60-81), as bitmasks ---- */
 typedef struct mc_ref_view {
@@ -562,6 +568,8 @@ int mc_ctx_parse_abandon(mc_ctx *ctx, int32_t slot);
 /* The columns of the table in `slot` copied back to the host (any may be NULL) -- what the parity tests compare. */
 int mc_ctx_fetch_columns(mc_ctx *ctx, int32_t slot, int64_t n_rows, int32_t *pos, int32_t *event_model_e4, int32_t *event_idx,
                          uint8_t *flags);
+/* ... and its model-N bit column: ceil(n_rows / 8) bytes (bits at or beyond n_rows are whatever the slot holds there). */
+int mc_ctx_fetch_model_n_bits(mc_ctx *ctx, int32_t slot, int64_t n_rows, uint8_t *out);
 
 /* ===== native `.diffs.<k>` row formatter (host), replaces the text assembly of the flush, extract_contexts.py:186-216 ===== */
 typedef struct mc_format_args {

@@ -99,6 +99,15 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def pack_model_n(flags):
+    """The model-N bit column of a flag column (mc_pack_model_n): bit r & 7 of byte r >> 3 is (flags[r] & F_MODEL_N) != 0."""
+    flags = np.ascontiguousarray(flags, dtype=np.uint8)
+    out = np.zeros((len(flags) + 7) // 8, dtype=np.uint8)
+    if len(flags):
+        lib().mc_pack_model_n(_ptr(flags), len(flags), _ptr(out))
+    return out
+
+
 def _from_ptr(ptr, n, dtype):
     if n == 0 or not ptr:
         return np.zeros(0, dtype=dtype)
@@ -132,7 +141,7 @@ class Table(object):
     column of (event, model) pairs, `evmu` [n, 2]; `event_e4` / `model_e4` are its two halves (strided views)."""
 
     def __init__(self, pos, event_e4, model_e4, event_idx, flags, seg_row_begin, seg_read, seg_contig, n_reads,
-                 read_names=None, unknown=(), owner=None, evmu=None):
+                 read_names=None, unknown=(), owner=None, evmu=None, model_n_bits=None):
         self.pos = np.ascontiguousarray(pos, dtype=np.int32)
         if evmu is None:
             evmu = np.empty((len(self.pos), 2), dtype=np.int32)
@@ -141,6 +150,8 @@ class Table(object):
         self.evmu = np.ascontiguousarray(evmu, dtype=np.int32).reshape(-1, 2)
         self.event_idx = np.ascontiguousarray(event_idx, dtype=np.int32)
         self.flags = np.ascontiguousarray(flags, dtype=np.uint8)
+        # the model-N bit column the table's maker wrote with the flags (a parser, pinned()); None: bare arrays
+        self._model_n_bits = None if model_n_bits is None else np.ascontiguousarray(model_n_bits, dtype=np.uint8)
         self.seg_row_begin = np.ascontiguousarray(seg_row_begin, dtype=np.int64)
         self.seg_read = np.ascontiguousarray(seg_read, dtype=np.int32)
         self.seg_contig = np.ascontiguousarray(seg_contig, dtype=np.int32)
@@ -159,6 +170,14 @@ class Table(object):
     def model_e4(self):
         return self.evmu[:, 1]
 
+    @property
+    def model_n_bits(self):
+        """The model-N bit column (mc_table_view.model_n_bits): the maker's, or -- a table built from bare arrays, whose flags
+        may have been edited since -- packed from the flags as they are now (mc_pack_model_n)."""
+        if self._model_n_bits is not None:
+            return self._model_n_bits
+        return None if self.flags is None else pack_model_n(self.flags)
+
     def pinned(self):
         """A copy whose columns sit in the pinned host pool (what mc_ctx_upload_table_async wants to read from)."""
         keep = []
@@ -169,7 +188,8 @@ class Table(object):
             keep.append(h)
             return h.array
         t = Table(pin(self.pos), None, None, pin(self.event_idx), pin(self.flags), self.seg_row_begin, self.seg_read,
-                  self.seg_contig, self.n_reads, read_names=self.read_names, unknown=self.unknown, evmu=pin(self.evmu))
+                  self.seg_contig, self.n_reads, read_names=self.read_names, unknown=self.unknown, evmu=pin(self.evmu),
+                  model_n_bits=pin(self.model_n_bits))
         t._owner = keep
         return t
 
@@ -180,6 +200,9 @@ class Table(object):
             v.pos, v.event_model_e4 = _ptr(self.pos), _ptr(self.evmu)
             v.event_idx = _ptr(self.event_idx)
         v.flags = _ptr(self.flags)
+        if self.pos is not None:
+            self._nbits_viewed = self.model_n_bits     # (kept: the view points into it)
+            v.model_n_bits = _ptr(self._nbits_viewed)
         v.n_seg = self.n_seg
         v.seg_row_begin, v.seg_read, v.seg_contig = _ptr(self.seg_row_begin), _ptr(self.seg_read), _ptr(self.seg_contig)
         v.n_reads = self.n_reads
@@ -188,10 +211,19 @@ class Table(object):
     def slice_segments(self, s0, s1):
         """Sub-table of segments [s0, s1) (a shard); row indices restart at 0, read ids are kept."""
         r0, r1 = int(self.seg_row_begin[s0]), int(self.seg_row_begin[s1])
+        # (the maker's bit column: whole bytes carry over when the cut falls on one, the bits of the rows behind the slice
+        # cleared; otherwise the slice's flags are packed again when the column is asked for)
+        bits = None
+        if self._model_n_bits is not None and r0 % 8 == 0:
+            bits = self._model_n_bits[r0 // 8:(r1 + 7) // 8]
+            if r1 % 8 and r1 < self.n_rows:
+                bits = bits.copy()
+                bits[-1] &= (1 << (r1 % 8)) - 1
         return Table(self.pos[r0:r1], None, None, self.event_idx[r0:r1],
                      self.flags[r0:r1], self.seg_row_begin[s0:s1 + 1] - r0, self.seg_read[s0:s1],
                      self.seg_contig[s0:s1], self.n_reads, read_names=self.read_names, owner=self._owner,
-                     evmu=self.evmu[r0:r1])
+                     evmu=self.evmu[r0:r1],
+                     model_n_bits=bits)
 
 
 class TextBlock(object):
@@ -241,6 +273,7 @@ def device_table(res, text):
     t = Table.__new__(Table)
     t.pos = t.evmu = t.event_idx = None                # (on the device only)
     t.flags = _from_ptr(res.flags, n, np.uint8).copy()
+    t._model_n_bits = None                             # (on the device only: kp_place wrote it with the flag column)
     rows = _from_ptr(res.seg_row_begin, ns, np.int64)
     t.seg_row_begin = np.concatenate([rows, np.array([n], dtype=np.int64)])
     t.seg_contig = _from_ptr(res.seg_contig, ns, np.int32).copy()
@@ -357,7 +390,8 @@ def parse_eventalign(path, startline, endline, contig_names, n_threads=0, exact_
               _from_ptr(v.event_idx, n, np.int32), _from_ptr(v.flags, n, np.uint8),
               _from_ptr(v.seg_row_begin, ns + 1, np.int64), _from_ptr(v.seg_read, ns, np.int32),
               _from_ptr(v.seg_contig, ns, np.int32), v.n_reads, read_names=names, unknown=unknown, owner=owner,
-              evmu=_from_ptr(v.event_model_e4, 2 * n, np.int32).reshape(-1, 2))
+              evmu=_from_ptr(v.event_model_e4, 2 * n, np.int32).reshape(-1, 2),
+              model_n_bits=_from_ptr(v.model_n_bits, (n + 7) // 8, np.uint8))
     t.n_pieces = int(L.mc_parsed_n_pieces(handle))
     return t
 

@@ -248,6 +248,18 @@ extern "C" int mc_host_pool_config(int32_t parser_uses_pool, int64_t keep_bytes)
     return 0;
 }
 
+// The model-N bit column of a flag column (mc_table_view::model_n_bits): what the scan streams in place of the flag bytes.
+// Whole bytes are written, the bits at or beyond n_rows as zeros.
+extern "C" void mc_pack_model_n(const uint8_t *flags, int64_t n_rows, uint8_t *out) {
+    static_assert(MC_F_MODEL_N == 2, "the bit picked out of the flag byte below");
+    for (int64_t b = 0; b * 8 < n_rows; ++b) {
+        const int64_t r0 = b * 8, n = n_rows - r0 < 8 ? n_rows - r0 : 8;
+        unsigned v = 0;
+        for (int64_t e = 0; e < n; ++e) v |= ((unsigned)(flags[r0 + e] >> 1) & 1u) << e;
+        out[b] = (uint8_t)v;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------
 // Marking a contig's motif sites (extract_contexts.py:33-41,:60-73 for a motif): seq.upper(), then str.replace(motif, repl)
 // for the motif and its reverse complement -- left to right, non-overlapping, len(repl) == len(motif).  CPython spends 14 ms

@@ -82,6 +82,8 @@ struct DevTable {
     int32_t *pos = nullptr, *idx = nullptr;
     int2 *evmu = nullptr;     // (event, model) pairs as the parser wrote them: one DRAM page per window for k1_emit
     uint8_t *flags = nullptr;
+    uint8_t *nbits = nullptr; // [ceil(n_rows / 8)] bit r & 7 of byte r >> 3: row r has an 'N' model k-mer (MC_F_MODEL_N of its flag byte) -- what
+                              // k1_scan streams in place of the flag bytes; written whole by whoever writes the flags
     int2 *unit_pp = nullptr;  // [ceil(n_rows / 8)] positions of the first and the last row of every unit of eight rows (k_summarize,
                               // when a table is scanned a second time): all the filter of a repeated scan looks at -- 1 B/row
     int32_t n_seg = 0;
@@ -501,8 +503,8 @@ struct LitArgs {
 
 // NumPy pairwise_sum over an array (np.mean of a slot list, :186)
 
-constexpr int SCAN_VALIDATE = 0;    // a table's first pass: positions, event indices and flag bytes streamed (9 B/row), every row validated
-constexpr int SCAN_STREAM = 1;      // a validated table, positions and flag bytes streamed (5 B/row): one-base motifs, where every unit is listed
+constexpr int SCAN_VALIDATE = 0;    // a table's first pass: positions, event indices and model-N bits streamed (8.125 B/row), every row validated
+constexpr int SCAN_STREAM = 1;      // a validated table, positions and model-N bits streamed (4.125 B/row): one-base motifs, where every unit is listed
 constexpr int SCAN_SUMMARY = 2;     // a validated table that has unit summaries (k_summarize): 1 B/row
 
 

@@ -535,13 +535,20 @@ struct KpPlaceArgs {
     int32_t *t_pos, *t_idx;
     int2 *t_evmu;
     uint8_t *t_flags;
+    uint8_t *t_nbits;               // the model-N bit column: one bit per row, made here from the rows' staged flag bytes
     KpSeg *segs;
     int cap_segs;
     KpUnknown *unknown;
 };
 
+// The model-N bit column (DevTable::nbits) is made here too, a byte per eight rows: the workgroup gathers the bits of its rows in
+// LDS, from the row of its first byte on (bit 0 = row base = first row & ~7), and WRITES every byte whose first row is one of
+// its own -- the last of these may need the rows of the lines behind the workgroup's, which wave 0 looks up (64 lines at a
+// time: status and staged flag byte are all it takes).  A byte that begins with an earlier workgroup's row is that workgroup's.
+// So every byte of [0, ceil(n_rows / 8)) is stored exactly once, whole, whatever the slot held before.
 __global__ __launch_bounds__(256) void kp_place(KpPlaceArgs A) {
     __shared__ int s_w[4];
+    __shared__ uint32_t s_nbits[10];                // bits of rows base .. base + 319 (7 in front, 256 rows, 7 behind)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t li = (int64_t)blockIdx.x * 256 + tid;
     const long long n_lines = min((long long)A.head->n_lines, (long long)A.cap_lines - 1);
@@ -549,9 +556,37 @@ __global__ __launch_bounds__(256) void kp_place(KpPlaceArgs A) {
     const bool is_row = st == KP_ST_ROW;
     const unsigned long long bal = __ballot(is_row);
     if (lane == 0) s_w[wave] = __popcll(bal);
+    if (tid < 10) s_nbits[tid] = 0u;
     __syncthreads();
-    long long row = A.blk_off[blockIdx.x] + __popcll(bal & ((1ull << lane) - 1ull));
+    const long long row0 = A.blk_off[blockIdx.x];
+    long long row = row0 + __popcll(bal & ((1ull << lane) - 1ull));
     for (int w = 0; w < wave; ++w) row += s_w[w];
+    {
+        const long long row_end = row0 + s_w[0] + s_w[1] + s_w[2] + s_w[3], base = row0 & ~7ll;
+        if (is_row && (A.fl[li] & MC_F_MODEL_N)) atomicOr(&s_nbits[(int)(row - base) >> 5], 1u << ((int)(row - base) & 31));
+        // (the rows behind the workgroup's that share its last byte -- only if that byte begins with one of its rows)
+        int need = (int)((8 - (row_end & 7)) & 7);
+        if (wave == 0 && row_end > row0 && ((row_end - 1) & ~7ll) >= row0 && need > 0) {
+            long long r = row_end;
+            for (int64_t l0 = (int64_t)blockIdx.x * 256 + 256; need > 0 && l0 < n_lines; l0 += 64) {       // (wave-uniform)
+                const int64_t l = l0 + lane;
+                const bool rw = l < n_lines && A.status[l] == KP_ST_ROW;
+                const unsigned long long rb = __ballot(rw);
+                const int nth = __popcll(rb & ((1ull << lane) - 1ull));
+                if (rw && nth < need && (A.fl[l] & MC_F_MODEL_N)) atomicOr(&s_nbits[(int)(r + nth - base) >> 5], 1u << ((int)(r + nth - base) & 31));
+                const int got = min(__popcll(rb), need);
+                r += got;
+                need -= got;
+            }
+        }
+        __syncthreads();
+        // bytes [b0, b1): those whose first row is in [row0, row_end) (and inside the slot)
+        const long long b0 = (row0 + 7) >> 3, b1 = min((row_end + 7) >> 3, (long long)((A.cap_rows + 7) >> 3));
+        if (b0 + tid < b1) {
+            const int off = (int)(b0 + tid - (base >> 3));
+            A.t_nbits[b0 + tid] = (uint8_t)(s_nbits[off >> 2] >> (8 * (off & 3)));
+        }
+    }
     if (st == KP_ST_UNKNOWN) {                          // :156-160: the line is skipped, the message names the contig
         const int k = atomicAdd(&A.head_w->n_unknown, 1);
         if (k < KP_MAX_UNKNOWN) { KpUnknown u; u.line = li; u.off = A.name_off[li]; u.len = A.name_len[li]; u.pad = 0; A.unknown[k] = u; }

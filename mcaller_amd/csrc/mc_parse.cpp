@@ -162,6 +162,7 @@ struct RawCol {
 struct mc_parsed {
     RawCol<int32_t> pos, evmu, idx;        // evmu: (event, model) pairs, two entries per row
     RawCol<uint8_t> flags;
+    RawCol<uint8_t> nbits;                 // the model-N bit column (mc_table_view::model_n_bits), written with the flags
     int n_pieces = 0;                      // pieces the byte range was cut into (one parser thread each)
     std::vector<int64_t> seg_begin;
     std::vector<int32_t> seg_read, seg_contig;
@@ -649,7 +650,8 @@ static int parse_file(const char *path, int64_t startline, int64_t endline, bool
     mc_parsed *P = new mc_parsed();
     P->n_pieces = np;
     if (!P->pos.alloc((size_t)total) || !P->evmu.alloc((size_t)total * 2) ||
-        !P->idx.alloc((size_t)total) || !P->flags.alloc((size_t)total)) {
+        !P->idx.alloc((size_t)total) || !P->flags.alloc((size_t)total) ||
+        !P->nbits.alloc((size_t)(total + 7) / 8)) {
         delete P;
         mc_set_error("out of memory for %lld rows", (long long)total);
         return -10;
@@ -667,6 +669,20 @@ static int parse_file(const char *path, int64_t startline, int64_t endline, bool
                 memcpy(P->evmu.data() + 2 * o, C.evmu.data(), n * 8);
                 memcpy(P->idx.data() + o, C.idx.data(), n * 4);
                 memcpy(P->flags.data() + o, C.flags.data(), n);
+                // the model-N bits of the bytes whose first row is this piece's (the last of them may run on into the pieces
+                // behind: their flags are read where the parser threads left them)
+                for (int64_t b = (o + 7) >> 3; b * 8 < o + (int64_t)n; ++b) {
+                    unsigned v = 0;
+                    int pj = i;
+                    int64_t pj_end = o + (int64_t)n;
+                    for (int e = 0; e < 8 && b * 8 + e < total; ++e) {
+                        const int64_t r = b * 8 + e;
+                        while (r >= pj_end) pj_end += (int64_t)chunks[(size_t)++pj].pos.size();
+                        const Chunk &D = chunks[(size_t)pj];
+                        if (D.flags[(size_t)(r - (pj_end - (int64_t)D.pos.size()))] & MC_F_MODEL_N) v |= 1u << e;
+                    }
+                    P->nbits[(size_t)b] = (uint8_t)v;
+                }
             }
             C.n_rows = (int64_t)n;
         };
@@ -764,6 +780,7 @@ extern "C" int mc_parsed_view(const mc_parsed *p, mc_table_view *out) {
     out->event_model_e4 = p->evmu.data();
     out->event_idx = p->idx.data();
     out->flags = p->flags.data();
+    out->model_n_bits = p->nbits.data();
     out->n_seg = (int32_t)p->seg_read.size();
     out->seg_row_begin = p->seg_begin.data();
     out->seg_read = p->seg_read.data();

@@ -90,7 +90,7 @@ __device__ __noinline__ RowRes far_row(const ScanGlobals G, const uint32_t *gbit
 
 struct __attribute__((aligned(16))) CandUnit {    // eight rows that may hold a site row, with the two rows behind them
     int32_t pos[10];
-    uint8_t fl[10];     // their flag bytes
+    uint8_t fl[10];     // their flag bytes (MC_F_MODEL_N or nothing where they were made from the bit column)
     uint16_t i0;        // first row of the unit (tile-relative)
     uint32_t mw[3];     // two words of the block's strand mask, and the word they start at (-1: none)
 };
@@ -276,23 +276,25 @@ __device__ __forceinline__ int64_t desc_row_end_uniform(const NbDesc *desc, int 
     return v;
 }
 
-#ifndef MC_STREAM_FLAGS
-#define MC_STREAM_FLAGS 1           // (variant builds: 0 = the flag bytes are not streamed, the listed units fetch theirs)
-#endif
-template <int MODE> constexpr bool flags_streamed() { return MODE != SCAN_SUMMARY && MC_STREAM_FLAGS != 0; }
+// (the one bit of the flag byte the scan looks at comes with the columns, from the table's bit column: SCAN_SUMMARY, which
+// streams unit summaries only, fetches the flag bytes of the units it lists)
+template <int MODE> constexpr bool nbits_streamed() { return MODE != SCAN_SUMMARY; }
+static_assert(MC_F_MODEL_N == 2, "flag_bytes(): where the bit goes in the flag byte");
+// four bits -> four flag bytes that hold MC_F_MODEL_N or nothing (one multiplication spreads the bits to bit 0 of the bytes)
+__device__ __forceinline__ uint32_t flag_bytes(uint32_t b4) { return (((b4 & 0xFu) * 0x00204081u) & 0x01010101u) << 1; }
 
 // The columns of one chunk in registers: every lane holds eight consecutive rows (a unit) of each 512-row stripe.
 template <int MODE>
 struct ChunkCols {
     int4 pa[NQ], pb[NQ];            // positions of rows i0 .. i0+3, i0+4 .. i0+7 of the lane's unit in stripe j (SCAN_SUMMARY: pa.x, pb.w only)
     int4 xa[NQ], xb[NQ];            // ... their event indices (SCAN_VALIDATE)
-    uint2 fl[NQ];                   // ... their flag bytes (not SCAN_SUMMARY)
+    uint32_t nb[NQ];                // ... their model-N bits, one byte of the table's bit column (not SCAN_SUMMARY)
     __device__ __forceinline__ void load(const DevTable &T, int64_t c0, int crows, int lane) {
 #pragma unroll
         for (int j = 0; j < NQ; ++j) {
             const int i0 = (j * 64 + lane) * 8;
             pa[j] = pb[j] = xa[j] = xb[j] = make_int4(0, 0, 0, 0);
-            fl[j] = make_uint2(0x02020202u, 0x02020202u);       // (rows past the table: MC_F_MODEL_N, never looked at anyway)
+            nb[j] = 0xFFu;                                      // (rows past the table: 'N', never looked at anyway)
             if (i0 < crows) {                       // (arrays are padded: whole units stay in bounds)
                 if (MODE == SCAN_SUMMARY) {
                     const int2 pp = T.unit_pp[(c0 + i0) >> 3];
@@ -301,7 +303,7 @@ struct ChunkCols {
                 } else {
                     pa[j] = *reinterpret_cast<const int4 *>(T.pos + c0 + i0);
                     pb[j] = *reinterpret_cast<const int4 *>(T.pos + c0 + i0 + 4);
-                    if (flags_streamed<MODE>()) fl[j] = *reinterpret_cast<const uint2 *>(T.flags + c0 + i0);
+                    nb[j] = T.nbits[(c0 + i0) >> 3];            // (a chunk begins at a multiple of eight rows: the lane's unit is one byte)
                     if (MODE == SCAN_VALIDATE) {
                         xa[j] = *reinterpret_cast<const int4 *>(T.idx + c0 + i0);
                         xb[j] = *reinterpret_cast<const int4 *>(T.idx + c0 + i0 + 4);
@@ -317,7 +319,7 @@ struct ChunkCols {
 // them there: the registers carry the next chunk's columns meanwhile), and every lane examines the eight rows of its unit of
 // each stripe with the two rows behind them (the next lane's): first which of them are last rows of windows, then -- the
 // lanes' counts added up -- the payloads, in row order.
-struct DenseStash { const int4 *pa, *pb, *fw; const int *dec; };      // [NQ * 64]: positions 0..3, 4..7 | flag bytes 0..7, the unit's two mask words | decidable
+struct DenseStash { const int4 *pa, *pb, *fw; const int *dec; };      // [NQ * 64]: positions 0..3, 4..7 | model-N bits 0..7, -, the unit's two mask words | decidable
 __device__ __forceinline__ void dense_block_rows(const K1Args &A, TileSlots &S, long long &ahead, DenseStash L, int nb_abs, int64_t c0,
                                                  int64_t c1, int2 tail_p, uint32_t tail_f) {
     const DevTable &T = A.T;
@@ -347,7 +349,6 @@ __device__ __forceinline__ void dense_block_rows(const K1Args &A, TileSlots &S, 
         if (j * 512 + 512 <= lo || j * 512 >= hi) continue;      // (wave-uniform)
         const int i0 = (j * 64 + lane) * 8;
         const int4 qa = L.pa[j * 64 + lane], qb = L.pb[j * 64 + lane], qw = L.fw[j * 64 + lane];
-        const uint2 qf = make_uint2((uint32_t)qw.x, (uint32_t)qw.y);
         // the two rows behind the unit: the next lane's first two (lane 63: the next stripe's, or the rows behind the chunk)
         const int un = j * 64 + lane + 1;           // (unit behind this one, < NQ * 64 unless this is the chunk's last)
         const bool last = un >= NQ * 64;
@@ -355,14 +356,8 @@ __device__ __forceinline__ void dense_block_rows(const K1Args &A, TileSlots &S, 
         const int nx = last ? tail_p.x : na.x, ny = last ? tail_p.y : na.y;
         const uint32_t nf = last ? tail_f : (uint32_t)nw.x;
         const int ps[10] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w, nx, ny};
-        // bit e: row e of the ten has an 'N' model k-mer (MC_F_MODEL_N is bit 1 of the flag byte)
-        static_assert(MC_F_MODEL_N == 2, "the bit picked out of the flag bytes below");
-        uint32_t nbits = 0;
-#pragma unroll
-        for (int e = 0; e < 10; ++e) {
-            const uint32_t wd = e < 4 ? qf.x : e < 8 ? qf.y : nf;
-            nbits |= ((wd >> (8 * (e & 3) + 1)) & 1u) << e;
-        }
+        // bit e: row e of the ten has an 'N' model k-mer (the unit's byte of the bit column, and two bits of the next)
+        const uint32_t nbits = ((uint32_t)qw.x & 0xFFu) | ((nf & 3u) << 8);
         // ... is a row of the block that is tested (>= lo) / lies in front of the block's (the chunk's) end: all ten at once
         const uint32_t below_hi = (1u << min(max(hi - i0, 0), 10)) - 1u, from_lo = ~((1u << min(max(lo - i0, 0), 10)) - 1u);
         const uint32_t act = below_hi & from_lo & ~nbits & 0xFFu;
@@ -467,7 +462,8 @@ __device__ __forceinline__ void dense_block_rows(const K1Args &A, TileSlots &S, 
 // of the current one are free, and travel while the current chunk's candidates are examined.
 //
 // The columns of a chunk go from HBM into REGISTERS -- every lane holds eight consecutive rows (a unit) of each 512-row stripe.
-// On a table's first pass (SCAN_VALIDATE) these are the positions, the event indices and the flag bytes, 9 B/row, and every row
+// On a table's first pass (SCAN_VALIDATE) these are the positions, the event indices and the model-N bits -- the table's bit
+// column, a byte per unit: the one bit of the flag byte the scan looks at, MC_F_MODEL_N -- 8.125 B/row, and every row
 // is compared with the row before it -- its neighbour in the lane, the previous lane's last row (one shuffle), the last row of
 // the chunk before -- which gives the validation flags of the chunk's name blocks: a chunk inside one block (the usual case)
 // ends with wave-wide flags that are held against what the block was classified on, and nothing is written unless they say
@@ -475,8 +471,8 @@ __device__ __forceinline__ void dense_block_rows(const K1Args &A, TileSlots &S, 
 //
 // 95 % of the units never leave the registers: one 32-bit extract from the strand bitmask (two words per unit, fetched
 // straight from L2 -- the masks of a bacterial genome are 0.6 MB per strand) tells whether any of the unit's k-mers holds an
-// 'M' at all.  Only the units that pass are written to an LDS list, with the two rows behind them, their flag bytes and their
-// mask words (where the filter read unit summaries instead of the columns, SCAN_SUMMARY, one lane per listed unit fetches its
+// 'M' at all.  Only the units that pass are written to an LDS list, with the two rows behind them, their model-N bits (a flag
+// byte each again) and their mask words (where the filter read unit summaries instead of the columns, SCAN_SUMMARY, one lane per listed unit fetches its
 // rows and flag bytes now); then -- the columns' registers are free again, the next chunk's columns are on their way -- one lane
 // per row of the listed units decides whether the row is the LAST row of a window: its k-mer holds an 'M' (first one: the
 // site m, :176) and the next unfiltered row of the read lies beyond m, or there is none and another read (or the next shard)
@@ -515,7 +511,8 @@ __global__ __launch_bounds__(64) MC_SCAN_ATTR void k1_scan(K1Args A) {
     uint32_t tail_f = 0;
     auto load_tail = [&](int64_t c1) {
         tail_p = make_int2(T.pos[c1], T.pos[c1 + 1]);
-        tail_f = (uint32_t)T.flags[c1] | ((uint32_t)T.flags[c1 + 1] << 8);
+        // (their model-N bits, bits 0 and 1: c1 is no multiple of eight at the table's end)
+        tail_f = ((((uint32_t)T.nbits[(c1 >> 3) + 1] << 8) | (uint32_t)T.nbits[c1 >> 3]) >> (int)(c1 & 7)) & 3u;
     };
     if constexpr (CG > 64) load_tail(t0 + min(nrows, CHUNK));
     int before_p = 0, before_x = 0;                 // the row before the chunk (its first row's predecessor, if that is in its block)
@@ -642,13 +639,13 @@ __global__ __launch_bounds__(64) MC_SCAN_ATTR void k1_scan(K1Args A) {
             // (the chunk out of the registers into LDS, every lane its own units: the loop below is one copy of the code for both
             // stripes, the rows behind a unit are the next lane's without a shuffle, and the registers are free for the next
             // chunk's columns, which set out now)
-            __shared__ int4 s_pa[NQ][64], s_pb[NQ][64], s_fw[NQ][64];      // positions 0..3, 4..7 | flag bytes 0..7, the unit's two mask words
+            __shared__ int4 s_pa[NQ][64], s_pb[NQ][64], s_fw[NQ][64];      // positions 0..3, 4..7 | model-N bits 0..7, -, the unit's two mask words
             __shared__ int s_dec[NQ][64];
 #pragma unroll
             for (int j = 0; j < NQ; ++j) {
                 s_pa[j][lane] = C.pa[j];
                 s_pb[j][lane] = C.pb[j];
-                s_fw[j][lane] = make_int4((int)C.fl[j].x, (int)C.fl[j].y, (int)mlo[j], (int)mhi[j]);
+                s_fw[j][lane] = make_int4((int)C.nb[j], 0, (int)mlo[j], (int)mhi[j]);
                 s_dec[j][lane] = decidable[j] ? 1 : 0;
             }
             const int2 tail_p_now = tail_p;
@@ -697,14 +694,14 @@ __global__ __launch_bounds__(64) MC_SCAN_ATTR void k1_scan(K1Args A) {
                     if (ncand + __popcll(bal) > CG) { overflow = true; continue; }
                     // the two rows behind the unit: the next lane's first two rows (lane 63: the next stripe's)
                     int nx = 0, ny = 0;
-                    uint32_t nf = 0x0202u;
+                    uint32_t nf = 0x3u;                 // (their model-N bits)
                     if (MODE != SCAN_SUMMARY) {
                         nx = __shfl_down(C.pa[j].x, 1);
                         ny = __shfl_down(C.pa[j].y, 1);
-                        nf = __shfl_down(C.fl[j].x, 1);
+                        nf = __shfl_down(C.nb[j], 1);
                         if (j + 1 < NQ) {
                             const int sx = __shfl(C.pa[(j + 1) % NQ].x, 0), sy = __shfl(C.pa[(j + 1) % NQ].y, 0);
-                            const uint32_t sf = __shfl(C.fl[(j + 1) % NQ].x, 0);
+                            const uint32_t sf = __shfl(C.nb[(j + 1) % NQ], 0);
                             if (lane == 63) { nx = sx; ny = sy; nf = sf; }
                         }
                     }
@@ -714,12 +711,12 @@ __global__ __launch_bounds__(64) MC_SCAN_ATTR void k1_scan(K1Args A) {
                         if (MODE != SCAN_SUMMARY) {
                             gp[0] = C.pa[j];
                             gp[1] = C.pb[j];
-                            // pos[8], pos[9] | flag bytes 0..7
-                            gp[2] = make_int4(nx, ny, (int)C.fl[j].x, (int)C.fl[j].y);
+                            // pos[8], pos[9] | flag bytes 0..7: the unit's model-N bits, a byte each again for the lanes that decide
+                            gp[2] = make_int4(nx, ny, (int)flag_bytes(C.nb[j]), (int)flag_bytes(C.nb[j] >> 4));
                         }
                         // flag bytes 8, 9 and the unit's first row | its two mask words and the word they start at (-1: none, every
                         // lookup out of line)
-                        gp[3] = make_int4((int)((nf & 0xFFFFu) | ((uint32_t)i0 << 16)), (int)mlo[j], (int)mhi[j], decidable[j] ? (p0 >> 5) : -1);
+                        gp[3] = make_int4((int)((flag_bytes(nf) & 0xFFFFu) | ((uint32_t)i0 << 16)), (int)mlo[j], (int)mhi[j], decidable[j] ? (p0 >> 5) : -1);
                     }
                     ncand += __popcll(bal);
                 }
@@ -732,7 +729,7 @@ __global__ __launch_bounds__(64) MC_SCAN_ATTR void k1_scan(K1Args A) {
             scan_blocks_slowly(A, nb0, nfast, c0, c1, S, lane);
         } else {
             __syncthreads();                            // (one wave: orders the list's words between the lanes)
-            if (!flags_streamed<MODE>()) {
+            if (!nbits_streamed<MODE>()) {
                 // the flag bytes of the listed units and of the two rows behind each (the columns are padded beyond the table's
                 // last row); SCAN_SUMMARY: their positions as well
                 for (int base = 0; base < ncand; base += 64) {

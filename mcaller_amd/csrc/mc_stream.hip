@@ -10,7 +10,8 @@
 //
 //   text         kp_count / kp_scan / kp_starts / kp_parse / kp_count_rows / kp_place   the eventalign TEXT of a streamed shard
 //                                parsed on the device (mc_devparse.inc): line starts, tokens, numbers, name blocks and segments,
-//                                the columns written straight into a table slot
+//                                the columns written straight into a table slot -- the model-N bit column (one bit per row:
+//                                the row's model k-mer is NNNNNN) with them, a byte per eight rows put together in kp_place
 //   per table     (nothing runs at upload: the first pass over a table validates it while it scans)
 //                (nb_template     the pass-independent fields of the name-block descriptors: inside the first k0_first_site over a table)
 //                k_summarize     a table that is scanned a second time gets unit summaries (first / last position of every
@@ -21,14 +22,15 @@
 //                                (direction of the event index, position 0) and the scan confirms it
 //                k0_classify / k0_extend   tables with repeated read names; irregular runs widened
 //                k1_scan         THE SCAN: one wave per tile of 2048 rows, nothing persistent.  First pass over a table: the
-//                                position and event-index columns (8 B/row) go from HBM into registers and every row is
+//                                position and event-index columns and the model-N bit column (8.125 B/row: the one bit of
+//                                the flag byte the scan looks at) go from HBM into registers and every row is
 //                                compared with the row before it (positions non-decreasing? event index strictly monotone?
 //                                -- what makes a name block "regular"); units of eight rows that can hold a site row are
 //                                found with one extract from the strand bitmask (two words per unit, straight from L2) and
-//                                listed in LDS, the listed units fetch their flag bytes, their rows are tested for "last row
+//                                listed in LDS with their model-N bits, their rows are tested for "last row
 //                                of a window"; every closed window leaves a 32-byte payload.  Later passes over the same
-//                                table read the unit summaries instead (1 B/row); one-base motifs, where every unit passes,
-//                                stream the positions.
+//                                table read the unit summaries instead (1 B/row; the listed units fetch their flag bytes);
+//                                one-base motifs, where every unit passes, stream the positions and the bits.
 //                k1_group_scan / k1_list   file order of the windows; payloads gathered into it
 //                k1_emit         eight lanes per window: which of the rows before its last row belong to which slot, slot
 //                                means in NumPy pairwise order (fp64) from the rows' (event, model) pairs -> one flush record
