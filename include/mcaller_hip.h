@@ -613,17 +613,28 @@ int mc_repr_fixed4(int32_t d, char *out32);
  * 1e-29 <= |v| < 1e9 and for zero; -> length, -1: a double it does not print. */
 int mc_repr_double_rowtext(double v, char *out32);
 
+/* ===== what the calls below that take whole text files through the GPU read from: a host text or a regular file =====
+ * A file is read in pinned blocks (mc_read_file_range) while the block before is on its way to the device; its bytes give what
+ * the same bytes as a text give.  Every source of a call is taken on its own: a file may stand beside a text.  A call returns
+ * -12 for a source that is null where one is required, has a text and a path, n_bytes < 0, or n_bytes > 0 and neither; and -1
+ * for a path that is no readable regular file. */
+typedef struct mc_text_source {
+    const char *text;              /* a host text of n_bytes (may be null when n_bytes == 0) ...                            */
+    const char *path;              /* ... or, when not null, a regular file (text must be null; n_bytes is ignored: the file is sized) */
+    int64_t n_bytes;
+} mc_text_source;
+
 /* ===== the per-site summary of a `.diffs.<k>` file on the GPU (make_bed.py:67-164 for BED, BED --control, BED --vo, GFF) =====
- * The text of the file -> the bytes make_bed writes: rows whose context has 'M' at its centre, grouped by the exact bytes of
- * (chrom, pos, strand, context) in first-occurrence order, an entry written when depth >= min_depth and
+ * mc_bed_summarise: the text of the file (src) -> the bytes make_bed writes: rows whose context has 'M' at its centre, grouped
+ * by the exact bytes of (chrom, pos, strand, context) in first-occurrence order, an entry written when depth >= min_depth and
  * (n_meth / depth >= mod_threshold) != control.  Integer counts, byte comparisons and one fp64 division: the bytes are the
  * reference's, or the call declines -- *status = 1, mc_last_error says why (and mc_bed_last_stats which line), nothing is
  * handed out and the caller runs the host code on the file.  Declined: a byte >= 0x80, a control byte other than tab and
  * newline (0x7f included), a line that is not 7 or 8 tab-separated fields (an empty line is one), a position that is not
  * 1-9 decimal digits, an empty context or label, a 7-field row with with_probs, a line longer than 65535 bytes, 2^31 - 2
- * lines or more, gff together with with_probs, a text that does not fit into free device memory beside its tables (the
- * whole text stays resident).  *out points at n_out bytes of pinned memory owned by the context: valid until the next
- * mc_bed_* call on it or mc_bed_release.  Test knobs (environment): MCALLER_BED_HASH_MASK=<hex> is anded onto the 64-bit
+ * lines or more, gff together with with_probs without site_stats, a text that does not fit into free device memory beside its
+ * tables (the whole text stays resident).  *out points at n_out bytes of pinned memory owned by the context: valid until the next
+ * mc_bed_summarise call on it or mc_bed_release.  Test knobs (environment): MCALLER_BED_HASH_MASK=<hex> is anded onto the 64-bit
  * hash of the key bytes; MCALLER_BED_TABLE_SLOTS=<n> fixes the number of table slots (fewer than 2 x the counted rows:
  * declined). */
 typedef struct mc_bed_params {
@@ -632,7 +643,7 @@ typedef struct mc_bed_params {
     int32_t control;               /* --control                                           */
     int32_t with_probs;            /* --vo                                                */
     int32_t gff;                   /* --gff                                               */
-    int32_t pad;
+    int32_t site_stats;            /* gff && with_probs is made (below); 0: it declines   */
 } mc_bed_params;
 typedef struct mc_bed_stats {
     int64_t n_bytes, n_lines, n_counted, n_entries, n_sites, n_out_bytes;
@@ -655,7 +666,7 @@ typedef struct mc_bed_stats {
 #define MC_BED_DECLINE_ROWS        10
 #define MC_BED_DECLINE_MEMORY      11
 #define MC_BED_DECLINE_OPTIONS     12
-/* ... with a positions file (mc_bed_positions_*); 13-15 name a line of the POSITIONS file, 16-19 a row, 20-25 an entry's first row */
+/* ... with a positions source; 13-15 name a line of the POSITIONS file, 16-19 a row, 20-25 an entry's first row */
 #define MC_BED_DECLINE_POS_HIGH_BYTE 13  /* positions: a byte >= 0x80                                                  */
 #define MC_BED_DECLINE_POS_CONTROL   14  /* positions: a control byte other than tab and newline                       */
 #define MC_BED_DECLINE_POS_LONG_LINE 15  /* positions: a line longer than 65535 bytes                                  */
@@ -668,7 +679,7 @@ typedef struct mc_bed_stats {
 #define MC_BED_DECLINE_PRINT_RANGE   22  /* a rounded value mc_rowtext.h does not print (|v| >= 1e9)                   */
 #define MC_BED_DECLINE_ROUNDING_TIE  23  /* a value within its error bound of a rounding tie of np.round(., 3)         */
 #define MC_BED_DECLINE_DEPTH         24  /* an entry of more than 100001 rows (the tail function's error is measured up to there) */
-/* ... through mc_bed_annotate_*: 25-27 with --gff --vo (25 names a row, 26-27 an entry's first row); 28-30 name a line of the FASTA,
+/* ... with site_stats or a FASTA source: 25-27 with --gff --vo (25 names a row, 26-27 an entry's first row); 28-30 name a line of the FASTA,
  * 31-32 an entry's first row */
 #define MC_BED_DECLINE_PROBABILITY   25  /* a row of a written entry with a probability mc_decimal.h declines           */
 #define MC_BED_DECLINE_STAT_RANGE    26  /* a fracLow / fracUp mc_rowtext.h does not print (0.0 and nan are printed)     */
@@ -679,15 +690,8 @@ typedef struct mc_bed_stats {
 #define MC_BED_DECLINE_REF_LETTER    31  /* an entry on '-' with a letter outside ACGTNM in its window (the host's KeyError) */
 #define MC_BED_DECLINE_REF_CONTIG    32  /* a written entry whose contig the FASTA lacks (the host's KeyError)           */
 #define MC_BED_MAX_VALUES 64
-int mc_bed_summarise_text(mc_ctx *ctx, const char *text, int64_t n_bytes, const mc_bed_params *prm, const char **out,
-                          int64_t *n_out, int64_t *n_sites, int32_t *status);
-/* ... of a file: read in pinned blocks (mc_read_file_range) while the block before is on its way to the device. */
-int mc_bed_summarise_file(mc_ctx *ctx, const char *path, const mc_bed_params *prm, const char **out, int64_t *n_out,
-                          int64_t *n_sites, int32_t *status);
-int mc_bed_last_stats(mc_ctx *ctx, mc_bed_stats *out);
-int mc_bed_release(mc_ctx *ctx);
-/* ... with make_bed -p: a positions file beside the .diffs file (make_bed.py:13-19,:84-96,:115-127).  Every positions line with
- * len(line) > 3, the newline counted, is stripped (blanks and tabs) and split on tabs; its first four fields are one tuple; a
+/* ... with make_bed -p: `positions` (null: none), a positions file beside the .diffs file (make_bed.py:13-19,:84-96,:115-127).
+ * Every positions line with len(line) > 3, the newline counted, is stripped (blanks and tabs) and split on tabs; its first four fields are one tuple; a
  * row counts when its context has 'M' at its centre AND (chrom, pos text, decimal digits of pos + 1, strand) is such a tuple,
  * byte for byte.  Every entry is written (min_depth, mod_threshold and control select nothing).  A BED row gets two more
  * columns before the --vo list: str(np.round(., 3)) of the largest t statistic and of the sum of -log10 p of one-sample
@@ -695,23 +699,16 @@ int mc_bed_release(mc_ctx *ctx);
  * With gff the ordinary attributes are written for every entry.  Every printed value is the host's or the call declines
  * (MC_BED_DECLINE_* 13-24 on top of the above): the sums are compensated, the bound on |device - host| of every value is
  * derived (moments) and measured (tail function; profiles/tstat_error.json), and a value whose bound reaches a rounding
- * tie declines the file.  MCALLER_BED_HASH_MASK applies to the hash of the position tuples too. */
-int mc_bed_positions_text(mc_ctx *ctx, const char *text, int64_t n_bytes, const char *positions, int64_t n_positions_bytes,
-                          const mc_bed_params *prm, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status);
-int mc_bed_positions_file(mc_ctx *ctx, const char *path, const char *positions_path, const mc_bed_params *prm, const char **out,
-                          int64_t *n_out, int64_t *n_sites, int32_t *status);
-
-/* ... with make_bed --gff --vo and --ref (make_bed.py:36-48,:146-149).  positions / positions_path and fasta / fasta_path may be
- * null: without them and without gff && with_probs the calls are mc_bed_summarise_*.  gff && with_probs: every written entry
- * carries ";fracLow=..;fracUp=..;identificationQv=.." from the probabilities of its rows in row order, in NumPy's own order of
+ * tie declines the file.  MCALLER_BED_HASH_MASK applies to the hash of the position tuples too.
+ * ... with make_bed --gff --vo (site_stats) and --ref (`fasta`; null: none) (make_bed.py:36-48,:146-149).  gff && with_probs
+ * with site_stats: every written entry carries ";fracLow=..;fracUp=..;identificationQv=.." from the probabilities of its rows in row order, in NumPy's own order of
  * additions (mcaller_amd/csrc/mc_npsum.h): the host's bits, no bound.  A FASTA: an entry's context in the GFF attributes is
  * the 41 bases around its position (Python's slice rule; upper-cased; complemented and reversed on '-'), a BED row keeps its own.
  * Declines on top of the above: MC_BED_DECLINE_* 25-32; a FASTA that does not fit beside the rest is MC_BED_DECLINE_MEMORY. */
-int mc_bed_annotate_text(mc_ctx *ctx, const char *text, int64_t n_bytes, const char *positions, int64_t n_positions_bytes,
-                         const char *fasta, int64_t n_fasta_bytes, const mc_bed_params *prm, const char **out, int64_t *n_out,
-                         int64_t *n_sites, int32_t *status);
-int mc_bed_annotate_file(mc_ctx *ctx, const char *path, const char *positions_path, const char *fasta_path,
-                         const mc_bed_params *prm, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status);
+int mc_bed_summarise(mc_ctx *ctx, const mc_text_source *src, const mc_text_source *positions, const mc_text_source *fasta,
+                     const mc_bed_params *prm, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status);
+int mc_bed_last_stats(mc_ctx *ctx, mc_bed_stats *out);
+int mc_bed_release(mc_ctx *ctx);
 
 /* ===== NumPy's summation order for make_bed --gff --vo (mcaller_amd/csrc/mc_npsum.h: one header for the host and the device) =====
  * p[0, n): an entry's probabilities in row order.  mc_gff_site_moments: out3 = {np.mean(p), np.var(p, ddof=1),
@@ -766,7 +763,7 @@ int mc_parse_doubles_device(mc_ctx *ctx, const char *text, int64_t n_bytes, cons
  * of base_models; at most MC_TRAINROWS_MAX_PAIRS).  The matrices are tsv2matrix's bit for bit, or the call declines --
  * *status = 1, mc_last_error says why (mc_train_rows_last_stats: which line and reason), the view is empty and the caller
  * runs the host code on the file.  Declined: MC_TRAINROWS_DECLINE_* below.  The view's pointers are memory owned by the
- * context: valid until the next mc_train_rows_* call on it or mc_train_rows_release.  Test knob (environment):
+ * context: valid until the next mc_train_rows call on it or mc_train_rows_release.  Test knob (environment):
  * MCALLER_TRAINROWS_HASH_MASK=<hex> is anded onto the 64-bit hash of a label's bytes. */
 #define MC_TRAINROWS_MAX_LABELS   16
 #define MC_TRAINROWS_MAX_FEATURES 64
@@ -802,10 +799,8 @@ typedef struct mc_train_rows_stats {
 #define MC_TRAINROWS_DECLINE_LONG_LINE     9   /* a line longer than 65535 bytes                                           */
 #define MC_TRAINROWS_DECLINE_ROWS          10  /* 2^31 - 2 lines or more                                                   */
 #define MC_TRAINROWS_DECLINE_MEMORY        11  /* the text does not fit into free device memory beside its outputs         */
-int mc_train_rows_text(mc_ctx *ctx, const char *text, int64_t n_bytes, const char *pairs, int32_t n_pairs, mc_train_rows_view *out,
-                       int32_t *status);
-/* ... of a file: read in pinned blocks (mc_read_file_range) while the block before is on its way to the device. */
-int mc_train_rows_file(mc_ctx *ctx, const char *path, const char *pairs, int32_t n_pairs, mc_train_rows_view *out, int32_t *status);
+int mc_train_rows(mc_ctx *ctx, const mc_text_source *src, const char *pairs, int32_t n_pairs, mc_train_rows_view *out,
+                  int32_t *status);
 int mc_train_rows_last_stats(mc_ctx *ctx, mc_train_rows_stats *out);
 int mc_train_rows_release(mc_ctx *ctx);
 
@@ -850,7 +845,7 @@ int mc_sort_key(const char *line, int64_t n, uint64_t *hi, uint64_t *lo);
  * the call declines -- *status = 1, mc_last_error says why (mc_fastq_quality_last_stats: which line and reason), the view is
  * empty and the caller runs the host reader on the file, which raises the reference's errors.  Declined:
  * MC_FASTQ_DECLINE_* below; of several offending lines the first is named, of several reasons on it the smallest.  The
- * view's pointers are pinned memory owned by the context: valid until the next mc_fastq_quality_* call on it or
+ * view's pointers are pinned memory owned by the context: valid until the next mc_fastq_quality call on it or
  * mc_fastq_quality_release.
  * mc_fastq_records_host: the same rules (csrc/mc_fastqrec.h) run line by line on the CPU, no GPU and no context -> a handle
  * for mc_fastq_view / mc_fastq_free (null when declined); mc_fastq_records_host_decline: the line and reason of the calling
@@ -879,9 +874,7 @@ typedef struct mc_fastq_quality_stats {
 #define MC_FASTQ_DECLINE_ROWS       8   /* 2^31 - 2 lines or more                                                         */
 #define MC_FASTQ_DECLINE_MEMORY     9   /* the text does not fit into free device memory beside its outputs               */
 #define MC_FASTQ_DECLINE_GZ         10  /* a path containing ".gz": decided by the caller (read_qual.py), nothing is read  */
-int mc_fastq_quality_text(mc_ctx *ctx, const char *text, int64_t n_bytes, mc_fastq_quality_view *out, int32_t *status);
-/* ... of a file: read in pinned blocks (mc_read_file_range) while the block before is on its way to the device. */
-int mc_fastq_quality_file(mc_ctx *ctx, const char *path, mc_fastq_quality_view *out, int32_t *status);
+int mc_fastq_quality(mc_ctx *ctx, const mc_text_source *src, mc_fastq_quality_view *out, int32_t *status);
 int mc_fastq_quality_last_stats(mc_ctx *ctx, mc_fastq_quality_stats *out);
 int mc_fastq_quality_release(mc_ctx *ctx);
 int mc_fastq_records_host(const char *text, int64_t n_bytes, mc_fastq **out, int32_t *status);
@@ -889,13 +882,13 @@ int mc_fastq_records_host_decline(int32_t *reason, int64_t *line);
 
 /* ===== two `make_bed --vo` BED files compared per site on the GPU (mcaller_amd/compare_genomes.py; csrc/mc_twosample.h,
  * csrc/compare/mc_bedcompare.hip) =====
- * One row per key (chrom, start, end, strand) of bed1 that bed2 also has, in bed1's file order: the two samples' Mann-Whitney,
+ * mc_bed_compare: one row per key (chrom, start, end, strand) of bed1 that bed2 also has, in bed1's file order: the two samples' Mann-Whitney,
  * rank-sum, Student and Kolmogorov-Smirnov statistics and -log10 p values.  The bytes are those of
  * compare_genomes.compare_by_position, or the call declines -- *status = 1, mc_last_error says why (mc_bed_compare_last_stats:
  * which file, line and reason), nothing is handed out and the caller runs the host statement, which words the errors.
  * Declined: MC_CMP_DECLINE_* below; of several offending lines the first is named (bed1's before bed2's), of several reasons
  * on it the smallest.  *out points at n_out bytes of pinned memory owned by the context: valid until the next
- * mc_bed_compare_* call on it or mc_bed_compare_release.
+ * mc_bed_compare call on it or mc_bed_compare_release.
  * mc_twosample: the arithmetic of one site by the host build of csrc/mc_twosample.h (needs no GPU) -> 0; out[9] = U, z_mwu, z_rs,
  * t, D, nlp_mwu, nlp_rs, nlp_t, nlp_ks (U and D as they are, the others rounded to three places), bound[9] the bound on
  * |device - host| of each before rounding, *status the TW_* bits of that header (0: every value is vouched for); -12: bad
@@ -931,27 +924,20 @@ typedef struct mc_cmp_stats {
 #define MC_CMP_DECLINE_FAR_TAIL    14  /* a log10 p below -290                                                            */
 #define MC_CMP_DECLINE_PRINT       15  /* a value mc_rowtext.h does not print                                             */
 #define MC_CMP_DECLINE_TIE         16  /* a value within its error bound of a rounding tie of np.round(., 3)              */
-int mc_bed_compare_text(mc_ctx *ctx, const char *text1, int64_t n_bytes1, const char *text2, int64_t n_bytes2, const char **out,
-                        int64_t *n_out, int64_t *n_sites, int32_t *status);
-/* ... of two files: read in pinned blocks (mc_read_file_range) while the block before is on its way to the device. */
-int mc_bed_compare_file(mc_ctx *ctx, const char *path1, const char *path2, const char **out, int64_t *n_out, int64_t *n_sites,
-                        int32_t *status);
-int mc_bed_compare_last_stats(mc_ctx *ctx, mc_cmp_stats *out);
-int mc_bed_compare_release(mc_ctx *ctx);
 /* ----- two genomes with their own assemblies: the comparison through a Mauve alignment (csrc/compare/mc_xmfamap.inc; the
  * definition stands in mcaller_amd/compare_genomes.py) -----
- * mc_xmfa_map_text / _file: the coordinate map of an XMFA file for its sequence numbers seq1 (n1 bases in concatenated
- * coordinates, bed1's genome) and seq2 (n2 bases), built on the GPU and kept in the context until the next mc_xmfa_map_* call or
+ * mc_xmfa_map: the coordinate map of an XMFA file (src) for its sequence numbers seq1 (n1 bases in concatenated
+ * coordinates, bed1's genome) and seq2 (n2 bases), built on the GPU and kept in the context until the next mc_xmfa_map call or
  * mc_xmfa_map_release: 8 bytes a base of genome 1.  view (may be NULL): host copies of g2[0 .. n1] and flip[0 .. n1], index g1,
  * 0: unmapped -- pinned memory of the context, valid as long as the map.  Declined (*status = 1, mc_last_error,
  * mc_xmfa_map_last_stats: reason and line; no map is kept): the MC_CMP_DECLINE_XMFA_* below, MC_CMP_DECLINE_ROWS,
  * MC_CMP_DECLINE_MEMORY (the map and the text beside free device memory, for which MCALLER_CMP_DEVICE_BYTES stands in tests).  Line by
  * line the first offending line is named and on it the smallest reason; in a file whose lines are sound, the header line of the
  * first offending entry and on it the smallest reason.
- * mc_bed_compare_lifted_text / _file: mc_bed_compare_text / _file through the resident map (-12 without one): a bed1 line is
- * matched to bed2 by its image, and a row carries the image's four fields behind bed1's.  contigs1 / contigs2: the two genomes'
- * .fai tables, whose totals must be the map's n1 and n2 (-12).  *n_unaligned: bed1's lines that have no image.  Declines as
- * mc_bed_compare_*, and MC_CMP_DECLINE_LIFT_START. */
+ * mc_bed_compare with contigs1 / contigs2 (both or neither, -12): the comparison through the resident map (-12 without one): a
+ * bed1 line is matched to bed2 by its image, and a row carries the image's four fields behind bed1's.  contigs1 / contigs2: the
+ * two genomes' .fai tables, whose totals must be the map's n1 and n2 (-12).  *n_unaligned (required with the tables, else may be
+ * null): bed1's lines that have no image.  Declines as without the tables, and MC_CMP_DECLINE_LIFT_START. */
 typedef struct mc_contig_table {
     int64_t n_contigs;
     const char *ids;               /* the names, one behind the other ...                          */
@@ -985,18 +971,15 @@ typedef struct mc_xmfa_stats {
 #define MC_CMP_DECLINE_XMFA_RANGE    23  /* an END beyond the .fai total of its genome                                      */
 #define MC_CMP_DECLINE_XMFA_GENOME   24  /* a genome of more than 2^31 - 2 bases, or 2^31 columns or more in paired blocks  */
 #define MC_CMP_DECLINE_LIFT_START    25  /* a bed1 start that is not plain digits (int() may accept it: the host decides)   */
-int mc_xmfa_map_text(mc_ctx *ctx, const char *text, int64_t n_bytes, int32_t seq1, int32_t seq2, int64_t n1, int64_t n2,
-                     mc_xmfa_map_view *view, int32_t *status);
-int mc_xmfa_map_file(mc_ctx *ctx, const char *path, int32_t seq1, int32_t seq2, int64_t n1, int64_t n2, mc_xmfa_map_view *view,
-                     int32_t *status);
+int mc_xmfa_map(mc_ctx *ctx, const mc_text_source *src, int32_t seq1, int32_t seq2, int64_t n1, int64_t n2, mc_xmfa_map_view *view,
+                int32_t *status);
 int mc_xmfa_map_last_stats(mc_ctx *ctx, mc_xmfa_stats *out);
 int mc_xmfa_map_release(mc_ctx *ctx);
-int mc_bed_compare_lifted_text(mc_ctx *ctx, const char *text1, int64_t n_bytes1, const char *text2, int64_t n_bytes2,
-                               const mc_contig_table *contigs1, const mc_contig_table *contigs2, const char **out, int64_t *n_out,
-                               int64_t *n_sites, int64_t *n_unaligned, int32_t *status);
-int mc_bed_compare_lifted_file(mc_ctx *ctx, const char *path1, const char *path2, const mc_contig_table *contigs1,
-                               const mc_contig_table *contigs2, const char **out, int64_t *n_out, int64_t *n_sites,
-                               int64_t *n_unaligned, int32_t *status);
+int mc_bed_compare(mc_ctx *ctx, const mc_text_source *bed1, const mc_text_source *bed2, const mc_contig_table *contigs1,
+                   const mc_contig_table *contigs2, const char **out, int64_t *n_out, int64_t *n_sites, int64_t *n_unaligned,
+                   int32_t *status);
+int mc_bed_compare_last_stats(mc_ctx *ctx, mc_cmp_stats *out);
+int mc_bed_compare_release(mc_ctx *ctx);
 int mc_twosample(const double *x, int64_t n1, const double *y, int64_t n2, double *out, double *bound, int32_t *status);
 int mc_twosample_device(mc_ctx *ctx, const double *x, const int64_t *x_off, const double *y, const int64_t *y_off, int64_t k,
                         double *out, double *bound, int32_t *status);
@@ -1004,7 +987,7 @@ double mc_twosample_log10_2sf(double z);
 double mc_twosample_log10_kolmogorov(double lam);
 
 /* ===== methylated motifs found de novo from called sites on the GPU (mcaller_amd/find_motifs.py; csrc/motifs/mc_motifscan.hip) =====
- * For every shape (a string of X and '.', first and last X, at most MC_MOTIF_MAX_WIDTH wide, 2 to 8 X), every X of it as the called
+ * mc_motif_report, with iupac = 0 and max_motifs = 0.  For every shape (a string of X and '.', first and last X, at most MC_MOTIF_MAX_WIDTH wide, 2 to 8 X), every X of it as the called
  * letter and every assignment of A, C, G, T to the X: the candidates of the reference (ref: contig_len, seq_off and the upper-cased
  * seq; the masks are not read) that stand in such a window, those the bed or the control lists (covered; without a control all
  * are) and those the bed lists (methylated).  The rows with nMethylated >= min_sites and nMethylated / nCovered >= min_fraction,
@@ -1012,7 +995,7 @@ double mc_twosample_log10_kolmogorov(double lam);
  * find_motifs.find_motifs does -- or the call declines: *status = 1, mc_last_error says why (mc_motif_report_last_stats: which
  * file, line and reason), nothing is handed out and the caller runs the host statement, which words the errors.  Of several
  * offending lines the first is named (the bed's before the control's), of several reasons on it the smallest.  *out points at
- * n_out bytes of pinned memory owned by the context: valid until the next mc_motif_report_* call on it.
+ * n_out bytes of pinned memory owned by the context: valid until the next mc_motif_report call on it or mc_motif_report_release.
  * Test knobs, read per call: MCALLER_MOTIF_HASH_MASK=<hex>, MCALLER_MOTIF_TABLE_SLOTS=n (the contig table),
  * MCALLER_MOTIF_STRETCH=n (bases a workgroup of the counting kernel takes: a multiple of 64, the effective value is in the
  * stats), MCALLER_MOTIF_DEVICE_BYTES=n (stands for the free device memory), MCALLER_TEXT_STAGE_BYTES (the feed). */
@@ -1054,15 +1037,9 @@ typedef struct mc_motif_stats {
 #define MC_MOTIF_DECLINE_REFERENCE   10  /* a reference of 2^31 bases or more (the counters are 32-bit)             */
 #define MC_MOTIF_DECLINE_PRINT       11  /* a fraction mc_rowtext.h does not print                                  */
 #define MC_MOTIF_DECLINE_ROWS        12  /* 2^31 - 2 lines or more in the two files together                        */
-int mc_motif_report_text(mc_ctx *ctx, const mc_ref_view *ref, const char *bed, int64_t n_bed, const char *control_or_null,
-                         int64_t n_control, const mc_motif_params *params, const char **out, int64_t *n_out, int64_t *n_rows,
-                         int32_t *status);
-/* ... of files: read in pinned blocks (mc_read_file_range) while the block before is on its way to the device. */
-int mc_motif_report_file(mc_ctx *ctx, const mc_ref_view *ref, const char *bed_path, const char *control_path_or_null,
-                         const mc_motif_params *params, const char **out, int64_t *n_out, int64_t *n_rows, int32_t *status);
 int mc_motif_report_last_stats(mc_ctx *ctx, mc_motif_stats *out);
-/* --iupac: the rows merged into degenerate motifs (the definition: mcaller_amd/find_motifs.py; csrc/motifs/mc_motifiupac.inc).  The
- * same arguments, declines and ownership of *out as above; a row is a maximal pure pattern, SPEC carries IUPAC letters.  Every
+/* iupac != 0, --iupac: the rows merged into degenerate motifs (the definition: mcaller_amd/find_motifs.py; csrc/motifs/mc_motifiupac.inc).  The
+ * same declines and ownership of *out as above; a row is a maximal pure pattern, SPEC carries IUPAC letters.  Every
  * table's purity lattice (15^(k-1) bytes) is resident during the call: lattice_bytes is what that adds to the plain call's need,
  * counted against free device memory (MCALLER_MOTIF_DEVICE_BYTES) before anything is allocated -> MC_MOTIF_DECLINE_MEMORY.
  * mc_motif_report_last_stats holds for these calls too (n_selected: maximal patterns over both thresholds). */
@@ -1073,15 +1050,10 @@ typedef struct mc_motif_iupac_stats {
     int64_t decline_line;          /* as in mc_motif_stats                                                      */
     int32_t decline_reason, decline_file;
 } mc_motif_iupac_stats;
-int mc_motif_report_iupac_text(mc_ctx *ctx, const mc_ref_view *ref, const char *bed, int64_t n_bed, const char *control_or_null,
-                               int64_t n_control, const mc_motif_params *params, const char **out, int64_t *n_out, int64_t *n_rows,
-                               int32_t *status);
-int mc_motif_report_iupac_file(mc_ctx *ctx, const mc_ref_view *ref, const char *bed_path, const char *control_path_or_null,
-                               const mc_motif_params *params, const char **out, int64_t *n_out, int64_t *n_rows, int32_t *status);
 int mc_motif_report_iupac_last_stats(mc_ctx *ctx, mc_motif_iupac_stats *out);
-/* --iterative: the motifs peeled off one at a time (the definition: mcaller_amd/find_motifs.py; csrc/motifs/mc_motifiter.inc).  The
- * same arguments, declines and ownership of *out as above, and iupac (0: concrete rows, 1: degenerate ones) and max_motifs (1 ..
- * MC_MOTIF_MAX_ROUNDS).  Round 1 is the call above; every later round takes the candidates the printed row explains out of the
+/* max_motifs != 0, --iterative: the motifs peeled off one at a time (the definition: mcaller_amd/find_motifs.py;
+ * csrc/motifs/mc_motifiter.inc).  The same declines and ownership of *out as above; iupac (0: concrete rows, else degenerate ones),
+ * max_motifs 1 .. MC_MOTIF_MAX_ROUNDS (0: not iterative; anything else: -12).  Round 1 is the call with max_motifs = 0; every later round takes the candidates the printed row explains out of the
  * candidate planes and out of every table's counters and selects again: planes, tables and lattices stay on the device for the
  * whole call.  The list of a round's explained candidates (list_bytes: 8 bytes a base) is counted against free device memory
  * (MCALLER_MOTIF_DEVICE_BYTES) before anything is allocated -> MC_MOTIF_DECLINE_MEMORY.  mc_motif_report_last_stats and
@@ -1098,16 +1070,13 @@ typedef struct mc_motif_iter_stats {
     double ms_first_round;         /* from the first kernel to the first row: the plain call's ms_kernels       */
     double ms_later_rounds;        /* all later rounds together, the explain step of the round before included  */
 } mc_motif_iter_stats;
-int mc_motif_report_iter_text(mc_ctx *ctx, const mc_ref_view *ref, const char *bed, int64_t n_bed, const char *control_or_null,
-                              int64_t n_control, const mc_motif_params *params, int32_t iupac, int32_t max_motifs, const char **out,
-                              int64_t *n_out, int64_t *n_rows, int32_t *status);
-int mc_motif_report_iter_file(mc_ctx *ctx, const mc_ref_view *ref, const char *bed_path, const char *control_path_or_null,
-                              const mc_motif_params *params, int32_t iupac, int32_t max_motifs, const char **out, int64_t *n_out,
-                              int64_t *n_rows, int32_t *status);
+int mc_motif_report(mc_ctx *ctx, const mc_ref_view *ref, const mc_text_source *bed, const mc_text_source *control_or_null,
+                    const mc_motif_params *params, int32_t iupac, int32_t max_motifs, const char **out, int64_t *n_out, int64_t *n_rows,
+                    int32_t *status);
 int mc_motif_report_iter_last_stats(mc_ctx *ctx, mc_motif_iter_stats *out);
-/* The methylated candidates the last mc_motif_report_iter_* call left unexplained, as two bit planes of n_words 64-bit words in
+/* The methylated candidates the last iterative mc_motif_report call left unexplained, as two bit planes of n_words 64-bit words in
  * pinned memory owned by the context ('+' and '-'; bit i of word w: base index 64 w + i), and contig_start[c], the base index of
- * contig c's first base (n_contigs entries).  Valid until the next mc_motif_report_* call; all null / 0 after a decline. */
+ * contig c's first base (n_contigs entries).  Valid until the next mc_motif_report call; all null / 0 after a decline. */
 int mc_motif_report_iter_left(mc_ctx *ctx, const uint64_t **plus, const uint64_t **minus, int64_t *n_words, const int64_t **contig_start,
                               int32_t *n_contigs);
 int mc_motif_report_release(mc_ctx *ctx);

@@ -41,6 +41,7 @@ ForestFitStats = _S['mc_forest_fit_stats']
 SvmParams = _S['mc_svm_params']
 LrParams = _S['mc_lr_params']
 NbParams = _S['mc_nb_params']
+TextSource = _S['mc_text_source']
 BedParams = _S['mc_bed_params']
 BedStats = _S['mc_bed_stats']
 TrainRowsView = _S['mc_train_rows_view']

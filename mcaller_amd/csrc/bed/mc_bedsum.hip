@@ -1,7 +1,6 @@
 // mc_bedsum.hip -- the per-site summary of a `.diffs.<k>` file on the GPU: what make_bed.py:67-164 writes for BED, BED --control,
-// BED --vo and GFF, with a positions file for -p, and through mc_bed_annotate_* for --gff --vo and --ref (C ABI: mc_bed_summarise_text /
-// _file, mc_bed_positions_text / _file, mc_bed_annotate_text / _file, mc_bed_last_stats, mc_bed_release; Python: Device.bed_summarise,
-// make_bed.summarise_diffs_device).  The unit stands in csrc/bed/,
+// BED --vo and GFF, with a positions source for -p, with site_stats for --gff --vo and a FASTA source for --ref (C ABI:
+// mc_bed_summarise, mc_bed_last_stats, mc_bed_release; Python: Device.bed_summarise, make_bed.summarise_diffs_device).  The unit stands in csrc/bed/,
 // beside the units of the passes, not among them: no pass runs
 // its kernels, and the benchmark's kernel hash (bench.KERNEL_SOURCES) names the files of the pass path one by one.
 //
@@ -17,9 +16,9 @@
 //   * a table with fewer than 2 x the counted rows' slots (only MCALLER_BED_TABLE_SLOTS makes one)
 //   * a text that does not fit into free device memory beside its tables: the WHOLE text stays resident, entries are compared
 //     against the bytes of a representative row and the output copies its fields from there
-//   * --gff with --vo through mc_bed_summarise_* / mc_bed_positions_*: not attempted (mc_bed_annotate_* makes it, below)
+//   * --gff with --vo without mc_bed_params.site_stats: not attempted (site_stats makes it, below)
 //
-// make_bed -p (mc_bed_positions_text / _file; Device.bed_summarise(positions_path= / positions_text=), make_bed.summarise_diffs_device(
+// make_bed -p (mc_bed_summarise's positions source; Device.bed_summarise(positions_path= / positions_text=), make_bed.summarise_diffs_device(
 // positions=); from the command line with MCALLER_BED_POSITIONS_DEVICE=1): a positions file beside the rows.  A row counts when its
 // context has 'M' at its centre AND (chrom, pos text, digits of pos + 1, strand) is a tuple of the file, byte for byte; every entry
 // is written, -d / -t / --control select nothing; a BED row carries two more columns before the --vo list, str(np.round(., 3)) of
@@ -46,7 +45,7 @@
 //   kq_finish     a lane per entry: t, log10 p, their bounds, the maximum and the sum, np.round(., 3), the tie test, the digits
 //   kb_sums / kb_apply again (the rows' sizes with the two columns), kb_write
 //
-// make_bed --gff --vo and --ref (mc_bed_annotate_text / _file; Device.bed_summarise(site_stats=, ref_path= / ref_text=),
+// make_bed --gff --vo and --ref (mc_bed_params.site_stats, mc_bed_summarise's FASTA source; Device.bed_summarise(site_stats=, ref_path= / ref_text=),
 // make_bed.summarise_diffs_device(ref=); from the command line with MCALLER_BED_GFF_DEVICE=1, with -p both knobs).  --gff --vo: every
 // written entry carries ";fracLow=..;fracUp=..;identificationQv=.." -- frac -+ 2 np.std(p, ddof=1) / np.sqrt(n) and int(100 np.mean(p))
 // of its probabilities in row order, every fp64 operation with NumPy's two operands (mc_npsum.h: the pairwise order of np.add.reduce,
@@ -871,26 +870,26 @@ int bs_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *d_p
     return 0;
 }
 
-// what every entry point begins with -> 0: go on; 1: done (declined, *status set)
-int bs_begin(mc_ctx *c, const mc_bed_params *P, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status, int64_t n, bool annotate) {
+// what a call begins with -> 0: go on; 1: done (declined, *status set)
+int bs_begin(mc_ctx *c, const mc_bed_params *P, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status, int64_t n) {
     c->bed_stats = mc_bed_stats();
     c->bed_stats.decline_line = -1;
     c->bed_stats.n_bytes = n;
     *out = nullptr; *n_out = 0; *n_sites = 0; *status = 0;
-    if (P->gff && P->with_probs && !annotate) { (void)bs_decline(c, status, MC_BED_DECLINE_OPTIONS, -1); return 1; }
+    if (P->gff && P->with_probs && !P->site_stats) { (void)bs_decline(c, status, MC_BED_DECLINE_OPTIONS, -1); return 1; }
     if (!device_fits((size_t)n + 4096)) { (void)bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1); return 1; }
     return 0;
 }
 
-// What every entry point runs: the texts of the sources, each padded in a buffer of its own, onto the device and through bs_run.
-// pos == null -> no -p; fa == null -> no --ref; annotate: the mc_bed_annotate_* entry points (--gff --vo is made)
-int bs_call(mc_ctx *c, const TextSource &src, const TextSource *pos, const TextSource *fa, bool annotate, const mc_bed_params *P,
+// What the entry point runs: the texts of the sources, each padded in a buffer of its own, onto the device and through bs_run.
+// pos == null -> no -p; fa == null -> no --ref
+int bs_call(mc_ctx *c, const mc_text_source &src, const mc_text_source *pos, const mc_text_source *fa, const mc_bed_params *P,
             const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status) {
     HIP_TRY(hipSetDevice(c->device));
     const auto t0 = std::chrono::steady_clock::now();
-    const int64_t pn = pos ? pos->n : 0, fn = fa ? fa->n : 0;
-    if (bs_begin(c, P, out, n_out, n_sites, status, src.n + pn + fn, annotate)) return 0;
-    c->bed_stats.n_bytes = src.n;
+    const int64_t pn = pos ? pos->n_bytes : 0, fn = fa ? fa->n_bytes : 0;
+    if (bs_begin(c, P, out, n_out, n_sites, status, src.n_bytes + pn + fn)) return 0;
+    c->bed_stats.n_bytes = src.n_bytes;
     Pool pool("bed summary");
     TextFeed feed(c, (size_t)64 << 20);
     char *d_text = nullptr, *d_ptext = nullptr, *d_ftext = nullptr;
@@ -900,25 +899,10 @@ int bs_call(mc_ctx *c, const TextSource &src, const TextSource *pos, const TextS
     if (fa)
         if (int rc = feed.put(pool, *fa, &d_ftext)) return rc;
     feed.times(c->bed_stats, t0);
-    const int rc = bs_run(c, pool, d_text, src.n, d_ptext, pn, d_ftext, fn, P, out, n_out, n_sites, status);
+    const int rc = bs_run(c, pool, d_text, src.n_bytes, d_ptext, pn, d_ftext, fn, P, out, n_out, n_sites, status);
     (void)hipStreamSynchronize(c->stream);                   // (an early return: nothing of the pool is in use when it goes)
     c->bed_stats.ms_total = ms_since(t0);
     return rc;
-}
-
-int bs_text(mc_ctx *c, const char *text, int64_t n_bytes, const char *positions, int64_t pn, const char *fasta, int64_t fn, bool annotate,
-            const mc_bed_params *P, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status) {
-    const TextSource src = {text, nullptr, n_bytes}, pos = {positions, nullptr, pn}, fa = {fasta, nullptr, fn};
-    return bs_call(c, src, positions ? &pos : nullptr, fasta ? &fa : nullptr, annotate, P, out, n_out, n_sites, status);
-}
-
-int bs_file(mc_ctx *c, const char *what, const char *path, const char *positions_path, const char *fasta_path, bool annotate,
-            const mc_bed_params *P, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status) {
-    TextSource src[3] = {{nullptr, path, 0}, {nullptr, positions_path, 0}, {nullptr, fasta_path, 0}};
-    for (TextSource &s : src)
-        if (s.path)
-            if (int rc = regular_file_size(what, s.path, &s.n)) return rc;
-    return bs_call(c, src[0], positions_path ? &src[1] : nullptr, fasta_path ? &src[2] : nullptr, annotate, P, out, n_out, n_sites, status);
 }
 
 // the probe of mc_tstat.h's device build: a lane per triple
@@ -933,58 +917,19 @@ __global__ __launch_bounds__(256) void k_ts_probe(const double *__restrict__ n, 
 
 }  // namespace
 
-extern "C" int mc_bed_summarise_text(mc_ctx *c, const char *text, int64_t n_bytes, const mc_bed_params *P, const char **out, int64_t *n_out,
-                                     int64_t *n_sites, int32_t *status) {
-    if (!c || !P || !out || !n_out || !n_sites || !status || n_bytes < 0 || (n_bytes > 0 && !text)) {
-        mc_set_error("mc_bed_summarise_text: bad arguments");
+extern "C" int mc_bed_summarise(mc_ctx *c, const mc_text_source *src, const mc_text_source *positions, const mc_text_source *fasta,
+                                const mc_bed_params *P, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status) {
+    if (!c || !P || !out || !n_out || !n_sites || !status) {
+        mc_set_error("mc_bed_summarise: bad arguments");
         return -12;
     }
-    return bs_text(c, text, n_bytes, nullptr, 0, nullptr, 0, false, P, out, n_out, n_sites, status);
-}
-
-extern "C" int mc_bed_summarise_file(mc_ctx *c, const char *path, const mc_bed_params *P, const char **out, int64_t *n_out, int64_t *n_sites,
-                                     int32_t *status) {
-    if (!c || !path || !P || !out || !n_out || !n_sites || !status) {
-        mc_set_error("mc_bed_summarise_file: bad arguments");
-        return -12;
-    }
-    return bs_file(c, "mc_bed_summarise_file", path, nullptr, nullptr, false, P, out, n_out, n_sites, status);
-}
-
-extern "C" int mc_bed_positions_text(mc_ctx *c, const char *text, int64_t n_bytes, const char *positions, int64_t pn, const mc_bed_params *P,
-                                     const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status) {
-    if (!c || !P || !out || !n_out || !n_sites || !status || n_bytes < 0 || (n_bytes > 0 && !text) || pn < 0 || !positions) {
-        mc_set_error("mc_bed_positions_text: bad arguments");
-        return -12;
-    }
-    return bs_text(c, text, n_bytes, positions, pn, nullptr, 0, false, P, out, n_out, n_sites, status);
-}
-
-extern "C" int mc_bed_positions_file(mc_ctx *c, const char *path, const char *positions_path, const mc_bed_params *P, const char **out,
-                                     int64_t *n_out, int64_t *n_sites, int32_t *status) {
-    if (!c || !path || !positions_path || !P || !out || !n_out || !n_sites || !status) {
-        mc_set_error("mc_bed_positions_file: bad arguments");
-        return -12;
-    }
-    return bs_file(c, "mc_bed_positions_file", path, positions_path, nullptr, false, P, out, n_out, n_sites, status);
-}
-
-extern "C" int mc_bed_annotate_text(mc_ctx *c, const char *text, int64_t n_bytes, const char *positions, int64_t pn, const char *fasta, int64_t fn,
-                                    const mc_bed_params *P, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status) {
-    if (!c || !P || !out || !n_out || !n_sites || !status || n_bytes < 0 || (n_bytes > 0 && !text) || pn < 0 || fn < 0) {
-        mc_set_error("mc_bed_annotate_text: bad arguments");
-        return -12;
-    }
-    return bs_text(c, text, n_bytes, positions, positions ? pn : 0, fasta, fasta ? fn : 0, true, P, out, n_out, n_sites, status);
-}
-
-extern "C" int mc_bed_annotate_file(mc_ctx *c, const char *path, const char *positions_path, const char *fasta_path, const mc_bed_params *P,
-                                    const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status) {
-    if (!c || !path || !P || !out || !n_out || !n_sites || !status) {
-        mc_set_error("mc_bed_annotate_file: bad arguments");
-        return -12;
-    }
-    return bs_file(c, "mc_bed_annotate_file", path, positions_path, fasta_path, true, P, out, n_out, n_sites, status);
+    mc_text_source s = {}, pos = {}, fa = {};
+    if (int rc = text_source("mc_bed_summarise", src, &s)) return rc;
+    if (positions)
+        if (int rc = text_source("mc_bed_summarise", positions, &pos)) return rc;
+    if (fasta)
+        if (int rc = text_source("mc_bed_summarise", fasta, &fa)) return rc;
+    return bs_call(c, s, positions ? &pos : nullptr, fasta ? &fa : nullptr, P, out, n_out, n_sites, status);
 }
 
 // p: the arrays one behind the other, off[count + 1] their places; out6 per array: fracLow, fracUp, 100 * mean, mean, var, se

@@ -1,10 +1,10 @@
 // mc_bedcompare.hip -- two `make_bed --vo` BED files compared per site on the GPU: one row of two-sample statistics per key
 // (chrom, start, end, strand) of bed1 that bed2 also has, in bed1's order -- what compare_genomes.compare_by_position builds with
-// four SciPy calls per site in a Python loop (C ABI: mc_bed_compare_text / _file, mc_bed_compare_last_stats,
+// four SciPy calls per site in a Python loop (C ABI: mc_bed_compare, mc_bed_compare_last_stats,
 // mc_bed_compare_release, mc_twosample_device; Python: Device.bed_compare, compare_genomes.compare_by_position_device).  The unit
 // stands in csrc/compare/, beside csrc/bed/, csrc/train/, csrc/merge/ and csrc/fastq/: no pass runs its kernels.
 // Two genomes with their own assemblies are compared through a Mauve alignment: mc_xmfamap.inc, included below, builds the coordinate
-// map from the XMFA text (kx_*) and lifts bed1's lines onto bed2's keys (kc_lift, in kc_probe's place; mc_bed_compare_lifted_*); its
+// map from the XMFA text (kx_*) and lifts bed1's lines onto bed2's keys (kc_lift, in kc_probe's place; mc_bed_compare's contig tables); its
 // header comment lists its declines (MC_CMP_DECLINE_XMFA_*, MC_CMP_DECLINE_LIFT_START) and its kernels' resources.
 //
 // The result is the host statement's bytes or a decline (status 1, mc_last_error; the stats say which file and line):
@@ -675,33 +675,33 @@ bool lift_tables_ok(const mc_contig_table *t) {
     return true;
 }
 
-int cmp_call(mc_ctx *c, const TextSource &s1, const TextSource &s2, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status,
+int cmp_call(mc_ctx *c, const mc_text_source &s1, const mc_text_source &s2, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status,
              const mc_contig_table *t1 = nullptr, const mc_contig_table *t2 = nullptr) {
     HIP_TRY(hipSetDevice(c->device));
     const auto t0 = std::chrono::steady_clock::now();
     c->cmp_stats = mc_cmp_stats();
     c->cmp_unaligned = 0;
     c->cmp_stats.decline_line = -1;
-    c->cmp_stats.n_bytes1 = s1.n; c->cmp_stats.n_bytes2 = s2.n;
+    c->cmp_stats.n_bytes1 = s1.n_bytes; c->cmp_stats.n_bytes2 = s2.n_bytes;
     *out = nullptr; *n_out = 0; *n_sites = 0; *status = 0;
-    if (!cmp_fits((size_t)(s1.n + s2.n) + 4096)) return cmp_decline(c, status, MC_CMP_DECLINE_MEMORY, 0, -1);
+    if (!cmp_fits((size_t)(s1.n_bytes + s2.n_bytes) + 4096)) return cmp_decline(c, status, MC_CMP_DECLINE_MEMORY, 0, -1);
     Pool pool("bed comparison");
     TextFeed feed(c, (size_t)32 << 20);
     char *d_text = nullptr, last1 = '\n';
-    if (pool.get(&d_text, (size_t)(s1.n + s2.n) + 1 + 64)) return -10;
+    if (pool.get(&d_text, (size_t)(s1.n_bytes + s2.n_bytes) + 1 + 64)) return -10;
     if (int rc = feed.send(s1, d_text, &last1)) return rc;
-    int64_t off2 = s1.n;
-    if (s1.n > 0 && last1 != '\n') {                                   // bed1's last line ends where bed2's first begins
+    int64_t off2 = s1.n_bytes;
+    if (s1.n_bytes > 0 && last1 != '\n') {                             // bed1's last line ends where bed2's first begins
         HIP_TRY(hipMemsetAsync(d_text + off2, '\n', 1, c->up_stream));
         ++off2;
     }
     if (int rc = feed.send(s2, d_text + off2)) return rc;
-    if (int rc = feed.pad_and_wait(d_text + off2 + s2.n)) return rc;
+    if (int rc = feed.pad_and_wait(d_text + off2 + s2.n_bytes)) return rc;
     feed.times(c->cmp_stats, t0);
     const auto t_kernels = std::chrono::steady_clock::now();
     LiftDev lift;
     int rc = t1 ? lift_prepare(c, pool, t1, t2, &lift) : 0;
-    if (rc == 0) rc = cmp_run(c, pool, d_text, off2 + s2.n, off2, out, n_out, n_sites, status, t1 ? &lift : nullptr);
+    if (rc == 0) rc = cmp_run(c, pool, d_text, off2 + s2.n_bytes, off2, out, n_out, n_sites, status, t1 ? &lift : nullptr);
     (void)hipStreamSynchronize(c->stream);                             // (an early return: nothing of the pool is in use when it goes)
     c->cmp_stats.ms_kernels = ms_since(t_kernels) - c->cmp_stats.ms_d2h;      // a declined call too: what ran until it declined
     if (rc != 0 || *status != 0) { *out = nullptr; *n_out = 0; *n_sites = 0; }
@@ -711,79 +711,41 @@ int cmp_call(mc_ctx *c, const TextSource &s1, const TextSource &s2, const char *
 
 }  // namespace
 
-extern "C" int mc_bed_compare_text(mc_ctx *c, const char *text1, int64_t n1, const char *text2, int64_t n2, const char **out, int64_t *n_out,
-                                   int64_t *n_sites, int32_t *status) {
-    if (!c || !out || !n_out || !n_sites || !status || n1 < 0 || n2 < 0 || (n1 > 0 && !text1) || (n2 > 0 && !text2)) {
-        mc_set_error("mc_bed_compare_text: bad arguments");
-        return -12;
-    }
-    return cmp_call(c, TextSource{text1, nullptr, n1}, TextSource{text2, nullptr, n2}, out, n_out, n_sites, status);
-}
-
-extern "C" int mc_bed_compare_file(mc_ctx *c, const char *path1, const char *path2, const char **out, int64_t *n_out, int64_t *n_sites,
-                                   int32_t *status) {
-    if (!c || !path1 || !path2 || !out || !n_out || !n_sites || !status) {
-        mc_set_error("mc_bed_compare_file: bad arguments");
-        return -12;
-    }
-    int64_t n1 = 0, n2 = 0;
-    if (int rc = regular_file_size("mc_bed_compare_file", path1, &n1)) return rc;
-    if (int rc = regular_file_size("mc_bed_compare_file", path2, &n2)) return rc;
-    return cmp_call(c, TextSource{nullptr, path1, n1}, TextSource{nullptr, path2, n2}, out, n_out, n_sites, status);
-}
-
 // the arguments of a lifted comparison beyond those of a plain one -> 0, or -12 with the error set
-static int lifted_arguments(const char *who, mc_ctx *c, const mc_contig_table *t1, const mc_contig_table *t2, int64_t *n_unaligned) {
-    if (!n_unaligned || !lift_tables_ok(t1) || !lift_tables_ok(t2)) { mc_set_error("%s: bad arguments", who); return -12; }
-    *n_unaligned = 0;
-    if (!c->xmfa_map) { mc_set_error("%s: no alignment map is resident (mc_xmfa_map_text / _file first)", who); return -12; }
+static int lifted_arguments(mc_ctx *c, const mc_contig_table *t1, const mc_contig_table *t2, int64_t *n_unaligned) {
+    if (!n_unaligned || !lift_tables_ok(t1) || !lift_tables_ok(t2)) { mc_set_error("mc_bed_compare: bad arguments"); return -12; }
+    if (!c->xmfa_map) { mc_set_error("mc_bed_compare: no alignment map is resident (mc_xmfa_map first)"); return -12; }
     if (t1->off[t1->n_contigs] != c->xmfa_n1 || t2->off[t2->n_contigs] != c->xmfa_n2) {
-        mc_set_error("%s: the contig tables' totals are not those the map was built for", who);
+        mc_set_error("mc_bed_compare: the contig tables' totals are not those the map was built for");
         return -12;
     }
     return 0;
 }
 
-extern "C" int mc_bed_compare_lifted_text(mc_ctx *c, const char *text1, int64_t n1, const char *text2, int64_t n2, const mc_contig_table *t1,
-                                          const mc_contig_table *t2, const char **out, int64_t *n_out, int64_t *n_sites, int64_t *n_unaligned,
-                                          int32_t *status) {
-    if (!c || !out || !n_out || !n_sites || !status || n1 < 0 || n2 < 0 || (n1 > 0 && !text1) || (n2 > 0 && !text2)) {
-        mc_set_error("mc_bed_compare_lifted_text: bad arguments");
+extern "C" int mc_bed_compare(mc_ctx *c, const mc_text_source *bed1, const mc_text_source *bed2, const mc_contig_table *t1,
+                              const mc_contig_table *t2, const char **out, int64_t *n_out, int64_t *n_sites, int64_t *n_unaligned,
+                              int32_t *status) {
+    if (!c || !out || !n_out || !n_sites || !status || !t1 != !t2) {
+        mc_set_error("mc_bed_compare: bad arguments");
         return -12;
     }
-    if (int rc = lifted_arguments("mc_bed_compare_lifted_text", c, t1, t2, n_unaligned)) return rc;
-    const int rc = cmp_call(c, TextSource{text1, nullptr, n1}, TextSource{text2, nullptr, n2}, out, n_out, n_sites, status, t1, t2);
-    if (rc == 0 && *status == 0) *n_unaligned = c->cmp_unaligned;
+    if (n_unaligned) *n_unaligned = 0;
+    if (t1)
+        if (int rc = lifted_arguments(c, t1, t2, n_unaligned)) return rc;
+    mc_text_source s1 = {}, s2 = {};
+    if (int rc = text_source("mc_bed_compare", bed1, &s1)) return rc;
+    if (int rc = text_source("mc_bed_compare", bed2, &s2)) return rc;
+    const int rc = cmp_call(c, s1, s2, out, n_out, n_sites, status, t1, t2);
+    if (t1 && rc == 0 && *status == 0) *n_unaligned = c->cmp_unaligned;
     return rc;
 }
 
-extern "C" int mc_bed_compare_lifted_file(mc_ctx *c, const char *path1, const char *path2, const mc_contig_table *t1, const mc_contig_table *t2,
-                                          const char **out, int64_t *n_out, int64_t *n_sites, int64_t *n_unaligned, int32_t *status) {
-    if (!c || !path1 || !path2 || !out || !n_out || !n_sites || !status) {
-        mc_set_error("mc_bed_compare_lifted_file: bad arguments");
-        return -12;
-    }
-    if (int rc = lifted_arguments("mc_bed_compare_lifted_file", c, t1, t2, n_unaligned)) return rc;
-    int64_t n1 = 0, n2 = 0;
-    if (int rc = regular_file_size("mc_bed_compare_lifted_file", path1, &n1)) return rc;
-    if (int rc = regular_file_size("mc_bed_compare_lifted_file", path2, &n2)) return rc;
-    const int rc = cmp_call(c, TextSource{nullptr, path1, n1}, TextSource{nullptr, path2, n2}, out, n_out, n_sites, status, t1, t2);
-    if (rc == 0 && *status == 0) *n_unaligned = c->cmp_unaligned;
-    return rc;
-}
-
-extern "C" int mc_xmfa_map_text(mc_ctx *c, const char *text, int64_t n, int32_t seq1, int32_t seq2, int64_t n1, int64_t n2,
-                                mc_xmfa_map_view *view, int32_t *status) {
-    if (!c || !status || n < 0 || (n > 0 && !text) || n1 < 0 || n2 < 0 || seq1 == seq2) { mc_set_error("mc_xmfa_map_text: bad arguments"); return -12; }
-    return xm_call(c, TextSource{text, nullptr, n}, seq1, seq2, n1, n2, view, status);
-}
-
-extern "C" int mc_xmfa_map_file(mc_ctx *c, const char *path, int32_t seq1, int32_t seq2, int64_t n1, int64_t n2, mc_xmfa_map_view *view,
-                                int32_t *status) {
-    if (!c || !path || !status || n1 < 0 || n2 < 0 || seq1 == seq2) { mc_set_error("mc_xmfa_map_file: bad arguments"); return -12; }
-    int64_t n = 0;
-    if (int rc = regular_file_size("mc_xmfa_map_file", path, &n)) return rc;
-    return xm_call(c, TextSource{nullptr, path, n}, seq1, seq2, n1, n2, view, status);
+extern "C" int mc_xmfa_map(mc_ctx *c, const mc_text_source *src, int32_t seq1, int32_t seq2, int64_t n1, int64_t n2, mc_xmfa_map_view *view,
+                           int32_t *status) {
+    if (!c || !status || n1 < 0 || n2 < 0 || seq1 == seq2) { mc_set_error("mc_xmfa_map: bad arguments"); return -12; }
+    mc_text_source s = {};
+    if (int rc = text_source("mc_xmfa_map", src, &s)) return rc;
+    return xm_call(c, s, seq1, seq2, n1, n2, view, status);
 }
 
 extern "C" int mc_xmfa_map_last_stats(mc_ctx *c, mc_xmfa_stats *out) {

@@ -1,12 +1,12 @@
 // mc_xmfamap.inc -- two genomes with their own assemblies compared through a Mauve alignment: the XMFA text into a coordinate map
 // on the GPU, and bed1's lines lifted through it onto bed2's keys.  Part of the mc_bedcompare.hip unit (included there, inside its
 // unnamed namespace, behind kc_probe): kc_lift stands in kc_probe's place and everything from kc_sites on runs as it is.  The
-// definition -- lines, entries, columns, first-wins, the lift -- stands in mcaller_amd/compare_genomes.py; C ABI: mc_xmfa_map_text
-// / _file, mc_xmfa_map_last_stats, mc_xmfa_map_release, mc_bed_compare_lifted_text / _file; Python: Device.xmfa_map,
+// definition -- lines, entries, columns, first-wins, the lift -- stands in mcaller_amd/compare_genomes.py; C ABI: mc_xmfa_map,
+// mc_xmfa_map_last_stats, mc_xmfa_map_release, mc_bed_compare with its contig tables; Python: Device.xmfa_map,
 // Device.bed_compare(contigs1=, contigs2=), compare_genomes.compare_by_position_device(xmfa_path=).
 //
 // The map is map[g1] = (the column's ordinal among the paired columns of the file) << 33 | g2 << 1 | flip, ~0: unmapped, 8 bytes a
-// base of genome 1, resident in the context (mc_ctx::xmfa_map) from mc_xmfa_map_* to the next such call or mc_xmfa_map_release.
+// base of genome 1, resident in the context (mc_ctx::xmfa_map) from mc_xmfa_map to the next such call or mc_xmfa_map_release.
 // Declines (status 1, mc_last_error, mc_xmfa_map_last_stats: reason and line; no map is kept):
 //   line by line   MC_CMP_DECLINE_XMFA_BYTE      a '\r' or a byte >= 0x80, on any line (comments too)
 //                  MC_CMP_DECLINE_XMFA_HEADER    a header that is not `>[blanks]SEQ:START-END blanks +|- [blank anything]` with START-END
@@ -503,7 +503,7 @@ int xm_run(mc_ctx *c, Pool &pool, XmArgs &A, XmHead *d_head, int32_t *status) {
     return 0;
 }
 
-int xm_call(mc_ctx *c, const TextSource &src, int32_t seq1, int32_t seq2, int64_t n1, int64_t n2, mc_xmfa_map_view *view, int32_t *status) {
+int xm_call(mc_ctx *c, const mc_text_source &src, int32_t seq1, int32_t seq2, int64_t n1, int64_t n2, mc_xmfa_map_view *view, int32_t *status) {
     HIP_TRY(hipSetDevice(c->device));
     const auto t0 = std::chrono::steady_clock::now();
     hipStream_t st = c->stream;
@@ -512,12 +512,12 @@ int xm_call(mc_ctx *c, const TextSource &src, int32_t seq1, int32_t seq2, int64_
     mc_xmfa_stats &S = c->xmfa_stats;
     S = mc_xmfa_stats();
     S.decline_line = -1;
-    S.n_bytes = src.n; S.n1 = n1; S.n2 = n2;
+    S.n_bytes = src.n_bytes; S.n1 = n1; S.n2 = n2;
     *status = 0;
     if (view) *view = mc_xmfa_map_view();
     if (n1 > XM_COORD_CAP || n2 > XM_COORD_CAP) return xm_decline(c, status, MC_CMP_DECLINE_XMFA_GENOME, -1);
     const size_t n_map = (size_t)n1 + 1;
-    if (!cmp_fits((size_t)src.n + 4096 + n_map * (view ? 17 : 8))) return xm_decline(c, status, MC_CMP_DECLINE_MEMORY, -1);
+    if (!cmp_fits((size_t)src.n_bytes + 4096 + n_map * (view ? 17 : 8))) return xm_decline(c, status, MC_CMP_DECLINE_MEMORY, -1);
     unsigned long long *map = c->xmfa_allocs.get<unsigned long long>(n_map);
     if (!map) return -10;
     HIP_TRY(hipMemsetAsync(map, 0xff, n_map * 8, st));
@@ -529,7 +529,7 @@ int xm_call(mc_ctx *c, const TextSource &src, int32_t seq1, int32_t seq2, int64_
     const auto t_kernels = std::chrono::steady_clock::now();
     XmHead *d_head = nullptr, h = {};
     XmArgs A = {};
-    A.text = d_text; A.n_bytes = src.n; A.seq1 = seq1; A.seq2 = seq2; A.n1 = n1; A.n2 = n2; A.map = map;
+    A.text = d_text; A.n_bytes = src.n_bytes; A.seq1 = seq1; A.seq2 = seq2; A.n1 = n1; A.n2 = n2; A.map = map;
     int rc = pool.get(&d_head, 1);
     A.head = d_head;
     if (rc == 0) rc = xm_run(c, pool, A, d_head, status);

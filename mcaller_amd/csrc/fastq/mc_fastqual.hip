@@ -1,5 +1,5 @@
 // mc_fastqual.hip -- the read qualities of a FASTQ file, made on the GPU: one (key, mean phred) pair per record, what
-// read_qual.py:15-47 builds line by line in Python (C ABI: mc_fastq_quality_text / _file, mc_fastq_quality_last_stats,
+// read_qual.py:15-47 builds line by line in Python (C ABI: mc_fastq_quality, mc_fastq_quality_last_stats,
 // mc_fastq_quality_release; Python: Device.fastq_qualities, read_qual.extract_read_quality_device).  The unit stands in csrc/fastq/,
 // beside the units of the passes like csrc/bed/, csrc/train/ and csrc/merge/: no pass runs its kernels.
 //
@@ -292,7 +292,7 @@ int fq_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, mc_fastq_qualit
     return 0;
 }
 
-// what both entry points begin with -> 0: go on; 1: done (declined, *status set)
+// what a call begins with -> 0: go on; 1: done (declined, *status set)
 int fq_begin(mc_ctx *c, mc_fastq_quality_view *V, int32_t *status, int64_t n) {
     c->fq_stats = mc_fastq_quality_stats();
     c->fq_stats.decline_line = -1;
@@ -304,17 +304,17 @@ int fq_begin(mc_ctx *c, mc_fastq_quality_view *V, int32_t *status, int64_t n) {
     return 0;
 }
 
-// what both entry points run: the text of `src` onto the device and through fq_run
-int fq_call(mc_ctx *c, const TextSource &src, mc_fastq_quality_view *out, int32_t *status) {
+// what the entry point runs: the text of `src` onto the device and through fq_run
+int fq_call(mc_ctx *c, const mc_text_source &src, mc_fastq_quality_view *out, int32_t *status) {
     HIP_TRY(hipSetDevice(c->device));
     const auto t0 = std::chrono::steady_clock::now();
-    if (fq_begin(c, out, status, src.n)) return 0;
+    if (fq_begin(c, out, status, src.n_bytes)) return 0;
     Pool pool("fastq qualities");
     TextFeed feed(c, (size_t)32 << 20);
     char *d_text = nullptr;
     if (int rc = feed.put(pool, src, &d_text)) return rc;
     feed.times(c->fq_stats, t0);
-    const int rc = fq_run(c, pool, d_text, src.n, out, status);
+    const int rc = fq_run(c, pool, d_text, src.n_bytes, out, status);
     (void)hipStreamSynchronize(c->stream);                   // (an early return: nothing of the pool is in use when it goes)
     if (rc != 0 || *status != 0) *out = mc_fastq_quality_view();
     c->fq_stats.ms_total = ms_since(t0);
@@ -323,22 +323,14 @@ int fq_call(mc_ctx *c, const TextSource &src, mc_fastq_quality_view *out, int32_
 
 }  // namespace
 
-extern "C" int mc_fastq_quality_text(mc_ctx *c, const char *text, int64_t n_bytes, mc_fastq_quality_view *out, int32_t *status) {
-    if (!c || !out || !status || n_bytes < 0 || (n_bytes > 0 && !text)) {
-        mc_set_error("mc_fastq_quality_text: bad arguments");
+extern "C" int mc_fastq_quality(mc_ctx *c, const mc_text_source *src, mc_fastq_quality_view *out, int32_t *status) {
+    if (!c || !out || !status) {
+        mc_set_error("mc_fastq_quality: bad arguments");
         return -12;
     }
-    return fq_call(c, TextSource{text, nullptr, n_bytes}, out, status);
-}
-
-extern "C" int mc_fastq_quality_file(mc_ctx *c, const char *path, mc_fastq_quality_view *out, int32_t *status) {
-    if (!c || !path || !out || !status) {
-        mc_set_error("mc_fastq_quality_file: bad arguments");
-        return -12;
-    }
-    int64_t n = 0;
-    if (int rc = regular_file_size("mc_fastq_quality_file", path, &n)) return rc;
-    return fq_call(c, TextSource{nullptr, path, n}, out, status);
+    mc_text_source s = {};
+    if (int rc = text_source("mc_fastq_quality", src, &s)) return rc;
+    return fq_call(c, s, out, status);
 }
 
 extern "C" int mc_fastq_quality_last_stats(mc_ctx *c, mc_fastq_quality_stats *out) {

@@ -327,7 +327,7 @@ struct mc_ctx {
     size_t cmp_out_cap = 0;
     mc_cmp_stats cmp_stats = {};
     int64_t cmp_unaligned = 0;                    // (a lifted comparison) bed1's lines without an image
-    // ... the coordinate map of an XMFA alignment (compare/mc_xmfamap.inc): on the device from mc_xmfa_map_* until the next such
+    // ... the coordinate map of an XMFA alignment (compare/mc_xmfamap.inc): on the device from mc_xmfa_map until the next such
     // call or mc_xmfa_map_release; map[g1] = ordinal << 33 | g2 << 1 | flip, ~0: unmapped.  The view's host copies are pinned
     Pool xmfa_allocs{"alignment map"};
     unsigned long long *xmfa_map = nullptr;

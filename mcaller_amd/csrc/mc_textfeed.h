@@ -1,8 +1,8 @@
 // mc_textfeed.h -- what the six units that take whole text files through the GPU share on the host side (bed/mc_bedsum.hip,
 // train/mc_trainrows.hip, merge/mc_rowmerge.hip, fastq/mc_fastqual.hip, compare/mc_bedcompare.hip -- whose mc_xmfamap.inc sends an XMFA
 // alignment through the same feed, the seventh kind of file --, motifs/mc_motifscan.hip).  Included by those six units only, hence the unnamed
-// namespace: nothing here is linked across units.  An entry point refuses its arguments (-12), sizes its files
-// (regular_file_size), selects the device, and then
+// namespace: nothing here is linked across units.  An entry point refuses its arguments (-12), takes each of its sources
+// (text_source: the checks on a mc_text_source, a file sized), selects the device, and then
 //
 //     const auto t0 = std::chrono::steady_clock::now();
 //     ... blank the stats and the result; device_fits(n + ...) or decline(stats, status, "reader", text, reason, -1) ...
@@ -126,11 +126,16 @@ inline int lines_starts(Pool &pool, hipStream_t st, const char *d_text, int64_t 
     return 0;
 }
 
-// what an entry point takes its text from: a host text, or (path != nullptr) a file of n bytes
-struct TextSource {
-    const char *text, *path;
-    int64_t n;
-};
+// A source (mcaller_hip.h) as an entry point `what` was given it -> 0 and *out: the source with n_bytes filled in (a file is
+// sized); -12: none, a text and a path, a negative size, bytes without a text; -1: a path that is no readable regular file
+inline int text_source(const char *what, const mc_text_source *s, mc_text_source *out) {
+    if (!s || (s->text && s->path) || (!s->path && (s->n_bytes < 0 || (s->n_bytes > 0 && !s->text)))) {
+        mc_set_error("%s: bad arguments", what);
+        return -12;
+    }
+    *out = *s;
+    return s->path ? regular_file_size(what, s->path, &out->n_bytes) : 0;
+}
 
 // Host texts and files, one behind the other, into device buffers: copies on c->up_stream.  A file goes in blocks through the
 // context's two pinned stages in turn: block i is read while block i - 1 is on its way.  A stage is not written again until the
@@ -185,20 +190,20 @@ struct TextFeed {
         }
         return 0;
     }
-    int send(const TextSource &s, char *d_dst, char *last_byte = nullptr) {
-        if (s.path) return file(s.path, s.n, d_dst, last_byte);
-        if (last_byte && s.n > 0) *last_byte = s.text[s.n - 1];
-        return text(s.text, s.n, d_dst);
+    int send(const mc_text_source &s, char *d_dst, char *last_byte = nullptr) {
+        if (s.path) return file(s.path, s.n_bytes, d_dst, last_byte);
+        if (last_byte && s.n_bytes > 0) *last_byte = s.text[s.n_bytes - 1];
+        return text(s.text, s.n_bytes, d_dst);
     }
     int pad_and_wait(char *d_end) {              // 64 zero bytes behind a buffer's texts; everything sent is there
         HIP_TRY(hipMemsetAsync(d_end, 0, 64, c->up_stream));
         HIP_TRY(hipStreamSynchronize(c->up_stream));
         return 0;
     }
-    int put(Pool &pool, const TextSource &s, char **d_text) {      // one text in a buffer of its own, padded and waited for
-        if (pool.get(d_text, (size_t)s.n + 64)) return -10;
+    int put(Pool &pool, const mc_text_source &s, char **d_text) {  // one text in a buffer of its own, padded and waited for
+        if (pool.get(d_text, (size_t)s.n_bytes + 64)) return -10;
         if (int rc = send(s, *d_text)) return rc;
-        return pad_and_wait(*d_text + s.n);
+        return pad_and_wait(*d_text + s.n_bytes);
     }
     template <typename S>
     void times(S &stats, std::chrono::steady_clock::time_point t0) const {             // ms_h2d: what the copies added behind the reads they ran beside

@@ -550,10 +550,10 @@ int mg_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const MgFiles &
 
 // what both entry points begin with: the sources' texts onto the device, one behind the other -> 0: go on; 1: done (declined,
 // *status set); < 0: an error
-int mg_upload(mc_ctx *c, MgCall &M, const TextSource *src, int n_src, int32_t *status) {
+int mg_upload(mc_ctx *c, MgCall &M, const mc_text_source *src, int n_src, int32_t *status) {
     HIP_TRY(hipSetDevice(c->device));
     M.t0 = std::chrono::steady_clock::now();
-    for (int i = 0; i < n_src; ++i) M.F.end.push_back(M.n += src[i].n);
+    for (int i = 0; i < n_src; ++i) M.F.end.push_back(M.n += src[i].n_bytes);
     c->mg_stats = mc_rows_merge_stats();
     c->mg_stats.decline_line = -1;
     c->mg_stats.decline_file = -1;
@@ -569,7 +569,7 @@ int mg_upload(mc_ctx *c, MgCall &M, const TextSource *src, int n_src, int32_t *s
         if (int rc = feed.stages(M.block)) return rc;
     for (int i = 0; i < n_src; ++i) {
         char last = '\n';
-        if (int rc = feed.send(src[i], M.d_text + (M.F.end[i] - src[i].n), &last)) return rc;
+        if (int rc = feed.send(src[i], M.d_text + (M.F.end[i] - src[i].n_bytes), &last)) return rc;
         if (last != '\n' && M.bad_end < 0) M.bad_end = M.F.end[i];
     }
     if (int rc = feed.pad_and_wait(M.d_text + M.n)) return rc;
@@ -597,7 +597,7 @@ extern "C" int mc_rows_merge_text(mc_ctx *c, const char *text, int64_t n_bytes, 
         return -12;
     }
     *out = nullptr; *n_out = 0;
-    const TextSource src = {text, nullptr, n_bytes};
+    const mc_text_source src = {text, nullptr, n_bytes};
     MgCall M;
     if (int rc = mg_upload(c, M, &src, 1, status)) return rc < 0 ? rc : 0;
     int rc = mg_run(c, M.pool, M.d_text, M.n, M.F, M.bad_end, M.A, &M.nb, status);
@@ -621,10 +621,10 @@ extern "C" int mc_rows_merge_files(mc_ctx *c, const char *const *paths, int32_t 
         mc_set_error("mc_rows_merge_files: bad arguments");
         return -12;
     }
-    std::vector<TextSource> src((size_t)n_paths);
+    std::vector<mc_text_source> src((size_t)n_paths);
     for (int i = 0; i < n_paths; ++i) {
-        src[i] = TextSource{nullptr, paths[i], 0};
-        if (int rc = regular_file_size("mc_rows_merge_files", paths[i], &src[i].n)) return rc;
+        src[i] = mc_text_source{nullptr, paths[i], 0};
+        if (int rc = regular_file_size("mc_rows_merge_files", paths[i], &src[i].n_bytes)) return rc;
     }
     *n_lines_out = 0;
     MgCall M;

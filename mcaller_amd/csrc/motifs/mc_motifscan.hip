@@ -1,7 +1,7 @@
 // mc_motifscan.hip -- methylated motifs found de novo from called sites on the GPU: for every shape of X and '.', every X of it as
 // the called letter and every assignment of A, C, G, T to the X, how many candidates of the reference stand in such a window
 // (nGenome), how many of them are covered and how many methylated; the rows that are mostly methylated, less those a shorter
-// selected row explains, in order, as text -- what find_motifs.find_motifs builds in NumPy (C ABI: mc_motif_report_text / _file,
+// selected row explains, in order, as text -- what find_motifs.find_motifs builds in NumPy (C ABI: mc_motif_report,
 // mc_motif_report_last_stats, mc_motif_report_release; Python: Device.motif_report, find_motifs.find_motifs_device).  The unit
 // stands in csrc/motifs/, beside csrc/bed/, csrc/train/, csrc/merge/, csrc/fastq/ and csrc/compare/: no pass runs its kernels.
 //
@@ -46,12 +46,12 @@
 //                parent letter comes from), the parent's selected flag at the parent's key: set -> dropped.  Counts the survivors
 //   km_gather    the survivors' (entry, nGenome, nCovered, nMethylated) into a list, slots by atomicAdd: the host sorts them by
 //                the integer keys of the definition (they are few) and writes SPEC and the numbers with mc_rowtext.h
-//   --iupac      behind km_count, in place of km_select / km_keep / km_gather: mc_motifiupac.inc (C ABI: mc_motif_report_iupac_text /
-//                _file, mc_motif_report_iupac_last_stats)
+//   --iupac      behind km_count, in place of km_select / km_keep / km_gather: mc_motifiupac.inc (C ABI: mc_motif_report's iupac,
+//                mc_motif_report_iupac_last_stats)
 //   --iterative  behind km_count, round after round: the selection above (ms_rows, or mi_rows of mc_motifiupac.inc) gives the ordered
 //                rows in structured form, the first is printed, km_explain takes the candidates it explains out of the candidate
 //                planes and km_uncount out of every table (ms_key: the one statement of a window's validity and key, shared with
-//                km_count), and the selection runs again: mc_motifiter.inc (C ABI: mc_motif_report_iter_text / _file, _iter_last_stats,
+//                km_count), and the selection runs again: mc_motifiter.inc (C ABI: mc_motif_report's max_motifs, _iter_last_stats,
 //                _iter_left: the methylated candidates no row explains, as two planes in pinned memory)
 // No floating-point atomic anywhere; the counts are exact integers whatever the order of arrival.
 #include "../mc_textfeed.h"
@@ -616,14 +616,14 @@ int ms_run(mc_ctx *c, Pool &pool, MsArgs &A, MsHead *d_head, const mc_motif_para
 }
 
 // max_motifs: 0, or --iterative's 1 .. MC_MOTIF_MAX_ROUNDS
-int ms_call(mc_ctx *c, const mc_ref_view *ref, const TextSource &s1, const TextSource *s2, const mc_motif_params *P, bool iupac,
+int ms_call(mc_ctx *c, const mc_ref_view *ref, const mc_text_source &s1, const mc_text_source *s2, const mc_motif_params *P, bool iupac,
             int max_motifs, const char **out, int64_t *n_out, int64_t *n_rows, int32_t *status) {
     HIP_TRY(hipSetDevice(c->device));
     const auto t0 = std::chrono::steady_clock::now();
     mc_motif_stats &S = c->motif_stats;
     S = mc_motif_stats();
     S.decline_line = -1;
-    S.n_bytes1 = s1.n; S.n_bytes2 = s2 ? s2->n : 0;
+    S.n_bytes1 = s1.n_bytes; S.n_bytes2 = s2 ? s2->n_bytes : 0;
     c->motif_iupac_stats = mc_motif_iupac_stats();
     c->motif_iter_stats = mc_motif_iter_stats();
     c->motif_iter_stats.decline_line = -1;
@@ -650,7 +650,7 @@ int ms_call(mc_ctx *c, const mc_ref_view *ref, const TextSource &s1, const TextS
     }
     const int64_t n_words = G / 64 + 2;
     const uint32_t n_entries = tables.back().off + tables.back().entries;
-    const int64_t n_text = s1.n + (s2 ? s2->n : 0);
+    const int64_t n_text = s1.n_bytes + (s2 ? s2->n_bytes : 0);
     const int64_t id_bytes = NC > 0 ? P->contig_id_off[NC] : 0;
     const char *hs = getenv("MCALLER_MOTIF_STRETCH");
     int64_t stretch = hs && atoll(hs) >= 64 ? (atoll(hs) + 63) & ~63ll : MS_STRETCH;      // (below 64: as if unset)
@@ -706,14 +706,14 @@ int ms_call(mc_ctx *c, const mc_ref_view *ref, const TextSource &s1, const TextS
     TextFeed feed(c, (size_t)32 << 20);
     char last1 = '\n';
     if (int rc = feed.send(s1, d_text, &last1)) return rc;
-    int64_t off2 = s1.n;
-    if (s2 && s1.n > 0 && last1 != '\n') {                             // the bed's last line ends where the control's first begins
+    int64_t off2 = s1.n_bytes;
+    if (s2 && s1.n_bytes > 0 && last1 != '\n') {                       // the bed's last line ends where the control's first begins
         HIP_TRY(hipMemsetAsync(d_text + off2, '\n', 1, up));
         ++off2;
     }
     if (s2)
         if (int rc = feed.send(*s2, d_text + off2)) return rc;
-    const int64_t n_bytes = s2 ? off2 + s2->n : s1.n;
+    const int64_t n_bytes = s2 ? off2 + s2->n_bytes : s1.n_bytes;
     if (int rc = feed.pad_and_wait(d_text + n_bytes)) return rc;
     feed.times(S, t0);
     A.seq = d_seq; A.contig_len = d_meta; A.seq_off = d_meta + NC; A.gstart = d_meta + 2 * NC;
@@ -756,28 +756,29 @@ bool ms_bad_args(const mc_ctx *c, const mc_ref_view *ref, const mc_motif_params 
 
 }  // namespace
 
-extern "C" int mc_motif_report_text(mc_ctx *c, const mc_ref_view *ref, const char *bed, int64_t n_bed, const char *control, int64_t n_control,
-                                    const mc_motif_params *params, const char **out, int64_t *n_out, int64_t *n_rows, int32_t *status) {
-    if (ms_bad_args(c, ref, params, out, n_out, n_rows, status) || n_bed < 0 || (n_bed > 0 && !bed) || n_control < 0) {
-        mc_set_error("mc_motif_report_text: bad arguments");
+extern "C" int mc_motif_report(mc_ctx *c, const mc_ref_view *ref, const mc_text_source *bed, const mc_text_source *control,
+                               const mc_motif_params *params, int32_t iupac, int32_t max_motifs, const char **out, int64_t *n_out,
+                               int64_t *n_rows, int32_t *status) {
+    if (ms_bad_args(c, ref, params, out, n_out, n_rows, status) || max_motifs < 0 || max_motifs > MC_MOTIF_MAX_ROUNDS) {
+        mc_set_error("mc_motif_report: bad arguments");
         return -12;
     }
-    const TextSource s1{bed, nullptr, n_bed}, s2{control, nullptr, n_control};
-    return ms_call(c, ref, s1, control ? &s2 : nullptr, params, false, 0, out, n_out, n_rows, status);
-}
-
-extern "C" int mc_motif_report_file(mc_ctx *c, const mc_ref_view *ref, const char *bed_path, const char *control_path,
-                                    const mc_motif_params *params, const char **out, int64_t *n_out, int64_t *n_rows, int32_t *status) {
-    if (ms_bad_args(c, ref, params, out, n_out, n_rows, status) || !bed_path) {
-        mc_set_error("mc_motif_report_file: bad arguments");
-        return -12;
+    mc_text_source s1 = {}, s2 = {};
+    if (int rc = text_source("mc_motif_report", bed, &s1)) return rc;
+    if (control)
+        if (int rc = text_source("mc_motif_report", control, &s2)) return rc;
+    const int rc = ms_call(c, ref, s1, control ? &s2 : nullptr, params, iupac != 0, max_motifs, out, n_out, n_rows, status);
+    // the decline, if any, in the stats of --iupac and --iterative too (an iterative call fills both)
+    const mc_motif_stats &S = c->motif_stats;
+    if (iupac || max_motifs > 0) {
+        mc_motif_iupac_stats &I = c->motif_iupac_stats;
+        I.decline_line = S.decline_line; I.decline_reason = S.decline_reason; I.decline_file = S.decline_file;
     }
-    int64_t n1 = 0, n2 = 0;
-    if (int rc = regular_file_size("mc_motif_report_file", bed_path, &n1)) return rc;
-    if (control_path)
-        if (int rc = regular_file_size("mc_motif_report_file", control_path, &n2)) return rc;
-    const TextSource s1{nullptr, bed_path, n1}, s2{nullptr, control_path, n2};
-    return ms_call(c, ref, s1, control_path ? &s2 : nullptr, params, false, 0, out, n_out, n_rows, status);
+    if (max_motifs > 0) {
+        mc_motif_iter_stats &I = c->motif_iter_stats;
+        I.decline_line = S.decline_line; I.decline_reason = S.decline_reason; I.decline_file = S.decline_file;
+    }
+    return rc;
 }
 
 extern "C" int mc_motif_report_last_stats(mc_ctx *c, mc_motif_stats *out) {
@@ -786,76 +787,10 @@ extern "C" int mc_motif_report_last_stats(mc_ctx *c, mc_motif_stats *out) {
     return 0;
 }
 
-// ---- --iupac: the same calls with the rows merged into degenerate motifs (mc_motifiupac.inc) ----
-static int mi_done(mc_ctx *c, int rc) {                               // the decline, if any, in the iupac stats too
-    mc_motif_iupac_stats &I = c->motif_iupac_stats;
-    I.decline_line = c->motif_stats.decline_line; I.decline_reason = c->motif_stats.decline_reason; I.decline_file = c->motif_stats.decline_file;
-    return rc;
-}
-
-extern "C" int mc_motif_report_iupac_text(mc_ctx *c, const mc_ref_view *ref, const char *bed, int64_t n_bed, const char *control,
-                                          int64_t n_control, const mc_motif_params *params, const char **out, int64_t *n_out, int64_t *n_rows,
-                                          int32_t *status) {
-    if (ms_bad_args(c, ref, params, out, n_out, n_rows, status) || n_bed < 0 || (n_bed > 0 && !bed) || n_control < 0) {
-        mc_set_error("mc_motif_report_iupac_text: bad arguments");
-        return -12;
-    }
-    const TextSource s1{bed, nullptr, n_bed}, s2{control, nullptr, n_control};
-    return mi_done(c, ms_call(c, ref, s1, control ? &s2 : nullptr, params, true, 0, out, n_out, n_rows, status));
-}
-
-extern "C" int mc_motif_report_iupac_file(mc_ctx *c, const mc_ref_view *ref, const char *bed_path, const char *control_path,
-                                          const mc_motif_params *params, const char **out, int64_t *n_out, int64_t *n_rows, int32_t *status) {
-    if (ms_bad_args(c, ref, params, out, n_out, n_rows, status) || !bed_path) {
-        mc_set_error("mc_motif_report_iupac_file: bad arguments");
-        return -12;
-    }
-    int64_t n1 = 0, n2 = 0;
-    if (int rc = regular_file_size("mc_motif_report_iupac_file", bed_path, &n1)) return rc;
-    if (control_path)
-        if (int rc = regular_file_size("mc_motif_report_iupac_file", control_path, &n2)) return rc;
-    const TextSource s1{nullptr, bed_path, n1}, s2{nullptr, control_path, n2};
-    return mi_done(c, ms_call(c, ref, s1, control_path ? &s2 : nullptr, params, true, 0, out, n_out, n_rows, status));
-}
-
 extern "C" int mc_motif_report_iupac_last_stats(mc_ctx *c, mc_motif_iupac_stats *out) {
     if (!c || !out) { mc_set_error("mc_motif_report_iupac_last_stats: bad arguments"); return -12; }
     *out = c->motif_iupac_stats;
     return 0;
-}
-
-// ---- --iterative: the motifs peeled off one at a time (mc_motifiter.inc) ----
-static int it_done(mc_ctx *c, int rc) {                               // the decline, if any, in the iterative stats too
-    mc_motif_iter_stats &I = c->motif_iter_stats;
-    I.decline_line = c->motif_stats.decline_line; I.decline_reason = c->motif_stats.decline_reason; I.decline_file = c->motif_stats.decline_file;
-    return mi_done(c, rc);
-}
-
-extern "C" int mc_motif_report_iter_text(mc_ctx *c, const mc_ref_view *ref, const char *bed, int64_t n_bed, const char *control, int64_t n_control,
-                                         const mc_motif_params *params, int32_t iupac, int32_t max_motifs, const char **out, int64_t *n_out,
-                                         int64_t *n_rows, int32_t *status) {
-    if (ms_bad_args(c, ref, params, out, n_out, n_rows, status) || n_bed < 0 || (n_bed > 0 && !bed) || n_control < 0 || max_motifs < 1 ||
-        max_motifs > MC_MOTIF_MAX_ROUNDS) {
-        mc_set_error("mc_motif_report_iter_text: bad arguments");
-        return -12;
-    }
-    const TextSource s1{bed, nullptr, n_bed}, s2{control, nullptr, n_control};
-    return it_done(c, ms_call(c, ref, s1, control ? &s2 : nullptr, params, iupac != 0, max_motifs, out, n_out, n_rows, status));
-}
-
-extern "C" int mc_motif_report_iter_file(mc_ctx *c, const mc_ref_view *ref, const char *bed_path, const char *control_path,
-                                         const mc_motif_params *params, int32_t iupac, int32_t max_motifs, const char **out, int64_t *n_out,
-                                         int64_t *n_rows, int32_t *status) {
-    if (ms_bad_args(c, ref, params, out, n_out, n_rows, status) || !bed_path || max_motifs < 1 || max_motifs > MC_MOTIF_MAX_ROUNDS) {
-        mc_set_error("mc_motif_report_iter_file: bad arguments");
-        return -12;
-    }
-    int64_t n1 = 0, n2 = 0;
-    if (int rc = regular_file_size("mc_motif_report_iter_file", bed_path, &n1)) return rc;
-    if (control_path)
-        if (int rc = regular_file_size("mc_motif_report_iter_file", control_path, &n2)) return rc;
-    const TextSource s1{nullptr, bed_path, n1}, s2{nullptr, control_path, n2};
-    return it_done(c, ms_call(c, ref, s1, control_path ? &s2 : nullptr, params, iupac != 0, max_motifs, out, n_out, n_rows, status));
 }
 
 extern "C" int mc_motif_report_iter_last_stats(mc_ctx *c, mc_motif_iter_stats *out) {

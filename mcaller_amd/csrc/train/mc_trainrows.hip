@@ -1,5 +1,5 @@
 // mc_trainrows.hip -- the rows of a `--training_tsv` file (`.diffs.<k>.train`) as matrices, made on the GPU: what
-// load_mCaller_data.py:14-29 (tsv2matrix) builds line by line in Python (C ABI: mc_train_rows_text / _file, mc_train_rows_last_stats,
+// load_mCaller_data.py:14-29 (tsv2matrix) builds line by line in Python (C ABI: mc_train_rows, mc_train_rows_last_stats,
 // mc_train_rows_release; Python: Device.training_rows, load_mCaller_data.tsv2matrix_device).  The unit stands in csrc/train/, beside
 // the units of the passes like csrc/bed/: no pass runs its kernels.  mc_parse_doubles_device, the probe of mc_decimal.h's device
 // build (Device.parse_doubles), lives here too: this unit is that header's device user.
@@ -403,7 +403,7 @@ int tr_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *pai
     return 0;
 }
 
-// what both entry points begin with -> 0: go on; 1: done (declined, *status set); < 0: an error
+// what a call begins with -> 0: go on; 1: done (declined, *status set); < 0: an error
 int tr_begin(mc_ctx *c, const char *pairs, int32_t n_pairs, mc_train_rows_view *V, int32_t *status, int64_t n) {
     c->tr_stats = mc_train_rows_stats();
     c->tr_stats.decline_line = -1;
@@ -418,17 +418,17 @@ int tr_begin(mc_ctx *c, const char *pairs, int32_t n_pairs, mc_train_rows_view *
     return 0;
 }
 
-// what both entry points run: the text of `src` onto the device and through tr_run
-int tr_call(mc_ctx *c, const TextSource &src, const char *pairs, int32_t n_pairs, mc_train_rows_view *out, int32_t *status) {
+// what the entry point runs: the text of `src` onto the device and through tr_run
+int tr_call(mc_ctx *c, const mc_text_source &src, const char *pairs, int32_t n_pairs, mc_train_rows_view *out, int32_t *status) {
     HIP_TRY(hipSetDevice(c->device));
     const auto t0 = std::chrono::steady_clock::now();
-    if (int rc = tr_begin(c, pairs, n_pairs, out, status, src.n)) return rc < 0 ? rc : 0;
+    if (int rc = tr_begin(c, pairs, n_pairs, out, status, src.n_bytes)) return rc < 0 ? rc : 0;
     Pool pool("training rows");
     TextFeed feed(c, (size_t)64 << 20);
     char *d_text = nullptr;
     if (int rc = feed.put(pool, src, &d_text)) return rc;
     feed.times(c->tr_stats, t0);
-    const int rc = tr_run(c, pool, d_text, src.n, pairs, n_pairs, out, status);
+    const int rc = tr_run(c, pool, d_text, src.n_bytes, pairs, n_pairs, out, status);
     (void)hipStreamSynchronize(c->stream);                   // (an early return: nothing of the pool is in use when it goes)
     if (rc != 0 || *status != 0) *out = mc_train_rows_view();
     c->tr_stats.ms_total = ms_since(t0);
@@ -437,23 +437,15 @@ int tr_call(mc_ctx *c, const TextSource &src, const char *pairs, int32_t n_pairs
 
 }  // namespace
 
-extern "C" int mc_train_rows_text(mc_ctx *c, const char *text, int64_t n_bytes, const char *pairs, int32_t n_pairs, mc_train_rows_view *out,
-                                  int32_t *status) {
-    if (!c || !out || !status || n_bytes < 0 || (n_bytes > 0 && !text)) {
-        mc_set_error("mc_train_rows_text: bad arguments");
+extern "C" int mc_train_rows(mc_ctx *c, const mc_text_source *src, const char *pairs, int32_t n_pairs, mc_train_rows_view *out,
+                             int32_t *status) {
+    if (!c || !out || !status) {
+        mc_set_error("mc_train_rows: bad arguments");
         return -12;
     }
-    return tr_call(c, TextSource{text, nullptr, n_bytes}, pairs, n_pairs, out, status);
-}
-
-extern "C" int mc_train_rows_file(mc_ctx *c, const char *path, const char *pairs, int32_t n_pairs, mc_train_rows_view *out, int32_t *status) {
-    if (!c || !path || !out || !status) {
-        mc_set_error("mc_train_rows_file: bad arguments");
-        return -12;
-    }
-    int64_t n = 0;
-    if (int rc = regular_file_size("mc_train_rows_file", path, &n)) return rc;
-    return tr_call(c, TextSource{nullptr, path, n}, pairs, n_pairs, out, status);
+    mc_text_source s = {};
+    if (int rc = text_source("mc_train_rows", src, &s)) return rc;
+    return tr_call(c, s, pairs, n_pairs, out, status);
 }
 
 extern "C" int mc_train_rows_last_stats(mc_ctx *c, mc_train_rows_stats *out) {

@@ -40,6 +40,20 @@ def _contig_table(contigs):
     return t, (pool, id_off, offs)
 
 
+def _source(path=None, text=None):
+    """A file (`path`) or a text (`text`, bytes) as a mc_text_source -> (what a call takes: a reference to the struct, or None
+    without either; what the call reads from)."""
+    if path is None and text is None:
+        return None, None
+    keep = os.fsencode(path) if path is not None else bytes(text)
+    s = _lib.TextSource()
+    if path is not None:
+        s.path = C.cast(C.c_char_p(keep), C.c_void_p)
+    else:
+        s.text, s.n_bytes = C.cast(C.c_char_p(keep), C.c_void_p), len(keep)
+    return C.byref(s), (s, keep)
+
+
 class Device(object):
     def __init__(self, index=None):
         import threading
@@ -678,7 +692,7 @@ class Device(object):
         `positions_path` (beside `path`) or `positions_text` (beside `text`) what make_bed -p writes: the rows at the listed
         positions, every entry, two t-test columns in a BED row.
         With `ref_path` / `ref_text` (a FASTA: make_bed --ref) the GFF attributes carry the 41 bases around the site; with
-        `site_stats` --gff --vo is made (fracLow, fracUp, identificationQv: mc_bed_annotate_*) -- without it that combination
+        `site_stats` --gff --vo is made (fracLow, fracUp, identificationQv: mc_bed_params.site_stats) -- without it that combination
         declines, as it always did.
         -> (bytes, number of sites, None), or (None, 0, reason) when the device declines: the caller runs the host code."""
         if (path is None) == (text is None):
@@ -688,34 +702,12 @@ class Device(object):
         if (ref_path is not None and path is None) or (ref_text is not None and text is None):
             raise ValueError('bed_summarise: ref_path goes with path, ref_text with text')
         d = int(min_depth)
-        prm = _lib.BedParams(max(-2 ** 62, min(2 ** 62, d)), float(mod_threshold), int(bool(control)), int(bool(with_probs)), int(bool(gff)), 0)
+        prm = _lib.BedParams(max(-2 ** 62, min(2 ** 62, d)), float(mod_threshold), int(bool(control)), int(bool(with_probs)), int(bool(gff)),
+                             int(bool(site_stats) or ref_path is not None or ref_text is not None))
         out, n_out, n_sites, status = C.c_void_p(), C.c_int64(), C.c_int64(), C.c_int32()
-        if site_stats or ref_path is not None or ref_text is not None:
-            if path is not None:
-                check(lib().mc_bed_annotate_file(self._ctx, os.fsencode(path), None if positions_path is None else os.fsencode(positions_path),
-                                                 None if ref_path is None else os.fsencode(ref_path), C.byref(prm), C.byref(out),
-                                                 C.byref(n_out), C.byref(n_sites), C.byref(status)))
-            else:
-                text = bytes(text)
-                positions_text = None if positions_text is None else bytes(positions_text)
-                ref_text = None if ref_text is None else bytes(ref_text)
-                check(lib().mc_bed_annotate_text(self._ctx, text, len(text), positions_text, len(positions_text or b''), ref_text,
-                                                 len(ref_text or b''), C.byref(prm), C.byref(out), C.byref(n_out), C.byref(n_sites),
-                                                 C.byref(status)))
-        elif positions_path is not None:
-            check(lib().mc_bed_positions_file(self._ctx, os.fsencode(path), os.fsencode(positions_path), C.byref(prm), C.byref(out),
-                                              C.byref(n_out), C.byref(n_sites), C.byref(status)))
-        elif positions_text is not None:
-            text, positions_text = bytes(text), bytes(positions_text)
-            check(lib().mc_bed_positions_text(self._ctx, text, len(text), positions_text, len(positions_text), C.byref(prm), C.byref(out),
-                                              C.byref(n_out), C.byref(n_sites), C.byref(status)))
-        elif path is not None:
-            check(lib().mc_bed_summarise_file(self._ctx, os.fsencode(path), C.byref(prm), C.byref(out), C.byref(n_out), C.byref(n_sites),
-                                              C.byref(status)))
-        else:
-            text = bytes(text)
-            check(lib().mc_bed_summarise_text(self._ctx, text, len(text), C.byref(prm), C.byref(out), C.byref(n_out), C.byref(n_sites),
-                                              C.byref(status)))
+        (src, keep), (pos, keep_pos), (ref, keep_ref) = _source(path, text), _source(positions_path, positions_text), _source(ref_path, ref_text)
+        check(lib().mc_bed_summarise(self._ctx, src, pos, ref, C.byref(prm), C.byref(out), C.byref(n_out), C.byref(n_sites), C.byref(status)))
+        del keep, keep_pos, keep_ref
         if status.value != 0:
             return None, 0, last_error()
         blob = C.string_at(out.value, n_out.value) if n_out.value else b''
@@ -829,11 +821,9 @@ class Device(object):
             raise ValueError('training_rows: a centre pair is two characters')
         blob = b''.join(pairs)
         view, status = _lib.TrainRowsView(), C.c_int32()
-        if path is not None:
-            check(lib().mc_train_rows_file(self._ctx, os.fsencode(path), blob, len(pairs), C.byref(view), C.byref(status)))
-        else:
-            text = bytes(text)
-            check(lib().mc_train_rows_text(self._ctx, text, len(text), blob, len(pairs), C.byref(view), C.byref(status)))
+        src, keep = _source(path, text)
+        check(lib().mc_train_rows(self._ctx, src, blob, len(pairs), C.byref(view), C.byref(status)))
+        del keep
         if status.value != 0:
             return None, None, None, last_error()
         nf, width, total = view.n_features, view.ctx_width, view.n_rows_total
@@ -870,11 +860,9 @@ class Device(object):
         if (path is None) == (text is None):
             raise ValueError('fastq_qualities: a path or a text')
         view, status = _lib.FastqQualityView(), C.c_int32()
-        if path is not None:
-            check(lib().mc_fastq_quality_file(self._ctx, os.fsencode(path), C.byref(view), C.byref(status)))
-        else:
-            text = bytes(text)
-            check(lib().mc_fastq_quality_text(self._ctx, text, len(text), C.byref(view), C.byref(status)))
+        src, keep = _source(path, text)
+        check(lib().mc_fastq_quality(self._ctx, src, C.byref(view), C.byref(status)))
+        del keep
         if status.value != 0:
             return None, None, last_error()
         return _lib.fastq_unpack(view.key_pool, view.key_off, view.mean, int(view.n_records)) + (None,)
@@ -902,26 +890,17 @@ class Device(object):
             raise ValueError('bed_compare: the contigs of both genomes or of neither')
         out, n_out, n_sites, status = C.c_void_p(), C.c_int64(), C.c_int64(), C.c_int32()
         self._unaligned = None
+        n_unaligned = C.c_int64()
+        (bed1, keep1), (bed2, keep2) = _source(path1, text1), _source(path2, text2)
+        t1, t2, keep = None, None, None
         if contigs1 is not None:
-            (t1, keep1), (t2, keep2) = _contig_table(contigs1), _contig_table(contigs2)
-            n_unaligned = C.c_int64()
-            if path1 is not None:
-                check(lib().mc_bed_compare_lifted_file(self._ctx, os.fsencode(path1), os.fsencode(path2), C.byref(t1), C.byref(t2),
-                                                       C.byref(out), C.byref(n_out), C.byref(n_sites), C.byref(n_unaligned), C.byref(status)))
-            else:
-                text1, text2 = bytes(text1), bytes(text2)
-                check(lib().mc_bed_compare_lifted_text(self._ctx, text1, len(text1), text2, len(text2), C.byref(t1), C.byref(t2),
-                                                       C.byref(out), C.byref(n_out), C.byref(n_sites), C.byref(n_unaligned), C.byref(status)))
-            del keep1, keep2
-            if status.value == 0:
-                self._unaligned = int(n_unaligned.value)
-        elif path1 is not None:
-            check(lib().mc_bed_compare_file(self._ctx, os.fsencode(path1), os.fsencode(path2), C.byref(out), C.byref(n_out),
-                                            C.byref(n_sites), C.byref(status)))
-        else:
-            text1, text2 = bytes(text1), bytes(text2)
-            check(lib().mc_bed_compare_text(self._ctx, text1, len(text1), text2, len(text2), C.byref(out), C.byref(n_out),
-                                            C.byref(n_sites), C.byref(status)))
+            (t1, keep_t1), (t2, keep_t2) = _contig_table(contigs1), _contig_table(contigs2)
+            t1, t2, keep = C.byref(t1), C.byref(t2), (keep_t1, keep_t2)
+        check(lib().mc_bed_compare(self._ctx, bed1, bed2, t1, t2, C.byref(out), C.byref(n_out), C.byref(n_sites), C.byref(n_unaligned),
+                                   C.byref(status)))
+        del keep, keep1, keep2
+        if contigs1 is not None and status.value == 0:
+            self._unaligned = int(n_unaligned.value)
         if status.value != 0:
             return None, 0, last_error()
         return (C.string_at(out.value, n_out.value) if n_out.value else b''), int(n_sites.value), None
@@ -942,11 +921,9 @@ class Device(object):
         v, status = _lib.XmfaMapView(), C.c_int32()
         pv = C.byref(v) if view else None
         n2 = (1 << 31) - 2 if n2 is None else int(n2)
-        if path is not None:
-            check(lib().mc_xmfa_map_file(self._ctx, os.fsencode(path), int(seqs[0]), int(seqs[1]), int(n1), n2, pv, C.byref(status)))
-        else:
-            text = bytes(text)
-            check(lib().mc_xmfa_map_text(self._ctx, text, len(text), int(seqs[0]), int(seqs[1]), int(n1), n2, pv, C.byref(status)))
+        src, keep = _source(path, text)
+        check(lib().mc_xmfa_map(self._ctx, src, int(seqs[0]), int(seqs[1]), int(n1), n2, pv, C.byref(status)))
+        del keep
         if status.value != 0:
             return None, None, last_error()
         if not view:
@@ -1011,32 +988,10 @@ class Device(object):
         P.min_sites, P.min_fraction, P.keep_all = int(min_sites), float(min_fraction), int(bool(keep_all))
         P.contig_ids, P.contig_id_off = _ptr(id_pool), _ptr(id_off)
         out, n_out, n_rows, status = C.c_void_p(), C.c_int64(), C.c_int64(), C.c_int32()
-        if iterative and path is not None:
-            check(lib().mc_motif_report_iter_file(self._ctx, C.byref(v), os.fsencode(path), None if control_path is None else os.fsencode(control_path),
-                                                  C.byref(P), int(bool(iupac)), int(max_motifs), C.byref(out), C.byref(n_out), C.byref(n_rows),
-                                                  C.byref(status)))
-        elif iterative:
-            text = bytes(text)
-            control_text = None if control_text is None else bytes(control_text)
-            check(lib().mc_motif_report_iter_text(self._ctx, C.byref(v), text, len(text), control_text, 0 if control_text is None else len(control_text),
-                                                  C.byref(P), int(bool(iupac)), int(max_motifs), C.byref(out), C.byref(n_out), C.byref(n_rows),
-                                                  C.byref(status)))
-        elif path is not None and iupac:
-            check(lib().mc_motif_report_iupac_file(self._ctx, C.byref(v), os.fsencode(path), None if control_path is None else os.fsencode(control_path),
-                                                   C.byref(P), C.byref(out), C.byref(n_out), C.byref(n_rows), C.byref(status)))
-        elif path is not None:
-            check(lib().mc_motif_report_file(self._ctx, C.byref(v), os.fsencode(path), None if control_path is None else os.fsencode(control_path),
-                                             C.byref(P), C.byref(out), C.byref(n_out), C.byref(n_rows), C.byref(status)))
-        else:
-            text = bytes(text)
-            control_text = None if control_text is None else bytes(control_text)
-            n_control = 0 if control_text is None else len(control_text)
-            if iupac:
-                check(lib().mc_motif_report_iupac_text(self._ctx, C.byref(v), text, len(text), control_text, n_control, C.byref(P), C.byref(out),
-                                                       C.byref(n_out), C.byref(n_rows), C.byref(status)))
-            else:
-                check(lib().mc_motif_report_text(self._ctx, C.byref(v), text, len(text), control_text, n_control, C.byref(P), C.byref(out),
-                                                 C.byref(n_out), C.byref(n_rows), C.byref(status)))
+        (bed, keep), (control, keep_control) = _source(path, text), _source(control_path, control_text)
+        check(lib().mc_motif_report(self._ctx, C.byref(v), bed, control, C.byref(P), int(bool(iupac)), int(max_motifs) if iterative else 0,
+                                    C.byref(out), C.byref(n_out), C.byref(n_rows), C.byref(status)))
+        del keep, keep_control
         blob = C.string_at(out.value, n_out.value) if status.value == 0 and n_out.value else b''
         if iterative:
             if status.value != 0:

@@ -50,6 +50,115 @@ def test_bed_takes_three_files_through_the_feed_in_one_call(dev, cases, monkeypa
     case.check_stats(dev)
 
 
+def _entry_points(dev, cases, tmp_path):
+    """{entry point: (its sources' names, which of them may be null, call(**sources) -> (rc, status) with every other argument
+    sound, works() -> the pipeline's small case, from files, gives the host's result on the context)}.  The bed summary, the training
+    rows and the FASTQ qualities run their case of tests/textfeed_cases.py; the comparison, the alignment map and the motif finder
+    have none there and run the smallest case of their own tests."""
+    import ctypes
+    import numpy as np
+    from mcaller_amd import _lib, compare_genomes as CG, find_motifs as FM
+    from tests import gpu_compare_cases as GC, motif_sites as MS, xmfa_cases as X
+    L, ctx = _lib.lib(), dev._ctx
+    by = ctypes.byref
+
+    def call(name, *args):
+        status = ctypes.c_int32(77)
+        return getattr(L, name)(ctx, *args, by(status)), status.value
+
+    out, n_out, n, view = ctypes.c_void_p(), ctypes.c_int64(), ctypes.c_int64(), _lib.TrainRowsView()
+    fq_view, ref, params = _lib.FastqQualityView(), _lib.RefView(), _lib.MotifParams()
+    prm = _lib.BedParams(1, 0.5, 0, 0, 0, 0)
+
+    def case_works(name):
+        return lambda: cases[name].run_file(dev) == cases[name].twin
+
+    t1, t2 = GC.key_pair()
+    (tmp_path / 'a.bed').write_bytes(t1)
+    (tmp_path / 'b.bed').write_bytes(t2)
+    cmp_want = CG.compare_rows(str(tmp_path / 'a.bed'), str(tmp_path / 'b.bed'))
+
+    def compare_works():
+        return dev.bed_compare(path1=str(tmp_path / 'a.bed'), path2=str(tmp_path / 'b.bed')) == cmp_want + (None,)
+
+    xc = X.identity_case()
+    (tmp_path / 'x.xmfa').write_bytes(xc['xmfa'])
+    want_g2, want_flip = CG.xmfa_map(str(tmp_path / 'x.xmfa'), xc['n1'], xc['seqs'], xc['n2'])
+
+    def xmfa_works():
+        g2, flip, why = dev.xmfa_map(path=str(tmp_path / 'x.xmfa'), n1=xc['n1'], n2=xc['n2'], seqs=xc['seqs'])
+        dev.xmfa_map_release()
+        return why is None and np.array_equal(g2, want_g2) and np.array_equal(flip, want_flip)
+
+    contigs, bed, control, shapes = MS.placed_case()
+    m_bed, m_ctl, m_kw = MS.bed_text(bed, 'vo'), MS.bed_text(control), dict(min_sites=1, min_fraction=0.0, keep_all=True)
+    for key, blob in (('ref.fasta', MS.fasta(contigs)), ('sites.bed', m_bed), ('control.bed', m_ctl)):
+        (tmp_path / key).write_bytes(blob)
+    m_n = FM.find_motifs(str(tmp_path / 'ref.fasta'), str(tmp_path / 'sites.bed'), str(tmp_path / 'control.bed'), out=str(tmp_path / 'host.tsv'),
+                         shapes=shapes, **m_kw)
+    m_want = ((tmp_path / 'host.tsv').read_bytes(), m_n, None)
+    m_ref = FM.read_reference(str(tmp_path / 'ref.fasta'))
+
+    def motif_works():
+        return dev.motif_report(m_ref, path=str(tmp_path / 'sites.bed'), control_path=str(tmp_path / 'control.bed'), shapes=FM.parse_shapes(shapes),
+                                **m_kw) == m_want
+
+    return {
+        'mc_bed_summarise': (('src', 'positions', 'fasta'), ('positions', 'fasta'), lambda src, positions, fasta: call(
+            'mc_bed_summarise', src, positions, fasta, by(prm), by(out), by(n_out), by(n)), case_works('bed')),
+        'mc_motif_report': (('bed', 'control'), ('control',), lambda bed, control: call(
+            'mc_motif_report', by(ref), bed, control, by(params), 0, 0, by(out), by(n_out), by(n)), motif_works),
+        'mc_bed_compare': (('bed1', 'bed2'), (), lambda bed1, bed2: call(
+            'mc_bed_compare', bed1, bed2, None, None, by(out), by(n_out), by(n), None), compare_works),
+        'mc_xmfa_map': (('src',), (), lambda src: call('mc_xmfa_map', src, 1, 2, 8, 8, None), xmfa_works),
+        'mc_train_rows': (('src',), (), lambda src: call('mc_train_rows', src, b'', 0, by(view)), case_works('train')),
+        'mc_fastq_quality': (('src',), (), lambda src: call('mc_fastq_quality', src, by(fq_view)), case_works('fastq')),
+    }
+
+
+def test_every_entry_point_refuses_a_source_that_is_none_and_runs_its_pipeline_afterwards(dev, cases, tmp_path):
+    """What mc_textfeed.h's text_source checks, for every source of the six entry points that take mc_text_source: no kernel runs in
+    a refusal, the error names the entry point, and the context does the pipeline's small case behind every one of them."""
+    import ctypes
+    from mcaller_amd import _lib
+    L = _lib.lib()
+    text = b'x\ty\n'                                                   # (a sound source beside the one on trial; never reached)
+    keep = ctypes.c_char_p(text)
+    at = ctypes.cast(keep, ctypes.c_void_p)
+    folder = ctypes.cast(ctypes.c_char_p(os.fsencode(str(tmp_path))), ctypes.c_void_p)
+    sound = _lib.TextSource(at, None, len(text))
+    refused = dict(both=_lib.TextSource(at, folder, len(text)), neither=_lib.TextSource(None, None, 1), negative=_lib.TextSource(at, None, -1))
+    points = _entry_points(dev, cases, tmp_path)
+    assert len(points) == 6
+    for name, (sources, optional, call, works) in points.items():
+        for on_trial in sources:
+            trials = dict(refused, folder=_lib.TextSource(None, folder, 0))
+            if on_trial not in optional:
+                trials['null'] = None
+            for what, source in trials.items():
+                args = {s: ctypes.byref(sound) for s in sources}
+                args[on_trial] = None if source is None else ctypes.byref(source)
+                rc, status = call(**args)
+                said = L.mc_last_error()
+                if what == 'folder':
+                    assert rc < 0 and b'is not a readable file' in said and status != 1, (name, on_trial, rc, said, status)
+                else:
+                    assert rc == -12, (name, on_trial, what, rc, said)
+                assert name.encode() in said, (name, on_trial, what, said)
+                assert works(), (name, on_trial, what)
+    # mc_bed_params.site_stats: --gff --vo declines without it and is made with it
+    by = ctypes.byref
+    diffs = cases['bed'].files['diffs']
+    src = _lib.TextSource(ctypes.cast(ctypes.c_char_p(diffs), ctypes.c_void_p), None, len(diffs))
+    seen = []
+    for site_stats in (0, 1):
+        prm = _lib.BedParams(1, 0.5, 0, 1, 1, site_stats)
+        out, n_out, n, status = ctypes.c_void_p(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32(77)
+        assert L.mc_bed_summarise(dev._ctx, by(src), None, None, by(prm), by(out), by(n_out), by(n), by(status)) == 0
+        seen.append((status.value, dev.bed_last_stats()['decline_reason'], n_out.value > 0 and n.value > 0))
+    assert seen == [(1, _lib.ABI.constants['MC_BED_DECLINE_OPTIONS'], False), (0, 0, True)], seen
+
+
 SIZES = (0, 45, 255, 256, 257, 700)          # an empty part, one line, file ends beside and on a block edge, three blocks
 
 
