@@ -64,10 +64,18 @@ typedef struct mc_table_view {
     const uint8_t *model_n_bits;  /* [ceil(n_rows / 8)] bit r & 7 of byte r >> 3: (flags[r] & MC_F_MODEL_N) != 0 -- the one bit of the
                                      flag column the scan looks at, 1/8 B/row where the flag bytes are 1 (mc_pack_model_n).  NULL: the
                                      upload calls pack it from `flags` */
+    const uint16_t *idx_rel_bits; /* [ceil(n_rows / 8)] one word per unit of eight rows, row r = 8u + e: bit e of word u is
+                                     event_idx[r] > event_idx[r-1], bit 8 + e is event_idx[r] < event_idx[r-1] (neither: equal) --
+                                     the row before it in the TABLE, whatever block that belongs to; row 0: neither.  All the
+                                     first pass's validation asks of the index column, 1/4 B/row where the indices are 4
+                                     (mc_pack_idx_rel).  NULL: the upload calls pack it from `event_idx` */
 } mc_table_view;
 /* The model-N bit column of a flag column: out[r >> 3] bit r & 7 = (flags[r] & MC_F_MODEL_N) != 0, every byte of
  * [0, ceil(n_rows / 8)) written (bits at or beyond n_rows: 0). */
 void mc_pack_model_n(const uint8_t *flags, int64_t n_rows, uint8_t *out);
+/* The index-relation column of an event-index column (mc_table_view.idx_rel_bits): every word of [0, ceil(n_rows / 8))
+ * written (row 0 and the bits at or beyond n_rows: 0). */
+void mc_pack_idx_rel(const int32_t *event_idx, int64_t n_rows, uint16_t *out);
 
 /* ---- marked reference: what find_and_methylate builds (extract_contexts.py:60-81), as bitmasks ---- */
 typedef struct mc_ref_view {
@@ -570,6 +578,8 @@ int mc_ctx_fetch_columns(mc_ctx *ctx, int32_t slot, int64_t n_rows, int32_t *pos
                          uint8_t *flags);
 /* ... and its model-N bit column: ceil(n_rows / 8) bytes (bits at or beyond n_rows are whatever the slot holds there). */
 int mc_ctx_fetch_model_n_bits(mc_ctx *ctx, int32_t slot, int64_t n_rows, uint8_t *out);
+/* ... and its index-relation column: ceil(n_rows / 8) words (bits at or beyond n_rows are whatever the slot holds there). */
+int mc_ctx_fetch_idx_rel_bits(mc_ctx *ctx, int32_t slot, int64_t n_rows, uint16_t *out);
 
 /* ===== native `.diffs.<k>` row formatter (host), replaces the text assembly of the flush, extract_contexts.py:186-216 ===== */
 typedef struct mc_format_args {

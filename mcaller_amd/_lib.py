@@ -109,6 +109,16 @@ def pack_model_n(flags):
     return out
 
 
+def pack_idx_rel(event_idx):
+    """The index-relation column of an event-index column (mc_pack_idx_rel): a uint16 per eight rows, bit e of word u is
+    event_idx[8u + e] > event_idx[8u + e - 1], bit 8 + e is `<` (row 0 and the bits beyond the last row: 0)."""
+    event_idx = np.ascontiguousarray(event_idx, dtype=np.int32)
+    out = np.zeros((len(event_idx) + 7) // 8, dtype=np.uint16)
+    if len(event_idx):
+        lib().mc_pack_idx_rel(_ptr(event_idx), len(event_idx), _ptr(out))
+    return out
+
+
 def _from_ptr(ptr, n, dtype):
     if n == 0 or not ptr:
         return np.zeros(0, dtype=dtype)
@@ -142,7 +152,7 @@ class Table(object):
     column of (event, model) pairs, `evmu` [n, 2]; `event_e4` / `model_e4` are its two halves (strided views)."""
 
     def __init__(self, pos, event_e4, model_e4, event_idx, flags, seg_row_begin, seg_read, seg_contig, n_reads,
-                 read_names=None, unknown=(), owner=None, evmu=None, model_n_bits=None):
+                 read_names=None, unknown=(), owner=None, evmu=None, model_n_bits=None, idx_rel_bits=None):
         self.pos = np.ascontiguousarray(pos, dtype=np.int32)
         if evmu is None:
             evmu = np.empty((len(self.pos), 2), dtype=np.int32)
@@ -153,6 +163,8 @@ class Table(object):
         self.flags = np.ascontiguousarray(flags, dtype=np.uint8)
         # the model-N bit column the table's maker wrote with the flags (a parser, pinned()); None: bare arrays
         self._model_n_bits = None if model_n_bits is None else np.ascontiguousarray(model_n_bits, dtype=np.uint8)
+        # ... and the index-relation column written with the event indices; None: bare arrays
+        self._idx_rel_bits = None if idx_rel_bits is None else np.ascontiguousarray(idx_rel_bits, dtype=np.uint16)
         self.seg_row_begin = np.ascontiguousarray(seg_row_begin, dtype=np.int64)
         self.seg_read = np.ascontiguousarray(seg_read, dtype=np.int32)
         self.seg_contig = np.ascontiguousarray(seg_contig, dtype=np.int32)
@@ -179,6 +191,14 @@ class Table(object):
             return self._model_n_bits
         return None if self.flags is None else pack_model_n(self.flags)
 
+    @property
+    def idx_rel_bits(self):
+        """The index-relation column (mc_table_view.idx_rel_bits): the maker's, or -- a table built from bare arrays, whose
+        indices may have been edited since -- packed from the event indices as they are now (mc_pack_idx_rel)."""
+        if self._idx_rel_bits is not None:
+            return self._idx_rel_bits
+        return None if self.event_idx is None else pack_idx_rel(self.event_idx)
+
     def pinned(self):
         """A copy whose columns sit in the pinned host pool (what mc_ctx_upload_table_async wants to read from)."""
         keep = []
@@ -190,7 +210,7 @@ class Table(object):
             return h.array
         t = Table(pin(self.pos), None, None, pin(self.event_idx), pin(self.flags), self.seg_row_begin, self.seg_read,
                   self.seg_contig, self.n_reads, read_names=self.read_names, unknown=self.unknown, evmu=pin(self.evmu),
-                  model_n_bits=pin(self.model_n_bits))
+                  model_n_bits=pin(self.model_n_bits), idx_rel_bits=pin(self.idx_rel_bits))
         t._owner = keep
         return t
 
@@ -204,6 +224,8 @@ class Table(object):
         if self.pos is not None:
             self._nbits_viewed = self.model_n_bits     # (kept: the view points into it)
             v.model_n_bits = _ptr(self._nbits_viewed)
+            self._xrel_viewed = self.idx_rel_bits      # (likewise)
+            v.idx_rel_bits = _ptr(self._xrel_viewed)
         v.n_seg = self.n_seg
         v.seg_row_begin, v.seg_read, v.seg_contig = _ptr(self.seg_row_begin), _ptr(self.seg_read), _ptr(self.seg_contig)
         v.n_reads = self.n_reads
@@ -220,11 +242,19 @@ class Table(object):
             if r1 % 8 and r1 < self.n_rows:
                 bits = bits.copy()
                 bits[-1] &= (1 << (r1 % 8)) - 1
+        # (the maker's relation column likewise: whole words on a cut at a multiple of eight rows, the slice's first row with no
+        # row before it any more, the bits of the rows behind the slice cleared)
+        rel = None
+        if self._idx_rel_bits is not None and r0 % 8 == 0 and r1 > r0:
+            rel = self._idx_rel_bits[r0 // 8:(r1 + 7) // 8].copy()
+            rel[0] &= 0xFEFE
+            if r1 % 8 and r1 < self.n_rows:
+                rel[-1] &= ((1 << (r1 % 8)) - 1) * 0x0101
         return Table(self.pos[r0:r1], None, None, self.event_idx[r0:r1],
                      self.flags[r0:r1], self.seg_row_begin[s0:s1 + 1] - r0, self.seg_read[s0:s1],
                      self.seg_contig[s0:s1], self.n_reads, read_names=self.read_names, owner=self._owner,
                      evmu=self.evmu[r0:r1],
-                     model_n_bits=bits)
+                     model_n_bits=bits, idx_rel_bits=rel)
 
 
 class TextBlock(object):
@@ -275,6 +305,7 @@ def device_table(res, text):
     t.pos = t.evmu = t.event_idx = None                # (on the device only)
     t.flags = _from_ptr(res.flags, n, np.uint8).copy()
     t._model_n_bits = None                             # (on the device only: kp_place wrote it with the flag column)
+    t._idx_rel_bits = None                             # (likewise, with the index column)
     rows = _from_ptr(res.seg_row_begin, ns, np.int64)
     t.seg_row_begin = np.concatenate([rows, np.array([n], dtype=np.int64)])
     t.seg_contig = _from_ptr(res.seg_contig, ns, np.int32).copy()
@@ -392,7 +423,8 @@ def parse_eventalign(path, startline, endline, contig_names, n_threads=0, exact_
               _from_ptr(v.seg_row_begin, ns + 1, np.int64), _from_ptr(v.seg_read, ns, np.int32),
               _from_ptr(v.seg_contig, ns, np.int32), v.n_reads, read_names=names, unknown=unknown, owner=owner,
               evmu=_from_ptr(v.event_model_e4, 2 * n, np.int32).reshape(-1, 2),
-              model_n_bits=_from_ptr(v.model_n_bits, (n + 7) // 8, np.uint8))
+              model_n_bits=_from_ptr(v.model_n_bits, (n + 7) // 8, np.uint8),
+              idx_rel_bits=_from_ptr(v.idx_rel_bits, (n + 7) // 8, np.uint16))
     t.n_pieces = int(L.mc_parsed_n_pieces(handle))
     return t
 

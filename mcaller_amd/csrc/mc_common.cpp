@@ -260,6 +260,22 @@ extern "C" void mc_pack_model_n(const uint8_t *flags, int64_t n_rows, uint8_t *o
     }
 }
 
+// The index-relation column of an event-index column (mc_table_view::idx_rel_bits): what the first pass's validation streams
+// in place of the indices -- per row, is its index greater than, less than or equal to that of the row before it in the table.
+// Whole words are written; row 0 (no row before it) and the bits at or beyond n_rows as zeros.  (Comparisons, no subtraction:
+// INT32_MIN beside INT32_MAX is a pair like any other.)
+extern "C" void mc_pack_idx_rel(const int32_t *event_idx, int64_t n_rows, uint16_t *out) {
+    for (int64_t u = 0; u * 8 < n_rows; ++u) {
+        const int64_t r0 = u * 8, n = n_rows - r0 < 8 ? n_rows - r0 : 8;
+        unsigned v = 0;
+        for (int64_t e = r0 ? 0 : 1; e < n; ++e) {
+            const int32_t a = event_idx[r0 + e], b = event_idx[r0 + e - 1];
+            v |= (unsigned)(a > b) << e | (unsigned)(a < b) << (8 + e);
+        }
+        out[u] = (uint16_t)v;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------
 // Marking a contig's motif sites (extract_contexts.py:33-41,:60-73 for a motif): seq.upper(), then str.replace(motif, repl)
 // for the motif and its reverse complement -- left to right, non-overlapping, len(repl) == len(motif).  CPython spends 14 ms

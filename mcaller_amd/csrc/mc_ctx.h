@@ -86,6 +86,8 @@ struct TableSlot {
     uint8_t *flags = nullptr;
     uint8_t *nbits = nullptr;          // the model-N bit column (DevTable::nbits)
     Pinned nbits_h;                    // ... packed here for a caller that passes none (mc_table_view::model_n_bits == NULL)
+    uint16_t *xrel = nullptr;          // the index-relation column (DevTable::xrel)
+    Pinned xrel_h;                     // ... packed here for a caller that passes none (mc_table_view::idx_rel_bits == NULL)
     int2 *unit_pp = nullptr;
     NbDesc *nb_tmpl = nullptr;
     unsigned char *small_dev = nullptr;   // the small arrays: device block ...

@@ -84,6 +84,9 @@ struct DevTable {
     uint8_t *flags = nullptr;
     uint8_t *nbits = nullptr; // [ceil(n_rows / 8)] bit r & 7 of byte r >> 3: row r has an 'N' model k-mer (MC_F_MODEL_N of its flag byte) -- what
                               // k1_scan streams in place of the flag bytes; written whole by whoever writes the flags
+    uint16_t *xrel = nullptr; // [ceil(n_rows / 8)] a word per unit of eight rows, row r = 8u + e: bit e of word u is idx[r] > idx[r-1], bit 8 + e is
+                              // idx[r] < idx[r-1] (neither: equal; row 0: neither) -- the row before it in the table, whatever block that is in.
+                              // What a first pass streams in place of the event indices (1/4 B/row for 4); written whole by whoever writes idx
     int2 *unit_pp = nullptr;  // [ceil(n_rows / 8)] positions of the first and the last row of every unit of eight rows (k_summarize,
                               // when a table is scanned a second time): all the filter of a repeated scan looks at -- 1 B/row
     int32_t n_seg = 0;
@@ -503,7 +506,7 @@ struct LitArgs {
 
 // NumPy pairwise_sum over an array (np.mean of a slot list, :186)
 
-constexpr int SCAN_VALIDATE = 0;    // a table's first pass: positions, event indices and model-N bits streamed (8.125 B/row), every row validated
+constexpr int SCAN_VALIDATE = 0;    // a table's first pass: positions, index relations and model-N bits streamed (4.375 B/row), every row validated
 constexpr int SCAN_STREAM = 1;      // a validated table, positions and model-N bits streamed (4.125 B/row): one-base motifs, where every unit is listed
 constexpr int SCAN_SUMMARY = 2;     // a validated table that has unit summaries (k_summarize): 1 B/row
 

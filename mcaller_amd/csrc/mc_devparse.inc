@@ -536,6 +536,7 @@ struct KpPlaceArgs {
     int2 *t_evmu;
     uint8_t *t_flags;
     uint8_t *t_nbits;               // the model-N bit column: one bit per row, made here from the rows' staged flag bytes
+    uint16_t *t_xrel;               // the index-relation column: two bits per row, each row's staged index against its predecessor's
     KpSeg *segs;
     int cap_segs;
     KpUnknown *unknown;
@@ -546,9 +547,13 @@ struct KpPlaceArgs {
 // its own -- the last of these may need the rows of the lines behind the workgroup's, which wave 0 looks up (64 lines at a
 // time: status and staged flag byte are all it takes).  A byte that begins with an earlier workgroup's row is that workgroup's.
 // So every byte of [0, ceil(n_rows / 8)) is stored exactly once, whole, whatever the slot held before.
+// The index-relation column (DevTable::xrel) goes the same way, a 16-bit word per eight rows from two bit planes gathered beside
+// the model-N bits ("greater than", "less than" the index of the row before it -- the predecessor every row looks for anyway,
+// whatever its name; the table's first row has none and leaves both bits clear), under the same ownership rule.
 __global__ __launch_bounds__(256) void kp_place(KpPlaceArgs A) {
     __shared__ int s_w[4];
     __shared__ uint32_t s_nbits[10];                // bits of rows base .. base + 319 (7 in front, 256 rows, 7 behind)
+    __shared__ uint32_t s_xinc[10], s_xdec[10];     // ... likewise: the row's index is greater / less than its predecessor's
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t li = (int64_t)blockIdx.x * 256 + tid;
     const long long n_lines = min((long long)A.head->n_lines, (long long)A.cap_lines - 1);
@@ -556,14 +561,29 @@ __global__ __launch_bounds__(256) void kp_place(KpPlaceArgs A) {
     const bool is_row = st == KP_ST_ROW;
     const unsigned long long bal = __ballot(is_row);
     if (lane == 0) s_w[wave] = __popcll(bal);
-    if (tid < 10) s_nbits[tid] = 0u;
+    if (tid < 10) s_nbits[tid] = s_xinc[tid] = s_xdec[tid] = 0u;
     __syncthreads();
+    // the row before a row: the line before it, unless that one is no row (-1: the table's first row)
+    auto row_before = [&](int64_t l) {
+        int64_t q = l - 1;
+        while (q >= 0 && A.status[q] != KP_ST_ROW) --q;
+        return q;
+    };
+    // (bit `at` of the two planes from a row's index and its predecessor's)
+    auto note_rel = [&](int at, int64_t l, int64_t q) {
+        if (q < 0) return;
+        const int32_t xi = A.idx[l], xq = A.idx[q];
+        if (xi > xq) atomicOr(&s_xinc[at >> 5], 1u << (at & 31));
+        if (xi < xq) atomicOr(&s_xdec[at >> 5], 1u << (at & 31));
+    };
+    const int64_t pl = is_row ? row_before(li) : -1;
     const long long row0 = A.blk_off[blockIdx.x];
     long long row = row0 + __popcll(bal & ((1ull << lane) - 1ull));
     for (int w = 0; w < wave; ++w) row += s_w[w];
     {
         const long long row_end = row0 + s_w[0] + s_w[1] + s_w[2] + s_w[3], base = row0 & ~7ll;
         if (is_row && (A.fl[li] & MC_F_MODEL_N)) atomicOr(&s_nbits[(int)(row - base) >> 5], 1u << ((int)(row - base) & 31));
+        if (is_row) note_rel((int)(row - base), li, pl);
         // (the rows behind the workgroup's that share its last byte -- only if that byte begins with one of its rows)
         int need = (int)((8 - (row_end & 7)) & 7);
         if (wave == 0 && row_end > row0 && ((row_end - 1) & ~7ll) >= row0 && need > 0) {
@@ -574,6 +594,9 @@ __global__ __launch_bounds__(256) void kp_place(KpPlaceArgs A) {
                 const unsigned long long rb = __ballot(rw);
                 const int nth = __popcll(rb & ((1ull << lane) - 1ull));
                 if (rw && nth < need && (A.fl[l] & MC_F_MODEL_N)) atomicOr(&s_nbits[(int)(r + nth - base) >> 5], 1u << ((int)(r + nth - base) & 31));
+                // (its predecessor -- the row lane before it in the ballot, for the first one the workgroup's last row -- found as
+                // every row finds its own: at most seven lanes walk back over the lines that are no rows)
+                if (rw && nth < need) note_rel((int)(r + nth - base), l, row_before(l));
                 const int got = min(__popcll(rb), need);
                 r += got;
                 need -= got;
@@ -585,6 +608,7 @@ __global__ __launch_bounds__(256) void kp_place(KpPlaceArgs A) {
         if (b0 + tid < b1) {
             const int off = (int)(b0 + tid - (base >> 3));
             A.t_nbits[b0 + tid] = (uint8_t)(s_nbits[off >> 2] >> (8 * (off & 3)));
+            A.t_xrel[b0 + tid] = (uint16_t)(((s_xinc[off >> 2] >> (8 * (off & 3))) & 0xFFu) | (((s_xdec[off >> 2] >> (8 * (off & 3))) & 0xFFu) << 8));
         }
     }
     if (st == KP_ST_UNKNOWN) {                          // :156-160: the line is skipped, the message names the contig
@@ -594,9 +618,6 @@ __global__ __launch_bounds__(256) void kp_place(KpPlaceArgs A) {
     }
     if (!is_row) return;
     if (row >= A.cap_rows) { atomicOr(&A.head_w->overflow, 1); return; }
-    // the row before this one: the line before it, unless that one is no row
-    int64_t pl = li - 1;
-    while (pl >= 0 && A.status[pl] != KP_ST_ROW) --pl;
     const uint32_t no = A.name_off[li];
     const int nl = A.name_len[li];
     bool new_name = true, new_seg = true;

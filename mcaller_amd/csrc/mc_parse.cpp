@@ -163,6 +163,7 @@ struct mc_parsed {
     RawCol<int32_t> pos, evmu, idx;        // evmu: (event, model) pairs, two entries per row
     RawCol<uint8_t> flags;
     RawCol<uint8_t> nbits;                 // the model-N bit column (mc_table_view::model_n_bits), written with the flags
+    RawCol<uint16_t> xrel;                 // the index-relation column (mc_table_view::idx_rel_bits), written with the indices
     int n_pieces = 0;                      // pieces the byte range was cut into (one parser thread each)
     std::vector<int64_t> seg_begin;
     std::vector<int32_t> seg_read, seg_contig;
@@ -651,7 +652,7 @@ static int parse_file(const char *path, int64_t startline, int64_t endline, bool
     P->n_pieces = np;
     if (!P->pos.alloc((size_t)total) || !P->evmu.alloc((size_t)total * 2) ||
         !P->idx.alloc((size_t)total) || !P->flags.alloc((size_t)total) ||
-        !P->nbits.alloc((size_t)(total + 7) / 8)) {
+        !P->nbits.alloc((size_t)(total + 7) / 8) || !P->xrel.alloc((size_t)(total + 7) / 8)) {
         delete P;
         mc_set_error("out of memory for %lld rows", (long long)total);
         return -10;
@@ -660,6 +661,11 @@ static int parse_file(const char *path, int64_t startline, int64_t endline, bool
     {
         std::vector<int64_t> offs((size_t)np + 1, 0);
         for (int i = 0; i < np; ++i) offs[(size_t)i + 1] = offs[(size_t)i] + (int64_t)chunks[(size_t)i].pos.size();
+        // (the event index of table row r, where the parser threads left it: a row of another piece than the one being placed)
+        auto idx_of = [&](int64_t r) {
+            const size_t j = (size_t)(std::upper_bound(offs.begin(), offs.end(), r) - offs.begin()) - 1;
+            return chunks[j].idx[(size_t)(r - offs[j])];
+        };
         auto place = [&](int i) {
             Chunk &C = chunks[(size_t)i];
             const size_t n = C.pos.size();
@@ -682,6 +688,20 @@ static int parse_file(const char *path, int64_t startline, int64_t endline, bool
                         if (D.flags[(size_t)(r - (pj_end - (int64_t)D.pos.size()))] & MC_F_MODEL_N) v |= 1u << e;
                     }
                     P->nbits[(size_t)b] = (uint8_t)v;
+                }
+                // the index relations of the same units, by the same rule: every row against the row before it in the table -- the
+                // piece's first row against the last row of the piece in front of it, the rows of a last word that runs on into
+                // the pieces behind against theirs; row 0 has no row before it and keeps both bits clear
+                for (int64_t u = (o + 7) >> 3; u * 8 < o + (int64_t)n; ++u) {
+                    unsigned v = 0;
+                    for (int e = 0; e < 8 && u * 8 + e < total; ++e) {
+                        const int64_t r = u * 8 + e;
+                        if (r == 0) continue;
+                        const bool here = r - 1 >= o && r < o + (int64_t)n;
+                        const int32_t a = here ? C.idx[(size_t)(r - o)] : idx_of(r), b = here ? C.idx[(size_t)(r - 1 - o)] : idx_of(r - 1);
+                        v |= (unsigned)(a > b) << e | (unsigned)(a < b) << (8 + e);
+                    }
+                    P->xrel[(size_t)u] = (uint16_t)v;
                 }
             }
             C.n_rows = (int64_t)n;
@@ -781,6 +801,7 @@ extern "C" int mc_parsed_view(const mc_parsed *p, mc_table_view *out) {
     out->event_idx = p->idx.data();
     out->flags = p->flags.data();
     out->model_n_bits = p->nbits.data();
+    out->idx_rel_bits = p->xrel.data();
     out->n_seg = (int32_t)p->seg_read.size();
     out->seg_row_begin = p->seg_begin.data();
     out->seg_read = p->seg_read.data();

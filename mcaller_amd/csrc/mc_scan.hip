@@ -21,7 +21,8 @@ __global__ __launch_bounds__(256) void k_summarize(DevTable T) {
 // ---------------------------------------------------------------------------------------------------
 // K1: the window scan, as two launches
 //
-//   k1_scan  streams the position column (and, on a table's first pass, the event-index column, validating every row),
+//   k1_scan  streams the position column (and, on a table's first pass, the index-relation column -- two bits per row: how its
+//            event index stands to the index of the row before it -- validating every row),
 //            finds the units of eight rows that can hold a site row at all (one extract from the strand bitmask per unit)
 //            and decides for every site row of those whether it is the LAST row of its window: the next unfiltered row
 //            starts another read or lies beyond the site (:179).  Output: a 32-byte payload per closed window + a count
@@ -287,13 +288,15 @@ __device__ __forceinline__ uint32_t flag_bytes(uint32_t b4) { return (((b4 & 0xF
 template <int MODE>
 struct ChunkCols {
     int4 pa[NQ], pb[NQ];            // positions of rows i0 .. i0+3, i0+4 .. i0+7 of the lane's unit in stripe j (SCAN_SUMMARY: pa.x, pb.w only)
-    int4 xa[NQ], xb[NQ];            // ... their event indices (SCAN_VALIDATE)
+    uint32_t xr[NQ];                // ... their index relations, one word of the table's relation column: bit e, row e's event index is greater
+                                    // than that of the row before it, bit 8 + e, less (SCAN_VALIDATE) -- all the validation asks of the indices
     uint32_t nb[NQ];                // ... their model-N bits, one byte of the table's bit column (not SCAN_SUMMARY)
     __device__ __forceinline__ void load(const DevTable &T, int64_t c0, int crows, int lane) {
 #pragma unroll
         for (int j = 0; j < NQ; ++j) {
             const int i0 = (j * 64 + lane) * 8;
-            pa[j] = pb[j] = xa[j] = xb[j] = make_int4(0, 0, 0, 0);
+            pa[j] = pb[j] = make_int4(0, 0, 0, 0);
+            xr[j] = 0u;
             nb[j] = 0xFFu;                                      // (rows past the table: 'N', never looked at anyway)
             if (i0 < crows) {                       // (arrays are padded: whole units stay in bounds)
                 if (MODE == SCAN_SUMMARY) {
@@ -305,8 +308,8 @@ struct ChunkCols {
                     pb[j] = *reinterpret_cast<const int4 *>(T.pos + c0 + i0 + 4);
                     nb[j] = T.nbits[(c0 + i0) >> 3];            // (a chunk begins at a multiple of eight rows: the lane's unit is one byte)
                     if (MODE == SCAN_VALIDATE) {
-                        xa[j] = *reinterpret_cast<const int4 *>(T.idx + c0 + i0);
-                        xb[j] = *reinterpret_cast<const int4 *>(T.idx + c0 + i0 + 4);
+                        // (two bytes per lane, 128 contiguous bytes per wave and stripe, where the indices were two 16-byte loads per lane)
+                        xr[j] = T.xrel[(c0 + i0) >> 3];
                     }
                 }
             }
@@ -462,10 +465,12 @@ __device__ __forceinline__ void dense_block_rows(const K1Args &A, TileSlots &S, 
 // of the current one are free, and travel while the current chunk's candidates are examined.
 //
 // The columns of a chunk go from HBM into REGISTERS -- every lane holds eight consecutive rows (a unit) of each 512-row stripe.
-// On a table's first pass (SCAN_VALIDATE) these are the positions, the event indices and the model-N bits -- the table's bit
-// column, a byte per unit: the one bit of the flag byte the scan looks at, MC_F_MODEL_N -- 8.125 B/row, and every row
-// is compared with the row before it -- its neighbour in the lane, the previous lane's last row (one shuffle), the last row of
-// the chunk before -- which gives the validation flags of the chunk's name blocks: a chunk inside one block (the usual case)
+// On a table's first pass (SCAN_VALIDATE) these are the positions, the index relations and the model-N bits -- the table's two
+// bit columns, a word and a byte per unit: how a row's event index stands to that of the row before it (greater, less, equal:
+// the table's maker had both in hand), and the one bit of the flag byte the scan looks at, MC_F_MODEL_N -- 4.375 B/row, and
+// every row is compared with the row before it -- positions: its neighbour in the lane, the previous lane's last row (one
+// shuffle), the last row of the chunk before; indices: the comparison comes made, two bits of the unit's word -- which gives
+// the validation flags of the chunk's name blocks: a chunk inside one block (the usual case)
 // ends with wave-wide flags that are held against what the block was classified on, and nothing is written unless they say
 // more.  The comparisons run while the mask words below are on their way.
 //
@@ -515,8 +520,8 @@ __global__ __launch_bounds__(64) MC_SCAN_ATTR void k1_scan(K1Args A) {
         tail_f = ((((uint32_t)T.nbits[(c1 >> 3) + 1] << 8) | (uint32_t)T.nbits[c1 >> 3]) >> (int)(c1 & 7)) & 3u;
     };
     if constexpr (CG > 64) load_tail(t0 + min(nrows, CHUNK));
-    int before_p = 0, before_x = 0;                 // the row before the chunk (its first row's predecessor, if that is in its block)
-    if (MODE == SCAN_VALIDATE && t0 > 0) { before_p = T.pos[t0 - 1]; before_x = T.idx[t0 - 1]; }
+    int before_p = 0;                               // the row before the chunk (its first row's predecessor, if that is in its block)
+    if (MODE == SCAN_VALIDATE && t0 > 0) before_p = T.pos[t0 - 1];
     int nb0 = __builtin_amdgcn_readfirstlane(T.tile_nb[tile]);      // first name block that overlaps the chunk
     ScanGlobals G;
     G.pos = T.pos; G.flags = T.flags; G.nb_row_begin = T.nb_row_begin; G.desc = A.desc; G.n_rows = T.n_rows;
@@ -573,9 +578,11 @@ __global__ __launch_bounds__(64) MC_SCAN_ATTR void k1_scan(K1Args A) {
         if (CG <= 64 || MODE != SCAN_VALIDATE) fetch_mask_words();
 
         // ---- first pass over the table: every row against the row before it (while the mask words are on their way) ----
-        // (per-lane COUNTS of what the pairs of rows say -- a comparison and an add-with-carry each, two vector instructions and
-        // no scalar state; accumulating the lane masks of the comparisons themselves costs this kernel more scalar registers than
-        // it has)
+        // (per-lane COUNTS of what the pairs of rows say -- positions: a comparison and an add-with-carry each, two vector
+        // instructions and no scalar state; accumulating the lane masks of the comparisons themselves costs this kernel more scalar
+        // registers than it has.  Event indices: the table's relation column holds the comparisons of a unit's eight rows, each
+        // with the row before it in the table -- which is its predecessor in the block wherever the count is taken -- so a unit
+        // adds two population counts)
         if (MODE == SCAN_VALIDATE) {
             for (int bi = 0; bi < nfast; ++bi) {
                 const int64_t rb = bi ? db.row_begin : da.row_begin, re = bi ? db.row_end : da.row_end;
@@ -589,24 +596,25 @@ __global__ __launch_bounds__(64) MC_SCAN_ATTR void k1_scan(K1Args A) {
                     if (j * 512 + 512 <= vlo || j * 512 >= vhi) continue;      // (wave-uniform)
                     const int i0 = (j * 64 + lane) * 8;
                     // the row before the unit: the previous lane's last row (lane 0: the previous stripe's, or the row before the chunk)
-                    int qp = __shfl_up(C.pb[j].w, 1), qx = __shfl_up(C.xb[j].w, 1);
+                    // (positions only: the index relation of the unit's first row to that row is bit 0 of the unit's own word)
+                    int qp = __shfl_up(C.pb[j].w, 1);
                     {
                         const int sp = j > 0 ? __shfl(C.pb[(j + NQ - 1) % NQ].w, 63) : before_p;
-                        const int sx = j > 0 ? __shfl(C.xb[(j + NQ - 1) % NQ].w, 63) : before_x;
-                        if (lane == 0) { qp = sp; qx = sx; }
+                        if (lane == 0) qp = sp;
                     }
                     const int ps[8] = {C.pa[j].x, C.pa[j].y, C.pa[j].z, C.pa[j].w, C.pb[j].x, C.pb[j].y, C.pb[j].z, C.pb[j].w};
-                    const int xs[8] = {C.xa[j].x, C.xa[j].y, C.xa[j].z, C.xa[j].w, C.xb[j].x, C.xb[j].y, C.xb[j].z, C.xb[j].w};
                     const bool whole = i0 >= pred_from && i0 + 8 <= vhi;
                     const bool cut = !whole && i0 + 8 > vlo && i0 < vhi;
                     if (whole) {                                // the unit and the row before it inside the block: the usual case
 #pragma unroll
                         for (int e = 0; e < 8; ++e) {
-                            const int pp = e ? ps[e - 1] : qp, px = e ? xs[e - 1] : qx;
+                            const int pp = e ? ps[e - 1] : qp;
                             n_pdec += ps[e] < pp;
-                            n_inc += xs[e] > px;
-                            n_dec += xs[e] < px;
                         }
+                        // (all eight rows have their predecessor in the block here: every bit of the word counts, and a pair
+                        // that set neither is an equal one -- the test on n_pairs below)
+                        n_inc += __popc(C.xr[j] & 0xFFu);
+                        n_dec += __popc(C.xr[j] >> 8);
                         n_pairs += 8;
                         const uint32_t m01 = min((uint32_t)ps[0], (uint32_t)ps[1]), m23 = min((uint32_t)ps[2], (uint32_t)ps[3]);
                         const uint32_t m45 = min((uint32_t)ps[4], (uint32_t)ps[5]), m67 = min((uint32_t)ps[6], (uint32_t)ps[7]);
@@ -627,7 +635,6 @@ __global__ __launch_bounds__(64) MC_SCAN_ATTR void k1_scan(K1Args A) {
             // the next chunk's "row before": this chunk's last row
             if (more) {
                 before_p = __shfl(C.pb[NQ - 1].w, 63);
-                before_x = __shfl(C.xb[NQ - 1].w, 63);
             }
         }
 

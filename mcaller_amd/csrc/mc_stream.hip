@@ -11,7 +11,8 @@
 //   text         kp_count / kp_scan / kp_starts / kp_parse / kp_count_rows / kp_place   the eventalign TEXT of a streamed shard
 //                                parsed on the device (mc_devparse.inc): line starts, tokens, numbers, name blocks and segments,
 //                                the columns written straight into a table slot -- the model-N bit column (one bit per row:
-//                                the row's model k-mer is NNNNNN) with them, a byte per eight rows put together in kp_place
+//                                the row's model k-mer is NNNNNN) and the index-relation column (two bits per row) with
+//                                them, a byte and a word per eight rows put together in kp_place
 //   per table     (nothing runs at upload: the first pass over a table validates it while it scans)
 //                (nb_template     the pass-independent fields of the name-block descriptors: inside the first k0_first_site over a table)
 //                k_summarize     a table that is scanned a second time gets unit summaries (first / last position of every
@@ -22,8 +23,10 @@
 //                                (direction of the event index, position 0) and the scan confirms it
 //                k0_classify / k0_extend   tables with repeated read names; irregular runs widened
 //                k1_scan         THE SCAN: one wave per tile of 2048 rows, nothing persistent.  First pass over a table: the
-//                                position and event-index columns and the model-N bit column (8.125 B/row: the one bit of
-//                                the flag byte the scan looks at) go from HBM into registers and every row is
+//                                position column, the index-relation column (two bits per row: its event index against the
+//                                index of the row before it, written by the table's maker) and the model-N bit column
+//                                (the one bit of the flag byte the scan looks at; 4.375 B/row in all) go from HBM into
+//                                registers and every row is
 //                                compared with the row before it (positions non-decreasing? event index strictly monotone?
 //                                -- what makes a name block "regular"); units of eight rows that can hold a site row are
 //                                found with one extract from the strand bitmask (two words per unit, straight from L2) and

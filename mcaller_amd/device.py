@@ -215,6 +215,16 @@ class Device(object):
         return out
 
     @_serialized
+    def fetch_idx_rel_bits(self, slot, n_rows):
+        """The index-relation column of the table in `slot`, ceil(n_rows / 8) uint16, the bits at or beyond n_rows cleared (tests)."""
+        out = np.zeros((n_rows + 7) // 8 + 1, dtype=np.uint16)
+        check(lib().mc_ctx_fetch_idx_rel_bits(self._ctx, int(slot), int(n_rows), _ptr(out)))
+        out = out[:(n_rows + 7) // 8]
+        if n_rows % 8:
+            out[-1] &= ((1 << (n_rows % 8)) - 1) * 0x0101
+        return out
+
+    @_serialized
     def wait_upload(self, slot):
         check(lib().mc_ctx_wait_upload(self._ctx, int(slot)))
 

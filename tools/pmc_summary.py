@@ -6,7 +6,7 @@ Each pass is `rocprofv3 --kernel-trace --pmc FETCH_SIZE|WRITE_SIZE --output-form
 (separate passes: the two counters do not fit the TCC slots together, MI355X_MICROARCH.md "rocprofv3 PMC slots").
 Correction applied (same guide, HBM section): on gfx950 FETCH_SIZE reports half the bytes of a wide coalesced streaming
 read -> x2; WRITE_SIZE is taken as reported.  Calibration inside the same run: the validating scan (k1_scan<64,0>) streams
-exactly 8.125 B/row (positions, event indices, the model-N bit column: 0.8125 GB at 10^8 rows) plus the mask words of its units (L2) -- its
+exactly 4.375 B/row (positions, the index-relation column, the model-N bit column: 0.4375 GB at 10^8 rows) plus the mask words of its units (L2) -- its
 corrected figure is stored as `calibration` and must come out slightly above 1.0.
 Both counters are in KB.  The file records the hash of the kernel sources it was collected on (`kernel_source_sha16`): bench.py
 quotes `roofline.traffic` from it only while the library is built from the same sources."""
@@ -72,9 +72,9 @@ def main():
     fe = sum(per[kname]['hbm_bytes'] for kname in names if kname in per)
     cal = None
     if 'k1_scan<64,0>' in per:
-        cal = {'kernel': 'k1_scan<64,0>', 'expected_fetch_bytes': 8.125e8, 'fetch_bytes_corrected': per['k1_scan<64,0>']['fetch_bytes_corrected'],
-               'ratio': per['k1_scan<64,0>']['fetch_bytes_corrected'] / 8.125e8,
-               'note': 'expected value holds for the 10^8-row workload: 8.125 B/row streamed; the mask words and the descriptors come on top'}
+        cal = {'kernel': 'k1_scan<64,0>', 'expected_fetch_bytes': 4.375e8, 'fetch_bytes_corrected': per['k1_scan<64,0>']['fetch_bytes_corrected'],
+               'ratio': per['k1_scan<64,0>']['fetch_bytes_corrected'] / 4.375e8,
+               'note': 'expected value holds for the 10^8-row workload: 4.375 B/row streamed; the mask words and the descriptors come on top'}
     json.dump({'FETCH_SIZE_KB': fetch, 'WRITE_SIZE_KB': write, 'per_launch_bytes_corrected': per, 'workload': workload,
                'head': head, 'kernel_source_sha16': kernel_source_hash(), 'per_table_kernels': [n for n in names if n in per],
                'calibration': cal, 'per_table_hbm_bytes': fe,
