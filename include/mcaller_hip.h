@@ -328,6 +328,10 @@ typedef struct mc_params {
  * *rerun != 0 -- the pipelined pass could not be finished as enqueued (record room too small, an irregular read, a row that
  * contradicts what a block was classified on) and was repeated synchronously inside mc_wait_records. */
 int mc_last_pass_info(mc_ctx *ctx, int32_t *fused_room, int32_t *rerun);
+/* What the scan of the pass enqueued last streams (tests): 0 positions, index relations and model-N bits, every row validated;
+ * 1 positions and model-N bits; 2 unit summaries; 3 unit summaries and both relation columns, every row validated; -1 no pass
+ * yet.  A pass that was repeated synchronously inside mc_wait_records leaves the repeat's mode. */
+int mc_ctx_last_scan_mode(mc_ctx *ctx);
 /* The rows of a pipelined pass as TEXT, made on the device (mc_rowtext.hip; replaces mc_format_diffs on the host, the row writer of
  * extract_contexts.py:207-216).  mc_ctx_row_text(on = 1, the two labels of :200-206; on = 2 at the start of a stream: also takes back the
  * blocks an earlier stream never released -- nobody may be reading them any more): the passes enqueued from now on also print their
@@ -580,6 +584,13 @@ int mc_ctx_fetch_columns(mc_ctx *ctx, int32_t slot, int64_t n_rows, int32_t *pos
 int mc_ctx_fetch_model_n_bits(mc_ctx *ctx, int32_t slot, int64_t n_rows, uint8_t *out);
 /* ... and its index-relation column: ceil(n_rows / 8) words (bits at or beyond n_rows are whatever the slot holds there). */
 int mc_ctx_fetch_idx_rel_bits(mc_ctx *ctx, int32_t slot, int64_t n_rows, uint16_t *out);
+/* ... its position-relation column, which the table's maker on the device writes with the positions: ceil(n_rows / 8) words,
+ * row r = 8u + e: bit e of word u is pos[r] < pos[r-1] (the row before it in the table; row 0: clear), bit 8 + e is
+ * pos[r] == 0 (bits at or beyond n_rows: 0). */
+int mc_ctx_fetch_pos_rel_bits(mc_ctx *ctx, int32_t slot, int64_t n_rows, uint16_t *out);
+/* ... and its unit summaries: ceil(n_rows / 8) pairs of int32, the positions of the first and the last row of every unit of
+ * eight rows (the second of a last, partial unit is unspecified). */
+int mc_ctx_fetch_unit_summaries(mc_ctx *ctx, int32_t slot, int64_t n_rows, int32_t *out);
 
 /* ===== native `.diffs.<k>` row formatter (host), replaces the text assembly of the flush, extract_contexts.py:186-216 ===== */
 typedef struct mc_format_args {

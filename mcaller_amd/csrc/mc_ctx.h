@@ -88,7 +88,8 @@ struct TableSlot {
     Pinned nbits_h;                    // ... packed here for a caller that passes none (mc_table_view::model_n_bits == NULL)
     uint16_t *xrel = nullptr;          // the index-relation column (DevTable::xrel)
     Pinned xrel_h;                     // ... packed here for a caller that passes none (mc_table_view::idx_rel_bits == NULL)
-    int2 *unit_pp = nullptr;
+    uint16_t *prel = nullptr;          // the position-relation column (DevTable::prel)
+    int2 *unit_pp = nullptr;           // the unit summaries (DevTable::unit_pp)
     NbDesc *nb_tmpl = nullptr;
     unsigned char *small_dev = nullptr;   // the small arrays: device block ...
     Pinned stage;                         // ... and pinned host stage
@@ -100,11 +101,10 @@ struct TableSlot {
     bool holds_table = false;          // S.T describes the columns in the slot (set by fill_slot; cleared when a parse begins to
                                        // overwrite them or is abandoned): what mc_ctx_select_table may make current again
     // What the passes enqueued so far leave behind for the next one (host-side notes; the work is ordered by the ctx stream):
-    int passes = 0;                    // passes enqueued over this table.  The first streams positions and event indices and
-                                       // completes the validation flags (k1_scan, SCAN_VALIDATE); later ones classify on the flags.
-                                       // A table that comes back a third time (other parameters, a resident table) is worth
-                                       // unit summaries (k_summarize): from then on a scan reads 1 B/row
-    bool summarized = false;           // ... the summaries exist
+    int passes = 0;                    // passes enqueued over this table.  The first completes the validation flags (k1_scan,
+                                       // SCAN_VALIDATE_SUMMARY / SCAN_VALIDATE); later ones classify on the flags
+    bool summarized = false;           // the table's maker has written unit_pp and prel (part of the table, like nbits and xrel:
+                                       // mc_ctx_select_table(as_new) keeps it)
     // the device parser (mc_ctx_parse_begin .. _finish)
     char *text = nullptr;              // the shard's text on the device
     int64_t cap_text = 0;
@@ -279,6 +279,7 @@ struct mc_ctx {
     int64_t last_n = 0;
     int64_t last_slots = 0;        // record slots the records handed out last occupy on the device (a fused dense pass: with holes in between)
     int last_fused_room = 0, last_rerun = 0;   // how the pass handed out last ran (mc_last_pass_info)
+    int last_scan_mode = -1;       // the scan mode (SCAN_*) of the pass planned last (mc_ctx_last_scan_mode)
     size_t pack_min_bytes = 0;     // a pass's packed block: at least this (what a pass that did not fit said it needed, and a quarter)
     int fused_scale = 1;           // the fused dense pass (k1_fused): room per piece x this (doubled when a piece ran out of room)
     int64_t ref_total_len = 0;    // bases of the marked reference (record capacity guess)

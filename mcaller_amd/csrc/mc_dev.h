@@ -87,8 +87,12 @@ struct DevTable {
     uint16_t *xrel = nullptr; // [ceil(n_rows / 8)] a word per unit of eight rows, row r = 8u + e: bit e of word u is idx[r] > idx[r-1], bit 8 + e is
                               // idx[r] < idx[r-1] (neither: equal; row 0: neither) -- the row before it in the table, whatever block that is in.
                               // What a first pass streams in place of the event indices (1/4 B/row for 4); written whole by whoever writes idx
-    int2 *unit_pp = nullptr;  // [ceil(n_rows / 8)] positions of the first and the last row of every unit of eight rows (k_summarize,
-                              // when a table is scanned a second time): all the filter of a repeated scan looks at -- 1 B/row
+    uint16_t *prel = nullptr; // [ceil(n_rows / 8)] likewise for the positions: bit e of word u is pos[r] < pos[r-1] (the row before it in the table,
+                              // whatever block that is in; row 0: clear), bit 8 + e is pos[r] == 0; the bits of rows beyond the last are 0.  All
+                              // the validation asks of a row's position; written whole by whoever writes pos
+    int2 *unit_pp = nullptr;  // [ceil(n_rows / 8)] positions of the first and the last row of every unit of eight rows, written by whoever writes
+                              // pos (kp_place; k_unit_columns behind an upload): all the scan's filter looks at -- 1 B/row.  The .y of a
+                              // table's last, partial unit is unspecified: only units wholly inside a block decide anything
     int32_t n_seg = 0;
     int64_t *seg_begin = nullptr;
     int32_t *seg_read = nullptr, *seg_contig = nullptr;
@@ -506,9 +510,11 @@ struct LitArgs {
 
 // NumPy pairwise_sum over an array (np.mean of a slot list, :186)
 
-constexpr int SCAN_VALIDATE = 0;    // a table's first pass: positions, index relations and model-N bits streamed (4.375 B/row), every row validated
+constexpr int SCAN_VALIDATE = 0;    // a table's first pass, one-base motifs: positions, index relations and model-N bits streamed (4.375 B/row), every row validated
 constexpr int SCAN_STREAM = 1;      // a validated table, positions and model-N bits streamed (4.125 B/row): one-base motifs, where every unit is listed
-constexpr int SCAN_SUMMARY = 2;     // a validated table that has unit summaries (k_summarize): 1 B/row
+constexpr int SCAN_SUMMARY = 2;     // a validated table that has unit summaries: 1 B/row
+constexpr int SCAN_VALIDATE_SUMMARY = 3;    // a first pass over a table that has unit summaries, sparse reference: summaries and the two relation
+                                            // columns streamed (1.5 B/row), every row validated from the relation bits
 
 
 // ---- what the kernel units hand to the host side (mc_stream.hip): every kernel with its launch geometry, on stream st; `stop`:
@@ -519,7 +525,7 @@ void mc_launch_classify(const DevTable &T, const DevRef &R, NbDesc *desc, const 
                         Counters *cnt, unsigned long long pass_no, hipStream_t st);
 void mc_launch_extend(const DevTable &T, NbDesc *desc, const int64_t *nb_f0, int entry_read, Counters *cnt, unsigned long long pass_no,
                       hipStream_t st);
-void mc_launch_summarize(const DevTable &T, hipStream_t st);
+void mc_launch_unit_columns(const DevTable &T, hipStream_t st);
 void mc_launch_scan(const K1Args &A, bool dense, int scan_mode, hipStream_t st);
 void mc_launch_group_scan(const int32_t *cnt, int64_t n, int32_t *local, int64_t *group_sum, hipStream_t st);
 void mc_launch_list(const K1Args &A, Payload *sorted, int gather, hipStream_t st, hipEvent_t stop = nullptr);

@@ -537,6 +537,8 @@ struct KpPlaceArgs {
     uint8_t *t_flags;
     uint8_t *t_nbits;               // the model-N bit column: one bit per row, made here from the rows' staged flag bytes
     uint16_t *t_xrel;               // the index-relation column: two bits per row, each row's staged index against its predecessor's
+    uint16_t *t_prel;               // the position-relation column: two bits per row, its staged position against its predecessor's, and against 0
+    int2 *t_unit_pp;                // the unit summaries: the positions of rows 8u and 8u + 7, stored by the threads that place those rows
     KpSeg *segs;
     int cap_segs;
     KpUnknown *unknown;
@@ -550,10 +552,14 @@ struct KpPlaceArgs {
 // The index-relation column (DevTable::xrel) goes the same way, a 16-bit word per eight rows from two bit planes gathered beside
 // the model-N bits ("greater than", "less than" the index of the row before it -- the predecessor every row looks for anyway,
 // whatever its name; the table's first row has none and leaves both bits clear), under the same ownership rule.
+// The position-relation column (DevTable::prel) likewise, from two more planes: the row's position is less than its predecessor's,
+// the row's position is 0.  The unit summaries (DevTable::unit_pp) need no gathering: the thread that places row 8u stores the
+// unit's first position, the thread that places row 8u + 7 its last (a table's last, partial unit keeps whatever .y the slot held).
 __global__ __launch_bounds__(256) void kp_place(KpPlaceArgs A) {
     __shared__ int s_w[4];
     __shared__ uint32_t s_nbits[10];                // bits of rows base .. base + 319 (7 in front, 256 rows, 7 behind)
     __shared__ uint32_t s_xinc[10], s_xdec[10];     // ... likewise: the row's index is greater / less than its predecessor's
+    __shared__ uint32_t s_pdec[10], s_pos0[10];     // ... its position is less than its predecessor's / is 0
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t li = (int64_t)blockIdx.x * 256 + tid;
     const long long n_lines = min((long long)A.head->n_lines, (long long)A.cap_lines - 1);
@@ -561,7 +567,7 @@ __global__ __launch_bounds__(256) void kp_place(KpPlaceArgs A) {
     const bool is_row = st == KP_ST_ROW;
     const unsigned long long bal = __ballot(is_row);
     if (lane == 0) s_w[wave] = __popcll(bal);
-    if (tid < 10) s_nbits[tid] = s_xinc[tid] = s_xdec[tid] = 0u;
+    if (tid < 10) s_nbits[tid] = s_xinc[tid] = s_xdec[tid] = s_pdec[tid] = s_pos0[tid] = 0u;
     __syncthreads();
     // the row before a row: the line before it, unless that one is no row (-1: the table's first row)
     auto row_before = [&](int64_t l) {
@@ -569,12 +575,15 @@ __global__ __launch_bounds__(256) void kp_place(KpPlaceArgs A) {
         while (q >= 0 && A.status[q] != KP_ST_ROW) --q;
         return q;
     };
-    // (bit `at` of the two planes from a row's index and its predecessor's)
+    // (bit `at` of the planes from a row's index and position and its predecessor's)
     auto note_rel = [&](int at, int64_t l, int64_t q) {
+        const int32_t pi = A.pos[l];
+        if (pi == 0) atomicOr(&s_pos0[at >> 5], 1u << (at & 31));
         if (q < 0) return;
         const int32_t xi = A.idx[l], xq = A.idx[q];
         if (xi > xq) atomicOr(&s_xinc[at >> 5], 1u << (at & 31));
         if (xi < xq) atomicOr(&s_xdec[at >> 5], 1u << (at & 31));
+        if (pi < A.pos[q]) atomicOr(&s_pdec[at >> 5], 1u << (at & 31));
     };
     const int64_t pl = is_row ? row_before(li) : -1;
     const long long row0 = A.blk_off[blockIdx.x];
@@ -609,6 +618,7 @@ __global__ __launch_bounds__(256) void kp_place(KpPlaceArgs A) {
             const int off = (int)(b0 + tid - (base >> 3));
             A.t_nbits[b0 + tid] = (uint8_t)(s_nbits[off >> 2] >> (8 * (off & 3)));
             A.t_xrel[b0 + tid] = (uint16_t)(((s_xinc[off >> 2] >> (8 * (off & 3))) & 0xFFu) | (((s_xdec[off >> 2] >> (8 * (off & 3))) & 0xFFu) << 8));
+            A.t_prel[b0 + tid] = (uint16_t)(((s_pdec[off >> 2] >> (8 * (off & 3))) & 0xFFu) | (((s_pos0[off >> 2] >> (8 * (off & 3))) & 0xFFu) << 8));
         }
     }
     if (st == KP_ST_UNKNOWN) {                          // :156-160: the line is skipped, the message names the contig
@@ -635,7 +645,10 @@ __global__ __launch_bounds__(256) void kp_place(KpPlaceArgs A) {
         if (k < A.cap_segs) { KpSeg s; s.row = row; s.name_off = no; s.name_len = nl; s.contig = A.contig[li]; s.name_start = new_name ? 1 : 0; s.pad = 0; A.segs[k] = s; }
         else atomicOr(&A.head_w->overflow, 2);
     }
-    A.t_pos[row] = A.pos[li];
+    const int32_t p_staged = A.pos[li];
+    A.t_pos[row] = p_staged;
+    if ((row & 7) == 0) A.t_unit_pp[row >> 3].x = p_staged;
+    if ((row & 7) == 7) A.t_unit_pp[row >> 3].y = p_staged;
     A.t_idx[row] = A.idx[li];
     A.t_evmu[row] = make_int2(A.ev[li], A.mu[li]);
     A.t_flags[row] = fl;

@@ -1,4 +1,4 @@
-// mc_scan.hip: the scan (k1_scan, k_summarize) and the ordering of its payloads (k1_group_scan, k1_list) -- part of libmcaller_hip.so's device side (gfx950 / MI355X); shared structures and helpers: mc_dev.h; the map of the
+// mc_scan.hip: the scan (k1_scan, k_unit_columns) and the ordering of its payloads (k1_group_scan, k1_list) -- part of libmcaller_hip.so's device side (gfx950 / MI355X); shared structures and helpers: mc_dev.h; the map of the
 // kernels: mc_stream.hip.
 #include "mc_dev.h"
 
@@ -7,22 +7,42 @@ namespace {
 // ---------------------------------------------------------------------------------------------------
 // per-table kernels
 // ---------------------------------------------------------------------------------------------------
-// k_summarize: the unit summaries of a table that is scanned again (other parameters; a resident table): first and last
-// position of every unit of eight rows, 1 B/row -- what the filter of a repeated scan reads instead of the columns.  A flat
-// stream over the positions; the thread that holds the first or the second half of a unit writes one word, consecutive
-// threads consecutive words.  (A table that is scanned once never pays for this: its scan streams the columns themselves.)
-__global__ __launch_bounds__(256) void k_summarize(DevTable T) {
+// k_unit_columns: what a table's maker writes with the positions, for a table that arrived as columns (mc_ctx_upload_table*: on
+// the upload stream, behind the position column's transfer).  The unit summaries -- first and last position of every unit of
+// eight rows, 1 B/row: what the scan's filter reads instead of the positions -- and the position-relation column
+// (DevTable::prel), a word per unit.  A flat stream over the positions, four rows per thread; the thread that holds the first
+// or the second half of a unit writes one summary word, consecutive threads consecutive words; the row before a thread's four
+// is the neighbouring lane's last (lane 0: from memory), and a relation word is put together from the two threads of a unit
+// and stored whole by the first -- the bits of rows beyond the table's last are 0 whatever the padding holds.
+__global__ __launch_bounds__(256) void k_unit_columns(DevTable T) {
     const int64_t g4 = blockIdx.x * (int64_t)256 + threadIdx.x;       // group of four rows (the columns are padded to whole tiles)
-    if (g4 * 4 >= T.n_rows) return;
-    const int4 p = *reinterpret_cast<const int4 *>(T.pos + g4 * 4);
-    reinterpret_cast<int32_t *>(T.unit_pp)[g4] = (g4 & 1) ? p.w : p.x;
+    const bool have = g4 * 4 < T.n_rows;
+    int4 p = make_int4(0, 0, 0, 0);
+    if (have) {
+        p = *reinterpret_cast<const int4 *>(T.pos + g4 * 4);
+        reinterpret_cast<int32_t *>(T.unit_pp)[g4] = (g4 & 1) ? p.w : p.x;
+    }
+    int before = __shfl_up(p.w, 1);
+    if ((threadIdx.x & 63) == 0 && have && g4 > 0) before = T.pos[g4 * 4 - 1];
+    const int ps[5] = {before, p.x, p.y, p.z, p.w};
+    uint32_t dec = 0, zero = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int64_t r = g4 * 4 + e;
+        const bool in = r < T.n_rows;
+        dec |= (in && r > 0 && ps[e + 1] < ps[e] ? 1u : 0u) << e;
+        zero |= (in && ps[e + 1] == 0 ? 1u : 0u) << e;
+    }
+    const uint32_t mine = dec | (zero << 8);
+    const uint32_t other = __shfl_down(mine, 1);                     // (the unit's second half: the next lane, always in the same wave)
+    if (have && !(g4 & 1)) T.prel[g4 >> 1] = (uint16_t)(mine | (other << 4));
 }
 
 // ---------------------------------------------------------------------------------------------------
 // K1: the window scan, as two launches
 //
-//   k1_scan  streams the position column (and, on a table's first pass, the index-relation column -- two bits per row: how its
-//            event index stands to the index of the row before it -- validating every row),
+//   k1_scan  streams the unit summaries or the position column (and, on a table's first pass, the relation columns -- two bits
+//            per row each: how its event index and its position stand to those of the row before it -- validating every row),
 //            finds the units of eight rows that can hold a site row at all (one extract from the strand bitmask per unit)
 //            and decides for every site row of those whether it is the LAST row of its window: the next unfiltered row
 //            starts another read or lies beyond the site (:179).  Output: a 32-byte payload per closed window + a count
@@ -277,9 +297,12 @@ __device__ __forceinline__ int64_t desc_row_end_uniform(const NbDesc *desc, int 
     return v;
 }
 
-// (the one bit of the flag byte the scan looks at comes with the columns, from the table's bit column: SCAN_SUMMARY, which
-// streams unit summaries only, fetches the flag bytes of the units it lists)
-template <int MODE> constexpr bool nbits_streamed() { return MODE != SCAN_SUMMARY; }
+// (the instances that stream unit summaries in place of the positions, and those that validate every row)
+template <int MODE> constexpr bool summary_cols() { return MODE == SCAN_SUMMARY || MODE == SCAN_VALIDATE_SUMMARY; }
+template <int MODE> constexpr bool validating() { return MODE == SCAN_VALIDATE || MODE == SCAN_VALIDATE_SUMMARY; }
+// (the one bit of the flag byte the scan looks at comes with the columns, from the table's bit column: the instances that
+// stream unit summaries fetch the flag bytes of the units they list)
+template <int MODE> constexpr bool nbits_streamed() { return !summary_cols<MODE>(); }
 static_assert(MC_F_MODEL_N == 2, "flag_bytes(): where the bit goes in the flag byte");
 // four bits -> four flag bytes that hold MC_F_MODEL_N or nothing (one multiplication spreads the bits to bit 0 of the bytes)
 __device__ __forceinline__ uint32_t flag_bytes(uint32_t b4) { return (((b4 & 0xFu) * 0x00204081u) & 0x01010101u) << 1; }
@@ -287,22 +310,28 @@ __device__ __forceinline__ uint32_t flag_bytes(uint32_t b4) { return (((b4 & 0xF
 // The columns of one chunk in registers: every lane holds eight consecutive rows (a unit) of each 512-row stripe.
 template <int MODE>
 struct ChunkCols {
-    int4 pa[NQ], pb[NQ];            // positions of rows i0 .. i0+3, i0+4 .. i0+7 of the lane's unit in stripe j (SCAN_SUMMARY: pa.x, pb.w only)
+    int4 pa[NQ], pb[NQ];            // positions of rows i0 .. i0+3, i0+4 .. i0+7 of the lane's unit in stripe j (unit summaries: pa.x, pb.w only)
     uint32_t xr[NQ];                // ... their index relations, one word of the table's relation column: bit e, row e's event index is greater
-                                    // than that of the row before it, bit 8 + e, less (SCAN_VALIDATE) -- all the validation asks of the indices
-    uint32_t nb[NQ];                // ... their model-N bits, one byte of the table's bit column (not SCAN_SUMMARY)
+                                    // than that of the row before it, bit 8 + e, less (validating instances) -- all the validation asks of the indices
+    uint32_t pr[NQ];                // ... their position relations, likewise: bit e, row e's position is less than that of the row before it, bit
+                                    // 8 + e, it is 0 (SCAN_VALIDATE_SUMMARY) -- all the validation asks of the positions
+    uint32_t nb[NQ];                // ... their model-N bits, one byte of the table's bit column (not with unit summaries)
     __device__ __forceinline__ void load(const DevTable &T, int64_t c0, int crows, int lane) {
 #pragma unroll
         for (int j = 0; j < NQ; ++j) {
             const int i0 = (j * 64 + lane) * 8;
             pa[j] = pb[j] = make_int4(0, 0, 0, 0);
-            xr[j] = 0u;
+            xr[j] = pr[j] = 0u;
             nb[j] = 0xFFu;                                      // (rows past the table: 'N', never looked at anyway)
             if (i0 < crows) {                       // (arrays are padded: whole units stay in bounds)
-                if (MODE == SCAN_SUMMARY) {
+                if (summary_cols<MODE>()) {
                     const int2 pp = T.unit_pp[(c0 + i0) >> 3];
                     pa[j].x = pp.x;
                     pb[j].w = pp.y;
+                    if (MODE == SCAN_VALIDATE_SUMMARY) {        // (two words per lane and stripe: 1.5 B/row in all)
+                        xr[j] = T.xrel[(c0 + i0) >> 3];
+                        pr[j] = T.prel[(c0 + i0) >> 3];
+                    }
                 } else {
                     pa[j] = *reinterpret_cast<const int4 *>(T.pos + c0 + i0);
                     pb[j] = *reinterpret_cast<const int4 *>(T.pos + c0 + i0 + 4);
@@ -465,8 +494,12 @@ __device__ __forceinline__ void dense_block_rows(const K1Args &A, TileSlots &S, 
 // of the current one are free, and travel while the current chunk's candidates are examined.
 //
 // The columns of a chunk go from HBM into REGISTERS -- every lane holds eight consecutive rows (a unit) of each 512-row stripe.
-// On a table's first pass (SCAN_VALIDATE) these are the positions, the index relations and the model-N bits -- the table's two
-// bit columns, a word and a byte per unit: how a row's event index stands to that of the row before it (greater, less, equal:
+// On a table's first pass under a sparse motif (SCAN_VALIDATE_SUMMARY) these are the unit summaries (first and last position of
+// the unit: all the filter below asks) and the table's two relation columns, a word each per unit: how a row's event index and
+// its position stand to those of the row before it, and whether the position is 0 -- 1.5 B/row; a unit that lies in a block with
+// the row before it adds four population counts to the lanes' counts, a unit cut by a block's ends reads its rows from memory
+// out of line, and nothing is compared in registers.  Under a one-base motif (SCAN_VALIDATE) these are the positions, the
+// index relations and the model-N bits -- the table's two bit columns, a word and a byte per unit: how a row's event index stands to that of the row before it (greater, less, equal:
 // the table's maker had both in hand), and the one bit of the flag byte the scan looks at, MC_F_MODEL_N -- 4.375 B/row, and
 // every row is compared with the row before it -- positions: its neighbour in the lane, the previous lane's last row (one
 // shuffle), the last row of the chunk before; indices: the comparison comes made, two bits of the unit's word -- which gives
@@ -491,7 +524,8 @@ __device__ __forceinline__ void dense_block_rows(const K1Args &A, TileSlots &S, 
 #ifdef MC_SCAN_WPE                  // (variant builds, tools/variants.sh)
 #define MC_SCAN_ATTR __attribute__((amdgpu_waves_per_eu(MC_SCAN_WPE, MC_SCAN_WPE)))
 #else
-// (the instance that reads unit summaries fits 80 registers -- six waves per SIMD -- give or take one: said to the compiler)
+// (the instance that reads unit summaries alone fits 80 registers -- six waves per SIMD -- give or take one: said to the
+// compiler; the validating one that reads them is left to it)
 #define MC_SCAN_ATTR __attribute__((amdgpu_waves_per_eu(MODE == SCAN_SUMMARY ? 6 : 1)))
 #endif
 template <int CG, int MODE>
@@ -583,7 +617,7 @@ __global__ __launch_bounds__(64) MC_SCAN_ATTR void k1_scan(K1Args A) {
         // registers than it has.  Event indices: the table's relation column holds the comparisons of a unit's eight rows, each
         // with the row before it in the table -- which is its predecessor in the block wherever the count is taken -- so a unit
         // adds two population counts)
-        if (MODE == SCAN_VALIDATE) {
+        if (validating<MODE>()) {
             for (int bi = 0; bi < nfast; ++bi) {
                 const int64_t rb = bi ? db.row_begin : da.row_begin, re = bi ? db.row_end : da.row_end;
                 const uint32_t vf_known = bi ? db.vf : da.vf;
@@ -595,6 +629,19 @@ __global__ __launch_bounds__(64) MC_SCAN_ATTR void k1_scan(K1Args A) {
                 for (int j = 0; j < NQ; ++j) {
                     if (j * 512 + 512 <= vlo || j * 512 >= vhi) continue;      // (wave-uniform)
                     const int i0 = (j * 64 + lane) * 8;
+                    const bool whole = i0 >= pred_from && i0 + 8 <= vhi;
+                    const bool cut = !whole && i0 + 8 > vlo && i0 < vhi;
+                    if (MODE == SCAN_VALIDATE_SUMMARY) {
+                        // the unit and the row before it inside the block: every bit of its two relation words counts -- the row
+                        // before a row in the table is its predecessor in the block here -- and the unit adds four population counts
+                        if (whole) {
+                            n_pdec += __popc(C.pr[j] & 0xFFu);
+                            n_pos0 += __popc(C.pr[j] >> 8);
+                            n_inc += __popc(C.xr[j] & 0xFFu);
+                            n_dec += __popc(C.xr[j] >> 8);
+                            n_pairs += 8;
+                        }
+                    } else {
                     // the row before the unit: the previous lane's last row (lane 0: the previous stripe's, or the row before the chunk)
                     // (positions only: the index relation of the unit's first row to that row is bit 0 of the unit's own word)
                     int qp = __shfl_up(C.pb[j].w, 1);
@@ -603,8 +650,6 @@ __global__ __launch_bounds__(64) MC_SCAN_ATTR void k1_scan(K1Args A) {
                         if (lane == 0) qp = sp;
                     }
                     const int ps[8] = {C.pa[j].x, C.pa[j].y, C.pa[j].z, C.pa[j].w, C.pb[j].x, C.pb[j].y, C.pb[j].z, C.pb[j].w};
-                    const bool whole = i0 >= pred_from && i0 + 8 <= vhi;
-                    const bool cut = !whole && i0 + 8 > vlo && i0 < vhi;
                     if (whole) {                                // the unit and the row before it inside the block: the usual case
 #pragma unroll
                         for (int e = 0; e < 8; ++e) {
@@ -620,6 +665,7 @@ __global__ __launch_bounds__(64) MC_SCAN_ATTR void k1_scan(K1Args A) {
                         const uint32_t m45 = min((uint32_t)ps[4], (uint32_t)ps[5]), m67 = min((uint32_t)ps[6], (uint32_t)ps[7]);
                         n_pos0 += min(min(m01, m23), min(m45, m67)) == 0u;
                     }
+                    }
                     // a unit cut by the block's ends (or the block's very first rows): its rows once more, from memory, out of line
                     // (written here on the registers, the compiler shares the comparisons with the usual case above and keeps
                     // their lane masks alive for every unit: 130 spilled scalar registers)
@@ -633,7 +679,7 @@ __global__ __launch_bounds__(64) MC_SCAN_ATTR void k1_scan(K1Args A) {
             }
             if (has_c) validate_rows_slowly(A, nb0 + 2, db.row_end, c1, lane);
             // the next chunk's "row before": this chunk's last row
-            if (more) {
+            if (MODE == SCAN_VALIDATE && more) {
                 before_p = __shfl(C.pb[NQ - 1].w, 63);
             }
         }
@@ -702,7 +748,7 @@ __global__ __launch_bounds__(64) MC_SCAN_ATTR void k1_scan(K1Args A) {
                     // the two rows behind the unit: the next lane's first two rows (lane 63: the next stripe's)
                     int nx = 0, ny = 0;
                     uint32_t nf = 0x3u;                 // (their model-N bits)
-                    if (MODE != SCAN_SUMMARY) {
+                    if (!summary_cols<MODE>()) {
                         nx = __shfl_down(C.pa[j].x, 1);
                         ny = __shfl_down(C.pa[j].y, 1);
                         nf = __shfl_down(C.nb[j], 1);
@@ -715,7 +761,7 @@ __global__ __launch_bounds__(64) MC_SCAN_ATTR void k1_scan(K1Args A) {
                     if (cand) {
                         CandUnit *g = s_cand + (ncand + __popcll(bal & below));
                         int4 *gp = reinterpret_cast<int4 *>(g);
-                        if (MODE != SCAN_SUMMARY) {
+                        if (!summary_cols<MODE>()) {
                             gp[0] = C.pa[j];
                             gp[1] = C.pb[j];
                             // pos[8], pos[9] | flag bytes 0..7: the unit's model-N bits, a byte each again for the lanes that decide
@@ -738,7 +784,7 @@ __global__ __launch_bounds__(64) MC_SCAN_ATTR void k1_scan(K1Args A) {
             __syncthreads();                            // (one wave: orders the list's words between the lanes)
             if (!nbits_streamed<MODE>()) {
                 // the flag bytes of the listed units and of the two rows behind each (the columns are padded beyond the table's
-                // last row); SCAN_SUMMARY: their positions as well
+                // last row); with unit summaries: their positions as well
                 for (int base = 0; base < ncand; base += 64) {
                     const int gi = base + lane;
                     if (gi < ncand) {
@@ -747,7 +793,7 @@ __global__ __launch_bounds__(64) MC_SCAN_ATTR void k1_scan(K1Args A) {
                         const uint8_t *fr = T.flags + c0 + i0;
                         const uint2 f8 = *reinterpret_cast<const uint2 *>(fr);
                         const uint32_t nf = *reinterpret_cast<const uint16_t *>(fr + 8);
-                        if (MODE == SCAN_SUMMARY) {
+                        if (summary_cols<MODE>()) {
                             const int32_t *pr = T.pos + c0 + i0;
                             const int4 a = *reinterpret_cast<const int4 *>(pr), b4 = *reinterpret_cast<const int4 *>(pr + 4);
                             const int2 nx = *reinterpret_cast<const int2 *>(pr + 8);
@@ -925,8 +971,8 @@ __global__ __launch_bounds__(256) void k1_list(K1Args A, Payload *__restrict__ s
 
 }  // namespace
 
-void mc_launch_summarize(const DevTable &T, hipStream_t st) {
-    hipLaunchKernelGGL(k_summarize, dim3((unsigned)((T.n_rows / 4 + 256) / 256)), dim3(256), 0, st, T);
+void mc_launch_unit_columns(const DevTable &T, hipStream_t st) {
+    hipLaunchKernelGGL(k_unit_columns, dim3((unsigned)((T.n_rows / 4 + 256) / 256)), dim3(256), 0, st, T);
 }
 
 // one wave per tile; the instance with the small candidate list unless marked positions are dense (a one-base motif)
@@ -938,6 +984,7 @@ void mc_launch_scan(const K1Args &A, bool dense, int scan_mode, hipStream_t st) 
         else hipLaunchKernelGGL((k1_scan<CG_DENSE, SCAN_STREAM>), grid, dim3(64), 0, st, A);
     } else {
         if (scan_mode == SCAN_VALIDATE) hipLaunchKernelGGL((k1_scan<64, SCAN_VALIDATE>), grid, dim3(64), 0, st, A);
+        else if (scan_mode == SCAN_VALIDATE_SUMMARY) hipLaunchKernelGGL((k1_scan<64, SCAN_VALIDATE_SUMMARY>), grid, dim3(64), 0, st, A);
         else if (scan_mode == SCAN_STREAM) hipLaunchKernelGGL((k1_scan<64, SCAN_STREAM>), grid, dim3(64), 0, st, A);
         else hipLaunchKernelGGL((k1_scan<64, SCAN_SUMMARY>), grid, dim3(64), 0, st, A);
     }

@@ -11,29 +11,31 @@
 //   text         kp_count / kp_scan / kp_starts / kp_parse / kp_count_rows / kp_place   the eventalign TEXT of a streamed shard
 //                                parsed on the device (mc_devparse.inc): line starts, tokens, numbers, name blocks and segments,
 //                                the columns written straight into a table slot -- the model-N bit column (one bit per row:
-//                                the row's model k-mer is NNNNNN) and the index-relation column (two bits per row) with
-//                                them, a byte and a word per eight rows put together in kp_place
-//   per table     (nothing runs at upload: the first pass over a table validates it while it scans)
+//                                the row's model k-mer is NNNNNN), the index- and position-relation columns (two bits per
+//                                row each) and the unit summaries (first / last position of every eight rows) with them, put
+//                                together in kp_place
+//   per table     k_unit_columns  a table that arrives as columns (mc_ctx_upload_table*): unit summaries and the
+//                                position-relation column from the position column, on the upload stream behind its transfer
+//                                (a device-parsed table has them from kp_place).  Nothing else runs at upload: the first
+//                                pass over a table validates it while it scans
 //                (nb_template     the pass-independent fields of the name-block descriptors: inside the first k0_first_site over a table)
-//                k_summarize     a table that is scanned a second time gets unit summaries (first / last position of every
-//                                eight rows): every further scan reads 1 B/row instead of streaming the columns
 //   per pass     k0_first_site   first site row of every name block under the "new read" strand rule (:161-174) -> strand of
 //                                the block; classifies the block (regular / no sites / irregular) in the same workgroup.  On
 //                                a table no pass has validated yet the classification rests on the block's first rows
 //                                (direction of the event index, position 0) and the scan confirms it
 //                k0_classify / k0_extend   tables with repeated read names; irregular runs widened
 //                k1_scan         THE SCAN: one wave per tile of 2048 rows, nothing persistent.  First pass over a table: the
-//                                position column, the index-relation column (two bits per row: its event index against the
-//                                index of the row before it, written by the table's maker) and the model-N bit column
-//                                (the one bit of the flag byte the scan looks at; 4.375 B/row in all) go from HBM into
-//                                registers and every row is
-//                                compared with the row before it (positions non-decreasing? event index strictly monotone?
-//                                -- what makes a name block "regular"); units of eight rows that can hold a site row are
+//                                unit summaries and the two relation columns (two bits per row each: its event index and
+//                                its position against those of the row before it, position 0; all written by the table's
+//                                maker; 1.5 B/row in all) go from HBM into registers and every row is validated from its
+//                                bits (positions non-decreasing? event index strictly monotone? -- what makes a name block
+//                                "regular"); units of eight rows that can hold a site row are
 //                                found with one extract from the strand bitmask (two words per unit, straight from L2) and
-//                                listed in LDS with their model-N bits, their rows are tested for "last row
-//                                of a window"; every closed window leaves a 32-byte payload.  Later passes over the same
-//                                table read the unit summaries instead (1 B/row; the listed units fetch their flag bytes);
-//                                one-base motifs, where every unit passes, stream the positions and the bits.
+//                                listed in LDS, fetch their rows' positions and flag bytes, and their rows are tested for
+//                                "last row of a window"; every closed window leaves a 32-byte payload.  Later passes over the
+//                                same table read the unit summaries alone (1 B/row); one-base motifs, where every unit
+//                                passes, stream the positions and the model-N bits, and on a first pass the index relations
+//                                with them (4.375 B/row), comparing the positions in registers.
 //                k1_group_scan / k1_list   file order of the windows; payloads gathered into it
 //                k1_emit         eight lanes per window: which of the rows before its last row belong to which slot, slot
 //                                means in NumPy pairwise order (fp64) from the rows' (event, model) pairs -> one flush record
@@ -195,25 +197,23 @@ struct PassPlan {
     bool first;          // no pass has validated the table: classification on the blocks' first rows, the scan validates every row
     int scan_mode;       // SCAN_*
 };
-static PassPlan plan_pass(mc_ctx *c, hipStream_t st) {
+static PassPlan plan_pass(mc_ctx *c) {
     PassPlan P;
     P.first = true;
-    P.scan_mode = SCAN_VALIDATE;
+    P.scan_mode = c->last_scan_mode = SCAN_VALIDATE;
     if (c->cur < 0) return P;
     TableSlot &S = c->slots[c->cur];
-    const bool dense = dense_reference(c);                 // (a one-base motif: every unit is listed, summaries would not help)
+    // (a one-base motif: every unit is listed, summaries would not help.  The summaries and the position relations are the
+    // table maker's columns: nothing is launched for them here)
+    const bool summaries = !dense_reference(c) && S.summarized;
     if (S.passes > 0) {
         P.first = false;
-        P.scan_mode = SCAN_STREAM;
-        if (!dense && S.passes >= 2) {
-            if (!S.summarized && S.T.n_rows > 0) {
-                mc_launch_summarize(S.T, st);
-                S.summarized = true;
-            }
-            P.scan_mode = SCAN_SUMMARY;
-        }
+        P.scan_mode = summaries ? SCAN_SUMMARY : SCAN_STREAM;
+    } else if (summaries) {
+        P.scan_mode = SCAN_VALIDATE_SUMMARY;
     }
     S.passes += 1;
+    c->last_scan_mode = P.scan_mode;
     return P;
 }
 
@@ -265,7 +265,7 @@ static int enqueue_k1(mc_ctx *c, const mc_params *prm, const PassBufs &B, const 
     if (fused_room > 0) {
         // a dense reference, a pipelined pass: scan, ordering and emit as ONE kernel with fixed room per piece (k1_fused,
         // mc_fused.hip); the pass's event rides on its dispatch packet
-        mc_launch_fused(A, B.sorted, fused_room, plan.scan_mode == SCAN_VALIDATE, st, on_packet);
+        mc_launch_fused(A, B.sorted, fused_room, plan.first, st, on_packet);
         if (!on_packet) HIP_TRY(hipEventRecord(ev_emit_end, st));
         *out_args = A;
         return 0;
@@ -298,7 +298,7 @@ static int enqueue_k1(mc_ctx *c, const mc_params *prm, const PassBufs &B, const 
 
 // the synchronous pass: everything on the ctx stream, ev[0..3] around the stages (mc_last_times_ms)
 static int enqueue_fast_path(mc_ctx *c, const mc_params *prm, K1Args *out_args) {
-    const PassPlan plan = plan_pass(c, c->stream);            // (in front of ev[0]: a table's summaries are not part of a pass)
+    const PassPlan plan = plan_pass(c);
     HIP_TRY(hipEventRecord(c->ev[0], c->stream));
     if (int rc = enqueue_k0(c, prm, c->sync, plan, nullptr)) return rc;
     HIP_TRY(hipEventRecord(c->ev[1], c->stream));
@@ -614,7 +614,7 @@ extern "C" int mc_extract_features_async(mc_ctx *c, const mc_params *prm) {
     // (a hipEventRecord between two kernels costs this queue ~9 us -- rocprofv3 timeline -- so the two events that only time
     // the pass, unlike ev_emit_end, which the side stream waits for, can be thinned out: mc_ctx_set_pass_timing)
     b.timed = c->timing_every > 0 && (c->pass_seq++ % c->timing_every) == 0;
-    const PassPlan plan = plan_pass(c, st);
+    const PassPlan plan = plan_pass(c);
     if (b.timed) HIP_TRY(hipEventRecord(b.ev[EV_K0_START], st));
     // (the buffer's last pass has been handed out, nothing on the device writes st_host: the mark mc_wait_records_begin looks for)
     b.st.get<Counters>()->side_done = ST_UNPUBLISHED;
@@ -841,6 +841,8 @@ extern "C" int mc_last_pass_info(mc_ctx *c, int32_t *fused_room, int32_t *rerun)
     if (rerun) *rerun = c->last_rerun;
     return 0;
 }
+
+extern "C" int mc_ctx_last_scan_mode(mc_ctx *c) { return c->last_scan_mode; }
 
 extern "C" int mc_ctx_set_pass_timing(mc_ctx *c, int every_n) {
     if (every_n < 0) { mc_set_error("mc_ctx_set_pass_timing: every_n < 0"); return -12; }

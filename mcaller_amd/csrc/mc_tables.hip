@@ -274,7 +274,7 @@ static void slot_free(TableSlot &S) {
     S.nbits_h.reset();
     S.xrel_h.reset();
     S.small_dev = nullptr;
-    S.pos = S.idx = nullptr; S.evmu = nullptr; S.flags = nullptr; S.nbits = nullptr; S.xrel = nullptr; S.nb_tmpl = nullptr; S.unit_pp = nullptr;
+    S.pos = S.idx = nullptr; S.evmu = nullptr; S.flags = nullptr; S.nbits = nullptr; S.xrel = nullptr; S.prel = nullptr; S.nb_tmpl = nullptr; S.unit_pp = nullptr;
     S.cap_rows = S.cap_segs = S.cap_reads = 0;
     S.T = DevTable();
     S.qual = nullptr; S.n_qual = 0; S.tmpl_ref = -1;
@@ -301,7 +301,7 @@ static int slot_ensure(mc_ctx *c, TableSlot &S, int64_t rows, int64_t segs, int6
     if (S.allocs.get(&S.pos, (size_t)padded) || S.allocs.get(&S.idx, (size_t)padded) ||
         S.allocs.get(&S.evmu, (size_t)padded) || S.allocs.get(&S.flags, (size_t)padded) ||
         S.allocs.get(&S.unit_pp, (size_t)padded / 8 + 8) || S.allocs.get(&S.nbits, (size_t)padded / 8 + 8) ||
-        S.allocs.get(&S.xrel, (size_t)padded / 8 + 8))
+        S.allocs.get(&S.xrel, (size_t)padded / 8 + 8) || S.allocs.get(&S.prel, (size_t)padded / 8 + 8))
         return -10;
     // (FRONT rows of padding before row 0 of the columns k1_emit looks back into: rows -1 .. -64 are readable; nothing looks
     // back through the bit column, which like the others reaches a tile beyond the table's last whole tile)
@@ -403,7 +403,7 @@ static int fill_slot(mc_ctx *c, int at, int64_t n, int32_t n_seg, const int64_t 
     DevTable &T = S.T;
     T = DevTable();
     T.n_rows = n; T.n_seg = n_seg; T.n_reads = n_reads; T.n_nb = n_nb; T.n_tiles = n_tiles; T.has_repeats = has_rep;
-    T.pos = S.pos; T.idx = S.idx; T.evmu = S.evmu; T.flags = S.flags; T.nbits = S.nbits; T.xrel = S.xrel; T.nb_tmpl = S.nb_tmpl; T.unit_pp = S.unit_pp;
+    T.pos = S.pos; T.idx = S.idx; T.evmu = S.evmu; T.flags = S.flags; T.nbits = S.nbits; T.xrel = S.xrel; T.prel = S.prel; T.nb_tmpl = S.nb_tmpl; T.unit_pp = S.unit_pp;
     unsigned char *dv = S.small_dev;
     T.seg_begin = (int64_t *)(dv + L.seg_begin); T.seg_read = (int32_t *)(dv + L.seg_read); T.seg_contig = (int32_t *)(dv + L.seg_contig);
     T.nb_row_begin = (int64_t *)(dv + L.nb_row_begin); T.nb_seg_begin = (int32_t *)(dv + L.nb_seg_begin);
@@ -413,7 +413,7 @@ static int fill_slot(mc_ctx *c, int at, int64_t n, int32_t n_seg, const int64_t 
     S.n_qual = read_qual ? n_reads : 0;
     S.tmpl_ref = -1;
     S.passes = 0;                                          // (the first pass over these rows validates them)
-    S.summarized = false;
+    S.summarized = n > 0;                                  // (kp_place wrote unit_pp and prel with the columns; k_unit_columns below)
 
     // ---- H2D on the upload stream (nothing reads the slot: its passes have been handed out); the ctx stream waits for the
     //      transfer ----
@@ -445,6 +445,9 @@ static int fill_slot(mc_ctx *c, int at, int64_t n, int32_t n_seg, const int64_t 
                 xrel = S.xrel_h.get<uint16_t>();
             }
             HIP_TRY(hipMemcpyAsync(T.xrel, xrel, (size_t)(n + 7) / 8 * 2, hipMemcpyHostToDevice, us));
+            // the unit summaries and the position relations: made on the device from the position column that has just arrived
+            // (one read of 4 B/row from HBM behind 17.4 B/row over the link; nothing more to pack, pin or send)
+            mc_launch_unit_columns(T, us);
         }
     }
     if (!cols && L.total <= COPY_BY_KERNEL_MAX) { if (int rc = mc_copy_by_kernel(dv, st, L.total, us)) return rc; }     // (not behind the next shard's text)
@@ -631,7 +634,7 @@ extern "C" int mc_ctx_parse_begin(mc_ctx *c, const char *text, int64_t n_bytes, 
         QA.text = S.text; QA.head = S.kp_head; QA.head_w = S.kp_head; QA.cap_lines = cap_lines; QA.cap_rows = S.cap_rows;
         QA.blk_off = K.tile_off; QA.pos = K.pos; QA.idx = K.idx; QA.ev = K.ev; QA.mu = K.mu; QA.contig = K.contig;
         QA.name_off = K.name_off; QA.name_len = K.name_len; QA.fl = K.fl; QA.status = K.status;
-        QA.t_pos = S.pos; QA.t_idx = S.idx; QA.t_evmu = S.evmu; QA.t_flags = S.flags; QA.t_nbits = S.nbits; QA.t_xrel = S.xrel; QA.segs = S.kp_segs; QA.cap_segs = S.kp_cap_segs;
+        QA.t_pos = S.pos; QA.t_idx = S.idx; QA.t_evmu = S.evmu; QA.t_flags = S.flags; QA.t_nbits = S.nbits; QA.t_xrel = S.xrel; QA.t_prel = S.prel; QA.t_unit_pp = S.unit_pp; QA.segs = S.kp_segs; QA.cap_segs = S.kp_cap_segs;
         QA.unknown = S.kp_unknown;
         hipLaunchKernelGGL(kp_place, dim3(line_blocks), dim3(256), 0, us, QA);
         KP_STEP("kp_place");
@@ -786,6 +789,35 @@ extern "C" int mc_ctx_fetch_idx_rel_bits(mc_ctx *c, int32_t slot, int64_t n_rows
     HIP_TRY(hipStreamSynchronize(c->up_stream));
     if (c->parse_stream) HIP_TRY(hipStreamSynchronize(c->parse_stream));
     if (n_rows > 0) HIP_TRY(hipMemcpy(out, S.xrel, (size_t)(n_rows + 7) / 8 * 2, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ... its position-relation column, likewise
+extern "C" int mc_ctx_fetch_pos_rel_bits(mc_ctx *c, int32_t slot, int64_t n_rows, uint16_t *out) {
+    HIP_TRY(hipSetDevice(c->device));
+    if (slot < 0 || slot >= MC_TABLE_SLOTS || !c->slots[slot].pos || n_rows < 0 || n_rows > c->slots[slot].cap_rows || !out) {
+        mc_set_error("mc_ctx_fetch_pos_rel_bits: slot %d, %lld rows", slot, (long long)n_rows);
+        return -12;
+    }
+    TableSlot &S = c->slots[slot];
+    HIP_TRY(hipStreamSynchronize(c->up_stream));
+    if (c->parse_stream) HIP_TRY(hipStreamSynchronize(c->parse_stream));
+    if (n_rows > 0) HIP_TRY(hipMemcpy(out, S.prel, (size_t)(n_rows + 7) / 8 * 2, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ... and its unit summaries: ceil(n_rows / 8) pairs (first, last position of the unit; the second of a last, partial unit is
+// whatever the slot holds there)
+extern "C" int mc_ctx_fetch_unit_summaries(mc_ctx *c, int32_t slot, int64_t n_rows, int32_t *out) {
+    HIP_TRY(hipSetDevice(c->device));
+    if (slot < 0 || slot >= MC_TABLE_SLOTS || !c->slots[slot].pos || n_rows < 0 || n_rows > c->slots[slot].cap_rows || !out) {
+        mc_set_error("mc_ctx_fetch_unit_summaries: slot %d, %lld rows", slot, (long long)n_rows);
+        return -12;
+    }
+    TableSlot &S = c->slots[slot];
+    HIP_TRY(hipStreamSynchronize(c->up_stream));
+    if (c->parse_stream) HIP_TRY(hipStreamSynchronize(c->parse_stream));
+    if (n_rows > 0) HIP_TRY(hipMemcpy(out, S.unit_pp, (size_t)(n_rows + 7) / 8 * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -225,6 +225,21 @@ class Device(object):
         return out
 
     @_serialized
+    def fetch_pos_rel_bits(self, slot, n_rows):
+        """The position-relation column of the table in `slot`, ceil(n_rows / 8) uint16 (tests)."""
+        out = np.zeros((n_rows + 7) // 8 + 1, dtype=np.uint16)
+        check(lib().mc_ctx_fetch_pos_rel_bits(self._ctx, int(slot), int(n_rows), _ptr(out)))
+        return out[:(n_rows + 7) // 8]
+
+    @_serialized
+    def fetch_unit_summaries(self, slot, n_rows):
+        """The unit summaries of the table in `slot`, [ceil(n_rows / 8), 2] int32: first and last position of every unit of eight
+        rows; the second of a last, partial unit is unspecified (tests)."""
+        out = np.zeros(((n_rows + 7) // 8 + 1, 2), dtype=np.int32)
+        check(lib().mc_ctx_fetch_unit_summaries(self._ctx, int(slot), int(n_rows), _ptr(out)))
+        return out[:(n_rows + 7) // 8]
+
+    @_serialized
     def wait_upload(self, slot):
         check(lib().mc_ctx_wait_upload(self._ctx, int(slot)))
 
@@ -436,6 +451,12 @@ class Device(object):
         a, b = C.c_int32(0), C.c_int32(0)
         check(lib().mc_last_pass_info(self._ctx, C.byref(a), C.byref(b)))
         return a.value, bool(b.value)
+
+    @_serialized
+    def last_scan_mode(self):
+        """What the scan of the pass enqueued last streams (mc_ctx_last_scan_mode): 0 the columns, validating; 1 the columns;
+        2 unit summaries; 3 unit summaries and the relation columns, validating (tests)."""
+        return int(lib().mc_ctx_last_scan_mode(self._ctx))
 
     @_serialized
     def times_ms(self):
