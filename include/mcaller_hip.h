@@ -765,6 +765,21 @@ double mc_tstat_round3(double v);
 int mc_tstat_tie(double v, double err);
 int mc_tstat_site(const double *X, int64_t n_rows, int32_t n_cols, double *out2);
 
+/* ===== the hypergeometric tail of evaluate.py (mcaller_amd/csrc/mc_hypergeom.h: one header for the host and the device) =====
+ * mc_hypergeom_tail: the host build on one case -> 0, or 1 for arguments outside 0 <= K <= N < 2^31, 0 <= d <= min(N, 2^20)
+ * (*tail and *err NaN then); *tail = P(X >= k) for X the number of marked among d drawn without replacement from N of which K
+ * are marked, *err a DERIVED bound on |*tail - exact| (0 where the tail is 1 or 0 by the range of X alone).
+ * mc_hypergeom_tail_many: the same on `count` cases.  mc_hypergeom_tail_device: the device build, a lane per case.
+ * mc_hypergeom_round4: rint(v * 10000) / 10000, the fp64 operations of np.round(v, 4).  mc_hypergeom_tie4: 1 when
+ * np.round(h, 4) can differ from np.round(v, 4) for an h within err of v (another ten-thousandth, or the other zero). */
+int mc_hypergeom_tail(int64_t N, int64_t K, int64_t d, int64_t k, double *tail, double *err);
+int mc_hypergeom_tail_many(const int64_t *N, const int64_t *K, const int64_t *d, const int64_t *k, int64_t count, double *tail,
+                           double *err);
+int mc_hypergeom_tail_device(mc_ctx *ctx, const int64_t *N, const int64_t *K, const int64_t *d, const int64_t *k, int64_t count,
+                             double *tail, double *err);
+double mc_hypergeom_round4(double v);
+int mc_hypergeom_tie4(double v, double err);
+
 /* ===== decimal text -> double, correctly rounded (mcaller_amd/csrc/mc_decimal.h: one header for the host and the device) =====
  * float(s) of a token [+-]? digits? ('.' digits?)? ([eE] [+-]? digits)? with at least one mantissa digit whose significand
  * (leading zeros stripped, trailing zeros folded into the exponent) has at most 19 digits and whose decimal exponent q has

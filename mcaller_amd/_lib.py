@@ -609,6 +609,34 @@ def tstat_site(rows):
     return st, float(out[0]), float(out[1])
 
 
+def hypergeom_tail(N, K, d, k):
+    """P(X >= k) for X ~ Hypergeometric(N, K, d) and the derived bound on its error, by mc_hypergeom.h's host build.  Scalars
+    -> (status, tail, err) (mc_hypergeom_tail); four arrays of one length -> (tail float64 [n], err float64 [n]), NaN where the
+    arguments are out of range (mc_hypergeom_tail_many)."""
+    if np.ndim(N) == 0:
+        t, e = C.c_double(), C.c_double()
+        st = lib().mc_hypergeom_tail(int(N), int(K), int(d), int(k), C.byref(t), C.byref(e))
+        return st, t.value, e.value
+    N, K, d, k = (np.ascontiguousarray(a, dtype=np.int64) for a in (N, K, d, k))
+    if not (N.ndim == 1 and N.shape == K.shape == d.shape == k.shape):
+        raise ValueError('hypergeom_tail: four arrays of one length')
+    tail, err = np.zeros(len(N)), np.zeros(len(N))
+    rc = lib().mc_hypergeom_tail_many(N.ctypes.data, K.ctypes.data, d.ctypes.data, k.ctypes.data, len(N), tail.ctypes.data, err.ctypes.data)
+    if rc:
+        raise ValueError('mc_hypergeom_tail_many: %d' % rc)
+    return tail, err
+
+
+def hypergeom_round4(v):
+    """np.round(v, 4) by mc_hypergeom.h's host build."""
+    return lib().mc_hypergeom_round4(float(v))
+
+
+def hypergeom_tie4(v, err):
+    """Can np.round(h, 4) differ from np.round(v, 4) for an h within err of v?  (mc_hypergeom.h's tie test, host build)"""
+    return bool(lib().mc_hypergeom_tie4(float(v), float(err)))
+
+
 def parse_double(token):
     """float(token) by mc_decimal.h's host build (mc_parse_double): the double, or None for a form that header declines.
     `token`: bytes (a str is encoded as latin-1, so that every character is one byte)."""

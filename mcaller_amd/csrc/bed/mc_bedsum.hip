@@ -92,6 +92,7 @@
 #include "../mc_rowtext.h"
 #include "../mc_decimal.h"
 #include "../mc_tstat.h"
+#include "../mc_hypergeom.h"
 #include "../mc_npsum.h"
 
 namespace {
@@ -915,6 +916,16 @@ __global__ __launch_bounds__(256) void k_ts_probe(const double *__restrict__ n, 
     t[i] = tv; l[i] = lv;
 }
 
+// the probe of mc_hypergeom.h's device build: a lane per case (bad arguments: NaN twice)
+__global__ __launch_bounds__(256) void k_hg_probe(const long long *__restrict__ N, const long long *__restrict__ K, const long long *__restrict__ d,
+                                                  const long long *__restrict__ k, int64_t count, double *__restrict__ tail, double *__restrict__ err) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    double t, e;
+    (void)hg_tail(N[i], K[i], d[i], k[i], &t, &e);
+    tail[i] = t; err[i] = e;
+}
+
 }  // namespace
 
 extern "C" int mc_bed_summarise(mc_ctx *c, const mc_text_source *src, const mc_text_source *positions, const mc_text_source *fasta,
@@ -1006,6 +1017,30 @@ extern "C" int mc_tstat_device(mc_ctx *c, const double *n, const double *mean, c
     HIP_TRY(hipMemcpyAsync(t, d_out, (size_t)count * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(log10_p, d_out + count, (size_t)count * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(status, d_st, (size_t)count * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int mc_hypergeom_tail_device(mc_ctx *c, const int64_t *N, const int64_t *K, const int64_t *d, const int64_t *k, int64_t count, double *tail,
+                                        double *err) {
+    if (!c || count < 0 || (count > 0 && (!N || !K || !d || !k || !tail || !err))) {
+        mc_set_error("mc_hypergeom_tail_device: bad arguments");
+        return -12;
+    }
+    if (count == 0) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    Pool pool("hypergeometric tail probe");
+    long long *d_in = nullptr;
+    double *d_out = nullptr;
+    if (pool.get(&d_in, (size_t)count * 4) || pool.get(&d_out, (size_t)count * 2)) return -10;
+    hipStream_t st = c->stream;
+    const int64_t *in[4] = {N, K, d, k};
+    for (int q = 0; q < 4; ++q) HIP_TRY(hipMemcpyAsync(d_in + q * count, in[q], (size_t)count * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_hg_probe, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, (const long long *)d_in, (const long long *)(d_in + count),
+                       (const long long *)(d_in + 2 * count), (const long long *)(d_in + 3 * count), count, d_out, d_out + count);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(tail, d_out, (size_t)count * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(err, d_out + count, (size_t)count * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }

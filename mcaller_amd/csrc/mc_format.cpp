@@ -11,6 +11,7 @@
 #include "mc_sortkey.h"
 #include "mc_rowtext.h"
 #include "mc_tstat.h"
+#include "mc_hypergeom.h"
 #include "mc_twosample.h"
 #include "mc_npsum.h"
 #include "../../include/mcaller_hip.h"
@@ -645,6 +646,19 @@ extern "C" int mc_tstat_site(const double *X, int64_t n_rows, int32_t n_cols, do
     if (n_rows >= 2 && (!rt_num_of(out2[0]).ok || !rt_num_of(out2[1]).ok)) flags |= 64;      // (a value mc_rowtext.h does not print)
     return flags;
 }
+
+// the hypergeometric tail of evaluate.py's subsampled-depth tables by mc_hypergeom.h's host build (include/mcaller_hip.h)
+extern "C" int mc_hypergeom_tail(int64_t N, int64_t K, int64_t d, int64_t k, double *tail, double *err) {
+    if (!tail || !err) return -12;
+    return hg_tail(N, K, d, k, tail, err);
+}
+extern "C" int mc_hypergeom_tail_many(const int64_t *N, const int64_t *K, const int64_t *d, const int64_t *k, int64_t count, double *tail, double *err) {
+    if (count < 0 || (count > 0 && (!N || !K || !d || !k || !tail || !err))) return -12;
+    for (int64_t i = 0; i < count; ++i) (void)hg_tail(N[i], K[i], d[i], k[i], &tail[i], &err[i]);
+    return 0;
+}
+extern "C" double mc_hypergeom_round4(double v) { return hg_round4(v); }
+extern "C" int mc_hypergeom_tie4(double v, double err) { return hg_tie4(v, err) ? 1 : 0; }
 
 // the two-sample arithmetic of compare_genomes by mc_twosample.h's host build (include/mcaller_hip.h): the counts from sorted
 // copies of the two samples, the moments in row order, then tw_finish

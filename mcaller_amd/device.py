@@ -814,6 +814,18 @@ class Device(object):
         return st, t, l
 
     @_serialized
+    def hypergeom_tail(self, N, K, d, k):
+        """P(X >= k) for X ~ Hypergeometric(N, K, d) and the derived bound on its error by mc_hypergeom.h's device build, a lane
+        per case, one launch (mc_hypergeom_tail_device, tests and tools/hypergeom_error.py) -> (tail float64 [n], err float64 [n]);
+        NaN where the arguments are out of range."""
+        N, K, d, k = (np.ascontiguousarray(a, dtype=np.int64) for a in (N, K, d, k))
+        if not (N.ndim == 1 and N.shape == K.shape == d.shape == k.shape):
+            raise ValueError('hypergeom_tail: four arrays of one length')
+        tail, err = np.zeros(len(N)), np.zeros(len(N))
+        check(lib().mc_hypergeom_tail_device(self._ctx, _ptr(N), _ptr(K), _ptr(d), _ptr(k), len(N), _ptr(tail), _ptr(err)))
+        return tail, err
+
+    @_serialized
     def gff_site_stats(self, arrays, frac):
         """fracLow, fracUp and 100 * mean of make_bed --gff --vo for every array of probabilities (frac: its entry's fraction) by
         mc_npsum.h's device build, a workgroup per array (mc_gff_site_stats_device, tests)
