@@ -779,6 +779,66 @@ int mc_hypergeom_tail_device(mc_ctx *ctx, const int64_t *N, const int64_t *K, co
                              double *tail, double *err);
 double mc_hypergeom_round4(double v);
 int mc_hypergeom_tie4(double v, double err);
+/* All 101 tails of one (N, K, d) in one call: x of 0 .. d passes c(x) = (100 x) / d + 1 of the thresholds j / 100, j = 0 .. 100
+ * (x / d >= j / 100), so with mass102[c] = P(c(X) = c), c = 1 .. 101 (mass102[0] = 0: 102 doubles a case),
+ * P(X >= k_min(d, j)) = sum over c > j of mass102[c].  *err: a DERIVED bound on the sum over c of |mass102[c] - exact|, which
+ * bounds the error of every such tail; 0, with one mass of exactly 1, where X takes one value (d = N, K = 0, K = N).  Bad arguments
+ * (as above): 1, NaN everywhere.  _many: `count` cases, 102 doubles each; _device: the device build, a lane per case. */
+#define MC_HYPERGEOM_BUCKETS 102
+int mc_hypergeom_masses(int64_t N, int64_t K, int64_t d, double *mass102, double *err);
+int mc_hypergeom_masses_many(const int64_t *N, const int64_t *K, const int64_t *d, int64_t count, double *mass102, double *err);
+int mc_hypergeom_masses_device(mc_ctx *ctx, const int64_t *N, const int64_t *K, const int64_t *d, int64_t count, double *mass102,
+                               double *err);
+
+/* ===== the evaluation file of mcaller_amd/evaluate.py, made on the GPU (csrc/eval/mc_evalcalls.hip) =====
+ * mc_eval_calls: the text of a `.diffs.<k>` file and of a labelled positions file -> the bytes evaluate.evaluate_calls gives for
+ * them: the ROC tables by read, by site at min_depth or more, and by site at each of the n_depths subsampled depths (1 .. 16 of
+ * them or none, each 1 .. 1024, strictly increasing: anything else is -12).  The integer tables are the host's bits; an expected
+ * ("site d") value is printed only where its DERIVED bound shows that no value within the bound rounds to another ten-thousandth.
+ * Otherwise, and wherever the host statement would raise or the device reader is not sure it reads what Python reads, the call
+ * declines -- *status = 1, mc_last_error says why (mc_eval_last_stats: which file, line and reason), nothing is handed out and
+ * the caller runs the host statement.  *out points at n_out bytes of pinned memory owned by the context: valid until the next
+ * mc_eval_calls on it or mc_eval_release.  Test knobs (environment): MCALLER_EVAL_HASH_MASK=<hex> is anded onto the 64-bit hash
+ * of a key; MCALLER_EVAL_TABLE_SLOTS=<n> fixes the number of slots of the truth table; MCALLER_EVAL_DEVICE_BYTES=<n> stands for
+ * the free device memory. */
+typedef struct mc_eval_params {
+    int64_t min_depth;             /* least depth of a site of the "site all" table */
+    int32_t n_depths;
+    int32_t depths[16];
+} mc_eval_params;
+typedef struct mc_eval_stats {
+    int64_t n_bytes, n_pos_bytes;  /* the two texts                                                       */
+    int64_t n_rows, n_pos_lines;   /* lines of the .diffs text, of the positions text                     */
+    int64_t n_kept, n_unlabelled, n_not_m;
+    int64_t n_sites, n_pos_sites, n_neg_sites;     /* truth keys with a kept row                          */
+    int64_t n_expect;              /* (site, depth) pairs the expectation ran on                          */
+    int64_t decline_line;          /* 0-based line the decline names, -1: none                            */
+    int64_t longest_probe;         /* slots a row's look-up read at the most                              */
+    int64_t table_slots;
+    int64_t kernel_bytes;          /* device memory the call held                                         */
+    int32_t decline_reason;        /* 0: not declined; MC_EVAL_DECLINE_*                                  */
+    int32_t decline_file;          /* 0: the .diffs text; 1: the positions text                           */
+    double largest_bound;          /* the largest derived bound of a printed expected value (0: none)     */
+    double ms_read, ms_h2d, ms_truth, ms_rows, ms_expect, ms_finish, ms_d2h, ms_total;
+} mc_eval_stats;
+#define MC_EVAL_DECLINE_HIGH_BYTE     1   /* a byte >= 0x80 (either file)                                                   */
+#define MC_EVAL_DECLINE_CONTROL       2   /* a control byte other than tab and '\n' ('\r' too), or 0x7f                     */
+#define MC_EVAL_DECLINE_LONG_LINE     3   /* a line of more than 65535 bytes                                                */
+#define MC_EVAL_DECLINE_FIELDS        4   /* a .diffs line that is not eight tab-separated fields                           */
+#define MC_EVAL_DECLINE_CONTEXT       5   /* an empty context                                                               */
+#define MC_EVAL_DECLINE_POSITION      6   /* a position of a centre-M row that is not 1-18 decimal digits                   */
+#define MC_EVAL_DECLINE_PROBABILITY   7   /* a kept row's probability that mc_decimal.h declines, or one outside [0, 1]     */
+#define MC_EVAL_DECLINE_POS_TOKENS    8   /* a positions line of two or three tokens (the host's IndexError)                */
+#define MC_EVAL_DECLINE_POS_NUMBER    9   /* a positions line whose second token is not 1-18 decimal digits                 */
+#define MC_EVAL_DECLINE_TABLE         10  /* the truth table is full                                                        */
+#define MC_EVAL_DECLINE_MEMORY        11  /* the texts do not fit into free device memory beside their tables               */
+#define MC_EVAL_DECLINE_ROWS          12  /* 2^31 - 2 lines or more in a file                                               */
+#define MC_EVAL_DECLINE_DEPTH         13  /* a site of 2^31 rows or more                                                    */
+#define MC_EVAL_DECLINE_ROUNDING_TIE  14  /* an expected value whose bound reaches a tie of np.round(., 4)                  */
+int mc_eval_calls(mc_ctx *ctx, const mc_text_source *diffs, const mc_text_source *positions, const mc_eval_params *params,
+                  const char **out, int64_t *n_out, int32_t *status);
+int mc_eval_last_stats(mc_ctx *ctx, mc_eval_stats *out);
+int mc_eval_release(mc_ctx *ctx);
 
 /* ===== decimal text -> double, correctly rounded (mcaller_amd/csrc/mc_decimal.h: one header for the host and the device) =====
  * float(s) of a token [+-]? digits? ('.' digits?)? ([eE] [+-]? digits)? with at least one mantissa digit whose significand

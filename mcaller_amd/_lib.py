@@ -58,8 +58,11 @@ MotifParams = _S['mc_motif_params']
 MotifStats = _S['mc_motif_stats']
 MotifIupacStats = _S['mc_motif_iupac_stats']
 MotifIterStats = _S['mc_motif_iter_stats']
+EvalParams = _S['mc_eval_params']
+EvalStats = _S['mc_eval_stats']
 Params = _S['mc_params']
 
+EVAL_DECLINE = ABI.prefixed('MC_EVAL_DECLINE_')
 MOTIF_DECLINE = ABI.prefixed('MC_MOTIF_DECLINE_')
 CMP_DECLINE = ABI.prefixed('MC_CMP_DECLINE_')
 FASTQ_DECLINE = ABI.prefixed('MC_FASTQ_DECLINE_')
@@ -625,6 +628,26 @@ def hypergeom_tail(N, K, d, k):
     if rc:
         raise ValueError('mc_hypergeom_tail_many: %d' % rc)
     return tail, err
+
+
+def hypergeom_masses(N, K, d):
+    """The bucket masses behind all 101 tails of X ~ Hypergeometric(N, K, d) and the derived bound on their summed error, by
+    mc_hypergeom.h's host build: P(X >= k_min(d, j)) = mass[j + 1:].sum().  Scalars -> (status, mass float64 [102], err)
+    (mc_hypergeom_masses); three arrays of one length -> (mass float64 [n, 102], err float64 [n]), NaN where the arguments are out
+    of range (mc_hypergeom_masses_many)."""
+    B = _K['MC_HYPERGEOM_BUCKETS']
+    if np.ndim(N) == 0:
+        mass, e = np.zeros(B), C.c_double()
+        st = lib().mc_hypergeom_masses(int(N), int(K), int(d), mass.ctypes.data, C.byref(e))
+        return st, mass, e.value
+    N, K, d = (np.ascontiguousarray(a, dtype=np.int64) for a in (N, K, d))
+    if not (N.ndim == 1 and N.shape == K.shape == d.shape):
+        raise ValueError('hypergeom_masses: three arrays of one length')
+    mass, err = np.zeros((len(N), B)), np.zeros(len(N))
+    rc = lib().mc_hypergeom_masses_many(N.ctypes.data, K.ctypes.data, d.ctypes.data, len(N), mass.ctypes.data, err.ctypes.data)
+    if rc:
+        raise ValueError('mc_hypergeom_masses_many: %d' % rc)
+    return mass, err
 
 
 def hypergeom_round4(v):

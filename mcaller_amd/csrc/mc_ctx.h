@@ -325,6 +325,10 @@ struct mc_ctx {
     Pinned fq_pool, fq_off, fq_mean;
     size_t fq_pool_cap = 0, fq_off_cap = 0, fq_mean_cap = 0;
     mc_fastq_quality_stats fq_stats = {};
+    // ... the evaluation file of a .diffs file against labelled positions (eval/mc_evalcalls.hip)
+    Pinned eval_out;
+    size_t eval_out_cap = 0;
+    mc_eval_stats eval_stats = {};
     // ... the rows of two --vo BED files compared per site (compare/mc_bedcompare.hip)
     Pinned cmp_out;
     size_t cmp_out_cap = 0;

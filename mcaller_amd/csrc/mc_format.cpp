@@ -657,6 +657,16 @@ extern "C" int mc_hypergeom_tail_many(const int64_t *N, const int64_t *K, const 
     for (int64_t i = 0; i < count; ++i) (void)hg_tail(N[i], K[i], d[i], k[i], &tail[i], &err[i]);
     return 0;
 }
+// the bucket masses behind all 101 tails of one (N, K, d): mass102[0 .. 101], *err the bound on their summed error
+extern "C" int mc_hypergeom_masses(int64_t N, int64_t K, int64_t d, double *mass102, double *err) {
+    if (!mass102 || !err) return -12;
+    return hg_masses(N, K, d, mass102, err);
+}
+extern "C" int mc_hypergeom_masses_many(const int64_t *N, const int64_t *K, const int64_t *d, int64_t count, double *mass102, double *err) {
+    if (count < 0 || (count > 0 && (!N || !K || !d || !mass102 || !err))) return -12;
+    for (int64_t i = 0; i < count; ++i) (void)hg_masses(N[i], K[i], d[i], mass102 + i * HG_BUCKETS, &err[i]);
+    return 0;
+}
 extern "C" double mc_hypergeom_round4(double v) { return hg_round4(v); }
 extern "C" int mc_hypergeom_tie4(double v, double err) { return hg_tie4(v, err) ? 1 : 0; }
 

@@ -826,6 +826,18 @@ class Device(object):
         return tail, err
 
     @_serialized
+    def hypergeom_masses(self, N, K, d):
+        """The bucket masses behind all 101 tails of X ~ Hypergeometric(N, K, d) and the derived bound on their summed error by
+        mc_hypergeom.h's device build, a lane per case, one launch (mc_hypergeom_masses_device, tests and tools/hypergeom_error.py)
+        -> (mass float64 [n, 102], err float64 [n]); NaN where the arguments are out of range."""
+        N, K, d = (np.ascontiguousarray(a, dtype=np.int64) for a in (N, K, d))
+        if not (N.ndim == 1 and N.shape == K.shape == d.shape):
+            raise ValueError('hypergeom_masses: three arrays of one length')
+        mass, err = np.zeros((len(N), _lib.ABI.constants['MC_HYPERGEOM_BUCKETS'])), np.zeros(len(N))
+        check(lib().mc_hypergeom_masses_device(self._ctx, _ptr(N), _ptr(K), _ptr(d), len(N), _ptr(mass), _ptr(err)))
+        return mass, err
+
+    @_serialized
     def gff_site_stats(self, arrays, frac):
         """fracLow, fracUp and 100 * mean of make_bed --gff --vo for every array of probabilities (frac: its entry's fraction) by
         mc_npsum.h's device build, a workgroup per array (mc_gff_site_stats_device, tests)
@@ -893,6 +905,39 @@ class Device(object):
     @_serialized
     def training_rows_release(self):
         check(lib().mc_train_rows_release(self._ctx))
+
+    # ---- the evaluation file of a .diffs file against labelled positions (csrc/eval/mc_evalcalls.hip) ----
+    @_serialized
+    def eval_calls(self, path=None, text=None, positions_path=None, positions_text=None, min_depth=15, depths=(1, 2, 5, 10, 15, 20, 30, 50)):
+        """The bytes evaluate.evaluate_calls gives for a `.diffs.<k>` file (`path`) or its text (`text`, bytes) against the labelled
+        positions (`positions_path` or `positions_text`), made on the GPU -> (bytes, None), or (None, reason) when the device
+        declines: the caller runs the host statement."""
+        if (path is None) == (text is None) or (positions_path is None) == (positions_text is None):
+            raise ValueError('eval_calls: a path or a text, and the positions as a path or a text')
+        depths = [int(d) for d in depths]
+        if len(depths) > 16:
+            raise ValueError('eval_calls: at most 16 depths')
+        prm = _lib.EvalParams()
+        prm.min_depth, prm.n_depths = max(-2 ** 62, min(2 ** 62, int(min_depth))), len(depths)
+        for i, d in enumerate(depths):
+            prm.depths[i] = max(-1, min(2 ** 30, d))
+        out, n_out, status = C.c_void_p(), C.c_int64(), C.c_int32()
+        (src, keep), (pos, keep_pos) = _source(path, text), _source(positions_path, positions_text)
+        check(lib().mc_eval_calls(self._ctx, src, pos, C.byref(prm), C.byref(out), C.byref(n_out), C.byref(status)))
+        del keep, keep_pos
+        if status.value != 0:
+            return None, last_error()
+        return (C.string_at(out.value, n_out.value) if n_out.value else b''), None
+
+    @_serialized
+    def eval_calls_last_stats(self):
+        """Figures of the last eval_calls: lines, kept / unlabelled / non-M rows, sites, (site, depth) pairs, the longest probe chain,
+        the largest derived bound of a printed value, the decline (file, line, reason), milliseconds."""
+        return self._last_stats(lib().mc_eval_last_stats, _lib.EvalStats)
+
+    @_serialized
+    def eval_calls_release(self):
+        check(lib().mc_eval_release(self._ctx))
 
     # ---- the read qualities of a FASTQ file (csrc/fastq/mc_fastqual.hip) ----
     @_serialized

@@ -2,7 +2,7 @@
 """How good are the calls of a `.diffs.<k>` file, and which `-d` / `-t` should make_bed run with?  ROC tables by read, by site
 and by site at subsampled depth, against a labelled positions file:
 
-    python -m mcaller_amd.evaluate -f reads.eventalign.diffs.6 -p labelled_positions.txt [-d 15] [--depths 1,2,5,10,15,20,30,50] [-o OUT]
+    python -m mcaller_amd.evaluate -f reads.eventalign.diffs.6 -p labelled_positions.txt [-d 15] [--depths 1,2,5,10,15,20,30,50] [-o OUT] [--device]
 
 The reference prints cross-validation accuracy at --train and nothing else; the curves of the paper behind it (per read, per
 site, per site at subsampled coverage) have no code there.  This module is their definition here: `evaluate_calls` is the host
@@ -39,9 +39,14 @@ Bytes.  '#level\\tdepth\\tthreshold\\tn_pos\\tn_neg\\ttp\\tfp\\ttpr\\tfpr', then
 'site\\t<d>\\t..' in the order of --depths (tp and fp are '-' there), the threshold as repr(j / 100); then 'auc\\tread\\t-\\t<v>',
 'auc\\tsite\\tall\\t<v>', 'auc\\tsite\\t<d>\\t<v>'.
 
-`last_eval` records what the last call did, in the style of make_bed.last_summary.  The tables are made on the host.  What a GPU
-path of the "site d" tables needs numerically -- the hypergeometric tail with a derived error bound, np.round(., 4) restated, the
-tie test -- is csrc/mc_hypergeom.h, built for the host and the device (_lib.hypergeom_tail, Device.hypergeom_tail)."""
+`last_eval` records what the last call did, in the style of make_bed.last_summary.  Without --device the tables are made on the host
+and no GPU is touched.  --device makes the file on the GPU (csrc/eval/mc_evalcalls.hip; evaluate_calls_device): the text of both
+files -> kernels -> these bytes, or a decline -- wherever the host would raise, wherever the device reader is not sure it reads
+what Python reads, and wherever an expected value's DERIVED error bound reaches a tie of np.round(., 4) -- which main says on stderr
+before it runs the host statement (last_eval['by'] is 'device' or 'host', last_eval['reason'] the decline).  The arithmetic of the
+"site d" tables on the device is csrc/mc_hypergeom.h, built for the host and the device: all 101 tails of a (N, K, d) from one pair of
+walks with one bound (_lib.hypergeom_masses, Device.hypergeom_masses), the single tail (_lib.hypergeom_tail), np.round(., 4)
+restated, the tie test."""
 import argparse
 import io
 import math
@@ -222,6 +227,26 @@ def evaluate_calls(diffs, positions, min_depth=15, depths=DEFAULT_DEPTHS):
     return ('\n'.join(lines + aucs) + '\n').encode('ascii')
 
 
+def evaluate_calls_device(diffs, positions, min_depth=15, depths=DEFAULT_DEPTHS, device=None):
+    """evaluate_calls on the GPU (csrc/eval/mc_evalcalls.hip; `device`: a Device, default the process's): the same bytes, or None
+    when the device declines -- last_eval['reason'] says why, and the caller runs evaluate_calls.  Fills last_eval from the
+    device's figures (by='device') when it served the call.  No GPU: the error of the device's creation, never a host run."""
+    from .device import get_device
+    depths = check_depths(depths)
+    dev = device if device is not None else get_device()
+    is_text = lambda s: isinstance(s, (bytes, bytearray, memoryview))
+    kw = dict(text=bytes(diffs)) if is_text(diffs) else dict(path=diffs)
+    kw.update(dict(positions_text=bytes(positions)) if is_text(positions) else dict(positions_path=positions))
+    data, reason = dev.eval_calls(min_depth=int(min_depth), depths=depths, **kw)
+    if data is None:
+        last_eval.update(by=None, reason=reason)
+        return None
+    s = dev.eval_calls_last_stats()
+    last_eval.update(by='device', reason=None, n_rows=int(s['n_rows']), n_kept=int(s['n_kept']), n_unlabelled=int(s['n_unlabelled']),
+                     n_not_m=int(s['n_not_m']), n_sites=int(s['n_sites']), n_pos_sites=int(s['n_pos_sites']), n_neg_sites=int(s['n_neg_sites']))
+    return data
+
+
 def default_output(diffs_path):
     return diffs_path.split('.')[0] + '.evaluation.tsv'
 
@@ -233,10 +258,17 @@ def main(argv=None):
     ap.add_argument('-d', '--min_read_depth', type=int, default=15, help='least depth of a site of the "site all" table (default 15)')
     ap.add_argument('--depths', default=','.join(str(d) for d in DEFAULT_DEPTHS), help='subsampled depths, comma-separated, increasing')
     ap.add_argument('-o', '--output', default=None, help='output file (default: <-f up to its first dot>.evaluation.tsv)')
+    ap.add_argument('--device', action='store_true', help='make the file on the GPU; where the device declines, say so and run the host statement')
     args = ap.parse_args(argv)
     depths = check_depths(int(x) for x in args.depths.split(',') if x.strip())
     out = args.output or default_output(args.file)
-    data = evaluate_calls(args.file, args.positions, args.min_read_depth, depths)
+    data = evaluate_calls_device(args.file, args.positions, args.min_read_depth, depths) if args.device else None
+    if data is None:
+        reason = last_eval['reason'] if args.device else None
+        if args.device:
+            print('%s: %s; the host statement makes the file' % (args.file, reason), file=sys.stderr)
+        data = evaluate_calls(args.file, args.positions, args.min_read_depth, depths)
+        last_eval['reason'] = reason
     with open(out, 'wb') as fh:
         fh.write(data)
     print('%s: %d rows, %d kept (%d unlabelled, %d without a centre M), %d sites (%d positive, %d negative)' % (

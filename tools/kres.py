@@ -9,7 +9,7 @@ import sys
 import tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-UNITS = ['mc_k0', 'mc_scan', 'mc_emit', 'mc_fused', 'mc_literal', 'mc_classify', 'mc_train', 'mc_forest_fit', 'mc_svm_fit', 'mc_simple_fit', 'mc_stream', 'mc_tables', 'bed/mc_bedsum', 'train/mc_trainrows', 'merge/mc_rowmerge', 'fastq/mc_fastqual', 'compare/mc_bedcompare', 'motifs/mc_motifscan']
+UNITS = ['mc_k0', 'mc_scan', 'mc_emit', 'mc_fused', 'mc_literal', 'mc_classify', 'mc_train', 'mc_forest_fit', 'mc_svm_fit', 'mc_simple_fit', 'mc_stream', 'mc_tables', 'bed/mc_bedsum', 'train/mc_trainrows', 'merge/mc_rowmerge', 'fastq/mc_fastqual', 'compare/mc_bedcompare', 'motifs/mc_motifscan', 'eval/mc_evalcalls']
 
 
 def report(src_dir, unit):
