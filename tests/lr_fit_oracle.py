@@ -15,7 +15,21 @@ of scikit-learn 1.7's sklearn/svm/src/liblinear/linear.cpp.
   draw) from a generator seeded once per fit with the 31-bit seed -- train_model.MT19937Draws, shared with libsvm's Platt shuffle.
 * Sums run over the rows one after another as liblinear's column walk does (dense X with its zeros skipped: the same numbers),
   np.cumsum(v)[-1]; exp and log are the C library's (math.exp, math.log).
+
+For the case tables (tests/lr_fit_cases.py) `solve` can also say which way it went, add in the kernel's order, and go wrong on purpose;
+with the defaults none of this changes a returned bit:
+* trace=: a dict that gets 'iters', one Counter per Newton iteration, and 'total', their sum.  Keys: outer_shrink (and
+  outer_shrink_bias when the column shrunk is the bias), inner_shrink, reactivation, z_clip_pos / z_clip_neg (z cut to
+  +10 / -10), z_skip (|z| < 1e-12), sweeps, inner_cap (1000 sweeps), halvings,
+  ls_exhausted, nonfinite (an inf or NaN among cond, exp_wTx_new, Grad or Hdiag); 'total' also counts qp_no_change_stop and
+  gnorm_stop, the two ways out of the Newton loop before max_iter.
+* order='device': every sum over the rows in k7_lr_fit's order (csrc/mc_simple_fit.hip: reduce_cols, block_sum, wave_sum) -- lane tid
+  of BT = 512 adds its rows t = tid + BT r in order from 0.0 (a masked row adds nothing), v += shfl_xor(v, o) for o = 32, 16, .. 1 over
+  the 64 lanes of a wave, then the 8 waves' sums in order, from NU for Hdiag and from 0.0 otherwise, the block's sum added last to
+  what liblinear starts its sum with.  It shows that a case does not hang on the order of addition; it is not a yardstick.
+* mutate=: one named single-branch defect (MUTANTS), to show that a case can tell a right kernel from a wrong one.
 """
+import collections
 import math
 
 import numpy as np
@@ -32,7 +46,50 @@ def _seq(first, terms):
 
 
 def _exp(v):
-    return np.array([math.exp(a) for a in v])
+    out = np.empty(len(v))
+    for k, a in enumerate(v):
+        try:
+            out[k] = math.exp(a)
+        except OverflowError:                                          # (the C library's exp: inf, no exception)
+            out[k] = math.inf
+    return out
+
+
+def _log(a):
+    if a != a:
+        return math.nan
+    if a <= 0:
+        return -math.inf if a == 0 else math.nan
+    return math.log(a)
+
+
+MUTANTS = ('no_negsum_halving', 'no_xTd_halving', 'no_z_clip', 'no_reactivation', 'no_inner_shrink', 'no_outer_shrink',
+           'no_recompute_after_exhaust', 'inner_eps_not_quartered')
+_LANE = np.arange(64)
+
+
+def device_sum(terms, bt=512):
+    """The block's sum of one term per row in the kernels' order: a lane's rows in order, a butterfly over the wave, the waves'
+    sums returned for the caller to fold (k7_lr_fit, k7_nb_fit: bt = 512; k6_svm_sigmoid: bt = 1024)."""
+    l = len(terms)
+    rounds = max(1, -(-l // bt))
+    pad = np.zeros(rounds * bt)
+    pad[:l] = terms
+    v = pad[:bt].copy()
+    for r in range(1, rounds):
+        v = v + pad[r * bt:(r + 1) * bt]
+    v = v.reshape(bt // 64, 64)
+    for o in (32, 16, 8, 4, 2, 1):
+        v = v + v[:, _LANE ^ o]
+    return v[:, 0]
+
+
+def _dev(first, terms, fold_from_first=False):
+    waves = device_sum(terms)
+    s = first if fold_from_first else 0.0
+    for w in waves:
+        s = s + w
+    return float(s if fold_from_first else first + s)
 
 
 def liblinear_order(y):
@@ -41,9 +98,17 @@ def liblinear_order(y):
     return np.concatenate([np.nonzero(y == 0)[0], np.nonzero(y == 1)[0]])
 
 
-def solve(X, y, seed, C=1.0, tol=1e-4, max_iter=100):
+def solve(X, y, seed, C=1.0, tol=1e-4, max_iter=100, trace=None, order=None, mutate=None):
     """solve_l1r_lr on rows X (already in liblinear's order, y in {0, 1}: 0 first) -> dict(w: d+1 weights, the last the bias;
-    n_iter: Newton iterations; status: 1 when max_iter was reached)."""
+    n_iter: Newton iterations; status: 1 when max_iter was reached).  trace, order, mutate: the module docstring."""
+    if order not in (None, 'device') or mutate not in (None,) + MUTANTS:
+        raise ValueError('solve: order is None or \'device\', mutate one of MUTANTS')
+    dev = order == 'device'
+    iters = []
+    total = collections.Counter()
+    if trace is not None:
+        trace['iters'], trace['total'] = iters, total
+    seen = collections.Counter()
     X = np.asarray(X, dtype=np.float64)
     y = np.asarray(y)
     l, d = X.shape
@@ -62,7 +127,10 @@ def solve(X, y, seed, C=1.0, tol=1e-4, max_iter=100):
     wpd = np.zeros(n)
     index = list(range(n))
     w_norm = 0.0
-    xjneg_sum = np.array([_seq(0.0, (Cr * cols[j])[neg]) for j in range(n)])      # :1821-1838
+    if dev:
+        xjneg_sum = np.array([_dev(0.0, np.where(neg, Cr * cols[j], 0.0)) for j in range(n)])
+    else:
+        xjneg_sum = np.array([_seq(0.0, (Cr * cols[j])[neg]) for j in range(n)])  # :1821-1838
     exp_wTx = np.ones(l)                                               # exp(0)  (:1839-1845)
     tau_tmp = 1.0 / (1.0 + exp_wTx)
     tau = Cr * tau_tmp
@@ -73,14 +141,17 @@ def solve(X, y, seed, C=1.0, tol=1e-4, max_iter=100):
     xTd = np.zeros(l)
 
     while newton_iter < max_iter:                                      # :1847
+        seen = collections.Counter()
         Gmax_new, Gnorm1_new = 0.0, 0.0
         active_size = n
         s = 0
         while s < active_size:                                         # :1853-1895
             j = index[s]
-            Hdiag[j] = _seq(NU, cols[j] * cols[j] * D)
-            tmp = _seq(0.0, cols[j] * tau)
+            Hdiag[j] = _dev(NU, cols[j] * cols[j] * D, True) if dev else _seq(NU, cols[j] * cols[j] * D)
+            tmp = _dev(0.0, cols[j] * tau) if dev else _seq(0.0, cols[j] * tau)
             Grad[j] = -tmp + xjneg_sum[j]
+            if not (math.isfinite(Hdiag[j]) and math.isfinite(Grad[j])):
+                seen['nonfinite'] += 1
             Gp, Gn = Grad[j] + 1, Grad[j] - 1
             violation = 0.0
             if w[j] == 0:
@@ -88,7 +159,10 @@ def solve(X, y, seed, C=1.0, tol=1e-4, max_iter=100):
                     violation = -Gp
                 elif Gn > 0:
                     violation = Gn
-                elif Gp > Gmax_old / l and Gn < -Gmax_old / l:         # outer-level shrinking
+                elif Gp > Gmax_old / l and Gn < -Gmax_old / l and mutate != 'no_outer_shrink':   # outer-level shrinking
+                    seen['outer_shrink'] += 1
+                    if j == n - 1:
+                        seen['outer_shrink_bias'] += 1
                     active_size -= 1
                     index[s], index[active_size] = index[active_size], index[s]
                     continue
@@ -102,6 +176,7 @@ def solve(X, y, seed, C=1.0, tol=1e-4, max_iter=100):
         if newton_iter == 0:
             Gnorm1_init = Gnorm1_new
         if Gnorm1_new <= eps * Gnorm1_init or QP_no_change >= 10:     # :1902
+            total['gnorm_stop' if Gnorm1_new <= eps * Gnorm1_init else 'qp_no_change_stop'] += 1
             break
         QP_no_change += 1
 
@@ -118,7 +193,8 @@ def solve(X, y, seed, C=1.0, tol=1e-4, max_iter=100):
             while s < QP_active_size:
                 j = index[s]
                 H = Hdiag[j]
-                G = _seq(Grad[j] + (wpd[j] - w[j]) * NU, cols[j] * D * xTd)
+                G0 = Grad[j] + (wpd[j] - w[j]) * NU
+                G = _dev(G0, cols[j] * D * xTd) if dev else _seq(G0, cols[j] * D * xTd)
                 Gp, Gn = G + 1, G - 1
                 violation = 0.0
                 if wpd[j] == 0:
@@ -126,7 +202,8 @@ def solve(X, y, seed, C=1.0, tol=1e-4, max_iter=100):
                         violation = -Gp
                     elif Gn > 0:
                         violation = Gn
-                    elif Gp > QP_Gmax_old / l and Gn < -QP_Gmax_old / l:   # inner-level shrinking
+                    elif Gp > QP_Gmax_old / l and Gn < -QP_Gmax_old / l and mutate != 'no_inner_shrink':   # inner-level shrinking
+                        seen['inner_shrink'] += 1
                         QP_active_size -= 1
                         index[s], index[QP_active_size] = index[QP_active_size], index[s]
                         continue
@@ -141,9 +218,13 @@ def solve(X, y, seed, C=1.0, tol=1e-4, max_iter=100):
                 else:
                     z = -wpd[j]
                 if abs(z) < 1.0e-12:
+                    seen['z_skip'] += 1
                     s += 1
                     continue
-                z = min(max(z, -10.0), 10.0)
+                if z > 10.0 or z < -10.0:
+                    seen['z_clip_pos' if z > 0 else 'z_clip_neg'] += 1
+                if mutate != 'no_z_clip':
+                    z = min(max(z, -10.0), 10.0)
                 QP_no_change = 0
                 QP_Gmax_new = max(QP_Gmax_new, violation)
                 QP_Gnorm1_new += violation
@@ -151,21 +232,25 @@ def solve(X, y, seed, C=1.0, tol=1e-4, max_iter=100):
                 xTd += cols[j] * z
                 s += 1
             it += 1
+            seen['sweeps'] += 1
             if QP_Gnorm1_new <= inner_eps * Gnorm1_init:
-                if QP_active_size == active_size:
+                if QP_active_size == active_size or mutate == 'no_reactivation':
                     break
+                seen['reactivation'] += 1
                 QP_active_size = active_size                           # active set reactivation
                 QP_Gmax_old = math.inf
                 continue
             QP_Gmax_old = QP_Gmax_new
 
+        if it >= MAX_INNER:
+            seen['inner_cap'] += 1
         delta, w_norm_new = 0.0, 0.0                                   # :2012-2025
         for j in range(n):
             delta += Grad[j] * (wpd[j] - w[j])
             if wpd[j] != 0:
                 w_norm_new += abs(wpd[j])
         delta += w_norm_new - w_norm
-        negsum_xTd = _seq(0.0, (Cr * xTd)[neg])
+        negsum_xTd = _dev(0.0, np.where(neg, Cr * xTd, 0.0)) if dev else _seq(0.0, (Cr * xTd)[neg])
 
         num_linesearch = 0
         while num_linesearch < MAX_LINESEARCH:                         # :2028-2067
@@ -173,7 +258,10 @@ def solve(X, y, seed, C=1.0, tol=1e-4, max_iter=100):
             exp_xTd = _exp(xTd)
             exp_wTx_new = exp_wTx * exp_xTd
             r = (1 + exp_wTx_new) / (exp_xTd + exp_wTx_new)
-            cond = _seq(cond, Cr * np.array([math.log(a) for a in r]))
+            logs = Cr * np.array([_log(a) for a in r])
+            cond = _dev(cond, logs) if dev else _seq(cond, logs)
+            if not (math.isfinite(cond) and np.isfinite(exp_wTx_new).all()):
+                seen['nonfinite'] += 1
             if cond <= 0:
                 w_norm = w_norm_new
                 w[:] = wpd
@@ -188,17 +276,24 @@ def solve(X, y, seed, C=1.0, tol=1e-4, max_iter=100):
                 if wpd[j] != 0:
                     w_norm_new += abs(wpd[j])
             delta *= 0.5
-            negsum_xTd *= 0.5
-            xTd *= 0.5
+            if mutate != 'no_negsum_halving':
+                negsum_xTd *= 0.5
+            if mutate != 'no_xTd_halving':
+                xTd *= 0.5
             num_linesearch += 1
-        if num_linesearch >= MAX_LINESEARCH:                           # :2070-2088 (tau and D stay)
+        seen['halvings'] += num_linesearch
+        if num_linesearch >= MAX_LINESEARCH:
+            seen['ls_exhausted'] += 1
+        if num_linesearch >= MAX_LINESEARCH and mutate != 'no_recompute_after_exhaust':   # :2070-2088 (tau and D stay)
             acc = np.zeros(l)
             for i in range(n):
                 if w[i] != 0:
                     acc += w[i] * cols[i]
             exp_wTx = _exp(acc)
-        if it == 1:
+        if it == 1 and mutate != 'inner_eps_not_quartered':
             inner_eps *= 0.25
+        iters.append(seen)
+        total.update(seen)
         newton_iter += 1
         Gmax_old = Gmax_new
     return dict(w=w.copy(), n_iter=newton_iter, status=1 if newton_iter >= max_iter else 0)
@@ -245,7 +340,8 @@ def decision(X, w):
 
 
 def solve_job(X, y, train, val, seed, **kw):
-    """A device job: fit on rows `train` (any order: they are put in liblinear's), score rows `val` (class 1 iff dec > 0)."""
+    """A device job: fit on rows `train` (any order: they are put in liblinear's), score rows `val` (class 1 iff dec > 0).
+    (Keyword arguments go to solve.)"""
     train = np.asarray(train)
     tr = train[liblinear_order(y[train])]
     out = solve(X[tr], y[tr], seed, **kw)

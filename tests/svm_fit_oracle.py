@@ -57,21 +57,73 @@ def kernel_rows(A, B, gamma):
     return np.exp(-gamma * d2)
 
 
-def smo(X, ys, gamma, C=1.0, eps=1e-3, max_iter=None):
-    """One solve on the rows X (in solve order) with labels ys in {+1, -1}.  -> dict(alpha, rho, n_iter, status)."""
+CLIPS = ('diff_pos_aj_below_0', 'diff_neg_ai_below_0', 'diff_pos_ai_above_C', 'diff_neg_aj_above_C',
+         'sum_big_ai_above_C', 'sum_small_aj_below_0', 'sum_big_aj_above_C', 'sum_small_ai_below_0')
+SMO_MUTANTS = ('ties_to_highest_index',) + tuple('skip_' + c for c in CLIPS) + ('tau_ignored', 'rho_midpoint_as_mean')
+
+
+def _ulp_signs(d2, seed):
+    """+1 / -1 per entry, a fixed function of the entry's bits and the seed (an exp that is one ulp off is off the same way
+    wherever its argument is the same: equal squared distances keep equal kernel values)."""
+    h = np.ascontiguousarray(d2).view(np.uint64) ^ np.uint64(0x9E3779B97F4A7C15 * (2 * int(seed) + 1) % 2 ** 64)
+    h = h * np.uint64(0xBF58476D1CE4E5B9)
+    h ^= h >> np.uint64(31)
+    h = h * np.uint64(0x94D049BB133111EB)
+    return np.where((h >> np.uint64(40)) & np.uint64(1), 1.0, -1.0)
+
+
+def _first_max(v, last=False):
+    return len(v) - 1 - int(np.argmax(v[::-1])) if last else int(np.argmax(v))
+
+
+def _gap(v, k):
+    """(v[k] minus the largest other entry, that entry's index): (inf, -1) without a rival."""
+    rest = v.copy()
+    rest[k] = -np.inf
+    r = int(np.argmax(rest))
+    if rest[r] == -np.inf:
+        return math.inf, -1
+    return float(v[k] - rest[r]), r
+
+
+def smo(X, ys, gamma, C=1.0, eps=1e-3, max_iter=None, trace=None, mutate=None, wobble=None):
+    """One solve on the rows X (in solve order) with labels ys in {+1, -1}.  -> dict(alpha, rho, n_iter, status).
+    trace=: a dict that gets a Counter 'branches' -- the eight clipping branches (CLIPS, named by libsvm's tests: the sign of
+    diff = ai - aj for unequal labels, sum = ai + aj against C for equal ones, then the bound crossed), tau_select (a candidate j
+    with quad <= 0, an exact duplicate of row i) and tau_update, rho_mean / rho_midpoint, and the loop's three exits exit_max_iter,
+    exit_no_up (I_up empty) and exit_converged (Gmax + Gmax2 < eps, or no candidate) -- and the lists 'gap_i' and 'gap_j': per
+    selection the chosen candidate's value minus the runner-up's (0: an exact tie, won by the lowest index), and the list 'picks' of
+    (i, runner-up of i, j, runner-up of j, Gmax = -y_i G_i) per selection (-1: no rival).
+    mutate=: one of SMO_MUTANTS, a defect on purpose.  wobble=: a seed; every kernel value other than an exact 1 is multiplied by
+    1 + 2^-52 or 1 - 2^-52 (_ulp_signs): an exp one ulp off.  With the defaults no returned bit changes."""
+    if mutate not in (None,) + SMO_MUTANTS:
+        raise ValueError('smo: mutate is one of SMO_MUTANTS')
+    import collections
     X = np.asarray(X, dtype=np.float64)
     ys = np.asarray(ys, dtype=np.float64)
     l = len(ys)
     if max_iter is None:
         max_iter = max(10 ** 7, 100 * l)
     cols = [np.ascontiguousarray(X[:, f]) for f in range(X.shape[1])]
+    seen = collections.Counter()
+    gap_i, gap_j, picks = [], [], []
+    last = mutate == 'ties_to_highest_index'
 
     def row(i):
         d2 = np.zeros(l)
         for c in cols:
             t = c[i] - c
             d2 = d2 + t * t
-        return np.exp(-gamma * d2)
+        k = np.exp(-gamma * d2)
+        if wobble is not None:
+            k = np.where(d2 == 0, k, k * (1.0 + _ulp_signs(d2, wobble) * 2.0 ** -52))
+        return k
+
+    def clip(name, test):
+        """libsvm's `if (test)` of the branch `name`: counted, and not taken by the mutant that skips it."""
+        if test:
+            seen[name] += 1
+        return test and mutate != 'skip_' + name
 
     alpha = np.zeros(l)
     G = -np.ones(l)
@@ -80,12 +132,14 @@ def smo(X, ys, gamma, C=1.0, eps=1e-3, max_iter=None):
     while True:
         if it >= max_iter:
             status = 1
+            seen['exit_max_iter'] += 1
             break
         up = np.where(pos, alpha < C, alpha > 0)
         if not up.any():
+            seen['exit_no_up'] += 1
             break
         v = np.where(up, -ys * G, -np.inf)
-        i = int(np.argmax(v))                                 # (the first of equals)
+        i = _first_max(v, last)                               # (the first of equals)
         Gmax = v[i]
         Ki = row(i)
         low = np.where(pos, alpha > 0, alpha < C)
@@ -94,10 +148,22 @@ def smo(X, ys, gamma, C=1.0, eps=1e-3, max_iter=None):
         gd = Gmax + yg
         cand = low & (gd > 0)
         quad = 1.0 + 1.0 - 2.0 * Ki
-        obj = -(gd * gd) / np.where(quad > 0, quad, TAU)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            obj = -(gd * gd) / (quad if mutate == 'tau_ignored' else np.where(quad > 0, quad, TAU))
         if Gmax + Gmax2 < eps or not cand.any():
+            seen['exit_converged'] += 1
             break
-        j = int(np.argmax(np.where(cand, -obj, -np.inf)))
+        score = np.where(cand, -obj, -np.inf)
+        if mutate == 'tau_ignored':
+            score = np.where(np.isnan(score), -np.inf, score)
+        j = _first_max(score, last)
+        if trace is not None:
+            (gi, ri), (gj, rj) = _gap(v, i), _gap(score, j)
+            gap_i.append(gi)
+            gap_j.append(gj)
+            picks.append((i, ri, j, rj, float(Gmax)))
+            if (cand & (quad <= 0)).any():
+                seen['tau_select'] += 1
         it += 1
         yi, yj = ys[i], ys[j]
         ai0, aj0, Gi, Gj = alpha[i], alpha[j], G[i], G[j]
@@ -105,43 +171,57 @@ def smo(X, ys, gamma, C=1.0, eps=1e-3, max_iter=None):
         ai, aj = ai0, aj0
         if yi != yj:
             q = 1.0 + 1.0 + 2.0 * Qij
-            q = q if q > 0 else TAU
-            delta = (-Gi - Gj) / q
+            if q <= 0:
+                seen['tau_update'] += 1
+            q = q if q > 0 or mutate == 'tau_ignored' else TAU
+            with np.errstate(divide='ignore', invalid='ignore'):
+                delta = np.float64(-Gi - Gj) / q
             diff = ai - aj
             ai += delta
             aj += delta
             if diff > 0:
-                if aj < 0:
+                if clip(CLIPS[0], aj < 0):
                     aj, ai = 0.0, diff
-            elif ai < 0:
+            elif clip(CLIPS[1], ai < 0):
                 ai, aj = 0.0, -diff
             if diff > C - C:
-                if ai > C:
+                if clip(CLIPS[2], ai > C):
                     ai, aj = C, C - diff
-            elif aj > C:
+            elif clip(CLIPS[3], aj > C):
                 aj, ai = C, C + diff
         else:
             q = 1.0 + 1.0 - 2.0 * Qij
-            q = q if q > 0 else TAU
-            delta = (Gi - Gj) / q
+            if q <= 0:
+                seen['tau_update'] += 1
+            q = q if q > 0 or mutate == 'tau_ignored' else TAU
+            with np.errstate(divide='ignore', invalid='ignore'):
+                delta = np.float64(Gi - Gj) / q
             s = ai + aj
             ai -= delta
             aj += delta
             if s > C:
-                if ai > C:
+                if clip(CLIPS[4], ai > C):
                     ai, aj = C, s - C
-            elif aj < 0:
+            elif clip(CLIPS[5], aj < 0):
                 aj, ai = 0.0, s
             if s > C:
-                if aj > C:
+                if clip(CLIPS[6], aj > C):
                     aj, ai = C, s - C
-            elif ai < 0:
+            elif clip(CLIPS[7], ai < 0):
                 ai, aj = 0.0, s
         dai, daj = ai - ai0, aj - aj0
         Kj = row(j)
         G = G + (((yi * ys) * Ki) * dai + ((yj * ys) * Kj) * daj)
         alpha[i], alpha[j] = ai, aj
-    return dict(alpha=alpha, rho=rho_of(alpha, ys, G, C), n_iter=it, status=status)
+    free = (alpha > 0) & (alpha < C)
+    seen['rho_mean' if free.any() else 'rho_midpoint'] += 1
+    if mutate == 'rho_midpoint_as_mean' and not free.any():
+        rho = float((ys * G).mean())
+    else:
+        rho = rho_of(alpha, ys, G, C)
+    if trace is not None:
+        trace['branches'], trace['gap_i'], trace['gap_j'], trace['picks'] = seen, gap_i, gap_j, picks
+    return dict(alpha=alpha, rho=rho, n_iter=it, status=status)
 
 
 def rho_of(alpha, ys, G, C=1.0):
@@ -187,8 +267,19 @@ def dual_objective(X, coef, gamma, chunk=2048):
     return 0.5 * q - float(np.abs(c).sum())
 
 
-def sigmoid_train(dec, labels):
-    """libsvm's sigmoid_train, sequential Python floats.  labels: +1 / -1 (> 0 counts as prior1).  -> (A, B)."""
+SIGMOID_MUTANTS = ('no_backtracking', 'targets_swapped')
+
+
+def sigmoid_train(dec, labels, trace=None, order=None, mutate=None):
+    """libsvm's sigmoid_train, sequential Python floats.  labels: +1 / -1 (> 0 counts as prior1).  -> (A, B).
+    trace=: a dict that gets 'halvings' (a list: the halvings of every Newton iteration that searched) and 'exit', one of
+    'gradient_at_entry' (the gradient below eps before any step: the starting point is returned), 'gradient', 'min_step' and
+    'max_iter'.  order='device': the sums in k6_svm_sigmoid's order (csrc/mc_svm_fit.hip: `reduce`) -- lane tid of ST = 1024 adds
+    its values k = tid + ST r in order from 0.0, s += shfl_xor(s, o) for o = 32 .. 1 over a wave, the 16 waves' sums in order from
+    0.0, and sigma added to h11 and h22 after the sum; it shows that a case does not hang on the order, it is not a yardstick.
+    mutate=: one of SIGMOID_MUTANTS, a defect on purpose.  With the defaults no returned bit changes."""
+    if order not in (None, 'device') or mutate not in (None,) + SIGMOID_MUTANTS:
+        raise ValueError("sigmoid_train: order is None or 'device', mutate one of SIGMOID_MUTANTS")
     dec = [float(v) for v in dec]
     lab = [float(v) for v in labels]
     l = len(dec)
@@ -197,22 +288,37 @@ def sigmoid_train(dec, labels):
     max_iter, min_step, sigma, eps = 100, 1e-10, 1e-12, 1e-5
     hiTarget = (prior1 + 1.0) / (prior1 + 2.0)
     loTarget = 1 / (prior0 + 2.0)
-    t = [hiTarget if v > 0 else loTarget for v in lab]
+    if mutate == 'targets_swapped':
+        t = [loTarget if v > 0 else hiTarget for v in lab]
+    else:
+        t = [hiTarget if v > 0 else loTarget for v in lab]
     A, B = 0.0, math.log((prior0 + 1.0) / (prior1 + 1.0))
+    halvings, leave = [], 'max_iter'
+
+    def total(start, terms):
+        if order == 'device':
+            from tests.lr_fit_oracle import device_sum
+            s = 0.0
+            for w in device_sum(np.asarray(terms, dtype=np.float64), 1024):
+                s = s + float(w)
+            return start + s
+        for v in terms:
+            start += v
+        return start
 
     def fun(A, B):
-        f = 0.0
+        terms = []
         for i in range(l):
             fApB = dec[i] * A + B
             if fApB >= 0:
-                f += t[i] * fApB + math.log(1 + math.exp(-fApB))
+                terms.append(t[i] * fApB + math.log(1 + math.exp(-fApB)))
             else:
-                f += (t[i] - 1) * fApB + math.log(1 + math.exp(fApB))
-        return f
+                terms.append((t[i] - 1) * fApB + math.log(1 + math.exp(fApB)))
+        return total(0.0, terms)
 
     fval = fun(A, B)
-    for _ in range(max_iter):
-        h11, h22, h21, g1, g2 = sigma, sigma, 0.0, 0.0, 0.0
+    for it in range(max_iter):
+        sums = [[], [], [], [], []]
         for i in range(l):
             fApB = dec[i] * A + B
             if fApB >= 0:
@@ -222,28 +328,33 @@ def sigmoid_train(dec, labels):
                 p = 1.0 / (1.0 + math.exp(fApB))
                 q = math.exp(fApB) / (1.0 + math.exp(fApB))
             d2 = p * q
-            h11 += dec[i] * dec[i] * d2
-            h22 += d2
-            h21 += dec[i] * d2
             d1 = t[i] - p
-            g1 += dec[i] * d1
-            g2 += d1
+            for k, v in enumerate((dec[i] * dec[i] * d2, d2, dec[i] * d2, dec[i] * d1, d1)):
+                sums[k].append(v)
+        h11, h22, h21, g1, g2 = (total(start, terms) for start, terms in zip((sigma, sigma, 0.0, 0.0, 0.0), sums))
         if abs(g1) < eps and abs(g2) < eps:
+            leave = 'gradient_at_entry' if it == 0 else 'gradient'
             break
         det = h11 * h22 - h21 * h21
         dA = -(h22 * g1 - h21 * g2) / det
         dB = -(-h21 * g1 + h11 * g2) / det
         gd = g1 * dA + g2 * dB
         stepsize = 1
+        n_half = 0
         while stepsize >= min_step:
             newA, newB = A + stepsize * dA, B + stepsize * dB
             newf = fun(newA, newB)
-            if newf < fval + 0.0001 * stepsize * gd:
+            if newf < fval + 0.0001 * stepsize * gd or mutate == 'no_backtracking':
                 A, B, fval = newA, newB, newf
                 break
             stepsize = stepsize / 2.0
+            n_half += 1
+        halvings.append(n_half)
         if stepsize < min_step:
+            leave = 'min_step'
             break
+    if trace is not None:
+        trace['halvings'], trace['exit'] = halvings, leave
     return A, B
 
 
