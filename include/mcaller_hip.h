@@ -790,6 +790,39 @@ int mc_hypergeom_masses_many(const int64_t *N, const int64_t *K, const int64_t *
 int mc_hypergeom_masses_device(mc_ctx *ctx, const int64_t *N, const int64_t *K, const int64_t *d, int64_t count, double *mass102,
                                double *err);
 
+/* ===== Fisher's exact test of compare_genomes --fisher (mcaller_amd/csrc/mc_fisher.h: one header for the host and the device) =====
+ * The table of two samples' counts, K1 methylated reads of n1 and K2 of n2: X ~ Hypergeometric(n1 + n2, K1 + K2, n1), observed
+ * K1; the two-sided p sums P(x) over the x with P(x) <= P(K1) (1 + 10^-7).  mc_fisher_exact: the host build on one table ->
+ * *log10_p (0.0 exactly where X takes one value), *bound a DERIVED bound on |*log10_p - log10 of the exact rational p|, *status
+ * the bits below (0: the value stands within its bound).  BAD_ARGS (not 0 <= K1 <= n1 <= 2^20, 0 <= K2 <= n2, n1 + n2 < 2^31):
+ * NaN twice.  FAR_TAIL: log10 p < -250 -- the value and the bound still stand, unless K1's own mass lies below 2^-900 of the
+ * mode's: -inf and +inf then.  SELECT: some P(x) / P(K1) lies within its own error of 1 + 10^-7, so the computed selection may
+ * not be the exact one.  _many: `count` tables; _device: the device build, a lane per table.
+ * mc_fisher_select(w, w_obs, steps): the selection predicate on two weights reached in at most `steps` steps from the mode:
+ * bit 0 selected, bit 1 within the error. */
+#define MC_FISHER_BAD_ARGS 1
+#define MC_FISHER_FAR_TAIL 2
+#define MC_FISHER_SELECT   4
+int mc_fisher_exact(int64_t K1, int64_t n1, int64_t K2, int64_t n2, double *log10_p, double *bound, int32_t *status);
+int mc_fisher_exact_many(const int64_t *K1, const int64_t *n1, const int64_t *K2, const int64_t *n2, int64_t count, double *log10_p,
+                         double *bound, int32_t *status);
+int mc_fisher_exact_device(mc_ctx *ctx, const int64_t *K1, const int64_t *n1, const int64_t *K2, const int64_t *n2, int64_t count,
+                           double *log10_p, double *bound, int32_t *status);
+int mc_fisher_select(double w, double w_obs, double steps);
+
+/* ===== Benjamini-Hochberg q-values of compare_genomes --fdr, in the log domain (mcaller_amd/csrc/mc_bh.h) =====
+ * L[n]: log10 p of the rows of one column (NaN: an untested row, which is not counted), bound[n]: the bound on each.  Q[n]:
+ * log10 q, Q_(j) = min(0, min over k >= j of L_(k) + (log10 m - log10 k)) over the m tested rows sorted ascending; rounded[n]:
+ * np.round(0.0 - Q, 3); NaN twice for an untested row.  *status: MC_BH_TIE when some row's value lies within the column's bound
+ * (the largest of bound[], plus the derived slack of the terms) of a rounding tie; MC_BH_RANGE (NaN everywhere) for an L above
+ * 0 or below -350 or a bound that is negative or not finite.  n <= 2^31 - 2.  mc_bh_adjust: the host build (a std::sort);
+ * mc_bh_adjust_device: the kernels -- a device-wide radix sort of the rows' 64-bit keys, the terms, a two-level minimum from the
+ * end, the finish at the rows' own places.  No floating-point atomic, and no atomic decides an order or a value. */
+#define MC_BH_TIE   1
+#define MC_BH_RANGE 2
+int mc_bh_adjust(const double *L, const double *bound, int64_t n, double *Q, double *rounded, int32_t *status);
+int mc_bh_adjust_device(mc_ctx *ctx, const double *L, const double *bound, int64_t n, double *Q, double *rounded, int32_t *status);
+
 /* ===== the evaluation file of mcaller_amd/evaluate.py, made on the GPU (csrc/eval/mc_evalcalls.hip) =====
  * mc_eval_calls: the text of a `.diffs.<k>` file and of a labelled positions file -> the bytes evaluate.evaluate_calls gives for
  * them: the ROC tables by read, by site at min_depth or more, and by site at each of the n_depths subsampled depths (1 .. 16 of
@@ -1003,6 +1036,9 @@ typedef struct mc_cmp_stats {
     int32_t longest_probe;         /* slots the longest probe of the table looked at             */
     int32_t deepest_site;          /* pooled values of the deepest shared site                   */
     double ms_read, ms_h2d, ms_kernels, ms_d2h, ms_total;
+    int64_t n_fisher;              /* sites Fisher's test ran on (mc_bed_compare_with)           */
+    int64_t n_fdr_columns;         /* columns of q-values made                                   */
+    double ms_fdr;                 /* the sorts and minima of the q-values (part of ms_kernels)  */
 } mc_cmp_stats;
 #define MC_CMP_DECLINE_HIGH_BYTE   1   /* a byte >= 0x80                                                                  */
 #define MC_CMP_DECLINE_CONTROL     2   /* a control byte other than tab and newline (0x7f and '\r' included)               */
@@ -1067,6 +1103,17 @@ typedef struct mc_xmfa_stats {
 #define MC_CMP_DECLINE_XMFA_RANGE    23  /* an END beyond the .fai total of its genome                                      */
 #define MC_CMP_DECLINE_XMFA_GENOME   24  /* a genome of more than 2^31 - 2 bases, or 2^31 columns or more in paired blocks  */
 #define MC_CMP_DECLINE_LIFT_START    25  /* a bed1 start that is not plain digits (int() may accept it: the host decides)   */
+/* ... with mc_bed_compare_with's options (compare_genomes --fisher --fdr; csrc/compare/mc_cmpfdr.inc).  fisher: one more column behind
+ * nlp_ks, -log10 p of Fisher's exact test on the counts of the site's two lines (frac, field 5, is the count K over the line's n
+ * probabilities: K = rint(frac n), sound iff 0 <= K <= n and K / n == frac in fp64).  fdr: behind that, -log10 of the
+ * Benjamini-Hochberg q-value of each -log10 p column over the rows written (mc_bh_adjust below).  Null options, or both 0: mc_bed_compare,
+ * byte for byte.  Declines on top of the above: 26-27, and MC_CMP_DECLINE_FAR_TAIL (Fisher's log10 p below -250), _TIE (a site's
+ * nlp_fisher, or -- no line named -- a q-value within its column's bound of a rounding tie), _PRINT, _MEMORY (the sort buffers). */
+#define MC_CMP_DECLINE_FRAC          26  /* a shared line whose frac mc_decimal.h declines or that is no count over its reads */
+#define MC_CMP_DECLINE_FISHER_SELECT 27  /* a table with a mass within its error of the selection factor 1 + 10^-7           */
+typedef struct mc_cmp_options {
+    int32_t fisher, fdr;
+} mc_cmp_options;
 int mc_xmfa_map(mc_ctx *ctx, const mc_text_source *src, int32_t seq1, int32_t seq2, int64_t n1, int64_t n2, mc_xmfa_map_view *view,
                 int32_t *status);
 int mc_xmfa_map_last_stats(mc_ctx *ctx, mc_xmfa_stats *out);
@@ -1074,6 +1121,9 @@ int mc_xmfa_map_release(mc_ctx *ctx);
 int mc_bed_compare(mc_ctx *ctx, const mc_text_source *bed1, const mc_text_source *bed2, const mc_contig_table *contigs1,
                    const mc_contig_table *contigs2, const char **out, int64_t *n_out, int64_t *n_sites, int64_t *n_unaligned,
                    int32_t *status);
+int mc_bed_compare_with(mc_ctx *ctx, const mc_text_source *bed1, const mc_text_source *bed2, const mc_contig_table *contigs1,
+                        const mc_contig_table *contigs2, const mc_cmp_options *opt, const char **out, int64_t *n_out, int64_t *n_sites,
+                        int64_t *n_unaligned, int32_t *status);
 int mc_bed_compare_last_stats(mc_ctx *ctx, mc_cmp_stats *out);
 int mc_bed_compare_release(mc_ctx *ctx);
 int mc_twosample(const double *x, int64_t n1, const double *y, int64_t n2, double *out, double *bound, int32_t *status);

@@ -650,6 +650,47 @@ def hypergeom_masses(N, K, d):
     return mass, err
 
 
+def fisher_exact(K1, n1, K2, n2):
+    """log10 of the two-sided p of Fisher's exact test on K1 of n1 against K2 of n2, its derived bound and the status bits
+    (MC_FISHER_*), by mc_fisher.h's host build.  Scalars -> (status, log10_p, bound) (mc_fisher_exact); four arrays of one
+    length -> (log10_p float64 [n], bound float64 [n], status int32 [n]) (mc_fisher_exact_many)."""
+    if np.ndim(K1) == 0:
+        l, b, st = C.c_double(), C.c_double(), C.c_int32()
+        rc = lib().mc_fisher_exact(int(K1), int(n1), int(K2), int(n2), C.byref(l), C.byref(b), C.byref(st))
+        if rc != 0:
+            raise ValueError('mc_fisher_exact: %d' % rc)
+        return int(st.value), l.value, b.value
+    K1, n1, K2, n2 = (np.ascontiguousarray(a, dtype=np.int64) for a in (K1, n1, K2, n2))
+    if not (K1.ndim == 1 and K1.shape == n1.shape == K2.shape == n2.shape):
+        raise ValueError('fisher_exact: four arrays of one length')
+    l, b, st = np.zeros(len(K1)), np.zeros(len(K1)), np.zeros(len(K1), dtype=np.int32)
+    rc = lib().mc_fisher_exact_many(K1.ctypes.data, n1.ctypes.data, K2.ctypes.data, n2.ctypes.data, len(K1), l.ctypes.data, b.ctypes.data,
+                                    st.ctypes.data)
+    if rc != 0:
+        raise ValueError('mc_fisher_exact_many: %d' % rc)
+    return l, b, st
+
+
+def fisher_select(w, w_obs, steps):
+    """mc_fisher.h's selection predicate on a weight beside the observed one, both at most `steps` steps from the mode
+    -> (selected, within its error of the factor 1 + 10^-7)."""
+    r = lib().mc_fisher_select(float(w), float(w_obs), float(steps))
+    return bool(r & 1), bool(r & 2)
+
+
+def bh_adjust(L, bound):
+    """The Benjamini-Hochberg adjustment of one column of log10 p (NaN: an untested row) by mc_bh.h's host build
+    -> (Q float64 [n]: log10 q, rounded float64 [n]: np.round(0.0 - Q, 3), status: MC_BH_* bits)."""
+    L, bound = np.ascontiguousarray(L, dtype=np.float64), np.ascontiguousarray(bound, dtype=np.float64)
+    if not (L.ndim == 1 and L.shape == bound.shape):
+        raise ValueError('bh_adjust: two arrays of one length')
+    Q, rounded, st = np.zeros(len(L)), np.zeros(len(L)), C.c_int32()
+    rc = lib().mc_bh_adjust(L.ctypes.data, bound.ctypes.data, len(L), Q.ctypes.data, rounded.ctypes.data, C.byref(st))
+    if rc != 0:
+        raise ValueError('mc_bh_adjust: %d' % rc)
+    return Q, rounded, int(st.value)
+
+
 def hypergeom_round4(v):
     """np.round(v, 4) by mc_hypergeom.h's host build."""
     return lib().mc_hypergeom_round4(float(v))

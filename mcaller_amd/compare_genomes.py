@@ -58,7 +58,33 @@ a malformed header, or a sequence line before its block's first header; a sequen
 file whose lines are sound, entry by entry (the header's line is named), the first of: a non-gap count that disagrees with the
 header; a column count other than that of the entry before it in the block; an entry behind the last '='; an END beyond the
 .fai total of its genome (--xmfa_seqs' two).  The device declines on each (MC_CMP_DECLINE_XMFA_*) and this statement words the error;
-it also declines a bed1 start that is not plain digits, and this statement does the file."""
+it also declines a bed1 start that is not plain digits, and this statement does the file.
+
+A COUNT TEST AND A MULTIPLE-TESTING CORRECTION:
+
+    python -m mcaller_amd.compare_genomes --bed1 A.bed --bed2 B.bed [--xmfa ... --fai1 ... --fai2 ...] [--fisher] [--fdr] [-o OUT] [--device]
+
+Rows, their order and the first 17 columns (21 with --xmfa) stay as they are; without the flags every byte does.  Appended:
+
+    ... nlp_ks [nlp_fisher] [nlq_mwu nlq_rs nlq_t nlq_ks [nlq_fisher]]
+
+Counts (--fisher only; frac is not parsed without it): for a line, n = len(probabilities), f = float(frac) (field 5) and
+K = int(np.rint(f * n)).  The line is sound iff 0 <= K <= n and np.float64(K) / np.float64(n) == f: frac is the str(np.mean(labels))
+make_bed wrote (the rule recovers K for every 0 <= K <= n <= 8192).  A shared line that is not sound is
+ValueError('bed<i> line <no>: frac is not a count over its reads'); the depth field stays opaque text.
+nlp_fisher: X ~ Hypergeometric(N = n1 + n2, K = K1 + K2, d = n1), observed K1; the two-sided p is the sum of P(x) over
+{x : P(x) <= P(K1) (1 + 10^-7)}, compared in exact rationals (fractions.Fraction; the factor is R's, the fp64 number).  Printed:
+str(np.round(0.0 - L, 3)), L the fp64 number nearest to log10 of the exact rational p (decimal, 60 digits); p = 1 prints 0.0.
+nlq_* (Benjamini-Hochberg in the log domain, per column): L_i the unrounded log10 p of row i (np.log10 of SciPy's p for the four
+tests, L above for Fisher's), m the rows whose L_i is not NaN, sorted ascending, ranks j = 1 .. m:
+    T_(j) = L_(j) + (np.log10(np.float64(m)) - np.log10(np.float64(j)))          Q_(j) = min(0.0, min over k >= j of T_(k))
+Tied L get one Q however they are sorted.  Printed: str(np.round(0.0 - Q_i, 3)); a NaN row prints nan and is not counted in m; m
+counts the rows written, not bed1's lines.  10 ** Q is scipy.stats.false_discovery_control(p) to 1.4e-15.
+On the GPU (--device; csrc/mc_fisher.h, csrc/mc_bh.h, csrc/compare/mc_cmpfdr.inc): the host statement's bytes, or a decline and the
+host statement -- a shared line whose frac the device's decimal reader declines or that is no count (this statement words the error),
+a Fisher log10 p below -250, a mass within its derived error of the selection factor, a value (nlp_fisher or a q-value) within its
+derived bound of a rounding tie, too little device memory for the sort buffers (MC_CMP_DECLINE_*)."""
+import functools
 import os
 import re
 import sys
@@ -82,8 +108,9 @@ def read_bed(bed):
     return sites
 
 
-def site_values(x, y):
-    """The nine printed values of a site, as text, from the SciPy calls of the definition."""
+def site_values(x, y, logs=None):
+    """The nine printed values of a site, as text, from the SciPy calls of the definition; logs (a list): the unrounded log10 p of the
+    four tests are appended to it."""
     from scipy.stats import ks_2samp, kstwobign, mannwhitneyu, ranksums, ttest_ind
     n1, n2 = len(x), len(y)
     n = n1 + n2
@@ -104,8 +131,116 @@ def site_values(x, y):
         D = ks_2samp(x, y, method='asymp').statistic
         p_ks = kstwobign.sf(np.sqrt(n1 * n2 / (n1 + n2)) * D)
         nlp = [str(np.round(0.0 - np.log10(p), 3)) for p in (mwu.pvalue, rs.pvalue, tt.pvalue, p_ks)]
+        if logs is not None:
+            logs.extend(np.log10(p) for p in (mwu.pvalue, rs.pvalue, tt.pvalue, p_ks))
         return [str(float(U1)), str(np.round(z_mwu, 3)), str(np.round(rs.statistic, 3)), str(np.round(tt.statistic, 3)),
                 repr(float(D))] + nlp
+
+
+_FISHER_FACTOR = None
+
+
+def site_counts(frac, n):
+    """K of a line with n probabilities whose field 5 is `frac`, the str(np.mean(labels)) make_bed wrote, or None when the
+    text is not a count over n reads."""
+    try:
+        f = float(frac)
+    except ValueError:
+        return None
+    if n < 1 or not np.isfinite(f):
+        return None
+    K = int(np.rint(f * n))
+    if not 0 <= K <= n or np.float64(K) / np.float64(n) != f:
+        return None
+    return K
+
+
+def fisher_log10p(K1, n1, K2, n2):
+    """The fp64 number nearest to log10 of the two-sided p of Fisher's exact test on K1 of n1 against K2 of n2, in exact rationals:
+    X ~ Hypergeometric(n1 + n2, K1 + K2, n1), p the sum of P(x) over the x with P(x) <= P(K1) (1 + 10^-7)."""
+    from decimal import Context, Decimal
+    from fractions import Fraction
+    from math import comb
+    global _FISHER_FACTOR
+    if _FISHER_FACTOR is None:
+        _FISHER_FACTOR = Fraction(1.0 + 1e-7)               # R's factor, the fp64 number itself
+    if not (0 <= K1 <= n1 and 0 <= K2 <= n2):
+        raise ValueError('fisher_log10p: not 0 <= K1 <= n1, 0 <= K2 <= n2')
+    N, K, d = n1 + n2, K1 + K2, n1
+    lo, hi = max(0, d - (N - K)), min(K, d)
+    mass = [comb(K, lo) * comb(N - K, d - lo)]                               # P(x) C(N, d) = C(K, x) C(N - K, d - x): integers
+    for x in range(lo, hi):                                                  # (the ratio of two neighbours, an exact division)
+        mass.append(mass[-1] * ((K - x) * (d - x)) // ((x + 1) * (N - K - d + x + 1)))
+    limit = mass[K1 - lo] * _FISHER_FACTOR
+    part, total = sum(w for w in mass if w <= limit), sum(mass)
+    if part == total:
+        return 0.0
+    ctx = Context(prec=60)
+    return float(ctx.log10(ctx.divide(Decimal(part), Decimal(total))))
+
+
+def fisher_nlp(K1, n1, K2, n2):
+    """The printed value of the nlp_fisher column."""
+    return str(np.round(0.0 - fisher_log10p(K1, n1, K2, n2), 3))
+
+
+def bh_log10(L):
+    """log10 of the Benjamini-Hochberg q-values of a column of log10 p (float64 [n]; NaN: the row is not tested and stays NaN):
+    with the m tested rows sorted ascending, Q_(j) = min(0, min over k >= j of L_(k) + (log10 m - log10 k))."""
+    L = np.asarray(L, dtype=np.float64).reshape(-1)
+    Q = np.full(len(L), np.nan)
+    tested = np.flatnonzero(~np.isnan(L))
+    m = len(tested)
+    if m == 0:
+        return Q
+    order = tested[np.argsort(L[tested], kind='stable')]
+    T = L[order] + (np.log10(np.float64(m)) - np.log10(np.arange(1, m + 1, dtype=np.float64)))
+    Q[order] = np.minimum(0.0, np.minimum.accumulate(T[::-1])[::-1])
+    return Q
+
+
+def _line_numbers(bed):
+    """{key: 1-based number of the line whose value read_bed keeps (the last of a key)}"""
+    numbers = {}
+    with open(bed, 'r') as fi:
+        for no, line in enumerate(fi, 1):
+            fields = line.split('\t')
+            numbers[(fields[0], fields[1], fields[2], fields[5])] = no
+    return numbers
+
+
+class _Extra(object):
+    """The columns behind nlp_ks: per row the unrounded log10 p of the four tests and of Fisher's, then the q-values."""
+
+    def __init__(self, bed1, bed2, fisher, fdr):
+        self.fisher, self.fdr, self.logs = fisher, fdr, []
+        self.numbers = (_line_numbers(bed1), _line_numbers(bed2)) if fisher else None
+
+    def site(self):
+        """-> the row's list of logs, for site_values to fill"""
+        row = []
+        self.logs.append(row)
+        return row
+
+    def fisher_column(self, row, key1, key2, site1, site2):
+        counts = []
+        for which, (key, ((frac, _), p)) in enumerate(((key1, site1), (key2, site2))):
+            K = site_counts(frac, len(p))
+            if K is None:
+                raise ValueError('bed%d line %d: frac is not a count over its reads' % (which + 1, self.numbers[which][key]))
+            counts += [K, len(p)]
+        L = fisher_log10p(*counts)
+        row.append(L)
+        return str(np.round(0.0 - L, 3))
+
+    def finish(self, rows):
+        """rows: lists of fields; the q-value columns are appended in place"""
+        if not self.fdr or not rows:
+            return
+        with np.errstate(all='ignore'):
+            for L in np.asarray(self.logs, dtype=np.float64).T:
+                for fields, q in zip(rows, bh_log10(L)):
+                    fields.append(str(np.round(0.0 - q, 3)))
 
 
 def _write(out, data):
@@ -266,17 +401,36 @@ def _contigs(fai):
     return index, lens, offs, list(names)
 
 
-def _rows(bed1, bed2, xmfa_path=None, fai1=None, fai2=None, seqs=(1, 2)):
+def _rows(bed1, bed2, xmfa_path=None, fai1=None, fai2=None, seqs=(1, 2), fisher=False, fdr=False):
     """-> the rows as bytes, their number, and (with an alignment) the keys of bed1 that have no image, else None."""
     sites1, sites2 = read_bed(bed1), read_bed(bed2)
     rows = []
+    extra = _Extra(bed1, bed2, fisher, fdr) if fisher or fdr else None
+
+    def add(pos, image, lifted):
+        (frac1, depth1), x = sites1[pos]
+        (frac2, depth2), y = sites2[image]
+        head = list(pos) + (list(image) if lifted else []) + [frac1, depth1, frac2, depth2]
+        if extra is None:
+            rows.append('\t'.join(head + site_values(x, y)) + '\n')
+            return
+        logs = extra.site()
+        fields = head + site_values(x, y, logs)
+        if fisher:
+            fields.append(extra.fisher_column(logs, pos, image, sites1[pos], sites2[image]))
+        rows.append(fields)
+
+    def done(n_unaligned):
+        if extra is not None:
+            extra.finish(rows)
+            rows[:] = ['\t'.join(fields) + '\n' for fields in rows]
+        return ''.join(rows).encode('utf-8', 'surrogateescape'), len(rows), n_unaligned
+
     if xmfa_path is None:
         for pos in sites1:
             if pos in sites2:
-                (frac1, depth1), x = sites1[pos]
-                (frac2, depth2), y = sites2[pos]
-                rows.append('\t'.join(list(pos) + [frac1, depth1, frac2, depth2] + site_values(x, y)) + '\n')
-        return ''.join(rows).encode('utf-8', 'surrogateescape'), len(rows), None
+                add(pos, pos, False)
+        return done(None)
     if fai1 is None or fai2 is None:
         raise ValueError('an alignment needs the .fai of both genomes')
     contigs1, contigs2 = _contigs(fai1), _contigs(fai2)
@@ -287,22 +441,22 @@ def _rows(bed1, bed2, xmfa_path=None, fai1=None, fai2=None, seqs=(1, 2)):
         if image is None:
             n_unaligned += 1
         elif image in sites2:
-            (frac1, depth1), x = sites1[pos]
-            (frac2, depth2), y = sites2[image]
-            rows.append('\t'.join(list(pos) + list(image) + [frac1, depth1, frac2, depth2] + site_values(x, y)) + '\n')
-    return ''.join(rows).encode('utf-8', 'surrogateescape'), len(rows), n_unaligned
+            add(pos, image, True)
+    return done(n_unaligned)
 
 
-def compare_rows(bed1, bed2, xmfa_path=None, fai1=None, fai2=None, seqs=(1, 2)):
+def compare_rows(bed1, bed2, xmfa_path=None, fai1=None, fai2=None, seqs=(1, 2), fisher=False, fdr=False):
     """The rows of the definition as bytes, and their number."""
-    return _rows(bed1, bed2, xmfa_path, fai1, fai2, seqs)[:2]
+    return _rows(bed1, bed2, xmfa_path, fai1, fai2, seqs, fisher, fdr)[:2]
 
 
-def _done(by, reason, n_sites, n_unaligned):
+def _done(by, reason, n_sites, n_unaligned, fisher=False, fdr=False):
     global last_compare
     last_compare = dict(by=by, reason=reason, n_sites=n_sites)
     if n_unaligned is not None:
         last_compare['n_unaligned'] = n_unaligned
+    if fisher or fdr:                             # (a comparison without the flags says what it always said)
+        last_compare.update(fisher=bool(fisher), fdr=bool(fdr))
     return n_sites
 
 
@@ -311,23 +465,26 @@ def _host(bed1, bed2, out, reason, lift=()):
     last_compare = None
     data, n_sites, n_unaligned = _rows(bed1, bed2, *lift)
     _write(out, data)
-    return _done('host', reason, n_sites, n_unaligned)
+    return _done('host', reason, n_sites, n_unaligned, *lift[4:6])
 
 
-def compare_by_position(bed1, bed2, xmfa=None, out=None, xmfa_path=None, fai1=None, fai2=None, seqs=(1, 2)):
+def compare_by_position(bed1, bed2, xmfa=None, out=None, xmfa_path=None, fai1=None, fai2=None, seqs=(1, 2), fisher=False, fdr=False):
     """The host statement: the definition above, one SciPy call after the other.  xmfa (-g) is accepted and unused; the
     alignment is xmfa_path."""
-    return _host(bed1, bed2, out, 'the host statement was asked for', (xmfa_path, fai1, fai2, seqs))
+    return _host(bed1, bed2, out, 'the host statement was asked for', (xmfa_path, fai1, fai2, seqs, fisher, fdr))
 
 
-def compare_by_position_device(bed1, bed2, xmfa=None, out=None, xmfa_path=None, fai1=None, fai2=None, seqs=(1, 2)):
+def compare_by_position_device(bed1, bed2, xmfa=None, out=None, xmfa_path=None, fai1=None, fai2=None, seqs=(1, 2), fisher=False, fdr=False):
     """The same bytes made on the GPU, or -- when the device declines -- by the host statement, which also words the errors."""
     global last_compare
     from .device import get_device
     last_compare = None
-    lift = (xmfa_path, fai1, fai2, seqs)
+    lift = (xmfa_path, fai1, fai2, seqs, fisher, fdr)
+    flags = dict(fisher=True) if fisher else {}
+    if fdr:
+        flags['fdr'] = True
     if xmfa_path is None:
-        blob, n_sites, reason = get_device().bed_compare(path1=bed1, path2=bed2)
+        blob, n_sites, reason = get_device().bed_compare(path1=bed1, path2=bed2, **flags)
         n_unaligned = None
     else:
         if fai1 is None or fai2 is None:
@@ -339,14 +496,14 @@ def compare_by_position_device(bed1, bed2, xmfa=None, out=None, xmfa_path=None, 
         if reason is not None:
             return _host(bed1, bed2, out, reason, lift)
         try:
-            blob, n_sites, reason = dev.bed_compare(path1=bed1, path2=bed2, contigs1=contigs1, contigs2=contigs2)
+            blob, n_sites, reason = dev.bed_compare(path1=bed1, path2=bed2, contigs1=contigs1, contigs2=contigs2, **flags)
         finally:
             dev.xmfa_map_release()
         n_unaligned = dev.bed_compare_last_unaligned()
     if blob is None:
         return _host(bed1, bed2, out, reason, lift)
     _write(out, blob)
-    return _done('device', None, n_sites, n_unaligned)
+    return _done('device', None, n_sites, n_unaligned, fisher, fdr)
 
 
 def main(argv=None):
@@ -362,6 +519,8 @@ def main(argv=None):
     parser.add_argument('--xmfa_seqs', type=str, default='1,2', help="the alignment's sequence numbers of bed1's and bed2's genome (default 1,2)")
     parser.add_argument('-o', '--output', type=str, required=False, help='write the rows to this file (default: standard output)')
     parser.add_argument('--device', action='store_true', required=False, help='make the rows on the GPU (the host statement runs when it declines)')
+    parser.add_argument('--fisher', action='store_true', required=False, help="append nlp_fisher: Fisher's exact test on the two lines' counts")
+    parser.add_argument('--fdr', action='store_true', required=False, help='append the Benjamini-Hochberg q-value (-log10) of every p-value column')
     parser.add_argument('-v', '--version', action='store_true', required=False, help='print version')
     args = parser.parse_args(argv)
 
@@ -375,6 +534,8 @@ def main(argv=None):
     assert os.path.isfile(args.bed2), 'file not found at ' + args.bed2
 
     run = compare_by_position_device if args.device else compare_by_position
+    if args.fisher or args.fdr:
+        run = functools.partial(run, fisher=args.fisher, fdr=args.fdr)
     if args.xmfa is None:
         run(args.bed1, args.bed2, args.genome_alignment, args.output)
         return

@@ -6,6 +6,16 @@
 // Two genomes with their own assemblies are compared through a Mauve alignment: mc_xmfamap.inc, included below, builds the coordinate
 // map from the XMFA text (kx_*) and lifts bed1's lines onto bed2's keys (kc_lift, in kc_probe's place; mc_bed_compare's contig tables); its
 // header comment lists its declines (MC_CMP_DECLINE_XMFA_*, MC_CMP_DECLINE_LIFT_START) and its kernels' resources.
+// Fisher's exact test on the sites' counts and the Benjamini-Hochberg q-values of every -log10 p column (compare_genomes --fisher
+// --fdr; mc_bed_compare_with's options) are mc_cmpfdr.inc, included behind it: its kernels run between kc_finish and kc_size and hand
+// kc_size / kc_write the columns behind nlp_ks.  Their declines:
+//   site-level   MC_CMP_DECLINE_FRAC           a SHARED line whose frac (field 5) mc_decimal.h declines or that is no count over the
+//                                              line's reads (the host words the error, or float() takes what the device does not)
+//                MC_CMP_DECLINE_FISHER_SELECT  a table with a mass within its derived error of the selection factor 1 + 10^-7
+//                MC_CMP_DECLINE_FAR_TAIL, _TIE, _PRINT   Fisher's log10 p below -250, its printed value within its bound of a rounding
+//                                              tie, a value mc_rowtext.h does not print
+//   file-level   MC_CMP_DECLINE_TIE            a q-value within its column's bound of a rounding tie (no line is named)
+//                MC_CMP_DECLINE_MEMORY         the columns and the sort buffers beside the rest
 //
 // The result is the host statement's bytes or a decline (status 1, mc_last_error; the stats say which file and line):
 //   file-level   MC_CMP_DECLINE_HIGH_BYTE   a byte >= 0x80 (the host decodes the file; the device compares bytes)
@@ -71,6 +81,8 @@
 #include "../mc_textfeed.h"
 #include "../mc_decimal.h"
 #include "../mc_twosample.h"
+#include "../mc_fisher.h"
+#include "../mc_bh.h"
 
 #include <cstdio>
 #include <cstring>
@@ -128,7 +140,13 @@ struct CmpArgs {
     char *out;
     int lifted;                              // 1: kc_lift matched the lines; a row carries the image's key behind bed1's
     LiftDev lift;
+    // mc_bed_compare_with (mc_cmpfdr.inc): the columns behind nlp_ks
+    int fisher, fdr, n_extra;                // n_extra: fisher + (4 + fisher) fdr columns a row
+    double *logs, *log_bound;                // per site: the log10 p of the four tests and of Fisher's before rounding, their bounds
+    double *extra;                           // per site: the n_extra printed values
 };
+
+constexpr int CMP_LOGS = 5;
 
 __device__ __forceinline__ TabSpan cmp_line(const CmpArgs &A, int64_t li) { return tabs_unpack(A.span[li]); }
 
@@ -406,19 +424,23 @@ __global__ __launch_bounds__(THREADS) void kc_rank_large(RankArgs R) {
 // x_cnt / y_cnt of a site no rank kernel takes: its TwSite with the counts alone (tw_finish names it)
 __global__ __launch_bounds__(256) void kc_finish(const TwSite *__restrict__ sites, const long long *__restrict__ x_cnt,
                                                  const long long *__restrict__ y_cnt, int64_t S, double *__restrict__ out9,
-                                                 double *__restrict__ bound9, int32_t *__restrict__ status) {
+                                                 double *__restrict__ bound9, int32_t *__restrict__ status, double *__restrict__ logs,
+                                                 double *__restrict__ log_bound) {
     const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (s >= S) return;
-    double o[TW_N_OUT], b[TW_N_OUT];
+    double o[TW_N_OUT], b[TW_N_OUT], l[4];
     int st;
     if (x_cnt[s] + y_cnt[s] > TW_MAX_N) {
         st = TW_DEEP;
         for (int i = 0; i < TW_N_OUT; ++i) { o[i] = __builtin_nan(""); b[i] = 0.0; }
+        for (int i = 0; i < 4; ++i) l[i] = __builtin_nan("");
     } else {
-        st = tw_finish(sites[s], o, b);
+        st = tw_finish(sites[s], o, b, l);
     }
     for (int i = 0; i < TW_N_OUT; ++i) { out9[s * TW_N_OUT + i] = o[i]; bound9[s * TW_N_OUT + i] = b[i]; }
     status[s] = st;
+    if (logs)                                                          // (mc_bed_compare_with's fdr: the q-values start from these)
+        for (int i = 0; i < 4; ++i) { logs[s * CMP_LOGS + i] = l[i]; log_bound[s * CMP_LOGS + i] = b[5 + i]; }
 }
 
 // the row of site s into the sink: the key, frac and depth of the two lines as they stand, the nine numbers
@@ -439,7 +461,11 @@ __device__ __forceinline__ void cmp_put_row(const CmpArgs &A, int64_t s, Sink &o
     for (int i = L2.t[5] + 1; i <= L2.t[6]; ++i) o.put(p2[i]);
     for (int i = 0; i < TW_N_OUT; ++i) {
         rt_put_num(o, rt_num_of(A.out9[s * TW_N_OUT + i]));
-        o.put(i + 1 < TW_N_OUT ? '\t' : '\n');
+        o.put(i + 1 < TW_N_OUT || A.n_extra ? '\t' : '\n');
+    }
+    for (int i = 0; i < A.n_extra; ++i) {                              // nlp_fisher, the q-values
+        rt_put_num(o, rt_num_of(A.extra[s * A.n_extra + i]));
+        o.put(i + 1 < A.n_extra ? '\t' : '\n');
     }
 }
 
@@ -454,6 +480,11 @@ __global__ __launch_bounds__(256) void kc_size(CmpArgs A) {
                          : (st & TW_UNPRINTABLE) ? MC_CMP_DECLINE_PRINT : MC_CMP_DECLINE_TIE;
         line_flag(&A.head->decline, A.line1[s], reason);
         return;
+    }
+    for (int i = 0; i < A.n_extra; ++i) {                              // (a NaN: the site's line has declined the file with its own reason)
+        const double v = A.extra[s * A.n_extra + i];
+        if (v != v) return;
+        if (!rt_num_of(v).ok) { line_flag(&A.head->decline, A.line1[s], MC_CMP_DECLINE_PRINT); return; }
     }
     RtCount count;
     cmp_put_row(A, s, count);
@@ -486,10 +517,12 @@ const char *cmp_reason_text(int reason) {
         case MC_CMP_DECLINE_DEPTH: return "a site with more than 8192 pooled values";
         case MC_CMP_DECLINE_NAN: return "a site with fewer than 3 pooled values or a zero pooled variance";
         case MC_CMP_DECLINE_ALL_EQUAL: return "a site whose pooled values are all equal";
-        case MC_CMP_DECLINE_FAR_TAIL: return "a log10 p below -290";
+        case MC_CMP_DECLINE_FAR_TAIL: return "a log10 p below -290 (Fisher's test: -250)";
         case MC_CMP_DECLINE_PRINT: return "a value the device's row writer does not print";
         case MC_CMP_DECLINE_TIE: return "a value within its error bound of a rounding tie";
         case MC_CMP_DECLINE_LIFT_START: return "a start that is not plain digits";
+        case MC_CMP_DECLINE_FRAC: return "a shared line whose frac is not a count over its reads";
+        case MC_CMP_DECLINE_FISHER_SELECT: return "a table of Fisher's test with a mass within its error of the selection factor";
     }
     return "unknown";
 }
@@ -526,11 +559,12 @@ int launch_ranks(hipStream_t st, const RankArgs &R) {
 }
 
 #include "mc_xmfamap.inc"
+#include "mc_cmpfdr.inc"
 
 // The texts are on the device (d_text[0, n): bed1's, a newline if it lacked its last, bed2's from off2 on; padded): everything behind that
 // (lift: the device side of a lifted comparison, nullptr: keys are matched as they stand)
 int cmp_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, int64_t off2, const char **out, int64_t *n_out, int64_t *n_sites,
-            int32_t *status, const LiftDev *lift) {
+            int32_t *status, const LiftDev *lift, const mc_cmp_options *opt) {
     mc_cmp_stats &S = c->cmp_stats;
     hipStream_t st = c->stream;
     if (n == 0) return 0;
@@ -590,6 +624,14 @@ int cmp_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, int64_t off2, 
             pool.get(&A.off2v, ns) || pool.get(&A.row_len, ns) || pool.get(&A.row_off, ns) || pool.get(&A.sites, ns) ||
             pool.get(&A.out9, ns * TW_N_OUT) || pool.get(&A.bound9, ns * TW_N_OUT) || pool.get(&A.status, ns))
             return -10;
+        if (opt && (opt->fisher || opt->fdr)) {                        // the columns behind nlp_ks, and the sort buffers of their q-values
+            A.fisher = opt->fisher != 0; A.fdr = opt->fdr != 0;
+            A.n_extra = A.fisher + (4 + A.fisher) * A.fdr;
+            if (!cmp_fits(ns * (8 * 8 + sizeof(TwSite) + 2 * 8 * TW_N_OUT + 4) + ns * 8 * (2 * CMP_LOGS + (size_t)A.n_extra) + (A.fdr ? fdr_bytes(NS) : 0) +
+                          ((size_t)1 << 20)))
+                return cmp_decline(c, status, MC_CMP_DECLINE_MEMORY, 0, -1);
+            if (pool.get(&A.logs, ns * CMP_LOGS) || pool.get(&A.log_bound, ns * CMP_LOGS) || pool.get(&A.extra, ns * (size_t)A.n_extra)) return -10;
+        }
         hipLaunchKernelGGL(kc_sites, dim3(blocks(L1)), dim3(256), 0, st, A);
         hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)A.cnt1, NS, A.off1, &d_head->n_x);
         hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)A.cnt2, NS, A.off2v, &d_head->n_y);
@@ -610,13 +652,18 @@ int cmp_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, int64_t off2, 
         RankArgs R = {A.vals, A.vals + A.n_x, A.off1, A.cnt1, A.off2v, A.cnt2, NS, A.sites, &d_head->n_small, &d_head->n_large};
         if (int rc = launch_ranks(st, R)) return rc;
         hipLaunchKernelGGL(kc_finish, dim3(blocks(NS)), dim3(256), 0, st, (const TwSite *)A.sites, (const long long *)A.cnt1,
-                           (const long long *)A.cnt2, NS, A.out9, A.bound9, A.status);
+                           (const long long *)A.cnt2, NS, A.out9, A.bound9, A.status, A.logs, A.log_bound);
+        unsigned bh_flags = 0;
+        if (A.n_extra)
+            if (int rc = cmp_extra_columns(c, pool, A, &bh_flags)) return rc;
         hipLaunchKernelGGL(kc_size, dim3(blocks(NS)), dim3(256), 0, st, A);
         hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)A.row_len, NS, A.row_off, &d_head->out_bytes);
         HIP_TRY(hipGetLastError());
         if (int rc = fetch_head(st, d_head, h)) return rc;
         S.n_rank_small = (int64_t)h.n_small; S.n_rank_large = (int64_t)h.n_large;
         if (h.decline != CMP_NO_DECLINE) return cmp_decline_head(c, status, h);
+        if (bh_flags & BH_RANGE) return cmp_decline(c, status, MC_CMP_DECLINE_FAR_TAIL, 0, -1);
+        if (bh_flags & BH_TIE) return cmp_decline(c, status, MC_CMP_DECLINE_TIE, 0, -1);
         const size_t ob = (size_t)h.out_bytes;
         if (!cmp_fits(ob + ((size_t)1 << 20))) return cmp_decline(c, status, MC_CMP_DECLINE_MEMORY, 0, -1);
         if (pool.get(&A.out, ob)) return -10;
@@ -676,7 +723,7 @@ bool lift_tables_ok(const mc_contig_table *t) {
 }
 
 int cmp_call(mc_ctx *c, const mc_text_source &s1, const mc_text_source &s2, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status,
-             const mc_contig_table *t1 = nullptr, const mc_contig_table *t2 = nullptr) {
+             const mc_contig_table *t1 = nullptr, const mc_contig_table *t2 = nullptr, const mc_cmp_options *opt = nullptr) {
     HIP_TRY(hipSetDevice(c->device));
     const auto t0 = std::chrono::steady_clock::now();
     c->cmp_stats = mc_cmp_stats();
@@ -701,7 +748,7 @@ int cmp_call(mc_ctx *c, const mc_text_source &s1, const mc_text_source &s2, cons
     const auto t_kernels = std::chrono::steady_clock::now();
     LiftDev lift;
     int rc = t1 ? lift_prepare(c, pool, t1, t2, &lift) : 0;
-    if (rc == 0) rc = cmp_run(c, pool, d_text, off2 + s2.n_bytes, off2, out, n_out, n_sites, status, t1 ? &lift : nullptr);
+    if (rc == 0) rc = cmp_run(c, pool, d_text, off2 + s2.n_bytes, off2, out, n_out, n_sites, status, t1 ? &lift : nullptr, opt);
     (void)hipStreamSynchronize(c->stream);                             // (an early return: nothing of the pool is in use when it goes)
     c->cmp_stats.ms_kernels = ms_since(t_kernels) - c->cmp_stats.ms_d2h;      // a declined call too: what ran until it declined
     if (rc != 0 || *status != 0) { *out = nullptr; *n_out = 0; *n_sites = 0; }
@@ -722,9 +769,10 @@ static int lifted_arguments(mc_ctx *c, const mc_contig_table *t1, const mc_conti
     return 0;
 }
 
-extern "C" int mc_bed_compare(mc_ctx *c, const mc_text_source *bed1, const mc_text_source *bed2, const mc_contig_table *t1,
-                              const mc_contig_table *t2, const char **out, int64_t *n_out, int64_t *n_sites, int64_t *n_unaligned,
-                              int32_t *status) {
+// opt: null, or the columns behind nlp_ks (mc_cmpfdr.inc)
+extern "C" int mc_bed_compare_with(mc_ctx *c, const mc_text_source *bed1, const mc_text_source *bed2, const mc_contig_table *t1,
+                                   const mc_contig_table *t2, const mc_cmp_options *opt, const char **out, int64_t *n_out, int64_t *n_sites,
+                                   int64_t *n_unaligned, int32_t *status) {
     if (!c || !out || !n_out || !n_sites || !status || !t1 != !t2) {
         mc_set_error("mc_bed_compare: bad arguments");
         return -12;
@@ -735,9 +783,15 @@ extern "C" int mc_bed_compare(mc_ctx *c, const mc_text_source *bed1, const mc_te
     mc_text_source s1 = {}, s2 = {};
     if (int rc = text_source("mc_bed_compare", bed1, &s1)) return rc;
     if (int rc = text_source("mc_bed_compare", bed2, &s2)) return rc;
-    const int rc = cmp_call(c, s1, s2, out, n_out, n_sites, status, t1, t2);
+    const int rc = cmp_call(c, s1, s2, out, n_out, n_sites, status, t1, t2, opt);
     if (t1 && rc == 0 && *status == 0) *n_unaligned = c->cmp_unaligned;
     return rc;
+}
+
+extern "C" int mc_bed_compare(mc_ctx *c, const mc_text_source *bed1, const mc_text_source *bed2, const mc_contig_table *t1,
+                              const mc_contig_table *t2, const char **out, int64_t *n_out, int64_t *n_sites, int64_t *n_unaligned,
+                              int32_t *status) {
+    return mc_bed_compare_with(c, bed1, bed2, t1, t2, nullptr, out, n_out, n_sites, n_unaligned, status);
 }
 
 extern "C" int mc_xmfa_map(mc_ctx *c, const mc_text_source *src, int32_t seq1, int32_t seq2, int64_t n1, int64_t n2, mc_xmfa_map_view *view,
@@ -820,7 +874,7 @@ extern "C" int mc_twosample_device(mc_ctx *c, const double *x, const int64_t *x_
     int rc = launch_ranks(st, R);
     if (rc == 0) {
         hipLaunchKernelGGL(kc_finish, dim3(blocks(k)), dim3(256), 0, st, (const TwSite *)d_sites, (const long long *)(d_cnt + nk),
-                           (const long long *)(d_cnt + 3 * nk), k, d_out, d_bound, d_status);
+                           (const long long *)(d_cnt + 3 * nk), k, d_out, d_bound, d_status, (double *)nullptr, (double *)nullptr);
         rc = mc_hip_rc(hipGetLastError(), "kc_finish");
     }
     if (rc == 0) rc = mc_hip_rc(hipMemcpyAsync(out, d_out, nk * TW_N_OUT * 8, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
@@ -828,4 +882,28 @@ extern "C" int mc_twosample_device(mc_ctx *c, const double *x, const int64_t *x_
     if (rc == 0) rc = mc_hip_rc(hipMemcpyAsync(status, d_status, nk * 4, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
     const int rc_sync = mc_hip_rc(hipStreamSynchronize(st), "hipStreamSynchronize");      // (nothing of the pool is in use when it goes)
     return rc ? rc : rc_sync;
+}
+
+// mc_fisher.h's device build on `count` tables, a lane per table (mc_cmpfdr.inc)
+extern "C" int mc_fisher_exact_device(mc_ctx *c, const int64_t *K1, const int64_t *n1, const int64_t *K2, const int64_t *n2, int64_t count,
+                                      double *log10_p, double *bound, int32_t *status) {
+    if (!c || count < 0 || (count > 0 && (!K1 || !n1 || !K2 || !n2 || !log10_p || !bound || !status))) {
+        mc_set_error("mc_fisher_exact_device: bad arguments");
+        return -12;
+    }
+    if (count == 0) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    return fisher_batch(c, K1, n1, K2, n2, count, log10_p, bound, status);
+}
+
+// the Benjamini-Hochberg adjustment of one column on the device (mc_cmpfdr.inc)
+extern "C" int mc_bh_adjust_device(mc_ctx *c, const double *L, const double *bound, int64_t n, double *Q, double *rounded, int32_t *status) {
+    if (!c || n < 0 || n > 2147483646LL || !status || (n > 0 && (!L || !bound || !Q || !rounded))) {
+        mc_set_error("mc_bh_adjust_device: bad arguments");
+        return -12;
+    }
+    *status = 0;
+    if (n == 0) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    return fdr_adjust(c, L, bound, n, Q, rounded, status);
 }

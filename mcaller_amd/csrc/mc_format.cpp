@@ -12,6 +12,8 @@
 #include "mc_rowtext.h"
 #include "mc_tstat.h"
 #include "mc_hypergeom.h"
+#include "mc_fisher.h"
+#include "mc_bh.h"
 #include "mc_twosample.h"
 #include "mc_npsum.h"
 #include "../../include/mcaller_hip.h"
@@ -669,6 +671,57 @@ extern "C" int mc_hypergeom_masses_many(const int64_t *N, const int64_t *K, cons
 }
 extern "C" double mc_hypergeom_round4(double v) { return hg_round4(v); }
 extern "C" int mc_hypergeom_tie4(double v, double err) { return hg_tie4(v, err) ? 1 : 0; }
+
+// Fisher's exact test of compare_genomes --fisher by mc_fisher.h's host build (include/mcaller_hip.h)
+extern "C" int mc_fisher_exact(int64_t K1, int64_t n1, int64_t K2, int64_t n2, double *log10_p, double *bound, int32_t *status) {
+    if (!log10_p || !bound || !status) return -12;
+    int st;
+    fe_log10p(K1, n1, K2, n2, log10_p, bound, &st);
+    *status = st;
+    return 0;
+}
+extern "C" int mc_fisher_exact_many(const int64_t *K1, const int64_t *n1, const int64_t *K2, const int64_t *n2, int64_t count, double *log10_p,
+                                    double *bound, int32_t *status) {
+    if (count < 0 || (count > 0 && (!K1 || !n1 || !K2 || !n2 || !log10_p || !bound || !status))) return -12;
+    for (int64_t i = 0; i < count; ++i) {
+        int st;
+        fe_log10p(K1[i], n1[i], K2[i], n2[i], &log10_p[i], &bound[i], &st);
+        status[i] = st;
+    }
+    return 0;
+}
+extern "C" int mc_fisher_select(double w, double w_obs, double steps) { return fe_select(w, w_obs, steps); }
+
+// the Benjamini-Hochberg adjustment of compare_genomes --fdr by mc_bh.h's host build: a sort of the keys, the terms, a minimum from
+// the end, the finish
+extern "C" int mc_bh_adjust(const double *L, const double *bound, int64_t n, double *Q, double *rounded, int32_t *status) {
+    if (n < 0 || !status || (n > 0 && (!L || !bound || !Q || !rounded)) || n > 2147483646LL) return -12;
+    *status = BH_OK;
+    std::vector<std::pair<uint64_t, uint32_t>> keyed((size_t)n);
+    double col_bound = 0.0;
+    int64_t m = 0;
+    bool range = false;
+    for (int64_t i = 0; i < n; ++i) {
+        keyed[(size_t)i] = {bh_key(L[i]), (uint32_t)i};
+        if (!bh_in_range(L[i], bound[i])) range = true;
+        else if (L[i] == L[i]) { ++m; col_bound = std::max(col_bound, bound[i]); }
+    }
+    if (range) {
+        for (int64_t i = 0; i < n; ++i) Q[i] = rounded[i] = __builtin_nan("");
+        *status = BH_RANGE;
+        return 0;
+    }
+    std::sort(keyed.begin(), keyed.end());
+    const double log10m = log10((double)m);
+    double t_min = INFINITY;
+    for (int64_t j = n; j-- > 0;) {
+        const uint32_t i = keyed[(size_t)j].second;
+        if (j >= m) { Q[i] = rounded[i] = __builtin_nan(""); continue; }
+        t_min = std::min(t_min, bh_term(bh_unkey(keyed[(size_t)j].first), log10m, j + 1));
+        *status |= bh_finish(t_min, col_bound, &Q[i], &rounded[i]);
+    }
+    return 0;
+}
 
 // the two-sample arithmetic of compare_genomes by mc_twosample.h's host build (include/mcaller_hip.h): the counts from sorted
 // copies of the two samples, the moments in row order, then tw_finish

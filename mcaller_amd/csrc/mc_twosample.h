@@ -166,9 +166,11 @@ TS_HD double tw_nlp(double log10_p) { return ts_round3(0.0 - log10_p); }
 
 // a site's counts and moments -> the nine values of its row (U and D as they are, the others as np.round(., 3) gives them), the
 // bound on |device - host| of each BEFORE rounding (0: exact), and the status bits: why they cannot be vouched for (0: they can)
-TS_HD int tw_finish(const TwSite &S, double *out, double *bound) {
+// logs (null: not wanted): the four log10 p before rounding, in the row's order, for the q-values of mc_bh.h -- bound[5 .. 8] bound them
+TS_HD int tw_finish(const TwSite &S, double *out, double *bound, double *logs = nullptr) {
     const double nan = __builtin_nan(""), u = 1.1102230246251565e-16;
     for (int i = 0; i < TW_N_OUT; ++i) { out[i] = nan; bound[i] = 0.0; }
+    if (logs) logs[0] = logs[1] = logs[2] = logs[3] = nan;
     if (S.n1 < 1 || S.n2 < 1 || S.n1 + S.n2 < 3) return TW_BAD_N;
     const long long ni = S.n1 + S.n2;
     const double n1 = (double)S.n1, n2 = (double)S.n2, n = (double)ni;
@@ -213,6 +215,7 @@ TS_HD int tw_finish(const TwSite &S, double *out, double *bound) {
         flags |= TW_TIE;
     out[1] = ts_round3(z_mwu); out[2] = ts_round3(z_rs); out[3] = ts_round3(t);
     out[5] = tw_nlp(l_mwu); out[6] = tw_nlp(l_rs); out[7] = tw_nlp(l_t); out[8] = tw_nlp(l_ks);
+    if (logs) { logs[0] = l_mwu; logs[1] = l_rs; logs[2] = l_t; logs[3] = l_ks; }
     bound[1] = e_mwu; bound[2] = e_rs; bound[3] = e_t;
     bound[5] = (n_mwu - f_mwu) + TW_FN_BOUND * (1.0 - f_mwu); bound[6] = (n_rs - f_rs) + TW_FN_BOUND * (1.0 - f_rs);
     bound[7] = (n_t - f_t) + TS_FN_BOUND * (1.0 - f_t); bound[8] = (n_ks - f_ks) + TW_FN_BOUND * (1.0 - f_ks);

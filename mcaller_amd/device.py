@@ -838,6 +838,30 @@ class Device(object):
         return mass, err
 
     @_serialized
+    def fisher_exact(self, K1, n1, K2, n2):
+        """log10 of the two-sided p of Fisher's exact test on K1 of n1 against K2 of n2, its derived bound and the status bits
+        (MC_FISHER_*) by mc_fisher.h's device build, a lane per table, one launch (mc_fisher_exact_device)
+        -> (log10_p float64 [n], bound float64 [n], status int32 [n])."""
+        K1, n1, K2, n2 = (np.ascontiguousarray(a, dtype=np.int64) for a in (K1, n1, K2, n2))
+        if not (K1.ndim == 1 and K1.shape == n1.shape == K2.shape == n2.shape):
+            raise ValueError('fisher_exact: four arrays of one length')
+        l, b, st = np.zeros(len(K1)), np.zeros(len(K1)), np.zeros(len(K1), dtype=np.int32)
+        check(lib().mc_fisher_exact_device(self._ctx, _ptr(K1), _ptr(n1), _ptr(K2), _ptr(n2), len(K1), _ptr(l), _ptr(b), _ptr(st)))
+        return l, b, st
+
+    @_serialized
+    def bh_adjust(self, L, bound):
+        """The Benjamini-Hochberg adjustment of one column of log10 p (NaN: an untested row) on the GPU: a device-wide radix sort of
+        the rows' keys, the terms, a two-level minimum from the end (mc_bh_adjust_device; csrc/compare/mc_cmpfdr.inc)
+        -> (Q float64 [n]: log10 q, rounded float64 [n]: np.round(0.0 - Q, 3), status: MC_BH_* bits)."""
+        L, bound = np.ascontiguousarray(L, dtype=np.float64), np.ascontiguousarray(bound, dtype=np.float64)
+        if not (L.ndim == 1 and L.shape == bound.shape):
+            raise ValueError('bh_adjust: two arrays of one length')
+        Q, rounded, st = np.zeros(len(L)), np.zeros(len(L)), C.c_int32()
+        check(lib().mc_bh_adjust_device(self._ctx, _ptr(L), _ptr(bound), len(L), _ptr(Q), _ptr(rounded), C.byref(st)))
+        return Q, rounded, int(st.value)
+
+    @_serialized
     def gff_site_stats(self, arrays, frac):
         """fracLow, fracUp and 100 * mean of make_bed --gff --vo for every array of probabilities (frac: its entry's fraction) by
         mc_npsum.h's device build, a workgroup per array (mc_gff_site_stats_device, tests)
@@ -966,12 +990,13 @@ class Device(object):
 
     # ---- two --vo BED files compared per site (csrc/compare/mc_bedcompare.hip) ----
     @_serialized
-    def bed_compare(self, path1=None, path2=None, text1=None, text2=None, contigs1=None, contigs2=None):
+    def bed_compare(self, path1=None, path2=None, text1=None, text2=None, contigs1=None, contigs2=None, fisher=False, fdr=False):
         """The rows of compare_genomes for two `make_bed --vo` files (`path1`, `path2`) or their texts (`text1`, `text2`, bytes),
         made on the GPU -> (blob: bytes, n_sites, None), or (None, 0, reason) when the device declines: the caller runs the
         host statement.  contigs1 / contigs2 (compare_genomes.read_fai's (names, lens, offs) of the two genomes): the comparison
         through the alignment map that xmfa_map left in the context; bed_compare_last_unaligned() then says how many lines of
-        bed1 had no image."""
+        bed1 had no image.  fisher / fdr: the columns behind nlp_ks (compare_genomes --fisher --fdr; mc_bed_compare_with): Fisher's
+        exact test on the two lines' counts, the Benjamini-Hochberg q-values of every -log10 p column."""
         if (path1 is None) != (path2 is None) or (text1 is None) != (text2 is None) or (path1 is None) == (text1 is None):
             raise ValueError('bed_compare: two paths or two texts')
         if (contigs1 is None) != (contigs2 is None):
@@ -984,8 +1009,13 @@ class Device(object):
         if contigs1 is not None:
             (t1, keep_t1), (t2, keep_t2) = _contig_table(contigs1), _contig_table(contigs2)
             t1, t2, keep = C.byref(t1), C.byref(t2), (keep_t1, keep_t2)
-        check(lib().mc_bed_compare(self._ctx, bed1, bed2, t1, t2, C.byref(out), C.byref(n_out), C.byref(n_sites), C.byref(n_unaligned),
-                                   C.byref(status)))
+        if fisher or fdr:
+            opt = _lib.ABI.structs['mc_cmp_options'](int(bool(fisher)), int(bool(fdr)))
+            check(lib().mc_bed_compare_with(self._ctx, bed1, bed2, t1, t2, C.byref(opt), C.byref(out), C.byref(n_out), C.byref(n_sites),
+                                            C.byref(n_unaligned), C.byref(status)))
+        else:
+            check(lib().mc_bed_compare(self._ctx, bed1, bed2, t1, t2, C.byref(out), C.byref(n_out), C.byref(n_sites), C.byref(n_unaligned),
+                                       C.byref(status)))
         del keep, keep1, keep2
         if contigs1 is not None and status.value == 0:
             self._unaligned = int(n_unaligned.value)

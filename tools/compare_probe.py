@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """tools/compare_probe.py [--sites 1e4,1e5] [--runs 5] [--host-runs 1] [--host-max 1e4] [--json profiles/compare_probe.json]
                          [--kernel-stats profiles/compare_kernel_stats.csv] [--keep DIR] [--device-only] [--host-only] [--seed 7]
+                         [--fisher] [--fdr]
 
 Two --vo BED files to the rows of compare_genomes, host statement against device, file to file on the same box:
   host    compare_genomes.compare_by_position          (four SciPy calls a site in a Python loop)
@@ -11,6 +12,8 @@ declines is recorded with its reason and not timed.
 
 The files: N shared sites on one contig, depths 15 .. 60 in each file, probabilities in hundredths, every fourth site of bed2
 shifted up by 0.3; bed2 in reverse order and with one line in ten of its own.  --host-only needs no GPU.
+--fisher / --fdr: the same legs with compare_genomes' flags of those names (profiles/compare_fdr_probe.json); the files' fracs are
+then counts over their reads, str(np.mean(p >= 0.5)) as make_bed writes them, in place of the four-decimal ones.
 --kernel-stats: the kernels' times from a `rocprofv3 --kernel-trace --stats` run of this tool's own (--device-only, the smallest
 case)."""
 import glob
@@ -31,7 +34,11 @@ def arg(name, default):
     return a[a.index(name) + 1] if name in a else default
 
 
-def write_pair(p1, p2, n, seed):
+def flags():
+    return {k: True for k in ('fisher', 'fdr') if '--' + k in sys.argv[1:]}
+
+
+def write_pair(p1, p2, n, seed, counts=False):
     """-> (bytes of bed1, bytes of bed2, probabilities in both)."""
     import numpy as np
     rng = np.random.default_rng(seed)
@@ -44,7 +51,8 @@ def write_pair(p1, p2, n, seed):
         total += n1 + n2
         strand = '+-'[i & 1]
         for lines, v in ((l1, x), (l2, y)):
-            lines.append('contig_1\t%d\t%d\tGATC\t%s\t%s\t%d\t%s\n' % (100 + 5 * i, 101 + 5 * i, repr(round(float((v >= 0.5).mean()), 4)), strand,
+            frac = str((v >= 0.5).mean()) if counts else repr(round(float((v >= 0.5).mean()), 4))
+            lines.append('contig_1\t%d\t%d\tGATC\t%s\t%s\t%d\t%s\n' % (100 + 5 * i, 101 + 5 * i, frac, strand,
                                                                      len(v), ','.join(repr(float(p)) for p in v)))
         if i % 10 == 0:
             l2.append('contig_2\t%d\t%d\tGATC\t0.5\t%s\t2\t0.25,0.75\n' % (100 + 5 * i, 101 + 5 * i, strand))
@@ -58,7 +66,7 @@ def kernel_stats(out_csv, sites, seed):
     d = tempfile.mkdtemp(prefix='mc_compare_stats_')
     try:
         cmd = ['rocprofv3', '--kernel-trace', '--stats', '--output-format', 'csv', '-d', d, '--', sys.executable, os.path.abspath(__file__),
-               '--device-only', '--sites', str(sites), '--runs', '3', '--seed', str(seed)]
+               '--device-only', '--sites', str(sites), '--runs', '3', '--seed', str(seed)] + ['--' + k for k in flags()]
         subprocess.run(cmd, check=True, timeout=900, stdout=subprocess.DEVNULL)
         found = glob.glob(os.path.join(d, '**', '*kernel_stats.csv'), recursive=True)
         if not found:
@@ -81,13 +89,13 @@ def main():
     for n in sizes:
         p1, p2 = os.path.join(d, 'a%d.bed' % n), os.path.join(d, 'b%d.bed' % n)
         out_d, out_h = os.path.join(d, 'device%d.tsv' % n), os.path.join(d, 'host%d.tsv' % n)
-        b1, b2, n_values = write_pair(p1, p2, n, seed)
-        r = dict(sites=n, bed1_bytes=b1, bed2_bytes=b2, probabilities=n_values)
+        b1, b2, n_values = write_pair(p1, p2, n, seed, counts=bool(flags()))
+        r = dict(sites=n, bed1_bytes=b1, bed2_bytes=b2, probabilities=n_values, **flags())
         if not host_only:
             from mcaller_amd.device import get_device
 
             def device():
-                compare_genomes.compare_by_position_device(p1, p2, out=out_d)
+                compare_genomes.compare_by_position_device(p1, p2, out=out_d, **flags())
                 return compare_genomes.last_compare
 
             who = device()                                      # warm-up: pinned blocks, the first launches, the files in the page cache
@@ -109,7 +117,7 @@ def main():
             t_host = []
             for _ in range(host_runs):
                 t = time.perf_counter()
-                compare_genomes.compare_by_position(p1, p2, out=out_h)
+                compare_genomes.compare_by_position(p1, p2, out=out_h, **flags())
                 t_host.append(time.perf_counter() - t)
             r.update(host_s=statistics.median(t_host), host_all_s=t_host, host_runs=host_runs, host_cores=cores,
                      host_ms_per_site=1e3 * statistics.median(t_host) / n)
