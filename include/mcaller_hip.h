@@ -1132,6 +1132,55 @@ int mc_twosample_device(mc_ctx *ctx, const double *x, const int64_t *x_off, cons
 double mc_twosample_log10_2sf(double z);
 double mc_twosample_log10_kolmogorov(double lam);
 
+/* ===== a native sample against an unmodified control, site by site and without a model (mcaller_amd/compare_currents.py;
+ * csrc/mc_curcombine.h, csrc/compare/mc_curcompare.inc) =====
+ * mc_currents_compare: the two texts are the mCaller rows (.diffs, 7 or 8 fields) of the native sample and of the control.  One row per
+ * key (chrom, pos, strand) of the native text that the control has too, with at least opt->depth rows in both, in the order of the
+ * keys' first native rows: per value column Student's t, then per test (Mann-Whitney, rank-sum, Student, Kolmogorov-Smirnov) the
+ * Bonferroni combination of the columns' -log10 p; opt->fdr: behind them the Benjamini-Hochberg q-values (mc_bh_adjust) of the four.
+ * opt->by (0 .. 3: mwu, rs, t, ks; -1: none): the rows whose printed value of that test (with fdr: its q-value) is at least
+ * opt->threshold also go to res->bed as BED lines.  opt->n_columns is c, the values of a row less the read quality, and opt->log10c the
+ * caller's float(np.log10(c)): no side computes it anew.  The bytes are those of compare_currents.compare_currents, or the call
+ * declines -- *status = 1, mc_last_error says why (mc_currents_compare_last_stats: which file, line and reason), nothing is handed out
+ * and the caller runs the host statement, which words the errors.  Declines: MC_CMP_DECLINE_* above where they apply, and 28-30.
+ * res->out and res->bed point at pinned memory owned by the context: valid until the next mc_currents_compare call on it or
+ * mc_currents_compare_release.
+ * mc_curcombine: one test's c columns by the host build of csrc/mc_curcombine.h (needs no GPU) -> 0; out2 = the combined log10 p
+ * before rounding and np.round(0.0 - L, 3), *bound_out the bound on |device L - host L|, *status the CC_* bits of that header
+ * (0: the value is vouched for); -12: bad arguments. */
+#define MC_CMP_DECLINE_CUR_FIELDS    28  /* a line that does not have 7 or 8 tab-separated fields (the host's ValueError)      */
+#define MC_CMP_DECLINE_CUR_VALUES    29  /* a line whose number of values is not n_columns + 1, or fewer than 2               */
+#define MC_CMP_DECLINE_CUR_POS       30  /* a pos that is not 1 .. 9 plain digits (int() may accept it: the host decides)     */
+typedef struct mc_cur_options {
+    int32_t depth, fdr, by, n_columns;
+    double threshold, log10c;
+} mc_cur_options;
+typedef struct mc_cur_result {
+    const char *out, *bed;
+    int64_t n_out, n_bed, n_sites, n_sig;
+} mc_cur_result;
+typedef struct mc_cur_stats {
+    int64_t n_bytes1, n_bytes2, n_lines1, n_lines2;
+    int64_t n_keys;                /* keys of the two files together                             */
+    int64_t n_sites, n_columns;    /* kept sites; value columns of a row                         */
+    int64_t n_values;              /* numbers of the kept sites' rows, both samples              */
+    int64_t n_rank_small, n_rank_large;   /* (site, column) pairs a wave ranked (<= 64 pooled values), a workgroup ranked */
+    int64_t n_out_bytes, n_bed_bytes, n_sig, table_slots;
+    int64_t decline_line;          /* 0-based line in its file the decline names, -1: none       */
+    int32_t decline_reason;        /* 0: not declined; MC_CMP_DECLINE_*                          */
+    int32_t decline_file;          /* 1: native, 2: control, 0: none                             */
+    int32_t longest_probe;         /* slots the longest probe of the table looked at             */
+    int32_t deepest_site;          /* pooled rows of the deepest kept site                       */
+    double ms_read, ms_h2d, ms_kernels, ms_d2h, ms_total;
+    int64_t n_fdr_columns;         /* columns of q-values made                                   */
+    double ms_fdr;                 /* the sorts and minima of the q-values (part of ms_kernels)  */
+} mc_cur_stats;
+int mc_currents_compare(mc_ctx *ctx, const mc_text_source *native, const mc_text_source *control, const mc_cur_options *opt,
+                        mc_cur_result *res, int32_t *status);
+int mc_currents_compare_last_stats(mc_ctx *ctx, mc_cur_stats *out);
+int mc_currents_compare_release(mc_ctx *ctx);
+int mc_curcombine(const double *L, const double *bound, int64_t c, double log10c, double out2[2], double *bound_out, int32_t *status);
+
 /* ===== methylated motifs found de novo from called sites on the GPU (mcaller_amd/find_motifs.py; csrc/motifs/mc_motifscan.hip) =====
  * mc_motif_report, with iupac = 0 and max_motifs = 0.  For every shape (a string of X and '.', first and last X, at most MC_MOTIF_MAX_WIDTH wide, 2 to 8 X), every X of it as the called
  * letter and every assignment of A, C, G, T to the X: the candidates of the reference (ref: contig_len, seq_off and the upper-cased

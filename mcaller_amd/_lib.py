@@ -51,6 +51,9 @@ RowsMergeStats = _S['mc_rows_merge_stats']
 FastqQualityView = _S['mc_fastq_quality_view']
 FastqQualityStats = _S['mc_fastq_quality_stats']
 CmpStats = _S['mc_cmp_stats']
+CurOptions = _S['mc_cur_options']
+CurResult = _S['mc_cur_result']
+CurStats = _S['mc_cur_stats']
 ContigTable = _S['mc_contig_table']
 XmfaMapView = _S['mc_xmfa_map_view']
 XmfaStats = _S['mc_xmfa_stats']
@@ -69,6 +72,7 @@ FASTQ_DECLINE = ABI.prefixed('MC_FASTQ_DECLINE_')
 MERGE_DECLINE = ABI.prefixed('MC_MERGE_DECLINE_')
 TW_STATUS = {'bad_n': 1, 'zero_var': 2, 'far_tail': 4, 'no_convergence': 8, 'all_equal': 16, 'tie': 32, 'unprintable': 64,
              'deep': 128}                                                                        # TW_* (csrc/mc_twosample.h)
+CC_STATUS = {'nan': 1, 'range': 2, 'tie': 4, 'unprintable': 8}                                 # CC_* (csrc/mc_curcombine.h)
 TW_NAMES = ('U', 'z_mwu', 'z_rs', 't', 'D', 'nlp_mwu', 'nlp_rs', 'nlp_t', 'nlp_ks')
 
 _lib = None
@@ -689,6 +693,19 @@ def bh_adjust(L, bound):
     if rc != 0:
         raise ValueError('mc_bh_adjust: %d' % rc)
     return Q, rounded, int(st.value)
+
+
+def curcombine(L, bound, log10c):
+    """compare_currents' Bonferroni combination of one test's columns (L: their unrounded log10 p, bound: the bounds on them) by
+    mc_curcombine.h's host build -> (combined log10 p, np.round(0.0 - L, 3), the bound on L, status: CC_* bits)."""
+    L, bound = np.ascontiguousarray(L, dtype=np.float64), np.ascontiguousarray(bound, dtype=np.float64)
+    if not (L.ndim == 1 and L.shape == bound.shape and len(L) >= 1):
+        raise ValueError('curcombine: two arrays of one length, at least 1')
+    out, b, st = np.zeros(2), C.c_double(), C.c_int32()
+    rc = lib().mc_curcombine(L.ctypes.data, bound.ctypes.data, len(L), float(log10c), out.ctypes.data, C.byref(b), C.byref(st))
+    if rc != 0:
+        raise ValueError('mc_curcombine: %d' % rc)
+    return float(out[0]), float(out[1]), float(b.value), int(st.value)
 
 
 def hypergeom_round4(v):

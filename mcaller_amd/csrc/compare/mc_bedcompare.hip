@@ -6,6 +6,7 @@
 // Two genomes with their own assemblies are compared through a Mauve alignment: mc_xmfamap.inc, included below, builds the coordinate
 // map from the XMFA text (kx_*) and lifts bed1's lines onto bed2's keys (kc_lift, in kc_probe's place; mc_bed_compare's contig tables); its
 // header comment lists its declines (MC_CMP_DECLINE_XMFA_*, MC_CMP_DECLINE_LIFT_START) and its kernels' resources.
+// A native sample against a control, site by site and without a model (compare_currents), is mc_curcompare.inc, included last (kn_*).
 // Fisher's exact test on the sites' counts and the Benjamini-Hochberg q-values of every -log10 p column (compare_genomes --fisher
 // --fdr; mc_bed_compare_with's options) are mc_cmpfdr.inc, included behind it: its kernels run between kc_finish and kc_size and hand
 // kc_size / kc_write the columns behind nlp_ks.  Their declines:
@@ -560,6 +561,7 @@ int launch_ranks(hipStream_t st, const RankArgs &R) {
 
 #include "mc_xmfamap.inc"
 #include "mc_cmpfdr.inc"
+#include "mc_curcompare.inc"
 
 // The texts are on the device (d_text[0, n): bed1's, a newline if it lacked its last, bed2's from off2 on; padded): everything behind that
 // (lift: the device side of a lifted comparison, nullptr: keys are matched as they stand)
@@ -831,6 +833,37 @@ extern "C" int mc_bed_compare_release(mc_ctx *c) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipStreamSynchronize(c->up_stream));
     c->cmp_out.reset(); c->cmp_out_cap = 0;
+    c->text_stages.release();
+    return 0;
+}
+
+// a native sample against a control, site by site (mc_curcompare.inc)
+extern "C" int mc_currents_compare(mc_ctx *c, const mc_text_source *native, const mc_text_source *control, const mc_cur_options *opt,
+                                   mc_cur_result *res, int32_t *status) {
+    if (!c || !opt || !res || !status || opt->depth < 2 || opt->by < -1 || opt->by > 3 || opt->n_columns < 0 || opt->n_columns > 65535 ||
+        !(opt->log10c >= 0.0) || !(opt->log10c < 16.0) || !(opt->threshold == opt->threshold)) {
+        mc_set_error("mc_currents_compare: bad arguments");
+        return -12;
+    }
+    mc_text_source s1 = {}, s2 = {};
+    if (int rc = text_source("mc_currents_compare", native, &s1)) return rc;
+    if (int rc = text_source("mc_currents_compare", control, &s2)) return rc;
+    return cur_call(c, s1, s2, *opt, res, status);
+}
+
+extern "C" int mc_currents_compare_last_stats(mc_ctx *c, mc_cur_stats *out) {
+    if (!c || !out) { mc_set_error("mc_currents_compare_last_stats: bad arguments"); return -12; }
+    *out = c->cur_stats;
+    return 0;
+}
+
+extern "C" int mc_currents_compare_release(mc_ctx *c) {
+    if (!c) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipStreamSynchronize(c->up_stream));
+    c->cur_out.reset(); c->cur_out_cap = 0;
+    c->cur_bed.reset(); c->cur_bed_cap = 0;
     c->text_stages.release();
     return 0;
 }

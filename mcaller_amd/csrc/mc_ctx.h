@@ -334,6 +334,10 @@ struct mc_ctx {
     size_t cmp_out_cap = 0;
     mc_cmp_stats cmp_stats = {};
     int64_t cmp_unaligned = 0;                    // (a lifted comparison) bed1's lines without an image
+    // ... the rows and the BED lines of a native sample compared with a control (compare/mc_curcompare.inc)
+    Pinned cur_out, cur_bed;
+    size_t cur_out_cap = 0, cur_bed_cap = 0;
+    mc_cur_stats cur_stats = {};
     // ... the coordinate map of an XMFA alignment (compare/mc_xmfamap.inc): on the device from mc_xmfa_map until the next such
     // call or mc_xmfa_map_release; map[g1] = ordinal << 33 | g2 << 1 | flip, ~0: unmapped.  The view's host copies are pinned
     Pool xmfa_allocs{"alignment map"};

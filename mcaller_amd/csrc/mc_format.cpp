@@ -15,6 +15,7 @@
 #include "mc_fisher.h"
 #include "mc_bh.h"
 #include "mc_twosample.h"
+#include "mc_curcombine.h"
 #include "mc_npsum.h"
 #include "../../include/mcaller_hip.h"
 
@@ -750,6 +751,13 @@ extern "C" int mc_twosample(const double *x, int64_t n1, const double *y, int64_
 }
 extern "C" double mc_twosample_log10_2sf(double z) { return tw_log10_2sf(z); }
 extern "C" double mc_twosample_log10_kolmogorov(double lam) { return tw_log10_kolmogorov(lam); }
+
+// compare_currents' Bonferroni combination of one test's c columns by mc_curcombine.h's host build (include/mcaller_hip.h)
+extern "C" int mc_curcombine(const double *L, const double *bound, int64_t c, double log10c, double out2[2], double *bound_out, int32_t *status) {
+    if (!L || !bound || !out2 || !bound_out || !status || c < 1) return -12;
+    *status = cc_combine(L, bound, c, 1, log10c, &out2[0], bound_out, &out2[1]);
+    return 0;
+}
 
 // the attributes of make_bed --gff --vo by mc_npsum.h's host build (include/mcaller_hip.h): p[0, n) the probabilities in row order
 extern "C" int mc_gff_site_moments(const double *p, int64_t n, double out3[3]) {

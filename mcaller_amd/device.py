@@ -1027,6 +1027,48 @@ class Device(object):
         """bed1's lines without an image in the last bed_compare through an alignment (None: it declined, or had none)."""
         return getattr(self, '_unaligned', None)
 
+    # ---- a native sample against a control, site by site (csrc/compare/mc_curcompare.inc) ----
+    @_serialized
+    def currents_compare(self, path1=None, path2=None, text1=None, text2=None, depth=15, fdr=False, by=None, threshold=2.0):
+        """The rows of compare_currents for the .diffs files of a native sample and a control (`path1`, `path2`) or their texts
+        (`text1`, `text2`, bytes), made on the GPU -> (blob: bytes, bed: bytes, n_sites, n_sig, None), or (None, None, 0, 0, reason)
+        when the device declines: the caller runs the host statement.  by ('mwu', 'rs', 't', 'ks'; None: no bed): the rows whose
+        printed value of that test (fdr: its q-value) is at least `threshold` are the bed's lines."""
+        if (path1 is None) != (path2 is None) or (text1 is None) != (text2 is None) or (path1 is None) == (text1 is None):
+            raise ValueError('currents_compare: two paths or two texts')
+        tests = ('mwu', 'rs', 't', 'ks')
+        if by is not None and by not in tests:
+            raise ValueError('currents_compare: by is one of mwu, rs, t, ks')
+        if int(depth) < 2:
+            raise ValueError('currents_compare: a depth of at least 2')
+        # c and log10(c) from the native text's first row: the constant is NumPy's, the bits the host statement adds
+        if path1 is not None:
+            with open(path1, 'rb') as fh:
+                first = fh.readline()
+        else:
+            first = bytes(text1).split(b'\n', 1)[0]
+        fields = first.split(b'\t')
+        c = fields[4].count(b',') if len(fields) in (7, 8) else 0
+        opt = _lib.CurOptions(int(depth), int(bool(fdr)), -1 if by is None else tests.index(by), min(c, 65535), float(threshold),
+                              float(np.log10(c)) if c >= 1 else 0.0)
+        res, status = _lib.CurResult(), C.c_int32()
+        (src1, keep1), (src2, keep2) = _source(path1, text1), _source(path2, text2)
+        check(lib().mc_currents_compare(self._ctx, src1, src2, C.byref(opt), C.byref(res), C.byref(status)))
+        del keep1, keep2
+        if status.value != 0:
+            return None, None, 0, 0, last_error()
+        return ((C.string_at(res.out, res.n_out) if res.n_out else b''), (C.string_at(res.bed, res.n_bed) if res.n_bed else b''),
+                int(res.n_sites), int(res.n_sig), None)
+
+    @_serialized
+    def currents_compare_last_stats(self):
+        """Figures of the last currents_compare: bytes, lines, keys, kept sites, the rank kernels' shares, the decline, milliseconds."""
+        return self._last_stats(lib().mc_currents_compare_last_stats, _lib.CurStats)
+
+    @_serialized
+    def currents_compare_release(self):
+        check(lib().mc_currents_compare_release(self._ctx))
+
     # ---- the coordinate map of a Mauve alignment (csrc/compare/mc_xmfamap.inc) ----
     @_serialized
     def xmfa_map(self, path=None, text=None, n1=0, seqs=(1, 2), n2=None, view=True):
