@@ -332,6 +332,12 @@ int mc_last_pass_info(mc_ctx *ctx, int32_t *fused_room, int32_t *rerun);
  * 1 positions and model-N bits; 2 unit summaries; 3 unit summaries and both relation columns, every row validated; -1 no pass
  * yet.  A pass that was repeated synchronously inside mc_wait_records leaves the repeat's mode. */
 int mc_ctx_last_scan_mode(mc_ctx *ctx);
+/* Which tiles of the current table the scan takes in a single batch when it streams unit summaries (modes 2 and 3; tests): the
+ * name-block descriptors of the SYNCHRONOUS pass run last over this table (mc_extract_features) and the tiles' first blocks are
+ * copied to the host and the scan's own predicate (scan_tile_is_whole, mc_dev.h) is evaluated per tile of 2048 rows.  Returns the
+ * number of tiles for which it holds, negative on error; per_tile (NULL, or a byte per tile): 1 where it holds, else 0.  (A tile
+ * for which it holds but which lists more than 64 units is taken by the general loop all the same.) */
+int64_t mc_ctx_whole_tiles(mc_ctx *ctx, uint8_t *per_tile);
 /* The rows of a pipelined pass as TEXT, made on the device (mc_rowtext.hip; replaces mc_format_diffs on the host, the row writer of
  * extract_contexts.py:207-216).  mc_ctx_row_text(on = 1, the two labels of :200-206; on = 2 at the start of a stream: also takes back the
  * blocks an earlier stream never released -- nobody may be reading them any more): the passes enqueued from now on also print their

@@ -448,6 +448,18 @@ constexpr int NCH = TILE / CHUNK;
 constexpr int NQ = CHUNK / 512;     // ... stripes of 512 rows per chunk -- every lane holds EIGHT consecutive rows of a stripe
 static_assert(CHUNK % 512 == 0 && TILE % CHUNK == 0, "whole stripes, whole chunks");
 
+constexpr int NQT = TILE / 512;     // ... stripes per tile (k1_scan's whole-tile path holds them all)
+
+// k1_scan, the instances that stream unit summaries: a tile that lies wholly inside ONE name block, behind the block's first row
+// and (a regular block) behind its first tested row, is taken in a single batch (scan_whole_tile, mc_scan.hip) -- there is no
+// second block, no unit is cut, the '+' extra row lies in front of the tile, every unit is tested from its first row on and one
+// descriptor serves all TILE rows.  d: the descriptor of the block that holds row t0 (the tile's first); nrows: the tile's rows.
+// (mc_ctx_whole_tiles evaluates the same function on the host: the tests say which path a tile took.)
+__host__ __device__ inline bool scan_tile_is_whole(const NbDesc &d, int64_t t0, int nrows) {
+    if (nrows != TILE || d.row_begin >= t0 || d.row_end < t0 + TILE) return false;
+    return d.mode != MODE_REGULAR || (d.first() >= 0 && d.first() <= t0);
+}
+
 constexpr int GROUP = 1024;
 
 // first record slot of a tile; wave-uniform call (all 64 lanes), n_groups <= a few hundred

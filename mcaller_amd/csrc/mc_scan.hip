@@ -346,6 +346,198 @@ struct ChunkCols {
     }
 };
 
+// ---- the instances that stream unit summaries: the whole tile's columns at once, and the path of a tile inside one block ----
+// A value that is the same in all lanes through the scalar cache (nothing in the kernel that calls this writes it): no vector load
+// whose wait is a wait for every column load in front of it.
+__device__ __forceinline__ int32_t i32_uniform(const int32_t *p) {
+    int32_t v;
+    asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(uniform_ptr(p)));
+    return v;
+}
+
+// The columns of a whole tile in registers, requested at the kernel's entry: a lane and stripe hold one int2 and (first pass) two
+// 16-bit words -- sixteen registers for the four stripes.  The general chunk loop takes its chunks from these (take_chunk).
+template <int MODE>
+struct TileCols {
+    int2 pp[NQT];                   // first and last position of the lane's unit in stripe j
+    uint32_t xr[NQT], pr[NQT];      // its index and position relations (SCAN_VALIDATE_SUMMARY)
+    __device__ __forceinline__ void load(const DevTable &T, int64_t t0, int nrows, int lane) {
+#pragma unroll
+        for (int j = 0; j < NQT; ++j) {
+            const int i0 = (j * 64 + lane) * 8;
+            pp[j] = make_int2(0, 0);
+            xr[j] = pr[j] = 0u;
+            if (i0 < nrows) {                       // (arrays are padded: whole units stay in bounds)
+                pp[j] = T.unit_pp[(t0 + i0) >> 3];
+                if (MODE == SCAN_VALIDATE_SUMMARY) {
+                    xr[j] = T.xrel[(t0 + i0) >> 3];
+                    pr[j] = T.prel[(t0 + i0) >> 3];
+                }
+            }
+        }
+    }
+};
+template <int MODE>
+__device__ __forceinline__ void take_chunk(ChunkCols<MODE> &C, const TileCols<MODE> &W, int ch) {
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {
+        C.pa[j] = C.pb[j] = make_int4(0, 0, 0, 0);
+        C.pa[j].x = W.pp[ch * NQ + j].x;
+        C.pb[j].w = W.pp[ch * NQ + j].y;
+        C.xr[j] = W.xr[ch * NQ + j];
+        C.pr[j] = W.pr[ch * NQ + j];
+        C.nb[j] = 0xFFu;
+    }
+}
+
+// A tile for which scan_tile_is_whole() holds (mc_dev.h), in one batch: straight-line code, every memory trip taken ONCE for the
+// tile -- the columns (on their way since the kernel's entry), the one descriptor d (the caller's), the mask words of all four
+// stripes, the listed units' positions and flag bytes, the payloads.  Validation: every row of the tile has its predecessor in the
+// block, so every bit of the relation words counts, and what the per-lane counts of the general loop are asked -- is any set, does
+// every pair have one of its two index bits -- the words ORed and ANDed together answer.  One list of at most CG units with
+// tile-relative first rows, one decide loop over rows [0, TILE): a closing row beyond the former chunk edge is the list's like any
+// other, only the tile's last rows go out of line.  Payloads leave through TileSlots::put in row order.  Returns false -- nothing
+// written -- if the tile lists more than CG units: the general chunk loop takes it, with CG units per chunk.
+// (The list's LDS words are ordered by wave-scope fences, as the dense instance's: LDS operations of one wave execute in order,
+// and a __syncthreads() would wait for every load in flight.)
+template <int CG, int MODE>
+__device__ __forceinline__ bool scan_whole_tile(const K1Args &A, const ScanGlobals &G, TileSlots &S, CandUnit *s_cand, const TileCols<MODE> &W,
+                                                const NbDesc &d, int nb_abs, int64_t t0, int lane) {
+    static_assert(TILE <= 65536 && NQT * 64 * 8 == TILE, "CandUnit::i0 holds a tile-relative row");
+    const DevTable &T = A.T;
+    const int k = A.k;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const uint32_t kmask = (1u << k) - 1u;
+    const bool reg = d.mode == MODE_REGULAR;
+    const uint32_t *gbits = (d.rev ? A.R.mr : A.R.mf) + d.mask_off;
+    const int nw = ((d.contig_len + 31) >> 5) + 2;                  // (two zero words behind every contig's mask)
+    // ---- the mask words of all four stripes, requested together (every lane loads, the undecidable ones the mask's first words) ----
+    uint32_t mlo[NQT], mhi[NQT];
+    bool decidable[NQT];
+#pragma unroll
+    for (int j = 0; j < NQT; ++j) {
+        const int p0 = W.pp[j].x, p7 = W.pp[j].y;
+        const uint32_t span = (uint32_t)p7 - (uint32_t)p0 + (uint32_t)k;
+        const int w = p0 >> 5;
+        decidable[j] = reg && span - 1u < 32u && p0 >= 0 && w + 1 < nw;
+        const uint32_t *g = gbits + (decidable[j] ? w : 0);
+        mlo[j] = g[0];
+        mhi[j] = g[1];
+    }
+    // ---- first pass over the table (while the mask words are on their way) ----
+    if (MODE == SCAN_VALIDATE_SUMMARY) {
+        uint32_t any_p = 0u, any_x = 0u, all_x = 0xFFu;
+#pragma unroll
+        for (int j = 0; j < NQT; ++j) {
+            any_p |= W.pr[j];
+            any_x |= W.xr[j];
+            all_x &= W.xr[j] | (W.xr[j] >> 8);      // (bit e: row e's event index is greater or less than that of the row before it)
+        }
+        const uint32_t seen = (__ballot((any_p & 0xFFu) != 0u) ? V_POS_DEC : 0u) | (__ballot((any_x & 0xFFu) != 0u) ? V_IDX_INC : 0u) |
+                              (__ballot((any_x >> 8) != 0u) ? V_IDX_DEC : 0u) | (__ballot((all_x & 0xFFu) != 0xFFu) ? V_IDX_EQ : 0u) |
+                              (__ballot((any_p >> 8) != 0u) ? V_POS0 : 0u);
+        if ((seen & ~d.vf) && lane == 0) note_validation(A, nb_abs, seen);
+    }
+    if (!reg) return true;                          // (an irregular, filtered or siteless block: validated, nothing to list)
+    // ---- which units of eight rows can hold a site row at all? ----
+    int ncand = 0;
+#pragma unroll
+    for (int j = 0; j < NQT; ++j) {
+        const int i0 = (j * 64 + lane) * 8;
+        const int p0 = W.pp[j].x, p7 = W.pp[j].y;
+        const int span = p7 - p0 + k;
+        const uint32_t bits = bits_from(mlo[j], mhi[j], p0 & 31) & (0xFFFFFFFFu >> ((32 - span) & 31));
+        const bool cand = !decidable[j] || bits != 0u;
+        const unsigned long long bal = __ballot(cand);
+        if (ncand + __popcll(bal) > CG) return false;
+        if (cand) {
+            // flag bytes 8, 9 (fetched below) and the unit's first row | its two mask words and the word they start at (-1: none)
+            int4 *gp = reinterpret_cast<int4 *>(s_cand + (ncand + __popcll(bal & below)));
+            gp[3] = make_int4((int)((uint32_t)i0 << 16), (int)mlo[j], (int)mhi[j], decidable[j] ? (p0 >> 5) : -1);
+        }
+        ncand += __popcll(bal);
+    }
+    if (ncand == 0) return true;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    // ---- the listed units' positions and flag bytes, and those of the two rows behind each: one round (ncand <= CG <= 64) ----
+    static_assert(CG <= 64, "one lane per listed unit");
+    if (lane < ncand) {
+        CandUnit *g = s_cand + lane;
+        const int i0 = (int)(reinterpret_cast<const uint32_t *>(g)[12] >> 16);
+        const uint8_t *fr = T.flags + t0 + i0;
+        const int32_t *pr = T.pos + t0 + i0;
+        const uint2 f8 = *reinterpret_cast<const uint2 *>(fr);
+        const uint32_t nf = *reinterpret_cast<const uint16_t *>(fr + 8);
+        const int4 a = *reinterpret_cast<const int4 *>(pr), b4 = *reinterpret_cast<const int4 *>(pr + 4);
+        const int2 nx = *reinterpret_cast<const int2 *>(pr + 8);
+        int4 *gp = reinterpret_cast<int4 *>(g);
+        gp[0] = a;
+        gp[1] = b4;
+        reinterpret_cast<int2 *>(g)[4] = nx;
+        reinterpret_cast<uint2 *>(g)[5] = f8;
+        reinterpret_cast<uint32_t *>(g)[12] = nf | ((uint32_t)i0 << 16);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    // ---- one lane per row of the listed units: is this row the last row of a window? ----
+    auto site_off = [&](const CandUnit *g, int p, bool &ok) -> int {
+        const int wb = (int)g->mw[2], wi = (p >> 5) - wb, sh = p & 31;
+        const uint32_t two = bits_from(g->mw[0], g->mw[1], sh), one = g->mw[1] >> sh;
+        ok = wb >= 0 && (wi == 0 || (wi == 1 && sh + k <= 32));
+        const uint32_t bits = (wi == 0 ? two : one) & kmask;
+        int o = bits ? (int)__builtin_ctz(bits) : -1;
+        if (p >= d.contig_len) { o = -1; ok = true; }
+        return o;
+    };
+    const uint32_t base_flags = (d.stray_q != NO_STRAY ? PF_STRAY : 0u) | (d.rev ? PF_REV : 0u);
+    for (int base = 0; base < ncand * 8; base += 64) {
+        const int idx = base + lane;
+        const bool have = idx < ncand * 8;
+        const CandUnit *g = s_cand + (have ? idx >> 3 : 0);
+        const int e = idx & 7;
+        const int p = g->pos[e], p1 = g->pos[e + 1], p2 = g->pos[e + 2];
+        const uint32_t f = g->fl[e], f1 = g->fl[e + 1], f2 = g->fl[e + 2];
+        const int i = (int)g->i0 + e;
+        bool closed = false, far = false;
+        int m = 0, cp = 0;
+        int64_t cr = 0;
+        uint32_t pf = 0;
+        if (have && !(f & MC_F_MODEL_N)) {
+            bool ok;
+            const int o = site_off(g, p, ok);
+            if (!ok) far = true;
+            else if (o >= 0) {
+                m = p + o;
+                // the next unfiltered row of the read inside the tile: the row behind this one, or the one behind an 'N' row
+                int c = -1;
+                if (i + 1 < TILE && !(f1 & MC_F_MODEL_N)) { c = i + 1; cp = p1; }
+                else if (i + 2 < TILE && (f1 & MC_F_MODEL_N) && !(f2 & MC_F_MODEL_N)) { c = i + 2; cp = p2; }
+                if (c >= 0) {
+                    cr = t0 + c;
+                    closed = cp > m;
+                    if (closed && cp <= m + A.skip_thresh + 1) {
+                        bool ok2;
+                        const int o2 = site_off(g, cp, ok2);
+                        if (!ok2) far = true;
+                        else if (o2 > 0) pf |= PF_MULTI;
+                    }
+                } else far = true;                  // past the tile, or behind two 'N' rows
+            }
+        }
+        if (__ballot(far)) {                        // rare
+            if (far) {
+                const RowRes fr = far_row(G, gbits, d.contig_len, nb_abs, d.row_end, t0 + i);
+                closed = fr.closed; m = fr.m; cp = fr.cp; cr = fr.cr; pf = fr.pf;
+            }
+        }
+        Payload P;
+        P.r = t0 + i; P.close_row = cr; P.m = m; P.close_pos = cp;
+        P.flags = pf | base_flags;
+        P.nb = nb_abs;
+        S.put(closed, P);
+    }
+    return true;
+}
+
 // The rows of one regular name block inside a chunk, for a one-base motif (k1_scan<CG_DENSE>): four rows in five are site rows
 // there and every unit would be listed -- so no list: the chunk's columns are in LDS, every lane its own units (k1_scan put
 // them there: the registers carry the next chunk's columns meanwhile), and every lane examines the eight rows of its unit of
@@ -519,7 +711,15 @@ __device__ __forceinline__ void dense_block_rows(const K1Args &A, TileSlots &S, 
 // row beyond the chunk or behind two 'N' rows, mask words beyond the unit's two) is an out-of-line call that reads global
 // memory.  The descriptors of the chunk's first two name blocks sit in SGPRs; a third block (reads of a few hundred rows) is
 // examined row by row from global memory.
-// CG: capacity of the candidate list (per chunk).  The sparse instance (a GATC-like motif: one unit in 20 is listed) bails out
+//
+// The instances that stream unit summaries (SCAN_SUMMARY, SCAN_VALIDATE_SUMMARY) request the columns of the WHOLE tile at the
+// kernel's entry (TileCols: sixteen registers) and take a tile that lies inside one name block -- scan_tile_is_whole(), mc_dev.h:
+// five tiles in six with reads of 5 000 - 20 000 rows -- in a single batch (scan_whole_tile): tile_nb and the one descriptor
+// through the scalar cache, the mask words of all four stripes in one trip, one list, one round of fetches, one decide loop
+// over [0, TILE); no second block, no cut unit, no `touches` test, nothing per chunk.  A tile with a block edge, the table's last,
+// partial tile and a tile that lists more than CG units go through the chunk loop below, which takes its two chunks from the
+// same registers.
+// CG: capacity of the candidate list (per chunk; the whole-tile path: per tile).  The sparse instance (a GATC-like motif: one unit in 20 is listed) bails out
 // to scan_blocks_slowly if a chunk overflows it; the dense instance holds every unit of a chunk.
 #ifdef MC_SCAN_WPE                  // (variant builds, tools/variants.sh)
 #define MC_SCAN_ATTR __attribute__((amdgpu_waves_per_eu(MC_SCAN_WPE, MC_SCAN_WPE)))
@@ -541,8 +741,15 @@ __global__ __launch_bounds__(64) MC_SCAN_ATTR void k1_scan(K1Args A) {
     const unsigned long long below = (1ull << lane) - 1ull;
     const uint32_t kmask = (1u << k) - 1u;
 
+    // (unit summaries: all four stripes of the tile are requested here, sixteen registers; the chunk loop takes its chunks from them)
+    constexpr bool WHOLE = CG <= 64 && summary_cols<MODE>();
+    static_assert(!WHOLE || NCH == 2, "take_chunk(C, W, 1): two chunks per tile");
+    TileCols<MODE> W;
     ChunkCols<MODE> C;
-    C.load(T, t0, min(nrows, CHUNK), lane);
+    if constexpr (WHOLE) {
+        W.load(T, t0, nrows, lane);
+        take_chunk(C, W, 0);
+    } else C.load(T, t0, min(nrows, CHUNK), lane);
     // (a one-base motif: the two rows behind the chunk -- the columns are padded by a tile -- so that the windows of the chunk's
     // last rows are closed like all others: one in eight chunks ends on a site row, and a row that is looked at out of line costs
     // the wave a chain of five loads)
@@ -556,7 +763,9 @@ __global__ __launch_bounds__(64) MC_SCAN_ATTR void k1_scan(K1Args A) {
     if constexpr (CG > 64) load_tail(t0 + min(nrows, CHUNK));
     int before_p = 0;                               // the row before the chunk (its first row's predecessor, if that is in its block)
     if (MODE == SCAN_VALIDATE && t0 > 0) before_p = T.pos[t0 - 1];
-    int nb0 = __builtin_amdgcn_readfirstlane(T.tile_nb[tile]);      // first name block that overlaps the chunk
+    int nb0;                                        // first name block that overlaps the chunk
+    if constexpr (WHOLE) nb0 = i32_uniform(T.tile_nb + tile);
+    else nb0 = __builtin_amdgcn_readfirstlane(T.tile_nb[tile]);
     ScanGlobals G;
     G.pos = T.pos; G.flags = T.flags; G.nb_row_begin = T.nb_row_begin; G.desc = A.desc; G.n_rows = T.n_rows;
     G.n_nb = T.n_nb; G.tail_contig = A.tail_contig; G.k = k; G.skip_thresh = A.skip_thresh;
@@ -565,6 +774,16 @@ __global__ __launch_bounds__(64) MC_SCAN_ATTR void k1_scan(K1Args A) {
     if constexpr (CG > 64) ahead = S.take_ahead();
     int half = 0;                                   // windows closed in the first chunk
     static_assert(CG <= 64 || NCH == 2, "tile_half: two chunks per tile");
+
+    // ---- unit summaries: a tile inside one name block (five in six, with reads of 5 000 - 20 000 rows) in a single batch ----
+    if constexpr (WHOLE) {
+        NbDesc d0 = desc_uniform(A.desc, nb0);
+        while (nb0 + 1 < T.n_nb && d0.row_end <= t0) d0 = desc_uniform(A.desc, ++nb0);       // (rare)
+        if (scan_tile_is_whole(d0, t0, nrows) && scan_whole_tile<CG, MODE>(A, G, S, s_cand, W, d0, nb0, t0, lane)) {
+            if (lane == 0) A.tile_cnt[tile] = S.total;
+            return;
+        }
+    }
 
 #pragma unroll 1
     for (int ch = 0; ch < NCH; ++ch) {
@@ -777,8 +996,11 @@ __global__ __launch_bounds__(64) MC_SCAN_ATTR void k1_scan(K1Args A) {
             if (bi == 0) seg_end_a = ncand;
         }
         // ---- the columns' registers are free: the next chunk's columns set out ----
-        if (more) C.load(T, c0 + CHUNK, min(nrows - (ch + 1) * CHUNK, CHUNK), lane);
-        if (overflow) {                                 // (nothing of the chunk has been written yet)
+        if (more) {
+            if constexpr (WHOLE) take_chunk(C, W, 1);
+            else C.load(T, c0 + CHUNK, min(nrows - (ch + 1) * CHUNK, CHUNK), lane);
+        }
+        if (overflow) {                               // (nothing of the chunk has been written yet)
             scan_blocks_slowly(A, nb0, nfast, c0, c1, S, lane);
         } else {
             __syncthreads();                            // (one wave: orders the list's words between the lanes)

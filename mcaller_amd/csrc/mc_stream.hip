@@ -33,7 +33,10 @@
 //                                found with one extract from the strand bitmask (two words per unit, straight from L2) and
 //                                listed in LDS, fetch their rows' positions and flag bytes, and their rows are tested for
 //                                "last row of a window"; every closed window leaves a 32-byte payload.  Later passes over the
-//                                same table read the unit summaries alone (1 B/row); one-base motifs, where every unit
+//                                same table read the unit summaries alone (1 B/row).  These two instances take a tile that
+//                                lies inside ONE name block in a single batch (scan_whole_tile: the whole tile's columns
+//                                requested at entry, one descriptor, one trip for the mask words, one list, one decide
+//                                loop); tiles with a block edge go chunk by chunk.  One-base motifs, where every unit
 //                                passes, stream the positions and the model-N bits, and on a first pass the index relations
 //                                with them (4.375 B/row), comparing the positions in registers.
 //                k1_group_scan / k1_list   file order of the windows; payloads gathered into it
@@ -843,6 +846,32 @@ extern "C" int mc_last_pass_info(mc_ctx *c, int32_t *fused_room, int32_t *rerun)
 }
 
 extern "C" int mc_ctx_last_scan_mode(mc_ctx *c) { return c->last_scan_mode; }
+
+// (tests) the scan's whole-tile predicate, evaluated on the host over the descriptors the synchronous pass left
+extern "C" int64_t mc_ctx_whole_tiles(mc_ctx *c, uint8_t *per_tile) {
+    HIP_TRY(hipSetDevice(c->device));
+    const DevTable &T = c->T;
+    if (c->cur < 0 || !c->sync.K.desc || T.n_nb <= 0 || T.n_nb > c->scratch_nb || T.n_tiles <= 0) {
+        mc_set_error("mc_ctx_whole_tiles: no table, or no synchronous pass over it yet");
+        return -12;
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::vector<NbDesc> desc((size_t)T.n_nb);
+    std::vector<int32_t> tile_nb((size_t)T.n_tiles);
+    HIP_TRY(hipMemcpy(desc.data(), c->sync.K.desc, desc.size() * sizeof(NbDesc), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(tile_nb.data(), T.tile_nb, tile_nb.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    int64_t n = 0;
+    for (int64_t tile = 0; tile < T.n_tiles; ++tile) {
+        const int64_t t0 = tile * TILE;
+        int nb = tile_nb[(size_t)tile];                 // (as k1_scan finds the block of the tile's first row)
+        if (nb < 0 || nb >= T.n_nb) { mc_set_error("mc_ctx_whole_tiles: tile %lld begins in block %d", (long long)tile, nb); return -12; }
+        while (nb + 1 < T.n_nb && desc[(size_t)nb].row_end <= t0) ++nb;
+        const bool whole = scan_tile_is_whole(desc[(size_t)nb], t0, (int)(std::min<int64_t>(t0 + TILE, T.n_rows) - t0));
+        if (per_tile) per_tile[tile] = whole ? 1 : 0;
+        n += whole;
+    }
+    return n;
+}
 
 extern "C" int mc_ctx_set_pass_timing(mc_ctx *c, int every_n) {
     if (every_n < 0) { mc_set_error("mc_ctx_set_pass_timing: every_n < 0"); return -12; }

@@ -459,6 +459,16 @@ class Device(object):
         return int(lib().mc_ctx_last_scan_mode(self._ctx))
 
     @_serialized
+    def whole_tiles(self, n_rows):
+        """A bool per tile of 2048 rows of the current table (n_rows rows): the scan that streams unit summaries takes the tile in
+        a single batch -- its own predicate on the descriptors of the synchronous pass run last (mc_ctx_whole_tiles; tests)."""
+        out = np.zeros((n_rows + 2047) // 2048, dtype=np.uint8)
+        n = int(lib().mc_ctx_whole_tiles(self._ctx, _ptr(out)))
+        check(min(n, 0))
+        assert n == int(out.sum())
+        return out.astype(bool)
+
+    @_serialized
     def times_ms(self):
         t = np.zeros(5, dtype=np.float32)
         check(lib().mc_last_times_ms(self._ctx, _ptr(t)))
