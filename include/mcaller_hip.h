@@ -126,6 +126,21 @@ typedef struct mc_calls_view {
     const uint32_t *feats_hi32;
     const uint8_t *feats_wide;
     int64_t n_wide;
+    /* mc_wait_records, "narrow records": site_pos, site_seg, info, close_row and close_row32 are NULL and the four columns travel
+     * as 16-bit halves plus a run list (the sparse MLP passes on tables of fewer than 2^31 - 1 rows whose rows the host prints) --
+     * close_lo16[j] = close_row & 0xFFFF, pos_lo16[j] = site_pos & 0xFFFF, info_lo16[j] = info & 0xFFFF, info_next[j] = info >> 16
+     * (bits 24..31 of info are 0); runs holds n_runs entries of four int32 { first_record, site_seg, close_row >> 16,
+     * site_pos >> 16 } (arithmetic shifts), first_record ascending from 0: an entry says the segment and the high halves of
+     * every record from first_record up to the next entry's.  Record j starts an entry iff j == 0 or one of the three differs
+     * from record j - 1's.  mc_format_diffs and mc_count_records read either layout; mc_records_expand rebuilds the columns. */
+    const uint16_t *close_lo16;
+    const uint16_t *pos_lo16;
+    const uint16_t *info_lo16;
+    const uint8_t *info_next;
+    const int32_t *runs;
+    int64_t n_runs;
+    /* mc_wait_records: bytes the pass's records took on their way to the host, in whichever layout (0: not a packed pass) */
+    int64_t copy_out_bytes;
 } mc_calls_view;
 
 const char *mc_last_error(void);
@@ -630,6 +645,11 @@ int mc_count_records(const mc_calls_view *rec, int64_t n, const int32_t *seg_rea
  * close_row_out[n] (64-bit closing rows), feats_out[n_call_rows * k] (the slot means as doubles); any may be NULL. */
 int mc_calls_expand(const mc_calls_view *rec, int64_t n_records, int32_t k, int32_t *call_row_out, int64_t *close_row_out,
                     double *feats_out);
+/* The four record columns in full from either layout of a view (narrow records: mc_calls_view.close_lo16; all cores):
+ * site_pos_out[n], site_seg_out[n], info_out[n], close_row_out[n]; any may be NULL.  -12: a run list that does not begin at
+ * record 0, does not ascend or leaves [0, n). */
+int mc_records_expand(const mc_calls_view *rec, int64_t n_records, int32_t *site_pos_out, int32_t *site_seg_out, uint32_t *info_out,
+                      int64_t *close_row_out);
 void mc_free(void *p);
 /* repr(float) == str(np.float64) of one value into out32 (NUL-terminated); returns its length. */
 int mc_repr_double(double v, char *out32);

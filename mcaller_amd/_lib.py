@@ -758,14 +758,23 @@ class Records(object):
     def view(self):
         v = CallsView()
         v.capacity = self.capacity
-        v.site_pos, v.site_seg = _ptr(self.site_pos), _ptr(self.site_seg)
-        v.info, v.prob = _ptr(self.info), _ptr(self.prob)
+        v.prob = _ptr(self.prob)
+        v.copy_out_bytes = int(self.copy_out_bytes)
+        narrow = self._narrow is not None and self._site_pos is None       # narrow records as mc_wait_records sent them
+        if narrow:
+            close_lo, pos_lo, info_lo, info_next, runs = self._narrow
+            v.close_lo16, v.pos_lo16, v.info_lo16, v.info_next = _ptr(close_lo), _ptr(pos_lo), _ptr(info_lo), _ptr(info_next)
+            v.runs, v.n_runs = _ptr(runs), len(runs) // 4
+        else:
+            v.site_pos, v.site_seg, v.info = _ptr(self.site_pos), _ptr(self.site_seg), _ptr(self.info)
         if self._feats is None and self._packed is not None:           # slot means as mc_wait_records sent them
             lo, hi, wide = self._packed
             v.feats_lo32, v.feats_hi32, v.feats_wide, v.n_wide = _ptr(lo), _ptr(hi), _ptr(wide), len(hi)
         else:
             v.feats = _ptr(self.feats)
-        if self._close_row is not None or self._close_row32 is None:
+        if narrow:
+            pass
+        elif self._close_row is not None or self._close_row32 is None:
             v.close_row = _ptr(self.close_row)
         else:
             v.close_row32 = _ptr(self._close_row32)
@@ -782,13 +791,18 @@ class Records(object):
         r.k, r.capacity, r.n, r._owner = k, n, n, owner
         if v.feats:
             r.feats = _from_ptr(v.feats, n * k, np.float64)
-        r.site_pos = _from_ptr(v.site_pos, n, np.int32)
-        r.site_seg = _from_ptr(v.site_seg, n, np.int32)
-        if v.close_row:
-            r._close_row = _from_ptr(v.close_row, n, np.int64)
-        else:                                # mc_wait_records on tables below 2^31 - 1 rows: 32-bit closing rows
-            r._close_row32 = _from_ptr(v.close_row32, n, np.int32)
-        r.info = _from_ptr(v.info, n, np.uint32)
+        r.copy_out_bytes = int(v.copy_out_bytes)
+        if v.close_lo16:                     # narrow records (mc_calls_view.close_lo16): the four columns are rebuilt on first use
+            r._narrow = (_from_ptr(v.close_lo16, n, np.uint16), _from_ptr(v.pos_lo16, n, np.uint16), _from_ptr(v.info_lo16, n, np.uint16),
+                         _from_ptr(v.info_next, n, np.uint8), _from_ptr(v.runs, 4 * int(v.n_runs), np.int32))
+        else:
+            r.site_pos = _from_ptr(v.site_pos, n, np.int32)
+            r.site_seg = _from_ptr(v.site_seg, n, np.int32)
+            if v.close_row:
+                r._close_row = _from_ptr(v.close_row, n, np.int64)
+            else:                            # mc_wait_records on tables below 2^31 - 1 rows: 32-bit closing rows
+                r._close_row32 = _from_ptr(v.close_row32, n, np.int32)
+            r.info = _from_ptr(v.info, n, np.uint32)
         if v.compacted:                      # mc_wait_records: means / probabilities of the calls only, compacted
             m = int(v.n_call_rows)
             r._compacted = True
@@ -807,7 +821,57 @@ class Records(object):
 
     # closing rows, call rows, slot means: columns mc_wait_records does not send in full (mc_calls_view) are rebuilt on first use
     _close_row = _close_row32 = _call_row = _feats = _packed = None
+    _site_pos = _site_seg = _info = _narrow = None
     _compacted = False
+    copy_out_bytes = 0          # bytes the pass's records took on their way to the host (mc_wait_records), whichever layout
+
+    @property
+    def n_runs(self):
+        """Entries of the run list of narrow records as they arrived; 0: the columns travelled in full."""
+        return len(self._narrow[4]) // 4 if self._narrow is not None else 0
+
+    def _widen(self):
+        """Narrow records: site_pos, site_seg, info and close_row in full (mc_records_expand), once."""
+        if self._narrow is not None and self._site_pos is None:
+            n = max(1, int(self.n))
+            pos, seg, info, close = (np.empty(n, dtype=t) for t in (np.int32, np.int32, np.uint32, np.int64))
+            v = self.view()
+            check(lib().mc_records_expand(C.byref(v), int(self.n), _ptr(pos), _ptr(seg), _ptr(info), _ptr(close)))
+            self._site_seg, self._info, self._close_row, self._site_pos = seg, info, close, pos
+
+    def end_segments(self):
+        """(segment of the first record, of the last): narrow records say so in their run list's first and last entries."""
+        if self._narrow is not None and self._site_pos is None:
+            runs = self._narrow[4]
+            return int(runs[1]), int(runs[-3])
+        return int(self.site_seg[0]), int(self.site_seg[self.n - 1])
+
+    @property
+    def site_pos(self):
+        self._widen()
+        return self._site_pos
+
+    @site_pos.setter
+    def site_pos(self, a):
+        self._site_pos = a
+
+    @property
+    def site_seg(self):
+        self._widen()
+        return self._site_seg
+
+    @site_seg.setter
+    def site_seg(self, a):
+        self._site_seg = a
+
+    @property
+    def info(self):
+        self._widen()
+        return self._info
+
+    @info.setter
+    def info(self, a):
+        self._info = a
 
     @property
     def feats(self):
@@ -825,6 +889,7 @@ class Records(object):
 
     @property
     def close_row(self):
+        self._widen()
         if self._close_row is None and self._close_row32 is not None:
             self._close_row = self._close_row32.astype(np.int64)
         return self._close_row

@@ -234,6 +234,8 @@ struct SidePack {
     size_t out_bytes;             // ... its size: a pass that needs more is marked (overflow, pack_need of host_status) and repeated
     Counters *host_status;        // the pass's counters as the host reads them (pinned)
     int close32, score;
+    int narrow;                   // the record columns as narrow records (narrow_layout) where the pass allows it: no pieces, no window
+                                  // left to the row-by-row walk (its key columns are written by this kernel, behind the emit's counts)
 };
 struct NoPack {};
 #ifndef MC_SIDE_WAVES
@@ -277,8 +279,9 @@ __global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu((FAST && !RO
     __shared__ int32_t s_slot[KB];             // a stretch made of pieces: the slot of every record, from the stretch's first piece's first slot
     __shared__ uint32_t s_fixrow[(FAST && PACK) ? KFIX : 1];   // PACK: ... and their rows in the packed block
     __shared__ int2 s_pk[PACK ? 2 : 1][PACK ? KW : 1];    // PACK: a wave's calls and their wide slot means in the stretch (two sets, like s_tot)
-    __shared__ unsigned long long s_base[PACK ? 2 : 1][4];      // PACK: calls, wide slot means, records in front of the stretch (two sets)
-    __shared__ unsigned long long s_red[PACK ? 6 : 1][PACK ? KW : 1];
+    __shared__ unsigned long long s_base[PACK ? 2 : 1][4];      // PACK: calls, wide slot means, records, run starts in front of the stretch (two sets)
+    __shared__ unsigned long long s_red[PACK ? 8 : 1][PACK ? KW : 1];
+    __shared__ unsigned long long s_runm[PACK ? 2 : 1][PACK ? KW : 1];      // PACK, narrow records: which of a wave's records start a run (two sets, like s_pk)
     __shared__ unsigned long long s_lay[PACK ? 8 : 1];     // PACK: where the packed block's columns begin (byte offsets): looked up where a stretch is packed,
                                                            // not carried through the hidden layer in registers the weights need
     const int tid = threadIdx.x, lane = tid & 63;
@@ -324,8 +327,11 @@ __global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu((FAST && !RO
     // in all (the emit's counts: nothing here waits for another workgroup); the pass's counters for the host; then the windows of its
     // own records that were left to the row-by-row walk ----
     K2_WALL(1);
+    [[maybe_unused]] bool narrow_k = false;    // PACK: this pass's record columns go out as narrow records (the same in every workgroup)
     if constexpr (PACK) {
         unsigned long long v[6] = {0, 0, 0, 0, 0, 0};           // calls, wide, records: in all; in front of the range
+        unsigned long long vr = 0, vr_before = 0;               // narrow records: run starts in all; in front of the range (the emit's counts)
+        const bool narrow = SP.narrow && !pieces && SP.A.cnt->n_rare == 0;
         if (pieces) {
             // (one word per piece: records | calls << 9 | wide slot means << 18; thirty-two pieces per thread and turn, eight 16-byte
             // loads side by side: a turn is a round trip, and a table of 10^8 rows has 10^5 pieces -- a piece at a time this took a
@@ -354,13 +360,18 @@ __global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu((FAST && !RO
                 const unsigned long long kk = SP.A.chunk_cnt[PACK_PAD * j], ww = SP.A.chunk_cnt[PACK_PAD * j + 1];
                 v[0] += kk; v[1] += ww;
                 if (j < c0) { v[3] += kk; v[4] += ww; }
+                if (narrow) {
+                    const unsigned long long rr = SP.A.chunk_cnt[PACK_PAD * j + PACK_RUNS_LANE];
+                    vr += rr;
+                    if (j < c0) vr_before += rr;
+                }
             }
             if (tid == 0) { v[2] = (unsigned long long)n; v[5] = (unsigned long long)lo; }
         }
         K2_WALL(2);
         // (added up across the wave, then one 64-bit LDS atomic per wave and sum.  Not sixteen partial sums per value read back by
         // everybody: the compiler fetches all ninety-six at once and spills them)
-        if (tid < 6) s_red[PACK ? tid : 0][0] = 0ull;
+        if (tid < 8) s_red[PACK ? tid : 0][0] = 0ull;
         __syncthreads();
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
@@ -369,25 +380,39 @@ __global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu((FAST && !RO
             for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
             if (lane == 0 && x) atomicAdd(&s_red[PACK ? i : 0][0], x);
         }
+        if (narrow) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) { vr += __shfl_xor(vr, o); vr_before += __shfl_xor(vr_before, o); }
+            if (lane == 0 && vr) atomicAdd(&s_red[PACK ? 6 : 0][0], vr);
+            if (lane == 0 && vr_before) atomicAdd(&s_red[PACK ? 7 : 0][0], vr_before);
+        }
         __syncthreads();
 #pragma unroll
         for (int i = 0; i < 6; ++i) v[i] = s_red[PACK ? i : 0][0];
+        vr = s_red[PACK ? 6 : 0][0]; vr_before = s_red[PACK ? 7 : 0][0];
         __syncthreads();            // (s_red has been read)
         // (the block is sized for the records a table of this size is expected to leave, not for every slot of a fused pass: a pass that
         // needs more says how much and is repeated -- every workgroup comes to the same conclusion from the same sums, so nothing is
         // marked on the device: Counters.overflow is what the workgroups look at when they START, and one that started behind the
         // mark would return without counting itself in side_done -- the workgroup through last tells the host, below)
-        const size_t need_bytes = pack_tail(pack_layout((int64_t)v[2], SP.close32).feats, (size_t)v[0], k, (size_t)v[1]).end;
+        const size_t feats_at = narrow ? narrow_layout((int64_t)v[2], (int64_t)vr).feats : pack_layout((int64_t)v[2], SP.close32).feats;
+        const size_t need_bytes = pack_tail(feats_at, (size_t)v[0], k, (size_t)v[1]).end;
         const bool too_big = need_bytes > SP.out_bytes;
         if (too_big) lo = hi;                          // (no stretch; the counters still go to the host, below)
+        narrow_k = narrow;
         if (tid == 0) {
             const PackLayout PL = pack_layout((int64_t)v[2], SP.close32);
-            const PackTail PTl = pack_tail(PL.feats, (size_t)v[0], k, (size_t)v[1]);
-            s_lay[0] = PL.pos; s_lay[1] = PL.seg; s_lay[2] = PL.info; s_lay[3] = PTl.lo32; s_lay[4] = PTl.wmask; s_lay[5] = PTl.hi32;
+            const NarrowLayout NL = narrow_layout((int64_t)v[2], (int64_t)vr);
+            const PackTail PTl = pack_tail(feats_at, (size_t)v[0], k, (size_t)v[1]);
+            // (narrow records: the three 16-bit columns in the places of pos, seg and info; the context bytes and the run list have their own)
+            s_lay[0] = narrow ? NL.pos_lo : PL.pos; s_lay[1] = narrow ? NL.info_lo : PL.seg; s_lay[2] = narrow ? NL.info_next : PL.info;
+            s_lay[3] = PTl.lo32; s_lay[4] = PTl.wmask; s_lay[5] = PTl.hi32;
             s_lay[6] = PTl.prob;
-            s_base[0][0] = v[3]; s_base[0][1] = v[4]; s_base[0][2] = v[5];
+            s_lay[7] = NL.runs;
+            s_base[0][0] = v[3]; s_base[0][1] = v[4]; s_base[0][2] = v[5]; s_base[0][3] = vr_before;
             s_red[0][1] = v[2]; s_red[1][1] = v[0]; s_red[2][1] = v[1];         // (records, calls, wide slot means in all: for the host, at the end)
             s_red[3][1] = need_bytes;                                           // (... and the block they need)
+            s_red[4][1] = narrow ? vr : 0ull;                                   // (... and the run list's entries; 0: the columns are wide)
         }
         __syncthreads();
         K2_WALL(3);
@@ -478,12 +503,29 @@ __global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu((FAST && !RO
         int mi = 255;                               // sub-model of record r (255: not scored here)
         double qv = 0.0;
         [[maybe_unused]] int p_nw = -1;                // PACK: wide slot means of the thread's record if it is a call, else -1
+        [[maybe_unused]] bool p_run = false;           // PACK, narrow records: the thread's record starts a run
         if (tid < n_here) {
             if (submodel_in) mi = submodel_in[r];
             else {
                 const uint32_t inf = info[r];
                 const int32_t seg = site_seg[r];
+                // narrow records: does the record start a run?  Its key against its predecessor's, both from the records (the
+                // predecessor may be another workgroup's: every record was written by the emit, no window was left to the walk).
+                // Asked for HERE, behind the info word and the segment and in front of everything that depends on them: the five
+                // loads travel with those two -- behind the mask byte's test they were a round trip of their own per stretch
+                // (the kernel alone 61.6 us instead of 59.5, beside the next pass's scan 96-104 instead of 80-87)
+                [[maybe_unused]] int64_t key_c = 0, key_cp = 0;
+                [[maybe_unused]] int32_t key_p = 0, key_pp = 0, key_sp = 0;
+                if constexpr (PACK) {
+                    if (narrow_k) {
+                        const int64_t rp = r > 0 ? r - 1 : 0;
+                        key_c = SP.A.O.close_row[r]; key_cp = SP.A.O.close_row[rp];
+                        key_p = SP.A.O.site_pos[r]; key_pp = SP.A.O.site_pos[rp];
+                        key_sp = site_seg[rp];
+                    }
+                }
                 if constexpr (PACK) { if (!(inf & MC_I_TOO_MANY)) p_nw = __popc((uint32_t)SP.A.O.wmask[r] & ((1u << k) - 1u)); }
+                if constexpr (PACK) p_run = narrow_k && (r == 0 || record_starts_run(seg, key_c, key_p, key_sp, key_cp, key_pp));
                 bool scored = !(inf & (MC_I_TOO_MANY | MC_I_EDGE));
                 if constexpr (PACK) scored = scored && SP.score != 0;
                 if (scored) {
@@ -499,6 +541,8 @@ __global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu((FAST && !RO
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) nw += __shfl_xor(nw, o);
             if (lane == 0) s_pk[PACK ? buf : 0][PACK ? wave : 0] = make_int2(nk, nw);
+            const unsigned long long rm = __ballot(p_run);
+            if (lane == 0) s_runm[PACK ? buf : 0][PACK ? wave : 0] = rm;
         }
         int rank = 0, cnt_lane = 0;                 // (lane m: the wave's records of sub-model m)
 #pragma unroll
@@ -650,8 +694,12 @@ __global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu((FAST && !RO
             // (the next stretch's bases: written whatever this stretch holds -- sixteen pieces without a record, a long read under
             // the quality threshold, are a stretch of nothing, and the stretch behind it reads what is written here)
             if (tid == 0) {
-                unsigned kept_s = 0, wide_s = 0;
-                for (int w = 0; w < KW; ++w) { const int2 c = s_pk[PACK ? buf : 0][PACK ? w : 0]; kept_s += (unsigned)c.x; wide_s += (unsigned)c.y; }
+                unsigned kept_s = 0, wide_s = 0, runs_s = 0;
+                for (int w = 0; w < KW; ++w) {
+                    const int2 c = s_pk[PACK ? buf : 0][PACK ? w : 0]; kept_s += (unsigned)c.x; wide_s += (unsigned)c.y;
+                    runs_s += (unsigned)__popcll(s_runm[PACK ? buf : 0][PACK ? w : 0]);
+                }
+                s_base[PACK ? buf ^ 1 : 0][3] = s_base[PACK ? buf : 0][3] + runs_s;
                 s_base[PACK ? buf ^ 1 : 0][0] = s_base[PACK ? buf : 0][0] + kept_s;
                 s_base[PACK ? buf ^ 1 : 0][1] = s_base[PACK ? buf : 0][1] + wide_s;
                 s_base[PACK ? buf ^ 1 : 0][2] = s_base[PACK ? buf : 0][2] + (unsigned long long)n_here;
@@ -683,11 +731,38 @@ __global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu((FAST && !RO
                 const unsigned long long real0 = s_base[PACK ? buf : 0][2];
                 const int64_t io = pieces ? (int64_t)real0 + tid : r;               // (holes are never looked at: the host never sees one)
                 unsigned char *const out = SP.out;
+                if (narrow_k) {
+                    // narrow records: 16-bit halves, the context byte, and the run entry of a record that starts a run at its counted place
+                    reinterpret_cast<uint16_t *>(out)[io] = (uint16_t)close;
+                    reinterpret_cast<uint16_t *>(out + s_lay[0])[io] = (uint16_t)pos;
+                    reinterpret_cast<uint16_t *>(out + s_lay[PACK ? 1 : 0])[io] = (uint16_t)inf;
+                    (out + s_lay[PACK ? 2 : 0])[io] = (uint8_t)(inf >> 16);
+                    const unsigned long long rm = s_runm[PACK ? buf : 0][PACK ? wave : 0];
+                    bool misfit = (inf >> 24) != 0u;
+                    if ((rm >> lane) & 1ull) {
+                        unsigned long long at = s_base[PACK ? buf : 0][3] + (unsigned)__popcll(rm & below);
+#pragma unroll
+                        for (int w = 0; w < KW; ++w)
+                            if (w < wave) at += (unsigned)__popcll(s_runm[PACK ? buf : 0][PACK ? w : 0]);
+                        // (the emit counted by the same rule from the payloads these records were written from: a place beyond the
+                        // list cannot be -- and is not written)
+                        if (at < s_red[PACK ? 4 : 0][PACK ? 1 : 0])
+                            reinterpret_cast<int4 *>(out + s_lay[PACK ? 7 : 0])[at] = make_int4((int)io, seg, (int)(close >> 16), pos >> 16);
+                        else misfit = true;
+                    }
+                    if (misfit) {
+                        // (an info word with a bit in 24..31: the pass is marked like one with irregular reads and repeated by the
+                        // synchronous path, which hands out wide columns -- the mark is all that crosses workgroups, see below)
+                        const unsigned long long was = atomicExch(&SP.A.cnt->irregular_pass, SP.A.pass_no);
+                        asm volatile("" :: "v"(was));
+                    }
+                } else {
                 if (SP.close32) reinterpret_cast<int32_t *>(out)[io] = (int32_t)close;
                 else reinterpret_cast<int64_t *>(out)[io] = close;
                 reinterpret_cast<int32_t *>(out + s_lay[0])[io] = pos;
                 reinterpret_cast<int32_t *>(out + s_lay[PACK ? 1 : 0])[io] = seg;
                 reinterpret_cast<uint32_t *>(out + s_lay[PACK ? 2 : 0])[io] = inf;
+                }
                 if (keep) {
                     int32_t *o_lo = reinterpret_cast<int32_t *>(out + s_lay[PACK ? 3 : 0]) + row * k;
                     uint32_t *o_hi = reinterpret_cast<uint32_t *>(out + s_lay[PACK ? 5 : 0]);
@@ -746,7 +821,8 @@ __global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu((FAST && !RO
             static_assert(sizeof(Counters::overflow) == 4 && sizeof(Counters::pack_need) == 8 && offsetof(Counters, pack_need) % 8 == 0, "Counters layout");
             const unsigned long long need_bytes = s_red[PACK ? 3 : 0][PACK ? 1 : 0];
             const bool too_big = need_bytes > SP.out_bytes;
-            if (tid < (int)head_words && (tid < kept_word || tid >= kept_word + 4) && tid >= 2) {
+            constexpr int runs_word = (int)(offsetof(Counters, n_runs) / 4);
+            if (tid < (int)head_words && (tid < kept_word || tid >= kept_word + 4) && tid >= 2 && tid != runs_word && tid != runs_word + 1) {
                 unsigned int w = __hip_atomic_load(reinterpret_cast<unsigned int *>(SP.A.cnt) + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 // (a packed block too small: marked here, as k_pack marks it -- the pass is repeated, the next block holds pack_need)
                 if (too_big && tid == overflow_word) w |= 1u;
@@ -757,6 +833,7 @@ __global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu((FAST && !RO
                 *reinterpret_cast<volatile unsigned long long *>(&SP.host_status->n_records) = s_red[0][PACK ? 1 : 0];
                 *reinterpret_cast<volatile unsigned long long *>(&SP.host_status->n_kept) = s_red[PACK ? 1 : 0][PACK ? 1 : 0];
                 *reinterpret_cast<volatile unsigned long long *>(&SP.host_status->n_wide) = s_red[PACK ? 2 : 0][PACK ? 1 : 0];
+                *reinterpret_cast<volatile unsigned long long *>(&SP.host_status->n_runs) = s_red[PACK ? 4 : 0][PACK ? 1 : 0];
             }
         }
     }
@@ -1276,7 +1353,6 @@ __global__ __launch_bounds__(PACK_THREADS) void k_pack(DevRecords O, const Count
     }
 }
 
-
 }  // namespace
 
 // k2_mlp workgroups: the records are divided evenly over them (the kernel does that with the count on the device); one
@@ -1352,7 +1428,7 @@ void mc_launch_pack(const DevRecords &O, const Counters *cnt, const unsigned lon
 // pass (another classifier, a piece's room beyond a stretch): the caller launches k1_rare_dev, the classifier and the packing kernels.
 bool mc_launch_side(const DevMlp &M, bool other_classifier, int n_cu, hipStream_t st, const K1Args &A, const Payload *sorted, const int32_t *seg_read,
                     const double *qual, int64_t cap, int score, unsigned char *out, size_t out_bytes, int close32, Counters *host_status,
-                    int piece_room, int64_t n_pieces, hipEvent_t stop) {
+                    int piece_room, int64_t n_pieces, hipEvent_t stop, int narrow) {
     static const bool off = getenv("MCALLER_SIDE_FUSED") && atoi(getenv("MCALLER_SIDE_FUSED")) == 0;       // (tests, profiles: the three kernels)
     if (off || cap <= 0) return false;
     if (score && (other_classifier || !M.W1)) return false;
@@ -1361,6 +1437,7 @@ bool mc_launch_side(const DevMlp &M, bool other_classifier, int n_cu, hipStream_
     if (by_piece ? (piece_room >= TH_SIDE || !A.piece_kw || !A.piece_cnt) : !A.chunk_cnt) return false;
     SidePack SP;
     SP.A = A; SP.sorted = sorted; SP.out = out; SP.out_bytes = out_bytes; SP.host_status = host_status; SP.close32 = close32; SP.score = score;
+    SP.narrow = (narrow && !by_piece && close32) ? 1 : 0;
     const K2Pieces P{by_piece ? A.piece_cnt : nullptr, piece_room, n_pieces};
     const bool fast = score && M.fast && M.wp32;
     // Workgroups of 512 threads (a stretch: 512 records) at 128 registers a lane, two to a CU -- with 1024 threads and 64 registers

@@ -174,6 +174,12 @@ struct AsyncBuf {
     int64_t h_n_wide = 0;
     int32_t *h_close32 = nullptr;                          // in pack_host: 32-bit closing rows (tables below 2^31 - 1 rows), else H.close_row
     bool close32 = false;
+    bool narrow = false;                                   // the side kernel was told to pack narrow records (narrow_layout) where the pass allows it
+    const uint16_t *h_close_lo16 = nullptr, *h_pos_lo16 = nullptr, *h_info_lo16 = nullptr;      // in pack_host: a pass that took them (else H.site_pos ...)
+    const uint8_t *h_info_next = nullptr;
+    const int32_t *h_runs = nullptr;
+    int64_t h_n_runs = 0;
+    int64_t h_copy_out_bytes = 0;                          // what the pass sent over the link
     int64_t h_n_calls = 0;
     Event ev[EV_N];
     mc_params prm;

@@ -197,8 +197,10 @@ struct Counters {          // device-side status block
     // never zeroed: k0_first_site classifies while it zeroes the other counters, so a count could lose updates -- a pass is
     // special iff this equals its own number
     unsigned long long irregular_pass;
+    unsigned long long n_runs;     // narrow records (narrow_layout): entries of the pass's run list, as the last k2_mlp<.., PACK> workgroup sends it;
+                                   // 0 in the host's copy: the pass's record columns travel wide (pack_layout)
     unsigned long long end_of_head;   // (k_pack copies everything before this field to the host)
-    unsigned long long pad_to_line[SHARD_PAD];
+    unsigned long long pad_to_line[SHARD_PAD - 1];     // (n_runs took one word of the padding: the shard counters stand where they stood)
     unsigned long long shard[NSHARD * SHARD_PAD];
 };
 // what the host writes into the pinned copy's side_done when it enqueues a pipelined pass: every kernel that publishes the counters
@@ -332,6 +334,7 @@ constexpr int PACK_WGS = MC_PACK_WGS, PACK_THREADS = MC_PACK_THREADS;
 // that are not fl(d / 1e4) -- every chunk's pair in a cache line of its own: the emit's waves work on neighbouring records, and
 // atomics on one line are served one after the other (all 418 records of a chunk, sixteen chunks to a line: k1_emit 40 -> 139 us).
 constexpr int PACK_PAD = 16;
+constexpr int PACK_RUNS_LANE = 3;     // chunk_cnt[PACK_PAD * b + PACK_RUNS_LANE]: records of chunk b that start a run of narrow records (narrow_layout; k1_emit)
 
 // One record (q of n_rec) for the packing's counts.  Called by one lane per record (the rare paths).
 __device__ __forceinline__ void count_for_packing(unsigned long long *chunk_cnt, int64_t q, int64_t n_rec, bool kept, int n_wide) {
@@ -344,9 +347,16 @@ __device__ __forceinline__ void count_for_packing(unsigned long long *chunk_cnt,
 
 // ... the records of a wave, all lanes calling: kept (one lane per record), q, wmask (bit f: slot mean f is wide) of the lane's
 // record.  One pair of atomics for the wave unless its records straddle a chunk boundary.
-__device__ __forceinline__ void count_wave_for_packing(unsigned long long *chunk_cnt, int64_t n_rec, bool kept, int64_t q, uint32_t wmask, int k) {
+// run_start (one lane per record; kept or not): the record starts a run of narrow records (narrow_layout) -- counted per chunk too.
+__device__ __forceinline__ void count_wave_for_packing(unsigned long long *chunk_cnt, int64_t n_rec, bool kept, int64_t q, uint32_t wmask, int k, bool run_start) {
     if (!chunk_cnt) return;
     const unsigned long long km = __ballot(kept);
+    const unsigned long long sm = __ballot(run_start);
+    if (sm) {       // (one record in seventeen of the headline workload: most waves have none)
+        uint32_t per_s = (uint32_t)((n_rec + PACK_WGS - 1) / PACK_WGS);
+        asm volatile("" : "+s"(per_s));
+        if (run_start) atomicAdd(&chunk_cnt[PACK_PAD * ((uint32_t)q / per_s) + PACK_RUNS_LANE], 1ull);
+    }
     if (!km) return;
     uint32_t per = (uint32_t)((n_rec + PACK_WGS - 1) / PACK_WGS);
     // (the division is made here, every time: its reciprocal, worked out once in front of the caller's loop, is one more value the
@@ -485,6 +495,33 @@ __host__ __device__ inline PackLayout pack_layout(int64_t n, int close32) {
     return L;
 }
 
+// "Narrow records": the same four columns, lossless, for the passes the MLP side kernel packs record by record (k2_mlp<.., PACK>
+// without pieces, 32-bit closing rows, no row text on the device).  Records come in table order, so the segment and the high halves
+// of the closing row and of the site position hardly ever change from one record to the next: per record the low halves and the
+// info word's used bits travel, 7 bytes instead of 16 --
+//   close_lo16[n] (u16: close_row & 0xFFFF) | pos_lo16[n] (u16: site_pos & 0xFFFF) | info_lo16[n] (u16: info & 0xFFFF) |
+//   info_next[n] (u8: info >> 16, the context character) | runs[n_runs] (16 bytes each, 16-byte aligned)
+// -- and a run list says the rest: record j starts a run iff j == 0 or its key (site_seg, close_row >> 16, site_pos >> 16; arithmetic
+// shifts) differs from record j - 1's.  A record's flag needs its predecessor alone; nothing is assumed about order, which only
+// decides how many runs there are.  An info word with a bit in 24..31 does not fit: such a pass is repeated and travels wide.
+// The call tail (pack_tail) follows at NarrowLayout::feats exactly as it follows the wide columns.
+struct RecordRun { int32_t first_record, seg, close_hi, pos_hi; };
+static_assert(sizeof(RecordRun) == 16, "RecordRun layout");
+struct NarrowLayout { size_t close_lo, pos_lo, info_lo, info_next, runs, feats; };
+__host__ __device__ inline NarrowLayout narrow_layout(int64_t n, int64_t n_runs) {
+    NarrowLayout L;
+    L.close_lo = 0;
+    L.pos_lo = (size_t)n * 2;
+    L.info_lo = (size_t)n * 4;
+    L.info_next = (size_t)n * 6;
+    L.runs = ((size_t)n * 7 + 15) & ~(size_t)15;
+    L.feats = L.runs + (size_t)n_runs * sizeof(RecordRun);      // (a multiple of 16: the tail's 8-byte rule holds)
+    return L;
+}
+__host__ __device__ inline bool record_starts_run(int32_t seg, int64_t close_row, int32_t pos, int32_t seg_p, int64_t close_row_p, int32_t pos_p) {
+    return seg != seg_p || (close_row >> 16) != (close_row_p >> 16) || (pos >> 16) != (pos_p >> 16);
+}
+
 // The slot means of the m calls behind the narrow columns.  A slot mean is very often fl(d / 10^4) for an integer d -- every
 // slot that holds ONE event is (its value is fl((E4 - M4) / 10^4), section 2 of DESIGN.md), 53 % of the slots of the headline
 // workload -- and then d travels, 32 bits, and the host divides again (IEEE division: the same double); the others travel
@@ -563,7 +600,7 @@ void mc_launch_pack(const DevRecords &O, const Counters *cnt, const unsigned lon
                     int close32, Counters *host_status, int holes, int look, hipStream_t st, hipEvent_t stop);
 bool mc_launch_side(const DevMlp &M, bool other_classifier, int n_cu, hipStream_t st, const K1Args &A, const Payload *sorted, const int32_t *seg_read,
                     const double *qual, int64_t cap, int score, unsigned char *out, size_t out_bytes, int close32, Counters *host_status,
-                    int piece_room, int64_t n_pieces, hipEvent_t stop);
+                    int piece_room, int64_t n_pieces, hipEvent_t stop, int narrow);
 
 // ---- rows of text on the device (mc_rowtext.hip) ----
 // a segment as the device parser leaves it (mc_devparse.inc): first row, where its read name stands in the shard's text, contig

@@ -103,6 +103,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MC_EMIT_WAV
     const int64_t r = P.r;
     const int m = P.m;
     const bool window = live && !(P.flags & PF_EXTRA);
+    // narrow records (narrow_layout): the packing needs the run starts of every packing chunk, and a record starts a run when its
+    // key differs from its predecessor's.  The predecessor's RECORD may be another wave's and not written yet -- its PAYLOAD is there
+    // (k1_list is through), and the key is the payload's: site, closing row, the block's segment.  The groups of a wave hold
+    // consecutive records, so the predecessor is the group below; the wave's first group asks for the payload in front of the wave's
+    // (one address for the wave: scalar loads, in flight beside everything else)
+    const int64_t q_before = max(tw / EG - 1, (int64_t)0);
+    const int32_t nb_before = sorted[q_before].nb, m_before = sorted[q_before].m;
+    const int32_t ch_before = (int32_t)(sorted[q_before].close_row >> 16);
+    const int32_t seg_before = T.nb_seg_begin[nb_before];
     // ---- everything the payload addresses, in ONE round trip: what every window needs of the name block's descriptor (28 of its
     // 64 bytes, the eight lanes of a group the same ones), the segment of the block, and the rows before the window's last row -- lane l of the group looks
     // at rows r-l, r-l-8, r-l-16, r-l-24: four independent loads of the position and of the flag byte, eight consecutive rows
@@ -130,6 +139,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MC_EMIT_WAV
     asm volatile("" : "+v"(d_rb.x), "+v"(d_rb.y), "+v"(d_1.x), "+v"(d_1.y), "+v"(d_1.z), "+v"(d_1.w), "+v"(d_sdel),
                       "+v"(seg_of), "+v"(pj[0]), "+v"(pj[1]), "+v"(pj[2]), "+v"(pj[3]), "+v"(fj[0]), "+v"(fj[1]), "+v"(fj[2]), "+v"(fj[3]));
     EM_STAMP(1);
+    bool run_start;
+    {
+        const int32_t ch = (int32_t)(P.close_row >> 16);
+        int32_t seg_p = __shfl_up(seg_of, EG), m_p = __shfl_up(m, EG), ch_p = __shfl_up(ch, EG);
+        if (lane_now < EG) { seg_p = seg_before; m_p = m_before; ch_p = ch_before; }
+        run_start = live && s == 0 && (q == 0 || seg_of != seg_p || ch != ch_p || (m >> 16) != (m_p >> 16));
+    }
     const int64_t d_row_begin = ((int64_t)(uint32_t)d_rb.x) | ((int64_t)d_rb.y << 32), d_mask_off = ((int64_t)(uint32_t)d_1.x) | ((int64_t)d_1.y << 32);
     const int64_t d_first = d_1.z < 0 ? -1 : d_row_begin + d_1.z;         // (NbDesc::first())
     const int64_t Lc = d_1.w;
@@ -324,7 +340,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MC_EMIT_WAV
         }
         A.O.info[q] = info_out;
     }
-    count_wave_for_packing(A.chunk_cnt, n_rec, kept_rec, q, wide_bit, k);       // (the packing's counts, k_pack)
+    count_wave_for_packing(A.chunk_cnt, n_rec, kept_rec, q, wide_bit, k, run_start);       // (the packing's counts, k_pack)
     EM_STAMP(5);
     ++em_round;
     }

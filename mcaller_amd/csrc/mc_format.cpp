@@ -206,18 +206,57 @@ inline int32_t seg_of_row(const mc_table_view *t, int64_t r) {
     return (int32_t)(std::upper_bound(b, e, r) - b) - 1;
 }
 
-// marked context of record j into ctx[0..2k-1); false: the host has to handle this record
-inline bool build_context(const mc_format_args *a, int64_t j, char *ctx) {
-    const mc_calls_view *rec = a->rec;
+// The four record columns of a view, whichever way they travelled: in full, or as "narrow records" (mc_calls_view.close_lo16) --
+// 16-bit halves per record and a run list that holds the segment and the high halves.  A walk over ascending records carries
+// the run along (to); a thread that starts in the middle finds its run by bisection (seek).
+inline uint32_t info_of(const mc_calls_view *rec, int64_t j) {
+    return rec->info_lo16 ? ((uint32_t)rec->info_lo16[j] | ((uint32_t)rec->info_next[j] << 16)) : rec->info[j];
+}
+struct RecCols {
+    const mc_calls_view *rec;
+    bool narrow;
+    int64_t run;            // narrow records: the entry that holds the record asked for last
+    explicit RecCols(const mc_calls_view *r) : rec(r), narrow(r->close_lo16 != nullptr), run(0) {}
+    RecCols(const mc_calls_view *r, int64_t first) : RecCols(r) { seek(first); }
+    void seek(int64_t j) {
+        if (!narrow) return;
+        int64_t lo = 0, hi = rec->n_runs - 1;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi + 1) >> 1;
+            if (rec->runs[4 * mid] <= j) lo = mid; else hi = mid - 1;
+        }
+        run = lo;
+    }
+    void to(int64_t j) {
+        if (narrow) while (run + 1 < rec->n_runs && rec->runs[4 * (run + 1)] <= j) ++run;
+    }
+    // (of the record `to` or `seek` was called for last)
+    int32_t seg(int64_t j) const { return narrow ? rec->runs[4 * run + 1] : rec->site_seg[j]; }
+    int32_t pos(int64_t j) const { return narrow ? (int32_t)(((uint32_t)rec->runs[4 * run + 3] << 16) | rec->pos_lo16[j]) : rec->site_pos[j]; }
+    int64_t close(int64_t j) const {
+        if (narrow) return (int64_t)rec->runs[4 * run + 2] * 65536 + rec->close_lo16[j];
+        return rec->close_row ? rec->close_row[j] : (int64_t)rec->close_row32[j];
+    }
+};
+// a view's record columns are there, in one layout or the other; narrow records: the run list begins at record 0, ascends and stays below n
+bool record_columns_ok(const mc_calls_view *rec, int64_t n) {
+    if (n <= 0) return true;
+    if (!rec->close_lo16) return rec->info && rec->site_pos && rec->site_seg && (rec->close_row || rec->close_row32);
+    if (!rec->pos_lo16 || !rec->info_lo16 || !rec->info_next || !rec->runs || rec->n_runs < 1 || rec->n_runs > n || rec->runs[0] != 0) return false;
+    for (int64_t r = 1; r < rec->n_runs; ++r)
+        if (rec->runs[4 * r] <= rec->runs[4 * (r - 1)] || rec->runs[4 * r] >= n) return false;
+    return true;
+}
+
+// marked context of a record (its info word, segment and site position) into ctx[0..2k-1); false: the host has to handle this record
+inline bool build_context(const mc_format_args *a, uint32_t info, int32_t seg, int32_t site_pos, char *ctx) {
     const mc_ref_view *ref = a->ref;
     const int k = a->k;
-    const uint32_t info = rec->info[j];
     if (info & MC_I_EDGE) return false;
-    const int32_t seg = rec->site_seg[j];
     if (seg < 0 || seg >= a->table->n_seg) return false;
     const int32_t cid = a->table->seg_contig[seg];
     if (cid < 0 || cid >= ref->n_contigs) return false;
-    const int64_t L = ref->contig_len[cid], m = rec->site_pos[j];
+    const int64_t L = ref->contig_len[cid], m = site_pos;
     const int64_t lo = m - k + 1, hi = m + k;           // last_ref[mpos-k+1 : mpos+k]  (:194)
     if (lo < 0 || hi > L) return false;
     const bool rev = info & MC_I_REV;
@@ -241,14 +280,10 @@ inline bool build_context(const mc_format_args *a, int64_t j, char *ctx) {
     return true;
 }
 
-inline int64_t close_row_of(const mc_calls_view *rec, int64_t j) {
-    return rec->close_row ? rec->close_row[j] : (int64_t)rec->close_row32[j];
-}
-
 // records [lo, hi) without MC_I_TOO_MANY
 int64_t kept_in(const mc_calls_view *rec, int64_t lo, int64_t hi) {
     int64_t kept = 0;
-    for (int64_t j = lo; j < hi; ++j) kept += (rec->info[j] & MC_I_TOO_MANY) ? 0 : 1;
+    for (int64_t j = lo; j < hi; ++j) kept += (info_of(rec, j) & MC_I_TOO_MANY) ? 0 : 1;
     return kept;
 }
 
@@ -271,7 +306,7 @@ struct RowCursor {
     // (the caller has counted: kept records before `first`, wide slots of the call rows before the first one of this walk)
     RowCursor(const mc_calls_view *r, int64_t kept_before, int64_t wide_before_)
         : rec(r), kept(kept_before), wide(wide_before_), wide_known(true) {}
-    // (call for every record in order; info = rec->info[j])
+    // (call for every record in order; info = the record's info word)
     int64_t row(int64_t j, uint32_t info) {
         if (!rec->compacted) return j;
         if (rec->call_row) return rec->call_row[j];
@@ -329,16 +364,18 @@ int64_t format_range(const Job &J, int64_t j0, int64_t j1, PartBuf &out_shared, 
     const int k = a->k;
     out.used = 0;
     RowCursor cur = start;
+    RecCols cols(rec, j0);              // (narrow records: the piece may begin in the middle of a run)
     int32_t cseg = -1;                  // (the closing rows of consecutive records ascend: the segment is carried along)
     int64_t j = j0;
     for (; j < j1; ++j) {
-        const uint32_t info = rec->info[j];
+        const uint32_t info = info_of(rec, j);
         const int64_t row = cur.row(j, info);                                      // (compacted views: mc_wait_records)
         if (info & MC_I_TOO_MANY) continue;
         if (std::isnan(rec->prob[row])) break;                                     // (scored by the host)
-        const int32_t seg = rec->site_seg[j];
+        cols.to(j);
+        const int32_t seg = cols.seg(j);
         const int32_t rid = t->seg_read[seg];
-        const int64_t crow = close_row_of(rec, j);
+        const int64_t crow = cols.close(j);
         if (cseg < 0 || crow < t->seg_row_begin[cseg] || (cseg < t->n_seg && crow >= t->seg_row_begin[cseg + 1])) {
             if (cseg >= 0 && cseg + 1 < t->n_seg && crow >= t->seg_row_begin[cseg + 1] && crow < t->seg_row_begin[cseg + 2]) ++cseg;
             else cseg = seg_of_row(t, crow);
@@ -352,8 +389,9 @@ int64_t format_range(const Job &J, int64_t j0, int64_t j1, PartBuf &out_shared, 
         char *o = out.p + out.used;
         o = put_str(o, chrom, chrom_len); *o++ = '\t';
         o = put_str(o, a->read_names[rid], J.name_len[(size_t)rid]); *o++ = '\t';
-        o = put_int(o, rec->site_pos[j]); *o++ = '\t';
-        if (!build_context(a, j, o)) break;                                        // (the host's own handling: nothing of this row is kept)
+        const int32_t site_pos = cols.pos(j);
+        o = put_int(o, site_pos); *o++ = '\t';
+        if (!build_context(a, info, seg, site_pos, o)) break;                                        // (the host's own handling: nothing of this row is kept)
         o += 2 * k - 1;
         *o++ = '\t';
         const uint32_t empty = info & MC_I_EMPTY_MASK;
@@ -394,7 +432,8 @@ extern "C" int mc_format_diffs(const mc_format_args *a, int64_t first, int32_t n
     *n_bytes = 0;
     *n_rows = 0;
     *stop_at = first;
-    if (!a || !a->rec || !a->table || !a->ref || a->k < 1 || a->k > MC_MAX_K || first < 0 || first > a->n_records) {
+    if (!a || !a->rec || !a->table || !a->ref || a->k < 1 || a->k > MC_MAX_K || first < 0 || first > a->n_records ||
+        !record_columns_ok(a->rec, a->n_records)) {
         mc_set_error("mc_format_diffs: bad arguments");
         return -12;
     }
@@ -489,19 +528,22 @@ extern "C" int mc_format_diffs(const mc_format_args *a, int64_t first, int32_t n
 // dozen numpy passes this replaces were 1 ms of interpreter lock per shard, taken from the other helper and from the main thread.
 extern "C" int mc_count_records(const mc_calls_view *rec, int64_t n, const int32_t *seg_read, int64_t n_seg, int64_t *counts3,
                                 int32_t *ascending, uint8_t *pos_marks, int64_t n_marks, int64_t *pos_min, int64_t *pos_top) {
-    if (!rec || n < 0 || (n > 0 && (!rec->info || !rec->site_pos || !rec->site_seg)) || (counts3 && !seg_read)) {
+    if (!rec || n < 0 || (counts3 && !seg_read) ||
+        (n > 0 && (rec->close_lo16 ? !record_columns_ok(rec, n) : (!rec->info || !rec->site_pos || !rec->site_seg)))) {
         mc_set_error("mc_count_records: bad arguments");
         return -12;
     }
+    RecCols cols(rec);
     int64_t too = 0, wskips = 0, multi = 0, lo_pos = INT64_MAX, top = 0;
     bool asc = true;
     int64_t prev_key = INT64_MIN;
     for (int64_t j = 0; j < n; ++j) {
-        const uint32_t info = rec->info[j];
-        const int32_t pos = rec->site_pos[j];
+        const uint32_t info = info_of(rec, j);
+        cols.to(j);
+        const int32_t pos = cols.pos(j);
         const bool is_too = (info & MC_I_TOO_MANY) != 0;
         if (counts3) {
-            const int32_t seg = rec->site_seg[j];
+            const int32_t seg = cols.seg(j);
             if (seg < 0 || seg >= n_seg) { mc_set_error("mc_count_records: record %lld names segment %d of %lld", (long long)j, seg, (long long)n_seg); return -12; }
             const int64_t key = ((int64_t)seg_read[seg] << 32) | (int64_t)(uint32_t)pos;
             asc = asc && key > prev_key;
@@ -525,7 +567,8 @@ extern "C" int mc_count_records(const mc_calls_view *rec, int64_t n, const int32
 
 extern "C" int mc_calls_expand(const mc_calls_view *rec, int64_t n, int32_t k, int32_t *call_row_out, int64_t *close_row_out,
                                double *feats_out) {
-    if (!rec || n < 0 || (n > 0 && !rec->info) || (close_row_out && n > 0 && !rec->close_row && !rec->close_row32) ||
+    if (!rec || n < 0 || (n > 0 && !rec->info && !rec->close_lo16) || (n > 0 && rec->close_lo16 && !record_columns_ok(rec, n)) ||
+        (close_row_out && n > 0 && !rec->close_row && !rec->close_row32 && !rec->close_lo16) ||
         (feats_out && (k < 1 || k > MC_MAX_K || (!rec->feats && !(rec->feats_lo32 && rec->feats_wide))))) {
         mc_set_error("mc_calls_expand: bad arguments");
         return -12;
@@ -560,14 +603,16 @@ extern "C" int mc_calls_expand(const mc_calls_view *rec, int64_t n, int32_t k, i
     mc_parallel_for(nt, [&](int w) {
         int64_t lo, hi;
         piece(w, lo, hi);
-        if (close_row_out)
-            for (int64_t j = lo; j < hi; ++j) close_row_out[j] = close_row_of(rec, j);
+        if (close_row_out) {
+            RecCols cols(rec, lo);
+            for (int64_t j = lo; j < hi; ++j) { cols.to(j); close_row_out[j] = cols.close(j); }
+        }
         if (call_row_out) {
             int64_t row = kept[(size_t)w];
             for (int64_t j = lo; j < hi; ++j) {
                 if (!rec->compacted) call_row_out[j] = (int32_t)j;
                 else if (rec->call_row) call_row_out[j] = rec->call_row[j];
-                else call_row_out[j] = (rec->info[j] & MC_I_TOO_MANY) ? -1 : (int32_t)row++;
+                else call_row_out[j] = (info_of(rec, j) & MC_I_TOO_MANY) ? -1 : (int32_t)row++;
             }
         }
         if (feats_out) {
@@ -580,6 +625,27 @@ extern "C" int mc_calls_expand(const mc_calls_view *rec, int64_t n, int32_t k, i
                 cur.wide_known = true;
                 for (int64_t r = r0; r < r1; ++r) cur.feats(r, k, feats_out + r * k);
             }
+        }
+    });
+    return 0;
+}
+
+extern "C" int mc_records_expand(const mc_calls_view *rec, int64_t n, int32_t *site_pos_out, int32_t *site_seg_out, uint32_t *info_out,
+                                 int64_t *close_row_out) {
+    if (!rec || n < 0 || !record_columns_ok(rec, n)) {
+        mc_set_error("mc_records_expand: bad arguments");
+        return -12;
+    }
+    const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(mc_host_cores(), n / 16384));
+    mc_parallel_for(nt, [&](int w) {
+        const int64_t lo = n * w / nt, hi = n * (w + 1) / nt;
+        RecCols cols(rec, lo);
+        for (int64_t j = lo; j < hi; ++j) {
+            cols.to(j);
+            if (site_pos_out) site_pos_out[j] = cols.pos(j);
+            if (site_seg_out) site_seg_out[j] = cols.seg(j);
+            if (info_out) info_out[j] = info_of(rec, j);
+            if (close_row_out) close_row_out[j] = cols.close(j);
         }
     });
     return 0;

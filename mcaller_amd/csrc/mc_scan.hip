@@ -1156,7 +1156,7 @@ __global__ __launch_bounds__(256) void k1_list(K1Args A, Payload *__restrict__ s
     MC_FRONT_OF_THE_QUEUE;
     const DevTable &T = A.T;
     if (A.chunk_cnt && blockIdx.x == 0)              // (the packing's counts: the emit behind this kernel adds them up)
-        for (int i = threadIdx.x; i < PACK_WGS; i += blockDim.x) { A.chunk_cnt[PACK_PAD * i] = 0ull; A.chunk_cnt[PACK_PAD * i + 1] = 0ull; }
+        for (int i = threadIdx.x; i < PACK_WGS; i += blockDim.x) { A.chunk_cnt[PACK_PAD * i] = 0ull; A.chunk_cnt[PACK_PAD * i + 1] = 0ull; A.chunk_cnt[PACK_PAD * i + PACK_RUNS_LANE] = 0ull; }
     constexpr int LG = 8;
     const int64_t tile = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / LG;
     const int l = threadIdx.x & (LG - 1);

@@ -443,6 +443,9 @@ extern "C" int mc_fetch_records_view(mc_ctx *c, mc_calls_view *out) {
     out->close_row32 = nullptr;
     out->compacted = 0;
     out->feats_lo32 = nullptr; out->feats_hi32 = nullptr; out->feats_wide = nullptr; out->n_wide = 0;
+    out->close_lo16 = nullptr; out->pos_lo16 = nullptr; out->info_lo16 = nullptr; out->info_next = nullptr;
+    out->runs = nullptr; out->n_runs = 0;
+    out->copy_out_bytes = 0;          // (a synchronous pass: six plain copies, nothing packed)
     return 0;
 }
 
@@ -471,7 +474,7 @@ static int ensure_async_buf(mc_ctx *c, AsyncBuf &b, int64_t cap, int k, int64_t 
         b.n_nb = nb;
     }
     if (pack_rec <= 0 || pack_rec > cap) pack_rec = cap;
-    const size_t pack_bytes = std::max((size_t)pack_rec * (20 + ((size_t)k + 1) * 8 + 1) + 128, c->pack_min_bytes);       // (every slot mean 64 bits wide at worst, a mask byte per call)
+    const size_t pack_bytes = std::max((size_t)pack_rec * (24 + ((size_t)k + 1) * 8 + 1) + 128, c->pack_min_bytes);       // (every slot mean 64 bits wide at worst, a mask byte per call; narrow records, every record a run of its own: 23 bytes)
     if (b.cap >= cap && b.k == k && b.pack_bytes >= pack_bytes) return 0;
     if (b.used) HIP_TRY(hipEventSynchronize(b.ev[EV_DONE]));
     b.dev_allocs.clear();
@@ -527,9 +530,16 @@ static int enqueue_side(mc_ctx *c, AsyncBuf &b, const K1Args &A, bool *done) {
     if (b.prm.score && c->clf.kind != Classifier::MLP) return 0;
     HIP_TRY(hipStreamWaitEvent(st, b.ev[EV_EMIT_END], 0));
     if (b.timed || !MC_EVENTS_ON_KERNELS) HIP_TRY(hipEventRecord(b.ev[EV_K2_START], st));
+    // narrow records (narrow_layout) for what the side kernel packs record by record: not the pieces of a fused dense pass, not 64-bit
+    // closing rows, not a pass whose rows the device writes as text (mc_rowtext.hip reads the wide columns on the device).
+    // (MCALLER_NARROW_RECORDS=0: tests, profiles -- the wide columns; read per pass)
+    const bool narrow_off = getenv("MCALLER_NARROW_RECORDS") && atoi(getenv("MCALLER_NARROW_RECORDS")) == 0;
+    b.narrow = !narrow_off && b.fused_room == 0 && b.close32 && !b.want_text;
     if (!mc_launch_side(c->clf.M, other, c->n_cu, st, A, b.B.sorted, T.seg_read, c->qual, b.cap, b.prm.score ? 1 : 0, b.pack, b.pack_bytes, b.close32 ? 1 : 0, (Counters *)b.st.dev,
-                        b.fused_room, b.fused_room > 0 ? b.slots / b.fused_room : 0, MC_EVENTS_ON_KERNELS ? b.ev[EV_DONE] : nullptr))
+                        b.fused_room, b.fused_room > 0 ? b.slots / b.fused_room : 0, MC_EVENTS_ON_KERNELS ? b.ev[EV_DONE] : nullptr, b.narrow ? 1 : 0)) {
+        b.narrow = false;
         return 0;           // (the wait and the event stay where they are: harmless in front of the three kernels)
+    }
     if (!MC_EVENTS_ON_KERNELS) HIP_TRY(hipEventRecord(b.ev[EV_DONE], st));
     HIP_TRY(hipGetLastError());
     *done = true;
@@ -565,6 +575,7 @@ extern "C" int mc_extract_features_async(mc_ctx *c, const mc_params *prm) {
         b.B.pass_no = ++c->pass_counter;
         b.used = false;
         b.want_text = 0; b.text_block = -1;
+        b.narrow = false;
         b.fused_room = 0; b.slots = 0;
         b.slot = -1;
         c->ab_head = (c->ab_head + 1) % MC_PASSES_IN_FLIGHT;
@@ -633,6 +644,7 @@ extern "C" int mc_extract_features_async(mc_ctx *c, const mc_params *prm) {
     b.want_text = c->rt.on;
     b.text_block = -1;
     b.one_kernel = false;
+    b.narrow = false;
     if (int rc = enqueue_side(c, b, A, &b.one_kernel)) return rc;
     if (!b.one_kernel) {
         if (int rc = enqueue_k2(c, b, A)) return rc;
@@ -698,7 +710,11 @@ extern "C" int mc_wait_records_begin(mc_ctx *c) {
         const size_t m = (size_t)std::min<unsigned long long>(st.n_kept, n);
         const PackLayout L = pack_layout((int64_t)n, b.close32 ? 1 : 0);
         const size_t n_wide = (size_t)std::min<unsigned long long>(st.n_wide, (unsigned long long)m * (size_t)k);
-        const PackTail PT_ = pack_tail(L.feats, m, k, n_wide);
+        // (narrow records: the side kernel says whether the pass took them -- a run list of at least one entry -- or left the columns wide)
+        const size_t n_runs = b.narrow ? (size_t)std::min<unsigned long long>(st.n_runs, (unsigned long long)n) : 0;
+        const bool narrow = n_runs > 0;
+        const NarrowLayout NL = narrow_layout((int64_t)n, (int64_t)n_runs);
+        const PackTail PT_ = pack_tail(narrow ? NL.feats : L.feats, m, k, n_wide);
         const size_t out_bytes = PT_.end;
         if (out_bytes > b.pack_bytes) {
             mc_set_error("mc_wait_records_begin: pass %llu counts %zu bytes of records, its packed block holds %zu",
@@ -720,11 +736,18 @@ extern "C" int mc_wait_records_begin(mc_ctx *c) {
             cs = c->side_stream;
             if (int rc = mc_copy_by_kernel(pack_host, b.pack, out_bytes, cs)) return rc;
         } else HIP_TRY(hipMemcpyAsync(pack_host, b.pack, out_bytes, hipMemcpyDeviceToHost, cs));
-        b.H.close_row = b.close32 ? nullptr : reinterpret_cast<int64_t *>(pack_host);
-        b.h_close32 = b.close32 ? reinterpret_cast<int32_t *>(pack_host) : nullptr;
-        b.H.site_pos = reinterpret_cast<int32_t *>(pack_host + L.pos);
-        b.H.site_seg = reinterpret_cast<int32_t *>(pack_host + L.seg);
-        b.H.info = reinterpret_cast<uint32_t *>(pack_host + L.info);
+        b.H.close_row = (b.close32 || narrow) ? nullptr : reinterpret_cast<int64_t *>(pack_host);
+        b.h_close32 = (b.close32 && !narrow) ? reinterpret_cast<int32_t *>(pack_host) : nullptr;
+        b.H.site_pos = narrow ? nullptr : reinterpret_cast<int32_t *>(pack_host + L.pos);
+        b.H.site_seg = narrow ? nullptr : reinterpret_cast<int32_t *>(pack_host + L.seg);
+        b.H.info = narrow ? nullptr : reinterpret_cast<uint32_t *>(pack_host + L.info);
+        b.h_close_lo16 = narrow ? reinterpret_cast<const uint16_t *>(pack_host + NL.close_lo) : nullptr;
+        b.h_pos_lo16 = narrow ? reinterpret_cast<const uint16_t *>(pack_host + NL.pos_lo) : nullptr;
+        b.h_info_lo16 = narrow ? reinterpret_cast<const uint16_t *>(pack_host + NL.info_lo) : nullptr;
+        b.h_info_next = narrow ? pack_host + NL.info_next : nullptr;
+        b.h_runs = narrow ? reinterpret_cast<const int32_t *>(pack_host + NL.runs) : nullptr;
+        b.h_n_runs = (int64_t)n_runs;
+        b.h_copy_out_bytes = (int64_t)out_bytes;
         b.H.feats = nullptr;                                             // (they travel as 32-bit integers where they can)
         b.h_lo32 = reinterpret_cast<int32_t *>(pack_host + PT_.lo32);
         b.H.prob = reinterpret_cast<double *>(pack_host + PT_.prob);
@@ -836,6 +859,14 @@ extern "C" int mc_wait_records(mc_ctx *c, int64_t *n_records, mc_calls_view *out
     out->feats_wide = packed ? b.h_wmask : nullptr;
     out->n_wide = packed ? b.h_n_wide : 0;
     out->n_call_rows = n > 0 && b.used ? b.h_n_calls : 0;
+    const bool narrow = packed && b.h_n_runs > 0;
+    out->close_lo16 = narrow ? b.h_close_lo16 : nullptr;
+    out->pos_lo16 = narrow ? b.h_pos_lo16 : nullptr;
+    out->info_lo16 = narrow ? b.h_info_lo16 : nullptr;
+    out->info_next = narrow ? b.h_info_next : nullptr;
+    out->runs = narrow ? b.h_runs : nullptr;
+    out->n_runs = narrow ? b.h_n_runs : 0;
+    out->copy_out_bytes = packed ? b.h_copy_out_bytes : 0;
     return 0;
 }
 

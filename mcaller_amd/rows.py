@@ -196,10 +196,21 @@ class Finisher(object):
     def _bind(self, rec):
         n = rec.n
         self._rec = rec
-        self._info = rec.info[:n]
-        self._site_pos = rec.site_pos[:n]
-        self._seg_of = rec.site_seg[:n]
         self._lazy = None
+
+    # (read where the per-record paths need them: a shard whose rows the native formatter prints and whose counters
+    # mc_count_records makes leaves narrow records -- Records.site_pos -- as they arrived)
+    @property
+    def _info(self):
+        return self._rec.info[:self._rec.n]
+
+    @property
+    def _site_pos(self):
+        return self._rec.site_pos[:self._rec.n]
+
+    @property
+    def _seg_of(self):
+        return self._rec.site_seg[:self._rec.n]
 
     def _per_record(self):
         """(slot means [calls, k], row of every record in them or None, segment of every record's closing row): only the
@@ -383,7 +394,7 @@ def cut_names(table, rec):
     if n == 0:
         every = set(names[int(r)] for r in seg_read)
         return every, every, False
-    first_seg, last_seg = int(rec.site_seg[0]), int(rec.site_seg[n - 1])
+    first_seg, last_seg = rec.end_segments()
     return (set(names[int(r)] for r in seg_read[:first_seg + 1]), set(names[int(r)] for r in seg_read[last_seg:]), True)
 
 
