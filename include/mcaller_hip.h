@@ -1207,6 +1207,57 @@ int mc_currents_compare_last_stats(mc_ctx *ctx, mc_cur_stats *out);
 int mc_currents_compare_release(mc_ctx *ctx);
 int mc_curcombine(const double *L, const double *bound, int64_t c, double log10c, double out2[2], double *bound_out, int32_t *status);
 
+/* ===== the rows of every site split in two by their currents (mcaller_amd/cluster_sites.py; csrc/mc_linkage.h,
+ * csrc/compare/mc_sitecluster.inc) =====
+ * mc_sites_cluster: the text is the mCaller rows (.diffs, 7 or 8 fields) of one sample.  One row per key (chrom, pos, strand) with at
+ * least opt->depth usable rows among its first opt->max_depth, in the order of the keys' first rows: the rows' vectors (opt->n_columns
+ * values, the read quality left out) linked by complete linkage under opt->metric down to two clusters, the clusters' sizes and
+ * methylated rows, the heights h_top and h_sub and the adjusted Rand index of (cluster, label).  opt->mixed: the rows with
+ * min(n_1, n_2) / (n_1 + n_2) >= opt->min_minor and h_top >= opt->min_gap * h_sub also go to res->bed as BED lines.  The bytes are
+ * those of cluster_sites.cluster_sites, or the call declines -- *status = 1, mc_last_error says why (mc_sites_cluster_last_stats:
+ * line and reason), nothing is handed out and the caller runs the host statement, which words the errors.  Declines:
+ * MC_CMP_DECLINE_HIGH_BYTE, _CONTROL, _LONG_LINE, _ROWS, _MEMORY, _TABLE, _NUMBER, _PRINT (a height outside mc_rowtext.h's range) and
+ * the three _CUR_* (fewer than 2 columns is _CUR_VALUES at line 0).  A depth is never a decline.  No code for a value that is not finite:
+ * mc_decimal.h hands out no such value, it declines the token (_NUMBER).
+ * res->out and res->bed point at pinned memory owned by the context: valid until the next mc_sites_cluster call on it or
+ * mc_sites_cluster_release.  Test knobs as for mc_currents_compare (MCALLER_CMP_HASH_MASK, _TABLE_SLOTS, _DEVICE_BYTES).
+ * mc_site_cluster_host: one site by the host build of csrc/mc_linkage.h (needs no GPU): values[n, c] row-major, n <= 1024, metric
+ * MC_CLU_* -> 0: labels_out[i] = 0 (a flat row), 1 or 2, out3 = h_top, h_sub, the usable rows; 1: fewer than 2 usable rows (out3[2]
+ * alone is set); -12: bad arguments.  mc_site_ari_host: the adjusted Rand index from the clusters' sizes and methylated rows. */
+#define MC_CLU_CORRELATION 0
+#define MC_CLU_EUCLIDEAN   1
+#define MC_CLU_MAX_DEPTH   1024
+#define MC_CLU_WAVE_ROWS   64    /* up to here a wave links a site (kl_link_small)                       */
+#define MC_CLU_LDS_ROWS    141   /* up to here a workgroup keeps the distance matrix in LDS, beyond in its slab of device memory */
+typedef struct mc_clu_options {
+    int32_t depth, max_depth, metric, mixed, n_columns, pad;
+    double min_minor, min_gap;
+} mc_clu_options;
+typedef struct mc_clu_result {
+    const char *out, *bed;
+    int64_t n_out, n_bed, n_sites, n_mixed;
+} mc_clu_result;
+typedef struct mc_clu_stats {
+    int64_t n_bytes, n_lines, n_keys;
+    int64_t n_candidates;          /* keys with at least depth rows                               */
+    int64_t n_sites, n_mixed;      /* kept sites; those in the bed                                */
+    int64_t n_rows;                /* rows of the candidates                                      */
+    int64_t n_link_small, n_link_lds, n_link_slab;   /* kept sites by the kernel that linked them */
+    int64_t slab_groups, slab_bytes;                 /* persistent workgroups of the slab kernel, bytes of their slabs */
+    int64_t n_out_bytes, n_bed_bytes, table_slots;
+    int64_t decline_line;          /* 0-based line the decline names, -1: none                    */
+    int32_t decline_reason;        /* 0: not declined; MC_CMP_DECLINE_*                           */
+    int32_t longest_probe;         /* slots the longest probe of the table looked at              */
+    int32_t deepest_site;          /* usable rows of the deepest kept site                        */
+    int32_t n_columns;
+    double ms_read, ms_h2d, ms_kernels, ms_d2h, ms_total;
+} mc_clu_stats;
+int mc_sites_cluster(mc_ctx *ctx, const mc_text_source *source, const mc_clu_options *opt, mc_clu_result *res, int32_t *status);
+int mc_sites_cluster_last_stats(mc_ctx *ctx, mc_clu_stats *out);
+int mc_sites_cluster_release(mc_ctx *ctx);
+int mc_site_cluster_host(const double *values, int64_t n, int64_t c, int32_t metric, int32_t *labels_out, double out3[3]);
+double mc_site_ari_host(int64_t n1, int64_t n2, int64_t m1, int64_t m2);
+
 /* ===== methylated motifs found de novo from called sites on the GPU (mcaller_amd/find_motifs.py; csrc/motifs/mc_motifscan.hip) =====
  * mc_motif_report, with iupac = 0 and max_motifs = 0.  For every shape (a string of X and '.', first and last X, at most MC_MOTIF_MAX_WIDTH wide, 2 to 8 X), every X of it as the called
  * letter and every assignment of A, C, G, T to the X: the candidates of the reference (ref: contig_len, seq_off and the upper-cased

@@ -54,6 +54,9 @@ CmpStats = _S['mc_cmp_stats']
 CurOptions = _S['mc_cur_options']
 CurResult = _S['mc_cur_result']
 CurStats = _S['mc_cur_stats']
+CluOptions = _S['mc_clu_options']
+CluResult = _S['mc_clu_result']
+CluStats = _S['mc_clu_stats']
 ContigTable = _S['mc_contig_table']
 XmfaMapView = _S['mc_xmfa_map_view']
 XmfaStats = _S['mc_xmfa_stats']
@@ -72,6 +75,8 @@ FASTQ_DECLINE = ABI.prefixed('MC_FASTQ_DECLINE_')
 MERGE_DECLINE = ABI.prefixed('MC_MERGE_DECLINE_')
 TW_STATUS = {'bad_n': 1, 'zero_var': 2, 'far_tail': 4, 'no_convergence': 8, 'all_equal': 16, 'tie': 32, 'unprintable': 64,
              'deep': 128}                                                                        # TW_* (csrc/mc_twosample.h)
+CLU_METRIC = {'correlation': _K['MC_CLU_CORRELATION'], 'euclidean': _K['MC_CLU_EUCLIDEAN']}
+CLU_WAVE_ROWS, CLU_LDS_ROWS, CLU_MAX_DEPTH = _K['MC_CLU_WAVE_ROWS'], _K['MC_CLU_LDS_ROWS'], _K['MC_CLU_MAX_DEPTH']
 CC_STATUS = {'nan': 1, 'range': 2, 'tie': 4, 'unprintable': 8}                                 # CC_* (csrc/mc_curcombine.h)
 TW_NAMES = ('U', 'z_mwu', 'z_rs', 't', 'D', 'nlp_mwu', 'nlp_rs', 'nlp_t', 'nlp_ks')
 
@@ -706,6 +711,26 @@ def curcombine(L, bound, log10c):
     if rc != 0:
         raise ValueError('mc_curcombine: %d' % rc)
     return float(out[0]), float(out[1]), float(b.value), int(st.value)
+
+
+def site_cluster(values, metric='correlation'):
+    """cluster_sites' split of one site (values [n, c], n <= 1024) by mc_linkage.h's host build -> None when fewer than 2 rows are
+    usable, else (labels: int32 [n], 0 a flat row, 1 or 2; h_top; h_sub)."""
+    X = np.ascontiguousarray(values, dtype=np.float64)
+    if X.ndim != 2 or metric not in CLU_METRIC:
+        raise ValueError('site_cluster: values [n, c] and a metric of correlation or euclidean')
+    labels, out = np.zeros(X.shape[0], dtype=np.int32), np.zeros(3)
+    rc = lib().mc_site_cluster_host(X.ctypes.data, X.shape[0], X.shape[1], CLU_METRIC[metric], labels.ctypes.data, out.ctypes.data)
+    if rc == 1:
+        return None
+    if rc != 0:
+        raise ValueError('mc_site_cluster_host: %d' % rc)
+    return labels, float(out[0]), float(out[1])
+
+
+def site_ari(n1, n2, m1, m2):
+    """The adjusted Rand index of (cluster, methylated) by mc_linkage.h's host build (nan: counts that are none)."""
+    return lib().mc_site_ari_host(int(n1), int(n2), int(m1), int(m2))
 
 
 def hypergeom_round4(v):

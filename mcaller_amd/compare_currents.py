@@ -54,9 +54,10 @@ TESTS = ('mwu', 'rs', 't', 'ks')
 last_compare = None
 
 
-def read_rows(path, nv=None):
+def read_rows(path, nv=None, min_values=2, labels=False):
     """{(chrom, pos, strand): [context of the first row, [values of a row, ...]]} of a .diffs file in the order of the keys' first rows,
-    and the number of values of a row (nv: what it has to be, None: that of the first row)."""
+    and the number of values of a row (nv: what it has to be, None: that of the first row).  labels (cluster_sites): a third list per
+    site, True where the row's label starts with 'm', and a value that is not finite is a ValueError too."""
     sites = {}
     with open(path, 'r') as fh:
         for no, line in enumerate(fh, 1):
@@ -69,15 +70,19 @@ def read_rows(path, nv=None):
                 raise ValueError('%s line %d: a value that is no number' % (path, no))
             if nv is None:
                 nv = len(values)
-            if len(values) != nv or nv < 2:
-                raise ValueError('%s line %d: %d values, %s' % (path, no, len(values), 'at least 2 are needed' if nv < 2 else
-                                                                '%d are expected' % nv))
+            if len(values) != nv or nv < min_values:
+                raise ValueError('%s line %d: %d values, %s' % (path, no, len(values), 'at least %d are needed' % min_values if nv < min_values
+                                                                else '%d are expected' % nv))
+            if labels and not all(v - v == 0.0 for v in values):
+                raise ValueError('%s line %d: a value that is not finite' % (path, no))
             try:
                 int(f[2])
             except ValueError:
                 raise ValueError('%s line %d: a position that is no integer' % (path, no))
-            site = sites.setdefault((f[0], f[2], f[5]), [f[3], []])
+            site = sites.setdefault((f[0], f[2], f[5]), [f[3], [], []] if labels else [f[3], []])
             site[1].append(values[:-1])
+            if labels:
+                site[2].append(f[6][:1] == 'm')
     return sites, nv
 
 

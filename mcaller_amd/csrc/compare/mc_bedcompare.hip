@@ -6,7 +6,8 @@
 // Two genomes with their own assemblies are compared through a Mauve alignment: mc_xmfamap.inc, included below, builds the coordinate
 // map from the XMFA text (kx_*) and lifts bed1's lines onto bed2's keys (kc_lift, in kc_probe's place; mc_bed_compare's contig tables); its
 // header comment lists its declines (MC_CMP_DECLINE_XMFA_*, MC_CMP_DECLINE_LIFT_START) and its kernels' resources.
-// A native sample against a control, site by site and without a model (compare_currents), is mc_curcompare.inc, included last (kn_*).
+// A native sample against a control, site by site and without a model (compare_currents), is mc_curcompare.inc (kn_*); the rows of one
+// sample's sites split in two by their currents (cluster_sites) are mc_sitecluster.inc, included last (kl_*).
 // Fisher's exact test on the sites' counts and the Benjamini-Hochberg q-values of every -log10 p column (compare_genomes --fisher
 // --fdr; mc_bed_compare_with's options) are mc_cmpfdr.inc, included behind it: its kernels run between kc_finish and kc_size and hand
 // kc_size / kc_write the columns behind nlp_ks.  Their declines:
@@ -562,6 +563,7 @@ int launch_ranks(hipStream_t st, const RankArgs &R) {
 #include "mc_xmfamap.inc"
 #include "mc_cmpfdr.inc"
 #include "mc_curcompare.inc"
+#include "mc_sitecluster.inc"
 
 // The texts are on the device (d_text[0, n): bed1's, a newline if it lacked its last, bed2's from off2 on; padded): everything behind that
 // (lift: the device side of a lifted comparison, nullptr: keys are matched as they stand)
@@ -864,6 +866,36 @@ extern "C" int mc_currents_compare_release(mc_ctx *c) {
     HIP_TRY(hipStreamSynchronize(c->up_stream));
     c->cur_out.reset(); c->cur_out_cap = 0;
     c->cur_bed.reset(); c->cur_bed_cap = 0;
+    c->text_stages.release();
+    return 0;
+}
+
+// the rows of a sample's sites split in two by their currents (mc_sitecluster.inc)
+extern "C" int mc_sites_cluster(mc_ctx *c, const mc_text_source *source, const mc_clu_options *opt, mc_clu_result *res, int32_t *status) {
+    if (!c || !opt || !res || !status || opt->depth < 2 || opt->max_depth < 2 || opt->max_depth > MC_CLU_MAX_DEPTH ||
+        (opt->metric != MC_CLU_CORRELATION && opt->metric != MC_CLU_EUCLIDEAN) || opt->n_columns < 0 || opt->n_columns > 65535 ||
+        !(opt->min_minor == opt->min_minor) || !(opt->min_gap == opt->min_gap)) {
+        mc_set_error("mc_sites_cluster: bad arguments");
+        return -12;
+    }
+    mc_text_source src = {};
+    if (int rc = text_source("mc_sites_cluster", source, &src)) return rc;
+    return clu_call(c, src, *opt, res, status);
+}
+
+extern "C" int mc_sites_cluster_last_stats(mc_ctx *c, mc_clu_stats *out) {
+    if (!c || !out) { mc_set_error("mc_sites_cluster_last_stats: bad arguments"); return -12; }
+    *out = c->clu_stats;
+    return 0;
+}
+
+extern "C" int mc_sites_cluster_release(mc_ctx *c) {
+    if (!c) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipStreamSynchronize(c->up_stream));
+    c->clu_out.reset(); c->clu_out_cap = 0;
+    c->clu_bed.reset(); c->clu_bed_cap = 0;
     c->text_stages.release();
     return 0;
 }

@@ -344,6 +344,10 @@ struct mc_ctx {
     Pinned cur_out, cur_bed;
     size_t cur_out_cap = 0, cur_bed_cap = 0;
     mc_cur_stats cur_stats = {};
+    // ... the rows and the BED lines of a sample's sites split in two by their currents (compare/mc_sitecluster.inc)
+    Pinned clu_out, clu_bed;
+    size_t clu_out_cap = 0, clu_bed_cap = 0;
+    mc_clu_stats clu_stats = {};
     // ... the coordinate map of an XMFA alignment (compare/mc_xmfamap.inc): on the device from mc_xmfa_map until the next such
     // call or mc_xmfa_map_release; map[g1] = ordinal << 33 | g2 << 1 | flip, ~0: unmapped.  The view's host copies are pinned
     Pool xmfa_allocs{"alignment map"};

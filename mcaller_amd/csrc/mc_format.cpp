@@ -16,6 +16,7 @@
 #include "mc_bh.h"
 #include "mc_twosample.h"
 #include "mc_curcombine.h"
+#include "mc_linkage.h"
 #include "mc_npsum.h"
 #include "../../include/mcaller_hip.h"
 
@@ -823,6 +824,35 @@ extern "C" int mc_curcombine(const double *L, const double *bound, int64_t c, do
     if (!L || !bound || !out2 || !bound_out || !status || c < 1) return -12;
     *status = cc_combine(L, bound, c, 1, log10c, &out2[0], bound_out, &out2[1]);
     return 0;
+}
+
+// cluster_sites' split of one site by mc_linkage.h's host build (include/mcaller_hip.h): values[n, c] row-major
+extern "C" int mc_site_cluster_host(const double *values, int64_t n, int64_t c, int32_t metric, int32_t *labels_out, double out3[3]) {
+    if (!values || !labels_out || !out3 || n < 1 || n > LK_MAX_ROWS || c < 2 || c > 65535 || (metric != LK_CORRELATION && metric != LK_EUCLIDEAN))
+        return -12;
+    std::vector<double> U((size_t)n * (size_t)c);
+    std::vector<int> rows;
+    for (int64_t i = 0; i < n; ++i) {
+        labels_out[i] = 0;
+        if (lk_prepare(values + i * c, 1, (int)c, metric, U.data() + rows.size() * (size_t)c, 1)) rows.push_back((int)i);
+    }
+    const int m = (int)rows.size();
+    out3[2] = (double)m;
+    if (m < 2) return 1;
+    const long long pitch = m | 1;
+    std::vector<double> M((size_t)m * (size_t)pitch, 0.0);
+    for (int i = 0; i < m; ++i)
+        for (int j = 0; j < m; ++j)
+            if (i != j) M[i * pitch + j] = lk_dist(U.data() + (size_t)i * c, U.data() + (size_t)j * c, (int)c, metric);
+    std::vector<int> work(m);
+    std::vector<uint8_t> label(m);
+    lk_link(M.data(), pitch, m, work.data(), label.data(), &out3[0], &out3[1]);
+    for (int i = 0; i < m; ++i) labels_out[rows[i]] = label[i];
+    return 0;
+}
+extern "C" double mc_site_ari_host(int64_t n1, int64_t n2, int64_t m1, int64_t m2) {
+    if (n1 < 1 || n2 < 1 || n1 + n2 > LK_MAX_ROWS || m1 < 0 || m2 < 0 || m1 > n1 || m2 > n2) return __builtin_nan("");
+    return lk_ari(n1, n2, m1, m2);
 }
 
 // the attributes of make_bed --gff --vo by mc_npsum.h's host build (include/mcaller_hip.h): p[0, n) the probabilities in row order

@@ -1079,6 +1079,48 @@ class Device(object):
     def currents_compare_release(self):
         check(lib().mc_currents_compare_release(self._ctx))
 
+    # ---- the rows of every site split in two by their currents (csrc/compare/mc_sitecluster.inc) ----
+    @_serialized
+    def sites_cluster(self, path=None, text=None, depth=15, max_depth=256, metric='correlation', mixed=False, min_minor=0.2, min_gap=2.0):
+        """The rows of cluster_sites for a .diffs file (`path`) or its text (`text`, bytes), made on the GPU -> (blob: bytes, bed:
+        bytes, n_sites, n_mixed, None), or (None, None, 0, 0, reason) when the device declines: the caller runs the host statement.
+        mixed: the rows whose smaller cluster holds at least `min_minor` of the rows and whose h_top is at least `min_gap` times
+        h_sub are the bed's lines."""
+        if (path is None) == (text is None):
+            raise ValueError('sites_cluster: a path or a text')
+        if metric not in _lib.CLU_METRIC:
+            raise ValueError('sites_cluster: metric is correlation or euclidean')
+        if int(depth) < 2 or not 2 <= int(max_depth) <= _lib.CLU_MAX_DEPTH:
+            raise ValueError('sites_cluster: a depth of at least 2 and a max_depth of 2 to %d' % _lib.CLU_MAX_DEPTH)
+        # c from the first row: the values of a row less the read quality
+        if path is not None:
+            with open(path, 'rb') as fh:
+                first = fh.readline()
+        else:
+            first = bytes(text).split(b'\n', 1)[0]
+        fields = first.split(b'\t')
+        c = fields[4].count(b',') if len(fields) in (7, 8) else 0
+        opt = _lib.CluOptions(int(depth), int(max_depth), _lib.CLU_METRIC[metric], int(bool(mixed)), min(c, 65535), 0, float(min_minor),
+                              float(min_gap))
+        res, status = _lib.CluResult(), C.c_int32()
+        src, keep = _source(path, text)
+        check(lib().mc_sites_cluster(self._ctx, src, C.byref(opt), C.byref(res), C.byref(status)))
+        del keep
+        if status.value != 0:
+            return None, None, 0, 0, last_error()
+        return ((C.string_at(res.out, res.n_out) if res.n_out else b''), (C.string_at(res.bed, res.n_bed) if res.n_bed else b''),
+                int(res.n_sites), int(res.n_mixed), None)
+
+    @_serialized
+    def sites_cluster_last_stats(self):
+        """Figures of the last sites_cluster: bytes, lines, keys, candidates, kept sites, the link kernels' shares, the slabs, the
+        decline, milliseconds."""
+        return self._last_stats(lib().mc_sites_cluster_last_stats, _lib.CluStats)
+
+    @_serialized
+    def sites_cluster_release(self):
+        check(lib().mc_sites_cluster_release(self._ctx))
+
     # ---- the coordinate map of a Mauve alignment (csrc/compare/mc_xmfamap.inc) ----
     @_serialized
     def xmfa_map(self, path=None, text=None, n1=0, seqs=(1, 2), n2=None, view=True):

@@ -389,7 +389,7 @@ def main(argv=None):
     output_file = output_file + ('.gff' if args.gff else '.bed')
     print(args.mCaller_file)
     if args.plot or args.plotsummary:
-        raise NotImplementedError('plotting is out of scope')
+        raise NotImplementedError('plotting is out of scope (the numbers behind the clustered plot: mcaller_amd.cluster_sites)')
     if args.device:
         return _main_device(args, output_file)
     summarise_diffs(args.mCaller_file, output_file, args.min_read_depth, args.mod_threshold, positions=args.positions,
