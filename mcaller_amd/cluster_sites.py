@@ -41,7 +41,7 @@ h_top >= G * h_sub (one multiplication), as
 which find_motifs --bed reads unchanged.
 
 `cluster_sites` is that definition in NumPy, column by column (the host statement).  `cluster_sites_device` (--device) has the GPU
-make the same bytes from the text (Device.sites_cluster: csrc/compare/mc_sitecluster.inc, csrc/mc_linkage.h) and runs the host
+make the same bytes from the text (Device.sites_cluster: csrc/compare/mc_sitegroup.inc, mc_sitecluster.inc, csrc/mc_linkage.h) and runs the host
 statement whenever the device declines; `last_cluster` says who made the output: dict(by='device' | 'host', reason=None | str,
 n_sites=int, n_mixed=int)."""
 import os

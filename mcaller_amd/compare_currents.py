@@ -39,7 +39,7 @@ SciPy's nan sites (fewer than 3 pooled values, a zero pooled variance, a column 
 them here; the device declines them, as it does for compare_genomes.
 
 `compare_currents` is that definition written with the SciPy calls (the host statement).  `compare_currents_device` (--device) has
-the GPU make the same bytes from the two texts (Device.currents_compare: csrc/compare/mc_curcompare.inc, csrc/mc_curcombine.h) and
+the GPU make the same bytes from the two texts (Device.currents_compare: csrc/compare/mc_sitegroup.inc, mc_curcompare.inc, csrc/mc_curcombine.h) and
 runs the host statement whenever the device declines; `last_compare` says who made the output: dict(by='device' | 'host',
 reason=None | str, n_sites=int, n_sig=int)."""
 import os

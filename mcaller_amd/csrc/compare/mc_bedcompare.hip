@@ -6,8 +6,9 @@
 // Two genomes with their own assemblies are compared through a Mauve alignment: mc_xmfamap.inc, included below, builds the coordinate
 // map from the XMFA text (kx_*) and lifts bed1's lines onto bed2's keys (kc_lift, in kc_probe's place; mc_bed_compare's contig tables); its
 // header comment lists its declines (MC_CMP_DECLINE_XMFA_*, MC_CMP_DECLINE_LIFT_START) and its kernels' resources.
-// A native sample against a control, site by site and without a model (compare_currents), is mc_curcompare.inc (kn_*); the rows of one
-// sample's sites split in two by their currents (cluster_sites) are mc_sitecluster.inc, included last (kl_*).
+// The lines of .diffs files grouped by site are mc_sitegroup.inc (kn_parse .. kn_place, SgRun); the two pipelines included behind it
+// start from it: a native sample against a control, site by site and without a model (compare_currents), is mc_curcompare.inc (the
+// other kn_*); the rows of one sample's sites split in two by their currents (cluster_sites) are mc_sitecluster.inc, included last (kl_*).
 // Fisher's exact test on the sites' counts and the Benjamini-Hochberg q-values of every -log10 p column (compare_genomes --fisher
 // --fdr; mc_bed_compare_with's options) are mc_cmpfdr.inc, included behind it: its kernels run between kc_finish and kc_size and hand
 // kc_size / kc_write the columns behind nlp_ks.  Their declines:
@@ -551,6 +552,12 @@ bool cmp_fits(size_t bytes) {
     return have > 0 ? bytes <= (size_t)have : device_fits(bytes);
 }
 
+// (tests: long probe chains) the mask every key hash of the unit is cut to: MCALLER_CMP_HASH_MASK, hexadecimal
+uint64_t cmp_hash_mask() {
+    const char *hm = getenv("MCALLER_CMP_HASH_MASK");
+    return hm && *hm ? strtoull(hm, nullptr, 16) : ~0ull;
+}
+
 int launch_ranks(hipStream_t st, const RankArgs &R) {
     if (R.S <= 0) return 0;
     hipLaunchKernelGGL(kc_rank_small, dim3((unsigned)((R.S + 3) / 4)), dim3(CR_THREADS), 0, st, R);
@@ -562,6 +569,7 @@ int launch_ranks(hipStream_t st, const RankArgs &R) {
 
 #include "mc_xmfamap.inc"
 #include "mc_cmpfdr.inc"
+#include "mc_sitegroup.inc"
 #include "mc_curcompare.inc"
 #include "mc_sitecluster.inc"
 
@@ -587,8 +595,7 @@ int cmp_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, int64_t off2, 
     CmpArgs A = {};
     A.text = d_text; A.n_bytes = n; A.off2 = off2; A.n_nl = n_nl; A.line_start = line_start; A.head = d_head;
     if (lift) { A.lifted = 1; A.lift = *lift; }
-    const char *hm = getenv("MCALLER_CMP_HASH_MASK");
-    A.hash_mask = hm && *hm ? strtoull(hm, nullptr, 16) : ~0ull;      // (tests: long probe chains)
+    A.hash_mask = cmp_hash_mask();
     if (pool.get(&A.span, cap) || pool.get(&A.hash, cap) || pool.get(&A.n_vals, cap) || pool.get(&A.match, cap) || pool.get(&A.flag, cap) ||
         pool.get(&A.site_of, cap))
         return -10;
@@ -713,8 +720,7 @@ int lift_prepare(mc_ctx *c, Pool &pool, const mc_contig_table *t1, const mc_cont
     unsigned long long *table = nullptr;
     if (int rc = table_get(pool, st, &table, T->cmask + 1)) return rc;
     T->ctable = table;
-    const char *hm = getenv("MCALLER_CMP_HASH_MASK");
-    if (T->nc1 > 0) hipLaunchKernelGGL(kc_contigs, dim3(blocks(T->nc1)), dim3(256), 0, st, *T, table, hm && *hm ? strtoull(hm, nullptr, 16) : ~0ull);
+    if (T->nc1 > 0) hipLaunchKernelGGL(kc_contigs, dim3(blocks(T->nc1)), dim3(256), 0, st, *T, table, cmp_hash_mask());
     HIP_TRY(hipGetLastError());
     return 0;
 }

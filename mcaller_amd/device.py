@@ -1037,7 +1037,7 @@ class Device(object):
         """bed1's lines without an image in the last bed_compare through an alignment (None: it declined, or had none)."""
         return getattr(self, '_unaligned', None)
 
-    # ---- a native sample against a control, site by site (csrc/compare/mc_curcompare.inc) ----
+    # ---- a native sample against a control, site by site (csrc/compare/mc_sitegroup.inc groups the lines, mc_curcompare.inc) ----
     @_serialized
     def currents_compare(self, path1=None, path2=None, text1=None, text2=None, depth=15, fdr=False, by=None, threshold=2.0):
         """The rows of compare_currents for the .diffs files of a native sample and a control (`path1`, `path2`) or their texts
@@ -1079,7 +1079,7 @@ class Device(object):
     def currents_compare_release(self):
         check(lib().mc_currents_compare_release(self._ctx))
 
-    # ---- the rows of every site split in two by their currents (csrc/compare/mc_sitecluster.inc) ----
+    # ---- the rows of every site split in two by their currents (csrc/compare/mc_sitegroup.inc groups the lines, mc_sitecluster.inc) ----
     @_serialized
     def sites_cluster(self, path=None, text=None, depth=15, max_depth=256, metric='correlation', mixed=False, min_minor=0.2, min_gap=2.0):
         """The rows of cluster_sites for a .diffs file (`path`) or its text (`text`, bytes), made on the GPU -> (blob: bytes, bed:

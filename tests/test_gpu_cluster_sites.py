@@ -179,6 +179,46 @@ def test_declines_with_reason_and_line(dev, tmp_path):
     assert device_makes_it(dev, tmp_path, far, depth=2, what='the same rows under correlation')[2] == 1
 
 
+def shared_stage_pair():
+    """Two files of 3 sites each with 3 .. 5 rows a site, the sites' rows interleaved: two shared sites, one in the native file alone (a
+    key with no control count), one in the control alone (a key no native line is the first of); the native file lacks its last newline."""
+    from tests import currents_cases as KC
+    native, control = KC.seeded_pair(2, 3, 5, seed=67, c=3)
+    return native[:-1], control
+
+
+def test_currents_and_cluster_take_turns_on_one_device(dev, tmp_path, monkeypatch):
+    """compare_currents and cluster_sites share the site-grouping stage (mc_sitegroup.inc): on one Device a comparison, a clustering of
+    its native file, and both again give the host statements' bytes each time -- nothing of one call's grouping is left for the next.
+    The keys share probe chains (four slots of hash); a key table too small declines both, and the calls behind it are as before."""
+    from mcaller_amd import compare_currents as CC
+    from tests import currents_cases as KC
+    monkeypatch.setenv('MCALLER_CMP_HASH_MASK', '3')
+    native, control = shared_stage_pair()
+    p1, p2 = KC.files(tmp_path, native, control)
+    rows, bed, n, n_sig = CC._rows(p1, p2, 3, False, 't', 0.0, True)
+    c_rows, c_bed, c_n, c_mixed = CS._rows(p1, 3, 256, 'correlation', True, 0.0, 0.0)
+    assert n == 2 and c_n == 3 and not native.endswith(b'\n')
+
+    def compare():
+        return dev.currents_compare(text1=native, text2=control, depth=3, by='t', threshold=0.0)
+
+    def cluster():
+        return dev.sites_cluster(text=native, depth=3, mixed=True, min_minor=0.0, min_gap=0.0)
+
+    first, second, third, fourth = compare(), cluster(), compare(), cluster()
+    assert first == (rows, bed or b'', n, n_sig, None), first
+    assert second == (c_rows, c_bed or b'', c_n, c_mixed, None), second
+    assert third == first and fourth == second
+    assert dev.currents_compare_last_stats()['longest_probe'] > 1 and dev.sites_cluster_last_stats()['longest_probe'] > 1
+    monkeypatch.setenv('MCALLER_CMP_TABLE_SLOTS', '2')                 # four keys, three in the native file
+    assert compare()[0] is None and cluster()[0] is None
+    assert dev.currents_compare_last_stats()['decline_reason'] == _lib.CMP_DECLINE['table']
+    assert dev.sites_cluster_last_stats()['decline_reason'] == _lib.CMP_DECLINE['table']
+    monkeypatch.delenv('MCALLER_CMP_TABLE_SLOTS')
+    assert compare() == first and cluster() == second
+
+
 def test_table_memory_and_slab_declines_then_two_calls_and_release(dev, tmp_path, monkeypatch):
     text = K.seeded_text(40, 3, 4, seed=53, c=2)
     p = K.write(tmp_path, text)

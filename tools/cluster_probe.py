@@ -4,7 +4,7 @@
 
 One `-m A`-like .diffs file to the rows of cluster_sites --mixed_bed, host statement against device, file to file on the same box:
   host    cluster_sites.cluster_sites          (NumPy distances and a merge loop per site in Python)
-  device  cluster_sites.cluster_sites_device   (csrc/compare/mc_sitecluster.inc)
+  device  cluster_sites.cluster_sites_device   (csrc/compare/mc_sitegroup.inc, mc_sitecluster.inc)
 medians of --runs after a warm-up, with mc_sites_cluster_last_stats of the last device run.  Every device file is compared with the
 host's, byte for byte, wherever the host ran (cases of up to --host-max sites).  A file the device declines is recorded with its reason
 and not timed.

@@ -5,7 +5,7 @@
 Two `-m A`-like .diffs files (a native sample and a control) to the rows of compare_currents --fdr --sig_bed, host statement against
 device, file to file on the same box:
   host    compare_currents.compare_currents          (four SciPy calls a site and column in a Python loop)
-  device  compare_currents.compare_currents_device   (csrc/compare/mc_curcompare.inc)
+  device  compare_currents.compare_currents_device   (csrc/compare/mc_sitegroup.inc, mc_curcompare.inc)
 medians of --runs after a warm-up, with mc_currents_compare_last_stats of the last device run.  Every device file is compared with the
 host's, byte for byte, wherever the host ran (cases of up to --host-max sites: the host takes milliseconds a site and column).  A pair
 the device declines is recorded with its reason and not timed.
