@@ -607,7 +607,7 @@ const char *bs_reason_text(int reason) {
 }
 
 int bs_decline(mc_ctx *c, int32_t *status, int reason, long long line) {
-    return decline(c->bed_stats, status, "summary", bs_reason_text(reason), reason, line);
+    return decline(c->bed.stats, status, "summary", bs_reason_text(reason), reason, line);
 }
 
 int bs_decline_head(mc_ctx *c, int32_t *status, const BsHead &h) {
@@ -652,7 +652,7 @@ int bs_position_set(mc_ctx *c, Pool &pool, BsArgs &A, BsHead *d_head, BsHead &h,
         hipLaunchKernelGGL(kq_parse, dim3(pb), dim3(256), 0, st, A);
         hipLaunchKernelGGL(kq_insert, dim3(pb), dim3(256), 0, st, A);
         if (fetch_head(st, d_head, h)) { *rc = -11; return 1; }
-        c->bed_stats.kernel_bytes += 3 * pn + A.p_lines * (8 + 16 + 8) * 2 + (int64_t)slots * 8;
+        c->bed.stats.kernel_bytes += 3 * pn + A.p_lines * (8 + 16 + 8) * 2 + (int64_t)slots * 8;
         if (h.decline != ~0ull) { (void)bs_decline_head(c, status, h); return 1; }
     }
     return 0;
@@ -678,7 +678,7 @@ int bs_fasta(mc_ctx *c, Pool &pool, BsArgs &A, BsHead *d_head, BsHead &h, const 
     hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)A.f_cnt, A.f_lines, A.f_off, &d_head->f_total);
     hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)(A.f_cnt + fl), A.f_lines, A.f_off + fl, &d_head->f_nrec);
     if (fetch_head(st, d_head, h)) { *rc = -11; return 1; }
-    c->bed_stats.kernel_bytes += 3 * fn + A.f_lines * 6 * 8;
+    c->bed.stats.kernel_bytes += 3 * fn + A.f_lines * 6 * 8;
     if (h.decline != ~0ull) { (void)bs_decline_head(c, status, h); return 1; }
     A.n_rec = h.f_nrec;
     const uint64_t slots = table_slots(A.n_rec, 16);
@@ -690,7 +690,7 @@ int bs_fasta(mc_ctx *c, Pool &pool, BsArgs &A, BsHead *d_head, BsHead &h, const 
     hipLaunchKernelGGL(kf_pack, dim3(wb), dim3(256), 0, st, A, A.n_rec, h.f_total);
     if (A.n_rec > 0) hipLaunchKernelGGL(kf_ids, dim3((unsigned)((A.n_rec + 255) / 256)), dim3(256), 0, st, A, A.n_rec);
     if (fetch_head(st, d_head, h)) { *rc = -11; return 1; }
-    c->bed_stats.kernel_bytes += fn + h.f_total + A.f_lines * 3 * 8 + A.n_rec * 40;
+    c->bed.stats.kernel_bytes += fn + h.f_total + A.f_lines * 3 * 8 + A.n_rec * 40;
     if (h.decline != ~0ull) { (void)bs_decline_head(c, status, h); return 1; }
     return 0;
 }
@@ -699,7 +699,7 @@ int bs_fasta(mc_ctx *c, Pool &pool, BsArgs &A, BsHead *d_head, BsHead &h, const 
 // positions text of -p (pn bytes, padded), or null; d_ftext: the FASTA text of --ref (fn bytes, padded), or null
 int bs_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *d_ptext, int64_t pn, const char *d_ftext, int64_t fn,
            const mc_bed_params *P, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status) {
-    mc_bed_stats &S = c->bed_stats;
+    mc_bed_stats &S = c->bed.stats;
     hipStream_t st = c->stream;
     HIP_TRY(hipStreamSynchronize(c->up_stream));
     const auto t_kernels = std::chrono::steady_clock::now();
@@ -860,25 +860,8 @@ int bs_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *d_p
     S.n_out_bytes = n_outb;
     S.ms_kernels = ms_since(t_kernels);
     const auto t_d2h = std::chrono::steady_clock::now();
-    if (n_outb > 0) {
-        if (int rc = grow(c->bed_out, c->bed_out_cap, (size_t)n_outb)) return rc;
-        HIP_TRY(hipMemcpyAsync(c->bed_out.p, A.out, (size_t)n_outb, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
+    if (int rc = fetch_out(c, c->bed.out, A.out, (size_t)n_outb, out, n_out)) return rc;
     S.ms_d2h = ms_since(t_d2h);
-    *out = (const char *)c->bed_out.p;
-    *n_out = n_outb;
-    return 0;
-}
-
-// what a call begins with -> 0: go on; 1: done (declined, *status set)
-int bs_begin(mc_ctx *c, const mc_bed_params *P, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status, int64_t n) {
-    c->bed_stats = mc_bed_stats();
-    c->bed_stats.decline_line = -1;
-    c->bed_stats.n_bytes = n;
-    *out = nullptr; *n_out = 0; *n_sites = 0; *status = 0;
-    if (P->gff && P->with_probs && !P->site_stats) { (void)bs_decline(c, status, MC_BED_DECLINE_OPTIONS, -1); return 1; }
-    if (!device_fits((size_t)n + 4096)) { (void)bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1); return 1; }
     return 0;
 }
 
@@ -886,24 +869,23 @@ int bs_begin(mc_ctx *c, const mc_bed_params *P, const char **out, int64_t *n_out
 // pos == null -> no -p; fa == null -> no --ref
 int bs_call(mc_ctx *c, const mc_text_source &src, const mc_text_source *pos, const mc_text_source *fa, const mc_bed_params *P,
             const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status) {
-    HIP_TRY(hipSetDevice(c->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    const int64_t pn = pos ? pos->n_bytes : 0, fn = fa ? fa->n_bytes : 0;
-    if (bs_begin(c, P, out, n_out, n_sites, status, src.n_bytes + pn + fn)) return 0;
-    c->bed_stats.n_bytes = src.n_bytes;
-    Pool pool("bed summary");
-    TextFeed feed(c, (size_t)64 << 20);
-    char *d_text = nullptr, *d_ptext = nullptr, *d_ftext = nullptr;
-    if (int rc = feed.put(pool, src, &d_text)) return rc;
-    if (pos)
-        if (int rc = feed.put(pool, *pos, &d_ptext)) return rc;
-    if (fa)
-        if (int rc = feed.put(pool, *fa, &d_ftext)) return rc;
-    feed.times(c->bed_stats, t0);
-    const int rc = bs_run(c, pool, d_text, src.n_bytes, d_ptext, pn, d_ftext, fn, P, out, n_out, n_sites, status);
-    (void)hipStreamSynchronize(c->stream);                   // (an early return: nothing of the pool is in use when it goes)
-    c->bed_stats.ms_total = ms_since(t0);
-    return rc;
+    mc_bed_stats &S = c->bed.stats;
+    return pipeline_call(c, S, status, "bed summary", (size_t)64 << 20, [&] { *out = nullptr; *n_out = 0; *n_sites = 0; }, [&](Call &K) -> int {
+        const int64_t pn = pos ? pos->n_bytes : 0, fn = fa ? fa->n_bytes : 0;
+        S.n_bytes = src.n_bytes + pn + fn;                    // (a call that declines here: the bytes of all its texts)
+        // the options first: such a call declines before any device work
+        if (P->gff && P->with_probs && !P->site_stats) return bs_decline(c, status, MC_BED_DECLINE_OPTIONS, -1);
+        if (!device_fits((size_t)S.n_bytes + 4096)) return bs_decline(c, status, MC_BED_DECLINE_MEMORY, -1);
+        S.n_bytes = src.n_bytes;
+        char *d_text = nullptr, *d_ptext = nullptr, *d_ftext = nullptr;
+        if (int rc = K.feed.put(K.pool, src, &d_text)) return rc;
+        if (pos)
+            if (int rc = K.feed.put(K.pool, *pos, &d_ptext)) return rc;
+        if (fa)
+            if (int rc = K.feed.put(K.pool, *fa, &d_ftext)) return rc;
+        K.feed.times(S, K.t0);
+        return bs_run(c, K.pool, d_text, src.n_bytes, d_ptext, pn, d_ftext, fn, P, out, n_out, n_sites, status);
+    });
 }
 
 // the probe of mc_tstat.h's device build: a lane per triple
@@ -1045,18 +1027,6 @@ extern "C" int mc_hypergeom_tail_device(mc_ctx *c, const int64_t *N, const int64
     return 0;
 }
 
-extern "C" int mc_bed_last_stats(mc_ctx *c, mc_bed_stats *out) {
-    if (!c || !out) { mc_set_error("mc_bed_last_stats: bad arguments"); return -12; }
-    *out = c->bed_stats;
-    return 0;
-}
+extern "C" int mc_bed_last_stats(mc_ctx *c, mc_bed_stats *out) { return stats_out("mc_bed_last_stats", c, out, &mc_ctx::bed, &BedPipe::stats); }
 
-extern "C" int mc_bed_release(mc_ctx *c) {
-    if (!c) return 0;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipStreamSynchronize(c->up_stream));
-    c->bed_out.reset(); c->bed_out_cap = 0;
-    c->text_stages.release();
-    return 0;
-}
+extern "C" int mc_bed_release(mc_ctx *c) { return release_pipeline(c, &mc_ctx::bed); }

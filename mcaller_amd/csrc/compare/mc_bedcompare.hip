@@ -532,11 +532,8 @@ const char *cmp_reason_text(int reason) {
 
 // file: 1, 2 or 0; line: in that file, -1: none
 int cmp_decline(mc_ctx *c, int32_t *status, int reason, int file, long long line) {
-    c->cmp_stats.decline_file = file;
-    char what[160];
-    if (file) snprintf(what, sizeof what, "%s (bed%d)", cmp_reason_text(reason), file);
-    else snprintf(what, sizeof what, "%s", cmp_reason_text(reason));
-    return decline(c->cmp_stats, status, "comparison", what, reason, line);
+    static const char *const nouns[2] = {"bed1", "bed2"};
+    return decline_in_file(c->cmp.stats, status, "comparison", cmp_reason_text(reason), nouns, reason, file, line);
 }
 
 int cmp_decline_head(mc_ctx *c, int32_t *status, const CmpHead &h) {
@@ -546,11 +543,7 @@ int cmp_decline_head(mc_ctx *c, int32_t *status, const CmpHead &h) {
 }
 
 // device_fits, or (tests) as if MCALLER_CMP_DEVICE_BYTES were all the device had free
-bool cmp_fits(size_t bytes) {
-    const char *e = getenv("MCALLER_CMP_DEVICE_BYTES");
-    const long long have = e ? atoll(e) : 0;
-    return have > 0 ? bytes <= (size_t)have : device_fits(bytes);
-}
+bool cmp_fits(size_t bytes) { return fits("MCALLER_CMP_DEVICE_BYTES", bytes); }
 
 // (tests: long probe chains) the mask every key hash of the unit is cut to: MCALLER_CMP_HASH_MASK, hexadecimal
 uint64_t cmp_hash_mask() {
@@ -577,7 +570,7 @@ int launch_ranks(hipStream_t st, const RankArgs &R) {
 // (lift: the device side of a lifted comparison, nullptr: keys are matched as they stand)
 int cmp_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, int64_t off2, const char **out, int64_t *n_out, int64_t *n_sites,
             int32_t *status, const LiftDev *lift, const mc_cmp_options *opt) {
-    mc_cmp_stats &S = c->cmp_stats;
+    mc_cmp_stats &S = c->cmp.stats;
     hipStream_t st = c->stream;
     if (n == 0) return 0;
     CmpHead *d_head = nullptr, h = {};
@@ -622,7 +615,7 @@ int cmp_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, int64_t off2, 
         if (int rc = fetch_head(st, d_head, h)) return rc;
         if (h.decline != CMP_NO_DECLINE) return cmp_decline_head(c, status, h);
         S.longest_probe = h.longest_probe;
-        c->cmp_unaligned = (int64_t)h.n_unaligned;
+        c->cmp.unaligned = (int64_t)h.n_unaligned;
     }
     const int64_t NS = h.n_sites;
     S.n_sites = NS;
@@ -682,13 +675,9 @@ int cmp_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, int64_t off2, 
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(st));
         const auto t_d2h = std::chrono::steady_clock::now();
-        if (int rc = grow(c->cmp_out, c->cmp_out_cap, ob)) return rc;
-        HIP_TRY(hipMemcpyAsync(c->cmp_out.p, A.out, ob, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        if (int rc = fetch_out(c, c->cmp.out, A.out, ob, out, n_out)) return rc;
         S.ms_d2h = ms_since(t_d2h);
         S.n_out_bytes = (int64_t)ob;
-        *out = c->cmp_out.get<char>();
-        *n_out = (int64_t)ob;
         *n_sites = NS;
         return 0;
     }
@@ -713,7 +702,7 @@ int lift_upload(Pool &pool, hipStream_t st, const mc_contig_table *t, const char
 int lift_prepare(mc_ctx *c, Pool &pool, const mc_contig_table *t1, const mc_contig_table *t2, LiftDev *T) {
     hipStream_t st = c->stream;
     *T = LiftDev();
-    T->map = c->xmfa_map; T->n1 = c->xmfa_n1; T->nc1 = t1->n_contigs; T->nc2 = t2->n_contigs;
+    T->map = c->xmfa.map; T->n1 = c->xmfa.n1; T->nc1 = t1->n_contigs; T->nc2 = t2->n_contigs;
     if (int rc = lift_upload(pool, st, t1, &T->ids1, &T->id_off1, &T->off1)) return rc;
     if (int rc = lift_upload(pool, st, t2, &T->ids2, &T->id_off2, &T->off2)) return rc;
     T->cmask = table_slots(T->nc1, 64) - 1;
@@ -734,36 +723,23 @@ bool lift_tables_ok(const mc_contig_table *t) {
 
 int cmp_call(mc_ctx *c, const mc_text_source &s1, const mc_text_source &s2, const char **out, int64_t *n_out, int64_t *n_sites, int32_t *status,
              const mc_contig_table *t1 = nullptr, const mc_contig_table *t2 = nullptr, const mc_cmp_options *opt = nullptr) {
-    HIP_TRY(hipSetDevice(c->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    c->cmp_stats = mc_cmp_stats();
-    c->cmp_unaligned = 0;
-    c->cmp_stats.decline_line = -1;
-    c->cmp_stats.n_bytes1 = s1.n_bytes; c->cmp_stats.n_bytes2 = s2.n_bytes;
-    *out = nullptr; *n_out = 0; *n_sites = 0; *status = 0;
-    if (!cmp_fits((size_t)(s1.n_bytes + s2.n_bytes) + 4096)) return cmp_decline(c, status, MC_CMP_DECLINE_MEMORY, 0, -1);
-    Pool pool("bed comparison");
-    TextFeed feed(c, (size_t)32 << 20);
-    char *d_text = nullptr, last1 = '\n';
-    if (pool.get(&d_text, (size_t)(s1.n_bytes + s2.n_bytes) + 1 + 64)) return -10;
-    if (int rc = feed.send(s1, d_text, &last1)) return rc;
-    int64_t off2 = s1.n_bytes;
-    if (s1.n_bytes > 0 && last1 != '\n') {                             // bed1's last line ends where bed2's first begins
-        HIP_TRY(hipMemsetAsync(d_text + off2, '\n', 1, c->up_stream));
-        ++off2;
-    }
-    if (int rc = feed.send(s2, d_text + off2)) return rc;
-    if (int rc = feed.pad_and_wait(d_text + off2 + s2.n_bytes)) return rc;
-    feed.times(c->cmp_stats, t0);
-    const auto t_kernels = std::chrono::steady_clock::now();
-    LiftDev lift;
-    int rc = t1 ? lift_prepare(c, pool, t1, t2, &lift) : 0;
-    if (rc == 0) rc = cmp_run(c, pool, d_text, off2 + s2.n_bytes, off2, out, n_out, n_sites, status, t1 ? &lift : nullptr, opt);
-    (void)hipStreamSynchronize(c->stream);                             // (an early return: nothing of the pool is in use when it goes)
-    c->cmp_stats.ms_kernels = ms_since(t_kernels) - c->cmp_stats.ms_d2h;      // a declined call too: what ran until it declined
-    if (rc != 0 || *status != 0) { *out = nullptr; *n_out = 0; *n_sites = 0; }
-    c->cmp_stats.ms_total = ms_since(t0);
-    return rc;
+    mc_cmp_stats &S = c->cmp.stats;
+    return pipeline_call(c, S, status, "bed comparison", (size_t)32 << 20, [&] { *out = nullptr; *n_out = 0; *n_sites = 0; }, [&](Call &K) -> int {
+        c->cmp.unaligned = 0;
+        S.n_bytes1 = s1.n_bytes; S.n_bytes2 = s2.n_bytes;
+        if (!cmp_fits((size_t)(s1.n_bytes + s2.n_bytes) + 4096)) return cmp_decline(c, status, MC_CMP_DECLINE_MEMORY, 0, -1);
+        char *d_text = nullptr;
+        int64_t off2 = 0;
+        if (K.pool.get(&d_text, (size_t)(s1.n_bytes + s2.n_bytes) + 1 + 64)) return -10;
+        if (int rc = K.feed.put_pair(s1, &s2, d_text, &off2)) return rc;
+        K.feed.times(S, K.t0);
+        const auto t_kernels = std::chrono::steady_clock::now();
+        LiftDev lift;
+        int rc = t1 ? lift_prepare(c, K.pool, t1, t2, &lift) : 0;
+        if (rc == 0) rc = cmp_run(c, K.pool, d_text, off2 + s2.n_bytes, off2, out, n_out, n_sites, status, t1 ? &lift : nullptr, opt);
+        S.ms_kernels = ms_since(t_kernels) - S.ms_d2h;        // a declined call too: what ran until it declined
+        return rc;
+    });
 }
 
 }  // namespace
@@ -771,8 +747,8 @@ int cmp_call(mc_ctx *c, const mc_text_source &s1, const mc_text_source &s2, cons
 // the arguments of a lifted comparison beyond those of a plain one -> 0, or -12 with the error set
 static int lifted_arguments(mc_ctx *c, const mc_contig_table *t1, const mc_contig_table *t2, int64_t *n_unaligned) {
     if (!n_unaligned || !lift_tables_ok(t1) || !lift_tables_ok(t2)) { mc_set_error("mc_bed_compare: bad arguments"); return -12; }
-    if (!c->xmfa_map) { mc_set_error("mc_bed_compare: no alignment map is resident (mc_xmfa_map first)"); return -12; }
-    if (t1->off[t1->n_contigs] != c->xmfa_n1 || t2->off[t2->n_contigs] != c->xmfa_n2) {
+    if (!c->xmfa.map) { mc_set_error("mc_bed_compare: no alignment map is resident (mc_xmfa_map first)"); return -12; }
+    if (t1->off[t1->n_contigs] != c->xmfa.n1 || t2->off[t2->n_contigs] != c->xmfa.n2) {
         mc_set_error("mc_bed_compare: the contig tables' totals are not those the map was built for");
         return -12;
     }
@@ -794,7 +770,7 @@ extern "C" int mc_bed_compare_with(mc_ctx *c, const mc_text_source *bed1, const 
     if (int rc = text_source("mc_bed_compare", bed1, &s1)) return rc;
     if (int rc = text_source("mc_bed_compare", bed2, &s2)) return rc;
     const int rc = cmp_call(c, s1, s2, out, n_out, n_sites, status, t1, t2, opt);
-    if (t1 && rc == 0 && *status == 0) *n_unaligned = c->cmp_unaligned;
+    if (t1 && rc == 0 && *status == 0) *n_unaligned = c->cmp.unaligned;
     return rc;
 }
 
@@ -813,37 +789,16 @@ extern "C" int mc_xmfa_map(mc_ctx *c, const mc_text_source *src, int32_t seq1, i
 }
 
 extern "C" int mc_xmfa_map_last_stats(mc_ctx *c, mc_xmfa_stats *out) {
-    if (!c || !out) { mc_set_error("mc_xmfa_map_last_stats: bad arguments"); return -12; }
-    *out = c->xmfa_stats;
-    return 0;
+    return stats_out("mc_xmfa_map_last_stats", c, out, &mc_ctx::xmfa, &XmfaPipe::stats);
 }
 
-extern "C" int mc_xmfa_map_release(mc_ctx *c) {
-    if (!c) return 0;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipStreamSynchronize(c->up_stream));
-    xm_release(c);
-    c->xmfa_g2.reset(); c->xmfa_flip.reset();
-    c->text_stages.release();
-    return 0;
-}
+extern "C" int mc_xmfa_map_release(mc_ctx *c) { return release_pipeline(c, &mc_ctx::xmfa); }
 
 extern "C" int mc_bed_compare_last_stats(mc_ctx *c, mc_cmp_stats *out) {
-    if (!c || !out) { mc_set_error("mc_bed_compare_last_stats: bad arguments"); return -12; }
-    *out = c->cmp_stats;
-    return 0;
+    return stats_out("mc_bed_compare_last_stats", c, out, &mc_ctx::cmp, &CmpPipe::stats);
 }
 
-extern "C" int mc_bed_compare_release(mc_ctx *c) {
-    if (!c) return 0;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipStreamSynchronize(c->up_stream));
-    c->cmp_out.reset(); c->cmp_out_cap = 0;
-    c->text_stages.release();
-    return 0;
-}
+extern "C" int mc_bed_compare_release(mc_ctx *c) { return release_pipeline(c, &mc_ctx::cmp); }
 
 // a native sample against a control, site by site (mc_curcompare.inc)
 extern "C" int mc_currents_compare(mc_ctx *c, const mc_text_source *native, const mc_text_source *control, const mc_cur_options *opt,
@@ -860,21 +815,10 @@ extern "C" int mc_currents_compare(mc_ctx *c, const mc_text_source *native, cons
 }
 
 extern "C" int mc_currents_compare_last_stats(mc_ctx *c, mc_cur_stats *out) {
-    if (!c || !out) { mc_set_error("mc_currents_compare_last_stats: bad arguments"); return -12; }
-    *out = c->cur_stats;
-    return 0;
+    return stats_out("mc_currents_compare_last_stats", c, out, &mc_ctx::currents, &CurPipe::stats);
 }
 
-extern "C" int mc_currents_compare_release(mc_ctx *c) {
-    if (!c) return 0;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipStreamSynchronize(c->up_stream));
-    c->cur_out.reset(); c->cur_out_cap = 0;
-    c->cur_bed.reset(); c->cur_bed_cap = 0;
-    c->text_stages.release();
-    return 0;
-}
+extern "C" int mc_currents_compare_release(mc_ctx *c) { return release_pipeline(c, &mc_ctx::currents); }
 
 // the rows of a sample's sites split in two by their currents (mc_sitecluster.inc)
 extern "C" int mc_sites_cluster(mc_ctx *c, const mc_text_source *source, const mc_clu_options *opt, mc_clu_result *res, int32_t *status) {
@@ -890,21 +834,10 @@ extern "C" int mc_sites_cluster(mc_ctx *c, const mc_text_source *source, const m
 }
 
 extern "C" int mc_sites_cluster_last_stats(mc_ctx *c, mc_clu_stats *out) {
-    if (!c || !out) { mc_set_error("mc_sites_cluster_last_stats: bad arguments"); return -12; }
-    *out = c->clu_stats;
-    return 0;
+    return stats_out("mc_sites_cluster_last_stats", c, out, &mc_ctx::clusters, &CluPipe::stats);
 }
 
-extern "C" int mc_sites_cluster_release(mc_ctx *c) {
-    if (!c) return 0;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipStreamSynchronize(c->up_stream));
-    c->clu_out.reset(); c->clu_out_cap = 0;
-    c->clu_bed.reset(); c->clu_bed_cap = 0;
-    c->text_stages.release();
-    return 0;
-}
+extern "C" int mc_sites_cluster_release(mc_ctx *c) { return release_pipeline(c, &mc_ctx::clusters); }
 
 // the device build of mc_twosample.h on k sites: the rank kernels and kc_finish as the file pipeline runs them
 extern "C" int mc_twosample_device(mc_ctx *c, const double *x, const int64_t *x_off, const double *y, const int64_t *y_off, int64_t k,

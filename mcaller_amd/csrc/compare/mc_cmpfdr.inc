@@ -337,7 +337,7 @@ __global__ __launch_bounds__(256) void kc_fisher_sites(CmpArgs A) {
 // of all columns
 int cmp_extra_columns(mc_ctx *c, Pool &pool, const CmpArgs &A, unsigned *bh_flags) {
     hipStream_t st = c->stream;
-    mc_cmp_stats &S = c->cmp_stats;
+    mc_cmp_stats &S = c->cmp.stats;
     HIP_TRY(hipMemsetAsync(A.extra, 0, (size_t)A.S * (size_t)A.n_extra * 8, st));
     if (A.fisher) {
         hipLaunchKernelGGL(kc_fisher_sites, dim3(blocks(A.S)), dim3(256), 0, st, A);

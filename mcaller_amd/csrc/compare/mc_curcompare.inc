@@ -186,16 +186,13 @@ const char *cur_reason_text(int reason) {
 
 // file: 1 (native), 2 (control) or 0; line: in that file, -1: none
 int cur_decline(mc_ctx *c, int32_t *status, int reason, int file, long long line) {
-    c->cur_stats.decline_file = file;
-    char what[200];
-    if (file) snprintf(what, sizeof what, "%s (%s)", cur_reason_text(reason), file == 1 ? "native" : "control");
-    else snprintf(what, sizeof what, "%s", cur_reason_text(reason));
-    return decline(c->cur_stats, status, "current comparison", what, reason, line);
+    static const char *const nouns[2] = {"native", "control"};
+    return decline_in_file(c->currents.stats, status, "current comparison", cur_reason_text(reason), nouns, reason, file, line);
 }
 
 // The texts are on the device (d_text[0, n): the native text, a newline if it lacked its last, the control's from off2 on; padded)
 int cur_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, int64_t off2, const mc_cur_options &opt, mc_cur_result *res, int32_t *status) {
-    mc_cur_stats &S = c->cur_stats;
+    mc_cur_stats &S = c->currents.stats;
     hipStream_t st = c->stream;
     if (n == 0) return 0;
     CurHead *d_head = nullptr, h = {};
@@ -259,39 +256,25 @@ int cur_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, int64_t off2, 
         if (bh_flags & BH_RANGE) return cur_decline(c, status, MC_CMP_DECLINE_FAR_TAIL, 0, -1);
         if (bh_flags & BH_TIE) return cur_decline(c, status, MC_CMP_DECLINE_TIE, 0, -1);
     }
-    if (int rc = sg_outputs(c, R, A, d_head, h, kn_size, kn_write, c->cur_out, c->cur_out_cap, c->cur_bed, c->cur_bed_cap, S, res)) return std::min(rc, 0);
+    if (int rc = sg_outputs(c, R, A, d_head, h, kn_size, kn_write, c->currents.out, c->currents.bed, S, res)) return std::min(rc, 0);
     S.n_sig = (int64_t)h.n_sig;
     res->n_sites = NS; res->n_sig = (int64_t)h.n_sig;
     return 0;
 }
 
 int cur_call(mc_ctx *c, const mc_text_source &s1, const mc_text_source &s2, const mc_cur_options &opt, mc_cur_result *res, int32_t *status) {
-    HIP_TRY(hipSetDevice(c->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    c->cur_stats = mc_cur_stats();
-    c->cur_stats.decline_line = -1;
-    c->cur_stats.n_bytes1 = s1.n_bytes; c->cur_stats.n_bytes2 = s2.n_bytes; c->cur_stats.n_columns = opt.n_columns;
-    *res = mc_cur_result();
-    *status = 0;
-    if (!cmp_fits((size_t)(s1.n_bytes + s2.n_bytes) + 4096)) return cur_decline(c, status, MC_CMP_DECLINE_MEMORY, 0, -1);
-    Pool pool("current comparison");
-    TextFeed feed(c, (size_t)32 << 20);
-    char *d_text = nullptr, last1 = '\n';
-    if (pool.get(&d_text, (size_t)(s1.n_bytes + s2.n_bytes) + 1 + 64)) return -10;
-    if (int rc = feed.send(s1, d_text, &last1)) return rc;
-    int64_t off2 = s1.n_bytes;
-    if (s1.n_bytes > 0 && last1 != '\n') {                             // the native text's last line ends where the control's first begins
-        HIP_TRY(hipMemsetAsync(d_text + off2, '\n', 1, c->up_stream));
-        ++off2;
-    }
-    if (int rc = feed.send(s2, d_text + off2)) return rc;
-    if (int rc = feed.pad_and_wait(d_text + off2 + s2.n_bytes)) return rc;
-    feed.times(c->cur_stats, t0);
-    const auto t_kernels = std::chrono::steady_clock::now();
-    const int rc = cur_run(c, pool, d_text, off2 + s2.n_bytes, off2, opt, res, status);
-    (void)hipStreamSynchronize(c->stream);                             // (an early return: nothing of the pool is in use when it goes)
-    c->cur_stats.ms_kernels = ms_since(t_kernels) - c->cur_stats.ms_d2h;
-    if (rc != 0 || *status != 0) *res = mc_cur_result();
-    c->cur_stats.ms_total = ms_since(t0);
-    return rc;
+    mc_cur_stats &S = c->currents.stats;
+    return pipeline_call(c, S, status, "current comparison", (size_t)32 << 20, [&] { *res = mc_cur_result(); }, [&](Call &K) -> int {
+        S.n_bytes1 = s1.n_bytes; S.n_bytes2 = s2.n_bytes; S.n_columns = opt.n_columns;
+        if (!cmp_fits((size_t)(s1.n_bytes + s2.n_bytes) + 4096)) return cur_decline(c, status, MC_CMP_DECLINE_MEMORY, 0, -1);
+        char *d_text = nullptr;
+        int64_t off2 = 0;
+        if (K.pool.get(&d_text, (size_t)(s1.n_bytes + s2.n_bytes) + 1 + 64)) return -10;
+        if (int rc = K.feed.put_pair(s1, &s2, d_text, &off2)) return rc;
+        K.feed.times(S, K.t0);
+        const auto t_kernels = std::chrono::steady_clock::now();
+        const int rc = cur_run(c, K.pool, d_text, off2 + s2.n_bytes, off2, opt, res, status);
+        S.ms_kernels = ms_since(t_kernels) - S.ms_d2h;        // a declined call too: what ran until it declined
+        return rc;
+    });
 }

@@ -412,12 +412,12 @@ int clu_decline(mc_ctx *c, int32_t *status, int reason, long long line) {
                      : reason == MC_CMP_DECLINE_PRINT ? "a height the device's row writer does not print"
                      : reason == MC_CMP_DECLINE_MEMORY ? "the text, its tables or the distance slabs do not fit into free device memory"
                      : cur_reason_text(reason);
-    return decline(c->clu_stats, status, "site clustering", what, reason, line);
+    return decline(c->clusters.stats, status, "site clustering", what, reason, line);
 }
 
 // The text is on the device (d_text[0, n), padded): everything behind that
 int clu_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const mc_clu_options &opt, mc_clu_result *res, int32_t *status) {
-    mc_clu_stats &S = c->clu_stats;
+    mc_clu_stats &S = c->clusters.stats;
     hipStream_t st = c->stream;
     if (n == 0) return 0;
     if (opt.n_columns < 2) return clu_decline(c, status, MC_CMP_DECLINE_CUR_VALUES, 0);
@@ -481,32 +481,23 @@ int clu_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const mc_clu_o
     if (h.n_lds > 0) hipLaunchKernelGGL(kl_link_large<false>, dim3((unsigned)h.n_large), dim3(KL_THREADS), 0, st, A);
     if (h.n_slab > 0) hipLaunchKernelGGL(kl_link_large<true>, dim3((unsigned)S.slab_groups), dim3(KL_THREADS), 0, st, A);
     hipLaunchKernelGGL(kl_finish, dim3(blocks(NS)), dim3(256), 0, st, A);
-    if (int rc = sg_outputs(c, R, A, d_head, h, kl_size, kl_write, c->clu_out, c->clu_out_cap, c->clu_bed, c->clu_bed_cap, S, res)) return std::min(rc, 0);
+    if (int rc = sg_outputs(c, R, A, d_head, h, kl_size, kl_write, c->clusters.out, c->clusters.bed, S, res)) return std::min(rc, 0);
     S.n_sites = (int64_t)h.n_kept; S.n_mixed = (int64_t)h.n_mixed;
     res->n_sites = (int64_t)h.n_kept; res->n_mixed = (int64_t)h.n_mixed;
     return 0;
 }
 
-
 int clu_call(mc_ctx *c, const mc_text_source &src, const mc_clu_options &opt, mc_clu_result *res, int32_t *status) {
-    HIP_TRY(hipSetDevice(c->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    c->clu_stats = mc_clu_stats();
-    c->clu_stats.decline_line = -1;
-    c->clu_stats.n_bytes = src.n_bytes; c->clu_stats.n_columns = opt.n_columns;
-    *res = mc_clu_result();
-    *status = 0;
-    if (!cmp_fits((size_t)src.n_bytes + 4096)) return clu_decline(c, status, MC_CMP_DECLINE_MEMORY, -1);
-    Pool pool("site clustering");
-    TextFeed feed(c, (size_t)32 << 20);
-    char *d_text = nullptr;
-    if (int rc = feed.put(pool, src, &d_text)) return rc;
-    feed.times(c->clu_stats, t0);
-    const auto t_kernels = std::chrono::steady_clock::now();
-    const int rc = clu_run(c, pool, d_text, src.n_bytes, opt, res, status);
-    (void)hipStreamSynchronize(c->stream);                             // (an early return: nothing of the pool is in use when it goes)
-    c->clu_stats.ms_kernels = ms_since(t_kernels) - c->clu_stats.ms_d2h;
-    if (rc != 0 || *status != 0) *res = mc_clu_result();
-    c->clu_stats.ms_total = ms_since(t0);
-    return rc;
+    mc_clu_stats &S = c->clusters.stats;
+    return pipeline_call(c, S, status, "site clustering", (size_t)32 << 20, [&] { *res = mc_clu_result(); }, [&](Call &K) -> int {
+        S.n_bytes = src.n_bytes; S.n_columns = opt.n_columns;
+        if (!cmp_fits((size_t)src.n_bytes + 4096)) return clu_decline(c, status, MC_CMP_DECLINE_MEMORY, -1);
+        char *d_text = nullptr;
+        if (int rc = K.feed.put(K.pool, src, &d_text)) return rc;
+        K.feed.times(S, K.t0);
+        const auto t_kernels = std::chrono::steady_clock::now();
+        const int rc = clu_run(c, K.pool, d_text, src.n_bytes, opt, res, status);
+        S.ms_kernels = ms_since(t_kernels) - S.ms_d2h;        // a declined call too: what ran until it declined
+        return rc;
+    });
 }

@@ -377,23 +377,11 @@ struct SgRun {
     }
 };
 
-// one of a call's two outputs: device bytes -> the context's pinned block
-int sg_fetch(mc_ctx *c, Pinned &dst, size_t &dst_cap, const char *d_src, size_t n, const char **out, int64_t *n_out) {
-    *out = nullptr; *n_out = 0;
-    if (n == 0) return 0;
-    if (int rc = grow(dst, dst_cap, n)) return rc;
-    HIP_TRY(hipMemcpyAsync(dst.p, d_src, n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    *out = dst.get<char>();
-    *n_out = (int64_t)n;
-    return 0;
-}
-
 // The tail of a pipeline: its size kernel, the two scans, the head (h: the whole of it, fetched here), the two outputs written by its
 // write kernel and copied into the context's pinned blocks; the outputs' stats and the result's pointers.  Returns as a phase does
 template <class Args, class Head, class Stats, class Res>
-int sg_outputs(mc_ctx *c, SgRun &R, Args &A, Head *d_head, Head &h, void (*k_size)(Args), void (*k_write)(Args), Pinned &out, size_t &out_cap,
-               Pinned &bed, size_t &bed_cap, Stats &S, Res *res) {
+int sg_outputs(mc_ctx *c, SgRun &R, Args &A, Head *d_head, Head &h, void (*k_size)(Args), void (*k_write)(Args), Grown &out, Grown &bed,
+               Stats &S, Res *res) {
     static_assert(offsetof(Head, g) == 0, "SgRun::keys clears the head from its g on, and fetches that");
     hipStream_t st = R.st;
     const int64_t NS = A.g.S;
@@ -410,8 +398,8 @@ int sg_outputs(mc_ctx *c, SgRun &R, Args &A, Head *d_head, Head &h, void (*k_siz
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
     const auto t_d2h = std::chrono::steady_clock::now();
-    if (int rc = sg_fetch(c, out, out_cap, A.o.out, ob, &res->out, &res->n_out)) return rc;
-    if (int rc = sg_fetch(c, bed, bed_cap, A.o.bed, bb, &res->bed, &res->n_bed)) return rc;
+    if (int rc = fetch_out(c, out, A.o.out, ob, &res->out, &res->n_out)) return rc;
+    if (int rc = fetch_out(c, bed, A.o.bed, bb, &res->bed, &res->n_bed)) return rc;
     S.ms_d2h = ms_since(t_d2h);
     S.n_out_bytes = (int64_t)ob; S.n_bed_bytes = (int64_t)bb;
     return 0;

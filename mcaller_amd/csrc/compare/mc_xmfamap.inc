@@ -410,14 +410,8 @@ const char *xm_reason_text(int reason) {
     return "unknown";
 }
 
-void xm_release(mc_ctx *c) {
-    c->xmfa_allocs.clear();
-    c->xmfa_map = nullptr;
-    c->xmfa_n1 = c->xmfa_n2 = 0;
-}
-
 int xm_decline(mc_ctx *c, int32_t *status, int reason, long long line) {
-    return decline(c->xmfa_stats, status, "alignment reader", xm_reason_text(reason), reason, line);
+    return decline(c->xmfa.stats, status, "alignment reader", xm_reason_text(reason), reason, line);
 }
 
 int xm_scan(hipStream_t st, const long long *cnt, int64_t n, long long *off, long long *total) {
@@ -428,7 +422,7 @@ int xm_scan(hipStream_t st, const long long *cnt, int64_t n, long long *off, lon
 
 // the text is on the device (padded), the map allocated and all unmapped: everything behind that
 int xm_run(mc_ctx *c, Pool &pool, XmArgs &A, XmHead *d_head, int32_t *status) {
-    mc_xmfa_stats &S = c->xmfa_stats;
+    mc_xmfa_stats &S = c->xmfa.stats;
     hipStream_t st = c->stream;
     XmHead h = {};
     h.decline = CMP_NO_DECLINE;
@@ -504,60 +498,56 @@ int xm_run(mc_ctx *c, Pool &pool, XmArgs &A, XmHead *d_head, int32_t *status) {
 }
 
 int xm_call(mc_ctx *c, const mc_text_source &src, int32_t seq1, int32_t seq2, int64_t n1, int64_t n2, mc_xmfa_map_view *view, int32_t *status) {
-    HIP_TRY(hipSetDevice(c->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    hipStream_t st = c->stream;
-    HIP_TRY(hipStreamSynchronize(st));
-    xm_release(c);
-    mc_xmfa_stats &S = c->xmfa_stats;
-    S = mc_xmfa_stats();
-    S.decline_line = -1;
-    S.n_bytes = src.n_bytes; S.n1 = n1; S.n2 = n2;
-    *status = 0;
-    if (view) *view = mc_xmfa_map_view();
-    if (n1 > XM_COORD_CAP || n2 > XM_COORD_CAP) return xm_decline(c, status, MC_CMP_DECLINE_XMFA_GENOME, -1);
-    const size_t n_map = (size_t)n1 + 1;
-    if (!cmp_fits((size_t)src.n_bytes + 4096 + n_map * (view ? 17 : 8))) return xm_decline(c, status, MC_CMP_DECLINE_MEMORY, -1);
-    unsigned long long *map = c->xmfa_allocs.get<unsigned long long>(n_map);
-    if (!map) return -10;
-    HIP_TRY(hipMemsetAsync(map, 0xff, n_map * 8, st));
-    Pool pool("alignment map");
-    TextFeed feed(c, (size_t)32 << 20);
-    char *d_text = nullptr;
-    if (int rc = feed.put(pool, src, &d_text)) { xm_release(c); return rc; }
-    feed.times(S, t0);
-    const auto t_kernels = std::chrono::steady_clock::now();
-    XmHead *d_head = nullptr, h = {};
-    XmArgs A = {};
-    A.text = d_text; A.n_bytes = src.n_bytes; A.seq1 = seq1; A.seq2 = seq2; A.n1 = n1; A.n2 = n2; A.map = map;
-    int rc = pool.get(&d_head, 1);
-    A.head = d_head;
-    if (rc == 0) rc = xm_run(c, pool, A, d_head, status);
-    if (rc == 0 && *status == 0) {
-        if (view && (pool.get(&A.view_g2, n_map) || pool.get(&A.view_flip, n_map))) rc = -10;
-        if (rc == 0) {
-            hipLaunchKernelGGL(kx_view, dim3(std::min(blocks((int64_t)n_map), 2048u)), dim3(256), 0, st, A);
-            rc = mc_hip_rc(hipGetLastError(), "kx_view");
+    mc_xmfa_stats &S = c->xmfa.stats;
+    unsigned long long *map = nullptr;
+    const int rc_call = pipeline_call(c, S, status, "alignment map", (size_t)32 << 20, [&] { if (view) *view = mc_xmfa_map_view(); }, [&](Call &K) -> int {
+        hipStream_t st = c->stream;
+        HIP_TRY(hipStreamSynchronize(st));
+        c->xmfa.drop_map();                                            // an earlier call's map goes before this one's is made
+        S.n_bytes = src.n_bytes; S.n1 = n1; S.n2 = n2;
+        if (n1 > XM_COORD_CAP || n2 > XM_COORD_CAP) return xm_decline(c, status, MC_CMP_DECLINE_XMFA_GENOME, -1);
+        const size_t n_map = (size_t)n1 + 1;
+        if (!cmp_fits((size_t)src.n_bytes + 4096 + n_map * (view ? 17 : 8))) return xm_decline(c, status, MC_CMP_DECLINE_MEMORY, -1);
+        map = c->xmfa.allocs.get<unsigned long long>(n_map);
+        if (!map) return -10;
+        HIP_TRY(hipMemsetAsync(map, 0xff, n_map * 8, st));
+        Pool &pool = K.pool;
+        char *d_text = nullptr;
+        if (int rc = K.feed.put(pool, src, &d_text)) return rc;
+        K.feed.times(S, K.t0);
+        const auto t_kernels = std::chrono::steady_clock::now();
+        XmHead *d_head = nullptr, h = {};
+        XmArgs A = {};
+        A.text = d_text; A.n_bytes = src.n_bytes; A.seq1 = seq1; A.seq2 = seq2; A.n1 = n1; A.n2 = n2; A.map = map;
+        int rc = pool.get(&d_head, 1);
+        A.head = d_head;
+        if (rc == 0) rc = xm_run(c, pool, A, d_head, status);
+        if (rc == 0 && *status == 0) {
+            if (view && (pool.get(&A.view_g2, n_map) || pool.get(&A.view_flip, n_map))) rc = -10;
+            if (rc == 0) {
+                hipLaunchKernelGGL(kx_view, dim3(std::min(blocks((int64_t)n_map), 2048u)), dim3(256), 0, st, A);
+                rc = mc_hip_rc(hipGetLastError(), "kx_view");
+            }
+            if (rc == 0) rc = fetch_head(st, d_head, h);
+            S.n_mapped = (int64_t)h.n_mapped;
+            S.ms_kernels = ms_since(t_kernels);
+            if (rc == 0 && view) {
+                const auto t_d2h = std::chrono::steady_clock::now();
+                rc = c->xmfa.g2.alloc(n_map * 8);
+                if (rc == 0) rc = c->xmfa.flip.alloc(n_map);
+                if (rc == 0) rc = mc_hip_rc(hipMemcpyAsync(c->xmfa.g2.p, A.view_g2, n_map * 8, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+                if (rc == 0) rc = mc_hip_rc(hipMemcpyAsync(c->xmfa.flip.p, A.view_flip, n_map, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+                if (rc == 0) rc = mc_hip_rc(hipStreamSynchronize(st), "hipStreamSynchronize");
+                S.ms_d2h = ms_since(t_d2h);
+                if (rc == 0) { view->n1 = n1; view->g2 = c->xmfa.g2.get<int64_t>(); view->flip = c->xmfa.flip.get<uint8_t>(); }
+            }
+        } else {
+            S.ms_kernels = ms_since(t_kernels);                        // a declined call too: what ran until it declined
         }
-        if (rc == 0) rc = fetch_head(st, d_head, h);
-        S.n_mapped = (int64_t)h.n_mapped;
-        S.ms_kernels = ms_since(t_kernels);
-        if (rc == 0 && view) {
-            const auto t_d2h = std::chrono::steady_clock::now();
-            rc = c->xmfa_g2.alloc(n_map * 8);
-            if (rc == 0) rc = c->xmfa_flip.alloc(n_map);
-            if (rc == 0) rc = mc_hip_rc(hipMemcpyAsync(c->xmfa_g2.p, A.view_g2, n_map * 8, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
-            if (rc == 0) rc = mc_hip_rc(hipMemcpyAsync(c->xmfa_flip.p, A.view_flip, n_map, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
-            if (rc == 0) rc = mc_hip_rc(hipStreamSynchronize(st), "hipStreamSynchronize");
-            S.ms_d2h = ms_since(t_d2h);
-            if (rc == 0) { view->n1 = n1; view->g2 = c->xmfa_g2.get<int64_t>(); view->flip = c->xmfa_flip.get<uint8_t>(); }
-        }
-    } else {
-        S.ms_kernels = ms_since(t_kernels);
-    }
-    (void)hipStreamSynchronize(st);                                    // (an early return: nothing of the pool is in use when it goes)
-    if (rc != 0 || *status != 0) xm_release(c);
-    else { c->xmfa_map = map; c->xmfa_n1 = n1; c->xmfa_n2 = n2; }
-    S.ms_total = ms_since(t0);
-    return rc;
+        return rc;
+    });
+    // a call that fails or declines leaves no map behind, however far it got: a lifted comparison asks whether one is resident
+    if (rc_call != 0 || *status != 0) c->xmfa.drop_map();
+    else { c->xmfa.map = map; c->xmfa.n1 = n1; c->xmfa.n2 = n2; }
+    return rc_call;
 }

@@ -493,23 +493,19 @@ const char *ev_reason_text(int reason) {
 }
 
 int ev_decline(mc_ctx *c, int32_t *status, int reason, long long line, int file) {
-    c->eval_stats.decline_file = file;
-    return decline(c->eval_stats, status, file ? "evaluation (the positions file)" : "evaluation", ev_reason_text(reason), reason, line);
+    c->eval.stats.decline_file = file;
+    return decline(c->eval.stats, status, file ? "evaluation (the positions file)" : "evaluation", ev_reason_text(reason), reason, line);
 }
 
 // MCALLER_EVAL_DEVICE_BYTES=n stands for the free device memory (tests)
-bool ev_fits(size_t bytes) {
-    const char *e = getenv("MCALLER_EVAL_DEVICE_BYTES");
-    if (e && *e) return bytes <= (size_t)strtoull(e, nullptr, 10);
-    return device_fits(bytes);
-}
+bool ev_fits(size_t bytes) { return fits("MCALLER_EVAL_DEVICE_BYTES", bytes); }
 
 inline unsigned ev_blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 // both texts are on the device (padded): everything behind that
 int ev_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *d_ptext, int64_t np, const mc_eval_params *P, const char **out,
            int64_t *n_out, int32_t *status) {
-    mc_eval_stats &S = c->eval_stats;
+    mc_eval_stats &S = c->eval.stats;
     hipStream_t st = c->stream;
     HIP_TRY(hipStreamSynchronize(c->up_stream));
     auto t_step = std::chrono::steady_clock::now();
@@ -625,35 +621,23 @@ int ev_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *d_p
     S.ms_finish = ms_since(t_step);
     t_step = std::chrono::steady_clock::now();
     if (h.out_bytes < 0 || (size_t)h.out_bytes > nl * EV_ROW_W) { mc_set_error("mc_eval_calls: the file's size is off"); return -1; }
-    if (int rc = grow(c->eval_out, c->eval_out_cap, (size_t)h.out_bytes)) return rc;
-    HIP_TRY(hipMemcpyAsync(c->eval_out.p, A.out, (size_t)h.out_bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = fetch_out(c, c->eval.out, A.out, (size_t)h.out_bytes, out, n_out)) return rc;
     S.ms_d2h = ms_since(t_step);
-    *out = c->eval_out.get<char>();
-    *n_out = h.out_bytes;
     return 0;
 }
 
 int ev_call(mc_ctx *c, const mc_text_source &src, const mc_text_source &pos, const mc_eval_params *P, const char **out, int64_t *n_out, int32_t *status) {
-    HIP_TRY(hipSetDevice(c->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    c->eval_stats = mc_eval_stats();
-    c->eval_stats.decline_line = -1;
-    c->eval_stats.n_bytes = src.n_bytes;
-    c->eval_stats.n_pos_bytes = pos.n_bytes;
-    *out = nullptr; *n_out = 0; *status = 0;
-    if (!ev_fits((size_t)src.n_bytes + (size_t)pos.n_bytes + ((size_t)1 << 20))) return ev_decline(c, status, MC_EVAL_DECLINE_MEMORY, -1, 0);
-    Pool pool("evaluation");
-    TextFeed feed(c, (size_t)64 << 20);
-    char *d_text = nullptr, *d_ptext = nullptr;
-    if (int rc = feed.put(pool, src, &d_text)) return rc;
-    if (int rc = feed.put(pool, pos, &d_ptext)) return rc;
-    feed.times(c->eval_stats, t0);
-    const int rc = ev_run(c, pool, d_text, src.n_bytes, d_ptext, pos.n_bytes, P, out, n_out, status);
-    (void)hipStreamSynchronize(c->stream);                   // (an early return: nothing of the pool is in use when it goes)
-    if (rc != 0 || *status != 0) { *out = nullptr; *n_out = 0; }
-    c->eval_stats.ms_total = ms_since(t0);
-    return rc;
+    mc_eval_stats &S = c->eval.stats;
+    return pipeline_call(c, S, status, "evaluation", (size_t)64 << 20, [&] { *out = nullptr; *n_out = 0; }, [&](Call &K) -> int {
+        S.n_bytes = src.n_bytes;
+        S.n_pos_bytes = pos.n_bytes;
+        if (!ev_fits((size_t)src.n_bytes + (size_t)pos.n_bytes + ((size_t)1 << 20))) return ev_decline(c, status, MC_EVAL_DECLINE_MEMORY, -1, 0);
+        char *d_text = nullptr, *d_ptext = nullptr;
+        if (int rc = K.feed.put(K.pool, src, &d_text)) return rc;
+        if (int rc = K.feed.put(K.pool, pos, &d_ptext)) return rc;
+        K.feed.times(S, K.t0);
+        return ev_run(c, K.pool, d_text, src.n_bytes, d_ptext, pos.n_bytes, P, out, n_out, status);
+    });
 }
 
 struct HgMassOut {
@@ -691,21 +675,9 @@ extern "C" int mc_eval_calls(mc_ctx *c, const mc_text_source *diffs, const mc_te
     return ev_call(c, s, p, P, out, n_out, status);
 }
 
-extern "C" int mc_eval_last_stats(mc_ctx *c, mc_eval_stats *out) {
-    if (!c || !out) { mc_set_error("mc_eval_last_stats: bad arguments"); return -12; }
-    *out = c->eval_stats;
-    return 0;
-}
+extern "C" int mc_eval_last_stats(mc_ctx *c, mc_eval_stats *out) { return stats_out("mc_eval_last_stats", c, out, &mc_ctx::eval, &EvalPipe::stats); }
 
-extern "C" int mc_eval_release(mc_ctx *c) {
-    if (!c) return 0;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipStreamSynchronize(c->up_stream));
-    c->eval_out.reset(); c->eval_out_cap = 0;
-    c->text_stages.release();
-    return 0;
-}
+extern "C" int mc_eval_release(mc_ctx *c) { return release_pipeline(c, &mc_ctx::eval); }
 
 extern "C" int mc_hypergeom_masses_device(mc_ctx *c, const int64_t *N, const int64_t *K, const int64_t *d, int64_t count, double *mass102, double *err) {
     if (!c || count < 0 || (count > 0 && (!N || !K || !d || !mass102 || !err))) {

@@ -209,7 +209,7 @@ __global__ __launch_bounds__(256) void kfq_keys(FqArgs A) {
 }
 
 int fq_decline(mc_ctx *c, int32_t *status, int reason, long long line) {
-    return decline(c->fq_stats, status, "reader", fq_reason_text(reason), reason, line);
+    return decline(c->fq.stats, status, "reader", fq_reason_text(reason), reason, line);
 }
 
 int fq_decline_head(mc_ctx *c, int32_t *status, const FqHead &h) {
@@ -218,7 +218,7 @@ int fq_decline_head(mc_ctx *c, int32_t *status, const FqHead &h) {
 
 // The text is on the device (d_text[0, n), its buffer aligned and padded; copies enqueued on c->up_stream): everything behind that
 int fq_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, mc_fastq_quality_view *V, int32_t *status) {
-    mc_fastq_quality_stats &S = c->fq_stats;
+    mc_fastq_quality_stats &S = c->fq.stats;
     hipStream_t st = c->stream;
     HIP_TRY(hipStreamSynchronize(c->up_stream));
     const auto t_kernels = std::chrono::steady_clock::now();
@@ -277,48 +277,33 @@ int fq_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, mc_fastq_qualit
     HIP_TRY(hipStreamSynchronize(st));
     S.ms_kernels = ms_since(t_kernels);
     const auto t_d2h = std::chrono::steady_clock::now();
-    if (int rc = grow(c->fq_pool, c->fq_pool_cap, pb)) return rc;
-    if (int rc = grow(c->fq_off, c->fq_off_cap, (nr + 1) * 8)) return rc;
-    if (int rc = grow(c->fq_mean, c->fq_mean_cap, nr * 8)) return rc;
-    HIP_TRY(hipMemcpyAsync(c->fq_pool.p, A.pool, pb, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(c->fq_off.p, A.key_off, (nr + 1) * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(c->fq_mean.p, A.mean, nr * 8, hipMemcpyDeviceToHost, st));
+    if (int rc = c->fq.pool.need(pb)) return rc;
+    if (int rc = c->fq.off.need((nr + 1) * 8)) return rc;
+    if (int rc = c->fq.mean.need(nr * 8)) return rc;
+    HIP_TRY(hipMemcpyAsync(c->fq.pool.get<char>(), A.pool, pb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(c->fq.off.get<int64_t>(), A.key_off, (nr + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(c->fq.mean.get<double>(), A.mean, nr * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     S.ms_d2h = ms_since(t_d2h);
-    V->key_pool = c->fq_pool.get<char>();
-    V->key_off = c->fq_off.get<int64_t>();
-    V->mean = c->fq_mean.get<double>();
+    V->key_pool = c->fq.pool.get<char>();
+    V->key_off = c->fq.off.get<int64_t>();
+    V->mean = c->fq.mean.get<double>();
     V->n_records = R;
-    return 0;
-}
-
-// what a call begins with -> 0: go on; 1: done (declined, *status set)
-int fq_begin(mc_ctx *c, mc_fastq_quality_view *V, int32_t *status, int64_t n) {
-    c->fq_stats = mc_fastq_quality_stats();
-    c->fq_stats.decline_line = -1;
-    c->fq_stats.n_bytes = n;
-    c->fq_stats.piece_bytes = FQ_PIECE;
-    *V = mc_fastq_quality_view();
-    *status = 0;
-    if (!device_fits((size_t)n + 4096)) { (void)fq_decline(c, status, MC_FASTQ_DECLINE_MEMORY, -1); return 1; }
     return 0;
 }
 
 // what the entry point runs: the text of `src` onto the device and through fq_run
 int fq_call(mc_ctx *c, const mc_text_source &src, mc_fastq_quality_view *out, int32_t *status) {
-    HIP_TRY(hipSetDevice(c->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    if (fq_begin(c, out, status, src.n_bytes)) return 0;
-    Pool pool("fastq qualities");
-    TextFeed feed(c, (size_t)32 << 20);
-    char *d_text = nullptr;
-    if (int rc = feed.put(pool, src, &d_text)) return rc;
-    feed.times(c->fq_stats, t0);
-    const int rc = fq_run(c, pool, d_text, src.n_bytes, out, status);
-    (void)hipStreamSynchronize(c->stream);                   // (an early return: nothing of the pool is in use when it goes)
-    if (rc != 0 || *status != 0) *out = mc_fastq_quality_view();
-    c->fq_stats.ms_total = ms_since(t0);
-    return rc;
+    mc_fastq_quality_stats &S = c->fq.stats;
+    return pipeline_call(c, S, status, "fastq qualities", (size_t)32 << 20, [&] { *out = mc_fastq_quality_view(); }, [&](Call &K) -> int {
+        S.n_bytes = src.n_bytes;
+        S.piece_bytes = FQ_PIECE;
+        if (!device_fits((size_t)src.n_bytes + 4096)) return fq_decline(c, status, MC_FASTQ_DECLINE_MEMORY, -1);
+        char *d_text = nullptr;
+        if (int rc = K.feed.put(K.pool, src, &d_text)) return rc;
+        K.feed.times(S, K.t0);
+        return fq_run(c, K.pool, d_text, src.n_bytes, out, status);
+    });
 }
 
 }  // namespace
@@ -334,19 +319,7 @@ extern "C" int mc_fastq_quality(mc_ctx *c, const mc_text_source *src, mc_fastq_q
 }
 
 extern "C" int mc_fastq_quality_last_stats(mc_ctx *c, mc_fastq_quality_stats *out) {
-    if (!c || !out) { mc_set_error("mc_fastq_quality_last_stats: bad arguments"); return -12; }
-    *out = c->fq_stats;
-    return 0;
+    return stats_out("mc_fastq_quality_last_stats", c, out, &mc_ctx::fq, &FastqPipe::stats);
 }
 
-extern "C" int mc_fastq_quality_release(mc_ctx *c) {
-    if (!c) return 0;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipStreamSynchronize(c->up_stream));
-    c->fq_pool.reset(); c->fq_pool_cap = 0;
-    c->fq_off.reset(); c->fq_off_cap = 0;
-    c->fq_mean.reset(); c->fq_mean_cap = 0;
-    c->text_stages.release();
-    return 0;
-}
+extern "C" int mc_fastq_quality_release(mc_ctx *c) { return release_pipeline(c, &mc_ctx::fq); }

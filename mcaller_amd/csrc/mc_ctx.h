@@ -1,7 +1,8 @@
 // mc_ctx.h -- the context of libmcaller_hip.so as its host units see it (mc_stream.hip: the passes; mc_tables.hip: table slots, the
 // device parser's host side, the reference; mc_context.hip: life cycle and classifier setters; mc_rowtext_host.hip: rows of text;
 // mc_comm.hip: RCCL), and the few functions that cross those units.  Included by them and by nothing else.  Everything the context
-// takes from the runtime is held by an owner of mc_own.h: nothing here is freed by hand.
+// takes from the runtime is held by an owner of mc_own.h: nothing here is freed by hand.  What the file pipelines keep between
+// calls (mc_textfeed.h: through it the seven units of those see the context too) stands in a record each -- BedPipe .. MotifPipe.
 #pragma once
 #include "mc_dev.h"
 #include "mc_own.h"
@@ -234,6 +235,87 @@ struct TextStages {
     }
 };
 
+// ---- a record per file pipeline (mc_textfeed.h): the pinned blocks its results are handed out in, the figures of its last call
+// and what else outlives a call.  release(): what mc_<pipeline>_release frees, behind a sync of the streams (release_pipeline) ----
+struct BedPipe {                       // the summary of a .diffs file (bed/mc_bedsum.hip)
+    Grown out;
+    mc_bed_stats stats = {};
+    void release() { out.reset(); }
+};
+struct TrainPipe {                     // the matrices of a --training_tsv file (train/mc_trainrows.hip): X, the contexts, the labels' bytes
+    Grown X, ctx;
+    std::string labels;
+    mc_train_rows_stats stats = {};
+    void release() {
+        X.reset(); ctx.reset();
+        std::string().swap(labels);
+    }
+};
+struct MergePipe {                     // the text of the merge behind `-t N` (merge/mc_rowmerge.hip)
+    Grown out;
+    mc_rows_merge_stats stats = {};
+    void release() { out.reset(); }
+};
+struct FastqPipe {                     // the read qualities of a FASTQ file (fastq/mc_fastqual.hip): keys, offsets and means
+    Grown pool, off, mean;
+    mc_fastq_quality_stats stats = {};
+    void release() { pool.reset(); off.reset(); mean.reset(); }
+};
+struct EvalPipe {                      // the evaluation file of a .diffs file against labelled positions (eval/mc_evalcalls.hip)
+    Grown out;
+    mc_eval_stats stats = {};
+    void release() { out.reset(); }
+};
+struct CmpPipe {                       // the rows of two --vo BED files compared per site (compare/mc_bedcompare.hip)
+    Grown out;
+    mc_cmp_stats stats = {};
+    int64_t unaligned = 0;             // (a lifted comparison) bed1's lines without an image
+    void release() { out.reset(); }
+};
+struct CurPipe {                       // the rows and the BED lines of a native sample compared with a control (compare/mc_curcompare.inc)
+    Grown out, bed;
+    mc_cur_stats stats = {};
+    void release() { out.reset(); bed.reset(); }
+};
+struct CluPipe {                       // the rows and the BED lines of a sample's sites split in two by their currents (compare/mc_sitecluster.inc)
+    Grown out, bed;
+    mc_clu_stats stats = {};
+    void release() { out.reset(); bed.reset(); }
+};
+// The coordinate map of an XMFA alignment (compare/mc_xmfamap.inc): on the device from mc_xmfa_map until the next such call or
+// mc_xmfa_map_release; map[g1] = ordinal << 33 | g2 << 1 | flip, ~0: unmapped.  The view's host copies are pinned, and plain
+// Pinned blocks, not Grown ones: each call allocates them anew at exactly the view's size
+struct XmfaPipe {
+    Pool allocs{"alignment map"};
+    unsigned long long *map = nullptr;
+    int64_t n1 = 0, n2 = 0;
+    Pinned g2, flip;
+    mc_xmfa_stats stats = {};
+    void drop_map() {
+        allocs.clear();
+        map = nullptr;
+        n1 = n2 = 0;
+    }
+    void release() {
+        drop_map();
+        g2.reset(); flip.reset();
+    }
+};
+struct MotifPipe {                     // the rows of the motif finder (motifs/mc_motifscan.hip)
+    Grown out;
+    mc_motif_stats stats = {};
+    mc_motif_iupac_stats iupac_stats = {};
+    // --iterative (motifs/mc_motifiter.inc): the left-over sites' two planes, '+' then '-', and where the contigs stand in them
+    Grown left;
+    int64_t left_words = 0;
+    std::vector<int64_t> left_starts;
+    mc_motif_iter_stats iter_stats = {};
+    void release() {
+        out.reset(); left.reset();
+        left_words = 0;
+    }
+};
+
 // The members' order is the order of construction, and its reverse the order of destruction (mc_ctx_destroy: `delete c` behind a
 // sync of every stream): the streams stand first and go last, behind every event, allocation and pinned block used on them.
 struct mc_ctx {
@@ -309,63 +391,21 @@ struct mc_ctx {
     Pinned site_status_host;                            // pinned copy the host reads (written by a kernel: no DMA)
     void *comm = nullptr;             // ncclComm_t
     int comm_world = 1;
-    // The five units that take whole text files through the GPU (mc_textfeed.h).  Their calls are synchronous and never run side
+    // The seven units that take whole text files through the GPU (mc_textfeed.h).  Their calls are synchronous and never run side
     // by side, so they share the file reader's two pinned blocks and the events that say a block's copy is done (the merge's
     // output leaves through them too): grown on demand, freed by every mc_*_release.  What a call hands out is its pipeline's own
-    // and stays valid until the next call of that pipeline:
+    // (the records above) and stays valid until the next call of that pipeline or its release:
     TextStages text_stages;
-    // ... the summary of a .diffs file (bed/mc_bedsum.hip) and the figures of the last call
-    Pinned bed_out;
-    size_t bed_out_cap = 0;
-    mc_bed_stats bed_stats = {};
-    // ... the matrices of a --training_tsv file (train/mc_trainrows.hip): X and the contexts in pinned memory, the labels' bytes
-    Pinned tr_X, tr_ctx;
-    size_t tr_X_cap = 0, tr_ctx_cap = 0;
-    std::string tr_labels;
-    mc_train_rows_stats tr_stats = {};
-    // ... the text of the merge behind `-t N` (merge/mc_rowmerge.hip)
-    Pinned mg_out;
-    size_t mg_out_cap = 0;
-    mc_rows_merge_stats mg_stats = {};
-    // ... the read qualities of a FASTQ file (fastq/mc_fastqual.hip): keys, offsets and means in pinned memory
-    Pinned fq_pool, fq_off, fq_mean;
-    size_t fq_pool_cap = 0, fq_off_cap = 0, fq_mean_cap = 0;
-    mc_fastq_quality_stats fq_stats = {};
-    // ... the evaluation file of a .diffs file against labelled positions (eval/mc_evalcalls.hip)
-    Pinned eval_out;
-    size_t eval_out_cap = 0;
-    mc_eval_stats eval_stats = {};
-    // ... the rows of two --vo BED files compared per site (compare/mc_bedcompare.hip)
-    Pinned cmp_out;
-    size_t cmp_out_cap = 0;
-    mc_cmp_stats cmp_stats = {};
-    int64_t cmp_unaligned = 0;                    // (a lifted comparison) bed1's lines without an image
-    // ... the rows and the BED lines of a native sample compared with a control (compare/mc_curcompare.inc)
-    Pinned cur_out, cur_bed;
-    size_t cur_out_cap = 0, cur_bed_cap = 0;
-    mc_cur_stats cur_stats = {};
-    // ... the rows and the BED lines of a sample's sites split in two by their currents (compare/mc_sitecluster.inc)
-    Pinned clu_out, clu_bed;
-    size_t clu_out_cap = 0, clu_bed_cap = 0;
-    mc_clu_stats clu_stats = {};
-    // ... the coordinate map of an XMFA alignment (compare/mc_xmfamap.inc): on the device from mc_xmfa_map until the next such
-    // call or mc_xmfa_map_release; map[g1] = ordinal << 33 | g2 << 1 | flip, ~0: unmapped.  The view's host copies are pinned
-    Pool xmfa_allocs{"alignment map"};
-    unsigned long long *xmfa_map = nullptr;
-    int64_t xmfa_n1 = 0, xmfa_n2 = 0;
-    Pinned xmfa_g2, xmfa_flip;
-    mc_xmfa_stats xmfa_stats = {};
-    // ... the rows of the motif finder (motifs/mc_motifscan.hip)
-    Pinned motif_out;
-    size_t motif_out_cap = 0;
-    mc_motif_stats motif_stats = {};
-    mc_motif_iupac_stats motif_iupac_stats = {};
-    // ... --iterative (motifs/mc_motifiter.inc): the left-over sites' two planes, '+' then '-', and where the contigs stand in them
-    Pinned motif_left;
-    size_t motif_left_cap = 0;
-    int64_t motif_left_words = 0;
-    std::vector<int64_t> motif_left_starts;
-    mc_motif_iter_stats motif_iter_stats = {};
+    BedPipe bed;
+    TrainPipe tr;
+    MergePipe mg;
+    FastqPipe fq;
+    EvalPipe eval;
+    CmpPipe cmp;
+    CurPipe currents;
+    CluPipe clusters;
+    XmfaPipe xmfa;
+    MotifPipe motif;
     // the figures of the last random-forest fit (mc_forest_fit.hip, through mc_internal_forest_stats)
     mc_forest_fit_stats forest_stats = {};
 };

@@ -1,9 +1,9 @@
-// mc_own.h -- the owners of what the host side takes from the HIP runtime: device allocations (Pool), a pinned block (Pinned), an
-// event (Event), a stream (Stream).  Each releases what it holds in its destructor, so a function that returns early (HIP_TRY) and a
-// context that is deleted free everything on every path.  hipFree, hipHostFree, hipEventDestroy and hipStreamDestroy are called
+// mc_own.h -- the owners of what the host side takes from the HIP runtime: device allocations (Pool), a pinned block (Pinned), one
+// that grows with the results handed out in it (Grown), an event (Event), a stream (Stream).  Each releases what it holds in its
+// destructor, so a function that returns early (HIP_TRY) and a context that is deleted free everything on every path.  hipFree, hipHostFree, hipEventDestroy and hipStreamDestroy are called
 // here and in two other places under csrc/: mc_host_alloc's block cache (mc_common.cpp: process-wide host buffers that fall back
 // to malloc, no context owns them) and mc_debug_tanh32_max_err (mc_classify.hip, a kernel unit: eight bytes around one launch).
-// Included by mc_ctx.h (the context's units; through it by mc_lines.h and mc_textfeed.h, the five file pipelines' units) and by
+// Included by mc_ctx.h (the context's units; through it by mc_lines.h and mc_textfeed.h, the seven file pipelines' units) and by
 // mc_fit.h (the --train fits).
 #pragma once
 
@@ -79,6 +79,25 @@ struct Pinned {
     }
     template <typename T>
     T *get() const { return (T *)p; }
+};
+
+// a pinned block a result is handed out in, grown on demand.  It owns its capacity: the block and the figure cannot drift apart
+struct Grown {
+    Pinned block;
+    size_t cap = 0;
+    int need(size_t bytes) {                    // at least `bytes`, a quarter more when it has to grow (a failed allocation: nothing, cap 0)
+        if (cap >= bytes) return 0;
+        cap = 0;
+        if (int rc = block.alloc(bytes + bytes / 4)) return rc;
+        cap = bytes + bytes / 4;
+        return 0;
+    }
+    void reset() {
+        block.reset();
+        cap = 0;
+    }
+    template <typename T>
+    T *get() const { return block.get<T>(); }
 };
 
 struct Event {

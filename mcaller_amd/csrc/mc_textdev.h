@@ -1,6 +1,7 @@
-// mc_textdev.h -- what the six units that take whole text files through the GPU share on the device side, the twin of
+// mc_textdev.h -- what the seven units that take whole text files through the GPU share on the device side, the twin of
 // mc_textfeed.h (bed/mc_bedsum.hip with its .inc files, train/mc_trainrows.hip, merge/mc_rowmerge.hip, fastq/mc_fastqual.hip,
-// compare/mc_bedcompare.hip, motifs/mc_motifscan.hip).  Included by those six units only, hence the unnamed namespace.
+// compare/mc_bedcompare.hip, motifs/mc_motifscan.hip, eval/mc_evalcalls.hip).  Included by those seven units only, hence the
+// unnamed namespace.
 //   line_flag     a line declines its file: atomicMin of line << 8 | reason on the head's word -- the FIRST flagged line is named, and
 //                 of several reasons on it the smallest, whatever the order of arrival (the host's half: decline_reason / _line)
 //   ByteClass     the bytes no pipeline takes: >= 0x80; a control byte other than tab (newlines are no part of a line), 0x7f

@@ -1,26 +1,33 @@
-// mc_textfeed.h -- what the six units that take whole text files through the GPU share on the host side (bed/mc_bedsum.hip,
-// train/mc_trainrows.hip, merge/mc_rowmerge.hip, fastq/mc_fastqual.hip, compare/mc_bedcompare.hip -- whose mc_xmfamap.inc sends an XMFA
-// alignment through the same feed, the seventh kind of file --, motifs/mc_motifscan.hip).  Included by those six units only, hence the unnamed
-// namespace: nothing here is linked across units.  An entry point refuses its arguments (-12), takes each of its sources
-// (text_source: the checks on a mc_text_source, a file sized), selects the device, and then
+// mc_textfeed.h -- what the seven units that take whole text files through the GPU share on the host side (bed/mc_bedsum.hip,
+// train/mc_trainrows.hip, merge/mc_rowmerge.hip, fastq/mc_fastqual.hip, eval/mc_evalcalls.hip, motifs/mc_motifscan.hip and
+// compare/mc_bedcompare.hip, whose .inc files hold four pipelines: the comparison, the alignment map, the currents, the clusters).
+// Included by those seven units only, hence the unnamed namespace: nothing here is linked across units.
 //
-//     const auto t0 = std::chrono::steady_clock::now();
-//     ... blank the stats and the result; device_fits(n + ...) or decline(stats, status, "reader", text, reason, -1) ...
-//     Pool pool("x");                                  // device allocations (mc_own.h), freed when the entry point returns
-//     TextFeed feed(c, (size_t)64 << 20);              // the step through a file: at most this (MCALLER_TEXT_STAGE_BYTES)
-//     char *d_text = nullptr;
-//     if (int rc = feed.put(pool, src, &d_text)) return rc;        // src: a host text or a file; padded and waited for
-//     feed.times(stats, t0);                           // ms_read, ms_h2d
-//     long long *tile_off = nullptr, *line_start = nullptr;
-//     lines_count(pool, st, d_text, n, &d_head->kp, &tile_off); ... the unit's own kernels ...; fetch_head(st, d_head, h);
-//     if (too_many_lines(h.kp.n_newlines)) return decline(...);
-//     lines_starts(pool, st, d_text, n, h.kp.n_newlines, tile_off, &d_head->kp, &line_start); ...; fetch_head(st, d_head, h);
-//     if (h.decline != ~0ull) return decline(stats, status, "reader", text, decline_reason(h.decline), decline_line(h.decline));
+// What the author of another pipeline writes.  In mc_ctx.h a record `XPipe x` with the Grown blocks its results are handed out in,
+// its stats and a release().  An entry point that refuses its arguments (-12), takes each of its sources (text_source: the checks
+// on a mc_text_source, a file sized) and then runs its body inside the call frame:
 //
-// Several texts behind one another in one buffer (the merge, the comparison): feed.send(src, d_dst, &last_byte) for each, then
-// feed.pad_and_wait(d_end).  The feed's two pinned stages and their events are the context's (mc_ctx::text_stages): the calls of
-// the five units are synchronous and never run side by side, so one pair serves them all.
-// The device side the five share -- the decline word, byte classes, key hash, key table, tab spans, LDS staging -- is mc_textdev.h,
+//     return pipeline_call(c, c->x.stats, status, "x", (size_t)64 << 20, [&] { *out = nullptr; *n_out = 0; }, [&](Call &K) -> int {
+//         c->x.stats.n_bytes = src.n_bytes;
+//         if (!fits("MCALLER_X_DEVICE_BYTES", n + ...)) return decline(c->x.stats, status, "reader", text, reason, -1);
+//         char *d_text = nullptr;
+//         if (int rc = K.feed.put(K.pool, src, &d_text)) return rc;        // src: a host text or a file; padded and waited for
+//         K.feed.times(c->x.stats, K.t0);                                  // ms_read, ms_h2d
+//         lines_count(..); the unit's own kernels; fetch_head(..); too_many_lines(..); lines_starts(..); fetch_head(..);
+//         if (h.decline != ~0ull) return decline(.., decline_reason(h.decline), decline_line(h.decline));
+//         return fetch_out(c, c->x.out, d_out, n, out, n_out);             // the result into the pipeline's pinned block
+//     });
+//
+// The frame (pipeline_call) selects the device, blanks the stats, the status and -- through the first callable -- the results,
+// owns the call's Pool and TextFeed (K.pool, K.feed), and on every way out waits for c->stream before the pool goes, blanks the
+// results again unless the call produced some (rc == 0 and *status == 0) and writes ms_total.  Two more entry points are one line
+// each: mc_x_last_stats (stats_out) and mc_x_release (release_pipeline).
+//
+// Several texts behind one another in one buffer: K.feed.put_pair for two whose lines are numbered through (the comparisons, the
+// motif finder), or K.feed.send(src, d_dst, &last_byte) for each and then K.feed.pad_and_wait(d_end) (the merge).  The feed's two
+// pinned stages and their events are the context's (mc_ctx::text_stages): the calls of the seven units are synchronous and never
+// run side by side, so one pair serves them all.
+// The device side they share -- the decline word, byte classes, key hash, key table, tab spans, LDS staging -- is mc_textdev.h,
 // which comes in through this header; table_slots / table_get below are its key table's host half.
 #pragma once
 #include "mc_lines.h"
@@ -46,13 +53,12 @@ inline bool device_fits(size_t bytes) {
     return free_b > margin && bytes <= free_b - margin;
 }
 
-// a pinned block a result is handed out in: at least `bytes`, a quarter more when it has to grow
-inline int grow(Pinned &p, size_t &cap, size_t bytes) {
-    if (cap >= bytes) return 0;
-    cap = 0;
-    if (int rc = p.alloc(bytes + bytes / 4)) return rc;
-    cap = bytes + bytes / 4;
-    return 0;
+// the same behind a test's knob: where the environment variable `knob` holds a positive number, that stands for the free device
+// memory (anything else: as if unset)
+inline bool fits(const char *knob, size_t bytes) {
+    const char *e = getenv(knob);
+    const long long have = e ? atoll(e) : 0;
+    return have > 0 ? bytes <= (size_t)have : device_fits(bytes);
 }
 
 inline int regular_file_size(const char *what, const char *path, int64_t *n) {
@@ -83,6 +89,15 @@ int decline(S &stats, int32_t *status, const char *noun, const char *text, int r
     else mc_set_error("the device %s declines: %s", noun, text);
     *status = 1;
     return 0;
+}
+// ... of one of a call's files: decline_file, and the file's noun behind the reason -- nouns[file - 1]; file 0: no file, no noun
+template <typename S>
+int decline_in_file(S &stats, int32_t *status, const char *noun, const char *text, const char *const *nouns, int reason, int file, long long line) {
+    stats.decline_file = file;
+    char what[200];
+    if (file) snprintf(what, sizeof what, "%s (%s)", text, nouns[file - 1]);
+    else snprintf(what, sizeof what, "%s", text);
+    return decline(stats, status, noun, what, reason, line);
 }
 inline int decline_reason(unsigned long long word) { return (int)(word & 0xff); }
 inline long long decline_line(unsigned long long word) { return (long long)(word >> 8); }
@@ -200,6 +215,20 @@ struct TextFeed {
         HIP_TRY(hipStreamSynchronize(c->up_stream));
         return 0;
     }
+    // Two texts in one buffer, padded and waited for: the first, a newline if a second follows and the first lacked its last (its
+    // last line ends where the second's first begins), the second (null: none) from *off2 on.  Room: both texts, 1 + 64 bytes
+    int put_pair(const mc_text_source &s1, const mc_text_source *s2, char *d_dst, int64_t *off2) {
+        char last1 = '\n';
+        if (int rc = send(s1, d_dst, &last1)) return rc;
+        *off2 = s1.n_bytes;
+        if (s2 && s1.n_bytes > 0 && last1 != '\n') {
+            HIP_TRY(hipMemsetAsync(d_dst + *off2, '\n', 1, c->up_stream));
+            ++*off2;
+        }
+        if (s2)
+            if (int rc = send(*s2, d_dst + *off2)) return rc;
+        return pad_and_wait(d_dst + *off2 + (s2 ? s2->n_bytes : 0));
+    }
     int put(Pool &pool, const mc_text_source &s, char **d_text) {  // one text in a buffer of its own, padded and waited for
         if (pool.get(d_text, (size_t)s.n_bytes + 64)) return -10;
         if (int rc = send(s, *d_text)) return rc;
@@ -211,5 +240,64 @@ struct TextFeed {
         stats.ms_h2d = ms_since(t0) - ms_read;
     }
 };
+
+// ---- the frame of a call ----
+// what a call owns while it runs: its device allocations, freed when the frame is left, and the feed its texts go through
+struct Call {
+    Pool pool;
+    TextFeed feed;
+    const std::chrono::steady_clock::time_point t0;
+};
+
+// One call of a file pipeline around its `body`: int(Call &), which returns 0 with the results filled in, 0 behind a decline (the
+// status set) or an error.  blank(): the entry point's results to none -- run before the body, and behind it unless the call
+// produced a result
+template <typename S, typename Blank, typename Body>
+int pipeline_call(mc_ctx *c, S &stats, int32_t *status, const char *who, size_t max_block, Blank blank, Body body) {
+    blank();
+    *status = 0;
+    HIP_TRY(hipSetDevice(c->device));
+    Call K{Pool(who), TextFeed(c, max_block), std::chrono::steady_clock::now()};
+    stats = S();
+    stats.decline_line = -1;
+    const int rc = body(K);
+    (void)hipStreamSynchronize(c->stream);                   // (whatever the way out: nothing of the pool is in use when it goes)
+    if (rc != 0 || *status != 0) blank();
+    stats.ms_total = ms_since(K.t0);
+    return rc;
+}
+
+// mc_<pipeline>_last_stats: a copy of one of the pipeline's stats
+template <typename P, typename S>
+int stats_out(const char *what, mc_ctx *c, S *out, P mc_ctx::*pipe, S P::*member) {
+    if (!c || !out) { mc_set_error("%s: bad arguments", what); return -12; }
+    *out = (c->*pipe).*member;
+    return 0;
+}
+
+// mc_<pipeline>_release: what the pipeline hands out and the feed's stages, behind everything that may still use them
+template <typename P>
+int release_pipeline(mc_ctx *c, P mc_ctx::*pipe) {
+    if (!c) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipStreamSynchronize(c->up_stream));
+    (c->*pipe).release();
+    c->text_stages.release();
+    return 0;
+}
+
+// A result of n bytes on the device into the pipeline's pinned block, waited for and handed out (n == 0: no block, no copy, a
+// null pointer)
+inline int fetch_out(mc_ctx *c, Grown &dst, const char *d_src, size_t n, const char **out, int64_t *n_out) {
+    *out = nullptr; *n_out = 0;
+    if (n == 0) return 0;
+    if (int rc = dst.need(n)) return rc;
+    HIP_TRY(hipMemcpyAsync(dst.get<char>(), d_src, n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *out = dst.get<char>();
+    *n_out = (int64_t)n;
+    return 0;
+}
 
 }  // namespace

@@ -393,8 +393,8 @@ int mg_file_of(const MgFiles &F, int64_t offset) {
 }
 
 int mg_decline(mc_ctx *c, int32_t *status, int reason, long long line, int file) {
-    c->mg_stats.decline_file = file;
-    return decline(c->mg_stats, status, "merge", mg_reason_text(reason), reason, line);
+    c->mg.stats.decline_file = file;
+    return decline(c->mg.stats, status, "merge", mg_reason_text(reason), reason, line);
 }
 
 constexpr size_t MG_BYTES_PER_LINE = 8 + 8 + 8 + 2 + 4 + 1 + 8 + 2 * (8 + 4 + 4 + 4) + 1 + 4 + 4 + 4 + 4;   // the tables of MgArgs
@@ -407,15 +407,13 @@ int mg_pass(mc_ctx *c, MgArgs &A, int64_t m, int of_seg, int sh) {
     hipLaunchKernelGGL(kp_scan, dim3(1), dim3(1024), 0, st, (const long long *)A.cnt, (int64_t)256 * wgs, A.cnt_off, &A.head->scratch);
     hipLaunchKernelGGL(km_scatter, dim3(wgs), dim3(256), 0, st, A, m, of_seg, sh);
     std::swap(A.kw, A.kw_dst); std::swap(A.sg, A.sg_dst); std::swap(A.ln, A.ln_dst);
-    c->mg_stats.n_passes += 1;
-    c->mg_stats.kernel_bytes += m * (of_seg ? 4 : 8) + m * 2 * 16 + (int64_t)wgs * 256 * 8 * 4;
+    c->mg.stats.n_passes += 1;
+    c->mg.stats.kernel_bytes += m * (of_seg ? 4 : 8) + m * 2 * 16 + (int64_t)wgs * 256 * 8 * 4;
     return 0;
 }
 
 // a call of either entry point: the texts one behind the other on the device (mg_upload), and what mg_run makes of them
 struct MgCall {
-    std::chrono::steady_clock::time_point t0;
-    Pool pool{"row merge"};
     MgFiles F;
     char *d_text = nullptr;
     int64_t n = 0;                               // bytes of all texts
@@ -429,7 +427,7 @@ struct MgCall {
 // bad_end: the offset behind a part file that does not end in a newline, -1: none
 int mg_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const MgFiles &F, int64_t bad_end, MgArgs &A, int64_t *n_out,
            int32_t *status) {
-    mc_rows_merge_stats &S = c->mg_stats;
+    mc_rows_merge_stats &S = c->mg.stats;
     hipStream_t st = c->stream;
     HIP_TRY(hipStreamSynchronize(c->up_stream));
     const auto t_kernels = std::chrono::steady_clock::now();
@@ -550,18 +548,13 @@ int mg_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const MgFiles &
 
 // what both entry points begin with: the sources' texts onto the device, one behind the other -> 0: go on; 1: done (declined,
 // *status set); < 0: an error
-int mg_upload(mc_ctx *c, MgCall &M, const mc_text_source *src, int n_src, int32_t *status) {
-    HIP_TRY(hipSetDevice(c->device));
-    M.t0 = std::chrono::steady_clock::now();
+int mg_upload(mc_ctx *c, Call &K, MgCall &M, const mc_text_source *src, int n_src, int32_t *status) {
+    TextFeed &feed = K.feed;
     for (int i = 0; i < n_src; ++i) M.F.end.push_back(M.n += src[i].n_bytes);
-    c->mg_stats = mc_rows_merge_stats();
-    c->mg_stats.decline_line = -1;
-    c->mg_stats.decline_file = -1;
-    c->mg_stats.n_bytes = M.n;
-    *status = 0;
+    c->mg.stats.decline_file = -1;
+    c->mg.stats.n_bytes = M.n;
     if (!device_fits(2 * (size_t)M.n + 4096)) { (void)mg_decline(c, status, MC_MERGE_DECLINE_MEMORY, -1, -1); return 1; }
-    if (M.pool.get(&M.d_text, (size_t)M.n + 64)) return -10;
-    TextFeed feed(c, (size_t)64 << 20);
+    if (K.pool.get(&M.d_text, (size_t)M.n + 64)) return -10;
     M.block = feed.block_for(M.n);
     // files (a call's sources are all files or all texts): the stages sized once, before the first block, for the step of all
     // texts together -- the output's
@@ -573,7 +566,7 @@ int mg_upload(mc_ctx *c, MgCall &M, const mc_text_source *src, int n_src, int32_
         if (last != '\n' && M.bad_end < 0) M.bad_end = M.F.end[i];
     }
     if (int rc = feed.pad_and_wait(M.d_text + M.n)) return rc;
-    feed.times(c->mg_stats, M.t0);
+    feed.times(c->mg.stats, K.t0);
     return 0;
 }
 
@@ -589,6 +582,48 @@ int mg_write_all(int fd, const char *p, size_t n) {
     return 0;
 }
 
+// The output in blocks through the feed's two stages: a block is written while the next is on its way.  The file appears under
+// its name only when it is complete
+int mg_to_file(mc_ctx *c, const MgCall &M, const char *out_path) {
+    int rc = 0;
+    TextStages &T = c->text_stages;
+    const int64_t nb = M.nb, cap = (int64_t)M.block;
+    const std::string tmp = std::string(out_path) + ".merging";
+    const int fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
+    if (fd < 0) { mc_set_error("mc_rows_merge_files: cannot write %s: %s", tmp.c_str(), strerror(errno)); rc = -1; }
+    double ms_write = 0;
+    const auto t_out = std::chrono::steady_clock::now();
+    // block i goes through stage i & 1: its successor is enqueued before block i is waited for and written
+    const int64_t n_blocks_out = (nb + cap - 1) / cap;
+    auto enqueue = [&](int64_t i) {
+        const int64_t lo = i * cap, k = std::min<int64_t>(cap, nb - lo);
+        int r = mc_hip_rc(hipMemcpyAsync(T.stage[i & 1].p, M.A.out + lo, (size_t)k, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync");
+        if (r == 0) r = mc_hip_rc(hipEventRecord(T.ev[i & 1], c->stream), "hipEventRecord");
+        return r;
+    };
+    if (rc == 0 && n_blocks_out > 0) rc = enqueue(0);
+    for (int64_t i = 0; i < n_blocks_out && rc == 0; ++i) {
+        if (i + 1 < n_blocks_out) rc = enqueue(i + 1);
+        if (rc == 0) rc = mc_hip_rc(hipEventSynchronize(T.ev[i & 1]), "hipEventSynchronize");
+        if (rc) break;
+        const auto tw = std::chrono::steady_clock::now();
+        if (mg_write_all(fd, T.stage[i & 1].get<char>(), (size_t)std::min<int64_t>(cap, nb - i * cap))) {
+            mc_set_error("mc_rows_merge_files: writing %s failed: %s", tmp.c_str(), strerror(errno));
+            rc = -1;
+        }
+        ms_write += ms_since(tw);
+    }
+    if (fd >= 0 && close(fd) != 0 && rc == 0) { mc_set_error("mc_rows_merge_files: closing %s failed: %s", tmp.c_str(), strerror(errno)); rc = -1; }
+    if (rc == 0 && rename(tmp.c_str(), out_path) != 0) {
+        mc_set_error("mc_rows_merge_files: renaming %s failed: %s", tmp.c_str(), strerror(errno));
+        rc = -1;
+    }
+    if (rc != 0 && fd >= 0) (void)unlink(tmp.c_str());
+    c->mg.stats.ms_write = ms_write;
+    c->mg.stats.ms_d2h = ms_since(t_out) - ms_write;
+    return rc;
+}
+
 }  // namespace
 
 extern "C" int mc_rows_merge_text(mc_ctx *c, const char *text, int64_t n_bytes, const char **out, int64_t *n_out, int32_t *status) {
@@ -596,23 +631,17 @@ extern "C" int mc_rows_merge_text(mc_ctx *c, const char *text, int64_t n_bytes, 
         mc_set_error("mc_rows_merge_text: bad arguments");
         return -12;
     }
-    *out = nullptr; *n_out = 0;
     const mc_text_source src = {text, nullptr, n_bytes};
     MgCall M;
-    if (int rc = mg_upload(c, M, &src, 1, status)) return rc < 0 ? rc : 0;
-    int rc = mg_run(c, M.pool, M.d_text, M.n, M.F, M.bad_end, M.A, &M.nb, status);
-    if (rc == 0 && *status == 0 && M.nb > 0) {
+    return pipeline_call(c, c->mg.stats, status, "row merge", (size_t)64 << 20, [&] { *out = nullptr; *n_out = 0; }, [&](Call &K) -> int {
+        if (int rc = mg_upload(c, K, M, &src, 1, status)) return rc < 0 ? rc : 0;
+        if (int rc = mg_run(c, K.pool, M.d_text, M.n, M.F, M.bad_end, M.A, &M.nb, status)) return rc;
+        if (*status != 0) return 0;
         const auto t_d2h = std::chrono::steady_clock::now();
-        const size_t nb = (size_t)M.nb;
-        rc = grow(c->mg_out, c->mg_out_cap, nb);
-        if (rc == 0) rc = mc_hip_rc(hipMemcpyAsync(c->mg_out.p, M.A.out, nb, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync");
-        if (rc == 0) rc = mc_hip_rc(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
-        c->mg_stats.ms_d2h = ms_since(t_d2h);
-        if (rc == 0) { *out = (const char *)c->mg_out.p; *n_out = M.nb; }
-    }
-    (void)hipStreamSynchronize(c->stream);                   // (an early return: nothing of the pool is in use when it goes)
-    c->mg_stats.ms_total = ms_since(M.t0);
-    return rc;
+        const int rc = fetch_out(c, c->mg.out, M.A.out, (size_t)M.nb, out, n_out);
+        c->mg.stats.ms_d2h = ms_since(t_d2h);
+        return rc;
+    });
 }
 
 extern "C" int mc_rows_merge_files(mc_ctx *c, const char *const *paths, int32_t n_paths, const char *out_path, int64_t *n_lines_out,
@@ -626,67 +655,19 @@ extern "C" int mc_rows_merge_files(mc_ctx *c, const char *const *paths, int32_t 
         src[i] = mc_text_source{nullptr, paths[i], 0};
         if (int rc = regular_file_size("mc_rows_merge_files", paths[i], &src[i].n_bytes)) return rc;
     }
-    *n_lines_out = 0;
     MgCall M;
-    if (int rc = mg_upload(c, M, src.data(), n_paths, status)) return rc < 0 ? rc : 0;
-    int rc = mg_run(c, M.pool, M.d_text, M.n, M.F, M.bad_end, M.A, &M.nb, status);
-    if (rc == 0 && *status == 0) {
-        // the output in blocks through the feed's two stages: a block is written while the next is on its way.  The file appears
-        // under its name only when it is complete
-        TextStages &T = c->text_stages;
-        const int64_t nb = M.nb, cap = (int64_t)M.block;
-        const std::string tmp = std::string(out_path) + ".merging";
-        const int fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
-        if (fd < 0) { mc_set_error("mc_rows_merge_files: cannot write %s: %s", tmp.c_str(), strerror(errno)); rc = -1; }
-        double ms_write = 0;
-        const auto t_out = std::chrono::steady_clock::now();
-        // block i goes through stage i & 1: its successor is enqueued before block i is waited for and written
-        const int64_t n_blocks_out = (nb + cap - 1) / cap;
-        auto enqueue = [&](int64_t i) {
-            const int64_t lo = i * cap, k = std::min<int64_t>(cap, nb - lo);
-            int r = mc_hip_rc(hipMemcpyAsync(T.stage[i & 1].p, M.A.out + lo, (size_t)k, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync");
-            if (r == 0) r = mc_hip_rc(hipEventRecord(T.ev[i & 1], c->stream), "hipEventRecord");
-            return r;
-        };
-        if (rc == 0 && n_blocks_out > 0) rc = enqueue(0);
-        for (int64_t i = 0; i < n_blocks_out && rc == 0; ++i) {
-            if (i + 1 < n_blocks_out) rc = enqueue(i + 1);
-            if (rc == 0) rc = mc_hip_rc(hipEventSynchronize(T.ev[i & 1]), "hipEventSynchronize");
-            if (rc) break;
-            const auto tw = std::chrono::steady_clock::now();
-            if (mg_write_all(fd, T.stage[i & 1].get<char>(), (size_t)std::min<int64_t>(cap, nb - i * cap))) {
-                mc_set_error("mc_rows_merge_files: writing %s failed: %s", tmp.c_str(), strerror(errno));
-                rc = -1;
-            }
-            ms_write += ms_since(tw);
-        }
-        if (fd >= 0 && close(fd) != 0 && rc == 0) { mc_set_error("mc_rows_merge_files: closing %s failed: %s", tmp.c_str(), strerror(errno)); rc = -1; }
-        if (rc == 0 && rename(tmp.c_str(), out_path) != 0) {
-            mc_set_error("mc_rows_merge_files: renaming %s failed: %s", tmp.c_str(), strerror(errno));
-            rc = -1;
-        }
-        if (rc != 0 && fd >= 0) (void)unlink(tmp.c_str());
-        c->mg_stats.ms_write = ms_write;
-        c->mg_stats.ms_d2h = ms_since(t_out) - ms_write;
-        if (rc == 0) *n_lines_out = c->mg_stats.n_lines_out;
-    }
-    (void)hipStreamSynchronize(c->stream);
-    c->mg_stats.ms_total = ms_since(M.t0);
-    return rc;
+    return pipeline_call(c, c->mg.stats, status, "row merge", (size_t)64 << 20, [&] { *n_lines_out = 0; }, [&](Call &K) -> int {
+        if (int rc = mg_upload(c, K, M, src.data(), n_paths, status)) return rc < 0 ? rc : 0;
+        if (int rc = mg_run(c, K.pool, M.d_text, M.n, M.F, M.bad_end, M.A, &M.nb, status)) return rc;
+        if (*status != 0) return 0;
+        if (int rc = mg_to_file(c, M, out_path)) return rc;
+        *n_lines_out = c->mg.stats.n_lines_out;
+        return 0;
+    });
 }
 
 extern "C" int mc_rows_merge_last_stats(mc_ctx *c, mc_rows_merge_stats *out) {
-    if (!c || !out) { mc_set_error("mc_rows_merge_last_stats: bad arguments"); return -12; }
-    *out = c->mg_stats;
-    return 0;
+    return stats_out("mc_rows_merge_last_stats", c, out, &mc_ctx::mg, &MergePipe::stats);
 }
 
-extern "C" int mc_rows_merge_release(mc_ctx *c) {
-    if (!c) return 0;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipStreamSynchronize(c->up_stream));
-    c->mg_out.reset(); c->mg_out_cap = 0;
-    c->text_stages.release();
-    return 0;
-}
+extern "C" int mc_rows_merge_release(mc_ctx *c) { return release_pipeline(c, &mc_ctx::mg); }

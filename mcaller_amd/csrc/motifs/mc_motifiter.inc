@@ -94,8 +94,8 @@ inline size_t it_need(int64_t n_bases, int64_t n_words, int64_t *list_bytes) {
 int it_run(mc_ctx *c, Pool &pool, MsArgs &A, MsHead *d_head, const mc_motif_params &P, const std::vector<MsTable> &tables, bool iupac,
            int max_motifs, size_t scratch, std::chrono::steady_clock::time_point t_first, const char **out, int64_t *n_out, int64_t *n_rows,
            int32_t *status) {
-    mc_motif_stats &S = c->motif_stats;
-    mc_motif_iter_stats &I = c->motif_iter_stats;
+    mc_motif_stats &S = c->motif.stats;
+    mc_motif_iter_stats &I = c->motif.iter_stats;
     hipStream_t st = c->stream;
     MiState mi;
     if (iupac)
@@ -172,11 +172,11 @@ int it_run(mc_ctx *c, Pool &pool, MsArgs &A, MsHead *d_head, const mc_motif_para
     if (int rc = fetch_head(st, d_head, h)) return rc;
     if (rounds > 1) I.ms_later_rounds = ms_since(t_later);
     const size_t left_bytes = (size_t)A.n_words * 16;
-    if (int rc = grow(c->motif_left, c->motif_left_cap, left_bytes)) return rc;
+    if (int rc = c->motif.left.need(left_bytes)) return rc;
     t_d2h = std::chrono::steady_clock::now();
-    HIP_TRY(hipMemcpyAsync(c->motif_left.p, A.left, left_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(c->motif.left.get<uint64_t>(), A.left, left_bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    c->motif_left_words = A.n_words;
+    c->motif.left_words = A.n_words;
     I.n_rounds = rounds;
     I.n_unexplained = (int64_t)h.n_left;
     S.n_rows = rounds;

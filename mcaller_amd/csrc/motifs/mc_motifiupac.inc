@@ -226,8 +226,8 @@ int mi_setup(Pool &pool, const MsArgs &A, const std::vector<MsTable> &tables, si
 // stats keep round 1's figures; the flags, the lattices and the head are made anew every round
 int mi_rows(mc_ctx *c, Pool &pool, MiState &mi, const std::vector<MsTable> &tables, bool again, std::vector<MiPat> &rows,
             std::chrono::steady_clock::time_point *t_d2h, int32_t *status) {
-    mc_motif_stats &S = c->motif_stats;
-    mc_motif_iupac_stats &I = c->motif_iupac_stats;
+    mc_motif_stats &S = c->motif.stats;
+    mc_motif_iupac_stats &I = c->motif.iupac_stats;
     hipStream_t st = c->stream;
     MiArgs &M = mi.M;
     rows.clear();

@@ -377,11 +377,8 @@ const char *ms_reason_text(int reason) {
 
 // file: 1 (the bed), 2 (the control) or 0; line: in that file, -1: none
 int ms_decline(mc_ctx *c, int32_t *status, int reason, int file, long long line) {
-    c->motif_stats.decline_file = file;
-    char what[160];
-    if (file) snprintf(what, sizeof what, "%s (%s)", ms_reason_text(reason), file == 1 ? "bed" : "control");
-    else snprintf(what, sizeof what, "%s", ms_reason_text(reason));
-    return decline(c->motif_stats, status, "motif finder", what, reason, line);
+    static const char *const nouns[2] = {"bed", "control"};
+    return decline_in_file(c->motif.stats, status, "motif finder", ms_reason_text(reason), nouns, reason, file, line);
 }
 
 int ms_decline_head(mc_ctx *c, int32_t *status, const MsHead &h) {
@@ -391,11 +388,7 @@ int ms_decline_head(mc_ctx *c, int32_t *status, const MsHead &h) {
 }
 
 // device_fits, or (tests) as if MCALLER_MOTIF_DEVICE_BYTES were all the device had free
-bool ms_fits(size_t bytes) {
-    const char *e = getenv("MCALLER_MOTIF_DEVICE_BYTES");
-    const long long have = e ? atoll(e) : 0;
-    return have > 0 ? bytes <= (size_t)have : device_fits(bytes);
-}
+bool ms_fits(size_t bytes) { return fits("MCALLER_MOTIF_DEVICE_BYTES", bytes); }
 
 // the tables of the shapes and, for every table, the tables that embed in it -> false: the params are not what the header allows
 bool ms_tables(const mc_motif_params &P, std::vector<MsTable> &tables, std::vector<MsParent> &parents) {
@@ -466,14 +459,14 @@ bool ms_put_numbers(MsText &text, int o, uint32_t nG, uint32_t nC, uint32_t nM) 
     return true;
 }
 
-// the rows' bytes into the context's pinned block, handed out
+// the rows' bytes into the context's pinned block, handed out (built on the host: a memcpy, no fetch_out)
 int ms_hand_out(mc_ctx *c, const MsText &text, std::chrono::steady_clock::time_point t_d2h, const char **out, int64_t *n_out) {
-    mc_motif_stats &S = c->motif_stats;
-    if (int rc = grow(c->motif_out, c->motif_out_cap, text.s.size())) return rc;
-    memcpy(c->motif_out.p, text.s.data(), text.s.size());
+    mc_motif_stats &S = c->motif.stats;
+    if (int rc = c->motif.out.need(text.s.size())) return rc;
+    memcpy(c->motif.out.get<char>(), text.s.data(), text.s.size());
     S.ms_d2h = ms_since(t_d2h);
     S.n_out_bytes = (int64_t)text.s.size();
-    *out = c->motif_out.get<char>();
+    *out = c->motif.out.get<char>();
     *n_out = (int64_t)text.s.size();
     return 0;
 }
@@ -482,7 +475,7 @@ int ms_hand_out(mc_ctx *c, const MsText &text, std::chrono::steady_clock::time_p
 // head's counters are zeroed first and the stats keep round 1's figures
 int ms_rows(mc_ctx *c, Pool &pool, MsArgs &A, MsHead *d_head, bool again, std::vector<MsRow> &rows, std::chrono::steady_clock::time_point *t_d2h,
             int32_t *status) {
-    mc_motif_stats &S = c->motif_stats;
+    mc_motif_stats &S = c->motif.stats;
     hipStream_t st = c->stream;
     MsHead h = {};
     rows.clear();
@@ -545,7 +538,7 @@ bool ms_line(MsText &text, const mc_motif_params &P, const std::vector<MsTable> 
 // max_motifs: 0, or --iterative's
 int ms_run(mc_ctx *c, Pool &pool, MsArgs &A, MsHead *d_head, const mc_motif_params &P, const std::vector<MsTable> &tables, bool iupac,
            int max_motifs, size_t scratch, const char **out, int64_t *n_out, int64_t *n_rows, int32_t *status) {
-    mc_motif_stats &S = c->motif_stats;
+    mc_motif_stats &S = c->motif.stats;
     hipStream_t st = c->stream;
     const auto t_first = std::chrono::steady_clock::now();
     MsHead h = {};
@@ -618,128 +611,113 @@ int ms_run(mc_ctx *c, Pool &pool, MsArgs &A, MsHead *d_head, const mc_motif_para
 // max_motifs: 0, or --iterative's 1 .. MC_MOTIF_MAX_ROUNDS
 int ms_call(mc_ctx *c, const mc_ref_view *ref, const mc_text_source &s1, const mc_text_source *s2, const mc_motif_params *P, bool iupac,
             int max_motifs, const char **out, int64_t *n_out, int64_t *n_rows, int32_t *status) {
-    HIP_TRY(hipSetDevice(c->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    mc_motif_stats &S = c->motif_stats;
-    S = mc_motif_stats();
-    S.decline_line = -1;
-    S.n_bytes1 = s1.n_bytes; S.n_bytes2 = s2 ? s2->n_bytes : 0;
-    c->motif_iupac_stats = mc_motif_iupac_stats();
-    c->motif_iter_stats = mc_motif_iter_stats();
-    c->motif_iter_stats.decline_line = -1;
-    c->motif_left_words = 0;
-    c->motif_left_starts.clear();
-    *out = nullptr; *n_out = 0; *n_rows = 0; *status = 0;
-    std::vector<MsTable> tables;
-    std::vector<MsParent> parents;
-    const int base_code = P->base == 'A' ? 0 : P->base == 'C' ? 1 : P->base == 'G' ? 2 : P->base == 'T' ? 3 : -1;
-    if (base_code < 0 || !ms_tables(*P, tables, parents) || !(P->min_fraction >= 0.0) || P->min_sites < 0) {
-        mc_set_error("mc_motif_report: a base other than A, C, G, T, a string that is no shape, or a negative threshold");
-        return -12;
-    }
-    const int NC = ref->n_contigs;
-    int64_t n_bases = 0;
-    for (int i = 0; i < NC; ++i) n_bases += ref->contig_len[i];
-    if (n_bases >= ((int64_t)1 << 31) || NC >= (1 << 24)) return ms_decline(c, status, MC_MOTIF_DECLINE_REFERENCE, 0, -1);
-    // where the contigs stand: multiples of 64, at least 32 bases of padding behind each, 64 in front of the first
-    std::vector<int64_t> gstart((size_t)NC + 1);
-    int64_t G = 64;
-    for (int i = 0; i < NC; ++i) {
-        gstart[i] = G;
-        G = (G + ref->contig_len[i] + 32 + 63) & ~(int64_t)63;
-    }
-    const int64_t n_words = G / 64 + 2;
-    const uint32_t n_entries = tables.back().off + tables.back().entries;
-    const int64_t n_text = s1.n_bytes + (s2 ? s2->n_bytes : 0);
-    const int64_t id_bytes = NC > 0 ? P->contig_id_off[NC] : 0;
-    const char *hs = getenv("MCALLER_MOTIF_STRETCH");
-    int64_t stretch = hs && atoll(hs) >= 64 ? (atoll(hs) + 63) & ~63ll : MS_STRETCH;      // (below 64: as if unset)
-    stretch = std::min<int64_t>(stretch, G);
-    S.stretch = stretch; S.n_entries = n_entries;
-    const uint64_t slots = table_slots(NC, 64, "MCALLER_MOTIF_TABLE_SLOTS");
-    S.table_slots = (int64_t)slots;
-    const size_t need = (size_t)ref->n_seq_bytes + (size_t)n_words * 8 * 9 + (size_t)n_entries * 14 + (size_t)n_text + (size_t)id_bytes +
-                        (size_t)NC * 32 + slots * 8 + parents.size() * sizeof(MsParent) + ((size_t)1 << 20);
-    size_t scratch = 0;
-    const size_t need_iupac = iupac ? mi_need(tables, &scratch) : 0;    // (and the tables learn their places in the lattice block)
-    c->motif_iupac_stats.lattice_bytes = (int64_t)need_iupac;
-    const size_t need_iter = max_motifs > 0 ? it_need(n_bases, n_words, &c->motif_iter_stats.list_bytes) : 0;
-    c->motif_iter_stats.need_bytes = (int64_t)(need + need_iupac + need_iter);
-    if (!ms_fits(need + need_iupac + need_iter)) return ms_decline(c, status, MC_MOTIF_DECLINE_MEMORY, 0, -1);
-    Pool pool("motif finder");
-    hipStream_t up = c->up_stream;
-    MsArgs A = {};
-    uint8_t *d_seq = nullptr;
-    int64_t *d_meta = nullptr, *d_id_off = nullptr;
-    char *d_ids = nullptr, *d_text = nullptr;
-    uint64_t *d_planes = nullptr;
-    MsTable *d_tables = nullptr;
-    MsParent *d_parents = nullptr;
-    MsHead *d_head = nullptr;
-    if (pool.get(&d_seq, (size_t)ref->n_seq_bytes + 1) || pool.get(&d_meta, (size_t)NC * 3 + 1) || pool.get(&d_id_off, (size_t)NC + 1) ||
-        pool.get(&d_ids, (size_t)id_bytes + 1) || pool.get(&d_text, (size_t)n_text + 1 + 64) || pool.get(&d_planes, (size_t)n_words * 9) ||
-        pool.get(&d_tables, tables.size()) || pool.get(&d_parents, parents.size() + 1) || pool.get(&d_head, 1) ||
-        pool.get(&A.nG, (size_t)n_entries * 3) || pool.get(&A.selected, (size_t)n_entries * 2))
-        return -10;
-    if (max_motifs > 0) {
-        if (pool.get(&A.list, (size_t)n_bases + 1) || pool.get(&A.left, (size_t)n_words * 2)) return -10;
-        A.cap_list = n_bases;
-    }
-    if (int rc = table_get(pool, up, &A.table, slots)) return rc;
-    // the reference and the tables (pageable host memory: the copies are done when the calls return), then the texts
-    std::vector<int64_t> meta((size_t)NC * 3 + 1);
-    for (int i = 0; i < NC; ++i) { meta[i] = ref->contig_len[i]; meta[NC + i] = ref->seq_off[i]; meta[2 * NC + i] = gstart[i]; }
-    MsHead h = {};
-    h.decline = MS_NO_DECLINE;
-    if (ref->n_seq_bytes > 0) HIP_TRY(hipMemcpyAsync(d_seq, ref->seq, (size_t)ref->n_seq_bytes, hipMemcpyHostToDevice, up));
-    if (NC > 0) {
-        HIP_TRY(hipMemcpyAsync(d_meta, meta.data(), (size_t)NC * 3 * 8, hipMemcpyHostToDevice, up));
-        HIP_TRY(hipMemcpyAsync(d_id_off, P->contig_id_off, ((size_t)NC + 1) * 8, hipMemcpyHostToDevice, up));
-        if (id_bytes > 0) HIP_TRY(hipMemcpyAsync(d_ids, P->contig_ids, (size_t)id_bytes, hipMemcpyHostToDevice, up));
-    }
-    HIP_TRY(hipMemcpyAsync(d_tables, tables.data(), tables.size() * sizeof(MsTable), hipMemcpyHostToDevice, up));
-    if (!parents.empty()) HIP_TRY(hipMemcpyAsync(d_parents, parents.data(), parents.size() * sizeof(MsParent), hipMemcpyHostToDevice, up));
-    HIP_TRY(hipMemcpyAsync(d_head, &h, sizeof h, hipMemcpyHostToDevice, up));
-    HIP_TRY(hipMemsetAsync(d_planes + 5 * n_words, 0, (size_t)n_words * 4 * 8, up));             // methylated and control, both strands
-    HIP_TRY(hipMemsetAsync(A.nG, 0, (size_t)n_entries * 3 * 4, up));
-    HIP_TRY(hipStreamSynchronize(up));                                // (meta, h and the vectors are the host's again)
-    TextFeed feed(c, (size_t)32 << 20);
-    char last1 = '\n';
-    if (int rc = feed.send(s1, d_text, &last1)) return rc;
-    int64_t off2 = s1.n_bytes;
-    if (s2 && s1.n_bytes > 0 && last1 != '\n') {                       // the bed's last line ends where the control's first begins
-        HIP_TRY(hipMemsetAsync(d_text + off2, '\n', 1, up));
-        ++off2;
-    }
-    if (s2)
-        if (int rc = feed.send(*s2, d_text + off2)) return rc;
-    const int64_t n_bytes = s2 ? off2 + s2->n_bytes : s1.n_bytes;
-    if (int rc = feed.pad_and_wait(d_text + n_bytes)) return rc;
-    feed.times(S, t0);
-    A.seq = d_seq; A.contig_len = d_meta; A.seq_off = d_meta + NC; A.gstart = d_meta + 2 * NC;
-    A.n_contigs = NC; A.base_code = base_code; A.n_words = n_words;
-    A.code0 = d_planes; A.code1 = d_planes + n_words; A.valid = d_planes + 2 * n_words;
-    A.cand[0] = d_planes + 3 * n_words; A.cand[1] = d_planes + 4 * n_words;
-    A.meth[0] = (unsigned long long *)(d_planes + 5 * n_words); A.meth[1] = (unsigned long long *)(d_planes + 6 * n_words);
-    A.ctl[0] = (unsigned long long *)(d_planes + 7 * n_words); A.ctl[1] = (unsigned long long *)(d_planes + 8 * n_words);
-    A.ids = d_ids; A.id_off = d_id_off; A.table_mask = slots - 1;
-    const char *hm = getenv("MCALLER_MOTIF_HASH_MASK");
-    A.hash_mask = hm && *hm ? strtoull(hm, nullptr, 16) : ~0ull;      // (tests: long probe chains)
-    A.text = d_text; A.n_bytes = n_bytes; A.off2 = s2 ? off2 : n_bytes; A.head = d_head;
-    A.tables = d_tables; A.parents = d_parents; A.n_tables = (int32_t)tables.size();
-    A.has_control = s2 ? 1 : 0; A.keep_all = P->keep_all ? 1 : 0;
-    A.stretch = stretch; A.G = G; A.n_entries = n_entries;
-    A.nC = A.nG + n_entries; A.nM = A.nG + 2 * (size_t)n_entries;
-    A.keep = A.selected + n_entries;
-    A.min_sites = P->min_sites; A.min_fraction = P->min_fraction;
-    const auto t_kernels = std::chrono::steady_clock::now();
-    const int rc = ms_run(c, pool, A, d_head, *P, tables, iupac, max_motifs, scratch, out, n_out, n_rows, status);
-    (void)hipStreamSynchronize(c->stream);                             // (an early return: nothing of the pool is in use when it goes)
-    S.ms_kernels = ms_since(t_kernels) - S.ms_d2h;                     // a declined call too: what ran until it declined
-    if (rc != 0 || *status != 0) { *out = nullptr; *n_out = 0; *n_rows = 0; c->motif_left_words = 0; }
-    else if (max_motifs > 0) c->motif_left_starts.assign(gstart.begin(), gstart.begin() + NC);
-    S.ms_total = ms_since(t0);
-    return rc;
+    mc_motif_stats &S = c->motif.stats;
+    const auto blank = [&] { *out = nullptr; *n_out = 0; *n_rows = 0; c->motif.left_words = 0; };
+    return pipeline_call(c, S, status, "motif finder", (size_t)32 << 20, blank, [&](Call &K) -> int {
+        Pool &pool = K.pool;
+        S.n_bytes1 = s1.n_bytes; S.n_bytes2 = s2 ? s2->n_bytes : 0;
+        c->motif.iupac_stats = mc_motif_iupac_stats();
+        c->motif.iter_stats = mc_motif_iter_stats();
+        c->motif.iter_stats.decline_line = -1;
+        c->motif.left_starts.clear();
+        std::vector<MsTable> tables;
+        std::vector<MsParent> parents;
+        const int base_code = P->base == 'A' ? 0 : P->base == 'C' ? 1 : P->base == 'G' ? 2 : P->base == 'T' ? 3 : -1;
+        if (base_code < 0 || !ms_tables(*P, tables, parents) || !(P->min_fraction >= 0.0) || P->min_sites < 0) {
+            mc_set_error("mc_motif_report: a base other than A, C, G, T, a string that is no shape, or a negative threshold");
+            return -12;
+        }
+        const int NC = ref->n_contigs;
+        int64_t n_bases = 0;
+        for (int i = 0; i < NC; ++i) n_bases += ref->contig_len[i];
+        if (n_bases >= ((int64_t)1 << 31) || NC >= (1 << 24)) return ms_decline(c, status, MC_MOTIF_DECLINE_REFERENCE, 0, -1);
+        // where the contigs stand: multiples of 64, at least 32 bases of padding behind each, 64 in front of the first
+        std::vector<int64_t> gstart((size_t)NC + 1);
+        int64_t G = 64;
+        for (int i = 0; i < NC; ++i) {
+            gstart[i] = G;
+            G = (G + ref->contig_len[i] + 32 + 63) & ~(int64_t)63;
+        }
+        const int64_t n_words = G / 64 + 2;
+        const uint32_t n_entries = tables.back().off + tables.back().entries;
+        const int64_t n_text = s1.n_bytes + (s2 ? s2->n_bytes : 0);
+        const int64_t id_bytes = NC > 0 ? P->contig_id_off[NC] : 0;
+        const char *hs = getenv("MCALLER_MOTIF_STRETCH");
+        int64_t stretch = hs && atoll(hs) >= 64 ? (atoll(hs) + 63) & ~63ll : MS_STRETCH;      // (below 64: as if unset)
+        stretch = std::min<int64_t>(stretch, G);
+        S.stretch = stretch; S.n_entries = n_entries;
+        const uint64_t slots = table_slots(NC, 64, "MCALLER_MOTIF_TABLE_SLOTS");
+        S.table_slots = (int64_t)slots;
+        const size_t need = (size_t)ref->n_seq_bytes + (size_t)n_words * 8 * 9 + (size_t)n_entries * 14 + (size_t)n_text + (size_t)id_bytes +
+                            (size_t)NC * 32 + slots * 8 + parents.size() * sizeof(MsParent) + ((size_t)1 << 20);
+        size_t scratch = 0;
+        const size_t need_iupac = iupac ? mi_need(tables, &scratch) : 0;    // (and the tables learn their places in the lattice block)
+        c->motif.iupac_stats.lattice_bytes = (int64_t)need_iupac;
+        const size_t need_iter = max_motifs > 0 ? it_need(n_bases, n_words, &c->motif.iter_stats.list_bytes) : 0;
+        c->motif.iter_stats.need_bytes = (int64_t)(need + need_iupac + need_iter);
+        if (!ms_fits(need + need_iupac + need_iter)) return ms_decline(c, status, MC_MOTIF_DECLINE_MEMORY, 0, -1);
+        hipStream_t up = c->up_stream;
+        MsArgs A = {};
+        uint8_t *d_seq = nullptr;
+        int64_t *d_meta = nullptr, *d_id_off = nullptr;
+        char *d_ids = nullptr, *d_text = nullptr;
+        uint64_t *d_planes = nullptr;
+        MsTable *d_tables = nullptr;
+        MsParent *d_parents = nullptr;
+        MsHead *d_head = nullptr;
+        if (pool.get(&d_seq, (size_t)ref->n_seq_bytes + 1) || pool.get(&d_meta, (size_t)NC * 3 + 1) || pool.get(&d_id_off, (size_t)NC + 1) ||
+            pool.get(&d_ids, (size_t)id_bytes + 1) || pool.get(&d_text, (size_t)n_text + 1 + 64) || pool.get(&d_planes, (size_t)n_words * 9) ||
+            pool.get(&d_tables, tables.size()) || pool.get(&d_parents, parents.size() + 1) || pool.get(&d_head, 1) ||
+            pool.get(&A.nG, (size_t)n_entries * 3) || pool.get(&A.selected, (size_t)n_entries * 2))
+            return -10;
+        if (max_motifs > 0) {
+            if (pool.get(&A.list, (size_t)n_bases + 1) || pool.get(&A.left, (size_t)n_words * 2)) return -10;
+            A.cap_list = n_bases;
+        }
+        if (int rc = table_get(pool, up, &A.table, slots)) return rc;
+        // the reference and the tables (pageable host memory: the copies are done when the calls return), then the texts
+        std::vector<int64_t> meta((size_t)NC * 3 + 1);
+        for (int i = 0; i < NC; ++i) { meta[i] = ref->contig_len[i]; meta[NC + i] = ref->seq_off[i]; meta[2 * NC + i] = gstart[i]; }
+        MsHead h = {};
+        h.decline = MS_NO_DECLINE;
+        if (ref->n_seq_bytes > 0) HIP_TRY(hipMemcpyAsync(d_seq, ref->seq, (size_t)ref->n_seq_bytes, hipMemcpyHostToDevice, up));
+        if (NC > 0) {
+            HIP_TRY(hipMemcpyAsync(d_meta, meta.data(), (size_t)NC * 3 * 8, hipMemcpyHostToDevice, up));
+            HIP_TRY(hipMemcpyAsync(d_id_off, P->contig_id_off, ((size_t)NC + 1) * 8, hipMemcpyHostToDevice, up));
+            if (id_bytes > 0) HIP_TRY(hipMemcpyAsync(d_ids, P->contig_ids, (size_t)id_bytes, hipMemcpyHostToDevice, up));
+        }
+        HIP_TRY(hipMemcpyAsync(d_tables, tables.data(), tables.size() * sizeof(MsTable), hipMemcpyHostToDevice, up));
+        if (!parents.empty()) HIP_TRY(hipMemcpyAsync(d_parents, parents.data(), parents.size() * sizeof(MsParent), hipMemcpyHostToDevice, up));
+        HIP_TRY(hipMemcpyAsync(d_head, &h, sizeof h, hipMemcpyHostToDevice, up));
+        HIP_TRY(hipMemsetAsync(d_planes + 5 * n_words, 0, (size_t)n_words * 4 * 8, up));             // methylated and control, both strands
+        HIP_TRY(hipMemsetAsync(A.nG, 0, (size_t)n_entries * 3 * 4, up));
+        HIP_TRY(hipStreamSynchronize(up));                                // (meta, h and the vectors are the host's again)
+        int64_t off2 = 0;
+        if (int rc = K.feed.put_pair(s1, s2, d_text, &off2)) return rc;
+        const int64_t n_bytes = s2 ? off2 + s2->n_bytes : s1.n_bytes;
+        K.feed.times(S, K.t0);
+        A.seq = d_seq; A.contig_len = d_meta; A.seq_off = d_meta + NC; A.gstart = d_meta + 2 * NC;
+        A.n_contigs = NC; A.base_code = base_code; A.n_words = n_words;
+        A.code0 = d_planes; A.code1 = d_planes + n_words; A.valid = d_planes + 2 * n_words;
+        A.cand[0] = d_planes + 3 * n_words; A.cand[1] = d_planes + 4 * n_words;
+        A.meth[0] = (unsigned long long *)(d_planes + 5 * n_words); A.meth[1] = (unsigned long long *)(d_planes + 6 * n_words);
+        A.ctl[0] = (unsigned long long *)(d_planes + 7 * n_words); A.ctl[1] = (unsigned long long *)(d_planes + 8 * n_words);
+        A.ids = d_ids; A.id_off = d_id_off; A.table_mask = slots - 1;
+        const char *hm = getenv("MCALLER_MOTIF_HASH_MASK");
+        A.hash_mask = hm && *hm ? strtoull(hm, nullptr, 16) : ~0ull;      // (tests: long probe chains)
+        A.text = d_text; A.n_bytes = n_bytes; A.off2 = s2 ? off2 : n_bytes; A.head = d_head;
+        A.tables = d_tables; A.parents = d_parents; A.n_tables = (int32_t)tables.size();
+        A.has_control = s2 ? 1 : 0; A.keep_all = P->keep_all ? 1 : 0;
+        A.stretch = stretch; A.G = G; A.n_entries = n_entries;
+        A.nC = A.nG + n_entries; A.nM = A.nG + 2 * (size_t)n_entries;
+        A.keep = A.selected + n_entries;
+        A.min_sites = P->min_sites; A.min_fraction = P->min_fraction;
+        const auto t_kernels = std::chrono::steady_clock::now();
+        const int rc = ms_run(c, pool, A, d_head, *P, tables, iupac, max_motifs, scratch, out, n_out, n_rows, status);
+        S.ms_kernels = ms_since(t_kernels) - S.ms_d2h;                     // a declined call too: what ran until it declined
+        if (rc == 0 && *status == 0 && max_motifs > 0) c->motif.left_starts.assign(gstart.begin(), gstart.begin() + NC);
+        return rc;
+    });
 }
 
 bool ms_bad_args(const mc_ctx *c, const mc_ref_view *ref, const mc_motif_params *P, const char **out, int64_t *n_out, int64_t *n_rows,
@@ -769,55 +747,40 @@ extern "C" int mc_motif_report(mc_ctx *c, const mc_ref_view *ref, const mc_text_
         if (int rc = text_source("mc_motif_report", control, &s2)) return rc;
     const int rc = ms_call(c, ref, s1, control ? &s2 : nullptr, params, iupac != 0, max_motifs, out, n_out, n_rows, status);
     // the decline, if any, in the stats of --iupac and --iterative too (an iterative call fills both)
-    const mc_motif_stats &S = c->motif_stats;
+    const mc_motif_stats &S = c->motif.stats;
     if (iupac || max_motifs > 0) {
-        mc_motif_iupac_stats &I = c->motif_iupac_stats;
+        mc_motif_iupac_stats &I = c->motif.iupac_stats;
         I.decline_line = S.decline_line; I.decline_reason = S.decline_reason; I.decline_file = S.decline_file;
     }
     if (max_motifs > 0) {
-        mc_motif_iter_stats &I = c->motif_iter_stats;
+        mc_motif_iter_stats &I = c->motif.iter_stats;
         I.decline_line = S.decline_line; I.decline_reason = S.decline_reason; I.decline_file = S.decline_file;
     }
     return rc;
 }
 
 extern "C" int mc_motif_report_last_stats(mc_ctx *c, mc_motif_stats *out) {
-    if (!c || !out) { mc_set_error("mc_motif_report_last_stats: bad arguments"); return -12; }
-    *out = c->motif_stats;
-    return 0;
+    return stats_out("mc_motif_report_last_stats", c, out, &mc_ctx::motif, &MotifPipe::stats);
 }
 
 extern "C" int mc_motif_report_iupac_last_stats(mc_ctx *c, mc_motif_iupac_stats *out) {
-    if (!c || !out) { mc_set_error("mc_motif_report_iupac_last_stats: bad arguments"); return -12; }
-    *out = c->motif_iupac_stats;
-    return 0;
+    return stats_out("mc_motif_report_iupac_last_stats", c, out, &mc_ctx::motif, &MotifPipe::iupac_stats);
 }
 
 extern "C" int mc_motif_report_iter_last_stats(mc_ctx *c, mc_motif_iter_stats *out) {
-    if (!c || !out) { mc_set_error("mc_motif_report_iter_last_stats: bad arguments"); return -12; }
-    *out = c->motif_iter_stats;
-    return 0;
+    return stats_out("mc_motif_report_iter_last_stats", c, out, &mc_ctx::motif, &MotifPipe::iter_stats);
 }
 
 extern "C" int mc_motif_report_iter_left(mc_ctx *c, const uint64_t **plus, const uint64_t **minus, int64_t *n_words, const int64_t **contig_start,
                                          int32_t *n_contigs) {
     if (!c || !plus || !minus || !n_words || !contig_start || !n_contigs) { mc_set_error("mc_motif_report_iter_left: bad arguments"); return -12; }
-    const bool have = c->motif_left_words > 0 && c->motif_left.p;
-    *plus = have ? c->motif_left.get<uint64_t>() : nullptr;
-    *minus = have ? c->motif_left.get<uint64_t>() + c->motif_left_words : nullptr;
-    *n_words = have ? c->motif_left_words : 0;
-    *contig_start = have && !c->motif_left_starts.empty() ? c->motif_left_starts.data() : nullptr;
-    *n_contigs = have ? (int32_t)c->motif_left_starts.size() : 0;
+    const bool have = c->motif.left_words > 0 && c->motif.left.get<uint64_t>();
+    *plus = have ? c->motif.left.get<uint64_t>() : nullptr;
+    *minus = have ? c->motif.left.get<uint64_t>() + c->motif.left_words : nullptr;
+    *n_words = have ? c->motif.left_words : 0;
+    *contig_start = have && !c->motif.left_starts.empty() ? c->motif.left_starts.data() : nullptr;
+    *n_contigs = have ? (int32_t)c->motif.left_starts.size() : 0;
     return 0;
 }
 
-extern "C" int mc_motif_report_release(mc_ctx *c) {
-    if (!c) return 0;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipStreamSynchronize(c->up_stream));
-    c->motif_out.reset(); c->motif_out_cap = 0;
-    c->motif_left.reset(); c->motif_left_cap = 0; c->motif_left_words = 0;
-    c->text_stages.release();
-    return 0;
-}
+extern "C" int mc_motif_report_release(mc_ctx *c) { return release_pipeline(c, &mc_ctx::motif); }

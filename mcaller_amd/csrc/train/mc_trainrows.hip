@@ -283,7 +283,7 @@ const char *tr_reason_text(int reason) {
 }
 
 int tr_decline(mc_ctx *c, int32_t *status, int reason, long long line) {
-    return decline(c->tr_stats, status, "reader", tr_reason_text(reason), reason, line);
+    return decline(c->tr.stats, status, "reader", tr_reason_text(reason), reason, line);
 }
 
 int tr_decline_head(mc_ctx *c, int32_t *status, const TrHead &h) {
@@ -292,7 +292,7 @@ int tr_decline_head(mc_ctx *c, int32_t *status, const TrHead &h) {
 
 // The text is on the device (d_text[0, n), padded; copies enqueued on c->up_stream): everything behind that
 int tr_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *pairs, int32_t n_pairs, mc_train_rows_view *V, int32_t *status) {
-    mc_train_rows_stats &S = c->tr_stats;
+    mc_train_rows_stats &S = c->tr.stats;
     hipStream_t st = c->stream;
     HIP_TRY(hipStreamSynchronize(c->up_stream));
     const auto t_kernels = std::chrono::steady_clock::now();
@@ -369,7 +369,7 @@ int tr_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *pai
     S.ms_kernels = ms_since(t_kernels);
     const auto t_d2h = std::chrono::steady_clock::now();
     // the labels' bytes: where the row that claimed the slot has them
-    c->tr_labels.clear();
+    c->tr.labels.clear();
     V->label_off[0] = 0;
     for (int i = 0; i < n_labels; ++i) {
         const int64_t r = (int64_t)(h.table[slots[i]] & 0xffffffffull) - 1;
@@ -377,62 +377,47 @@ int tr_run(mc_ctx *c, Pool &pool, const char *d_text, int64_t n, const char *pai
         long long ls = 0;
         HIP_TRY(hipMemcpy(&row, A.row + r, sizeof row, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(&ls, line_start + r, 8, hipMemcpyDeviceToHost));
-        const size_t at = c->tr_labels.size(), ln = row.z >> 16;
-        c->tr_labels.resize(at + ln);
-        if (ln) HIP_TRY(hipMemcpy(&c->tr_labels[at], d_text + ls + (row.z & 0xffffu), ln, hipMemcpyDeviceToHost));
-        V->label_off[i + 1] = (int32_t)c->tr_labels.size();
+        const size_t at = c->tr.labels.size(), ln = row.z >> 16;
+        c->tr.labels.resize(at + ln);
+        if (ln) HIP_TRY(hipMemcpy(&c->tr.labels[at], d_text + ls + (row.z & 0xffffu), ln, hipMemcpyDeviceToHost));
+        V->label_off[i + 1] = (int32_t)c->tr.labels.size();
         V->n_rows[i] = first_off[i + 1] - first_off[i];
         V->first_line[i] = (int64_t)h.first[slots[i]];
     }
     if (n_kept > 0) {
         const size_t xb = (size_t)n_kept * (size_t)A.nf * 8, cb = (size_t)n_kept * (size_t)A.ctx_w;
-        if (int rc = grow(c->tr_X, c->tr_X_cap, xb)) return rc;
-        if (int rc = grow(c->tr_ctx, c->tr_ctx_cap, cb)) return rc;
-        HIP_TRY(hipMemcpyAsync(c->tr_X.p, A.X, xb, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(c->tr_ctx.p, A.ctx, cb, hipMemcpyDeviceToHost, st));
+        if (int rc = c->tr.X.need(xb)) return rc;
+        if (int rc = c->tr.ctx.need(cb)) return rc;
+        HIP_TRY(hipMemcpyAsync(c->tr.X.get<double>(), A.X, xb, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(c->tr.ctx.get<char>(), A.ctx, cb, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        V->X = c->tr_X.get<double>();
-        V->contexts = c->tr_ctx.get<char>();
+        V->X = c->tr.X.get<double>();
+        V->contexts = c->tr.ctx.get<char>();
     }
     S.ms_d2h = ms_since(t_d2h);
     V->n_labels = n_labels;
     V->n_features = n_kept > 0 ? A.nf : 0;
     V->ctx_width = n_kept > 0 ? A.ctx_w : 0;
     V->n_rows_total = n_kept;
-    V->label_bytes = c->tr_labels.data();
-    return 0;
-}
-
-// what a call begins with -> 0: go on; 1: done (declined, *status set); < 0: an error
-int tr_begin(mc_ctx *c, const char *pairs, int32_t n_pairs, mc_train_rows_view *V, int32_t *status, int64_t n) {
-    c->tr_stats = mc_train_rows_stats();
-    c->tr_stats.decline_line = -1;
-    c->tr_stats.n_bytes = n;
-    *V = mc_train_rows_view();
-    *status = 0;
-    if (n_pairs < 0 || n_pairs > MC_TRAINROWS_MAX_PAIRS || (n_pairs > 0 && !pairs)) {
-        mc_set_error("mc_train_rows: 0 to %d centre pairs", MC_TRAINROWS_MAX_PAIRS);
-        return -12;
-    }
-    if (!device_fits((size_t)n + 4096)) { (void)tr_decline(c, status, MC_TRAINROWS_DECLINE_MEMORY, -1); return 1; }
+    V->label_bytes = c->tr.labels.data();
     return 0;
 }
 
 // what the entry point runs: the text of `src` onto the device and through tr_run
 int tr_call(mc_ctx *c, const mc_text_source &src, const char *pairs, int32_t n_pairs, mc_train_rows_view *out, int32_t *status) {
-    HIP_TRY(hipSetDevice(c->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    if (int rc = tr_begin(c, pairs, n_pairs, out, status, src.n_bytes)) return rc < 0 ? rc : 0;
-    Pool pool("training rows");
-    TextFeed feed(c, (size_t)64 << 20);
-    char *d_text = nullptr;
-    if (int rc = feed.put(pool, src, &d_text)) return rc;
-    feed.times(c->tr_stats, t0);
-    const int rc = tr_run(c, pool, d_text, src.n_bytes, pairs, n_pairs, out, status);
-    (void)hipStreamSynchronize(c->stream);                   // (an early return: nothing of the pool is in use when it goes)
-    if (rc != 0 || *status != 0) *out = mc_train_rows_view();
-    c->tr_stats.ms_total = ms_since(t0);
-    return rc;
+    mc_train_rows_stats &S = c->tr.stats;
+    return pipeline_call(c, S, status, "training rows", (size_t)64 << 20, [&] { *out = mc_train_rows_view(); }, [&](Call &K) -> int {
+        S.n_bytes = src.n_bytes;
+        if (n_pairs < 0 || n_pairs > MC_TRAINROWS_MAX_PAIRS || (n_pairs > 0 && !pairs)) {
+            mc_set_error("mc_train_rows: 0 to %d centre pairs", MC_TRAINROWS_MAX_PAIRS);
+            return -12;
+        }
+        if (!device_fits((size_t)src.n_bytes + 4096)) return tr_decline(c, status, MC_TRAINROWS_DECLINE_MEMORY, -1);
+        char *d_text = nullptr;
+        if (int rc = K.feed.put(K.pool, src, &d_text)) return rc;
+        K.feed.times(S, K.t0);
+        return tr_run(c, K.pool, d_text, src.n_bytes, pairs, n_pairs, out, status);
+    });
 }
 
 }  // namespace
@@ -449,22 +434,10 @@ extern "C" int mc_train_rows(mc_ctx *c, const mc_text_source *src, const char *p
 }
 
 extern "C" int mc_train_rows_last_stats(mc_ctx *c, mc_train_rows_stats *out) {
-    if (!c || !out) { mc_set_error("mc_train_rows_last_stats: bad arguments"); return -12; }
-    *out = c->tr_stats;
-    return 0;
+    return stats_out("mc_train_rows_last_stats", c, out, &mc_ctx::tr, &TrainPipe::stats);
 }
 
-extern "C" int mc_train_rows_release(mc_ctx *c) {
-    if (!c) return 0;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipStreamSynchronize(c->up_stream));
-    c->tr_X.reset(); c->tr_X_cap = 0;
-    c->tr_ctx.reset(); c->tr_ctx_cap = 0;
-    std::string().swap(c->tr_labels);
-    c->text_stages.release();
-    return 0;
-}
+extern "C" int mc_train_rows_release(mc_ctx *c) { return release_pipeline(c, &mc_ctx::tr); }
 
 extern "C" int mc_parse_doubles_device(mc_ctx *c, const char *text, int64_t n_bytes, const int64_t *off, const int32_t *len, int64_t n,
                                        double *out, uint8_t *ok) {

@@ -54,6 +54,23 @@ def _source(path=None, text=None):
     return C.byref(s), (s, keep)
 
 
+def _blob(ptr, n):
+    """The n bytes a call handed out at `ptr`, as the caller's own copy (no bytes: b'', whatever the pointer)."""
+    return C.string_at(ptr, n) if n else b''
+
+
+def _first_row_columns(path=None, text=None):
+    """c, the value columns of a .diffs file (`path`) or text (`text`, bytes), from its first row: the values of a row less the
+    read quality (0: the row has not 7 or 8 fields)."""
+    if path is not None:
+        with open(path, 'rb') as fh:
+            first = fh.readline()
+    else:
+        first = bytes(text).split(b'\n', 1)[0]
+    fields = first.split(b'\t')
+    return fields[4].count(b',') if len(fields) in (7, 8) else 0
+
+
 class Device(object):
     def __init__(self, index=None):
         import threading
@@ -751,8 +768,7 @@ class Device(object):
         del keep, keep_pos, keep_ref
         if status.value != 0:
             return None, 0, last_error()
-        blob = C.string_at(out.value, n_out.value) if n_out.value else b''
-        return blob, int(n_sites.value), None
+        return _blob(out.value, n_out.value), int(n_sites.value), None
 
     @_serialized
     def bed_last_stats(self):
@@ -784,7 +800,7 @@ class Device(object):
         check(lib().mc_rows_merge_text(self._ctx, text, len(text), C.byref(out), C.byref(n_out), C.byref(status)))
         if status.value != 0:
             return None, last_error()
-        return (C.string_at(out.value, n_out.value) if n_out.value else b''), None
+        return _blob(out.value, n_out.value), None
 
     @_serialized
     def merge_rows_last_stats(self):
@@ -921,7 +937,7 @@ class Device(object):
         if total:                                                 # (one copy each, out of the context's pinned memory)
             C.memmove(X.ctypes.data, view.X, X.nbytes)
             C.memmove(ctx.ctypes.data, view.contexts, ctx.nbytes)
-        names = C.string_at(view.label_bytes, view.label_off[view.n_labels]) if view.n_labels else b''
+        names = _blob(view.label_bytes, view.label_off[view.n_labels])
         labels, sig, grp, at = [], {}, {}, 0
         for i in range(view.n_labels):
             label = names[view.label_off[i]:view.label_off[i + 1]].decode('ascii')
@@ -961,7 +977,7 @@ class Device(object):
         del keep, keep_pos
         if status.value != 0:
             return None, last_error()
-        return (C.string_at(out.value, n_out.value) if n_out.value else b''), None
+        return _blob(out.value, n_out.value), None
 
     @_serialized
     def eval_calls_last_stats(self):
@@ -1031,7 +1047,7 @@ class Device(object):
             self._unaligned = int(n_unaligned.value)
         if status.value != 0:
             return None, 0, last_error()
-        return (C.string_at(out.value, n_out.value) if n_out.value else b''), int(n_sites.value), None
+        return _blob(out.value, n_out.value), int(n_sites.value), None
 
     def bed_compare_last_unaligned(self):
         """bed1's lines without an image in the last bed_compare through an alignment (None: it declined, or had none)."""
@@ -1052,13 +1068,7 @@ class Device(object):
         if int(depth) < 2:
             raise ValueError('currents_compare: a depth of at least 2')
         # c and log10(c) from the native text's first row: the constant is NumPy's, the bits the host statement adds
-        if path1 is not None:
-            with open(path1, 'rb') as fh:
-                first = fh.readline()
-        else:
-            first = bytes(text1).split(b'\n', 1)[0]
-        fields = first.split(b'\t')
-        c = fields[4].count(b',') if len(fields) in (7, 8) else 0
+        c = _first_row_columns(path1, text1)
         opt = _lib.CurOptions(int(depth), int(bool(fdr)), -1 if by is None else tests.index(by), min(c, 65535), float(threshold),
                               float(np.log10(c)) if c >= 1 else 0.0)
         res, status = _lib.CurResult(), C.c_int32()
@@ -1067,8 +1077,7 @@ class Device(object):
         del keep1, keep2
         if status.value != 0:
             return None, None, 0, 0, last_error()
-        return ((C.string_at(res.out, res.n_out) if res.n_out else b''), (C.string_at(res.bed, res.n_bed) if res.n_bed else b''),
-                int(res.n_sites), int(res.n_sig), None)
+        return _blob(res.out, res.n_out), _blob(res.bed, res.n_bed), int(res.n_sites), int(res.n_sig), None
 
     @_serialized
     def currents_compare_last_stats(self):
@@ -1092,14 +1101,7 @@ class Device(object):
             raise ValueError('sites_cluster: metric is correlation or euclidean')
         if int(depth) < 2 or not 2 <= int(max_depth) <= _lib.CLU_MAX_DEPTH:
             raise ValueError('sites_cluster: a depth of at least 2 and a max_depth of 2 to %d' % _lib.CLU_MAX_DEPTH)
-        # c from the first row: the values of a row less the read quality
-        if path is not None:
-            with open(path, 'rb') as fh:
-                first = fh.readline()
-        else:
-            first = bytes(text).split(b'\n', 1)[0]
-        fields = first.split(b'\t')
-        c = fields[4].count(b',') if len(fields) in (7, 8) else 0
+        c = _first_row_columns(path, text)
         opt = _lib.CluOptions(int(depth), int(max_depth), _lib.CLU_METRIC[metric], int(bool(mixed)), min(c, 65535), 0, float(min_minor),
                               float(min_gap))
         res, status = _lib.CluResult(), C.c_int32()
@@ -1108,8 +1110,7 @@ class Device(object):
         del keep
         if status.value != 0:
             return None, None, 0, 0, last_error()
-        return ((C.string_at(res.out, res.n_out) if res.n_out else b''), (C.string_at(res.bed, res.n_bed) if res.n_bed else b''),
-                int(res.n_sites), int(res.n_mixed), None)
+        return _blob(res.out, res.n_out), _blob(res.bed, res.n_bed), int(res.n_sites), int(res.n_mixed), None
 
     @_serialized
     def sites_cluster_last_stats(self):
@@ -1204,7 +1205,7 @@ class Device(object):
         check(lib().mc_motif_report(self._ctx, C.byref(v), bed, control, C.byref(P), int(bool(iupac)), int(max_motifs) if iterative else 0,
                                     C.byref(out), C.byref(n_out), C.byref(n_rows), C.byref(status)))
         del keep, keep_control
-        blob = C.string_at(out.value, n_out.value) if status.value == 0 and n_out.value else b''
+        blob = _blob(out.value, n_out.value) if status.value == 0 else b''
         if iterative:
             if status.value != 0:
                 return None, 0, last_error(), None
