@@ -1258,6 +1258,62 @@ int mc_sites_cluster_release(mc_ctx *ctx);
 int mc_site_cluster_host(const double *values, int64_t n, int64_t c, int32_t metric, int32_t *labels_out, double out3[3]);
 double mc_site_ari_host(int64_t n1, int64_t n2, int64_t m1, int64_t m2);
 
+/* ===== methylation linkage between sites along reads (mcaller_amd/phase_reads.py; csrc/mc_pairphase.h,
+ * csrc/compare/mc_readphase.inc) =====
+ * mc_reads_phase: the text is the mCaller rows (.diffs, 7 or 8 fields) of one sample.  A site (chrom, pos, strand) is kept with at
+ * least opt->depth rows; for every pair of kept sites of one chrom and strand at most opt->max_dist apart, the reads (chrom, read,
+ * strand) with a row at both are counted by (A methylated, B methylated).  res->out: one row per pair with at least opt->min_reads
+ * shared reads and every margin at least opt->min_margin -- the counts, phi, -log10 of Fisher's p and, with opt->fdr, of its
+ * Benjamini-Hochberg q -- ordered by A's first row, then B's pos; res->reads: one row per read with a row at a kept site, in the
+ * order of the reads' first rows; res->bed (opt->bed): the kept sites that are A or B of a written pair whose printed value (fdr:
+ * the q-value) is at least opt->threshold, as BED lines.  opt->n_columns: the values of a row less the read quality.  The bytes are
+ * those of phase_reads.phase_reads, or the call declines -- *status = 1, mc_last_error says why (mc_reads_phase_last_stats: line and
+ * reason), nothing is handed out and the caller runs the host statement, which words the errors.  Declines: MC_CMP_DECLINE_HIGH_BYTE,
+ * _CONTROL, _LONG_LINE, _ROWS, _MEMORY (the text, its tables, the S W pair counters of 8 bytes and their columns, the sort buffers),
+ * _TABLE (the site table, the read table or the strands'), _NUMBER, the three _CUR_* (no value column is _CUR_VALUES at line 0),
+ * _DUPLICATE (a read with two rows at one pos: the later line), _DEPTH (a kept site of more than MC_PHASE_MAX_DEPTH rows: the four
+ * counts of a pair are 16-bit fields of one word), _FAR_TAIL, _FISHER_SELECT, _TIE, _PRINT (Fisher's value of a written pair: site
+ * A's first line; a q-value's tie names no line) and MC_CMP_DECLINE_READ_ROWS.  A file without a kept site hands out nothing.
+ * The three outputs point at pinned memory owned by the context: valid until the next mc_reads_phase call on it or
+ * mc_reads_phase_release.  Test knobs as for mc_currents_compare: MCALLER_CMP_HASH_MASK and MCALLER_CMP_TABLE_SLOTS hold for the read
+ * table too, MCALLER_CMP_DEVICE_BYTES for the counters and the sort buffers too.
+ * mc_pair_phi: phi of one table by the host build of csrc/mc_pairphase.h (needs no GPU) and np.round(phi, 3) -> 0; 1: a margin of
+ * zero, nothing is written; -12: bad arguments (a count below 0 or above 65535). */
+#define MC_CMP_DECLINE_READ_ROWS     31  /* a read (chrom, read, strand) with more than MC_PHASE_GROUP_ROWS rows              */
+#define MC_PHASE_WAVE_ROWS   64      /* up to here a wave orders a read's rows (kr_order)                    */
+#define MC_PHASE_GROUP_ROWS  2048    /* up to here a workgroup does, in LDS; beyond, the file is declined    */
+#define MC_PHASE_MAX_DEPTH   65535   /* rows of a kept site                                                  */
+typedef struct mc_phase_options {
+    int32_t depth, max_dist, min_reads, min_margin, fdr, bed, n_columns, pad;
+    double threshold;
+} mc_phase_options;
+typedef struct mc_phase_result {
+    const char *out, *reads, *bed;
+    int64_t n_out, n_reads_bytes, n_bed, n_pairs, n_reads, n_linked;
+} mc_phase_result;
+typedef struct mc_phase_stats {
+    int64_t n_bytes, n_lines, n_keys;
+    int64_t n_sites;               /* kept sites                                                  */
+    int64_t n_read_keys;           /* reads (chrom, read, strand) of the file                     */
+    int64_t n_reads_wave, n_reads_group;   /* reads whose rows a wave ordered (<= 64 rows), a workgroup ordered */
+    int64_t window;                /* W: the most kept sites behind a site within max_dist, at least 1 */
+    int64_t n_counters;            /* n_sites * window                                            */
+    int64_t n_instances;           /* pair instances counted: atomics of the hot path             */
+    int64_t n_pairs, n_reads, n_linked;    /* rows written, rows of the reads output, lines of the bed */
+    int64_t n_out_bytes, n_reads_bytes, n_bed_bytes, table_slots, read_table_slots;
+    int64_t decline_line;          /* 0-based line the decline names, -1: none                    */
+    int32_t decline_reason;        /* 0: not declined; MC_CMP_DECLINE_*                           */
+    int32_t longest_probe, longest_read_probe;   /* slots the longest probe of the site table, the read table looked at */
+    int32_t deepest_site;          /* rows of the deepest kept site                               */
+    int32_t longest_read;          /* rows of the longest read                                    */
+    int32_t n_columns;
+    double ms_read, ms_h2d, ms_kernels, ms_d2h, ms_total;
+} mc_phase_stats;
+int mc_reads_phase(mc_ctx *ctx, const mc_text_source *source, const mc_phase_options *opt, mc_phase_result *res, int32_t *status);
+int mc_reads_phase_last_stats(mc_ctx *ctx, mc_phase_stats *out);
+int mc_reads_phase_release(mc_ctx *ctx);
+int mc_pair_phi(int64_t n11, int64_t n10, int64_t n01, int64_t n00, double *phi, double *rounded);
+
 /* ===== methylated motifs found de novo from called sites on the GPU (mcaller_amd/find_motifs.py; csrc/motifs/mc_motifscan.hip) =====
  * mc_motif_report, with iupac = 0 and max_motifs = 0.  For every shape (a string of X and '.', first and last X, at most MC_MOTIF_MAX_WIDTH wide, 2 to 8 X), every X of it as the called
  * letter and every assignment of A, C, G, T to the X: the candidates of the reference (ref: contig_len, seq_off and the upper-cased

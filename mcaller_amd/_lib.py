@@ -57,6 +57,9 @@ CurStats = _S['mc_cur_stats']
 CluOptions = _S['mc_clu_options']
 CluResult = _S['mc_clu_result']
 CluStats = _S['mc_clu_stats']
+PhaseOptions = _S['mc_phase_options']
+PhaseResult = _S['mc_phase_result']
+PhaseStats = _S['mc_phase_stats']
 ContigTable = _S['mc_contig_table']
 XmfaMapView = _S['mc_xmfa_map_view']
 XmfaStats = _S['mc_xmfa_stats']
@@ -77,6 +80,7 @@ TW_STATUS = {'bad_n': 1, 'zero_var': 2, 'far_tail': 4, 'no_convergence': 8, 'all
              'deep': 128}                                                                        # TW_* (csrc/mc_twosample.h)
 CLU_METRIC = {'correlation': _K['MC_CLU_CORRELATION'], 'euclidean': _K['MC_CLU_EUCLIDEAN']}
 CLU_WAVE_ROWS, CLU_LDS_ROWS, CLU_MAX_DEPTH = _K['MC_CLU_WAVE_ROWS'], _K['MC_CLU_LDS_ROWS'], _K['MC_CLU_MAX_DEPTH']
+PHASE_WAVE_ROWS, PHASE_GROUP_ROWS, PHASE_MAX_DEPTH = _K['MC_PHASE_WAVE_ROWS'], _K['MC_PHASE_GROUP_ROWS'], _K['MC_PHASE_MAX_DEPTH']
 CC_STATUS = {'nan': 1, 'range': 2, 'tie': 4, 'unprintable': 8}                                 # CC_* (csrc/mc_curcombine.h)
 TW_NAMES = ('U', 'z_mwu', 'z_rs', 't', 'D', 'nlp_mwu', 'nlp_rs', 'nlp_t', 'nlp_ks')
 
@@ -726,6 +730,17 @@ def site_cluster(values, metric='correlation'):
     if rc != 0:
         raise ValueError('mc_site_cluster_host: %d' % rc)
     return labels, float(out[0]), float(out[1])
+
+
+def pair_phi(n11, n10, n01, n00):
+    """phase_reads' phi of one 2 x 2 table by mc_pairphase.h's host build -> None when a margin is zero, else (phi, np.round(phi, 3))."""
+    phi, rounded = C.c_double(), C.c_double()
+    rc = lib().mc_pair_phi(int(n11), int(n10), int(n01), int(n00), C.byref(phi), C.byref(rounded))
+    if rc == 1:
+        return None
+    if rc != 0:
+        raise ValueError('mc_pair_phi: %d' % rc)
+    return phi.value, rounded.value
 
 
 def site_ari(n1, n2, m1, m2):

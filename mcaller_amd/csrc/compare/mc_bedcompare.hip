@@ -8,7 +8,8 @@
 // header comment lists its declines (MC_CMP_DECLINE_XMFA_*, MC_CMP_DECLINE_LIFT_START) and its kernels' resources.
 // The lines of .diffs files grouped by site are mc_sitegroup.inc (kn_parse .. kn_place, SgRun); the two pipelines included behind it
 // start from it: a native sample against a control, site by site and without a model (compare_currents), is mc_curcompare.inc (the
-// other kn_*); the rows of one sample's sites split in two by their currents (cluster_sites) are mc_sitecluster.inc, included last (kl_*).
+// other kn_*); the rows of one sample's sites split in two by their currents (cluster_sites) are mc_sitecluster.inc (kl_*); the linkage of
+// one sample's sites along its reads (phase_reads) is mc_readphase.inc, included last (kr_*).
 // Fisher's exact test on the sites' counts and the Benjamini-Hochberg q-values of every -log10 p column (compare_genomes --fisher
 // --fdr; mc_bed_compare_with's options) are mc_cmpfdr.inc, included behind it: its kernels run between kc_finish and kc_size and hand
 // kc_size / kc_write the columns behind nlp_ks.  Their declines:
@@ -565,6 +566,7 @@ int launch_ranks(hipStream_t st, const RankArgs &R) {
 #include "mc_sitegroup.inc"
 #include "mc_curcompare.inc"
 #include "mc_sitecluster.inc"
+#include "mc_readphase.inc"
 
 // The texts are on the device (d_text[0, n): bed1's, a newline if it lacked its last, bed2's from off2 on; padded): everything behind that
 // (lift: the device side of a lifted comparison, nullptr: keys are matched as they stand)
@@ -838,6 +840,24 @@ extern "C" int mc_sites_cluster_last_stats(mc_ctx *c, mc_clu_stats *out) {
 }
 
 extern "C" int mc_sites_cluster_release(mc_ctx *c) { return release_pipeline(c, &mc_ctx::clusters); }
+
+// methylation linkage between a sample's sites along its reads (mc_readphase.inc)
+extern "C" int mc_reads_phase(mc_ctx *c, const mc_text_source *source, const mc_phase_options *opt, mc_phase_result *res, int32_t *status) {
+    if (!c || !opt || !res || !status || opt->depth < 1 || opt->max_dist < 1 || opt->min_reads < 1 || opt->min_margin < 1 || opt->n_columns < 0 ||
+        opt->n_columns > 65535 || !(opt->threshold == opt->threshold)) {
+        mc_set_error("mc_reads_phase: bad arguments");
+        return -12;
+    }
+    mc_text_source src = {};
+    if (int rc = text_source("mc_reads_phase", source, &src)) return rc;
+    return ph_call(c, src, *opt, res, status);
+}
+
+extern "C" int mc_reads_phase_last_stats(mc_ctx *c, mc_phase_stats *out) {
+    return stats_out("mc_reads_phase_last_stats", c, out, &mc_ctx::phase, &PhasePipe::stats);
+}
+
+extern "C" int mc_reads_phase_release(mc_ctx *c) { return release_pipeline(c, &mc_ctx::phase); }
 
 // the device build of mc_twosample.h on k sites: the rank kernels and kc_finish as the file pipeline runs them
 extern "C" int mc_twosample_device(mc_ctx *c, const double *x, const int64_t *x_off, const double *y, const int64_t *y_off, int64_t k,

@@ -282,6 +282,11 @@ struct CluPipe {                       // the rows and the BED lines of a sample
     mc_clu_stats stats = {};
     void release() { out.reset(); bed.reset(); }
 };
+struct PhasePipe {                     // the pair rows, the read rows and the BED lines of a sample's linked sites (compare/mc_readphase.inc)
+    Grown out, reads, bed;
+    mc_phase_stats stats = {};
+    void release() { out.reset(); reads.reset(); bed.reset(); }
+};
 // The coordinate map of an XMFA alignment (compare/mc_xmfamap.inc): on the device from mc_xmfa_map until the next such call or
 // mc_xmfa_map_release; map[g1] = ordinal << 33 | g2 << 1 | flip, ~0: unmapped.  The view's host copies are pinned, and plain
 // Pinned blocks, not Grown ones: each call allocates them anew at exactly the view's size
@@ -404,6 +409,7 @@ struct mc_ctx {
     CmpPipe cmp;
     CurPipe currents;
     CluPipe clusters;
+    PhasePipe phase;
     XmfaPipe xmfa;
     MotifPipe motif;
     // the figures of the last random-forest fit (mc_forest_fit.hip, through mc_internal_forest_stats)

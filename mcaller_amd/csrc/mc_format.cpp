@@ -17,6 +17,7 @@
 #include "mc_twosample.h"
 #include "mc_curcombine.h"
 #include "mc_linkage.h"
+#include "mc_pairphase.h"
 #include "mc_npsum.h"
 #include "../../include/mcaller_hip.h"
 
@@ -853,6 +854,18 @@ extern "C" int mc_site_cluster_host(const double *values, int64_t n, int64_t c, 
 extern "C" double mc_site_ari_host(int64_t n1, int64_t n2, int64_t m1, int64_t m2) {
     if (n1 < 1 || n2 < 1 || n1 + n2 > LK_MAX_ROWS || m1 < 0 || m2 < 0 || m1 > n1 || m2 > n2) return __builtin_nan("");
     return lk_ari(n1, n2, m1, m2);
+}
+
+// phase_reads' phi of one 2 x 2 table by mc_pairphase.h's host build (include/mcaller_hip.h) -> 0; 1: a margin of zero (nothing is
+// written); -12: bad arguments
+extern "C" int mc_pair_phi(int64_t n11, int64_t n10, int64_t n01, int64_t n00, double *phi, double *rounded) {
+    if (!phi || !rounded || n11 < 0 || n10 < 0 || n01 < 0 || n00 < 0 || n11 > PP_MAX_COUNT || n10 > PP_MAX_COUNT || n01 > PP_MAX_COUNT ||
+        n00 > PP_MAX_COUNT)
+        return -12;
+    if (!pp_written(n11, n10, n01, n00, 0, 1)) return 1;
+    *phi = pp_phi(n11, n10, n01, n00);
+    *rounded = pp_round3(*phi);
+    return 0;
 }
 
 // the attributes of make_bed --gff --vo by mc_npsum.h's host build (include/mcaller_hip.h): p[0, n) the probabilities in row order

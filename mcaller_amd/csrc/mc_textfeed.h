@@ -1,6 +1,6 @@
 // mc_textfeed.h -- what the seven units that take whole text files through the GPU share on the host side (bed/mc_bedsum.hip,
 // train/mc_trainrows.hip, merge/mc_rowmerge.hip, fastq/mc_fastqual.hip, eval/mc_evalcalls.hip, motifs/mc_motifscan.hip and
-// compare/mc_bedcompare.hip, whose .inc files hold four pipelines: the comparison, the alignment map, the currents, the clusters).
+// compare/mc_bedcompare.hip, whose .inc files hold five pipelines: the comparison, the alignment map, the currents, the clusters, the read phasing).
 // Included by those seven units only, hence the unnamed namespace: nothing here is linked across units.
 //
 // What the author of another pipeline writes.  In mc_ctx.h a record `XPipe x` with the Grown blocks its results are handed out in,

@@ -1122,6 +1122,41 @@ class Device(object):
     def sites_cluster_release(self):
         check(lib().mc_sites_cluster_release(self._ctx))
 
+    # ---- methylation linkage between sites along reads (csrc/compare/mc_sitegroup.inc groups the lines, mc_readphase.inc) ----
+    @_serialized
+    def reads_phase(self, path=None, text=None, depth=15, max_dist=1000, min_reads=10, min_margin=2, fdr=False, threshold=None):
+        """The rows of phase_reads for a .diffs file (`path`) or its text (`text`, bytes), made on the GPU -> (blob: bytes, reads:
+        bytes, bed: bytes, n_pairs, n_reads, n_linked, None), or (None, None, None, 0, 0, 0, reason) when the device declines: the
+        caller runs the host statement.  threshold (None: no bed): the kept sites of a written pair whose printed -log10 p (fdr:
+        q) is at least it are the bed's lines."""
+        if (path is None) == (text is None):
+            raise ValueError('reads_phase: a path or a text')
+        if min(int(depth), int(max_dist), int(min_reads), int(min_margin)) < 1:
+            raise ValueError('reads_phase: depth, max_dist, min_reads and min_margin of at least 1')
+        if threshold is not None and float(threshold) != float(threshold):
+            raise ValueError('reads_phase: a threshold that is a number')
+        c = _first_row_columns(path, text)
+        opt = _lib.PhaseOptions(int(depth), min(int(max_dist), 2 ** 31 - 1), min(int(min_reads), 2 ** 31 - 1), min(int(min_margin), 2 ** 31 - 1),
+                                int(bool(fdr)), int(threshold is not None), min(c, 65535), 0, 0.0 if threshold is None else float(threshold))
+        res, status = _lib.PhaseResult(), C.c_int32()
+        src, keep = _source(path, text)
+        check(lib().mc_reads_phase(self._ctx, src, C.byref(opt), C.byref(res), C.byref(status)))
+        del keep
+        if status.value != 0:
+            return None, None, None, 0, 0, 0, last_error()
+        return (_blob(res.out, res.n_out), _blob(res.reads, res.n_reads_bytes), _blob(res.bed, res.n_bed), int(res.n_pairs), int(res.n_reads),
+                int(res.n_linked), None)
+
+    @_serialized
+    def reads_phase_last_stats(self):
+        """Figures of the last reads_phase: bytes, lines, keys, kept sites, reads and who ordered them, the window, the counters, the
+        pair instances, the three outputs, the decline, milliseconds."""
+        return self._last_stats(lib().mc_reads_phase_last_stats, _lib.PhaseStats)
+
+    @_serialized
+    def reads_phase_release(self):
+        check(lib().mc_reads_phase_release(self._ctx))
+
     # ---- the coordinate map of a Mauve alignment (csrc/compare/mc_xmfamap.inc) ----
     @_serialized
     def xmfa_map(self, path=None, text=None, n1=0, seqs=(1, 2), n2=None, view=True):
