@@ -1409,6 +1409,61 @@ int mc_motif_report_iter_left(mc_ctx *ctx, const uint64_t **plus, const uint64_t
                               int32_t *n_contigs);
 int mc_motif_report_release(mc_ctx *ctx);
 
+/* ===== motif methylation per contig or window and every bin's nearest bins (mcaller_amd/motif_profile.py;
+ * csrc/motifs/mc_motifprofile.inc) =====
+ * For 1 .. MC_PROFILE_MAX_MOTIFS motifs (upper-case IUPAC letters, bit j of called[i]: letter j of motif i is a called letter and
+ * holds the base; the rule: csrc/mc_iupac.h) and every bin -- a contig of ref (window 0), or a window of `window` >= 64 bases of
+ * one -- the sites of the motif, those the bed or the control lists (without a control: all) and those the bed lists; one line per
+ * (bin, motif) with a site, as motif_profile.motif_profile writes it.  neighbours 1 .. MC_PROFILE_MAX_NEIGHBOURS (0: none): for
+ * every bin with a defined motif (nCovered >= min_sites) its nearest bins by the mean absolute difference of the fractions over the
+ * motifs both define (at least min_shared), as the definition's second file.  ref, the sources, the ids and the declines
+ * (MC_MOTIF_DECLINE_*; *status = 1, mc_last_error, the stats name file, line and reason) are mc_motif_report's, and so are the test
+ * knobs MCALLER_MOTIF_HASH_MASK, MCALLER_MOTIF_TABLE_SLOTS and MCALLER_MOTIF_DEVICE_BYTES: all the call needs before the texts'
+ * line starts and the two outputs (need_bytes) is counted against free device memory before anything is allocated.  The result's
+ * blocks are pinned memory owned by the context: valid until the next mc_motif_profile call on it or mc_motif_profile_release. */
+#define MC_PROFILE_MAX_MOTIFS 64
+#define MC_PROFILE_MAX_NEIGHBOURS 16
+typedef struct mc_motif_profile_params {
+    int32_t base;                  /* 'A', 'C', 'G' or 'T'                                        */
+    int32_t n_motifs;              /* 1 .. MC_PROFILE_MAX_MOTIFS                                  */
+    const char *letters;           /* the motifs' letters, one motif behind the other ...         */
+    const int64_t *letters_off;    /* ... motif i is letters[letters_off[i], letters_off[i + 1]); n_motifs + 1 entries */
+    const uint32_t *called;        /* n_motifs masks                                              */
+    const char *specs;             /* what a row prints for motif i (its canonical text): specs[spec_off[i], spec_off[i + 1]) */
+    const int64_t *spec_off;
+    int64_t window;                /* 0: a bin is a contig; else >= 64                            */
+    int64_t min_sites;             /* >= 1                                                        */
+    int32_t neighbours;            /* 0: no second file; else 1 .. MC_PROFILE_MAX_NEIGHBOURS      */
+    int32_t min_shared;            /* >= 1                                                        */
+    const char *contig_ids;        /* as in mc_motif_params                                       */
+    const int64_t *contig_id_off;
+} mc_motif_profile_params;
+typedef struct mc_motif_profile_result {
+    const char *out;               /* the profile file                                            */
+    int64_t n_out, n_rows;
+    const char *nn;                /* the neighbours file                                         */
+    int64_t n_nn, n_nn_rows;
+} mc_motif_profile_result;
+typedef struct mc_motif_profile_stats {
+    int64_t n_bytes1, n_bytes2, n_lines1, n_lines2;
+    int64_t n_candidates, n_sites, n_control, n_off_base;     /* as in mc_motif_stats                  */
+    int64_t n_bins, n_rows;        /* bins; lines of the profile file                             */
+    int64_t n_defined;             /* bins with at least one defined motif                        */
+    int64_t n_pairs;               /* ordered pairs of bins that have a distance (0 without neighbours) */
+    int64_t n_nn_rows;             /* lines of the neighbours file                                */
+    int64_t table_slots, need_bytes, n_out_bytes, n_nn_bytes;
+    int64_t nn_lds_bytes;          /* dynamic LDS of a workgroup of the neighbours kernel         */
+    int64_t decline_line;          /* as in mc_motif_stats                                        */
+    int32_t decline_reason, decline_file;
+    double ms_read, ms_h2d, ms_kernels, ms_d2h, ms_total;
+    double ms_counts;              /* of ms_kernels: from the first launch until the profile file's sizes are known */
+    double ms_neighbours;          /* of ms_kernels: the neighbours kernel, waited for            */
+} mc_motif_profile_stats;
+int mc_motif_profile(mc_ctx *ctx, const mc_ref_view *ref, const mc_text_source *bed, const mc_text_source *control_or_null,
+                     const mc_motif_profile_params *params, mc_motif_profile_result *result, int32_t *status);
+int mc_motif_profile_last_stats(mc_ctx *ctx, mc_motif_profile_stats *out);
+int mc_motif_profile_release(mc_ctx *ctx);
+
 /* ===== measurement plumbing: a table as nanopolish-eventalign text (13 columns), written by all host cores =====
  * For file-to-file timing on synthetic workloads (bench.py); seq = the contig's bases (k-mers of columns 3 and 10). */
 int mc_synth_write_tsv(const char *path, const mc_table_view *table, const char *seq, int64_t seq_len, const char *contig,

@@ -67,6 +67,9 @@ MotifParams = _S['mc_motif_params']
 MotifStats = _S['mc_motif_stats']
 MotifIupacStats = _S['mc_motif_iupac_stats']
 MotifIterStats = _S['mc_motif_iter_stats']
+MotifProfileParams = _S['mc_motif_profile_params']
+MotifProfileResult = _S['mc_motif_profile_result']
+MotifProfileStats = _S['mc_motif_profile_stats']
 EvalParams = _S['mc_eval_params']
 EvalStats = _S['mc_eval_stats']
 Params = _S['mc_params']

@@ -315,10 +315,14 @@ struct MotifPipe {                     // the rows of the motif finder (motifs/m
     int64_t left_words = 0;
     std::vector<int64_t> left_starts;
     mc_motif_iter_stats iter_stats = {};
+    // the two files of the motif profile (motifs/mc_motifprofile.inc)
+    Grown profile_out, profile_nn;
+    mc_motif_profile_stats profile_stats = {};
     void release() {
         out.reset(); left.reset();
         left_words = 0;
     }
+    void release_profile() { profile_out.reset(); profile_nn.reset(); }
 };
 
 // The members' order is the order of construction, and its reverse the order of destruction (mc_ctx_destroy: `delete c` behind a

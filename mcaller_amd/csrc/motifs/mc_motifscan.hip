@@ -53,9 +53,13 @@
 //                planes and km_uncount out of every table (ms_key: the one statement of a window's validity and key, shared with
 //                km_count), and the selection runs again: mc_motifiter.inc (C ABI: mc_motif_report's max_motifs, _iter_last_stats,
 //                _iter_left: the methylated candidates no row explains, as two planes in pinned memory)
+//   motif_profile  another question over the same planes -- given motifs counted per contig or window, and every bin's nearest bins:
+//                mc_motifprofile.inc (C ABI: mc_motif_profile, _last_stats, _release); km_pack, km_contigs, km_parse and km_figures
+//                run there as they are, nothing of it runs in a mc_motif_report call
 // No floating-point atomic anywhere; the counts are exact integers whatever the order of arrival.
 #include "../mc_textfeed.h"
 #include "../mc_rowtext.h"
+#include "../mc_iupac.h"
 
 #include <cstdio>
 #include <cstring>
@@ -533,6 +537,7 @@ bool ms_line(MsText &text, const mc_motif_params &P, const std::vector<MsTable> 
 
 #include "mc_motifiupac.inc"
 #include "mc_motifiter.inc"
+#include "mc_motifprofile.inc"
 
 // Everything behind the uploads.  d_text[0, n): the bed's text, a newline if it lacked its last, the control's from off2 on; padded.
 // max_motifs: 0, or --iterative's
@@ -784,3 +789,38 @@ extern "C" int mc_motif_report_iter_left(mc_ctx *c, const uint64_t **plus, const
 }
 
 extern "C" int mc_motif_report_release(mc_ctx *c) { return release_pipeline(c, &mc_ctx::motif); }
+
+extern "C" int mc_motif_profile(mc_ctx *c, const mc_ref_view *ref, const mc_text_source *bed, const mc_text_source *control,
+                                const mc_motif_profile_params *params, mc_motif_profile_result *result, int32_t *status) {
+    if (!c || !ref || !result || !status || mq_bad_params(params) || ref->n_contigs < 0 ||
+        (ref->n_contigs > 0 && (!ref->contig_len || !ref->seq_off || !params->contig_id_off || !params->contig_ids)) || ref->n_seq_bytes < 0 ||
+        (ref->n_seq_bytes > 0 && !ref->seq)) {
+        mc_set_error("mc_motif_profile: bad arguments");
+        return -12;
+    }
+    for (int i = 0; i < ref->n_contigs; ++i)
+        if (ref->contig_len[i] < 0 || ref->seq_off[i] < 0 || ref->seq_off[i] + ref->contig_len[i] > ref->n_seq_bytes ||
+            params->contig_id_off[i + 1] < params->contig_id_off[i] || params->contig_id_off[0] != 0) {
+            mc_set_error("mc_motif_profile: bad arguments");
+            return -12;
+        }
+    mc_text_source s1 = {}, s2 = {};
+    if (int rc = text_source("mc_motif_profile", bed, &s1)) return rc;
+    if (control)
+        if (int rc = text_source("mc_motif_profile", control, &s2)) return rc;
+    return mq_call(c, ref, s1, control ? &s2 : nullptr, params, result, status);
+}
+
+extern "C" int mc_motif_profile_last_stats(mc_ctx *c, mc_motif_profile_stats *out) {
+    return stats_out("mc_motif_profile_last_stats", c, out, &mc_ctx::motif, &MotifPipe::profile_stats);
+}
+
+extern "C" int mc_motif_profile_release(mc_ctx *c) {
+    if (!c) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipStreamSynchronize(c->up_stream));
+    c->motif.release_profile();
+    c->text_stages.release();
+    return 0;
+}

@@ -1289,6 +1289,63 @@ class Device(object):
     def motif_report_release(self):
         check(lib().mc_motif_report_release(self._ctx))
 
+    # ---- motif methylation per bin and the bins' nearest bins (csrc/motifs/mc_motifprofile.inc) ----
+    @_serialized
+    def motif_profile(self, ref, path=None, control_path=None, text=None, control_text=None, base='A', specs=(), window=0, min_sites=5,
+                      neighbours=None, min_shared=2):
+        """The two files of motif_profile for the reference `ref` ({id: upper-cased sequence}), the sites of a make_bed summary (`path`,
+        or its `text`, bytes), optionally a make_bed --control summary, and `specs` (motif_profile.parse_profile_motifs), made on the
+        GPU -> (profile: bytes, n_rows, neighbours: bytes, n_nn_rows, None), or (None, 0, None, 0, reason) when the device declines:
+        the caller runs the host statement.  neighbours None: no second file (b'')."""
+        if (path is None) == (text is None) or (path is None and control_path is not None) or (text is None and control_text is not None):
+            raise ValueError('motif_profile: paths or texts')
+        specs = list(specs)
+        if not 1 <= len(specs) <= 64 or any(len(s.entries) != 1 for s in specs):
+            raise ValueError('motif_profile: 1 to 64 motifs of one entry each')
+        ids = [name.encode('latin-1', 'replace') for name in ref]
+        seqs = [seq.encode('latin-1', 'replace') for seq in ref.values()]
+        lens = np.asarray([len(s) for s in seqs], dtype=np.int64).reshape(-1)
+        seq_off = np.zeros(len(seqs) + 1, dtype=np.int64)
+        seq_off[1:] = np.cumsum(lens, dtype=np.int64)
+        seq = np.frombuffer(b''.join(seqs) + b'\0', dtype=np.uint8)
+
+        def pooled(items):
+            off = np.zeros(len(items) + 1, dtype=np.int64)
+            off[1:] = np.cumsum([len(i) for i in items], dtype=np.int64)
+            return np.frombuffer(b''.join(items) + b'\0', dtype=np.uint8), off
+        id_pool, id_off = pooled(ids)
+        letter_pool, letter_off = pooled([s.entries[0][0].encode('ascii') for s in specs])
+        spec_pool, spec_off = pooled([s.text.encode('ascii') for s in specs])
+        called = np.asarray([sum(1 << (i - 1) for i in s.entries[0][1]) for s in specs], dtype=np.uint32).reshape(-1)
+        v = _lib.RefView()
+        v.n_contigs = len(seqs)
+        v.contig_len, v.seq_off, v.seq = _ptr(lens), _ptr(seq_off), _ptr(seq)
+        v.n_seq_bytes = int(seq_off[-1])
+        P = _lib.MotifProfileParams()
+        P.base, P.n_motifs = ord(base), len(specs)
+        P.letters, P.letters_off, P.called = _ptr(letter_pool), _ptr(letter_off), _ptr(called)
+        P.specs, P.spec_off = _ptr(spec_pool), _ptr(spec_off)
+        P.window, P.min_sites = int(window), int(min_sites)
+        P.neighbours, P.min_shared = (0 if neighbours is None else int(neighbours)), int(min_shared)
+        P.contig_ids, P.contig_id_off = _ptr(id_pool), _ptr(id_off)
+        res, status = _lib.MotifProfileResult(), C.c_int32()
+        (bed, keep), (control, keep_control) = _source(path, text), _source(control_path, control_text)
+        check(lib().mc_motif_profile(self._ctx, C.byref(v), bed, control, C.byref(P), C.byref(res), C.byref(status)))
+        del keep, keep_control
+        if status.value != 0:
+            return None, 0, None, 0, last_error()
+        return _blob(res.out, res.n_out), int(res.n_rows), _blob(res.nn, res.n_nn), int(res.n_nn_rows), None
+
+    @_serialized
+    def motif_profile_last_stats(self):
+        """Figures of the last motif_profile: bytes, lines, candidates and sites, bins, rows, defined bins, pairs, neighbour rows, the
+        outputs' bytes, the decline, milliseconds."""
+        return self._last_stats(lib().mc_motif_profile_last_stats, _lib.MotifProfileStats)
+
+    @_serialized
+    def motif_profile_release(self):
+        check(lib().mc_motif_profile_release(self._ctx))
+
     @_serialized
     def twosample(self, xs, ys):
         """The nine values of a compare_genomes row for every pair of samples by mc_twosample.h's device build, a wave or a
